@@ -7,14 +7,26 @@ all enqueued on HIP streams with the frames already resident in HBM.  After the 
 the clips are closed inside the timed region too: export-id selection + preprocessing +
 VelocityTracker on the device, then (N > 1) one RCCL all-gather of the per-clip result records.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; ranks own disjoint clips, no
    data-path collective -> "weak" scaling; the only exchange is the final result gather.)
+
+A plain run sets up, runs the W warm-up steps, times the K steps + clip close, writes the outputs of that timed run when
+--dump-outputs is given, and prints the line.  Everything else below (value_settled, value_h2d_inclusive and the splits,
+configs, roofline, cpu_baseline) runs only with --full; the --no-* / --cpu-frames / --settle-steps options tune a --full run.
+
+--dump-outputs DIR   after the timed region, what its caller received, as .npy (float32 / float64, < 64 MB in all): the
+                     last step's detections (det_boxes, det_scores, det_classes, det_counts), the per-clip result records
+                     the clip close produced (records: best id, rows, phases, then PH x (t0,t1,y0,y1,rom,type); N > 1: every
+                     rank's, gathered) and their overflow flags, and every DataFrame row of the clips (rows: id, time, x, y, dx,
+                     dy, norm_plate_height, norm_plate_width; a fixed seeded sample of rows_sample_index when they would not
+                     fit).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 Prints ONE JSON line on rank 0.  Which number is which:
   value                 the contract and nothing else: W warm-up steps, then exactly K steps + clip close between two fences,
                         frames resident in HBM (what the task's bench contract defines as `value`).  No other GPU work precedes
                         the W warm-up steps in this process.
+  ms_per_step           the timed region (K steps + clip close) / K, in milliseconds.
   value_settled         (N = 1) the same W + K run repeated after `--settle-steps` detector-only steps: the GPU's clocks have
                         settled; informational.
   value_h2d_inclusive   SURVEY.md 8d's metric, measured with the SAME W and K in the same process: uint8 frames in pinned
@@ -65,6 +77,7 @@ CORPUS_META = os.path.join(ROOT, "tests", "golden", "corpus_meta.json")   # real
 # weight elements / batch, at the 1 byte per element of the full-integer graph
 ALG_ELEMS = {0: (36.84e6, 3.27e6), 2: (115.56e6, 5.44e6)}
 STEADY_STEPS = 1000        # length of the steady-state repeat of the host-fed pass when the contract's K is shorter
+PH_MAX = 512               # phases a clip can hold at all (MAXPH, vbt_amd/csrc/tracker.hip)
 
 
 def alg_bytes_per_frame(arch, batch):
@@ -220,7 +233,16 @@ def main():
                     help="N = 1: detector-only steps run before the REPEAT of the contract run that is reported as value_settled (0 = no repeat); "
                          "`value` itself is never preceded by them")
     ap.add_argument("--seed-offset", type=int, default=0, help="rehearsal: run this rank on the clips another rank would own")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the clock-settled repeat, the H2D-inclusive pass and splits, "
+                         "the roofline block, the other configurations (N > 1: the sharded ones) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run computed (last step's detections, clip results, tracker rows) to DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_roofline = args.no_configs = True
+        args.cpu_frames = 0
+        args.settle_steps = 0
     if args.contract_only:
         args.no_extras = args.no_roofline = True
         args.cold_start = False
@@ -306,12 +328,12 @@ def main():
         run_steps(K, W)
         t_enq = time.perf_counter()
         # clip close inside the timed region: pipeline drain, export-id selection + rep analysis on the device, ONE packed D2H
-        best, rows_n, nph, ovf, ph = pipe.close(cap=PH)
+        best, rows_n, nph, ovf, ph = close_clips(pipe, PH)
         t_close = time.perf_counter()
         # result record per clip: [best_id, n_rows, n_phases, PH x (t0,t1,y0,y1,rom,type)]
         rec = np.zeros((n, 3 + PH * 6), np.float64)
         rec[:, 0], rec[:, 1], rec[:, 2] = best, rows_n, nph
-        rec[:, 3:] = ph.reshape(n, -1)
+        rec[:, 3:] = ph[:, :PH].reshape(n, -1)
         if dist is not None:                                             # the one exchange of the path: RCCL all-gather
             rec_all = gather_records(dist, rec, world, cdev)
         else:
@@ -333,6 +355,8 @@ def main():
         per_rank = [K * n / float(t) for t in tall.tolist()]
         dt = float(tall.max().item())
     overflow = int((ovf != 0).sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe, rec_all, ovf)       # before anything below resets the pipeline
 
     extras = {}
     if world == 1 and args.settle_steps > 0 and not args.contract_only:
@@ -403,6 +427,43 @@ def gather_records(dist, rec, world, cdev):
     return allrec.cpu().numpy().reshape(world, *rec.shape)
 
 
+def close_clips(pipe, cap):
+    """pipe.close(cap), and on a long run where some clip ends with more than `cap` phases, the same clip close with room for
+    all of them: close() has already finished the clips when it finds its buffer too small, so their summary is packed again
+    with PH_MAX phases per clip (phases[:, :cap] are the same either way)."""
+    from vbt_amd._lib import VbtError
+    try:
+        return pipe.close(cap=cap)
+    except VbtError:
+        return pipe.tracker.summary(cap=PH_MAX)
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, pipe, rec_all, ovf):
+    """--dump-outputs: what the timed run handed its caller, read after its closing fence (the pipeline is drained and closed):
+    the last step's detections, the per-clip result records of the clip close, and the DataFrame rows of every clip.  Rows beyond
+    the size budget are replaced by a fixed seeded sample (rows_sample_index says which)."""
+    os.makedirs(out_dir, exist_ok=True)
+    b, s, c, k = pipe.detections()
+    out = {"det_boxes": b.astype(np.float32), "det_scores": s.astype(np.float32), "det_classes": c.astype(np.float32),
+           "det_counts": k.astype(np.float32),
+           "records": rec_all.reshape(-1, rec_all.shape[-1]).astype(np.float64), "overflow": ovf.astype(np.float64)}
+    counts, rows = pipe.rows_all()
+    flat = np.concatenate([rows[i, :counts[i]] for i in range(len(counts))])
+    table = np.stack([flat[f].astype(np.float64) for f in flat.dtype.names], axis=1) if len(flat) else np.zeros((0, len(rows.dtype.names)))
+    budget = DUMP_BYTES - sum(a.nbytes for a in out.values()) - (1 << 20)      # (headroom for the .npy headers and the index)
+    if table.nbytes > budget:
+        keep = budget // (table.shape[1] * 8 + 8)                               # each sampled row and its float64 index
+        idx = np.sort(np.random.default_rng(0).choice(len(table), keep, replace=False))
+        table = table[idx]
+        out["rows_sample_index"] = idx.astype(np.float64)
+    out["rows"] = table
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # measurements beside the contract's timed region (rank 0, N = 1)
 # ----------------------------------------------------------------------------------------------------------------
@@ -438,7 +499,7 @@ def extra_measurements(torch, pipe, frames, frames_np, n, K, W, U, fbytes, strea
         for i in range(steps):
             pipe.step(host[(W + i) % Uh], stream)
         host_fed.enqueue_ms = (time.perf_counter() - t0) * 1e3      # host time spent enqueueing (a copy that blocks the host shows here)
-        best, rows_n, nph, ovf, ph = pipe.close(cap=PH)
+        best, rows_n, nph, ovf, ph = close_clips(pipe, PH)
         host_fed.close_ms = (time.perf_counter() - t0) * 1e3 - host_fed.enqueue_ms
         counts, rows = pipe.rows_all(out=rows_host)
         torch.cuda.synchronize()

@@ -30,7 +30,7 @@ def test_two_rank_line_carries_the_sharded_configs():
     """N > 1: BASELINE config 5 (the 34-clip corpus LPT-sharded over the ranks, one all-gather of the result records) and SURVEY 8e's
     frame-major mode of one long clip (one all-gather of the 504-byte per-frame detection records, rank 0 tracks) are part of the
     line; the frame-major rows equal the single-GPU time-batched run of the same clip."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline", "--full"],
                        env=ENV, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -25,11 +25,12 @@ def test_graph_reproduces_the_converters_op_counts(arch, macs_m, anchors):
     assert f"{one / 1e9:.3f}" != want_ops and 0.997 < one / ops < 0.999
     assert round(g.total_macs() / 1e6, 1) == macs_m
     assert g.num_anchors() == anchors == len(spec.make_anchors(arch))
+    import json
     import os
-    log = os.path.join("/root/reference/models", name)           # (the reference tree is not on the GPU box; this is a CPU-suite check)
-    if os.path.exists(log):
-        line = [ln for ln in open(log, errors="replace").read().replace("\r", "\n").split("\n") if "Estimated count of arithmetic ops" in ln][0]
-        assert f"{want_ops} G  ops" in line and f"{want_macs} G  MACs" in line
+    from conftest import GOLDEN
+    # the converter's own line, as printed in the reference's models/<name> (tests/golden/converter_op_counts.json)
+    line = json.load(open(os.path.join(GOLDEN, "converter_op_counts.json")))[name]
+    assert f"{want_ops} G  ops" in line and f"{want_macs} G  MACs" in line
 
 
 def test_lite0_op_inventory():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Pipeline depth 3 vs 4 with the pinned plan (resident and host-fed, bench.py at 600 steps), and EfficientDet-Lite2 at depths 2 / 3 / 4.
 cd "${GRAFT_REPO_ROOT:-.}"
-for d in 3 4 3 4; do VBT_PIPELINE_DEPTH=$d python3 bench.py --steps 600 --cpu-frames 0 --no-roofline --no-configs --settle-steps 0 2>/dev/null | python3 -c "
+for d in 3 4 3 4; do VBT_PIPELINE_DEPTH=$d python3 bench.py --full --steps 600 --cpu-frames 0 --no-roofline --no-configs --settle-steps 0 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=j['h2d_inclusive']
 print('depth $d', round(j['value']), round(h['frames_per_s']))"; done

@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 export VBT_PLAN_FILE=$PWD/profiles/plan_lite0
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench default done"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err
 echo "bench k20 done"
 session() {   # $1 = output prefix ("" | lite2_), environment selects model and plan
   local PRE=$1
