@@ -184,6 +184,41 @@ int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int3
  * rows_host may be pinned host memory (one DMA) or pageable. */
 int vbt_tracker_rows_all(vbt_tracker* t, int32_t* counts, void* rows_host, int cap, void* stream);
 
+/* Live rep analysis (off unless enabled): per-rep ROM / ACV while the clips are still being tracked.
+ * After every tracker launch one more kernel on the same stream feeds the rows it appended to the log, in emission order, to the
+ * preprocessing of reference plot.py:90-95 and a VelocityTracker (VelocityTracker.py:92-158) per id - for every id that can still win
+ * the export (a live track, or the best dead id: at most 65 per clip).  Guarantee: the phases of such an id equal reference
+ * VelocityTracker(plate_diameter, diff_threshold, min_distance).phases fed the preprocessed rows of the id emitted so far, bit for bit
+ * (the close-time scan and the live path share one per-row step); with flush_view, that list after end_processing() - computed on a
+ * copy, the live state is not touched.  The clip's leader is the id vbt_tracker_finish would export if the clip closed now
+ * (track.py:107-115).  After the last frame, the leader and its flush view are exactly the close's export id and phases.
+ * Capacities are reported, never guessed around: an id whose open phase outgrows path_cap samples or whose list outgrows phase_cap
+ * phases is frozen and flagged, a clip whose row log overflowed is flagged, and a flagged id / clip reports no phases. */
+#define VBT_LIVE_PATH_FULL 1      /* the open phase's bar path outgrew path_cap */
+#define VBT_LIVE_PHASES_FULL 2    /* the phase list outgrew phase_cap */
+#define VBT_LIVE_ROWS_LOST 4      /* the clip's row log overflowed (rows_cap): rows never reached the analysis */
+#define VBT_LIVE_MAX_PATH 65536
+#define VBT_LIVE_MAX_PHASES 512
+typedef struct {
+  int64_t leader_id;              /* the export rule applied to the rows so far (-1: no id has 2 rows yet) */
+  int32_t rows_consumed;          /* rows of the clip's log analysed */
+  int32_t n_phases;               /* phases of the leader (0 when overflow != 0) */
+  int32_t phase_state;            /* the leader's VelocityTracker state: 0 concentric, 1 eccentric, 2 hold */
+  int32_t overflow;               /* VBT_LIVE_* bits of the clip and its leader */
+  uint64_t seq;                   /* bumped whenever the leader or its phase list changes */
+} vbt_live_clip;
+/* Before the first update (or after vbt_tracker_reset), else VBT_ERR_STATE; once per tracker.  path_cap in [2, VBT_LIVE_MAX_PATH],
+ * phase_cap in [1, VBT_LIVE_MAX_PHASES], else VBT_ERR_ARG.  VelocityTracker parameters as in vbt_tracker_finish.  Allocates
+ * n_clips x 65 x (5 path_cap + 6 phase_cap) doubles.  vbt_tracker_reset clears the live state too. */
+int vbt_tracker_live_enable(vbt_tracker* t, int path_cap, int phase_cap, double plate_diameter, double diff_threshold, double min_distance);
+/* Every clip's record and its leader's phases6 [n_clips][cap][6]: one pack launch on `stream` (which must follow the tracker launches
+ * of interest), ONE copy, ONE synchronisation of `stream`.  VBT_ERR_STATE when live analysis is not enabled. */
+int vbt_tracker_live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, int cap, void* stream);
+/* Every analysed id of one clip (the ids that can still win, with at least one row): ids, rows consumed, phases, VBT_LIVE_* flags;
+ * phases6 [cap_tracks][cap_phases][6].  Synchronises the device (tests, clips with several plates). */
+int vbt_tracker_live_tracks(vbt_tracker* t, int clip, int flush_view, int64_t* ids, int32_t* n_rows, int32_t* n_phases, int32_t* flags,
+                            double* phases6, int cap_tracks, int cap_phases, int* n);
+
 /* ------------------------------------------------------------------ pipeline ----------------
  * Replaces the clip loop of the reference (track.py:129-260: `while cap.isOpened()` -> cap.read -> run_odt -> OCSort.update ->
  * row assembly, then the export of track.py:103-126 and analyze_df of plot.py:33-47) as ONE object behind the C ABI: SURVEY.md 8b's
@@ -270,6 +305,13 @@ int vbt_pipeline_rows(vbt_pipeline* p, int clip, int64_t* id, double* cols7, int
 int vbt_pipeline_detections(vbt_pipeline* p, float* boxes, float* scores, float* classes, int32_t* counts, int cap_slots, int* B);
 /* measurement split: `count` tracker steps of all clips on the detections sitting in ring slot `slot` */
 int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot);
+/* Live rep analysis of the pipeline's clips (vbt_tracker_live_enable with the VelocityTracker parameters of vbt_pipeline_params):
+ * before the first step (or after vbt_pipeline_reset), else VBT_ERR_STATE.  The analysis then runs on the tracker's stream right
+ * after every tracker launch, whichever path launched it. */
+int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap);
+/* Drains the tracker steps still held back (vbt_pipeline_drain), then vbt_tracker_live_poll on the tracker stream: waits for the last
+ * tracker launch only, ONE packed copy.  phases6 [n_clips][cap][6] = the leaders' phases. */
+int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap);
 typedef struct {
   int32_t n_slots, n_clips, rows_cap, device, depth, ring, defer, tracker_inline, image_size, frame_count, steps_enqueued, placement_ok;
   int32_t queue_groups_seen;  /* distinct hardware queues the placement probe has seen on this device */

@@ -29,6 +29,12 @@ class Run(ctypes.Structure):
                 ("frame0", ctypes.c_int32), ("frame_step", ctypes.c_int32), ("fps", c_double)]
 
 
+class LiveClip(ctypes.Structure):
+    """vbt_live_clip (include/vbt_hip.h): one clip's live rep analysis record"""
+    _fields_ = [("leader_id", ctypes.c_int64), ("rows_consumed", ctypes.c_int32), ("n_phases", ctypes.c_int32),
+                ("phase_state", ctypes.c_int32), ("overflow", ctypes.c_int32), ("seq", ctypes.c_uint64)]
+
+
 class PipelineParams(ctypes.Structure):
     """vbt_pipeline_params (include/vbt_hip.h)"""
     _fields_ = [("n_slots", ctypes.c_int32), ("n_clips", ctypes.c_int32), ("rows_cap", ctypes.c_int32), ("device", ctypes.c_int32),
@@ -95,6 +101,9 @@ _SIGS = {
     "vbt_gather_frames": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_size_t, c_void_p]),
     "vbt_tracker_summary": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_tracker_rows_all": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vbt_tracker_live_enable": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double]),
+    "vbt_tracker_live_poll": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "vbt_tracker_live_tracks": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int)]),
     "vbt_pipeline_default_params": (None, [ctypes.POINTER(PipelineParams)]),
     "vbt_pipeline_create": (c_int, [c_char_p, ctypes.POINTER(PipelineParams), c_void_p, ctypes.POINTER(c_void_p)]),
     "vbt_pipeline_destroy": (None, [c_void_p]),
@@ -112,6 +121,8 @@ _SIGS = {
     "vbt_pipeline_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_pipeline_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_pipeline_tracker_only_steps": (c_int, [c_void_p, c_int, c_int]),
+    "vbt_pipeline_live_enable": (c_int, [c_void_p, c_int, c_int]),
+    "vbt_pipeline_live_poll": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "vbt_pipeline_get_info": (c_int, [c_void_p, ctypes.POINTER(PipelineInfo)]),
     "vbt_pipeline_model": (c_void_p, [c_void_p, c_int]),
     "vbt_pipeline_tracker": (c_void_p, [c_void_p]),

@@ -1,9 +1,12 @@
 """Command line mirror of the reference's two entry points, minus GUI/plotting:
 
-  python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1]
+  python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1] [--live]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
       dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
+      --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
+      list that changes afterwards (the leading id changes, or a larger rep makes the filter drop small ones) is announced with a
+      "revised" line and reprinted from the first rep that differs.  The reps standing at the end are those `analyze` prints.
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
@@ -27,6 +30,34 @@ def main():
     pass
 
 
+def _rep_line(i, p):
+    return f"  rep {i}: t {p.time_start:.4f}-{p.time_end:.4f} s  ROM {p.rom:.6f} m  ACV {p.rom / p.duration:.6f} m/s"
+
+
+class _LiveReps:
+    """track --live: the concentric reps of the clip's leader as they complete (see the module docstring)."""
+
+    def __init__(self, name):
+        self.name, self.shown, self.warned = name, [], False
+
+    def __call__(self, rec, final):
+        from .velocity import Phase
+        if rec.overflow:
+            if not self.warned:
+                click.echo(f"{self.name}: live analysis overflow (flags {rec.overflow}); live reps stop here", err=True)
+                self.warned = True
+            return
+        lines = [_rep_line(i, p) for i, p in enumerate((p for p in rec.phases if p.type == Phase.CONCENTRIC), 1)]
+        k = 0
+        while k < min(len(lines), len(self.shown)) and lines[k] == self.shown[k]:
+            k += 1
+        if k < len(self.shown):
+            click.echo(f"  revised: id {rec.leader}, from rep {k + 1}")
+        for ln in lines[k:]:
+            click.echo(ln)
+        self.shown = lines
+
+
 @main.command()
 @click.argument("src", type=str, nargs=-1)
 @click.option("--model", default=DEFAULT_MODEL, show_default=True, type=str, help="VBTM model container.")
@@ -35,7 +66,8 @@ def main():
 @click.option("--fps", default=30.0, show_default=True, type=float, help="Frame rate of the source (cap.get(CAP_PROP_FPS) in the reference).")
 @click.option("--frame_stride", default=1, show_default=True, type=int, help="16 reproduces `frame_count %% 16` of reference track.py:166.")
 @click.option("--time_batch", default=64, show_default=True, type=int, help="Consecutive frames of the clip per detector batch (1 = one frame per step).")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch):
+@click.option("--live", is_flag=True, default=False, help="Print each concentric rep (ROM, ACV) as soon as it is complete.")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live):
     from .track import export_dataframe, track_frames
     for s in src:
         if not os.path.isfile(s):
@@ -43,7 +75,8 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch)
         frames = np.load(s, mmap_mode="r")
         if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
             raise click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
-        data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch)
+        data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
+                            live=_LiveReps(s) if live else None)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")
             continue
@@ -72,7 +105,7 @@ def analyze(src, plate_diameter):
         reps = [p for p in phases if p.type == Phase.CONCENTRIC]
         click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {len(reps)} concentric reps")
         for i, p in enumerate(reps, 1):
-            click.echo(f"  rep {i}: t {p.time_start:.4f}-{p.time_end:.4f} s  ROM {p.rom:.6f} m  ACV {p.rom / p.duration:.6f} m/s")
+            click.echo(_rep_line(i, p))
 
 
 @main.command()

@@ -47,6 +47,7 @@ struct vbt_pipeline {
   vbt_pipeline_params prm{};
   int n = 0, n_trk = 0, depth = 0, ring = 0, defer = 0, device = 0, size = 0;
   bool trk_inline = false, placement_ok = true;
+  bool live = false;               // vbt_pipeline_live_enable succeeded
   std::vector<double> fps;
   std::vector<vbt_model*> models;
   vbt_tracker* trk = nullptr;
@@ -928,6 +929,25 @@ int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
     PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, slot), scores_of(p, slot), counts_of(p, slot), tm.data(), p->prm.detection_threshold, (void*)T));
   }
   return record_trk(p, slot, T);
+}
+
+// Every tracker launch goes through vbt_tracker_update_from_*, which enqueue the live analysis right behind it on the launch's stream -
+// before the ev_trk event the pipeline records there - so every site above (plain / slot / run steps, deferred groups, both tracker
+// stream modes, tracker-only steps) is covered.
+int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (p->step_idx > 0) { set_error("vbt_pipeline_live_enable: steps were enqueued (enable before the first step, or after a reset)"); return VBT_ERR_STATE; }
+  PL_CHECK(vbt_tracker_live_enable(p->trk, path_cap, phase_cap, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance));
+  p->live = true;
+  return VBT_OK;
+}
+
+int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (!p->live) { set_error("vbt_pipeline_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));   // (inline mode: the tracker stream now waits for the last tracker launch)
+  return vbt_tracker_live_poll(p->trk, flush_view, clips, phases6, cap, (void*)p->trk_stream);
 }
 
 int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {

@@ -1115,7 +1115,20 @@ struct VtState {  // reference VelocityTracker.py:30-48
   double win[30];
   int whead, wcount;
   double wtotal;
+  int ver;   // bumped whenever the phase list changes (an append, or a filter that drops phases)
+  int full;  // a capacity was hit: 1 = the open phase's path, 2 = the phase list (the state is not the reference's any more)
 };
+
+// The open phase's bar path (VelocityTracker.xs / ys / widths / heights / times), room for `cap` samples per column
+struct VtPath {
+  double *xs, *ys, *ws, *hs, *ts;
+  int cap;
+};
+
+__device__ inline void vt_init(VtState& s) {
+  s.phase = 2; s.neg = 0; s.pos = 0; s.nph = 0; s.n = 0; s.has_prev = 0; s.has_max = 0; s.y_prev = 0; s.max_y_diff = 0;
+  s.whead = 0; s.wcount = 0; s.wtotal = 0.0; s.ver = 0; s.full = 0;
+}
 
 __device__ inline double ra_update(VtState& s, double v) {  // reference RunningAverage.py:16-27
   s.win[(s.whead + s.wcount) % 30] = v;
@@ -1141,11 +1154,13 @@ __device__ inline void vt_filter(VtState& s, double* ph) {  // VelocityTracker.p
       o++;
     }
   }
+  if (o != s.nph) s.ver += 1;
   s.nph = o;
 }
 
-__device__ inline void vt_end_phase(VtState& s, const VtParams& p, const double* xs, const double* ys, const double* ws,
-                                    const double* hs, const double* ts, double* ph) {  // VelocityTracker.py:171-222
+// ph holds room for phcap phases
+__device__ inline void vt_end_phase(VtState& s, const VtParams& p, const VtPath& q, double* ph, int phcap) {  // VelocityTracker.py:171-222
+  const double *xs = q.xs, *ys = q.ys, *ws = q.ws, *hs = q.hs, *ts = q.ts;
   int imax = 0, imin = 0;
   for (int i = 1; i < s.n; i++) {
     if (ys[i] > ys[imax]) imax = i;
@@ -1169,10 +1184,13 @@ __device__ inline void vt_end_phase(VtState& s, const VtParams& p, const double*
       s.neg = 0; s.pos = 0; s.phase = 2;
       return;
     }
-    if (s.nph < MAXPH) {
+    if (s.nph < phcap) {
       double* o = ph + s.nph * 6;
       o[0] = ts[st]; o[1] = ts[en]; o[2] = ys[st]; o[3] = ys[en]; o[4] = distance; o[5] = (double)s.phase;
       s.nph += 1;
+      s.ver += 1;
+    } else {
+      s.full |= 2;
     }
     vt_filter(s, ph);
   }
@@ -1180,52 +1198,65 @@ __device__ inline void vt_end_phase(VtState& s, const VtParams& p, const double*
   s.pos = 0; s.neg = 0;
 }
 
+__device__ inline void vt_push(VtState& s, const VtPath& q, double x, double y, double w, double h, double t) {
+  if (s.n < q.cap) { q.xs[s.n] = x; q.ys[s.n] = y; q.ws[s.n] = w; q.hs[s.n] = h; q.ts[s.n] = t; s.n++; }
+  else s.full |= 1;
+}
+
+// ONE row of one track - the per-row step shared by the close-time scan (analyze_track) and the live analysis
+// (live_analyze_kernel), so that the two cannot drift apart.  r = time,x,y,dx,dy,h,w.  p.preprocess: plot.py:90-95 first, with
+// rm = the rolling(5) x / y and expanding h / w means and (drop_x, drop_y) the raw values leaving the window (drop: row >= 5).
+__device__ inline void vt_row(VtState& s, RollMean* rm, const VtParams& p, const double* r, bool drop, double drop_x, double drop_y,
+                              const VtPath& q, double* ph, int phcap) {
+  double time = r[0], x = r[1], y = r[2], h = r[5], w = r[6];
+  if (p.preprocess) {  // (dx, dy columns are smoothed there too but never used downstream)
+    if (drop) { rm[0].remove(drop_x); rm[1].remove(drop_y); }
+    rm[0].add(x); rm[1].add(y); rm[2].add(h); rm[3].add(w);
+    x = rm[0].mean(); y = rm[1].mean(); h = rm[2].mean(); w = rm[3].mean();
+  }
+  // VelocityTracker.process_measurements (VelocityTracker.py:92-158)
+  double width = ra_update(s, w);
+  double height = ra_update(s, h);
+  double dy = r[4];
+  if (s.has_prev) dy = y - s.y_prev;
+  else if (p.preprocess) dy = r[4];  // first sample: the (smoothed == raw) incoming dy
+  if (s.phase != 2) vt_push(s, q, x, y, width, height, time);
+  if (s.phase == 0) {
+    if (dy > 0) { s.pos += 1; s.neg = 0; if (s.pos >= 1) vt_end_phase(s, p, q, ph, phcap); }
+    else s.pos = 0;
+  }
+  if (s.phase == 1) {
+    if (dy < 0) { s.neg += 1; s.pos = 0; if (s.neg >= 1) vt_end_phase(s, p, q, ph, phcap); }
+    else { s.neg = 0; s.pos += 1; }
+  }
+  if (dy < 0 && s.phase == 2) {
+    s.neg += 1; s.pos = 0;
+    if (s.neg == 1) s.n = 0;
+    else vt_push(s, q, x, y, width, height, time);
+    if (s.neg >= 3) { s.phase = 0; s.pos = 0; s.neg = 0; }
+  }
+  if (dy > 0 && s.phase == 2) {
+    s.pos += 1; s.neg = 0;
+    if (s.pos == 1) s.n = 0;
+    else vt_push(s, q, x, y, width, height, time);
+    if (s.pos >= 3) { s.phase = 1; s.pos = 0; s.neg = 0; }
+  }
+  s.y_prev = y; s.has_prev = 1;
+}
+
 // cols: [T][7] = time,x,y,dx,dy,h,w of ONE track.  One lane per clip does the sequential scan.
 __device__ void analyze_track(const double* cols, int T, const VtParams& p, double* scratch /*5*T*/, double* ph, int* nph_out) {
-  double* xs = scratch; double* ys = xs + T; double* ws = ys + T; double* hs = ws + T; double* ts = hs + T;
+  const VtPath q{scratch, scratch + T, scratch + 2 * T, scratch + 3 * T, scratch + 4 * T, T};
   VtState s;
-  s.phase = 2; s.neg = 0; s.pos = 0; s.nph = 0; s.n = 0; s.has_prev = 0; s.has_max = 0; s.y_prev = 0; s.max_y_diff = 0;
-  s.whead = 0; s.wcount = 0; s.wtotal = 0.0;
-  RollMean rx, ry, rh, rw;
-  rx.init(); ry.init(); rh.init(); rw.init();
+  vt_init(s);
+  RollMean rm[4];
+  for (int j = 0; j < 4; j++) rm[j].init();
   for (int i = 0; i < T; i++) {
-    const double* r = cols + (size_t)i * 7;
-    double time = r[0], x = r[1], y = r[2], h = r[5], w = r[6];
-    if (p.preprocess) {  // plot.py:90-95 (dx, dy columns are smoothed there too but never used downstream)
-      if (i >= 5) { rx.remove(cols[(size_t)(i - 5) * 7 + 1]); ry.remove(cols[(size_t)(i - 5) * 7 + 2]); }
-      rx.add(x); ry.add(y); rh.add(h); rw.add(w);
-      x = rx.mean(); y = ry.mean(); h = rh.mean(); w = rw.mean();
-    }
-    // VelocityTracker.process_measurements (VelocityTracker.py:92-158)
-    double width = ra_update(s, w);
-    double height = ra_update(s, h);
-    double dy = r[4];
-    if (s.has_prev) dy = y - s.y_prev;
-    else if (p.preprocess) dy = r[4];  // first sample: the (smoothed == raw) incoming dy
-    if (s.phase != 2) { xs[s.n] = x; ys[s.n] = y; ws[s.n] = width; hs[s.n] = height; ts[s.n] = time; s.n++; }
-    if (s.phase == 0) {
-      if (dy > 0) { s.pos += 1; s.neg = 0; if (s.pos >= 1) vt_end_phase(s, p, xs, ys, ws, hs, ts, ph); }
-      else s.pos = 0;
-    }
-    if (s.phase == 1) {
-      if (dy < 0) { s.neg += 1; s.pos = 0; if (s.neg >= 1) vt_end_phase(s, p, xs, ys, ws, hs, ts, ph); }
-      else { s.neg = 0; s.pos += 1; }
-    }
-    if (dy < 0 && s.phase == 2) {
-      s.neg += 1; s.pos = 0;
-      if (s.neg == 1) s.n = 0;
-      else { xs[s.n] = x; ys[s.n] = y; ws[s.n] = width; hs[s.n] = height; ts[s.n] = time; s.n++; }
-      if (s.neg >= 3) { s.phase = 0; s.pos = 0; s.neg = 0; }
-    }
-    if (dy > 0 && s.phase == 2) {
-      s.pos += 1; s.neg = 0;
-      if (s.pos == 1) s.n = 0;
-      else { xs[s.n] = x; ys[s.n] = y; ws[s.n] = width; hs[s.n] = height; ts[s.n] = time; s.n++; }
-      if (s.pos >= 3) { s.phase = 1; s.pos = 0; s.neg = 0; }
-    }
-    s.y_prev = y; s.has_prev = 1;
+    const bool drop = i >= 5;
+    const double* old = cols + (size_t)(drop ? i - 5 : i) * 7;
+    vt_row(s, rm, p, cols + (size_t)i * 7, drop, old[1], old[2], q, ph, MAXPH);
   }
-  if (p.flush && s.phase != 2) vt_end_phase(s, p, xs, ys, ws, hs, ts, ph);  // end_processing, VelocityTracker.py:224-230
+  if (p.flush && s.phase != 2) vt_end_phase(s, p, q, ph, MAXPH);  // end_processing, VelocityTracker.py:224-230
   *nph_out = s.nph;
 }
 
@@ -1256,6 +1287,19 @@ __global__ __launch_bounds__(64) void window_means_kernel(const double* rows, in
   }
 }
 
+// The export rule (reference track.py:107-115) applied to the clip as it stands: the largest cumulative path length among the ids
+// with at least 2 rows - the dead ones are summed up in best_cum / best_id, the live ones compete here - ties to the lower id.
+// -1: no id qualifies.  The clip close's export id and the live analysis' leader.
+__device__ inline int export_id(const ClipState& st) {
+  double bc = st.best_cum;
+  int bi = st.best_id;
+  for (int t = 0; t < st.ntrk; t++) {
+    const Trk& k = st.trk[st.order[t]];
+    if (k.nrows >= 2 && (k.cum > bc || (k.cum == bc && (bi < 0 || k.id + 1 < bi)))) { bc = k.cum; bi = k.id + 1; }
+  }
+  return bi;
+}
+
 // end of clip: live tracks compete for the export id too; then gather the rows of the winner.
 __global__ __launch_bounds__(64) void select_gather_kernel(ClipState* states, const Row* rows, int rows_cap, double* cols, int* T,
                                                            int* best_ids) {
@@ -1263,12 +1307,7 @@ __global__ __launch_bounds__(64) void select_gather_kernel(ClipState* states, co
   ClipState& st = states[clip];
   __shared__ int s_best;
   if (lane == 0) {
-    double bc = st.best_cum;
-    int bi = st.best_id;
-    for (int t = 0; t < st.ntrk; t++) {
-      const Trk& k = st.trk[st.order[t]];
-      if (k.nrows >= 2 && (k.cum > bc || (k.cum == bc && (bi < 0 || k.id + 1 < bi)))) { bc = k.cum; bi = k.id + 1; }
-    }
+    const int bi = export_id(st);
     s_best = bi;
     best_ids[clip] = bi;
   }
@@ -1316,6 +1355,240 @@ __global__ void init_states_kernel(ClipState* states, int n) {
   st.best_id = -1; st.last_n = 0; st.best_cum = -1.0; st.used = 0ull;
 }
 
+// ------------------------------------------------------------------------------------------
+// live rep analysis (vbt_tracker_live_enable): the VelocityTracker of every id that can still win the export, fed while the clip runs
+// ------------------------------------------------------------------------------------------
+// Per clip a table of LIVE_ENTRIES entries keyed by row id: an id whose tracker is live (<= MAXT of them) or the best dead id (the
+// only dead one that can still win: a dead id's cum never grows, and best_cum only grows).  Every other entry is retired.  Each entry
+// carries the state of reference plot.py:90-95 (rolling / expanding means) and of VelocityTracker.py:30-48 after the id's rows so far;
+// fed through vt_row, the step of the close-time scan, its phase list IS the list analyze_track would give on those rows.
+constexpr int LIVE_ENTRIES = MAXT + 1;
+constexpr int LIVE_PATH_FULL = 1, LIVE_PHASES_FULL = 2, LIVE_ROWS_LOST = 4;   // = VBT_LIVE_* (include/vbt_hip.h)
+static_assert(LIVE_PATH_FULL == 1 && LIVE_PHASES_FULL == 2, "VtState.full bits");
+
+struct LiveEntry {
+  long long id;        // Row.id; -1 = free
+  int nrows, pad;      // rows of the id consumed
+  RollMean rm[4];      // rolling(5) x, y; expanding h, w
+  double ring[5][2];   // raw (x, y) of the id's last 5 rows: what leaves the rolling window
+  VtState s;
+};
+
+struct LiveClip {
+  int cursor, flags;           // rows of the log consumed; LIVE_ROWS_LOST
+  long long leader;            // export_id() after the rows consumed (-1: none)
+  int leader_ver, pad;         // VtState.ver of the leader's entry when seq was last bumped
+  unsigned long long seq;      // bumped whenever the leader or its phase list changes
+};
+
+struct LiveCfg {
+  VtParams p;                  // preprocess = 1, flush = 0
+  int path_cap, phase_cap;
+};
+
+struct LiveBufs {
+  LiveClip* clips;             // [n_clips]
+  LiveEntry* ents;             // [n_clips][LIVE_ENTRIES]
+  double* paths;               // [n_clips][LIVE_ENTRIES][5][path_cap]
+  double* phases;              // [n_clips][LIVE_ENTRIES][phase_cap][6]
+  double* view;                // [n_clips][phase_cap][6]: flush-view scratch of the poll
+};
+
+__device__ inline VtPath live_path(const LiveBufs& b, const LiveCfg& c, int clip, int e) {
+  const size_t pc = (size_t)c.path_cap;
+  double* base = b.paths + ((size_t)clip * LIVE_ENTRIES + e) * 5 * pc;
+  return VtPath{base, base + pc, base + 2 * pc, base + 3 * pc, base + 4 * pc, c.path_cap};
+}
+__device__ inline double* live_phases(const LiveBufs& b, const LiveCfg& c, int clip, int e) {
+  return b.phases + ((size_t)clip * LIVE_ENTRIES + e) * c.phase_cap * 6;
+}
+
+__device__ inline void live_entry_init(LiveEntry& x, long long id) {
+  x.id = id;
+  x.nrows = 0;
+  for (int j = 0; j < 4; j++) x.rm[j].init();
+  vt_init(x.s);
+}
+
+// One row of the entry's id (the rows of an id are applied in log order).  A full entry is frozen: it only counts rows.
+__device__ inline void live_apply(LiveEntry& x, const Row& r, const LiveBufs& b, const LiveCfg& c, int clip, int e) {
+  if (!x.s.full) {
+    const int k = x.nrows % 5;   // slot of row nrows - 5, the one leaving the rolling window
+    vt_row(x.s, x.rm, c.p, &r.time, x.nrows >= 5, x.ring[k][0], x.ring[k][1], live_path(b, c, clip, e), live_phases(b, c, clip, e),
+           c.phase_cap);
+    x.ring[k][0] = r.x;
+    x.ring[k][1] = r.y;
+  }
+  x.nrows += 1;
+}
+
+// One wavefront per clip, after every tracker launch, on the tracker launch's stream: consumes rows [cursor, nrows) of the clip's log,
+// whatever number of frames the launch walked.  Lane e owns entry e (lane 0 also entry 64): the rows of one frame carry distinct ids,
+// so the entries advance side by side, each lane applying its id's rows in log order.  Then the leader: export_id() as it stands.
+__global__ __launch_bounds__(64) void live_analyze_kernel(const ClipState* states, const Row* rows, int rows_cap, LiveBufs b, LiveCfg c) {
+  __shared__ long long s_keep[LIVE_ENTRIES];   // ids that can still win the export: the live tracks' and the best dead one
+  __shared__ long long s_eid[LIVE_ENTRIES];    // entry ids (-1: free)
+  __shared__ int s_free[LIVE_ENTRIES];
+  __shared__ int s_ver[LIVE_ENTRIES];
+  const int clip = blockIdx.x, lane = threadIdx.x;
+  const ClipState& st = states[clip];
+  const Row* R = rows + (size_t)clip * rows_cap;
+  LiveClip& L = b.clips[clip];
+  LiveEntry* E = b.ents + (size_t)clip * LIVE_ENTRIES;
+  const int ntrk = st.ntrk, best = st.best_id;
+  const int nkeep = ntrk + (best >= 0 ? 1 : 0);
+  for (int k = lane; k < LIVE_ENTRIES; k += 64) {
+    s_keep[k] = k < ntrk ? (long long)st.trk[st.order[k]].id + 1 : (k == ntrk && best >= 0 ? (long long)best : -2);
+    s_eid[k] = E[k].id;
+  }
+  __syncthreads();
+  // retire the entries of ids that can no longer win
+  for (int e = lane; e < LIVE_ENTRIES; e += 64) {
+    const long long id = s_eid[e];
+    bool keep = false;
+    for (int k = 0; k < nkeep; k++) keep = keep || s_keep[k] == id;
+    if (id >= 0 && !keep) { s_eid[e] = -1; E[e].id = -1; }
+  }
+  __syncthreads();
+  // a keeper without an entry takes a free one, the i-th such keeper the i-th free entry (enough of them: one entry per keeper at most)
+  auto missing = [&](int k) {
+    if (k >= nkeep) return false;
+    for (int e = 0; e < LIVE_ENTRIES; e++)
+      if (s_eid[e] == s_keep[k]) return false;
+    return true;
+  };
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const bool need0 = missing(lane), need1 = lane == 0 && missing(64);
+  const bool free0 = s_eid[lane] < 0, free1 = lane == 0 && s_eid[64] < 0;
+  const unsigned long long mn = __ballot(need0), mf = __ballot(free0);
+  if (free0) s_free[__popcll(mf & below)] = lane;
+  if (free1) s_free[__popcll(mf)] = 64;
+  __syncthreads();
+  if (need0) { const int e = s_free[__popcll(mn & below)]; live_entry_init(E[e], s_keep[lane]); s_eid[e] = s_keep[lane]; }
+  if (need1) { const int e = s_free[__popcll(mn)]; live_entry_init(E[e], s_keep[64]); s_eid[e] = s_keep[64]; }
+  __syncthreads();
+  // the new rows, 64 at a time: lane j reads row base + j's id, every entry lane collects the positions of its id's rows
+  const int n = st.nrows, cur = L.cursor;
+  const int my0 = (int)s_eid[lane], my1 = lane == 0 ? (int)s_eid[64] : -3;
+  for (int base = cur; base < n; base += 64) {
+    const int rid = base + lane < n ? (int)R[base + lane].id : -4;
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    for (int j = 0; j < 64; j++) {
+      const int v = __shfl(rid, j);
+      m0 |= (unsigned long long)(v == my0) << j;
+      m1 |= (unsigned long long)(v == my1) << j;
+    }
+    while (m0) {
+      const int j = __ffsll((long long)m0) - 1;
+      m0 &= m0 - 1;
+      live_apply(E[lane], R[base + j], b, c, clip, lane);
+    }
+    while (m1) {
+      const int j = __ffsll((long long)m1) - 1;
+      m1 &= m1 - 1;
+      live_apply(E[64], R[base + j], b, c, clip, 64);
+    }
+  }
+  s_ver[lane] = my0 >= 0 ? E[lane].s.ver : -1;
+  if (lane == 0) s_ver[64] = my1 >= 0 ? E[64].s.ver : -1;
+  __syncthreads();
+  if (lane == 0) {
+    const int ld = export_id(st);
+    int ver = -1;
+    for (int e = 0; e < LIVE_ENTRIES; e++)
+      if (ld >= 0 && s_eid[e] == ld) ver = s_ver[e];
+    if (ld != L.leader || ver != L.leader_ver) L.seq += 1;
+    L.leader = ld;
+    L.leader_ver = ver;
+    L.cursor = n;
+    if (st.rows_overflow > 0) L.flags |= LIVE_ROWS_LOST;
+  }
+}
+
+// The entry's phase list into out[phase_cap][6], as it stands or - flush - as end_processing() (VelocityTracker.py:224-230) would
+// leave it, applied to a COPY of the state: it may append one phase and re-filter.  The live state is not touched.  One wavefront,
+// uniform entry; returns the number of phases and ORs the entry's VBT_LIVE_* flags into *flags.
+__device__ inline int live_view(const LiveEntry& x, const LiveBufs& b, const LiveCfg& c, int clip, int e, bool flush, double* out,
+                                int* s_n, int* flags, int lane) {
+  const double* ph = live_phases(b, c, clip, e);
+  const int nph = x.s.nph;
+  for (int i = lane; i < nph * 6; i += 64) out[i] = ph[i];
+  __syncthreads();
+  if (lane == 0) {
+    int f = x.s.full, m = nph;
+    if (flush && x.s.phase != 2 && !f) {
+      VtState s = x.s;
+      vt_end_phase(s, c.p, live_path(b, c, clip, e), out, c.phase_cap);
+      f |= s.full;
+      m = s.nph;
+    }
+    *flags |= f;
+    *s_n = m;
+  }
+  __syncthreads();
+  return *s_n;
+}
+
+// vbt_tracker_live_poll: per clip a record { int64 leader; int32 rows_consumed, n_phases, phase_state, overflow; uint64 seq } (=
+// vbt_live_clip) + the leader's phases [cap][6], packed for ONE copy.  A flagged clip reports no phases.
+__global__ __launch_bounds__(64) void live_pack_kernel(LiveBufs b, LiveCfg c, int flush, int cap, unsigned char* out) {
+  __shared__ int s_e, s_n, s_flags;
+  const int clip = blockIdx.x, lane = threadIdx.x;
+  const LiveClip& L = b.clips[clip];
+  const LiveEntry* E = b.ents + (size_t)clip * LIVE_ENTRIES;
+  unsigned char* o = out + (size_t)clip * (32 + (size_t)cap * 48);
+  const long long ld = L.leader;
+  if (lane == 0) { s_e = -1; s_flags = L.flags; s_n = 0; }
+  __syncthreads();
+  if (ld >= 0 && E[lane].id == ld) s_e = lane;
+  if (lane == 0 && ld >= 0 && E[64].id == ld) s_e = 64;
+  __syncthreads();
+  const int e = s_e;
+  double* view = b.view + (size_t)clip * c.phase_cap * 6;
+  int n = 0;
+  if (e >= 0) n = live_view(E[e], b, c, clip, e, flush != 0, view, &s_n, &s_flags, lane);
+  else if (lane == 0 && ld >= 0) s_flags |= LIVE_ROWS_LOST;   // the leader's rows are not in the log
+  __syncthreads();
+  const int flags = s_flags;
+  if (flags) n = 0;
+  if (lane == 0) {
+    *(long long*)o = ld;
+    int* h = (int*)(o + 8);
+    h[0] = L.cursor; h[1] = n; h[2] = e >= 0 ? E[e].s.phase : 2; h[3] = flags;
+    *(unsigned long long*)(o + 24) = L.seq;
+  }
+  double* dst = (double*)(o + 32);
+  for (int i = lane; i < min(n, cap) * 6; i += 64) dst[i] = view[i];
+}
+
+// vbt_tracker_live_tracks: every entry of one clip, LIVE_ENTRIES records { int64 id; int32 n_rows, n_phases, flags, phase_state;
+// double phases[phase_cap][6] } (free entries: id -1).  One wavefront per entry.
+__global__ __launch_bounds__(64) void live_tracks_kernel(LiveBufs b, LiveCfg c, int clip, int flush, unsigned char* out) {
+  __shared__ int s_n, s_flags;
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const LiveEntry& x = b.ents[(size_t)clip * LIVE_ENTRIES + e];
+  unsigned char* o = out + (size_t)e * (24 + (size_t)c.phase_cap * 48);
+  if (lane == 0) { s_n = 0; s_flags = b.clips[clip].flags; }
+  __syncthreads();
+  const long long id = x.id;
+  int n = 0;
+  if (id >= 0) n = live_view(x, b, c, clip, e, flush != 0, (double*)(o + 24), &s_n, &s_flags, lane);
+  if (lane == 0) {
+    *(long long*)o = id;
+    int* h = (int*)(o + 8);
+    h[0] = id >= 0 ? x.nrows : 0; h[1] = s_flags ? 0 : n; h[2] = s_flags; h[3] = id >= 0 ? x.s.phase : 2;
+  }
+}
+
+__global__ void live_init_kernel(LiveClip* clips, LiveEntry* ents, int n_clips) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_clips) {
+    LiveClip& L = clips[i];
+    L.cursor = 0; L.flags = 0; L.leader = -1; L.leader_ver = -1; L.seq = 0;
+  }
+  if (i < n_clips * LIVE_ENTRIES) { ents[i].id = -1; ents[i].nrows = 0; }
+}
+
 }  // namespace vbt
 
 using namespace vbt;
@@ -1340,7 +1613,39 @@ struct vbt_tracker {
   double* d_view = nullptr;              // packed read-back block of the one-frame path (tracker_one_kernel)
   double* h_view = nullptr;              // its pinned host copy
   int view_clip = -1;                    // clip whose state h_view mirrors (-1: none: the state changed on another path)
+  bool stepped = false;                  // a tracker step was enqueued since creation / the last reset
+  // live rep analysis (vbt_tracker_live_enable); off: no allocation, no launch
+  bool live = false;
+  LiveBufs lb{};
+  LiveCfg lc{};
+  unsigned char* d_live = nullptr;       // packed poll block (live_pack_kernel), grown on demand
+  unsigned char* h_live = nullptr;       // its pinned host copy
+  size_t live_bytes = 0;
 };
+
+namespace {
+// live analysis after a tracker launch, on the same stream (so before whatever the caller records there next)
+int live_after(vbt_tracker* t, hipStream_t st) {
+  t->stepped = true;
+  if (!t->live) return VBT_OK;
+  live_analyze_kernel<<<t->n_clips, 64, 0, st>>>(t->states, t->rows, t->rows_cap, t->lb, t->lc);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+void live_free(vbt_tracker* t) {
+  if (t->lb.clips) (void)hipFree(t->lb.clips);
+  if (t->lb.ents) (void)hipFree(t->lb.ents);
+  if (t->lb.paths) (void)hipFree(t->lb.paths);
+  if (t->lb.phases) (void)hipFree(t->lb.phases);
+  if (t->lb.view) (void)hipFree(t->lb.view);
+  if (t->d_live) (void)hipFree(t->d_live);
+  if (t->h_live) (void)hipHostFree(t->h_live);
+  t->lb = LiveBufs{};
+  t->d_live = nullptr; t->h_live = nullptr; t->live_bytes = 0;
+  t->live = false;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1395,15 +1700,18 @@ void vbt_tracker_destroy(vbt_tracker* t) {
   if (t->h_summary) (void)hipHostFree(t->h_summary);
   if (t->d_view) (void)hipFree(t->d_view);
   if (t->h_view) (void)hipHostFree(t->h_view);
+  live_free(t);
   delete t;
 }
 
 int vbt_tracker_reset(vbt_tracker* t) {
   if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
   init_states_kernel<<<(t->n_clips + 63) / 64, 64>>>(t->states, t->n_clips);
+  if (t->live) live_init_kernel<<<(t->n_clips * LIVE_ENTRIES + 63) / 64, 64>>>(t->lb.clips, t->lb.ents, t->n_clips);
   VBT_HIP_CHECK(hipDeviceSynchronize());
   t->finished = false;
   t->view_clip = -1;
+  t->stepped = false;
   return VBT_OK;
 }
 
@@ -1420,6 +1728,7 @@ int vbt_tracker_update(vbt_tracker* t, const double* dets, const int32_t* counts
     memcpy(a.det, dets, sizeof(double) * 6 * a.n);
     tracker_one_kernel<<<1, 64, 0, nullptr>>>(t->states, t->rows, t->rows_cap, 0, a, t->p, t->q44, t->q66, t->d_view);
     VBT_HIP_CHECK(hipGetLastError());
+    if (int rc = live_after(t, nullptr)) return rc;
     VBT_HIP_CHECK(hipMemcpyAsync(t->h_view, t->d_view, sizeof(double) * VIEW_DOUBLES, hipMemcpyDeviceToHost, nullptr));
     VBT_HIP_CHECK(hipStreamSynchronize(nullptr));
     t->view_clip = 0;
@@ -1435,9 +1744,11 @@ int vbt_tracker_update(vbt_tracker* t, const double* dets, const int32_t* counts
   VBT_HIP_CHECK(hipMemcpy(dc, counts, nd * sizeof(int), hipMemcpyHostToDevice));
   VBT_HIP_CHECK(hipMemcpy(dt, times, nd * sizeof(double), hipMemcpyHostToDevice));
   tracker_kernel<<<t->n_clips, 64>>>(t->states, t->rows, t->rows_cap, dd, dc, dt, F, t->n_clips, t->p, t->q44, t->q66);
+  const int lrc = live_after(t, nullptr);
   hipError_t e = hipDeviceSynchronize();
   (void)hipFree(dd); (void)hipFree(dc); (void)hipFree(dt);
   if (e != hipSuccess) { set_error("tracker kernel failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  if (lrc != VBT_OK) return lrc;
   t->finished = false;
   return VBT_OK;
 }
@@ -1458,6 +1769,7 @@ static int launch_steps(vbt_tracker* t, const float* boxes_dev, const float* sco
                                                t->p, t->q44, t->q66);
   }
   VBT_HIP_CHECK(hipGetLastError());
+  if (int rc = live_after(t, st)) return rc;
   t->finished = false;
   t->view_clip = -1;
   return VBT_OK;
@@ -1535,6 +1847,7 @@ int vbt_tracker_update_from_detections_seq(vbt_tracker* t, const float* boxes_de
                                                                            det_threshold, t->p, t->q44, t->q66, lds_state);
   }
   VBT_HIP_CHECK(hipGetLastError());
+  if (int rc = live_after(t, st)) return rc;
   t->finished = false;
   t->view_clip = -1;
   return VBT_OK;
@@ -1792,6 +2105,102 @@ int vbt_tracker_rows_all(vbt_tracker* t, int32_t* counts, void* rows_host, int c
                                    hipMemcpyDeviceToHost, st));
     VBT_HIP_CHECK(hipStreamSynchronize(st));
   }
+  return VBT_OK;
+}
+
+// ---- live rep analysis ----
+int vbt_tracker_live_enable(vbt_tracker* t, int path_cap, int phase_cap, double plate_diameter, double diff_threshold, double min_distance) {
+  if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
+  if (path_cap < 2 || path_cap > VBT_LIVE_MAX_PATH || phase_cap < 1 || phase_cap > VBT_LIVE_MAX_PHASES) {
+    set_error("vbt_tracker_live_enable: path_cap must be in [2, %d], phase_cap in [1, %d]", VBT_LIVE_MAX_PATH, VBT_LIVE_MAX_PHASES);
+    return VBT_ERR_ARG;
+  }
+  if (t->live) { set_error("vbt_tracker_live_enable: live analysis is already enabled"); return VBT_ERR_STATE; }
+  if (t->stepped) { set_error("vbt_tracker_live_enable: the tracker has been stepped (enable before the first update, or after a reset)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  const size_t n = (size_t)t->n_clips, ne = n * LIVE_ENTRIES;
+  LiveBufs& b = t->lb;
+  if (hipMalloc((void**)&b.clips, sizeof(LiveClip) * n) != hipSuccess || hipMalloc((void**)&b.ents, sizeof(LiveEntry) * ne) != hipSuccess ||
+      hipMalloc((void**)&b.paths, sizeof(double) * 5 * (size_t)path_cap * ne) != hipSuccess ||
+      hipMalloc((void**)&b.phases, sizeof(double) * 6 * (size_t)phase_cap * ne) != hipSuccess ||
+      hipMalloc((void**)&b.view, sizeof(double) * 6 * (size_t)phase_cap * n) != hipSuccess) {
+    live_free(t);
+    (void)hipGetLastError();
+    set_error("vbt_tracker_live_enable: hipMalloc of the live tables failed (%d clips, path_cap %d, phase_cap %d)", t->n_clips, path_cap, phase_cap);
+    return VBT_ERR_HIP;
+  }
+  t->lc.p = VtParams{plate_diameter, diff_threshold, min_distance, 1, 0};
+  t->lc.path_cap = path_cap;
+  t->lc.phase_cap = phase_cap;
+  live_init_kernel<<<(int)((ne + 63) / 64), 64>>>(b.clips, b.ents, t->n_clips);
+  const hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) { live_free(t); set_error("live init failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  t->live = true;
+  return VBT_OK;
+}
+
+// One pack launch on `stream` (after the tracker launches it carries), ONE copy into pinned memory, ONE synchronisation of that stream.
+int vbt_tracker_live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, int cap, void* stream) {
+  if (!t || !clips || cap < 0 || (cap > 0 && !phases6)) { set_error("vbt_tracker_live_poll: bad argument"); return VBT_ERR_ARG; }
+  if (!t->live) { set_error("vbt_tracker_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
+  static_assert(sizeof(vbt_live_clip) == 32, "vbt_live_clip record");
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  const int n = t->n_clips;
+  const int pcap = std::min(cap, t->lc.phase_cap);   // a clip never reports more than phase_cap phases
+  const size_t rec = 32 + (size_t)pcap * 48, bytes = rec * n;
+  if (bytes > t->live_bytes) {
+    if (t->d_live) (void)hipFree(t->d_live);
+    if (t->h_live) (void)hipHostFree(t->h_live);
+    t->d_live = nullptr; t->h_live = nullptr; t->live_bytes = 0;
+    VBT_HIP_CHECK(hipMalloc((void**)&t->d_live, bytes));
+    VBT_HIP_CHECK(hipHostMalloc((void**)&t->h_live, bytes, hipHostMallocDefault));
+    t->live_bytes = bytes;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  live_pack_kernel<<<n, 64, 0, st>>>(t->lb, t->lc, flush_view, pcap, t->d_live);
+  VBT_HIP_CHECK(hipGetLastError());
+  VBT_HIP_CHECK(hipMemcpyAsync(t->h_live, t->d_live, bytes, hipMemcpyDeviceToHost, st));
+  VBT_HIP_CHECK(hipStreamSynchronize(st));
+  for (int c = 0; c < n; c++) {
+    const unsigned char* r = t->h_live + c * rec;
+    memcpy(&clips[c], r, sizeof(vbt_live_clip));
+    if (clips[c].n_phases > cap) { set_error("clip %d: %d phases, buffer holds %d", c, clips[c].n_phases, cap); return VBT_ERR_CAPACITY; }
+    if (clips[c].n_phases > 0) memcpy(phases6 + (size_t)c * cap * 6, r + 32, (size_t)clips[c].n_phases * 48);
+  }
+  return VBT_OK;
+}
+
+int vbt_tracker_live_tracks(vbt_tracker* t, int clip, int flush_view, int64_t* ids, int32_t* n_rows, int32_t* n_phases, int32_t* flags,
+                            double* phases6, int cap_tracks, int cap_phases, int* n) {
+  if (!t || !ids || !n_rows || !n_phases || !flags || !phases6 || !n || clip < 0 || clip >= t->n_clips || cap_tracks < 1 || cap_phases < 1) {
+    set_error("vbt_tracker_live_tracks: bad argument");
+    return VBT_ERR_ARG;
+  }
+  if (!t->live) { set_error("vbt_tracker_live_tracks: live analysis is not enabled"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  VBT_HIP_CHECK(hipDeviceSynchronize());
+  const size_t rec = 24 + (size_t)t->lc.phase_cap * 48, bytes = rec * LIVE_ENTRIES;
+  unsigned char* d = nullptr;
+  VBT_HIP_CHECK(hipMalloc((void**)&d, bytes));
+  std::vector<unsigned char> h(bytes);
+  live_tracks_kernel<<<LIVE_ENTRIES, 64>>>(t->lb, t->lc, clip, flush_view, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) { set_error("live tracks kernel failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  int m = 0;
+  for (int k = 0; k < LIVE_ENTRIES; k++) {
+    const unsigned char* r = h.data() + k * rec;
+    const long long id = *(const long long*)r;
+    const int* hd = (const int*)(r + 8);
+    if (id < 0 || hd[0] == 0) continue;   // free, or no row of the id yet
+    if (m >= cap_tracks) { set_error("clip %d holds more than %d live tracks", clip, cap_tracks); return VBT_ERR_CAPACITY; }
+    if (hd[1] > cap_phases) { set_error("id %lld: %d phases, buffer holds %d", id, hd[1], cap_phases); return VBT_ERR_CAPACITY; }
+    ids[m] = id; n_rows[m] = hd[0]; n_phases[m] = hd[1]; flags[m] = hd[2];
+    memcpy(phases6 + (size_t)m * cap_phases * 6, r + 24, (size_t)hd[1] * 48);
+    m++;
+  }
+  *n = m;
   return VBT_OK;
 }
 

@@ -6,6 +6,7 @@ Mirrors what reference track.py uses of the (unpinned) `ocsort` package:
   .trackers: list of objects with .id (0-based) and .kf.x (7x1)    track.py:194-199
 plus `MultiClipTracker`, the batched form used by the fused pipeline (n clips in one launch).
 """
+import collections
 import ctypes
 from types import SimpleNamespace
 
@@ -140,6 +141,58 @@ def _rows_all(self, cap=None, out=None, stream=None):
 
 
 MultiClipTracker.rows_all = _rows_all
+
+# ---- live rep analysis (vbt_tracker_live_enable, include/vbt_hip.h) ----
+LIVE_PATH_CAP, LIVE_PHASE_CAP = 2048, 128          # defaults: samples of an open phase, phases of one id
+LIVE_PATH_FULL, LIVE_PHASES_FULL, LIVE_ROWS_LOST = 1, 2, 4
+# one clip: leader = the id the clip close would export now (-1: none yet); phases = its list[velocity.Phase] (empty when overflow != 0);
+# seq bumps whenever the leader or its list changes; overflow = LIVE_* bits; rows = rows analysed; phase_state 0 conc / 1 ecc / 2 hold
+LiveClip = collections.namedtuple("LiveClip", "leader phases seq overflow rows phase_state")
+LiveTrack = collections.namedtuple("LiveTrack", "rows phases flags")   # phases: float64 [n, 6] (Phase.py:16-22 order)
+
+
+def _phase_list(ph):
+    from .velocity import Phase
+    return [Phase(r[0], r[1], r[2], r[3], r[4], int(r[5])) for r in ph]
+
+
+def _live_records(recs, ph):
+    return [LiveClip(int(r.leader_id), _phase_list(ph[i, :r.n_phases]), int(r.seq), int(r.overflow), int(r.rows_consumed), int(r.phase_state))
+            for i, r in enumerate(recs)]
+
+
+def _enable_live(self, path_cap=LIVE_PATH_CAP, phase_cap=LIVE_PHASE_CAP, plate_diameter=0.45, diff_threshold=0.6, min_distance=0.1):
+    """Live rep analysis (before the first update_frames / after reset): every id that can still win the export keeps a VelocityTracker
+    fed with its rows as they are emitted.  path_cap: samples of one open phase; phase_cap: phases of one id."""
+    _lib.check(_lib.lib().vbt_tracker_live_enable(self._h, int(path_cap), int(phase_cap), float(plate_diameter), float(diff_threshold),
+                                                  float(min_distance)))
+    self._live_phase_cap = int(phase_cap)
+
+
+def _live(self, flush_view=False, stream=None):
+    """One LiveClip per clip; flush_view: the phases as if the clip ended now (end_processing() on a copy)."""
+    n, cap = self.n_clips, getattr(self, "_live_phase_cap", LIVE_PHASE_CAP)
+    recs = (_lib.LiveClip * n)()
+    ph = np.zeros((n, cap, 6), np.float64)
+    _lib.check(_lib.lib().vbt_tracker_live_poll(self._h, int(bool(flush_view)), recs, ph.ctypes.data, cap, stream))
+    return _live_records(recs, ph)
+
+
+def _live_tracks(self, clip=0, flush_view=False):
+    """{id: LiveTrack(rows, phases [n,6], flags)} of every analysed id of `clip` (the ids that can still win, with a row)."""
+    cap = getattr(self, "_live_phase_cap", LIVE_PHASE_CAP)
+    ids = np.zeros(65, np.int64)
+    rows, nph, flags = (np.zeros(65, np.int32) for _ in range(3))
+    ph = np.zeros((65, cap, 6), np.float64)
+    n = ctypes.c_int()
+    _lib.check(_lib.lib().vbt_tracker_live_tracks(self._h, int(clip), int(bool(flush_view)), ids.ctypes.data, rows.ctypes.data, nph.ctypes.data,
+                                                  flags.ctypes.data, ph.ctypes.data, 65, cap, ctypes.byref(n)))
+    return {int(ids[i]): LiveTrack(int(rows[i]), ph[i, :nph[i]].copy(), int(flags[i])) for i in sorted(range(n.value), key=lambda i: ids[i])}
+
+
+MultiClipTracker.enable_live = _enable_live
+MultiClipTracker.live = _live
+MultiClipTracker.live_tracks = _live_tracks
 
 
 class OCSort:

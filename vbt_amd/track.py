@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .interpreter import Interpreter
-from .ocsort import ROW_DTYPE, MultiClipTracker, OCSort
+from .ocsort import LIVE_PATH_CAP, LIVE_PHASE_CAP, ROW_DTYPE, MultiClipTracker, OCSort, _live_records
 from .odt import (calc_bounding_box_center, calc_plate_height, calc_plate_width, results_to_sorttracker_inputs,
                   run_odt)
 
@@ -62,12 +62,14 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
     return data
 
 
-def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0):
+def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
     odt.py:10-19).  frame_stride = the `frame_count % 16` of track.py:166: frames whose 1-based number is not a multiple are
-    read and dropped, they only advance the clip time.  Returns the reference's dict of lists (track.py:144-145)."""
+    read and dropped, they only advance the clip time.  Returns the reference's dict of lists (track.py:144-145).
+    live: optional callable(ocsort.LiveClip, final) - live rep analysis on: called after every batch with the clip's record, and
+    once more after the last one with the flush view (final=True: the phases the clip close gives)."""
     T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     stride = max(int(frame_stride), 1)
     kept = T // stride                                               # frames that are processed
@@ -76,14 +78,20 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
                     rows_per_frame=25, tracker_clips=1)
     size = pipe._size
     src_hw = None if (H, W) == (size, size) else (H, W)
-    if isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
+    if live is not None:
+        pipe.enable_live()
+    elif isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
         return pipe.track_clip(frames, frame_stride=stride, src_hw=src_hw)      # vbt_track_clip: the whole loop inside the library
-    # any other sequence: chunk by chunk through contiguous host copies
+    # any other sequence (or live analysis): chunk by chunk through contiguous host copies
     idx_all = np.arange(stride - 1, T, stride)
     for i0 in range(0, len(idx_all), F):
         idx = idx_all[i0:i0 + F]
         chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
         pipe.step_runs(chunk, [(0, 0, len(idx), int(idx[0]) + 1, stride)], src_hw=src_hw)
+        if live is not None:
+            live(pipe.live()[0], False)
+    if live is not None:
+        live(pipe.live(flush_view=True)[0], True)
     pipe.finish()
     return pipe.rows(0)
 
@@ -372,6 +380,22 @@ class Pipeline:
     def tracker_only_steps(self, count, slot=0):
         """Measurement split: `count` tracker steps of all clips on the detections sitting in ring slot `slot`."""
         _lib.check(_lib.lib().vbt_pipeline_tracker_only_steps(self._h, int(count), int(slot)))
+
+    def enable_live(self, path_cap=LIVE_PATH_CAP, phase_cap=LIVE_PHASE_CAP):
+        """Live rep analysis (before the first step / after reset()): after every tracker launch the rows it emitted feed a
+        VelocityTracker per id that can still win the export, on the tracker's stream.  live() reads the result."""
+        _lib.check(_lib.lib().vbt_pipeline_live_enable(self._h, int(path_cap), int(phase_cap)))
+        self.tracker._live_phase_cap = int(phase_cap)
+
+    def live(self, flush_view=False):
+        """One ocsort.LiveClip per clip - leader (the id close() would export now), its list[velocity.Phase], seq, overflow - after
+        every step enqueued so far (held-back tracker steps are drained; waits for the last tracker launch only).  flush_view: the
+        phases as if the clip ended now."""
+        n, cap = self.n_trk, getattr(self.tracker, "_live_phase_cap", LIVE_PHASE_CAP)
+        recs = (_lib.LiveClip * n)()
+        ph = np.zeros((n, cap, 6), np.float64)
+        _lib.check(_lib.lib().vbt_pipeline_live_poll(self._h, int(bool(flush_view)), recs, ph.ctypes.data, cap))
+        return _live_records(recs, ph)
 
     def skip_frames(self, n=1):
         """Frames read from the source but not processed (`frame_count % 16` of reference track.py:161-167): they advance the clip
