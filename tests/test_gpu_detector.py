@@ -265,18 +265,19 @@ def test_integer_add_ties_bit_exact_in_every_fused_path(tie_model, oracle_lib, f
 def test_plan_file_with_a_foreign_kernel_name_is_refused(model_path, tmp_path, monkeypatch):
     """Plan files name the kernel family of every step (format 2): a file whose names do not fit this build of the planner - tuned for
     another set of alternatives - must not select kernels by bare index; the library refuses it, re-tunes and re-writes it.  A format-1
-    file (indices only) and the pinned format-2 file both load unchanged."""
+    file (indices only) and every pinned format-2 file load unchanged."""
     import shutil
     from conftest import ROOT
     from vbt_amd.interpreter import Interpreter
-    pinned = os.path.join(ROOT, "profiles", "plan_lite0.b8.f0")
-    good = open(pinned).read()
-    assert good.startswith("VBTPLAN2 ")
     prefix = str(tmp_path / "plan")
     monkeypatch.setenv("VBT_PLAN_FILE", prefix)
-    shutil.copy(pinned, prefix + ".b8.f0")
-    Interpreter(model_path, max_batch=8)
-    assert open(prefix + ".b8.f0").read() == good                       # accepted as it is
+    for b in (1, 8, 64, 256):
+        pinned = os.path.join(ROOT, "profiles", f"plan_lite0.b{b}.f0")
+        shutil.copy(pinned, f"{prefix}.b{b}.f0")
+        Interpreter(model_path, max_batch=b)
+        assert open(f"{prefix}.b{b}.f0").read() == open(pinned).read(), b   # accepted as it is
+    good = open(os.path.join(ROOT, "profiles", "plan_lite0.b8.f0")).read()
+    assert good.startswith("VBTPLAN2 ")
     bad = good.replace("fused_mbconv:", "fused_mbconv_of_another_build:", 1)
     open(prefix + ".b8.f0", "w").write(bad)
     it = Interpreter(model_path, max_batch=8)
@@ -286,3 +287,29 @@ def test_plan_file_with_a_foreign_kernel_name_is_refused(model_path, tmp_path, m
     open(prefix + ".b8.f0", "w").write(legacy)
     Interpreter(model_path, max_batch=8)
     assert open(prefix + ".b8.f0").read() == legacy                     # format 1 still loads (and is left alone without VBT_PLAN_CONVERT)
+
+
+@pytest.mark.parametrize("line,variant", [(2, 5), (4, 17)])
+def test_plan_file_with_a_variant_that_does_not_fit_is_refused(model_path, frames, oracle_run, tmp_path, monkeypatch, line, variant):
+    """A plan value the kernel cannot run on that step is refused when the file is read (the library re-tunes and re-writes it), not at
+    every forward: the whole-image kernel (5) on the 160x160 -> 80x80 block b1, and the 128-pixel tile (17) on the 5x5 stride-2 block b3,
+    whose 80-byte E rows need more than 64 KB of LDS there.  The model then detects what the oracle does."""
+    import shutil
+    from conftest import ROOT
+    from vbt_amd.interpreter import Interpreter
+    prefix = str(tmp_path / "plan")
+    monkeypatch.setenv("VBT_PLAN_FILE", prefix)
+    shutil.copy(os.path.join(ROOT, "profiles", "plan_lite0.b8.f0"), prefix + ".b8.f0")
+    lines = open(prefix + ".b8.f0").read().split("\n")
+    assert lines[line].startswith(("1 1 fused_mbconv:", "2 1 fused_mbconv:")), lines[line]
+    lines[line] = lines[line].rsplit(":", 1)[0] + f":{variant}"
+    bad = "\n".join(lines)
+    open(prefix + ".b8.f0", "w").write(bad)
+    it = Interpreter(model_path, max_batch=8)
+    after = open(prefix + ".b8.f0").read()
+    assert after != bad and after.startswith("VBTPLAN2 ")
+    boxes, scores, classes, counts = it.detect(frames)
+    outs, _ = oracle_run
+    for b in range(len(frames)):
+        ob, os_, oc, on = outs[b]
+        assert counts[b] == on and np.array_equal(scores[b], os_) and np.array_equal(boxes[b], ob) and np.array_equal(classes[b], oc)

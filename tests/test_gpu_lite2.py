@@ -89,6 +89,8 @@ def test_lite2_batch64_equals_oracle_with_the_pinned_plan(oracle_lib):
     model = os.path.join(ROOT, "models", "efficientdet_lite2_synth.vbtm")
     old = os.environ.get("VBT_PLAN_FILE")
     os.environ["VBT_PLAN_FILE"] = os.path.join(ROOT, "profiles", "plan_lite2")
+    pinned = os.path.join(ROOT, "profiles", "plan_lite2.b64.f0")
+    pinned_bytes = open(pinned, "rb").read()
     try:
         n, T, S = 64, 16, 448                      # 16 steps: the tracker is past min_hits on every clip, the ring of the pipeline wraps five times
         frames = np.stack([np.stack([synth.render(synth.background(300 + c, S), 5 * c + 2 * t) for c in range(n)]) for t in range(T)])
@@ -98,6 +100,7 @@ def test_lite2_batch64_equals_oracle_with_the_pinned_plan(oracle_lib):
             os.environ.pop("VBT_PLAN_FILE", None)
         else:
             os.environ["VBT_PLAN_FILE"] = old
+    assert open(pinned, "rb").read() == pinned_bytes       # the pinned plan loaded as it is (a refused file would have been re-tuned and re-written)
     fd = torch.from_numpy(frames).cuda()
     got = []
     for t in range(T):

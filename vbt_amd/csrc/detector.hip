@@ -319,6 +319,18 @@ static void choose_tile(int OH, int OW, int KK, int S, bool expand, int* TXo, in
   }
 }
 
+// LDS bytes of one fused tile (fused_block.h): the input halo of a TX x TY tile (T0S bytes per pixel), the expanded halo (est bytes per
+// pixel; 0: no expand stage), the depthwise output of 64 * ppw pixels and, for a single-chunk SeparableConv / node, the projection
+// weights + bias / multipliers staged in LDS.  (Rounding the E rows up to 16 bytes changes only the 72-byte rows: FB_EST and 48 are
+// multiples of 16.)
+static int fused_tile_lds(const FusedArgs& a, int k, int stride, int TX, int TY, int est, int ppw, int nbp) {
+  const int TXp = (TX + 3) & ~3;
+  const int NPh = ((TXp - 1) * stride + k) * ((TY - 1) * stride + k);
+  int lds = ((NPh * a.T0S + 15) & ~15) + ((NPh * est + 15) & ~15) + ppw * 64 * FB_DST;
+  if (!est && a.nchunks == 1 && nbp <= 2) lds += nbp * (4096 + 512);
+  return lds;
+}
+
 // sources of a BiFPN node's sum.  pre_add >= 0: the sum is two chained binary ADDs (3-input sums of a TFLite graph):
 // sources 0,1 are the inputs of ops[pre_add], source 2 the other input of the final ADD, chain = 1|2 the position of the
 // partial sum among the final ADD's inputs (+1).
@@ -472,10 +484,7 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
     }
   }
   s.nbp = ps.NB <= 3 ? ps.NB : 5;
-  const int TXp = (a.TX + 3) & ~3;
-  const int NPh = ((TXp - 1) * dop.stride + dop.k) * ((a.TY - 1) * dop.stride + dop.k);
-  s.lds_bytes = ((NPh * a.T0S + 15) & ~15) + (expand ? NPh * FB_EST : 0) + 64 * FB_DST;
-  if (!expand && a.nchunks == 1 && s.nbp <= 2) s.lds_bytes += s.nbp * (4096 + 512);   // projection weights + bias / multipliers staged in LDS
+  s.lds_bytes = fused_tile_lds(a, dop.k, dop.stride, a.TX, a.TY, expand ? FB_EST : 0, 1, s.nbp);
   // accounting = compulsory traffic of the constituent graph ops
   std::vector<int> parts{e_op, d_op, p_op, a_op, sum_op};
   if (ns) for (int j = 0; j < ns->n; j++) parts.push_back(ns->rs_op[j]);
@@ -970,9 +979,9 @@ static ExpDwGeom expdw_geom(int H, int W, int OH, int OW, int k, int stride, int
   return g;
 }
 // whole image when the map has at most 400 pixels and fits (every block of Lite0: the round-2 plan is unchanged); otherwise the
-// fewest bands whose workgroup stays below VBT_XD_BAND_LDS bytes (default 96 KB: one and a half workgroups' worth of a CU)
+// fewest bands whose workgroup stays below 96 KB (one and a half workgroups' worth of a CU)
 static ExpDwGeom expdw_choose(int H, int W, int OH, int OW, int k, int stride, int pad_t, int pad_l, int T0S) {
-  static const int budget = getenv("VBT_XD_BAND_LDS") ? atoi(getenv("VBT_XD_BAND_LDS")) : 96 * 1024;
+  const int budget = 96 * 1024;
   ExpDwGeom g = expdw_geom(H, W, OH, OW, k, stride, pad_t, pad_l, T0S, 1);
   if (H * W <= 400 && OH * OW <= 400 && g.t0_bytes + g.e_bytes + g.d_bytes <= 160 * 1024) return g;
   for (int nb = 2; nb <= OH; nb++) {
@@ -1159,12 +1168,11 @@ static ExpDw2Geom expdw2_choose(int H, int W, int OH, int OW, int k, int stride,
 // fills s->xd2 from the finished first-form arguments s->xd and the host images of its expand weights / biases / multipliers
 static int make_expdw2(vbt_model* m, int e_op, int d_op, Step* s, const std::vector<v4i>& pe, const std::vector<int>& be, const std::vector<float>& me,
                        const std::vector<int>& bd, const std::vector<float>& md) {
-  static const bool enabled = !(getenv("VBT_XD_V2") && atoi(getenv("VBT_XD_V2")) == 0);
   const OpRec& dop = m->ops[d_op];
   const ExpDwArgs& a1 = s->xd;
   s->xd2_ok = false;
   const int KS64 = (a1.Cin + 63) / 64;
-  if (!enabled || (dop.stride != 1 && dop.stride != 2) || (dop.k != 3 && dop.k != 5) || a1.Cin % 8 != 0 || KS64 < 2 || KS64 > 4) return VBT_OK;
+  if ((dop.stride != 1 && dop.stride != 2) || (dop.k != 3 && dop.k != 5) || a1.Cin % 8 != 0 || KS64 < 2 || KS64 > 4) return VBT_OK;
   const ExpDw2Geom geo = expdw2_choose(a1.H, a1.W, a1.OH, a1.OW, dop.k, dop.stride, a1.pad_t, KS64);
   if (!geo.ok) return VBT_OK;
   ExpDw2Args& a = s->xd2;
@@ -1784,262 +1792,348 @@ static int build_plan(vbt_model* m) {
   return fuse_plan(m);
 }
 
-template <int KS>
-static void launch_pw_a(int MS, dim3 grid, hipStream_t st, const int8_t* x, const v4i* wp, Epi e, ResArgs ra, int8_t* out, long M, int K,
-                        int N, int NB, int nb_per_y) {
-  if (MS == 2) pw_a_kernel<KS, 2><<<grid, 256, 0, st>>>(x, wp, e, ra, out, M, K, N, NB, nb_per_y);
-  else pw_a_kernel<KS, 1><<<grid, 256, 0, st>>>(x, wp, e, ra, out, M, K, N, NB, nb_per_y);
+// ---- variant resolution: one pure host function per launch family turns (step, variant, batch; -1 = heuristic default) into the
+// launch it stands for, or refuses it.  The launches, the autotuner's candidates and the plan-file check all ask these. ----
+struct Verdict {   // rc != VBT_OK: the step is refused, and `why` is the error text of its launch
+  int rc = VBT_OK; char why[160] = "";
+  void refuse(int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(why, sizeof(why), fmt, ap); va_end(ap); rc = code; }
+  int report() const { set_error("%s", why); return rc; }
+};
+
+// pointwise conv (one conv; the merged launch of merge_side_convs has no variants)
+enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E };
+struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0; dim3 grid; };
+static PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B) {
+  PwLaunch L;
+  const TensorRec& to = m->tensors[m->ops[s.res_op >= 0 ? s.p_op : s.op].output];
+  const long M = (long)B * to.h * to.w;
+  if (s.KS64 <= 4) {   // K <= 256 (pw_a_kernel): variant bit 0 = two pixel groups per wave
+    L.form = PW_A;
+    L.ms = variant >= 0 ? (variant & 1) + 1 : (M >= 32768 ? 2 : 1);
+    const long waves = (M + 16 * L.ms - 1) / (16 * L.ms);
+    const unsigned gx = (unsigned)((waves + 3) / 4);
+    int ysplit = 1;
+    while (gx * ysplit < 1024 && ysplit < s.NB) ysplit++;
+    L.nb_per_y = (s.NB + ysplit - 1) / ysplit;
+    L.grid = dim3(gx, (s.NB + L.nb_per_y - 1) / L.nb_per_y);
+    return L;
+  }
+  // VBT_PW_VARIANT (tests): the kernel variant of every pointwise conv with K > 256, whatever the plan says
+  static const int pw_force = getenv("VBT_PW_VARIANT") ? atoi(getenv("VBT_PW_VARIANT")) : -100;
+  if (pw_force != -100) variant = pw_force;
+  if (variant >= 3 && variant <= 6) {   // 64 (3 / 5) or 128 (4 / 6) pixels per workgroup; weights shared through LDS (3 / 4: pw_d_kernel)
+    L.form = variant <= 4 ? PW_D : PW_E;   // or the block's whole weight panel in LDS and a K loop without barriers (5 / 6: pw_e_kernel)
+    L.ms = 2 - (variant & 1);
+    L.lds = L.form == PW_E ? s.KS64 * 4096 : 0;
+    L.grid = dim3((unsigned)((M + 64 * L.ms - 1) / (64 * L.ms)), (unsigned)s.NB);
+    if (L.lds > 160 * 1024) L.refuse(VBT_ERR_ARG, "pw_conv: a weight panel of %d bytes does not fit the LDS", L.lds);
+  } else if (variant == 2) {   // split-K over the 4 waves of a workgroup
+    // one 64-channel block per workgroup (16 KB of LDS for the cross-wave reduction, twice the workgroups) rather than two
+    // (32 KB): +1.4 % end to end with three forwards in flight - the workgroups of one launch then fit the CUs in one round.
+    // Two pixel groups per workgroup (half the weight bytes through L1) as long as the grid still has two workgroups per CU.
+    L.form = PW_C;
+    L.ms = ((M + 31) / 32) * s.NB >= 512 ? 2 : 1;
+    L.grid = dim3((unsigned)((M + 16 * L.ms - 1) / (16 * L.ms)), (unsigned)s.NB);
+  } else {   // K streamed through registers (pw_b_kernel), nbt 64-channel blocks per wave
+    const unsigned gx = (unsigned)(((M + 15) / 16 + 3) / 4);
+    L.nbt = std::min(s.NB, 4);   // (1 or 2 blocks per wave measured no better: 93.0 / 92.7 k vs 93.0 k frames/s)
+    if (gx < 512 && L.nbt > 2) L.nbt = 2;  // more workgroups for the low-resolution layers
+    if (gx < 128) L.nbt = 1;
+    L.grid = dim3(gx, (s.NB + L.nbt - 1) / L.nbt);
+  }
+  return L;
+}
+static int launch_pw_step(const vbt_model* m, const Step& s, int B, hipStream_t st, const int8_t* x, const int8_t* res, int8_t* out) {
+  const PwLaunch L = resolve_pw(m, s, s.variant, B);
+  if (L.rc) return L.report();
+  const OpRec& pop = m->ops[s.res_op >= 0 ? s.p_op : s.op];
+  const TensorRec& tpo = m->tensors[pop.output];
+  const Epi e{s.bias, s.mult, tpo.zero_point, pop.act_min, pop.act_max, make_rq(tpo.zero_point, pop.act_min, pop.act_max)};
+  const ResArgs ra{res, s.addq};
+  const long M = (long)B * tpo.h * tpo.w;
+  const int K = m->tensors[pop.inputs[0]].c, N = tpo.c;
+#define PW(KERNEL, LDS) KERNEL<<<L.grid, 256, LDS, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB)
+#define PW_A(KS) (L.ms == 2 ? pw_a_kernel<KS, 2><<<L.grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, N, s.NB, L.nb_per_y) \
+                            : pw_a_kernel<KS, 1><<<L.grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, N, s.NB, L.nb_per_y))
+  switch (L.form) {
+    case PW_A: if (s.KS64 == 1) PW_A(1); else if (s.KS64 == 2) PW_A(2); else if (s.KS64 == 3) PW_A(3); else PW_A(4); break;
+    case PW_D: if (L.ms == 2) PW(pw_d_kernel<2>, 0); else PW(pw_d_kernel<1>, 0); break;
+    case PW_C: if (L.ms == 2) PW((pw_c_kernel<1, 2>), 0); else PW((pw_c_kernel<1, 1>), 0); break;
+    case PW_E:
+      if (L.ms == 2) { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<2, 4>); PW((pw_e_kernel<2, 4>), L.lds); }
+      else { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<1, 4>); PW((pw_e_kernel<1, 4>), L.lds); }
+      break;
+    case PW_B:
+      if (L.nbt == 1) PW(pw_b_kernel<1>, 0); else if (L.nbt == 2) PW(pw_b_kernel<2>, 0); else if (L.nbt == 3) PW(pw_b_kernel<3>, 0); else PW(pw_b_kernel<4>, 0);
+      break;
+  }
+#undef PW
+#undef PW_A
+  return VBT_OK;
 }
 
-static bool ppw2_fits(const vbt_model* m, const Step& st) {
-  const OpRec& dop = m->ops[st.d_op];
-  const int TX = 16, TY = 8;   // the 128-pixel kernels are DW64 (fused_block.h): 16 x 8 tiles only
-  if (st.fa.OW < TX || st.fa.OH < TY || !st.fa.wd64) return false;
-  const int TXp = TX;
-  const int NPh = ((TXp - 1) * dop.stride + dop.k) * ((TY - 1) * dop.stride + dop.k);
-  return ((NPh * st.fa.T0S + 15) & ~15) + ((NPh * FB_EST + 15) & ~15) + 128 * FB_DST <= 64 * 1024;
+// stand-alone depthwise conv: 0 = one output row x 4 columns per lane, 100 / 101 = LDS tiles, chunk-parallel (101: depthwise on the
+// matrix pipe), anything else = column walker with `variant` output rows per lane (-1: rows chosen by the map size)
+enum DwForm { DW_ROW, DW_COL, DW_TILE };
+struct DwLaunch : Verdict {   // tile geometry (DW_TILE), rows per lane and row segments (DW_COL), lanes (DW_ROW / DW_COL)
+  DwForm form = DW_COL; bool mdw = false; int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0, lds = 0, rows = 0, nseg = 0; long total = 0; dim3 grid;
+};
+static DwLaunch resolve_dw(const vbt_model* m, const Step& s, int variant, int B) {
+  DwLaunch L;
+  const OpRec& op = m->ops[s.op];
+  const TensorRec& to = m->tensors[op.output];
+  if (variant == 100 || variant == 101) {
+    L.form = DW_TILE; L.mdw = variant == 101;
+    choose_tile(to.h, to.w, op.k, op.stride, false, &L.TX, &L.TY);
+    L.tiles_x = (to.w + L.TX - 1) / L.TX;
+    L.tiles_y = (to.h + L.TY - 1) / L.TY;
+    const int TXp = (L.TX + 3) & ~3;
+    L.lds = ((TXp - 1) * op.stride + op.k) * ((L.TY - 1) * op.stride + op.k) * 80;
+    L.grid = dim3((unsigned)((long)B * L.tiles_x * L.tiles_y), (unsigned)((to.c + 63) / 64));
+  } else if (variant == 0) {
+    L.form = DW_ROW;
+    L.total = (long)B * to.h * ((to.w + 3) / 4) * (to.c / 4);
+    L.grid = dim3((unsigned)((L.total + 255) / 256));
+  } else {
+    const long per_seg = (long)B * ((to.w + 3) / 4) * (to.c / 4);
+    L.rows = std::min(variant > 0 ? variant : (int)std::min<long>(std::max<long>(to.h * per_seg / 400000, 1), 16), to.h);
+    L.nseg = (to.h + L.rows - 1) / L.rows;
+    L.total = per_seg * L.nseg;
+    L.grid = dim3((unsigned)((L.total + 255) / 256));
+  }
+  return L;
+}
+static int launch_dw_step(const vbt_model* m, const Step& s, int B, hipStream_t st, const int8_t* x, int8_t* out, const Epi& e) {
+  const DwLaunch L = resolve_dw(m, s, s.variant, B);
+  if (L.rc) return L.report();
+  const OpRec& op = m->ops[s.op];
+  const TensorRec& ti = m->tensors[op.inputs[0]];
+  const TensorRec& to = m->tensors[op.output];
+  if (L.form == DW_TILE) {
+    DwTileArgs a;
+    a.x = x; a.out = out; a.wf = s.wf; a.bias = s.bias; a.mult = s.mult; a.wdm = s.wdm; a.bdm = s.bdm; a.mdm = s.mdm;
+    a.H = ti.h; a.W = ti.w; a.C = to.c; a.OH = to.h; a.OW = to.w; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
+    a.TX = L.TX; a.TY = L.TY; a.tiles_x = L.tiles_x; a.tiles_y = L.tiles_y; a.zx = ti.zero_point; a.rq = e.rq;
+    return launch_dw_tile(a, op.k, op.stride, L.mdw, L.grid, L.lds, st);
+  }
+  const unsigned pb = (unsigned)((128 + ti.zero_point) & 255);
+  const unsigned pad4 = pb | (pb << 8) | (pb << 16) | (pb << 24);
+#define DW_LAUNCH(KERNEL, ...)                                                                    \
+  do {                                                                                            \
+    if (op.k == 3 && op.stride == 1) KERNEL<3, 1><<<L.grid, 256, 0, st>>>(__VA_ARGS__);           \
+    else if (op.k == 3 && op.stride == 2) KERNEL<3, 2><<<L.grid, 256, 0, st>>>(__VA_ARGS__);      \
+    else if (op.k == 5 && op.stride == 1) KERNEL<5, 1><<<L.grid, 256, 0, st>>>(__VA_ARGS__);      \
+    else KERNEL<5, 2><<<L.grid, 256, 0, st>>>(__VA_ARGS__);                                       \
+  } while (0)
+  if (L.form == DW_ROW) DW_LAUNCH(dw_kernel, x, s.wf, e, out, L.total, ti.h, ti.w, to.c, to.h, to.w, op.pad_t, op.pad_l, pad4);
+  else DW_LAUNCH(dw_col_kernel, x, s.wf, e, out, L.total, ti.h, ti.w, to.c, to.h, to.w, op.pad_t, op.pad_l, pad4, L.rows, L.nseg);
+#undef DW_LAUNCH
+  return VBT_OK;
 }
 
-// Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major).
-// Whole-image MBConv kernel (image_block.h): eligibility and launch geometry.
-struct ImageGeom { int PW, PH, NB, maxu, lds; bool ok; };
-static ImageGeom image_geom(const vbt_model* m, const Step& s) {
-  ImageGeom g{0, 0, 0, 0, 0, false};
-  if (s.family != F_MBCONV) return g;
+// fused MBConv / SeparableConv / BiFPN node on LDS tiles (fused_block.h) or, MBConv on a low-resolution map, one workgroup per image
+// (image_block.h).  Variant bits: 1 = depthwise on the matrix pipe (else VALU), 2 = half-height tile, 4 = whole image, 8 = 48-channel
+// chunks, 16 = 128-pixel (16 x 8) tiles; a bit whose conditions the step does not meet is ignored, except that the whole-image and
+// 128-pixel kernels refuse a step they do not fit.
+struct FusedPlan : Verdict {
+  bool image = false; int PW = 0, PH = 0, NB = 0, maxu = 0;   // whole-image kernel: padded map, output channel blocks, work units per wave
+  int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0; FusedLaunch L{};   // (whole image: k, stride and lds_bytes of L)
+};
+static FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   const FusedArgs& a = s.fa;
   const OpRec& dop = m->ops[s.d_op];
-  const int HW = a.H * a.W, OHW = a.OH * a.OW;
-  if (HW > 400 || OHW > 400) return g;
-  g.PH = std::max((a.OH - 1) * dop.stride + dop.k, a.pad_t + a.H);
-  g.PW = std::max((a.OW - 1) * dop.stride + dop.k, a.pad_l + a.W);
-  g.NB = (a.Cout + 63) / 64;
-  const int NPGo = (OHW + 15) / 16;
-  const int units = (NPGo * g.NB + IB_WAVES - 1) / IB_WAVES;
-  g.maxu = units <= 2 ? 2 : units <= 3 ? 3 : 4;
-  g.lds = ((HW * a.T0S + 15) & ~15) + g.PH * g.PW * FB_EST + NPGo * 16 * FB_DST + s.ib.bytes;
-  g.ok = s.ib.data != nullptr && units <= 4 && g.lds <= 160 * 1024 && s.ib.bytes <= 16 * IB_NPF * IB_THREADS;
-  return g;
+  const int k = dop.k, stride = dop.stride;
+  const bool ex = s.family == F_MBCONV, ks12 = a.KSe == 1 || a.KSe == 2;
+  int var = variant;
+  if (var < 0) {   // heuristic default: what the plan-shaping flags ask for, where it applies
+    var = ((m->flags & VBT_MODEL_IMAGE_BLOCKS) && !resolve_fused(m, s, 5, B).rc) ? 5 : ((m->flags & VBT_MODEL_CHUNK48) ? 9 : 1);
+    const FusedPlan p17 = (m->flags & VBT_MODEL_TILE128) ? resolve_fused(m, s, 17, B) : FusedPlan{};
+    if (!p17.rc && p17.L.ppw2) var |= 16;
+  }
+  const bool mdw = var & 1, half = var & 2;
+  const bool nt3 = (var & 8) && mdw && a.nch3 > 0 && s.nbp <= 2 && a.KSe >= 1 && a.KSe <= 4;
+  FusedPlan p;
+  if (var & 4) {
+    const int HW = a.H * a.W, OHW = a.OH * a.OW;
+    if (!ex || HW > 400 || OHW > 400 || !s.ib.data) { p.refuse(VBT_ERR_ARG, "fused_mbconv: whole-image variant not applicable"); return p; }
+    p.image = true;
+    p.PH = std::max((a.OH - 1) * stride + k, a.pad_t + a.H);
+    p.PW = std::max((a.OW - 1) * stride + k, a.pad_l + a.W);
+    p.NB = (a.Cout + 63) / 64;
+    const int NPGo = (OHW + 15) / 16;
+    const int units = (NPGo * p.NB + IB_WAVES - 1) / IB_WAVES;
+    p.maxu = units <= 2 ? 2 : units <= 3 ? 3 : 4;
+    p.L.k = k; p.L.stride = stride; p.L.lds_bytes = ((HW * a.T0S + 15) & ~15) + p.PH * p.PW * FB_EST + NPGo * 16 * FB_DST + s.ib.bytes;
+    if (units > 4 || p.L.lds_bytes > 160 * 1024 || s.ib.bytes > 16 * IB_NPF * IB_THREADS) p.refuse(VBT_ERR_ARG, "fused_mbconv: whole-image variant not applicable");
+    return p;
+  }
+  p.TX = a.TX;
+  p.TY = half && a.TY >= 2 ? (a.TY + 1) / 2 : a.TY;
+  // 128-pixel tiles (PPW = 2): matrix-pipe depthwise on the 16x16x64 MFMA, register-resident expand weights (K <= 64), <= 128 output channels
+  const bool ppw2 = (var & 16) && ex && mdw && ks12 && s.nbp <= 2 && !half;
+  if (ppw2) { p.TX = 16; p.TY = 8; }
+  // otherwise 64-pixel tiles of exactly 8 x 8 outputs with the same limits take the 16x16x64 depthwise too (DW64)
+  const bool dw64 = ppw2 || (ex && mdw && a.wd64 && p.TX == 8 && p.TY == 8 && ks12 && s.nbp <= 2);
+  const int est = !ex ? 0 : !nt3 ? FB_EST : dw64 ? 48 : 72;   // E row bytes (fused_block.h: EST)
+  p.tiles_x = (a.OW + p.TX - 1) / p.TX;
+  p.tiles_y = (a.OH + p.TY - 1) / p.TY;
+  p.L = FusedLaunch{k, stride, s.nbp, ex, mdw, nt3, ppw2, dw64, fused_tile_lds(a, k, stride, p.TX, p.TY, est, ppw2 ? 2 : 1, s.nbp),
+                    (unsigned)((long)B * p.tiles_x * p.tiles_y)};
+  if (ppw2 && (a.OW < 16 || a.OH < 8 || !a.wd64)) p.refuse(VBT_ERR_ARG, "fused_mbconv: the 128-pixel variant needs maps of at least 16 x 8");
+  else if (ppw2 && p.L.lds_bytes > 64 * 1024) p.refuse(VBT_ERR_ARG, "fused_mbconv: 128-pixel tile needs %d bytes of LDS", p.L.lds_bytes);
+  return p;
 }
+static int launch_fused_step(const vbt_model* m, const Step& s, FusedArgs a, int B, hipStream_t st) {
+  const FusedPlan p = resolve_fused(m, s, s.variant, B);
+  if (p.rc) return p.report();
+  if (p.image) return launch_mbconv_image(a, s.ib, p.L.k, p.L.stride, p.maxu, p.PW, p.PH, p.NB, p.L.lds_bytes, B, st);
+  a.TX = p.TX; a.TY = p.TY; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
+  return launch_fused_block(a, p.L, st);
+}
+
+// expand + depthwise on whole images or row bands.  Variant: chunks per workgroup on the first form of the kernel (expdw_block.h),
+// 100 + chunks per workgroup on the second (expdw2_block.h) with 8 waves, 200 + chunks with 16 waves; -1: heuristic default
+struct ExpDwLaunch : Verdict {   // chunks per workgroup; second form: waves per workgroup, input pixel groups per wave
+  bool second = false; int cpw = 1, nw = 0, gpw = 0, lds = 0; unsigned grid = 0;
+};
+static ExpDwLaunch resolve_expdw(const vbt_model*, const Step& s, int variant, int B) {
+  // VBT_XD_VARIANT (tests): that variant for every step that supports it, whatever the plan says
+  static const int xd_force = getenv("VBT_XD_VARIANT") ? atoi(getenv("VBT_XD_VARIANT")) : -100;
+  if (xd_force != -100 && (xd_force < 100 || (s.xd2_ok && (xd_force < 200 ? s.xd2_gpw > 0 : s.xd2_gpw16 > 0)))) variant = std::min(xd_force, xd_force / 100 * 100 + s.xd.nchunks);
+  ExpDwLaunch L;
+  if (s.xd2_ok && (variant >= 100 || variant < 0)) {
+    if (variant >= 200 && s.xd2_gpw16 == 0) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the 16-wave form on a step that does not support it"); return L; }
+    if (variant >= 100 && variant < 200 && s.xd2_gpw == 0) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the 8-wave form on a step that does not support it"); return L; }
+    const ExpDw2Args& a = s.xd2;   // the second form
+    L.second = true;
+    L.nw = (variant >= 200 || (variant < 0 && s.xd2_gpw16 > 0)) ? 16 : 8;
+    L.gpw = L.nw == 16 ? s.xd2_gpw16 : s.xd2_gpw;
+    L.cpw = std::min(variant >= 100 ? variant % 100 : std::max(1, (a.nchunks * a.nbands * B + 1023) / 1024), a.nchunks);   // default: about four workgroups per CU
+    L.grid = (unsigned)(B * ((a.nchunks + L.cpw - 1) / L.cpw) * a.nbands);
+    L.lds = s.xd2_lds;
+    return L;
+  }
+  if (variant >= 100) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the second kernel form on a step that does not support it"); return L; }
+  const ExpDwArgs& a = s.xd;
+  L.cpw = variant > 0 ? variant : std::max(1, (a.nchunks * a.nbands * B + 511) / 512);   // default: about two workgroups per CU
+  L.grid = (unsigned)(B * ((a.nchunks + L.cpw - 1) / L.cpw) * a.nbands);
+  L.lds = s.lds_bytes;
+  return L;
+}
+static int launch_expdw_step(const vbt_model* m, const Step& s, int B, hipStream_t st, const int8_t* x, int8_t* out) {
+  const ExpDwLaunch L = resolve_expdw(m, s, s.variant, B);
+  if (L.rc) return L.report();
+  const OpRec& dop = m->ops[s.d_op];
+  if (L.second) {
+    ExpDw2Args a = s.xd2;
+    a.x = x; a.out = out; a.cpw = L.cpw;
+    return launch_expdw2(a, dop.k, dop.stride, (a.Cin + 63) / 64, L.nw, L.gpw, L.grid, L.lds, st);
+  }
+  ExpDwArgs a = s.xd;
+  a.x = x; a.out = out; a.cpw = L.cpw;
+  return launch_expdw(a, dop.k, dop.stride, (a.Cin + 63) / 64, L.grid, L.lds, st);
+}
+
+// Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major): the batch-offset pointers here, the
+// variant and the launch in the family's own function above.
 static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_t* frames, float* boxes, float* scores,
                        float* classes, int* counts, int boff = 0) {
   if (m->pool_dirty) { const int rc = flush_uploads(m); if (rc) return rc; }
   const OpRec& op = m->ops[s.op];
   const TensorRec& to = m->tensors[op.output];
   auto TP = [&](int t) { return m->tptr[t] + (size_t)boff * m->telems[t]; };
-  frames += (size_t)boff * m->hdr.image_size * m->hdr.image_size * 3;
-  boxes += (size_t)boff * m->hdr.max_detections * 4;
-  scores += (size_t)boff * m->hdr.max_detections;
-  classes += (size_t)boff * m->hdr.max_detections;
-  counts += boff;
+  const uint8_t* frame0 = frames + (size_t)boff * m->hdr.image_size * m->hdr.image_size * 3;
   int8_t* out = TP(op.output);
-  Epi e{s.bias, s.mult, to.zero_point, op.act_min, op.act_max, make_rq(to.zero_point, op.act_min, op.act_max)};   // (F_PW rebuilds it from its conv op)
+  // start of every member's workgroups in a grid of several problems (F_MULTI, F_BAND); start[n] = the grid
+  auto member_tiles = [&](auto tiles_of) {
+    MultiTiles mt;
+    mt.n = (int)s.members.size();
+    mt.start[0] = 0;
+    for (int i = 0; i < mt.n; i++) mt.start[i + 1] = mt.start[i] + B * tiles_of(s.members[i]);
+    return mt;
+  };
+  const Epi e{s.bias, s.mult, to.zero_point, op.act_min, op.act_max, make_rq(to.zero_point, op.act_min, op.act_max)};   // (F_PW builds its own from its conv op)
   switch (s.family) {
     case F_STEM: {
       const TensorRec& ti = m->tensors[op.inputs[0]];
       long M = (long)B * to.h * to.w;
       dim3 grid((unsigned)((M + 63) / 64));
-      stem_kernel<<<grid, 256, 0, st>>>(frames, s.wp, e, out, M, ti.h, ti.w, to.h, to.w, to.c, op.pad_t, op.pad_l, ti.zero_point);
-      break;
+      stem_kernel<<<grid, 256, 0, st>>>(frame0, s.wp, e, out, M, ti.h, ti.w, to.h, to.w, to.c, op.pad_t, op.pad_l, ti.zero_point);
+      return VBT_OK;
     }
     case F_PW: {
-      if (!s.members.empty()) {   // several convs in one launch (merge_side_convs)
-        if (boff != 0) { set_error("merged pointwise convs: sub-batch streams are not supported (VBT_SUBSTREAMS)"); return VBT_ERR_ARG; }
-        PwMulti pm;
-        memset(&pm, 0, sizeof(pm));
-        const int nconv = (int)s.members.size() - (s.nbp ? 2 : 0);
-        int acc = 0;
-        for (int i = 0; i < nconv; i++) {
-          const Step& ms = s.members[i];
-          const OpRec& pop = m->ops[ms.op];
-          const TensorRec& ti = m->tensors[pop.inputs[0]];
-          const TensorRec& tpo = m->tensors[pop.output];
-          PwProb& q = pm.p[i];
-          q.x = TP(pop.inputs[0]); q.wp = ms.wp64; q.bias = ms.bias; q.mult = ms.mult; q.out = TP(pop.output);
-          q.rq = make_rq(tpo.zero_point, pop.act_min, pop.act_max);
-          q.K = ti.c; q.KS = ms.KS64; q.N = tpo.c; q.NB = ms.NB;
-          pm.start[i] = acc;
-          if (i == 0 && s.nbp) {
-            const OpRec &p1 = m->ops[s.members[nconv].op], &p2 = m->ops[s.members[nconv + 1].op];
-            const TensorRec &t1 = m->tensors[p1.output], &t2 = m->tensors[p2.output];
-            q.M = tpo.h * tpo.w;
-            q.pool1 = TP(p1.output); q.pool2 = TP(p2.output);
-            q.H = tpo.h; q.W = tpo.w; q.H1 = t1.h; q.W1 = t1.w; q.pt1 = p1.pad_t; q.pl1 = p1.pad_l;
-            q.H2 = t2.h; q.W2 = t2.w; q.pt2 = p2.pad_t; q.pl2 = p2.pad_l;
-            acc += B;
-          } else {
-            q.M = B * tpo.h * tpo.w;
-            acc += ((q.M + 63) / 64) * q.NB;
-          }
-        }
-        pm.n = nconv;
-        pm.start[nconv] = acc;
-        for (int i = nconv + 1; i <= PWM_MAX; i++) pm.start[i] = acc;
-        pw_multi_kernel<<<dim3((unsigned)acc), 256, s.nbp ? s.lds_bytes : 0, st>>>(pm);
-        break;
-      }
-      // op = the op whose output is written: the conv itself, or the residual ADD evaluated in its epilogue (res_op)
-      const OpRec& pop = m->ops[s.res_op >= 0 ? s.p_op : s.op];
-      const TensorRec& ti = m->tensors[pop.inputs[0]];
-      const TensorRec& tpo = m->tensors[pop.output];
-      const int8_t* x = TP(pop.inputs[0]);
-      e = Epi{s.bias, s.mult, tpo.zero_point, pop.act_min, pop.act_max, make_rq(tpo.zero_point, pop.act_min, pop.act_max)};
-      ResArgs ra{nullptr, s.addq};
-      if (s.res_op >= 0) ra.res = TP(m->ops[s.res_op].inputs[1]);   // ADD(conv output, skip): planner guarantees the order
-      long M = (long)B * tpo.h * tpo.w;
-      int K = ti.c, N = tpo.c;
-      // VBT_PW_VARIANT (tests): the kernel variant of every pointwise conv with K > 256, whatever the plan says
-      static const int pw_force = getenv("VBT_PW_VARIANT") ? atoi(getenv("VBT_PW_VARIANT")) : -100;
-      const int pw_variant = (pw_force != -100 && s.KS64 > 4) ? pw_force : s.variant;
-      if (s.KS64 <= 4) {
-        int MS = s.variant >= 0 ? (s.variant & 1) + 1 : (M >= 32768 ? 2 : 1);
-        long waves = (M + 16 * MS - 1) / (16 * MS);
-        unsigned gx = (unsigned)((waves + 3) / 4);
-        int ysplit = 1;
-        while (gx * ysplit < 1024 && ysplit < s.NB) ysplit++;
-        int nb_per_y = (s.NB + ysplit - 1) / ysplit;
-        ysplit = (s.NB + nb_per_y - 1) / nb_per_y;
-        dim3 grid(gx, ysplit);
-        switch (s.KS64) {
-          case 1: launch_pw_a<1>(MS, grid, st, x, s.wp64, e, ra, out, M, K, N, s.NB, nb_per_y); break;
-          case 2: launch_pw_a<2>(MS, grid, st, x, s.wp64, e, ra, out, M, K, N, s.NB, nb_per_y); break;
-          case 3: launch_pw_a<3>(MS, grid, st, x, s.wp64, e, ra, out, M, K, N, s.NB, nb_per_y); break;
-          default: launch_pw_a<4>(MS, grid, st, x, s.wp64, e, ra, out, M, K, N, s.NB, nb_per_y); break;
-        }
-      } else if (pw_variant == 3 || pw_variant == 4) {  // weights shared through LDS, 64 (variant 3) or 128 (variant 4) pixels per workgroup
-        const int ms = pw_variant - 2;
-        dim3 grid((unsigned)((M + 64 * ms - 1) / (64 * ms)), (unsigned)s.NB);
-        if (ms == 2) pw_d_kernel<2><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-        else pw_d_kernel<1><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-      } else if (pw_variant == 5 || pw_variant == 6) {  // the block's whole weight panel in LDS, a K loop without barriers (pw_e_kernel), 64 / 128 pixels per workgroup
-        const int ms = pw_variant - 4;
-        const int lds = s.KS64 * 4096;
-        if (lds > 160 * 1024) { set_error("pw_conv: a weight panel of %d bytes does not fit the LDS", lds); return VBT_ERR_ARG; }
-        dim3 grid((unsigned)((M + 64 * ms - 1) / (64 * ms)), (unsigned)s.NB);
-        if (ms == 2) {
-          if (lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<2, 4>);
-          pw_e_kernel<2, 4><<<grid, 256, lds, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
+      if (s.members.empty())   // op = the op whose output is written: the conv itself, or the residual ADD evaluated in its epilogue (res_op)
+        return launch_pw_step(m, s, B, st, TP(m->ops[s.res_op >= 0 ? s.p_op : s.op].inputs[0]),
+                              s.res_op >= 0 ? TP(m->ops[s.res_op].inputs[1]) : nullptr, out);   // ADD(conv output, skip): planner guarantees the order
+      // several convs in one launch (merge_side_convs)
+      if (boff != 0) { set_error("merged pointwise convs: sub-batch streams are not supported (VBT_SUBSTREAMS)"); return VBT_ERR_ARG; }
+      PwMulti pm;
+      memset(&pm, 0, sizeof(pm));
+      const int nconv = (int)s.members.size() - (s.nbp ? 2 : 0);
+      int acc = 0;
+      for (int i = 0; i < nconv; i++) {
+        const Step& ms = s.members[i];
+        const OpRec& pop = m->ops[ms.op];
+        const TensorRec& ti = m->tensors[pop.inputs[0]];
+        const TensorRec& tpo = m->tensors[pop.output];
+        PwProb& q = pm.p[i];
+        q.x = TP(pop.inputs[0]); q.wp = ms.wp64; q.bias = ms.bias; q.mult = ms.mult; q.out = TP(pop.output);
+        q.rq = make_rq(tpo.zero_point, pop.act_min, pop.act_max);
+        q.K = ti.c; q.KS = ms.KS64; q.N = tpo.c; q.NB = ms.NB;
+        pm.start[i] = acc;
+        if (i == 0 && s.nbp) {
+          const OpRec &p1 = m->ops[s.members[nconv].op], &p2 = m->ops[s.members[nconv + 1].op];
+          const TensorRec &t1 = m->tensors[p1.output], &t2 = m->tensors[p2.output];
+          q.M = tpo.h * tpo.w;
+          q.pool1 = TP(p1.output); q.pool2 = TP(p2.output);
+          q.H = tpo.h; q.W = tpo.w; q.H1 = t1.h; q.W1 = t1.w; q.pt1 = p1.pad_t; q.pl1 = p1.pad_l;
+          q.H2 = t2.h; q.W2 = t2.w; q.pt2 = p2.pad_t; q.pl2 = p2.pad_l;
+          acc += B;
         } else {
-          if (lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<1, 4>);
-          pw_e_kernel<1, 4><<<grid, 256, lds, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-        }
-      } else if (pw_variant == 2) {  // split-K over the 4 waves of a workgroup
-        // one 64-channel block per workgroup (16 KB of LDS for the cross-wave reduction, twice the workgroups) rather than two
-        // (32 KB): +1.4 % end to end with three forwards in flight - the workgroups of one launch then fit the CUs in one round
-        static const int nbt_max = getenv("VBT_PWC_NBT") ? atoi(getenv("VBT_PWC_NBT")) : 1;
-        static const int ms_env = getenv("VBT_PWC_MS") ? atoi(getenv("VBT_PWC_MS")) : 2;
-        int nbt = std::min(s.NB, nbt_max);
-        // two pixel groups per workgroup (half the weight bytes through L1) as long as the grid still has two workgroups per CU
-        const int ms = (ms_env >= 2 && nbt == 1 && ((M + 31) / 32) * s.NB >= 512) ? 2 : 1;
-        dim3 grid((unsigned)((M + 16 * ms - 1) / (16 * ms)), (unsigned)((s.NB + nbt - 1) / nbt));
-        if (ms == 2) pw_c_kernel<1, 2><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-        else if (nbt == 1) pw_c_kernel<1, 1><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-        else pw_c_kernel<2, 1><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB);
-      } else {
-        long waves = (M + 15) / 16;
-        unsigned gx = (unsigned)((waves + 3) / 4);
-        int nbt = std::min(s.NB, 4);   // (1 or 2 blocks per wave measured no better: 93.0 / 92.7 k vs 93.0 k frames/s)
-        if (gx < 512 && nbt > 2) nbt = 2;  // more workgroups for the low-resolution layers
-        if (gx < 128) nbt = 1;
-        dim3 grid(gx, (s.NB + nbt - 1) / nbt);
-        switch (nbt) {
-          case 1: pw_b_kernel<1><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB); break;
-          case 2: pw_b_kernel<2><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB); break;
-          case 3: pw_b_kernel<3><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB); break;
-          default: pw_b_kernel<4><<<grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB); break;
+          q.M = B * tpo.h * tpo.w;
+          acc += ((q.M + 63) / 64) * q.NB;
         }
       }
-      break;
+      pm.n = nconv;
+      pm.start[nconv] = acc;
+      for (int i = nconv + 1; i <= PWM_MAX; i++) pm.start[i] = acc;
+      pw_multi_kernel<<<dim3((unsigned)acc), 256, s.nbp ? s.lds_bytes : 0, st>>>(pm);
+      return VBT_OK;
     }
-    case F_DW: {
-      const TensorRec& ti = m->tensors[op.inputs[0]];
-      const int8_t* x = TP(op.inputs[0]);
-      int C = to.c;
-      unsigned pb = (unsigned)((128 + ti.zero_point) & 255);
-      unsigned pad4 = pb | (pb << 8) | (pb << 16) | (pb << 24);
-      if (s.variant == 100 || s.variant == 101) {  // LDS-tiled, chunk-parallel (101: depthwise on the matrix pipe)
-        DwTileArgs a;
-        a.x = x; a.out = out; a.wf = s.wf; a.bias = s.bias; a.mult = s.mult;
-        a.wdm = s.wdm; a.bdm = s.bdm; a.mdm = s.mdm;
-        a.H = ti.h; a.W = ti.w; a.C = C; a.OH = to.h; a.OW = to.w; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
-        choose_tile(to.h, to.w, op.k, op.stride, false, &a.TX, &a.TY);
-        a.tiles_x = (to.w + a.TX - 1) / a.TX;
-        a.tiles_y = (to.h + a.TY - 1) / a.TY;
-        a.zx = ti.zero_point;
-        a.rq = e.rq;
-        const int TXp = (a.TX + 3) & ~3;
-        const int NPh = ((TXp - 1) * op.stride + op.k) * ((a.TY - 1) * op.stride + op.k);
-        dim3 grid((unsigned)((long)B * a.tiles_x * a.tiles_y), (unsigned)((C + 63) / 64));
-        const int lds = NPh * 80;
-        launch_dw_tile(a, op.k, op.stride, s.variant == 101, grid, lds, st);
-      } else if (s.variant == 0) {  // one output row x 4 columns per lane
-        long total = (long)B * to.h * ((to.w + 3) / 4) * (C / 4);
-        dim3 grid((unsigned)((total + 255) / 256));
-#define DW_LAUNCH(KK, S) dw_kernel<KK, S><<<grid, 256, 0, st>>>(x, s.wf, e, out, total, ti.h, ti.w, C, to.h, to.w, op.pad_t, op.pad_l, pad4)
-        if (op.k == 3 && op.stride == 1) DW_LAUNCH(3, 1);
-        else if (op.k == 3 && op.stride == 2) DW_LAUNCH(3, 2);
-        else if (op.k == 5 && op.stride == 1) DW_LAUNCH(5, 1);
-        else DW_LAUNCH(5, 2);
-#undef DW_LAUNCH
-      } else {               // column walker, `rows` output rows per lane
-        const int XR = (to.w + 3) / 4;
-        long per_seg = (long)B * XR * (C / 4);
-        int rows = s.variant > 0 ? s.variant : (int)std::min<long>(std::max<long>(to.h * per_seg / 400000, 1), 16);
-        rows = std::min(rows, to.h);
-        int nseg = (to.h + rows - 1) / rows;
-        long total = per_seg * nseg;
-        dim3 grid((unsigned)((total + 255) / 256));
-#define DW_LAUNCH(KK, S) dw_col_kernel<KK, S><<<grid, 256, 0, st>>>(x, s.wf, e, out, total, ti.h, ti.w, C, to.h, to.w, op.pad_t, op.pad_l, pad4, rows, nseg)
-        if (op.k == 3 && op.stride == 1) DW_LAUNCH(3, 1);
-        else if (op.k == 3 && op.stride == 2) DW_LAUNCH(3, 2);
-        else if (op.k == 5 && op.stride == 1) DW_LAUNCH(5, 1);
-        else DW_LAUNCH(5, 2);
-#undef DW_LAUNCH
-      }
-      break;
-    }
+    case F_DW:
+      return launch_dw_step(m, s, B, st, TP(op.inputs[0]), out, e);
     case F_ADD: {
       long n4 = (long)B * to.h * to.w * to.c / 4;
       add_kernel<<<dim3((unsigned)((n4 + 1023) / 1024)), 256, 0, st>>>(TP(op.inputs[0]), TP(op.inputs[1]), s.addq, out, n4);
-      break;
+      return VBT_OK;
     }
     case F_MAXPOOL: {
       const TensorRec& ti = m->tensors[op.inputs[0]];
       long total = (long)B * to.h * to.w * (to.c / 4);
       maxpool_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(TP(op.inputs[0]), out, total, ti.h, ti.w, ti.c,
                                                                              to.h, to.w, op.pad_t, op.pad_l);
-      break;
+      return VBT_OK;
     }
     case F_RESIZE: {
       const TensorRec& ti = m->tensors[op.inputs[0]];
       long total = (long)B * to.h * to.w * (to.c / 4);
       resize_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(TP(op.inputs[0]), out, total, ti.h, ti.w, ti.c,
                                                                             to.h, to.w);
-      break;
+      return VBT_OK;
     }
     case F_MULTI: {
       if (boff != 0) {  // side-stream sub-batches: pointers differ, launch the members one by one
         for (const Step& ms : s.members) {
           Step t = ms;
           t.variant = s.variant;
-          int rc = launch_step(m, t, B, st, frames - (size_t)boff * m->hdr.image_size * m->hdr.image_size * 3, boxes - (size_t)boff * m->hdr.max_detections * 4,
-                               scores - (size_t)boff * m->hdr.max_detections, classes - (size_t)boff * m->hdr.max_detections, counts - boff, boff);
+          const int rc = launch_step(m, t, B, st, frames, boxes, scores, classes, counts, boff);
           if (rc) return rc;
         }
-        break;
+        return VBT_OK;
       }
-      MultiTiles mt;
-      mt.n = (int)s.members.size();
-      int acc = 0;
-      for (int i = 0; i < mt.n; i++) {
-        mt.start[i] = acc;
-        acc += B * s.members[i].fa.tiles_x * s.members[i].fa.tiles_y;
-      }
-      mt.start[mt.n] = acc;
+      const MultiTiles mt = member_tiles([](const Step& ms) { return ms.fa.tiles_x * ms.fa.tiles_y; });
       const OpRec& dop = m->ops[s.d_op];
-      dim3 grid((unsigned)acc);
-      const bool mdw = s.variant != 0;
-      { const int rc = launch_fused_multi(s.d_multi, mt, dop.k, dop.stride, s.nbp, mdw, s.lds_bytes, (unsigned)acc, st); if (rc) return rc; }
-      break;
+      return launch_fused_multi(s.d_multi, mt, dop.k, dop.stride, s.nbp, s.variant != 0, s.lds_bytes, (unsigned)mt.start[mt.n], st);
     }
     case F_MBCONV:
     case F_NODE:
@@ -2048,118 +2142,21 @@ static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const
       a.x = s.e_op >= 0 ? TP(m->ops[s.e_op].inputs[0]) : TP(m->ops[s.d_op].inputs[0]);
       for (int j = 0; j < 3; j++) a.src[j] = s.src_tensor[j] >= 0 ? TP(s.src_tensor[j]) : nullptr;
       a.out = out;
-      const OpRec& dop = m->ops[s.d_op];
-      dim3 grid((unsigned)((long)B * a.tiles_x * a.tiles_y));
-      const bool ex = s.family == F_MBCONV;
-      // (the tile option of the variant is applied below, before the launch macros use `grid` / `lds_bytes`)
-      // variant bit 0: depthwise on the matrix pipe (default) / VALU; bits 1..: 0 = heuristic tile, 1 = half-height tile
-      int var = s.variant < 0 ? (((m->flags & VBT_MODEL_IMAGE_BLOCKS) && image_geom(m, s).ok) ? 5 : ((m->flags & VBT_MODEL_CHUNK48) ? 9 : 1)) : s.variant;
-      if (s.variant < 0 && (m->flags & VBT_MODEL_TILE128) && s.family == F_MBCONV && s.nbp <= 2 && (a.KSe == 1 || a.KSe == 2) && ppw2_fits(m, s)) var |= 16;
-      const bool mdw = var & 1;
-      const bool nt3 = (var & 8) && mdw && a.nch3 > 0 && s.nbp <= 2 && a.KSe >= 1 && a.KSe <= 4;  // 48-channel chunks
-      if (var & 4) {  // one workgroup per image (low-resolution blocks)
-        const ImageGeom ig = image_geom(m, s);
-        if (!ig.ok) { set_error("fused_mbconv: whole-image variant not applicable"); return VBT_ERR_ARG; }
-        launch_mbconv_image(a, s.ib, dop.k, dop.stride, ig.maxu, ig.PW, ig.PH, ig.NB, ig.lds, B, st);
-        break;
-      }
-      int lds_bytes = s.lds_bytes;
-      if (((var >> 1) & 1) == 1 && a.TY >= 2) {
-        a.TY = (a.TY + 1) / 2;
-        a.tiles_y = (a.OH + a.TY - 1) / a.TY;
-        const int TXp_ = (a.TX + 3) & ~3;
-        const int NPh_ = ((TXp_ - 1) * dop.stride + dop.k) * ((a.TY - 1) * dop.stride + dop.k);
-        lds_bytes = ((NPh_ * a.T0S + 15) & ~15) + (s.family == F_MBCONV ? NPh_ * FB_EST : 0) + 64 * FB_DST;
-        if (s.family != F_MBCONV && a.nchunks == 1 && s.nbp <= 2) lds_bytes += s.nbp * (4096 + 512);
-        grid = dim3((unsigned)((long)B * a.tiles_x * a.tiles_y));
-      }
-      if (nt3) {  // 72-byte E rows (fused_block.h)
-        const int TXp_ = (a.TX + 3) & ~3;
-        const int NPh_ = ((TXp_ - 1) * dop.stride + dop.k) * ((a.TY - 1) * dop.stride + dop.k);
-        lds_bytes = ((NPh_ * a.T0S + 15) & ~15) + ((NPh_ * 72 + 15) & ~15) + 64 * FB_DST;
-      }
-      // variant bit 4: 128-pixel tiles (PPW = 2), matrix-pipe depthwise, register-resident expand weights (K <= 64), <= 128 output channels
-      const bool ppw2 = (var & 16) && ex && mdw && (a.KSe == 1 || a.KSe == 2) && s.nbp <= 2 && !((var >> 1) & 1);
-      if (ppw2) {
-        a.TX = 16; a.TY = 8;
-        a.tiles_x = (a.OW + a.TX - 1) / a.TX;
-        a.tiles_y = (a.OH + a.TY - 1) / a.TY;
-        const int TXp_ = (a.TX + 3) & ~3;
-        const int NPh_ = ((TXp_ - 1) * dop.stride + dop.k) * ((a.TY - 1) * dop.stride + dop.k);
-        lds_bytes = ((NPh_ * a.T0S + 15) & ~15) + ((NPh_ * (nt3 ? 48 : FB_EST) + 15) & ~15) + 128 * FB_DST;
-        grid = dim3((unsigned)((long)B * a.tiles_x * a.tiles_y));
-        if (a.OW < 16 || a.OH < 8 || !a.wd64) { set_error("fused_mbconv: the 128-pixel variant needs maps of at least 16 x 8"); return VBT_ERR_ARG; }
-        if (lds_bytes > 64 * 1024) { set_error("fused_mbconv: 128-pixel tile needs %d bytes of LDS", lds_bytes); return VBT_ERR_ARG; }
-        return launch_fused_block(a, FusedLaunch{dop.k, dop.stride, s.nbp, true, true, nt3, true, true, lds_bytes, grid.x}, st);
-        break;
-      }
-      // 64-pixel tiles of exactly 8 x 8 outputs, K <= 64, <= 128 output channels: depthwise on the 16x16x64 MFMA (DW64)
-      const bool dw64 = ex && mdw && a.wd64 && a.TX == 8 && a.TY == 8 && (a.KSe == 1 || a.KSe == 2) && s.nbp <= 2 && !getenv("VBT_NO_DW64");
-      if (dw64 && nt3) {   // E rows are 48 bytes in the 48-channel DW64 kernels
-        const int NPh_ = ((8 - 1) * dop.stride + dop.k) * ((8 - 1) * dop.stride + dop.k);
-        lds_bytes = ((NPh_ * a.T0S + 15) & ~15) + ((NPh_ * 48 + 15) & ~15) + 64 * FB_DST;
-      }
-      { const int rc = launch_fused_block(a, FusedLaunch{dop.k, dop.stride, s.nbp, ex, mdw, nt3, false, dw64, lds_bytes, grid.x}, st); if (rc) return rc; }
-      break;
+      return launch_fused_step(m, s, a, B, st);
     }
     case F_BAND: {
       if (boff != 0) { set_error("fused_sepconv_band: sub-batch streams are not supported (VBT_SUBSTREAMS)"); return VBT_ERR_ARG; }
-      MultiTiles mt;
-      int acc = 0;
-      if (s.members.empty()) {
-        launch_band_one(s.ba, (unsigned)(B * s.band_tiles), s.lds_bytes, st);
-        break;
-      } else {
-        mt.n = (int)s.members.size();
-        for (int i = 0; i < mt.n; i++) {
-          mt.start[i] = acc;
-          acc += B * s.members[i].band_tiles;
-        }
-      }
-      mt.start[mt.n] = acc;
-      launch_band_multi(s.d_band, mt, s.members[0].bd_args.C, (unsigned)acc, s.lds_bytes, st);
-      break;
+      if (s.members.empty()) return launch_band_one(s.ba, (unsigned)(B * s.band_tiles), s.lds_bytes, st);
+      const MultiTiles mt = member_tiles([](const Step& ms) { return ms.band_tiles; });
+      return launch_band_multi(s.d_band, mt, s.members[0].bd_args.C, (unsigned)mt.start[mt.n], s.lds_bytes, st);
     }
-    case F_EXPDW: {
-      const OpRec& eop = m->ops[s.e_op];
-      const OpRec& dop = m->ops[s.d_op];
-      // variant: chunks per workgroup on the first form of the kernel, 100 + chunks per workgroup on the second with 8 waves, 200 + chunks
-      // with 16 waves; -1: heuristic default
-      // VBT_XD_VARIANT (tests): that variant for every step that supports it, whatever the plan says
-      static const int xd_force = getenv("VBT_XD_VARIANT") ? atoi(getenv("VBT_XD_VARIANT")) : -100;
-      int variant = s.variant;
-      if (xd_force != -100 && (xd_force < 100 || (s.xd2_ok && (xd_force < 200 ? s.xd2_gpw > 0 : s.xd2_gpw16 > 0)))) variant = std::min(xd_force, xd_force / 100 * 100 + s.xd.nchunks);
-      if (s.xd2_ok && (variant >= 100 || variant < 0)) {
-        if (variant >= 200 && s.xd2_gpw16 == 0) { set_error("expand + depthwise: plan asks for the 16-wave form on a step that does not support it"); return VBT_ERR_ARG; }
-        if (variant >= 100 && variant < 200 && s.xd2_gpw == 0) { set_error("expand + depthwise: plan asks for the 8-wave form on a step that does not support it"); return VBT_ERR_ARG; }
-        const int nw = (variant >= 200 || (variant < 0 && s.xd2_gpw16 > 0)) ? 16 : 8;
-        ExpDw2Args a = s.xd2;
-        a.x = TP(eop.inputs[0]);
-        a.out = out;
-        a.cpw = variant >= 100 ? variant % 100 : std::max(1, (a.nchunks * a.nbands * B + 1023) / 1024);   // default: about four workgroups per CU
-        a.cpw = std::min(a.cpw, a.nchunks);
-        const int ngroups = (a.nchunks + a.cpw - 1) / a.cpw;
-        const int rc = launch_expdw2(a, dop.k, dop.stride, (a.Cin + 63) / 64, nw, nw == 16 ? s.xd2_gpw16 : s.xd2_gpw, (unsigned)(B * ngroups * a.nbands), s.xd2_lds, st);
-        if (rc) return rc;
-        break;
-      }
-      if (variant >= 100) { set_error("expand + depthwise: plan asks for the second kernel form on a step that does not support it"); return VBT_ERR_ARG; }
-      ExpDwArgs a = s.xd;
-      a.x = TP(eop.inputs[0]);
-      a.out = out;
-      a.cpw = variant > 0 ? variant : std::max(1, (a.nchunks * a.nbands * B + 511) / 512);   // default: about two workgroups per CU
-      const int ngroups = (a.nchunks + a.cpw - 1) / a.cpw;
-      const int KS64 = (a.Cin + 63) / 64;
-      dim3 grid((unsigned)(B * ngroups * a.nbands));
-      launch_expdw(a, dop.k, dop.stride, KS64, grid.x, s.lds_bytes, st);
-      break;
-    }
+    case F_EXPDW:
+      return launch_expdw_step(m, s, B, st, TP(m->ops[s.e_op].inputs[0]), out);
     case F_STEMBLK: {
       StemBlockArgs a = s.sb;
-      a.frames = frames;
+      a.frames = frame0;
       a.out = out;
-      launch_stem_block(a, a.rqs.full && a.rqd.full && a.rqp.full, (unsigned)((long)B * a.tiles_x * a.tiles_y), st);
-      break;
+      return launch_stem_block(a, a.rqs.full && a.rqd.full && a.rqp.full, (unsigned)((long)B * a.tiles_x * a.tiles_y), st);
     }
     case F_POST: {
       PostArgs p;
@@ -2185,8 +2182,9 @@ static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const
       const int lds = post_lds_bytes(p.A);
       if (lds > 64 * 1024) VBT_LDS_OPT_IN(postprocess_kernel);
       if (lds > 160 * 1024 || p.A > 65535) { set_error("decode + NMS: %d anchors do not fit the kernel (LDS %d bytes, 16-bit anchor index)", p.A, lds); return VBT_ERR_CAPACITY; }
-      postprocess_kernel<<<dim3((unsigned)B), POST_THREADS, lds, st>>>(p, boxes, scores, classes, counts);
-      break;
+      const size_t o = (size_t)boff * m->hdr.max_detections;
+      postprocess_kernel<<<dim3((unsigned)B), POST_THREADS, lds, st>>>(p, boxes + 4 * o, scores + o, classes + o, counts + boff);
+      return VBT_OK;
     }
   }
   return VBT_OK;
@@ -2207,34 +2205,43 @@ static double time_step(vbt_model* m, const Step& s, int B, int reps) {
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 1e30;
   float ms = 1e30f;
+  int rc = VBT_OK;   // a refused launch (nothing enqueued) makes the candidate unusable, not fast
   if (nconc <= 1) {
-    launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
+    rc = launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
     (void)hipEventRecord(e0, nullptr);
-    for (int r = 0; r < reps; r++)
-      launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
+    for (int r = 0; r < reps && !rc; r++)
+      rc = launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
     (void)hipEventRecord(e1, nullptr);
     if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 1e30f;
     ms /= reps;
   } else {
     (void)hipDeviceSynchronize();
-    for (int i = 0; i < nconc; i++)
-      launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
+    for (int i = 0; i < nconc && !rc; i++)
+      rc = launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
     (void)hipDeviceSynchronize();
     auto t0 = std::chrono::steady_clock::now();
     for (int r = 0; r < reps; r++)
-      for (int i = 0; i < nconc; i++)
-        launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
+      for (int i = 0; i < nconc && !rc; i++)
+        rc = launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
     (void)hipDeviceSynchronize();
     ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (reps * nconc));
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  return ms;
+  return rc ? 1e30 : ms;
+}
+
+static bool is_fused_tile(int family) { return family == F_MBCONV || family == F_SEPCONV || family == F_NODE; }
+// whether `v` resolves to a launch of this step (the depthwise resolver and the families without one take any value)
+static bool variant_ok(const vbt_model* m, const Step& st, int v) {
+  if (st.family == F_PW) return !st.members.empty() || !resolve_pw(m, st, v, m->max_batch).rc;
+  if (is_fused_tile(st.family)) return !resolve_fused(m, st, v, m->max_batch).rc;
+  return st.family != F_EXPDW || !resolve_expdw(m, st, v, m->max_batch).rc;
 }
 
 // Plan-time autotuning: every alternative computes bit-identical tensors, so only speed is at stake.
-// Kernel variants the planner offers for a step: what the autotuner times, and all a plan file may select (anything else in a file
-// refuses the file: load_plan).  -1 = the launcher's own default.
+// Kernel variants the planner offers for a step: what the autotuner times, and (with the rest of the fused tile kernels' flag
+// combinations) what a plan file may select: load_plan.  -1 = the launcher's own default.  Only values that resolve are offered.
 static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
   std::vector<int> cand{-1};
   const OpRec& op = m->ops[st.op];
@@ -2247,11 +2254,10 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
     cand = {0, 1};
   } else if (st.family == F_PW) {
     cand = {-1, 2, 3, 4, 5, 6};
-  } else if (st.family == F_MBCONV || st.family == F_SEPCONV || st.family == F_NODE) {
-    cand = {0, 1, 3};   // VALU dw, matrix-pipe dw, matrix-pipe dw + half-height tile
-    if (image_geom(m, st).ok) cand.push_back(5);  // one workgroup per image
+  } else if (is_fused_tile(st.family)) {
+    cand = {0, 1, 3, 5};   // VALU dw, matrix-pipe dw, matrix-pipe dw + half-height tile, one workgroup per image
     if (st.family == F_MBCONV && st.fa.nch3 > 0 && st.nbp <= 2 && st.fa.KSe >= 1 && st.fa.KSe <= 4) { cand.push_back(9); cand.push_back(11); }  // 48-channel chunks
-    if (st.family == F_MBCONV && st.nbp <= 2 && (st.fa.KSe == 1 || st.fa.KSe == 2) && ppw2_fits(m, st)) {   // 128-pixel tiles
+    if (st.family == F_MBCONV && st.nbp <= 2 && (st.fa.KSe == 1 || st.fa.KSe == 2)) {   // 128-pixel tiles
       cand.push_back(17);
       if (st.fa.nch3 > 0) cand.push_back(25);
     }
@@ -2268,6 +2274,7 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
           if (st.xd2_gpw16 > 0) cand.push_back(200 + cpw);
         }
   }
+  cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int v) { return !variant_ok(m, st, v); }), cand.end());
   return cand;
 }
 
@@ -2294,7 +2301,6 @@ static void autotune(vbt_model* m) {
           if (ms < best) { best = ms; bestv = v; }
         }
         st.variant = bestv;
-        st.macs_per_frame = st.macs_per_frame;  // (unchanged)
         st.tuned_ms = best;
         a.ms += best;
       }
@@ -2302,14 +2308,6 @@ static void autotune(vbt_model* m) {
     int bi = 0;
     for (size_t i = 1; i < g.alts.size(); i++)
       if (g.alts[i].ms < g.alts[bi].ms) bi = (int)i;
-    if (const char* pe = getenv("VBT_PREFER_IMAGE")) {  // experiment: whole-image kernel on maps of at most this many pixels
-      for (size_t i = 0; i < g.alts.size(); i++)
-        if (g.alts[i].steps.size() == 1 && g.alts[i].steps[0].family == F_MBCONV && image_geom(m, g.alts[i].steps[0]).ok &&
-            g.alts[i].steps[0].fa.H * g.alts[i].steps[0].fa.W <= atoi(pe)) {
-          bi = (int)i;
-          g.alts[i].steps[0].variant = 5;
-        }
-    }
     g.chosen = bi;
     if (getenv("VBT_AUTOTUNE_VERBOSE")) {
       const Step& f = g.alts[0].steps[0];
@@ -2332,8 +2330,8 @@ static void autotune(vbt_model* m) {
 // refused and the plan re-tuned.  Format 1 ("<ngroups>" then "<chosen> <nsteps> <variant>...") is still read - the group and step
 // counts are all it can be checked against - and re-written in format 2 when VBT_PLAN_CONVERT is set.
 static bool load_plan(vbt_model* m, const char* path) {
-  // the shape a file may select from: this library's groups, their alternatives, the family of every step and the variants the planner
-  // offers for it (container_parse.h: parse_plan_file refuses everything else, and the model is tuned afresh)
+  // the shape a file may select from: this library's groups, their alternatives, the family of every step and the variants that resolve
+  // for it (container_parse.h: parse_plan_file refuses everything else, and the model is tuned afresh)
   PlanShape shape;
   for (const Group& g : m->groups) {
     std::vector<std::vector<PlanStepShape>> alts;
@@ -2343,14 +2341,13 @@ static bool load_plan(vbt_model* m, const char* path) {
         PlanStepShape ps;
         ps.family = kFamilyName[st.family];
         ps.variants = candidate_variants(m, st);
-        // the fused tile kernels read their variant as a set of flags (matrix-pipe depthwise, half-height tile, 48-channel chunks,
-        // 128-pixel tiles ...), each guarded by its own fit test in launch_step: plans searched under load (tools/tune_under_load.py)
-        // hold combinations the isolated autotuner does not time
-        if (st.family == F_MBCONV || st.family == F_SEPCONV || st.family == F_NODE)
-          for (int v = 0; v < 32; v++)
-            if (std::find(ps.variants.begin(), ps.variants.end(), v) == ps.variants.end()) ps.variants.push_back(v);
-        if (std::find(ps.variants.begin(), ps.variants.end(), -1) == ps.variants.end()) ps.variants.push_back(-1);
-        if (std::find(ps.variants.begin(), ps.variants.end(), st.variant) == ps.variants.end()) ps.variants.push_back(st.variant);   // the heuristic plan's own choice
+        auto add = [&](int v) { if (std::find(ps.variants.begin(), ps.variants.end(), v) == ps.variants.end()) ps.variants.push_back(v); };
+        // the fused tile kernels read their variant as a set of flags (resolve_fused): plans searched under load (tools/tune_under_load.py)
+        // hold combinations the isolated autotuner does not time, and every combination that resolves is accepted
+        for (int v = 0; v < 32 && is_fused_tile(st.family); v++)
+          if (variant_ok(m, st, v)) add(v);
+        add(-1);
+        add(st.variant);   // the heuristic plan's own choice
         steps.push_back(ps);
       }
       alts.push_back(steps);
@@ -2937,7 +2934,7 @@ int vbt_model_profile_overlap(vbt_model* m, int B, int reps, int nstreams, float
       VBT_HIP_CHECK(hipDeviceSynchronize());
       auto t0 = std::chrono::steady_clock::now();
       for (int r = 0; r < reps; r++)
-        for (int j = 0; j < k; j++) (void)launch_step(m, s, B, ss[j], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
+        for (int j = 0; j < k; j++) rc = rc ? rc : launch_step(m, s, B, ss[j], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
       VBT_HIP_CHECK(hipDeviceSynchronize());
       const float ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (reps * k));
       (pass == 0 ? single_ms : conc_ms)[i] = ms;
