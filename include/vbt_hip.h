@@ -106,6 +106,11 @@ typedef struct {
 int vbt_tracker_create(int n_clips, int rows_cap, const vbt_tracker_params* p, int device, vbt_tracker** out);
 void vbt_tracker_destroy(vbt_tracker* t);
 int vbt_tracker_reset(vbt_tracker* t);
+/* A fresh clip in each of the slots clips[0..n): its OC-SORT state cleared (ids restart at 1), its row log empty, its frame counter 0
+ * and - live analysis on - its live record and entries re-initialised, exactly as vbt_tracker_reset leaves a clip; the other clips
+ * are untouched.  Enqueue only, on `stream` (the list travels in the kernel arguments).  VBT_ERR_ARG: n < 1, a clip outside
+ * 0..n_clips-1 or listed twice. */
+int vbt_tracker_reset_clips(vbt_tracker* t, const int32_t* clips, int n, void* stream);
 
 /* OCSort.update for F consecutive frames of every clip (host pointers; synchronous):
  *   dets   float64 [F][n_clips][25][6] = x1,y1,x2,y2,score,cls   (reference odt.py:102-118)
@@ -287,7 +292,7 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
 /* frames read from the source but not processed (`frame_count % 16`, track.py:161-167): they advance the clip time only */
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n);
 int vbt_pipeline_set_frame_count(vbt_pipeline* p, int frame_count);
-/* back to frame 0 of fresh clips; models, streams and buffers are kept (synchronises) */
+/* back to frame 0 of fresh clips; models, streams and buffers are kept; unread slot-close results are dropped (synchronises) */
 int vbt_pipeline_reset(vbt_pipeline* p);
 /* `stream` waits for every forward enqueued so far (after detector-only steps their outputs are then safe to read on it) */
 int vbt_pipeline_join_detectors(vbt_pipeline* p, void* stream);
@@ -296,6 +301,38 @@ int vbt_pipeline_join_detectors(vbt_pipeline* p, void* stream);
  * output pointers may be NULL (vbt_pipeline_finish = close without the read-back, synchronises too). */
 int vbt_pipeline_close(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6, int cap);
 int vbt_pipeline_finish(vbt_pipeline* p);
+/* Slot close: one clip ends while the others keep running, and a new clip starts in its tracker slot (a host whose clips arrive and
+ * end at different times).  The result of a closed slot is what vbt_pipeline_close gives for that clip at that point, bit for bit. */
+typedef struct {
+  int32_t clip;      /* tracker slot the clip was closed from */
+  int32_t best_id;   /* export id (track.py:107-115), -1: none */
+  int32_t n_rows;    /* rows of the clip's log, all ids */
+  int32_t n_phases;  /* phases of best_id */
+  int32_t overflow;  /* tracker overflow | rows_overflow, as vbt_pipeline_close reports it */
+  int32_t reserved;
+} vbt_closed_clip;
+/* Allocates what the slot close needs, once, so that no close allocates: per tracker clip a pinned record (24.6 KB), a device row outbox
+ * (rows_cap x 64 bytes) and an event, and the stream rows are read back on.  Call it after vbt_pipeline_create; a second call does
+ * nothing.  Synchronous (allocation). */
+int vbt_pipeline_close_clips_enable(vbt_pipeline* p);
+/* Enqueue the close of `n` slots and their reset to fresh clips; next_fps [n] or NULL (keep). Does not synchronise.
+ * Every frame of a listed slot handed to a step before the call is covered (held-back tracker steps are enqueued first,
+ * vbt_pipeline_drain); on the tracker stream the export id + rep analysis of the listed clips run (plot.py:33-47), their records go to
+ * pinned memory and their rows into the slot's outbox, and the slots are reset (vbt_tracker_reset_clips); every later tracker launch
+ * waits for the reset.  Only kernels, event records and event waits are enqueued: no allocation, no copy, no host wait.  The next step
+ * may carry frames of the new clip at once: its plain-step frame numbers restart at 1 (time 1 / fps), as do those of `active` steps;
+ * clip_map / run steps number frames themselves.  VBT_ERR_ARG: a slot out of range or listed twice, next_fps <= 0; VBT_ERR_STATE: the
+ * slot close is not enabled (vbt_pipeline_close_clips_enable), or a listed slot still holds an unread result (vbt_pipeline_closed_clip). */
+int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const double* next_fps);
+/* The unread result of slot `clip`: wait = 0 never blocks (*ready = 0 until the device has done the close), wait = 1 waits for
+ * that close only. phases6 [cap_phases][6]; rows_host [cap_rows] 64-byte records (NULL: rows not copied).
+ * Once the close is done, rows_host != NULL copies the clip's whole log (emission order, the record of vbt_tracker_rows_all) on the
+ * pipeline's read stream, after this close only, and waits for that copy (n_rows x 64 bytes) - with wait = 0 too; the record and the
+ * phases need no copy.  A successful read (ready = 1) releases the slot's result.  VBT_ERR_STATE: nothing pending for `clip`;
+ * VBT_ERR_CAPACITY: cap_phases < n_phases or (rows_host != NULL) cap_rows < n_rows - the result stays readable.  vbt_pipeline_reset
+ * drops unread results. */
+int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, int cap_phases,
+                             void* rows_host, int cap_rows);
 /* enqueue every tracker step still held back (deferred groups, the `depth - 1` steps the own-stream mode keeps ahead); no synchronisation */
 int vbt_pipeline_drain(vbt_pipeline* p);
 /* vbt_tracker_rows_all / vbt_tracker_rows / vbt_tracker_phases after draining the pipeline (synchronise) */

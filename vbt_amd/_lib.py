@@ -35,6 +35,12 @@ class LiveClip(ctypes.Structure):
                 ("phase_state", ctypes.c_int32), ("overflow", ctypes.c_int32), ("seq", ctypes.c_uint64)]
 
 
+class ClosedClip(ctypes.Structure):
+    """vbt_closed_clip (include/vbt_hip.h): the result of one slot close"""
+    _fields_ = [("clip", ctypes.c_int32), ("best_id", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_phases", ctypes.c_int32),
+                ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class PipelineParams(ctypes.Structure):
     """vbt_pipeline_params (include/vbt_hip.h)"""
     _fields_ = [("n_slots", ctypes.c_int32), ("n_clips", ctypes.c_int32), ("rows_cap", ctypes.c_int32), ("device", ctypes.c_int32),
@@ -88,6 +94,7 @@ _SIGS = {
     "vbt_tracker_create": (c_int, [c_int, c_int, ctypes.POINTER(TrackerParams), c_int, ctypes.POINTER(c_void_p)]),
     "vbt_tracker_destroy": (None, [c_void_p]),
     "vbt_tracker_reset": (c_int, [c_void_p]),
+    "vbt_tracker_reset_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_tracker_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_tracker_update_from_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
     "vbt_tracker_last_output": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
@@ -116,6 +123,9 @@ _SIGS = {
     "vbt_pipeline_join_detectors": (c_int, [c_void_p, c_void_p]),
     "vbt_pipeline_close": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_pipeline_finish": (c_int, [c_void_p]),
+    "vbt_pipeline_close_clips_enable": (c_int, [c_void_p]),
+    "vbt_pipeline_close_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "vbt_pipeline_closed_clip": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ClosedClip), c_void_p, c_int, c_void_p, c_int]),
     "vbt_pipeline_drain": (c_int, [c_void_p]),
     "vbt_pipeline_rows_all": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_pipeline_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),

@@ -1,12 +1,15 @@
 """Command line mirror of the reference's two entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1] [--live]
+                            [--concurrent N]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
       dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
       --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
       list that changes afterwards (the leading id changes, or a larger rep makes the filter drop small ones) is announced with a
       "revised" line and reprinted from the first rep that differs.  The reps standing at the end are those `analyze` prints.
+      --concurrent N > 1: all files through one pipeline, N clips side by side (a finished clip's tracker slot takes the next
+      file); the same files and lines as N = 1, in input order.  Not with --live.
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
@@ -67,8 +70,16 @@ class _LiveReps:
 @click.option("--frame_stride", default=1, show_default=True, type=int, help="16 reproduces `frame_count %% 16` of reference track.py:166.")
 @click.option("--time_batch", default=64, show_default=True, type=int, help="Consecutive frames of the clip per detector batch (1 = one frame per step).")
 @click.option("--live", is_flag=True, default=False, help="Print each concentric rep (ROM, ACV) as soon as it is complete.")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live):
+@click.option("--concurrent", default=1, show_default=True, type=int,
+              help="Clips tracked side by side in one pipeline (a finished clip's tracker slot takes the next file); 1 = one pipeline per file.")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent):
     from .track import export_dataframe, track_frames
+    if concurrent < 1:
+        raise click.UsageError("--concurrent must be at least 1")
+    if concurrent > 1:
+        if live:
+            raise click.UsageError("--live works with --concurrent 1 only")
+        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent)
     for s in src:
         if not os.path.isfile(s):
             raise FileNotFoundError(s)                                   # reference track.py:89-90
@@ -82,6 +93,37 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
             continue
         df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
         click.echo(f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else ""))
+
+
+def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent):
+    """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
+    DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
+    that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
+    from .track import export_dataframe, track_many
+    sources, error = [], None
+    for s in src:
+        if not os.path.isfile(s):
+            error = FileNotFoundError(s)
+            break
+        frames = np.load(s, mmap_mode="r")
+        if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
+            error = click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
+            break
+        sources.append(frames)
+    lines, nxt = {}, 0
+    for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
+                              time_batch=time_batch):
+        s = src[i]
+        if not data["id"]:
+            lines[i] = f"{s}: no tracked rows"
+        else:
+            df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
+            lines[i] = f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else "")
+        while nxt in lines:
+            click.echo(lines.pop(nxt))
+            nxt += 1
+    if error is not None:
+        raise error
 
 
 @main.command()

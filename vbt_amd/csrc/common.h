@@ -49,6 +49,17 @@ bool lds_opt_in(const void* fn, LdsOptIn* state);
 // preprocess_image (reference odt.py:10-19) on device memory (detector.hip); compact != 0: src holds only the row pairs the resize reads
 int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st);
 
+// Slot close (vbt_pipeline_close_clips): the per-clip record close_pack_kernel writes, { int best_id, n_rows, n_phases, overflow ;
+// double phases[512][6] } (512 = the phases a clip keeps, tracker.hip MAXPH)
+constexpr size_t CLOSED_HEAD_BYTES = 16 + 512 * 48;
+// clips[0..n): each in [0, n_clips), none twice, n >= 1 - else VBT_ERR_ARG with the error text set (fn: the caller's name)
+int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips);
+// Device part of vbt_pipeline_close_clips (tracker.hip), enqueue only, on st: export id + rep analysis of the listed clips (the kernels
+// of vbt_tracker_finish on the list), their records into head (pinned, [n_clips][CLOSED_HEAD_BYTES]) and their rows into out_rows
+// (device, [n_clips][rows_cap] 64-byte rows), then a fresh clip in every listed slot (vbt_tracker_reset_clips)
+int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
+                        unsigned char* head, void* out_rows, hipStream_t st);
+
 // ---- VBTM container records, reader + validator, plan-file reader: container_parse.h (pure C++, also built host-only under
 // -fsanitize=address,undefined by tests/test_parser_fuzz.py) ----
 // Integer parameters of an int8 ADD exactly as XNNPACK derives them (xnn_create_add_nd_qs8 +

@@ -1,7 +1,7 @@
 // vbt_pipeline: the clip loop of reference track.py:129-260 as one object behind the C ABI (include/vbt_hip.h, "pipeline").
 //
 // Host code only - every kernel it enqueues is reached through the library's own entry points (vbt_detect_async,
-// vbt_tracker_update_from_*, vbt_resize_frames, vbt_gather_frames).  What lives here is the part of the fast path that is not a
+// vbt_tracker_update_from_*, vbt_resize_frames, vbt_gather_frames; the slot close through tracker_close_clips, common.h).  What lives here is the part of the fast path that is not a
 // kernel: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
 // events that order detector(t) -> tracker(t) -> slot reuse, the staging ring of the host-fed mode, the deferred tracker groups of
 // the small-batch path, clip close.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
@@ -81,6 +81,15 @@ struct vbt_pipeline {
   int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
+  // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
+  // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
+  unsigned char* closed_head = nullptr;
+  unsigned char* closed_head_dev = nullptr;   // (its device address)
+  void* closed_rows = nullptr;
+  std::vector<hipEvent_t> ev_closed;
+  std::vector<char> closed_unread;
+  std::vector<int> fc_base;
+  hipStream_t read_stream = nullptr;   // the rows of a closed slot come back on it (a pool stream that carries nothing else)
 };
 
 namespace {
@@ -294,7 +303,8 @@ int flush_group(vbt_pipeline* p) {
   if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));
   const int fstep = p->meta[g[1]].fc - p->meta[g[0]].fc;
   std::vector<vbt_run> ra((size_t)n);
-  for (int c = 0; c < n; c++) ra[c] = vbt_run{c, c, n, (int)g.size(), p->meta[g[0]].fc, fstep, p->fps[c]};
+  // (a slot close flushes the group first: the bases are those of the whole group)
+  for (int c = 0; c < n; c++) ra[c] = vbt_run{c, c, n, (int)g.size(), p->meta[g[0]].fc - p->fc_base[c], fstep, p->fps[c]};
   // slot (o - g[0]) * n + c of the block that starts at ring slot g[0]
   PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, g[0]), scores_of(p, g[0]), counts_of(p, g[0]), (int)g.size() * n, ra.data(), n,
                                                   p->prm.detection_threshold, (void*)T));
@@ -578,6 +588,9 @@ void vbt_pipeline_destroy(vbt_pipeline* p) {
   for (hipEvent_t e : p->ev_in) (void)hipEventDestroy(e);
   for (hipEvent_t e : p->ev_det) (void)hipEventDestroy(e);
   for (hipEvent_t e : p->ev_trk) (void)hipEventDestroy(e);
+  for (hipEvent_t e : p->ev_closed) (void)hipEventDestroy(e);
+  if (p->closed_head) (void)hipHostFree(p->closed_head);
+  if (p->closed_rows) (void)hipFree(p->closed_rows);
   {
     // streams are never destroyed: they go back to the process-wide pool, classified, for the next pipeline
     std::lock_guard<std::mutex> lock(g_pool_mu);
@@ -609,6 +622,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
     if (!(fps_host[c] > 0.0)) { delete p; set_error("vbt_pipeline_create: fps of clip %d must be > 0", c); return VBT_ERR_ARG; }
     p->fps.push_back(fps_host[c]);
   }
+  p->fc_base.assign((size_t)p->n_trk, 0);
   // forwards in flight: 3 at batch 64 (four hardware queues: three forwards + the copy stream); a batch of one to
   // eight frames is launch latency, where a fourth forward still pays
   p->depth = prm->depth > 0 ? prm->depth : env_int("VBT_PIPELINE_DEPTH", p->n <= 8 ? 4 : 3);
@@ -749,7 +763,10 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
     m.cmap.assign(clip_map, clip_map + p->n);
     for (int i = 0; i < p->n; i++) m.times[i] = clip_map[i] >= 0 ? (double)frame_idx[i] / p->fps[clip_map[i]] : -1.0;
   } else if (!active) {
-    for (int i = 0; i < p->n; i++) m.times[i] = (double)p->frame_count / p->fps[std::min(i, p->n_trk - 1)];   // time = frame_count / fps (track.py:169)
+    for (int i = 0; i < p->n; i++) {   // time = frame_count / fps (track.py:169), counted from the slot's last reopen
+      const int c = std::min(i, p->n_trk - 1);
+      m.times[i] = (double)(p->frame_count - p->fc_base[c]) / p->fps[c];
+    }
   } else {
     for (int i = 0; i < p->n; i++) {
       if (active[i]) {
@@ -847,6 +864,8 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
   std::fill(p->trk_ev_of.begin(), p->trk_ev_of.end(), -1);
   p->last_trk = -1;
   std::fill(p->clip_frames.begin(), p->clip_frames.end(), 0);
+  std::fill(p->fc_base.begin(), p->fc_base.end(), 0);
+  std::fill(p->closed_unread.begin(), p->closed_unread.end(), 0);   // unread slot-close results are dropped
   p->step_host_ns = p->step_calls = 0;
   return VBT_OK;
 }
@@ -869,6 +888,124 @@ int vbt_pipeline_finish(vbt_pipeline* p) {
   PL_CHECK(drain(p));
   PL_CHECK(vbt_tracker_finish(p->trk, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
   VBT_HIP_CHECK(hipStreamSynchronize(p->trk_stream));
+  return VBT_OK;
+}
+
+// The slot close's buffers, allocated once so that no close allocates: per tracker clip a pinned record, a device row outbox and an
+// event; and the stream the rows come back on.  All or nothing.
+int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (p->closed_head) return VBT_OK;
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  const size_t nt = (size_t)p->n_trk;
+  void* rows = nullptr;
+  unsigned char *head = nullptr, *head_dev = nullptr;
+  std::vector<hipEvent_t> evs;
+  auto undo = [&](const char* what, hipError_t e) {
+    for (hipEvent_t x : evs) (void)hipEventDestroy(x);
+    if (head) (void)hipHostFree(head);
+    if (rows) (void)hipFree(rows);
+    set_error("vbt_pipeline_close_clips_enable: %s failed: %s", what, hipGetErrorString(e));
+    return VBT_ERR_HIP;
+  };
+  hipError_t e = hipMalloc(&rows, nt * (size_t)p->prm.rows_cap * 64);
+  if (e != hipSuccess) { rows = nullptr; return undo("hipMalloc of the row outboxes", e); }
+  // coherent: the close kernel's stores reach host memory directly, visible once the close's event has completed
+  e = hipHostMalloc((void**)&head, nt * CLOSED_HEAD_BYTES, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) { head = nullptr; return undo("hipHostMalloc of the close records", e); }
+  e = hipHostGetDevicePointer((void**)&head_dev, head, 0);
+  if (e != hipSuccess) return undo("hipHostGetDevicePointer", e);
+  for (size_t c = 0; c < nt; c++) {
+    hipEvent_t ev = nullptr;
+    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return undo("hipEventCreate", e);
+    evs.push_back(ev);
+  }
+  {
+    std::lock_guard<std::mutex> lock(g_pool_mu);
+    StreamPool& pool = g_pools[p->device];
+    int i = -1;
+    const int rc = pool_take(p, pool, -1, false, &i);
+    if (rc != VBT_OK) { undo("taking the read stream", hipSuccess); return rc; }
+    p->read_stream = pool.streams[(size_t)i];
+  }
+  p->closed_rows = rows;
+  p->closed_head = head;
+  p->closed_head_dev = head_dev;
+  p->ev_closed.swap(evs);
+  p->closed_unread.assign(nt, 0);
+  return VBT_OK;
+}
+
+// Slot close.  Enqueue only: drain() hands the held-back tracker steps to their streams, the close kernels and the reset follow on the
+// tracker stream (in inline mode drain() made it wait for the last tracker launch), and the reset is recorded as the most recent tracker
+// launch - every later tracker launch waits for it, whichever stream it runs on (enqueue_tracker, flush_group, tracker-only steps run
+// on the tracker stream itself).  The record goes straight into pinned memory (close_pack_kernel), so no copy is enqueued here.
+int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const double* next_fps) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  PL_CHECK(check_clip_list("vbt_pipeline_close_clips", clips, n, p->n_trk));
+  for (int i = 0; i < n; i++) {
+    if (next_fps && !(next_fps[i] > 0.0)) { set_error("vbt_pipeline_close_clips: next_fps[%d] = %g must be > 0", i, next_fps[i]); return VBT_ERR_ARG; }
+    if (!p->closed_unread.empty() && p->closed_unread[(size_t)clips[i]]) {
+      set_error("vbt_pipeline_close_clips: slot %d still holds an unread result (vbt_pipeline_closed_clip)", clips[i]);
+      return VBT_ERR_STATE;
+    }
+  }
+  if (!p->closed_head) {
+    set_error("vbt_pipeline_close_clips: the slot close is not enabled (vbt_pipeline_close_clips_enable)");
+    return VBT_ERR_STATE;
+  }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));
+  hipStream_t T = p->trk_stream;
+  PL_CHECK(tracker_close_clips(p->trk, clips, n, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, p->closed_head_dev,
+                               p->closed_rows, T));
+  for (int i = 0; i < n; i++) {
+    const int c = clips[i];
+    VBT_HIP_CHECK(hipEventRecord(p->ev_closed[(size_t)c], T));
+    p->closed_unread[(size_t)c] = 1;
+    p->fc_base[(size_t)c] = p->frame_count;                       // the next plain step is frame 1 of the new clip
+    if ((size_t)c < p->clip_frames.size()) p->clip_frames[(size_t)c] = 0;
+    if (next_fps) p->fps[(size_t)c] = next_fps[i];
+  }
+  const int e = p->last_trk >= 0 ? p->last_trk : 0;
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e], T));
+  p->last_trk = e;
+  return VBT_OK;
+}
+
+int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, int cap_phases,
+                             void* rows_host, int cap_rows) {
+  if (!p || !ready || !rec || cap_phases < 0 || (cap_phases > 0 && !phases6) || (rows_host && cap_rows < 0)) {
+    set_error("vbt_pipeline_closed_clip: bad argument");
+    return VBT_ERR_ARG;
+  }
+  if (clip < 0 || clip >= p->n_trk) { set_error("vbt_pipeline_closed_clip: slot %d outside the %d clips", clip, p->n_trk); return VBT_ERR_ARG; }
+  *ready = 0;
+  if (p->closed_unread.empty() || !p->closed_unread[(size_t)clip]) { set_error("vbt_pipeline_closed_clip: slot %d has no unread result", clip); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  hipEvent_t ev = p->ev_closed[(size_t)clip];
+  if (wait) {
+    VBT_HIP_CHECK(hipEventSynchronize(ev));
+  } else {
+    const hipError_t q = hipEventQuery(ev);
+    if (q == hipErrorNotReady) return VBT_OK;
+    VBT_HIP_CHECK(q);
+  }
+  const unsigned char* h = p->closed_head + (size_t)clip * CLOSED_HEAD_BYTES;
+  const int32_t* hd = (const int32_t*)h;
+  rec->clip = clip; rec->best_id = hd[0]; rec->n_rows = hd[1]; rec->n_phases = hd[2]; rec->overflow = hd[3]; rec->reserved = 0;
+  if (hd[2] > cap_phases) { set_error("vbt_pipeline_closed_clip: slot %d has %d phases, buffer holds %d", clip, hd[2], cap_phases); return VBT_ERR_CAPACITY; }
+  if (rows_host && hd[1] > cap_rows) { set_error("vbt_pipeline_closed_clip: slot %d has %d rows, buffer holds %d", clip, hd[1], cap_rows); return VBT_ERR_CAPACITY; }
+  if (hd[2] > 0) memcpy(phases6, h + 16, (size_t)hd[2] * 48);
+  if (rows_host && hd[1] > 0) {
+    const unsigned char* src = (const unsigned char*)p->closed_rows + (size_t)clip * p->prm.rows_cap * 64;
+    VBT_HIP_CHECK(hipStreamWaitEvent(p->read_stream, ev, 0));   // (done already: the copy waits for this close only)
+    VBT_HIP_CHECK(hipMemcpyAsync(rows_host, src, (size_t)hd[1] * 64, hipMemcpyDeviceToHost, p->read_stream));
+    VBT_HIP_CHECK(hipStreamSynchronize(p->read_stream));
+  }
+  p->closed_unread[(size_t)clip] = 0;
+  *ready = 1;
   return VBT_OK;
 }
 
@@ -925,7 +1062,7 @@ int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
   std::vector<double> tm((size_t)p->n);
   for (int i = 0; i < count; i++) {
     p->frame_count++;
-    for (int c = 0; c < p->n; c++) tm[c] = (double)p->frame_count / p->fps[c];
+    for (int c = 0; c < p->n; c++) tm[c] = (double)(p->frame_count - p->fc_base[c]) / p->fps[c];
     PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, slot), scores_of(p, slot), counts_of(p, slot), tm.data(), p->prm.detection_threshold, (void*)T));
   }
   return record_trk(p, slot, T);

@@ -33,6 +33,7 @@ __device__ unsigned long long g_trk_prof[16];
 constexpr int MAXT = 64;
 constexpr int MAXD = VBT_MAX_DETECTIONS;
 constexpr int MAXPH = 512;  // phases kept per clip
+static_assert(CLOSED_HEAD_BYTES == 16 + (size_t)MAXPH * 48, "slot close record (common.h)");
 
 struct Trk {
   double x[7];
@@ -1260,9 +1261,18 @@ __device__ void analyze_track(const double* cols, int T, const VtParams& p, doub
   *nph_out = s.nph;
 }
 
+// A clip list in the kernel arguments (no host-to-device copy): block b works on clip[b]; n == 0 - no list - block b on clip b.  A
+// longer list takes several launches of at most CLIP_LIST workgroups.
+constexpr int CLIP_LIST = 64;
+struct ClipList {
+  int n;
+  int clip[CLIP_LIST];
+};
+__device__ inline int listed_clip(const ClipList& l) { return l.n ? l.clip[blockIdx.x] : (int)blockIdx.x; }
+
 __global__ __launch_bounds__(64) void analyze_kernel(const double* cols, const int* T, int stride_rows, VtParams p, double* scratch,
-                                                     double* phases, int* nph) {
-  const int clip = blockIdx.x;
+                                                     double* phases, int* nph, ClipList l) {
+  const int clip = listed_clip(l);
   if (threadIdx.x != 0) return;
   analyze_track(cols + (size_t)clip * stride_rows * 7, T[clip], p, scratch + (size_t)clip * stride_rows * 5,
                 phases + (size_t)clip * MAXPH * 6, nph + clip);
@@ -1302,8 +1312,8 @@ __device__ inline int export_id(const ClipState& st) {
 
 // end of clip: live tracks compete for the export id too; then gather the rows of the winner.
 __global__ __launch_bounds__(64) void select_gather_kernel(ClipState* states, const Row* rows, int rows_cap, double* cols, int* T,
-                                                           int* best_ids) {
-  const int clip = blockIdx.x, lane = threadIdx.x;
+                                                           int* best_ids, ClipList l) {
+  const int clip = listed_clip(l), lane = threadIdx.x;
   ClipState& st = states[clip];
   __shared__ int s_best;
   if (lane == 0) {
@@ -1332,9 +1342,10 @@ __global__ __launch_bounds__(64) void select_gather_kernel(ClipState* states, co
 
 // Clip close: everything the host reads per clip, packed into one block so that ONE copy fetches it:
 //   record c = { int best_id, n_rows, n_phases, overflow ; double phases[cap][6] }
+// On a clip list (vbt_pipeline_close_clips, cap = MAXPH) the records of the listed clips only, straight into pinned host memory.
 __global__ __launch_bounds__(64) void pack_summary_kernel(const ClipState* states, const int* best, const int* nph, const double* phases,
-                                                          int cap, unsigned char* out) {
-  const int clip = blockIdx.x, lane = threadIdx.x;
+                                                          int cap, unsigned char* out, ClipList l) {
+  const int clip = listed_clip(l), lane = threadIdx.x;
   const size_t rec = 16 + (size_t)cap * 48;
   unsigned char* o = out + clip * rec;
   const int n = nph[clip];
@@ -1347,12 +1358,25 @@ __global__ __launch_bounds__(64) void pack_summary_kernel(const ClipState* state
   for (int i = lane; i < min(n, cap) * 6; i += 64) ph[i] = src[i];
 }
 
+// Slot close (vbt_pipeline_close_clips): the first n_rows rows of every listed clip's log - the 64-byte records of vbt_tracker_rows_all -
+// into out_rows + clip * rows_cap (device memory: the slot's log is overwritten as soon as its next clip steps).  One workgroup per clip.
+__global__ __launch_bounds__(64) void close_rows_kernel(const ClipState* states, const Row* rows, int rows_cap, ClipList l, Row* out_rows) {
+  const int clip = l.clip[blockIdx.x], lane = threadIdx.x;
+  const int nr = states[clip].nrows;   // <= rows_cap (the log never grows past it)
+  const uint4* rs = (const uint4*)(rows + (size_t)clip * rows_cap);   // 4 x 16 bytes per row
+  uint4* rd = (uint4*)(out_rows + (size_t)clip * rows_cap);
+  for (int i = lane; i < nr * 4; i += 64) rd[i] = rs[i];
+}
+
+__device__ inline void init_state(ClipState& st) {
+  st.ntrk = 0; st.frame_count = 0; st.next_id = 0; st.overflow = 0; st.nrows = 0; st.rows_overflow = 0;
+  st.best_id = -1; st.last_n = 0; st.best_cum = -1.0; st.used = 0ull;
+}
+
 __global__ void init_states_kernel(ClipState* states, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  ClipState& st = states[i];
-  st.ntrk = 0; st.frame_count = 0; st.next_id = 0; st.overflow = 0; st.nrows = 0; st.rows_overflow = 0;
-  st.best_id = -1; st.last_n = 0; st.best_cum = -1.0; st.used = 0ull;
+  init_state(states[i]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1580,13 +1604,23 @@ __global__ __launch_bounds__(64) void live_tracks_kernel(LiveBufs b, LiveCfg c, 
   }
 }
 
+__device__ inline void live_clip_init(LiveClip& L) { L.cursor = 0; L.flags = 0; L.leader = -1; L.leader_ver = -1; L.seq = 0; }
+__device__ inline void live_entry_free(LiveEntry& x) { x.id = -1; x.nrows = 0; }
+
 __global__ void live_init_kernel(LiveClip* clips, LiveEntry* ents, int n_clips) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_clips) {
-    LiveClip& L = clips[i];
-    L.cursor = 0; L.flags = 0; L.leader = -1; L.leader_ver = -1; L.seq = 0;
-  }
-  if (i < n_clips * LIVE_ENTRIES) { ents[i].id = -1; ents[i].nrows = 0; }
+  if (i < n_clips) live_clip_init(clips[i]);
+  if (i < n_clips * LIVE_ENTRIES) live_entry_free(ents[i]);
+}
+
+// A fresh clip in every listed slot (vbt_tracker_reset_clips), one workgroup per listed clip: its ClipState as init_states_kernel leaves it
+// and - live analysis on (clips != nullptr) - its LiveClip and LIVE_ENTRIES entries as live_init_kernel leaves them.
+__global__ __launch_bounds__(64) void reset_clips_kernel(ClipState* states, LiveClip* clips, LiveEntry* ents, ClipList l) {
+  const int clip = l.clip[blockIdx.x], lane = threadIdx.x;
+  if (lane == 0) init_state(states[clip]);
+  if (!clips) return;
+  if (lane == 0) live_clip_init(clips[clip]);
+  for (int e = lane; e < LIVE_ENTRIES; e += 64) live_entry_free(ents[(size_t)clip * LIVE_ENTRIES + e]);
 }
 
 }  // namespace vbt
@@ -1712,6 +1746,22 @@ int vbt_tracker_reset(vbt_tracker* t) {
   t->finished = false;
   t->view_clip = -1;
   t->stepped = false;
+  return VBT_OK;
+}
+
+int vbt_tracker_reset_clips(vbt_tracker* t, const int32_t* clips, int n, void* stream) {
+  if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
+  if (int rc = check_clip_list("vbt_tracker_reset_clips", clips, n, t->n_clips)) return rc;
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < n; i0 += CLIP_LIST) {
+    ClipList l{};
+    l.n = std::min(CLIP_LIST, n - i0);
+    for (int i = 0; i < l.n; i++) l.clip[i] = clips[i0 + i];
+    reset_clips_kernel<<<l.n, 64, 0, st>>>(t->states, t->live ? t->lb.clips : nullptr, t->live ? t->lb.ents : nullptr, l);
+  }
+  VBT_HIP_CHECK(hipGetLastError());
+  t->view_clip = -1;
   return VBT_OK;
 }
 
@@ -1966,14 +2016,51 @@ int vbt_tracker_finish(vbt_tracker* t, double plate_diameter, double diff_thresh
   RoctxRange range("vbt:finish");
   if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  select_gather_kernel<<<t->n_clips, 64, 0, st>>>(t->states, t->rows, t->rows_cap, t->cols, t->T, t->best);
+  select_gather_kernel<<<t->n_clips, 64, 0, st>>>(t->states, t->rows, t->rows_cap, t->cols, t->T, t->best, ClipList{});
   VtParams vp{plate_diameter, diff_threshold, min_distance, 1, 1};
-  analyze_kernel<<<t->n_clips, 64, 0, st>>>(t->cols, t->T, t->rows_cap, vp, t->scratch, t->phases, t->nph);
+  analyze_kernel<<<t->n_clips, 64, 0, st>>>(t->cols, t->T, t->rows_cap, vp, t->scratch, t->phases, t->nph, ClipList{});
   VBT_HIP_CHECK(hipGetLastError());
   t->finished = true;
   t->finish_stream = st;
   return VBT_OK;
 }
+
+}  // extern "C"
+
+namespace vbt {
+
+int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips) {
+  if (!clips || n < 1) { set_error("%s: a list of at least one clip required", fn); return VBT_ERR_ARG; }
+  std::vector<char> seen((size_t)n_clips, 0);
+  for (int i = 0; i < n; i++) {
+    const int c = clips[i];
+    if (c < 0 || c >= n_clips) { set_error("%s: clip %d outside the %d clips", fn, c, n_clips); return VBT_ERR_ARG; }
+    if (seen[(size_t)c]) { set_error("%s: clip %d listed twice", fn, c); return VBT_ERR_ARG; }
+    seen[(size_t)c] = 1;
+  }
+  return VBT_OK;
+}
+
+int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
+                        unsigned char* head, void* out_rows, hipStream_t st) {
+  RoctxRange range("vbt:close_clips");
+  const VtParams vp{plate_diameter, diff_threshold, min_distance, 1, 1};
+  for (int i0 = 0; i0 < n; i0 += CLIP_LIST) {
+    ClipList l{};
+    l.n = std::min(CLIP_LIST, n - i0);
+    for (int i = 0; i < l.n; i++) l.clip[i] = clips[i0 + i];
+    select_gather_kernel<<<l.n, 64, 0, st>>>(t->states, t->rows, t->rows_cap, t->cols, t->T, t->best, l);
+    analyze_kernel<<<l.n, 64, 0, st>>>(t->cols, t->T, t->rows_cap, vp, t->scratch, t->phases, t->nph, l);
+    pack_summary_kernel<<<l.n, 64, 0, st>>>(t->states, t->best, t->nph, t->phases, MAXPH, head, l);
+    close_rows_kernel<<<l.n, 64, 0, st>>>(t->states, t->rows, t->rows_cap, l, (Row*)out_rows);
+  }
+  VBT_HIP_CHECK(hipGetLastError());
+  return vbt_tracker_reset_clips(t, clips, n, (void*)st);
+}
+
+}  // namespace vbt
+
+extern "C" {
 
 int vbt_tracker_phases(vbt_tracker* t, int clip, int32_t* best_id, double* phases6, int cap, int* P) {
   if (!t || !best_id || !phases6 || !P || clip < 0 || clip >= t->n_clips) { set_error("bad argument"); return VBT_ERR_ARG; }
@@ -2010,7 +2097,7 @@ int vbt_analyze(const double* cols7, int T, int preprocess, int flush, double pl
   VBT_HIP_CHECK(hipMemcpy(dc, cols7, sizeof(double) * 7 * T, hipMemcpyHostToDevice));
   VBT_HIP_CHECK(hipMemcpy(dT, &T, sizeof(int), hipMemcpyHostToDevice));
   VtParams vp{plate_diameter, diff_threshold, min_distance, preprocess, flush};
-  analyze_kernel<<<1, 64>>>(dc, dT, T, vp, ds, dp, dn);
+  analyze_kernel<<<1, 64>>>(dc, dT, T, vp, ds, dp, dn, ClipList{});
   int n = 0;
   hipError_t e = hipMemcpy(&n, dn, sizeof(int), hipMemcpyDeviceToHost);
   int rc = VBT_OK;
@@ -2066,7 +2153,7 @@ int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int3
     t->summary_bytes = bytes;
   }
   hipStream_t st = t->finish_stream;
-  pack_summary_kernel<<<n, 64, 0, st>>>(t->states, t->best, t->nph, t->phases, cap, t->d_summary);
+  pack_summary_kernel<<<n, 64, 0, st>>>(t->states, t->best, t->nph, t->phases, cap, t->d_summary, ClipList{});
   VBT_HIP_CHECK(hipMemcpyAsync(t->h_summary, t->d_summary, bytes, hipMemcpyDeviceToHost, st));
   VBT_HIP_CHECK(hipStreamSynchronize(st));
   for (int c = 0; c < n; c++) {

@@ -54,6 +54,12 @@ class MultiClipTracker:
     def reset(self):
         _lib.check(_lib.lib().vbt_tracker_reset(self._h))
 
+    def reset_clips(self, clips, stream=None):
+        """A fresh clip in each listed slot (ids restart at 1, empty row log, frame counter 0, live state re-initialised); the other
+        clips are untouched.  Enqueued on `stream` (default: the null stream, which update_frames uses)."""
+        cl = np.ascontiguousarray(np.atleast_1d(np.asarray(clips, np.int32)))
+        _lib.check(_lib.lib().vbt_tracker_reset_clips(self._h, cl.ctypes.data, len(cl), stream))
+
     def update_frames(self, dets, counts, times):
         """dets [F,n_clips,25,6] float64, counts [F,n_clips] int32, times [F,n_clips] float64."""
         dets = np.ascontiguousarray(dets, np.float64)

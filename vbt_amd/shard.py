@@ -84,6 +84,63 @@ def run_schedule(lengths, n_slots, max_run=None):
     return steps
 
 
+def stream_schedule(lengths, concurrent, n_slots, groups=None):
+    """Clips that arrive one after the other, run through `concurrent` tracker slots and a detector batch of `n_slots` frames
+    (vbt_pipeline_close_clips: a slot is closed when its clip ends and the next clip opens in it).  Clip c has lengths[c] frames and
+    source group groups[c] (its resolution: one step carries one group only).  Clips open in input order, group after group in the
+    order the groups first appear, into the lowest free slot; a new group opens once every clip of the previous one has closed.
+    Each step shares the batch evenly among the open clips (a clip takes no more than it has left; what it leaves goes to the others).
+    Returns a list of steps (opens, runs, closes): opens [(slot, clip)] before the step, runs [(slot, slot0, n_frames, frame0)]
+    (frame0 1-based, within the clip) covering batch slots 0..B-1 in slot order, closes [slot] after it (the clips that ended)."""
+    if int(concurrent) < 1 or int(n_slots) < 1:
+        raise ValueError("stream_schedule: concurrent and n_slots must be at least 1")
+    lengths = [int(n) for n in lengths]
+    if any(n < 0 for n in lengths):
+        raise ValueError("stream_schedule: negative clip length")
+    groups = list(groups) if groups is not None else [0] * len(lengths)
+    first_seen = {}
+    for c, g in enumerate(groups):
+        first_seen.setdefault(g, c)
+    queue = sorted((c for c in range(len(lengths)) if lengths[c] > 0), key=lambda c: (first_seen[groups[c]], c))
+    free = list(range(int(concurrent)))
+    open_ = {}                                       # slot -> [clip, frames handed out]
+    steps = []
+    while queue or open_:
+        opens = []
+        group = groups[open_[min(open_)][0]] if open_ else groups[queue[0]]
+        while queue and free and groups[queue[0]] == group:
+            slot = min(free)
+            free.remove(slot)
+            c = queue.pop(0)
+            open_[slot] = [c, 0]
+            opens.append((slot, c))
+        slots = sorted(open_)
+        left = {s: lengths[open_[s][0]] - open_[s][1] for s in slots}
+        give = dict.fromkeys(slots, 0)
+        budget = int(n_slots)
+        while budget > 0:
+            hungry = [s for s in slots if give[s] < left[s]]
+            if not hungry:
+                break
+            share = max(budget // len(hungry), 1)
+            for s in hungry:
+                g = min(share, left[s] - give[s], budget)
+                give[s] += g
+                budget -= g
+        runs, slot0 = [], 0
+        for s in slots:
+            if give[s]:
+                runs.append((s, slot0, give[s], open_[s][1] + 1))
+                slot0 += give[s]
+                open_[s][1] += give[s]
+        closes = [s for s in slots if open_[s][1] == lengths[open_[s][0]]]
+        for s in closes:
+            del open_[s]
+            free.append(s)
+        steps.append((opens, runs, closes))
+    return steps
+
+
 def gather_records(rec, dist, pad_to):
     """rec: tensor [n_i, k] of this rank's records (n_i <= pad_to).  Returns the valid rows of all ranks
     (numpy) on every rank via ONE all_gather of equal-size blocks (row 0 of each block carries n_i)."""

@@ -96,6 +96,55 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return pipe.rows(0)
 
 
+def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0):
+    """track_frames() for many clips through ONE pipeline: `concurrent` tracker slots, `time_batch` detector slots per step.  Each
+    step hands runs of consecutive frames to the open clips (shard.stream_schedule); a clip whose frames are used up is closed in its
+    slot (Pipeline.close_clips) and the next source opens there.  Only clips of one source resolution are open together (the
+    resize is set per step).  sources: uint8 [T,H,W,3] arrays (numpy / memmap); fps: one value or one per source.
+    Yields (index, rows) as clips finish - rows = the dict track_frames returns for that source."""
+    from .shard import stream_schedule
+    sources = list(sources)
+    fps_of = np.broadcast_to(np.asarray(fps, np.float64), (len(sources),))
+    stride = max(int(frame_stride), 1)
+    kept = [int(s.shape[0]) // stride for s in sources]
+    hw = [(int(s.shape[1]), int(s.shape[2])) for s in sources]
+    for i in range(len(sources)):
+        if kept[i] == 0:
+            yield i, {k: [] for k in COLUMNS}
+    if not any(kept):
+        return
+    pipe = Pipeline(model_path, max(1, int(time_batch)), max_frames=max(kept), fps=fps_of[0], detection_treshold=detection_treshold,
+                    device=device, rows_per_frame=25, tracker_clips=int(concurrent), slot_close=True)
+    size = pipe._size
+    clip_of = {}                                     # tracker slot -> source index of the clip open in it
+    unread = {}                                      # tracker slot -> source index of its close not read yet
+    for opens, runs, closes in stream_schedule(kept, int(concurrent), pipe.n, groups=hw):
+        for slot, i in opens:
+            clip_of[slot] = i
+            pipe.fps[slot] = fps_of[i]
+        i0 = clip_of[runs[0][0]]
+        src_hw = None if hw[i0] == (size, size) else hw[i0]
+        chunks = []
+        for slot, _, n, f0 in runs:
+            a = sources[clip_of[slot]]
+            first = f0 * stride - 1                  # 0-based index of the run's first kept frame
+            chunks.append(np.ascontiguousarray(a[first:first + (n - 1) * stride + 1:stride], dtype=np.uint8))
+        pipe.step_runs(chunks, [(slot, slot0, n, f0 * stride, stride) for slot, slot0, n, f0 in runs], src_hw=src_hw)
+        for slot in list(unread):                    # results the device has finished (never waits)
+            got = pipe.closed(slot, wait=False)
+            if got is not None:
+                yield unread.pop(slot), got[1]
+        if closes:
+            for slot in closes:                      # a slot's previous result is read before the slot closes again: waits only if
+                if slot in unread:                   # that close, a whole clip ago, is still not done
+                    yield unread.pop(slot), pipe.closed(slot, wait=True)[1]
+            pipe.close_clips(closes)
+            for slot in closes:
+                unread[slot] = clip_of.pop(slot)
+    for slot in sorted(unread):
+        yield unread[slot], pipe.closed(slot, wait=True)[1]
+
+
 def export_dataframe(data, src_name, model_path, df_dir=None, write=True):
     """reference track.py:103-126: sort by (id,time) keeping the original row labels, pick the id with
     the largest cumulative path length, name the file f'{video}_id{id}_{model}.pkl.gz'."""
@@ -154,7 +203,7 @@ class Pipeline:
     convenience for callers who hold them - torch tensors (device or pinned host).  torch is never imported here."""
 
     def __init__(self, model_path, n_clips, max_frames, fps=60.0, detection_treshold=0.5, device=0, rows_per_frame=4,
-                 plate_diameter=0.45, depth=None, tracker_clips=None):
+                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False):
         L = _lib.lib()
         self.n = int(n_clips)                       # slots of the detector batch
         # tracker_clips > n_clips: more clips than batch slots; step(clip_map=...) says which clip sits in which slot
@@ -185,6 +234,8 @@ class Pipeline:
         _lib.check(rc)
         self._owner = _PipelineHandle(h)            # shared with the borrowed Interpreter / tracker views: the library object lives as long as any of them
         self._h = h
+        if slot_close:                              # close_clips() / closed(): their buffers now, so that no close allocates
+            _lib.check(L.vbt_pipeline_close_clips_enable(self._h))
         info = self.info()
         self.depth, self._ring, self._defer, self._trk_inline = info.depth, info.ring, info.defer, bool(info.tracker_inline)
         self._size = info.image_size
@@ -417,6 +468,37 @@ class Pipeline:
         ph = np.zeros((n, cap, 6), np.float64)
         _lib.check(_lib.lib().vbt_pipeline_close(self._h, best.ctypes.data, rows.ctypes.data, nph.ctypes.data, ovf.ctypes.data, ph.ctypes.data, int(cap)))
         return best, rows, nph, ovf, ph
+
+    def close_clips(self, clips, next_fps=None):
+        """Slot close (a pipeline created with slot_close=True): the listed tracker slots' clips end while the others keep running, and
+        each slot starts a fresh clip (fps next_fps - one value or one per slot - or the slot's current one).  Only enqueues
+        (vbt_pipeline_close_clips); closed() reads a slot's result, and must have done so before the slot is closed again."""
+        cl = np.ascontiguousarray(np.atleast_1d(np.asarray(clips, np.int32)))
+        nf = None
+        if next_fps is not None:
+            nf = np.ascontiguousarray(np.broadcast_to(np.asarray(next_fps, np.float64), cl.shape))
+        _lib.check(_lib.lib().vbt_pipeline_close_clips(self._h, cl.ctypes.data, len(cl), nf.ctypes.data if nf is not None else None))
+        if nf is not None:
+            self.fps[cl] = nf
+
+    def closed(self, clip, wait=True):
+        """The result of slot `clip`'s last close_clips(): None while the device has not done it (wait=False), else
+        (best_id, rows, phases, overflow) - the export id of reference track.py:107-115, the clip's rows as rows() gives them, its
+        list[velocity.Phase] (plot.py:33-47) and the tracker's overflow flags; export_dataframe() takes the rows as they are."""
+        from .ocsort import _phase_list
+        rec = _lib.ClosedClip()
+        ready = ctypes.c_int()
+        ph = np.zeros((512, 6), np.float64)
+        rows = np.empty(self.tracker.rows_cap, ROW_DTYPE)
+        _lib.check(_lib.lib().vbt_pipeline_closed_clip(self._h, int(clip), int(bool(wait)), ctypes.byref(ready), ctypes.byref(rec), ph.ctypes.data,
+                                                       len(ph), rows.ctypes.data, len(rows)))
+        if not ready.value:
+            return None
+        r = rows[:rec.n_rows]
+        d = {"id": r["id"].tolist()}
+        for nm in COLUMNS[1:]:
+            d[nm] = r[nm].tolist()
+        return int(rec.best_id), d, _phase_list(ph[:rec.n_phases]), int(rec.overflow)
 
     def rows_all(self, cap=None, out=None):
         """DataFrame rows of every clip, one strided copy (after close() / finish()): (counts[n], rows[n, cap] of ROW_DTYPE).  `out`:
