@@ -42,6 +42,20 @@ int vbt_model_num_launches(const vbt_model* m);
 /* Parity/debug: copy graph tensor `tensor_id` ([B,H,W,C] int8) of the last vbt_detect to host. */
 int vbt_model_read_tensor(vbt_model* m, int tensor_id, int B, int8_t* host_out);
 
+/* The plan space: what a plan file (VBT_PLAN_FILE) may select, as the loader checks it.  One entry per step of every alternative
+ * of every group, in that order; `variants` lists the values a file may name for that step.  *n = the number of entries; a `cap`
+ * below it, or a step with more than 48 variants, is VBT_ERR_CAPACITY (nothing is truncated; *n still says how many are needed). */
+typedef struct {
+  int group, alt, step;
+  int chosen;             /* 1 if `alt` is the group's current alternative */
+  int variant;            /* this step's current variant */
+  int first_op, last_op;  /* lowest and highest graph op the step evaluates */
+  char family[32];        /* kernel family, as the plan file spells it */
+  int n_variants;
+  int variants[48];
+} vbt_plan_step_space;
+int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, int* n);
+
 /* ------------------------------------------------------------------ stream placement probe ----------------------------- */
 /* *shared = 1 when the two streams sit on one hardware queue (their kernels cannot overlap): a single wave spins `us`
  * microseconds on each and the pair is timed.  The device must be otherwise idle. */

@@ -67,6 +67,13 @@ class StepTime(ctypes.Structure):
                 ("algorithmic_bytes", c_double), ("macs", c_double)]
 
 
+class PlanStepSpace(ctypes.Structure):
+    """vbt_plan_step_space (include/vbt_hip_diag.h): one step of one alternative of one plan group and what a plan file may select for it"""
+    _fields_ = [("group", c_int), ("alt", c_int), ("step", c_int), ("chosen", c_int), ("variant", c_int), ("first_op", c_int),
+                ("last_op", c_int), ("family", ctypes.c_char * 32),
+                ("n_variants", c_int), ("variants", c_int * 48)]
+
+
 _SIGS = {
     "vbt_last_error": (c_char_p, []),
     "vbt_device_count": (c_int, []),
@@ -85,6 +92,7 @@ _SIGS = {
     "vbt_stream_destroy": (c_int, [c_void_p]),
     "vbt_streams_share_queue": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_model_read_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "vbt_model_plan_space": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_model_kernel_stats": (c_int, [c_void_p, c_int, ctypes.POINTER(KernelStat), c_int, ctypes.POINTER(c_int)]),
     "vbt_model_profile": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int]),

@@ -2329,9 +2329,9 @@ static void autotune(vbt_model* m) {
 // alternative added, removed or re-ordered: the bare indices of format 1 would still load and silently select other kernels) is
 // refused and the plan re-tuned.  Format 1 ("<ngroups>" then "<chosen> <nsteps> <variant>...") is still read - the group and step
 // counts are all it can be checked against - and re-written in format 2 when VBT_PLAN_CONVERT is set.
-static bool load_plan(vbt_model* m, const char* path) {
-  // the shape a file may select from: this library's groups, their alternatives, the family of every step and the variants that resolve
-  // for it (container_parse.h: parse_plan_file refuses everything else, and the model is tuned afresh)
+// The shape a file may select from: this library's groups, their alternatives, the family of every step and the variants that resolve
+// for it (container_parse.h: parse_plan_file refuses everything else, and the model is tuned afresh).  vbt_model_plan_space reports it.
+static PlanShape plan_shape(const vbt_model* m) {
   PlanShape shape;
   for (const Group& g : m->groups) {
     std::vector<std::vector<PlanStepShape>> alts;
@@ -2354,6 +2354,10 @@ static bool load_plan(vbt_model* m, const char* path) {
     }
     shape.groups.push_back(alts);
   }
+  return shape;
+}
+static bool load_plan(vbt_model* m, const char* path) {
+  const PlanShape shape = plan_shape(m);
   std::vector<PlanChoice> sel;
   std::string note;
   if (!parse_plan_file(path, shape, &sel, &note)) {
@@ -2478,6 +2482,43 @@ int vbt_model_tensor_materialized(const vbt_model* m, int id) {
 }
 
 int vbt_model_num_launches(const vbt_model* m) { return m ? (int)m->steps.size() : VBT_ERR_ARG; }
+
+int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, int* n) {
+  if (!m || !n || cap < 0 || (cap > 0 && !out)) { set_error("vbt_model_plan_space: bad argument"); return VBT_ERR_ARG; }
+  const PlanShape shape = plan_shape(m);
+  int total = 0;
+  for (const auto& alts : shape.groups)
+    for (const auto& steps : alts) total += (int)steps.size();
+  *n = total;
+  if (total > cap) { set_error("plan space: %d steps, buffer holds %d", total, cap); return VBT_ERR_CAPACITY; }
+  int i = 0;
+  for (size_t gi = 0; gi < shape.groups.size(); gi++)
+    for (size_t ai = 0; ai < shape.groups[gi].size(); ai++)
+      for (size_t si = 0; si < shape.groups[gi][ai].size(); si++, i++) {
+        const PlanStepShape& ps = shape.groups[gi][ai][si];
+        vbt_plan_step_space& o = out[i];
+        memset(&o, 0, sizeof(o));
+        if (ps.variants.size() > sizeof(o.variants) / sizeof(o.variants[0])) {
+          set_error("plan space: group %zu alternative %zu step %zu has %zu variants", gi, ai, si, ps.variants.size());
+          return VBT_ERR_CAPACITY;
+        }
+        o.group = (int)gi; o.alt = (int)ai; o.step = (int)si;
+        o.chosen = m->groups[gi].chosen == (int)ai;
+        const Step& st = m->groups[gi].alts[ai].steps[si];
+        o.variant = st.variant;
+        o.first_op = (int)m->ops.size(); o.last_op = -1;
+        std::function<void(const Step&)> span = [&](const Step& s) {
+          for (int op : {s.op, s.e_op, s.d_op, s.p_op, s.a_op, s.sum_op})
+            if (op >= 0) { o.first_op = std::min(o.first_op, op); o.last_op = std::max(o.last_op, op); }
+          for (const Step& mb : s.members) span(mb);
+        };
+        span(st);
+        snprintf(o.family, sizeof(o.family), "%s", ps.family.c_str());
+        o.n_variants = (int)ps.variants.size();
+        std::copy(ps.variants.begin(), ps.variants.end(), o.variants);
+      }
+  return VBT_OK;
+}
 
 int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, vbt_model** out) {
   if (!path || !out || max_batch < 1) { set_error("vbt_model_create: bad argument"); return VBT_ERR_ARG; }

@@ -99,6 +99,19 @@ class Interpreter:
     def num_launches(self):
         return _lib.lib().vbt_model_num_launches(self._h)
 
+    def plan_space(self):
+        """Every step of every alternative of every plan group, in that order, as a dict: group, alt, step, chosen (the group's
+        current alternative), variant (the step's current one), first_op / last_op (the graph ops it evaluates), family, and
+        variants (what a plan file may name for the step: vbt_model_plan_space)."""
+        n = ctypes.c_int()
+        rc = _lib.lib().vbt_model_plan_space(self._h, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):       # VBT_ERR_CAPACITY: the count of entries is in n
+            _lib.check(rc)
+        buf = (_lib.PlanStepSpace * max(n.value, 1))()
+        _lib.check(_lib.lib().vbt_model_plan_space(self._h, buf, n.value, ctypes.byref(n)))
+        return [{"group": e.group, "alt": e.alt, "step": e.step, "chosen": bool(e.chosen), "variant": e.variant, "first_op": e.first_op,
+                 "last_op": e.last_op, "family": e.family.decode(), "variants": list(e.variants[:e.n_variants])} for e in buf[:n.value]]
+
     def read_tensor(self, tid, B):
         shp = (ctypes.c_int * 3)()
         _lib.check(_lib.lib().vbt_model_tensor_shape(self._h, tid, shp))
