@@ -396,6 +396,62 @@ int vbt_analyze(const double* cols7, int T, int preprocess, int flush, double pl
  * Replaces the smoothing of reference plot.py:90-95, kinovea.py:99-105 and qualysis.py:113-117. */
 int vbt_window_means(const double* rows, int T, int ncols, const int32_t* windows, double* out, int device);
 
+/* ------------------------------------------------------------------ detector evaluation -----
+ * Replaces the device-worthy part of the reference's eval.py: scaled_bbox / calculate_iou / match_bboxes for every image
+ * (eval.py:57-71,74-93,96-153,182-205) and the curves scikit-learn computes for it (eval.py:232,245,360,370,515).
+ * One handle holds ONE model's detection table on the device: rows (score float32, IoU float64, image number, detection index,
+ * padded-matrix row) in the order eval.py:194-205 emits them for that model - images in the order they were added, inside an image
+ * in idx_gt order, i.e. ground-truth rows first, then the dummy rows scipy's tie rule orders. */
+typedef struct vbt_eval vbt_eval;
+#define VBT_EVAL_MAX_GT 64          /* ground-truth boxes per image (the assignment solver's side) */
+#define VBT_EVAL_NO_POSITIVES 1     /* no row with IoU > iou_threshold: recall, tpr, AP and AUC are NaN */
+#define VBT_EVAL_NO_NEGATIVES 2     /* no row with IoU <= iou_threshold: fpr and AUC are NaN */
+typedef struct {
+  int32_t n_rows, n_pos, n_neg;   /* rows of the table, rows labelled True / False */
+  int32_t n_pr;                   /* points of the PR curve (distinct scores + 1); it has n_pr - 1 thresholds */
+  int32_t n_roc;                  /* points of the ROC curve after drop_intermediate, the leading (0, 0) included */
+  int32_t flags;                  /* VBT_EVAL_NO_* */
+  double ap, auc;                 /* average_precision_score, roc_auc_score (eval.py:245,370) */
+} vbt_eval_summary;
+/* max_batch: images per vbt_eval_add_detections call (1..4096); rows_cap: rows the table holds (25 per image is the most). */
+int vbt_eval_create(int device, int max_batch, int rows_cap, vbt_eval** out);
+void vbt_eval_destroy(vbt_eval* e);
+/* an empty table again (synchronises the device) */
+int vbt_eval_reset(vbt_eval* e);
+/* The detections of B images as vbt_detect_async / vbt_pipeline_step_runs leave them on the device (boxes float32 [B,25,4]
+ * normalised ymin,xmin,ymax,xmax, scores float32 [B,25], counts int32 [B]; every counted detection takes part: run_odt at
+ * threshold 0, eval.py:176-180) matched against the images' ground truth and appended to the table: eval.py:182-205 for one model.
+ * hw_host int32 [B][2] = the source image's (height, width) (eval.py:174,183-184); ground truth in CSR form: image b owns boxes
+ * gt_offsets_host[b] .. gt_offsets_host[b+1]-1 of gt_boxes_host int32 [*][4] = ymin,xmin,ymax,xmax (create_bbox, eval.py:42-54).
+ * Enqueue only, on `stream`: the host arrays are copied into pinned staging during the call and go up in ONE small copy per call
+ * (four uploads may be in flight; a fifth call waits for the first).  Calls on one handle run in call order whatever their streams:
+ * a call on another stream than the last one first makes its stream wait for the last call's kernels (the handle's scratch and table
+ * are shared).  Box corners must be finite (numpy's astype(int) of a NaN / inf corner has no counterpart here).  VBT_ERR_CAPACITY, with nothing enqueued: B > max_batch, or an
+ * image with more than VBT_EVAL_MAX_GT boxes (the message names it).  Rows beyond rows_cap are counted, not stored, and reported
+ * as VBT_ERR_CAPACITY by vbt_eval_table / vbt_eval_curves. */
+int vbt_eval_add_detections(vbt_eval* e, const float* boxes_dev, const float* scores_dev, const int32_t* counts_dev, int B,
+                            const int32_t* hw_host, const int32_t* gt_offsets_host, const int32_t* gt_boxes_host, void* stream);
+/* The table (the columns of the DataFrame of eval.py:207-211 plus the indices match_bboxes returns, eval.py:153): *n_rows always;
+ * with any array non-NULL one copy per array, cap rows each (VBT_ERR_CAPACITY if cap < *n_rows).  gt_idx >= the image's number of
+ * boxes marks a detection the assignment gave to a dummy row.  Synchronises the stream of the last vbt_eval_add_detections. */
+int vbt_eval_table(vbt_eval* e, int* n_rows, float* scores, double* ious, int32_t* image, int32_t* det_idx, int32_t* gt_idx, int cap);
+/* Label = IoU > iou_threshold (eval.py:515), then over the device table, without copying it:
+ *   precision_recall_curve (eval.py:232): precision / recall [n_pr] ending in the (1, 0) point, pr_thresholds [n_pr - 1] increasing;
+ *   average_precision_score (eval.py:245): ap = -sum(diff(recall) * precision[:-1]);
+ *   roc_curve, drop_intermediate=True (eval.py:360): fpr / tpr / roc_thresholds [n_roc], the first point (0, 0) at threshold +inf;
+ *   roc_auc_score (eval.py:370): auc by the trapezoid rule over those points.
+ * Every point is bit-identical to scikit-learn's; ap / auc differ from it by the summation order only.  A rate whose denominator is
+ * zero is NaN and `flags` says why (scikit-learn warns or raises there).  Scores must not be NaN.  Capacities in points;
+ * VBT_ERR_CAPACITY when n_pr > pr_cap or n_roc > roc_cap: *s is filled, the arrays are not, and the call can be repeated.
+ * Any array may be NULL.  Synchronises the stream of the last vbt_eval_add_detections. */
+int vbt_eval_curves(vbt_eval* e, double iou_threshold, vbt_eval_summary* s, double* precision, double* recall, float* pr_thresholds,
+                    int pr_cap, double* fpr, double* tpr, float* roc_thresholds, int roc_cap);
+/* The same for a table held by the caller (host pointers, n rows: the Score and IoU columns of a DataFrame written earlier,
+ * eval.py:510-512): upload, one launch, read-back.  No handle needed.  VBT_ERR_ARG: a NaN score. */
+int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, double iou_threshold, int device, vbt_eval_summary* s,
+                               double* precision, double* recall, float* pr_thresholds, int pr_cap, double* fpr, double* tpr,
+                               float* roc_thresholds, int roc_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,11 @@ class PipelineInfo(ctypes.Structure):
                 ("h2d_bytes", ctypes.c_uint64), ("step_host_ns", ctypes.c_uint64), ("step_calls", ctypes.c_uint64)]
 
 
+class EvalSummary(ctypes.Structure):
+    """vbt_eval_summary (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_rows", "n_pos", "n_neg", "n_pr", "n_roc", "flags")] + [("ap", c_double), ("auc", c_double)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int), ("algorithmic_bytes", c_double), ("macs", c_double)]
 
@@ -154,6 +159,14 @@ _SIGS = {
     "vbt_device_synchronize": (c_int, [c_int]),
     "vbt_analyze": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_int, ctypes.POINTER(c_int), c_int]),
     "vbt_window_means": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "vbt_eval_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_eval_destroy": (None, [c_void_p]),
+    "vbt_eval_reset": (c_int, [c_void_p]),
+    "vbt_eval_add_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_eval_table": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_eval_curves": (c_int, [c_void_p, c_double, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_eval_curves_from_table": (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int]),
 }
 
 

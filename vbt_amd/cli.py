@@ -1,4 +1,4 @@
-"""Command line mirror of the reference's two entry points, minus GUI/plotting:
+"""Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1] [--live]
                             [--concurrent N]
@@ -16,6 +16,12 @@
   python -m vbt_amd.cli validate [--kinovea_dir D | --qualysis_dir D] [--df_dir dfs] [--plate_diameter 0.45]
       reference kinovea.py:29-38,57-172,203-215 / qualysis.py:29-38,57-187 without the figures: per export with a
       matching {video}_id{N}_{model}.pkl.gz, MSE and Pearson r of x(t) and y(t) in metres, then the totals line.
+  python -m vbt_amd.cli eval MODELS... [--img_dir data/test] [--annotations_dir data/test] [--iou_threshold 0.5]
+                           [--detections_df dfs/eval_detections.pkl.gz] [--replace_df] [--score_thresholds "[0.2, 0.5]"] [--curve_dir DIR] [--rgb]
+      reference eval.py:471-521 without the figures: VOC annotations, every image through each model at threshold 0, Hungarian
+      matching and the PR / ROC curves on the GPU; writes (or, when it exists and --replace_df is not given, reads) the detections
+      DataFrame, prints AP and AUC per model as the reference's legends show them and, for each --score_thresholds value, the
+      closest curve point; --curve_dir writes the curve points as CSV.
 Option names (including the reference's `treshold` / `qualysis` spellings) and defaults follow the reference.
 """
 import os
@@ -182,6 +188,53 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter):
         rows_out.append((video, r))
         click.echo(f"{video}: MSEx {r['mse_x']:.4f}  MSEy {r['mse_y']:.4f}  r_x {r['r_x']:.4f}  r_y {r['r_y']:.4f}")
     click.echo(f"Total MSEx = {sum(r['mse_x'] for _, r in rows_out)}, MSEy = {sum(r['mse_y'] for _, r in rows_out)}")
+
+
+@main.command(name="eval")
+@click.argument("models", type=str, nargs=-1)
+@click.option("--img_dir", default="data/test", show_default=True, help="Directory containing the test images (.jpg / .png / .npy).")
+@click.option("--annotations_dir", default="data/test", show_default=True, help="Directory containing the XML annotation files.")
+@click.option("--iou_threshold", default=0.5, show_default=True, type=float,
+              help="Intersection over union threshold to label detections as correct or not against the ground truth bounding boxes.")
+@click.option("--detections_df", default="dfs/eval_detections.pkl.gz", show_default=True, help="Path for storing/reading the detection results dataframe.")
+@click.option("--replace_df", is_flag=True, help="If exists, replace the detections dataframe.")
+@click.option("--score_thresholds", default="[]", show_default=True, help='List of score thresholds to locate on the curves, e.g. "[0.2, 0.5]".')
+@click.option("--curve_dir", default=None, show_default=True, help="Directory for the curve points as CSV. If not set they are not written.")
+@click.option("--rgb", is_flag=True, help="Feed RGB to the network (the reference's eval.py feeds cv2's BGR unswapped; that is the default).")
+def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb):
+    import ast
+    import pandas as pd
+    from . import evaluate as E
+    try:
+        score_thresholds = list(ast.literal_eval(score_thresholds))                # reference eval.py:26-39
+    except (ValueError, SyntaxError, TypeError):
+        raise click.BadParameter(score_thresholds)
+    if not os.path.exists(detections_df) or replace_df:                            # reference eval.py:506-512
+        click.echo(f"Creating dataframe '{detections_df}'.")
+        annotations = E.read_annotations(annotations_dir)
+        df = E.create_detections_df(models, img_dir, annotations, detections_df, rgb=rgb)
+    else:
+        click.echo(f"Loading dataframe '{detections_df}'.")
+        df = pd.read_pickle(detections_df)
+    if curve_dir is not None:
+        os.makedirs(curve_dir, exist_ok=True)
+    for m, c in E.curves(df, iou_threshold).items():
+        click.echo(f"{m}, AP_{iou_threshold * 100:0.0f}={c.ap:.4f}, AUC={c.auc:.4f}  ({c.n_rows} rows, {c.n_pos} correct)")   # eval.py:261,388
+        if c.flags:
+            click.echo(f"{m}: " + " and ".join(t for b, t in ((E.NO_POSITIVES, "no correct detection"), (E.NO_NEGATIVES, "no incorrect detection"))
+                                              if c.flags & b) + " at this IoU threshold: the rates without a denominator are NaN", err=True)
+        for v in score_thresholds:
+            if len(c.pr_thresholds):
+                i = E.closest_point(c.pr_thresholds, v)                            # reference eval.py:313-321
+                click.echo(f"  PR  threshold {c.pr_thresholds[i]:.4f}: precision {c.precision[i]:.4f}  recall {c.recall[i]:.4f}")
+            j = E.closest_point(c.roc_thresholds, v)                               # reference eval.py:443-451
+            click.echo(f"  ROC threshold {c.roc_thresholds[j]:.4f}: FP rate {c.fpr[j]:.4f}  TP rate {c.tpr[j]:.4f}")
+        if curve_dir is not None:
+            thr = np.r_[c.pr_thresholds, c.pr_thresholds[-1:]] if len(c.pr_thresholds) else np.full(len(c.precision), np.nan)   # eval.py:235
+            pd.DataFrame({"Precision": c.precision, "Recall": c.recall, "Threshold": thr, "Model": m}).to_csv(
+                os.path.join(curve_dir, f"precision_recall_{m}_iou_{iou_threshold}.csv"), index=False)
+            pd.DataFrame({"FP Rate": c.fpr, "TP Rate": c.tpr, "Threshold": c.roc_thresholds, "Model": m}).to_csv(
+                os.path.join(curve_dir, f"roc_{m}_iou_{iou_threshold}.csv"), index=False)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,286 @@
+"""Detector evaluation - the reference's eval.py without the figures: VOC annotations, detections of every test image at threshold 0,
+Hungarian matching against the ground truth and precision-recall / ROC curves, AP and AUC per model.
+
+Matching and curves run on the GPU (`vbt_eval_*`, include/vbt_hip.h; vbt_amd/csrc/evaluate.hip); the detections never leave the
+device between the detector and the matcher.  No torch, no scipy, no scikit-learn.
+
+Images.  eval.py reads every image with cv2.imread and hands that **BGR** array to the network unswapped (eval.py:173-180;
+track.py:171 swaps, eval.py does not).  The default here reproduces that: `.jpg` / `.png` files are decoded with PIL and reordered to
+BGR, `.npy` files hold a decoded image uint8 [H,W,3] in cv2's BGR order; `rgb=True` (CLI `--rgb`) feeds RGB instead.  JPEG decoders
+differ in the low bits, so pixel parity with cv2 is not claimed for `.jpg` sources.
+"""
+import ctypes
+import os
+import xml.etree.ElementTree as ET
+
+import numpy as np
+
+from . import _lib
+from .mem import DeviceBuffer
+
+LABEL = "barbell"                  # eval.py:23
+MAX_DETECTIONS = 25
+MAX_GT = 64                        # VBT_EVAL_MAX_GT
+NO_POSITIVES, NO_NEGATIVES = 1, 2  # VBT_EVAL_NO_*
+BATCH = 64
+
+
+class Annotations(dict):
+    """{filename: int array [n,4] = ymin,xmin,ymax,xmax} as eval.py:487-504 builds it, in sorted file order, plus
+    `.sizes` = {filename: (height, width)} from the XML's <size> element (None when the file has none)."""
+
+    def __init__(self):
+        super().__init__()
+        self.sizes = {}
+
+
+def read_annotations(annotations_dir, label=LABEL):
+    """eval.py:487-504: every *.xml of the directory (VOC), objects whose <name> is not `label` skipped."""
+    out = Annotations()
+    for f in sorted(os.listdir(annotations_dir)):
+        if not f.endswith(".xml"):
+            continue
+        root = ET.parse(os.path.join(annotations_dir, f)).getroot()
+        key = root.find("filename").text
+        boxes = []
+        for o in root.findall("object"):
+            if o.find("name").text != label:
+                continue
+            bb = o.find("bndbox")
+            boxes.append([bb.find(k).text for k in ("ymin", "xmin", "ymax", "xmax")])
+        out[key] = np.array(boxes, dtype=int).reshape(-1, 4)
+        size = root.find("size")
+        out.sizes[key] = (int(size.find("height").text), int(size.find("width").text)) if size is not None else None
+    return out
+
+
+def find_image(img_dir, filename):
+    """the annotation's <filename> inside img_dir, or the same stem as .npy / .png / .jpg"""
+    stem = os.path.splitext(filename)[0]
+    for cand in (filename, stem + ".npy", stem + ".png", stem + ".jpg"):
+        p = os.path.join(img_dir, cand)
+        if os.path.isfile(p):
+            return p
+    raise FileNotFoundError(f"{os.path.join(img_dir, filename)}: no such image (also tried .npy / .png / .jpg)")
+
+
+def load_image(path):
+    """uint8 [H,W,3] in BGR order (see the module docstring)."""
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError(f"{path}: expected uint8 [H,W,3], got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError(f"{path}: reading .jpg / .png images needs PIL (pillow); store the decoded image as .npy uint8 [H,W,3] instead") from None
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+class CurveResult:
+    """precision, recall, pr_thresholds (precision_recall_curve); fpr, tpr, roc_thresholds (roc_curve); ap, auc; n_rows, n_pos,
+    n_neg; flags (NO_POSITIVES / NO_NEGATIVES: the rates and scalars that have no denominator are NaN)."""
+
+    def __init__(self, s, arrays):
+        self.n_rows, self.n_pos, self.n_neg, self.flags, self.ap, self.auc = s.n_rows, s.n_pos, s.n_neg, s.flags, s.ap, s.auc
+        self.precision, self.recall, self.pr_thresholds, self.fpr, self.tpr, self.roc_thresholds = arrays
+
+
+def _curve_call(fn, n_rows):
+    """run fn(summary, six arrays, capacities): n_rows + 1 points are always enough"""
+    cap = int(n_rows) + 1
+    p, r, f, t = (np.empty(cap, np.float64) for _ in range(4))
+    pt, rt = np.empty(cap, np.float32), np.empty(cap, np.float32)
+    s = _lib.EvalSummary()
+    _lib.check(fn(ctypes.byref(s), p.ctypes.data, r.ctypes.data, pt.ctypes.data, cap, f.ctypes.data, t.ctypes.data, rt.ctypes.data, cap))
+    return CurveResult(s, (p[:s.n_pr].copy(), r[:s.n_pr].copy(), pt[:s.n_pr - 1].copy(), f[:s.n_roc].copy(), t[:s.n_roc].copy(), rt[:s.n_roc].copy()))
+
+
+def curves_from_table(scores, ious, iou_threshold=0.5, device=0):
+    """vbt_eval_curves_from_table: curves of one model's table (Score float32, IoU float64) held by the caller."""
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    io = np.ascontiguousarray(ious, dtype=np.float64)
+    if sc.shape != io.shape or sc.ndim != 1:
+        raise ValueError("scores and ious must be one-dimensional and of one length")
+    L = _lib.lib()
+    return _curve_call(lambda s, *a: L.vbt_eval_curves_from_table(sc.ctypes.data, io.ctypes.data, len(sc), float(iou_threshold), int(device), s, *a),
+                       len(sc))
+
+
+class Evaluator:
+    """One model's detection table on the device (`vbt_eval`, include/vbt_hip.h)."""
+
+    def __init__(self, rows_cap, max_batch=BATCH, device=0):
+        self._h = ctypes.c_void_p()
+        self.rows_cap, self.max_batch, self.device = int(rows_cap), int(max_batch), int(device)
+        _lib.check(_lib.lib().vbt_eval_create(self.device, self.max_batch, self.rows_cap, ctypes.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.lib().vbt_eval_destroy(self._h)
+            self._h = None
+
+    def reset(self):
+        _lib.check(_lib.lib().vbt_eval_reset(self._h))
+
+    def add(self, boxes_ptr, scores_ptr, counts_ptr, hw, gt_list, stream=None):
+        """B images' detections (raw device pointers, the detector's layout) + per image (height, width) and ground-truth boxes
+        int [n,4] = ymin,xmin,ymax,xmax.  Enqueue only."""
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        B = len(hw)
+        if len(gt_list) != B:
+            raise ValueError("one ground-truth array per image")
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum([len(g) for g in gt_list])
+        gt = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int64).reshape(-1, 4) for g in gt_list]) if B else np.zeros((0, 4)), dtype=np.int32)
+        _lib.check(_lib.lib().vbt_eval_add_detections(self._h, boxes_ptr, scores_ptr, counts_ptr, B, hw.ctypes.data, off.ctypes.data,
+                                                      gt.ctypes.data if len(gt) else None, stream))
+
+    def table(self):
+        """{"score" f32, "iou" f64, "image" i32, "det_idx" i32, "gt_idx" i32}, rows in emission order (synchronises)."""
+        L = _lib.lib()
+        n = ctypes.c_int(0)
+        _lib.check(L.vbt_eval_table(self._h, ctypes.byref(n), None, None, None, None, None, 0))
+        out = {"score": np.empty(n.value, np.float32), "iou": np.empty(n.value, np.float64), "image": np.empty(n.value, np.int32),
+               "det_idx": np.empty(n.value, np.int32), "gt_idx": np.empty(n.value, np.int32)}
+        if n.value:
+            _lib.check(L.vbt_eval_table(self._h, ctypes.byref(n), *(out[k].ctypes.data for k in ("score", "iou", "image", "det_idx", "gt_idx")), n.value))
+        return out
+
+    def curves(self, iou_threshold=0.5):
+        """vbt_eval_curves over the device table."""
+        L = _lib.lib()
+        return _curve_call(lambda s, *a: L.vbt_eval_curves(self._h, float(iou_threshold), s, *a), self.rows_cap)
+
+
+def match_bboxes(gt_bboxes, det_bboxes, device=0):
+    """match_bboxes of eval.py:96-153, same call shape and return value (idx_gt_actual, idx_pred_actual, ious_actual), on the device
+    kernel: integer boxes [n,4] = ymin,xmin,ymax,xmax.  At most 25 predictions and 64 ground-truth boxes (the kernel's sides);
+    coordinates below 2^24 in magnitude (they travel as float32)."""
+    gt = np.asarray(gt_bboxes).reshape(-1, 4).astype(np.int64)
+    det = np.asarray(det_bboxes).reshape(-1, 4).astype(np.int64)
+    if len(det) > MAX_DETECTIONS:
+        raise ValueError(f"match_bboxes: {len(det)} predictions, the device matcher takes {MAX_DETECTIONS}")
+    if len(det) and np.abs(det).max() >= 1 << 24:
+        raise ValueError("match_bboxes: box coordinates must be below 2^24 in magnitude")
+    boxes = np.zeros((1, MAX_DETECTIONS, 4), np.float32)
+    boxes[0, :len(det)] = det                                  # times (height, width) = (1, 1): the integers come back exactly
+    scores = np.zeros((1, MAX_DETECTIONS), np.float32)
+    bufs = [DeviceBuffer.from_host(a, device) for a in (boxes, scores, np.array([len(det)], np.int32))]
+    ev = Evaluator(MAX_DETECTIONS, 1, device)
+    ev.add(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, [(1, 1)], [gt])
+    t = ev.table()
+    return t["gt_idx"].astype(np.int64), t["det_idx"].astype(np.int64), t["iou"]
+
+
+def model_name(path):
+    return os.path.basename(path).split(".")[0]               # eval.py:188
+
+
+def image_size(path):
+    """(height, width) of an image file from its header, without decoding it"""
+    if path.endswith(".npy"):
+        shp = np.load(path, mmap_mode="r").shape
+        if len(shp) != 3 or shp[2] != 3:
+            raise ValueError(f"{path}: expected uint8 [H,W,3], got shape {shp}")
+        return int(shp[0]), int(shp[1])
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError(f"{path}: reading .jpg / .png images needs PIL (pillow); store the decoded image as .npy uint8 [H,W,3] instead") from None
+    with Image.open(path) as im:
+        return int(im.size[1]), int(im.size[0])
+
+
+def detections_table(model, images, annotations, rgb=False, device=0, batch=BATCH):
+    """One model over `images` = [(filename, path)]: every image through the pipeline's detector-only step at source resolution
+    (device resize), the detections handed to the matcher on the device.  Images are grouped by size (read from the file headers) and
+    decoded one batch at a time; at most 8 batches of host frames are alive at once.  Returns (table, image_names): table as
+    Evaluator.table(), its `image` column indexing image_names (the order the images were processed in, not the order given)."""
+    from .track import Pipeline
+    L = _lib.lib()
+    paths = dict(images)
+    groups = {}
+    for name, path in images:
+        groups.setdefault(image_size(path), []).append(name)
+    pipe = Pipeline(model, batch, max_frames=1, detection_treshold=0.0, device=device)
+    stream = ctypes.c_void_p()
+    _lib.check(L.vbt_stream_create(int(device), ctypes.byref(stream)))
+    ev = Evaluator(max(1, len(images)) * MAX_DETECTIONS, batch, device)
+    order, outs, alive = [], [], []                          # outs: device outputs, alive: host frames of steps in flight
+    try:
+        for (H, W), names in groups.items():
+            n = len(names)
+            out = [DeviceBuffer(n * MAX_DETECTIONS * 4 * 4, device), DeviceBuffer(n * MAX_DETECTIONS * 4, device),
+                   DeviceBuffer(n * MAX_DETECTIONS * 4, device), DeviceBuffer(n * 4, device)]
+            outs.append(out)
+            for i0 in range(0, n, batch):
+                part = names[i0:i0 + batch]                     # the last batch of a size group may be partial
+                B = len(part)
+                frames = np.empty((B, H, W, 3), np.uint8)
+                for i, k in enumerate(part):
+                    a = load_image(paths[k])
+                    if a.shape != (H, W, 3):
+                        raise ValueError(f"{paths[k]}: decoded to {a.shape}, its header says {(H, W, 3)}")
+                    frames[i] = a
+                alive.append(frames)                            # host frames stay untouched until their step has run
+                ptrs = (out[0].ptr + i0 * MAX_DETECTIONS * 16, out[1].ptr + i0 * MAX_DETECTIONS * 4, out[2].ptr + i0 * MAX_DETECTIONS * 4,
+                        out[3].ptr + i0 * 4)
+                pipe.detect_into(frames, *ptrs, src_hw=(H, W), swap_rb=rgb)
+                pipe.join_detectors(stream.value)
+                ev.add(ptrs[0], ptrs[1], ptrs[3], [(H, W)] * B, [annotations[k] for k in part], stream)
+                order += part
+                if len(alive) >= 8:                             # bound the host memory held for steps in flight
+                    _lib.check(L.vbt_stream_synchronize(stream))
+                    alive.clear()
+        table = ev.table()                                      # synchronises `stream`
+    finally:
+        L.vbt_stream_synchronize(stream)
+        L.vbt_stream_destroy(stream)
+    return table, order
+
+
+def create_detections_df(models, img_dir, annotations, export_path=None, rgb=False, device=0):
+    """create_detections_df of eval.py:156-215: the DataFrame with columns Score (float32), Model, IoU (float64), one row per matched
+    detection, files outer / models inner in the order of `annotations` (eval.py:194-205); written to export_path as a pickle."""
+    import pandas as pd
+    images = [(name, find_image(img_dir, name)) for name in annotations]
+    per_model = {}
+    for m in models:
+        table, order = detections_table(m, images, annotations, rgb=rgb, device=device)
+        first = np.searchsorted(table["image"], np.arange(len(order) + 1))       # rows of image k: first[k] .. first[k+1]
+        per_model[model_name(m)] = (table, {name: (first[k], first[k + 1]) for k, name in enumerate(order)})
+    scores, names, ious = [], [], []
+    for name in annotations:
+        for mname, (table, span) in per_model.items():
+            a, b = span[name]
+            scores.append(table["score"][a:b])
+            ious.append(table["iou"][a:b])
+            names += [mname] * int(b - a)
+    df = pd.DataFrame({"Score": np.concatenate(scores).astype(np.float32) if scores else np.zeros(0, np.float32), "Model": names,
+                       "IoU": np.concatenate(ious) if ious else np.zeros(0)})
+    if export_path is not None:
+        d = os.path.dirname(export_path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        df.to_pickle(export_path)
+    return df
+
+
+def curves(df_or_table, iou_threshold=0.5, device=0):
+    """{model: CurveResult} of a detections DataFrame (columns Score, Model, IoU; models in order of first appearance, eval.py:227)
+    or of a mapping {model: (scores, ious)}; Label = IoU > iou_threshold (eval.py:515)."""
+    if hasattr(df_or_table, "columns"):
+        import pandas as pd
+        tables = {m: (df_or_table["Score"][df_or_table["Model"] == m].to_numpy(), df_or_table["IoU"][df_or_table["Model"] == m].to_numpy())
+                  for m in pd.unique(df_or_table["Model"])}
+    else:
+        tables = dict(df_or_table)
+    return {m: curves_from_table(s, i, iou_threshold, device) for m, (s, i) in tables.items()}
+
+
+def closest_point(thresholds, value):
+    """index of the curve point whose threshold is closest to `value` (the first among equals: idxmin, eval.py:313-315,443-445)"""
+    return int(np.argmin(np.abs(np.asarray(thresholds, np.float64) - value)))

@@ -386,6 +386,22 @@ class Pipeline:
         self._enqueued(L.vbt_pipeline_step_runs(self._h, fptr, srcs, int(on_dev), ra, len(runs), H if src_hw is not None else 0, W if src_hw is not None else 0,
                                                 int(bool(swap_rb)), int(bool(track)), outs[0], outs[1], outs[2], outs[3], self._caller_stream(stream) if on_dev else None))
 
+    def detect_into(self, frames, boxes_ptr, scores_ptr, classes_ptr, counts_ptr, stream=None, src_hw=None, swap_rb=False):
+        """Detector-only step over the B <= n_slots frames of `frames` ([B,H,W,3], host or device, as step() takes them) whose
+        detections go to the caller's DEVICE buffers given as raw pointers (boxes float32 [B,25,4], scores / classes float32 [B,25],
+        counts int32 [B]) instead of the pipeline's ring; the tracker is not stepped.  The caller keeps the buffers alive and
+        untouched until the step has run (join_detectors); no torch on this path (the detector evaluation uses it)."""
+        B = int(frames.shape[0]) if hasattr(frames, "shape") else self.n
+        if not 1 <= B <= self.n:
+            raise ValueError(f"detect_into: {B} frames, the pipeline has {self.n} slots")
+        k = (self._step_idx % self._ring) % self.depth
+        H, W = self._hw(src_hw)
+        ptr, on_dev = self._source(frames, k, B, (H, W))
+        run = (_lib.Run * 1)(_lib.Run(0, 0, 1, B, 1, 1, float(self.fps[0])))
+        self._enqueued(_lib.lib().vbt_pipeline_step_runs(self._h, ptr, None, int(on_dev), run, 1, H if src_hw is not None else 0,
+                                                         W if src_hw is not None else 0, int(bool(swap_rb)), 0, int(boxes_ptr), int(scores_ptr),
+                                                         int(classes_ptr), int(counts_ptr), self._caller_stream(stream) if on_dev else None))
+
     def join_detectors(self, stream=None):
         """The caller's stream waits for every forward enqueued so far (after detector-only steps their outputs are then safe to read on it)."""
         _lib.check(_lib.lib().vbt_pipeline_join_detectors(self._h, self._caller_stream(stream)))
