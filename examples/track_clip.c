@@ -55,6 +55,8 @@ int main(int argc, char** argv) {
   int64_t* id = (int64_t*)malloc(sizeof(int64_t) * (size_t)prm.rows_cap);
   double* cols = (double*)malloc(sizeof(double) * 7 * (size_t)prm.rows_cap);
   int n = 0;
+  /* (a clip of raw NV12 / I420 frames, H * W * 3 / 2 bytes each, as a decoder emits them: vbt_pipeline_set_pixel_format(p, VBT_PIX_NV12)
+   *  here, and H, W always passed - conversion and resize then run fused on the device) */
   if (vbt_track_clip(p, (const uint8_t*)frames, /*frames_on_device=*/0, T, native ? 0 : H, native ? 0 : W, /*swap_rb=*/0, stride, id, cols,
                      prm.rows_cap, &n) != VBT_OK)
     return fail("vbt_track_clip");

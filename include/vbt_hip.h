@@ -86,6 +86,27 @@ int vbt_stream_destroy(void* stream);
 int vbt_resize_frames(const uint8_t* src, int B, int H, int W, int src_on_device, uint8_t* dst, int h, int w,
                       int dst_on_device, int swap_rb, int device, void* stream);
 
+/* Pixel formats of source frames.  VBT_PIX_RGB24 (the default everywhere): packed uint8 [H,W,3].  The two YUV 4:2:0 formats are
+ * what a video decoder emits (`ffmpeg -pix_fmt nv12|yuv420p -f rawvideo`); a frame is H*W*3/2 bytes, H and W even, the frames of a
+ * clip contiguous:
+ *   VBT_PIX_NV12: H*W luma bytes, then H/2 rows of interleaved U,V (W bytes per row);
+ *   VBT_PIX_I420: H*W luma bytes, then an H/2 x W/2 U plane, then an H/2 x W/2 V plane.
+ * Arithmetic contract.  Source pixel (y, x) has luma Y[y][x] and the chroma sample at (y >> 1, x >> 1), taken nearest (no chroma
+ * interpolation).  BT.601 limited range in 20-bit fixed point, all int32, >> arithmetic, clip8 saturating to 0..255:
+ *   Yp = max(0, Y - 16);  u = U - 128;  v = V - 128
+ *   R = clip8((1220542*Yp             + 1673527*v + (1<<19)) >> 20)
+ *   G = clip8((1220542*Yp -  409993*u -  852492*v + (1<<19)) >> 20)
+ *   B = clip8((1220542*Yp + 2116026*u             + (1<<19)) >> 20)
+ * Those uint8 RGB values go through the arithmetic of vbt_resize_frames unchanged (float32 bilinear, truncating cast), in one
+ * kernel: no full-resolution RGB frame is written.  A source already at h x w is still converted. */
+#define VBT_PIX_RGB24 0
+#define VBT_PIX_NV12 1
+#define VBT_PIX_I420 2
+/* vbt_resize_frames for YUV 4:2:0 sources: src = B frames of H*W*3/2 bytes, dst = uint8 [B,h,w,3] RGB.  VBT_ERR_ARG, before any
+ * device call: H or W odd, an unknown pix_fmt, or VBT_PIX_RGB24 (that is vbt_resize_frames). */
+int vbt_resize_frames_yuv(const uint8_t* src, int B, int H, int W, int pix_fmt, int src_on_device, uint8_t* dst, int h, int w,
+                          int dst_on_device, int device, void* stream);
+
 /* ------------------------------------------------------------------ tracker -----------------
  * Replaces ocsort.OCSort (reference track.py:17,157,186-199), the row assembly of
  * reference track.py:189-234 and the export id selection of track.py:107-115.
@@ -289,6 +310,13 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
 int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t* const* run_sources, int frames_on_device,
                            const vbt_run* runs, int n_runs, int src_h, int src_w, int swap_rb, int track,
                            float* out_boxes, float* out_scores, float* out_classes, int32_t* out_counts, void* caller_stream);
+/* Pixel format (VBT_PIX_*) of the frames of every later vbt_pipeline_step, vbt_pipeline_step_runs and vbt_track_clip on this handle;
+ * VBT_PIX_RGB24 is the default and restores it.  With a YUV format those calls take frames of src_h*src_w*3/2 bytes (that is the frame
+ * stride of batches, run sources and clips), src_h and src_w must be given, > 0 and even, and swap_rb must be 0 - else VBT_ERR_ARG
+ * with nothing enqueued and no state changed.  Conversion and resize run fused on the device (see VBT_PIX_NV12 above); host frames
+ * of a source more than twice as tall as the network input upload only the luma row pairs the resize reads plus the chroma
+ * plane(s).  VBT_ERR_ARG: an unknown format. */
+int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt);
 /* frames read from the source but not processed (`frame_count % 16`, track.py:161-167): they advance the clip time only */
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n);
 int vbt_pipeline_set_frame_count(vbt_pipeline* p, int frame_count);

@@ -1,7 +1,7 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1] [--live]
-                            [--concurrent N]
+                            [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
       dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
@@ -10,6 +10,9 @@
       "revised" line and reprinted from the first rep that differs.  The reps standing at the end are those `analyze` prints.
       --concurrent N > 1: all files through one pipeline, N clips side by side (a finished clip's tracker slot takes the next
       file); the same files and lines as N = 1, in input order.  Not with --live.
+      --pix_fmt nv12|i420 --size 1920x1080: SRC is a headerless raw video file, YUV 4:2:0 as a decoder emits it (what
+      `ffmpeg -i clip.mp4 -pix_fmt nv12 -f rawvideo clip.yuv` writes; nothing here runs ffmpeg), mapped read-only; colour conversion and
+      resize run fused on the GPU.  --pix_fmt rgb24 --size WxH reads packed raw RGB the same way; without --size SRC is a .npy stack.
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
@@ -67,6 +70,37 @@ class _LiveReps:
         self.shown = lines
 
 
+def _open_source(s, pix_fmt, size):
+    """One SRC of `track` as the clip array of its pixel format: a .npy stack (no --size) or a headerless raw video file."""
+    from .rawvideo import open_raw
+    if not os.path.isfile(s):
+        raise FileNotFoundError(s)                                       # reference track.py:89-90
+    if size is not None:
+        try:
+            return open_raw(s, pix_fmt, size)
+        except ValueError as e:
+            raise click.ClickException(str(e))
+    frames = np.load(s, mmap_mode="r")
+    if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
+        raise click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
+    return frames
+
+
+def _raw_size(pix_fmt, size):
+    """--size as (W, H), or None for .npy sources; the combinations `track` refuses"""
+    from .rawvideo import frame_shape, is_yuv, parse_size
+    if size is None:
+        if is_yuv(pix_fmt):
+            raise click.UsageError(f"--pix_fmt {pix_fmt} reads headerless raw video: give the frame size with --size WIDTHxHEIGHT")
+        return None
+    try:
+        wh = parse_size(size)
+        frame_shape(pix_fmt, wh[1], wh[0])
+    except ValueError as e:
+        raise click.BadParameter(str(e), param_hint="--size")
+    return wh
+
+
 @main.command()
 @click.argument("src", type=str, nargs=-1)
 @click.option("--model", default=DEFAULT_MODEL, show_default=True, type=str, help="VBTM model container.")
@@ -78,22 +112,22 @@ class _LiveReps:
 @click.option("--live", is_flag=True, default=False, help="Print each concentric rep (ROM, ACV) as soon as it is complete.")
 @click.option("--concurrent", default=1, show_default=True, type=int,
               help="Clips tracked side by side in one pipeline (a finished clip's tracker slot takes the next file); 1 = one pipeline per file.")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent):
+@click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420"]),
+              help="Pixel format of the sources; nv12 / i420 (YUV 4:2:0, as a decoder emits it) need --size.")
+@click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of headerless raw video sources, e.g. 1920x1080; without it SRC is a .npy stack.")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size):
     from .track import export_dataframe, track_frames
+    size = _raw_size(pix_fmt, size)
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
-        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent)
+        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size)
     for s in src:
-        if not os.path.isfile(s):
-            raise FileNotFoundError(s)                                   # reference track.py:89-90
-        frames = np.load(s, mmap_mode="r")
-        if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
-            raise click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
+        frames = _open_source(s, pix_fmt, size)
         data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                            live=_LiveReps(s) if live else None)
+                            live=_LiveReps(s) if live else None, pix_fmt=pix_fmt)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")
             continue
@@ -101,24 +135,21 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         click.echo(f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else ""))
 
 
-def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent):
+def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
     from .track import export_dataframe, track_many
     sources, error = [], None
     for s in src:
-        if not os.path.isfile(s):
-            error = FileNotFoundError(s)
+        try:
+            sources.append(_open_source(s, pix_fmt, size))
+        except (FileNotFoundError, click.ClickException) as e:
+            error = e
             break
-        frames = np.load(s, mmap_mode="r")
-        if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
-            error = click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
-            break
-        sources.append(frames)
     lines, nxt = {}, 0
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
-                              time_batch=time_batch):
+                              time_batch=time_batch, pix_fmt=pix_fmt):
         s = src[i]
         if not data["id"]:
             lines[i] = f"{s}: no tracked rows"

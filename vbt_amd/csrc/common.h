@@ -48,6 +48,11 @@ bool lds_opt_in(const void* fn, LdsOptIn* state);
 
 // preprocess_image (reference odt.py:10-19) on device memory (detector.hip); compact != 0: src holds only the row pairs the resize reads
 int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st);
+// the same for VBT_PIX_NV12 / VBT_PIX_I420 sources, conversion fused (yuv_kernels.h): frame b at src_dev + b * frame_stride, its chroma
+// plane(s) at chroma_off; compact != 0: the luma part holds only the row pairs.  Whole frames: frame_stride H*W*3/2, chroma_off H*W.
+inline bool pix_fmt_is_yuv(int pix_fmt) { return pix_fmt == VBT_PIX_NV12 || pix_fmt == VBT_PIX_I420; }
+int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_fmt, size_t frame_stride, size_t chroma_off, int compact,
+                          uint8_t* dst_dev, int h, int w, hipStream_t st);
 
 // Slot close (vbt_pipeline_close_clips): the per-clip record close_pack_kernel writes, { int best_id, n_rows, n_phases, overflow ;
 // double phases[512][6] } (512 = the phases a clip keeps, tracker.hip MAXPH)

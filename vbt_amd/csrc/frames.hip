@@ -1,8 +1,10 @@
 // Frame plumbing in front of the detector (gfx950): assembling a detector batch from frames that live in different
-// places of device memory.  HBM-bound byte moves: 16 bytes per lane, consecutive lanes on consecutive addresses.
+// places of device memory (HBM-bound byte moves: 16 bytes per lane, consecutive lanes on consecutive addresses), and the
+// YUV 4:2:0 entry of preprocess_image (yuv_kernels.h: NV12 / I420 -> RGB fused into the bilinear resize).
 #include <dlfcn.h>
 
 #include "common.h"
+#include "yuv_kernels.h"
 
 namespace vbt {
 
@@ -19,6 +21,17 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(uint4* __restrict__ 
 #pragma unroll 4
   for (int k = 0; k < per; k++, i += 256)
     if (i < frame_vec) d[i] = s[i];
+}
+
+int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_fmt, size_t frame_stride, size_t chroma_off, int compact,
+                          uint8_t* dst_dev, int h, int w, hipStream_t st) {
+  if (!pix_fmt_is_yuv(pix_fmt) || H < 2 || W < 2 || (H & 1) || (W & 1)) { set_error("resize: YUV 4:2:0 needs NV12 / I420 and even H, W >= 2"); return VBT_ERR_ARG; }
+  const long total = (long)B * h * w;
+  const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+  yuv_resize_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(src_dev, dst_dev, total, H, W, h, w, sy, sx, pix_fmt, (long)frame_stride,
+                                                                           (long)chroma_off, compact);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
 }
 
 // ---- roctx ranges (common.h): resolved lazily with dlopen, so that the library has no link-time dependency on the profiler SDK ----
@@ -67,4 +80,39 @@ extern "C" int vbt_gather_frames(uint8_t* dst_dev, const uint8_t* const* src_fra
   }
   VBT_HIP_CHECK(hipGetLastError());
   return VBT_OK;
+}
+
+extern "C" int vbt_resize_frames_yuv(const uint8_t* src, int B, int H, int W, int pix_fmt, int src_on_device, uint8_t* dst, int h, int w, int dst_on_device,
+                          int device, void* stream) {
+  if (!src || !dst || B < 1 || H < 1 || W < 1 || h < 1 || w < 1) { set_error("vbt_resize_frames_yuv: bad argument"); return VBT_ERR_ARG; }
+  if (pix_fmt == VBT_PIX_RGB24) { set_error("vbt_resize_frames_yuv: VBT_PIX_RGB24 frames go through vbt_resize_frames"); return VBT_ERR_ARG; }
+  if (!pix_fmt_is_yuv(pix_fmt)) { set_error("vbt_resize_frames_yuv: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
+  if ((H & 1) || (W & 1)) { set_error("vbt_resize_frames_yuv: YUV 4:2:0 frames have even H and W, got %d x %d", H, W); return VBT_ERR_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    set_error("vbt_resize_frames_yuv: HIP device %d not available (%d visible) - no CPU fallback", device, ndev);
+    return VBT_ERR_HIP;
+  }
+  VBT_HIP_CHECK(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t fb = (size_t)H * W * 3 / 2, sb = (size_t)B * fb, db = (size_t)B * h * w * 3;
+  // every failure below goes through the one clean-up; rc keeps the error a callee already described
+  uint8_t *ds = nullptr, *dd = nullptr;
+  hipError_t e = hipSuccess;
+  int rc = VBT_OK;
+  if (!src_on_device) {
+    e = hipMalloc((void**)&ds, sb);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess && !dst_on_device) e = hipMalloc((void**)&dd, db);
+  if (e == hipSuccess) rc = resize_frames_yuv_dev(ds ? ds : src, B, H, W, pix_fmt, fb, (size_t)H * W, 0, dd ? dd : dst, h, w, st);
+  if (e == hipSuccess && rc == VBT_OK && !dst_on_device) e = hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, st);
+  if (ds || dd) {   // (also after a failure: a copy may still be in flight on the buffers freed next)
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+  }
+  if (ds) (void)hipFree(ds);
+  if (dd) (void)hipFree(dd);
+  if (e != hipSuccess) { set_error("vbt_resize_frames_yuv failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  return rc;
 }

@@ -14,7 +14,8 @@
 #include "common.h"
 
 // (resize_frames_dev, common.h: preprocess_image reading either whole source frames [B][H][W][3] or, compact != 0, only the row pairs the
-//  bilinear resize touches: [B][2h][W][3], pair d = source rows p(d), p(d) + 1 with p(d) = min(floor(src_y(d)), H - 2))
+//  bilinear resize touches: [B][2h][W][3], pair d = source rows p(d), p(d) + 1 with p(d) = min(floor(src_y(d)), H - 2);
+//  resize_frames_yuv_dev: the same with the NV12 / I420 conversion fused, vbt_pipeline_set_pixel_format)
 
 using namespace vbt;
 
@@ -80,6 +81,7 @@ struct vbt_pipeline {
   std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
   int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
+  int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
   // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
   // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
@@ -412,6 +414,54 @@ int h2d_frames(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* ho
   return VBT_OK;
 }
 
+// Compact upload of a YUV 4:2:0 frame (NV12 / I420, H x W, network size h): the luma row pairs 0..h-2, [2 (h - 1)][W], then the
+// source frame from luma row p(h - 1) to its end as it is - the last pair, the luma rows below it (none or a few) and the whole chroma
+// plane(s).  The tail is one contiguous piece of the source, so the chroma costs no copy call of its own.
+struct YuvCompact {
+  size_t tail_src, tail_bytes, chroma_off, frame_bytes;   // tail: offset in the source frame / length; chroma_off, frame_bytes: of the compact frame
+};
+YuvCompact yuv_compact(vbt_pipeline* p, int H, int W) {
+  const int h = p->size, p_last = row_table(p, H, h)[(size_t)h - 1];
+  YuvCompact c;
+  c.tail_src = (size_t)p_last * W;
+  c.tail_bytes = (size_t)H * W * 3 / 2 - c.tail_src;
+  c.chroma_off = (size_t)2 * (h - 1) * W + (size_t)(H - p_last) * W;
+  c.frame_bytes = (size_t)2 * (h - 1) * W + c.tail_bytes;
+  return c;
+}
+
+// nf host frames of H*W*3/2 bytes -> staging buffer (frame slot0 onwards) on the copy stream; compact: the layout of yuv_compact
+int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, int W, bool compact) {
+  hipStream_t C = p->copy_stream;
+  const size_t fb = (size_t)H * W * 3 / 2, row = (size_t)W;
+  if (!compact) {
+    VBT_HIP_CHECK(hipMemcpyAsync(stage_buf + (size_t)slot0 * fb, host, (size_t)nf * fb, hipMemcpyHostToDevice, C));
+    p->h2d_bytes += (uint64_t)nf * fb;
+    return VBT_OK;
+  }
+  const int h = p->size;
+  const std::vector<int>& tab = row_table(p, H, h);
+  const YuvCompact cl = yuv_compact(p, H, W);
+  uint8_t* dst = stage_buf + (size_t)slot0 * cl.frame_bytes;
+  const int step = h > 1 ? tab[1] - tab[0] : 0;
+  bool uniform = h > 2;
+  for (int d = 1; d < h - 1 && uniform; d++) uniform = tab[d] - tab[d - 1] == step;
+  if (uniform && nf < h - 1) {
+    // pairs 0..h-2 sit at one pitch inside a frame: one strided copy per frame (the chroma between the frames breaks the pitch)
+    for (int b = 0; b < nf; b++)
+      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)b * cl.frame_bytes, 2 * row, host + (size_t)b * fb + (size_t)tab[0] * row, (size_t)step * row, 2 * row,
+                                     (size_t)(h - 1), hipMemcpyHostToDevice, C));
+  } else {
+    // pair d of every frame in one strided copy (pitch = one source frame / one compact frame)
+    for (int d = 0; d < h - 1; d++)
+      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)d * 2 * row, cl.frame_bytes, host + (size_t)tab[d] * row, fb, 2 * row, (size_t)nf, hipMemcpyHostToDevice, C));
+  }
+  // the tails of all frames: one strided copy
+  VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)2 * (h - 1) * row, cl.frame_bytes, host + cl.tail_src, fb, cl.tail_bytes, (size_t)nf, hipMemcpyHostToDevice, C));
+  p->h2d_bytes += (uint64_t)nf * cl.frame_bytes;
+  return VBT_OK;
+}
+
 int ensure_resized(vbt_pipeline* p, int k) {
   if (!p->resized[k]) VBT_HIP_CHECK(hipMalloc((void**)&p->resized[k], (size_t)p->n * p->size * p->size * 3 + 64));
   return VBT_OK;
@@ -424,13 +474,31 @@ struct Sources {
   int src_h = 0, src_w = 0, swap_rb = 0;
 };
 
+// What a step may ask for under the pipeline's pixel format; checked before anything is enqueued or counted.
+int check_source_format(const vbt_pipeline* p, const char* fn, int src_h, int src_w, int swap_rb) {
+  if ((src_h > 0) != (src_w > 0)) { set_error("%s: src_h and src_w come together", fn); return VBT_ERR_ARG; }
+  if (!pix_fmt_is_yuv(p->pix_fmt)) return VBT_OK;
+  if (src_h <= 0 || src_w <= 0 || (src_h & 1) || (src_w & 1)) {
+    set_error("%s: YUV 4:2:0 frames need src_h and src_w, > 0 and even, got %d x %d", fn, src_h, src_w);
+    return VBT_ERR_ARG;
+  }
+  if (swap_rb) { set_error("%s: swap_rb does not apply to YUV frames", fn); return VBT_ERR_ARG; }
+  return VBT_OK;
+}
+
 // Brings B frames to the network resolution on stream S of forward slot k and returns the device pointer the detector reads.
 int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, const vbt_run* runs, int n_runs, int B, void* caller_stream,
                    const uint8_t** frames_dev, int* stage_j) {
   const int size = p->size;
-  const bool resize = src.src_h > 0 && src.src_w > 0 && (src.src_h != size || src.src_w != size || src.swap_rb);
+  const bool yuv = pix_fmt_is_yuv(p->pix_fmt);   // (a YUV source at the network resolution is still converted)
+  const bool resize = yuv || (src.src_h > 0 && src.src_w > 0 && (src.src_h != size || src.src_w != size || src.swap_rb));
   const int H = src.src_h > 0 ? src.src_h : size, W = src.src_w > 0 ? src.src_w : size;
-  const size_t fb = (size_t)H * W * 3;
+  const size_t fb = yuv ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
+  // bytes of one frame in the staging buffer / upload of nf host frames, per format
+  auto stage_bytes = [&](bool compact_) { return !compact_ ? fb : yuv ? yuv_compact(p, H, W).frame_bytes : (size_t)2 * size * W * 3; };
+  auto upload = [&](uint8_t* st_, int slot0, const uint8_t* host, int nf, bool compact_) {
+    return yuv ? h2d_frames_yuv(p, st_, slot0, host, nf, H, W, compact_) : h2d_frames(p, st_, slot0, host, nf, H, W, compact_);
+  };
   *stage_j = -1;
   const uint8_t* ptr = nullptr;
   bool compact = false;
@@ -446,8 +514,8 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
     } else {
       compact = resize && compact_rows(p, H, W);
       int j = 0;
-      PL_CHECK(stage_take(p, compact ? (size_t)p->n * 2 * size * W * 3 : (size_t)p->n * fb, true, S, &j));
-      PL_CHECK(h2d_frames(p, p->stage[j].buf, 0, src.frames, B, H, W, compact));
+      PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), true, S, &j));
+      PL_CHECK(upload(p->stage[j].buf, 0, src.frames, B, compact));
       VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev, p->copy_stream));
       VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev, 0));
       ptr = p->stage[j].buf;
@@ -457,10 +525,10 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
     // one source per run: the batch is assembled in a staging buffer
     compact = !src.on_device && resize && compact_rows(p, H, W);
     int j = 0;
-    PL_CHECK(stage_take(p, compact ? (size_t)p->n * 2 * size * W * 3 : (size_t)p->n * fb, !src.on_device, S, &j));
+    PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), !src.on_device, S, &j));
     uint8_t* st = p->stage[j].buf;
     if (!src.on_device) {
-      for (int i = 0; i < n_runs; i++) PL_CHECK(h2d_frames(p, st, runs[i].slot0, src.run_sources[i], runs[i].n_frames, H, W, compact));
+      for (int i = 0; i < n_runs; i++) PL_CHECK(upload(st, runs[i].slot0, src.run_sources[i], runs[i].n_frames, compact));
       VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev, p->copy_stream));
       VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev, 0));
     } else {
@@ -483,7 +551,12 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
   }
   if (resize) {
     PL_CHECK(ensure_resized(p, k));
-    PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k], size, size, src.swap_rb, compact ? 1 : 0, S));
+    if (yuv) {
+      const YuvCompact cl = compact ? yuv_compact(p, H, W) : YuvCompact{0, 0, (size_t)H * W, fb};
+      PL_CHECK(resize_frames_yuv_dev(ptr, B, H, W, p->pix_fmt, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0, p->resized[k], size, size, S));
+    } else {
+      PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k], size, size, src.swap_rb, compact ? 1 : 0, S));
+    }
     ptr = p->resized[k];
   }
   *frames_dev = ptr;
@@ -726,7 +799,7 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
                       const int32_t* clip_map, const int32_t* frame_idx, int track, void* caller_stream) {
   if (!p || !frames) { set_error("vbt_pipeline_step: NULL argument"); return VBT_ERR_ARG; }
   if ((clip_map != nullptr) != (frame_idx != nullptr)) { set_error("vbt_pipeline_step: clip_map and frame_idx come together"); return VBT_ERR_ARG; }
-  if ((src_h > 0) != (src_w > 0)) { set_error("vbt_pipeline_step: src_h and src_w come together"); return VBT_ERR_ARG; }
+  PL_CHECK(check_source_format(p, "vbt_pipeline_step", src_h, src_w, swap_rb));
   if (active && p->n_trk != p->n) { set_error("vbt_pipeline_step: `active` needs one clip per slot"); return VBT_ERR_ARG; }
   if (clip_map)
     for (int i = 0; i < p->n; i++)
@@ -808,7 +881,7 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
     set_error("vbt_pipeline_step_runs: out_* come together and are for detector-only steps (track = 0)");
     return VBT_ERR_ARG;
   }
-  if ((src_h > 0) != (src_w > 0)) { set_error("vbt_pipeline_step_runs: src_h and src_w come together"); return VBT_ERR_ARG; }
+  PL_CHECK(check_source_format(p, "vbt_pipeline_step_runs", src_h, src_w, swap_rb));
   StepTimer timer(p);
   VBT_HIP_CHECK(hipSetDevice(p->device));
   std::vector<vbt_run> ra(runs, runs + n_runs);
@@ -839,6 +912,13 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
   src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
   std::vector<vbt_run> asm_runs(ra);
   return step_runs_impl(p, src, asm_runs.data(), n_runs, ra, B, track, out_boxes, out_scores, out_classes, out_counts, caller_stream);
+}
+
+int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_yuv(pix_fmt)) { set_error("vbt_pipeline_set_pixel_format: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
+  p->pix_fmt = pix_fmt;   // read by the next step call: steps already enqueued carry their own kernels and copies
+  return VBT_OK;
 }
 
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n) {
@@ -1113,10 +1193,10 @@ int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device,
                    int64_t* id, double* cols7, int cap, int* n_rows) {
   if (!p || !frames || T < 0 || !id || !cols7 || !n_rows || cap < 0) { set_error("vbt_track_clip: bad argument"); return VBT_ERR_ARG; }
   if (p->n_trk != 1) { set_error("vbt_track_clip: the pipeline must follow exactly one clip (n_clips = 1), it follows %d", p->n_trk); return VBT_ERR_ARG; }
-  if ((src_h > 0) != (src_w > 0)) { set_error("vbt_track_clip: src_h and src_w come together"); return VBT_ERR_ARG; }
+  PL_CHECK(check_source_format(p, "vbt_track_clip", src_h, src_w, swap_rb));
   const int stride = std::max(frame_stride, 1);
   const int H = src_h > 0 ? src_h : p->size, W = src_w > 0 ? src_w : p->size;
-  const size_t fb = (size_t)H * W * 3;
+  const size_t fb = pix_fmt_is_yuv(p->pix_fmt) ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
   PL_CHECK(vbt_pipeline_reset(p));
   // frames whose 1-based number is not a multiple of the stride are read and dropped (track.py:161-167): they only advance the time
   const int kept = T / stride, F = p->n;

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .interpreter import Interpreter
 from .ocsort import LIVE_PATH_CAP, LIVE_PHASE_CAP, ROW_DTYPE, MultiClipTracker, OCSort, _live_records
+from .rawvideo import frame_shape, is_yuv, pix_fmt_code, source_hw
 from .odt import (calc_bounding_box_center, calc_plate_height, calc_plate_width, results_to_sorttracker_inputs,
                   run_odt)
 
@@ -62,22 +63,29 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
     return data
 
 
-def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None):
+def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
+                 src_hw=None):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
     odt.py:10-19).  frame_stride = the `frame_count % 16` of track.py:166: frames whose 1-based number is not a multiple are
     read and dropped, they only advance the clip time.  Returns the reference's dict of lists (track.py:144-145).
     live: optional callable(ocsort.LiveClip, final) - live rep analysis on: called after every batch with the clip's record, and
-    once more after the last one with the flush view (final=True: the phases the clip close gives)."""
-    T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    once more after the last one with the flush view (final=True: the phases the clip close gives).
+    pix_fmt "nv12" / "i420": frames is uint8 [T, H*3//2, W], YUV 4:2:0 as a decoder emits it (rawvideo.py); converted and resized
+    on the GPU.  src_hw=(H, W) is then optional (the shape gives it)."""
+    T = int(frames.shape[0])
+    H, W = source_hw(frames, pix_fmt)
+    if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
+        raise ValueError(f"track_frames: src_hw {tuple(src_hw)} does not match the frames' {(H, W)}")
     stride = max(int(frame_stride), 1)
     kept = T // stride                                               # frames that are processed
     F = max(1, min(int(time_batch), max(kept, 1)))
     pipe = Pipeline(model_path, F, max_frames=max(kept, 1), fps=fps, detection_treshold=detection_treshold, device=device,
                     rows_per_frame=25, tracker_clips=1)
     size = pipe._size
-    src_hw = None if (H, W) == (size, size) else (H, W)
+    pipe.set_pixel_format(pix_fmt)
+    src_hw = None if (H, W) == (size, size) and not is_yuv(pix_fmt) else (H, W)
     if live is not None:
         pipe.enable_live()
     elif isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
@@ -96,18 +104,19 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return pipe.rows(0)
 
 
-def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0):
+def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, pix_fmt="rgb24"):
     """track_frames() for many clips through ONE pipeline: `concurrent` tracker slots, `time_batch` detector slots per step.  Each
     step hands runs of consecutive frames to the open clips (shard.stream_schedule); a clip whose frames are used up is closed in its
     slot (Pipeline.close_clips) and the next source opens there.  Only clips of one source resolution are open together (the
-    resize is set per step).  sources: uint8 [T,H,W,3] arrays (numpy / memmap); fps: one value or one per source.
+    resize is set per step).  sources: uint8 [T,H,W,3] arrays (numpy / memmap), or [T,H*3//2,W] with pix_fmt "nv12" / "i420"; fps:
+    one value or one per source.
     Yields (index, rows) as clips finish - rows = the dict track_frames returns for that source."""
     from .shard import stream_schedule
     sources = list(sources)
     fps_of = np.broadcast_to(np.asarray(fps, np.float64), (len(sources),))
     stride = max(int(frame_stride), 1)
     kept = [int(s.shape[0]) // stride for s in sources]
-    hw = [(int(s.shape[1]), int(s.shape[2])) for s in sources]
+    hw = [source_hw(s, pix_fmt) for s in sources]
     for i in range(len(sources)):
         if kept[i] == 0:
             yield i, {k: [] for k in COLUMNS}
@@ -116,6 +125,7 @@ def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5
     pipe = Pipeline(model_path, max(1, int(time_batch)), max_frames=max(kept), fps=fps_of[0], detection_treshold=detection_treshold,
                     device=device, rows_per_frame=25, tracker_clips=int(concurrent), slot_close=True)
     size = pipe._size
+    pipe.set_pixel_format(pix_fmt)
     clip_of = {}                                     # tracker slot -> source index of the clip open in it
     unread = {}                                      # tracker slot -> source index of its close not read yet
     for opens, runs, closes in stream_schedule(kept, int(concurrent), pipe.n, groups=hw):
@@ -123,7 +133,7 @@ def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5
             clip_of[slot] = i
             pipe.fps[slot] = fps_of[i]
         i0 = clip_of[runs[0][0]]
-        src_hw = None if hw[i0] == (size, size) else hw[i0]
+        src_hw = None if hw[i0] == (size, size) and not is_yuv(pix_fmt) else hw[i0]
         chunks = []
         for slot, _, n, f0 in runs:
             a = sources[clip_of[slot]]
@@ -248,6 +258,7 @@ class Pipeline:
         self._step_idx = 0                          # steps enqueued so far (mirror of the library's counter: which stream a step runs on)
         self._keep = collections.deque(maxlen=2 * self._ring + 4)   # host sources / foreign device arrays of the steps in flight
         self._ext = {}                              # torch.cuda.ExternalStream views of the detector streams (record_stream)
+        self.pix_fmt = "rgb24"                      # set_pixel_format()
 
     def info(self):
         out = _lib.PipelineInfo()
@@ -264,6 +275,22 @@ class Pipeline:
         _lib.check(_lib.lib().vbt_pipeline_set_frame_count(self._h, int(v)))
 
     # ---- frame sources ----
+    def set_pixel_format(self, pix_fmt):
+        """"rgb24" (default), "nv12" or "i420" (vbt_pipeline_set_pixel_format): the format of the frames of every later step(),
+        step_runs() and track_clip().  YUV 4:2:0 frames are uint8 [*, H*3//2, W] - the 2-D view of a raw frame, planes as
+        include/vbt_hip.h lays them out - need src_hw=(H, W), both even, and take no swap_rb; the BT.601 conversion runs fused with the
+        resize on the device."""
+        _lib.check(_lib.lib().vbt_pipeline_set_pixel_format(self._h, pix_fmt_code(pix_fmt)))
+        self.pix_fmt = str(pix_fmt).lower()
+
+    def _yuv_hw(self, src_hw, swap_rb):
+        """the checks of a YUV step that the library would refuse (check_source_format, pipeline.hip), before a shape is compared"""
+        if is_yuv(self.pix_fmt):
+            if src_hw is None:
+                raise ValueError(f"{self.pix_fmt} frames need src_hw=(H, W)")
+            if swap_rb:
+                raise ValueError(f"swap_rb does not apply to {self.pix_fmt} frames")
+
     def _caller_stream(self, stream):
         if stream is not None:
             return int(stream)
@@ -278,7 +305,11 @@ class Pipeline:
         ptr, on_dev, keep = _host_or_device_ptr(x)
         if keep is not None:
             shp = tuple(keep.shape)
-            if len(shp) != 4 or shp[3] != 3 or (hw is not None and shp[1:3] != tuple(hw)) or (n_frames is not None and shp[0] < n_frames):
+            if is_yuv(self.pix_fmt):
+                want = frame_shape(self.pix_fmt, *hw)
+                if len(shp) != 3 or shp[1:] != want or (n_frames is not None and shp[0] < n_frames):
+                    raise ValueError(f"{self.pix_fmt} frames must be uint8 [{n_frames if n_frames is not None else 'B'}, {want[0]}, {want[1]}], got {shp}")
+            elif len(shp) != 4 or shp[3] != 3 or (hw is not None and shp[1:3] != tuple(hw)) or (n_frames is not None and shp[0] < n_frames):
                 raise ValueError(f"frames must be uint8 [{n_frames if n_frames is not None else 'B'}, {hw[0] if hw else 'H'}, {hw[1] if hw else 'W'}, 3], got {shp}")
             if on_dev and hasattr(keep, "record_stream"):
                 t = _torch()
@@ -311,6 +342,7 @@ class Pipeline:
         reference processes them one after the other, track.py:85-126).
         clip_map / frame_idx: int [n] - slot i carries frame number frame_idx[i] (1-based) of tracker clip clip_map[i] (-1: empty)."""
         k = (self._step_idx % self._ring) % self.depth
+        self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ptr, on_dev = self._source(frames_dev_ptr, k, self.n, (H, W))
         act = cm = fi = None
@@ -340,6 +372,7 @@ class Pipeline:
         if outputs is not None and track:
             raise ValueError("step_runs: outputs= is for detector-only steps (track=False)")
         k = (self._step_idx % self._ring) % self.depth
+        self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ra = (_lib.Run * len(runs))()
         B = 0
@@ -395,6 +428,7 @@ class Pipeline:
         if not 1 <= B <= self.n:
             raise ValueError(f"detect_into: {B} frames, the pipeline has {self.n} slots")
         k = (self._step_idx % self._ring) % self.depth
+        self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ptr, on_dev = self._source(frames, k, B, (H, W))
         run = (_lib.Run * 1)(_lib.Run(0, 0, 1, B, 1, 1, float(self.fps[0])))
@@ -417,15 +451,16 @@ class Pipeline:
         self.frame_count = f0 + F - 1
 
     def track_clip(self, frames, frame_stride=1, src_hw=None, swap_rb=False):
-        """vbt_track_clip: the whole loop of reference track.py:129-260 for ONE clip held in memory (frames uint8 [T,H,W,3], host or
-        device), `n` consecutive kept frames per detector batch.  Returns the reference's dict of lists (track.py:144-145)."""
+        """vbt_track_clip: the whole loop of reference track.py:129-260 for ONE clip held in memory (frames uint8 [T,H,W,3] - or
+        [T,H*3//2,W] after set_pixel_format("nv12" / "i420") - host or device), `n` consecutive kept frames per detector batch.  Returns the reference's dict of lists (track.py:144-145)."""
         ptr, on_dev, keep = _host_or_device_ptr(frames)
         T = int(frames.shape[0]) if keep is not None else None
         if T is None:
             raise ValueError("track_clip needs an array (its length is the clip's frame count)")
+        self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
-        if tuple(frames.shape[1:]) != (H, W, 3):
-            raise ValueError(f"track_clip: frames must be [T, {H}, {W}, 3], got {tuple(frames.shape)}")
+        if tuple(frames.shape[1:]) != frame_shape(self.pix_fmt, H, W):
+            raise ValueError(f"track_clip: {self.pix_fmt} frames must be [T, {', '.join(str(v) for v in frame_shape(self.pix_fmt, H, W))}], got {tuple(frames.shape)}")
         cap = self.tracker.rows_cap
         ids = np.empty(cap, np.int64)
         cols = np.empty((cap, 7), np.float64)
