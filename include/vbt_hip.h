@@ -73,6 +73,18 @@ int vbt_detect(vbt_model* m, const uint8_t* frames, int B, int frames_on_device,
 int vbt_detect_async(vbt_model* m, const uint8_t* frames_dev, int B, void* stream,
                      float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* counts_dev);
 
+/* A part of the forward: plan steps [step0, step1) (step1 < 0: to the end; vbt_model_num_launches of them) on images
+ * [img0, img0 + n_img) of the model's max_batch-image tensors.  The detector is per-image, so a batch may be brought through the
+ * network entry a few images at a time and through the rest at once: steps [0, vbt_model_entry_steps) - the stem convolution, with
+ * block 0 where the plan fuses the two - on images [g n, (g + 1) n) as they arrive, then steps [entry, end) on images [0, G n).
+ * frames_dev = the n_img frames of the range (NULL when step0 >= vbt_model_entry_steps); the output pointers are those of image 0
+ * of the batch, as vbt_detect_async takes them (NULL when the range ends before decode + NMS).  Steps behind the entry run from
+ * img0 = 0 only (VBT_ERR_ARG otherwise).  Enqueue only; never replayed from a graph. */
+int vbt_detect_range_async(vbt_model* m, const uint8_t* frames_dev, int img0, int n_img, int step0, int step1, void* stream,
+                           float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* counts_dev);
+/* plan steps that form the network entry: every step up to the last one that reads the frames; all tensors behind it are materialised */
+int vbt_model_entry_steps(const vbt_model* m);
+
 /* Streams for a pipeline that keeps several forwards in flight (the reference runs one interpreter.invoke() at a time,
  * odt.py:58-61; there is no reference counterpart).  A HIP stream is bound to a hardware queue at its first command,
  * round-robin: the stream returned here has already run one empty launch, so streams created back to back use distinct
@@ -257,7 +269,10 @@ int vbt_tracker_live_tracks(vbt_tracker* t, int clip, int flush_view, int64_t* i
  *   - a copy stream with a ring of depth + 2 device staging buffers: frames handed over in host memory (the reference's situation,
  *     track.py:160) are uploaded up to two steps ahead of their forward; with frames at source resolution only the rows the bilinear
  *     resize of odt.py:10-19 reads are uploaded;
- *   - for batches of <= 8 frames, groups of `depth` tracker steps walked by one launch (the forward of a small batch is launch latency).
+ *   - for batches of <= 8 frames, groups of `depth` tracker steps walked by one launch (the forward of a small batch is launch latency);
+ *   - for batches of 32..64 frames, groups of `group` steps behind ONE forward of group x n_slots images: each step call runs the
+ *     network entry on its own frames at once - the caller's buffer is consumed exactly as without groups - and the group's last
+ *     call (or whatever reads or changes the pipeline's state before it) enqueues the rest of the network and one OC-SORT walk.
  * One handle is used by one host thread at a time.  Every call only ENQUEUES work unless its comment says it synchronises.
  * Frames: uint8 [*,H,W,3]; H,W = the network resolution (vbt_model_input_shape) unless src_h/src_w say otherwise.
  */
@@ -277,7 +292,10 @@ typedef struct {
                                 VBT_ERR_STATE, 0 = a note on stderr, -1 = environment VBT_STRICT_PLACEMENT (default 0) */
   int32_t model_flags;       /* vbt_model_create_ex flags; VBT_MODEL_DEFAULT_FLAGS */
   float detection_threshold; /* detection_treshold of reference track.py:129,174 / odt.py:70-75 */
-  float reserved0;
+  int32_t group;             /* consecutive vbt_pipeline_step calls that share ONE forward of group x n_slots images (the network entry still
+                                runs inside every call) and one time-batched OC-SORT walk: 0 = default (VBT_PIPELINE_GROUP, else 4 for
+                                32 <= n_slots <= 64 with one clip per slot and a plan at that batch - a pinned VBT_PLAN_FILE or no
+                                autotuning - else 1), 1 = off, up to 8.  One clip per slot only; replaces `defer` */
   double plate_diameter;     /* VelocityTracker(plate_diameter, diff_threshold, min_distance), reference VelocityTracker.py:16 */
   double diff_threshold;
   double min_distance;
@@ -380,7 +398,9 @@ int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips
 typedef struct {
   int32_t n_slots, n_clips, rows_cap, device, depth, ring, defer, tracker_inline, image_size, frame_count, steps_enqueued, placement_ok;
   int32_t queue_groups_seen;  /* distinct hardware queues the placement probe has seen on this device */
-  int32_t reserved[3];
+  int32_t group;              /* steps per forward (1: every step runs its own forward) */
+  int32_t next_slot;          /* detector instance / stream (index into det_streams) the next step call enqueues on */
+  int32_t reserved[1];
   void* det_streams[8];
   void* copy_stream;
   void* tracker_stream;

@@ -46,15 +46,15 @@ class PipelineParams(ctypes.Structure):
     _fields_ = [("n_slots", ctypes.c_int32), ("n_clips", ctypes.c_int32), ("rows_cap", ctypes.c_int32), ("device", ctypes.c_int32),
                 ("depth", ctypes.c_int32), ("tracker_stream", ctypes.c_int32), ("defer", ctypes.c_int32), ("selfcheck", ctypes.c_int32),
                 ("strict_placement", ctypes.c_int32), ("model_flags", ctypes.c_int32), ("detection_threshold", ctypes.c_float),
-                ("reserved0", ctypes.c_float), ("plate_diameter", c_double), ("diff_threshold", c_double), ("min_distance", c_double),
+                ("group", ctypes.c_int32), ("plate_diameter", c_double), ("diff_threshold", c_double), ("min_distance", c_double),
                 ("tracker", TrackerParams)]
 
 
 class PipelineInfo(ctypes.Structure):
     """vbt_pipeline_info (include/vbt_hip.h)"""
     _fields_ = [(k, ctypes.c_int32) for k in ("n_slots", "n_clips", "rows_cap", "device", "depth", "ring", "defer", "tracker_inline", "image_size",
-                                               "frame_count", "steps_enqueued", "placement_ok", "queue_groups_seen")] + \
-               [("reserved", ctypes.c_int32 * 3), ("det_streams", c_void_p * 8), ("copy_stream", c_void_p), ("tracker_stream", c_void_p),
+                                               "frame_count", "steps_enqueued", "placement_ok", "queue_groups_seen", "group", "next_slot")] + \
+               [("reserved", ctypes.c_int32 * 1), ("det_streams", c_void_p * 8), ("copy_stream", c_void_p), ("tracker_stream", c_void_p),
                 ("h2d_bytes", ctypes.c_uint64), ("step_host_ns", ctypes.c_uint64), ("step_calls", ctypes.c_uint64)]
 
 
@@ -93,6 +93,8 @@ _SIGS = {
     "vbt_model_tensor_shape": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_detect_async": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_detect_range_async": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_model_entry_steps": (c_int, [c_void_p]),
     "vbt_stream_create": (c_int, [c_int, c_void_p]),
     "vbt_stream_destroy": (c_int, [c_void_p]),
     "vbt_streams_share_queue": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -497,14 +497,15 @@ static int launch_expdw_step(const vbt_model* m, const Step& s, int B, hipStream
 }
 
 // Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major): the batch-offset pointers here, the
-// variant and the launch in the family's own function above.
+// variant and the launch in the family's own function above.  `frames` = frame boff, the first one of the range; the output pointers
+// are those of the whole batch.
 static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_t* frames, float* boxes, float* scores,
                        float* classes, int* counts, int boff = 0) {
   if (m->pool_dirty) { const int rc = flush_uploads(m); if (rc) return rc; }
   const OpRec& op = m->ops[s.op];
   const TensorRec& to = m->tensors[op.output];
   auto TP = [&](int t) { return m->tptr[t] + (size_t)boff * m->telems[t]; };
-  const uint8_t* frame0 = frames + (size_t)boff * m->hdr.image_size * m->hdr.image_size * 3;
+  const uint8_t* frame0 = frames;
   int8_t* out = TP(op.output);
   // start of every member's workgroups in a grid of several problems (F_MULTI, F_BAND); start[n] = the grid
   auto member_tiles = [&](auto tiles_of) {
@@ -869,7 +870,7 @@ static int enqueue_forward(vbt_model* m, const uint8_t* frames_dev, int B, hipSt
       hipStream_t ss = m->sub_streams[k];
       (void)hipStreamWaitEvent(ss, m->ev_fork, 0);
       for (const Step& s : m->steps) {
-        int rc = launch_step(m, s, bk, ss, frames_dev, boxes, scores, classes, counts, b0);
+        int rc = launch_step(m, s, bk, ss, frames_dev + (size_t)b0 * m->hdr.image_size * m->hdr.image_size * 3, boxes, scores, classes, counts, b0);
         if (rc) return rc;
       }
       (void)hipEventRecord(m->ev_join[k], ss);
@@ -879,6 +880,15 @@ static int enqueue_forward(vbt_model* m, const uint8_t* frames_dev, int B, hipSt
   VBT_HIP_CHECK(hipGetLastError());
   m->last_B = B;
   return VBT_OK;
+}
+
+// The network entry: the plan steps up to and including the last one that reads the frames (the stem convolution, alone or fused with
+// block 0 - the first plan group of the pinned plans).  Every tensor behind it is materialised, batch-major, in a buffer of its own.
+static int entry_steps(const vbt_model* m) {
+  int k = 0;
+  for (size_t i = 0; i < m->steps.size(); i++)
+    if (m->steps[i].family == F_STEM || m->steps[i].family == F_STEMBLK) k = (int)i + 1;
+  return k;
 }
 
 // Forward = eager launches, or (small batches: the 120-odd launches are host-bound) replay of a captured hipGraph.
@@ -1162,6 +1172,33 @@ int vbt_detect_async(vbt_model* m, const uint8_t* frames_dev, int B, void* strea
   if (!m || !frames_dev || !boxes || !scores || !classes || !counts) { set_error("vbt_detect_async: NULL argument"); return VBT_ERR_ARG; }
   if (B < 1 || B > m->max_batch) { set_error("vbt_detect: batch %d outside 1..%d", B, m->max_batch); return VBT_ERR_CAPACITY; }
   return forward(m, frames_dev, B, (hipStream_t)stream, boxes, scores, classes, counts);
+}
+
+int vbt_model_entry_steps(const vbt_model* m) { return m ? entry_steps(m) : VBT_ERR_ARG; }
+
+int vbt_detect_range_async(vbt_model* m, const uint8_t* frames_dev, int img0, int n_img, int step0, int step1, void* stream, float* boxes,
+                           float* scores, float* classes, int32_t* counts) {
+  if (!m) { set_error("vbt_detect_range_async: NULL model"); return VBT_ERR_ARG; }
+  const int ns = (int)m->steps.size();
+  if (step1 < 0) step1 = ns;
+  if (img0 < 0 || n_img < 1 || (long)img0 + n_img > m->max_batch) { set_error("vbt_detect_range_async: images %d..%ld outside 0..%d", img0, (long)img0 + n_img - 1, m->max_batch - 1); return VBT_ERR_CAPACITY; }
+  if (step0 < 0 || step0 >= step1 || step1 > ns) { set_error("vbt_detect_range_async: steps [%d, %d) outside the plan's %d", step0, step1, ns); return VBT_ERR_ARG; }
+  if (step0 < entry_steps(m) && !frames_dev) { set_error("vbt_detect_range_async: the range reads the frames, frames_dev is NULL"); return VBT_ERR_ARG; }
+  for (int i = step0; i < step1; i++) {
+    const Step& s = m->steps[(size_t)i];
+    if (s.family == F_POST && (!boxes || !scores || !classes || !counts)) { set_error("vbt_detect_range_async: the range ends in decode + NMS, an output pointer is NULL"); return VBT_ERR_ARG; }
+    // grids of several problems carry whole-batch pointers (launch_step)
+    if (img0 != 0 && ((s.family == F_PW && !s.members.empty()) || s.family == F_BAND)) { set_error("vbt_detect_range_async: plan step %d (%s) runs from image 0 only", i, kFamilyName[s.family]); return VBT_ERR_ARG; }
+  }
+  RoctxRange range("vbt:detect");
+  if (m->pool_dirty) { const int rc = flush_uploads(m); if (rc) return rc; }
+  for (int i = step0; i < step1; i++) {
+    const int rc = launch_step(m, m->steps[(size_t)i], n_img, (hipStream_t)stream, frames_dev, boxes, scores, classes, counts, img0);
+    if (rc) return rc;
+  }
+  VBT_HIP_CHECK(hipGetLastError());
+  m->last_B = img0 + n_img;
+  return VBT_OK;
 }
 
 int vbt_detect(vbt_model* m, const uint8_t* frames, int B, int frames_on_device, void* stream, float* boxes, float* scores,

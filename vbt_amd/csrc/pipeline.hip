@@ -4,7 +4,7 @@
 // vbt_tracker_update_from_*, vbt_resize_frames, vbt_gather_frames; the slot close through tracker_close_clips, common.h).  What lives here is the part of the fast path that is not a
 // kernel: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
 // events that order detector(t) -> tracker(t) -> slot reuse, the staging ring of the host-fed mode, the deferred tracker groups of
-// the small-batch path, clip close.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
+// the small-batch path, the step groups of the large-batch path (one forward of G x n images behind G step calls), clip close.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
 // framework streams.
 #include <algorithm>
 #include <chrono>
@@ -61,6 +61,9 @@ struct vbt_pipeline {
     std::vector<double> times;
     std::vector<int32_t> cmap;
     std::vector<vbt_run> runs;
+    // a member of a step group: per batch slot the tracker clip (-1: none) and the 1-based frame number it carries; track == 0: not walked
+    std::vector<int32_t> clip, frame;
+    int track = 1;
   };
   std::vector<SlotMeta> meta;
   std::vector<int> group, pending, own_streams;
@@ -81,6 +84,14 @@ struct vbt_pipeline {
   std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
   int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
+  // Step groups: G consecutive vbt_pipeline_step calls share ONE forward.  Every call runs the network entry (resize / upload + the plan
+  // steps that read the frames) on its own n images at once, into slice g of the G n-image tensors of detector instance hold_k; the
+  // group's last call - or whatever reads or changes state first (flush_hold) - enqueues the rest of the plan at batch hold_used * n,
+  // whose decode + NMS fills ring slots hold_o0 .. hold_o0 + hold_used - 1 (one contiguous block), and one time-batched walk.
+  int G = 1;
+  int hold_k = 0, hold_o0 = 0, hold_used = 0;
+  int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step; forwards opened since creation / reset
+  int last_o = 0, last_k = 0;      // ring slot / forward slot of the most recent step
   int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
   // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
@@ -291,9 +302,68 @@ int enqueue_tracker(vbt_pipeline* p, int o) {
   return record_trk(p, o, T);
 }
 
+int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S);
+
+// Close the held-back step group: the rest of the forward at batch hold_used * n on the group's stream, then the OC-SORT walk of its
+// tracked steps in frame order.  A clip walks ONE run per tracker call (its frames at one slot stride and one frame step - every plain
+// group); steps that break the pattern (an `active` mask or clip map that changes inside the group, a detector-only step in the
+// middle) continue in a further call on the same stream.
+int flush_hold(vbt_pipeline* p) {
+  if (p->hold_used == 0) return VBT_OK;
+  const int k = p->hold_k, o0 = p->hold_o0, used = p->hold_used, n = p->n, o_last = o0 + used - 1;
+  p->hold_used = 0;
+  p->next_o = o0 + used + p->G > p->ring ? 0 : o0 + used;   // (a block never wraps)
+  hipStream_t S = p->det_streams[k];
+  for (int g = 0; g < used; g++) PL_CHECK(wait_slot_free(p, o0 + g, S));
+  vbt_model* m = p->models[(size_t)k];
+  PL_CHECK(vbt_detect_range_async(m, nullptr, 0, used * n, vbt_model_entry_steps(m), -1, (void*)S, boxes_of(p, o0), scores_of(p, o0), classes_of(p, o0),
+                                  counts_of(p, o0)));
+  for (int g = 0; g < used; g++) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o0 + g], S));
+  struct Fr { int slot, frame; };
+  std::vector<std::vector<Fr>> per((size_t)p->n_trk);
+  bool any = false;
+  for (int g = 0; g < used; g++) {
+    const vbt_pipeline::SlotMeta& sm = p->meta[(size_t)(o0 + g)];
+    if (!sm.track) continue;
+    for (int i = 0; i < n; i++)
+      if (sm.clip[i] >= 0) { per[(size_t)sm.clip[i]].push_back(Fr{g * n + i, sm.frame[i]}); any = true; }
+  }
+  if (!any) return VBT_OK;
+  hipStream_t T = p->trk_inline ? S : p->trk_stream;
+  if (!p->trk_inline) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o_last], 0));
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));   // tracker launches run in frame order
+  std::vector<size_t> cur((size_t)p->n_trk, 0);
+  std::vector<vbt_run> ra;
+  for (;;) {
+    ra.clear();
+    for (int c = 0; c < p->n_trk; c++) {
+      const std::vector<Fr>& v = per[(size_t)c];
+      const size_t a = cur[(size_t)c];
+      if (a >= v.size()) continue;
+      size_t b = a + 1;
+      int ss = 1, fs = 1;
+      if (b < v.size() && v[b].frame > v[a].frame) {
+        ss = v[b].slot - v[a].slot;
+        fs = v[b].frame - v[a].frame;
+        for (b++; b < v.size() && v[b].slot - v[b - 1].slot == ss && v[b].frame - v[b - 1].frame == fs;) b++;
+      }
+      ra.push_back(vbt_run{c, v[a].slot, ss, (int)(b - a), v[a].frame, fs, p->fps[(size_t)c]});
+      cur[(size_t)c] = b;
+    }
+    if (ra.empty()) break;
+    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o0), scores_of(p, o0), counts_of(p, o0), used * n, ra.data(), (int)ra.size(),
+                                                    p->prm.detection_threshold, (void*)T));
+  }
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o_last], T));
+  for (int g = 0; g < used; g++) p->trk_ev_of[o0 + g] = o_last;
+  p->last_trk = o_last;
+  return VBT_OK;
+}
+
 // Hand the deferred plain steps to the tracker: ONE launch of the time-batched walk on the stream of the group's last forward,
 // after the other members' forwards (events) and the previous tracker launch.
 int flush_group(vbt_pipeline* p) {
+  PL_CHECK(flush_hold(p));   // (a pipeline holds back either a step group or deferred tracker steps, never both)
   std::vector<int> g;
   g.swap(p->group);
   if (g.empty()) return VBT_OK;
@@ -585,7 +655,14 @@ int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S) {
 int step_runs_impl(vbt_pipeline* p, const Sources& src, const vbt_run* asm_runs, int n_asm, std::vector<vbt_run>& walk_runs, int B, int track,
                    float* out_boxes, float* out_scores, float* out_classes, int32_t* out_counts, void* caller_stream) {
   PL_CHECK(flush_group(p));
-  const int o = p->step_idx % p->ring, k = o % p->depth;
+  int o = p->step_idx % p->ring, k = o % p->depth;
+  if (p->G > 1) {   // a forward of its own between the step groups
+    o = p->next_o;
+    k = p->fwd_idx++ % p->depth;
+    p->next_o = o + 1 + p->G > p->ring ? 0 : o + 1;
+  }
+  p->last_o = o;
+  p->last_k = k;
   hipStream_t S = p->det_streams[k];
   PL_CHECK(wait_slot_free(p, o, S));
   p->step_idx++;
@@ -611,6 +688,66 @@ int step_runs_impl(vbt_pipeline* p, const Sources& src, const vbt_run* asm_runs,
     p->pending.erase(p->pending.begin());
     PL_CHECK(enqueue_tracker(p, q));
   }
+  return VBT_OK;
+}
+
+// vbt_pipeline_step of a grouped pipeline (arguments checked by the caller).  Everything that touches the caller's frames happens here, in
+// the call, stream-ordered as in an ungrouped step: the wait for the caller's stream, upload, resize / conversion and the network entry;
+// what is held back reads the model's own tensors only.  There is no ramp: groups of one for the first `depth` forwards measured
+// slower over a 20-step run than full groups from the first step (profiles/r07_step_groups_ab.md).
+int step_grouped(vbt_pipeline* p, const uint8_t* frames, int frames_on_device, int src_h, int src_w, int swap_rb, const uint8_t* active,
+                 const int32_t* clip_map, const int32_t* frame_idx, int track, void* caller_stream) {
+  const int n = p->n;
+  if (clip_map)
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < i; j++)
+        if (clip_map[i] >= 0 && clip_map[i] == clip_map[j]) { set_error("vbt_pipeline_step: clip %d sits in two slots", clip_map[i]); return VBT_ERR_ARG; }
+  if (p->hold_used == 0) {
+    p->hold_k = p->fwd_idx % p->depth;
+    p->hold_o0 = p->next_o;
+    p->fwd_idx++;
+  }
+  const int g = p->hold_used, o = p->hold_o0 + g, k = p->hold_k;
+  hipStream_t S = p->det_streams[k];
+  p->step_idx++;
+  p->frame_count++;
+  Sources src;
+  src.frames = frames;
+  src.on_device = frames_on_device != 0;
+  src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
+  const uint8_t* fd = nullptr;
+  int stage_j = -1;
+  PL_CHECK(prepare_frames(p, k, S, src, nullptr, 0, n, caller_stream, &fd, &stage_j));
+  vbt_pipeline::SlotMeta& m = p->meta[(size_t)o];
+  m.kind = clip_map ? vbt_pipeline::SLOTS : vbt_pipeline::PLAIN;
+  m.fc = p->frame_count;
+  m.B = n;
+  m.track = track;
+  for (int i = 0; i < n; i++) {
+    if (clip_map) {
+      m.clip[i] = clip_map[i];
+      m.frame[i] = frame_idx[i];
+    } else if (!active) {   // frame_count / fps (track.py:169), counted from the slot's last reopen
+      m.clip[i] = i;
+      m.frame[i] = p->frame_count - p->fc_base[(size_t)i];
+    } else if (active[i]) {
+      m.clip[i] = i;
+      m.frame[i] = (int)++p->clip_frames[(size_t)i];
+    } else {
+      m.clip[i] = -1;
+    }
+  }
+  vbt_model* mdl = p->models[(size_t)k];
+  PL_CHECK(vbt_detect_range_async(mdl, fd, g * n, n, 0, vbt_model_entry_steps(mdl), (void*)S, nullptr, nullptr, nullptr, nullptr));
+  if (stage_j >= 0) {   // the entry was the staging buffer's only reader
+    VBT_HIP_CHECK(hipEventRecord(p->stage[(size_t)stage_j].free_ev, S));
+    p->stage[(size_t)stage_j].free_set = true;
+  }
+  p->hold_used++;
+  p->last_o = o;
+  p->last_k = k;
+  p->last_B = n;
+  if (p->hold_used >= p->G) PL_CHECK(flush_hold(p));
   return VBT_OK;
 }
 
@@ -641,6 +778,7 @@ void vbt_pipeline_default_params(vbt_pipeline_params* p) {
 void vbt_pipeline_destroy(vbt_pipeline* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
+  if (p->hold_used > 0) (void)flush_hold(p);   // (the models' tensors are released below: nothing half-run stays behind)
   for (int k = 0; k < p->depth; k++)
     if (p->det_streams[k]) (void)hipStreamSynchronize(p->det_streams[k]);
   if (p->copy_stream) (void)hipStreamSynchronize(p->copy_stream);
@@ -676,8 +814,9 @@ void vbt_pipeline_destroy(vbt_pipeline* p) {
 int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* prm, const double* fps_host, vbt_pipeline** out) {
   if (!container_path || !prm || !fps_host || !out) { set_error("vbt_pipeline_create: NULL argument"); return VBT_ERR_ARG; }
   *out = nullptr;
-  if (prm->n_slots < 1 || prm->n_clips < 0 || prm->rows_cap < 1 || prm->depth < 0 || prm->depth > 8 || prm->device < 0 || prm->device >= 64) {
-    set_error("vbt_pipeline_create: n_slots >= 1, n_clips >= 0, rows_cap >= 1, depth 0..8 required");
+  if (prm->n_slots < 1 || prm->n_clips < 0 || prm->rows_cap < 1 || prm->depth < 0 || prm->depth > 8 || prm->device < 0 || prm->device >= 64 ||
+      prm->group < 0 || prm->group > 8) {
+    set_error("vbt_pipeline_create: n_slots >= 1, n_clips >= 0, rows_cap >= 1, depth 0..8, group 0..8 required");
     return VBT_ERR_ARG;
   }
   int ndev = 0;
@@ -713,12 +852,30 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   const bool defer_ok = p->n_trk == p->n && p->depth >= 2 && p->trk_inline;
   int want = prm->defer >= 0 ? prm->defer : env_int("VBT_TRACKER_DEFER", (p->n <= 8 && p->n_trk == p->n && p->depth >= 2) ? 1 : 0);
   p->defer = (want == 1 && defer_ok) ? p->depth : 0;
-  p->ring = p->defer ? 2 * p->depth : p->depth;
+  // Step groups: at 32..64 images the low-resolution half of the network runs grids too small for the GPU, launch after launch; a forward
+  // of 4 x n images runs the same launches once per four steps on grids four times as wide.  Default only where the plan of that batch
+  // is at hand - a pinned plan file, or no autotuning - so that no pipeline that reads a pinned plan today tunes a new one at creation.
+  {
+    int g = prm->group;
+    if (g == 0) {
+      bool planned = (prm->model_flags & VBT_MODEL_NO_AUTOTUNE) != 0;
+      if (const char* pf = getenv("VBT_PLAN_FILE")) {
+        char path[1024];
+        snprintf(path, sizeof(path), "%s.b%d.f%d", pf, 4 * p->n, prm->model_flags);
+        if (FILE* f = fopen(path, "r")) { planned = true; fclose(f); }
+      }
+      g = (p->n >= 32 && p->n <= 64 && planned) ? 4 : 1;
+    }
+    g = env_int("VBT_PIPELINE_GROUP", g);
+    p->G = p->n_trk == p->n ? std::max(1, std::min(g, 8)) : 1;
+  }
+  if (p->G > 1) p->defer = 0;
+  p->ring = p->G > 1 ? (p->depth + 1) * p->G : p->defer ? 2 * p->depth : p->depth;
   auto fail = [&](int rc) { vbt_pipeline_destroy(p); return rc; };
   int rc = VBT_OK;
   for (int k = 0; k < p->depth; k++) {
     vbt_model* m = nullptr;
-    if ((rc = vbt_model_create_ex(container_path, p->device, p->n, prm->model_flags, &m)) != VBT_OK) return fail(rc);
+    if ((rc = vbt_model_create_ex(container_path, p->device, p->G * p->n, prm->model_flags, &m)) != VBT_OK) return fail(rc);
     p->models.push_back(m);
   }
   int shp[4];
@@ -733,7 +890,10 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   }
   (void)hipMemset(p->counts, 0, R * n * 4);
   p->meta.resize(R);
-  for (auto& m : p->meta) m.times.assign(n, 0.0);
+  for (auto& m : p->meta) {
+    m.times.assign(n, 0.0);
+    if (p->G > 1) { m.clip.assign(n, -1); m.frame.assign(n, 0); }
+  }
   p->trk_ev_of.assign(R, -1);
   auto new_events = [&](std::vector<hipEvent_t>& v, size_t cnt) {
     for (size_t i = 0; i < cnt; i++) {
@@ -775,13 +935,14 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   const int n_check = prm->selfcheck >= 0 ? prm->selfcheck : env_int("VBT_PIPELINE_SELFCHECK", 1);
   if (n_check > 0) {
     uint8_t* blank = nullptr;
-    const size_t bytes = n * p->size * p->size * 3;
+    const size_t bytes = (size_t)p->G * n * p->size * p->size * 3;   // (a grouped pipeline checks the batch its forwards run at)
     if (hipMalloc((void**)&blank, bytes + 64) != hipSuccess) { set_error("vbt_pipeline_create: hipMalloc of the self-check batch failed"); return fail(VBT_ERR_HIP); }
     (void)hipMemset(blank, 0, bytes);
     (void)hipDeviceSynchronize();
     for (int i = 0; i < n_check && rc == VBT_OK; i++)
       for (int k = 0; k < p->depth && rc == VBT_OK; k++)
-        rc = vbt_detect_async(p->models[k], blank, p->n, (void*)p->det_streams[k], boxes_of(p, k), scores_of(p, k), classes_of(p, k), counts_of(p, k));
+        rc = vbt_detect_async(p->models[k], blank, p->G * p->n, (void*)p->det_streams[k], boxes_of(p, k * p->G), scores_of(p, k * p->G),
+                              classes_of(p, k * p->G), counts_of(p, k * p->G));
     hipError_t e = hipSuccess;
     for (int k = 0; k < p->depth; k++) {
       const hipError_t ek = hipStreamSynchronize(p->det_streams[k]);
@@ -807,7 +968,10 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
   if (!clip_map && track && p->n_trk > p->n) { set_error("vbt_pipeline_step: %d clips on %d slots needs clip_map / frame_idx (or vbt_pipeline_step_runs)", p->n_trk, p->n); return VBT_ERR_ARG; }
   StepTimer timer(p);
   VBT_HIP_CHECK(hipSetDevice(p->device));
+  if (p->G > 1) return step_grouped(p, frames, frames_on_device, src_h, src_w, swap_rb, active, clip_map, frame_idx, track, caller_stream);
   const int o = p->step_idx % p->ring, k = o % p->depth;   // output slot; forward slot (model instance, stream)
+  p->last_o = o;
+  p->last_k = k;
   const bool plain = !clip_map && !active && track;
   if (!p->group.empty()) {
     const std::vector<int>& g = p->group;
@@ -923,12 +1087,14 @@ int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt) {
 
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n) {
   if (!p || n < 0) { set_error("vbt_pipeline_skip_frames: bad argument"); return VBT_ERR_ARG; }
+  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
   p->frame_count += n;
   return VBT_OK;
 }
 
 int vbt_pipeline_set_frame_count(vbt_pipeline* p, int frame_count) {
   if (!p || frame_count < 0) { set_error("vbt_pipeline_set_frame_count: bad argument"); return VBT_ERR_ARG; }
+  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
   p->frame_count = frame_count;
   return VBT_OK;
 }
@@ -941,6 +1107,7 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
   PL_CHECK(vbt_tracker_reset(p->trk));
   p->frame_count = 0;
   p->step_idx = 0;
+  p->next_o = p->fwd_idx = p->last_o = p->last_k = 0;
   std::fill(p->trk_ev_of.begin(), p->trk_ev_of.end(), -1);
   p->last_trk = -1;
   std::fill(p->clip_frames.begin(), p->clip_frames.end(), 0);
@@ -952,6 +1119,7 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
 
 int vbt_pipeline_join_detectors(vbt_pipeline* p, void* stream) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
   for (hipEvent_t e : p->ev_det) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, e, 0));
   return VBT_OK;
 }
@@ -1064,6 +1232,7 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
   *ready = 0;
   if (p->closed_unread.empty() || !p->closed_unread[(size_t)clip]) { set_error("vbt_pipeline_closed_clip: slot %d has no unread result", clip); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(flush_hold(p));
   hipEvent_t ev = p->ev_closed[(size_t)clip];
   if (wait) {
     VBT_HIP_CHECK(hipEventSynchronize(ev));
@@ -1119,9 +1288,11 @@ int vbt_pipeline_rows(vbt_pipeline* p, int clip, int64_t* id, double* cols7, int
 int vbt_pipeline_detections(vbt_pipeline* p, float* boxes, float* scores, float* classes, int32_t* counts, int cap_slots, int* B) {
   if (!p || !boxes || !scores || !classes || !counts || !B) { set_error("vbt_pipeline_detections: NULL argument"); return VBT_ERR_ARG; }
   if (p->step_idx < 1) { set_error("vbt_pipeline_detections: no step yet"); return VBT_ERR_STATE; }
-  const int o = (p->step_idx - 1) % p->ring, nb = p->last_B;
+  const int o = p->last_o, nb = p->last_B;
   if (nb > cap_slots) { set_error("vbt_pipeline_detections: %d slots, buffers hold %d", nb, cap_slots); return VBT_ERR_CAPACITY; }
-  hipStream_t S = p->det_streams[o % p->depth];
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(flush_hold(p));   // (the last step's detections are slice `hold_used - 1` of its group's block)
+  hipStream_t S = p->det_streams[p->last_k];
   const size_t md = VBT_MAX_DETECTIONS;
   VBT_HIP_CHECK(hipMemcpyAsync(boxes, boxes_of(p, o), nb * md * 16, hipMemcpyDeviceToHost, S));
   VBT_HIP_CHECK(hipMemcpyAsync(scores, scores_of(p, o), nb * md * 4, hipMemcpyDeviceToHost, S));
@@ -1135,7 +1306,8 @@ int vbt_pipeline_detections(vbt_pipeline* p, float* boxes, float* scores, float*
 int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
   if (!p || count < 1 || slot < 0 || slot >= p->ring) { set_error("vbt_pipeline_tracker_only_steps: bad argument"); return VBT_ERR_ARG; }
   if (p->n_trk != p->n) { set_error("vbt_pipeline_tracker_only_steps needs one tracker clip per detector slot"); return VBT_ERR_STATE; }
-  PL_CHECK(flush_group(p));   // (deferred steps first: tracker launches stay in frame order)
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(flush_group(p));   // (deferred steps / a held-back step group first: tracker launches stay in frame order)
   hipStream_t T = p->trk_stream;
   VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[slot], 0));
   if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));
@@ -1173,6 +1345,8 @@ int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
   out->n_slots = p->n; out->n_clips = p->n_trk; out->rows_cap = p->prm.rows_cap; out->device = p->device; out->depth = p->depth;
   out->ring = p->ring; out->defer = p->defer; out->tracker_inline = p->trk_inline ? 1 : 0; out->image_size = p->size;
   out->frame_count = p->frame_count; out->steps_enqueued = p->step_idx; out->placement_ok = p->placement_ok ? 1 : 0;
+  out->group = p->G;
+  out->next_slot = p->G == 1 ? (p->step_idx % p->ring) % p->depth : p->hold_used > 0 ? p->hold_k : p->fwd_idx % p->depth;
   {
     std::lock_guard<std::mutex> lock(g_pool_mu);
     out->queue_groups_seen = (int)g_pools[p->device].reps.size();

@@ -206,14 +206,15 @@ class Pipeline:
     """n clips processed frame-wise - the batched form of the clip loop of reference track.py:129-260 - as a thin ctypes wrapper of
     `vbt_pipeline` (include/vbt_hip.h): streams and their placement on hardware queues, the ring of detector outputs, the staging
     ring of the host-fed mode, the deferred tracker groups and the clip close all live in libvbt_hip.so (vbt_amd/csrc/pipeline.hip).
-    step(frames) enqueues detect + NMS + one OC-SORT step per clip; close() drains, selects each clip's export id and runs the rep
+    step(frames) enqueues detect + NMS + one OC-SORT step per clip (with `group` > 1 the network entry at once, the rest of the forward and
+    the OC-SORT walk once per `group` calls - same results, wider grids); close() drains, selects each clip's export id and runs the rep
     analysis on the device.  Nothing leaves the GPU until rows() / phases() / close() are read.
 
     Frame sources: numpy arrays (host memory; `vbt_amd.mem.pinned_empty` gives DMA-able ones), raw device pointers, and - a
     convenience for callers who hold them - torch tensors (device or pinned host).  torch is never imported here."""
 
     def __init__(self, model_path, n_clips, max_frames, fps=60.0, detection_treshold=0.5, device=0, rows_per_frame=4,
-                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False):
+                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False, group=None):
         L = _lib.lib()
         self.n = int(n_clips)                       # slots of the detector batch
         # tracker_clips > n_clips: more clips than batch slots; step(clip_map=...) says which clip sits in which slot
@@ -227,6 +228,7 @@ class Pipeline:
         prm.n_slots, prm.n_clips, prm.device = self.n, self.n_trk, self._dev
         prm.rows_cap = int(max_frames) * rows_per_frame + 3 * 25          # frames 1-3 may emit 25 rows each
         prm.depth = int(depth) if depth is not None else 0                 # 0: VBT_PIPELINE_DEPTH, else 4 for <= 8 slots, else 3
+        prm.group = int(group) if group is not None else 0                 # 0: VBT_PIPELINE_GROUP, else 4 for 32..64 slots with a plan at hand, else 1
         prm.detection_threshold = self.thr
         prm.plate_diameter = float(plate_diameter)
         prm.model_flags = int(os.environ.get("VBT_FUSION_FLAGS", "0"))
@@ -249,6 +251,7 @@ class Pipeline:
         info = self.info()
         self.depth, self._ring, self._defer, self._trk_inline = info.depth, info.ring, info.defer, bool(info.tracker_inline)
         self._size = info.image_size
+        self.group = int(info.group)                # step() calls that share one forward (vbt_pipeline_params.group)
         self._det_streams = [_StreamHandle(info.det_streams[k]) for k in range(self.depth)]
         self._copy_stream = _StreamHandle(info.copy_stream)
         self._trk_stream = _StreamHandle(info.tracker_stream)
@@ -328,6 +331,12 @@ class Pipeline:
         self._step_idx = int(self.info().steps_enqueued)
         _lib.check(rc)
 
+    def _next_slot(self):
+        """detector instance / stream the next step call enqueues on (a torch tensor is recorded on that stream)"""
+        if self.group > 1:
+            return int(self.info().next_slot)
+        return (self._step_idx % self._ring) % self.depth
+
     def _hw(self, src_hw):
         return (int(src_hw[0]), int(src_hw[1])) if src_hw is not None else (self._size, self._size)
 
@@ -341,7 +350,7 @@ class Pipeline:
         active: optional bool [n] - clips that still have a frame in this step (clips of different lengths batched together; the
         reference processes them one after the other, track.py:85-126).
         clip_map / frame_idx: int [n] - slot i carries frame number frame_idx[i] (1-based) of tracker clip clip_map[i] (-1: empty)."""
-        k = (self._step_idx % self._ring) % self.depth
+        k = self._next_slot()
         self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ptr, on_dev = self._source(frames_dev_ptr, k, self.n, (H, W))
@@ -371,7 +380,7 @@ class Pipeline:
         L = _lib.lib()
         if outputs is not None and track:
             raise ValueError("step_runs: outputs= is for detector-only steps (track=False)")
-        k = (self._step_idx % self._ring) % self.depth
+        k = self._next_slot()
         self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ra = (_lib.Run * len(runs))()
@@ -427,7 +436,7 @@ class Pipeline:
         B = int(frames.shape[0]) if hasattr(frames, "shape") else self.n
         if not 1 <= B <= self.n:
             raise ValueError(f"detect_into: {B} frames, the pipeline has {self.n} slots")
-        k = (self._step_idx % self._ring) % self.depth
+        k = self._next_slot()
         self._yuv_hw(src_hw, swap_rb)
         H, W = self._hw(src_hw)
         ptr, on_dev = self._source(frames, k, B, (H, W))
