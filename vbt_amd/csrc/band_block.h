@@ -13,6 +13,22 @@
 //       WP [NT][KS][64] x 16 B  projection weights, natural channel order | bias int[16 NT] | mult float[16 NT]
 // 16 wavefronts; both stages on the 16x16x64 int8 MFMA (depthwise as a diagonal-embedded matrix product, four taps per
 // instruction: three instructions for 3x3).  Arithmetic identical to the per-op kernels.
+//
+// Two forms of the depthwise and projection stages:
+//   two-stage  stage D deals (pixel group, channel group) units over the waves and writes the requantised depthwise output to D; a
+//              barrier; stage P deals (pixel group, output tile) units and reads D back as its B operand.  Any width.
+//   chained    (64-channel maps, at most 64 output channels) a wave owns whole pixel groups: it runs the depthwise of all four channel
+//              groups and keeps the four packed dwords in registers.  The depthwise MFMA leaves lane (r, g) with channels 16cg + 4g +
+//              0..3 of pixel r, so those four dwords are 16 int8 channels of pixel r: a B operand of the projection MFMA as it
+//              stands.  The MFMA pairs byte (g, p) of A with byte (g, p) of B and sums in exact int32, so the order of K is free: the
+//              projection panel is packed in that order (pack_band_pw_chain) and the result is bit-identical.  No D tile, no second
+//              barrier, no ds_write / ds_read of D, one slot / address computation per pixel group instead of eight.
+//              LDS:  T0 | WP [NT][64] x 16 B in the chained K order | bias | mult | WD [4][3][64] x 16 B depthwise operands | bias
+//              int[64] | mult float[64] - every wave needs all twelve depthwise operands, so they are staged once per workgroup.
+//              A 240-pixel head band is 44.8 KB against 51 KB: still three workgroups per CU (six waves per SIMD), the cap is not lifted.
+//              A 64-pixel band is LARGER than on the two-stage form (WD 12.5 KB against a D of 5 KB).
+// The planner offers both as kernel variants of the step; the default is the chained form where it exists and max_batch > 8
+// (detector.hip: resolve_band).
 #pragma once
 #include <type_traits>
 
@@ -24,6 +40,7 @@ constexpr int BD_LIT = 3;           // lane-iterations of the load stage whose g
 constexpr int BD_LIT_NODE = 1;      // the same for a node's source loads (up to three 16-byte loads per iteration; registers: the head layers share this kernel)
 constexpr int BD_LIT_NODE_WIDE = 3; // maps of more than 64 channels: LDS leaves at most four waves per SIMD, so 128 registers are free to use
 constexpr int BD_WP_TAIL = 1024;   // bias (512 B) | multipliers (512 B) behind the projection weights in LDS
+constexpr int BD_WD_CHAIN = 12 * 1024 + 512;   // chained form: the twelve depthwise operands | bias (256 B) | multipliers (256 B) behind that
 
 // Developer build (tools/probes/bd_probe.hip): s_memtime stamps of wave 0 at the stage boundaries of every workgroup.
 #ifdef VBT_BD_PROF
@@ -44,6 +61,7 @@ struct BandArgs {
   const float* md;
   Rq rqd;
   const v4i* wp;     // [t][ks][lane] x 16 B: row i = output channel 16t + i, k = 64ks + 16g + j
+  const v4i* wpc;    // chained form (C == 64, else null): [t][lane] x 16 B: row i = output channel 16t + i, byte 4cg + j = k 16cg + 4g + j
   const int* bp;     // bias with the depthwise output's zero point folded, padded to 64-channel blocks
   const float* mp;
   Rq rqp;
@@ -124,9 +142,11 @@ __device__ __forceinline__ uint4 band_source16(const BandArgs& a, int j, long b,
 // 95.0 k vs 98.0 k frames/s; Lite2's 112-channel kernels ran 116 M scalar and 248 M vector instructions per forward on it, against a
 // requantisation floor of about 50 M).
 // NODES: the input may be a BiFPN node's sum of sources; false (the head-layer kernels) compiles that path - and its registers - out.
-template <int NW, int CT, bool NODES = true>
+// CHAIN: the chained form of the depthwise and projection stages (CT == 64 only), see the header comment.
+template <int NW, int CT, bool NODES = true, bool CHAIN = false>
 __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, unsigned char* bd_smem) {
   constexpr int nwaves = NW, nthreads = 64 * NW;
+  static_assert(!CHAIN || CT == 64, "the chained form is built for 64-channel maps");
   constexpr bool C64 = CT == 64, CK = CT != 0;                 // CK: the width is known at compile time
   constexpr int CS_T = CT == 64 ? 80 : CT;                      // bytes per pixel row in LDS: an odd multiple of 16 >= C (64 -> 80, 112 -> 112)
   static_assert(CT == 0 || CT == 64 || CT == 112, "compile-time widths: 64, 112");
@@ -138,13 +158,19 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
   const int C = CK ? CT : a.C, CS = CK ? CS_T : a.CS;
   unsigned char* T0 = bd_smem;
   unsigned char* D = T0 + (a.rows + 2) * PW * CS;
-  unsigned char* WP = D + (((a.rows * a.W + 15) >> 4) << 4) * CS;   // NT x KS KB of weights | 512 B bias | 512 B mult
+  unsigned char* WP = CHAIN ? D : D + (((a.rows * a.W + 15) >> 4) << 4) * CS;   // NT x KS KB of weights | 512 B bias | 512 B mult (chained form: no D)
   const int NT = (a.Cout + 15) >> 4, KS = CK ? (CT + 63) / 64 : a.KS, NCG = CK ? (CT + 15) / 16 : a.NCG;
   unsigned char* WB = WP + NT * KS * 1024;
   BD_STAMP(0);
 
   // ---- stage L: band + border -> T0; projection weights / bias / multipliers -> LDS ----
-  for (int i = tid; i < NT * KS * 64; i += nthreads) *(v4i*)(WP + 16 * i) = a.wp[i];
+  const v4i* wpg = CHAIN ? a.wpc : a.wp;
+  for (int i = tid; i < NT * KS * 64; i += nthreads) *(v4i*)(WP + 16 * i) = wpg[i];
+  if constexpr (CHAIN) {   // all twelve depthwise operands and their bias / multipliers: every wave runs every channel group
+    for (int i = tid; i < 12 * 64; i += nthreads) *(v4i*)(WB + BD_WP_TAIL + 16 * i) = a.wd[i];
+    if (tid >= 64 && tid < 80) *(uint4*)(WB + BD_WP_TAIL + 12 * 1024 + 16 * (tid - 64)) = *(const uint4*)((const unsigned char*)a.bd + 16 * (tid - 64));
+    else if (tid >= 96 && tid < 112) *(uint4*)(WB + BD_WP_TAIL + 12 * 1024 + 256 + 16 * (tid - 96)) = *(const uint4*)((const unsigned char*)a.md + 16 * (tid - 96));
+  }
   if (tid < 4 * NT) *(uint4*)(WB + 16 * tid) = *(const uint4*)((const unsigned char*)a.bp + 16 * tid);
   else if (tid >= 32 && tid < 32 + 4 * NT) *(uint4*)(WB + 512 + 16 * (tid - 32)) = *(const uint4*)((const unsigned char*)a.mp + 16 * (tid - 32));
   const float rcp_pw = frcp(PW);
@@ -279,6 +305,93 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
     }
     }
   }
+  int tapoff[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    const int tap = min(4 * m + g, 8);
+    tapoff[m] = ((tap / 3) * PW + (tap % 3)) * CS;
+  }
+  const float rcp_w = frcp(a.W);
+  if constexpr (CHAIN) {
+    // ---- stages D + P chained: a wave owns whole pixel groups (every NW-th one, two in flight).  It runs the depthwise of all four
+    // channel groups of a pixel group and keeps the four packed dwords: lane (r, g) then holds channels 16cg + 4g + 0..3 of pixel r in
+    // dword cg - a B operand of the projection as it stands, in the K order the chained weight panel (pack_band_pw_chain) is packed
+    // for.  No D tile, no second barrier, one slot / address computation per pixel group instead of one per unit. ----
+    const unsigned char* WD = WB + BD_WP_TAIL;        // [cg][m][lane] x 16 B
+    const unsigned char* WDB = WD + 12 * 1024;        // bias int[64] | multipliers float[64]
+    __syncthreads();
+    BD_STAMP(1);
+    int8_t* ob = a.out + ((b * a.H + y0) * (long)a.W) * a.Cout + 4 * g;   // the band's pixels are contiguous: (y0 + py) * W + px = y0 * W + slot
+    const bool dword_out = (a.Cout & 3) == 0;
+    auto chain = [&](auto fd_c, auto u_c, int pg0) {
+      constexpr int U = decltype(u_c)::value, FULL = decltype(fd_c)::value;
+      int slot[U];
+      const unsigned char* pb[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        slot[u] = (pg0 + u * nwaves) * 16 + r;
+        const int sc = min(slot[u], NPo - 1);
+        const int py = fdiv_small(sc, rcp_w);
+        pb[u] = T0 + (sc + 2 * py) * CS;   // (py * PW + px) with PW = W + 2 and px = sc - py * W
+      }
+      v4i dv[U];
+      {
+#pragma unroll
+        for (int cg = 0; cg < 4; cg++) {
+          v4i wdv[3], bv[U][3], acc[U];
+#pragma unroll
+          for (int m = 0; m < 3; m++) wdv[m] = *(const v4i*)(WD + ((cg * 3 + m) * 64 + lane) * 16);
+          const int4 bq = *(const int4*)(WDB + 64 * cg + 16 * g);
+          const float4 mu = *(const float4*)(WDB + 256 + 64 * cg + 16 * g);
+#pragma unroll
+          for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int m = 0; m < 3; m++) bv[u][m] = *(const v4i*)(pb[u] + tapoff[m] + 16 * cg);
+#pragma unroll
+          for (int u = 0; u < U; u++) acc[u] = v4i_from(int4_plus(bq, FULL >= 2 ? RQ_KBIAS : 0));
+#pragma unroll
+          for (int m = 0; m < 3; m++)
+#pragma unroll
+            for (int u = 0; u < U; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wdv[m], bv[u][m], acc[u], 0, 0, 0);
+#pragma unroll
+          for (int u = 0; u < U; u++) dv[u][cg] = (int)rq_pack_b<FULL>(acc[u], mu, a.rqd);
+          __builtin_amdgcn_sched_barrier(0);   // one channel group's operands at a time: hoisted together, those of all four cost 100 registers more
+        }
+      }
+      rq_dispatch(a.rqp, [&](auto fp_c) {
+        constexpr int FULL = decltype(fp_c)::value;
+        for (int t = 0; t < NT; t++) {
+          const int c0 = 16 * t + 4 * g;
+          const v4i wv = *(const v4i*)(WP + (t * 64 + lane) * 16);
+          const int4 bb = *(const int4*)(WB + 4 * c0);
+          const float4 mm = *(const float4*)(WB + 512 + 4 * c0);
+          v4i acc[U];
+#pragma unroll
+          for (int u = 0; u < U; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, dv[u], v4i_from(int4_plus(bb, FULL >= 2 ? RQ_KBIAS : 0)), 0, 0, 0);
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            const unsigned d = rq_pack_b<FULL>(acc[u], mm, a.rqp);
+            if (slot[u] < NPo && c0 < a.Cout) {
+              int8_t* o = ob + (long)slot[u] * a.Cout + 16 * t;
+              if (dword_out) *(unsigned*)o = d;
+              else
+                for (int j = 0; j < 4; j++)
+                  if (c0 + j < a.Cout) o[j] = (int8_t)(d >> (8 * j));
+            }
+          }
+        }
+      });
+    };
+    // the depthwise's requantisation flavour is picked once per band (inside a pass the operand loads every flavour shares were hoisted above
+    // the choice and spilled), the projection's once per pass
+    rq_dispatch(a.rqd, [&](auto fd_c) {
+      int pg = wave;
+      for (; pg + nwaves < NPG; pg += 2 * nwaves) chain(fd_c, std::integral_constant<int, 2>{}, pg);
+      if (pg < NPG) chain(fd_c, std::integral_constant<int, 1>{}, pg);
+    });
+    BD_STAMP(3);
+    return;
+  }
   // depthwise operands of this wave's channel group (requested before the barrier): wave w owns group w % NCG and, of its
   // pixel groups, every (NW / NCG)-th one; waves beyond NCG * (NW / NCG) sit the stage out (7 groups on 8 / 16 waves: one / two)
   const int cg = wave % NCG, sub = wave / NCG, nsub = nwaves / NCG;
@@ -287,13 +400,6 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
   for (int m = 0; m < 3; m++) wdv[m] = a.wd[(cg * 3 + m) * 64 + lane];
   const int4 bq = *(const int4*)(a.bd + 16 * cg + 4 * g);
   const float4 mu = *(const float4*)(a.md + 16 * cg + 4 * g);
-  int tapoff[3];
-#pragma unroll
-  for (int m = 0; m < 3; m++) {
-    const int tap = min(4 * m + g, 8);
-    tapoff[m] = ((tap / 3) * PW + (tap % 3)) * CS;
-  }
-  const float rcp_w = frcp(a.W);
   __syncthreads();
   BD_STAMP(1);
   // ---- stage D: depthwise; unit = (output pixel group, channel group cg).  Two units of a wave in flight: their operand reads are
@@ -461,11 +567,21 @@ __global__ __launch_bounds__(64 * BD_HEAD_WAVES_WIDE, 2) void sepconv_band_c112_
   const int pi = band_problem(mt);
   sepconv_band_body<BD_HEAD_WAVES_WIDE, 112, false>(probs[pi], (int)blockIdx.x - mt.start[pi], bd_smem_dyn);
 }
+// (three workgroups per CU = six waves per SIMD, as the LDS allows: held to 80 registers)
+__global__ __launch_bounds__(64 * BD_HEAD_WAVES) __attribute__((amdgpu_waves_per_eu(6))) void sepconv_band_chain_kernel(const BandArgs* __restrict__ probs, MultiTiles mt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];
+  const int pi = band_problem(mt);
+  sepconv_band_body<BD_HEAD_WAVES, 64, false, true>(probs[pi], (int)blockIdx.x - mt.start[pi], bd_smem_dyn);
+}
 // One problem (a BiFPN node): the arguments travel in the kernel-argument segment, one dependent memory round trip
 // less at the head of a kernel that is a chain of round trips.
 __global__ __launch_bounds__(BD_THREADS) void sepconv_band_one_kernel(BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];
   sepconv_band_body<BD_WAVES, 64>(a, (int)blockIdx.x, bd_smem_dyn);
+}
+__global__ __launch_bounds__(BD_THREADS) void sepconv_band_one_chain_kernel(BandArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];
+  sepconv_band_body<BD_WAVES, 64, true, true>(a, (int)blockIdx.x, bd_smem_dyn);
 }
 __global__ __launch_bounds__(BD_THREADS) void sepconv_band_one_wide_kernel(BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];

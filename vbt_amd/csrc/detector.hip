@@ -496,6 +496,34 @@ static int launch_expdw_step(const vbt_model* m, const Step& s, int B, hipStream
   return launch_expdw(a, dop.k, dop.stride, (a.Cin + 63) / 64, L.grid, L.lds, st);
 }
 
+// SeparableConv / BiFPN node / head layer on row bands.  Variant: 0 = depthwise and projection as two stages around the LDS tile D,
+// 1 = chained (band_block.h; 64-channel maps with at most 64 output channels), -1: chained where it resolves and max_batch > 8, else two stages.  A step of several
+// problems carries one variant for all its members.
+struct BandLaunch : Verdict { bool chained = false; int lds = 0; };
+static bool band_chainable(const Step& s) {
+  if (s.members.empty()) return s.bd_args.wpc != nullptr;
+  for (const Step& ms : s.members)
+    if (!ms.bd_args.wpc) return false;
+  return true;
+}
+static BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, int) {
+  BandLaunch L;
+  const bool can = band_chainable(s);
+  // what the plan asks for is judged as it stands, before any override: a variant that does not exist for the step is never offered
+  if (variant < -1 || variant > 1) { L.refuse(VBT_ERR_ARG, "fused_sepconv_band: no kernel form %d", variant); return L; }
+  if (variant == 1 && !can) { L.refuse(VBT_ERR_ARG, "fused_sepconv_band: plan asks for the chained form on a step that does not support it"); return L; }
+  // VBT_BAND_VARIANT (tests): that form for every step that supports it, whatever the plan says
+  static const int bd_force = getenv("VBT_BAND_VARIANT") ? atoi(getenv("VBT_BAND_VARIANT")) : -100;
+  if (bd_force == 0 || (bd_force == 1 && can)) variant = bd_force;
+  // the default: chained where it resolves, except for models of max_batch <= 8 (64-pixel bands, make_band): forced onto them the chained
+  // form lost 3-7 % at batch 1 and 1-3 % at batch 8 (profiles/r08_band_chain_ab.md section 5), so they stay on the two-stage form
+  L.chained = variant == 1 || (variant < 0 && can && m->max_batch > 8);
+  if (s.members.empty()) L.lds = band_lds(s.bd_args, L.chained);
+  for (const Step& ms : s.members) L.lds = std::max(L.lds, band_lds(ms.bd_args, L.chained));
+  if (L.lds > 160 * 1024) L.refuse(VBT_ERR_ARG, "fused_sepconv_band: a band of %d bytes does not fit the LDS", L.lds);
+  return L;
+}
+
 // Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major): the batch-offset pointers here, the
 // variant and the launch in the family's own function above.  `frames` = frame boff, the first one of the range; the output pointers
 // are those of the whole batch.
@@ -609,9 +637,11 @@ static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const
     }
     case F_BAND: {
       if (boff != 0) { set_error("fused_sepconv_band: sub-batch streams are not supported (VBT_SUBSTREAMS)"); return VBT_ERR_ARG; }
-      if (s.members.empty()) return launch_band_one(s.bd_args, (unsigned)(B * s.band_tiles), s.lds_bytes, st);
+      const BandLaunch L = resolve_band(m, s, s.variant, B);
+      if (L.rc) return L.report();
+      if (s.members.empty()) return launch_band_one(s.bd_args, L.chained, (unsigned)(B * s.band_tiles), L.lds, st);
       const MultiTiles mt = member_tiles([](const Step& ms) { return ms.band_tiles; });
-      return launch_band_multi(s.d_band, mt, s.members[0].bd_args.C, (unsigned)mt.start[mt.n], s.lds_bytes, st);
+      return launch_band_multi(s.d_band, mt, s.members[0].bd_args.C, L.chained, (unsigned)mt.start[mt.n], L.lds, st);
     }
     case F_EXPDW:
       return launch_expdw_step(m, s, B, st, TP(m->ops[s.e_op].inputs[0]), out);
@@ -699,6 +729,7 @@ static bool is_fused_tile(int family) { return family == F_MBCONV || family == F
 static bool variant_ok(const vbt_model* m, const Step& st, int v) {
   if (st.family == F_PW) return !st.members.empty() || !resolve_pw(m, st, v, m->max_batch).rc;
   if (is_fused_tile(st.family)) return !resolve_fused(m, st, v, m->max_batch).rc;
+  if (st.family == F_BAND) return !resolve_band(m, st, v, m->max_batch).rc;
   return st.family != F_EXPDW || !resolve_expdw(m, st, v, m->max_batch).rc;
 }
 
@@ -736,6 +767,8 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
           if (st.xd2_gpw > 0) cand.push_back(100 + cpw);
           if (st.xd2_gpw16 > 0) cand.push_back(200 + cpw);
         }
+  } else if (st.family == F_BAND) {
+    cand = {-1, 0, 1};   // the launch kind's default, two stages, chained (64-channel maps only)
   }
   cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int v) { return !variant_ok(m, st, v); }), cand.end());
   return cand;

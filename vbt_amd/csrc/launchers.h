@@ -32,8 +32,9 @@ int launch_dw_tile(const DwTileArgs& a, int k, int stride, bool mdw, dim3 grid, 
 int launch_mbconv_image(const FusedArgs& a, const ImageBundle& wb, int k, int stride, int maxu, int PW, int PH, int NB, int lds_bytes, int B,
                         hipStream_t st);
 // SeparableConv / BiFPN node on row bands (band_block.h): one problem by value, or several problems in one grid
-int launch_band_one(const BandArgs& a, unsigned grid, int lds_bytes, hipStream_t st);
-int launch_band_multi(const BandArgs* d_probs, const MultiTiles& mt, int C, unsigned grid, int lds_bytes, hipStream_t st);   // C: channels of the maps (all problems alike)
+// chained: the chained depthwise + projection form (64-channel maps; lds_bytes is then band_lds of that form)
+int launch_band_one(const BandArgs& a, bool chained, unsigned grid, int lds_bytes, hipStream_t st);
+int launch_band_multi(const BandArgs* d_probs, const MultiTiles& mt, int C, bool chained, unsigned grid, int lds_bytes, hipStream_t st);   // C: channels of the maps (all problems alike)
 // whole-image expand + depthwise (expdw_block.h)
 int launch_expdw(const ExpDwArgs& a, int k, int stride, int KS64, unsigned grid, int lds_bytes, hipStream_t st);
 // the same on the second form of the kernel (expdw2_block.h); nw = waves per workgroup (8 or 16; stride 2: 16), gpw = input pixel groups

@@ -246,9 +246,11 @@ static bool band_ok(const vbt_model* m, int d_op, int p_op) {
   return d.k == 3 && d.stride == 1 && d.pad_t == 1 && d.pad_l == 1 && ti.c % 8 == 0 && ti.c >= 16 && ti.c <= 128 && to.c <= 128 && to.h == ti.h &&
          to.w == ti.w && ti.w <= 160;
 }
-static int band_lds(const BandArgs& a) {
+// chained: the form without the depthwise tile D, with the depthwise operands staged behind the projection panel instead (band_block.h)
+static int band_lds(const BandArgs& a, bool chained = false) {
   const int NT = (a.Cout + 15) / 16;
-  return (a.rows + 2) * (a.W + 2) * a.CS + (((a.rows * a.W + 15) >> 4) << 4) * a.CS + NT * a.KS * 1024 + BD_WP_TAIL;
+  const int t0 = (a.rows + 2) * (a.W + 2) * a.CS, wp = NT * a.KS * 1024 + BD_WP_TAIL;
+  return chained ? t0 + wp + BD_WD_CHAIN : t0 + (((a.rows * a.W + 15) >> 4) << 4) * a.CS + wp;
 }
 static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc* ns, Step* out) {
   const OpRec& dop = m->ops[d_op];
@@ -279,7 +281,7 @@ static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc
   a.nbands = (tin.h + a.rows - 1) / a.rows;
   a.zx4 = (unsigned)(tin.zero_point & 255) * 0x01010101u;
   const int8_t* wd = (const int8_t*)(m->blob.data() + dop.w_off);
-  v4i *dpd, *dpp;
+  v4i *dpd, *dpp, *dpc = nullptr;
   int* dbd;
   float* dmd;
   int rc;
@@ -287,7 +289,9 @@ static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc
       (rc = upload(m, fold_bias((const int32_t*)(m->blob.data() + dop.b_off), wd, C, 9, tin.zero_point, W_TAPS, a.NCG * 16), &dbd)) ||
       (rc = upload(m, pad_floats((const float*)(m->blob.data() + dop.m_off), C, a.NCG * 16), &dmd)))
     return rc;
-  a.wd = dpd; a.wp = dpp; a.bd = dbd; a.md = dmd;
+  // the chained form's panel beside the natural-order one: both forms stay launchable (resolve_band)
+  if (C == 64 && to.c <= 64 && (rc = upload(m, pack_band_pw_chain((const int8_t*)(m->blob.data() + pop.w_off), to.c, C), &dpc))) return rc;
+  a.wd = dpd; a.wp = dpp; a.wpc = dpc; a.bd = dbd; a.md = dmd;
   a.bp = m->op_steps[p_op].bias;   // folded with the depthwise output's zero point, padded to 64
   a.mp = m->op_steps[p_op].mult;
   a.rqd = make_rq(td.zero_point, dop.act_min, dop.act_max, conv_kb(m, dop));

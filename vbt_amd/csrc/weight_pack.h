@@ -175,6 +175,24 @@ static std::vector<v4i> pack_band_pw(const int8_t* w, int N, int C) {
       }
   return out;
 }
+// Row-band kernel, projection of the chained form (C = 64): [t][lane] x 16 B in the K order the depthwise leaves in registers; lane
+// (i, g), byte 4cg + j holds W[cout = 16t + i][k = 16cg + 4g + j].  The MFMA pairs byte (g, p) of A with byte (g, p) of B and sums in
+// int32, so any K order the two operands share gives the same sum: each (t, i) row is a permutation of pack_band_pw's.
+static std::vector<v4i> pack_band_pw_chain(const int8_t* w, int N, int C) {
+  const int NT = (N + 15) / 16;
+  std::vector<v4i> out((size_t)NT * 64, (v4i){0, 0, 0, 0});
+  int8_t* o = (int8_t*)out.data();
+  for (int t = 0; t < NT; t++)
+    for (int lane = 0; lane < 64; lane++) {
+      const int i = lane & 15, g = lane >> 4, co = 16 * t + i;
+      for (int cg = 0; cg < 4; cg++)
+        for (int j = 0; j < 4; j++) {
+          const int k = 16 * cg + 4 * g + j;
+          o[((size_t)t * 64 + lane) * 16 + 4 * cg + j] = (co < N && k < C) ? w[(size_t)co * C + k] : 0;
+        }
+    }
+  return out;
+}
 
 // Stem conv K order of the stand-alone stem kernel (3x3x3 -> 32 packed K): 8g + j -> (ky = g, kx = j/3, c = j%3) for g < 3,
 // 24 + j -> (ky = j, kx = 2, c = 2)
