@@ -500,6 +500,81 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
                                double* precision, double* recall, float* pr_thresholds, int pr_cap, double* fpr, double* tpr,
                                float* roc_thresholds, int roc_cap);
 
+/* ------------------------------------------------------------------ tracking overlay --------
+ * Replaces draw_bounding_box / draw_bar_path (reference track.py:28-62,201-224): the tracked plate's box, its tracking id and the bar
+ * path of its last `trail` centres, drawn into frames that already sit in device memory, in place and in the frames' own pixel
+ * format (VBT_PIX_*).  The renderer is a pure function of (frames, DataFrame rows, fps): it needs nothing but the rows
+ * vbt_tracker_rows_all returns, so it runs right after tracking or later from a stored DataFrame.  One colour per handle: the result
+ * does not depend on the drawing order, so the kernel scatters.
+ *
+ * Raster contract.  cv2 is not a dependency: its rasteriser and Hershey font are not pinned and are not the contract.  The geometry
+ * is the reference's; the coverage rules are this library's, stated so that they can be evaluated per pixel.  Once the pixel
+ * coordinates are formed every value is an integer and every product is exact (int64 holds them, see rule 2).
+ *
+ * Per row (id, time, x, y, dx, dy, norm_plate_height h, norm_plate_width w) and a frame of H x W pixels, in IEEE double without
+ * contraction, each double clamped to +-2^20 before a truncating cast (time * fps to +-2^30 before llrint):
+ *   frame = llrint(time * fps)          the 1-based frame_count of track.py:169
+ *   cx = trunc(x * W), cy = trunc(y * H)                                        the np.int32 cast of track.py:213-214
+ *   xmin = trunc((x - w/2) * W), xmax = trunc((x + w/2) * W), ymin = trunc((y - h/2) * H), ymax = trunc((y + h/2) * H)
+ * The box is rebuilt from the row, not taken from the tracker's x1..y2: it can differ from track.py:36-39 by one pixel where a
+ * rounding falls on an integer.
+ * The trail of a row is the (cx, cy) of that row and of the up to trail - 1 rows of the same id before it in (id, time) order -
+ * rows of all earlier frames, whether or not those frames are drawn (track.py:57-58,217-224).
+ *
+ * Pixel (px, py) of a frame is covered when for some row of that frame one of these holds (t = thickness, R = radius, s = label_scale):
+ *   1. Box outline (box != 0).  a = t/2, b = (t+1)/2 (integer division): the pixel lies inside [xmin-a, xmax+a] x [ymin-a, ymax+a]
+ *      and not inside [xmin+b, xmax-b] x [ymin+b, ymax-b]; an empty inner rectangle excludes nothing.  t = 2: columns xmin-1, xmin.
+ *   2. Trail segment, for consecutive trail points P0, P1, each coordinate of both first clamped to [-32768, 32768] (a point that
+ *      far outside the frame bends its segment; frames are at most 16384 a side).  d = P1 - P0, q = (px, py) - P0, L2 = d.d,
+ *      u = q.d, c = q x d = qx dy - qy dx.  If 0 < u < L2: covered iff 4 c^2 <= t^2 L2.  Otherwise: covered iff 4 |p - P|^2 <= t^2
+ *      for the nearer end point P (P0 if u <= 0, else P1); L2 = 0 is the end-point test alone.  With those clamps |2c| < 2^34 and
+ *      t^2 L2 < 2^54: whoever evaluates this in int64 compares |2c| with 3037000499 = floor(sqrt(2^63 - 1)) before squaring it.
+ *   3. Marker: (px - cx)^2 + (py - cy)^2 <= R^2 around the row's own centre (track.py:61-62, filled).
+ *   4. Label (label != 0): the text "id" followed by the decimal id, no space, bottom-left at (xmin, yb), yb = ymin - 15 if
+ *      ymin - 15 > 15 else ymin + 15 (track.py:45).  The score of track.py:46-47 is not in the row log and is left out.  Character
+ *      k, bitmap column c (0..4, left to right = MSB to LSB of the 5 bits) and bitmap row r (0..6, top to bottom) cover the s x s
+ *      block with left column xmin + 6 s k + s c and top row yb - 7 s + 1 + s r.  Glyphs, rows top to bottom:
+ *        0: 01110 10001 10011 10101 11001 10001 01110    6: 00110 01000 10000 11110 10001 10001 01110
+ *        1: 00100 01100 00100 00100 00100 00100 01110    7: 11111 00001 00010 00100 01000 01000 01000
+ *        2: 01110 10001 00001 00010 00100 01000 11111    8: 01110 10001 10001 01110 10001 10001 01110
+ *        3: 11111 00010 00100 00010 00001 10001 01110    9: 01110 10001 10001 01111 00001 00010 01100
+ *        4: 00010 00110 01010 10010 11111 00010 00010    i: 00100 00000 01100 00100 00100 00100 01110
+ *        5: 11111 10000 11110 00001 00001 10001 01110    d: 00001 00001 01101 10011 10001 10001 01111
+ * Covered pixels outside the frame are dropped.  VBT_PIX_RGB24: a covered pixel gets (r, g, b).  YUV: its luma sample gets Y and the
+ * chroma sample at (py >> 1, px >> 1) gets U, V - a chroma sample is written iff one of its four pixels is covered - with
+ *   Y = ((66 r + 129 g + 25 b + 128) >> 8) + 16;  U = ((-38 r - 74 g + 112 b + 128) >> 8) + 128;  V = ((112 r - 94 g - 18 b + 128) >> 8) + 128
+ * (>> arithmetic).  Every other byte is untouched; drawing twice gives the frame drawing once gives.
+ * One difference from the reference: it skips the VideoWriter.write of frames on which the detector found nothing (track.py:180-181),
+ * which makes its video jump in time; here the caller keeps every frame, and a frame without rows comes back as it went in. */
+typedef struct vbt_overlay vbt_overlay;
+typedef struct {
+  int32_t trail;        /* bar path length in points, track.py:57-58 -> 120 */
+  int32_t thickness;    /* box outline and bar path, track.py:42,60 -> 2 */
+  int32_t radius;       /* marker, track.py:62 -> 10 */
+  int32_t label_scale;  /* pixels per bitmap cell -> 3 (a 15 x 21 character) */
+  uint8_t rgb[3];       /* COLORS[1] of track.py:23 -> white */
+  uint8_t label;        /* 0: no label */
+  uint8_t box;          /* 0: no box outline */
+  uint8_t reserved[3];
+} vbt_overlay_params;
+void vbt_overlay_default_params(vbt_overlay_params* p);
+/* params NULL = the defaults.  VBT_ERR_ARG, before any device call: an unknown pix_fmt, H or W < 1 or above 16384, odd H or W with a
+ * YUV format, trail < 1 or > 65536, thickness < 0 or > 1024, radius < 0 or > 16384, label_scale < 1 or > 64. */
+int vbt_overlay_create(int device, int H, int W, int pix_fmt, const vbt_overlay_params* params, vbt_overlay** out);
+void vbt_overlay_destroy(vbt_overlay* o);
+/* The rows to draw from: rows_host = n of the 64-byte records vbt_tracker_rows_all returns, sorted by (id, time) - the order the
+ * exported DataFrame has (track.py:105); fps = the clip's (track.py:136); n = 0 is allowed.  Replaces the handle's previous rows.
+ * VBT_ERR_ARG, checked first and before any device call: fps <= 0 or not finite, a row with a non-finite value, an id < 0 (the label
+ * has no sign), w < 0 or h < 0, rows not sorted by (id, time); VBT_ERR_CAPACITY: a frame number above 2^24 (the frame index is dense).
+ * Uploads the rows and the index from frame number to rows, runs the prepare kernel (per row: the integers above and its trail
+ * length) on `stream` and synchronises it. */
+int vbt_overlay_set_rows(vbt_overlay* o, const void* rows_host, int n, double fps, void* stream);
+/* Draw into B frames, contiguous in device memory (H*W*3 bytes each, H*W*3/2 for the YUV formats), frame i being frame number
+ * frame0 + i * frame_step (frame0, frame_step >= 1).  In place; enqueue only: one launch, workgroups spread over (frame, row of that
+ * frame, primitive), each walking its primitive clipped to the frame - no pass over the frame, no pixel read.  Frames without rows
+ * are not touched. */
+int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

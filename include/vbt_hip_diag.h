@@ -93,6 +93,12 @@ int vbt_model_profile(vbt_model* m, const uint8_t* frames_dev, int B, int reps, 
  * events (`reps` passes), no event pair around every short launch.  ms_out[i] = milliseconds per pass of family i. */
 int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, double* ms_out, int cap);
 
+/* ------------------------------------------------------------------ tracking overlay ---------------------------------- */
+/* What the prepare kernel of vbt_overlay_set_rows made of every row, in row order: out[i] = frame, cx, cy, xmin, ymin, xmax, ymax,
+ * trail length (points) - so that a failing picture can be told from failing geometry.  *n = the handle's rows; cap < *n is
+ * VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
+int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Cost of the tracking overlay (vbt_overlay_draw) against the least any copy-then-draw or whole-frame design would pay.
+
+64 frames of 1920x1080 on the device, RGB24 and NV12, 4 rows per frame, every row with a full 120-point bar path.  Per format:
+  draw   HIP-event time of one vbt_overlay_draw of the batch (one launch), and of 10 back to back divided by 10;
+  copy   HIP-event time of a device-to-device hipMemcpyAsync of the same 64 frames, in the same process, alternating with the draws;
+  median of --reps after --warmup rounds each.  The draw writes well under 1 % of the bytes the copy moves.
+set_rows is timed on the host clock (it synchronises): validation, index, upload and the prepare kernel, for the benchmark's rows and
+for a 10-minute clip's worth (4 ids x 18000 frames).
+
+  python tools/overlay_bench.py [--frames 64] [--reps 20] [--warmup 5] [--out FILE.json]
+
+Prints one JSON line."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, FPS, TRAIL, IDS = 1080, 1920, 30.0, 120, 4
+
+
+def make_rows(n_frames):
+    """IDS plates on Lissajous paths, one row per plate and frame 1..n_frames (a step of about 15 pixels per frame at 1080p)"""
+    import numpy as np
+    d = {k: [] for k in ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")}
+    f = np.arange(1, n_frames + 1)
+    for i in range(IDS):
+        d["id"] += [i + 1] * n_frames
+        d["time"] += (f / FPS).tolist()
+        d["x"] += (0.5 + 0.35 * np.sin(2 * np.pi * f / (293 + 37 * i) + i)).tolist()
+        d["y"] += (0.5 + 0.35 * np.sin(2 * np.pi * f / (211 + 23 * i) + 2 * i)).tolist()
+        d["dx"] += [0.0] * n_frames
+        d["dy"] += [0.0] * n_frames
+        d["norm_plate_height"] += [0.25] * n_frames
+        d["norm_plate_width"] += [0.14] * n_frames
+    return d
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from vbt_amd.overlay import Overlay
+    from vbt_amd.rawvideo import frame_shape
+    if not torch.cuda.is_available():
+        raise SystemExit("overlay_bench: no GPU - a timing taken anywhere else says nothing")
+    so = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
+    hip = ctypes.CDLL(so if os.path.exists(so) else "libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    hip.hipMemcpyAsync.restype = ctypes.c_int
+    B = args.frames
+    frame0 = TRAIL + 1                                            # every row of the batch has a full trail
+    rows = make_rows(TRAIL + B)
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"frames": B, "H": H, "W": W, "rows_per_frame": IDS, "trail": TRAIL, "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+
+    def timed(fn, k=1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(k):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / k                      # microseconds
+
+    for fmt in ("rgb24", "nv12"):
+        shape = (B,) + frame_shape(fmt, H, W)
+        src = torch.from_numpy(np.random.default_rng(0).integers(0, 256, shape, dtype=np.uint8)).cuda()
+        dst = torch.empty_like(src)
+        nbytes = src.numel()
+        ov = Overlay(H, W, fmt)
+        t0 = time.perf_counter()
+        ov.set_rows(rows, FPS, stream)
+        set_rows_us = (time.perf_counter() - t0) * 1e6
+
+        def draw():
+            ov.draw(src.data_ptr(), B, frame0, 1, stream)
+
+        def copy():
+            rc = hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), nbytes, 3, stream)      # hipMemcpyDeviceToDevice
+            assert rc == 0, rc
+        before = src.clone()
+        draw()
+        torch.cuda.synchronize()
+        written = int((src != before).sum().item())               # bytes the draw changed on noise (a lower bound of what it writes)
+        del before
+        t = {"draw": [], "draw10": [], "copy": []}
+        for r in range(args.warmup + args.reps):
+            one = {"draw": timed(draw), "copy": timed(copy), "draw10": timed(draw, 10)}
+            if r >= args.warmup:
+                for k, v in one.items():
+                    t[k].append(v)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        res[fmt] = {"batch_bytes": nbytes, "bytes_changed_by_draw": written, "changed_share": written / nbytes,
+                    "draw_us": med["draw"], "draw_us_min": min(t["draw"]), "draw_back_to_back_us": med["draw10"], "copy_us": med["copy"],
+                    "copy_us_min": min(t["copy"]), "copy_GBps": 2 * nbytes / med["copy"] / 1e3, "draw_over_copy": med["draw"] / med["copy"],
+                    "set_rows_us": set_rows_us, "rows": len(rows["id"])}
+    long_rows = make_rows(18000)
+    ov = Overlay(H, W, "rgb24")
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        ov.set_rows(long_rows, FPS, stream)
+        ts.append((time.perf_counter() - t0) * 1e6)
+    res["set_rows_long"] = {"rows": len(long_rows["id"]), "us_median": statistics.median(ts), "note": "includes the numpy sort of the Python wrapper"}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -63,6 +63,12 @@ class EvalSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("n_rows", "n_pos", "n_neg", "n_pr", "n_roc", "flags")] + [("ap", c_double), ("auc", c_double)]
 
 
+class OverlayParams(ctypes.Structure):
+    """vbt_overlay_params (include/vbt_hip.h)"""
+    _fields_ = [("trail", ctypes.c_int32), ("thickness", ctypes.c_int32), ("radius", ctypes.c_int32), ("label_scale", ctypes.c_int32),
+                ("rgb", ctypes.c_uint8 * 3), ("label", ctypes.c_uint8), ("box", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int), ("algorithmic_bytes", c_double), ("macs", c_double)]
 
@@ -171,6 +177,12 @@ _SIGS = {
     "vbt_eval_curves": (c_int, [c_void_p, c_double, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_eval_curves_from_table": (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int,
                                            c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_overlay_default_params": (None, [ctypes.POINTER(OverlayParams)]),
+    "vbt_overlay_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(OverlayParams), ctypes.POINTER(c_void_p)]),
+    "vbt_overlay_destroy": (None, [c_void_p]),
+    "vbt_overlay_set_rows": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p]),
+    "vbt_overlay_draw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vbt_overlay_geometry": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
 }
 
 

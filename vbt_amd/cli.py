@@ -1,7 +1,7 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
-  python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--fps 30] [--frame_stride 1] [--live]
-                            [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH]
+  python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
+                            [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
       dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
@@ -13,6 +13,12 @@
       --pix_fmt nv12|i420 --size 1920x1080: SRC is a headerless raw video file, YUV 4:2:0 as a decoder emits it (what
       `ffmpeg -i clip.mp4 -pix_fmt nv12 -f rawvideo clip.yuv` writes; nothing here runs ffmpeg), mapped read-only; colour conversion and
       resize run fused on the GPU.  --pix_fmt rgb24 --size WxH reads packed raw RGB the same way; without --size SRC is a .npy stack.
+      --video_dir DIR (reference track.py:71,96-98,241-242): every processed frame with the tracked boxes, ids and bar paths drawn on
+      the GPU (include/vbt_hip.h, "tracking overlay"), as DIR/{video}.npy for .npy sources and as DIR/{video}.rgb / .yuv - headerless,
+      in the source's pixel format, what `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i` reads - for --size sources.  Unlike the reference,
+      frames on which nothing was detected are written too (undrawn): the video does not jump in time.  No container is encoded.
+  python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
+      the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn).
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
@@ -115,7 +121,9 @@ def _raw_size(pix_fmt, size):
 @click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420"]),
               help="Pixel format of the sources; nv12 / i420 (YUV 4:2:0, as a decoder emits it) need --size.")
 @click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of headerless raw video sources, e.g. 1920x1080; without it SRC is a .npy stack.")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size):
+@click.option("--video_dir", default=None, show_default=True,
+              help="Directory for exporting the frames with tracked objects and bar path ({video}.npy, or raw {video}.rgb / .yuv with --size).")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     if concurrent < 1:
@@ -123,11 +131,13 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
-        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size)
+        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir)
     for s in src:
         frames = _open_source(s, pix_fmt, size)
+        video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
         data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                            live=_LiveReps(s) if live else None, pix_fmt=pix_fmt)
+                            live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video)
+        _video_done(video)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")
             continue
@@ -135,7 +145,33 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         click.echo(f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else ""))
 
 
-def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None):
+def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size):
+    """The writable map of --video_dir for source `s` (None without --video_dir, or when no frame is kept): DIR/{video}.npy
+    (numpy.lib.format.open_memmap, so a long clip never sits in memory) or, for --size sources, raw DIR/{video}.rgb / .yuv."""
+    if video_dir is None:
+        return None
+    os.makedirs(video_dir, exist_ok=True)                                # reference track.py:85-86
+    stem = os.path.basename(s).split(".")[0]                             # reference track.py:97
+    shape = (int(frames.shape[0]) // max(int(frame_stride), 1),) + tuple(frames.shape[1:])
+    if size is None:
+        path = os.path.join(video_dir, stem + ".npy")
+        if shape[0] == 0:
+            np.save(path, np.zeros(shape, np.uint8))
+            return None
+        return np.lib.format.open_memmap(path, mode="w+", dtype=np.uint8, shape=shape)
+    path = os.path.join(video_dir, stem + (".rgb" if pix_fmt == "rgb24" else ".yuv"))
+    if shape[0] == 0:
+        open(path, "wb").close()
+        return None
+    return np.memmap(path, dtype=np.uint8, mode="w+", shape=shape)
+
+
+def _video_done(video):
+    if video is not None:
+        video.flush()
+
+
+def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -151,6 +187,11 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
                               time_batch=time_batch, pix_fmt=pix_fmt):
         s = src[i]
+        video = _video_out(video_dir, s, sources[i], frame_stride, pix_fmt, size)
+        if video is not None:                                            # the clip is finished: its rows are all the renderer needs
+            from .overlay import render
+            render(sources[i], data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video)
+            _video_done(video)
         if not data["id"]:
             lines[i] = f"{s}: no tracked rows"
         else:
@@ -161,6 +202,33 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
             nxt += 1
     if error is not None:
         raise error
+
+
+@main.command()
+@click.argument("src", type=str)
+@click.argument("dataframe", type=str)
+@click.option("--fps", default=30.0, show_default=True, type=float, help="Frame rate the DataFrame was tracked at (its times are frame numbers / fps).")
+@click.option("--frame_stride", default=1, show_default=True, type=int, help="The --frame_stride the DataFrame was tracked with: the frames that are kept.")
+@click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420"]),
+              help="Pixel format of the source; nv12 / i420 need --size.")
+@click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of a headerless raw video source; without it SRC is a .npy stack.")
+@click.option("--video_dir", default=".", show_default=True, help="Directory for the drawn frames ({video}.npy, or raw {video}.rgb / .yuv with --size).")
+def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir):
+    """Draw the boxes, ids and bar paths of a stored DataFrame into the frames of its clip (what `track --video_dir` writes)."""
+    import pandas as pd
+    from .overlay import render
+    size = _raw_size(pix_fmt, size)
+    if frame_stride < 1:
+        raise click.UsageError("--frame_stride must be at least 1")
+    if not os.path.isfile(dataframe):
+        raise FileNotFoundError(dataframe)
+    frames = _open_source(src, pix_fmt, size)
+    df = pd.read_pickle(dataframe)
+    video = _video_out(video_dir, src, frames, frame_stride, pix_fmt, size)
+    if video is not None:
+        render(frames, df, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, out=video)
+        _video_done(video)
+    click.echo(f"{src}: {0 if video is None else len(video)} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")
 
 
 @main.command()

@@ -1,0 +1,105 @@
+"""Tracking overlay: box, tracking id and bar path of the tracked plates drawn into the frames on the GPU - what the reference's
+`track.py --video_dir` writes (draw_bounding_box / draw_bar_path, track.py:28-62,201-224) without cv2.
+
+The renderer is a pure function of (frames, DataFrame rows, fps): `render` runs right after tracking or later from a stored
+`*.pkl.gz`.  The raster contract (which pixels a box, a bar path segment, the marker and the label cover, and the YUV colour) is in
+include/vbt_hip.h, "tracking overlay"; drawing happens in place, in the frames' own pixel format.  torch-free: device memory and
+copies through vbt_device_alloc / vbt_memcpy, like Pipeline."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .mem import DeviceBuffer
+from .ocsort import ROW_DTYPE
+from .rawvideo import frame_shape, pix_fmt_code, source_hw
+
+COLUMNS = ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
+COLORS = [(252, 3, 115), (255, 255, 255)]          # COLORS of reference track.py:23 (BGR there) as RGB; the reference draws with [1]
+
+
+def sorted_rows(data):
+    """DataFrame or dict of lists (reference track.py:144-145) -> ROW_DTYPE records sorted by (id, time), the order of track.py:105"""
+    n = len(data["id"])
+    rows = np.zeros(n, ROW_DTYPE)
+    for k in COLUMNS:
+        rows[k] = np.asarray(data[k])
+    return rows[np.lexsort((rows["time"], rows["id"]))]
+
+
+class Overlay:
+    """vbt_overlay (include/vbt_hip.h): one frame size, pixel format, colour and set of rows.
+    params: trail=120, thickness=2, radius=10, label_scale=3, rgb=(255, 255, 255), label=True, box=True."""
+
+    def __init__(self, H, W, pix_fmt="rgb24", device=0, **params):
+        L = _lib.lib()
+        prm = _lib.OverlayParams()
+        L.vbt_overlay_default_params(ctypes.byref(prm))
+        for k, v in params.items():
+            if k == "rgb":
+                prm.rgb[:] = [int(c) for c in v]
+            elif k in ("trail", "thickness", "radius", "label_scale", "label", "box"):
+                setattr(prm, k, int(v))
+            else:
+                raise TypeError(f"Overlay: unknown parameter {k!r}")
+        self.H, self.W, self.pix_fmt, self.device = int(H), int(W), str(pix_fmt).lower(), int(device)
+        h = ctypes.c_void_p()
+        _lib.check(L.vbt_overlay_create(self.device, self.H, self.W, pix_fmt_code(pix_fmt), ctypes.byref(prm), ctypes.byref(h)))
+        self._h = h
+        self.n = 0
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None and getattr(_lib, "_lib", None) is not None:
+            _lib._lib.vbt_overlay_destroy(h)
+
+    def set_rows(self, data, fps, stream=None):
+        """data: DataFrame or dict of lists with the reference's columns, any order; sorted here by (id, time)."""
+        rows = np.ascontiguousarray(sorted_rows(data))
+        _lib.check(_lib.lib().vbt_overlay_set_rows(self._h, rows.ctypes.data, len(rows), float(fps), stream))
+        self.n = len(rows)
+
+    def draw(self, frames_ptr, B, frame0, frame_step=1, stream=None):
+        """B frames at device pointer `frames_ptr`, frame i = frame number frame0 + i * frame_step; in place, enqueue only"""
+        _lib.check(_lib.lib().vbt_overlay_draw(self._h, int(frames_ptr), int(B), int(frame0), int(frame_step), stream))
+
+    def geometry(self):
+        """int32 [n, 8] = frame, cx, cy, xmin, ymin, xmax, ymax, trail length of every row (vbt_overlay_geometry)"""
+        out = np.zeros((max(self.n, 1), 8), np.int32)
+        n = ctypes.c_int()
+        _lib.check(_lib.lib().vbt_overlay_geometry(self._h, out.ctypes.data, len(out), ctypes.byref(n)))
+        return out[:n.value]
+
+
+def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, **params):
+    """The kept frames of a clip (1-based number a multiple of frame_stride, reference track.py:166) with the overlay of `data`:
+    frames uint8 [T,H,W,3] (or [T,H*3//2,W] for "nv12" / "i420"; numpy array or memmap), `batch` frames at a time through the device.
+    Returns (or fills `out`, e.g. a numpy.lib.format.open_memmap) uint8 [T // frame_stride, ...] of the same layout.  Unlike the
+    reference (track.py:180-181,241-242) every kept frame is there: one without rows comes back undrawn."""
+    stride = max(int(frame_stride), 1)
+    H, W = source_hw(frames, pix_fmt)
+    shape = frame_shape(pix_fmt, H, W)
+    if tuple(frames.shape[1:]) != shape or frames.dtype != np.uint8:
+        raise ValueError(f"render: {pix_fmt} frames must be uint8 [T, {', '.join(str(v) for v in shape)}], got {frames.dtype} {tuple(frames.shape)}")
+    kept = int(frames.shape[0]) // stride
+    if out is None:
+        out = np.empty((kept,) + shape, np.uint8)
+    elif tuple(out.shape) != (kept,) + shape or out.dtype != np.uint8:
+        raise ValueError(f"render: out must be uint8 {(kept,) + shape}, got {out.dtype} {tuple(out.shape)}")
+    ov = Overlay(H, W, pix_fmt, device=device, **params)
+    ov.set_rows(data, fps)
+    L = _lib.lib()
+    B = max(1, min(int(batch), max(kept, 1)))
+    fb = int(np.prod(shape))
+    buf = DeviceBuffer(B * fb, device)
+    host = np.empty((B,) + shape, np.uint8)
+    for i0 in range(0, kept, B):
+        nb = min(B, kept - i0)
+        first = (i0 + 1) * stride - 1                               # 0-based index of the batch's first kept frame
+        host[:nb] = frames[first:first + (nb - 1) * stride + 1:stride]
+        _lib.check(L.vbt_memcpy(buf.ptr, host.ctypes.data, nb * fb, 0))
+        ov.draw(buf.ptr, nb, (i0 + 1) * stride, stride)
+        _lib.check(L.vbt_stream_synchronize(None))
+        _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr, nb * fb, 1))
+        out[i0:i0 + nb] = host[:nb]
+    return out

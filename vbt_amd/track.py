@@ -2,8 +2,9 @@
 and `Pipeline`, its batched MI355X form (n clips frame-wise through detect -> NMS -> tracker on
 one stream, rep analysis at the end).
 
-No GUI: drawing / imshow / VideoWriter (reference track.py:28-62,201-207,237-247) are out of
-scope.  Frame sources are arrays / iterables of RGB uint8 frames instead of
+No GUI: imshow / waitKey (reference track.py:237-247) are out of scope; the
+annotated frames of `--video_dir` (track.py:28-62,201-224,241-242) are drawn on the GPU by
+vbt_amd/overlay.py.  Frame sources are arrays / iterables of RGB uint8 frames instead of
 cv2.VideoCapture (cv2 is not a dependency here).
 """
 import collections
@@ -64,7 +65,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None):
+                 src_hw=None, video_out=None):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -73,7 +74,17 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     live: optional callable(ocsort.LiveClip, final) - live rep analysis on: called after every batch with the clip's record, and
     once more after the last one with the flush view (final=True: the phases the clip close gives).
     pix_fmt "nv12" / "i420": frames is uint8 [T, H*3//2, W], YUV 4:2:0 as a decoder emits it (rawvideo.py); converted and resized
-    on the GPU.  src_hw=(H, W) is then optional (the shape gives it)."""
+    on the GPU.  src_hw=(H, W) is then optional (the shape gives it).
+    video_out: optional uint8 array [T // frame_stride, ...] with the frames' layout (e.g. a numpy.lib.format.open_memmap) that receives
+    every kept frame with the tracked boxes, ids and bar paths drawn (overlay.render; the reference's `--video_dir`, track.py:241-242)."""
+    data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw)
+    if video_out is not None:
+        from .overlay import render
+        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device)
+    return data
+
+
+def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw):
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
     if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
