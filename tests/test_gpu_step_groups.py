@@ -206,3 +206,29 @@ def test_reset_with_a_group_pending(pipes, frames_dev, ref7):
         pipe.step(frames_dev[5].data_ptr(), _stream())
         pipe.step(frames_dev[6].data_ptr(), _stream())      # group=3: both still held back
         _same(_seven_steps(pipe, frames_dev), ref7, f"group={pipe.group}")
+
+
+def test_step_groups_with_the_tracker_on_its_own_stream(model_path, frames_dev, ref7):
+    """depth 2 puts the OC-SORT walk on the tracker stream: it waits there for the group's forward and for the walk before it"""
+    from vbt_amd.track import Pipeline
+    pipe = Pipeline(model_path, N, max_frames=64, fps=60.0, slot_close=True, group=3, depth=2)
+    info = pipe.info()
+    assert pipe.group == 3 and info.depth == 2 and info.tracker_inline == 0
+    _same(_seven_steps(pipe, frames_dev), ref7)
+
+
+def test_step_runs_between_plain_steps(pipes, frames_dev):
+    """Frame 3 arrives as a time-batched step: on the grouped pipeline it closes the group of frames 1 and 2 and runs a forward of its own"""
+    got = []
+    for pipe in pipes:
+        pipe.reset()
+        st = _stream()
+        pipe.step(frames_dev[0].data_ptr(), st)
+        pipe.step(frames_dev[1].data_ptr(), st)
+        pipe.step_runs(frames_dev[2], [(c, c, 1, 3) for c in range(N)], st)
+        pipe.skip_frames(1)                         # the run step does not count frames: frame 3 is counted here
+        for t in range(3, T):
+            pipe.step(frames_dev[t].data_ptr(), st)
+        got.append(_result(pipe))
+    _same(got[1], got[0])
+    assert int(got[0]["counts"].sum()) > 0

@@ -4,45 +4,21 @@
 // vbt_tracker_update_from_*, vbt_resize_frames, vbt_gather_frames; the slot close through tracker_close_clips, common.h).  What lives here is the part of the fast path that is not a
 // kernel: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
 // events that order detector(t) -> tracker(t) -> slot reuse, the staging ring of the host-fed mode, the deferred tracker groups of
-// the small-batch path, the step groups of the large-batch path (one forward of G x n images behind G step calls), clip close.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
+// the small-batch path and the step groups of the large-batch path (one forward of G x n images behind G step calls) as one held-back
+// block, clip close.  The stream pool is stream_pool.h, the run lists of a block's walk walk_runs.h.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
 // framework streams.
 #include <algorithm>
 #include <chrono>
-#include <map>
-#include <mutex>
 
 #include "common.h"
+#include "stream_pool.h"
+#include "walk_runs.h"
 
 // (resize_frames_dev, common.h: preprocess_image reading either whole source frames [B][H][W][3] or, compact != 0, only the row pairs the
 //  bilinear resize touches: [B][2h][W][3], pair d = source rows p(d), p(d) + 1 with p(d) = min(floor(src_y(d)), H - 2);
 //  resize_frames_yuv_dev: the same with the NV12 / I420 conversion fused, vbt_pipeline_set_pixel_format)
 
 using namespace vbt;
-
-namespace {
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// Process-wide stream pool, one per device.  HIP binds a stream to one of GPU_MAX_HW_QUEUES hardware queues when it is created (a
-// zig-zag that also counts streams created by others) and the queue cannot be queried, so a pool stream is CLASSIFIED once per
-// process: timed with a spinning wave against one representative of every queue group known so far (vbt_streams_share_queue,
-// ~0.3 ms per probe).  Streams are kept for the life of the process and handed out again when a pipeline goes away, so that any
-// number of pipelines created one after the other end up on the same few streams.
-// ------------------------------------------------------------------------------------------------------------------------------
-struct StreamPool {
-  std::vector<hipStream_t> streams;
-  std::vector<int> free;          // indices not owned by a pipeline
-  std::map<int, int> group;       // stream index -> hardware-queue group
-  std::vector<int> reps;          // one stream index per known group
-};
-std::mutex g_pool_mu;
-StreamPool g_pools[64];
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
-}  // namespace
 
 struct vbt_pipeline {
   vbt_pipeline_params prm{};
@@ -52,21 +28,31 @@ struct vbt_pipeline {
   std::vector<double> fps;
   std::vector<vbt_model*> models;
   vbt_tracker* trk = nullptr;
-  // detector outputs: one block per tensor, [ring slot][batch slot]...: the deferred walk addresses frame f of clip c as slot (o0 + f) * n + c
+  // detector outputs: one array per tensor, [ring slot][batch slot]...: the walk of a block addresses batch slot i of its step g as slot g * n + i
   float *boxes = nullptr, *scores = nullptr, *classes = nullptr;
   int32_t* counts = nullptr;
-  enum { PLAIN = 0, SLOTS = 1, RUNS = 2 };
-  struct SlotMeta {
-    int kind = PLAIN, B = 0, fc = 0;
-    std::vector<double> times;
-    std::vector<int32_t> cmap;
-    std::vector<vbt_run> runs;
-    // a member of a step group: per batch slot the tracker clip (-1: none) and the 1-based frame number it carries; track == 0: not walked
+  // What the tracker needs to know about the step in a ring slot.  vbt_pipeline_step (fill_step): per batch slot the tracker clip (-1: none)
+  // and the 1-based frame number of that clip; vbt_pipeline_step_runs: the runs to walk, and then clip / frame are not read.
+  struct Step {
+    int B = 0, fc = 0, track = 1;   // batch slots used; frame_count at the step; 0: detector only, never walked
+    bool mapped = false;            // the step came with a clip map: its single-step launch is vbt_tracker_update_from_slots
     std::vector<int32_t> clip, frame;
-    int track = 1;
+    std::vector<vbt_run> runs;
   };
-  std::vector<SlotMeta> meta;
-  std::vector<int> group, pending, own_streams;
+  std::vector<Step> meta;
+  // The held-back block: `used` steps in ring slots o0 .. o0 + used - 1 whose OC-SORT walk goes out as one time-batched launch (flush_block).
+  //  - Step group (G > 1): the steps share ONE forward of detector instance k.  Every call runs the network entry (resize / upload + the
+  //    plan steps that read the frames) on its own n images at once, into slice g of the G n-image tensors; the flush enqueues the rest of
+  //    the plan at batch used * n, whose decode + NMS fills the block's ring slots.
+  //  - Deferred tracker steps (G == 1, defer > 0, plain steps only): every step ran its whole forward on its own stream; k is the
+  //    forward slot of the last one.
+  struct Block { int o0 = 0, used = 0, k = 0; } blk;
+  std::vector<int> pending;        // own-stream tracker: steps whose launch lags the detector, oldest first (never together with a block)
+  std::vector<int> own_streams;
+  std::vector<double> times;                      // scratch of a single-step launch
+  std::vector<std::vector<WalkFrame>> walk_per;   // scratch of flush_block: per tracker clip its frames in the block
+  std::vector<size_t> walk_cur;
+  std::vector<vbt_run> walk_runs;
   hipStream_t det_streams[8] = {nullptr}, copy_stream = nullptr, trk_stream = nullptr;
   std::vector<hipEvent_t> ev_in, ev_det, ev_trk;
   std::vector<int> trk_ev_of;      // ring slot -> index into ev_trk of the tracker launch that read it last (-1: none)
@@ -84,13 +70,8 @@ struct vbt_pipeline {
   std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
   int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
-  // Step groups: G consecutive vbt_pipeline_step calls share ONE forward.  Every call runs the network entry (resize / upload + the plan
-  // steps that read the frames) on its own n images at once, into slice g of the G n-image tensors of detector instance hold_k; the
-  // group's last call - or whatever reads or changes state first (flush_hold) - enqueues the rest of the plan at batch hold_used * n,
-  // whose decode + NMS fills ring slots hold_o0 .. hold_o0 + hold_used - 1 (one contiguous block), and one time-batched walk.
-  int G = 1;
-  int hold_k = 0, hold_o0 = 0, hold_used = 0;
-  int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step; forwards opened since creation / reset
+  int G = 1;                       // steps per forward (vbt_pipeline_params.group)
+  int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step (a block never wraps); forwards opened since creation / reset
   int last_o = 0, last_k = 0;      // ring slot / forward slot of the most recent step
   int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
@@ -118,151 +99,6 @@ struct StepTimer {
   }
 };
 
-#define PL_CHECK(expr)            \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_ != VBT_OK) return rc_; \
-  } while (0)
-
-// ---- stream pool ----
-int pool_take(vbt_pipeline* p, StreamPool& pool, int i, bool create, int* out) {
-  if (i < 0) {
-    if (!pool.free.empty() && !create) {
-      i = *std::min_element(pool.free.begin(), pool.free.end());
-    } else {
-      void* h = nullptr;
-      PL_CHECK(vbt_stream_create(p->device, &h));
-      pool.streams.push_back((hipStream_t)h);
-      i = (int)pool.streams.size() - 1;
-      pool.free.push_back(i);
-    }
-  }
-  pool.free.erase(std::find(pool.free.begin(), pool.free.end(), i));
-  p->own_streams.push_back(i);
-  *out = i;
-  return VBT_OK;
-}
-
-int streams_shared(StreamPool& pool, int i, int j, bool* shared) {
-  // host-timed: a descheduled host thread can make one probe read "shared"; two in a row cannot
-  for (int rep = 0; rep < 2; rep++) {
-    int sh = 0;
-    PL_CHECK(vbt_streams_share_queue((void*)pool.streams[i], (void*)pool.streams[j], 150, &sh));
-    if (!sh) { *shared = false; return VBT_OK; }
-  }
-  *shared = true;
-  return VBT_OK;
-}
-
-int group_of(StreamPool& pool, int i, int* g_out) {
-  auto it = pool.group.find(i);
-  if (it == pool.group.end()) {
-    int g = -1;
-    for (int k = 0; k < (int)pool.reps.size() && g < 0; k++) {
-      bool sh = false;
-      PL_CHECK(streams_shared(pool, i, pool.reps[k], &sh));
-      if (sh) g = k;
-    }
-    if (g < 0) {
-      g = (int)pool.reps.size();
-      pool.reps.push_back(i);
-    }
-    it = pool.group.emplace(i, g).first;
-  }
-  *g_out = it->second;
-  return VBT_OK;
-}
-
-// The streams that carry kernels side by side (detector slots, the copy stream, the tracker stream unless its step runs inline)
-// must sit on distinct hardware queues: a pipeline takes its busy streams from distinct groups - a stream that once collided is
-// simply left for another role - and only creates streams while some group is still unseen.
-int place_streams(vbt_pipeline* p, StreamPool& pool, int role_idx[10]) {
-  // roles: 0..depth-1 detector slots, 8 copy, 9 tracker
-  if (env_int("VBT_PLACE_STREAMS", 1) == 0) return VBT_OK;
-  VBT_HIP_CHECK(hipDeviceSynchronize());
-  std::vector<int> busy;
-  for (int k = 0; k < p->depth; k++) busy.push_back(k);
-  if (p->depth < 4) busy.push_back(8);   // (four hardware queues: with four forwards in flight the copy stream has to share one, which costs a small batch nothing)
-  if (!p->trk_inline) busy.push_back(9);
-  auto is_busy = [&](int r) { return std::find(busy.begin(), busy.end(), r) != busy.end(); };
-  const int all_roles[10] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9};
-  const int nq = std::max(1, env_int("GPU_MAX_HW_QUEUES", 4));
-  std::vector<int> used;
-  auto in_used = [&](int g) { return std::find(used.begin(), used.end(), g) != used.end(); };
-  bool failed = false;
-  for (int role : busy) {
-    int cur = role_idx[role], g = 0;
-    PL_CHECK(group_of(pool, cur, &g));
-    if (in_used(g)) {
-      // another stream of a group this pipeline does not use yet: one it already holds for an idle role, a free pool stream, or -
-      // while fewer groups than hardware queues are known, and at most 3 nq times - a new one
-      int cand = -1;
-      bool from_spare = false;
-      for (int r : all_roles) {
-        if (role_idx[r] < 0 || is_busy(r)) continue;
-        int gr = 0;
-        PL_CHECK(group_of(pool, role_idx[r], &gr));
-        if (!in_used(gr)) { cand = role_idx[r]; from_spare = true; break; }
-      }
-      if (cand < 0) {
-        std::vector<int> fr = pool.free;
-        std::sort(fr.begin(), fr.end());
-        for (int i : fr) {
-          int gi = 0;
-          PL_CHECK(group_of(pool, i, &gi));
-          if (!in_used(gi)) { cand = i; break; }
-        }
-      }
-      int created = 0;
-      while (cand < 0 && (int)pool.reps.size() < nq && created < 3 * nq) {
-        int i = -1, gi = 0;
-        PL_CHECK(pool_take(p, pool, -1, true, &i));
-        created++;
-        PL_CHECK(group_of(pool, i, &gi));
-        if (!in_used(gi)) {
-          cand = i;
-        } else {   // stays in the pool for a later pipeline / another role
-          pool.free.push_back(i);
-          p->own_streams.erase(std::find(p->own_streams.begin(), p->own_streams.end(), i));
-        }
-      }
-      if (cand < 0) { failed = true; continue; }
-      if (std::find(pool.free.begin(), pool.free.end(), cand) != pool.free.end()) {
-        int dummy = 0;
-        PL_CHECK(pool_take(p, pool, cand, false, &dummy));
-      }
-      if (from_spare)   // swap the two roles' streams
-        for (int r : all_roles)
-          if (role_idx[r] == cand) { role_idx[r] = cur; break; }
-      role_idx[role] = cand;
-      cur = cand;
-      PL_CHECK(group_of(pool, cur, &g));
-    }
-    used.push_back(g);
-  }
-  // streams taken but left without a role go back to the pool
-  for (size_t k = 0; k < p->own_streams.size();) {
-    const int i = p->own_streams[k];
-    bool held = false;
-    for (int r : all_roles) held = held || role_idx[r] == i;
-    if (held) { k++; continue; }
-    p->own_streams.erase(p->own_streams.begin() + (long)k);
-    pool.free.push_back(i);
-  }
-  if (failed) {
-    p->placement_ok = false;
-    char msg[512];
-    snprintf(msg, sizeof(msg),
-             "vbt_pipeline: could not give every pipeline stream its own hardware queue: %d busy streams (depth %d%s%s), %d distinct queues seen, "
-             "GPU_MAX_HW_QUEUES=%d (too few queues for this configuration, or kernels are being serialised by a profiler); throughput will be lower",
-             (int)busy.size(), p->depth, p->trk_inline ? "" : " + tracker stream", p->depth < 4 ? " + copy stream" : "", (int)pool.reps.size(), nq);
-    const int strict = p->prm.strict_placement >= 0 ? p->prm.strict_placement : env_int("VBT_STRICT_PLACEMENT", 0);
-    if (strict == 1) { set_error("%s", msg); return VBT_ERR_STATE; }
-    fprintf(stderr, "%s\n", msg);
-  }
-  return VBT_OK;
-}
-
 // ---- output ring ----
 inline float* boxes_of(vbt_pipeline* p, int o) { return p->boxes + (size_t)o * p->n * VBT_MAX_DETECTIONS * 4; }
 inline float* scores_of(vbt_pipeline* p, int o) { return p->scores + (size_t)o * p->n * VBT_MAX_DETECTIONS; }
@@ -276,8 +112,46 @@ int record_trk(vbt_pipeline* p, int o, hipStream_t T) {
   return VBT_OK;
 }
 
-// the OC-SORT step(s) of ring slot o: on the tracker stream after the slot's detections ("own"), or at the end of the slot's own
-// stream after the previous frame's tracker step ("inline": stream order gives "after this slot's detections")
+// Ring slot and forward slot (model instance, stream) of the next step.  Ungrouped: the ring in order.  Grouped: a block continues
+// while one is open, else the next forward starts at next_o.
+void next_slots(const vbt_pipeline* p, int* o, int* k) {
+  if (p->G == 1) {
+    *o = p->step_idx % p->ring;
+    *k = *o % p->depth;
+  } else if (p->blk.used > 0) {
+    *o = p->blk.o0 + p->blk.used;
+    *k = p->blk.k;
+  } else {
+    *o = p->next_o;
+    *k = p->fwd_idx % p->depth;
+  }
+}
+
+// The step record of a vbt_pipeline_step call (frame_count already counts the step)
+void fill_step(vbt_pipeline* p, vbt_pipeline::Step& m, const uint8_t* active, const int32_t* clip_map, const int32_t* frame_idx, int track) {
+  m.B = p->n;
+  m.fc = p->frame_count;
+  m.track = track;
+  m.mapped = clip_map != nullptr;
+  m.runs.clear();
+  for (int i = 0; i < p->n; i++) {
+    if (clip_map) {
+      m.clip[i] = clip_map[i];
+      m.frame[i] = frame_idx[i];
+    } else if (!active) {   // frame_count / fps (track.py:169), counted from the slot's last reopen; slots past the last clip carry none
+      m.clip[i] = i < p->n_trk ? i : -1;
+      m.frame[i] = i < p->n_trk ? p->frame_count - p->fc_base[(size_t)i] : 0;
+    } else if (active[i]) {
+      m.clip[i] = i;
+      m.frame[i] = (int)++p->clip_frames[(size_t)i];
+    } else {
+      m.clip[i] = -1;
+    }
+  }
+}
+
+// The OC-SORT launch of the one step in ring slot o: on the tracker stream after the slot's detections ("own"), or at the end of the
+// slot's own stream after the previous tracker launch ("inline": stream order gives "after this slot's detections")
 int enqueue_tracker(vbt_pipeline* p, int o) {
   hipStream_t T;
   if (p->trk_inline) {
@@ -287,112 +161,112 @@ int enqueue_tracker(vbt_pipeline* p, int o) {
     T = p->trk_stream;
     VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o], 0));
   }
-  vbt_pipeline::SlotMeta& m = p->meta[o];
+  const vbt_pipeline::Step& m = p->meta[o];
   // frame times / clip map / runs of the step travel in the kernel arguments (read during the call, no copy in flight)
-  if (m.kind == vbt_pipeline::RUNS) {
+  if (!m.runs.empty()) {
     PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.B, m.runs.data(), (int)m.runs.size(),
                                                     p->prm.detection_threshold, (void*)T));
-  } else if (m.kind == vbt_pipeline::SLOTS) {
-    PL_CHECK(vbt_tracker_update_from_slots(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.cmap.data(), m.times.data(), p->n,
+    return record_trk(p, o, T);
+  }
+  // time = frame number / fps of the clip; fps cannot have changed since the step: a slot close drains before it sets a new one
+  for (int i = 0; i < p->n; i++) p->times[i] = m.clip[i] >= 0 ? (double)m.frame[i] / p->fps[m.clip[i]] : -1.0;
+  if (m.mapped) {
+    PL_CHECK(vbt_tracker_update_from_slots(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.clip.data(), p->times.data(), p->n,
                                            p->prm.detection_threshold, (void*)T));
-  } else {
-    PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.times.data(), p->prm.detection_threshold,
+  } else {   // (reads the first n_trk slots: slot i is clip i)
+    PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), p->times.data(), p->prm.detection_threshold,
                                                 (void*)T));
   }
   return record_trk(p, o, T);
 }
 
-int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S);
+int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S) {
+  const bool held = o >= p->blk.o0 && o < p->blk.o0 + p->blk.used;
+  if (held || std::find(p->pending.begin(), p->pending.end(), o) != p->pending.end()) {
+    set_error("vbt_pipeline: ring slot %d still holds a step whose tracker update has not been enqueued", o);
+    return VBT_ERR_STATE;
+  }
+  if (p->trk_ev_of[o] >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_trk[p->trk_ev_of[o]], 0));   // the tracker is done with this slot's previous outputs
+  return VBT_OK;
+}
 
-// Close the held-back step group: the rest of the forward at batch hold_used * n on the group's stream, then the OC-SORT walk of its
-// tracked steps in frame order.  A clip walks ONE run per tracker call (its frames at one slot stride and one frame step - every plain
-// group); steps that break the pattern (an `active` mask or clip map that changes inside the group, a detector-only step in the
-// middle) continue in a further call on the same stream.
-int flush_hold(vbt_pipeline* p) {
-  if (p->hold_used == 0) return VBT_OK;
-  const int k = p->hold_k, o0 = p->hold_o0, used = p->hold_used, n = p->n, o_last = o0 + used - 1;
-  p->hold_used = 0;
-  p->next_o = o0 + used + p->G > p->ring ? 0 : o0 + used;   // (a block never wraps)
-  hipStream_t S = p->det_streams[k];
-  for (int g = 0; g < used; g++) PL_CHECK(wait_slot_free(p, o0 + g, S));
-  vbt_model* m = p->models[(size_t)k];
-  PL_CHECK(vbt_detect_range_async(m, nullptr, 0, used * n, vbt_model_entry_steps(m), -1, (void*)S, boxes_of(p, o0), scores_of(p, o0), classes_of(p, o0),
-                                  counts_of(p, o0)));
-  for (int g = 0; g < used; g++) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o0 + g], S));
-  struct Fr { int slot, frame; };
-  std::vector<std::vector<Fr>> per((size_t)p->n_trk);
+// Hands the held-back block to the GPU.  A step group first gets the rest of its forward.  Then the walk of the block's tracked steps in
+// frame order: one launch of the time-batched walk (walk_runs.h; a further one only where a clip's frames break their pattern), on the
+// stream of the block's last forward when the tracker runs inline, else on the tracker stream, after the block's other forwards and the
+// previous tracker launch.  A single deferred step is an ordinary single-step launch.
+//
+// Who calls what.
+//  - flush_block: the step that fills the block, a step that cannot join it (step_frames), and whatever launches tracker work of its own,
+//    so that tracker launches stay in frame order: vbt_pipeline_step_runs (vbt_track_clip with it), vbt_pipeline_tracker_only_steps.
+//  - drain: what reads or replaces tracker state - reset, drain, finish, close, close_clips, rows, rows_all, live_poll.  It also needs the
+//    own-stream lag enqueued and, with the inline tracker, the tracker stream behind the last launch.
+//  - finish_forward: what only needs the detections or the frame counter of the steps so far - detections, join_detectors, closed_clip,
+//    skip_frames, set_frame_count, destroy.  A step group's forward is completed (its walk goes with it).  Deferred steps stay deferred:
+//    their detections are in the ring already, and skipped frames between them are a frame step the walk carries (step_frames flushes
+//    when the step changes inside a block).
+int flush_block(vbt_pipeline* p) {
+  const vbt_pipeline::Block b = p->blk;
+  if (b.used == 0) return VBT_OK;
+  p->blk.used = 0;
+  const int n = p->n, o0 = b.o0, used = b.used, o_last = o0 + used - 1;
+  const bool grouped = p->G > 1;
+  auto fwd_slot = [&](int g) { return grouped ? b.k : (o0 + g) % p->depth; };
+  if (grouped) {
+    hipStream_t S = p->det_streams[b.k];
+    for (int g = 0; g < used; g++) PL_CHECK(wait_slot_free(p, o0 + g, S));
+    vbt_model* m = p->models[(size_t)b.k];
+    PL_CHECK(vbt_detect_range_async(m, nullptr, 0, used * n, vbt_model_entry_steps(m), -1, (void*)S, boxes_of(p, o0), scores_of(p, o0), classes_of(p, o0),
+                                    counts_of(p, o0)));
+    for (int g = 0; g < used; g++) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o0 + g], S));
+  } else if (used == 1) {
+    return enqueue_tracker(p, o0);
+  }
   bool any = false;
+  for (auto& v : p->walk_per) v.clear();
   for (int g = 0; g < used; g++) {
-    const vbt_pipeline::SlotMeta& sm = p->meta[(size_t)(o0 + g)];
+    const vbt_pipeline::Step& sm = p->meta[(size_t)(o0 + g)];
     if (!sm.track) continue;
     for (int i = 0; i < n; i++)
-      if (sm.clip[i] >= 0) { per[(size_t)sm.clip[i]].push_back(Fr{g * n + i, sm.frame[i]}); any = true; }
+      if (sm.clip[i] >= 0) { p->walk_per[(size_t)sm.clip[i]].push_back(WalkFrame{g * n + i, sm.frame[i]}); any = true; }
   }
   if (!any) return VBT_OK;
-  hipStream_t T = p->trk_inline ? S : p->trk_stream;
-  if (!p->trk_inline) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o_last], 0));
-  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));   // tracker launches run in frame order
-  std::vector<size_t> cur((size_t)p->n_trk, 0);
-  std::vector<vbt_run> ra;
-  for (;;) {
-    ra.clear();
-    for (int c = 0; c < p->n_trk; c++) {
-      const std::vector<Fr>& v = per[(size_t)c];
-      const size_t a = cur[(size_t)c];
-      if (a >= v.size()) continue;
-      size_t b = a + 1;
-      int ss = 1, fs = 1;
-      if (b < v.size() && v[b].frame > v[a].frame) {
-        ss = v[b].slot - v[a].slot;
-        fs = v[b].frame - v[a].frame;
-        for (b++; b < v.size() && v[b].slot - v[b - 1].slot == ss && v[b].frame - v[b - 1].frame == fs;) b++;
-      }
-      ra.push_back(vbt_run{c, v[a].slot, ss, (int)(b - a), v[a].frame, fs, p->fps[(size_t)c]});
-      cur[(size_t)c] = b;
-    }
-    if (ra.empty()) break;
-    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o0), scores_of(p, o0), counts_of(p, o0), used * n, ra.data(), (int)ra.size(),
-                                                    p->prm.detection_threshold, (void*)T));
+  hipStream_t T = p->trk_inline ? p->det_streams[b.k] : p->trk_stream;
+  for (int g = 0; g < used; g++) {   // the last forward of every other stream in the block
+    bool last = p->det_streams[fwd_slot(g)] != T;
+    for (int h = g + 1; h < used && last; h++) last = fwd_slot(h) != fwd_slot(g);
+    if (last) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o0 + g], 0));
   }
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));   // tracker launches run in frame order
+  // (a slot close drains first: fps and the frame bases are those of the whole block)
+  std::fill(p->walk_cur.begin(), p->walk_cur.end(), (size_t)0);
+  while (next_walk_call(p->walk_per, p->fps.data(), p->walk_cur, p->walk_runs))
+    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o0), scores_of(p, o0), counts_of(p, o0), used * n, p->walk_runs.data(),
+                                                    (int)p->walk_runs.size(), p->prm.detection_threshold, (void*)T));
   VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o_last], T));
   for (int g = 0; g < used; g++) p->trk_ev_of[o0 + g] = o_last;
   p->last_trk = o_last;
   return VBT_OK;
 }
 
-// Hand the deferred plain steps to the tracker: ONE launch of the time-batched walk on the stream of the group's last forward,
-// after the other members' forwards (events) and the previous tracker launch.
-int flush_group(vbt_pipeline* p) {
-  PL_CHECK(flush_hold(p));   // (a pipeline holds back either a step group or deferred tracker steps, never both)
-  std::vector<int> g;
-  g.swap(p->group);
-  if (g.empty()) return VBT_OK;
-  for (int o : g) p->pending.erase(std::find(p->pending.begin(), p->pending.end(), o));
-  if (g.size() == 1) return enqueue_tracker(p, g[0]);
-  const int n = p->n, last = g.back();
-  hipStream_t T = p->det_streams[last % p->depth];
-  for (size_t i = 0; i + 1 < g.size(); i++) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[g[i]], 0));
-  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));
-  const int fstep = p->meta[g[1]].fc - p->meta[g[0]].fc;
-  std::vector<vbt_run> ra((size_t)n);
-  // (a slot close flushes the group first: the bases are those of the whole group)
-  for (int c = 0; c < n; c++) ra[c] = vbt_run{c, c, n, (int)g.size(), p->meta[g[0]].fc - p->fc_base[c], fstep, p->fps[c]};
-  // slot (o - g[0]) * n + c of the block that starts at ring slot g[0]
-  PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, g[0]), scores_of(p, g[0]), counts_of(p, g[0]), (int)g.size() * n, ra.data(), n,
-                                                  p->prm.detection_threshold, (void*)T));
-  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[last], T));
-  for (int o : g) p->trk_ev_of[o] = last;
-  p->last_trk = last;
-  return VBT_OK;
+int finish_forward(vbt_pipeline* p) {
+  if (p->G == 1 || p->blk.used == 0) return VBT_OK;
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  return flush_block(p);
 }
 
-int drain(vbt_pipeline* p) {
-  PL_CHECK(flush_group(p));
-  while (!p->pending.empty()) {
+// own stream: the tracker stays up to `keep` steps behind the detector
+int enqueue_lagging(vbt_pipeline* p, int keep) {
+  while ((int)p->pending.size() > keep) {
     const int o = p->pending.front();
     p->pending.erase(p->pending.begin());
     PL_CHECK(enqueue_tracker(p, o));
   }
+  return VBT_OK;
+}
+
+int drain(vbt_pipeline* p) {
+  PL_CHECK(flush_block(p));
+  PL_CHECK(enqueue_lagging(p, 0));
   if (p->trk_inline && p->last_trk >= 0)   // clip close / row reads run on the tracker stream
     VBT_HIP_CHECK(hipStreamWaitEvent(p->trk_stream, p->ev_trk[p->last_trk], 0));
   return VBT_OK;
@@ -538,10 +412,12 @@ int ensure_resized(vbt_pipeline* p, int k) {
 }
 
 struct Sources {
-  const uint8_t* frames = nullptr;              // assembled batch, or
-  const uint8_t* const* run_sources = nullptr;  // one source per run
-  bool on_device = false;
-  int src_h = 0, src_w = 0, swap_rb = 0;
+  const uint8_t* frames;              // assembled batch, or
+  const uint8_t* const* run_sources;  // one source per run
+  bool on_device;
+  int src_h, src_w, swap_rb;
+  Sources(const uint8_t* frames_, const uint8_t* const* run_sources_, int frames_on_device, int src_h_, int src_w_, int swap_rb_)
+      : frames(frames_), run_sources(run_sources_), on_device(frames_on_device != 0), src_h(src_h_), src_w(src_w_), swap_rb(swap_rb_) {}
 };
 
 // What a step may ask for under the pipeline's pixel format; checked before anything is enqueued or counted.
@@ -633,8 +509,28 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
   return VBT_OK;
 }
 
-int after_detect(vbt_pipeline* p, int o, int stage_j, hipStream_t S) {
-  VBT_HIP_CHECK(hipEventRecord(p->ev_det[o], S));
+// The front of every step in ring slot o / forward slot k: the slot's previous outputs are free (`wait`: the step writes the slot now
+// - a member of a step group writes it at the flush, flush_block waits there), the counters, B frames at the network resolution.
+int begin_step(vbt_pipeline* p, int o, int k, bool wait, bool counts_frame, const Sources& src, const vbt_run* asm_runs, int n_asm, int B,
+               void* caller_stream, const uint8_t** frames_dev, int* stage_j) {
+  hipStream_t S = p->det_streams[k];
+  if (wait) PL_CHECK(wait_slot_free(p, o, S));
+  if (p->G > 1) {   // the forward this step opens or joins; a block never wraps
+    if (p->blk.used == 0) p->fwd_idx++;
+    p->next_o = o + 1 + p->G > p->ring ? 0 : o + 1;
+  }
+  p->step_idx++;
+  if (counts_frame) p->frame_count++;
+  p->last_o = o;
+  p->last_k = k;
+  p->last_B = B;
+  return prepare_frames(p, k, S, src, asm_runs, n_asm, B, caller_stream, frames_dev, stage_j);
+}
+
+// Behind the last kernel that reads the step's frames on S: the detections of ring slot o are complete (o < 0: not yet, the entry of
+// a step group), the staging buffer is free again
+int end_detect(vbt_pipeline* p, int o, int stage_j, hipStream_t S) {
+  if (o >= 0) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o], S));
   if (stage_j >= 0) {
     VBT_HIP_CHECK(hipEventRecord(p->stage[stage_j].free_ev, S));
     p->stage[stage_j].free_set = true;
@@ -642,113 +538,77 @@ int after_detect(vbt_pipeline* p, int o, int stage_j, hipStream_t S) {
   return VBT_OK;
 }
 
-int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S) {
-  if (std::find(p->pending.begin(), p->pending.end(), o) != p->pending.end()) {
-    set_error("vbt_pipeline: ring slot %d still holds a step whose tracker update has not been enqueued", o);
-    return VBT_ERR_STATE;
-  }
-  if (p->trk_ev_of[o] >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_trk[p->trk_ev_of[o]], 0));   // the tracker is done with this slot's previous outputs
-  return VBT_OK;
+// The tracker launch of a step that is not held back: inline right behind its forward, own stream depth - 1 detector steps behind
+int launch_or_lag(vbt_pipeline* p, int o) {
+  p->pending.push_back(o);
+  return enqueue_lagging(p, p->trk_inline ? 0 : p->depth - 1);
 }
 
-// One time-batched step: `asm_runs` say where the sources sit in the batch (assembly), `walk_runs` what the tracker walks.
+// One time-batched step: `asm_runs` say where the sources sit in the batch (assembly), `walk_runs` what the tracker walks.  On a grouped
+// pipeline it is a forward of its own between the step groups.
 int step_runs_impl(vbt_pipeline* p, const Sources& src, const vbt_run* asm_runs, int n_asm, std::vector<vbt_run>& walk_runs, int B, int track,
                    float* out_boxes, float* out_scores, float* out_classes, int32_t* out_counts, void* caller_stream) {
-  PL_CHECK(flush_group(p));
-  int o = p->step_idx % p->ring, k = o % p->depth;
-  if (p->G > 1) {   // a forward of its own between the step groups
-    o = p->next_o;
-    k = p->fwd_idx++ % p->depth;
-    p->next_o = o + 1 + p->G > p->ring ? 0 : o + 1;
-  }
-  p->last_o = o;
-  p->last_k = k;
+  PL_CHECK(flush_block(p));
+  int o = 0, k = 0;
+  next_slots(p, &o, &k);
   hipStream_t S = p->det_streams[k];
-  PL_CHECK(wait_slot_free(p, o, S));
-  p->step_idx++;
   const uint8_t* fd = nullptr;
   int stage_j = -1;
-  PL_CHECK(prepare_frames(p, k, S, src, asm_runs, n_asm, B, caller_stream, &fd, &stage_j));
+  PL_CHECK(begin_step(p, o, k, true, false, src, asm_runs, n_asm, B, caller_stream, &fd, &stage_j));
   const bool outs = out_boxes != nullptr;
   float* b = outs ? out_boxes : boxes_of(p, o);
   float* s = outs ? out_scores : scores_of(p, o);
   float* c = outs ? out_classes : classes_of(p, o);
   int32_t* cnt = outs ? out_counts : counts_of(p, o);
   PL_CHECK(vbt_detect_async(p->models[k], fd, B, (void*)S, b, s, c, cnt));
-  PL_CHECK(after_detect(p, o, stage_j, S));
-  vbt_pipeline::SlotMeta& m = p->meta[o];
-  m.kind = vbt_pipeline::RUNS;
+  PL_CHECK(end_detect(p, o, stage_j, S));
+  vbt_pipeline::Step& m = p->meta[o];
   m.runs.swap(walk_runs);
   m.B = B;
-  p->last_B = B;
-  if (!track) return VBT_OK;
-  p->pending.push_back(o);
-  while ((int)p->pending.size() >= (p->trk_inline ? 1 : p->depth)) {
-    const int q = p->pending.front();
-    p->pending.erase(p->pending.begin());
-    PL_CHECK(enqueue_tracker(p, q));
-  }
-  return VBT_OK;
+  m.track = track;
+  return track ? launch_or_lag(p, o) : VBT_OK;
 }
 
-// vbt_pipeline_step of a grouped pipeline (arguments checked by the caller).  Everything that touches the caller's frames happens here, in
-// the call, stream-ordered as in an ungrouped step: the wait for the caller's stream, upload, resize / conversion and the network entry;
-// what is held back reads the model's own tensors only.  There is no ramp: groups of one for the first `depth` forwards measured
-// slower over a 20-step run than full groups from the first step (profiles/r07_step_groups_ab.md).
-int step_grouped(vbt_pipeline* p, const uint8_t* frames, int frames_on_device, int src_h, int src_w, int swap_rb, const uint8_t* active,
-                 const int32_t* clip_map, const int32_t* frame_idx, int track, void* caller_stream) {
+// vbt_pipeline_step (arguments checked by the caller).  Everything that touches the caller's frames happens in the call, stream-ordered: the
+// wait for the caller's stream, upload, resize / conversion and - step group - the network entry, else the whole forward; what a step
+// group holds back reads the model's own tensors only.  There is no ramp: groups of one for the first `depth` forwards measured slower
+// over a 20-step run than full groups from the first step (profiles/r07_step_groups_ab.md).
+int step_frames(vbt_pipeline* p, const Sources& src, const uint8_t* active, const int32_t* clip_map, const int32_t* frame_idx, int track,
+                void* caller_stream) {
   const int n = p->n;
-  if (clip_map)
+  const bool grouped = p->G > 1, plain = !clip_map && !active && track;
+  if (grouped && clip_map)   // (the walk of a block takes a clip once per step)
     for (int i = 0; i < n; i++)
       for (int j = 0; j < i; j++)
         if (clip_map[i] >= 0 && clip_map[i] == clip_map[j]) { set_error("vbt_pipeline_step: clip %d sits in two slots", clip_map[i]); return VBT_ERR_ARG; }
-  if (p->hold_used == 0) {
-    p->hold_k = p->fwd_idx % p->depth;
-    p->hold_o0 = p->next_o;
-    p->fwd_idx++;
+  int o = 0, k = 0;
+  next_slots(p, &o, &k);
+  if (!grouped && p->blk.used > 0) {
+    // deferred steps go out before a step that cannot join them: another kind of step, a ring wrap, or skip_frames() changed the frame stride
+    const int o0 = p->blk.o0, last = o0 + p->blk.used - 1;
+    if (!plain || o <= last || (p->blk.used >= 2 && p->frame_count + 1 - p->meta[last].fc != p->meta[o0 + 1].fc - p->meta[o0].fc)) PL_CHECK(flush_block(p));
   }
-  const int g = p->hold_used, o = p->hold_o0 + g, k = p->hold_k;
   hipStream_t S = p->det_streams[k];
-  p->step_idx++;
-  p->frame_count++;
-  Sources src;
-  src.frames = frames;
-  src.on_device = frames_on_device != 0;
-  src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
   const uint8_t* fd = nullptr;
   int stage_j = -1;
-  PL_CHECK(prepare_frames(p, k, S, src, nullptr, 0, n, caller_stream, &fd, &stage_j));
-  vbt_pipeline::SlotMeta& m = p->meta[(size_t)o];
-  m.kind = clip_map ? vbt_pipeline::SLOTS : vbt_pipeline::PLAIN;
-  m.fc = p->frame_count;
-  m.B = n;
-  m.track = track;
-  for (int i = 0; i < n; i++) {
-    if (clip_map) {
-      m.clip[i] = clip_map[i];
-      m.frame[i] = frame_idx[i];
-    } else if (!active) {   // frame_count / fps (track.py:169), counted from the slot's last reopen
-      m.clip[i] = i;
-      m.frame[i] = p->frame_count - p->fc_base[(size_t)i];
-    } else if (active[i]) {
-      m.clip[i] = i;
-      m.frame[i] = (int)++p->clip_frames[(size_t)i];
-    } else {
-      m.clip[i] = -1;
-    }
-  }
+  PL_CHECK(begin_step(p, o, k, !grouped, true, src, nullptr, 0, n, caller_stream, &fd, &stage_j));
+  fill_step(p, p->meta[(size_t)o], active, clip_map, frame_idx, track);
   vbt_model* mdl = p->models[(size_t)k];
-  PL_CHECK(vbt_detect_range_async(mdl, fd, g * n, n, 0, vbt_model_entry_steps(mdl), (void*)S, nullptr, nullptr, nullptr, nullptr));
-  if (stage_j >= 0) {   // the entry was the staging buffer's only reader
-    VBT_HIP_CHECK(hipEventRecord(p->stage[(size_t)stage_j].free_ev, S));
-    p->stage[(size_t)stage_j].free_set = true;
+  if (grouped) {   // the entry on slice `used` of the forward; it was the staging buffer's only reader
+    PL_CHECK(vbt_detect_range_async(mdl, fd, p->blk.used * n, n, 0, vbt_model_entry_steps(mdl), (void*)S, nullptr, nullptr, nullptr, nullptr));
+    PL_CHECK(end_detect(p, -1, stage_j, S));
+  } else {
+    PL_CHECK(vbt_detect_async(mdl, fd, n, (void*)S, boxes_of(p, o), scores_of(p, o), classes_of(p, o), counts_of(p, o)));
+    PL_CHECK(end_detect(p, o, stage_j, S));
   }
-  p->hold_used++;
-  p->last_o = o;
-  p->last_k = k;
-  p->last_B = n;
-  if (p->hold_used >= p->G) PL_CHECK(flush_hold(p));
-  return VBT_OK;
+  if (grouped || (p->defer && plain)) {   // held back; deferred blocks are aligned to `defer` ring slots, so neither kind wraps
+    if (p->blk.used == 0) p->blk.o0 = o;
+    p->blk.k = k;
+    p->blk.used++;
+    if (grouped ? p->blk.used >= p->G : (p->blk.used >= p->defer || o % p->defer == p->defer - 1)) PL_CHECK(flush_block(p));
+    return VBT_OK;
+  }
+  return track ? launch_or_lag(p, o) : VBT_OK;   // (track == 0: detector-only step, measurement splits)
 }
 
 }  // namespace
@@ -778,7 +638,7 @@ void vbt_pipeline_default_params(vbt_pipeline_params* p) {
 void vbt_pipeline_destroy(vbt_pipeline* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  if (p->hold_used > 0) (void)flush_hold(p);   // (the models' tensors are released below: nothing half-run stays behind)
+  (void)finish_forward(p);   // (the models' tensors are released below: nothing half-run stays behind)
   for (int k = 0; k < p->depth; k++)
     if (p->det_streams[k]) (void)hipStreamSynchronize(p->det_streams[k]);
   if (p->copy_stream) (void)hipStreamSynchronize(p->copy_stream);
@@ -890,10 +750,10 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   }
   (void)hipMemset(p->counts, 0, R * n * 4);
   p->meta.resize(R);
-  for (auto& m : p->meta) {
-    m.times.assign(n, 0.0);
-    if (p->G > 1) { m.clip.assign(n, -1); m.frame.assign(n, 0); }
-  }
+  for (auto& m : p->meta) { m.clip.assign(n, -1); m.frame.assign(n, 0); }
+  p->times.assign(n, 0.0);
+  p->walk_per.resize((size_t)p->n_trk);
+  p->walk_cur.resize((size_t)p->n_trk);
   p->trk_ev_of.assign(R, -1);
   auto new_events = [&](std::vector<hipEvent_t>& v, size_t cnt) {
     for (size_t i = 0; i < cnt; i++) {
@@ -918,10 +778,17 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
     std::lock_guard<std::mutex> lock(g_pool_mu);
     StreamPool& pool = g_pools[p->device];
     int role_idx[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-    for (int k = 0; k < p->depth && rc == VBT_OK; k++) rc = pool_take(p, pool, -1, false, &role_idx[k]);
-    if (rc == VBT_OK) rc = pool_take(p, pool, -1, false, &role_idx[8]);
-    if (rc == VBT_OK) rc = pool_take(p, pool, -1, false, &role_idx[9]);
-    if (rc == VBT_OK) rc = place_streams(p, pool, role_idx);
+    for (int k = 0; k < p->depth && rc == VBT_OK; k++) rc = pool_take(pool, p->device, p->own_streams, -1, false, &role_idx[k]);
+    if (rc == VBT_OK) rc = pool_take(pool, p->device, p->own_streams, -1, false, &role_idx[8]);
+    if (rc == VBT_OK) rc = pool_take(pool, p->device, p->own_streams, -1, false, &role_idx[9]);
+    // busy: the streams that carry kernels side by side - the detector slots, the copy stream (four hardware queues: with four forwards in
+    // flight it has to share one, which costs a small batch nothing), the tracker stream unless its step runs inline
+    std::vector<int> busy;
+    for (int k = 0; k < p->depth; k++) busy.push_back(k);
+    if (p->depth < 4) busy.push_back(8);
+    if (!p->trk_inline) busy.push_back(9);
+    const bool strict = (prm->strict_placement >= 0 ? prm->strict_placement : env_int("VBT_STRICT_PLACEMENT", 0)) == 1;
+    if (rc == VBT_OK) rc = place_streams(pool, p->device, busy, strict, role_idx, p->own_streams, &p->placement_ok);
     if (rc == VBT_OK) {
       for (int k = 0; k < p->depth; k++) p->det_streams[k] = pool.streams[role_idx[k]];
       p->copy_stream = pool.streams[role_idx[8]];
@@ -968,69 +835,7 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
   if (!clip_map && track && p->n_trk > p->n) { set_error("vbt_pipeline_step: %d clips on %d slots needs clip_map / frame_idx (or vbt_pipeline_step_runs)", p->n_trk, p->n); return VBT_ERR_ARG; }
   StepTimer timer(p);
   VBT_HIP_CHECK(hipSetDevice(p->device));
-  if (p->G > 1) return step_grouped(p, frames, frames_on_device, src_h, src_w, swap_rb, active, clip_map, frame_idx, track, caller_stream);
-  const int o = p->step_idx % p->ring, k = o % p->depth;   // output slot; forward slot (model instance, stream)
-  p->last_o = o;
-  p->last_k = k;
-  const bool plain = !clip_map && !active && track;
-  if (!p->group.empty()) {
-    const std::vector<int>& g = p->group;
-    // ring wrap, another kind of step, or skip_frames() changed the frame stride
-    if (!plain || o <= g.back() ||
-        (g.size() >= 2 && p->frame_count + 1 - p->meta[g.back()].fc != p->meta[g[1]].fc - p->meta[g[0]].fc))
-      PL_CHECK(flush_group(p));
-  }
-  hipStream_t S = p->det_streams[k];
-  PL_CHECK(wait_slot_free(p, o, S));
-  p->step_idx++;
-  p->frame_count++;
-  Sources src;
-  src.frames = frames;
-  src.on_device = frames_on_device != 0;
-  src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
-  const uint8_t* fd = nullptr;
-  int stage_j = -1;
-  PL_CHECK(prepare_frames(p, k, S, src, nullptr, 0, p->n, caller_stream, &fd, &stage_j));
-  vbt_pipeline::SlotMeta& m = p->meta[o];
-  m.kind = vbt_pipeline::PLAIN;
-  m.fc = p->frame_count;
-  m.B = p->n;
-  if (clip_map) {
-    m.kind = vbt_pipeline::SLOTS;
-    m.cmap.assign(clip_map, clip_map + p->n);
-    for (int i = 0; i < p->n; i++) m.times[i] = clip_map[i] >= 0 ? (double)frame_idx[i] / p->fps[clip_map[i]] : -1.0;
-  } else if (!active) {
-    for (int i = 0; i < p->n; i++) {   // time = frame_count / fps (track.py:169), counted from the slot's last reopen
-      const int c = std::min(i, p->n_trk - 1);
-      m.times[i] = (double)(p->frame_count - p->fc_base[c]) / p->fps[c];
-    }
-  } else {
-    for (int i = 0; i < p->n; i++) {
-      if (active[i]) {
-        p->clip_frames[i]++;
-        m.times[i] = (double)p->clip_frames[i] / p->fps[i];
-      } else {
-        m.times[i] = -1.0;
-      }
-    }
-  }
-  PL_CHECK(vbt_detect_async(p->models[k], fd, p->n, (void*)S, boxes_of(p, o), scores_of(p, o), classes_of(p, o), counts_of(p, o)));
-  PL_CHECK(after_detect(p, o, stage_j, S));
-  p->last_B = p->n;
-  if (!track) return VBT_OK;   // detector-only step (measurement splits)
-  p->pending.push_back(o);
-  if (p->defer && plain) {
-    p->group.push_back(o);
-    if ((int)p->group.size() >= p->defer || o % p->defer == p->defer - 1) PL_CHECK(flush_group(p));   // groups are aligned: their slots never wrap
-    return VBT_OK;
-  }
-  // own stream: keep depth-1 detector steps ahead of the tracker; inline: the step follows its forward directly
-  while ((int)p->pending.size() >= (p->trk_inline ? 1 : p->depth)) {
-    const int q = p->pending.front();
-    p->pending.erase(p->pending.begin());
-    PL_CHECK(enqueue_tracker(p, q));
-  }
-  return VBT_OK;
+  return step_frames(p, Sources(frames, nullptr, frames_on_device, src_h, src_w, swap_rb), active, clip_map, frame_idx, track, caller_stream);
 }
 
 int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t* const* run_sources, int frames_on_device, const vbt_run* runs,
@@ -1069,11 +874,7 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
     for (char u : used)
       if (!u) { set_error("vbt_pipeline_step_runs: the runs leave a hole in the detector batch"); return VBT_ERR_ARG; }
   }
-  Sources src;
-  src.frames = frames;
-  src.run_sources = run_sources;
-  src.on_device = frames_on_device != 0;
-  src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
+  const Sources src(frames, run_sources, frames_on_device, src_h, src_w, swap_rb);
   std::vector<vbt_run> asm_runs(ra);
   return step_runs_impl(p, src, asm_runs.data(), n_runs, ra, B, track, out_boxes, out_scores, out_classes, out_counts, caller_stream);
 }
@@ -1087,14 +888,14 @@ int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt) {
 
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n) {
   if (!p || n < 0) { set_error("vbt_pipeline_skip_frames: bad argument"); return VBT_ERR_ARG; }
-  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
+  PL_CHECK(finish_forward(p));
   p->frame_count += n;
   return VBT_OK;
 }
 
 int vbt_pipeline_set_frame_count(vbt_pipeline* p, int frame_count) {
   if (!p || frame_count < 0) { set_error("vbt_pipeline_set_frame_count: bad argument"); return VBT_ERR_ARG; }
-  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
+  PL_CHECK(finish_forward(p));
   p->frame_count = frame_count;
   return VBT_OK;
 }
@@ -1119,7 +920,7 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
 
 int vbt_pipeline_join_detectors(vbt_pipeline* p, void* stream) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
-  if (p->hold_used > 0) { VBT_HIP_CHECK(hipSetDevice(p->device)); PL_CHECK(flush_hold(p)); }
+  PL_CHECK(finish_forward(p));
   for (hipEvent_t e : p->ev_det) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, e, 0));
   return VBT_OK;
 }
@@ -1173,7 +974,7 @@ int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
     std::lock_guard<std::mutex> lock(g_pool_mu);
     StreamPool& pool = g_pools[p->device];
     int i = -1;
-    const int rc = pool_take(p, pool, -1, false, &i);
+    const int rc = pool_take(pool, p->device, p->own_streams, -1, false, &i);
     if (rc != VBT_OK) { undo("taking the read stream", hipSuccess); return rc; }
     p->read_stream = pool.streams[(size_t)i];
   }
@@ -1187,7 +988,7 @@ int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
 
 // Slot close.  Enqueue only: drain() hands the held-back tracker steps to their streams, the close kernels and the reset follow on the
 // tracker stream (in inline mode drain() made it wait for the last tracker launch), and the reset is recorded as the most recent tracker
-// launch - every later tracker launch waits for it, whichever stream it runs on (enqueue_tracker, flush_group, tracker-only steps run
+// launch - every later tracker launch waits for it, whichever stream it runs on (enqueue_tracker, flush_block, tracker-only steps run
 // on the tracker stream itself).  The record goes straight into pinned memory (close_pack_kernel), so no copy is enqueued here.
 int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const double* next_fps) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
@@ -1232,7 +1033,7 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
   *ready = 0;
   if (p->closed_unread.empty() || !p->closed_unread[(size_t)clip]) { set_error("vbt_pipeline_closed_clip: slot %d has no unread result", clip); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(flush_hold(p));
+  PL_CHECK(finish_forward(p));
   hipEvent_t ev = p->ev_closed[(size_t)clip];
   if (wait) {
     VBT_HIP_CHECK(hipEventSynchronize(ev));
@@ -1291,7 +1092,7 @@ int vbt_pipeline_detections(vbt_pipeline* p, float* boxes, float* scores, float*
   const int o = p->last_o, nb = p->last_B;
   if (nb > cap_slots) { set_error("vbt_pipeline_detections: %d slots, buffers hold %d", nb, cap_slots); return VBT_ERR_CAPACITY; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(flush_hold(p));   // (the last step's detections are slice `hold_used - 1` of its group's block)
+  PL_CHECK(finish_forward(p));   // (the last step's detections are the last slice of its group's forward)
   hipStream_t S = p->det_streams[p->last_k];
   const size_t md = VBT_MAX_DETECTIONS;
   VBT_HIP_CHECK(hipMemcpyAsync(boxes, boxes_of(p, o), nb * md * 16, hipMemcpyDeviceToHost, S));
@@ -1307,7 +1108,7 @@ int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
   if (!p || count < 1 || slot < 0 || slot >= p->ring) { set_error("vbt_pipeline_tracker_only_steps: bad argument"); return VBT_ERR_ARG; }
   if (p->n_trk != p->n) { set_error("vbt_pipeline_tracker_only_steps needs one tracker clip per detector slot"); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(flush_group(p));   // (deferred steps / a held-back step group first: tracker launches stay in frame order)
+  PL_CHECK(flush_block(p));   // (tracker launches stay in frame order)
   hipStream_t T = p->trk_stream;
   VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[slot], 0));
   if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));
@@ -1346,7 +1147,8 @@ int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
   out->ring = p->ring; out->defer = p->defer; out->tracker_inline = p->trk_inline ? 1 : 0; out->image_size = p->size;
   out->frame_count = p->frame_count; out->steps_enqueued = p->step_idx; out->placement_ok = p->placement_ok ? 1 : 0;
   out->group = p->G;
-  out->next_slot = p->G == 1 ? (p->step_idx % p->ring) % p->depth : p->hold_used > 0 ? p->hold_k : p->fwd_idx % p->depth;
+  int next_o = 0;
+  next_slots(p, &next_o, &out->next_slot);
   {
     std::lock_guard<std::mutex> lock(g_pool_mu);
     out->queue_groups_seen = (int)g_pools[p->device].reps.size();
@@ -1391,10 +1193,7 @@ int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device,
       }
       // (the tracker sees ONE run for the clip: assembled from the per-frame sources, walked as the single run)
       VBT_HIP_CHECK(hipSetDevice(p->device));
-      Sources src;
-      src.run_sources = srcs.data();
-      src.on_device = frames_on_device != 0;
-      src.src_h = src_h; src.src_w = src_w; src.swap_rb = swap_rb;
+      const Sources src(nullptr, srcs.data(), frames_on_device, src_h, src_w, swap_rb);
       std::vector<vbt_run> walk(1, run);
       PL_CHECK(step_runs_impl(p, src, rr.data(), nf, walk, nf, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
     }
