@@ -575,6 +575,60 @@ int vbt_overlay_set_rows(vbt_overlay* o, const void* rows_host, int n, double fp
  * are not touched. */
 int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
 
+/* ------------------------------------------------------------------ MJPEG export --------
+ * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that
+ * sits in device memory is encoded there as one baseline JPEG and only the compressed bytes come back; the host wraps them in an AVI
+ * (vbt_amd/mjpeg.py).  The bitstream is pinned to the integer, so an implementation in numpy (tests/mjpeg_ref.py) gives the same bytes.
+ *
+ * Frame = one complete JFIF file: SOI; APP0 "JFIF\0" 1.01, density unit 0, 1:1, no thumbnail; DQT table 0 (luma), DQT table 1
+ * (chroma), each 8-bit, in zigzag order; SOF0 8-bit, H, W, 3 components: Y id 1 2x2 table 0, Cb id 2 1x1 table 1, Cr id 3 1x1 table 1
+ * (4:2:0); DHT DC 0, AC 0, DC 1, AC 1; DRI; SOS (Y: DC 0 / AC 0, Cb and Cr: DC 1 / AC 1, Ss 0, Se 63, Ah/Al 0); the scan; EOI.
+ * 629 bytes precede the scan.
+ *
+ * Size.  VBT_PIX_RGB24: any H, W in 1..16384; the YUV formats: even H and W.  An MCU is 16 x 16 pixels; partial MCUs are filled by
+ * replicating the last column and row.  The code clamps the coordinates it loads from: for RGB24 that replicates the pixel before
+ * the 2 x 2 chroma sum, for YUV it replicates the last sample of each plane - the same thing as replicating the converted samples.
+ *
+ * Colour (JFIF full range; >> arithmetic; results clipped to 0..255).
+ *   RGB24: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16 per pixel; per 2 x 2 cell, from the channel sums S (0..1020):
+ *     Cb = ((-11059 S_R - 21709 S_G + 32768 S_B + 2^17) >> 18) + 128;  Cr = ((32768 S_R - 27439 S_G - 5329 S_B + 2^17) >> 18) + 128.
+ *   NV12 / I420 are BT.601 limited range (see VBT_PIX_NV12): luma becomes (Y - 16) 255 / 219, chroma (C - 128) 255 / 224 + 128, each
+ *     the exact rational rounded to nearest, ties away from zero (the one tie: C = 128 +- 112).  Chroma samples are used at their own
+ *     resolution; nothing is resampled.
+ * Forward DCT of x = sample - 128, int32 throughout: T[k][n] = rint(2^13 s_k cos((2n+1) k pi / 16)) in double, s_0 = sqrt(1/8),
+ *   s_k = 1/2;  rows A[y][u] = (sum_n x[y][n] T[u][n] + 2^10) >> 11;  columns F[v][u] = (sum_y A[y][u] T[v][y] + 2^14) >> 15.
+ * Quantisation: base tables Annex K.1 / K.2; quality q in 1..100 by the IJG rule s = 5000 / q (integer) for q < 50, else 200 - 2 q,
+ *   Q = clip((base s + 50) / 100, 1, 255);  level = sign(F) ((|F| + (Q >> 1)) / Q);  AC clamped to +-1023, DC to -1024..1023.
+ * Entropy coding: the Annex K.3 tables, zigzag order, ZRL and EOB as in the standard.  The restart interval is one MCU row (DRI =
+ *   ceil(W / 16)): DC predictors reset, the interval is padded with 1-bits to a byte, 0xFF bytes are followed by 0x00, and RSTm (m =
+ *   interval index mod 8) follows every interval but the last.  Every MCU row is an independent byte-aligned unit: one workgroup each.
+ *
+ * Capacity.  Nothing is ever truncated: the scratch is sized for the proven worst case.  A block is at most 22 + 63 x 26 = 1660 bits
+ * (longest DC code + 11 bits; longest AC code + 10 bits per coefficient; ZRL and EOB only replace coefficients by something shorter)
+ * and stuffing at most doubles a byte, so an interval of n MCUs holds at most 2 ceil(6 n 1660 / 8) bytes.  With MW = ceil(W / 16) and
+ * MH = ceil(H / 16) a handle allocates, per frame of max_batch,
+ *     MW MH (768 + 2496) + 629 + MH (2496 MW + 2) bytes, about 5.8 KB per MCU
+ * (int16 levels, the intervals' stuffed bytes at a worst-case stride, and the contiguous output): 47 MB per frame of 1920 x 1080, 6 GB
+ * per frame of 16384 x 16384.  vbt_mjpeg_create fails with VBT_ERR_HIP, naming the size, when the device cannot give max_batch times
+ * that; a caller of very large frames chooses max_batch accordingly.  Every store in the kernels is still checked against its buffer;
+ * a miss sets an overflow word that lives behind the offset table at a fixed place, is cleared on the stream by every
+ * vbt_mjpeg_encode and, if ever set, makes vbt_mjpeg_read return VBT_ERR_CAPACITY and drop that batch.  No torch, no library: HIP
+ * kernels for gfx950 (vbt_amd/csrc/mjpeg.hip). */
+typedef struct vbt_mjpeg vbt_mjpeg;
+/* VBT_ERR_ARG, before any device call: out NULL, an unknown pix_fmt, H or W outside 1..16384, odd H or W with a YUV format, quality
+ * outside 1..100, max_batch outside 1..1024. */
+int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out);
+void vbt_mjpeg_destroy(vbt_mjpeg* m);
+/* Encode B frames, contiguous in device memory (the layout vbt_overlay_draw takes).  Enqueue only, on `stream`: behind a
+ * vbt_overlay_draw on the same stream it needs no synchronisation in between.  The frames are read, not written.  VBT_ERR_CAPACITY:
+ * B > max_batch; VBT_ERR_STATE: the previous batch has not been read; B = 0 is VBT_ERR_ARG.  Nothing is enqueued on an error. */
+int vbt_mjpeg_encode(vbt_mjpeg* m, const uint8_t* frames_dev, int B, void* stream);
+/* The batch's bytes: frame i is host_buf[offsets[i] .. offsets[i + 1]).  One synchronisation of `stream` (the one given to
+ * vbt_mjpeg_encode), then two copies: the offset table (max_batch + 2 words, the overflow word last), then offsets[B] bytes.
+ * VBT_ERR_CAPACITY when cap < offsets[B]: offsets is filled, nothing else is copied and the batch stays readable.  VBT_ERR_STATE:
+ * no batch is pending.  A successful read releases the handle for the next vbt_mjpeg_encode. */
+int vbt_mjpeg_read(vbt_mjpeg* m, uint8_t* host_buf, uint64_t cap, uint64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

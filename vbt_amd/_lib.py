@@ -183,6 +183,10 @@ _SIGS = {
     "vbt_overlay_set_rows": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p]),
     "vbt_overlay_draw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vbt_overlay_geometry": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_mjpeg_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_mjpeg_destroy": (None, [c_void_p]),
+    "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "vbt_mjpeg_read": (c_int, [c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
 }
 
 

@@ -1,7 +1,7 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
-                            [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH]
+                            [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
       dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
@@ -16,8 +16,13 @@
       --video_dir DIR (reference track.py:71,96-98,241-242): every processed frame with the tracked boxes, ids and bar paths drawn on
       the GPU (include/vbt_hip.h, "tracking overlay"), as DIR/{video}.npy for .npy sources and as DIR/{video}.rgb / .yuv - headerless,
       in the source's pixel format, what `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i` reads - for --size sources.  Unlike the reference,
-      frames on which nothing was detected are written too (undrawn): the video does not jump in time.  No container is encoded.
+      frames on which nothing was detected are written too (undrawn): the video does not jump in time.
+      --video_format mjpeg: DIR/{video}.avi instead, for every source kind and pixel format - the drawn frames encoded as baseline JPEG
+      on the GPU (include/vbt_hip.h, "MJPEG export") at --video_quality, in an AVI that players open; only the compressed bytes are
+      copied back.  Its frame rate is fps / frame_stride, so the export plays in real time - a second deliberate difference: the
+      reference writes every 16th frame at the source's full fps (track.py:153-154,166), which plays 16 times too fast.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
+                              [--video_format raw|mjpeg] [--video_quality 85]
       the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn).
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
@@ -33,6 +38,7 @@
       closest curve point; --curve_dir writes the curve points as CSV.
 Option names (including the reference's `treshold` / `qualysis` spellings) and defaults follow the reference.
 """
+import contextlib
 import os
 import re
 
@@ -123,7 +129,10 @@ def _raw_size(pix_fmt, size):
 @click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of headerless raw video sources, e.g. 1920x1080; without it SRC is a .npy stack.")
 @click.option("--video_dir", default=None, show_default=True,
               help="Directory for exporting the frames with tracked objects and bar path ({video}.npy, or raw {video}.rgb / .yuv with --size).")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir):
+@click.option("--video_format", default="raw", show_default=True, type=click.Choice(["raw", "mjpeg"]),
+              help="raw: the drawn frames as they are; mjpeg: {video}.avi, JPEG-encoded on the GPU, playing at fps / frame_stride.")
+@click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     if concurrent < 1:
@@ -131,12 +140,15 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
-        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir)
+        return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
+                                 video_format, video_quality)
     for s in src:
         frames = _open_source(s, pix_fmt, size)
-        video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
-        data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                            live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video)
+        mjpeg = video_dir is not None and video_format == "mjpeg"
+        video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
+        with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
+            data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
+                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink, video_quality=video_quality)
         _video_done(video)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")
@@ -166,12 +178,37 @@ def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size):
     return np.memmap(path, dtype=np.uint8, mode="w+", shape=shape)
 
 
+def _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt):
+    """The mjpeg.AviWriter of --video_format mjpeg for source `s`: DIR/{video}.avi at fps / frame_stride"""
+    from .mjpeg import AviWriter, frame_rate
+    from .rawvideo import source_hw
+    os.makedirs(video_dir, exist_ok=True)
+    H, W = source_hw(frames, pix_fmt)
+    rate, scale = frame_rate(fps, frame_stride)
+    return AviWriter(os.path.join(video_dir, os.path.basename(s).split(".")[0] + ".avi"), W, H, rate, scale)
+
+
 def _video_done(video):
     if video is not None:
         video.flush()
 
 
-def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None):
+def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, batch, pix_fmt, size):
+    """The export of a finished clip from its rows: DIR/{video}.avi (mjpeg) or the raw map of _video_out.  Returns the frames written."""
+    from .overlay import render
+    if video_format == "mjpeg":
+        with _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) as sink:   # closed, hence a valid file, on an error too
+            return render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, sink=sink, quality=video_quality)
+    video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
+    if video is None:
+        return 0
+    render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, out=video)
+    _video_done(video)
+    return len(video)
+
+
+def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
+                      video_format="raw", video_quality=85):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -187,11 +224,8 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
                               time_batch=time_batch, pix_fmt=pix_fmt):
         s = src[i]
-        video = _video_out(video_dir, s, sources[i], frame_stride, pix_fmt, size)
-        if video is not None:                                            # the clip is finished: its rows are all the renderer needs
-            from .overlay import render
-            render(sources[i], data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video)
-            _video_done(video)
+        if video_dir is not None:                                        # the clip is finished: its rows are all the renderer needs
+            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps, frame_stride, time_batch, pix_fmt, size)
         if not data["id"]:
             lines[i] = f"{s}: no tracked rows"
         else:
@@ -213,10 +247,12 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
               help="Pixel format of the source; nv12 / i420 need --size.")
 @click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of a headerless raw video source; without it SRC is a .npy stack.")
 @click.option("--video_dir", default=".", show_default=True, help="Directory for the drawn frames ({video}.npy, or raw {video}.rgb / .yuv with --size).")
-def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir):
+@click.option("--video_format", default="raw", show_default=True, type=click.Choice(["raw", "mjpeg"]),
+              help="raw: the drawn frames as they are; mjpeg: {video}.avi, JPEG-encoded on the GPU, playing at fps / frame_stride.")
+@click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
+def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality):
     """Draw the boxes, ids and bar paths of a stored DataFrame into the frames of its clip (what `track --video_dir` writes)."""
     import pandas as pd
-    from .overlay import render
     size = _raw_size(pix_fmt, size)
     if frame_stride < 1:
         raise click.UsageError("--frame_stride must be at least 1")
@@ -224,11 +260,8 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir):
         raise FileNotFoundError(dataframe)
     frames = _open_source(src, pix_fmt, size)
     df = pd.read_pickle(dataframe)
-    video = _video_out(video_dir, src, frames, frame_stride, pix_fmt, size)
-    if video is not None:
-        render(frames, df, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, out=video)
-        _video_done(video)
-    click.echo(f"{src}: {0 if video is None else len(video)} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")
+    n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size)
+    click.echo(f"{src}: {n} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")
 
 
 @main.command()

@@ -71,18 +71,23 @@ class Overlay:
         return out[:n.value]
 
 
-def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, **params):
+def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, **params):
     """The kept frames of a clip (1-based number a multiple of frame_stride, reference track.py:166) with the overlay of `data`:
     frames uint8 [T,H,W,3] (or [T,H*3//2,W] for "nv12" / "i420"; numpy array or memmap), `batch` frames at a time through the device.
     Returns (or fills `out`, e.g. a numpy.lib.format.open_memmap) uint8 [T // frame_stride, ...] of the same layout.  Unlike the
-    reference (track.py:180-181,241-242) every kept frame is there: one without rows comes back undrawn."""
+    reference (track.py:180-181,241-242) every kept frame is there: one without rows comes back undrawn.
+    sink: an mjpeg.AviWriter - each batch is then uploaded, drawn, encoded as JPEG on the device at `quality` (mjpeg.Encoder, on the
+    stream of the draw, nothing synchronised in between) and only its compressed bytes are read back and written to the sink; `out`
+    is not used and the number of frames written is returned."""
     stride = max(int(frame_stride), 1)
     H, W = source_hw(frames, pix_fmt)
     shape = frame_shape(pix_fmt, H, W)
     if tuple(frames.shape[1:]) != shape or frames.dtype != np.uint8:
         raise ValueError(f"render: {pix_fmt} frames must be uint8 [T, {', '.join(str(v) for v in shape)}], got {frames.dtype} {tuple(frames.shape)}")
     kept = int(frames.shape[0]) // stride
-    if out is None:
+    if sink is not None:
+        out = None
+    elif out is None:
         out = np.empty((kept,) + shape, np.uint8)
     elif tuple(out.shape) != (kept,) + shape or out.dtype != np.uint8:
         raise ValueError(f"render: out must be uint8 {(kept,) + shape}, got {out.dtype} {tuple(out.shape)}")
@@ -93,13 +98,22 @@ def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=Non
     fb = int(np.prod(shape))
     buf = DeviceBuffer(B * fb, device)
     host = np.empty((B,) + shape, np.uint8)
+    enc = None
+    if sink is not None and kept:
+        from .mjpeg import Encoder
+        enc = Encoder(H, W, pix_fmt, quality=quality, max_batch=B, device=device)
     for i0 in range(0, kept, B):
         nb = min(B, kept - i0)
         first = (i0 + 1) * stride - 1                               # 0-based index of the batch's first kept frame
         host[:nb] = frames[first:first + (nb - 1) * stride + 1:stride]
         _lib.check(L.vbt_memcpy(buf.ptr, host.ctypes.data, nb * fb, 0))
         ov.draw(buf.ptr, nb, (i0 + 1) * stride, stride)
+        if enc is not None:
+            enc.encode(buf.ptr, nb)
+            for jpeg in enc.read():
+                sink.write(jpeg)
+            continue
         _lib.check(L.vbt_stream_synchronize(None))
         _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr, nb * fb, 1))
         out[i0:i0 + nb] = host[:nb]
-    return out
+    return kept if sink is not None else out

@@ -65,7 +65,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -76,11 +76,15 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     pix_fmt "nv12" / "i420": frames is uint8 [T, H*3//2, W], YUV 4:2:0 as a decoder emits it (rawvideo.py); converted and resized
     on the GPU.  src_hw=(H, W) is then optional (the shape gives it).
     video_out: optional uint8 array [T // frame_stride, ...] with the frames' layout (e.g. a numpy.lib.format.open_memmap) that receives
-    every kept frame with the tracked boxes, ids and bar paths drawn (overlay.render; the reference's `--video_dir`, track.py:241-242)."""
+    every kept frame with the tracked boxes, ids and bar paths drawn (overlay.render; the reference's `--video_dir`, track.py:241-242).
+    video_sink: optional mjpeg.AviWriter that receives the same frames encoded as JPEG on the device at video_quality."""
     data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw)
     if video_out is not None:
         from .overlay import render
         render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device)
+    if video_sink is not None:
+        from .overlay import render
+        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, device=device, sink=video_sink, quality=video_quality)
     return data
 
 
