@@ -629,6 +629,86 @@ int vbt_mjpeg_encode(vbt_mjpeg* m, const uint8_t* frames_dev, int B, void* strea
  * no batch is pending.  A successful read releases the handle for the next vbt_mjpeg_encode. */
 int vbt_mjpeg_read(vbt_mjpeg* m, uint8_t* host_buf, uint64_t cap, uint64_t* offsets, void* stream);
 
+/* ------------------------------------------------------------------ MJPEG import --------
+ * The way in for video files (the reference's cv2.VideoCapture, track.py:129-160): the frames of a Motion-JPEG AVI - the files
+ * the export above writes, and what many cameras and ffmpeg -c:v mjpeg write - are decoded on the device.  The host parses the
+ * headers and uploads only the compressed bytes; the frames appear in device memory as RGB24 [B,H,W,3], the layout
+ * vbt_pipeline_step_runs and vbt_overlay_draw take.  The reconstruction is pinned to the integer and is, bit for bit, what
+ * libjpeg-turbo does by default (the decoder behind Pillow, OpenCV and most players); the numpy statement is tests/mjpeg_dec_ref.py.
+ *
+ * Accepted (one JPEG file per frame): SOF0 baseline, 8-bit, Huffman; 1 component (grey) or 3 components (JFIF YCbCr); luma
+ * sampling 1x1, 2x1 or 2x2 with both chroma components 1x1 (4:4:4, 4:2:2, 4:2:0); one scan holding all components in frame order
+ * with Ss = 0, Se = 63, Ah = Al = 0; 8-bit DQT with table ids 0..3, several tables per segment allowed, a later table replaces an
+ * earlier one of its id; DHT ids 0..1 per class, several per segment, redefinition before SOS; NO DHT AT ALL = the Annex K.3 tables
+ * (the MJPG-in-AVI convention); any DRI, none or 0 included (an interval of 0 MCUs, or of more MCUs than the frame has, is one
+ * interval); APPn, COM and other segments with a length are skipped; 0xFF fill bytes before markers; 1..16384 pixels a side; a
+ * missing EOI.  A DC size category up to 16 is decoded.
+ * Refused, VBT_ERR_IO with a vbt_last_error() text that names the frame of the batch and the reason: SOF1, SOF2 and every other
+ * SOFn (progressive, arithmetic, lossless, hierarchical); a precision other than 8 bits; a 16-bit DQT; any other sampling or
+ * component count; more than one scan (a scan that does not hold all components, or a SOS / SOFn / DQT / DRI behind the scan); an
+ * Adobe APP14 segment whose transform is not 1 (0 = RGB / CMYK, 2 = YCCK); a segment length that runs past the frame; a missing SOI,
+ * SOS, SOF, a DQT or DHT the scan names; a DHT with more codes than a length holds or more than 256 symbols; a frame size other
+ * than the handle's; a frame of 2 GiB or more.
+ *
+ * Entropy decoding (T.81 F.2.2): the scan runs from behind SOS to the first marker that is neither RSTm nor a stuffed FF 00.  It is
+ * cut at its RSTm markers into restart intervals; interval k holds MCUs k ri .. min((k + 1) ri, MCUs) and starts with DC predictors
+ * 0.  Its levels are stored as int16 in natural order.  Per-frame scan status (vbt_mjpeg_decode_status), the largest raised:
+ *   0 fine;  1 an interval's bits ended before its MCUs did;  2 a bit pattern that no code of the table matches (or a DC size
+ *   above 16);  3 a run that takes the coefficient index above 63;  4 the number of RSTm markers is not ceil(MCUs / ri) - 1 (the
+ *   frame is then not walked at all);  5 a marker's m is not its index mod 8.
+ * Codes 1..3 end their interval: the blocks it had not reached keep level 0 (mid-grey for a first block, since predictors restart
+ * per interval).  A damaged scan spoils its own frame only; what such a frame shows is deterministic, but not part of the contract.
+ *
+ * Reconstruction, int32 throughout (wrapping; >> arithmetic):
+ *   Dequantise: c = level Q, natural order.
+ *   IDCT ("islow", Loeffler-Ligtenberg-Moschytz, 13-bit constants).  One 8-point pass on x[0..7] with descale shift s:
+ *     z1 = (x2 + x6) 4433;  t2 = z1 - x6 15137;  t3 = z1 + x2 6270;  t0 = (x0 + x4) << 13;  t1 = (x0 - x4) << 13;
+ *     t10 = t0 + t3;  t13 = t0 - t3;  t11 = t1 + t2;  t12 = t1 - t2;
+ *     a0 = x7, a1 = x5, a2 = x3, a3 = x1;  z1 = a0 + a3;  z2 = a1 + a2;  z3 = a0 + a2;  z4 = a1 + a3;  z5 = (z3 + z4) 9633;
+ *     a0 *= 2446;  a1 *= 16819;  a2 *= 25172;  a3 *= 12299;  z1 *= -7373;  z2 *= -20995;  z3 = z3 (-16069) + z5;  z4 = z4 (-3196) + z5;
+ *     a0 += z1 + z3;  a1 += z2 + z4;  a2 += z2 + z3;  a3 += z1 + z4;
+ *     y0, y7 = t10 +- a3;  y1, y6 = t11 +- a2;  y2, y5 = t12 +- a1;  y3, y4 = t13 +- a0;  each (y + 2^(s-1)) >> s.
+ *   Pass 1 runs down the columns of c with s = 11 (2 extra bits kept), pass 2 along the rows of the result with s = 18; the sample is
+ *   clip(value + 128, 0, 255).  (A stream whose dequantised values or pass-1 results leave int16 is outside the bit-for-bit
+ *   claim: SIMD builds of libjpeg-turbo keep those in 16 bits.)
+ *   Upsampling ("fancy", triangle).  A chroma component holds dw = ceil(W / hs) by dh = ceil(H / vs) samples; the edge rules use dw
+ *   and dh, never the padded MCU grid.  With in[i] a row of it and i = x >> 1:
+ *     h2v1 (4:2:2): out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2; out[0] = in[0], out[2dw-1] = in[dw-1].
+ *     h2v2 (4:2:0): the output row y takes row j = y >> 1 and its neighbour j - 1 (y even) or j + 1 (y odd), clamped to 0 .. dh - 1:
+ *       s[i] = 3 in_j[i] + in_neighbour[i];  out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4;
+ *       out[0] = (4 s[0] + 8) >> 4, out[2dw-1] = (4 s[dw-1] + 7) >> 4.
+ *     dw <= 2 (W <= 4): no filter, every sample is replicated 2 x (and 2 x down for h2v2) - the IJG decoder's rule.
+ *   Colour (JFIF full range), cb = Cb - 128, cr = Cr - 128:
+ *     R = Y + ((91881 cr + 32768) >> 16);  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16);  B = Y + ((116130 cb + 32768) >> 16),
+ *     each clipped to 0..255.  Grey: R = G = B = Y.
+ *
+ * Capacity.  A handle is one frame size and up to max_batch frames.  vbt_mjpeg_decoder_create allocates, per frame of max_batch and
+ * with NB = 3 (2 ceil(W / 16)) (2 ceil(H / 16)) blocks (the 4:4:4 worst case), 128 NB bytes of levels, 64 NB bytes of planar
+ * components and 4 ceil(W / 8) ceil(H / 8) bytes of interval table (the worst case, one MCU per interval): 18.9 MB per frame of
+ * 1920 x 1080, 2.4 GB per frame of 16384 x 16384.  It fails with VBT_ERR_HIP, naming the size, when the device cannot give that.
+ * The compressed bytes of a batch (a 4.1 KB descriptor per frame and the entropy-coded segments) travel through two pinned staging
+ * buffers, used in turn, and one device buffer; these start at H W / 4 bytes per frame and grow on demand up to 1 GiB per batch
+ * (VBT_ERR_CAPACITY above that); a growing call allocates, and so waits for the device - every other call only enqueues.  One handle
+ * serves one stream at a time.  No torch, no library: HIP kernels for gfx950 (vbt_amd/csrc/mjpeg_decode.hip); the parser and the
+ * decoding statements are vbt_amd/csrc/jpeg_parse.h and jpeg_core.h. */
+typedef struct vbt_mjpeg_decoder vbt_mjpeg_decoder;
+/* Host only, no device call: the size, the component count (1 or 3) and the luma sampling as (hs << 4) | vs (0x11, 0x21, 0x22) of
+ * one JPEG file the decoder accepts; any of the four pointers may be NULL.  VBT_ERR_IO with the reason otherwise. */
+int vbt_jpeg_probe(const uint8_t* bytes, uint64_t n, int* H, int* W, int* components, int* sampling);
+/* VBT_ERR_ARG, before any device call: out NULL, H or W outside 1..16384, max_batch outside 1..1024. */
+int vbt_mjpeg_decoder_create(int device, int H, int W, int max_batch, vbt_mjpeg_decoder** out);
+void vbt_mjpeg_decoder_destroy(vbt_mjpeg_decoder* d);
+/* Decode B frames: frame i is host_bytes[offsets[i] .. offsets[i + 1]) (B + 1 offsets, ascending), a complete JPEG file; the frames
+ * go to frames_dev_out, B x H x W x 3 bytes of device memory.  All B headers are parsed first: a refusal returns VBT_ERR_IO with
+ * nothing enqueued and frames_dev_out untouched.  Then the descriptors and scans are packed into the staging buffer whose turn it
+ * is - the host waits for the event behind that buffer's last copy; no stream wait is put in front of the copy - followed by one
+ * H2D copy and the launches, all on `stream`.  host_bytes may be reused as soon as the call returns.  VBT_ERR_CAPACITY:
+ * B > max_batch, or more than 1 GiB of compressed bytes; VBT_ERR_ARG: B < 1 or a NULL argument. */
+int vbt_mjpeg_decode(vbt_mjpeg_decoder* d, const uint8_t* host_bytes, const uint64_t* offsets, int B, uint8_t* frames_dev_out, void* stream);
+/* The scan status of every frame of the last batch (B words, codes above): ONE synchronisation of `stream`, one copy.
+ * VBT_ERR_STATE: nothing has been decoded yet. */
+int vbt_mjpeg_decode_status(vbt_mjpeg_decoder* d, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

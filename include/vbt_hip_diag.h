@@ -99,6 +99,12 @@ int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, doub
  * VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
 int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
 
+/* MJPEG import, measurement (tools/mjpeg_decode_bench.py).  With VBT_MJPEG_DECODE_STAMPS=1 in the environment of
+ * vbt_mjpeg_decoder_create, every vbt_mjpeg_decode records a HIP event around each of its stages; this call waits for the last one and
+ * gives the six stage times of the last batch in milliseconds: H2D copy, memsets, marker scan, entropy decode, IDCT, upsampling +
+ * colour.  VBT_ERR_STATE without the variable or before the first decode. */
+int vbt_mjpeg_decode_stage_ms(vbt_mjpeg_decoder* d, float* ms6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,10 @@
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
-      reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3] (cv2 / video decode is not a
-      dependency here); any source resolution (resized on the GPU like odt.py:10-19).  Writes
+      reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
+      cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
+      import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it); any source
+      resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
       --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
       list that changes afterwards (the leading id changes, or a larger rep makes the filter drop small ones) is announced with a
@@ -87,6 +89,15 @@ def _open_source(s, pix_fmt, size):
     from .rawvideo import open_raw
     if not os.path.isfile(s):
         raise FileNotFoundError(s)                                       # reference track.py:89-90
+    if _is_avi(s):
+        if size is not None or pix_fmt != "rgb24":
+            raise click.UsageError(f"{s}: an .avi source carries its own frame size and decodes to RGB: --size and --pix_fmt {pix_fmt} do not apply")
+        from ._lib import VbtError
+        from .mjpeg import AviClip
+        try:
+            return AviClip(s)
+        except (ValueError, VbtError) as e:
+            raise click.ClickException(str(e))
     if size is not None:
         try:
             return open_raw(s, pix_fmt, size)
@@ -96,6 +107,20 @@ def _open_source(s, pix_fmt, size):
     if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
         raise click.ClickException(f"{s}: expected uint8 [T,H,W,3], got {frames.dtype} {frames.shape}")
     return frames
+
+
+def _is_avi(s):
+    return str(s).lower().endswith(".avi")
+
+
+def _fps_given():
+    """was --fps on the command line?  (an .avi source otherwise brings its own rate / scale)"""
+    from click.core import ParameterSource
+    return click.get_current_context().get_parameter_source("fps") == ParameterSource.COMMANDLINE
+
+
+def _source_fps(frames, fps, given):
+    return fps if given or not hasattr(frames, "fps") else float(frames.fps)
 
 
 def _raw_size(pix_fmt, size):
@@ -135,15 +160,18 @@ def _raw_size(pix_fmt, size):
 def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
+    fps_given = _fps_given()
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality)
+                                 video_format, video_quality, fps_given)
+    default_fps = fps
     for s in src:
         frames = _open_source(s, pix_fmt, size)
+        fps = _source_fps(frames, default_fps, fps_given)
         mjpeg = video_dir is not None and video_format == "mjpeg"
         video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
         with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
@@ -185,7 +213,10 @@ def _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt):
     os.makedirs(video_dir, exist_ok=True)
     H, W = source_hw(frames, pix_fmt)
     rate, scale = frame_rate(fps, frame_stride)
-    return AviWriter(os.path.join(video_dir, os.path.basename(s).split(".")[0] + ".avi"), W, H, rate, scale)
+    path = os.path.join(video_dir, os.path.basename(s).split(".")[0] + ".avi")
+    if os.path.exists(path) and os.path.samefile(path, s):
+        raise click.UsageError(f"--video_dir {video_dir}: the export {path} would overwrite its own source; choose another directory")
+    return AviWriter(path, W, H, rate, scale)
 
 
 def _video_done(video):
@@ -208,7 +239,7 @@ def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, 
 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
-                      video_format="raw", video_quality=85):
+                      video_format="raw", video_quality=85, fps_given=True):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -221,11 +252,12 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
             error = e
             break
     lines, nxt = {}, 0
+    fps = [_source_fps(a, fps, fps_given) for a in sources] or fps
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
                               time_batch=time_batch, pix_fmt=pix_fmt):
         s = src[i]
         if video_dir is not None:                                        # the clip is finished: its rows are all the renderer needs
-            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps, frame_stride, time_batch, pix_fmt, size)
+            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size)
         if not data["id"]:
             lines[i] = f"{s}: no tracked rows"
         else:
@@ -259,6 +291,7 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
     if not os.path.isfile(dataframe):
         raise FileNotFoundError(dataframe)
     frames = _open_source(src, pix_fmt, size)
+    fps = _source_fps(frames, fps, _fps_given())
     df = pd.read_pickle(dataframe)
     n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size)
     click.echo(f"{src}: {n} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")

@@ -107,10 +107,24 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
         return pipe.track_clip(frames, frame_stride=stride, src_hw=src_hw)      # vbt_track_clip: the whole loop inside the library
     # any other sequence (or live analysis): chunk by chunk through contiguous host copies
     idx_all = np.arange(stride - 1, T, stride)
+    dev = None
+    if hasattr(frames, "decode_into"):
+        # a compressed source (mjpeg.AviClip): only the kept frames are decoded, on the device, straight into one of two device buffers
+        # that step_runs takes by pointer; nothing but compressed bytes crosses the bus
+        if is_yuv(pix_fmt):
+            raise ValueError("track_frames: a decoded source gives rgb24 frames")
+        from .mem import DeviceBuffer
+        dev = [DeviceBuffer(F * H * W * 3, device) for _ in range(2)]
     for i0 in range(0, len(idx_all), F):
         idx = idx_all[i0:i0 + F]
-        chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
-        pipe.step_runs(chunk, [(0, 0, len(idx), int(idx[0]) + 1, stride)], src_hw=src_hw)
+        if dev is not None:
+            buf = dev[(i0 // F) % 2]
+            pipe.join_detectors(0)                                       # the forwards that still read the buffers come first
+            frames.decode_into(idx, buf.ptr, 0)
+            pipe.step_runs(buf.ptr, [(0, 0, len(idx), int(idx[0]) + 1, stride)], stream=0, src_hw=src_hw)
+        else:
+            chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
+            pipe.step_runs(chunk, [(0, 0, len(idx), int(idx[0]) + 1, stride)], src_hw=src_hw)
         if live is not None:
             live(pipe.live()[0], False)
     if live is not None:
