@@ -395,8 +395,9 @@ static int launch_dw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
 
 // fused MBConv / SeparableConv / BiFPN node on LDS tiles (fused_block.h) or, MBConv on a low-resolution map, one workgroup per image
 // (image_block.h).  Variant bits: 1 = depthwise on the matrix pipe (else VALU), 2 = half-height tile, 4 = whole image, 8 = 48-channel
-// chunks, 16 = 128-pixel (16 x 8) tiles; a bit whose conditions the step does not meet is ignored, except that the whole-image and
-// 128-pixel kernels refuse a step they do not fit.
+// chunks, 16 = 128-pixel (16 x 8) tiles, 32 = band-Toeplitz depthwise (fused_block.h: TPZ); a bit whose conditions the step does not
+// meet is ignored, except that the whole-image and 128-pixel kernels refuse a step they do not fit and that bit 32 resolves only as
+// 33, 41, 49 or 57 on a step where each of its other bits holds.
 struct FusedPlan : Verdict {
   bool image = false; int PW = 0, PH = 0, NB = 0, maxu = 0;   // whole-image kernel: padded map, output channel blocks, work units per wave
   int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0; FusedLaunch L{};   // (whole image: k, stride and lds_bytes of L)
@@ -415,6 +416,7 @@ static FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, i
   const bool mdw = var & 1, half = var & 2;
   const bool nt3 = (var & 8) && mdw && a.nch3 > 0 && s.nbp <= 2 && a.KSe >= 1 && a.KSe <= 4;
   FusedPlan p;
+  if ((var & 32) && (var & 4)) { p.refuse(VBT_ERR_ARG, "fused_mbconv: variant %d: the Toeplitz depthwise does not apply to this step", var); return p; }
   if (var & 4) {
     const int HW = a.H * a.W, OHW = a.OH * a.OW;
     if (!ex || HW > 400 || OHW > 400 || !s.ib.data) { p.refuse(VBT_ERR_ARG, "fused_mbconv: whole-image variant not applicable"); return p; }
@@ -437,12 +439,19 @@ static FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, i
   // otherwise 64-pixel tiles of exactly 8 x 8 outputs with the same limits take the 16x16x64 depthwise too (DW64)
   const bool dw64 = ppw2 || (ex && mdw && a.wd64 && p.TX == 8 && p.TY == 8 && ks12 && s.nbp <= 2);
   const int est = !ex ? 0 : !nt3 ? FB_EST : dw64 ? 48 : 72;   // E row bytes (fused_block.h: EST)
+  // Toeplitz depthwise (bit 32): a form of dw64, selected by exactly 33, 41, 49 or 57 on a step it is built for - refused anywhere else
+  const bool tpz = var & 32;
+  const bool tpz_ok = tpz && dw64 && a.wtz && fused_tpz_built(k, stride, s.nbp, a.KSe, ppw2) && (var & ~(1 | 8 | 16 | 32)) == 0 && nt3 == bool(var & 8) && ppw2 == bool(var & 16);
+  const TpzGeom tg = tpz_ok ? tpz_geom(k, stride, ppw2 ? 2 : 1, nt3 ? 3 : 4) : TpzGeom{};
+  const int e_bytes = tpz_ok ? tg.e_bytes + 8 * tg.DSK : -1;   // (with the tile rows' shift of D)
   p.tiles_x = (a.OW + p.TX - 1) / p.TX;
   p.tiles_y = (a.OH + p.TY - 1) / p.TY;
-  p.L = FusedLaunch{k, stride, s.nbp, ex, mdw, nt3, ppw2, dw64, fused_tile_lds(a, k, stride, p.TX, p.TY, est, ppw2 ? 2 : 1, s.nbp),
-                    (unsigned)((long)B * p.tiles_x * p.tiles_y)};
+  p.L = FusedLaunch{k, stride, s.nbp, ex, mdw, nt3, ppw2, dw64, fused_tile_lds(a, k, stride, p.TX, p.TY, est, ppw2 ? 2 : 1, s.nbp, e_bytes),
+                    (unsigned)((long)B * p.tiles_x * p.tiles_y), tpz_ok};
   if (ppw2 && (a.OW < 16 || a.OH < 8 || !a.wd64)) p.refuse(VBT_ERR_ARG, "fused_mbconv: the 128-pixel variant needs maps of at least 16 x 8");
   else if (ppw2 && p.L.lds_bytes > 64 * 1024) p.refuse(VBT_ERR_ARG, "fused_mbconv: 128-pixel tile needs %d bytes of LDS", p.L.lds_bytes);
+  else if (tpz && !tpz_ok) p.refuse(VBT_ERR_ARG, "fused_mbconv: variant %d: the Toeplitz depthwise does not apply to this step", var);
+  else if (tpz && p.L.lds_bytes > 64 * 1024) p.refuse(VBT_ERR_ARG, "fused_mbconv: the Toeplitz depthwise tile needs %d bytes of LDS", p.L.lds_bytes);
   return p;
 }
 static int launch_fused_step(const vbt_model* m, const Step& s, FusedArgs a, int B, hipStream_t st) {
@@ -755,6 +764,7 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
       cand.push_back(17);
       if (st.fa.nch3 > 0) cand.push_back(25);
     }
+    if (st.family == F_MBCONV && st.fa.wtz) cand.insert(cand.end(), {33, 41, 49, 57});   // Toeplitz depthwise on the four DW64 forms
   } else if (st.family == F_MULTI) {
     cand = {0, 1};
   } else if (st.family == F_EXPDW) {
@@ -840,7 +850,7 @@ static PlanShape plan_shape(const vbt_model* m) {
         auto add = [&](int v) { if (std::find(ps.variants.begin(), ps.variants.end(), v) == ps.variants.end()) ps.variants.push_back(v); };
         // the fused tile kernels read their variant as a set of flags (resolve_fused): plans searched under load (tools/tune_under_load.py)
         // hold combinations the isolated autotuner does not time, and every combination that resolves is accepted
-        for (int v = 0; v < 32 && is_fused_tile(st.family); v++)
+        for (int v = 0; v < 64 && is_fused_tile(st.family); v++)
           if (variant_ok(m, st, v)) add(v);
         add(-1);
         add(st.variant);   // the heuristic plan's own choice

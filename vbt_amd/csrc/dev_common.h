@@ -94,6 +94,12 @@ __device__ __forceinline__ v4i diag_operand(unsigned wb, int i) {
   const int d = i >> 2;
   return (v4i){d == 0 ? (int)sh : 0, d == 1 ? (int)sh : 0, d == 2 ? (int)sh : 0, d == 3 ? (int)sh : 0};
 }
+// A operand of the band-Toeplitz depthwise MFMA (expdw2_block.h, fused_block.h: TPZ) from its four bytes: dword j holds byte j at
+// byte position c = row & 3
+__device__ __forceinline__ v4i toeplitz_operand(unsigned w4, int c) {
+  const int sh = 8 * c;
+  return (v4i){(int)((w4 & 0xffu) << sh), (int)(((w4 >> 8) & 0xffu) << sh), (int)(((w4 >> 16) & 0xffu) << sh), (int)((w4 >> 24) << sh)};
+}
 // exact n / d for 0 <= n < 2^20, 1 <= d <= 4096 without the ~40-instruction integer division
 __device__ __forceinline__ int fdiv_small(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
 // reciprocal for fdiv_small: one v_rcp_f32 (1 ulp) instead of the IEEE division sequence.  (n + 0.5) / d lies at least

@@ -64,12 +64,6 @@ struct ExpDw2Args {
 #endif
 };
 
-// A operand of the band-Toeplitz depthwise MFMA from its four bytes: dword j holds byte j at byte position c = row & 3
-__device__ __forceinline__ v4i toeplitz_operand(unsigned w4, int c) {
-  const int sh = 8 * c;
-  return (v4i){(int)((w4 & 0xffu) << sh), (int)(((w4 >> 8) & 0xffu) << sh), (int)(((w4 >> 16) & 0xffu) << sh), (int)((w4 >> 24) << sh)};
-}
-
 constexpr int XD2_NPG = 8;   // position groups a band may have (128 positions = 512 output pixels)
 template <int PG, class F, class FC>
 __device__ __forceinline__ void d_pair(F& d_units, FC full_c, int NPGo) {

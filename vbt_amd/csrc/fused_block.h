@@ -15,6 +15,7 @@
 // output columns, weights in registers, cvt_f32_ubyte + fma, exact) -> barrier -> project accumulation
 // (int8 MFMA, wave w owns pixels 16w..16w+15, accumulators stay in registers across chunks).
 #pragma once
+#include "tpz_geom.h"
 
 struct FusedArgs {
   const int8_t* x;
@@ -56,6 +57,9 @@ struct FusedArgs {
   // the same operands as one byte each: [16-channel group q][lane] x 8 B, byte m = the non-zero byte of operand (q, m) of that
   // lane; the kernels rebuild the 16-byte operand in registers (diag_operand)
   const long* wd64c;
+  // band-Toeplitz depthwise (TPZ): tap table [channel quad q][m][lane] x 4 bytes (pack_expdw2_taps over all Ce_pad / 4 quads - a
+  // 64-channel chunk c starts at quad 16c, a 48-channel chunk at quad 12c); the kernel rebuilds the operands (toeplitz_operand)
+  const unsigned* wtz;
   // project
   const v4i* wp;    // packed for the 16x16x64 MFMA (pack_weights64), K = Ce_pad, one K-step per 64-channel chunk
   const int* bp;
@@ -107,10 +111,16 @@ constexpr int FB_DST = 80;  // D tile bytes per pixel: 16-byte aligned rows (the
 // row length is then a compile-time constant and every LDS address of the stage is `lane base + immediate` - no address
 // arithmetic in the stage at all (the 16x16x32 form spends one v_add per ds_read_b64 and needs 5 / 13 instructions per
 // pixel group instead of 3 / 7).
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false>
+// TPZ: the DW64 depthwise as a band-Toeplitz product (tpz_geom.h) - 10 taps per instruction and operand read instead of 4, wave w owns
+// the channel quads w NT .. w NT + NT - 1 of the chunk on every position group (no idle wave on 48-channel chunks); the expand
+// stage writes E quad-planar, the D tile, the projection stage and the epilogue are those of the diagonal form.
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false>
 __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, unsigned char* fb_smem) {
   static_assert(PPW == 1 || MDW, "128-pixel tiles exist for the matrix-pipe depthwise only");
   static_assert(!DW64 || (EXPAND && MDW && (KK == 3 || KK == 5)), "DW64: fused expand blocks, 3x3 / 5x5");
+  static_assert(!TPZ || (DW64 && (S == 1 || S == 2) && (NT == 3 || NT == 4) && NBP <= 2 && (KSE == 1 || KSE == 2)), "TPZ: a form of DW64");
+  constexpr TpzGeom TG = TPZ ? tpz_geom(KK, S, PPW, NT) : TpzGeom{};
+  constexpr int KT2 = (S * (S - 1) + KK + 1) / 2;   // TPZ: depthwise MFMAs per unit, two rows of the expanded image each
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
   // tile -> (image, ty, tx) and every later pixel -> (row, column) split go through fdiv_small: no integer division
   // (~40 VALU instructions each) anywhere in the prologue
@@ -131,13 +141,13 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   // DW64 reads 16-byte groups, so its rows stay 16-byte aligned: 48 bytes for 48-channel chunks (conflict-free b128 reads at
   // stride 1, 3-dword-skewed conflict-free writes, and 40 % less LDS than 80-byte rows: one more workgroup per CU on b1-b3)
   constexpr int EST = (EXPAND && NT == 3) ? (DW64 ? 48 : 72) : FB_EST;
-  unsigned char* D = E + (EXPAND ? ((NPh * EST + 15) & ~15) : 0);
+  unsigned char* D = E + (EXPAND ? (TPZ ? TG.e_bytes : ((NPh * EST + 15) & ~15)) : 0);
   // SeparableConv / node / head tiles whose depthwise input is ONE 64-channel chunk (BiFPN width 64): the projection
   // weights and its bias / multipliers are copied into LDS while the input tile loads, so the projection and the epilogue
   // start from LDS instead of from two more exposed L2 round trips (these kernels are latency chains, not bandwidth)
   bool stage_p = false;
   if constexpr (!EXPAND && NBP <= 2) stage_p = a.nchunks == 1;
-  unsigned char* WPS = D + 64 * PPW * FB_DST;    // [NBP][4][64] x 16 B
+  unsigned char* WPS = D + 64 * PPW * FB_DST;    // [NBP][4][64] x 16 B  (no expand stage: never with TPZ, whose D is 8 TG.DSK bytes longer)
   unsigned char* BPS = WPS + NBP * 4096;         // bias int[NBP*64] | mult float[NBP*64]
 
   // ---- stage L: input halo tile -> LDS ----
@@ -284,6 +294,15 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       hbase[pg] = (py_ * S) * HWx + px_ * S;
     }
   }
+  // TPZ: lane (r = position of a group, g = K slice / output pixel of the position) -> E byte offset of its operand (kernel rows
+  // 0 / 1, column half g & 1, the wave's first quad) and D byte offset of its output dword on position group 0, once per kernel:
+  // every address of the stage is then `lane base + immediate`
+  const int wq0 = TPZ ? __builtin_amdgcn_readfirstlane(wave) * NT : 0;   // the wave's first channel quad of a chunk
+  int tz_e = 0, tz_d = 0;
+  if constexpr (TPZ) {
+    tz_e = tpz_e_offset(TG, S, r, g, wq0);
+    tz_d = tpz_d_offset(TG, S, PPW, FB_DST, r, g, wq0);
+  }
   // SeparableConv / node / head tiles (no expand): the first chunk's depthwise operands do not depend on the tile, so
   // they are requested before the barrier and their latency overlaps the input tile loads
   constexpr int KTP = (KK * KK + 1) / 2;
@@ -315,6 +334,13 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         bpre = *(const int4*)(a.bdm + c * CH + 16 * wave + 4 * g);
         mpre = *(const float4*)(a.md + c * CH + 16 * wave + 4 * g);
       }
+    }
+    // TPZ: this wave's depthwise taps (NT * KT2 dwords) are requested before the expand stage and consumed after the barrier
+    unsigned wtz[TPZ ? NT * KT2 : 1];
+    if constexpr (TPZ) {
+      const unsigned* wt = a.wtz + ((long)(c * 4 * NT + wq0) * KT2) * 64 + lane;
+#pragma unroll
+      for (int i = 0; i < NT * KT2; i++) wtz[i] = wt[i * 64];
     }
     if (EXPAND) {
       // ---- stage E: expand chunk c on every halo pixel ----
@@ -371,7 +397,13 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
             if ((oob_mask >> i) & 1u) d[t] = zeb;
           }
           if (!((tail_mask >> i) & 1u)) {
-            if constexpr (NT == 4) {
+            if constexpr (TPZ) {
+              // quad-planar: the lane's NT dwords are the quads NT g .. NT g + NT - 1 of halo pixel (hy, hx)
+              const int hy = fdiv_small(p, rcp_hwx), hx = p - hy * HWx;
+              unsigned char* ep = E + tpz_e_store(TG, hy, hx, NT * g);
+#pragma unroll
+              for (int t = 0; t < NT; t++) *(unsigned*)(ep + t * TG.EQS) = d[t];
+            } else if constexpr (NT == 4) {
               *(uint4*)(E + p * FB_EST + 16 * g) = make_uint4(d[0], d[1], d[2], d[3]);
             } else {
 #pragma unroll
@@ -384,7 +416,45 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       __syncthreads();
     }
     // ---- stage D: depthwise on chunk c ----
-    if constexpr (DW64) {
+    if constexpr (TPZ) {
+      // unit = (channel quad q of the wave, position group pg), two at a time: independent accumulate chains.  A lane ends with the
+      // 4 channels of output pixel g of its position: one dword of the D tile.
+      constexpr int NU = NT * PPW, PGE = tpz_e_group(TG, S), PGD = tpz_d_group(TG, PPW, FB_DST);   // position group pg -> pg + 1 in E / in D
+      int4 bq[NT];
+      float4 mq[NT];
+#pragma unroll
+      for (int q = 0; q < NT; q++) {
+        bq[q] = *(const int4*)(a.bdm + c * CH + 4 * (wq0 + q));
+        mq[q] = *(const float4*)(a.md + c * CH + 4 * (wq0 + q));
+      }
+      const unsigned char* eb = E + tz_e;
+      unsigned char* db = D + tz_d;
+      auto tz_walk = [&](auto mode_tag) {
+        constexpr int RM = decltype(mode_tag)::value;
+#pragma unroll
+        for (int u0 = 0; u0 < NU; u0 += 2) {
+          v4i dq[2];
+#pragma unroll
+          for (int u = 0; u < 2; u++) dq[u] = v4i_from(int4_plus(bq[(u0 + u < NU ? u0 + u : u0) / PPW], RM >= 2 ? RQ_KBIAS : 0));
+#pragma unroll
+          for (int mi = 0; mi < KT2; mi++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+              if (u0 + u >= NU) continue;
+              const int q = (u0 + u) / PPW, pg = (u0 + u) % PPW;
+              const v4i bv = *(const v4i*)(eb + q * TG.EQS + pg * PGE + mi * 2 * TG.EYS);
+              dq[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(toeplitz_operand(wtz[q * KT2 + mi], r & 3), bv, dq[u], 0, 0, 0);
+            }
+#pragma unroll
+          for (int u = 0; u < 2; u++) {
+            if (u0 + u >= NU) continue;
+            const int q = (u0 + u) / PPW, pg = (u0 + u) % PPW;
+            *(unsigned*)(db + pg * PGD + 4 * q) = rq_pack_b<RM>(dq[u], mq[q], a.rqd);
+          }
+        }
+      };
+      rq_dispatch(a.rqd, tz_walk);
+    } else if constexpr (DW64) {
       constexpr int TXP = 8 * PPW, HWX = (TXP - 1) * S + KK;
       constexpr int KT64 = KK == 3 ? 3 : 7;
       constexpr int PGS = (16 / TXP) * S * HWX * EST;   // slot group pg -> pg + 1
@@ -512,7 +582,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
     {
       v4i bv[PPW];
 #pragma unroll
-      for (int pp = 0; pp < PPW; pp++) bv[pp] = *(const v4i*)(D + ((wave * PPW + pp) * 16 + r) * FB_DST + 16 * g);
+      for (int pp = 0; pp < PPW; pp++) {
+        const int slot = (wave * PPW + pp) * 16 + r;
+        bv[pp] = *(const v4i*)(D + (TPZ ? tpz_d_slot(TG, PPW, FB_DST, slot) : slot * FB_DST) + 16 * g);
+      }
 #pragma unroll
       for (int nb = 0; nb < NBP; nb++) {
         const v4i* w = stage_p ? (const v4i*)WPS + (nb * 4) * 64 + lane
@@ -583,10 +656,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
 #ifndef FB_MINW
 #define FB_MINW 1
 #endif
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false>
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false>
 __global__ __launch_bounds__(256, FB_MINW) void fused_block_kernel(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fb_smem_dyn[];
-  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64>(a, blockIdx.x, fb_smem_dyn);
+  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ>(a, blockIdx.x, fb_smem_dyn);
 }
 
 // Several independent problems (e.g. the same head layer on all 5 pyramid levels of both heads) in ONE grid:

@@ -46,7 +46,10 @@ namespace vbt {
     }                                                      \
   } while (0)
 
+int launch_fused_mbconv_tpz(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);   // k_fused_mbconv_tpz.hip
+
 int launch_fused_mbconv(const FusedArgs& a, const FusedLaunch& L, hipStream_t st) {
+  if (L.tpz) return launch_fused_mbconv_tpz(a, L, st);
   const dim3 grid(L.grid);
   if (L.ppw2) {
     if (L.k == 3 && L.stride == 1) FB_P2K(3, 1);

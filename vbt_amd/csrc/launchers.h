@@ -23,7 +23,16 @@ struct FusedLaunch {
   bool dw64;            // depthwise on the 16x16x64 MFMA with immediate LDS offsets (8 x 8 or 16 x 8 tiles)
   int lds_bytes;
   unsigned grid;
+  bool tpz = false;     // dw64 as a band-Toeplitz product on a quad-planar E (k_fused_mbconv_tpz.hip)
 };
+// The (k, stride, nbp, KSe) the Toeplitz form is built for - what the MBConv steps of the shipped models resolve to (the first five
+// four blocks of the EfficientNet-Lite backbones: the fifth is not cut into 8 x 8 tiles and its 16 x 8 tile does not fit 64 KB, the later
+// ones have KSe >= 3) - each with 48- and 64-channel chunks on 8 x 8 tiles and, except 5x5/2 (whose 16 x 8 tile needs 66-78 KB), on
+// 16 x 8 tiles.  Another shape needs a line here and one in k_fused_mbconv_tpz.hip.
+static inline bool fused_tpz_built(int k, int stride, int nbp, int kse, bool ppw2) {
+  return (k == 3 && stride == 2 && nbp == 1 && kse == 1) || (k == 3 && stride == 1 && nbp == 1 && kse == 1) ||
+         (k == 5 && stride == 2 && nbp == 1 && kse == 1 && !ppw2) || (k == 5 && stride == 1 && nbp == 1 && kse == 2);
+}
 int launch_fused_block(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);
 int launch_fused_multi(const FusedArgs* d_args, const MultiTiles& mt, int k, int stride, int nbp, bool mdw, int lds_bytes, unsigned grid,
                        hipStream_t st);

@@ -42,10 +42,11 @@ static void choose_tile(int OH, int OW, int KK, int S, bool expand, int* TXo, in
 // pixel; 0: no expand stage), the depthwise output of 64 * ppw pixels and, for a single-chunk SeparableConv / node, the projection
 // weights + bias / multipliers staged in LDS.  (Rounding the E rows up to 16 bytes changes only the 72-byte rows: FB_EST and 48 are
 // multiples of 16.)
-static int fused_tile_lds(const FusedArgs& a, int k, int stride, int TX, int TY, int est, int ppw, int nbp) {
+// e_bytes >= 0: the expanded halo takes that many bytes instead (the quad-planar E of the Toeplitz depthwise: tpz_geom).
+static int fused_tile_lds(const FusedArgs& a, int k, int stride, int TX, int TY, int est, int ppw, int nbp, int e_bytes = -1) {
   const int TXp = (TX + 3) & ~3;
   const int NPh = ((TXp - 1) * stride + k) * ((TY - 1) * stride + k);
-  int lds = ((NPh * a.T0S + 15) & ~15) + ((NPh * est + 15) & ~15) + ppw * 64 * FB_DST;
+  int lds = ((NPh * a.T0S + 15) & ~15) + (e_bytes >= 0 ? e_bytes : ((NPh * est + 15) & ~15)) + ppw * 64 * FB_DST;
   if (!est && a.nchunks == 1 && nbp <= 2) lds += nbp * (4096 + 512);
   return lds;
 }
@@ -183,6 +184,11 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
       v4i* d64; long* d64c;
       if ((rc = upload(m, w64, &d64)) || (rc = upload(m, pack_dw64_compact(w64, dop.k), &d64c))) return rc;
       a.wd64 = d64; a.wd64c = d64c;
+      if (fused_tpz_built(dop.k, dop.stride, s.nbp, a.KSe, false)) {   // band-Toeplitz form of the same stage: taps of all Cp / 4 quads
+        unsigned* dtz;
+        if ((rc = upload(m, pack_expdw2_taps(wd, Ce, 0, Cp / 4, dop.k, dop.stride), &dtz))) return rc;
+        a.wtz = dtz;
+      }
     }
     a.zd = tdout.zero_point; a.lod = dop.act_min; a.hid = dop.act_max;
     a.rqd = make_rq(a.zd, a.lod, a.hid, conv_kb(m, dop));
@@ -609,10 +615,6 @@ static int make_expdw(vbt_model* m, int e_op, int d_op, Step* out) {
 // LDS cycles of the depthwise operand reads (ds_read_b128: four groups of 16 lanes, one cycle per group when its 16-byte pieces
 // fall on distinct quarters of the 64 banks; equal addresses broadcast) summed over the positions of a band, for a row stride EYS
 static long xd2_read_cycles(int PR, int XB, int EYS, int RM) {   // PR position rows, RM rows of the expanded image between them
-  static const int grp[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                 {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
-                                 {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
-                                 {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
   const int NPOS = PR * XB;
   long cycles = 0;
   for (int pg = 0; pg * 16 < NPOS; pg++)
@@ -620,7 +622,7 @@ static long xd2_read_cycles(int PR, int XB, int EYS, int RM) {   // PR position 
       std::vector<int> seen[16];
       int worst = 1;
       for (int j = 0; j < 16; j++) {
-        const int lane = grp[k][j], r = lane & 15, g = lane >> 4, n = std::min(pg * 16 + r, NPOS - 1);
+        const int lane = DS_READ_B128_GROUPS[k][j], r = lane & 15, g = lane >> 4, n = std::min(pg * 16 + r, NPOS - 1);   // (tpz_geom.h)
         const int addr = (n / XB) * RM * EYS + (n % XB) * 16 + (g >> 1) * EYS + 16 * (g & 1);
         std::vector<int>& v = seen[(addr >> 4) & 15];
         if (std::find(v.begin(), v.end(), addr) == v.end()) v.push_back(addr);
@@ -707,7 +709,7 @@ static int make_expdw2(vbt_model* m, int e_op, int d_op, Step* s, const std::vec
     memcpy(e + KS64 * 256, &be[c * 64], 256);
     memcpy(e + KS64 * 256 + 16, &me[c * 64], 256);
     v4i* d = &ppd[(size_t)c * ND];
-    const std::vector<unsigned> tab = pack_expdw2_taps(wd, Ce, c, kk, S);
+    const std::vector<unsigned> tab = pack_expdw2_taps(wd, Ce, 64 * c, 16, kk, S);
     memcpy(d, tab.data(), tab.size() * sizeof(unsigned));
     memcpy(d + KT2 * 256, &bd[c * 64], 256);
     memcpy(d + KT2 * 256 + 16, &md[c * 64], 256);

@@ -261,16 +261,18 @@ static std::vector<long> pack_expdw_taps(const int8_t* w, int Ce, int kk) {
         }
   return out;
 }
-// Expand + depthwise, second form (expdw2_block.h), tap table of 64-channel chunk c: [q][m][lane] x 4 bytes.  Operand row i of
-// lane (i, g) computes output pixel i>>2 of a position (1 x 4 at stride 1, 2 x 2 at stride 2) for channel 64c + 4q + (i&3);
-// byte j = the weight at kernel row 2m + (g>>1) - S*dy, column 4(g&1) + j - S*dx, zero outside the k x k kernel
-static std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int c, int k, int S) {
+// Band-Toeplitz depthwise (expdw2_block.h; fused_block.h: TPZ), tap table of the nq channel quads from channel `base` on:
+// [q][m][lane] x 4 bytes.  Operand row i of lane (i, g) computes output pixel i>>2 of a position (1 x 4 at stride 1, 2 x 2 at
+// stride 2) for channel base + 4q + (i&3); byte j = the weight at kernel row 2m + (g>>1) - S*dy, column 4(g&1) + j - S*dx, zero
+// outside the k x k kernel and past channel Ce.  expdw2: one table per 64-channel chunk c (base 64c, 16 quads); the fused tiles:
+// one table over all quads, which serves 64- and 48-channel chunks alike (chunk c starts at quad 16c / 12c).
+static std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int base, int nq, int k, int S) {
   const int KT2 = (S * (S - 1) + k + 1) / 2;
-  std::vector<unsigned> out((size_t)16 * KT2 * 64, 0);
-  for (int q = 0; q < 16; q++)
+  std::vector<unsigned> out((size_t)nq * KT2 * 64, 0);
+  for (int q = 0; q < nq; q++)
     for (int mi = 0; mi < KT2; mi++)
       for (int lane = 0; lane < 64; lane++) {
-        const int i = lane & 15, g = lane >> 4, qq = i >> 2, cc = i & 3, ch = 64 * c + 4 * q + cc;
+        const int i = lane & 15, g = lane >> 4, qq = i >> 2, cc = i & 3, ch = base + 4 * q + cc;
         const int dy = S == 2 ? qq >> 1 : 0, dx = S == 2 ? qq & 1 : qq;   // the output pixel of the position this operand row computes
         const int ty = 2 * mi + (g >> 1) - S * dy;
         unsigned w4 = 0;
@@ -278,7 +280,7 @@ static std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int c, in
           const int tx = 4 * (g & 1) + j - S * dx;
           if (ty >= 0 && ty < k && tx >= 0 && tx < k && ch < Ce) w4 |= (unsigned)(uint8_t)w[(size_t)(ty * k + tx) * Ce + ch] << (8 * j);
         }
-        out[(q * KT2 + mi) * 64 + lane] = w4;
+        out[((size_t)q * KT2 + mi) * 64 + lane] = w4;
       }
   return out;
 }
