@@ -1,0 +1,71 @@
+// Host-only check of the memory owners of vbt_amd/csrc/dev_mem.h, built with -fsanitize=address,undefined (tests/test_dev_mem_host.py).
+// It needs no device: the test hides every device, so each allocation fails the way it does on a machine without one, and an
+// allocation of 2^60 bytes fails on any machine.  What is checked is the owners' bookkeeping around failures, moves and destruction;
+// where an allocation does succeed (a visible device) the same statements hold with a buffer in hand.
+#include <cstdio>
+#include <cstdlib>
+#include <utility>
+
+#include "../../vbt_amd/csrc/dev_mem.h"
+
+using namespace vbt;
+
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
+
+template <class Buf>
+static int check_buf(const char* name) {
+  constexpr size_t HUGE_COUNT = (size_t)1 << 57;   // x 8 bytes
+  {
+    Buf empty;                                      // destruction of an empty buffer
+    CHECK(!empty && empty.get() == nullptr);
+  }
+  Buf a;
+  CHECK(a.alloc(HUGE_COUNT) != hipSuccess);         // a failed alloc leaves the buffer null
+  CHECK(!a && a.get() == nullptr);
+  const hipError_t e = a.alloc(16);
+  CHECK((e == hipSuccess) == (a.get() != nullptr));
+  double* const p = a.get();
+  Buf b(std::move(a));                              // a move leaves the source empty
+  CHECK(a.get() == nullptr && b.get() == p);
+  Buf c;
+  c = std::move(b);
+  CHECK(b.get() == nullptr && c.get() == p);
+  Buf& same = c;
+  c = std::move(same);                              // self-move keeps the buffer
+  CHECK(c.get() == p);
+  CHECK(c.alloc(HUGE_COUNT) != hipSuccess);         // a failed re-alloc frees what was held
+  CHECK(c.get() == nullptr);
+  a.reset();                                        // reset of a moved-from buffer
+  std::printf("ok %s %s\n", name, e == hipSuccess ? "allocated" : "no-device");
+  return 0;                                         // a, b, c: destruction of moved-from and empty buffers
+}
+
+static int check_mirror() {
+  Mirror m;
+  CHECK(m.bytes() == 0 && m.dev() == nullptr && m.host() == nullptr);
+  CHECK(m.reserve((size_t)1 << 60) != hipSuccess);
+  CHECK(m.bytes() == 0 && m.dev() == nullptr);      // the device half failed
+  const hipError_t e = m.reserve(4096);             // still usable after a failure
+  if (e == hipSuccess) {
+    CHECK(m.bytes() == 4096 && m.dev() && m.host());
+    unsigned char* const d = m.dev();
+    CHECK(m.reserve(1024) == hipSuccess && m.dev() == d && m.bytes() == 4096);   // never shrinks
+    CHECK(m.fetch(4096, nullptr) == hipSuccess);
+  } else {
+    CHECK(m.bytes() == 0 && m.dev() == nullptr && m.host() == nullptr);
+    CHECK(m.reserve(4096) != hipSuccess && m.bytes() == 0);
+  }
+  CHECK(m.reserve(0) == hipSuccess);                // nothing to grow
+  m.reset();
+  CHECK(m.bytes() == 0 && m.dev() == nullptr && m.host() == nullptr);
+  Mirror untouched;                                 // destruction of an empty mirror
+  std::printf("ok Mirror %s\n", e == hipSuccess ? "allocated" : "no-device");
+  return 0;
+}
+
+int main() {
+  std::setvbuf(stdout, nullptr, _IOLBF, 0);
+  if (check_buf<DevBuf<double>>("DevBuf")) return 1;
+  if (check_buf<PinnedBuf<double>>("PinnedBuf")) return 1;
+  return check_mirror();
+}

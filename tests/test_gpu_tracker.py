@@ -122,6 +122,71 @@ def test_ocsort_dropin_call_shape():
             assert np.array_equal(x.kf.x, y.kf.x)
 
 
+def test_the_two_read_back_paths_agree_frame_by_frame():
+    """last_output / trackers after every frame, read two ways: handle A (one clip, one frame per call) is the one-frame kernel, whose
+    packed block comes back with the call; handle B (two clips, the scene in clip 1) is the multi-clip kernel, read through a copy of the
+    clip's state.  Both equal each other and the numpy oracle, bit for bit.  Seed 0's first 40 frames (picked with the oracle): two
+    tracks die, up to 4 rows per frame, 7 frames without a detection (on those A is not stepped and reads through the state copy too)."""
+    from oracle import ocsort_np as oc
+    from vbt_amd.ocsort import MultiClipTracker
+    frames, tm = _random_scene(0)
+    frames, tm = frames[:40], tm[:40]
+    kw = dict(max_age=30, asso_func="diou", iou_threshold=0.1)
+    a, b, o = MultiClipTracker(1, 512, **kw), MultiClipTracker(2, 512, **kw), oc.OCSort(**kw)
+    want, most, deaths, alive = np.empty((0, 7)), 0, 0, set()
+    for d, t in zip(frames, tm):
+        da, ca, ta = _pack([[d]], [[t]])
+        db, cb, tb = _pack([[d[:0]], [d]], [[t], [t]])
+        a.update_frames(da, ca, ta)
+        b.update_frames(db, cb, tb)
+        if len(d):                                    # (an empty frame steps nothing: track.py:180-181)
+            want = o.update(d, [])
+        (oa, va), (ob, vb) = a.last_output(0), b.last_output(1)
+        assert np.array_equal(oa, ob) and np.array_equal(va, vb)
+        assert np.array_equal(oa, want)
+        kx = {k.id: k.kf.x.flatten() for k in o.trackers}
+        assert np.array_equal(va, np.array([kx[int(r[4]) - 1][4:6] for r in want]).reshape(-1, 2))
+        tka, tkb = a.trackers(0), b.trackers(1)
+        assert [k.id for k in tka] == [k.id for k in tkb] == [k.id for k in o.trackers]
+        for x, y, z in zip(tka, tkb, o.trackers):
+            assert np.array_equal(x.kf.x, y.kf.x) and np.array_equal(x.kf.x, z.kf.x)
+        most = max(most, len(oa))
+        deaths += len(alive - set(kx))
+        alive = set(kx)
+    assert most >= 2 and deaths >= 1                  # not a degenerate scene
+    assert b.status(0)["frame_count"] == 0 and b.rows(1) == a.rows(0)
+
+
+def test_host_detection_filter_at_the_gate():
+    """dets = dets[confs > det_thresh] of the host-provided detections, with confidences exactly at, one ulp below and one ulp above the
+    gate, through the one-frame kernel (F == 1) and the multi-frame kernel (F > 1).  Frame 4 has detections but none passes: the tracker is
+    still stepped, on no detections (frame_count counts it), as the reference's update() is."""
+    from oracle import ocsort_np as oc
+    from vbt_amd.ocsort import MultiClipTracker
+    g = 0.2
+    at, below, above = g, np.nextafter(g, 0.0), np.nextafter(g, 1.0)
+
+    def box(cx, cy, conf):
+        return [cx - 0.05, cy - 0.04, cx + 0.05, cy + 0.04, conf, 0.0]
+
+    confs = [(above, 0.9, at), (above, below, above), (0.9, above, below), (at, below, at), (above, above, 0.9), (above, at, above)]
+    frames = [np.array([box(0.2 + 0.01 * f, 0.3, c0), box(0.5, 0.5 + 0.01 * f, c1), box(0.8 - 0.01 * f, 0.7, c2)]) for f, (c0, c1, c2) in enumerate(confs)]
+    tm = (np.arange(6) + 1) / 30.0
+    kw = dict(det_thresh=g, max_age=30, min_hits=1, asso_func="diou", iou_threshold=0.1)       # min_hits 1: every matched track emits a row
+    want = oc.track_boxes(frames, tm, **kw)
+    one, many = MultiClipTracker(1, 512, **kw), MultiClipTracker(1, 512, **kw)
+    for d, t in zip(frames, tm):
+        one.update_frames(*_pack([[d]], [[t]]))
+    many.update_frames(*_pack([frames], [tm]))
+    ra, rb = one.rows(0), many.rows(0)
+    assert ra == rb
+    assert ra["id"] == want["id"] and len(ra["id"]) >= 6
+    for k in COLS:
+        assert np.array_equal(np.asarray(ra[k]), np.asarray(want[k])), k
+    assert one.status(0)["frame_count"] == many.status(0)["frame_count"] == 6
+    assert max(ra["id"]) == 3 and 4.0 / 30.0 not in ra["time"]      # a fourth track is never born: nothing at or below the gate gets through
+
+
 def test_velocity_tracker_all_34_reference_clips():
     from vbt_amd.velocity import analyze_rows
     main = np.load(os.path.join(GOLDEN, "dfs_ocsort_main.npz"))

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -16,6 +17,10 @@
 namespace vbt {
 
 void set_error(const char* fmt, ...);
+
+// The library's one device check: `device` is a visible HIP device - else VBT_ERR_HIP with "<fn>: HIP device %d not available (%d visible)
+// - no CPU fallback" set - and, unless set_current is false, the calling thread's current device from here on.
+int use_device(const char* fn, int device, bool set_current = true);
 
 // roctx ranges around the host-side enqueue of the path's three stages (detect incl. decode + NMS, track, clip close): with
 // VBT_ROCTX=1 the library loads librocprofiler-sdk-roctx.so at the first use and `rocprofv3 --marker-trace` shows
@@ -55,11 +60,11 @@ int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_f
                           uint8_t* dst_dev, int h, int w, hipStream_t st);
 
 // Slot close (vbt_pipeline_close_clips): the per-clip record close_pack_kernel writes, { int best_id, n_rows, n_phases, overflow ;
-// double phases[512][6] } (512 = the phases a clip keeps, tracker.hip MAXPH)
+// double phases[512][6] } (512 = the phases a clip keeps, tracker_state.h MAXPH; tracker.hip asserts the two agree)
 constexpr size_t CLOSED_HEAD_BYTES = 16 + 512 * 48;
 // clips[0..n): each in [0, n_clips), none twice, n >= 1 - else VBT_ERR_ARG with the error text set (fn: the caller's name)
 int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips);
-// Device part of vbt_pipeline_close_clips (tracker.hip), enqueue only, on st: export id + rep analysis of the listed clips (the kernels
+// Device part of vbt_pipeline_close_clips (tracker_analysis.hip), enqueue only, on st: export id + rep analysis of the listed clips (the kernels
 // of vbt_tracker_finish on the list), their records into head (pinned, [n_clips][CLOSED_HEAD_BYTES]) and their rows into out_rows
 // (device, [n_clips][rows_cap] 64-byte rows), then a fresh clip in every listed slot (vbt_tracker_reset_clips)
 int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <tuple>
 
+#include "dev_mem.h"
 #include "launchers.h"   // dev_common.h + the argument structs / tile constants of every kernel family + the launchers
 
 namespace vbt {
@@ -38,6 +39,16 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+int use_device(const char* fn, int device, bool set_current) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    set_error("%s: HIP device %d not available (%d visible) - no CPU fallback", fn, device, ndev);
+    return VBT_ERR_HIP;
+  }
+  if (set_current) VBT_HIP_CHECK(hipSetDevice(device));
+  return VBT_OK;
 }
 
 bool lds_opt_in(const void* fn, LdsOptIn* state) {
@@ -1052,12 +1063,7 @@ int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, 
   m->device = device;
   m->max_batch = max_batch;
   m->flags = flags;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    delete m;
-    set_error("vbt_model_create: HIP device %d not available (%d visible) - the HIP path has no CPU fallback", device, ndev);
-    return VBT_ERR_HIP;
-  }
+  if (int drc = use_device("vbt_model_create", device, /*set_current=*/false)) { delete m; return drc; }
   int rc = VBT_OK;
   auto fail = [&](int code) { vbt_model_destroy(m); return code; };
   if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return fail(VBT_ERR_HIP); }
@@ -1350,31 +1356,24 @@ extern "C" {
 int vbt_resize_frames(const uint8_t* src, int B, int H, int W, int src_on_device, uint8_t* dst, int h, int w, int dst_on_device,
                       int swap_rb, int device, void* stream) {
   if (!src || !dst || B < 1 || H < 1 || W < 1 || h < 1 || w < 1) { set_error("vbt_resize_frames: bad argument"); return VBT_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("vbt_resize_frames: HIP device %d not available (%d visible) - no CPU fallback", device, ndev);
-    return VBT_ERR_HIP;
-  }
-  VBT_HIP_CHECK(hipSetDevice(device));
+  if (int rc = use_device("vbt_resize_frames", device)) return rc;
   hipStream_t st = (hipStream_t)stream;
   size_t sb = (size_t)B * H * W * 3, db = (size_t)B * h * w * 3;
-  uint8_t *ds = nullptr, *dd = nullptr;
+  DevBuf<uint8_t> ds, dd;   // freed when the function returns: after the stream synchronisation, or - on an error - by a hipFree that waits
   const uint8_t* sp = src;
   uint8_t* dp = dst;
   if (!src_on_device) {
-    VBT_HIP_CHECK(hipMalloc((void**)&ds, sb));
-    VBT_HIP_CHECK(hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, st));
-    sp = ds;
+    VBT_HIP_CHECK(ds.alloc(sb));
+    VBT_HIP_CHECK(hipMemcpyAsync(ds.get(), src, sb, hipMemcpyHostToDevice, st));
+    sp = ds.get();
   }
   if (!dst_on_device) {
-    VBT_HIP_CHECK(hipMalloc((void**)&dd, db));
-    dp = dd;
+    VBT_HIP_CHECK(dd.alloc(db));
+    dp = dd.get();
   }
   hipError_t e = resize_frames_dev(sp, B, H, W, dp, h, w, swap_rb, 0, st) == VBT_OK ? hipSuccess : hipErrorLaunchFailure;
-  if (e == hipSuccess && !dst_on_device) e = hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !dst_on_device) e = hipMemcpyAsync(dst, dd.get(), db, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && (ds || dd)) e = hipStreamSynchronize(st);
-  if (ds) (void)hipFree(ds);
-  if (dd) (void)hipFree(dd);
   if (e != hipSuccess) { set_error("vbt_resize_frames failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   return VBT_OK;
 }

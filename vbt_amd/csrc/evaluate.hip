@@ -14,6 +14,7 @@
 // compaction and the two sums.  All counts are integers and every rate is one IEEE double division of two exactly representable
 // integers, so the curve points equal scikit-learn's bit for bit; AP / AUC differ from numpy's by the summation order only.
 #include "common.h"
+#include "dev_mem.h"
 #include "lap.h"
 
 #include <algorithm>
@@ -349,6 +350,17 @@ __global__ __launch_bounds__(EV_THREADS) void eval_curve_kernel(const float* sco
 
 using namespace vbt;
 
+// owner of the twelve arrays of a CurveWork; view is what the kernel takes
+struct CurveBufs {
+  DevBuf<unsigned long long> e0, e1;
+  DevBuf<int> tps, fps;
+  DevBuf<unsigned char> keep;
+  DevBuf<double> prec, rec, fpr, tpr;
+  DevBuf<float> pthr, rthr;
+  DevBuf<CurveHead> head;
+  CurveWork view{};
+};
+
 struct vbt_eval {
   int device = 0, max_batch = 0, rows_cap = 0;
   EvalTable tab{};
@@ -365,39 +377,26 @@ struct vbt_eval {
   hipEvent_t done = nullptr;        // end of the last call's kernels: a call on another stream waits for it (shared scratch and staging)
   bool done_used = false;
   int images_host = 0;
-  CurveWork work{};
+  CurveBufs work;
   int work_cap = -1;
 };
 
 namespace {
 
-int device_ok(const char* fn, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("%s: HIP device %d not available (%d visible) - no CPU fallback", fn, device, ndev);
-    return VBT_ERR_HIP;
-  }
-  return VBT_OK;
-}
-
-void work_free(CurveWork& w) {
-  (void)hipFree(w.e0); (void)hipFree(w.e1); (void)hipFree(w.tps); (void)hipFree(w.fps); (void)hipFree(w.keep); (void)hipFree(w.prec);
-  (void)hipFree(w.rec); (void)hipFree(w.pthr); (void)hipFree(w.fpr); (void)hipFree(w.tpr); (void)hipFree(w.rthr); (void)hipFree(w.head);
-  w = CurveWork{};
-}
-
-int work_alloc(CurveWork& w, int n) {
+int work_alloc(CurveBufs& w, int n) {
   const size_t m = (size_t)std::max(n, 1);
   hipError_t e = hipSuccess;
-  auto get = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-  get((void**)&w.e0, 8 * m); get((void**)&w.e1, 8 * m); get((void**)&w.tps, 4 * m); get((void**)&w.fps, 4 * m); get((void**)&w.keep, m);
-  get((void**)&w.prec, 8 * (m + 1)); get((void**)&w.rec, 8 * (m + 1)); get((void**)&w.pthr, 4 * m);
-  get((void**)&w.fpr, 8 * (m + 1)); get((void**)&w.tpr, 8 * (m + 1)); get((void**)&w.rthr, 4 * (m + 1)); get((void**)&w.head, sizeof(CurveHead));
+  auto get = [&](auto& buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
+  get(w.e0, m); get(w.e1, m); get(w.tps, m); get(w.fps, m); get(w.keep, m);
+  get(w.prec, m + 1); get(w.rec, m + 1); get(w.pthr, m);
+  get(w.fpr, m + 1); get(w.tpr, m + 1); get(w.rthr, m + 1); get(w.head, 1);
   if (e != hipSuccess) {
     set_error("hipMalloc failed for the curve workspace of %d rows: %s", n, hipGetErrorString(e));
-    work_free(w);
+    w = CurveBufs{};
     return VBT_ERR_HIP;
   }
+  w.view = CurveWork{w.e0.get(), w.e1.get(), w.tps.get(), w.fps.get(), w.keep.get(), w.prec.get(), w.rec.get(), w.pthr.get(),
+                     w.fpr.get(), w.tpr.get(), w.rthr.get(), w.head.get()};
   return VBT_OK;
 }
 
@@ -444,8 +443,7 @@ extern "C" {
 int vbt_eval_create(int device, int max_batch, int rows_cap, vbt_eval** out) {
   if (!out || max_batch < 1 || max_batch > 4096 || rows_cap < 1) { set_error("vbt_eval_create: bad argument"); return VBT_ERR_ARG; }
   *out = nullptr;
-  if (int rc = device_ok("vbt_eval_create", device)) return rc;
-  VBT_HIP_CHECK(hipSetDevice(device));
+  if (int rc = use_device("vbt_eval_create", device)) return rc;
   vbt_eval* e = new vbt_eval();
   e->device = device; e->max_batch = max_batch; e->rows_cap = rows_cap;
   e->tab.cap = rows_cap;
@@ -489,7 +487,6 @@ void vbt_eval_destroy(vbt_eval* e) {
     if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
   }
   if (e->done) (void)hipEventDestroy(e->done);
-  work_free(e->work);
   delete e;
 }
 
@@ -579,7 +576,7 @@ int vbt_eval_curves(vbt_eval* e, double iou_threshold, vbt_eval_summary* s, doub
   EvalState es;
   if (int rc = read_state(e, &es)) return rc;
   // the row count is read by the kernel from the device state: the table never leaves the device for this call
-  return curves_run(e->work, e->tab.score, e->tab.iou, &e->state->n_rows, 0, iou_threshold, e->last_stream, s, precision, recall,
+  return curves_run(e->work.view, e->tab.score, e->tab.iou, &e->state->n_rows, 0, iou_threshold, e->last_stream, s, precision, recall,
                     pr_thresholds, pr_cap, fpr, tpr, roc_thresholds, roc_cap);
 }
 
@@ -589,27 +586,23 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
   if (!s || n < 0 || (n > 0 && (!scores || !ious))) { set_error("vbt_eval_curves_from_table: bad argument"); return VBT_ERR_ARG; }
   for (int i = 0; i < n; i++)
     if (scores[i] != scores[i]) { set_error("vbt_eval_curves_from_table: score %d is NaN", i); return VBT_ERR_ARG; }
-  if (int rc = device_ok("vbt_eval_curves_from_table", device)) return rc;
-  VBT_HIP_CHECK(hipSetDevice(device));
-  CurveWork w{};
+  if (int rc = use_device("vbt_eval_curves_from_table", device)) return rc;
+  CurveBufs w;      // with ds and di freed when the function returns: curves_run ends with a synchronisation of its stream
   if (int rc = work_alloc(w, n)) return rc;
-  float* ds = nullptr;
-  double* di = nullptr;
-  int rc = VBT_OK;
+  DevBuf<float> ds;
+  DevBuf<double> di;
   const size_t m = (size_t)std::max(n, 1);
-  if (hipMalloc((void**)&ds, 4 * m) != hipSuccess || hipMalloc((void**)&di, 8 * m) != hipSuccess) {
+  if (ds.alloc(m) != hipSuccess || di.alloc(m) != hipSuccess) {
     set_error("vbt_eval_curves_from_table: hipMalloc failed for %d rows", n);
-    rc = VBT_ERR_HIP;
-  } else if (n > 0 && (hipMemcpy(ds, scores, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-                       hipMemcpy(di, ious, 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)) {
-    set_error("vbt_eval_curves_from_table: upload failed");
-    rc = VBT_ERR_HIP;
-  } else {
-    rc = curves_run(w, ds, di, nullptr, n, iou_threshold, nullptr, s, precision, recall, pr_thresholds, pr_cap, fpr, tpr, roc_thresholds, roc_cap);
+    return VBT_ERR_HIP;
   }
-  (void)hipFree(ds); (void)hipFree(di);
-  work_free(w);
-  return rc;
+  if (n > 0 && (hipMemcpy(ds.get(), scores, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(di.get(), ious, 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)) {
+    set_error("vbt_eval_curves_from_table: upload failed");
+    return VBT_ERR_HIP;
+  }
+  return curves_run(w.view, ds.get(), di.get(), nullptr, n, iou_threshold, nullptr, s, precision, recall, pr_thresholds, pr_cap, fpr, tpr,
+                    roc_thresholds, roc_cap);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include "common.h"
+#include "dev_mem.h"
 #include "yuv_kernels.h"
 
 namespace vbt {
@@ -88,31 +89,24 @@ extern "C" int vbt_resize_frames_yuv(const uint8_t* src, int B, int H, int W, in
   if (pix_fmt == VBT_PIX_RGB24) { set_error("vbt_resize_frames_yuv: VBT_PIX_RGB24 frames go through vbt_resize_frames"); return VBT_ERR_ARG; }
   if (!pix_fmt_is_yuv(pix_fmt)) { set_error("vbt_resize_frames_yuv: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
   if ((H & 1) || (W & 1)) { set_error("vbt_resize_frames_yuv: YUV 4:2:0 frames have even H and W, got %d x %d", H, W); return VBT_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("vbt_resize_frames_yuv: HIP device %d not available (%d visible) - no CPU fallback", device, ndev);
-    return VBT_ERR_HIP;
-  }
-  VBT_HIP_CHECK(hipSetDevice(device));
+  if (int rc = use_device("vbt_resize_frames_yuv", device)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t fb = (size_t)H * W * 3 / 2, sb = (size_t)B * fb, db = (size_t)B * h * w * 3;
   // every failure below goes through the one clean-up; rc keeps the error a callee already described
-  uint8_t *ds = nullptr, *dd = nullptr;
+  DevBuf<uint8_t> ds, dd;
   hipError_t e = hipSuccess;
   int rc = VBT_OK;
   if (!src_on_device) {
-    e = hipMalloc((void**)&ds, sb);
-    if (e == hipSuccess) e = hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, st);
+    e = ds.alloc(sb);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds.get(), src, sb, hipMemcpyHostToDevice, st);
   }
-  if (e == hipSuccess && !dst_on_device) e = hipMalloc((void**)&dd, db);
-  if (e == hipSuccess) rc = resize_frames_yuv_dev(ds ? ds : src, B, H, W, pix_fmt, fb, (size_t)H * W, 0, dd ? dd : dst, h, w, st);
-  if (e == hipSuccess && rc == VBT_OK && !dst_on_device) e = hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, st);
-  if (ds || dd) {   // (also after a failure: a copy may still be in flight on the buffers freed next)
+  if (e == hipSuccess && !dst_on_device) e = dd.alloc(db);
+  if (e == hipSuccess) rc = resize_frames_yuv_dev(ds ? ds.get() : src, B, H, W, pix_fmt, fb, (size_t)H * W, 0, dd ? dd.get() : dst, h, w, st);
+  if (e == hipSuccess && rc == VBT_OK && !dst_on_device) e = hipMemcpyAsync(dst, dd.get(), db, hipMemcpyDeviceToHost, st);
+  if (ds || dd) {   // (also after a failure: a copy may still be in flight on the buffers freed when the function returns)
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
   }
-  if (ds) (void)hipFree(ds);
-  if (dd) (void)hipFree(dd);
   if (e != hipSuccess) { set_error("vbt_resize_frames_yuv failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   return rc;
 }

@@ -1,4 +1,4 @@
-// Wave-parallel linear assignment with scipy's tie rule, shared by the OC-SORT tracker (tracker.hip) and the detector
+// Wave-parallel linear assignment with scipy's tie rule, shared by the OC-SORT tracker (ocsort_step.h) and the detector
 // evaluation (evaluate.hip).  Device code only; one wavefront (64 lanes) per problem.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -473,12 +473,7 @@ int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max
   MjTables tab;
   build_tables(H, W, quality, &tab);
   if (!dct_table_ok() || tab.header[0] != 0xFF) { set_error("vbt_mjpeg_create: the built-in tables fail their self-check"); return VBT_ERR_STATE; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("vbt_mjpeg_create: HIP device %d not available (%d visible) - no CPU fallback", device, ndev);
-    return VBT_ERR_HIP;
-  }
-  VBT_HIP_CHECK(hipSetDevice(device));
+  if (int rc = use_device("vbt_mjpeg_create", device)) return rc;
   vbt_mjpeg* m = new vbt_mjpeg();
   m->device = device; m->H = H; m->W = W; m->fmt = pix_fmt; m->quality = quality; m->max_batch = max_batch;
   m->MW = (W + 15) / 16; m->MH = (H + 15) / 16;

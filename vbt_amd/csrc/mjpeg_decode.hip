@@ -215,12 +215,7 @@ int vbt_mjpeg_decoder_create(int device, int H, int W, int max_batch, vbt_mjpeg_
   *out = nullptr;
   if (H < 1 || W < 1 || H > JPEG_MAX_SIDE || W > JPEG_MAX_SIDE) { set_error("vbt_mjpeg_decoder_create: frames of 1..16384 pixels a side, got %d x %d", H, W); return VBT_ERR_ARG; }
   if (max_batch < 1 || max_batch > MJD_MAX_BATCH) { set_error("vbt_mjpeg_decoder_create: max_batch %d outside 1..%d", max_batch, MJD_MAX_BATCH); return VBT_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("vbt_mjpeg_decoder_create: HIP device %d not available (%d visible) - no CPU fallback", device, ndev);
-    return VBT_ERR_HIP;
-  }
-  VBT_HIP_CHECK(hipSetDevice(device));
+  if (int rc = use_device("vbt_mjpeg_decoder_create", device)) return rc;
   vbt_mjpeg_decoder* m = new vbt_mjpeg_decoder();
   m->device = device; m->H = H; m->W = W; m->max_batch = max_batch;
   m->frame_blocks = (size_t)jpeg_max_blocks(H, W);

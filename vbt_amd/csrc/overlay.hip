@@ -99,15 +99,6 @@ struct vbt_overlay {
 
 namespace {
 
-int overlay_device_ok(const char* fn, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("%s: HIP device %d not available (%d visible) - no CPU fallback", fn, device, ndev);
-    return VBT_ERR_HIP;
-  }
-  return VBT_OK;
-}
-
 // the refusals of vbt_overlay_set_rows that need no handle and no device
 int check_rows(const OverlayRow* rows, int n, double fps) {
   if (n < 0 || (n > 0 && !rows)) { set_error("vbt_overlay_set_rows: bad argument (n %d, rows %p)", n, (const void*)rows); return VBT_ERR_ARG; }
@@ -158,7 +149,7 @@ int vbt_overlay_create(int device, int H, int W, int pix_fmt, const vbt_overlay_
   if (p.thickness < 0 || p.thickness > 1024) { set_error("vbt_overlay_create: thickness %d outside 0..1024", p.thickness); return VBT_ERR_ARG; }
   if (p.radius < 0 || p.radius > 16384) { set_error("vbt_overlay_create: radius %d outside 0..16384", p.radius); return VBT_ERR_ARG; }
   if (p.label_scale < 1 || p.label_scale > 64) { set_error("vbt_overlay_create: label_scale %d outside 1..64", p.label_scale); return VBT_ERR_ARG; }
-  if (int rc = overlay_device_ok("vbt_overlay_create", device)) return rc;
+  if (int rc = use_device("vbt_overlay_create", device, /*set_current=*/false)) return rc;
   vbt_overlay* o = new vbt_overlay();
   o->device = device; o->H = H; o->W = W; o->fmt = pix_fmt; o->prm = p;
   const int r = p.rgb[0], g = p.rgb[1], b = p.rgb[2];

@@ -679,12 +679,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
     set_error("vbt_pipeline_create: n_slots >= 1, n_clips >= 0, rows_cap >= 1, depth 0..8, group 0..8 required");
     return VBT_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device >= ndev) {
-    set_error("vbt_pipeline_create: HIP device %d not available (%d visible) - the HIP path has no CPU fallback", prm->device, ndev);
-    return VBT_ERR_HIP;
-  }
-  VBT_HIP_CHECK(hipSetDevice(prm->device));
+  if (int rc = use_device("vbt_pipeline_create", prm->device)) return rc;
   vbt_pipeline* p = new vbt_pipeline();
   p->prm = *prm;
   p->n = prm->n_slots;
