@@ -658,6 +658,21 @@ int vbt_mjpeg_read(vbt_mjpeg* m, uint8_t* host_buf, uint64_t cap, uint64_t* offs
  *   frame is then not walked at all);  5 a marker's m is not its index mod 8.
  * Codes 1..3 end their interval: the blocks it had not reached keep level 0 (mid-grey for a first block, since predictors restart
  * per interval).  A damaged scan spoils its own frame only; what such a frame shows is deterministic, but not part of the contract.
+ * Two ways through an interval give these levels and this status, bit for bit (vbt_mjpeg_decoder_set_entropy):
+ *   INTERVAL  one lane walks the interval.  Fast when a frame has many intervals (this project's export: one per MCU row), one lane
+ *     per frame when it has no restart markers - what ffmpeg, cameras and Pillow write.
+ *   SYNC  one workgroup per interval.  The interval is cut into subsequences of S raw bytes (subseq_bytes, a power of two); lane i
+ *     owns the symbols that begin in its S bytes, 256 lanes (a chunk) at a time, the chunks in order.  A lane does not know the
+ *     state (raw bit position, block slot in the MCU, zigzag index) at its first byte: it guesses "a block begins here", walks, and
+ *     then takes its left neighbour's exit state as its entry, round after round, until no entry changes.  Lanes 0 .. r - 1 are final
+ *     after round r, so a chunk takes at most 257 rounds - the loop's bound; real scans synchronise within a few symbols, and the
+ *     rounds a batch needed are reported (vbt_mjpeg_decode_entropy_info).  Prefix sums over block counts and DC differences then give
+ *     every lane its block number and predictors, and a second walk stores the levels.  A walk from a guess meets codes no table
+ *     holds and indices above 63 all the time; it records them and goes on.  When a lane with a true entry recorded one before the
+ *     interval's last block, or the bits end before the blocks do, nothing of that chunk is stored in parallel: ONE lane finishes the
+ *     interval from the chunk's entry state with the statements of INTERVAL, so a damaged scan is decoded exactly as before.
+ *   AUTO (the default) takes SYNC for a batch in which some frame has scan bytes / intervals >= auto_min_interval_bytes
+ *     (vbt_mjpeg_decoder_get_entropy; measured, profiles/mjpeg_decode.md), INTERVAL otherwise.
  *
  * Reconstruction, int32 throughout (wrapping; >> arithmetic):
  *   Dequantise: c = level Q, natural order.
@@ -708,6 +723,14 @@ int vbt_mjpeg_decode(vbt_mjpeg_decoder* d, const uint8_t* host_bytes, const uint
 /* The scan status of every frame of the last batch (B words, codes above): ONE synchronisation of `stream`, one copy.
  * VBT_ERR_STATE: nothing has been decoded yet. */
 int vbt_mjpeg_decode_status(vbt_mjpeg_decoder* d, int32_t* status, void* stream);
+#define VBT_MJPEG_ENTROPY_AUTO     0   /* default */
+#define VBT_MJPEG_ENTROPY_INTERVAL 1   /* one lane per restart interval */
+#define VBT_MJPEG_ENTROPY_SYNC     2   /* subsequences that synchronise */
+/* Host only, takes effect at the next vbt_mjpeg_decode.  subseq_bytes: 0 = the default, else a power of two in 4..4096.
+ * VBT_ERR_ARG otherwise, handle unchanged. */
+int vbt_mjpeg_decoder_set_entropy(vbt_mjpeg_decoder* d, int mode, int subseq_bytes);
+/* The mode, the subsequence size SYNC would use (the default resolved) and AUTO's threshold; any pointer may be NULL. */
+int vbt_mjpeg_decoder_get_entropy(vbt_mjpeg_decoder* d, int* mode, int* subseq_bytes, int* auto_min_interval_bytes);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,10 @@ int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
  * gives the six stage times of the last batch in milliseconds: H2D copy, memsets, marker scan, entropy decode, IDCT, upsampling +
  * colour.  VBT_ERR_STATE without the variable or before the first decode. */
 int vbt_mjpeg_decode_stage_ms(vbt_mjpeg_decoder* d, float* ms6);
+/* How the last batch's entropy stage ran: info4 = { path taken (VBT_MJPEG_ENTROPY_INTERVAL or _SYNC), subseq_bytes used (0 on
+ * INTERVAL), the most rounds any chunk took, intervals finished by the single lane }.  One synchronisation of `stream`, one copy.
+ * VBT_ERR_STATE before the first decode. */
+int vbt_mjpeg_decode_entropy_info(vbt_mjpeg_decoder* d, int32_t* info4, void* stream);
 
 #ifdef __cplusplus
 }

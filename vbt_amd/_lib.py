@@ -193,6 +193,9 @@ _SIGS = {
     "vbt_mjpeg_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "vbt_mjpeg_decode_status": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vbt_mjpeg_decode_stage_ms": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "vbt_mjpeg_decoder_set_entropy": (c_int, [c_void_p, c_int, c_int]),
+    "vbt_mjpeg_decoder_get_entropy": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "vbt_mjpeg_decode_entropy_info": (c_int, [c_void_p, c_void_p, c_void_p]),
 }
 
 

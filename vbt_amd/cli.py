@@ -2,9 +2,12 @@
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
+                            [--mjpeg_entropy auto|interval|sync]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
-      import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it); any source
+      import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it;
+      --mjpeg_entropy picks how its scans are entropy-decoded - one lane per restart interval, subsequences that synchronise (for files
+      without restart markers: ffmpeg, cameras, Pillow), or auto by interval length - with the same frames either way); any source
       resolution (resized on the GPU like odt.py:10-19).  Writes
       {video}_id{N}_{model}.pkl.gz with the reference's columns, sort order and retained row labels.
       --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
@@ -24,7 +27,7 @@
       copied back.  Its frame rate is fps / frame_stride, so the export plays in real time - a second deliberate difference: the
       reference writes every 16th frame at the source's full fps (track.py:153-154,166), which plays 16 times too fast.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
-                              [--video_format raw|mjpeg] [--video_quality 85]
+                              [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync]
       the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn).
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
@@ -84,18 +87,20 @@ class _LiveReps:
         self.shown = lines
 
 
-def _open_source(s, pix_fmt, size):
+def _open_source(s, pix_fmt, size, mjpeg_entropy="auto"):
     """One SRC of `track` as the clip array of its pixel format: a .npy stack (no --size) or a headerless raw video file."""
     from .rawvideo import open_raw
     if not os.path.isfile(s):
         raise FileNotFoundError(s)                                       # reference track.py:89-90
+    if mjpeg_entropy != "auto" and not _is_avi(s):
+        raise click.UsageError(f"{s}: --mjpeg_entropy {mjpeg_entropy} is about decoding an .avi source and does not apply to this one")
     if _is_avi(s):
         if size is not None or pix_fmt != "rgb24":
             raise click.UsageError(f"{s}: an .avi source carries its own frame size and decodes to RGB: --size and --pix_fmt {pix_fmt} do not apply")
         from ._lib import VbtError
         from .mjpeg import AviClip
         try:
-            return AviClip(s)
+            return AviClip(s, entropy=mjpeg_entropy)
         except (ValueError, VbtError) as e:
             raise click.ClickException(str(e))
     if size is not None:
@@ -157,7 +162,10 @@ def _raw_size(pix_fmt, size):
 @click.option("--video_format", default="raw", show_default=True, type=click.Choice(["raw", "mjpeg"]),
               help="raw: the drawn frames as they are; mjpeg: {video}.avi, JPEG-encoded on the GPU, playing at fps / frame_stride.")
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality):
+@click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
+              help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality,
+          mjpeg_entropy):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     fps_given = _fps_given()
@@ -167,10 +175,10 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality, fps_given)
+                                 video_format, video_quality, fps_given, mjpeg_entropy)
     default_fps = fps
     for s in src:
-        frames = _open_source(s, pix_fmt, size)
+        frames = _open_source(s, pix_fmt, size, mjpeg_entropy)
         fps = _source_fps(frames, default_fps, fps_given)
         mjpeg = video_dir is not None and video_format == "mjpeg"
         video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
@@ -239,7 +247,7 @@ def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, 
 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
-                      video_format="raw", video_quality=85, fps_given=True):
+                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto"):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -247,7 +255,7 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     sources, error = [], None
     for s in src:
         try:
-            sources.append(_open_source(s, pix_fmt, size))
+            sources.append(_open_source(s, pix_fmt, size, mjpeg_entropy))
         except (FileNotFoundError, click.ClickException) as e:
             error = e
             break
@@ -282,7 +290,9 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
 @click.option("--video_format", default="raw", show_default=True, type=click.Choice(["raw", "mjpeg"]),
               help="raw: the drawn frames as they are; mjpeg: {video}.avi, JPEG-encoded on the GPU, playing at fps / frame_stride.")
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
-def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality):
+@click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
+              help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
+def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality, mjpeg_entropy):
     """Draw the boxes, ids and bar paths of a stored DataFrame into the frames of its clip (what `track --video_dir` writes)."""
     import pandas as pd
     size = _raw_size(pix_fmt, size)
@@ -290,7 +300,7 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
         raise click.UsageError("--frame_stride must be at least 1")
     if not os.path.isfile(dataframe):
         raise FileNotFoundError(dataframe)
-    frames = _open_source(src, pix_fmt, size)
+    frames = _open_source(src, pix_fmt, size, mjpeg_entropy)
     fps = _source_fps(frames, fps, _fps_given())
     df = pd.read_pickle(dataframe)
     n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size)

@@ -5,11 +5,14 @@
 //   jpeg_symbol          one Huffman symbol: an 8-bit look-up table, then canonical maxcode / valoff for lengths 9..16
 //   jpeg_decode_block    one block: DC difference + AC run / size pairs into 64 int16 levels, natural order
 //   jpeg_decode_interval the MCUs of one restart interval
+//   jpeg_sync_walk       one subsequence of an interval from a (possibly guessed) state: the lane's work in the decode by subsequences
+//                        that synchronise; jpeg_sync_cold: the guess; jpeg_decode_rest: one lane finishes an interval from a true state
 //   jpeg_idct_islow      dequantised coefficients -> 64 samples (the "islow" integer IDCT)
 //   jpeg_chroma_at       one chroma sample at full resolution ("fancy" triangle upsampling); jpeg_ycc_rgb: the colour tables
 // Every loop is bounded by a count known before it starts (MCUs of the interval, 64 coefficients, 16 code lengths, 7 bytes of a
-// refill); none is bounded by the data.  A read past the interval's end, a code no table holds and a coefficient index above 63 each
-// return a status and end the interval.  Nothing is read outside [start, end) of the scan or written outside the frame's levels.
+// refill, the 8 S + 32 symbols of a subsequence of S bytes); none is bounded by the data.  A read past the interval's end, a code no
+// table holds and a coefficient index above 63 each return a status and end the interval.  Nothing is read outside [start, end) of
+// the scan or written outside the frame's levels.
 #pragma once
 #include <stdint.h>
 
@@ -138,26 +141,14 @@ VBT_HD inline int jpeg_symbol(JpegBits& b, const JpegHuff& h, int* st) {
 
 VBT_HD inline int jpeg_extend(uint32_t r, int s) { return r < (1u << (s - 1)) ? (int)r - (1 << s) + 1 : (int)r; }   // 1 <= s <= 16
 
-// one block into out[64] (natural order; the caller zeroed it); *pred: the component's DC predictor
-VBT_HD inline int jpeg_decode_block(JpegBits& b, const JpegHuff& dc, const JpegHuff& ac, int* pred, int16_t* out) {
+// the AC coefficients of one block from zigzag index k (1..63) on, into out[64]
+VBT_HD inline int jpeg_decode_ac(JpegBits& b, const JpegHuff& ac, int k, int16_t* out) {
   int st = JPEG_ST_OK;
-  jpeg_bits_fill(b);
-  int s = jpeg_symbol(b, dc, &st);
-  if (s < 0) return st;
-  if (s > 16) return JPEG_ST_BAD_CODE;
-  if (s) {
-    const uint32_t r = jpeg_bits_peek(b, s);
-    if (!jpeg_bits_skip(b, s)) return JPEG_ST_OVERRUN;
-    *pred = (int)((uint32_t)*pred + (uint32_t)jpeg_extend(r, s));
-  }
-  out[0] = (int16_t)*pred;
-  int k = 1;
   for (int i = 1; i < 64 && k < 64; i++) {
     jpeg_bits_fill(b);
     const int rs = jpeg_symbol(b, ac, &st);
     if (rs < 0) return st;
-    const int r = rs >> 4;
-    s = rs & 15;
+    const int r = rs >> 4, s = rs & 15;
     if (s) {
       k += r;
       if (k > 63) return JPEG_ST_BAD_INDEX;
@@ -172,6 +163,22 @@ VBT_HD inline int jpeg_decode_block(JpegBits& b, const JpegHuff& dc, const JpegH
     }
   }
   return JPEG_ST_OK;
+}
+
+// one block into out[64] (natural order; the caller zeroed it); *pred: the component's DC predictor
+VBT_HD inline int jpeg_decode_block(JpegBits& b, const JpegHuff& dc, const JpegHuff& ac, int* pred, int16_t* out) {
+  int st = JPEG_ST_OK;
+  jpeg_bits_fill(b);
+  int s = jpeg_symbol(b, dc, &st);
+  if (s < 0) return st;
+  if (s > 16) return JPEG_ST_BAD_CODE;
+  if (s) {
+    const uint32_t r = jpeg_bits_peek(b, s);
+    if (!jpeg_bits_skip(b, s)) return JPEG_ST_OVERRUN;
+    *pred = (int)((uint32_t)*pred + (uint32_t)jpeg_extend(r, s));
+  }
+  out[0] = (int16_t)*pred;
+  return jpeg_decode_ac(b, ac, 1, out);
 }
 
 // restart interval k of a frame: scan[start .. end) -> the levels of its MCUs (levels: the frame's, jpeg_layout().blocks x 64, zeroed)
@@ -192,6 +199,218 @@ VBT_HD inline int jpeg_decode_interval(const JpegDesc& d, const JpegLayout& L, c
         if (st) return st;
       }
     }
+  }
+  return JPEG_ST_OK;
+}
+
+// ---- subsequences that synchronise (include/vbt_hip.h, "Entropy decoding"): an interval scan[start, end) is cut into subsequences
+// of S raw bytes; lane i owns the symbols that BEGIN in bytes [start + i S, start + (i + 1) S).  The decoder's state at a symbol
+// boundary is (p, u, k): p the raw byte and bit of the next unread bit (a stuffed FF 00 is named by its FF), u the block slot inside
+// the MCU (0 .. hs vs + 1; 0 for grey), k the zigzag index (0: a DC size comes next).  A lane that does not know its state guesses
+// (jpeg_sync_cold), walks, and takes its left neighbour's exit as its next entry until no entry changes: a walk is a pure function
+// of its entry and the bytes, so lanes 0 .. r - 1 are final after round r.  A walk from a guess meets bad codes all the time; it
+// records where the first one was and goes on by a fixed rule.  A chunk in which a lane with a true entry recorded one before the
+// interval's last block is finished by one lane with the statements of jpeg_decode_block (jpeg_decode_rest).
+struct JpegSyncState {
+  uint32_t pos;          // raw byte that holds the next unread bit (end: no bit is left)
+  uint32_t buk;          // bit inside it, from the top (0..7) | u << 3 | k << 8
+};
+VBT_HD inline bool jpeg_sync_same(const JpegSyncState& a, const JpegSyncState& b) { return a.pos == b.pos && a.buk == b.buk; }
+
+constexpr uint32_t JPEG_SYNC_NONE = 0xFFFFFFFFu;
+
+struct JpegSyncWalk {
+  JpegSyncState exit;
+  uint32_t blocks;       // blocks completed
+  uint32_t dc[3];        // per component: the wrapping sum of the DC differences read
+  uint32_t bad_at;       // blocks completed when the first status was recorded; JPEG_SYNC_NONE: none was
+};
+
+VBT_HD inline int jpeg_blocks_per_mcu(const JpegDesc& d) { return d.ncomp == 1 ? 1 : d.hs * d.vs + 2; }
+// blocks of restart interval k
+VBT_HD inline uint32_t jpeg_interval_blocks(const JpegDesc& d, int k) {
+  const int m0 = k * d.ri, nm = d.mcus - m0 < d.ri ? d.mcus - m0 : d.ri;
+  return (uint32_t)nm * (uint32_t)jpeg_blocks_per_mcu(d);
+}
+VBT_HD inline int jpeg_slot_component(const JpegDesc& d, int u) { const int hv = d.hs * d.vs; return u < hv ? 0 : u - hv + 1; }
+// the block of slot u of MCU (my, mx), by the arithmetic of jpeg_decode_interval
+VBT_HD inline uint32_t jpeg_slot_block(const JpegDesc& d, const JpegLayout& L, int my, int mx, int u) {
+  const int c = jpeg_slot_component(d, u), h = c == 0 ? d.hs : 1, v = c == 0 ? d.vs : 1, j = c == 0 ? u : 0;
+  return L.boff[c] + (uint32_t)(my * v + j / h) * (uint32_t)L.bw[c] + (uint32_t)(mx * h + j % h);
+}
+
+// the guess of a lane whose first byte is scan[pos], pos > start: a block begins there - behind the 00 if the byte is a stuffed one
+VBT_HD inline JpegSyncState jpeg_sync_cold(const uint8_t* scan, uint32_t pos) {
+  JpegSyncState s;
+  s.pos = scan[pos] == 0 && scan[pos - 1] == 0xFF ? pos + 1 : pos;
+  s.buk = 0;
+  return s;
+}
+
+// jpeg_bits_fill, but only bytes that begin before lim (lim <= b.end); returns the bits it added.  jpeg_bits_fill_to, then
+// jpeg_bits_fill, leaves in b what jpeg_bits_fill alone leaves
+VBT_HD inline int jpeg_bits_fill_to(JpegBits& b, uint32_t lim) {
+  int added = 0;
+  for (int i = 0; i < 8; i++) {
+    if (b.n > 56 || b.pos >= lim) break;
+    const uint32_t v = b.p[b.pos++];
+    if (v == 0xFF) {
+      if (b.pos < b.end && b.p[b.pos] == 0) b.pos++;
+      else { b.pos = b.end; break; }
+    }
+    b.acc |= (uint64_t)v << (56 - b.n);
+    b.n += 8;
+    added += 8;
+  }
+  return added;
+}
+
+// The symbols that begin before raw byte `limit` (<= end), from state `in`, at most max_syms of them (8 S + 32 covers a subsequence
+// of S bytes: every symbol takes a bit).  huff: the frame's dc[0], dc[1], ac[0], ac[1].  Bits are read up to `end` under the rules
+// of JpegBits and with its statements, so a walk from a true state sees what jpeg_decode_block sees.  A status is recorded, not
+// raised: an unmatched code consumes up to 16 bits and the walk goes on, an index above 63 ends the block, a DC size above 16 counts
+// as 0; when the bits run out the walk ends at `end`.
+// WRITE: the levels are stored as jpeg_decode_block stores them.  n0: the interval's blocks completed before `in` (the block `in`
+// lies in); pred: the predictors there; the walk stops behind block nblocks - 1 of the interval, whose first MCU is m0, and at a status.
+template <bool WRITE>
+VBT_HD inline JpegSyncWalk jpeg_sync_walk(const JpegDesc& d, const JpegLayout& L, const JpegHuff* huff, const uint8_t* scan, uint32_t end, JpegSyncState in,
+                                          uint32_t limit, int max_syms, int m0, uint32_t n0, uint32_t nblocks, const uint32_t* pred, int16_t* levels) {
+  JpegSyncWalk w;
+  w.exit = in; w.blocks = 0; w.dc[0] = w.dc[1] = w.dc[2] = 0; w.bad_at = JPEG_SYNC_NONE;
+  if (in.pos >= limit) return w;
+  if (WRITE && n0 >= nblocks) return w;
+  const int bpm = jpeg_blocks_per_mcu(d);
+  int u = (int)(in.buk >> 3) & 31, k = (int)(in.buk >> 8) & 63;
+  if (u >= bpm) u = 0;
+  uint32_t pr[3] = {0, 0, 0};
+  int mx = 0, my = 0;
+  int16_t* out = levels;
+  if (WRITE) {
+    u = (int)(n0 % (uint32_t)bpm);                                   // (what a true state holds; from n0, so that the MCU stays inside the interval whatever `in` is)
+    pr[0] = pred[0]; pr[1] = pred[1]; pr[2] = pred[2];
+    const int mcu = m0 + (int)(n0 / (uint32_t)bpm);
+    my = mcu / d.MW; mx = mcu % d.MW;
+    out = levels + (size_t)jpeg_slot_block(d, L, my, mx, u) * 64;
+  }
+  JpegBits b;
+  jpeg_bits_init(b, scan, in.pos, end);
+  int before = jpeg_bits_fill_to(b, limit);                          // bits of b.acc out of bytes that begin before limit
+  bool past = b.pos >= limit;
+  uint32_t lpos = b.pos;                                             // once past: the first raw byte that was not counted in `before`
+  if (in.buk & 7) { jpeg_bits_skip(b, (int)(in.buk & 7)); before -= (int)(in.buk & 7); }
+  for (int it = 0; it < max_syms; it++) {
+    if (!past) {
+      before += jpeg_bits_fill_to(b, limit);
+      past = b.pos >= limit;
+      lpos = b.pos;
+    }
+    if (before <= 0 || b.n == 0) break;
+    jpeg_bits_fill(b);
+    const int n_was = b.n, c = jpeg_slot_component(d, u);
+    int st = JPEG_ST_OK;
+    bool done = false;
+    if (k == 0) {
+      int s = jpeg_symbol(b, huff[d.td[c] & 1], &st);
+      if (s < 0) {
+        if (b.n) jpeg_bits_skip(b, b.n < 16 ? b.n : 16);
+      } else {
+        if (s > 16) { st = JPEG_ST_BAD_CODE; s = 0; }
+        bool have = true;
+        uint32_t diff = 0;
+        if (s) {
+          const uint32_t r = jpeg_bits_peek(b, s);
+          if (jpeg_bits_skip(b, s)) diff = (uint32_t)jpeg_extend(r, s);
+          else { st = JPEG_ST_OVERRUN; have = false; }
+        }
+        if (have) {
+          w.dc[0] += c == 0 ? diff : 0; w.dc[1] += c == 1 ? diff : 0; w.dc[2] += c == 2 ? diff : 0;   // (no runtime index: registers)
+          if (WRITE) {
+            pr[0] += c == 0 ? diff : 0; pr[1] += c == 1 ? diff : 0; pr[2] += c == 2 ? diff : 0;
+            out[0] = (int16_t)(int)(c == 0 ? pr[0] : c == 1 ? pr[1] : pr[2]);
+          }
+          k = 1;
+        }
+      }
+    } else {
+      const int rs = jpeg_symbol(b, huff[2 + (d.ta[c] & 1)], &st);
+      if (rs < 0) {
+        if (b.n) jpeg_bits_skip(b, b.n < 16 ? b.n : 16);
+      } else {
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+          k += r;
+          if (k > 63) { st = JPEG_ST_BAD_INDEX; done = true; }
+          else {
+            const uint32_t v = jpeg_bits_peek(b, s);
+            if (!jpeg_bits_skip(b, s)) st = JPEG_ST_OVERRUN;
+            else {
+              if (WRITE) out[jpeg_zigzag(k)] = (int16_t)jpeg_extend(v, s);
+              k++;
+              done = k > 63;
+            }
+          }
+        } else if (r == 15) {
+          k += 16;
+          done = k > 63;
+        } else {
+          done = true;                                               // EOB
+        }
+      }
+    }
+    before -= n_was - b.n;
+    if (st && w.bad_at == JPEG_SYNC_NONE) w.bad_at = w.blocks;
+    if (WRITE && st) break;
+    if (done) {
+      w.blocks++;
+      k = 0;
+      u = u + 1 == bpm ? 0 : u + 1;
+      if (WRITE) {
+        if (n0 + w.blocks >= nblocks) break;
+        if (u == 0 && ++mx == d.MW) { mx = 0; my++; }
+        out = levels + (size_t)jpeg_slot_block(d, L, my, mx, u) * 64;
+      }
+    }
+  }
+  // the raw position of the next unread bit
+  uint32_t q = end;
+  int over = 0;
+  if (b.n == 0 && b.pos >= b.end) {
+    // every bit of the interval is used up
+  } else if (past && before <= 0) {
+    q = lpos;
+    over = -before;                                                  // bits used out of the bytes from lpos on: whole data bytes, all below end
+    for (int i = 0; i < 8 && over >= 8; i++) {
+      q += q < end && scan[q] == 0xFF ? 2 : 1;
+      over -= 8;
+    }
+    if (q >= end) { q = end; over = 0; }
+  } else {
+    w.bad_at = 0;                                                    // (not reached: max_syms symbols without passing limit)
+  }
+  w.exit.pos = q;
+  w.exit.buk = (uint32_t)(over & 7) | (uint32_t)u << 3 | (uint32_t)k << 8;
+  return w;
+}
+
+// One lane finishes restart interval kint from the true state `in`: n0 blocks of the interval are complete, the predictors are
+// pred[3].  The rest of the block `in` lies in, then whole blocks, with the statements and the status of jpeg_decode_interval.
+VBT_HD inline int jpeg_decode_rest(const JpegDesc& d, const JpegLayout& L, const uint8_t* scan, uint32_t end, int kint, JpegSyncState in, uint32_t n0,
+                                   const uint32_t* pred, int16_t* levels) {
+  JpegBits b;
+  jpeg_bits_init(b, scan, in.pos < end ? in.pos : end, end);
+  if (in.buk & 7) {
+    jpeg_bits_fill(b);
+    if (!jpeg_bits_skip(b, (int)(in.buk & 7))) return JPEG_ST_OVERRUN;
+  }
+  int pr[3] = {(int)pred[0], (int)pred[1], (int)pred[2]};
+  const int m0 = kint * d.ri, bpm = jpeg_blocks_per_mcu(d), k = (int)(in.buk >> 8) & 63;
+  const uint32_t nblocks = jpeg_interval_blocks(d, kint);
+  for (uint32_t n = n0; n < nblocks; n++) {
+    const int mcu = m0 + (int)(n / (uint32_t)bpm), u = (int)(n % (uint32_t)bpm), c = jpeg_slot_component(d, u);
+    int16_t* out = levels + (size_t)jpeg_slot_block(d, L, mcu / d.MW, mcu % d.MW, u) * 64;
+    const JpegHuff& ac = d.ac[d.ta[c] & 1];
+    const int st = n == n0 && k ? jpeg_decode_ac(b, ac, k, out) : jpeg_decode_block(b, d.dc[d.td[c] & 1], ac, &pr[c], out);
+    if (st) return st;
   }
   return JPEG_ST_OK;
 }

@@ -6,6 +6,9 @@
 //     sum, positions into the frame's ordered interval table; count and m = index mod 8 checked against the descriptor.
 //   mjpegd_entropy_kernel  grid (groups of 64 intervals, frame), one lane per restart interval (jpeg_core.h: jpeg_decode_interval);
 //     the non-zero levels go, int16 in natural order, into the levels scratch (128 B per block) that a memset cleared.
+//   mjpegd_entropy_sync_kernel  in its place (vbt_mjpeg_decoder_set_entropy; AUTO: when a frame's intervals are long): grid (interval,
+//     frame), one workgroup per restart interval, 256 lanes on subsequences of the interval that synchronise (jpeg_core.h:
+//     jpeg_sync_walk); the same levels and status.
 //   mjpegd_idct_kernel     grid (groups of 256 blocks, frame), one thread per block: dequantise + islow IDCT into the component's
 //     plane at its own resolution.
 //   mjpegd_colour_kernel   grid (groups of 1024 pixels, frame), one thread per 4 pixels: fancy upsampling + YCbCr -> RGB24.
@@ -21,6 +24,8 @@ constexpr int MJD_THREADS = 256;
 constexpr int MJD_SLICE = 16;                                     // bytes of the scan per thread and chunk of the marker kernel
 constexpr int MJD_MAX_BATCH = 1024;
 constexpr size_t MJD_MAX_PACKED = (size_t)1 << 30;                // descriptors + entropy-coded bytes of one batch: 1 GiB
+constexpr int MJD_SUBSEQ = 1024;                                  // VBT_MJPEG_ENTROPY_SYNC: bytes per subsequence when the caller names none ...
+constexpr int MJD_AUTO_MIN_INTERVAL = 13920;                      // ... and VBT_MJPEG_ENTROPY_AUTO: the mean interval length from which a frame takes that path (profiles/mjpeg_decode.md)
 
 struct MjdArgs {
   const uint8_t* packed;     // [B] JpegDesc, then the frames' scans, each 16-byte aligned (scan_off counts from packed)
@@ -105,6 +110,120 @@ __global__ __launch_bounds__(64) void mjpegd_entropy_kernel(MjdArgs A) {
   if (st) atomicMax(&A.status[f], st);
 }
 
+// exclusive prefix sums of the four words of v over the workgroup, wrapping (every thread calls it); tot: the sums.  wsum: 4 x 4 words of LDS
+__device__ __forceinline__ void mjd_block_scan4(const uint32_t (&v)[4], uint32_t (&base)[4], uint32_t (&tot)[4], uint32_t (*wsum)[4]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc[4] = {v[0], v[1], v[2], v[3]};
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t o = (uint32_t)__shfl_up((int)inc[j], d, 64);
+      if (lane >= d) inc[j] += o;
+    }
+  }
+  __syncthreads();                                                // the readers of the call before are done with wsum
+  if (lane == 63) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) wsum[wave][j] = inc[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    uint32_t b = 0, t = 0;
+#pragma unroll
+    for (int k = 0; k < MJD_THREADS / 64; k++) {
+      const uint32_t s = wsum[k][j];
+      if (k < wave) b += s;
+      t += s;
+    }
+    base[j] = b + inc[j] - v[j];
+    tot[j] = t;
+  }
+}
+
+// Subsequences that synchronise (jpeg_core.h): grid (interval, frame), one workgroup per restart interval, its scan cut into
+// subsequences of S bytes, MJD_THREADS of them (a chunk) at a time, the chunks in order.  Per chunk: every lane walks from a guess (lane
+// 0 from the true state the chunk before left) and then from its left neighbour's exit until no entry changes - at most
+// MJD_THREADS + 1 rounds, since lanes 0 .. r - 1 are final after round r; prefix sums of the block counts and DC sums give each
+// lane its block number and predictors; a second walk stores the levels.  A chunk in which a lane recorded a status before the
+// interval's last block, or in which the bits end before the blocks do, is not stored that way: thread 0 finishes the interval from the
+// chunk's entry state with the statements of jpeg_decode_interval (jpeg_decode_rest).  Every loop is bounded before it starts;
+// no lane waits for another except at the workgroup's barriers, which every thread reaches.
+// info: { most rounds of any chunk, intervals finished by the single lane } of the batch.
+__global__ __launch_bounds__(MJD_THREADS) void mjpegd_entropy_sync_kernel(MjdArgs A, int S, int32_t* info) {
+  static_assert(sizeof(JpegHuff) % 4 == 0 && offsetof(JpegDesc, ac) == offsetof(JpegDesc, dc) + 2 * sizeof(JpegHuff) && offsetof(JpegDesc, dc) % 4 == 0,
+                "the four tables are staged as one run of words");
+  __shared__ JpegHuff sHuff[4];
+  __shared__ JpegSyncState sExit[MJD_THREADS];
+  __shared__ uint32_t sSum[MJD_THREADS / 64][4];
+  const int tid = threadIdx.x, f = blockIdx.y, k = blockIdx.x;
+  const JpegDesc& d = mjd_desc(A, f);
+  if (k >= d.n_int || A.rst_count[f] != (uint32_t)d.n_int - 1) return;   // (per workgroup: every thread returns or none does)
+  const JpegLayout L = jpeg_layout(d);
+  if (L.blocks > A.frame_blocks) return;
+  {
+    const uint32_t* src = (const uint32_t*)d.dc;
+    uint32_t* dst = (uint32_t*)sHuff;
+    for (int i = tid; i < (int)(4 * sizeof(JpegHuff) / 4); i += MJD_THREADS) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t* pos = A.rst + (size_t)f * A.rst_cap;
+  const uint32_t start = k ? pos[k - 1] + 2 : 0, end = k + 1 < d.n_int ? pos[k] : d.scan_len;
+  const uint8_t* scan = A.packed + d.scan_off;
+  int16_t* levels = A.levels + (size_t)f * A.frame_blocks * 64;
+  const uint32_t len = end > start ? end - start : 0, lanes = len ? (len + (uint32_t)S - 1) / (uint32_t)S : 1;
+  const uint32_t nblocks = jpeg_interval_blocks(d, k);
+  const int m0 = k * d.ri, max_syms = 8 * S + 32;
+  JpegSyncState carry;                                              // the true state in front of the chunk, the blocks complete and the DC sums there
+  carry.pos = start; carry.buk = 0;
+  uint32_t cb = 0, cdc[3] = {0, 0, 0};
+  int most = 0;
+  for (uint32_t c0 = 0; c0 < lanes; c0 += MJD_THREADS) {
+    const bool active = c0 + (uint32_t)tid < lanes;
+    const uint32_t first = active ? start + (c0 + (uint32_t)tid) * (uint32_t)S : end;
+    const uint32_t limit = active && end - first > (uint32_t)S ? first + (uint32_t)S : end;
+    JpegSyncState entry = tid == 0 || !active ? carry : jpeg_sync_cold(scan, first);
+    JpegSyncWalk w;
+    w.exit = entry; w.blocks = 0; w.dc[0] = w.dc[1] = w.dc[2] = 0; w.bad_at = JPEG_SYNC_NONE;
+    int rounds = 0;
+    for (int r = 0; r <= MJD_THREADS; r++) {
+      bool go = active && r == 0;
+      if (r > 0 && active && tid > 0) {
+        const JpegSyncState e = sExit[tid - 1];
+        if (!jpeg_sync_same(e, entry)) { entry = e; go = true; }
+      }
+      if (!__syncthreads_or(go)) break;                             // (also: every read of sExit is done before the writes below)
+      if (go) {
+        w = jpeg_sync_walk<false>(d, L, sHuff, scan, end, entry, limit, max_syms, 0, 0, 0, nullptr, nullptr);
+        sExit[tid] = w.exit;
+      }
+      rounds++;
+      __syncthreads();
+    }
+    most = rounds > most ? rounds : most;
+    const uint32_t v[4] = {w.blocks, w.dc[0], w.dc[1], w.dc[2]};
+    uint32_t base[4], tot[4];
+    mjd_block_scan4(v, base, tot, sSum);
+    base[0] += cb; base[1] += cdc[0]; base[2] += cdc[1]; base[3] += cdc[2];
+    const bool last = lanes - c0 <= (uint32_t)MJD_THREADS;
+    const bool dirty = (w.bad_at != JPEG_SYNC_NONE && base[0] + w.bad_at < nblocks) || (last && cb + tot[0] < nblocks);
+    if (__syncthreads_or(dirty)) {
+      if (tid == 0) {
+        const int st = jpeg_decode_rest(d, L, scan, end, k, carry, cb, cdc, levels);
+        if (st) atomicMax(&A.status[f], st);
+        atomicAdd(&info[1], 1);
+      }
+      break;
+    }
+    if (active) jpeg_sync_walk<true>(d, L, sHuff, scan, end, entry, limit, max_syms, m0, base[0], nblocks, &base[1], levels);
+    carry = sExit[last ? lanes - c0 - 1 : MJD_THREADS - 1];          // (the next chunk writes sExit only behind its first barrier)
+    cb += tot[0]; cdc[0] += tot[1]; cdc[1] += tot[2]; cdc[2] += tot[3];
+    if (cb >= nblocks) break;                                       // what is left is padding
+  }
+  if (tid == 0) atomicMax(&info[0], most);
+}
+
 __global__ __launch_bounds__(MJD_THREADS) void mjpegd_idct_kernel(MjdArgs A) {
   __shared__ uint16_t sQ[4][64];
   const int tid = threadIdx.x, f = blockIdx.y;
@@ -183,6 +302,9 @@ struct vbt_mjpeg_decoder {
   int next = 0, last_B = 0;
   hipEvent_t stamp[7] = {};              // VBT_MJPEG_DECODE_STAMPS=1: around each stage of a decode (vbt_mjpeg_decode_stage_ms)
   bool stamps = false;
+  int entropy = VBT_MJPEG_ENTROPY_AUTO, subseq = 0;   // vbt_mjpeg_decoder_set_entropy
+  int last_path = 0, last_subseq = 0;    // of the last batch
+  int32_t* info = nullptr;               // in blob: { most rounds of any chunk, intervals the single lane finished } of the last batch in SYNC
   std::vector<JpegDesc> descs;
   MjdArgs args{};
 };
@@ -222,7 +344,7 @@ int vbt_mjpeg_decoder_create(int device, int H, int W, int max_batch, vbt_mjpeg_
   m->rst_cap = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);
   const size_t B = (size_t)max_batch;
   const size_t o_status = 0, o_count = align256(B * 4), o_rst = o_count + align256(B * 4), o_levels = o_rst + align256(B * m->rst_cap * 4),
-               o_planes = o_levels + align256(B * m->frame_blocks * 128), total = o_planes + align256(B * m->frame_blocks * 64);
+               o_planes = o_levels + align256(B * m->frame_blocks * 128), o_info = o_planes + align256(B * m->frame_blocks * 64), total = o_info + 256;
   m->packed_cap = std::min(MJD_MAX_PACKED, align256(B * sizeof(JpegDesc) + B * (4096 + (size_t)H * W / 4)));
   hipError_t e = hipMalloc((void**)&m->blob, total);
   if (e == hipSuccess) e = hipMalloc((void**)&m->packed, m->packed_cap);
@@ -247,6 +369,7 @@ int vbt_mjpeg_decoder_create(int device, int H, int W, int max_batch, vbt_mjpeg_
   A.H = H; A.W = W;
   A.status = (int32_t*)(m->blob + o_status); A.rst_count = (uint32_t*)(m->blob + o_count); A.rst = (uint32_t*)(m->blob + o_rst);
   A.rst_cap = (uint32_t)m->rst_cap; A.levels = (int16_t*)(m->blob + o_levels); A.planes = m->blob + o_planes;
+  m->info = (int32_t*)(m->blob + o_info);
   *out = m;
   return VBT_OK;
 }
@@ -275,6 +398,7 @@ int vbt_mjpeg_decode(vbt_mjpeg_decoder* m, const uint8_t* host_bytes, const uint
   m->descs.resize((size_t)B);
   size_t total = align16((size_t)B * sizeof(JpegDesc));
   uint32_t max_int = 1, max_blocks = 1;
+  bool sync = m->entropy == VBT_MJPEG_ENTROPY_SYNC;
   for (int i = 0; i < B; i++) {
     JpegDesc& d = m->descs[(size_t)i];
     std::string why;
@@ -283,6 +407,7 @@ int vbt_mjpeg_decode(vbt_mjpeg_decoder* m, const uint8_t* host_bytes, const uint
       return VBT_ERR_IO;
     }
     max_int = std::max(max_int, (uint32_t)d.n_int);
+    if (m->entropy == VBT_MJPEG_ENTROPY_AUTO && d.scan_len / (uint32_t)d.n_int >= (uint32_t)MJD_AUTO_MIN_INTERVAL) sync = true;
     max_blocks = std::max(max_blocks, jpeg_layout(d).blocks);
     total += align16(d.scan_len);
   }
@@ -334,10 +459,13 @@ int vbt_mjpeg_decode(vbt_mjpeg_decoder* m, const uint8_t* host_bytes, const uint
   A.packed = m->packed; A.B = B; A.frame_blocks = max_blocks; A.out = frames_dev_out;
   VBT_HIP_CHECK(hipMemsetAsync(A.status, 0, (size_t)B * 4, st));
   VBT_HIP_CHECK(hipMemsetAsync(A.levels, 0, (size_t)B * max_blocks * 128, st));
+  if (sync) VBT_HIP_CHECK(hipMemsetAsync(m->info, 0, 8, st));
   VBT_HIP_CHECK(stamp(2));
   mjpegd_markers_kernel<<<dim3((unsigned)B), MJD_THREADS, 0, st>>>(A);
   VBT_HIP_CHECK(stamp(3));
-  mjpegd_entropy_kernel<<<dim3((max_int + 63) / 64, (unsigned)B), 64, 0, st>>>(A);
+  const int S = m->subseq ? m->subseq : MJD_SUBSEQ;
+  if (sync) mjpegd_entropy_sync_kernel<<<dim3(max_int, (unsigned)B), MJD_THREADS, 0, st>>>(A, S, m->info);
+  else mjpegd_entropy_kernel<<<dim3((max_int + 63) / 64, (unsigned)B), 64, 0, st>>>(A);
   VBT_HIP_CHECK(stamp(4));
   mjpegd_idct_kernel<<<dim3((max_blocks + MJD_THREADS - 1) / MJD_THREADS, (unsigned)B), MJD_THREADS, 0, st>>>(A);
   VBT_HIP_CHECK(stamp(5));
@@ -346,6 +474,28 @@ int vbt_mjpeg_decode(vbt_mjpeg_decoder* m, const uint8_t* host_bytes, const uint
   VBT_HIP_CHECK(stamp(6));
   VBT_HIP_CHECK(hipGetLastError());
   m->last_B = B;
+  m->last_path = sync ? VBT_MJPEG_ENTROPY_SYNC : VBT_MJPEG_ENTROPY_INTERVAL;
+  m->last_subseq = sync ? S : 0;
+  return VBT_OK;
+}
+
+int vbt_mjpeg_decoder_set_entropy(vbt_mjpeg_decoder* m, int mode, int subseq_bytes) {
+  if (!m) { set_error("vbt_mjpeg_decoder_set_entropy: handle is NULL"); return VBT_ERR_ARG; }
+  if (mode < VBT_MJPEG_ENTROPY_AUTO || mode > VBT_MJPEG_ENTROPY_SYNC) { set_error("vbt_mjpeg_decoder_set_entropy: mode %d is none of AUTO (0), INTERVAL (1), SYNC (2)", mode); return VBT_ERR_ARG; }
+  if (subseq_bytes && (subseq_bytes < 4 || subseq_bytes > 4096 || (subseq_bytes & (subseq_bytes - 1)))) {
+    set_error("vbt_mjpeg_decoder_set_entropy: subseq_bytes %d is neither 0 nor a power of two in 4..4096", subseq_bytes);
+    return VBT_ERR_ARG;
+  }
+  m->entropy = mode;
+  m->subseq = subseq_bytes;
+  return VBT_OK;
+}
+
+int vbt_mjpeg_decoder_get_entropy(vbt_mjpeg_decoder* m, int* mode, int* subseq_bytes, int* auto_min_interval_bytes) {
+  if (!m) { set_error("vbt_mjpeg_decoder_get_entropy: handle is NULL"); return VBT_ERR_ARG; }
+  if (mode) *mode = m->entropy;
+  if (subseq_bytes) *subseq_bytes = m->subseq ? m->subseq : MJD_SUBSEQ;
+  if (auto_min_interval_bytes) *auto_min_interval_bytes = MJD_AUTO_MIN_INTERVAL;
   return VBT_OK;
 }
 
@@ -355,6 +505,16 @@ int vbt_mjpeg_decode_status(vbt_mjpeg_decoder* m, int32_t* status, void* stream)
   VBT_HIP_CHECK(hipSetDevice(m->device));
   VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   VBT_HIP_CHECK(hipMemcpy(status, m->args.status, (size_t)m->last_B * 4, hipMemcpyDeviceToHost));
+  return VBT_OK;
+}
+
+int vbt_mjpeg_decode_entropy_info(vbt_mjpeg_decoder* m, int32_t* info4, void* stream) {
+  if (!m || !info4) { set_error("vbt_mjpeg_decode_entropy_info: bad argument"); return VBT_ERR_ARG; }
+  if (!m->last_B) { set_error("vbt_mjpeg_decode_entropy_info: no batch has been decoded (vbt_mjpeg_decode first)"); return VBT_ERR_STATE; }
+  info4[0] = m->last_path; info4[1] = m->last_subseq; info4[2] = info4[3] = 0;
+  VBT_HIP_CHECK(hipSetDevice(m->device));
+  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  if (m->last_path == VBT_MJPEG_ENTROPY_SYNC) VBT_HIP_CHECK(hipMemcpy(info4 + 2, m->info, 8, hipMemcpyDeviceToHost));
   return VBT_OK;
 }
 

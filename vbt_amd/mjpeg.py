@@ -140,15 +140,50 @@ def probe(jpeg):
     return tuple(x.value for x in v)
 
 
-class Decoder:
-    """vbt_mjpeg_decoder (include/vbt_hip.h): one frame size; batches of up to max_batch JPEG files -> RGB24 frames in device memory."""
+ENTROPY_MODES = {"auto": 0, "interval": 1, "sync": 2}
 
-    def __init__(self, H, W, max_batch=64, device=0):
+
+class Decoder:
+    """vbt_mjpeg_decoder (include/vbt_hip.h): one frame size; batches of up to max_batch JPEG files -> RGB24 frames in device memory.
+    `entropy` ("auto", "interval", "sync") and `subseq_bytes` (0: the default): how the scans are entropy-decoded - set_entropy."""
+
+    def __init__(self, H, W, max_batch=64, device=0, entropy="auto", subseq_bytes=0):
         self.H, self.W, self.max_batch = int(H), int(W), int(max_batch)
+        mode = self._mode(entropy)
         h = ctypes.c_void_p()
         _lib.check(_lib.lib().vbt_mjpeg_decoder_create(int(device), self.H, self.W, self.max_batch, ctypes.byref(h)))
         self._h = h
         self._B, self._stream = 0, None
+        if mode or subseq_bytes:
+            self.set_entropy(mode, subseq_bytes)
+
+    @staticmethod
+    def _mode(mode):
+        if isinstance(mode, str):
+            if mode.lower() not in ENTROPY_MODES:
+                raise ValueError(f"entropy mode {mode!r}: one of {', '.join(ENTROPY_MODES)}")
+            return ENTROPY_MODES[mode.lower()]
+        return int(mode)
+
+    def set_entropy(self, mode, subseq_bytes=0):
+        """"auto": by interval length; "interval": one lane per restart interval; "sync": subsequences of subseq_bytes (0: the default,
+        else a power of two in 4..4096) that synchronise.  The frames and the status are the same; it holds from the next decode on."""
+        _lib.check(_lib.lib().vbt_mjpeg_decoder_set_entropy(self._h, self._mode(mode), int(subseq_bytes)))
+
+    @property
+    def entropy(self):
+        """(mode, subseq_bytes, auto_min_interval_bytes): the mode's name, the subsequence size "sync" uses, and the scan bytes per
+        restart interval from which "auto" takes the "sync" path"""
+        v = [ctypes.c_int() for _ in range(3)]
+        _lib.check(_lib.lib().vbt_mjpeg_decoder_get_entropy(self._h, *(ctypes.byref(x) for x in v)))
+        return {n: k for k, n in ENTROPY_MODES.items()}[v[0].value], v[1].value, v[2].value
+
+    def entropy_info(self):
+        """how the entropy stage of the last batch ran: {"path": 1 (interval) or 2 (sync), "subseq_bytes", "rounds": the most rounds
+        any chunk of subsequences took, "single": intervals that one lane finished}; one synchronisation of its stream"""
+        info = np.zeros(4, np.int32)
+        _lib.check(_lib.lib().vbt_mjpeg_decode_entropy_info(self._h, info.ctypes.data, self._stream))
+        return dict(zip(("path", "subseq_bytes", "rounds", "single"), (int(x) for x in info)))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -289,14 +324,16 @@ class AviReader:
 class AviClip:
     """A Motion-JPEG AVI as the clip array [T, H, W, 3] uint8 that track_frames, track_many and overlay.render take: ints and slices
     are decoded on the GPU and read back; decode_into() leaves the frames in device memory.  The frame size is the first frame's (every
-    frame must have it); `fps` is the file's rate / scale.  `damaged` collects the indices of frames whose scan status was not 0."""
+    frame must have it); `entropy` is Decoder's; `fps` is the file's rate / scale.  `damaged` collects the indices of frames whose scan status was not 0."""
 
     dtype = np.dtype(np.uint8)
     ndim = 4
 
-    def __init__(self, path, batch=64, device=0):
+    def __init__(self, path, batch=64, device=0, entropy="auto"):
         self.reader = path if isinstance(path, AviReader) else AviReader(path)
         self.path, self.fps, self.device, self.batch = self.reader.path, self.reader.fps, int(device), max(int(batch), 1)
+        self.entropy = entropy
+        Decoder._mode(entropy)
         T = len(self.reader)
         if T:
             H, W, _, _ = probe(self.reader.frame(0))
@@ -311,7 +348,7 @@ class AviClip:
 
     def _decoder(self):
         if self._dec is None:
-            self._dec = Decoder(self.shape[1], self.shape[2], max_batch=self.batch, device=self.device)
+            self._dec = Decoder(self.shape[1], self.shape[2], max_batch=self.batch, device=self.device, entropy=self.entropy)
         return self._dec
 
     def decode_into(self, indices, dev_ptr, stream=None):
