@@ -1,12 +1,15 @@
-// Host-only check of the memory owners of vbt_amd/csrc/dev_mem.h, built with -fsanitize=address,undefined (tests/test_dev_mem_host.py).
+// Host-only check of the memory owners of vbt_amd/csrc/dev_mem.h and the event / stream owners of vbt_amd/csrc/hip_handles.h, built with
+// -fsanitize=address,undefined (tests/test_dev_mem_host.py).
 // It needs no device: the test hides every device, so each allocation fails the way it does on a machine without one, and an
 // allocation of 2^60 bytes fails on any machine.  What is checked is the owners' bookkeeping around failures, moves and destruction;
-// where an allocation does succeed (a visible device) the same statements hold with a buffer in hand.
+// where an allocation does succeed (a visible device) the same statements hold with a buffer in hand.  Events and streams likewise:
+// no create succeeds without a device, and one with flags no runtime knows fails on any machine.
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
 
 #include "../../vbt_amd/csrc/dev_mem.h"
+#include "../../vbt_amd/csrc/hip_handles.h"
 
 using namespace vbt;
 
@@ -63,9 +66,38 @@ static int check_mirror() {
   return 0;
 }
 
+template <class Own>
+static int check_handle(const char* name, unsigned flags) {
+  {
+    Own empty;                                      // destruction of an empty owner
+    CHECK(!empty && empty.get() == nullptr);
+  }
+  Own a;
+  CHECK(a.create(~0u) != hipSuccess);               // a failed create leaves the owner empty
+  CHECK(!a && a.get() == nullptr);
+  const hipError_t e = a.create(flags);
+  CHECK((e == hipSuccess) == (a.get() != nullptr));
+  const auto h = a.get();
+  Own b(std::move(a));                              // a move leaves the source empty
+  CHECK(a.get() == nullptr && b.get() == h);
+  Own c;
+  c = std::move(b);
+  CHECK(b.get() == nullptr && c.get() == h);
+  Own& same = c;
+  c = std::move(same);                              // self-move keeps the handle
+  CHECK(c.get() == h);
+  CHECK(c.create(~0u) != hipSuccess);               // a failed re-create destroys what was held
+  CHECK(c.get() == nullptr);
+  a.reset();                                        // reset of a moved-from owner
+  std::printf("ok %s %s\n", name, e == hipSuccess ? "created" : "no-device");
+  return 0;                                         // a, b, c: destruction of moved-from and empty owners
+}
+
 int main() {
   std::setvbuf(stdout, nullptr, _IOLBF, 0);
   if (check_buf<DevBuf<double>>("DevBuf")) return 1;
   if (check_buf<PinnedBuf<double>>("PinnedBuf")) return 1;
-  return check_mirror();
+  if (check_mirror()) return 1;
+  if (check_handle<Event>("Event", hipEventDisableTiming)) return 1;
+  return check_handle<Stream>("Stream", hipStreamNonBlocking);
 }

@@ -1,7 +1,8 @@
-"""The owners of device and pinned memory (vbt_amd/csrc/dev_mem.h: DevBuf, PinnedBuf, Mirror) under -fsanitize=address,undefined: a
-stand-alone host program (tests/fuzz/dev_mem_check.cc) with every device hidden, so that each allocation fails as it does on a machine
-without a GPU.  Checked: a failed alloc leaves the buffer null, a move leaves the source empty, a Mirror is usable after a failed
-reserve, empty and moved-from objects destruct cleanly.  Nothing loaded into Python is run under a sanitizer."""
+"""The owners of device and pinned memory (vbt_amd/csrc/dev_mem.h: DevBuf, PinnedBuf, Mirror) and of HIP events and streams
+(vbt_amd/csrc/hip_handles.h: Event, Stream) under -fsanitize=address,undefined: a stand-alone host program
+(tests/fuzz/dev_mem_check.cc) with every device hidden, so that each allocation fails as it does on a machine without a GPU.  Checked:
+a failed alloc leaves the buffer null, a move leaves the source empty, a Mirror is usable after a failed reserve, a failed create leaves
+an event / stream owner empty, empty and moved-from objects destruct cleanly.  Nothing loaded into Python is run under a sanitizer."""
 import os
 import subprocess
 
@@ -29,3 +30,6 @@ def test_owners_keep_their_books_when_every_allocation_fails(harness):
     lines = p.stdout.split("\n")[:3]          # "no-device" with the devices hidden; a runtime that shows one anyway gives "allocated"
     assert [ln.rsplit(" ", 1)[0] for ln in lines] == ["ok DevBuf", "ok PinnedBuf", "ok Mirror"], p.stdout
     assert all(ln.endswith((" no-device", " allocated")) for ln in lines), p.stdout
+    handles = p.stdout.split("\n")[3:5]       # the event and stream owners: "created" where a device showed
+    assert [ln.rsplit(" ", 1)[0] for ln in handles] == ["ok Event", "ok Stream"], p.stdout
+    assert all(ln.endswith((" no-device", " created")) for ln in handles), p.stdout

@@ -1,6 +1,6 @@
 """Every kernel variant a plan file may select, and the pinned plans at their own batch sizes, against the oracle tensor by tensor.
 
-The planner holds that all alternatives and kernel variants compute bit-identical tensors (detector.hip, above candidate_variants), and
+The planner holds that all alternatives and kernel variants compute bit-identical tensors (detector_plan.hip, above candidate_variants), and
 the autotuner, tools/tune_under_load.py and the pinned plan files may each pick any of them.  The sweep writes the covering plans of
 tests/plan_cover.py as plan files, so every (group, alternative, step, variant) the plan loader accepts runs at least once, and compares
 every materialised tensor and every detection with the oracle's.  At flags 0 every kernel family of the library appears in the plan

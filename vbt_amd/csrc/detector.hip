@@ -1,6 +1,8 @@
-// EfficientDet-Lite int8 detector on gfx950 (MI355X): execution plan (planner + autotuner), launches and the C ABI.
-// The single-op kernels are in op_kernels.h, the host-side weight layouts in weight_pack.h and the planner in planner.h (all three
-// included below); the fused kernel families live in their own translation units (k_*.hip, reached through launchers.h).
+// EfficientDet-Lite int8 detector on gfx950 (MI355X): variant resolution, launches, the forward (eager or hipGraph replay) and the
+// detect entry points of the C ABI.  The single-op kernels are in op_kernels.h, which only this unit includes; the fused kernel families
+// live in their own translation units (k_*.hip, reached through launchers.h).  The model handle and what the detector's units share:
+// detector_model.h; the planner: planner.hip (weight layouts: weight_pack.h); parameter pool, autotuner, plan files and model life
+// cycle: detector_plan.hip; diagnostic timings: detector_profile.hip; error text, device check and LDS opt-in: runtime.hip.
 //
 // Replaces the TFLite interpreter invoke at reference odt.py:58-66 (signature_fn(images=...)).
 // Arithmetic contract = the kernels tflite-runtime 2.14 executes on x86-64 (XNNPACK delegate by default, TFLite builtin
@@ -21,262 +23,20 @@
 //     candidates in LDS -> greedy suppression by one wavefront with ballot/shuffle.
 #include <algorithm>
 #include <cmath>
-#include <chrono>
-#include <functional>
-#include <map>
-#include <set>
-#include <type_traits>
-#include <tuple>
 
-#include "dev_mem.h"
-#include "launchers.h"   // dev_common.h + the argument structs / tile constants of every kernel family + the launchers
-
-namespace vbt {
-
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-int use_device(const char* fn, int device, bool set_current) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error("%s: HIP device %d not available (%d visible) - no CPU fallback", fn, device, ndev);
-    return VBT_ERR_HIP;
-  }
-  if (set_current) VBT_HIP_CHECK(hipSetDevice(device));
-  return VBT_OK;
-}
-
-bool lds_opt_in(const void* fn, LdsOptIn* state) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("lds_opt_in: no current HIP device"); return false; }
-  if (state->dev[dev] > 0) return true;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("device %d refuses more than 64 KB of dynamic LDS for a kernel that needs it: %s", dev, hipGetErrorString(e));
-    return false;
-  }
-  state->dev[dev] = 1;
-  return true;
-}
-
+#include "detector_model.h"
 #include "op_kernels.h"   // the single-op kernels (pw_a / pw_b / pw_c / pw_d, stem, depthwise, add, pool, resize, decode + NMS, frame resize)
 
-// ------------------------------------------------------------------------------------------
-// host: model, plan, launches
-// ------------------------------------------------------------------------------------------
-enum Family { F_STEM = 0, F_PW, F_DW, F_ADD, F_MAXPOOL, F_RESIZE, F_POST, F_MBCONV, F_SEPCONV, F_NODE, F_MULTI, F_STEMBLK, F_EXPDW, F_BAND, F_COUNT };
-static const char* kFamilyName[F_COUNT] = {"stem_conv_mfma_i8", "pw_conv_mfma_i8", "dw_conv_f32acc", "add_requant",
-                                           "maxpool3x3s2", "resize_nn", "decode_nms", "fused_mbconv", "fused_sepconv", "fused_bifpn_node", "fused_heads_multi",
-                                           "fused_stem_block", "fused_expand_dw", "fused_sepconv_band"};
-
-// accounting of a step: per-frame bytes / MACs and once-per-launch weight bytes of the graph ops it stands for (element counts far
-// below 2^53: sums are exact in any order)
-struct Cost {
-  double alg_bytes_per_frame = 0, weight_bytes = 0, macs_per_frame = 0;
-  Cost& operator+=(const Cost& o) { alg_bytes_per_frame += o.alg_bytes_per_frame; weight_bytes += o.weight_bytes; macs_per_frame += o.macs_per_frame; return *this; }
-};
-
-struct Step {
-  int op;       // index into ops
-  int family;
-  // conv
-  long* wp = nullptr;      // packed MFMA weights, 16x16x32 layout (device): stem kernel and the expand stage of the fused kernels
-  v4i* wp64 = nullptr;     // pointwise convs: 16x16x64 layout (pack_weights64)
-  int KS64 = 0;            // K-steps of 64
-  int res_op = -1;         // F_PW: the residual ADD evaluated in the epilogue (op = that ADD, p_op = the conv)
-  long* wdm = nullptr;     // depthwise: matrix-pipe (diagonal-embedded) weights
-  int* bdm = nullptr;      // depthwise: bias folded for raw int8 inputs, padded to 64
-  float* mdm = nullptr;    // depthwise: multipliers padded to 64
-  float* wf = nullptr;     // depthwise weights as float [k*k][C] (device)
-  int* bias = nullptr;     // folded bias (device, padded)
-  float* mult = nullptr;   // multipliers (device, padded)
-  int KS = 0, NB = 0;
-  AddQ addq = {0, 0, 0, 0, 0, 0, 0};   // F_ADD: XNNPACK qs8-vadd parameters, derived from the tensor scales
-  Cost cost;               // compulsory traffic and work of the graph ops this step stands for
-  // fused block (F_MBCONV / F_SEPCONV): constituent op indices (-1 = absent) and kernel arguments
-  int e_op = -1, d_op = -1, p_op = -1, a_op = -1;
-  int sum_op = -1;          // F_NODE: the n-ary ADD feeding the depthwise
-  int src_tensor[3] = {-1, -1, -1};
-  FusedArgs fa;
-  int nbp = 0, lds_bytes = 0;
-  int variant = -1;  // kernel variant chosen by the autotuner (-1 = heuristic default)
-  double tuned_ms = 0;
-  // F_MULTI: independent fused problems launched as one grid
-  std::vector<Step> members;
-  FusedArgs* d_multi = nullptr;
-  // F_STEMBLK: stem -> depthwise -> project in one kernel (op = project op, e_op = stem op)
-  StemBlockArgs sb;
-  // F_BAND: SeparableConv / BiFPN node on row bands (band_block.h); members non-empty: several problems in one grid
-  BandArgs bd_args;
-  BandArgs* d_band = nullptr;   // device copy of the problem list (pointers are those of the whole batch); a single problem passes bd_args by value
-  int band_tiles = 0;           // workgroups per image of this problem
-  // F_EXPDW: expand + depthwise on whole images, expanded channels split over workgroups (expdw_block.h; op = depthwise op)
-  ExpDwArgs xd;
-  ExpDw2Args xd2;              // the same step on the second form of the kernel (expdw2_block.h); variant 100 + cpw runs it
-  bool xd2_ok = false;
-  int xd2_lds = 0, xd2_gpw = 0, xd2_gpw16 = 0;   // input pixel groups per wave on 8 / 16 waves (0: that wave count is not available)
-  // F_MBCONV on a low-resolution map: per-chunk weight records of the whole-image kernel (data == nullptr: not built)
-  ImageBundle ib = {nullptr, 0, 0, 0, 0, 0, 0, 0};
-};
-
-// A group of consecutive graph ops with alternative realisations (all bit-identical); the planner keeps
-// the fastest one measured on this device at this batch size.
-struct Alt {
-  std::vector<Step> steps;
-  std::vector<int> hidden;  // tensors that never reach HBM under this alternative
-  double ms = 0;
-};
-struct Group {
-  std::vector<Alt> alts;
-  int chosen = 0;
-};
-
-}  // namespace vbt
-
-using namespace vbt;
-
-struct vbt_model {
-  Header hdr;
-  std::vector<TensorRec> tensors;
-  std::vector<OpRec> ops;
-  std::vector<uint8_t> blob;
-  int device = 0, max_batch = 0;
-  std::vector<int8_t*> tptr;   // device pointer of each tensor ([max_batch][h][w][c])
-  std::vector<size_t> telems;  // per-frame elements
-  int8_t* arena = nullptr;
-  uint8_t* frames_stage = nullptr;  // device staging for host frames
-  float* out_boxes = nullptr;       // device staging for host outputs: ONE block boxes | scores | classes | counts ...
-  float* out_scores = nullptr;
-  float* out_classes = nullptr;
-  int* out_counts = nullptr;
-  unsigned char* out_host = nullptr;   // ... and its pinned host mirror: vbt_detect's results come back with one copy
-  size_t out_bytes = 0;
-  float* d_anchors = nullptr;
-  unsigned char* d_luts = nullptr;   // post-process tables (see PostArgs)
-  std::vector<float> post_tables_host;   // scores indexed by rank byte + 128
-  std::vector<Step> steps;      // execution list (after fusion + autotuning)
-  std::vector<Group> groups;
-  std::vector<Step> op_steps;   // one per graph op (weights live here)
-  std::vector<char> materialized;  // per tensor: written to HBM by the execution list
-  int flags = 0;
-  int n_sub = 1;                         // sub-batches run concurrently on side streams
-  hipStream_t sub_streams[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-  // hipGraph replay of the forward for launch-bound (small) batches: one executable graph per (B, buffers)
-  struct GraphKey {
-    const void* frames; void* boxes; void* scores; void* classes; void* counts; int B;
-    bool operator<(const GraphKey& o) const {
-      return std::tie(frames, boxes, scores, classes, counts, B) < std::tie(o.frames, o.boxes, o.scores, o.classes, o.counts, o.B);
-    }
-  };
-  std::map<GraphKey, hipGraphExec_t> graphs;
-  hipStream_t cap_stream = nullptr;
-  int graph_max_batch = 0;  // 0 = graphs off
-  bool ran_eager = false;   // one forward has been enqueued outside a stream capture (per-device LDS opt-ins, lazy uploads)
-  std::vector<void*> owned;  // device allocations to free
-  // Parameter pool: weights, biases, multipliers and argument tables are sub-allocated from a few large device chunks and
-  // mirrored on the host; flush_uploads() brings a chunk up to date with ONE copy (a model used to issue ~1 800 small blocking
-  // hipMemcpy calls at creation).  Off under VBT_DEBUG_FENCE, where every buffer ends at its own allocation boundary.
-  struct PoolChunk { char* dev; std::vector<char> host; size_t used, flushed; };
-  std::vector<PoolChunk> pool;
-  bool pool_dirty = false;
-  int last_B = 0;
-};
-
 namespace vbt {
 
-// Debug "electric fence" (VBT_DEBUG_FENCE=1): every device buffer is placed so that it ENDS at the end of its own
-// 2 MiB-granular allocation; a kernel reading past the documented slack then touches unmapped memory and faults
-// instead of silently reading a neighbour.  Used once per model family by tests/tools, never in production.
-static bool fence_on() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("VBT_DEBUG_FENCE"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1;
-}
-static hipError_t fenced_malloc(vbt_model* m, void** out, size_t bytes) {
-  if (!fence_on()) {
-    hipError_t e = hipMalloc(out, bytes);
-    if (e == hipSuccess) m->owned.push_back(*out);
-    return e;
-  }
-  const size_t G = 2u << 20;
-  size_t total = (bytes + G - 1) / G * G;
-  char* base = nullptr;
-  hipError_t e = hipMalloc((void**)&base, total);
-  if (e != hipSuccess) return e;
-  m->owned.push_back(base);
-  *out = base + ((total - bytes) & ~(size_t)255);   // keep 256-B alignment; the buffer ends <= 255 B before the fence
-  return hipSuccess;
-}
-
-constexpr size_t POOL_CHUNK = 32u << 20;
-static int pool_alloc(vbt_model* m, size_t bytes, void** dev, char** host) {
-  bytes = (bytes + 255) & ~(size_t)255;   // 256-byte alignment, like hipMalloc
-  if (m->pool.empty() || m->pool.back().used + bytes > m->pool.back().host.size()) {
-    vbt_model::PoolChunk c;
-    c.dev = nullptr; c.used = 0; c.flushed = 0;
-    const size_t cap = std::max(POOL_CHUNK, bytes);
-    VBT_HIP_CHECK(hipMalloc((void**)&c.dev, cap));
-    m->owned.push_back(c.dev);
-    c.host.assign(cap, 0);
-    m->pool.push_back(std::move(c));
-  }
-  vbt_model::PoolChunk& c = m->pool.back();
-  *dev = c.dev + c.used;
-  *host = c.host.data() + c.used;
-  c.used += bytes;
-  m->pool_dirty = true;
-  return VBT_OK;
-}
-// Everything uploaded since the last flush reaches the device: one copy per chunk that grew.  Called before any kernel of
-// the model can run (launch_step).
-static int flush_uploads(vbt_model* m) {
-  if (!m->pool_dirty) return VBT_OK;
-  for (auto& c : m->pool)
-    if (c.used > c.flushed) {
-      VBT_HIP_CHECK(hipMemcpy(c.dev + c.flushed, c.host.data() + c.flushed, c.used - c.flushed, hipMemcpyHostToDevice));
-      c.flushed = c.used;
-    }
-  m->pool_dirty = false;
-  return VBT_OK;
-}
-
-template <typename T>
-static int upload(vbt_model* m, const std::vector<T>& h, T** d) {
-  size_t bytes = std::max<size_t>(h.size() * sizeof(T), 16);
-  if (fence_on()) {
-    VBT_HIP_CHECK(fenced_malloc(m, (void**)d, bytes + 64));
-    if (!h.empty()) VBT_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return VBT_OK;
-  }
-  char* host = nullptr;
-  int rc = pool_alloc(m, bytes + 64, (void**)d, &host);   // (+64: kernels read K-padding bytes past a weight row's end)
-  if (rc) return rc;
-  if (!h.empty()) memcpy(host, h.data(), h.size() * sizeof(T));
-  return VBT_OK;
-}
-
-#include "weight_pack.h"   // the weight / bias layouts of every kernel family: one pure host function each
-#include "planner.h"       // graph ops -> Steps, alternatives and groups (build_plan / fuse_plan / finalize_plan)
+static_assert(PWM_MAX == PW_MERGE_MAX, "the planner merges as many pointwise convs as one pw_multi_kernel launch takes");
 
 // ---- variant resolution: one pure host function per launch family turns (step, variant, batch; -1 = heuristic default) into the
-// launch it stands for, or refuses it.  The launches, the autotuner's candidates and the plan-file check all ask these. ----
-struct Verdict {   // rc != VBT_OK: the step is refused, and `why` is the error text of its launch
-  int rc = VBT_OK; char why[160] = "";
-  void refuse(int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(why, sizeof(why), fmt, ap); va_end(ap); rc = code; }
-  int report() const { set_error("%s", why); return rc; }
-};
+// launch it stands for, or refuses it.  The launches, the autotuner's candidates and the plan-file check all ask these.
+// (Result structs: detector_model.h.) ----
 
 // pointwise conv (one conv; the merged launch of merge_side_convs has no variants)
-enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E };
-struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0; dim3 grid; };
-static PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B) {
+PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B) {
   PwLaunch L;
   const TensorRec& to = m->tensors[m->ops[s.res_op >= 0 ? s.p_op : s.op].output];
   const long M = (long)B * to.h * to.w;
@@ -347,11 +107,7 @@ static int launch_pw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
 
 // stand-alone depthwise conv: 0 = one output row x 4 columns per lane, 100 / 101 = LDS tiles, chunk-parallel (101: depthwise on the
 // matrix pipe), anything else = column walker with `variant` output rows per lane (-1: rows chosen by the map size)
-enum DwForm { DW_ROW, DW_COL, DW_TILE };
-struct DwLaunch : Verdict {   // tile geometry (DW_TILE), rows per lane and row segments (DW_COL), lanes (DW_ROW / DW_COL)
-  DwForm form = DW_COL; bool mdw = false; int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0, lds = 0, rows = 0, nseg = 0; long total = 0; dim3 grid;
-};
-static DwLaunch resolve_dw(const vbt_model* m, const Step& s, int variant, int B) {
+DwLaunch resolve_dw(const vbt_model* m, const Step& s, int variant, int B) {
   DwLaunch L;
   const OpRec& op = m->ops[s.op];
   const TensorRec& to = m->tensors[op.output];
@@ -409,11 +165,7 @@ static int launch_dw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
 // chunks, 16 = 128-pixel (16 x 8) tiles, 32 = band-Toeplitz depthwise (fused_block.h: TPZ); a bit whose conditions the step does not
 // meet is ignored, except that the whole-image and 128-pixel kernels refuse a step they do not fit and that bit 32 resolves only as
 // 33, 41, 49 or 57 on a step where each of its other bits holds.
-struct FusedPlan : Verdict {
-  bool image = false; int PW = 0, PH = 0, NB = 0, maxu = 0;   // whole-image kernel: padded map, output channel blocks, work units per wave
-  int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0; FusedLaunch L{};   // (whole image: k, stride and lds_bytes of L)
-};
-static FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
+FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   const FusedArgs& a = s.fa;
   const OpRec& dop = m->ops[s.d_op];
   const int k = dop.k, stride = dop.stride;
@@ -475,10 +227,7 @@ static int launch_fused_step(const vbt_model* m, const Step& s, FusedArgs a, int
 
 // expand + depthwise on whole images or row bands.  Variant: chunks per workgroup on the first form of the kernel (expdw_block.h),
 // 100 + chunks per workgroup on the second (expdw2_block.h) with 8 waves, 200 + chunks with 16 waves; -1: heuristic default
-struct ExpDwLaunch : Verdict {   // chunks per workgroup; second form: waves per workgroup, input pixel groups per wave
-  bool second = false; int cpw = 1, nw = 0, gpw = 0, lds = 0; unsigned grid = 0;
-};
-static ExpDwLaunch resolve_expdw(const vbt_model*, const Step& s, int variant, int B) {
+ExpDwLaunch resolve_expdw(const vbt_model*, const Step& s, int variant, int B) {
   // VBT_XD_VARIANT (tests): that variant for every step that supports it, whatever the plan says
   static const int xd_force = getenv("VBT_XD_VARIANT") ? atoi(getenv("VBT_XD_VARIANT")) : -100;
   if (xd_force != -100 && (xd_force < 100 || (s.xd2_ok && (xd_force < 200 ? s.xd2_gpw > 0 : s.xd2_gpw16 > 0)))) variant = std::min(xd_force, xd_force / 100 * 100 + s.xd.nchunks);
@@ -519,14 +268,13 @@ static int launch_expdw_step(const vbt_model* m, const Step& s, int B, hipStream
 // SeparableConv / BiFPN node / head layer on row bands.  Variant: 0 = depthwise and projection as two stages around the LDS tile D,
 // 1 = chained (band_block.h; 64-channel maps with at most 64 output channels), -1: chained where it resolves and max_batch > 8, else two stages.  A step of several
 // problems carries one variant for all its members.
-struct BandLaunch : Verdict { bool chained = false; int lds = 0; };
 static bool band_chainable(const Step& s) {
   if (s.members.empty()) return s.bd_args.wpc != nullptr;
   for (const Step& ms : s.members)
     if (!ms.bd_args.wpc) return false;
   return true;
 }
-static BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, int) {
+BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, int) {
   BandLaunch L;
   const bool can = band_chainable(s);
   // what the plan asks for is judged as it stands, before any override: a variant that does not exist for the step is never offered
@@ -547,8 +295,8 @@ static BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, i
 // Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major): the batch-offset pointers here, the
 // variant and the launch in the family's own function above.  `frames` = frame boff, the first one of the range; the output pointers
 // are those of the whole batch.
-static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_t* frames, float* boxes, float* scores,
-                       float* classes, int* counts, int boff = 0) {
+int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_t* frames, float* boxes, float* scores, float* classes,
+                int* counts, int boff) {
   if (m->pool_dirty) { const int rc = flush_uploads(m); if (rc) return rc; }
   const OpRec& op = m->ops[s.op];
   const TensorRec& to = m->tensors[op.output];
@@ -703,232 +451,34 @@ static int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const
   return VBT_OK;
 }
 
-// VBT_AUTOTUNE_CONCURRENCY=n (default 1): time each candidate with n copies in flight on n streams (same buffers, same
-// results) and rank by time per copy, i.e. by throughput under contention - what a pipelined caller (Pipeline depth n)
-// experiences - instead of by isolated latency.
-static double time_step(vbt_model* m, const Step& s, int B, int reps) {
-  static int nconc = -1;
-  static hipStream_t cs[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (nconc < 0) {
-    const char* e = getenv("VBT_AUTOTUNE_CONCURRENCY");
-    nconc = e ? std::max(1, std::min(4, atoi(e))) : 1;
-    if (nconc > 1)
-      for (int i = 0; i < nconc; i++) (void)hipStreamCreateWithFlags(&cs[i], hipStreamNonBlocking);
-  }
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 1e30;
-  float ms = 1e30f;
-  int rc = VBT_OK;   // a refused launch (nothing enqueued) makes the candidate unusable, not fast
-  if (nconc <= 1) {
-    rc = launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-    (void)hipEventRecord(e0, nullptr);
-    for (int r = 0; r < reps && !rc; r++)
-      rc = launch_step(m, s, B, nullptr, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-    (void)hipEventRecord(e1, nullptr);
-    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 1e30f;
-    ms /= reps;
-  } else {
-    (void)hipDeviceSynchronize();
-    for (int i = 0; i < nconc && !rc; i++)
-      rc = launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-    (void)hipDeviceSynchronize();
-    auto t0 = std::chrono::steady_clock::now();
-    for (int r = 0; r < reps; r++)
-      for (int i = 0; i < nconc && !rc; i++)
-        rc = launch_step(m, s, B, cs[i], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-    (void)hipDeviceSynchronize();
-    ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (reps * nconc));
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return rc ? 1e30 : ms;
-}
-
-static bool is_fused_tile(int family) { return family == F_MBCONV || family == F_SEPCONV || family == F_NODE; }
-// whether `v` resolves to a launch of this step (the depthwise resolver and the families without one take any value)
-static bool variant_ok(const vbt_model* m, const Step& st, int v) {
-  if (st.family == F_PW) return !st.members.empty() || !resolve_pw(m, st, v, m->max_batch).rc;
-  if (is_fused_tile(st.family)) return !resolve_fused(m, st, v, m->max_batch).rc;
-  if (st.family == F_BAND) return !resolve_band(m, st, v, m->max_batch).rc;
-  return st.family != F_EXPDW || !resolve_expdw(m, st, v, m->max_batch).rc;
-}
-
-// Plan-time autotuning: every alternative computes bit-identical tensors, so only speed is at stake.
-// Kernel variants the planner offers for a step: what the autotuner times, and (with the rest of the fused tile kernels' flag
-// combinations) what a plan file may select: load_plan.  -1 = the launcher's own default.  Only values that resolve are offered.
-static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
-  std::vector<int> cand{-1};
-  const OpRec& op = m->ops[st.op];
-  if (st.family == F_DW) {
-    cand = {0};
-    for (int r : {1, 2, 4, 8, 16})
-      if (r <= m->tensors[op.output].h) cand.push_back(r);
-    if (m->tensors[op.output].c % 8 == 0) { cand.push_back(100); cand.push_back(101); }
-  } else if (st.family == F_PW && st.KS64 <= 4) {
-    cand = {0, 1};
-  } else if (st.family == F_PW) {
-    cand = {-1, 2, 3, 4, 5, 6};
-  } else if (is_fused_tile(st.family)) {
-    cand = {0, 1, 3, 5};   // VALU dw, matrix-pipe dw, matrix-pipe dw + half-height tile, one workgroup per image
-    if (st.family == F_MBCONV && st.fa.nch3 > 0 && st.nbp <= 2 && st.fa.KSe >= 1 && st.fa.KSe <= 4) { cand.push_back(9); cand.push_back(11); }  // 48-channel chunks
-    if (st.family == F_MBCONV && st.nbp <= 2 && (st.fa.KSe == 1 || st.fa.KSe == 2)) {   // 128-pixel tiles
-      cand.push_back(17);
-      if (st.fa.nch3 > 0) cand.push_back(25);
-    }
-    if (st.family == F_MBCONV && st.fa.wtz) cand.insert(cand.end(), {33, 41, 49, 57});   // Toeplitz depthwise on the four DW64 forms
-  } else if (st.family == F_MULTI) {
-    cand = {0, 1};
-  } else if (st.family == F_EXPDW) {
-    cand.clear();
-    for (int cpw : {1, 2, 3, 4, 6})
-      if (cpw <= st.xd.nchunks) cand.push_back(cpw);
-    if (st.xd2_ok)
-      for (int cpw : {1, 2, 3, 4, 6})
-        if (cpw <= st.xd.nchunks) {
-          if (st.xd2_gpw > 0) cand.push_back(100 + cpw);
-          if (st.xd2_gpw16 > 0) cand.push_back(200 + cpw);
-        }
-  } else if (st.family == F_BAND) {
-    cand = {-1, 0, 1};   // the launch kind's default, two stages, chained (64-channel maps only)
-  }
-  cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int v) { return !variant_ok(m, st, v); }), cand.end());
-  return cand;
-}
-
-static void autotune(vbt_model* m) {
-  const int B = (m->max_batch + m->n_sub - 1) / m->n_sub, reps = 4;  // the batch one stream actually sees
-  for (Group& g : m->groups) {
-    bool single = g.alts.size() == 1 && g.alts[0].steps.size() == 1;
-    if (single) {
-      int f = g.alts[0].steps[0].family;
-      if (f != F_DW && f != F_PW) continue;  // nothing to choose
-    }
-    for (Alt& a : g.alts) {
-      a.ms = 0;
-      for (Step& st : a.steps) {
-        const std::vector<int> cand = candidate_variants(m, st);
-        double best = 1e30;
-        int bestv = -1;
-        for (int v : cand) {
-          Step t = st;
-          t.variant = v;
-          double ms = time_step(m, t, B, reps);
-          if (getenv("VBT_AUTOTUNE_VERBOSE") && cand.size() > 1 && atoi(getenv("VBT_AUTOTUNE_VERBOSE")) > 1)
-            fprintf(stderr, "[autotune]   op %d %s v%d %.1fus\n", st.op, kFamilyName[st.family], v, ms * 1e3);
-          if (ms < best) { best = ms; bestv = v; }
-        }
-        st.variant = bestv;
-        st.tuned_ms = best;
-        a.ms += best;
-      }
-    }
-    int bi = 0;
-    for (size_t i = 1; i < g.alts.size(); i++)
-      if (g.alts[i].ms < g.alts[bi].ms) bi = (int)i;
-    g.chosen = bi;
-    if (getenv("VBT_AUTOTUNE_VERBOSE")) {
-      const Step& f = g.alts[0].steps[0];
-      const TensorRec& to = m->tensors[m->ops[g.alts[0].steps.back().op].output];
-      fprintf(stderr, "[autotune] op %3d.. out %3dx%3dx%4d :", f.op, to.h, to.w, to.c);
-      for (size_t i = 0; i < g.alts.size(); i++) {
-        fprintf(stderr, " alt%zu%s %.1fus(", i, (int)i == bi ? "*" : "", g.alts[i].ms * 1e3);
-        for (const Step& st : g.alts[i].steps) fprintf(stderr, "%s:v%d=%.1f ", kFamilyName[st.family], st.variant, st.tuned_ms * 1e3);
-        fprintf(stderr, ")");
-      }
-      fprintf(stderr, "\n");
-    }
-  }
-  (void)hipDeviceSynchronize();
-}
-
-// Plan cache.  Format 2 (written): "VBTPLAN2 <ngroups>" then per group "<chosen alternative> <nsteps> <family>:<variant> ..." - the
-// kernel family of every step of the chosen alternative by NAME, so that a file tuned for another build of the planner (an
-// alternative added, removed or re-ordered: the bare indices of format 1 would still load and silently select other kernels) is
-// refused and the plan re-tuned.  Format 1 ("<ngroups>" then "<chosen> <nsteps> <variant>...") is still read - the group and step
-// counts are all it can be checked against - and re-written in format 2 when VBT_PLAN_CONVERT is set.
-// The shape a file may select from: this library's groups, their alternatives, the family of every step and the variants that resolve
-// for it (container_parse.h: parse_plan_file refuses everything else, and the model is tuned afresh).  vbt_model_plan_space reports it.
-static PlanShape plan_shape(const vbt_model* m) {
-  PlanShape shape;
-  for (const Group& g : m->groups) {
-    std::vector<std::vector<PlanStepShape>> alts;
-    for (const Alt& a : g.alts) {
-      std::vector<PlanStepShape> steps;
-      for (const Step& st : a.steps) {
-        PlanStepShape ps;
-        ps.family = kFamilyName[st.family];
-        ps.variants = candidate_variants(m, st);
-        auto add = [&](int v) { if (std::find(ps.variants.begin(), ps.variants.end(), v) == ps.variants.end()) ps.variants.push_back(v); };
-        // the fused tile kernels read their variant as a set of flags (resolve_fused): plans searched under load (tools/tune_under_load.py)
-        // hold combinations the isolated autotuner does not time, and every combination that resolves is accepted
-        for (int v = 0; v < 64 && is_fused_tile(st.family); v++)
-          if (variant_ok(m, st, v)) add(v);
-        add(-1);
-        add(st.variant);   // the heuristic plan's own choice
-        steps.push_back(ps);
-      }
-      alts.push_back(steps);
-    }
-    shape.groups.push_back(alts);
-  }
-  return shape;
-}
-static bool load_plan(vbt_model* m, const char* path) {
-  const PlanShape shape = plan_shape(m);
-  std::vector<PlanChoice> sel;
-  std::string note;
-  if (!parse_plan_file(path, shape, &sel, &note)) {
-    if (note != "no such file") fprintf(stderr, "[vbt] plan %s: %s - plan refused, re-tuning\n", path, note.c_str());
-    return false;
-  }
-  for (size_t gi = 0; gi < m->groups.size(); gi++) {
-    m->groups[gi].chosen = sel[gi].chosen;
-    Alt& a = m->groups[gi].alts[(size_t)sel[gi].chosen];
-    for (size_t i = 0; i < a.steps.size(); i++) a.steps[i].variant = sel[gi].variants[i];
-  }
-  return true;
-}
-static void save_plan(const vbt_model* m, const char* path) {
-  FILE* f = fopen(path, "w");
-  if (!f) return;
-  fprintf(f, "VBTPLAN2 %d\n", (int)m->groups.size());
-  for (const Group& g : m->groups) {
-    const Alt& a = g.alts[g.chosen];
-    fprintf(f, "%d %d", g.chosen, (int)a.steps.size());
-    for (const Step& st : a.steps) fprintf(f, " %s:%d", kFamilyName[st.family], st.variant);
-    fprintf(f, "\n");
-  }
-  fclose(f);
-}
-
-static int enqueue_forward(vbt_model* m, const uint8_t* frames_dev, int B, hipStream_t st, float* boxes, float* scores,
-                           float* classes, int* counts, hipEvent_t* evs) {
+int enqueue_forward(vbt_model* m, const uint8_t* frames_dev, int B, hipStream_t st, float* boxes, float* scores, float* classes, int* counts,
+                    const Event* evs) {
   const int nsub = (!evs && m->n_sub > 1 && B >= 2 * m->n_sub) ? m->n_sub : 1;
   if (nsub == 1) {
     int i = 0;
     for (const Step& s : m->steps) {
-      if (evs) (void)hipEventRecord(evs[i], st);
+      if (evs) (void)hipEventRecord(evs[i].get(), st);
       int rc = launch_step(m, s, B, st, frames_dev, boxes, scores, classes, counts);
       if (rc) return rc;
       i++;
     }
-    if (evs) (void)hipEventRecord(evs[i], st);
+    if (evs) (void)hipEventRecord(evs[i].get(), st);
   } else {
     // Independent sub-batches on side streams: the many small, latency-bound kernels of one sub-batch overlap
     // with the other's.  Fork from / join into the caller's stream with events.
-    (void)hipEventRecord(m->ev_fork, st);
+    (void)hipEventRecord(m->ev_fork.get(), st);
     const int per = (B + nsub - 1) / nsub;
     for (int k = 0; k < nsub; k++) {
       const int b0 = k * per, bk = std::min(per, B - b0);
       if (bk <= 0) break;
-      hipStream_t ss = m->sub_streams[k];
-      (void)hipStreamWaitEvent(ss, m->ev_fork, 0);
+      hipStream_t ss = m->sub_streams[k].get();
+      (void)hipStreamWaitEvent(ss, m->ev_fork.get(), 0);
       for (const Step& s : m->steps) {
         int rc = launch_step(m, s, bk, ss, frames_dev + (size_t)b0 * m->hdr.image_size * m->hdr.image_size * 3, boxes, scores, classes, counts, b0);
         if (rc) return rc;
       }
-      (void)hipEventRecord(m->ev_join[k], ss);
-      (void)hipStreamWaitEvent(st, m->ev_join[k], 0);
+      (void)hipEventRecord(m->ev_join[k].get(), ss);
+      (void)hipStreamWaitEvent(st, m->ev_join[k].get(), 0);
     }
   }
   VBT_HIP_CHECK(hipGetLastError());
@@ -954,10 +504,7 @@ static int forward(vbt_model* m, const uint8_t* frames_dev, int B, hipStream_t s
   vbt_model::GraphKey key{frames_dev, boxes, scores, classes, counts, B};
   auto it = m->graphs.find(key);
   if (it == m->graphs.end()) {
-    if (m->graphs.size() >= 256) {  // bounded cache
-      for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-      m->graphs.clear();
-    }
+    if (m->graphs.size() >= 256) m->clear_graphs();  // bounded cache
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     if (!m->ran_eager) {
@@ -967,9 +514,9 @@ static int forward(vbt_model* m, const uint8_t* frames_dev, int B, hipStream_t s
       if (rc0) return rc0;
       m->ran_eager = true;
     }
-    VBT_HIP_CHECK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_forward(m, frames_dev, B, m->cap_stream, boxes, scores, classes, counts, nullptr);
-    hipError_t e = hipStreamEndCapture(m->cap_stream, &g);
+    VBT_HIP_CHECK(hipStreamBeginCapture(m->cap_stream.get(), hipStreamCaptureModeThreadLocal));
+    int rc = enqueue_forward(m, frames_dev, B, m->cap_stream.get(), boxes, scores, classes, counts, nullptr);
+    hipError_t e = hipStreamEndCapture(m->cap_stream.get(), &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
     e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
@@ -984,237 +531,12 @@ static int forward(vbt_model* m, const uint8_t* frames_dev, int B, hipStream_t s
 
 }  // namespace vbt
 
+using namespace vbt;
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
 extern "C" {
-
-const char* vbt_last_error(void) { return vbt::g_err; }
-
-int vbt_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int vbt_model_create(const char* path, int device, int max_batch, vbt_model** out) {
-  const char* nf = getenv("VBT_FUSION_FLAGS");  // bit0: no fusion, bit1: no MBConv fusion, bit2: no SeparableConv fusion
-  return vbt_model_create_ex(path, device, max_batch, nf ? atoi(nf) : VBT_MODEL_DEFAULT_FLAGS, out);
-}
-
-int vbt_model_tensor_materialized(const vbt_model* m, int id) {
-  if (!m || id < 0 || id >= (int)m->tensors.size()) { set_error("bad tensor id"); return VBT_ERR_ARG; }
-  return m->materialized[id] ? 1 : 0;
-}
-
-int vbt_model_num_launches(const vbt_model* m) { return m ? (int)m->steps.size() : VBT_ERR_ARG; }
-
-int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, int* n) {
-  if (!m || !n || cap < 0 || (cap > 0 && !out)) { set_error("vbt_model_plan_space: bad argument"); return VBT_ERR_ARG; }
-  const PlanShape shape = plan_shape(m);
-  int total = 0;
-  for (const auto& alts : shape.groups)
-    for (const auto& steps : alts) total += (int)steps.size();
-  *n = total;
-  if (total > cap) { set_error("plan space: %d steps, buffer holds %d", total, cap); return VBT_ERR_CAPACITY; }
-  int i = 0;
-  for (size_t gi = 0; gi < shape.groups.size(); gi++)
-    for (size_t ai = 0; ai < shape.groups[gi].size(); ai++)
-      for (size_t si = 0; si < shape.groups[gi][ai].size(); si++, i++) {
-        const PlanStepShape& ps = shape.groups[gi][ai][si];
-        vbt_plan_step_space& o = out[i];
-        memset(&o, 0, sizeof(o));
-        if (ps.variants.size() > sizeof(o.variants) / sizeof(o.variants[0])) {
-          set_error("plan space: group %zu alternative %zu step %zu has %zu variants", gi, ai, si, ps.variants.size());
-          return VBT_ERR_CAPACITY;
-        }
-        o.group = (int)gi; o.alt = (int)ai; o.step = (int)si;
-        o.chosen = m->groups[gi].chosen == (int)ai;
-        const Step& st = m->groups[gi].alts[ai].steps[si];
-        o.variant = st.variant;
-        o.first_op = (int)m->ops.size(); o.last_op = -1;
-        std::function<void(const Step&)> span = [&](const Step& s) {
-          for (int op : {s.op, s.e_op, s.d_op, s.p_op, s.a_op, s.sum_op})
-            if (op >= 0) { o.first_op = std::min(o.first_op, op); o.last_op = std::max(o.last_op, op); }
-          for (const Step& mb : s.members) span(mb);
-        };
-        span(st);
-        snprintf(o.family, sizeof(o.family), "%s", ps.family.c_str());
-        o.n_variants = (int)ps.variants.size();
-        std::copy(ps.variants.begin(), ps.variants.end(), o.variants);
-      }
-  return VBT_OK;
-}
-
-int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, vbt_model** out) {
-  if (!path || !out || max_batch < 1) { set_error("vbt_model_create: bad argument"); return VBT_ERR_ARG; }
-  *out = nullptr;
-  vbt_model* m = new vbt_model();
-  {
-    // reader + structural validation (container_parse.h): every index the planner and the kernels follow is in range before they see it
-    ContainerData cd;
-    std::string why;
-    if (!read_container(path, &cd, &why)) { delete m; set_error("%s", why.c_str()); return VBT_ERR_IO; }
-    m->hdr = cd.hdr;
-    m->tensors.swap(cd.tensors);
-    m->ops.swap(cd.ops);
-    m->blob.swap(cd.blob);
-  }
-  m->device = device;
-  m->max_batch = max_batch;
-  m->flags = flags;
-  if (int drc = use_device("vbt_model_create", device, /*set_current=*/false)) { delete m; return drc; }
-  int rc = VBT_OK;
-  auto fail = [&](int code) { vbt_model_destroy(m); return code; };
-  if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return fail(VBT_ERR_HIP); }
-  // activation arena: every graph tensor keeps its own [max_batch][h][w][c] int8 buffer
-  size_t total = 0;
-  m->telems.resize(m->tensors.size());
-  std::vector<size_t> off(m->tensors.size());
-  for (size_t i = 0; i < m->tensors.size(); i++) {
-    const TensorRec& t = m->tensors[i];
-    m->telems[i] = (size_t)t.h * t.w * t.c;
-    off[i] = total;
-    size_t bytes = (int)i == m->hdr.input_tensor ? 0 : m->telems[i] * max_batch;
-    total += (bytes + 255) / 256 * 256 + 256;
-  }
-  if (fenced_malloc(m, (void**)&m->arena, total + 4096) != hipSuccess) { set_error("hipMalloc(%zu) for activations failed", total); return fail(VBT_ERR_HIP); }
-  (void)hipMemset(m->arena, 0, total + 4096);
-  m->tptr.resize(m->tensors.size());
-  for (size_t i = 0; i < m->tensors.size(); i++) m->tptr[i] = m->arena + off[i];
-  size_t fbytes = (size_t)max_batch * m->hdr.image_size * m->hdr.image_size * 3;
-  const int md = m->hdr.max_detections;
-  m->out_bytes = (size_t)max_batch * (md * 24 + 4);
-  if (fenced_malloc(m, (void**)&m->frames_stage, fbytes + 64) != hipSuccess || hipMalloc((void**)&m->out_boxes, m->out_bytes) != hipSuccess ||
-      hipHostMalloc((void**)&m->out_host, m->out_bytes, hipHostMallocDefault) != hipSuccess) {
-    set_error("hipMalloc for staging buffers failed");
-    return fail(VBT_ERR_HIP);
-  }
-  m->out_scores = m->out_boxes + (size_t)max_batch * md * 4;
-  m->out_classes = m->out_scores + (size_t)max_batch * md;
-  m->out_counts = (int*)(m->out_classes + (size_t)max_batch * md);
-  if ((rc = build_plan(m)) != VBT_OK) return fail(rc);
-  for (const OpRec& op : m->ops)
-    if (op.type == OP_POSTPROCESS) {
-      std::vector<float> an((const float*)(m->blob.data() + op.aux_off), (const float*)(m->blob.data() + op.aux_off) + (size_t)m->hdr.num_anchors * 4);
-      if ((size_t)op.aux2_off + VBT_POST_TABLE_BYTES > m->blob.size()) { set_error("post-process tables truncated"); return fail(VBT_ERR_IO); }
-      std::vector<unsigned char> lut(m->blob.data() + op.aux2_off, m->blob.data() + op.aux2_off + VBT_POST_TABLE_BYTES);
-      const float* sv = (const float*)(lut.data() + 6144);
-      if (sv[0] != sv[1] || sv[2] != sv[3]) { set_error("post-process: y_scale != x_scale or h_scale != w_scale"); return fail(VBT_ERR_ARG); }
-      {
-        // The stored tables are checked, not trusted: every entry is derived again from the quantisation of the class and
-        // box tensors (XNNPACK's x8 LOGISTIC table in float32 with glibc expf; DEQUANTIZE as one float32 product; the
-        // decode's divisions and exp() in double, detection_postprocess.cc) and a container that differs is refused.
-        const int nl = op.n_inputs / 2;
-        const TensorRec& tc = m->tensors[op.inputs[0]];
-        const TensorRec& tb = m->tensors[op.inputs[nl]];
-        for (int l = 1; l < nl; l++) {   // CONCATENATION: one quantisation for all of its inputs
-          const TensorRec &c2 = m->tensors[op.inputs[l]], &b2 = m->tensors[op.inputs[nl + l]];
-          if (c2.scale != tc.scale || c2.zero_point != tc.zero_point || b2.scale != tb.scale || b2.zero_point != tb.zero_point) {
-            set_error("post-process: head outputs of level %d are quantised differently from level 0", l);
-            return fail(VBT_ERR_ARG);
-          }
-        }
-        const float* st_score = (const float*)lut.data();
-        const float* st_box = st_score + 256;
-        const double* st_dq = (const double*)(lut.data() + 2048);
-        const double* st_ex = st_dq + 256;
-        for (int q = -128; q < 128; q++) {
-          const float x = tc.scale * (float)(q - tc.zero_point);
-          float y = 256.0f / (1.0f + expf(-x));
-          y = y < 0.0f ? 0.0f : (y > 255.0f ? 255.0f : y);
-          const float want_score = (1.0f / 256.0f) * (float)lrintf(y);
-          const float want_box = tb.scale * (float)(q - tb.zero_point);
-          const double want_dq = (double)want_box / (double)sv[0];
-          const double want_ex = exp((double)want_box / (double)sv[2]);
-          if (st_score[q + 128] != want_score || st_box[q + 128] != want_box || st_dq[q + 128] != want_dq || st_ex[q + 128] != want_ex) {
-            set_error("post-process: stored table entry %d differs from the one derived from the tensor scales", q);
-            return fail(VBT_ERR_ARG);
-          }
-        }
-      }
-      // device tables: scores re-indexed by rank byte, decode tables, class byte -> rank byte
-      std::vector<unsigned char> dev(1024 + 2048 + 2048 + 256, 0);
-      const float* score = (const float*)lut.data();
-      float* score_by_rank = (float*)dev.data();
-      signed char* rank = (signed char*)(dev.data() + 5120);
-      for (int q = 1; q < 256; q++)
-        if (score[q] < score[q - 1]) { set_error("post-process: score table is not monotone"); return fail(VBT_ERR_ARG); }
-      int r = 127;   // highest class byte gets rank 127; a strictly lower score steps the rank down
-      for (int q = 255; q >= 0; q--) {
-        if (q < 255 && score[q] != score[q + 1]) r--;
-        rank[q] = (signed char)r;
-        score_by_rank[r + 128] = score[q];
-      }
-      for (int i = -128; i < r; i++) score_by_rank[i + 128] = -1.0f;   // unused rank bytes: below every threshold
-      memcpy(dev.data() + 1024, lut.data() + 2048, 4096);
-      if ((rc = upload(m, an, &m->d_anchors)) || (rc = upload(m, dev, &m->d_luts))) return fail(rc);
-      m->post_tables_host.assign(score_by_rank, score_by_rank + 256);
-    }
-  {
-    const char* ns = getenv("VBT_SUBSTREAMS");
-    int want = ns ? atoi(ns) : 1;  // side streams measured no gain on MI355X at B = 64 (the GPU is busy, not starved)
-    if (m->flags & VBT_MODEL_SINGLE_STREAM) want = 1;
-    m->n_sub = std::max(1, std::min(want, 4));
-    if (max_batch < 2 * m->n_sub) m->n_sub = 1;
-    if (m->n_sub > 1) {
-      bool ok = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess;
-      for (int k = 0; k < m->n_sub && ok; k++)
-        ok = hipStreamCreateWithFlags(&m->sub_streams[k], hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_join[k], hipEventDisableTiming) == hipSuccess;
-      if (!ok) { set_error("cannot create side streams"); return fail(VBT_ERR_HIP); }
-    }
-  }
-  {
-    const char* gm = getenv("VBT_GRAPH_MAX_BATCH");
-    m->graph_max_batch = (m->flags & VBT_MODEL_NO_GRAPH) ? 0 : (gm ? atoi(gm) : 8);
-    if (m->graph_max_batch > 0 && hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking) != hipSuccess) m->cap_stream = nullptr;
-  }
-  if (!(m->flags & VBT_MODEL_NO_AUTOTUNE)) {
-    // VBT_PLAN_FILE: reuse a previously tuned plan (keeps profiled and un-profiled runs on the same kernels)
-    const char* pf = getenv("VBT_PLAN_FILE");
-    char path[1024];
-    if (pf) snprintf(path, sizeof(path), "%s.b%d.f%d", pf, max_batch, m->flags);
-    if (!pf || !load_plan(m, path)) {
-      autotune(m);
-      if (pf) save_plan(m, path);
-    } else if (getenv("VBT_PLAN_CONVERT")) {
-      save_plan(m, path);       // a format-1 file comes back in format 2 (same choices, kernel families by name)
-    }
-  }
-  finalize_plan(m);
-  if ((rc = flush_uploads(m)) != VBT_OK) return fail(rc);
-  *out = m;
-  return VBT_OK;
-}
-
-void vbt_model_destroy(vbt_model* m) {
-  if (!m) return;
-  for (int k = 0; k < 4; k++) {
-    if (m->sub_streams[k]) (void)hipStreamDestroy(m->sub_streams[k]);
-    if (m->ev_join[k]) (void)hipEventDestroy(m->ev_join[k]);
-  }
-  if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-  for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-  if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
-  for (void* p : m->owned) (void)hipFree(p);
-  (void)hipFree(m->out_boxes);  // (one block: boxes | scores | classes | counts); arena and frames_stage are in `owned`
-  if (m->out_host) (void)hipHostFree(m->out_host);
-  delete m;
-}
-
-int vbt_model_input_shape(const vbt_model* m, int shape[4]) {
-  if (!m || !shape) { set_error("bad argument"); return VBT_ERR_ARG; }
-  shape[0] = m->max_batch; shape[1] = m->hdr.image_size; shape[2] = m->hdr.image_size; shape[3] = 3;
-  return VBT_OK;
-}
-int vbt_model_num_tensors(const vbt_model* m) { return m ? (int)m->tensors.size() : VBT_ERR_ARG; }
-int vbt_model_num_ops(const vbt_model* m) { return m ? (int)m->ops.size() : VBT_ERR_ARG; }
-int vbt_model_tensor_shape(const vbt_model* m, int id, int shape[3]) {
-  if (!m || !shape || id < 0 || id >= (int)m->tensors.size()) { set_error("bad tensor id"); return VBT_ERR_ARG; }
-  shape[0] = m->tensors[id].h; shape[1] = m->tensors[id].w; shape[2] = m->tensors[id].c;
-  return VBT_OK;
-}
 
 int vbt_detect_async(vbt_model* m, const uint8_t* frames_dev, int B, void* stream, float* boxes, float* scores, float* classes,
                      int32_t* counts) {
@@ -1273,7 +595,7 @@ int vbt_detect(vbt_model* m, const uint8_t* frames, int B, int frames_on_device,
     const int md = m->hdr.max_detections;
     const size_t mb = (size_t)m->max_batch;
     const unsigned char* d = (const unsigned char*)m->out_boxes;
-    unsigned char* h = m->out_host;
+    unsigned char* h = m->out_host.get();
     if (B == m->max_batch) {
       VBT_HIP_CHECK(hipMemcpyAsync(h, d, m->out_bytes, hipMemcpyDeviceToHost, st));
     } else {   // only the B-frame prefix of each of the four tensors (an interpreter created for 256 frames and called with 1 moved 615 KB)
@@ -1295,48 +617,6 @@ int vbt_model_read_tensor(vbt_model* m, int id, int B, int8_t* host_out) {
   if (!m->materialized[id]) { set_error("tensor %d lives only in LDS (fused away); create the model with VBT_MODEL_NO_FUSION to read it", id); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipDeviceSynchronize());
   VBT_HIP_CHECK(hipMemcpy(host_out, m->tptr[id], m->telems[id] * B, hipMemcpyDeviceToHost));
-  return VBT_OK;
-}
-
-// A HIP stream gets its hardware queue at its FIRST command, round-robin over GPU_MAX_HW_QUEUES (rocprofv3 Queue_Id).  Streams
-// drawn from a framework's pool may have been used before, so a pipeline's streams can land on one queue and serialise
-// (measured: 89 k -> 58 k frames/s).  Streams created here run one empty launch at once: streams created back to back sit on
-// consecutive queues.
-__global__ void stream_touch_kernel() {}
-int vbt_stream_create(int device, void** stream_out) {
-  if (!stream_out) { set_error("vbt_stream_create: NULL argument"); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  VBT_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  stream_touch_kernel<<<1, 64, 0, st>>>();
-  hipError_t e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { (void)hipStreamDestroy(st); set_error("vbt_stream_create: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
-  *stream_out = (void*)st;
-  return VBT_OK;
-}
-// Do two streams share a hardware queue?  A single-wave kernel that spins for `us` microseconds on each: side by side they
-// take `us`, on one in-order queue 2 x `us`.  (The queue of a stream cannot be queried; GPU otherwise idle when called.)
-__global__ void stream_spin_kernel(long ticks) {
-  const long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-int vbt_streams_share_queue(void* a, void* b, int us, int* shared) {
-  if (!a || !b || !shared || us < 20 || us > 100000) { set_error("vbt_streams_share_queue: bad argument"); return VBT_ERR_ARG; }
-  const long ticks = (long)us * 100;   // wall_clock64: 100 MHz
-  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)a));
-  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)b));
-  auto t0 = std::chrono::steady_clock::now();
-  stream_spin_kernel<<<1, 64, 0, (hipStream_t)a>>>(ticks);
-  stream_spin_kernel<<<1, 64, 0, (hipStream_t)b>>>(ticks);
-  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)a));
-  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)b));
-  const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-  *shared = el > 1.6 * us ? 1 : 0;
-  return VBT_OK;
-}
-int vbt_stream_destroy(void* stream) {
-  if (!stream) return VBT_OK;
-  VBT_HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
   return VBT_OK;
 }
 
@@ -1386,145 +666,5 @@ int vbt_post_prof_read(unsigned long long* out16, int reset) {
   return VBT_OK;
 }
 #endif
-
-int vbt_model_kernel_stats(const vbt_model* m, int B, vbt_kernel_stat* out, int cap, int* n) {
-  if (!m || !out || !n || cap < F_COUNT) { set_error("bad argument"); return VBT_ERR_ARG; }
-  for (int i = 0; i < F_COUNT; i++) {
-    memset(&out[i], 0, sizeof(out[i]));
-    snprintf(out[i].name, sizeof(out[i].name), "%s", kFamilyName[i]);
-  }
-  for (const Step& s : m->steps) {
-    out[s.family].launches++;
-    out[s.family].algorithmic_bytes += s.cost.alg_bytes_per_frame * B + s.cost.weight_bytes;
-    out[s.family].macs += s.cost.macs_per_frame * B;
-  }
-  *n = F_COUNT;
-  return VBT_OK;
-}
-
-int vbt_model_profile(vbt_model* m, const uint8_t* frames_dev, int B, int reps, void* stream, double* ms_out, int cap) {
-  if (!m || !frames_dev || !ms_out || cap < F_COUNT || reps < 1) { set_error("bad argument"); return VBT_ERR_ARG; }
-  if (B < 1 || B > m->max_batch) { set_error("bad batch"); return VBT_ERR_CAPACITY; }
-  hipStream_t st = (hipStream_t)stream;
-  const int ns = (int)m->steps.size();
-  std::vector<hipEvent_t> evs(ns + 1);
-  for (auto& e : evs) VBT_HIP_CHECK(hipEventCreate(&e));
-  for (int i = 0; i < F_COUNT; i++) ms_out[i] = 0.0;
-  int rc = VBT_OK;
-  for (int r = 0; r < reps && rc == VBT_OK; r++) {
-    rc = enqueue_forward(m, frames_dev, B, st, m->out_boxes, m->out_scores, m->out_classes, m->out_counts, evs.data());
-    if (rc) break;
-    if (hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); rc = VBT_ERR_HIP; break; }
-    for (int i = 0; i < ns; i++) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
-      ms_out[m->steps[i].family] += ms;
-    }
-  }
-  for (auto& e : evs) (void)hipEventDestroy(e);
-  for (int i = 0; i < F_COUNT; i++) ms_out[i] /= reps;
-  return rc;
-}
-
-// One bracket per kernel family: all launches of family i of the plan back to back on `stream` (`reps` passes between ONE pair
-// of HIP events), so ms_out[i] / launches is an average launch duration without the ~3 us a pair of events around every short
-// launch adds - the figure rocprofv3 --kernel-trace reports for the same kernels (profiles/) to within the dispatch gap.
-int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, double* ms_out, int cap) {
-  if (!m || !ms_out || cap < F_COUNT || reps < 1) { set_error("bad argument"); return VBT_ERR_ARG; }
-  if (B < 1 || B > m->max_batch) { set_error("bad batch"); return VBT_ERR_CAPACITY; }
-  hipStream_t st = (hipStream_t)stream;
-  hipEvent_t e0, e1;
-  VBT_HIP_CHECK(hipEventCreate(&e0));
-  VBT_HIP_CHECK(hipEventCreate(&e1));
-  int rc = VBT_OK;
-  for (int f = 0; f < F_COUNT && rc == VBT_OK; f++) {
-    ms_out[f] = 0.0;
-    bool any = false;
-    for (const Step& s : m->steps) any |= s.family == f;
-    if (!any) continue;
-    for (int pass = 0; pass < 2 && rc == VBT_OK; pass++) {   // pass 0: warm (code objects, caches)
-      const int n = pass == 0 ? 1 : reps;
-      (void)hipEventRecord(e0, st);
-      for (int r = 0; r < n && rc == VBT_OK; r++)
-        for (const Step& s : m->steps)
-          if (s.family == f && rc == VBT_OK) rc = launch_step(m, s, B, st, m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-      (void)hipEventRecord(e1, st);
-      if (hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); rc = VBT_ERR_HIP; break; }
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      if (pass == 1) ms_out[f] = (double)ms / reps;
-    }
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return rc;
-}
-
-// Per-launch timing of the plan (one forward in flight, HIP events around every launch): step i of the execution list ->
-// family name, index of the last graph op it covers, kernel variant and milliseconds (average over `reps`).
-int vbt_model_profile_steps(vbt_model* m, const uint8_t* frames_dev, int B, int reps, void* stream, vbt_step_time* out, int cap, int* n) {
-  if (!m || !frames_dev || !out || !n || reps < 1) { set_error("bad argument"); return VBT_ERR_ARG; }
-  if (B < 1 || B > m->max_batch) { set_error("bad batch"); return VBT_ERR_CAPACITY; }
-  const int ns = (int)m->steps.size();
-  if (cap < ns) { set_error("%d plan steps, buffer holds %d", ns, cap); return VBT_ERR_CAPACITY; }
-  hipStream_t st = (hipStream_t)stream;
-  std::vector<hipEvent_t> evs(ns + 1);
-  for (auto& e : evs) VBT_HIP_CHECK(hipEventCreate(&e));
-  for (int i = 0; i < ns; i++) {
-    const Step& s = m->steps[i];
-    memset(&out[i], 0, sizeof(out[i]));
-    snprintf(out[i].family, sizeof(out[i].family), "%s", kFamilyName[s.family]);
-    out[i].op = s.op;
-    out[i].first_op = s.e_op >= 0 ? s.e_op : (s.sum_op >= 0 ? s.sum_op : (s.d_op >= 0 ? s.d_op : s.op));
-    out[i].variant = s.variant;
-    out[i].algorithmic_bytes = s.cost.alg_bytes_per_frame * B + s.cost.weight_bytes;
-    out[i].macs = s.cost.macs_per_frame * B;
-  }
-  int rc = VBT_OK;
-  for (int r = 0; r < reps && rc == VBT_OK; r++) {
-    rc = enqueue_forward(m, frames_dev, B, st, m->out_boxes, m->out_scores, m->out_classes, m->out_counts, evs.data());
-    if (rc) break;
-    if (hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); rc = VBT_ERR_HIP; break; }
-    for (int i = 0; i < ns; i++) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
-      out[i].ms += ms / reps;
-    }
-  }
-  for (auto& e : evs) (void)hipEventDestroy(e);
-  *n = ns;
-  return rc;
-}
-
-// Measurement: every plan step launched `reps` times back to back on ONE stream, then `reps` times on each of `nstreams`
-// streams at once.  conc_ms[i] (time per launch with the streams racing) against single_ms[i] says how much of step i a
-// second and third forward in flight can hide: equal -> the kernel saturates a resource, 1/nstreams -> pure latency.
-int vbt_model_profile_overlap(vbt_model* m, int B, int reps, int nstreams, float* single_ms, float* conc_ms, int cap, int* n) {
-  if (!m || !single_ms || !conc_ms || !n || reps < 1 || nstreams < 1 || nstreams > 8) { set_error("bad argument"); return VBT_ERR_ARG; }
-  if (B < 1 || B > m->max_batch) { set_error("bad batch"); return VBT_ERR_CAPACITY; }
-  const int ns = (int)m->steps.size();
-  if (cap < ns) { set_error("%d plan steps, buffer holds %d", ns, cap); return VBT_ERR_CAPACITY; }
-  std::vector<hipStream_t> ss(nstreams, nullptr);
-  for (auto& st : ss) VBT_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc = VBT_OK;
-  for (int i = 0; i < ns && rc == VBT_OK; i++) {
-    const Step& s = m->steps[i];
-    for (int pass = 0; pass < 2 && rc == VBT_OK; pass++) {
-      const int k = pass == 0 ? 1 : nstreams;
-      for (int j = 0; j < k && rc == VBT_OK; j++) rc = launch_step(m, s, B, ss[j], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-      if (rc) break;
-      VBT_HIP_CHECK(hipDeviceSynchronize());
-      auto t0 = std::chrono::steady_clock::now();
-      for (int r = 0; r < reps; r++)
-        for (int j = 0; j < k; j++) rc = rc ? rc : launch_step(m, s, B, ss[j], m->frames_stage, m->out_boxes, m->out_scores, m->out_classes, m->out_counts);
-      VBT_HIP_CHECK(hipDeviceSynchronize());
-      const float ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (reps * k));
-      (pass == 0 ? single_ms : conc_ms)[i] = ms;
-    }
-  }
-  for (auto& st : ss) (void)hipStreamDestroy(st);
-  *n = ns;
-  return rc;
-}
 
 }  // extern "C"

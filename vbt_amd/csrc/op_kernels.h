@@ -1,8 +1,11 @@
 // Single-op kernels of the int8 detector (one graph op per launch): pointwise convs on the 16x16x64 int8 MFMA (four forms), stem conv,
 // depthwise convs (row / column walkers), integer ADD, max pool, nearest-neighbour resize, decode + NMS, bilinear frame resize.
-// Included by detector.hip inside namespace vbt, after dev_common.h; the planner, the autotuner and the C ABI stay in detector.hip, the
-// fused kernel families in their own headers / translation units (launchers.h).
+// Included by detector.hip alone, which launches them; the fused kernel families are in their own headers / translation units
+// (launchers.h).
 #pragma once
+#include "launchers.h"   // dev_common.h + pk_max_u16 (fused_block.h)
+
+namespace vbt {
 
 // ------------------------------------------------------------------------------------------
 // pointwise conv on the gfx950 double-rate int8 MFMA (v_mfma_i32_16x16x64_i8: same 16 issue cycles as the legacy
@@ -1373,3 +1376,5 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
     d[swap_rb ? 2 - c : c] = (uint8_t)(int)v;
   }
 }
+
+}  // namespace vbt

@@ -1,7 +1,17 @@
 // The planner of the int8 detector: graph ops -> Steps (build_plan), groups of alternative realisations (fuse_plan, batch_heads) and
 // the execution list of the chosen ones (finalize_plan, merge_side_convs).  Host code only; the weight layouts are in weight_pack.h.
-// Included once by detector.hip inside namespace vbt, after Step / Group / vbt_model / upload().
-#pragma once
+// A unit of its own: build_plan and finalize_plan are what it exports (detector_model.h, with Step / Group / vbt_model / upload()); the
+// tile and LDS geometry it shares with the variant resolvers of detector.hip is in plan_geom.h.  No kernel is instantiated here.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <functional>
+#include <initializer_list>
+
+#include "detector_model.h"
+#include "weight_pack.h"   // the weight / bias layouts of every kernel family: one pure host function each
+
+namespace vbt {
 
 // Rq::kb (dev_common.h): the int32 accumulator of this conv, bias included, stays inside (-2^22, 2^22) for EVERY input.  Whatever way a
 // kernel folds the zero point into its bias, the value it requantises is sum_k (x_k - z_x) w_k + b with |x_k - z_x| <= 255, so
@@ -24,32 +34,7 @@ static int conv_kb(const vbt_model* m, const OpRec& op) {
 }
 
 // ---- fusion pass: MBConv (pw+relu6 -> dw -> pw [-> add]) and SeparableConv (dw -> pw) -> fused_block_kernel ----
-static void choose_tile(int OH, int OW, int KK, int S, bool expand, int* TXo, int* TYo, int slots = 64) {
-  double best = 1e300;
-  for (int TX = 1; TX <= std::min(OW, 64); TX++) {
-    int TXp = (TX + 3) & ~3;
-    int TY = std::min(OH, slots / TXp);
-    if (TY < 1) continue;
-    int tiles = ((OW + TX - 1) / TX) * ((OH + TY - 1) / TY);
-    int NPh = ((TXp - 1) * S + KK) * ((TY - 1) * S + KK);
-    // halo pixels cost expand work + LDS loads; every tile also pays the 64-slot depthwise/project work
-    double cost = tiles * ((expand ? 1.0 : 0.35) * NPh + (double)slots);
-    if (cost < best) { best = cost; *TXo = TX; *TYo = TY; }
-  }
-}
-
-// LDS bytes of one fused tile (fused_block.h): the input halo of a TX x TY tile (T0S bytes per pixel), the expanded halo (est bytes per
-// pixel; 0: no expand stage), the depthwise output of 64 * ppw pixels and, for a single-chunk SeparableConv / node, the projection
-// weights + bias / multipliers staged in LDS.  (Rounding the E rows up to 16 bytes changes only the 72-byte rows: FB_EST and 48 are
-// multiples of 16.)
-// e_bytes >= 0: the expanded halo takes that many bytes instead (the quad-planar E of the Toeplitz depthwise: tpz_geom).
-static int fused_tile_lds(const FusedArgs& a, int k, int stride, int TX, int TY, int est, int ppw, int nbp, int e_bytes = -1) {
-  const int TXp = (TX + 3) & ~3;
-  const int NPh = ((TXp - 1) * stride + k) * ((TY - 1) * stride + k);
-  int lds = ((NPh * a.T0S + 15) & ~15) + (e_bytes >= 0 ? e_bytes : ((NPh * est + 15) & ~15)) + ppw * 64 * FB_DST;
-  if (!est && a.nchunks == 1 && nbp <= 2) lds += nbp * (4096 + 512);
-  return lds;
-}
+// (choose_tile, fused_tile_lds and band_lds: plan_geom.h)
 
 // sources of a BiFPN node's sum.  pre_add >= 0: the sum is two chained binary ADDs (3-input sums of a TFLite graph):
 // sources 0,1 are the inputs of ops[pre_add], source 2 the other input of the final ADD, chain = 1|2 the position of the
@@ -252,12 +237,6 @@ static bool band_ok(const vbt_model* m, int d_op, int p_op) {
   return d.k == 3 && d.stride == 1 && d.pad_t == 1 && d.pad_l == 1 && ti.c % 8 == 0 && ti.c >= 16 && ti.c <= 128 && to.c <= 128 && to.h == ti.h &&
          to.w == ti.w && ti.w <= 160;
 }
-// chained: the form without the depthwise tile D, with the depthwise operands staged behind the projection panel instead (band_block.h)
-static int band_lds(const BandArgs& a, bool chained = false) {
-  const int NT = (a.Cout + 15) / 16;
-  const int t0 = (a.rows + 2) * (a.W + 2) * a.CS, wp = NT * a.KS * 1024 + BD_WP_TAIL;
-  return chained ? t0 + wp + BD_WD_CHAIN : t0 + (((a.rows * a.W + 15) >> 4) << 4) * a.CS + wp;
-}
 static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc* ns, Step* out) {
   const OpRec& dop = m->ops[d_op];
   const OpRec& pop = m->ops[p_op];
@@ -295,7 +274,7 @@ static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc
       (rc = upload(m, fold_bias((const int32_t*)(m->blob.data() + dop.b_off), wd, C, 9, tin.zero_point, W_TAPS, a.NCG * 16), &dbd)) ||
       (rc = upload(m, pad_floats((const float*)(m->blob.data() + dop.m_off), C, a.NCG * 16), &dmd)))
     return rc;
-  // the chained form's panel beside the natural-order one: both forms stay launchable (resolve_band)
+  // the chained form's panel beside the natural-order one: both forms stay launchable (detector.hip: resolve_band)
   if (C == 64 && to.c <= 64 && (rc = upload(m, pack_band_pw_chain((const int8_t*)(m->blob.data() + pop.w_off), to.c, C), &dpc))) return rc;
   a.wd = dpd; a.wp = dpp; a.wpc = dpc; a.bd = dbd; a.md = dmd;
   a.bp = m->op_steps[p_op].bias;   // folded with the depthwise output's zero point, padded to 64
@@ -1010,7 +989,7 @@ static void merge_side_convs(vbt_model* m) {
     if (!pwm_mergeable(m, m->steps[a])) continue;
     std::vector<int> set;
     int chain = -1, k1 = -1, k2 = -1;
-    for (int j = 0; j < ns && (int)set.size() < PWM_MAX; j++) {
+    for (int j = 0; j < ns && (int)set.size() < PW_MERGE_MAX; j++) {
       if (!pwm_mergeable(m, m->steps[j])) continue;
       const OpRec& cj = m->ops[m->steps[j].op];
       if (j > a && made_at(cj.inputs[0]) >= a) continue;            // hoisted to the anchor: its input must exist by then
@@ -1077,7 +1056,7 @@ static void merge_side_convs(vbt_model* m) {
   m->steps.swap(out);
 }
 
-static void finalize_plan(vbt_model* m) {
+void finalize_plan(vbt_model* m) {
   m->steps.clear();
   m->materialized.assign(m->tensors.size(), 1);
   for (const Group& g : m->groups) {
@@ -1088,7 +1067,7 @@ static void finalize_plan(vbt_model* m) {
   merge_side_convs(m);
 }
 
-static int build_plan(vbt_model* m) {
+int build_plan(vbt_model* m) {
   const int no = (int)m->ops.size();
   for (int oi = 0; oi < no; oi++) {
     const OpRec& op = m->ops[oi];
@@ -1214,3 +1193,5 @@ static int build_plan(vbt_model* m) {
   }
   return fuse_plan(m);
 }
+
+}  // namespace vbt

@@ -1,12 +1,20 @@
 // Host-side weight / bias layouts of the detector's kernels: one pure function per layout.  Every function reads the container blob
 // (int8 weights, int32 biases, float multipliers) and shapes, and returns the host image of what a kernel reads; none touches the
 // model or HIP.  Weight orders in the blob: convs (stem, pointwise) are rows [cout][K], depthwise convs are taps [tap][C].
-// Included by detector.hip inside namespace vbt, after dev_common.h (v4i).
+// The functions sit at global scope.  v4i: dev_common.h's in a HIP unit (planner.hip); a plain C++ program that includes this header on
+// its own (tests/test_band_pack_host.py, tests/test_toeplitz_pack_host.py) defines its own 16-byte int vector first.
 #pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+#ifdef __HIP__
+#include "dev_common.h"
+using vbt::v4i;
+#endif
 
 // Packed MFMA A-operand layout: [(nb*KS + ks)*4 + t][lane][8 bytes]; lane (i = lane&15, g = lane>>4) holds
 // W[cout = 64nb + 16(i>>2) + 4t + (i&3)][k = 32ks + 8g + j].  kmap translates packed k -> source k (or -1).
-static void pack_weights(const int8_t* w, int N, int K, int KS, int NB, const std::vector<int>* kmap, std::vector<long>& out) {
+inline void pack_weights(const int8_t* w, int N, int K, int KS, int NB, const std::vector<int>* kmap, std::vector<long>& out) {
   out.assign((size_t)NB * KS * 4 * 64, 0);
   int8_t* o = (int8_t*)out.data();
   for (int nb = 0; nb < NB; nb++)
@@ -26,7 +34,7 @@ static void pack_weights(const int8_t* w, int N, int K, int KS, int NB, const st
 
 // 16x16x64 layout: [(nb*KS + ks)*4 + t][lane][16 bytes]; lane (i = lane&15, g = lane>>4) holds
 // W[cout = 64nb + 16(i>>2) + 4t + (i&3)][k = 64ks + 16g + j], zero beyond N / K.
-static void pack_weights64(const int8_t* w, int N, int K, int KS, int NB, std::vector<v4i>& out, const std::vector<int>* kmap = nullptr) {
+inline void pack_weights64(const int8_t* w, int N, int K, int KS, int NB, std::vector<v4i>& out, const std::vector<int>* kmap = nullptr) {
   out.assign((size_t)NB * KS * 4 * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
   for (int nb = 0; nb < NB; nb++)
@@ -45,7 +53,7 @@ static void pack_weights64(const int8_t* w, int N, int K, int KS, int NB, std::v
 // Zero point folded into the bias: out[c] = bq[c] - zp * sum_k w_c[k] for c < n, zero up to `padded` entries.  W_ROWS: w_c[k] =
 // w[c*K + k] (convs); W_TAPS: w_c[k] = w[k*n + c] (depthwise, K taps).  A kernel that accumulates u = x_q + 128 passes zp = 128 + z_x.
 enum WLayout { W_ROWS, W_TAPS };
-static std::vector<int> fold_bias(const int32_t* bq, const int8_t* w, int n, int K, int zp, WLayout layout, int padded = 0) {
+inline std::vector<int> fold_bias(const int32_t* bq, const int8_t* w, int n, int K, int zp, WLayout layout, int padded = 0) {
   std::vector<int> out(std::max(n, padded), 0);
   for (int c = 0; c < n; c++) {
     long sw = 0;
@@ -56,13 +64,13 @@ static std::vector<int> fold_bias(const int32_t* bq, const int8_t* w, int n, int
 }
 // n floats (multipliers; depthwise weights as floats) followed by zeros up to `padded` entries
 template <typename T>
-static std::vector<float> pad_floats(const T* v, int n, int padded) {
+inline std::vector<float> pad_floats(const T* v, int n, int padded) {
   std::vector<float> out(std::max(n, padded), 0.0f);
   for (int c = 0; c < n; c++) out[c] = (float)v[c];
   return out;
 }
 // depthwise weights as floats, [tap][Cp] (the VALU depthwise of the fused tiles; Cp == C: the stand-alone walkers)
-static std::vector<float> dw_weights_f32(const int8_t* w, int C, int kk, int Cp) {
+inline std::vector<float> dw_weights_f32(const int8_t* w, int C, int kk, int Cp) {
   std::vector<float> out((size_t)kk * Cp, 0.0f);
   for (int t = 0; t < kk; t++)
     for (int c = 0; c < C; c++) out[(size_t)t * Cp + c] = (float)w[(size_t)t * C + c];
@@ -72,7 +80,7 @@ static std::vector<float> dw_weights_f32(const int8_t* w, int C, int kk, int Cp)
 // Depthwise on the matrix pipe, 16x16x32 form: [chunk][cg][m][lane][8], chunks of `group_channels` (64, or 48 for the unpadded
 // chunking of fused_block.h) = cg groups of 16: lane (i = lane&15 -> channel group_channels*chunk + 16*cg + i, g): k = 8g + j ->
 // tap 2m + (g>>1), channel-in-group 8(g&1) + j; non-zero only on the diagonal
-static std::vector<long> pack_dw_diag(const int8_t* w, int C, int kk, int group_channels) {
+inline std::vector<long> pack_dw_diag(const int8_t* w, int C, int kk, int group_channels) {
   const int NCG = group_channels / 16, nch = (C + group_channels - 1) / group_channels, KT = (kk + 1) / 2;
   std::vector<long> out((size_t)nch * NCG * KT * 64, 0);
   int8_t* o = (int8_t*)out.data();
@@ -90,7 +98,7 @@ static std::vector<long> pack_dw_diag(const int8_t* w, int C, int kk, int group_
 // Depthwise in the 16x16x64 form of the fused tiles and the stem block (FusedArgs::wd64, StemBlockArgs::wd64): [q][m][lane] x 16 B
 // for nq groups of 16 channels, channel 16q + i on the diagonal byte i.  k = 3: m = kernel row, g = column (g < 3).  k = 5: m < 5 =
 // kernel row with columns 0..3 in g, m = 5 holds column 4 of rows 0..3, m = 6 the last tap.
-static std::vector<v4i> pack_dw64(const int8_t* w, int C, int k, int nq) {
+inline std::vector<v4i> pack_dw64(const int8_t* w, int C, int k, int nq) {
   const int K64 = k == 3 ? 3 : 7;
   std::vector<v4i> out((size_t)nq * K64 * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
@@ -108,7 +116,7 @@ static std::vector<v4i> pack_dw64(const int8_t* w, int C, int k, int nq) {
   return out;
 }
 // FusedArgs::wd64c: one byte per operand of pack_dw64, the diagonal byte of each lane: [q][lane][8], byte m
-static std::vector<long> pack_dw64_compact(const std::vector<v4i>& w64, int k) {
+inline std::vector<long> pack_dw64_compact(const std::vector<v4i>& w64, int k) {
   const int K64 = k == 3 ? 3 : 7, nq = (int)(w64.size() / ((size_t)K64 * 64));
   std::vector<long> out((size_t)nq * 64, 0);
   const int8_t* o = (const int8_t*)w64.data();
@@ -122,7 +130,7 @@ static std::vector<long> pack_dw64_compact(const std::vector<v4i>& w64, int k) {
 
 // Expand conv of the 48-channel chunking (FusedArgs::we3): [(c*KS + ks)*3 + t][lane][8]; lane (i, kg) holds
 // W[cout = 48c + 12(i>>2) + 4t + (i&3)][k = 32ks + 8kg + j]
-static std::vector<long> pack_expand48(const int8_t* w, int Ce, int K, int KS) {
+inline std::vector<long> pack_expand48(const int8_t* w, int Ce, int K, int KS) {
   const int nch3 = Ce / 48;
   std::vector<long> out((size_t)nch3 * KS * 3 * 64, 0);
   int8_t* o = (int8_t*)out.data();
@@ -139,7 +147,7 @@ static std::vector<long> pack_expand48(const int8_t* w, int Ce, int K, int KS) {
   return out;
 }
 // packed K of the 48-channel projection -> source channel: 64 slots per chunk, the first 48 used
-static std::vector<int> kmap48(int Ce) {
+inline std::vector<int> kmap48(int Ce) {
   std::vector<int> kmap((size_t)(Ce / 48) * 64, -1);
   for (int c = 0; c < Ce / 48; c++)
     for (int q = 0; q < 48; q++) kmap[(size_t)c * 64 + q] = 48 * c + q;
@@ -147,7 +155,7 @@ static std::vector<int> kmap48(int Ce) {
 }
 
 // Row-band kernel (band_block.h), depthwise 3x3 in the 16x16x64 form: [cg][m][lane] x 16 B, tap 4m + g, diagonal byte i
-static std::vector<v4i> pack_band_dw(const int8_t* w, int C) {
+inline std::vector<v4i> pack_band_dw(const int8_t* w, int C) {
   const int NCG = (C + 15) / 16;
   std::vector<v4i> out((size_t)NCG * 3 * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
@@ -160,7 +168,7 @@ static std::vector<v4i> pack_band_dw(const int8_t* w, int C) {
   return out;
 }
 // Row-band kernel, projection: [t][ks][lane] x 16 B; lane (i, g) holds W[cout = 16t + i][k = 64ks + 16g + j]
-static std::vector<v4i> pack_band_pw(const int8_t* w, int N, int C) {
+inline std::vector<v4i> pack_band_pw(const int8_t* w, int N, int C) {
   const int NT = (N + 15) / 16, KS = (C + 63) / 64;
   std::vector<v4i> out((size_t)NT * KS * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
@@ -178,7 +186,7 @@ static std::vector<v4i> pack_band_pw(const int8_t* w, int N, int C) {
 // Row-band kernel, projection of the chained form (C = 64): [t][lane] x 16 B in the K order the depthwise leaves in registers; lane
 // (i, g), byte 4cg + j holds W[cout = 16t + i][k = 16cg + 4g + j].  The MFMA pairs byte (g, p) of A with byte (g, p) of B and sums in
 // int32, so any K order the two operands share gives the same sum: each (t, i) row is a permutation of pack_band_pw's.
-static std::vector<v4i> pack_band_pw_chain(const int8_t* w, int N, int C) {
+inline std::vector<v4i> pack_band_pw_chain(const int8_t* w, int N, int C) {
   const int NT = (N + 15) / 16;
   std::vector<v4i> out((size_t)NT * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
@@ -196,7 +204,7 @@ static std::vector<v4i> pack_band_pw_chain(const int8_t* w, int N, int C) {
 
 // Stem conv K order of the stand-alone stem kernel (3x3x3 -> 32 packed K): 8g + j -> (ky = g, kx = j/3, c = j%3) for g < 3,
 // 24 + j -> (ky = j, kx = 2, c = 2)
-static std::vector<int> stem_kmap() {
+inline std::vector<int> stem_kmap() {
   std::vector<int> kmap(32, -1);
   for (int g = 0; g < 3; g++)
     for (int j = 0; j < 8; j++) kmap[8 * g + j] = (g * 3 + j / 3) * 3 + j % 3;
@@ -205,7 +213,7 @@ static std::vector<int> stem_kmap() {
 }
 // Stem block (stem_block.h), stem conv: [t][lane][8], cout = 8(i>>2) + 4t + (i&3); K index 8kg + j -> kernel row kg, byte j of its
 // 9 (kg < 3); (row j, byte 8) for kg == 3, j < 3
-static std::vector<long> pack_stem_block_stem(const int8_t* w) {
+inline std::vector<long> pack_stem_block_stem(const int8_t* w) {
   std::vector<long> out(2 * 64, 0);
   int8_t* o = (int8_t*)out.data();
   for (int t = 0; t < 2; t++)
@@ -219,7 +227,7 @@ static std::vector<long> pack_stem_block_stem(const int8_t* w) {
   return out;
 }
 // Stem block, projection: [lane][8], row i = cout i (N <= 16), K = 32: k = 8kg + j
-static std::vector<long> pack_stem_block_proj(const int8_t* w, int N) {
+inline std::vector<long> pack_stem_block_proj(const int8_t* w, int N) {
   std::vector<long> out(64, 0);
   int8_t* o = (int8_t*)out.data();
   for (int lane = 0; lane < 64; lane++) {
@@ -231,7 +239,7 @@ static std::vector<long> pack_stem_block_proj(const int8_t* w, int N) {
 
 // Expand + depthwise kernels (expdw_block.h), expand panels: [(c*KS + ks)*4 + t][lane] x 16 B; lane (i, g) holds
 // W[cout = 64c + 16t + i][k = 64ks + 16g + j]
-static std::vector<v4i> pack_expdw_expand(const int8_t* w, int Ce, int K) {
+inline std::vector<v4i> pack_expdw_expand(const int8_t* w, int Ce, int K) {
   const int nch = (Ce + 63) / 64, KS = (K + 63) / 64;
   std::vector<v4i> out((size_t)nch * KS * 4 * 64, (v4i){0, 0, 0, 0});
   int8_t* o = (int8_t*)out.data();
@@ -248,7 +256,7 @@ static std::vector<v4i> pack_expdw_expand(const int8_t* w, int Ce, int K) {
   return out;
 }
 // Expand + depthwise, first form, depthwise taps: [c][cg][lane][8], byte m = the weight of channel 64c + 16cg + i at tap 4m + g
-static std::vector<long> pack_expdw_taps(const int8_t* w, int Ce, int kk) {
+inline std::vector<long> pack_expdw_taps(const int8_t* w, int Ce, int kk) {
   const int nch = (Ce + 63) / 64, KT = (kk + 3) / 4;
   std::vector<long> out((size_t)nch * 4 * 64, 0);
   int8_t* o = (int8_t*)out.data();
@@ -266,7 +274,7 @@ static std::vector<long> pack_expdw_taps(const int8_t* w, int Ce, int kk) {
 // stride 2) for channel base + 4q + (i&3); byte j = the weight at kernel row 2m + (g>>1) - S*dy, column 4(g&1) + j - S*dx, zero
 // outside the k x k kernel and past channel Ce.  expdw2: one table per 64-channel chunk c (base 64c, 16 quads); the fused tiles:
 // one table over all quads, which serves 64- and 48-channel chunks alike (chunk c starts at quad 16c / 12c).
-static std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int base, int nq, int k, int S) {
+inline std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int base, int nq, int k, int S) {
   const int KT2 = (S * (S - 1) + k + 1) / 2;
   std::vector<unsigned> out((size_t)nq * KT2 * 64, 0);
   for (int q = 0; q < nq; q++)

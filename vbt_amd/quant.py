@@ -113,7 +113,7 @@ def postprocess_tables(s_cls, z_cls, s_box, z_box, y_scale=1.0, h_scale=1.0):
 
 
 def pack_postprocess_tables(s_cls, z_cls, s_box, z_box, y_scale=1.0, h_scale=1.0):
-    """Blob layout read by csrc/detector.hip and oracle/detector.c: score f32[256] | box f32[256] | dq f64[256] |
+    """Blob layout read by csrc/detector_plan.hip (vbt_model_create_ex) and oracle/detector.c: score f32[256] | box f32[256] | dq f64[256] |
     ex f64[256] | scales f32[4] (y, x, h, w)."""
     score, box, dq, ex = postprocess_tables(s_cls, z_cls, s_box, z_box, y_scale, h_scale)
     sc = np.asarray([y_scale, y_scale, h_scale, h_scale], F32)
