@@ -25,7 +25,7 @@
 #include <cmath>
 
 #include "detector_model.h"
-#include "op_kernels.h"   // the single-op kernels (pw_a / pw_b / pw_c / pw_d, stem, depthwise, add, pool, resize, decode + NMS, frame resize)
+#include "op_kernels.h"   // the single-op kernels (pw_a ... pw_f, stem, depthwise, add, pool, resize, decode + NMS, frame resize)
 
 namespace vbt {
 
@@ -53,8 +53,17 @@ PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B) {
   }
   // VBT_PW_VARIANT (tests): the kernel variant of every pointwise conv with K > 256, whatever the plan says
   static const int pw_force = getenv("VBT_PW_VARIANT") ? atoi(getenv("VBT_PW_VARIANT")) : -100;
-  if (pw_force != -100) variant = pw_force;
-  if (variant >= 3 && variant <= 6) {   // 64 (3 / 5) or 128 (4 / 6) pixels per workgroup; weights shared through LDS (3 / 4: pw_d_kernel)
+  // (a forced 7 / 8 leaves the convs that form refuses - one output block, or more than PW_F_MAX_NB - on the plan's variant)
+  const bool f_fits = s.NB >= 2 && s.NB <= PW_F_MAX_NB;
+  if (pw_force != -100 && (f_fits || (pw_force != 7 && pw_force != 8))) variant = pw_force;
+  if (variant == 7 || variant == 8) {   // 64 (7) or 128 (8) pixels per workgroup for ALL output blocks: activations fetched once (pw_f_kernel)
+    L.form = PW_F;
+    L.ms = variant - 6;
+    L.lds = s.NB * 8192;   // static: two stages of the K-step's 4 * NB weight tiles
+    L.grid = dim3((unsigned)((M + 64 * L.ms - 1) / (64 * L.ms)), 1);
+    if (s.NB < 2) L.refuse(VBT_ERR_ARG, "pw_conv: one output block - nothing for the all-blocks form to share");
+    else if (s.NB > PW_F_MAX_NB) L.refuse(VBT_ERR_ARG, "pw_conv: %d output blocks exceed the %d whose accumulators the all-blocks form holds", s.NB, PW_F_MAX_NB);
+  } else if (variant >= 3 && variant <= 6) {   // 64 (3 / 5) or 128 (4 / 6) pixels per workgroup; weights shared through LDS (3 / 4: pw_d_kernel)
     L.form = variant <= 4 ? PW_D : PW_E;   // or the block's whole weight panel in LDS and a K loop without barriers (5 / 6: pw_e_kernel)
     L.ms = 2 - (variant & 1);
     L.lds = L.form == PW_E ? s.KS64 * 4096 : 0;
@@ -95,6 +104,11 @@ static int launch_pw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
     case PW_E:
       if (L.ms == 2) { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<2, 4>); PW((pw_e_kernel<2, 4>), L.lds); }
       else { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<1, 4>); PW((pw_e_kernel<1, 4>), L.lds); }
+      break;
+    case PW_F:
+#define PW_F_NB(NBF) (L.ms == 2 ? PW((pw_f_kernel<NBF, 2, 4>), 0) : PW((pw_f_kernel<NBF, 1, 4>), 0))
+      if (s.NB == 2) PW_F_NB(2); else if (s.NB == 3) PW_F_NB(3); else if (s.NB == 4) PW_F_NB(4); else if (s.NB == 5) PW_F_NB(5); else PW_F_NB(6);
+#undef PW_F_NB
       break;
     case PW_B:
       if (L.nbt == 1) PW(pw_b_kernel<1>, 0); else if (L.nbt == 2) PW(pw_b_kernel<2>, 0); else if (L.nbt == 3) PW(pw_b_kernel<3>, 0); else PW(pw_b_kernel<4>, 0);

@@ -171,7 +171,8 @@ struct Verdict {   // rc != VBT_OK: the step is refused, and `why` is the error 
   void refuse(int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(why, sizeof(why), fmt, ap); va_end(ap); rc = code; }
   int report() const { set_error("%s", why); return rc; }
 };
-enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E };
+enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E, PW_F };
+constexpr int PW_F_MAX_NB = 6;   // output blocks whose accumulators one workgroup of the all-blocks form holds (N <= 384)
 struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0; dim3 grid; };
 enum DwForm { DW_ROW, DW_COL, DW_TILE };
 struct DwLaunch : Verdict {   // tile geometry (DW_TILE), rows per lane and row segments (DW_COL), lanes (DW_ROW / DW_COL)

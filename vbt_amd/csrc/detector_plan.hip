@@ -135,7 +135,7 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
   } else if (st.family == F_PW && st.KS64 <= 4) {
     cand = {0, 1};
   } else if (st.family == F_PW) {
-    cand = {-1, 2, 3, 4, 5, 6};
+    cand = {-1, 2, 3, 4, 5, 6, 7, 8};
   } else if (is_fused_tile(st.family)) {
     cand = {0, 1, 3, 5};   // VALU dw, matrix-pipe dw, matrix-pipe dw + half-height tile, one workgroup per image
     if (st.family == F_MBCONV && st.fa.nch3 > 0 && st.nbp <= 2 && st.fa.KSe >= 1 && st.fa.KSe <= 4) { cand.push_back(9); cand.push_back(11); }  // 48-channel chunks

@@ -1,4 +1,4 @@
-// Single-op kernels of the int8 detector (one graph op per launch): pointwise convs on the 16x16x64 int8 MFMA (four forms), stem conv,
+// Single-op kernels of the int8 detector (one graph op per launch): pointwise convs on the 16x16x64 int8 MFMA (six forms), stem conv,
 // depthwise convs (row / column walkers), integer ADD, max pool, nearest-neighbour resize, decode + NMS, bilinear frame resize.
 // Included by detector.hip alone, which launches them; the fused kernel families are in their own headers / translation units
 // (launchers.h).
@@ -406,6 +406,94 @@ __global__ __launch_bounds__(256) void pw_e_kernel(const int8_t* __restrict__ x,
     const long m = m0 + 16 * s + r;
     if (m < M) store_tile_e(acc[s], er[s], e, ra, out, m, N, nb, g);
   }
+}
+
+// variant F: large K, a workgroup owns its 64 * MS pixels for ALL NB output blocks, so every activation byte is fetched once (variants D and E
+// fetch the [M][K] tensor once per 64-channel block, a whole sweep apart in time).  Per K-step the 4 * NB weight tiles (NB x 4 KB) go through a
+// double-buffered LDS copy: every thread requests NB 16-byte operands (its wave's tile of every block) TWO steps ahead into registers and stores
+// the set requested one step earlier, so a weight load has a whole K-step of MFMAs to arrive in; the activation operands are PD steps ahead in
+// registers as in variant E, refilled two steps at a time (PD is even).  One barrier per K-step, between which a wave issues 4 * NB * MS MFMAs (variant D: 4 * MS).  No load is issued
+// under a condition (clamped indices), so the compiler's vmcnt waits stay exact; the loop runs KS rounded up to PD steps and only the MFMAs of
+// the steps past KS are skipped.  With the packed layout [nb][ks][t][lane] a tile holds channels 16 (i >> 2) + 4 t + (i & 3) of its block, so
+// a part-filled last block (N = 80, 112) has four part-filled tiles and no dead one: all 4 * NB tiles are multiplied.
+// The epilogue operands are loaded after the K loop, block by block: they would otherwise hold 12 * NB * MS registers through it.
+template <int NB, int MS, int PD>
+__global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x, const v4i* __restrict__ wp, Epi e, ResArgs ra,
+                                                   int8_t* __restrict__ out, long M, int K, int KS, int N, int /*NB*/) {
+  static_assert(PD % 2 == 0, "the activation queue is refilled in pairs of K-steps");
+  __shared__ v4i wbuf[2][NB * 4][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = lane & 15, g = lane >> 4;
+  const long m0 = ((long)blockIdx.x * 4 + wave) * (16 * MS);
+  const int8_t* p[MS];
+#pragma unroll
+  for (int s = 0; s < MS; s++) p[s] = x + min(m0 + 16 * s + r, M - 1) * K + 16 * g;
+  const v4i* w = wp + wave * 64 + lane;   // this wave's tile of block 0, K-step 0; a K-step is 4 * 64 operands further, a block KS K-steps
+  const long wblk = (long)KS * 4 * 64;
+  v4i wst[NB], wnx[NB];   // the weight operands of the next K-step (stored to LDS at the end of this one) and of the one after it
+#pragma unroll
+  for (int b = 0; b < NB; b++) wst[b] = w[b * wblk];
+  const int k1 = min(1, KS - 1);
+#pragma unroll
+  for (int b = 0; b < NB; b++) wnx[b] = w[b * wblk + (long)k1 * 4 * 64];
+  v4i aq[PD][MS];
+#pragma unroll
+  for (int i = 0; i < PD; i++) {
+    const int kn = min(i, KS - 1);
+#pragma unroll
+    for (int s = 0; s < MS; s++) aq[i][s] = ld16(p[s] + 64 * kn);
+  }
+  v4i acc[MS][NB][4];
+#pragma unroll
+  for (int s = 0; s < MS; s++)
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[s][b][t] = (v4i){0, 0, 0, 0};
+#pragma unroll
+  for (int b = 0; b < NB; b++) wbuf[0][b * 4 + wave][lane] = wst[b];
+#pragma unroll
+  for (int b = 0; b < NB; b++) wst[b] = wnx[b];
+  __syncthreads();
+  for (int ks0 = 0; ks0 < KS; ks0 += PD) {
+#pragma unroll
+    for (int j = 0; j < PD; j++) {
+      const int ks = ks0 + j;
+      const int kw = min(ks + 2, KS - 1);
+#pragma unroll
+      for (int b = 0; b < NB; b++) wnx[b] = w[b * wblk + (long)kw * 4 * 64];
+      asm volatile("" ::: "memory");
+      if (ks < KS) {
+#pragma unroll
+        for (int b = 0; b < NB; b++)
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            const v4i wv = wbuf[ks & 1][b * 4 + t][lane];
+#pragma unroll
+            for (int s = 0; s < MS; s++) acc[s][b][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, aq[j][s], acc[s][b][t], 0, 0, 0);
+          }
+      }
+      if (j & 1) {   // two K-steps of a pixel are one 128-byte line (where its row starts on one): both halves requested together
+        const int kn0 = min(ks - 1 + PD, KS - 1), kn = min(ks + PD, KS - 1);
+#pragma unroll
+        for (int s = 0; s < MS; s++) { aq[j - 1][s] = ld16(p[s] + 64 * kn0); aq[j][s] = ld16(p[s] + 64 * kn); }
+      }
+#pragma unroll
+      for (int b = 0; b < NB; b++) wbuf[(ks + 1) & 1][b * 4 + wave][lane] = wst[b];
+#pragma unroll
+      for (int b = 0; b < NB; b++) wst[b] = wnx[b];
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int s = 0; s < MS; s++) {
+      const long m = m0 + 16 * s + r;
+      EpiRegs er;
+      load_epi(er, e, ra, min(m, M - 1), N, b, g);
+      if (m < M) store_tile_e(acc[s][b], er, e, ra, out, m, N, b, g);
+    }
 }
 
 __device__ __forceinline__ unsigned max4_s8(unsigned a, unsigned b) {
