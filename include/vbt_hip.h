@@ -545,7 +545,48 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
  *   Y = ((66 r + 129 g + 25 b + 128) >> 8) + 16;  U = ((-38 r - 74 g + 112 b + 128) >> 8) + 128;  V = ((112 r - 94 g - 18 b + 128) >> 8) + 128
  * (>> arithmetic).  Every other byte is untouched; drawing twice gives the frame drawing once gives.
  * One difference from the reference: it skips the VideoWriter.write of frames on which the detector found nothing (track.py:180-181),
- * which makes its video jump in time; here the caller keeps every frame, and a frame without rows comes back as it went in. */
+ * which makes its video jump in time; here the caller keeps every frame, and a frame without rows comes back as it went in.
+ *
+ * Rep panel (vbt_overlay_set_hud; the content of the reference's figure, plot.py:112-232, in the video): the rep count, ROM and ACV
+ * of the last completed rep, a bar per recent rep and a scrolling phase timeline (the axvspan of plot.py:162-169), as a small panel
+ * on every frame.  Two colours and exactly one writer per pixel: the rules above scatter one colour and never read a pixel; the
+ * panel never reads a pixel either but is a gather - EVERY pixel of the panel rectangle is written, with fg (the handle's rgb) where
+ * it is covered and with bg (vbt_overlay_hud_params.bg) where it is not.  The result does not depend on any order and is idempotent.
+ * The panel is drawn after the rules above by the same vbt_overlay_draw on the same stream: where a box or a trail crosses the
+ * panel, the panel wins.  All values are integers once formed.  s = scale, (X, Y) = the panel's origin; the panel is
+ * [X, X + 52 s) x [Y, Y + 50 s).
+ *
+ * Per phase (time_start, time_end, y_start, y_end, rom, type; type 0 concentric, 1 eccentric, 2 hold), formed on the host when the
+ * phases are set, in IEEE double without contraction, frame() being the frame number above (llrint(time * fps) after the clamp):
+ *   fs = frame(time_start), fe = frame(time_end)
+ *   rom_cm = centi(rom);  acv_cm = centi(rom / (time_end - time_start)), and 0 when time_end - time_start <= 0
+ *   centi(v) = 0 if v is NaN or v <= 0, else llrint(min(v * 100.0, 9999.0))
+ * This is the library's own rounding: it can differ from Python's f'{v:0.2f}' (plot.py:178,186) in the last digit, where v * 100.0
+ * rounds across a tie that the decimal expansion of v does not reach.
+ *
+ * State of frame f: the concentric phases with fe <= f are "completed", in table order; n = their number, last = the latest of them.
+ *
+ * Text: three lines of 8 characters.  Character k (0..7) of line l (0..2), bitmap column c and row r (as in rule 4) cover the s x s
+ * block with left column X + 2 s + 6 s k + s c and top row Y + 2 s + 9 s l + s r.  Line 0 is "REP" and the decimal of
+ * min(n, 99999) right-aligned in 5; line 1 is "ROM" and field(rom_cm of last); line 2 is "ACV" and field(acv_cm of last).
+ * field(v) is five spaces when n = 0, else v / 100, '.', and the two digits of v % 100, right-aligned in 5 (field(5) = " 0.05").
+ * A space covers nothing.  Digits are those of rule 4; the other glyphs, rows top to bottom:
+ *        R: 11110 10001 10001 11110 10100 10010 10001    A: 01110 10001 10001 11111 10001 10001 10001
+ *        E: 11111 10000 10000 11110 10000 10000 11111    C: 01110 10001 10000 10000 10000 10001 01110
+ *        P: 11110 10001 10001 11110 10000 10000 10000    V: 10001 10001 10001 10001 10001 01010 00100
+ *        O: 01110 10001 10001 10001 10001 10001 01110    .: 00000 00000 00000 00000 00000 01100 01100
+ *        M: 10001 11011 10101 10101 10001 10001 10001
+ * Rep bars: eight slots.  Slot j (0..7) holds completed rep number max(n - 8, 0) + j (0-based) if that is < n, else it is empty.
+ * A filled slot has height hb = clamp(acv_cm * 12 s / full_scale_cm, 1, 12 s) (the product in int64, integer division) and covers
+ * columns [X + 2 s + 6 s j, X + 2 s + 6 s j + 5 s) and rows [Y + 41 s - hb, Y + 41 s).
+ * Phase timeline: columns c in [0, 47 s) at X + 2 s + c.  Column c stands for frame fc = f - (47 s - 1 - c) * frame_step (int64;
+ * frame_step is the draw call's).  The first phase of the table with fs < fc <= fe decides (only fc >= 1 can match): concentric -
+ * the column covers rows [Y + 43 s, Y + 47 s); eccentric - rows [Y + 45 s, Y + 47 s); a hold, or no such phase - nothing.  The
+ * timeline uses the whole table, completed or not: the panel is rendered after the clip is analysed.
+ * Colours.  VBT_PIX_RGB24: a covered panel pixel gets fg, every other panel pixel bg.  YUV: luma per pixel in the same way; the chroma
+ * sample at (py >> 1, px >> 1) gets fg's U, V if any of its four pixels is covered, else bg's - both colours through the integers
+ * above.  For the YUV formats X and Y are even (52 s and 50 s always are): every chroma sample of the panel lies wholly inside it.
+ * Every byte outside the panel rectangle is left as the rules above left it. */
 typedef struct vbt_overlay vbt_overlay;
 typedef struct {
   int32_t trail;        /* bar path length in points, track.py:57-58 -> 120 */
@@ -572,8 +613,29 @@ int vbt_overlay_set_rows(vbt_overlay* o, const void* rows_host, int n, double fp
 /* Draw into B frames, contiguous in device memory (H*W*3 bytes each, H*W*3/2 for the YUV formats), frame i being frame number
  * frame0 + i * frame_step (frame0, frame_step >= 1).  In place; enqueue only: one launch, workgroups spread over (frame, row of that
  * frame, primitive), each walking its primitive clipped to the frame - no pass over the frame, no pixel read.  Frames without rows
- * are not touched. */
+ * are not touched - but for the rep panel, if vbt_overlay_set_hud set one: one more launch over (tile of the panel, frame). */
 int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
+typedef struct {
+  int32_t x, y;           /* panel origin -> 16, 16 */
+  int32_t scale;          /* pixels per cell -> 3 (a 156 x 150 panel) */
+  int32_t full_scale_cm;  /* ACV of a full-height bar, cm/s -> 200 */
+  uint8_t bg[3];          /* -> 0,0,0 */
+  uint8_t reserved[5];
+} vbt_overlay_hud_params;
+void vbt_overlay_hud_default_params(vbt_overlay_hud_params* p);
+/* The rep panel ("Rep panel" above) of ONE id: phases6_host = P records of 6 doubles as vbt_tracker_phases / vbt_analyze return them,
+ * fps = the clip's.  Replaces the handle's previous panel; P = 0 with params is a panel that shows "REP    0" and blank fields on
+ * every frame; params NULL with P = 0 switches the panel off (only the handle is looked at then).  From then on every
+ * vbt_overlay_draw draws the panel into every frame of its batch - frames without rows and frames past the last row included - with
+ * one more launch that walks the panel, never the frame; without a panel vbt_overlay_draw launches exactly what it did before.
+ * VBT_ERR_ARG, checked in this order and before any device call: P < 0, P > 0 with a NULL pointer or params NULL with P > 0; fps <= 0
+ * or not finite; a non-finite phase value; a type outside {0, 1, 2}; time_end < time_start; time_start or time_end decreasing along
+ * the table; scale outside 1..64; full_scale_cm outside 1..100000; x < 0 or y < 0.  VBT_ERR_CAPACITY: P > 65536 or a frame number
+ * above 2^24.  Then the handle (NULL: VBT_ERR_ARG), then the geometry, VBT_ERR_ARG: odd x or y with a YUV handle, a panel that does
+ * not lie wholly inside the frame (x + 52 scale > W or y + 50 scale > H).  A refused call leaves the handle's panel as it was.
+ * Builds the table of per-phase integers (fs, fe, rom_cm, acv_cm, type, concentric phases up to and including this one) on the host,
+ * uploads it in one copy on `stream` and synchronises it. */
+int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, const double* phases6_host, int P, double fps, void* stream);
 
 /* ------------------------------------------------------------------ MJPEG export --------
  * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that

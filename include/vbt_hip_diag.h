@@ -98,6 +98,10 @@ int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, doub
  * trail length (points) - so that a failing picture can be told from failing geometry.  *n = the handle's rows; cap < *n is
  * VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
 int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
+/* The table vbt_overlay_set_hud uploaded, read back from the device: out[i] = fs, fe, rom_cm, acv_cm, type, concentric phases among
+ * phases 0..i - so that a failing panel pixel can be told from a wrong integer.  *P = the panel's phases (0 without a panel);
+ * cap < *P is VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
+int vbt_overlay_hud_table(vbt_overlay* o, int32_t* out /*[P][6]*/, int cap, int* P);
 
 /* MJPEG import, measurement (tools/mjpeg_decode_bench.py).  With VBT_MJPEG_DECODE_STAMPS=1 in the environment of
  * vbt_mjpeg_decoder_create, every vbt_mjpeg_decode records a HIP event around each of its stages; this call waits for the last one and

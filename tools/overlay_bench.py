@@ -8,7 +8,11 @@
 set_rows is timed on the host clock (it synchronises): validation, index, upload and the prepare kernel, for the benchmark's rows and
 for a 10-minute clip's worth (4 ids x 18000 frames).
 
-  python tools/overlay_bench.py [--frames 64] [--reps 20] [--warmup 5] [--out FILE.json]
+--hud: a second handle with the same rows and a rep panel (vbt_overlay_set_hud: default 156 x 150 panel, 24 phases) is timed in the same
+rounds, alternating with the first: per format "hud" = its draw time and the increment over the panel-off draw, next to the copy of
+the batch.  --size WxH (default 1920x1080): the same at another frame size - the increment must not grow with H * W.
+
+  python tools/overlay_bench.py [--frames 64] [--reps 20] [--warmup 5] [--hud] [--size 1920x1080] [--out FILE.json]
 
 Prints one JSON line."""
 import argparse
@@ -42,13 +46,23 @@ def make_rows(n_frames):
     return d
 
 
+def make_phases(n_frames):
+    """24 phases of equal length over frames 1..n_frames: eccentric and concentric in turn, 12 reps (the bar window is full)"""
+    step = n_frames / 24.0
+    return [((1 + i * step) / FPS, (1 + (i + 1) * step) / FPS, 0.3, 0.6, 0.4 + 0.01 * i, 1 - i % 2) for i in range(24)]
+
+
 def main():
+    global H, W
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--hud", action="store_true", help="also time the draw with a rep panel set")
+    ap.add_argument("--size", default=f"{W}x{H}", help="frame size WIDTHxHEIGHT")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    W, H = (int(v) for v in args.size.lower().split("x"))
     import numpy as np
     import torch
     from vbt_amd.overlay import Overlay
@@ -84,8 +98,17 @@ def main():
         ov.set_rows(rows, FPS, stream)
         set_rows_us = (time.perf_counter() - t0) * 1e6
 
+        ovh = None
+        if args.hud:
+            ovh = Overlay(H, W, fmt)
+            ovh.set_rows(rows, FPS, stream)
+            ovh.set_hud(make_phases(TRAIL + B), FPS, stream)
+
         def draw():
             ov.draw(src.data_ptr(), B, frame0, 1, stream)
+
+        def draw_hud():
+            ovh.draw(src.data_ptr(), B, frame0, 1, stream)
 
         def copy():
             rc = hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), nbytes, 3, stream)      # hipMemcpyDeviceToDevice
@@ -95,17 +118,27 @@ def main():
         torch.cuda.synchronize()
         written = int((src != before).sum().item())               # bytes the draw changed on noise (a lower bound of what it writes)
         del before
-        t = {"draw": [], "draw10": [], "copy": []}
+        t = {"draw": [], "draw10": [], "copy": [], "hud": [], "hud10": []}
         for r in range(args.warmup + args.reps):
             one = {"draw": timed(draw), "copy": timed(copy), "draw10": timed(draw, 10)}
+            if ovh is not None:
+                one.update({"hud": timed(draw_hud), "hud10": timed(draw_hud, 10)})
             if r >= args.warmup:
                 for k, v in one.items():
                     t[k].append(v)
-        med = {k: statistics.median(v) for k, v in t.items()}
+        med = {k: statistics.median(v) for k, v in t.items() if v}
         res[fmt] = {"batch_bytes": nbytes, "bytes_changed_by_draw": written, "changed_share": written / nbytes,
-                    "draw_us": med["draw"], "draw_us_min": min(t["draw"]), "draw_back_to_back_us": med["draw10"], "copy_us": med["copy"],
+                    "draw_us": med["draw"], "draw_us_min": min(t["draw"]), "draw_us_max": max(t["draw"]), "draw_back_to_back_us": med["draw10"],
+                    "draw_back_to_back_us_min": min(t["draw10"]), "draw_back_to_back_us_max": max(t["draw10"]), "copy_us": med["copy"],
                     "copy_us_min": min(t["copy"]), "copy_GBps": 2 * nbytes / med["copy"] / 1e3, "draw_over_copy": med["draw"] / med["copy"],
                     "set_rows_us": set_rows_us, "rows": len(rows["id"])}
+        if ovh is not None:
+            prm = dict(x=16, y=16, scale=3)
+            res[fmt]["hud"] = {"panel": [52 * prm["scale"], 50 * prm["scale"]], "phases": 24,
+                               "draw_us": med["hud"], "draw_us_min": min(t["hud"]), "draw_us_max": max(t["hud"]),
+                               "draw_back_to_back_us": med["hud10"], "draw_back_to_back_us_min": min(t["hud10"]),
+                               "draw_back_to_back_us_max": max(t["hud10"]), "increment_us": med["hud"] - med["draw"],
+                               "increment_back_to_back_us": med["hud10"] - med["draw10"], "copy_us": med["copy"]}
     long_rows = make_rows(18000)
     ov = Overlay(H, W, "rgb24")
     ts = []

@@ -69,6 +69,12 @@ class OverlayParams(ctypes.Structure):
                 ("rgb", ctypes.c_uint8 * 3), ("label", ctypes.c_uint8), ("box", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
 
 
+class OverlayHudParams(ctypes.Structure):
+    """vbt_overlay_hud_params (include/vbt_hip.h)"""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("scale", ctypes.c_int32), ("full_scale_cm", ctypes.c_int32),
+                ("bg", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 5)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int), ("algorithmic_bytes", c_double), ("macs", c_double)]
 
@@ -183,6 +189,9 @@ _SIGS = {
     "vbt_overlay_set_rows": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p]),
     "vbt_overlay_draw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vbt_overlay_geometry": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_overlay_hud_default_params": (None, [ctypes.POINTER(OverlayHudParams)]),
+    "vbt_overlay_set_hud": (c_int, [c_void_p, ctypes.POINTER(OverlayHudParams), c_void_p, c_int, c_double, c_void_p]),
+    "vbt_overlay_hud_table": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_mjpeg_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_mjpeg_destroy": (None, [c_void_p]),
     "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -2,7 +2,7 @@
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
-                            [--mjpeg_entropy auto|interval|sync]
+                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
       import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it;
@@ -26,9 +26,15 @@
       on the GPU (include/vbt_hip.h, "MJPEG export") at --video_quality, in an AVI that players open; only the compressed bytes are
       copied back.  Its frame rate is fps / frame_stride, so the export plays in real time - a second deliberate difference: the
       reference writes every 16th frame at the source's full fps (track.py:153-154,166), which plays 16 times too fast.
+      --hud (with --video_dir): the rep panel on every exported frame, drawn on the GPU with the rest (include/vbt_hip.h, "Rep
+      panel") - what the reference's figure shows (plot.py:112-232): the rep count, ROM and ACV of the last completed rep, a bar per
+      recent rep and the phase timeline of the export id, exactly the phases `analyze` prints for the exported DataFrame.  The phases
+      exist once the clip is analysed, so with --hud the frames are rendered after tracking, for every --concurrent.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
                               [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync]
-      the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn).
+                              [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
+      the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn; --hud takes the
+      panel's id from the file name).
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
@@ -85,6 +91,39 @@ class _LiveReps:
         for ln in lines[k:]:
             click.echo(ln)
         self.shown = lines
+
+
+ANALYZE_COLUMNS = ("time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
+
+
+def _id_phases(df, tid, plate_diameter):
+    """The phases of id `tid` of an exported DataFrame (reference plot.py:73-95): what `analyze` prints and what --hud shows"""
+    from .velocity import analyze_rows
+    df = df.query(f"id == {tid}").drop(columns=["id"])
+    return analyze_rows(np.stack([df[c].to_numpy(np.float64) for c in ANALYZE_COLUMNS], axis=1), plate_diameter, preprocess=True)
+
+
+def _hud_options(f):
+    """--hud and what goes with it, for `track` and `overlay`"""
+    for opt in (click.option("--hud_pos", default="16,16", show_default=True, type=str, help="X,Y of the rep panel's top left corner (even for nv12 / i420)."),
+                click.option("--hud_scale", default=3, show_default=True, type=click.IntRange(1, 64), help="Pixels per cell of the rep panel (52 x 50 cells)."),
+                click.option("--plate_diameter", default=0.45, show_default=True, type=float, help="Diameter of the weight plate used in meters (for --hud)."),
+                click.option("--hud", is_flag=True, default=False,
+                             help="Draw the rep panel on the exported frames: rep count, ROM / ACV of the last rep, a bar per rep, phase timeline (needs --video_dir).")):
+        f = opt(f)
+    return f
+
+
+def _hud_params(hud, video_dir, hud_scale, hud_pos):
+    """None without --hud, else the panel's parameters for overlay.render"""
+    if not hud:
+        return None
+    if video_dir is None:
+        raise click.UsageError("--hud draws on the exported frames: give --video_dir")
+    m = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", hud_pos)
+    if not m:
+        raise click.BadParameter(f"expected X,Y (two non-negative integers), got {hud_pos!r}", param_hint="--hud_pos")
+    return dict(x=int(m.group(1)), y=int(m.group(2)), scale=int(hud_scale))
 
 
 def _open_source(s, pix_fmt, size, mjpeg_entropy="auto"):
@@ -164,22 +203,31 @@ def _raw_size(pix_fmt, size):
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
 @click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
               help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
+@_hud_options
 def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality,
-          mjpeg_entropy):
+          mjpeg_entropy, hud, plate_diameter, hud_scale, hud_pos):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     fps_given = _fps_given()
+    hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality, fps_given, mjpeg_entropy)
+                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter)
     default_fps = fps
     for s in src:
         frames = _open_source(s, pix_fmt, size, mjpeg_entropy)
         fps = _source_fps(frames, default_fps, fps_given)
+        if hud_params is not None:                                       # the panel shows the finished analysis: render after tracking
+            data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
+                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt)
+            line, phases = _export_line(data, s, model, df_dir, plate_diameter)
+            _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params)
+            click.echo(line)
+            continue
         mjpeg = video_dir is not None and video_format == "mjpeg"
         video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
         with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
@@ -191,6 +239,17 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
             continue
         df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
         click.echo(f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else ""))
+
+
+def _export_line(data, s, model, df_dir, plate_diameter=None):
+    """Export of a tracked clip: (the line `track` prints, with a plate_diameter (--hud) the phases of the export id - none for a clip
+    without rows)"""
+    from .track import export_dataframe
+    if not data["id"]:
+        return f"{s}: no tracked rows", []
+    df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
+    line = f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else "")
+    return line, (_id_phases(df, best, plate_diameter) if plate_diameter is not None else None)
 
 
 def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size):
@@ -232,26 +291,35 @@ def _video_done(video):
         video.flush()
 
 
-def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, batch, pix_fmt, size):
-    """The export of a finished clip from its rows: DIR/{video}.avi (mjpeg) or the raw map of _video_out.  Returns the frames written."""
+def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, batch, pix_fmt, size, hud=None, hud_params=None):
+    """The export of a finished clip from its rows: DIR/{video}.avi (mjpeg) or the raw map of _video_out.  Returns the frames written.
+    hud_params (--hud): the rep panel of the phases `hud` on every frame; a panel the library refuses (outside the frame, odd origin
+    in a YUV frame) is a usage error."""
+    from ._lib import VbtArgError
     from .overlay import render
-    if video_format == "mjpeg":
-        with _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) as sink:   # closed, hence a valid file, on an error too
-            return render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, sink=sink, quality=video_quality)
-    video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
-    if video is None:
-        return 0
-    render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, out=video)
+    panel = {} if hud_params is None else dict(hud=hud, hud_params=hud_params)
+    try:
+        if video_format == "mjpeg":
+            with _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) as sink:   # closed, hence a valid file, on an error too
+                return render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, sink=sink, quality=video_quality, **panel)
+        video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
+        if video is None:
+            return 0
+        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, out=video, **panel)
+    except VbtArgError as e:
+        if hud_params is None or "vbt_overlay_set_hud" not in str(e):
+            raise
+        raise click.UsageError(f"--hud: {e}")
     _video_done(video)
     return len(video)
 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
-                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto"):
+                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
-    from .track import export_dataframe, track_many
+    from .track import track_many
     sources, error = [], None
     for s in src:
         try:
@@ -264,13 +332,11 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
                               time_batch=time_batch, pix_fmt=pix_fmt):
         s = src[i]
-        if video_dir is not None:                                        # the clip is finished: its rows are all the renderer needs
+        if hud_params is None and video_dir is not None:                 # the clip is finished: its rows are all the renderer needs
             _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size)
-        if not data["id"]:
-            lines[i] = f"{s}: no tracked rows"
-        else:
-            df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
-            lines[i] = f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else "")
+        lines[i], phases = _export_line(data, s, model, df_dir, plate_diameter if hud_params is not None else None)
+        if hud_params is not None:                                       # (--hud: the panel needs the export id's phases first)
+            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size, phases, hud_params)
         while nxt in lines:
             click.echo(lines.pop(nxt))
             nxt += 1
@@ -292,10 +358,16 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
 @click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
               help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
-def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality, mjpeg_entropy):
+@_hud_options
+def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality, mjpeg_entropy, hud, plate_diameter, hud_scale,
+            hud_pos):
     """Draw the boxes, ids and bar paths of a stored DataFrame into the frames of its clip (what `track --video_dir` writes)."""
     import pandas as pd
     size = _raw_size(pix_fmt, size)
+    hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
+    m = FILENAME_RE.match(os.path.basename(dataframe))
+    if hud and not m:
+        raise click.UsageError(f"--hud takes the panel's id from the DataFrame's file name: '{dataframe}' is not {{video}}_id{{N}}_{{model}}.pkl.gz")
     if frame_stride < 1:
         raise click.UsageError("--frame_stride must be at least 1")
     if not os.path.isfile(dataframe):
@@ -303,7 +375,8 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
     frames = _open_source(src, pix_fmt, size, mjpeg_entropy)
     fps = _source_fps(frames, fps, _fps_given())
     df = pd.read_pickle(dataframe)
-    n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size)
+    phases = _id_phases(df, int(m.group(2)), plate_diameter) if hud else None
+    n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size, phases, hud_params)
     click.echo(f"{src}: {n} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")
 
 
@@ -312,8 +385,7 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
 @click.option("--plate_diameter", default=0.45, show_default=True, type=float, help="Diameter of the weight plate used in meters.")
 def analyze(src, plate_diameter):
     import pandas as pd
-    from .velocity import Phase, analyze_rows
-    cols = ["time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width"]
+    from .velocity import Phase
     for s in src:
         if not os.path.isfile(s):
             raise FileNotFoundError(s)                                   # reference plot.py:67-68
@@ -322,9 +394,7 @@ def analyze(src, plate_diameter):
             click.echo(f"Couldn't create a plot for file '{s}'.")        # reference plot.py:81-85
             continue
         video, tid, model = m.groups()
-        df = pd.read_pickle(s)
-        df = df.query(f"id == {tid}").drop(columns=["id"])
-        phases = analyze_rows(np.stack([df[c].to_numpy(np.float64) for c in cols], axis=1), plate_diameter, preprocess=True)
+        phases = _id_phases(pd.read_pickle(s), tid, plate_diameter)
         reps = [p for p in phases if p.type == Phase.CONCENTRIC]
         click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {len(reps)} concentric reps")
         for i, p in enumerate(reps, 1):

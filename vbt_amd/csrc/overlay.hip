@@ -1,11 +1,15 @@
 // Tracking overlay on the device (gfx950): box, id label, marker and bar path of the tracked plates drawn into frames that are
-// already in device memory (include/vbt_hip.h, "tracking overlay"; reference track.py:28-62,201-224).  Two kernels:
+// already in device memory (include/vbt_hip.h, "tracking overlay"; reference track.py:28-62,201-224).  Three kernels:
 //   overlay_prepare_kernel, once per vbt_overlay_set_rows: one thread per row - frame number, the six pixel coordinates, trail length;
 //   overlay_draw_kernel, once per vbt_overlay_draw: grid (row slot x chunk, frame of the batch).  A frame's rows come from the dense
 //     index frame number -> rows (the host builds it while it validates the rows; it sizes the grid from it).  Chunk 0 of a row is its
 //     box outline (a few thousand pixels), chunk 1 its marker and label, chunk 2 + j the 16 trail segments 16 j .. 16 j + 15, one per
 //     16-lane group: a segment is a few dozen candidate pixels, so a wavefront takes four of them and a workgroup sixteen.
-// Nothing reads a pixel and nothing passes over a frame: a workgroup walks its primitive clipped to the frame (overlay_core.h).
+//   overlay_hud_kernel, once more per vbt_overlay_draw when vbt_overlay_set_hud set a rep panel: grid (tile of the panel, frame of the
+//     batch), one thread per 2 x 2 pixel quad - the chroma sample and its four lumas have one owner, and so has every RGB24 byte.
+//     The panel is a gather in two colours: every pixel of its rectangle is tested against the contract and written once.
+// Nothing reads a pixel and nothing passes over a frame: a workgroup walks its primitive clipped to the frame, or its tile of the
+// panel (overlay_core.h).
 #include <algorithm>
 
 #include "common.h"
@@ -17,6 +21,8 @@ constexpr int OV_THREADS = 256;
 constexpr int OV_SEG_LANES = 16;                                  // lanes per trail segment
 constexpr int OV_SEGS_PER_BLOCK = OV_THREADS / OV_SEG_LANES;
 constexpr int OV_MAX_FRAME = 1 << 24;                             // the frame index is dense: 64 MB at most
+constexpr int OV_HUD_TILE_X = 32, OV_HUD_TILE_Y = OV_THREADS / OV_HUD_TILE_X;   // quads of a workgroup: a row of a wavefront's stores is contiguous
+constexpr int OV_HUD_MAX_PHASES = 65536;
 
 struct OverlayDrawArgs {
   const int32_t* geom;     // [n][OV_GEOM]
@@ -28,6 +34,16 @@ struct OverlayDrawArgs {
   int frame0, frame_step, fmax, chunks;
   int H, W, fmt, t, R, s, label, box;
   uint8_t c0, c1, c2;
+};
+
+struct OverlayHudArgs {
+  const int32_t* tab;      // [P][OV_HUD_REC]
+  uint8_t* frames;
+  size_t frame_bytes;
+  int P, frame0, frame_step, tiles_x;
+  int H, W, fmt, X, Y, s, full_scale_cm;
+  int pairs;               // YUV: the frames start at an even address, so two lumas (and NV12's U, V) go out as one 2-byte store
+  uint8_t fg[3], bg[3];    // r, g, b or Y, U, V
 };
 
 __global__ __launch_bounds__(OV_THREADS) void overlay_prepare_kernel(const OverlayRow* __restrict__ rows, int n, double fps, int H, int W, int trail,
@@ -79,6 +95,56 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_draw_kernel(OverlayDrawArg
   }
 }
 
+// The panel lies wholly inside the frame (vbt_overlay_set_hud refuses any other, and the handle's H and W never change) and, for the
+// YUV formats, starts at even coordinates: no store here needs a test against the frame, and a quad is exactly one chroma sample.
+__global__ __launch_bounds__(OV_THREADS) void overlay_hud_kernel(OverlayHudArgs A) {
+  __shared__ OvHudState st;
+  const int64_t f = (int64_t)A.frame0 + (int64_t)blockIdx.y * A.frame_step;
+  if (threadIdx.x < OV_HUD_PARTS) ov_hud_state_part(A.tab, A.P, f, A.frame_step, A.s, A.full_scale_cm, (int)threadIdx.x, st);
+  __syncthreads();
+  const int qx = (int)(blockIdx.x % A.tiles_x) * OV_HUD_TILE_X + (int)threadIdx.x % OV_HUD_TILE_X;
+  const int qy = (int)(blockIdx.x / A.tiles_x) * OV_HUD_TILE_Y + (int)threadIdx.x / OV_HUD_TILE_X;
+  if (qx >= OV_HUD_CELLS_X / 2 * A.s || qy >= OV_HUD_CELLS_Y / 2 * A.s) return;
+  const int rx = 2 * qx, ry = 2 * qy;
+  bool on[2][2];
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+    for (int dx = 0; dx < 2; dx++) on[dy][dx] = ov_hud_covers(st, A.tab, rx + dx, ry + dy, A.s, f, A.frame_step);
+  uint8_t* frame = A.frames + (size_t)blockIdx.y * A.frame_bytes;
+  const int px = A.X + rx, py = A.Y + ry;
+  if (A.fmt == VBT_PIX_RGB24) {                                    // (X may be odd and a pixel is 3 bytes: no alignment to store wider by)
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      uint8_t* p = frame + ((size_t)(py + dy) * A.W + px) * 3;
+#pragma unroll
+      for (int dx = 0; dx < 2; dx++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) p[3 * dx + c] = on[dy][dx] ? A.fg[c] : A.bg[c];
+    }
+    return;
+  }
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++) {
+    uint8_t* p = frame + (size_t)(py + dy) * A.W + px;
+    const uint8_t y0 = on[dy][0] ? A.fg[0] : A.bg[0], y1 = on[dy][1] ? A.fg[0] : A.bg[0];
+    if (A.pairs) *(uint16_t*)p = (uint16_t)(y0 | (y1 << 8));
+    else { p[0] = y0; p[1] = y1; }
+  }
+  const bool any = on[0][0] || on[0][1] || on[1][0] || on[1][1];
+  const uint8_t u = any ? A.fg[1] : A.bg[1], v = any ? A.fg[2] : A.bg[2];
+  uint8_t* chroma = frame + (size_t)A.H * A.W;
+  if (A.fmt == VBT_PIX_NV12) {
+    uint8_t* p = chroma + (size_t)(py >> 1) * A.W + (size_t)(px >> 1) * 2;
+    if (A.pairs) *(uint16_t*)p = (uint16_t)(u | (v << 8));
+    else { p[0] = u; p[1] = v; }
+  } else {
+    const size_t i = (size_t)(py >> 1) * (A.W >> 1) + (px >> 1);
+    chroma[i] = u;
+    chroma[(size_t)(A.H >> 1) * (A.W >> 1) + i] = v;
+  }
+}
+
 }  // namespace vbt
 
 using namespace vbt;
@@ -95,6 +161,11 @@ struct vbt_overlay {
   const int32_t *d_frow = nullptr, *d_fstart = nullptr;
   int32_t* d_geom = nullptr;
   std::vector<int32_t> fstart;           // the host's copy of the index: sizes the grid of a draw
+  bool hud = false;                      // a rep panel is set (vbt_overlay_set_hud)
+  vbt_overlay_hud_params hud_prm{};
+  uint8_t b0 = 0, b1 = 0, b2 = 0;        // the panel's background in the frames' format
+  int hud_P = 0;
+  int32_t* d_hud = nullptr;              // [hud_P][OV_HUD_REC], an allocation of its own
 };
 
 namespace {
@@ -116,6 +187,79 @@ int check_rows(const OverlayRow* rows, int n, double fps) {
     }
   }
   return VBT_OK;
+}
+
+// the colour of the frames' format: r, g, b or the contract's Y, U, V
+void overlay_colour(int fmt, const uint8_t* rgb, uint8_t* c) {
+  const int r = rgb[0], g = rgb[1], b = rgb[2];
+  if (fmt == VBT_PIX_RGB24) { c[0] = rgb[0]; c[1] = rgb[1]; c[2] = rgb[2]; return; }
+  c[0] = (uint8_t)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
+  c[1] = (uint8_t)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
+  c[2] = (uint8_t)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
+}
+
+// the refusals of vbt_overlay_set_hud that need no handle and no device; on VBT_OK `tab` is the table to upload
+int check_hud(const vbt_overlay_hud_params* prm, const double* ph, int P, double fps, std::vector<int32_t>& tab) {
+  if (P < 0 || (P > 0 && (!ph || !prm))) {
+    set_error("vbt_overlay_set_hud: bad argument (P %d, phases %p, params %p)", P, (const void*)ph, (const void*)prm);
+    return VBT_ERR_ARG;
+  }
+  if (!(fps > 0) || !std::isfinite(fps)) { set_error("vbt_overlay_set_hud: fps must be positive and finite, got %g", fps); return VBT_ERR_ARG; }
+  for (int i = 0; i < P; i++) {
+    const double* r = ph + (size_t)i * 6;
+    for (int k = 0; k < 6; k++)
+      if (!std::isfinite(r[k])) { set_error("vbt_overlay_set_hud: phase %d holds a non-finite value", i); return VBT_ERR_ARG; }
+    if (r[5] != 0.0 && r[5] != 1.0 && r[5] != 2.0) { set_error("vbt_overlay_set_hud: phase %d has type %g, not 0, 1 or 2", i, r[5]); return VBT_ERR_ARG; }
+    if (r[1] < r[0]) { set_error("vbt_overlay_set_hud: phase %d ends before it starts (time_end < time_start)", i); return VBT_ERR_ARG; }
+    if (i > 0 && (r[0] < r[-6] || r[1] < r[-5])) { set_error("vbt_overlay_set_hud: phases are not ordered in time at phase %d", i); return VBT_ERR_ARG; }
+  }
+  if (prm->scale < 1 || prm->scale > 64) { set_error("vbt_overlay_set_hud: scale %d outside 1..64", prm->scale); return VBT_ERR_ARG; }
+  if (prm->full_scale_cm < 1 || prm->full_scale_cm > 100000) { set_error("vbt_overlay_set_hud: full_scale_cm %d outside 1..100000", prm->full_scale_cm); return VBT_ERR_ARG; }
+  if (prm->x < 0 || prm->y < 0) { set_error("vbt_overlay_set_hud: negative panel origin (%d, %d)", prm->x, prm->y); return VBT_ERR_ARG; }
+  if (P > OV_HUD_MAX_PHASES) { set_error("vbt_overlay_set_hud: %d phases, above %d", P, OV_HUD_MAX_PHASES); return VBT_ERR_CAPACITY; }
+  tab.assign((size_t)P * OV_HUD_REC, 0);
+  int count = 0;
+  for (int i = 0; i < P; i++) {
+    const double* r = ph + (size_t)i * 6;
+    int32_t* t = tab.data() + (size_t)i * OV_HUD_REC;
+    t[OV_HUD_FS] = ov_frame_number(r[0], fps);
+    t[OV_HUD_FE] = ov_frame_number(r[1], fps);
+    if (t[OV_HUD_FE] > OV_MAX_FRAME) { set_error("vbt_overlay_set_hud: phase %d ends at frame %d, above %d", i, t[OV_HUD_FE], OV_MAX_FRAME); return VBT_ERR_CAPACITY; }
+    const double dur = r[1] - r[0];
+    t[OV_HUD_ROM] = ov_centi(r[4]);
+    t[OV_HUD_ACV] = dur > 0 ? ov_centi(r[4] / dur) : 0;
+    t[OV_HUD_TYPE] = (int32_t)r[5];
+    count += t[OV_HUD_TYPE] == 0;
+    t[OV_HUD_COUNT] = count;
+  }
+  return VBT_OK;
+}
+
+// the launches of the row primitives (rules 1-4) for a handle with rows
+void overlay_launch_rows(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, int MAX_Y, hipStream_t stream) {
+  OverlayDrawArgs A{};
+  A.geom = o->d_geom; A.ids = (const int64_t*)o->d_rows; A.fstart = o->d_fstart; A.frow = o->d_frow;
+  A.frame_bytes = o->frame_bytes; A.frame_step = frame_step; A.fmax = o->fmax; A.chunks = o->chunks;
+  A.H = o->H; A.W = o->W; A.fmt = o->fmt; A.t = o->prm.thickness; A.R = o->prm.radius; A.s = o->prm.label_scale;
+  A.label = o->prm.label; A.box = o->prm.box; A.c0 = o->c0; A.c1 = o->c1; A.c2 = o->c2;
+  for (int b0 = 0; b0 < B; b0 += MAX_Y) {
+    const int nb = std::min(MAX_Y, B - b0);
+    int most = 0;                                                 // rows of the fullest frame of this launch
+    for (int i = 0; i < nb; i++) {
+      const long f = (long)frame0 + (long)(b0 + i) * frame_step;
+      if (f > o->fmax) break;
+      most = std::max(most, o->fstart[f + 1] - o->fstart[f]);
+    }
+    if (most == 0) continue;
+    A.frames = frames_dev + (size_t)b0 * o->frame_bytes;
+    A.frame0 = (int)((long)frame0 + (long)b0 * frame_step);
+    overlay_draw_kernel<<<dim3((unsigned)most * (unsigned)o->chunks, (unsigned)nb), OV_THREADS, 0, stream>>>(A);
+  }
+}
+
+void overlay_free_hud(vbt_overlay* o) {
+  if (o->d_hud) (void)hipFree(o->d_hud);   // (waits for the draws still reading it)
+  o->d_hud = nullptr; o->hud_P = 0; o->hud = false;
 }
 
 void overlay_free_rows(vbt_overlay* o) {
@@ -152,16 +296,10 @@ int vbt_overlay_create(int device, int H, int W, int pix_fmt, const vbt_overlay_
   if (int rc = use_device("vbt_overlay_create", device, /*set_current=*/false)) return rc;
   vbt_overlay* o = new vbt_overlay();
   o->device = device; o->H = H; o->W = W; o->fmt = pix_fmt; o->prm = p;
-  const int r = p.rgb[0], g = p.rgb[1], b = p.rgb[2];
-  if (pix_fmt == VBT_PIX_RGB24) {
-    o->c0 = (uint8_t)r; o->c1 = (uint8_t)g; o->c2 = (uint8_t)b;
-    o->frame_bytes = (size_t)H * W * 3;
-  } else {
-    o->c0 = (uint8_t)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
-    o->c1 = (uint8_t)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
-    o->c2 = (uint8_t)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
-    o->frame_bytes = (size_t)H * W * 3 / 2;
-  }
+  uint8_t c[3];
+  overlay_colour(pix_fmt, p.rgb, c);
+  o->c0 = c[0]; o->c1 = c[1]; o->c2 = c[2];
+  o->frame_bytes = pix_fmt == VBT_PIX_RGB24 ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2;
   o->chunks = 2 + (p.trail - 1 + OV_SEGS_PER_BLOCK - 1) / OV_SEGS_PER_BLOCK;
   *out = o;
   return VBT_OK;
@@ -169,7 +307,7 @@ int vbt_overlay_create(int device, int H, int W, int pix_fmt, const vbt_overlay_
 
 void vbt_overlay_destroy(vbt_overlay* o) {
   if (!o) return;
-  if (hipSetDevice(o->device) == hipSuccess) overlay_free_rows(o);
+  if (hipSetDevice(o->device) == hipSuccess) { overlay_free_rows(o); overlay_free_hud(o); }
   delete o;
 }
 
@@ -230,28 +368,83 @@ int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int
     set_error("vbt_overlay_draw: bad argument (B >= 0, frame0 >= 1, frame_step >= 1, frame numbers inside int32)");
     return VBT_ERR_ARG;
   }
-  if (B == 0 || o->n == 0) return VBT_OK;
+  if (B == 0 || (o->n == 0 && !o->hud)) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(o->device));
-  OverlayDrawArgs A{};
-  A.geom = o->d_geom; A.ids = (const int64_t*)o->d_rows; A.fstart = o->d_fstart; A.frow = o->d_frow;
-  A.frame_bytes = o->frame_bytes; A.frame_step = frame_step; A.fmax = o->fmax; A.chunks = o->chunks;
-  A.H = o->H; A.W = o->W; A.fmt = o->fmt; A.t = o->prm.thickness; A.R = o->prm.radius; A.s = o->prm.label_scale;
-  A.label = o->prm.label; A.box = o->prm.box; A.c0 = o->c0; A.c1 = o->c1; A.c2 = o->c2;
   constexpr int MAX_Y = 32768;                                    // frames per launch (grid.y)
-  for (int b0 = 0; b0 < B; b0 += MAX_Y) {
-    const int nb = std::min(MAX_Y, B - b0);
-    int most = 0;                                                 // rows of the fullest frame of this launch
-    for (int i = 0; i < nb; i++) {
-      const long f = (long)frame0 + (long)(b0 + i) * frame_step;
-      if (f > o->fmax) break;
-      most = std::max(most, o->fstart[f + 1] - o->fstart[f]);
+  if (o->n > 0) overlay_launch_rows(o, frames_dev, B, frame0, frame_step, MAX_Y, (hipStream_t)stream);
+  if (o->hud) {                                                   // after the rows, on the same stream: the panel wins
+    const vbt_overlay_hud_params& hp = o->hud_prm;
+    OverlayHudArgs G{};
+    G.tab = o->d_hud; G.frame_bytes = o->frame_bytes; G.P = o->hud_P; G.frame_step = frame_step;
+    G.H = o->H; G.W = o->W; G.fmt = o->fmt; G.X = hp.x; G.Y = hp.y; G.s = hp.scale; G.full_scale_cm = hp.full_scale_cm;
+    G.fg[0] = o->c0; G.fg[1] = o->c1; G.fg[2] = o->c2; G.bg[0] = o->b0; G.bg[1] = o->b1; G.bg[2] = o->b2;
+    G.pairs = o->fmt != VBT_PIX_RGB24 && ((uintptr_t)frames_dev & 1) == 0;        // (a YUV frame has an even number of bytes)
+    G.tiles_x = (OV_HUD_CELLS_X / 2 * hp.scale + OV_HUD_TILE_X - 1) / OV_HUD_TILE_X;
+    const int tiles_y = (OV_HUD_CELLS_Y / 2 * hp.scale + OV_HUD_TILE_Y - 1) / OV_HUD_TILE_Y;
+    for (int b0 = 0; b0 < B; b0 += MAX_Y) {
+      G.frames = frames_dev + (size_t)b0 * o->frame_bytes;
+      G.frame0 = (int)((long)frame0 + (long)b0 * frame_step);
+      overlay_hud_kernel<<<dim3((unsigned)(G.tiles_x * tiles_y), (unsigned)std::min(MAX_Y, B - b0)), OV_THREADS, 0, (hipStream_t)stream>>>(G);
     }
-    if (most == 0) continue;
-    A.frames = frames_dev + (size_t)b0 * o->frame_bytes;
-    A.frame0 = (int)((long)frame0 + (long)b0 * frame_step);
-    overlay_draw_kernel<<<dim3((unsigned)most * (unsigned)o->chunks, (unsigned)nb), OV_THREADS, 0, (hipStream_t)stream>>>(A);
   }
   VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+void vbt_overlay_hud_default_params(vbt_overlay_hud_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->x = 16; p->y = 16; p->scale = 3; p->full_scale_cm = 200;
+}
+
+int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, const double* phases6_host, int P, double fps, void* stream) {
+  if (!params && P == 0) {                                          // the panel off
+    if (!o) { set_error("vbt_overlay_set_hud: handle is NULL"); return VBT_ERR_ARG; }
+    VBT_HIP_CHECK(hipSetDevice(o->device));
+    overlay_free_hud(o);
+    return VBT_OK;
+  }
+  std::vector<int32_t> tab;
+  if (int rc = check_hud(params, phases6_host, P, fps, tab)) return rc;
+  if (!o) { set_error("vbt_overlay_set_hud: handle is NULL"); return VBT_ERR_ARG; }
+  const bool yuv = o->fmt != VBT_PIX_RGB24;
+  if (yuv && ((params->x | params->y) & 1)) {
+    set_error("vbt_overlay_set_hud: a YUV 4:2:0 panel starts at even coordinates, got (%d, %d)", params->x, params->y);
+    return VBT_ERR_ARG;
+  }
+  if ((long)params->x + OV_HUD_CELLS_X * params->scale > o->W || (long)params->y + OV_HUD_CELLS_Y * params->scale > o->H) {
+    set_error("vbt_overlay_set_hud: the %d x %d panel at (%d, %d) does not lie inside the %d x %d frame", OV_HUD_CELLS_X * params->scale,
+              OV_HUD_CELLS_Y * params->scale, params->x, params->y, o->W, o->H);
+    return VBT_ERR_ARG;
+  }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  int32_t* d = nullptr;
+  if (P > 0) {
+    VBT_HIP_CHECK(hipMalloc((void**)&d, tab.size() * 4));
+    hipError_t e = hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);    // (`tab` leaves scope: the copy must have read it)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      set_error("vbt_overlay_set_hud failed: %s", hipGetErrorString(e));
+      return VBT_ERR_HIP;
+    }
+  }
+  overlay_free_hud(o);
+  o->d_hud = d; o->hud_P = P; o->hud = true; o->hud_prm = *params;
+  uint8_t c[3];
+  overlay_colour(o->fmt, params->bg, c);
+  o->b0 = c[0]; o->b1 = c[1]; o->b2 = c[2];
+  return VBT_OK;
+}
+
+int vbt_overlay_hud_table(vbt_overlay* o, int32_t* out, int cap, int* P) {
+  if (!o || !P || cap < 0 || (cap > 0 && !out)) { set_error("vbt_overlay_hud_table: bad argument"); return VBT_ERR_ARG; }
+  *P = o->hud_P;
+  if (cap < o->hud_P) { set_error("vbt_overlay_hud_table: %d phases, room for %d", o->hud_P, cap); return VBT_ERR_CAPACITY; }
+  if (o->hud_P == 0) return VBT_OK;
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  VBT_HIP_CHECK(hipMemcpy(out, o->d_hud, (size_t)o->hud_P * OV_HUD_REC * 4, hipMemcpyDeviceToHost));
   return VBT_OK;
 }
 

@@ -175,4 +175,122 @@ __host__ __device__ inline void ov_draw_segment(const Painter& P, int x0, int y0
   }
 }
 
+// ---- rep panel (include/vbt_hip.h, "Rep panel"): a gather - every pixel of the panel rectangle is tested and written once ----
+
+// record of a phase (vbt_overlay_hud_table): 6 int32; OV_HUD_COUNT = the concentric phases among phases 0 .. this one
+enum { OV_HUD_FS = 0, OV_HUD_FE, OV_HUD_ROM, OV_HUD_ACV, OV_HUD_TYPE, OV_HUD_COUNT, OV_HUD_REC = 6 };
+enum { OV_HUD_CELLS_X = 52, OV_HUD_CELLS_Y = 50, OV_HUD_LINE = 8, OV_HUD_CHARS = 24, OV_HUD_BARS = 8, OV_HUD_SPAN = 47, OV_HUD_BAR_CELLS = 12 };
+enum { OV_GLYPH_R = 12, OV_GLYPH_E, OV_GLYPH_P, OV_GLYPH_O, OV_GLYPH_M, OV_GLYPH_A, OV_GLYPH_C, OV_GLYPH_V, OV_GLYPH_DOT, OV_GLYPH_SPACE };
+
+__host__ __device__ inline uint64_t ov_hud_glyph(int g) {
+  switch (g) {
+    case OV_GLYPH_R: return 0x7a31f5251ull; case OV_GLYPH_E: return 0x7e10f421full; case OV_GLYPH_P: return 0x7a31f4210ull;
+    case OV_GLYPH_O: return 0x3a318c62eull; case OV_GLYPH_M: return 0x4775ac631ull; case OV_GLYPH_A: return 0x3a31fc631ull;
+    case OV_GLYPH_C: return 0x3a308422eull; case OV_GLYPH_V: return 0x46318c544ull; case OV_GLYPH_DOT: return 0x18cull;
+    case OV_GLYPH_SPACE: return 0;
+    default: return ov_glyph(g);
+  }
+}
+
+// centimetres (per second) of a ROM / ACV in metres: the panel's own rounding
+__host__ __device__ inline int32_t ov_centi(double v) {
+  if (!(v > 0)) return 0;                              // NaN too
+  const double c = v * 100.0;
+  return (int32_t)llrint(c < 9999.0 ? c : 9999.0);
+}
+
+// first i of [lo, hi) with tab[i][col] >= v, hi if there is none; the column does not decrease along the table
+__host__ __device__ inline int ov_hud_lower_bound(const int32_t* tab, int lo, int hi, int col, int64_t v) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if ((int64_t)tab[(size_t)mid * OV_HUD_REC + col] >= v) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// n of frame f: the concentric phases with fe <= f
+__host__ __device__ inline int ov_hud_completed(const int32_t* tab, int P, int64_t f) {
+  const int ub = ov_hud_lower_bound(tab, 0, P, OV_HUD_FE, f + 1);
+  return ub > 0 ? tab[(size_t)(ub - 1) * OV_HUD_REC + OV_HUD_COUNT] : 0;
+}
+// table index of completed rep number m (0-based, m < n): the first phase whose running count reaches m + 1
+__host__ __device__ inline int ov_hud_rep(const int32_t* tab, int P, int m) { return ov_hud_lower_bound(tab, 0, P, OV_HUD_COUNT, (int64_t)m + 1); }
+
+// v (< 100000) in decimal, right-aligned in 5
+__host__ __device__ inline void ov_hud_number(int v, uint8_t* out) {
+  for (int k = 4; k >= 0; k--) {
+    out[k] = (uint8_t)(k == 4 || v ? v % 10 : OV_GLYPH_SPACE);
+    v /= 10;
+  }
+}
+// field(v) of the contract, v <= 9999
+__host__ __device__ inline void ov_hud_field(int n, int v, uint8_t* out) {
+  if (n == 0) { for (int k = 0; k < 5; k++) out[k] = OV_GLYPH_SPACE; return; }
+  const int w = v / 100;
+  out[0] = (uint8_t)(w >= 10 ? w / 10 % 10 : OV_GLYPH_SPACE); out[1] = (uint8_t)(w % 10); out[2] = OV_GLYPH_DOT;
+  out[3] = (uint8_t)(v / 10 % 10); out[4] = (uint8_t)(v % 10);
+}
+__host__ __device__ inline int ov_hud_bar_height(int acv_cm, int s, int full_scale_cm) {
+  const int64_t top = (int64_t)OV_HUD_BAR_CELLS * s, hb = (int64_t)acv_cm * top / full_scale_cm;
+  return (int)(hb < 1 ? 1 : (hb > top ? top : hb));
+}
+
+// What every pixel of a frame's panel needs, formed once per frame (per workgroup, in LDS)
+struct OvHudState {
+  int32_t n;
+  int32_t hb[OV_HUD_BARS];           // 0: the slot is empty
+  int32_t lo, hi;                    // the phases the timeline's columns can meet are [lo, hi)
+  uint8_t chars[OV_HUD_CHARS];
+};
+// The state in OV_HUD_PARTS independent parts, one per lane (or per turn of a host loop): 0 = n and the text, 1 + j = bar j, 9 = [lo, hi)
+enum { OV_HUD_PARTS = 2 + OV_HUD_BARS };
+__host__ __device__ inline void ov_hud_state_part(const int32_t* tab, int P, int64_t f, int frame_step, int s, int full_scale_cm, int part, OvHudState& st) {
+  if (part == OV_HUD_PARTS - 1) {
+    int64_t first = f - (int64_t)(OV_HUD_SPAN * s - 1) * frame_step;              // the frame of column 0
+    first = first < 1 ? 1 : first;
+    const int lo = ov_hud_lower_bound(tab, 0, P, OV_HUD_FE, first), last = ov_hud_lower_bound(tab, 0, P, OV_HUD_FE, f);
+    st.hi = last < P ? last + 1 : P;                                              // the phase that holds frame f itself is the last candidate
+    st.lo = lo < st.hi ? lo : st.hi;
+    return;
+  }
+  const int n = ov_hud_completed(tab, P, f);
+  if (part == 0) {
+    int rom = 0, acv = 0;
+    if (n > 0) {
+      const int32_t* r = tab + (size_t)ov_hud_rep(tab, P, n - 1) * OV_HUD_REC;
+      rom = r[OV_HUD_ROM]; acv = r[OV_HUD_ACV];
+    }
+    st.n = n;
+    uint8_t* c = st.chars;
+    c[0] = OV_GLYPH_R; c[1] = OV_GLYPH_E; c[2] = OV_GLYPH_P; ov_hud_number(n < 99999 ? n : 99999, c + 3);
+    c[8] = OV_GLYPH_R; c[9] = OV_GLYPH_O; c[10] = OV_GLYPH_M; ov_hud_field(n, rom, c + 11);
+    c[16] = OV_GLYPH_A; c[17] = OV_GLYPH_C; c[18] = OV_GLYPH_V; ov_hud_field(n, acv, c + 19);
+    return;
+  }
+  const int j = part - 1, m = (n > OV_HUD_BARS ? n - OV_HUD_BARS : 0) + j;
+  st.hb[j] = m < n ? ov_hud_bar_height(tab[(size_t)ov_hud_rep(tab, P, m) * OV_HUD_REC + OV_HUD_ACV], s, full_scale_cm) : 0;
+}
+
+// The contract's test for the panel pixel (rx, ry), counted from the panel's origin, of frame f
+__host__ __device__ inline bool ov_hud_covers(const OvHudState& st, const int32_t* tab, int rx, int ry, int s, int64_t f, int frame_step) {
+  const int ux = rx - 2 * s;
+  if (ux < 0 || ux >= OV_HUD_SPAN * s) return false;                              // text, bars and timeline all span 47 cells
+  if (ry < 29 * s) {                                                              // text: lines at 2 s, 11 s, 20 s, 7 cells high
+    const int uy = ry - 2 * s;
+    if (uy < 0 || uy >= 27 * s) return false;
+    const int l = uy / (9 * s), r = (uy - l * 9 * s) / s, k = ux / (6 * s), c = (ux - k * 6 * s) / s;
+    return r < 7 && c < 5 && ((ov_hud_glyph(st.chars[l * OV_HUD_LINE + k]) >> (5 * (6 - r) + 4 - c)) & 1);
+  }
+  if (ry < 41 * s) {                                                              // bars: bottom at 41 s, at most 12 cells high
+    const int k = ux / (6 * s);
+    return ux - k * 6 * s < 5 * s && ry >= 41 * s - st.hb[k];
+  }
+  if (ry < 43 * s || ry >= 47 * s) return false;
+  const int64_t fc = f - (int64_t)(OV_HUD_SPAN * s - 1 - ux) * frame_step;
+  if (fc < 1) return false;
+  const int i = ov_hud_lower_bound(tab, st.lo, st.hi, OV_HUD_FE, fc);             // fs does not decrease either: no later phase can hold fc
+  if (i >= st.hi || !((int64_t)tab[(size_t)i * OV_HUD_REC + OV_HUD_FS] < fc)) return false;
+  const int type = tab[(size_t)i * OV_HUD_REC + OV_HUD_TYPE];
+  return type == 0 || (type == 1 && ry >= 45 * s);
+}
+
 }  // namespace vbt

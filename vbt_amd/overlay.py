@@ -15,6 +15,7 @@ from .ocsort import ROW_DTYPE
 from .rawvideo import frame_shape, pix_fmt_code, source_hw
 
 COLUMNS = ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
+HUD_PARAMS = ("x", "y", "scale", "full_scale_cm", "bg")
 COLORS = [(252, 3, 115), (255, 255, 255)]          # COLORS of reference track.py:23 (BGR there) as RGB; the reference draws with [1]
 
 
@@ -25,6 +26,13 @@ def sorted_rows(data):
     for k in COLUMNS:
         rows[k] = np.asarray(data[k])
     return rows[np.lexsort((rows["time"], rows["id"]))]
+
+
+def phases6(phases):
+    """[P,6] array (time_start, time_end, y_start, y_end, rom, type - what vbt_analyze returns) or a list of velocity.Phase -> float64 [P,6]"""
+    if len(phases) and hasattr(phases[0], "time_start"):
+        phases = [(p.time_start, p.time_end, p.y_start, p.y_end, p.rom, p.type) for p in phases]
+    return np.ascontiguousarray(np.asarray(phases, np.float64).reshape(-1, 6))
 
 
 class Overlay:
@@ -47,6 +55,7 @@ class Overlay:
         _lib.check(L.vbt_overlay_create(self.device, self.H, self.W, pix_fmt_code(pix_fmt), ctypes.byref(prm), ctypes.byref(h)))
         self._h = h
         self.n = 0
+        self.hud_n = 0
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -63,6 +72,39 @@ class Overlay:
         """B frames at device pointer `frames_ptr`, frame i = frame number frame0 + i * frame_step; in place, enqueue only"""
         _lib.check(_lib.lib().vbt_overlay_draw(self._h, int(frames_ptr), int(B), int(frame0), int(frame_step), stream))
 
+    def set_hud(self, phases, fps=None, stream=None, **hud_params):
+        """The rep panel (include/vbt_hip.h, "Rep panel") of ONE id on every frame drawn from now on: rep count, ROM / ACV of the last
+        completed rep, a bar per recent rep, the phase timeline.  phases: [P,6] array or list of velocity.Phase (P = 0: "REP    0");
+        None switches the panel off.  hud_params: x=16, y=16, scale=3, full_scale_cm=200, bg=(0, 0, 0)."""
+        L = _lib.lib()
+        if phases is None:
+            if hud_params:
+                raise TypeError("Overlay.set_hud: no parameters go with phases=None (the panel off)")
+            _lib.check(L.vbt_overlay_set_hud(self._h, None, None, 0, 1.0, stream))
+            self.hud_n = 0
+            return
+        if fps is None:
+            raise TypeError("Overlay.set_hud: fps is needed with phases")
+        prm = _lib.OverlayHudParams()
+        L.vbt_overlay_hud_default_params(ctypes.byref(prm))
+        for k, v in hud_params.items():
+            if k == "bg":
+                prm.bg[:] = [int(c) for c in v]
+            elif k in HUD_PARAMS:
+                setattr(prm, k, int(v))
+            else:
+                raise TypeError(f"Overlay.set_hud: unknown parameter {k!r}")
+        ph = phases6(phases)
+        _lib.check(L.vbt_overlay_set_hud(self._h, ctypes.byref(prm), ph.ctypes.data if len(ph) else None, len(ph), float(fps), stream))
+        self.hud_n = len(ph)
+
+    def hud_table(self):
+        """int32 [P, 6] = fs, fe, rom_cm, acv_cm, type, concentric phases so far, of every phase of the panel (vbt_overlay_hud_table)"""
+        out = np.zeros((max(self.hud_n, 1), 6), np.int32)
+        n = ctypes.c_int()
+        _lib.check(_lib.lib().vbt_overlay_hud_table(self._h, out.ctypes.data, len(out), ctypes.byref(n)))
+        return out[:n.value]
+
     def geometry(self):
         """int32 [n, 8] = frame, cx, cy, xmin, ymin, xmax, ymax, trail length of every row (vbt_overlay_geometry)"""
         out = np.zeros((max(self.n, 1), 8), np.int32)
@@ -71,14 +113,16 @@ class Overlay:
         return out[:n.value]
 
 
-def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, **params):
+def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, hud=None, hud_params=None,
+           **params):
     """The kept frames of a clip (1-based number a multiple of frame_stride, reference track.py:166) with the overlay of `data`:
     frames uint8 [T,H,W,3] (or [T,H*3//2,W] for "nv12" / "i420"; numpy array or memmap), `batch` frames at a time through the device.
     Returns (or fills `out`, e.g. a numpy.lib.format.open_memmap) uint8 [T // frame_stride, ...] of the same layout.  Unlike the
     reference (track.py:180-181,241-242) every kept frame is there: one without rows comes back undrawn.
     sink: an mjpeg.AviWriter - each batch is then uploaded, drawn, encoded as JPEG on the device at `quality` (mjpeg.Encoder, on the
     stream of the draw, nothing synchronised in between) and only its compressed bytes are read back and written to the sink; `out`
-    is not used and the number of frames written is returned."""
+    is not used and the number of frames written is returned.
+    hud: the phases of one id (what Overlay.set_hud takes) - the rep panel is then drawn on every kept frame, with hud_params (a dict)."""
     stride = max(int(frame_stride), 1)
     H, W = source_hw(frames, pix_fmt)
     shape = frame_shape(pix_fmt, H, W)
@@ -93,6 +137,8 @@ def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=Non
         raise ValueError(f"render: out must be uint8 {(kept,) + shape}, got {out.dtype} {tuple(out.shape)}")
     ov = Overlay(H, W, pix_fmt, device=device, **params)
     ov.set_rows(data, fps)
+    if hud is not None:
+        ov.set_hud(hud, fps, **(hud_params or {}))
     L = _lib.lib()
     B = max(1, min(int(batch), max(kept, 1)))
     fb = int(np.prod(shape))
