@@ -221,6 +221,10 @@ int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int3
  * norm_plate_height, norm_plate_width}, all ids in emission order; counts[c] = number of rows of clip c.
  * rows_host may be pinned host memory (one DMA) or pageable. */
 int vbt_tracker_rows_all(vbt_tracker* t, int32_t* counts, void* rows_host, int cap, void* stream);
+/* The row log of `clip` where it lives, in device memory: *rows_dev = its 64-byte records in emission order (room for *rows_cap),
+ * *nrows_dev = the device int32 that counts them (never above *rows_cap; vbt_tracker_reset / _reset_clips set it back to 0).
+ * Borrowed pointers, valid until the tracker is destroyed; no device call.  VBT_ERR_ARG: a NULL argument, a clip out of range. */
+int vbt_tracker_rows_dev(vbt_tracker* t, int clip, const void** rows_dev, const int32_t** nrows_dev, int* rows_cap);
 
 /* Live rep analysis (off unless enabled): per-rep ROM / ACV while the clips are still being tracked.
  * After every tracker launch one more kernel on the same stream feeds the rows it appended to the log, in emission order, to the
@@ -586,7 +590,31 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
  * Colours.  VBT_PIX_RGB24: a covered panel pixel gets fg, every other panel pixel bg.  YUV: luma per pixel in the same way; the chroma
  * sample at (py >> 1, px >> 1) gets fg's U, V if any of its four pixels is covered, else bg's - both colours through the integers
  * above.  For the YUV formats X and Y are even (52 s and 50 s always are): every chroma sample of the panel lies wholly inside it.
- * Every byte outside the panel rectangle is left as the rules above left it. */
+ * Every byte outside the panel rectangle is left as the rules above left it.
+ *
+ * Following a device row log (vbt_overlay_follow).  The raster contract is the one above; follow mode changes only where the rows come
+ * from and when they become known.  The handle consumes a row log: rows_dev, the 64-byte records in emission order in device memory,
+ * and nrows_dev, a device int32 with the number of valid records, which the log's writer (the tracker) advances.  The overlay only
+ * ever reads both.  vbt_overlay_follow_update consumes rows [cursor, min(*nrows_dev, rows_cap)) in log order.  For each row it forms
+ * the integers above by the statements of the prepare kernel (frame = llrint(time * fps) included).  The trail of a row is that row
+ * and the up to trail - 1 ACCEPTED rows of the same id before it IN THE LOG; for a log whose per-id times do not decrease that is
+ * the (id, time) order of vbt_overlay_set_rows.
+ * Equality.  Let L be a log prefix that vbt_overlay_set_rows accepts once sorted by (id, time), every frame number in 1..max_frame
+ * and no frame with more than max_rows_per_frame rows, and f a frame number not above the largest one in L.  vbt_overlay_draw of
+ * frame f in follow mode then writes exactly the bytes it writes in sorted mode with the rows of the WHOLE clip: rows of later
+ * frames never reach frame f.  How the log was cut into updates does not matter: one update per frame, per batch or for the whole
+ * log leave the same handle state.
+ * Skipped rows.  A kernel cannot refuse a call: it skips the row and says so.  A row is skipped when vbt_overlay_set_rows would
+ * refuse it on its own (a non-finite value, id < 0, w < 0 or h < 0: VBT_OVERLAY_FOLLOW_BAD_ROW), when its time is smaller than that
+ * of the previous accepted row of its id (_ORDER), when its frame number is outside 1..max_frame (_FRAME_RANGE), or when its frame
+ * already holds max_rows_per_frame accepted rows (_FRAME_FULL); the first of these that holds, in this order of tests: BAD_ROW,
+ * FRAME_RANGE, ORDER, FRAME_FULL.  A skipped row is not drawn, joins no trail, and sets its bit in a device word that
+ * vbt_overlay_follow_status reads; its vbt_overlay_geometry record has trail length 0 (and is all zero for a BAD_ROW).  The equality
+ * above holds while the flags are 0.
+ * Rewound log.  *nrows_dev < cursor: the clip was reset or recycled.  Nothing is consumed, VBT_OVERLAY_FOLLOW_REWOUND is set, and the
+ * caller calls vbt_overlay_follow again.
+ * Frames without an accepted row, and frames beyond the last consumed row, are not touched.  The rep panel does not depend on the
+ * row source: vbt_overlay_set_hud works on a handle in follow mode as on any other. */
 typedef struct vbt_overlay vbt_overlay;
 typedef struct {
   int32_t trail;        /* bar path length in points, track.py:57-58 -> 120 */
@@ -636,6 +664,34 @@ void vbt_overlay_hud_default_params(vbt_overlay_hud_params* p);
  * Builds the table of per-phase integers (fs, fe, rom_cm, acv_cm, type, concentric phases up to and including this one) on the host,
  * uploads it in one copy on `stream` and synchronises it. */
 int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, const double* phases6_host, int P, double fps, void* stream);
+
+/* Follow mode ("Following a device row log" above) */
+enum {
+  VBT_OVERLAY_FOLLOW_BAD_ROW = 1,
+  VBT_OVERLAY_FOLLOW_ORDER = 2,
+  VBT_OVERLAY_FOLLOW_FRAME_RANGE = 4,
+  VBT_OVERLAY_FOLLOW_FRAME_FULL = 8,
+  VBT_OVERLAY_FOLLOW_REWOUND = 16
+};
+/* Switch the handle to follow mode: it replaces the handle's rows, and vbt_overlay_set_rows switches back.  rows_dev / nrows_dev are
+ * borrowed (vbt_tracker_rows_dev gives a clip's) and must outlive the handle's use of them.  Allocates, for rows_cap rows and frames
+ * 1..max_frame: 48 bytes per row (geometry, links), 8 per frame (the frame index) and 16 per slot of the id table (the power of two
+ * >= 2 rows_cap).  Synchronous (allocation + clears).  VBT_ERR_ARG, before any device call: a NULL pointer, rows_cap < 1, max_frame
+ * outside 1..2^24, max_rows_per_frame outside 1..64, fps <= 0 or not finite. */
+int vbt_overlay_follow(vbt_overlay* o, const void* rows_dev, const int32_t* nrows_dev, int rows_cap, int max_frame, int max_rows_per_frame,
+                       double fps);
+/* Consume the rows appended since the last call: ONE launch that reads *nrows_dev itself, enqueue only, on `stream` - which must be
+ * ordered behind the launch that wrote the rows.  VBT_ERR_STATE: the handle is not in follow mode. */
+int vbt_overlay_follow_update(vbt_overlay* o, void* stream);
+/* Rows consumed so far and the VBT_OVERLAY_FOLLOW_* flags; one 8-byte copy on `stream`, which it synchronises */
+int vbt_overlay_follow_status(vbt_overlay* o, int32_t* rows_consumed, int32_t* flags, void* stream);
+/* In follow mode vbt_overlay_draw draws from the rows consumed so far, with a grid of (max_rows_per_frame x primitives, B): the host
+ * knows no per-frame counts and never asks for them; the workgroups of absent rows leave at once. */
+/* The pipeline's side of a one-pass export, for an overlay that follows one of the pipeline's clips: enqueue the tracker steps still
+ * held back (vbt_pipeline_drain), make `stream` wait for the most recent tracker launch, then vbt_overlay_follow_update and
+ * vbt_overlay_draw on `stream`.  Enqueue only.  The frames may be the ones the steps were given (drawn in place): the tracker launch
+ * waited for depends on their forward, whichever stream the tracker runs on. */
+int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
 
 /* ------------------------------------------------------------------ MJPEG export --------
  * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that

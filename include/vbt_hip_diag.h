@@ -96,7 +96,8 @@ int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, doub
 /* ------------------------------------------------------------------ tracking overlay ---------------------------------- */
 /* What the prepare kernel of vbt_overlay_set_rows made of every row, in row order: out[i] = frame, cx, cy, xmin, ymin, xmax, ymax,
  * trail length (points) - so that a failing picture can be told from failing geometry.  *n = the handle's rows; cap < *n is
- * VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
+ * VBT_ERR_CAPACITY with nothing copied.  One blocking copy.  In follow mode: the records of the rows consumed so far, in log order
+ * (*n = their number, read from the device first: it waits for the updates enqueued); a skipped row has trail length 0. */
 int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
 /* The table vbt_overlay_set_hud uploaded, read back from the device: out[i] = fs, fe, rom_cm, acv_cm, type, concentric phases among
  * phases 0..i - so that a failing panel pixel can be told from a wrong integer.  *P = the panel's phases (0 without a panel);

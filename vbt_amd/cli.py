@@ -2,7 +2,7 @@
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
-                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
+                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
       import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it;
@@ -30,6 +30,10 @@
       panel") - what the reference's figure shows (plot.py:112-232): the rep count, ROM and ACV of the last completed rep, a bar per
       recent rep and the phase timeline of the export id, exactly the phases `analyze` prints for the exported DataFrame.  The phases
       exist once the clip is analysed, so with --hud the frames are rendered after tracking, for every --concurrent.
+      --one_pass (with --video_dir): the export in the same pass as the tracking - each batch of frames is uploaded or decoded once,
+      detected, tracked, drawn from the tracker's row log on the device (include/vbt_hip.h, "Following a device row log") and written,
+      instead of a second pass over the clip after it.  The same files, byte for byte.  Not with --hud (the panel shows the analysed
+      clip) and not with --concurrent above 1.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
                               [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync]
                               [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
@@ -203,15 +207,25 @@ def _raw_size(pix_fmt, size):
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
 @click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
               help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
+@click.option("--one_pass", is_flag=True, default=False,
+              help="Draw and write each batch of frames right after it is tracked, from the tracker's row log on the GPU, instead of in a second pass "
+                   "over the clip (needs --video_dir; same files; not with --hud or --concurrent above 1).")
 @_hud_options
 def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality,
-          mjpeg_entropy, hud, plate_diameter, hud_scale, hud_pos):
+          mjpeg_entropy, one_pass, hud, plate_diameter, hud_scale, hud_pos):
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     fps_given = _fps_given()
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
+    if one_pass:
+        if video_dir is None:
+            raise click.UsageError("--one_pass is a way to write the exported frames: give --video_dir")
+        if hud:
+            raise click.UsageError("--one_pass cannot draw --hud: the rep panel shows the phases of the analysed clip, which exist only after its last frame")
+        if concurrent > 1:
+            raise click.UsageError("--one_pass works with --concurrent 1 only: clips tracked side by side are rendered as each one finishes")
     if concurrent > 1:
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
@@ -232,7 +246,8 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
         with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
             data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink, video_quality=video_quality)
+                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink, video_quality=video_quality,
+                                one_pass=one_pass)
         _video_done(video)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")

@@ -1,10 +1,14 @@
 // Tracking overlay on the device (gfx950): box, id label, marker and bar path of the tracked plates drawn into frames that are
-// already in device memory (include/vbt_hip.h, "tracking overlay"; reference track.py:28-62,201-224).  Three kernels:
+// already in device memory (include/vbt_hip.h, "tracking overlay"; reference track.py:28-62,201-224).  Four kernels:
 //   overlay_prepare_kernel, once per vbt_overlay_set_rows: one thread per row - frame number, the six pixel coordinates, trail length;
 //   overlay_draw_kernel, once per vbt_overlay_draw: grid (row slot x chunk, frame of the batch).  A frame's rows come from the dense
-//     index frame number -> rows (the host builds it while it validates the rows; it sizes the grid from it).  Chunk 0 of a row is its
+//     index frame number -> rows (the host builds it while it validates the rows; it sizes the grid from it; follow mode: from the
+//     links of overlay_follow_kernel, with a grid of as many row slots as a frame can hold).  Chunk 0 of a row is its
 //     box outline (a few thousand pixels), chunk 1 its marker and label, chunk 2 + j the 16 trail segments 16 j .. 16 j + 15, one per
 //     16-lane group: a segment is a few dozen candidate pixels, so a wavefront takes four of them and a workgroup sixteen.
+//   overlay_follow_kernel, once per vbt_overlay_follow_update (follow mode: the rows are a log in device memory that its writer
+//     extends): one wavefront takes the new rows 64 at a time - geometry, the previous row of the id, the 16th one before it, the
+//     frame's row list, the id table.  The draw kernel then finds a frame's rows and a row's trail through those links.
 //   overlay_hud_kernel, once more per vbt_overlay_draw when vbt_overlay_set_hud set a rep panel: grid (tile of the panel, frame of the
 //     batch), one thread per 2 x 2 pixel quad - the chroma sample and its four lumas have one owner, and so has every RGB24 byte.
 //     The panel is a gather in two colours: every pixel of its rectangle is tested against the contract and written once.
@@ -29,6 +33,8 @@ struct OverlayDrawArgs {
   const int64_t* ids;      // row i's id at ids[8 i] (the rows as uploaded)
   const int32_t* fstart;   // [fmax + 2]: rows of frame f are frow[fstart[f] .. fstart[f + 1])
   const int32_t* frow;     // [n] row numbers ordered by frame
+  const int32_t* link;     // follow mode (else NULL): [rows_cap][OV_LINK], and
+  const int32_t* findex;   //   [fmax + 1][2] newest row of the frame, its rows
   uint8_t* frames;
   size_t frame_bytes;
   int frame0, frame_step, fmax, chunks;
@@ -68,9 +74,16 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_draw_kernel(OverlayDrawArg
   const long f = (long)A.frame0 + (long)blockIdx.y * A.frame_step;
   if (f < 1 || f > A.fmax) return;
   const int slot = blockIdx.x / A.chunks, chunk = blockIdx.x % A.chunks;
-  const int r0 = A.fstart[f], r1 = A.fstart[f + 1];
-  if (slot >= r1 - r0) return;
-  const int row = A.frow[r0 + slot];
+  int row;
+  if (A.link) {
+    if (slot >= A.findex[2 * (size_t)f + 1]) return;
+    row = ov_follow_frame_row(A.findex, A.link, f, slot);
+    if (row < 0) return;
+  } else {
+    const int r0 = A.fstart[f], r1 = A.fstart[f + 1];
+    if (slot >= r1 - r0) return;
+    row = A.frow[r0 + slot];
+  }
   const int32_t* g = A.geom + (size_t)row * OV_GEOM;
   Painter P{A.frames + (size_t)blockIdx.y * A.frame_bytes, A.H, A.W, A.fmt, A.c0, A.c1, A.c2};
   const int lane = threadIdx.x;
@@ -90,8 +103,96 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_draw_kernel(OverlayDrawArg
     const int nseg = g[OV_TRAIL] - 1;
     const int seg = (chunk - 2) * OV_SEGS_PER_BLOCK + lane / OV_SEG_LANES;
     if (seg >= nseg) return;
+    if (A.link) {                                                 // segments counted from the newest: at most chunks - 3 skip links, then 15 rows back
+      int older, newer;
+      ov_follow_segment(A.link, row, seg, &older, &newer);
+      if (older < 0) return;
+      const int32_t *q0 = A.geom + (size_t)older * OV_GEOM, *q1 = A.geom + (size_t)newer * OV_GEOM;
+      ov_draw_segment(P, q0[OV_CX], q0[OV_CY], q1[OV_CX], q1[OV_CY], A.t, lane % OV_SEG_LANES, OV_SEG_LANES);
+      return;
+    }
     const int32_t* p0 = A.geom + (size_t)(row - nseg + seg) * OV_GEOM;
     ov_draw_segment(P, p0[OV_CX], p0[OV_CY], p0[OV_GEOM + OV_CX], p0[OV_GEOM + OV_CY], A.t, lane % OV_SEG_LANES, OV_SEG_LANES);
+  }
+}
+
+// Follow mode: rows [cursor, min(*nrows_dev, rows_cap)) of the log, 64 at a time, lane j taking row base + j.  The rows of a group
+// are taken as if every one that can stand on its own were accepted: its place among the group's rows of its id and of its frame
+// comes from a walk over the lanes, what came before the group from the tables.  If under that assumption no row is out of order and
+// no frame overfull, the assumption holds (row by row, each sees exactly the state assumed) and the group is stored side by side.
+// Otherwise lane 0 takes the group row by row through ov_follow_row - the statement both paths implement.  The fences order one
+// lane's stores before another lane's loads of them: within a group (new ids, links) and from one group to the next.
+__global__ __launch_bounds__(64) void overlay_follow_kernel(OvFollow F, const int32_t* __restrict__ nrows_dev) {
+  const int lane = threadIdx.x;
+  const int cur = F.state[OV_STATE_CURSOR];
+  int n = *nrows_dev;
+  n = n > F.rows_cap ? F.rows_cap : n;
+  if (n < cur) {
+    if (lane == 0) F.state[OV_STATE_FLAGS] |= VBT_OVERLAY_FOLLOW_REWOUND;
+    return;
+  }
+  int flags = 0;
+  for (int base = cur; base < n; base += 64) {
+    const int i = base + lane;
+    const bool in = i < n;
+    OverlayRow r{};
+    int32_t g[OV_GEOM];
+    if (in) r = F.rows[i];
+    const int own = in ? ov_follow_static(r, F.fps, F.H, F.W, F.max_frame, g) : 0;
+    const bool ok = in && own == 0;
+    const long long id = ok ? (long long)r.id : -1;
+    const int f = ok ? g[OV_FRAME] : -1;
+    int pj = -1, rank = 0, qj = -1, frank = 0;                    // the lane before this one with its id / its frame, and how many there are
+    bool later_id = false, later_f = false;
+    for (int j = 0; j < 64; j++) {
+      const long long idj = __shfl(id, j);
+      const int fj = __shfl(f, j);
+      if (ok && idj == id) { if (j < lane) { pj = j; rank++; } else if (j > lane) later_id = true; }
+      if (ok && fj == f) { if (j < lane) { qj = j; frank++; } else if (j > lane) later_f = true; }
+    }
+    int slot = ok ? ov_follow_find(F.table, F.table_mask, r.id, false) : -1;
+    unsigned long long need = __ballot(ok && slot < 0 && pj < 0);   // new ids, one lane each: they take their slots one after the other
+    while (need) {
+      const int j = __ffsll((long long)need) - 1;
+      need &= need - 1;
+      if (lane == j) slot = ov_follow_find(F.table, F.table_mask, r.id, true);
+      __threadfence();
+    }
+    if (ok && slot < 0) slot = ov_follow_find(F.table, F.table_mask, r.id, false);
+    const bool lost = ok && slot < 0;                             // (never: the table is larger than the log)
+    const int tprev = ok && !lost ? F.table[slot].last : -1;
+    const int prev = pj >= 0 ? base + pj : tprev;
+    double ptime = __shfl(r.time, pj >= 0 ? pj : 0);
+    if (pj < 0 && tprev >= 0) ptime = F.rows[tprev].time;
+    const int cnt0 = ok ? F.findex[2 * (size_t)f + 1] : 0;
+    const int head0 = ok ? F.findex[2 * (size_t)f] : -1;
+    const bool order = ok && prev >= 0 && r.time < ptime, full = ok && cnt0 + frank >= F.max_rows_per_frame;
+    if (__ballot(lost || order || full)) {
+      if (lane == 0) {
+        const int end = base + 64 < n ? base + 64 : n;
+        for (int k = base; k < end; k++) flags |= ov_follow_row(F, k);
+      }
+      __threadfence();
+      continue;
+    }
+    flags |= own;
+    const int depth = ok ? (tprev >= 0 ? F.link[(size_t)tprev * OV_LINK + OV_LINK_DEPTH] : 0) + rank + 1 : 0;
+    if (in) {
+      g[OV_TRAIL] = depth < F.trail ? depth : F.trail;
+      ov_follow_store(F, i, g, ok ? prev : -1, -1, depth, !ok ? -1 : (qj >= 0 ? base + qj : (cnt0 > 0 ? head0 : -1)));
+    }
+    if (ok && !later_id) F.table[slot].last = i;
+    if (ok && !later_f) { F.findex[2 * (size_t)f] = i; F.findex[2 * (size_t)f + 1] = cnt0 + frank + 1; }
+    __threadfence();
+    if (ok && depth > OV_SKIP_HOPS) F.link[(size_t)i * OV_LINK + OV_LINK_SKIP] = ov_follow_skip(F.link, prev, depth);
+    __threadfence();
+  }
+  int all = 0;
+  for (int bit = 1; bit < VBT_OVERLAY_FOLLOW_REWOUND; bit <<= 1)
+    if (__ballot(flags & bit)) all |= bit;
+  if (lane == 0) {
+    F.state[OV_STATE_CURSOR] = n;
+    if (all) F.state[OV_STATE_FLAGS] |= all;
   }
 }
 
@@ -161,6 +262,10 @@ struct vbt_overlay {
   const int32_t *d_frow = nullptr, *d_fstart = nullptr;
   int32_t* d_geom = nullptr;
   std::vector<int32_t> fstart;           // the host's copy of the index: sizes the grid of a draw
+  bool follow = false;                   // follow mode (vbt_overlay_follow): the rows are F.rows, everything else of F in follow_blob
+  OvFollow F{};
+  const int32_t* nrows_dev = nullptr;
+  uint8_t* follow_blob = nullptr;        // geom | link | table | findex | state in one allocation
   bool hud = false;                      // a rep panel is set (vbt_overlay_set_hud)
   vbt_overlay_hud_params hud_prm{};
   uint8_t b0 = 0, b1 = 0, b2 = 0;        // the panel's background in the frames' format
@@ -239,13 +344,14 @@ int check_hud(const vbt_overlay_hud_params* prm, const double* ph, int P, double
 void overlay_launch_rows(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, int MAX_Y, hipStream_t stream) {
   OverlayDrawArgs A{};
   A.geom = o->d_geom; A.ids = (const int64_t*)o->d_rows; A.fstart = o->d_fstart; A.frow = o->d_frow;
+  if (o->follow) { A.geom = o->F.geom; A.ids = (const int64_t*)o->F.rows; A.link = o->F.link; A.findex = o->F.findex; }
   A.frame_bytes = o->frame_bytes; A.frame_step = frame_step; A.fmax = o->fmax; A.chunks = o->chunks;
   A.H = o->H; A.W = o->W; A.fmt = o->fmt; A.t = o->prm.thickness; A.R = o->prm.radius; A.s = o->prm.label_scale;
   A.label = o->prm.label; A.box = o->prm.box; A.c0 = o->c0; A.c1 = o->c1; A.c2 = o->c2;
   for (int b0 = 0; b0 < B; b0 += MAX_Y) {
     const int nb = std::min(MAX_Y, B - b0);
-    int most = 0;                                                 // rows of the fullest frame of this launch
-    for (int i = 0; i < nb; i++) {
+    int most = o->follow ? o->F.max_rows_per_frame : 0;           // rows of the fullest frame of this launch (follow mode: as many as a frame can hold)
+    for (int i = 0; i < nb && !o->follow; i++) {
       const long f = (long)frame0 + (long)(b0 + i) * frame_step;
       if (f > o->fmax) break;
       most = std::max(most, o->fstart[f + 1] - o->fstart[f]);
@@ -266,6 +372,8 @@ void overlay_free_rows(vbt_overlay* o) {
   if (o->blob) (void)hipFree(o->blob);   // (waits for the draws still reading it)
   o->blob = nullptr; o->d_rows = nullptr; o->d_frow = o->d_fstart = nullptr; o->d_geom = nullptr;
   o->n = 0; o->fmax = 0; o->fstart.clear();
+  if (o->follow_blob) (void)hipFree(o->follow_blob);
+  o->follow_blob = nullptr; o->follow = false; o->F = OvFollow{}; o->nrows_dev = nullptr;
 }
 
 }  // namespace
@@ -368,10 +476,10 @@ int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int
     set_error("vbt_overlay_draw: bad argument (B >= 0, frame0 >= 1, frame_step >= 1, frame numbers inside int32)");
     return VBT_ERR_ARG;
   }
-  if (B == 0 || (o->n == 0 && !o->hud)) return VBT_OK;
+  if (B == 0 || (o->n == 0 && !o->follow && !o->hud)) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(o->device));
   constexpr int MAX_Y = 32768;                                    // frames per launch (grid.y)
-  if (o->n > 0) overlay_launch_rows(o, frames_dev, B, frame0, frame_step, MAX_Y, (hipStream_t)stream);
+  if (o->n > 0 || o->follow) overlay_launch_rows(o, frames_dev, B, frame0, frame_step, MAX_Y, (hipStream_t)stream);
   if (o->hud) {                                                   // after the rows, on the same stream: the panel wins
     const vbt_overlay_hud_params& hp = o->hud_prm;
     OverlayHudArgs G{};
@@ -388,6 +496,63 @@ int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int
     }
   }
   VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+int vbt_overlay_follow(vbt_overlay* o, const void* rows_dev, const int32_t* nrows_dev, int rows_cap, int max_frame, int max_rows_per_frame,
+                       double fps) {
+  if (!rows_dev || !nrows_dev) { set_error("vbt_overlay_follow: NULL argument (rows %p, row count %p)", rows_dev, (const void*)nrows_dev); return VBT_ERR_ARG; }
+  if (rows_cap < 1) { set_error("vbt_overlay_follow: rows_cap %d < 1", rows_cap); return VBT_ERR_ARG; }
+  if (max_frame < 1 || max_frame > OV_MAX_FRAME) { set_error("vbt_overlay_follow: max_frame %d outside 1..%d", max_frame, OV_MAX_FRAME); return VBT_ERR_ARG; }
+  if (max_rows_per_frame < 1 || max_rows_per_frame > 64) { set_error("vbt_overlay_follow: max_rows_per_frame %d outside 1..64", max_rows_per_frame); return VBT_ERR_ARG; }
+  if (!(fps > 0) || !std::isfinite(fps)) { set_error("vbt_overlay_follow: fps must be positive and finite, got %g", fps); return VBT_ERR_ARG; }
+  if (!o) { set_error("vbt_overlay_follow: handle is NULL"); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  overlay_free_rows(o);
+  size_t slots = 64;
+  while (slots < 2 * (size_t)rows_cap) slots <<= 1;
+  const size_t geom_b = (size_t)rows_cap * OV_GEOM * 4, link_b = (size_t)rows_cap * OV_LINK * 4, table_b = slots * sizeof(OvIdSlot);
+  const size_t findex_b = ((size_t)max_frame + 1) * 8, state_b = OV_STATE * 4;
+  uint8_t* blob = nullptr;
+  VBT_HIP_CHECK(hipMalloc((void**)&blob, geom_b + link_b + table_b + findex_b + state_b));
+  uint8_t* table = blob + geom_b + link_b;
+  hipError_t e = hipMemsetAsync(blob, 0xff, geom_b + link_b + table_b, nullptr);   // every slot free (id -1), every link "none"
+  if (e == hipSuccess) e = hipMemsetAsync(table + table_b, 0, findex_b + state_b, nullptr);
+  const hipError_t es = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    (void)hipFree(blob);
+    set_error("vbt_overlay_follow failed: %s", hipGetErrorString(e));
+    return VBT_ERR_HIP;
+  }
+  OvFollow& F = o->F;
+  F.rows = (const OverlayRow*)rows_dev;
+  F.geom = (int32_t*)blob; F.link = (int32_t*)(blob + geom_b); F.table = (OvIdSlot*)table;
+  F.findex = (int32_t*)(table + table_b); F.state = (int32_t*)(table + table_b + findex_b);
+  F.fps = fps; F.rows_cap = rows_cap; F.max_frame = max_frame; F.max_rows_per_frame = max_rows_per_frame; F.table_mask = (int)(slots - 1);
+  F.H = o->H; F.W = o->W; F.trail = o->prm.trail;
+  o->follow_blob = blob; o->nrows_dev = nrows_dev; o->follow = true; o->fmax = max_frame;
+  return VBT_OK;
+}
+
+int vbt_overlay_follow_update(vbt_overlay* o, void* stream) {
+  if (!o) { set_error("vbt_overlay_follow_update: handle is NULL"); return VBT_ERR_ARG; }
+  if (!o->follow) { set_error("vbt_overlay_follow_update: the handle follows no row log (vbt_overlay_follow)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  overlay_follow_kernel<<<1, 64, 0, (hipStream_t)stream>>>(o->F, o->nrows_dev);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+int vbt_overlay_follow_status(vbt_overlay* o, int32_t* rows_consumed, int32_t* flags, void* stream) {
+  if (!o || !rows_consumed || !flags) { set_error("vbt_overlay_follow_status: NULL argument"); return VBT_ERR_ARG; }
+  if (!o->follow) { set_error("vbt_overlay_follow_status: the handle follows no row log (vbt_overlay_follow)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  int32_t st[OV_STATE];
+  VBT_HIP_CHECK(hipMemcpyAsync(st, o->F.state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  *rows_consumed = st[OV_STATE_CURSOR];
+  *flags = st[OV_STATE_FLAGS];
   return VBT_OK;
 }
 
@@ -450,6 +615,15 @@ int vbt_overlay_hud_table(vbt_overlay* o, int32_t* out, int cap, int* P) {
 
 int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n) {
   if (!o || !n || cap < 0 || (cap > 0 && !out)) { set_error("vbt_overlay_geometry: bad argument"); return VBT_ERR_ARG; }
+  if (o->follow) {
+    VBT_HIP_CHECK(hipSetDevice(o->device));
+    int32_t st[OV_STATE];
+    VBT_HIP_CHECK(hipMemcpy(st, o->F.state, sizeof(st), hipMemcpyDeviceToHost));
+    *n = st[OV_STATE_CURSOR];
+    if (cap < *n) { set_error("vbt_overlay_geometry: %d rows, room for %d", *n, cap); return VBT_ERR_CAPACITY; }
+    if (*n > 0) VBT_HIP_CHECK(hipMemcpy(out, o->F.geom, (size_t)*n * OV_GEOM * 4, hipMemcpyDeviceToHost));
+    return VBT_OK;
+  }
   *n = o->n;
   if (cap < o->n) { set_error("vbt_overlay_geometry: %d rows, room for %d", o->n, cap); return VBT_ERR_CAPACITY; }
   if (o->n == 0) return VBT_OK;

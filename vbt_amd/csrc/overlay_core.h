@@ -3,8 +3,15 @@
 // Every walk enumerates a candidate set that contains the primitive's covered pixels inside the frame and applies the contract's
 // test to each candidate; Painter::put is the only store and checks the frame's bounds itself.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#else   // a host compiler (tests/fuzz/overlay_follow_check.cc): the same statements, no HIP header needed
+#include <math.h>
+#include <stddef.h>
+#define __host__
+#define __device__
+#endif
 
 #include "../../include/vbt_hip.h"
 
@@ -173,6 +180,120 @@ __host__ __device__ inline void ov_draw_segment(const Painter& P, int x0, int y0
       if ((unsigned)n < (unsigned)Wn && ov_segment_covers(px, py, x0, y0, x1, y1, t)) P.put(px, py);
     }
   }
+}
+
+// ---- following a device row log (include/vbt_hip.h, "Following a device row log") ----
+// Per log row: its geometry record and a link record; per frame number: the newest accepted row of the frame and their count (the
+// frame's rows hang on OV_LINK_FNEXT, so they need not be neighbours in the log); per id: the newest accepted row (OvIdSlot, open
+// addressing).  OV_TRAIL = 0 marks a skipped row.
+enum { OV_LINK_PREV = 0, OV_LINK_SKIP, OV_LINK_DEPTH, OV_LINK_FNEXT, OV_LINK = 4 };   // previous row of the id, its 16th ancestor, rows of the id so far, next row of the frame
+enum { OV_SKIP_HOPS = 16 };
+enum { OV_STATE_CURSOR = 0, OV_STATE_FLAGS = 1, OV_STATE = 4 };
+
+struct OvIdSlot {
+  int64_t id;      // -1: free
+  int32_t last;    // log index of the id's newest accepted row, -1: none yet
+  int32_t pad;
+};
+
+struct OvFollow {
+  const OverlayRow* rows;   // the followed log (borrowed)
+  int32_t* geom;            // [rows_cap][OV_GEOM]
+  int32_t* link;            // [rows_cap][OV_LINK]
+  int32_t* findex;          // [max_frame + 1][2]: newest accepted row, accepted rows
+  OvIdSlot* table;          // [table_mask + 1], a power of two >= 2 rows_cap: it never fills
+  int32_t* state;           // [OV_STATE]
+  double fps;
+  int rows_cap, max_frame, max_rows_per_frame, table_mask, H, W, trail;
+};
+
+__host__ __device__ inline bool ov_finite(double v) { return __builtin_isfinite(v); }
+
+// What a row shows on its own: g[OV_FRAME .. OV_YMAX] (zeros for a row set_rows would refuse: its doubles have no integers) and 0,
+// VBT_OVERLAY_FOLLOW_BAD_ROW or _FRAME_RANGE
+__host__ __device__ inline int ov_follow_static(const OverlayRow& r, double fps, int H, int W, int max_frame, int32_t* g) {
+  for (int k = 0; k < OV_GEOM; k++) g[k] = 0;
+  const bool fin = ov_finite(r.time) && ov_finite(r.x) && ov_finite(r.y) && ov_finite(r.dx) && ov_finite(r.dy) && ov_finite(r.h) && ov_finite(r.w);
+  if (!fin || r.id < 0 || r.w < 0 || r.h < 0) return VBT_OVERLAY_FOLLOW_BAD_ROW;
+  ov_row_geometry(r, fps, H, W, g);
+  return g[OV_FRAME] < 1 || g[OV_FRAME] > max_frame ? VBT_OVERLAY_FOLLOW_FRAME_RANGE : 0;
+}
+
+// slot of `id`, taking a free one for it if `insert`; -1: not there (or, never, a full table)
+__host__ __device__ inline int ov_follow_find(OvIdSlot* table, int mask, int64_t id, bool insert) {
+  unsigned h = (unsigned)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> 32) & (unsigned)mask;
+  for (int probe = 0; probe <= mask; probe++, h = (h + 1) & (unsigned)mask) {
+    if (table[h].id == id) return (int)h;
+    if (table[h].id < 0) {
+      if (!insert) return -1;
+      table[h].last = -1;
+      table[h].id = id;
+      return (int)h;
+    }
+  }
+  return -1;
+}
+
+// 16th ancestor of a row with `depth` rows of its id up to itself, whose previous one is `prev`; the links of all older rows are final
+__host__ __device__ inline int ov_follow_skip(const int32_t* link, int prev, int depth) {
+  if (depth <= OV_SKIP_HOPS) return -1;
+  int a = prev;
+  for (int k = 1; k < OV_SKIP_HOPS && a >= 0; k++) a = link[(size_t)a * OV_LINK + OV_LINK_PREV];
+  return a;
+}
+
+__host__ __device__ inline void ov_follow_store(const OvFollow& F, int i, const int32_t* g, int prev, int skip, int depth, int fnext) {
+  for (int k = 0; k < OV_GEOM; k++) F.geom[(size_t)i * OV_GEOM + k] = g[k];
+  int32_t* l = F.link + (size_t)i * OV_LINK;
+  l[OV_LINK_PREV] = prev; l[OV_LINK_SKIP] = skip; l[OV_LINK_DEPTH] = depth; l[OV_LINK_FNEXT] = fnext;
+}
+
+// The step of log row i, every earlier row done: accept or skip, geometry, links, frame index, id table.  Returns the row's flag (0:
+// accepted).  The follow kernel takes 64 rows at a time through the same statements and falls back on this one where a row's fate
+// depends on another row of its group; a host loop over it is the statement of follow mode.
+__host__ __device__ inline int ov_follow_row(const OvFollow& F, int i) {
+  const OverlayRow r = F.rows[i];
+  int32_t g[OV_GEOM];
+  int flag = ov_follow_static(r, F.fps, F.H, F.W, F.max_frame, g);
+  int slot = -1, prev = -1, cnt = 0;
+  if (!flag) {
+    slot = ov_follow_find(F.table, F.table_mask, r.id, true);
+    if (slot < 0) flag = VBT_OVERLAY_FOLLOW_BAD_ROW;
+  }
+  if (!flag) {
+    prev = F.table[slot].last;
+    cnt = F.findex[2 * (size_t)g[OV_FRAME] + 1];
+    if (prev >= 0 && r.time < F.rows[prev].time) flag = VBT_OVERLAY_FOLLOW_ORDER;
+    else if (cnt >= F.max_rows_per_frame) flag = VBT_OVERLAY_FOLLOW_FRAME_FULL;
+  }
+  if (flag) {
+    ov_follow_store(F, i, g, -1, -1, 0, -1);
+    return flag;
+  }
+  const int depth = prev >= 0 ? F.link[(size_t)prev * OV_LINK + OV_LINK_DEPTH] + 1 : 1;
+  g[OV_TRAIL] = depth < F.trail ? depth : F.trail;
+  int32_t* fi = F.findex + 2 * (size_t)g[OV_FRAME];
+  ov_follow_store(F, i, g, prev, ov_follow_skip(F.link, prev, depth), depth, cnt > 0 ? fi[0] : -1);
+  fi[0] = i; fi[1] = cnt + 1;
+  F.table[slot].last = i;
+  return 0;
+}
+
+// The trail segment `seg` (0 = the newest) of `row`, seg < g[OV_TRAIL] - 1: end point rows (older, newer), by seg / 16 skip links and
+// seg % 16 previous-row links.  A link that is not there (-1; never, for a segment of the row's trail) ends the walk: *older = -1.
+__host__ __device__ inline void ov_follow_segment(const int32_t* link, int row, int seg, int* older, int* newer) {
+  int a = row;
+  for (int k = 0; k < seg / OV_SKIP_HOPS && a >= 0; k++) a = link[(size_t)a * OV_LINK + OV_LINK_SKIP];
+  for (int k = 0; k < seg % OV_SKIP_HOPS && a >= 0; k++) a = link[(size_t)a * OV_LINK + OV_LINK_PREV];
+  *newer = a;
+  *older = a >= 0 ? link[(size_t)a * OV_LINK + OV_LINK_PREV] : -1;
+}
+
+// row number `slot` (0 = the newest) of a frame with more than `slot` accepted rows (-1 if the list ends before it: never)
+__host__ __device__ inline int ov_follow_frame_row(const int32_t* findex, const int32_t* link, int64_t f, int slot) {
+  int row = findex[2 * (size_t)f];
+  for (int k = 0; k < slot && row >= 0; k++) row = link[(size_t)row * OV_LINK + OV_LINK_FNEXT];
+  return row;
 }
 
 // ---- rep panel (include/vbt_hip.h, "Rep panel"): a gather - every pixel of the panel rectangle is tested and written once ----

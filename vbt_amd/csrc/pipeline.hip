@@ -1135,6 +1135,18 @@ int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips
   return vbt_tracker_live_poll(p->trk, flush_view, clips, phases6, cap, (void*)p->trk_stream);
 }
 
+// One-pass export.  drain() hands every tracker step still held back to its stream - the block of deferred / grouped steps, the
+// own-stream lag - so ev_trk[last_trk] then stands behind every step enqueued so far in all three tracker placements, and each of
+// those launches is behind the forward whose preprocess read the frames: drawing into them on `stream` after the event is safe.
+int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream) {
+  if (!p || !o) { set_error("vbt_pipeline_overlay_draw: NULL %s", p ? "overlay" : "pipeline"); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, p->ev_trk[p->last_trk], 0));
+  PL_CHECK(vbt_overlay_follow_update(o, stream));
+  return vbt_overlay_draw(o, frames_dev, B, frame0, frame_step, stream);
+}
+
 int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
   if (!p || !out) { set_error("vbt_pipeline_get_info: NULL argument"); return VBT_ERR_ARG; }
   memset(out, 0, sizeof(*out));

@@ -238,6 +238,16 @@ int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int3
 // DataFrame rows of EVERY clip (all ids, emission order) in one strided copy: rows_host = [n_clips][cap] records of
 // 64 bytes {int64 id; double time, x, y, dx, dy, norm_plate_height, norm_plate_width} (reference track.py:227-234).
 // counts[c] = rows of clip c.  rows_host may be pinned (then the copy is one DMA) or pageable.
+int vbt_tracker_rows_dev(vbt_tracker* t, int clip, const void** rows_dev, const int32_t** nrows_dev, int* rows_cap) {
+  if (!t || !rows_dev || !nrows_dev || !rows_cap) { set_error("vbt_tracker_rows_dev: NULL argument"); return VBT_ERR_ARG; }
+  if (clip < 0 || clip >= t->n_clips) { set_error("vbt_tracker_rows_dev: clip %d outside the %d clips", clip, t->n_clips); return VBT_ERR_ARG; }
+  static_assert(sizeof(Row) == 64 && sizeof(int) == sizeof(int32_t), "row record and its counter");
+  *rows_dev = t->rows.get() + (size_t)clip * t->rows_cap;
+  *nrows_dev = (const int32_t*)((const char*)(t->states.get() + clip) + offsetof(ClipState, nrows));
+  *rows_cap = t->rows_cap;
+  return VBT_OK;
+}
+
 int vbt_tracker_rows_all(vbt_tracker* t, int32_t* counts, void* rows_host, int cap, void* stream) {
   if (!t || !counts || !rows_host || cap < 1) { set_error("vbt_tracker_rows_all: bad argument"); return VBT_ERR_ARG; }
   static_assert(sizeof(Row) == 64, "row record");

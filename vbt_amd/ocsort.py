@@ -33,6 +33,13 @@ class MultiClipTracker:
         p = _params(det_thresh, max_age, min_hits, iou_threshold, delta_t, asso_func, inertia)
         _lib.check(_lib.lib().vbt_tracker_create(self.n_clips, self.rows_cap, ctypes.byref(p), device, ctypes.byref(self._h)))
 
+    def rows_dev(self, clip):
+        """(rows pointer, row counter pointer, rows_cap) of the clip's row log in device memory (vbt_tracker_rows_dev): what
+        overlay.Overlay.follow takes.  Borrowed: valid while the tracker lives."""
+        rows, nrows, cap = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int()
+        _lib.check(_lib.lib().vbt_tracker_rows_dev(self._h, int(clip), ctypes.byref(rows), ctypes.byref(nrows), ctypes.byref(cap)))
+        return rows.value, nrows.value, cap.value
+
     @classmethod
     def _borrowed(cls, handle, n_clips, rows_cap, owner):
         """A view of the tracker owned by a vbt_pipeline (never destroyed from here; `owner` is kept alive)."""

@@ -16,6 +16,7 @@ from .rawvideo import frame_shape, pix_fmt_code, source_hw
 
 COLUMNS = ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
 HUD_PARAMS = ("x", "y", "scale", "full_scale_cm", "bg")
+FOLLOW_FLAGS = {1: "BAD_ROW", 2: "ORDER", 4: "FRAME_RANGE", 8: "FRAME_FULL", 16: "REWOUND"}     # VBT_OVERLAY_FOLLOW_*
 COLORS = [(252, 3, 115), (255, 255, 255)]          # COLORS of reference track.py:23 (BGR there) as RGB; the reference draws with [1]
 
 
@@ -68,6 +69,23 @@ class Overlay:
         _lib.check(_lib.lib().vbt_overlay_set_rows(self._h, rows.ctypes.data, len(rows), float(fps), stream))
         self.n = len(rows)
 
+    def follow(self, rows_ptr, nrows_ptr, rows_cap, max_frame, max_rows_per_frame, fps):
+        """Follow mode (include/vbt_hip.h, "Following a device row log"): draw from a row log in device memory - rows_ptr its 64-byte
+        records in emission order, nrows_ptr the device int32 that counts them (MultiClipTracker.rows_dev gives a clip's) - instead of
+        rows from the host.  Replaces the handle's rows; set_rows switches back."""
+        _lib.check(_lib.lib().vbt_overlay_follow(self._h, int(rows_ptr), int(nrows_ptr), int(rows_cap), int(max_frame), int(max_rows_per_frame), float(fps)))
+        self.n = int(rows_cap)
+
+    def follow_update(self, stream=None):
+        """consume the rows the log gained since the last call: one launch on `stream`, enqueue only"""
+        _lib.check(_lib.lib().vbt_overlay_follow_update(self._h, stream))
+
+    def follow_status(self, stream=None):
+        """(rows consumed, VBT_OVERLAY_FOLLOW_* flags) - synchronises `stream`"""
+        n, flags = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.lib().vbt_overlay_follow_status(self._h, ctypes.byref(n), ctypes.byref(flags), stream))
+        return n.value, flags.value
+
     def draw(self, frames_ptr, B, frame0, frame_step=1, stream=None):
         """B frames at device pointer `frames_ptr`, frame i = frame number frame0 + i * frame_step; in place, enqueue only"""
         _lib.check(_lib.lib().vbt_overlay_draw(self._h, int(frames_ptr), int(B), int(frame0), int(frame_step), stream))
@@ -111,6 +129,10 @@ class Overlay:
         n = ctypes.c_int()
         _lib.check(_lib.lib().vbt_overlay_geometry(self._h, out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value]
+
+
+def follow_flag_names(flags):
+    return [name for bit, name in FOLLOW_FLAGS.items() if flags & bit]
 
 
 def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, hud=None, hud_params=None,

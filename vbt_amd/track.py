@@ -65,7 +65,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None, video_sink=None, video_quality=85):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -77,7 +77,14 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     on the GPU.  src_hw=(H, W) is then optional (the shape gives it).
     video_out: optional uint8 array [T // frame_stride, ...] with the frames' layout (e.g. a numpy.lib.format.open_memmap) that receives
     every kept frame with the tracked boxes, ids and bar paths drawn (overlay.render; the reference's `--video_dir`, track.py:241-242).
-    video_sink: optional mjpeg.AviWriter that receives the same frames encoded as JPEG on the device at video_quality."""
+    video_sink: optional mjpeg.AviWriter that receives the same frames encoded as JPEG on the device at video_quality.
+    one_pass (with video_out or video_sink): the export in the same pass as the tracking instead of a second pass over the clip after
+    it - each batch of kept frames is uploaded (or decoded) once into a device buffer, detected and tracked from there, drawn in place
+    from the tracker's row log on the device (Overlay.follow; the rows never visit the host) and encoded or copied back.  The same
+    bytes and the same rows as without it.  (The rep panel of overlay.render needs the analysed clip: it has no one-pass form.)"""
+    if one_pass and (video_out is not None or video_sink is not None):
+        return _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw,
+                             export=(video_out, video_sink, video_quality))
     data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw)
     if video_out is not None:
         from .overlay import render
@@ -88,7 +95,8 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return data
 
 
-def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw):
+def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None):
+    """export: None, or (video_out, video_sink, video_quality) of a one-pass export"""
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
     if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
@@ -103,25 +111,59 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
     src_hw = None if (H, W) == (size, size) and not is_yuv(pix_fmt) else (H, W)
     if live is not None:
         pipe.enable_live()
-    elif isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
+    elif export is None and isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
         return pipe.track_clip(frames, frame_stride=stride, src_hw=src_hw)      # vbt_track_clip: the whole loop inside the library
-    # any other sequence (or live analysis): chunk by chunk through contiguous host copies
+    # any other sequence (or live analysis, or a one-pass export): chunk by chunk through contiguous host copies
     idx_all = np.arange(stride - 1, T, stride)
     dev = None
-    if hasattr(frames, "decode_into"):
+    decoded = hasattr(frames, "decode_into")
+    if decoded or export is not None:
         # a compressed source (mjpeg.AviClip): only the kept frames are decoded, on the device, straight into one of two device buffers
-        # that step_runs takes by pointer; nothing but compressed bytes crosses the bus
-        if is_yuv(pix_fmt):
+        # that step_runs takes by pointer; nothing but compressed bytes crosses the bus.  A one-pass export puts every source's batch
+        # there (one copy of the host chunk): the frames the detector reads are the frames that are drawn and written.
+        if decoded and is_yuv(pix_fmt):
             raise ValueError("track_frames: a decoded source gives rgb24 frames")
         from .mem import DeviceBuffer
-        dev = [DeviceBuffer(F * H * W * 3, device) for _ in range(2)]
+        shape = frame_shape(pix_fmt, H, W)
+        fb = int(np.prod(shape))
+        dev = [DeviceBuffer(F * fb, device) for _ in range(2)]
+    ov = enc = host = None
+    if export is not None:
+        from .overlay import Overlay, follow_flag_names
+        video_out, video_sink, video_quality = export
+        if video_out is not None and (tuple(video_out.shape) != (kept,) + shape or video_out.dtype != np.uint8):
+            raise ValueError(f"track_frames: video_out must be uint8 {(kept,) + shape}, got {video_out.dtype} {tuple(video_out.shape)}")
+        ov = Overlay(H, W, pix_fmt, device=device)
+        ov.follow(*pipe.tracker.rows_dev(0), max_frame=max(kept * stride, 1), max_rows_per_frame=25, fps=fps)   # (a frame has at most 25 detections)
+        if video_sink is not None and kept:
+            from .mjpeg import Encoder
+            enc = Encoder(H, W, pix_fmt, quality=video_quality, max_batch=F, device=device)
+        if video_out is not None:
+            host = np.empty((F,) + shape, np.uint8)
+    L = _lib.lib()
     for i0 in range(0, len(idx_all), F):
         idx = idx_all[i0:i0 + F]
         if dev is not None:
+            # a buffer is written again two batches later: its forwards are waited for here, and a one-pass export has read its drawn
+            # frames back by then (Encoder.read and the copy into video_out both synchronise)
             buf = dev[(i0 // F) % 2]
             pipe.join_detectors(0)                                       # the forwards that still read the buffers come first
-            frames.decode_into(idx, buf.ptr, 0)
+            if decoded:
+                frames.decode_into(idx, buf.ptr, 0)
+            else:
+                chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
+                _lib.check(L.vbt_memcpy(buf.ptr, chunk.ctypes.data, chunk.nbytes, 0))
             pipe.step_runs(buf.ptr, [(0, 0, len(idx), int(idx[0]) + 1, stride)], stream=0, src_hw=src_hw)
+            if ov is not None:
+                pipe.overlay_draw(ov, buf.ptr, len(idx), int(idx[0]) + 1, stride, stream=0)
+                if enc is not None:
+                    enc.encode(buf.ptr, len(idx))
+                    for jpeg in enc.read():
+                        video_sink.write(jpeg)
+                if host is not None:
+                    _lib.check(L.vbt_stream_synchronize(None))
+                    _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr, len(idx) * fb, 1))
+                    video_out[i0:i0 + len(idx)] = host[:len(idx)]
         else:
             chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
             pipe.step_runs(chunk, [(0, 0, len(idx), int(idx[0]) + 1, stride)], src_hw=src_hw)
@@ -129,6 +171,11 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
             live(pipe.live()[0], False)
     if live is not None:
         live(pipe.live(flush_view=True)[0], True)
+    if ov is not None:
+        _, flags = ov.follow_status(0)
+        if flags:
+            raise RuntimeError("track_frames: the one-pass export skipped rows of the tracker's log (VBT_OVERLAY_FOLLOW_" +
+                               ", ".join(follow_flag_names(flags)) + "): the exported frames are not those of the two-pass export")
     pipe.finish()
     return pipe.rows(0)
 
@@ -536,6 +583,12 @@ class Pipeline:
         ph = np.zeros((n, cap, 6), np.float64)
         _lib.check(_lib.lib().vbt_pipeline_live_poll(self._h, int(bool(flush_view)), recs, ph.ctypes.data, cap))
         return _live_records(recs, ph)
+
+    def overlay_draw(self, ov, frames_ptr, B, frame0, frame_step=1, stream=None):
+        """vbt_pipeline_overlay_draw: an overlay.Overlay that follows one of this pipeline's clips (Overlay.follow on tracker.rows_dev)
+        consumes the rows of every step enqueued so far and draws B frames at device pointer `frames_ptr` - they may be the frames the
+        steps were given - in place, frame i = frame number frame0 + i * frame_step.  Enqueue only, on `stream`."""
+        _lib.check(_lib.lib().vbt_pipeline_overlay_draw(self._h, ov._h, int(frames_ptr), int(B), int(frame0), int(frame_step), self._caller_stream(stream)))
 
     def skip_frames(self, n=1):
         """Frames read from the source but not processed (`frame_count % 16` of reference track.py:161-167): they advance the clip
