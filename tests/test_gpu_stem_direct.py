@@ -1,0 +1,190 @@
+"""The direct form of the network entry (stem_block.h: stem_block_direct_kernel, variant 1 of fused_stem_block) against the oracle.
+
+A case runs in a child process: it reads the plan space, writes a plan file that puts the network entry on fused_stem_block:1, loads
+it - the file must load unchanged - and returns every materialised tensor, the detections and the plan space of the model that ran.
+Lite0's stem map is 160 x 160 (10 x 10 tiles of 16 x 16: the border tiles have halo pixels outside the map on all four sides, which
+hold the stem's zero point), Lite2's is 224 x 224 (14 x 14 tiles).  The flavours of the requantisation: the pinned models run MODE 3,
+VBT_NO_KBIAS=1 the converting MODE 1, the narrowed-range model the explicit clamps of MODE 0.  All-0 and all-255 frames sit at the
+saturating ends of the stem's requantisation, where an operand byte that should have met a zero weight would show.  The step-group
+case runs the entry on slice g of a group's wide tensor."""
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from test_gpu_band_chain import _oracle
+from test_gpu_plan_space import LITE2, _lite2_frames, _noise_and_checkerboard
+
+pytestmark = pytest.mark.gpu
+
+PRELUDE = r"""
+import os, pickle, sys
+sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+from plan_cover import plan_text, current_plan
+from vbt_amd.interpreter import Interpreter
+
+def stem_plan(model, max_batch, variant):
+    # the heuristic plan (flags 8: no autotuning, the groups and alternatives are those of flags 0) with the entry on fused_stem_block:variant
+    space = Interpreter(model, max_batch=max_batch, flags=8).plan_space()
+    plan = [list(p) for p in current_plan(space)]
+    entry = [e for e in space if e["family"] == "fused_stem_block"]
+    assert len(entry) == 1 and entry[0]["step"] == 0 and sorted(entry[0]["variants"]) == [-1, 0, 1], entry
+    e = entry[0]
+    assert sum(1 for x in space if (x["group"], x["alt"]) == (e["group"], e["alt"])) == 1      # the entry is the one step of its alternative
+    plan[e["group"]] = [e["alt"], (("fused_stem_block", variant),)]
+    return plan_text([(a, tuple(s)) for a, s in plan])
+
+def entry_variant(space):
+    ran = [e["variant"] for e in space if e["chosen"] and e["family"] == "fused_stem_block"]
+    assert len(ran) == 1, ran
+    return ran[0]
+"""
+
+CHILD = PRELUDE + r"""
+model, frames, max_batch, prefix = pickle.load(open(sys.argv[1], "rb"))
+os.environ.pop("VBT_PLAN_FILE", None)
+text = stem_plan(model, max_batch, 1)
+fn = "%s.b%d.f0" % (prefix, max_batch)
+open(fn, "w").write(text)
+os.environ["VBT_PLAN_FILE"] = prefix
+it = Interpreter(model, max_batch=max_batch, flags=0)
+assert open(fn).read() == text, "the plan was refused (re-tuned and re-written)"
+B = len(frames)
+det = it.detect(frames)
+ten = {t: it.read_tensor(t, B) for t in range(1, it.num_tensors() - 1) if it.materialized(t)}
+pickle.dump((det, ten, entry_variant(it.plan_space())), open(sys.argv[2], "wb"))
+"""
+
+GROUP_CHILD = PRELUDE + r"""
+import numpy as np
+import torch
+from vbt_amd import synth
+from vbt_amd.track import Pipeline
+model, prefix = sys.argv[1], sys.argv[2]
+N, G, T = 4, 4, 5                       # one whole group and a partial one
+os.environ.pop("VBT_PLAN_FILE", None)
+texts = {N * G: stem_plan(model, N * G, 1), N: stem_plan(model, N, -1)}
+for mb, text in texts.items():
+    open("%s.b%d.f0" % (prefix, mb), "w").write(text)
+os.environ["VBT_PLAN_FILE"] = prefix
+frames = torch.from_numpy(np.stack([np.stack([synth.render(synth.background(21 + c), 7 * c + t) for c in range(N)]) for t in range(T)])).to("cuda:0")
+out = []
+for group, want in ((1, -1), (G, 1)):
+    pipe = Pipeline(model, N, max_frames=64, fps=60.0, group=group)
+    assert pipe.group == group and entry_variant(pipe.interpreter.plan_space()) == want
+    st = torch.cuda.current_stream().cuda_stream
+    dets = []
+    for t in range(T):
+        pipe.step(frames[t].data_ptr(), st)
+        if t in (3, 4):
+            dets.append([np.array(x) for x in pipe.detections()])
+    best, rows_n, nph, ovf, ph = pipe.close(cap=64)
+    counts, rows = pipe.rows_all()
+    out.append((dets, np.array(best), np.array(rows_n), np.array(counts), [rows[c, :counts[c]].copy() for c in range(N)]))
+for mb, text in texts.items():
+    assert open("%s.b%d.f0" % (prefix, mb)).read() == text, "the b%d plan was refused (re-tuned and re-written)" % mb
+pickle.dump(out, open(sys.argv[3], "wb"))
+"""
+
+
+def _child_env(extra=None):
+    env = {k: v for k, v in os.environ.items() if k not in ("VBT_NO_KBIAS", "VBT_PLAN_FILE", "VBT_FUSION_FLAGS", "VBT_PIPELINE_GROUP")}
+    return {**env, **(extra or {})}
+
+
+@pytest.fixture(scope="module")
+def frames():
+    from vbt_amd import synth
+    return np.concatenate([synth.clip_frames(0, 0, 2), _noise_and_checkerboard(320, 31)[:1]])   # two synth frames and noise
+
+
+@pytest.fixture(scope="module")
+def oracle_run(oracle_lib, model_path, frames):
+    return _oracle(oracle_lib, model_path, frames)
+
+
+@pytest.fixture(scope="module")
+def clamped(tmp_path_factory, oracle_lib, model_path, frames):
+    """The narrowed-range model of test_gpu_band_chain (the explicit-clamp requantisation flavours) and the oracle's run of it."""
+    from vbt_amd.container import Container
+    raw = bytearray(open(model_path, "rb").read())
+    c = Container(model_path)
+    ops = np.frombuffer(raw, dtype=c.ops.dtype, count=len(c.ops), offset=128 + 32 * len(c.tensors))
+    n = 0
+    for i, r in enumerate(ops):
+        if int(r["type"]) in (1, 2, 3) and i % 3 != 0:
+            r["act_min"], r["act_max"] = max(int(r["act_min"]), -101 + i % 7), min(int(r["act_max"]), 96 - i % 5)
+            n += 1
+    assert n > 100
+    path = str(tmp_path_factory.mktemp("models") / "clamped.vbtm")
+    open(path, "wb").write(bytes(raw))
+    return path, _oracle(oracle_lib, path, frames)
+
+
+def _run_case(tmp_path, path, frames, oracle, max_batch, env=None):
+    outs, tensors = oracle
+    src, dst = str(tmp_path / "in.pkl"), str(tmp_path / "out.pkl")
+    with open(src, "wb") as f:
+        pickle.dump((path, frames, max_batch, str(tmp_path / "plan")), f)
+    subprocess.run([sys.executable, "-c", CHILD, src, dst], check=True, cwd=ROOT, env=_child_env(env), timeout=300)
+    (boxes, scores, classes, counts), ten, variant = pickle.load(open(dst, "rb"))
+    assert variant == 1                                                     # the entry ran the direct form
+    assert len(ten) > 60
+    for tid, got in ten.items():
+        for b in range(len(frames)):
+            assert np.array_equal(got[b], tensors[b][tid - 1]), f"tensor {tid} of frame {b} differs ({env})"
+    for b in range(len(frames)):
+        ob, os_, oc, on = outs[b]
+        assert counts[b] == on and np.array_equal(scores[b], os_) and np.array_equal(boxes[b], ob) and np.array_equal(classes[b], oc), (env, b)
+
+
+def test_lite0_bit_exact(tmp_path, model_path, frames, oracle_run):
+    _run_case(tmp_path, model_path, frames, oracle_run, len(frames))
+
+
+def test_explicit_clamps(tmp_path, frames, clamped):
+    path, oracle = clamped
+    _run_case(tmp_path, path, frames, oracle, len(frames))
+
+
+def test_without_biased_accumulators(tmp_path, model_path, frames, oracle_run):
+    """VBT_NO_KBIAS=1: no conv starts its accumulators at bias + 0x4B400000, the entry takes the converting flavour."""
+    _run_case(tmp_path, model_path, frames, oracle_run, len(frames), {"VBT_NO_KBIAS": "1"})
+
+
+def test_partial_batch(tmp_path, model_path, frames, oracle_run):
+    """max_batch 4 running three frames: the grid is that of the frames given."""
+    _run_case(tmp_path, model_path, frames, oracle_run, 4)
+
+
+def test_lite2_bit_exact(tmp_path, oracle_lib):
+    f2 = _lite2_frames()
+    _run_case(tmp_path, LITE2, f2, _oracle(oracle_lib, LITE2, f2), len(f2))
+
+
+def test_all_black_and_all_white_frames(tmp_path, oracle_lib, model_path):
+    ends = np.stack([np.zeros((320, 320, 3), np.uint8), np.full((320, 320, 3), 255, np.uint8)])
+    _run_case(tmp_path, model_path, ends, _oracle(oracle_lib, model_path, ends), len(ends))
+
+
+def test_step_group_writes_its_slice_of_the_wide_tensor(tmp_path, model_path):
+    """4 clips, group 4 on a .b16 plan with the entry on :1, against group 1 on the im2col form: detections and rows equal."""
+    dst = str(tmp_path / "out.pkl")
+    subprocess.run([sys.executable, "-c", GROUP_CHILD, model_path, str(tmp_path / "plan"), dst], check=True, cwd=ROOT, env=_child_env(), timeout=300)
+    one, grouped = pickle.load(open(dst, "rb"))
+    assert int(one[3].sum()) > 0                                            # rows were emitted: the comparison is not vacuous
+    for (d1, dg) in zip(one[0], grouped[0]):
+        for x, y in zip(d1, dg):
+            assert np.array_equal(x, y)
+    for k in (1, 2, 3):
+        assert np.array_equal(one[k], grouped[k]), k
+    for r1, rg in zip(one[4], grouped[4]):
+        assert r1.shape == rg.shape
+        for f in r1.dtype.names or ():
+            assert np.array_equal(r1[f], rg[f], equal_nan=r1[f].dtype.kind == "f"), f
+        if not r1.dtype.names:
+            assert np.array_equal(r1, rg)

@@ -306,6 +306,15 @@ BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, int) {
   return L;
 }
 
+// Network entry (stem_block.h).  Variant: 0 = the im2col form (P and D tiles in LDS), 1 = the direct form (stem conv straight from the
+// raw rows, projection from the depthwise registers), -1 = the im2col form.  Both forms take every map the planner builds the step for.
+StemLaunch resolve_stemblk(const vbt_model*, const Step&, int variant, int) {
+  StemLaunch L;
+  if (variant < -1 || variant > 1) { L.refuse(VBT_ERR_ARG, "fused_stem_block: no kernel form %d", variant); return L; }
+  L.direct = variant == 1;
+  return L;
+}
+
 // Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major): the batch-offset pointers here, the
 // variant and the launch in the family's own function above.  `frames` = frame boff, the first one of the range; the output pointers
 // are those of the whole batch.
@@ -431,7 +440,9 @@ int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_
       StemBlockArgs a = s.sb;
       a.frames = frame0;
       a.out = out;
-      return launch_stem_block(a, a.rqs.full && a.rqd.full && a.rqp.full, (unsigned)((long)B * a.tiles_x * a.tiles_y), st);
+      const StemLaunch L = resolve_stemblk(m, s, s.variant, B);
+      if (L.rc) return L.report();
+      return launch_stem_block(a, L.direct, (unsigned)((long)B * a.tiles_x * a.tiles_y), st);
     }
     case F_POST: {
       PostArgs p;

@@ -186,11 +186,13 @@ struct ExpDwLaunch : Verdict {   // chunks per workgroup; second form: waves per
   bool second = false; int cpw = 1, nw = 0, gpw = 0, lds = 0; unsigned grid = 0;
 };
 struct BandLaunch : Verdict { bool chained = false; int lds = 0; };
+struct StemLaunch : Verdict { bool direct = false; };
 PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B);
 DwLaunch resolve_dw(const vbt_model* m, const Step& s, int variant, int B);
 FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B);
 ExpDwLaunch resolve_expdw(const vbt_model* m, const Step& s, int variant, int B);
 BandLaunch resolve_band(const vbt_model* m, const Step& s, int variant, int B);
+StemLaunch resolve_stemblk(const vbt_model* m, const Step& s, int variant, int B);
 
 // ---- launches (detector.hip) ----
 // Launches one plan step for frames [boff, boff + B) of the batch (every tensor is batch-major).  `frames` = frame boff, the first one

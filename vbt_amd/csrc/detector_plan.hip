@@ -118,6 +118,7 @@ static bool variant_ok(const vbt_model* m, const Step& st, int v) {
   if (st.family == F_PW) return !st.members.empty() || !resolve_pw(m, st, v, m->max_batch).rc;
   if (is_fused_tile(st.family)) return !resolve_fused(m, st, v, m->max_batch).rc;
   if (st.family == F_BAND) return !resolve_band(m, st, v, m->max_batch).rc;
+  if (st.family == F_STEMBLK) return !resolve_stemblk(m, st, v, m->max_batch).rc;
   return st.family != F_EXPDW || !resolve_expdw(m, st, v, m->max_batch).rc;
 }
 
@@ -158,6 +159,8 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
         }
   } else if (st.family == F_BAND) {
     cand = {-1, 0, 1};   // the launch kind's default, two stages, chained (64-channel maps only)
+  } else if (st.family == F_STEMBLK) {
+    cand = {-1, 0, 1};   // the default (the im2col form), the im2col form, the direct form
   }
   cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int v) { return !variant_ok(m, st, v); }), cand.end());
   return cand;

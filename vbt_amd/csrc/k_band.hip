@@ -99,10 +99,18 @@ int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int 
   return VBT_OK;
 }
 
-int launch_stem_block(const StemBlockArgs& a, bool full_range, unsigned grid, hipStream_t st) {
-  if (full_range && a.rqs.kb && a.rqd.kb && a.rqp.kb) stem_block_kernel<3><<<dim3(grid), 256, 0, st>>>(a);
-  else if (full_range) stem_block_kernel<1><<<dim3(grid), 256, 0, st>>>(a);
-  else stem_block_kernel<0><<<dim3(grid), 256, 0, st>>>(a);
+int launch_stem_block(const StemBlockArgs& a, bool direct, unsigned grid, hipStream_t st) {
+  const bool full_range = a.rqs.full && a.rqd.full && a.rqp.full;
+  const int mode = full_range ? (a.rqs.kb && a.rqd.kb && a.rqp.kb ? 3 : 1) : 0;
+  if (direct) {
+    if (mode == 3) stem_block_direct_kernel<3><<<dim3(grid), 256, 0, st>>>(a);
+    else if (mode == 1) stem_block_direct_kernel<1><<<dim3(grid), 256, 0, st>>>(a);
+    else stem_block_direct_kernel<0><<<dim3(grid), 256, 0, st>>>(a);
+  } else {
+    if (mode == 3) stem_block_kernel<3><<<dim3(grid), 256, 0, st>>>(a);
+    else if (mode == 1) stem_block_kernel<1><<<dim3(grid), 256, 0, st>>>(a);
+    else stem_block_kernel<0><<<dim3(grid), 256, 0, st>>>(a);
+  }
   return VBT_OK;
 }
 

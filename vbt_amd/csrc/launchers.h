@@ -50,6 +50,7 @@ int launch_expdw(const ExpDwArgs& a, int k, int stride, int KS64, unsigned grid,
 // per wave (8 waves: 2, 4 or 7; 16 waves: 1, 2 or 4)
 int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int gpw, unsigned grid, int lds_bytes, hipStream_t st);
 // network entry: stem 3x3/2 + first SeparableConv (stem_block.h)
-int launch_stem_block(const StemBlockArgs& a, bool full_range, unsigned grid, hipStream_t st);
+// (direct: the second form of the kernel, plan variant 1)
+int launch_stem_block(const StemBlockArgs& a, bool direct, unsigned grid, hipStream_t st);
 
 }  // namespace vbt

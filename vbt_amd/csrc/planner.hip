@@ -471,6 +471,10 @@ static int make_stem_block(vbt_model* m, int si, Step* out) {
         (rc = upload(m, pad_floats((const float*)(m->blob.data() + st.m_off), 32, 32), &dms)))
       return rc;
     a.ws = dws; a.bs = dbs; a.ms = dms;
+    v4i* dws64;   // the direct form (variant 1): kernel rows straight from the raw rows, 16x16x64
+    if ((rc = upload(m, pack_stem_block_stem64(w), &dws64))) return rc;
+    a.ws64 = dws64;
+    a.in_pad4s = a.in_pad4 ^ 0x80808080u;
   }
   const Step& ds = m->op_steps[si + 1];  // matrix-pipe depthwise bias / multipliers of the dw op
   a.bdm = ds.bdm; a.mdm = ds.mdm;
@@ -484,6 +488,9 @@ static int make_stem_block(vbt_model* m, int si, Step* out) {
         (rc = upload(m, pad_floats((const float*)(m->blob.data() + p.m_off), to.c, 16), &dmp)))
       return rc;
     a.wp = dwp; a.bp = dbp; a.mp = dmp;
+    long* dwpc;   // the direct form: K in the order of the depthwise registers
+    if ((rc = upload(m, pack_stem_block_proj_chain(w, to.c), &dwpc))) return rc;
+    a.wpc = dwpc;
   }
   s.cost = cost_of(m, {si, si + 1, si + 2});
   *out = s;

@@ -35,6 +35,10 @@ struct StemBlockArgs {
   const int* bp;        // [16] folded
   const float* mp;      // [16]
   Rq rqp;
+  // the direct form (stem_block_direct_kernel)
+  unsigned in_pad4s;    // in_pad4 in the int8 domain (every byte XOR 0x80)
+  const v4i* ws64;      // stem weights [t(2)][lane] x 16 B: lane group g < 3 = kernel row g, bytes 0..8 its nine taps, zero elsewhere
+  const long* wpc;      // project [lane] x 8 B in the K order the depthwise leaves in registers (pack_stem_block_proj_chain)
 };
 
 constexpr int SB_HW = 18, SB_NPH = SB_HW * SB_HW, SB_NPG = (SB_NPH + 15) / 16;
@@ -163,6 +167,123 @@ __global__ __launch_bounds__(256) void stem_block_kernel(StemBlockArgs a) {
       const unsigned q = rq_pack_b<FK>(acc, mm, a.rqp);
       const int oy = oy0 + py, ox = ox0 + r;
       if (oy < a.SH && ox < a.SW && 4 * g < a.Cout) *(unsigned*)(a.out + ((b * a.SH + oy) * (long)a.SW + ox) * a.Cout + 4 * g) = q;
+    }
+  }
+}
+
+// The direct form (plan variant 1): no im2col tile and no depthwise tile.
+//   R  [37][120]    the same raw rows, already int8 (XOR 0x80 once per loaded dword; out-of-image dwords = in_pad4s)
+//   S  [324][48]    as above; R and S are both live in the stem stage, so they do not share storage (20.1 KB -> 8 workgroups / CU)
+// stem: the K = 27 of a halo pixel goes to one 16x16x64 MFMA as it lies in R: lane (r, g < 3) takes kernel row g of pixel r as the three
+// aligned dwords that cover its 9 bytes, funnel-shifted to the pixel's first byte.  K slots 9..15 of the lane group hold the bytes
+// that follow in the row (or zero), lane group 3 repeats kernel row 2: all of these meet zero weights (pack_stem_block_stem64).
+// depthwise + project: wave w owns output rows 4w..4w+3 for BOTH channel groups, so lane (r, g) ends with channels 4g..4g+3 and
+// 16+4g..16+4g+3 of pixel r: those two dwords are the B operand of the projection's 16x16x32 MFMA with the weights packed in that
+// K order (pack_stem_block_proj_chain; the chained form of band_block.h).  Two barriers: fill | stem | depthwise + project.
+// 20.1 KB of LDS admit 8 workgroups per CU; the register allocator is held to the 64 VGPRs of 8 waves per SIMD.  MODE 1 / 3 pay one
+// spilled VGPR for it (one scratch store after the first barrier, one reload in the last stage); at 6 waves per SIMD nothing spills and
+// the launch is 10 % slower (profiles/r11_stem_direct_ab.md section 3).
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void stem_block_direct_kernel(StemBlockArgs a) {
+  constexpr int FK = MODE == 0 ? -1 : MODE;
+  constexpr int KB = MODE >= 2 ? RQ_KBIAS : 0;
+  __shared__ __attribute__((aligned(16))) unsigned char R[SB_RROWS * SB_RST];
+  __shared__ __attribute__((aligned(16))) unsigned char S[SB_NPH * SB_SST + 64];
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 15, g = lane >> 4;
+  const int tile = blockIdx.x;
+  const int trow = fdiv_small(tile, frcp(a.tiles_x));
+  const int tx = tile - trow * a.tiles_x;
+  const int bimg = fdiv_small(trow, frcp(a.tiles_y));
+  const int ty = trow - bimg * a.tiles_y;
+  const long b = bimg;
+  const int oy0 = ty * 16, ox0 = tx * 16;
+  const int sy0 = oy0 - 1, sx0 = ox0 - 1;
+  const int iy0 = 2 * sy0 - a.spad_t, ix0 = 2 * sx0 - a.spad_l;
+  const int rb0 = ix0 * 3;
+  const int al = rb0 & 3;
+  const int rstart = rb0 - al;
+  const int rowbytes = a.W * 3;
+
+  // ---- 1: raw patch rows -> R, 32 lanes per row (30 live), 8 rows per round ----
+  {
+    const int d = tid & 31, off = rstart + 4 * d;
+    const bool live = d < SB_RDW, in_x = off >= 0 && off < rowbytes;
+    const uint8_t* f = a.frames + b * (long)a.H * rowbytes + off;
+#pragma unroll
+    for (int row = tid >> 5; row < SB_RROWS; row += 8) {
+      const int iy = iy0 + row;
+      unsigned v = a.in_pad4s;
+      if (in_x && iy >= 0 && iy < a.H) v = *(const unsigned*)(f + (long)iy * rowbytes) ^ 0x80808080u;
+      if (live) *(unsigned*)(R + row * SB_RST + 4 * d) = v;
+    }
+  }
+  __syncthreads();
+  // ---- 2: stem conv on the 18x18 halo straight from R, 2 MFMAs per 16 pixels (32 output channels) ----
+  {
+    const v4i wa0 = a.ws64[lane], wa1 = a.ws64[64 + lane];
+    const int4 b0 = int4_plus(*(const int4*)(a.bs + 8 * g), KB), b1 = int4_plus(*(const int4*)(a.bs + 8 * g + 4), KB);
+    const float4 m0 = *(const float4*)(a.ms + 8 * g), m1 = *(const float4*)(a.ms + 8 * g + 4);
+    const bool border = sy0 < 0 || sx0 < 0 || sy0 + SB_HW > a.SH || sx0 + SB_HW > a.SW;   // halo pixels outside the stem's output map
+    const unsigned char* lane_row = R + min(g, 2) * SB_RST;
+    for (int pg = wave; pg < SB_NPG; pg += 4) {
+      const int p = pg * 16 + r;
+      const int pc = min(p, SB_NPH - 1);
+      const int hy = pc / SB_HW, hx = pc - hy * SB_HW;
+      const int o = al + 6 * hx;
+      const unsigned char* src = lane_row + hy * (2 * SB_RST) + (o & ~3);
+      const unsigned d0 = *(const unsigned*)src, d1 = *(const unsigned*)(src + 4), d2 = *(const unsigned*)(src + 8);
+      const unsigned sh = (unsigned)(o & 3);
+      const v4i bv = {(int)__builtin_amdgcn_alignbyte(d1, d0, sh), (int)__builtin_amdgcn_alignbyte(d2, d1, sh), (int)__builtin_amdgcn_alignbyte(d2, d2, sh), 0};
+      v4i a0 = v4i_from(b0), a1 = v4i_from(b1);
+      a0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa0, bv, a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa1, bv, a1, 0, 0, 0);
+      unsigned q0 = rq_pack_b<FK>(a0, m0, a.rqs), q1 = rq_pack_b<FK>(a1, m1, a.rqs);
+      if (border && !((unsigned)(sy0 + hy) < (unsigned)a.SH && (unsigned)(sx0 + hx) < (unsigned)a.SW)) { q0 = a.zs4; q1 = a.zs4; }
+      if (p < SB_NPH) *(uint2*)(S + p * SB_SST + 8 * g) = make_uint2(q0, q1);
+    }
+  }
+  __syncthreads();
+  // ---- 3: depthwise 3x3/1 on the 16x16x64 MFMA (wave -> output rows 4 wave.., both channel groups), project from its registers ----
+  {
+    // lane (r = output column, g = tap column): B operand of instruction m for output row py = 16 channels of halo pixel
+    // (py + m, r + g); g = 3 carries zero weights (it reads one pixel past the window: still inside S)
+    const unsigned char* lane_base = S + (wave * 4 * SB_HW + r + g) * SB_SST;
+    unsigned dq[2][4];
+#pragma unroll
+    for (int cg = 0; cg < 2; cg++) {
+      v4i wreg[3];
+#pragma unroll
+      for (int mi = 0; mi < 3; mi++) wreg[mi] = a.wd64[(cg * 3 + mi) * 64 + lane];
+      const int4 bqm = int4_plus(*(const int4*)(a.bdm + 16 * cg + 4 * g), KB);
+      const float4 mum = *(const float4*)(a.mdm + 16 * cg + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; i += 2) {   // two output rows at a time: independent accumulate chains on four halo rows
+        v4i rows[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) rows[j] = *(const v4i*)(lane_base + (i + j) * SB_HW * SB_SST + 16 * cg);
+        v4i dqa = v4i_from(bqm), dqb = v4i_from(bqm);
+#pragma unroll
+        for (int mi = 0; mi < 3; mi++) {
+          dqa = __builtin_amdgcn_mfma_i32_16x16x64_i8(wreg[mi], rows[mi], dqa, 0, 0, 0);
+          dqb = __builtin_amdgcn_mfma_i32_16x16x64_i8(wreg[mi], rows[mi + 1], dqb, 0, 0, 0);
+        }
+        dq[cg][i] = rq_pack_b<FK>(dqa, mum, a.rqd);
+        dq[cg][i + 1] = rq_pack_b<FK>(dqb, mum, a.rqd);
+      }
+    }
+    const long wa = a.wpc[lane];
+    const int4 bb = int4_plus(*(const int4*)(a.bp + 4 * g), KB);
+    const float4 mm = *(const float4*)(a.mp + 4 * g);
+    const int ox = ox0 + r;
+    int8_t* const op = a.out + ((b * a.SH + oy0 + wave * 4) * (long)a.SW + ox) * a.Cout + 4 * g;
+    const bool col_ok = ox < a.SW && 4 * g < a.Cout;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const long bv = (long)(((unsigned long)dq[1][i] << 32) | dq[0][i]);
+      v4i acc = v4i_from(bb);
+      acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(wa, bv, acc, 0, 0, 0);
+      const unsigned q = rq_pack_b<FK>(acc, mm, a.rqp);
+      if (col_ok && oy0 + wave * 4 + i < a.SH) *(unsigned*)(op + (long)i * a.SW * a.Cout) = q;
     }
   }
 }

@@ -236,6 +236,31 @@ inline std::vector<long> pack_stem_block_proj(const int8_t* w, int N) {
   }
   return out;
 }
+// Stem block, direct form, stem conv on the 16x16x64 MFMA: [t][lane] x 16 B, cout as above.  The B operand of lane group g < 3 is the
+// 16 bytes of the raw row 2 hy + g from the pixel's first byte on: byte j < 9 = tap (kernel row g, byte j of its 9); every other byte
+// (the row's next pixels, lane group 3) is zero here, so whatever the kernel feeds there does not count
+inline std::vector<v4i> pack_stem_block_stem64(const int8_t* w) {
+  std::vector<v4i> out(2 * 64, (v4i){0, 0, 0, 0});
+  int8_t* o = (int8_t*)out.data();
+  for (int t = 0; t < 2; t++)
+    for (int lane = 0; lane < 64; lane++) {
+      const int i = lane & 15, g = lane >> 4, co = 8 * (i >> 2) + 4 * t + (i & 3);
+      for (int j = 0; j < 9 && g < 3; j++) o[((size_t)t * 64 + lane) * 16 + j] = w[(size_t)co * 27 + g * 9 + j];
+    }
+  return out;
+}
+// Stem block, direct form, projection: [lane][8], row i = cout i (N <= 16) in the K order the depthwise leaves in registers: lane
+// (i, g), byte 4cg + j holds W[i][k = 16cg + 4g + j] (a permutation of pack_stem_block_proj's row: see pack_band_pw_chain)
+inline std::vector<long> pack_stem_block_proj_chain(const int8_t* w, int N) {
+  std::vector<long> out(64, 0);
+  int8_t* o = (int8_t*)out.data();
+  for (int lane = 0; lane < 64; lane++) {
+    const int i = lane & 15, g = lane >> 4;
+    for (int cg = 0; cg < 2; cg++)
+      for (int j = 0; j < 4; j++) o[(size_t)lane * 8 + 4 * cg + j] = i < N ? w[(size_t)i * 32 + 16 * cg + 4 * g + j] : 0;
+  }
+  return out;
+}
 
 // Expand + depthwise kernels (expdw_block.h), expand panels: [(c*KS + ks)*4 + t][lane] x 16 B; lane (i, g) holds
 // W[cout = 64c + 16t + i][k = 64ks + 16g + j]
