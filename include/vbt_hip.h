@@ -586,7 +586,9 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
  * Phase timeline: columns c in [0, 47 s) at X + 2 s + c.  Column c stands for frame fc = f - (47 s - 1 - c) * frame_step (int64;
  * frame_step is the draw call's).  The first phase of the table with fs < fc <= fe decides (only fc >= 1 can match): concentric -
  * the column covers rows [Y + 43 s, Y + 47 s); eccentric - rows [Y + 45 s, Y + 47 s); a hold, or no such phase - nothing.  The
- * timeline uses the whole table, completed or not: the panel is rendered after the clip is analysed.
+ * timeline uses the whole table, completed or not: with vbt_overlay_set_hud the panel is rendered after the clip is analysed and
+ * every frame shows the finished analysis; a panel that follows the live analysis ("Rep panel from the live analysis" below) shows
+ * the table as it stood at its last update.
  * Colours.  VBT_PIX_RGB24: a covered panel pixel gets fg, every other panel pixel bg.  YUV: luma per pixel in the same way; the chroma
  * sample at (py >> 1, px >> 1) gets fg's U, V if any of its four pixels is covered, else bg's - both colours through the integers
  * above.  For the YUV formats X and Y are even (52 s and 50 s always are): every chroma sample of the panel lies wholly inside it.
@@ -614,7 +616,41 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
  * Rewound log.  *nrows_dev < cursor: the clip was reset or recycled.  Nothing is consumed, VBT_OVERLAY_FOLLOW_REWOUND is set, and the
  * caller calls vbt_overlay_follow again.
  * Frames without an accepted row, and frames beyond the last consumed row, are not touched.  The rep panel does not depend on the
- * row source: vbt_overlay_set_hud works on a handle in follow mode as on any other. */
+ * row source: vbt_overlay_set_hud works on a handle in follow mode as on any other.
+ *
+ * Rep panel from the live analysis (vbt_overlay_hud_follow).  A handle's panel can FOLLOW one clip of a tracker that has live
+ * analysis enabled (vbt_tracker_live_enable): its table is then formed on the device, from the phase list the live analysis keeps
+ * for the clip's leader, by one launch per update.  The raster contract is the one of "Rep panel" above; only the table's source
+ * changes.
+ * Equality.  After vbt_overlay_hud_follow_update(o, flush_view, stream), a vbt_overlay_draw writes exactly the bytes it would write
+ * after vbt_tracker_live_poll(t, flush_view, ...) at the same point of the tracker's stream, followed by vbt_overlay_set_hud(o,
+ * params, the phases6 of that clip, its n_phases, fps, ...).  No byte is copied to the host and no stream is synchronised.  The
+ * table's integers come from the same statements as vbt_overlay_set_hud's (overlay_core.h: fs, fe, centi, ACV, the running
+ * concentric count), in IEEE double without contraction.
+ * Snapshot semantics.  The panel is a snapshot at update granularity: every frame of a draw sees the leader's phase list as it stood
+ * at the last update, and the per-frame rules above (completed = fe <= f, the timeline's window) apply to that snapshot.  With one
+ * frame per tracker launch and one update per launch the panel is exactly causal; with a batch of frames per launch the first
+ * frames of the batch already show what the batch's last frame established.
+ * Difference from a panel set after the analysis (track --hud): that one shows the finished analysis on every frame.  The live panel
+ * shows what is known so far.  Phases can also DISAPPEAR again - the analysis drops phases below its threshold when the clip's
+ * max_y_diff grows - and the leader can change, with which the whole table changes: the rep count of the live panel can go down.
+ * Blank panel.  The panel of P = 0 ("REP    0", blank fields, no bar, no timeline) is shown when the clip has no leader (-1), when the
+ * leader has no entry in the live tables, and when the clip or the leader's entry carries any VBT_LIVE_* bit - the cases in which
+ * the poll reports no phases.
+ * Refusals become flags.  A kernel cannot refuse a call.  What vbt_overlay_set_hud would refuse in the phases - a non-finite value,
+ * a type outside {0, 1, 2}, time_end < time_start, times decreasing along the table, fe above 2^24; the same tests in the same
+ * order - sets VBT_OVERLAY_HUD_FOLLOW_BAD_PHASE, and the panel is blank for that update.  VBT_OVERLAY_HUD_FOLLOW_FLAGGED: the
+ * VBT_LIVE_* case above.  VBT_OVERLAY_HUD_FOLLOW_CAPACITY: more phases than the handle's table holds (the tracker's phase_cap when
+ * the panel was bound); blank as well.  The bits are sticky: vbt_overlay_hud_follow_status returns every bit set by an update
+ * since vbt_overlay_hud_follow, with the leader and the phase count of the last update.
+ * Ordering.  (a) The live tables are changed in place by the tracker launch that follows (its live analysis compacts the lists),
+ * unlike the row log, which only grows: an update must not overlap a later launch of that tracker.  (b) An update overwrites the
+ * table the previous draw may still be reading.  For the bare vbt_overlay_hud_follow_update both are the caller's duty: `stream` is
+ * ordered behind the tracker launch whose state is to be shown, the next launch of that tracker behind the update, and the update
+ * behind every draw of the handle enqueued before it - all three hold when tracker, update and draw share one stream.
+ * vbt_pipeline_overlay_draw orders both itself, with one event in each direction and no host wait: the update runs on the
+ * pipeline's tracker stream behind the last tracker launch; the event every later tracker launch and `stream` wait for is recorded
+ * behind it; and the update waits for an event recorded on `stream` behind the handle's previous draw. */
 typedef struct vbt_overlay vbt_overlay;
 typedef struct {
   int32_t trail;        /* bar path length in points, track.py:57-58 -> 120 */
@@ -665,6 +701,30 @@ void vbt_overlay_hud_default_params(vbt_overlay_hud_params* p);
  * uploads it in one copy on `stream` and synchronises it. */
 int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, const double* phases6_host, int P, double fps, void* stream);
 
+/* A panel that follows the live analysis ("Rep panel from the live analysis" above) */
+enum {
+  VBT_OVERLAY_HUD_FOLLOW_FLAGGED = 1,    /* the clip or its leader carries a VBT_LIVE_* bit (or the leader has no entry) */
+  VBT_OVERLAY_HUD_FOLLOW_BAD_PHASE = 2,  /* a phase vbt_overlay_set_hud would refuse */
+  VBT_OVERLAY_HUD_FOLLOW_CAPACITY = 4    /* more phases than the handle's table holds */
+};
+/* Bind the handle's panel to clip `clip` of tracker `t`: replaces a panel set by vbt_overlay_set_hud, and vbt_overlay_set_hud
+ * replaces a following one (params NULL with P = 0 switches either off).  `t` is borrowed and must outlive the handle's use of it.
+ * The handle allocates its own table (phase_cap records of 24 bytes, the phase count, leader and flags) and its own flush-view
+ * scratch (phase_cap x 6 doubles; not the poll's).  Synchronous (allocation + clears); the panel is blank until the first update.
+ * Checked in this order and before any device call.  VBT_ERR_ARG: params NULL; fps <= 0 or not finite; scale outside 1..64;
+ * full_scale_cm outside 1..100000; x < 0 or y < 0; the handle NULL; t NULL; clip outside the tracker's clips; odd x or y with a YUV
+ * handle; a panel that does not lie wholly inside the frame.  VBT_ERR_STATE: live analysis is not enabled on t.  VBT_ERR_ARG: the
+ * tracker is on another device than the handle.  A refused call leaves the handle's panel as it was. */
+int vbt_overlay_hud_follow(vbt_overlay* o, const vbt_overlay_hud_params* params, vbt_tracker* t, int clip, double fps);
+/* Form the table from the live analysis as it stands: ONE launch of one wavefront on `stream`, enqueue only (see "Ordering").
+ * flush_view != 0: the phases as if the clip ended now, as the poll's flush view.  VBT_ERR_STATE: the panel follows nothing. */
+int vbt_overlay_hud_follow_update(vbt_overlay* o, int flush_view, void* stream);
+/* Leader and phase count of the last update and the VBT_OVERLAY_HUD_FOLLOW_* bits so far; one 16-byte copy on `stream`, which it
+ * synchronises */
+int vbt_overlay_hud_follow_status(vbt_overlay* o, int64_t* leader, int32_t* n_phases, int32_t* flags, void* stream);
+/* The flush_view vbt_pipeline_overlay_draw passes to the update it makes for this handle (default 0) */
+int vbt_overlay_hud_follow_flush(vbt_overlay* o, int flush_view);
+
 /* Follow mode ("Following a device row log" above) */
 enum {
   VBT_OVERLAY_FOLLOW_BAD_ROW = 1,
@@ -690,7 +750,10 @@ int vbt_overlay_follow_status(vbt_overlay* o, int32_t* rows_consumed, int32_t* f
 /* The pipeline's side of a one-pass export, for an overlay that follows one of the pipeline's clips: enqueue the tracker steps still
  * held back (vbt_pipeline_drain), make `stream` wait for the most recent tracker launch, then vbt_overlay_follow_update and
  * vbt_overlay_draw on `stream`.  Enqueue only.  The frames may be the ones the steps were given (drawn in place): the tracker launch
- * waited for depends on their forward, whichever stream the tracker runs on. */
+ * waited for depends on their forward, whichever stream the tracker runs on.
+ * A handle whose panel follows this pipeline's tracker (vbt_overlay_hud_follow) also gets its vbt_overlay_hud_follow_update, with
+ * the handle's vbt_overlay_hud_follow_flush setting, between the tracker launch and the draw ("Ordering" above: on the tracker
+ * stream, events both ways, no host wait).  For every other handle the call enqueues exactly what it did without that. */
 int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
 
 /* ------------------------------------------------------------------ MJPEG export --------

@@ -101,7 +101,11 @@ int vbt_model_profile_families(vbt_model* m, int B, int reps, void* stream, doub
 int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n);
 /* The table vbt_overlay_set_hud uploaded, read back from the device: out[i] = fs, fe, rom_cm, acv_cm, type, concentric phases among
  * phases 0..i - so that a failing panel pixel can be told from a wrong integer.  *P = the panel's phases (0 without a panel);
- * cap < *P is VBT_ERR_CAPACITY with nothing copied.  One blocking copy. */
+ * cap < *P is VBT_ERR_CAPACITY with nothing copied.  One blocking copy.  A panel that follows the live analysis
+ * (vbt_overlay_hud_follow): the table as the updates COMPLETED so far left it, *P read from the device first.  The copies are plain
+ * blocking copies: they wait for updates enqueued on the null stream or on a stream that synchronises with it, not for one on a
+ * non-blocking stream (the pipeline's tracker stream) - synchronise that stream, or a stream ordered behind it such as the one
+ * vbt_pipeline_overlay_draw was given, before the call. */
 int vbt_overlay_hud_table(vbt_overlay* o, int32_t* out /*[P][6]*/, int cap, int* P);
 
 /* MJPEG import, measurement (tools/mjpeg_decode_bench.py).  With VBT_MJPEG_DECODE_STAMPS=1 in the environment of

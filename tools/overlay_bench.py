@@ -12,7 +12,14 @@ for a 10-minute clip's worth (4 ids x 18000 frames).
 rounds, alternating with the first: per format "hud" = its draw time and the increment over the panel-off draw, next to the copy of
 the batch.  --size WxH (default 1920x1080): the same at another frame size - the increment must not grow with H * W.
 
-  python tools/overlay_bench.py [--frames 64] [--reps 20] [--warmup 5] [--hud] [--size 1920x1080] [--out FILE.json]
+--hud_follow: the rep panel that follows the live analysis (vbt_overlay_hud_follow) against the route it replaces, and nothing else.
+A tracker replays reference clip 029 (tests/golden) up to the launch after which its leader holds the most phases.  Per format, in
+one process, alternating: "follow" = HIP-event time of hud_follow_update + the panel draw of the batch (two launches, nothing
+synchronised); "poll" = host-clock time of live poll + set_hud + the same draw + the synchronisation that ends it (the poll and
+set_hud synchronise on their own), and of the poll + set_hud part alone.  Medians with min and max.  Then `track --one_pass
+--video_format mjpeg` on a synthetic clip with and without --live_hud, alternating, frames per second of the whole command.
+
+  python tools/overlay_bench.py [--frames 64] [--reps 20] [--warmup 5] [--hud | --hud_follow] [--size 1920x1080] [--out FILE.json]
 
 Prints one JSON line."""
 import argparse
@@ -52,6 +59,94 @@ def make_phases(n_frames):
     return [((1 + i * step) / FPS, (1 + (i + 1) * step) / FPS, 0.3, 0.6, 0.4 + 0.01 * i, 1 - i % 2) for i in range(24)]
 
 
+def replay_029(upto=None, chunk=64):
+    """a tracker with live analysis that replayed clip 029 `chunk` frames per launch - all of it, or its first `upto` launches; returns
+    (tracker, phases of the leader after every launch)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_tracker import _pack
+    from test_oracle_ocsort import frames_from_rows
+    from test_oracle_ocsort_corpus import load_all
+    from vbt_amd.ocsort import MultiClipTracker
+    fr, tm = frames_from_rows(load_all()["029"][0])
+    dets, counts, times = _pack([fr], [tm])
+    mc = MultiClipTracker(1, 8192, max_age=30, asso_func="diou", iou_threshold=0.1)
+    mc.enable_live(path_cap=4096, phase_cap=128)
+    seen = []
+    for k, f0 in enumerate(range(0, len(fr), chunk)):
+        if upto is not None and k >= upto:
+            break
+        mc.update_frames(dets[f0:f0 + chunk], counts[f0:f0 + chunk], times[f0:f0 + chunk])
+        seen.append(len(mc.live()[0].phases))
+    return mc, seen
+
+
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def hud_follow_bench(args, res):
+    import tempfile
+    import numpy as np
+    import torch
+    from click.testing import CliRunner
+    from vbt_amd import synth
+    from vbt_amd.cli import main as cli
+    from vbt_amd.overlay import Overlay
+    from vbt_amd.rawvideo import frame_shape
+    B = args.frames
+    _, seen = replay_029()
+    best = max(range(len(seen)), key=lambda k: seen[k])
+    mc, seen = replay_029(upto=best + 1)
+    frame0 = (best + 1) * 64
+    res["clip"] = {"name": "029", "launches_replayed": best + 1, "leader_phases": seen[-1], "frame0": frame0}
+    prm = dict(x=16, y=16, scale=3)
+    for fmt in ("rgb24", "nv12"):
+        src = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (B,) + frame_shape(fmt, H, W), dtype=np.uint8)).cuda()
+        fol, sta = Overlay(H, W, fmt), Overlay(H, W, fmt)
+        fol.hud_follow(mc, 0, FPS, **prm)
+        t = {"follow": [], "poll_route": [], "poll_set_hud": []}
+        for r in range(args.warmup + args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fol.hud_follow_update(False, None)
+            fol.draw(src.data_ptr(), B, frame0, 1, None)
+            e1.record()
+            e1.synchronize()
+            a = e0.elapsed_time(e1) * 1e3
+            t0 = time.perf_counter()
+            rec = mc.live()[0]
+            sta.set_hud(rec.phases, FPS, None, **prm)
+            t1 = time.perf_counter()
+            sta.draw(src.data_ptr(), B, frame0, 1, None)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if r >= args.warmup:
+                t["follow"].append(a)
+                t["poll_route"].append((t2 - t0) * 1e6)
+                t["poll_set_hud"].append((t1 - t0) * 1e6)
+        assert np.array_equal(fol.hud_table(), sta.hud_table()) and fol.hud_follow_status()[2] == 0
+        res[fmt] = {"panel": [52 * prm["scale"], 50 * prm["scale"]], "phases": len(rec.phases),
+                    "follow_update_plus_draw_us_events": spread(t["follow"]), "poll_set_hud_draw_sync_us_host": spread(t["poll_route"]),
+                    "poll_set_hud_us_host": spread(t["poll_set_hud"])}
+    T, S = 256, 416
+    model = os.path.join(ROOT, "models", "efficientdet_lite0_synth.vbtm")
+    fps_of = {"plain": [], "live_hud": []}
+    with tempfile.TemporaryDirectory() as d:
+        clip = os.path.join(d, "clip.npy")
+        np.save(clip, synth.clip_frames(12, 0, T, size=S))
+        for r in range(1 + 3):                                     # one warm-up round
+            for name, extra in (("plain", []), ("live_hud", ["--live_hud"])):
+                t0 = time.perf_counter()
+                out = CliRunner().invoke(cli, ["track", clip, "--model", model, "--detection_treshold", "0.3", "--fps", "60", "--video_dir",
+                                               os.path.join(d, name), "--video_format", "mjpeg", "--one_pass"] + extra)
+                dt = time.perf_counter() - t0
+                assert out.exit_code == 0, out.output
+                if r:
+                    fps_of[name].append(T / dt)
+    res["track_one_pass_mjpeg"] = {"frames": T, "size": S, "frames_per_s": {k: spread(v) for k, v in fps_of.items()},
+                                   "note": "whole command: model load, pipeline set-up and export included"}
+
+
 def main():
     global H, W
     ap = argparse.ArgumentParser()
@@ -59,6 +154,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hud", action="store_true", help="also time the draw with a rep panel set")
+    ap.add_argument("--hud_follow", action="store_true", help="time the panel that follows the live analysis against poll + set_hud, and nothing else")
     ap.add_argument("--size", default=f"{W}x{H}", help="frame size WIDTHxHEIGHT")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -78,6 +174,18 @@ def main():
     rows = make_rows(TRAIL + B)
     stream = torch.cuda.current_stream().cuda_stream
     res = {"frames": B, "H": H, "W": W, "rows_per_frame": IDS, "trail": TRAIL, "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+
+    def finish():
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+
+    if args.hud_follow:
+        hud_follow_bench(args, res)
+        return finish()
 
     def timed(fn, k=1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -147,12 +255,7 @@ def main():
         ov.set_rows(long_rows, FPS, stream)
         ts.append((time.perf_counter() - t0) * 1e6)
     res["set_rows_long"] = {"rows": len(long_rows["id"]), "us_median": statistics.median(ts), "note": "includes the numpy sort of the Python wrapper"}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    finish()
 
 
 if __name__ == "__main__":

@@ -192,6 +192,10 @@ _SIGS = {
     "vbt_overlay_hud_default_params": (None, [ctypes.POINTER(OverlayHudParams)]),
     "vbt_overlay_set_hud": (c_int, [c_void_p, ctypes.POINTER(OverlayHudParams), c_void_p, c_int, c_double, c_void_p]),
     "vbt_overlay_hud_table": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_overlay_hud_follow": (c_int, [c_void_p, ctypes.POINTER(OverlayHudParams), c_void_p, c_int, c_double]),
+    "vbt_overlay_hud_follow_update": (c_int, [c_void_p, c_int, c_void_p]),
+    "vbt_overlay_hud_follow_status": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_void_p]),
+    "vbt_overlay_hud_follow_flush": (c_int, [c_void_p, c_int]),
     "vbt_overlay_follow": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double]),
     "vbt_overlay_follow_update": (c_int, [c_void_p, c_void_p]),
     "vbt_overlay_follow_status": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_void_p]),

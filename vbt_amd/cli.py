@@ -2,7 +2,7 @@
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
-                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass]
+                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
       import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it;
@@ -34,6 +34,12 @@
       detected, tracked, drawn from the tracker's row log on the device (include/vbt_hip.h, "Following a device row log") and written,
       instead of a second pass over the clip after it.  The same files, byte for byte.  Not with --hud (the panel shows the analysed
       clip) and not with --concurrent above 1.
+      --live_hud (with --one_pass --video_dir): the rep panel of --hud fed by the live rep analysis on the device (include/vbt_hip.h,
+      "Rep panel from the live analysis"): rep count, ROM and ACV appear on the exported video as each rep completes, with nothing
+      copied to the host.  Every frame of a batch (--time_batch) shows the leading id's reps as they stand after that batch; the
+      last batch shows what `analyze` prints.  Unlike --hud the count can go down again (the leading id changes, or a larger rep
+      makes the filter drop small ones).  Takes --plate_diameter, --hud_scale and --hud_pos; not with --hud, not with --concurrent
+      above 1.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
                               [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync]
                               [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
@@ -210,15 +216,30 @@ def _raw_size(pix_fmt, size):
 @click.option("--one_pass", is_flag=True, default=False,
               help="Draw and write each batch of frames right after it is tracked, from the tracker's row log on the GPU, instead of in a second pass "
                    "over the clip (needs --video_dir; same files; not with --hud or --concurrent above 1).")
+@click.option("--live_hud", is_flag=True, default=False,
+              help="With --one_pass: the rep panel fed by the live rep analysis on the GPU - the reps appear on the video as they complete "
+                   "(uses --plate_diameter, --hud_scale, --hud_pos; not with --hud or --concurrent above 1).")
 @_hud_options
 def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality,
-          mjpeg_entropy, one_pass, hud, plate_diameter, hud_scale, hud_pos):
+          mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos):
+    from ._lib import VbtArgError
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
     fps_given = _fps_given()
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
+    hud_live = None
+    if live_hud:
+        if hud:
+            raise click.UsageError("--live_hud and --hud are two different panels (the reps so far / the finished analysis): give one of them")
+        if video_dir is None:
+            raise click.UsageError("--live_hud draws on the exported frames: give --video_dir")
+        if not one_pass:
+            raise click.UsageError("--live_hud draws while the clip is tracked: give --one_pass")
+        if concurrent > 1:
+            raise click.UsageError("--live_hud works with --concurrent 1 only")
+        hud_live = dict(_hud_params(True, video_dir, hud_scale, hud_pos), plate_diameter=plate_diameter)
     if one_pass:
         if video_dir is None:
             raise click.UsageError("--one_pass is a way to write the exported frames: give --video_dir")
@@ -242,18 +263,38 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
             _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params)
             click.echo(line)
             continue
+        if hud_live is not None:
+            _check_live_hud_fits(frames, pix_fmt, hud_live)                # before any output file exists
         mjpeg = video_dir is not None and video_format == "mjpeg"
         video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
         with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
-            data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink, video_quality=video_quality,
-                                one_pass=one_pass)
+            try:
+                data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
+                                    live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink,
+                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live)
+            except VbtArgError as e:                                     # a panel the library refuses (outside the frame, odd origin in a YUV frame)
+                if hud_live is None or "vbt_overlay_hud_follow" not in str(e):
+                    raise
+                raise click.UsageError(f"--live_hud: {e}")
         _video_done(video)
         if not data["id"]:
             click.echo(f"{s}: no tracked rows")
             continue
         df, best, path = export_dataframe(data, s, model, df_dir=df_dir, write=df_dir is not None)
         click.echo(f"{s}: {len(df)} rows, {df['id'].nunique()} ids, export id {best}" + (f" -> {path}" if df_dir is not None else ""))
+
+
+def _check_live_hud_fits(frames, pix_fmt, hud_live):
+    """--live_hud: the panel the library would refuse for this source (vbt_overlay_hud_follow: outside the frame, odd origin in a YUV
+    frame) is a usage error here, while nothing has been written yet"""
+    from .rawvideo import is_yuv, source_hw
+    H, W = source_hw(frames, pix_fmt)
+    x, y, s = hud_live["x"], hud_live["y"], hud_live["scale"]
+    if is_yuv(pix_fmt) and (x | y) & 1:
+        raise click.UsageError(f"--live_hud: a {pix_fmt} panel starts at even coordinates, got --hud_pos {x},{y}")
+    if x + 52 * s > W or y + 50 * s > H:
+        raise click.UsageError(f"--live_hud: the {52 * s} x {50 * s} panel at ({x}, {y}) does not lie inside the {W} x {H} frame "
+                               "(--hud_scale, --hud_pos)")
 
 
 def _export_line(data, s, model, df_dir, plate_diameter=None):

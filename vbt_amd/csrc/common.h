@@ -70,6 +70,15 @@ int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips);
 int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
                         unsigned char* head, void* out_rows, hipStream_t st);
 
+// The pipeline's side of a rep panel that follows the live analysis (overlay.hip; vbt_pipeline_overlay_draw is their one caller).
+// Does the handle's panel follow a clip of tracker t?
+bool overlay_hud_follows(const vbt_overlay* o, const vbt_tracker* t);
+// The handle's vbt_overlay_hud_follow_update, with its vbt_overlay_hud_follow_flush setting, on T - the stream the tracker's launches
+// are ordered on - behind the handle's previous pipeline draw (one event wait, none before the first draw).  Enqueue only.
+int overlay_hud_follow_enqueue(vbt_overlay* o, hipStream_t T);
+// The draw just enqueued on `stream` reads the handle's table: the next overlay_hud_follow_enqueue waits for it
+int overlay_hud_follow_drawn(vbt_overlay* o, hipStream_t stream);
+
 // ---- VBTM container records, reader + validator, plan-file reader: container_parse.h (pure C++, also built host-only under
 // -fsanitize=address,undefined by tests/test_parser_fuzz.py) ----
 // Integer parameters of an int8 ADD exactly as XNNPACK derives them (xnn_create_add_nd_qs8 +

@@ -12,19 +12,22 @@
 //   overlay_hud_kernel, once more per vbt_overlay_draw when vbt_overlay_set_hud set a rep panel: grid (tile of the panel, frame of the
 //     batch), one thread per 2 x 2 pixel quad - the chroma sample and its four lumas have one owner, and so has every RGB24 byte.
 //     The panel is a gather in two colours: every pixel of its rectangle is tested against the contract and written once.
+//   overlay_hud_follow_kernel, once per vbt_overlay_hud_follow_update (the panel follows the live rep analysis of a tracker's clip):
+//     one wavefront forms the panel's table from the leader's phase list in the live tables - the records vbt_overlay_set_hud
+//     forms on the host, by the same statements (overlay_core.h) - and leaves the phase count in device memory for the panel kernel.
 // Nothing reads a pixel and nothing passes over a frame: a workgroup walks its primitive clipped to the frame, or its tile of the
 // panel (overlay_core.h).
 #include <algorithm>
 
 #include "common.h"
 #include "overlay_core.h"
+#include "tracker_host.h"
 
 namespace vbt {
 
 constexpr int OV_THREADS = 256;
 constexpr int OV_SEG_LANES = 16;                                  // lanes per trail segment
 constexpr int OV_SEGS_PER_BLOCK = OV_THREADS / OV_SEG_LANES;
-constexpr int OV_MAX_FRAME = 1 << 24;                             // the frame index is dense: 64 MB at most
 constexpr int OV_HUD_TILE_X = 32, OV_HUD_TILE_Y = OV_THREADS / OV_HUD_TILE_X;   // quads of a workgroup: a row of a wavefront's stores is contiguous
 constexpr int OV_HUD_MAX_PHASES = 65536;
 
@@ -44,6 +47,7 @@ struct OverlayDrawArgs {
 
 struct OverlayHudArgs {
   const int32_t* tab;      // [P][OV_HUD_REC]
+  const int32_t* P_dev;    // a panel that follows the live analysis (else NULL): P is read here
   uint8_t* frames;
   size_t frame_bytes;
   int P, frame0, frame_step, tiles_x;
@@ -196,12 +200,71 @@ __global__ __launch_bounds__(64) void overlay_follow_kernel(OvFollow F, const in
   }
 }
 
+// What a panel that follows the live analysis owns (vbt_overlay_hud_follow), all in one allocation
+struct OvHudFollow {
+  int32_t* tab;      // [cap][OV_HUD_REC]
+  int32_t* state;    // [OV_HUD_STATE]
+  double* view;      // [cap][6]: the leader's phase list as the update sees it (the flush view appends to it)
+  double fps;
+  int cap, clip;     // cap = the tracker's phase_cap
+};
+
+// The panel's table from the live tables: the leader of the clip, its entry, its phase list (live_view: the poll's statements, into the
+// handle's own scratch), then one lane per phase in strides of 64 - the record of ov_hud_follow_table, whose running concentric
+// count is a prefix sum over the lanes carried from stride to stride.  A flag leaves P = 0: records already stored are never read.
+__global__ __launch_bounds__(64) void overlay_hud_follow_kernel(OvHudFollow F, LiveBufs b, LiveCfg c, int flush) {
+  __shared__ int s_e, s_n, s_flags;
+  const int lane = threadIdx.x, clip = F.clip;
+  const LiveClip& L = b.clips[clip];
+  const LiveEntry* E = b.ents + (size_t)clip * LIVE_ENTRIES;
+  const long long ld = L.leader;
+  if (lane == 0) { s_e = -1; s_flags = L.flags; s_n = 0; }
+  __syncthreads();
+  if (ld >= 0 && E[lane].id == ld) s_e = lane;
+  if (lane == 0 && ld >= 0 && E[64].id == ld) s_e = 64;
+  __syncthreads();
+  const int e = s_e;
+  int n = 0;
+  if (e >= 0) n = live_view(E[e], b, c, clip, e, flush != 0, F.view, &s_n, &s_flags, lane);
+  else if (lane == 0 && ld >= 0) s_flags |= LIVE_ROWS_LOST;   // the leader's rows are not in the log
+  __syncthreads();
+  int flags = s_flags ? VBT_OVERLAY_HUD_FOLLOW_FLAGGED : 0;
+  if (flags) n = 0;                                             // (the poll reports no phases then)
+  if (n > F.cap) { flags |= VBT_OVERLAY_HUD_FOLLOW_CAPACITY; n = 0; }
+  int carry = 0;
+  bool bad = false;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    const bool in = i < n;
+    int32_t t[OV_HUD_REC] = {0, 0, 0, 0, 0, 0};
+    bool ok = false;
+    if (in) {
+      const double* r = F.view + (size_t)i * 6;
+      ok = ov_hud_phase_check(r, i > 0 ? r - 6 : nullptr) == OV_HUD_PHASE_OK && ov_hud_phase_record(r, F.fps, t) == OV_HUD_PHASE_OK;
+    }
+    const unsigned long long conc = __ballot(ok && t[OV_HUD_TYPE] == 0);
+    t[OV_HUD_COUNT] = carry + __popcll(conc & ((2ull << lane) - 1ull));     // concentric phases among phases 0 .. i
+    carry += __popcll(conc);
+    if (ok) {
+#pragma unroll
+      for (int k = 0; k < OV_HUD_REC; k++) F.tab[(size_t)i * OV_HUD_REC + k] = t[k];
+    }
+    bad = bad || (in && !ok);
+  }
+  if (__ballot(bad)) { flags |= VBT_OVERLAY_HUD_FOLLOW_BAD_PHASE; n = 0; }
+  if (lane == 0) {
+    F.state[OV_HUD_STATE_P] = n;
+    if (flags) F.state[OV_HUD_STATE_FLAGS] |= flags;
+    *(long long*)(F.state + OV_HUD_STATE_LEADER) = ld;
+  }
+}
+
 // The panel lies wholly inside the frame (vbt_overlay_set_hud refuses any other, and the handle's H and W never change) and, for the
 // YUV formats, starts at even coordinates: no store here needs a test against the frame, and a quad is exactly one chroma sample.
 __global__ __launch_bounds__(OV_THREADS) void overlay_hud_kernel(OverlayHudArgs A) {
   __shared__ OvHudState st;
   const int64_t f = (int64_t)A.frame0 + (int64_t)blockIdx.y * A.frame_step;
-  if (threadIdx.x < OV_HUD_PARTS) ov_hud_state_part(A.tab, A.P, f, A.frame_step, A.s, A.full_scale_cm, (int)threadIdx.x, st);
+  if (threadIdx.x < OV_HUD_PARTS) ov_hud_state_part(A.tab, A.P_dev ? *A.P_dev : A.P, f, A.frame_step, A.s, A.full_scale_cm, (int)threadIdx.x, st);
   __syncthreads();
   const int qx = (int)(blockIdx.x % A.tiles_x) * OV_HUD_TILE_X + (int)threadIdx.x % OV_HUD_TILE_X;
   const int qy = (int)(blockIdx.x / A.tiles_x) * OV_HUD_TILE_Y + (int)threadIdx.x / OV_HUD_TILE_X;
@@ -270,7 +333,14 @@ struct vbt_overlay {
   vbt_overlay_hud_params hud_prm{};
   uint8_t b0 = 0, b1 = 0, b2 = 0;        // the panel's background in the frames' format
   int hud_P = 0;
-  int32_t* d_hud = nullptr;              // [hud_P][OV_HUD_REC], an allocation of its own
+  int32_t* d_hud = nullptr;              // [hud_P][OV_HUD_REC], an allocation of its own (hud_follow: HF.tab, inside hud_follow_blob)
+  bool hud_follow = false;               // the panel follows the live analysis (vbt_overlay_hud_follow): hud is set too
+  OvHudFollow HF{};
+  vbt_tracker* hud_trk = nullptr;        // the followed tracker (borrowed)
+  uint8_t* hud_follow_blob = nullptr;    // table | state | view in one allocation
+  int hud_flush = 0;                     // flush_view of the updates vbt_pipeline_overlay_draw makes
+  hipEvent_t ev_hud_drawn = nullptr;     // behind the last draw vbt_pipeline_overlay_draw enqueued: its next update waits for it
+  bool hud_drawn = false;
 };
 
 namespace {
@@ -303,7 +373,31 @@ void overlay_colour(int fmt, const uint8_t* rgb, uint8_t* c) {
   c[2] = (uint8_t)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
 }
 
-// the refusals of vbt_overlay_set_hud that need no handle and no device; on VBT_OK `tab` is the table to upload
+// the refusals on a panel's parameters alone (`who`: vbt_overlay_set_hud or vbt_overlay_hud_follow)
+int check_hud_panel(const char* who, const vbt_overlay_hud_params* prm) {
+  if (prm->scale < 1 || prm->scale > 64) { set_error("%s: scale %d outside 1..64", who, prm->scale); return VBT_ERR_ARG; }
+  if (prm->full_scale_cm < 1 || prm->full_scale_cm > 100000) { set_error("%s: full_scale_cm %d outside 1..100000", who, prm->full_scale_cm); return VBT_ERR_ARG; }
+  if (prm->x < 0 || prm->y < 0) { set_error("%s: negative panel origin (%d, %d)", who, prm->x, prm->y); return VBT_ERR_ARG; }
+  return VBT_OK;
+}
+
+// ... and on the panel's place in the handle's frames
+int check_hud_geometry(const char* who, const vbt_overlay* o, const vbt_overlay_hud_params* params) {
+  const bool yuv = o->fmt != VBT_PIX_RGB24;
+  if (yuv && ((params->x | params->y) & 1)) {
+    set_error("%s: a YUV 4:2:0 panel starts at even coordinates, got (%d, %d)", who, params->x, params->y);
+    return VBT_ERR_ARG;
+  }
+  if ((long)params->x + OV_HUD_CELLS_X * params->scale > o->W || (long)params->y + OV_HUD_CELLS_Y * params->scale > o->H) {
+    set_error("%s: the %d x %d panel at (%d, %d) does not lie inside the %d x %d frame", who, OV_HUD_CELLS_X * params->scale,
+              OV_HUD_CELLS_Y * params->scale, params->x, params->y, o->W, o->H);
+    return VBT_ERR_ARG;
+  }
+  return VBT_OK;
+}
+
+// the refusals of vbt_overlay_set_hud that need no handle and no device; on VBT_OK `tab` is the table to upload.  The tests on a
+// phase and its record are overlay_core.h's, shared with overlay_hud_follow_kernel.
 int check_hud(const vbt_overlay_hud_params* prm, const double* ph, int P, double fps, std::vector<int32_t>& tab) {
   if (P < 0 || (P > 0 && (!ph || !prm))) {
     set_error("vbt_overlay_set_hud: bad argument (P %d, phases %p, params %p)", P, (const void*)ph, (const void*)prm);
@@ -312,28 +406,22 @@ int check_hud(const vbt_overlay_hud_params* prm, const double* ph, int P, double
   if (!(fps > 0) || !std::isfinite(fps)) { set_error("vbt_overlay_set_hud: fps must be positive and finite, got %g", fps); return VBT_ERR_ARG; }
   for (int i = 0; i < P; i++) {
     const double* r = ph + (size_t)i * 6;
-    for (int k = 0; k < 6; k++)
-      if (!std::isfinite(r[k])) { set_error("vbt_overlay_set_hud: phase %d holds a non-finite value", i); return VBT_ERR_ARG; }
-    if (r[5] != 0.0 && r[5] != 1.0 && r[5] != 2.0) { set_error("vbt_overlay_set_hud: phase %d has type %g, not 0, 1 or 2", i, r[5]); return VBT_ERR_ARG; }
-    if (r[1] < r[0]) { set_error("vbt_overlay_set_hud: phase %d ends before it starts (time_end < time_start)", i); return VBT_ERR_ARG; }
-    if (i > 0 && (r[0] < r[-6] || r[1] < r[-5])) { set_error("vbt_overlay_set_hud: phases are not ordered in time at phase %d", i); return VBT_ERR_ARG; }
+    switch (ov_hud_phase_check(r, i > 0 ? r - 6 : nullptr)) {
+      case OV_HUD_PHASE_NONFINITE: set_error("vbt_overlay_set_hud: phase %d holds a non-finite value", i); return VBT_ERR_ARG;
+      case OV_HUD_PHASE_TYPE: set_error("vbt_overlay_set_hud: phase %d has type %g, not 0, 1 or 2", i, r[5]); return VBT_ERR_ARG;
+      case OV_HUD_PHASE_ENDS_BEFORE: set_error("vbt_overlay_set_hud: phase %d ends before it starts (time_end < time_start)", i); return VBT_ERR_ARG;
+      case OV_HUD_PHASE_ORDER: set_error("vbt_overlay_set_hud: phases are not ordered in time at phase %d", i); return VBT_ERR_ARG;
+      default: break;
+    }
   }
-  if (prm->scale < 1 || prm->scale > 64) { set_error("vbt_overlay_set_hud: scale %d outside 1..64", prm->scale); return VBT_ERR_ARG; }
-  if (prm->full_scale_cm < 1 || prm->full_scale_cm > 100000) { set_error("vbt_overlay_set_hud: full_scale_cm %d outside 1..100000", prm->full_scale_cm); return VBT_ERR_ARG; }
-  if (prm->x < 0 || prm->y < 0) { set_error("vbt_overlay_set_hud: negative panel origin (%d, %d)", prm->x, prm->y); return VBT_ERR_ARG; }
+  if (int rc = check_hud_panel("vbt_overlay_set_hud", prm)) return rc;
   if (P > OV_HUD_MAX_PHASES) { set_error("vbt_overlay_set_hud: %d phases, above %d", P, OV_HUD_MAX_PHASES); return VBT_ERR_CAPACITY; }
   tab.assign((size_t)P * OV_HUD_REC, 0);
   int count = 0;
   for (int i = 0; i < P; i++) {
     const double* r = ph + (size_t)i * 6;
     int32_t* t = tab.data() + (size_t)i * OV_HUD_REC;
-    t[OV_HUD_FS] = ov_frame_number(r[0], fps);
-    t[OV_HUD_FE] = ov_frame_number(r[1], fps);
-    if (t[OV_HUD_FE] > OV_MAX_FRAME) { set_error("vbt_overlay_set_hud: phase %d ends at frame %d, above %d", i, t[OV_HUD_FE], OV_MAX_FRAME); return VBT_ERR_CAPACITY; }
-    const double dur = r[1] - r[0];
-    t[OV_HUD_ROM] = ov_centi(r[4]);
-    t[OV_HUD_ACV] = dur > 0 ? ov_centi(r[4] / dur) : 0;
-    t[OV_HUD_TYPE] = (int32_t)r[5];
+    if (ov_hud_phase_record(r, fps, t)) { set_error("vbt_overlay_set_hud: phase %d ends at frame %d, above %d", i, t[OV_HUD_FE], (int)OV_MAX_FRAME); return VBT_ERR_CAPACITY; }
     count += t[OV_HUD_TYPE] == 0;
     t[OV_HUD_COUNT] = count;
   }
@@ -364,6 +452,13 @@ void overlay_launch_rows(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0,
 }
 
 void overlay_free_hud(vbt_overlay* o) {
+  if (o->hud_follow) {                     // the table is part of the follow allocation
+    if (o->hud_follow_blob) (void)hipFree(o->hud_follow_blob);   // (waits for the updates and draws still using it)
+    if (o->ev_hud_drawn) (void)hipEventDestroy(o->ev_hud_drawn);
+    o->hud_follow_blob = nullptr; o->ev_hud_drawn = nullptr; o->hud_drawn = false;
+    o->hud_follow = false; o->HF = OvHudFollow{}; o->hud_trk = nullptr; o->hud_flush = 0;
+    o->d_hud = nullptr;
+  }
   if (o->d_hud) (void)hipFree(o->d_hud);   // (waits for the draws still reading it)
   o->d_hud = nullptr; o->hud_P = 0; o->hud = false;
 }
@@ -483,7 +578,7 @@ int vbt_overlay_draw(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int
   if (o->hud) {                                                   // after the rows, on the same stream: the panel wins
     const vbt_overlay_hud_params& hp = o->hud_prm;
     OverlayHudArgs G{};
-    G.tab = o->d_hud; G.frame_bytes = o->frame_bytes; G.P = o->hud_P; G.frame_step = frame_step;
+    G.tab = o->d_hud; G.P_dev = o->hud_follow ? o->HF.state + OV_HUD_STATE_P : nullptr; G.frame_bytes = o->frame_bytes; G.P = o->hud_P; G.frame_step = frame_step;
     G.H = o->H; G.W = o->W; G.fmt = o->fmt; G.X = hp.x; G.Y = hp.y; G.s = hp.scale; G.full_scale_cm = hp.full_scale_cm;
     G.fg[0] = o->c0; G.fg[1] = o->c1; G.fg[2] = o->c2; G.bg[0] = o->b0; G.bg[1] = o->b1; G.bg[2] = o->b2;
     G.pairs = o->fmt != VBT_PIX_RGB24 && ((uintptr_t)frames_dev & 1) == 0;        // (a YUV frame has an even number of bytes)
@@ -572,16 +667,7 @@ int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, co
   std::vector<int32_t> tab;
   if (int rc = check_hud(params, phases6_host, P, fps, tab)) return rc;
   if (!o) { set_error("vbt_overlay_set_hud: handle is NULL"); return VBT_ERR_ARG; }
-  const bool yuv = o->fmt != VBT_PIX_RGB24;
-  if (yuv && ((params->x | params->y) & 1)) {
-    set_error("vbt_overlay_set_hud: a YUV 4:2:0 panel starts at even coordinates, got (%d, %d)", params->x, params->y);
-    return VBT_ERR_ARG;
-  }
-  if ((long)params->x + OV_HUD_CELLS_X * params->scale > o->W || (long)params->y + OV_HUD_CELLS_Y * params->scale > o->H) {
-    set_error("vbt_overlay_set_hud: the %d x %d panel at (%d, %d) does not lie inside the %d x %d frame", OV_HUD_CELLS_X * params->scale,
-              OV_HUD_CELLS_Y * params->scale, params->x, params->y, o->W, o->H);
-    return VBT_ERR_ARG;
-  }
+  if (int rc = check_hud_geometry("vbt_overlay_set_hud", o, params)) return rc;
   VBT_HIP_CHECK(hipSetDevice(o->device));
   int32_t* d = nullptr;
   if (P > 0) {
@@ -605,11 +691,91 @@ int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, co
 
 int vbt_overlay_hud_table(vbt_overlay* o, int32_t* out, int cap, int* P) {
   if (!o || !P || cap < 0 || (cap > 0 && !out)) { set_error("vbt_overlay_hud_table: bad argument"); return VBT_ERR_ARG; }
-  *P = o->hud_P;
-  if (cap < o->hud_P) { set_error("vbt_overlay_hud_table: %d phases, room for %d", o->hud_P, cap); return VBT_ERR_CAPACITY; }
-  if (o->hud_P == 0) return VBT_OK;
+  int n = o->hud_P;
+  if (o->hud_follow) {                                              // the count of the last update
+    VBT_HIP_CHECK(hipSetDevice(o->device));
+    int32_t st[OV_HUD_STATE];
+    VBT_HIP_CHECK(hipMemcpy(st, o->HF.state, sizeof(st), hipMemcpyDeviceToHost));
+    n = st[OV_HUD_STATE_P];
+  }
+  *P = n;
+  if (cap < n) { set_error("vbt_overlay_hud_table: %d phases, room for %d", n, cap); return VBT_ERR_CAPACITY; }
+  if (n == 0) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(o->device));
-  VBT_HIP_CHECK(hipMemcpy(out, o->d_hud, (size_t)o->hud_P * OV_HUD_REC * 4, hipMemcpyDeviceToHost));
+  VBT_HIP_CHECK(hipMemcpy(out, o->d_hud, (size_t)n * OV_HUD_REC * 4, hipMemcpyDeviceToHost));
+  return VBT_OK;
+}
+
+int vbt_overlay_hud_follow(vbt_overlay* o, const vbt_overlay_hud_params* params, vbt_tracker* t, int clip, double fps) {
+  const char* who = "vbt_overlay_hud_follow";
+  if (!params) { set_error("%s: params is NULL", who); return VBT_ERR_ARG; }
+  if (!(fps > 0) || !std::isfinite(fps)) { set_error("%s: fps must be positive and finite, got %g", who, fps); return VBT_ERR_ARG; }
+  if (int rc = check_hud_panel(who, params)) return rc;
+  if (!o) { set_error("%s: handle is NULL", who); return VBT_ERR_ARG; }
+  if (!t) { set_error("%s: tracker is NULL", who); return VBT_ERR_ARG; }
+  const LiveTables lt = live_tables(t);
+  if (clip < 0 || clip >= lt.n_clips) { set_error("%s: clip %d outside the tracker's %d clips", who, clip, lt.n_clips); return VBT_ERR_ARG; }
+  if (int rc = check_hud_geometry(who, o, params)) return rc;
+  if (!lt.on) { set_error("%s: live analysis is not enabled on the tracker (vbt_tracker_live_enable)", who); return VBT_ERR_STATE; }
+  if (lt.device != o->device) { set_error("%s: the tracker is on device %d, the handle on device %d", who, lt.device, o->device); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  const int cap = lt.c.phase_cap;
+  const size_t tab_b = (size_t)cap * OV_HUD_REC * 4, state_b = OV_HUD_STATE * 4, view_b = (size_t)cap * 6 * sizeof(double);   // (tab_b is a multiple of 8)
+  uint8_t* blob = nullptr;
+  hipEvent_t ev = nullptr;
+  VBT_HIP_CHECK(hipMalloc((void**)&blob, tab_b + state_b + view_b));
+  hipError_t e = hipMemsetAsync(blob, 0, tab_b + state_b + view_b, nullptr);
+  if (e == hipSuccess) e = hipMemsetAsync(blob + tab_b + OV_HUD_STATE_LEADER * 4, 0xff, 8, nullptr);   // leader -1, P = 0: blank until the first update
+  const hipError_t es = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    (void)hipFree(blob);
+    set_error("%s failed: %s", who, hipGetErrorString(e));
+    return VBT_ERR_HIP;
+  }
+  overlay_free_hud(o);
+  o->HF.tab = (int32_t*)blob; o->HF.state = (int32_t*)(blob + tab_b); o->HF.view = (double*)(blob + tab_b + state_b);
+  o->HF.fps = fps; o->HF.cap = cap; o->HF.clip = clip;
+  o->hud_follow_blob = blob; o->ev_hud_drawn = ev; o->hud_drawn = false; o->hud_trk = t; o->hud_flush = 0;
+  o->d_hud = o->HF.tab; o->hud_P = 0; o->hud = true; o->hud_follow = true; o->hud_prm = *params;
+  uint8_t c[3];
+  overlay_colour(o->fmt, params->bg, c);
+  o->b0 = c[0]; o->b1 = c[1]; o->b2 = c[2];
+  return VBT_OK;
+}
+
+int vbt_overlay_hud_follow_update(vbt_overlay* o, int flush_view, void* stream) {
+  if (!o) { set_error("vbt_overlay_hud_follow_update: handle is NULL"); return VBT_ERR_ARG; }
+  if (!o->hud_follow) { set_error("vbt_overlay_hud_follow_update: the handle's panel follows no live analysis (vbt_overlay_hud_follow)"); return VBT_ERR_STATE; }
+  const LiveTables lt = live_tables(o->hud_trk);
+  if (!lt.on || lt.c.phase_cap != o->HF.cap) {                     // (live analysis switched off or enabled anew since the panel was bound)
+    set_error("vbt_overlay_hud_follow_update: the tracker's live analysis is not the one the panel was bound to");
+    return VBT_ERR_STATE;
+  }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  overlay_hud_follow_kernel<<<1, 64, 0, (hipStream_t)stream>>>(o->HF, lt.b, lt.c, flush_view != 0);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+int vbt_overlay_hud_follow_status(vbt_overlay* o, int64_t* leader, int32_t* n_phases, int32_t* flags, void* stream) {
+  if (!o || !leader || !n_phases || !flags) { set_error("vbt_overlay_hud_follow_status: NULL argument"); return VBT_ERR_ARG; }
+  if (!o->hud_follow) { set_error("vbt_overlay_hud_follow_status: the handle's panel follows no live analysis (vbt_overlay_hud_follow)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(o->device));
+  int32_t st[OV_HUD_STATE];
+  VBT_HIP_CHECK(hipMemcpyAsync(st, o->HF.state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  *n_phases = st[OV_HUD_STATE_P];
+  *flags = st[OV_HUD_STATE_FLAGS];
+  memcpy(leader, st + OV_HUD_STATE_LEADER, 8);
+  return VBT_OK;
+}
+
+int vbt_overlay_hud_follow_flush(vbt_overlay* o, int flush_view) {
+  if (!o) { set_error("vbt_overlay_hud_follow_flush: handle is NULL"); return VBT_ERR_ARG; }
+  if (!o->hud_follow) { set_error("vbt_overlay_hud_follow_flush: the handle's panel follows no live analysis (vbt_overlay_hud_follow)"); return VBT_ERR_STATE; }
+  o->hud_flush = flush_view != 0;
   return VBT_OK;
 }
 
@@ -633,3 +799,20 @@ int vbt_overlay_geometry(vbt_overlay* o, int32_t* out, int cap, int* n) {
 }
 
 }  // extern "C"
+
+namespace vbt {
+
+bool overlay_hud_follows(const vbt_overlay* o, const vbt_tracker* t) { return o && o->hud_follow && o->hud_trk == t; }
+
+int overlay_hud_follow_enqueue(vbt_overlay* o, hipStream_t T) {
+  if (o->hud_drawn) VBT_HIP_CHECK(hipStreamWaitEvent(T, o->ev_hud_drawn, 0));
+  return vbt_overlay_hud_follow_update(o, o->hud_flush, (void*)T);
+}
+
+int overlay_hud_follow_drawn(vbt_overlay* o, hipStream_t stream) {
+  VBT_HIP_CHECK(hipEventRecord(o->ev_hud_drawn, stream));
+  o->hud_drawn = true;
+  return VBT_OK;
+}
+
+}  // namespace vbt

@@ -320,6 +320,58 @@ __host__ __device__ inline int32_t ov_centi(double v) {
   return (int32_t)llrint(c < 9999.0 ? c : 9999.0);
 }
 
+// The record of one phase (time_start, time_end, y_start, y_end, rom, type), for vbt_overlay_set_hud on the host and for
+// overlay_hud_follow_kernel on the device: both tables come from these statements.  IEEE double without contraction: one multiply
+// before llrint (ov_frame_number, ov_centi), one divide.
+enum { OV_MAX_FRAME = 1 << 24 };                                  // the frame index is dense: 64 MB at most
+enum { OV_HUD_PHASE_OK = 0, OV_HUD_PHASE_NONFINITE, OV_HUD_PHASE_TYPE, OV_HUD_PHASE_ENDS_BEFORE, OV_HUD_PHASE_ORDER, OV_HUD_PHASE_FRAME };
+
+// What vbt_overlay_set_hud refuses a phase for on its doubles, the first that holds in its order of tests; prev = the phase before
+// it in the table (NULL: it is the first)
+__host__ __device__ inline int ov_hud_phase_check(const double* r, const double* prev) {
+  for (int k = 0; k < 6; k++)
+    if (!ov_finite(r[k])) return OV_HUD_PHASE_NONFINITE;
+  if (r[5] != 0.0 && r[5] != 1.0 && r[5] != 2.0) return OV_HUD_PHASE_TYPE;
+  if (r[1] < r[0]) return OV_HUD_PHASE_ENDS_BEFORE;
+  if (prev && (r[0] < prev[0] || r[1] < prev[1])) return OV_HUD_PHASE_ORDER;
+  return OV_HUD_PHASE_OK;
+}
+
+// t[OV_HUD_FS .. OV_HUD_TYPE] of a phase that passed ov_hud_phase_check (its doubles are finite: every cast is defined); returns
+// OV_HUD_PHASE_FRAME when it ends above frame 2^24.  t[OV_HUD_COUNT] is the caller's: it needs the phases before this one.
+__host__ __device__ inline int ov_hud_phase_record(const double* r, double fps, int32_t* t) {
+  t[OV_HUD_FS] = ov_frame_number(r[0], fps);
+  t[OV_HUD_FE] = ov_frame_number(r[1], fps);
+  if (t[OV_HUD_FE] > OV_MAX_FRAME) return OV_HUD_PHASE_FRAME;
+  const double dur = r[1] - r[0];
+  t[OV_HUD_ROM] = ov_centi(r[4]);
+  t[OV_HUD_ACV] = dur > 0 ? ov_centi(r[4] / dur) : 0;
+  t[OV_HUD_TYPE] = (int32_t)r[5];
+  return OV_HUD_PHASE_OK;
+}
+
+// The panel's table from a phase list no longer than `cap`, in table order: the STATEMENT of what overlay_hud_follow_kernel forms 64
+// phases at a time.  Returns the number of records (0 with a flag) and ORs VBT_OVERLAY_HUD_FOLLOW_BAD_PHASE / _CAPACITY into *flags.
+// The library itself does not call it: the kernel restates this loop with ballots (the running count as a prefix sum over the lanes,
+// carried from stride to stride), so the host program that runs this under sanitizers (tests/fuzz/overlay_hud_follow_check.cc)
+// proves ov_hud_phase_check / ov_hud_phase_record and this loop, not the kernel's carry - that is the GPU tests'
+// (tests/test_gpu_overlay_hud_live.py, with a leader of more than 128 phases for the strides).
+__host__ __device__ inline int ov_hud_follow_table(const double* ph, int n, int cap, double fps, int32_t* tab, int* flags) {
+  if (n > cap) { *flags |= VBT_OVERLAY_HUD_FOLLOW_CAPACITY; return 0; }
+  int count = 0;
+  for (int i = 0; i < n; i++) {
+    const double* r = ph + (size_t)i * 6;
+    int32_t* t = tab + (size_t)i * OV_HUD_REC;
+    if (ov_hud_phase_check(r, i > 0 ? r - 6 : nullptr) || ov_hud_phase_record(r, fps, t)) { *flags |= VBT_OVERLAY_HUD_FOLLOW_BAD_PHASE; return 0; }
+    count += t[OV_HUD_TYPE] == 0;
+    t[OV_HUD_COUNT] = count;
+  }
+  return n;
+}
+
+// state of a panel that follows the live analysis (vbt_overlay_hud_follow): phases in the table, sticky flags, the leader (int64)
+enum { OV_HUD_STATE_P = 0, OV_HUD_STATE_FLAGS = 1, OV_HUD_STATE_LEADER = 2, OV_HUD_STATE = 4 };
+
 // first i of [lo, hi) with tab[i][col] >= v, hi if there is none; the column does not decrease along the table
 __host__ __device__ inline int ov_hud_lower_bound(const int32_t* tab, int lo, int hi, int col, int64_t v) {
   while (lo < hi) {

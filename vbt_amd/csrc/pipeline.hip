@@ -1142,9 +1142,22 @@ int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_d
   if (!p || !o) { set_error("vbt_pipeline_overlay_draw: NULL %s", p ? "overlay" : "pipeline"); return VBT_ERR_ARG; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
+  // A panel that follows this tracker's live analysis: its update reads tables the NEXT tracker launch changes in place, and writes
+  // the table the handle's previous draw may still read.  It runs on the tracker stream, which drain() has put behind the last
+  // tracker launch in every placement, after an event behind that draw; ev_trk[last_trk] is recorded again behind it, so `stream`
+  // (below) and every later tracker launch (each waits for ev_trk[last_trk], or runs on the tracker stream) come after the update.
+  const bool panel = overlay_hud_follows(o, p->trk);
+  if (panel) {
+    PL_CHECK(overlay_hud_follow_enqueue(o, p->trk_stream));
+    const int e = p->last_trk >= 0 ? p->last_trk : 0;
+    VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e], p->trk_stream));
+    p->last_trk = e;
+  }
   if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, p->ev_trk[p->last_trk], 0));
   PL_CHECK(vbt_overlay_follow_update(o, stream));
-  return vbt_overlay_draw(o, frames_dev, B, frame0, frame_step, stream);
+  PL_CHECK(vbt_overlay_draw(o, frames_dev, B, frame0, frame_step, stream));
+  if (panel) PL_CHECK(overlay_hud_follow_drawn(o, (hipStream_t)stream));
+  return VBT_OK;
 }
 
 int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {

@@ -42,6 +42,16 @@ void live_init(vbt_tracker* t);
 // live analysis off, its tables freed
 void live_free(vbt_tracker* t);
 
+// What a reader of the live tables outside the tracker's units needs (the overlay's rep panel, overlay.hip): the tables as the
+// tracker's kernels take them.  on == false: live analysis is not enabled and b holds no pointer.
+struct LiveTables {
+  LiveBufs b;
+  LiveCfg c;
+  int n_clips, device;
+  bool on;
+};
+inline LiveTables live_tables(const vbt_tracker* t) { return LiveTables{t->lb, t->lc, t->n_clips, t->device, t->live}; }
+
 // clips[i0 ...) as the argument of one launch (at most CLIP_LIST of them)
 inline ClipList clip_list(const int32_t* clips, int i0, int n) {
   ClipList l{};

@@ -17,6 +17,8 @@ from .rawvideo import frame_shape, pix_fmt_code, source_hw
 COLUMNS = ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
 HUD_PARAMS = ("x", "y", "scale", "full_scale_cm", "bg")
 FOLLOW_FLAGS = {1: "BAD_ROW", 2: "ORDER", 4: "FRAME_RANGE", 8: "FRAME_FULL", 16: "REWOUND"}     # VBT_OVERLAY_FOLLOW_*
+HUD_FOLLOW_FLAGS = {1: "FLAGGED", 2: "BAD_PHASE", 4: "CAPACITY"}                                   # VBT_OVERLAY_HUD_FOLLOW_*
+HUD_FOLLOW_FLAGGED = 1                                                                             # the one bit that is a warning: the live analysis overflowed
 COLORS = [(252, 3, 115), (255, 255, 255)]          # COLORS of reference track.py:23 (BGR there) as RGB; the reference draws with [1]
 
 
@@ -57,6 +59,7 @@ class Overlay:
         self._h = h
         self.n = 0
         self.hud_n = 0
+        self._hud_tracker = None                   # the tracker a following panel borrows: kept alive with the handle
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -100,24 +103,45 @@ class Overlay:
                 raise TypeError("Overlay.set_hud: no parameters go with phases=None (the panel off)")
             _lib.check(L.vbt_overlay_set_hud(self._h, None, None, 0, 1.0, stream))
             self.hud_n = 0
+            self._hud_tracker = None
             return
         if fps is None:
             raise TypeError("Overlay.set_hud: fps is needed with phases")
-        prm = _lib.OverlayHudParams()
-        L.vbt_overlay_hud_default_params(ctypes.byref(prm))
-        for k, v in hud_params.items():
-            if k == "bg":
-                prm.bg[:] = [int(c) for c in v]
-            elif k in HUD_PARAMS:
-                setattr(prm, k, int(v))
-            else:
-                raise TypeError(f"Overlay.set_hud: unknown parameter {k!r}")
+        prm = _hud_params("Overlay.set_hud", hud_params)
         ph = phases6(phases)
         _lib.check(L.vbt_overlay_set_hud(self._h, ctypes.byref(prm), ph.ctypes.data if len(ph) else None, len(ph), float(fps), stream))
         self.hud_n = len(ph)
+        self._hud_tracker = None
+
+    def hud_follow(self, tracker, clip, fps, **hud_params):
+        """The rep panel from the live rep analysis (include/vbt_hip.h, "Rep panel from the live analysis"): the panel follows clip
+        `clip` of `tracker` (an ocsort.MultiClipTracker with enable_live, or a Pipeline's .tracker) - its table is formed on the device
+        from the leader's phase list by hud_follow_update; nothing visits the host.  Replaces a panel of set_hud; set_hud replaces it.
+        hud_params: as set_hud."""
+        prm = _hud_params("Overlay.hud_follow", hud_params)
+        _lib.check(_lib.lib().vbt_overlay_hud_follow(self._h, ctypes.byref(prm), tracker.handle, int(clip), float(fps)))
+        self._hud_tracker = tracker
+        self.hud_n = int(getattr(tracker, "_live_phase_cap", 0)) or 512          # room for hud_table: the tracker's phase_cap
+
+    def hud_follow_update(self, flush_view=False, stream=None):
+        """the panel's table from the live analysis as it stands (flush_view: as if the clip ended now): one launch on `stream`,
+        enqueue only.  `stream` is ordered behind the tracker launch to show and ahead of the next one (see the header, "Ordering")."""
+        _lib.check(_lib.lib().vbt_overlay_hud_follow_update(self._h, int(bool(flush_view)), stream))
+
+    def hud_follow_flush(self, flush_view):
+        """the flush_view of the update Pipeline.overlay_draw makes for this handle"""
+        _lib.check(_lib.lib().vbt_overlay_hud_follow_flush(self._h, int(bool(flush_view))))
+
+    def hud_follow_status(self, stream=None):
+        """(leader, phases in the table, VBT_OVERLAY_HUD_FOLLOW_* flags so far) - synchronises `stream`"""
+        leader, n, flags = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.lib().vbt_overlay_hud_follow_status(self._h, ctypes.byref(leader), ctypes.byref(n), ctypes.byref(flags), stream))
+        return leader.value, n.value, flags.value
 
     def hud_table(self):
-        """int32 [P, 6] = fs, fe, rom_cm, acv_cm, type, concentric phases so far, of every phase of the panel (vbt_overlay_hud_table)"""
+        """int32 [P, 6] = fs, fe, rom_cm, acv_cm, type, concentric phases so far, of every phase of the panel (vbt_overlay_hud_table).
+        A following panel: the table of the updates completed so far - synchronise the stream they were enqueued on first, unless it
+        is the null stream."""
         out = np.zeros((max(self.hud_n, 1), 6), np.int32)
         n = ctypes.c_int()
         _lib.check(_lib.lib().vbt_overlay_hud_table(self._h, out.ctypes.data, len(out), ctypes.byref(n)))
@@ -133,6 +157,24 @@ class Overlay:
 
 def follow_flag_names(flags):
     return [name for bit, name in FOLLOW_FLAGS.items() if flags & bit]
+
+
+def hud_follow_flag_names(flags):
+    return [name for bit, name in HUD_FOLLOW_FLAGS.items() if flags & bit]
+
+
+def _hud_params(who, hud_params):
+    """vbt_overlay_hud_params: the defaults with hud_params (x, y, scale, full_scale_cm, bg) over them"""
+    prm = _lib.OverlayHudParams()
+    _lib.lib().vbt_overlay_hud_default_params(ctypes.byref(prm))
+    for k, v in hud_params.items():
+        if k == "bg":
+            prm.bg[:] = [int(c) for c in v]
+        elif k in HUD_PARAMS:
+            setattr(prm, k, int(v))
+        else:
+            raise TypeError(f"{who}: unknown parameter {k!r}")
+    return prm
 
 
 def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, hud=None, hud_params=None,

@@ -65,7 +65,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -81,10 +81,17 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     one_pass (with video_out or video_sink): the export in the same pass as the tracking instead of a second pass over the clip after
     it - each batch of kept frames is uploaded (or decoded) once into a device buffer, detected and tracked from there, drawn in place
     from the tracker's row log on the device (Overlay.follow; the rows never visit the host) and encoded or copied back.  The same
-    bytes and the same rows as without it.  (The rep panel of overlay.render needs the analysed clip: it has no one-pass form.)"""
+    bytes and the same rows as without it.  (The rep panel of overlay.render shows the finished analysis, which needs the whole clip: that panel has no one-pass form;
+    hud_live below is the one that has.)
+    hud_live (with one_pass and an export): a dict - the live rep panel on every exported frame (include/vbt_hip.h, "Rep panel from the
+    live analysis"): live rep analysis is switched on (with or without `live`), the panel follows the clip on the device and shows,
+    on every frame of a batch, the leader's reps as they stand after that batch.  Keys: plate_diameter (default 0.45, the live
+    analysis runs with it) and the panel's x, y, scale, full_scale_cm, bg.  The rows are those of a run without it."""
+    if hud_live is not None and not (one_pass and (video_out is not None or video_sink is not None)):
+        raise ValueError("track_frames: hud_live draws on a one-pass export (one_pass=True with video_out or video_sink)")
     if one_pass and (video_out is not None or video_sink is not None):
         return _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw,
-                             export=(video_out, video_sink, video_quality))
+                             export=(video_out, video_sink, video_quality), hud_live=hud_live)
     data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw)
     if video_out is not None:
         from .overlay import render
@@ -95,8 +102,8 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return data
 
 
-def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None):
-    """export: None, or (video_out, video_sink, video_quality) of a one-pass export"""
+def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None, hud_live=None):
+    """export: None, or (video_out, video_sink, video_quality) of a one-pass export; hud_live: None, or the live rep panel's dict"""
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
     if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
@@ -104,12 +111,14 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
     stride = max(int(frame_stride), 1)
     kept = T // stride                                               # frames that are processed
     F = max(1, min(int(time_batch), max(kept, 1)))
+    hud_live = None if hud_live is None else dict(hud_live)
+    plate = {} if hud_live is None else dict(plate_diameter=float(hud_live.pop("plate_diameter", 0.45)))   # the live analysis uses the pipeline's
     pipe = Pipeline(model_path, F, max_frames=max(kept, 1), fps=fps, detection_treshold=detection_treshold, device=device,
-                    rows_per_frame=25, tracker_clips=1)
+                    rows_per_frame=25, tracker_clips=1, **plate)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
     src_hw = None if (H, W) == (size, size) and not is_yuv(pix_fmt) else (H, W)
-    if live is not None:
+    if live is not None or hud_live is not None:
         pipe.enable_live()
     elif export is None and isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
         return pipe.track_clip(frames, frame_stride=stride, src_hw=src_hw)      # vbt_track_clip: the whole loop inside the library
@@ -129,12 +138,14 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
         dev = [DeviceBuffer(F * fb, device) for _ in range(2)]
     ov = enc = host = None
     if export is not None:
-        from .overlay import Overlay, follow_flag_names
+        from .overlay import HUD_FOLLOW_FLAGGED, Overlay, follow_flag_names, hud_follow_flag_names
         video_out, video_sink, video_quality = export
         if video_out is not None and (tuple(video_out.shape) != (kept,) + shape or video_out.dtype != np.uint8):
             raise ValueError(f"track_frames: video_out must be uint8 {(kept,) + shape}, got {video_out.dtype} {tuple(video_out.shape)}")
         ov = Overlay(H, W, pix_fmt, device=device)
         ov.follow(*pipe.tracker.rows_dev(0), max_frame=max(kept * stride, 1), max_rows_per_frame=25, fps=fps)   # (a frame has at most 25 detections)
+        if hud_live is not None:
+            ov.hud_follow(pipe.tracker, 0, fps, **hud_live)
         if video_sink is not None and kept:
             from .mjpeg import Encoder
             enc = Encoder(H, W, pix_fmt, quality=video_quality, max_batch=F, device=device)
@@ -155,6 +166,8 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
                 _lib.check(L.vbt_memcpy(buf.ptr, chunk.ctypes.data, chunk.nbytes, 0))
             pipe.step_runs(buf.ptr, [(0, 0, len(idx), int(idx[0]) + 1, stride)], stream=0, src_hw=src_hw)
             if ov is not None:
+                if hud_live is not None and i0 + F >= len(idx_all):      # the clip's last batch: its panel is the flush view, the close's phases
+                    ov.hud_follow_flush(True)
                 pipe.overlay_draw(ov, buf.ptr, len(idx), int(idx[0]) + 1, stride, stream=0)
                 if enc is not None:
                     enc.encode(buf.ptr, len(idx))
@@ -176,6 +189,15 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
         if flags:
             raise RuntimeError("track_frames: the one-pass export skipped rows of the tracker's log (VBT_OVERLAY_FOLLOW_" +
                                ", ".join(follow_flag_names(flags)) + "): the exported frames are not those of the two-pass export")
+        if hud_live is not None:
+            _, _, flags = ov.hud_follow_status(0)
+            if flags & ~HUD_FOLLOW_FLAGGED:
+                raise RuntimeError("track_frames: the live rep panel met phases it cannot show (VBT_OVERLAY_HUD_FOLLOW_" +
+                                   ", ".join(hud_follow_flag_names(flags & ~HUD_FOLLOW_FLAGGED)) + "): the panel was blank on those batches")
+            if flags:
+                import warnings
+                warnings.warn("track_frames: the live rep analysis overflowed (VBT_OVERLAY_HUD_FOLLOW_FLAGGED): the live rep panel is blank "
+                              "from that batch on", RuntimeWarning)
     pipe.finish()
     return pipe.rows(0)
 
