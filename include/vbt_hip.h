@@ -756,6 +756,126 @@ int vbt_overlay_follow_status(vbt_overlay* o, int32_t* rows_consumed, int32_t* f
  * stream, events both ways, no host wait).  For every other handle the call enqueues exactly what it did without that. */
 int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_dev, int B, int frame0, int frame_step, void* stream);
 
+/* ------------------------------------------------------------------ Rep figure ----------
+ * The reference's figure (plot.py:87-232) without a plotting library: bar position and velocity of ONE id over time, a tinted span
+ * per phase, ROM and ACV written over every concentric phase.  A figure is a frame: a handle renders N figures of one size - N
+ * tracks, each given as rows and phases - into N contiguous RGB24 frames in device memory, which vbt_mjpeg_encode can take on the
+ * same stream.  As with the rep panel, cv2's and matplotlib's rasterisation is NOT the contract: the contract is the rules below,
+ * stated a second time in numpy (tests/figure_ref.py).  All values are integers once formed; every double is IEEE, one operation
+ * per statement, without contraction (the statements themselves: vbt_amd/csrc/figure_core.h).
+ *
+ * Input per figure.  T rows of 7 doubles (time, x, y, dx, dy, norm_plate_height, norm_plate_width: the columns of vbt_analyze), the
+ * rows of one id sorted by time, and P phases of 6 doubles in the phases6 layout of vbt_overlay_set_hud.  The caller supplies the
+ * phases (the VelocityTracker scan is not run here).
+ * Series.  Four curves: pandas' rolling(5, min_periods=1) means of x, y (upper rectangle) and of dx, dy (lower rectangle), as
+ * plot.py:90-92, computed on the device with the rolling mean of the rep analysis.
+ *
+ * Layout.  A white W x H frame, s = scale, holds two plot rectangles of PW x PH pixels, [X0, X0 + PW) x [Y0, Y0 + PH) above
+ * [X0, X0 + PW) x [Y1, Y1 + PH).  Margins in cells of s pixels: 40 left, 4 right, 11 above the upper rectangle, 13 between the two,
+ * 14 below the lower one:  X0 = 40 s, Y0 = 11 s, PW = W - 44 s, PH = (H - 38 s) / 2 (integer division), Y1 = Y0 + PH + 13 s.
+ * vbt_figure_create refuses a size with PW < 16 or PH < 16.
+ *
+ * Axes.  t0, t1 = the first and last row time.  col(t) = t1 > t0 ? R((t - t0) / (t1 - t0) * (PW - 1)) : 0, where
+ * R(v) = llrint(v) after v is clamped to [-32768, 32768] (a NaN, which only inf / inf can give, goes to -32768).
+ * Position range, m and M the minimum and maximum over both smoothed position series: lo = max(m - 0.2, 0), hi = min(M + 0.2, 1);
+ * if that gives hi <= lo, lo = m - 0.2 and hi = M + 0.2.  This is plot.py:145 WITHOUT the margin matplotlib's autoscale adds to
+ * the data first.  Velocity range: pad = (M - m) * 0.05, and 0.5 when that is zero; lo = m - pad, hi = M + pad.
+ * row(v) = R((hi - v) / (hi - lo) * (PH - 1)).  With T = 0 both ranges are [0, 1], the time axis is [0, 0], there are no curves
+ * and everything else is drawn.  Rows and columns count from the rectangle's top left pixel.
+ *
+ * The figure is a list of RECORDS (vbt_figure_table returns them) and four curves.  A record is 12 int32:
+ *   kind, x0, y0, x1, y1, ox, oy, chars[3], value, aux
+ * [x0, x1] x [y0, y1] (inclusive, frame coordinates) is the part of the record that can be seen: its box [ox ..] x [oy ..] clipped to
+ * the frame or, for spans and rep labels, to their rectangle; it is empty when x0 > x1 or y0 > y1, and the record is still listed.
+ *   kind 0, span:   covers its visible box.  value = the phase's index, aux = its type.
+ *   kind 1, line:   covers its visible box (frame lines, tick marks).
+ *   kind 2, swatch: covers its visible box in the colour of curve aux (4 x, 5 y, 6 dx, 7 dy).
+ *   kind 3, text:   aux = n | rot << 8; character k (0 .. n - 1) is byte k % 4 of chars[k / 4].  Not turned (rot = 0) the text's box
+ *                   is (6 n - 1) s wide and 7 s high and bitmap column c, row r of character k cover the s x s block at
+ *                   (ox + 6 s k + s c, oy + s r), as in the rep panel.  Turned a quarter (rot = 1, it reads bottom to top) the box is
+ *                   7 s wide and (6 n - 1) s high and pixel (ox + a, oy + b) of it is pixel ((6 n - 1) s - 1 - b, a) of the text
+ *                   not turned.  Only pixels inside the visible box are covered.
+ * Character codes: 0..9 the digits, 12..21 R E P O M A C V . and space as in the rep panel (their glyphs are unchanged), and
+ *   22 '-': 00000 00000 00000 11111 00000 00000 00000      25 'X': 10001 10001 01010 00100 01010 10001 10001
+ *   23 '/': 00001 00001 00010 00100 01000 10000 10000      26 'Y': 10001 10001 01010 00100 00100 00100 00100
+ *   24 'S': 01111 10000 10000 01110 00001 00001 11110      27 'D': 11110 10001 10001 10001 10001 10001 11110
+ * The records, in table order:
+ *   1. Spans.  For every phase i of type 0 (concentric) or 1 (eccentric), in phase order, two spans (upper, then lower rectangle) of
+ *      columns X0 + col(time_start) .. X0 + col(time_end) over the rectangle's rows, clipped to the rectangle.  A hold draws nothing.
+ *   2. Rep labels.  For every concentric phase, in phase order, two turned texts (upper: centi(rom); lower: centi(acv),
+ *      acv = duration > 0 ? rom / duration : 0; centi as in the rep panel, so values above 99.99 show 99.99), "d.dd" or "dd.dd",
+ *      at ox = X0 + col((time_start + time_end) / 2) - 3 s, oy = Y + 2 s (Y = Y0 or Y1), clipped to the rectangle; value = the centi.
+ *   3. Per rectangle (upper first): four frame lines s wide AROUND the rectangle (top [X0 - s, X0 + PW + s) x [Y - s, Y), bottom the
+ *      same at [Y + PH, Y + PH + s), left [X0 - s, X0) and right [X0 + PW, X0 + PW + s) over the rectangle's rows); the title at
+ *      (X0, Y - 9 s): "ROM M" (position, ROM in m) / "ACV M/S" (velocity, ACV in m/s); two legend keys, at kx = X0 + 48 s and
+ *      X0 + 70 s: a swatch [kx, kx + 6 s) x [Y - 7 s, Y - 4 s) and the text "X", "Y" / "DX", "DY" at (kx + 7 s, Y - 9 s); then
+ *      the value ticks: step = the smallest of 10, 20, 50, 100, 200, 500, ... 10^7 thousandths with (hi - lo) * 1000 / step <= 6
+ *      (no ticks if none, or if lo < -10^9 or hi > 10^9); for k from floor(lo * 1000 / step) - 1, ten values, those whose
+ *      v = (k step) / 1000.0 (integer product, one divide) has lo <= v <= hi, each a line [X0 - 3 s, X0 - s) x [yt, yt + s),
+ *      yt = Y + row(v) - s / 2, and a text of c = k step / 10 clamped to +-9999, "[-]d.dd" or "[-]dd.dd", right-aligned to end at
+ *      X0 - 4 s (ox = X0 - 4 s - (6 n - 1) s), oy = Y + row(v) - 3 s; value = c.
+ *   4. Time ticks under the lower rectangle (plot.py:208-215): u = the smallest power of ten with 256 u >= t1 - t0 (1 for every set
+ *      shorter than 256 s), base = floor(t0) - floor(t0) mod 5 u (non-negative remainder); the seconds base + k u, k = 0 .. 263,
+ *      that lie inside [t0, t1] (none if t0 < -10^9 or t1 > 10^9): a line [xt, xt + s) x [Y1 + PH + s, Y1 + PH + s + L),
+ *      xt = X0 + col(second) - s / 2, L = 3 s for a multiple of 5 u (a major tick, aux = 1), else 2 s; a major tick is followed by
+ *      its text: the integer, centred (ox = X0 + col - ((6 n - 1) s) / 2, oy = Y1 + PH + 5 s); value = the second.
+ * Curves.  Point i of a figure is (col(time_i), row(v_i)) per series.  Consecutive points of a series are joined by rule 2 of the
+ * tracking overlay with thickness t, in rectangle coordinates (segment i joins points i and i + 1; a one-point series is the
+ * segment from the point to itself: a dot); a curve is clipped to its rectangle.
+ *
+ * One writer per pixel.  The value of every pixel is decided by the first of these that covers it: 1. a text record - ink;
+ * 2. the second curve of the rectangle (y / dy); 3. the first curve (x / dx); 4. a line or a swatch (no two of different colour
+ * meet); 5. a span - of those that cover it the one of the latest phase: concentric (247, 212, 212), eccentric (255, 229, 207),
+ * the opaque colours alpha = 0.2 of matplotlib's C3 / C1 gives over white (plot.py:27-30,166-169); 6. white.  Ink is (0, 0, 0); the
+ * curves are x (53, 25, 62), y (226, 75, 64), dx (112, 31, 87), dy (243, 118, 81) - four fixed colours in the spirit of the 'rocket'
+ * palette, not seaborn's.  Nothing is read from the frames, rendering twice equals rendering once, every byte of the N frames is
+ * written and no byte outside them.
+ *
+ * Staging.  A render workgroup owns a 256 x 32 pixel tile; it keeps the points its columns can meet and the records that touch it in
+ * LDS when there are at most VBT_FIGURE_STAGE_POINTS / VBT_FIGURE_STAGE_RECORDS of them and reads global memory otherwise, by the
+ * same statements. */
+#define VBT_FIGURE_STAGE_POINTS 512
+#define VBT_FIGURE_STAGE_RECORDS 96
+typedef struct vbt_figure vbt_figure;
+typedef struct {
+  int32_t width, height;  /* -> 1280 x 800 */
+  int32_t scale;          /* pixels per cell -> 2 */
+  int32_t thickness;      /* of the curves -> 2 */
+  int32_t max_figures;    /* -> 64 */
+  int32_t max_rows;       /* per figure -> 16384 */
+  int32_t max_phases;     /* per figure -> 512 */
+  int32_t reserved;
+} vbt_figure_params;
+void vbt_figure_default_params(vbt_figure_params* p);
+/* params NULL = the defaults.  VBT_ERR_ARG, before any device call: out NULL, width or height outside 1..16384, scale or thickness
+ * outside 1..64, max_figures outside 1..4096, max_rows outside 1..2^20, max_phases outside 0..65536, max_figures * max_rows above
+ * 2^26 or max_figures * max_phases above 2^22, a plot rectangle below 16 x 16.  One allocation: per figure 108 bytes per row and
+ * 48 bytes per record (384 + 4 max_phases records); VBT_ERR_HIP, naming the size, when the device cannot give it. */
+int vbt_figure_create(int device, const vbt_figure_params* params, vbt_figure** out);
+void vbt_figure_destroy(vbt_figure* f);
+/* The n figures to render: rows7_host = the rows of figure 0, 1, ... one after the other (row_counts[i] of 7 doubles each),
+ * phases6_host likewise (phase_counts[i] of 6 doubles).  Replaces what the handle held; n = 0 leaves it with nothing set.
+ * Refusals, on the host and before any launch, in this order: VBT_ERR_ARG n < 0 or NULL counts; VBT_ERR_CAPACITY n > 4096;
+ * per figure VBT_ERR_ARG a negative count, VBT_ERR_CAPACITY more than 2^20 rows or 65536 phases; VBT_ERR_ARG, naming the figure and
+ * the row or phase: a non-finite value, a time that decreases, a phase vbt_overlay_set_hud would refuse on its doubles.  Then the
+ * handle (NULL: VBT_ERR_ARG) and VBT_ERR_CAPACITY: more figures, rows or phases than it was created for.  A refused call leaves the
+ * handle as it was.  ONE upload (counts, rows and phases of all figures, concatenated) and ONE prepare launch, a workgroup per
+ * figure, on `stream`, which it synchronises (the upload buffer is the call's own). */
+int vbt_figure_set(vbt_figure* f, int n, const double* rows7_host, const int32_t* row_counts, const double* phases6_host,
+                   const int32_t* phase_counts, void* stream);
+/* Figures fig0 .. fig0 + n - 1 into n contiguous frames of W * H * 3 bytes at frames_dev.  Enqueue only: ONE launch, grid (tile,
+ * figure); it needs no synchronisation behind a vbt_figure_set on the same stream, and vbt_mjpeg_encode can follow on it.  With
+ * W % 4 == 0 and frames_dev 4-aligned four pixels go out as three 32-bit stores, else as bytes.  VBT_ERR_STATE: nothing is set;
+ * VBT_ERR_ARG: a NULL argument, fig0 < 0, n < 0 or fig0 + n above the figures set.  The handle's tables must not be replaced (by
+ * vbt_figure_set on another stream) while a render is in flight. */
+int vbt_figure_render(vbt_figure* f, uint8_t* frames_dev, int fig0, int n, void* stream);
+/* What the prepare launch formed for figure `fig`, read back (it waits for the stream of the last set or render): head6 = t0, t1,
+ * position lo, hi, velocity lo, hi; points = T records of 5 int32 (column, then the pixel row of x, y, dx, dy); records = the
+ * 12-int32 records above.  head6, *n_points and *n_records are always set; VBT_ERR_CAPACITY when cap_points or cap_records (in records)
+ * is below them: no point and no record is copied.  VBT_ERR_STATE: nothing is set; VBT_ERR_ARG: fig outside the figures set. */
+int vbt_figure_table(vbt_figure* f, int fig, double* head6, int32_t* points, int cap_points, int* n_points, int32_t* records, int cap_records,
+                     int* n_records);
+
 /* ------------------------------------------------------------------ MJPEG export --------
  * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that
  * sits in device memory is encoded there as one baseline JPEG and only the compressed bytes come back; the host wraps them in an AVI

@@ -75,6 +75,11 @@ class OverlayHudParams(ctypes.Structure):
                 ("bg", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 5)]
 
 
+class FigureParams(ctypes.Structure):
+    """vbt_figure_params (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "scale", "thickness", "max_figures", "max_rows", "max_phases", "reserved")]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int), ("algorithmic_bytes", c_double), ("macs", c_double)]
 
@@ -201,6 +206,12 @@ _SIGS = {
     "vbt_overlay_follow_status": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_void_p]),
     "vbt_tracker_rows_dev": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_int)]),
     "vbt_pipeline_overlay_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vbt_figure_default_params": (None, [ctypes.POINTER(FigureParams)]),
+    "vbt_figure_create": (c_int, [c_int, ctypes.POINTER(FigureParams), ctypes.POINTER(c_void_p)]),
+    "vbt_figure_destroy": (None, [c_void_p]),
+    "vbt_figure_set": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_figure_render": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "vbt_figure_table": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_mjpeg_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_mjpeg_destroy": (None, [c_void_p]),
     "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

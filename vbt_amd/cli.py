@@ -48,6 +48,13 @@
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
+  python -m vbt_amd.cli plot DF.pkl.gz... --fig_dir DIR [--plate_diameter 0.45] [--fig_size 1280x800] [--fig_scale 2] [--fig_format jpg|ppm]
+                           [--fig_quality 90]
+      reference plot.py:50-232 with the figure, and without matplotlib: per DataFrame the smoothed position and velocity curves, a
+      tinted span per phase and ROM / ACV over every concentric phase, rendered on the GPU (include/vbt_hip.h, "Rep figure") and written
+      as DIR/{name}.jpg (baseline JPEG encoded on the GPU) or DIR/{name}.ppm (the raw frame behind a P6 header) - plot.py:220's name
+      with the new extension.  Up to 64 files go through one upload, one render and one encode.  Prints what `analyze` prints.
+      There is no display, so --show_fig is not offered.
   python -m vbt_amd.cli validate [--kinovea_dir D | --qualysis_dir D] [--df_dir dfs] [--plate_diameter 0.45]
       reference kinovea.py:29-38,57-172,203-215 / qualysis.py:29-38,57-187 without the figures: per export with a
       matching {video}_id{N}_{model}.pkl.gz, MSE and Pearson r of x(t) and y(t) in metres, then the totals line.
@@ -455,6 +462,43 @@ def analyze(src, plate_diameter):
         click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {len(reps)} concentric reps")
         for i, p in enumerate(reps, 1):
             click.echo(_rep_line(i, p))
+
+
+def _analyze_lines(video, tid, model, phases):
+    from .velocity import Phase
+    reps = [p for p in phases if p.type == Phase.CONCENTRIC]
+    click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {len(reps)} concentric reps")
+    for i, p in enumerate(reps, 1):
+        click.echo(_rep_line(i, p))
+
+
+@main.command()
+@click.argument("src", type=str, nargs=-1)
+@click.option("--plate_diameter", default=0.45, show_default=True, type=float, help="Diameter of the weight plate used in meters.")
+@click.option("--fig_dir", default=None, help="Directory for saving the figures (required: there is no display to show them on).")
+@click.option("--fig_size", default="1280x800", show_default=True, type=str, help="WIDTHxHEIGHT of a figure in pixels.")
+@click.option("--fig_scale", default=2, show_default=True, type=click.IntRange(1, 64), help="Pixels per cell of the figure's text and margins.")
+@click.option("--fig_format", default="jpg", show_default=True, type=click.Choice(["jpg", "ppm"]),
+              help="jpg: baseline JPEG encoded on the GPU; ppm: the raw RGB frame behind a P6 header, lossless.")
+@click.option("--fig_quality", default=90, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --fig_format jpg.")
+def plot(src, plate_diameter, fig_dir, fig_size, fig_scale, fig_format, fig_quality):
+    if fig_dir is None:
+        raise click.UsageError("plot writes the figures: give --fig_dir (there is no display for --show_fig)")
+    m = re.fullmatch(r"\s*(\d+)\s*[xX]\s*(\d+)\s*", fig_size)
+    if not m:
+        raise click.BadParameter(f"expected WIDTHxHEIGHT, got {fig_size!r}", param_hint="--fig_size")
+    from . import figure
+
+    def on_file(s, loaded):
+        if loaded is None:
+            click.echo(f"Couldn't create a plot for file '{s}'.")        # reference plot.py:81-85
+            return
+        _analyze_lines(*FILENAME_RE.match(os.path.basename(s)).groups(), loaded[1])
+    try:
+        figure.plot_many(src, fig_dir, plate_diameter, fig_format, fig_quality, on_file=on_file, width=int(m.group(1)), height=int(m.group(2)),
+                         scale=fig_scale)
+    except ValueError as e:                                              # (VbtArgError: a figure size the layout refuses)
+        raise click.UsageError(str(e))
 
 
 @main.command()

@@ -4,40 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "roll_mean.h"   // RollMean: pandas roll_mean state (Kahan add / remove)
 #include "tracker_state.h"
 
 namespace vbt {
-
-struct RollMean {  // pandas roll_mean state (Kahan add / remove)
-  double sum, c_add, c_rem, prev;
-  long nobs, neg, same;
-  __device__ void init() { sum = 0; c_add = 0; c_rem = 0; prev = __builtin_nan(""); nobs = 0; neg = 0; same = 0; }
-  __device__ void add(double v) {
-    nobs += 1;
-    double y = v - c_add;
-    double t = sum + y;
-    c_add = (t - sum) - y;
-    sum = t;
-    if (__builtin_signbit(v)) neg += 1;
-    if (v == prev) same += 1; else same = 1;
-    prev = v;
-  }
-  __device__ void remove(double v) {
-    nobs -= 1;
-    double y = -v - c_rem;
-    double t = sum + y;
-    c_rem = (t - sum) - y;
-    sum = t;
-    if (__builtin_signbit(v)) neg -= 1;
-  }
-  __device__ double mean() const {
-    double r = sum / (double)nobs;
-    if (same >= nobs) r = prev;
-    else if (neg == 0 && r < 0) r = 0.0;
-    else if (neg == nobs && r > 0) r = 0.0;
-    return r;
-  }
-};
 
 struct VtParams {
   double plate_diameter, diff_threshold, min_distance;
