@@ -876,6 +876,180 @@ int vbt_figure_render(vbt_figure* f, uint8_t* frames_dev, int fig0, int n, void*
 int vbt_figure_table(vbt_figure* f, int fig, double* head6, int32_t* points, int cap_points, int* n_points, int32_t* records, int cap_records,
                      int* n_records);
 
+/* ------------------------------------------------------------------ Curve figure --------
+ * The reference's second figure kind (eval.py:218-468): precision-recall and ROC curves of up to max_series models in one plot
+ * rectangle, with a legend, a grid and, on the per-model figures, score-threshold annotations.  A handle renders N figures of one
+ * size into N contiguous RGB24 frames in device memory, which vbt_mjpeg_encode can take on the same stream.  As with the rep figure,
+ * matplotlib's rasterisation is NOT the contract: the contract is the rules below, stated a second time in numpy
+ * (tests/curve_figure_ref.py).  All values are integers once formed; every double is IEEE, one operation per statement, without
+ * contraction (the statements themselves: vbt_amd/csrc/curve_figure_core.h).  s = scale, t = thickness, b = (s + 1) / 2.
+ *
+ * Input per figure: a vbt_curve_figure_desc, n_series vbt_curve_series (a legend text, a colour 0..9 and n_points points of two
+ * doubles x, y) and n_marks vbt_curve_mark (a series of the figure, a point of it by its index in the input, a text).
+ *
+ * Layout.  A white W x H frame holds ONE plot rectangle [X0, X0 + PW) x [Y0, Y0 + PH); margins in cells of s pixels: 30 left,
+ * 4 right, 4 above, 22 below:  X0 = 30 s, Y0 = 4 s, PW = W - 34 s, PH = H - 26 s.  PW < 16 or PH < 16 is refused.
+ *
+ * Axes.  Both are fixed to [0, 1.01] (eval.py:254-255): col(x) = R(x / 1.01 * (PW - 1)), row(y) = R((1.01 - y) / 1.01 * (PH - 1)),
+ * R the clamp-then-llrint of the rep figure; columns and rows count from the rectangle's top left pixel.
+ *
+ * Points.  A point is FINITE when both coordinates are.  x over the finite points of a series must not decrease, or must not
+ * increase (roc_curve gives the first, precision_recall_curve the second); a series that decreases somewhere is taken in reversed
+ * order, so it renders byte-identically to the same points given reversed.  Every finite point is a dot (rule 2 of the tracking
+ * overlay on the segment from the point to itself) and two consecutive finite points are joined by rule 2, the exact capsule test,
+ * with thickness t, in rectangle coordinates.  A non-finite point draws nothing and breaks the polyline.  n_points = 0 draws no
+ * curve and still has its legend row.  Curves are clipped to the plot rectangle; where series overlap the later one wins.
+ *
+ * The run merge.  What vbt_curve_figure_table returns, and what the render kernel walks, are the MERGED points of a series: three
+ * int32 each - column, row, join (1: a segment joins it to the merged point before it).  A RUN is a maximal stretch of consecutive
+ * finite points of one column; of a run the first point, the last, the first of its lowest rows and the first of its highest rows
+ * are kept, in input order (of the reversed series, if it is reversed).  The pixels do not change: the segments of a run lie on one
+ * vertical line and form a connected path, so the union of their capsules is the capsule of [lowest, highest], which the kept
+ * points still span, and the joins to the neighbouring columns need only the first and the last point.  The numpy statement renders
+ * the UNMERGED polyline and the frames must match it byte for byte.
+ *
+ * Records (vbt_curve_figure_table returns them).  28 int32:  kind, x0, y0, x1, y1, ox, oy, value, aux, n, 0, 0, chars[16].
+ * [x0, x1] x [y0, y1] (inclusive, frame coordinates) is the part of the record that can be seen: its box [ox ..] x [oy ..] clipped to
+ * the frame or, for grid lines, to the plot rectangle; it is empty when x0 > x1 or y0 > y1, and the record is still listed.  The kind
+ * is also the record's PRIORITY (below).
+ *   kind 0 legend text, 3 mark text, 8 text: n bytes, byte k is byte k % 4 of chars[k / 4]; aux = rot.  Not turned the box is
+ *        (6 n - 1) s wide and 7 s high and bitmap column c, row r of byte k cover the s x s block at (ox + 6 s k + s c, oy + s r);
+ *        turned a quarter (rot = 1, reads bottom to top) the box is 7 s wide and (6 n - 1) s high and pixel (ox + a, oy + b') of it is
+ *        pixel ((6 n - 1) s - 1 - b', a) of the text not turned.  Ink.
+ *   kind 1 swatch: covers its visible box in the colour of palette index aux; value = the series.
+ *   kind 2 legend box: value = its width BW, aux = its height BH.  A pixel within b of an edge of [ox, ox + BW) x [oy, oy + BH) is
+ *        border grey (128, 128, 128), every other one white: the box is opaque.
+ *   kind 4 marker: the disc (px - value)^2 + (py - aux)^2 <= (2 s)^2 around the marked point (value, aux); ox = value - 2 s.  Ink.
+ *   kind 5 leader: rule 2 with thickness 1 on the segment from (ox, oy) to (value, aux), frame coordinates; the visible box is the
+ *        segment's bounding box widened by 1.  Ink.  (The reference's arc is not reproduced.)
+ *   kind 7 line: covers its visible box (spines, ticks).  Ink.  value = the tick's thousandths, aux = 1 on the y axis.
+ *   kind 9 major grid line, kind 10 minor grid line: aux = 0 vertical, 1 horizontal; value = thousandths.  A major line covers its
+ *        visible box, (176, 176, 176).  A minor line is DOTTED: with a = py - oy on a vertical and px - ox on a horizontal line,
+ *        the pixels with (a / b) % 3 == 0 are covered, (204, 204, 204).  Both are opaque, not blended.
+ * The records, in table order:
+ *   1. The left spine [X0 - s, X0) x [Y0, Y0 + PH + s) and the bottom spine [X0, X0 + PW) x [Y0 + PH, Y0 + PH + s); no others
+ *      (eval.py:256-257).
+ *   2. Major ticks at v = 200 k / 1000.0, k = 0 .. 5, the x axis first.  x axis, x = X0 + col(v): the tick [x - s / 2, x - s / 2 + s)
+ *      x [Y0 + PH + s, Y0 + PH + 4 s), the label "0.0" .. "1.0" at (x - (17 s) / 2, Y0 + PH + 5 s), the grid line [x, x + b) over the
+ *      rectangle's rows.  y axis, y = Y0 + row(v): the tick [X0 - 4 s, X0 - s) x [y - s / 2, y - s / 2 + s), the label at
+ *      (X0 - 22 s, y - 3 s), the grid line [y, y + b) over the rectangle's columns.
+ *   3. Minor grid lines, x axis first: for every multiple m of the axis' step (minor_x, minor_y; 0 = none) with m <= 1000 that is no
+ *      multiple of 200, a grid line as in 2 at v = m / 1000.0.
+ *   4. The x title, centred under the labels at (X0 + (PW - (6 n - 1) s) / 2, Y0 + PH + 14 s), and the y title, turned, at
+ *      (s, Y0 + (PH - (6 n - 1) s) / 2); an empty title has no record.
+ *   5. The legend, when the figure has series: L = the longest legend text in bytes, BW = (L ? (6 L - 1) s : 0) + 16 s,
+ *      BH = 9 s n_series + 4 s; the box at bx = X0 + 3 s (lower left, eval.py:264) or X0 + PW - 3 s - BW (lower right, eval.py:391),
+ *      by = Y0 + PH - 3 s - BH, clipped to the frame; then per series k, ty = by + 3 s + 9 s k: the swatch
+ *      [bx + 3 s, bx + 11 s) x [ty + 2 s, ty + 5 s) and the text at (bx + 13 s, ty).
+ *   6. Per mark i of M (eval.py:313-334,443-464), (px, py) = (X0 + col, Y0 + row) of its point: the text, the marker, the leader.
+ *      Lower-left figures (PR): the text's top RIGHT pixel is the corner (px - 8 s, py + (min(i, 3) + 1) 10 s); lower-right figures
+ *      (ROC): its top LEFT pixel is the corner (px + (M - i) 6 s, py + (i + 1) 10 s).  The leader runs from the corner to (px, py).
+ *      A mark on a non-finite point has its three records with an empty visible box.
+ * Font.  The 5 x 7 cell of the rep panel for every byte 0x20..0x7E (vbt_amd/csrc/curve_font.h), rows top to bottom.  The characters
+ * the overlay, the rep panel and the rep figure already draw (digits, R E P O M A C V S X Y D . - / space, i, d) have exactly their
+ * bits; those tables and their codes 0..27 are untouched.
+ *   ' ' 00000 00000 00000 00000 00000 00000 00000   '!' 00100 00100 00100 00100 00100 00000 00100   '"' 01010 01010 01010 00000 00000 00000 00000
+ *   '#' 01010 01010 11111 01010 11111 01010 01010   '$' 00100 01111 10100 01110 00101 11110 00100   '%' 11000 11001 00010 00100 01000 10011 00011
+ *   '&' 01100 10010 10100 01000 10101 10010 01101   ''' 00100 00100 01000 00000 00000 00000 00000   '(' 00010 00100 01000 01000 01000 00100 00010
+ *   ')' 01000 00100 00010 00010 00010 00100 01000   '*' 00000 00100 10101 01110 10101 00100 00000   '+' 00000 00100 00100 11111 00100 00100 00000
+ *   ',' 00000 00000 00000 00000 01100 00100 01000   '-' 00000 00000 00000 11111 00000 00000 00000   '.' 00000 00000 00000 00000 00000 01100 01100
+ *   '/' 00001 00001 00010 00100 01000 10000 10000   '0' 01110 10001 10011 10101 11001 10001 01110   '1' 00100 01100 00100 00100 00100 00100 01110
+ *   '2' 01110 10001 00001 00010 00100 01000 11111   '3' 11111 00010 00100 00010 00001 10001 01110   '4' 00010 00110 01010 10010 11111 00010 00010
+ *   '5' 11111 10000 11110 00001 00001 10001 01110   '6' 00110 01000 10000 11110 10001 10001 01110   '7' 11111 00001 00010 00100 01000 01000 01000
+ *   '8' 01110 10001 10001 01110 10001 10001 01110   '9' 01110 10001 10001 01111 00001 00010 01100   ':' 00000 01100 01100 00000 01100 01100 00000
+ *   ';' 00000 01100 01100 00000 01100 00100 01000   '<' 00010 00100 01000 10000 01000 00100 00010   '=' 00000 00000 11111 00000 11111 00000 00000
+ *   '>' 01000 00100 00010 00001 00010 00100 01000   '?' 01110 10001 00001 00010 00100 00000 00100   '@' 01110 10001 00001 01101 10101 10101 01110
+ *   'A' 01110 10001 10001 11111 10001 10001 10001   'B' 11110 10001 10001 11110 10001 10001 11110   'C' 01110 10001 10000 10000 10000 10001 01110
+ *   'D' 11110 10001 10001 10001 10001 10001 11110   'E' 11111 10000 10000 11110 10000 10000 11111   'F' 11111 10000 10000 11110 10000 10000 10000
+ *   'G' 01110 10001 10000 10111 10001 10001 01111   'H' 10001 10001 10001 11111 10001 10001 10001   'I' 01110 00100 00100 00100 00100 00100 01110
+ *   'J' 00111 00010 00010 00010 00010 10010 01100   'K' 10001 10010 10100 11000 10100 10010 10001   'L' 10000 10000 10000 10000 10000 10000 11111
+ *   'M' 10001 11011 10101 10101 10001 10001 10001   'N' 10001 10001 11001 10101 10011 10001 10001   'O' 01110 10001 10001 10001 10001 10001 01110
+ *   'P' 11110 10001 10001 11110 10000 10000 10000   'Q' 01110 10001 10001 10001 10101 10010 01101   'R' 11110 10001 10001 11110 10100 10010 10001
+ *   'S' 01111 10000 10000 01110 00001 00001 11110   'T' 11111 00100 00100 00100 00100 00100 00100   'U' 10001 10001 10001 10001 10001 10001 01110
+ *   'V' 10001 10001 10001 10001 10001 01010 00100   'W' 10001 10001 10001 10101 10101 10101 01010   'X' 10001 10001 01010 00100 01010 10001 10001
+ *   'Y' 10001 10001 01010 00100 00100 00100 00100   'Z' 11111 00001 00010 00100 01000 10000 11111   '[' 01110 01000 01000 01000 01000 01000 01110
+ *   '\' 10000 10000 01000 00100 00010 00001 00001   ']' 01110 00010 00010 00010 00010 00010 01110   '^' 00100 01010 10001 00000 00000 00000 00000
+ *   '_' 00000 00000 00000 00000 00000 00000 11111   '`' 01000 00100 00010 00000 00000 00000 00000   'a' 00000 00000 01110 00001 01111 10001 01111
+ *   'b' 10000 10000 10110 11001 10001 10001 11110   'c' 00000 00000 01110 10000 10000 10001 01110   'd' 00001 00001 01101 10011 10001 10001 01111
+ *   'e' 00000 00000 01110 10001 11111 10000 01110   'f' 00110 01001 01000 11100 01000 01000 01000   'g' 00000 01111 10001 10001 01111 00001 01110
+ *   'h' 10000 10000 10110 11001 10001 10001 10001   'i' 00100 00000 01100 00100 00100 00100 01110   'j' 00010 00000 00110 00010 00010 10010 01100
+ *   'k' 10000 10000 10010 10100 11000 10100 10010   'l' 01100 00100 00100 00100 00100 00100 01110   'm' 00000 00000 11010 10101 10101 10001 10001
+ *   'n' 00000 00000 10110 11001 10001 10001 10001   'o' 00000 00000 01110 10001 10001 10001 01110   'p' 00000 00000 11110 10001 11110 10000 10000
+ *   'q' 00000 00000 01101 10011 01111 00001 00001   'r' 00000 00000 10110 11001 10000 10000 10000   's' 00000 00000 01110 10000 01110 00001 11110
+ *   't' 01000 01000 11100 01000 01000 01001 00110   'u' 00000 00000 10001 10001 10001 10011 01101   'v' 00000 00000 10001 10001 10001 01010 00100
+ *   'w' 00000 00000 10001 10001 10101 10101 01010   'x' 00000 00000 10001 01010 00100 01010 10001   'y' 00000 00000 10001 10001 01111 00001 01110
+ *   'z' 00000 00000 11111 00010 00100 01000 11111   '{' 00010 00100 00100 01000 00100 00100 00010   '|' 00100 00100 00100 00100 00100 00100 00100
+ *   '}' 01000 00100 00100 00010 00100 00100 01000   '~' 00000 00000 01000 10101 00010 00000 00000
+ *
+ * One writer per pixel.  The value of every pixel is decided by the first of these that covers it, a total order that is the same in
+ * the kernel, in the shared core and in numpy: 0 legend text (ink); 1 legend swatch; 2 legend box (border or white); 3 mark text;
+ * 4 marker; 5 leader; 6 the curves, from the last series to the first, in their palette colours; 7 spines and ticks; 8 tick and axis
+ * text; 9 major grid; 10 minor grid; then white.  Palette 0..9: (31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40),
+ * (148, 103, 189), (140, 86, 75), (227, 119, 194), (127, 127, 127), (188, 189, 34), (23, 190, 207).  Nothing is read from the frames,
+ * rendering twice equals rendering once, every byte of the N frames is written and no byte outside them.
+ *
+ * Staging.  A render workgroup owns a 256 x 8 pixel tile; it keeps the merged points of all series its columns can meet and the
+ * records that touch it in LDS when there are at most VBT_CURVE_FIGURE_STAGE_POINTS / VBT_CURVE_FIGURE_STAGE_RECORDS of them, and
+ * reads both from global memory otherwise, by the same statements. */
+#define VBT_CURVE_FIGURE_STAGE_POINTS 384
+#define VBT_CURVE_FIGURE_STAGE_RECORDS 64
+typedef struct vbt_curve_figure vbt_curve_figure;
+typedef struct {
+  int32_t width, height;  /* -> 1120 x 640 (the reference's 7 x 4 in) */
+  int32_t scale;          /* pixels per cell -> 2 */
+  int32_t thickness;      /* of the curves -> 2 */
+  int32_t max_figures;    /* -> 16 */
+  int32_t max_series;     /* per figure -> 8 */
+  int32_t max_points;     /* per figure, all its series together -> 131072 */
+  int32_t max_marks;      /* per figure -> 8 */
+} vbt_curve_figure_params;
+typedef struct {
+  int32_t n_series, n_marks;
+  int32_t legend_corner;  /* 0 lower left (PR), 1 lower right (ROC); it also chooses the side of the marks' texts */
+  int32_t minor_x, minor_y; /* minor grid step in thousandths, 0 = none, else 20..1000 */
+  int32_t reserved[3];
+  char x_title[32], y_title[32]; /* NUL-terminated, at most 31 bytes */
+} vbt_curve_figure_desc;
+typedef struct {
+  int32_t n_points;
+  int32_t colour;         /* palette index 0..9 */
+  char text[64];          /* the legend text, NUL-terminated, at most 63 bytes */
+} vbt_curve_series;
+typedef struct {
+  int32_t series, point;  /* a series of the figure and a point of it, by its index in the input */
+  char text[16];          /* NUL-terminated, at most 15 bytes */
+} vbt_curve_mark;
+void vbt_curve_figure_default_params(vbt_curve_figure_params* p);
+/* params NULL = the defaults.  VBT_ERR_ARG, before any device call: out NULL, width or height outside 1..16384, scale or thickness
+ * outside 1..64, max_figures outside 1..1024, max_series outside 1..16, max_points outside 1..2^22, max_marks outside 0..64,
+ * max_figures * max_points above 2^26, a plot rectangle below 16 x 16.  One allocation: per figure 52 bytes per point and 112 bytes
+ * per record (145 + 2 max_series + 3 max_marks records); VBT_ERR_HIP, naming the size, when the device cannot give it. */
+int vbt_curve_figure_create(int device, const vbt_curve_figure_params* params, vbt_curve_figure** out);
+void vbt_curve_figure_destroy(vbt_curve_figure* f);
+/* The n figures to render: figs[n]; series = the series of figure 0, 1, ... one after the other; xy = their points in the same order,
+ * two doubles each; marks likewise.  Replaces what the handle held; n = 0 leaves it with nothing set.  Refusals, on the host and
+ * before any launch, in this order: VBT_ERR_ARG n < 0 or figs NULL; VBT_ERR_CAPACITY n > 1024; per figure VBT_ERR_ARG a negative
+ * count, a corner that is not 0 or 1, a minor step that is neither 0 nor in 20..1000, VBT_ERR_CAPACITY more than 16 series or 64
+ * marks; VBT_ERR_ARG NULL series, marks or xy where some are counted; then, naming the figure and the series or mark, VBT_ERR_ARG: a
+ * negative n_points (VBT_ERR_CAPACITY above 2^22 per figure), a colour outside 0..9, a text or title without its NUL or with a byte
+ * outside 0x20..0x7E, x that is not monotone (the point's index is named), a mark whose series or point does not exist.  Then the
+ * handle (NULL: VBT_ERR_ARG) and VBT_ERR_CAPACITY: more figures, series, points or marks than it was created for.  A refused call
+ * leaves the handle as it was.  ONE upload (everything, concatenated) and ONE prepare launch, a workgroup per figure, on `stream`,
+ * which it synchronises (the upload buffer is the call's own). */
+int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc* figs, const vbt_curve_series* series, const double* xy,
+                         const vbt_curve_mark* marks, void* stream);
+/* Figures fig0 .. fig0 + n - 1 into n contiguous frames of W * H * 3 bytes at frames_dev.  Enqueue only: ONE launch, grid (tile,
+ * figure); vbt_mjpeg_encode can follow on the same stream.  With W % 4 == 0 and frames_dev 4-aligned four pixels go out as three
+ * 32-bit stores, else as bytes.  VBT_ERR_STATE: nothing is set; VBT_ERR_ARG: a NULL argument, fig0 < 0, n < 0 or fig0 + n above the
+ * figures set.  The handle's tables must not be replaced while a render is in flight. */
+int vbt_curve_figure_render(vbt_curve_figure* f, uint8_t* frames_dev, int fig0, int n, void* stream);
+/* What the prepare launch formed for figure `fig`, read back (it waits for the stream of the last set or render): counts[k] = the
+ * merged points of series k; points = those of all series, one after the other, 3 int32 each; records = the 28-int32 records above.
+ * *n_series, *n_points and *n_records are always set; VBT_ERR_CAPACITY when a capacity (in entries) is below them: nothing is copied.
+ * VBT_ERR_STATE: nothing is set; VBT_ERR_ARG: fig outside the figures set. */
+int vbt_curve_figure_table(vbt_curve_figure* f, int fig, int32_t* counts, int cap_series, int* n_series, int32_t* points, int cap_points,
+                           int* n_points, int32_t* records, int cap_records, int* n_records);
+
 /* ------------------------------------------------------------------ MJPEG export --------
  * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that
  * sits in device memory is encoded there as one baseline JPEG and only the compressed bytes come back; the host wraps them in an AVI

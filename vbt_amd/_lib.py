@@ -80,6 +80,27 @@ class FigureParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "scale", "thickness", "max_figures", "max_rows", "max_phases", "reserved")]
 
 
+class CurveFigureParams(ctypes.Structure):
+    """vbt_curve_figure_params (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "scale", "thickness", "max_figures", "max_series", "max_points", "max_marks")]
+
+
+class CurveFigureDesc(ctypes.Structure):
+    """vbt_curve_figure_desc (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_series", "n_marks", "legend_corner", "minor_x", "minor_y")] + \
+               [("reserved", ctypes.c_int32 * 3), ("x_title", ctypes.c_char * 32), ("y_title", ctypes.c_char * 32)]
+
+
+class CurveSeries(ctypes.Structure):
+    """vbt_curve_series (include/vbt_hip.h)"""
+    _fields_ = [("n_points", ctypes.c_int32), ("colour", ctypes.c_int32), ("text", ctypes.c_char * 64)]
+
+
+class CurveMark(ctypes.Structure):
+    """vbt_curve_mark (include/vbt_hip.h)"""
+    _fields_ = [("series", ctypes.c_int32), ("point", ctypes.c_int32), ("text", ctypes.c_char * 16)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int), ("algorithmic_bytes", c_double), ("macs", c_double)]
 
@@ -212,6 +233,13 @@ _SIGS = {
     "vbt_figure_set": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vbt_figure_render": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "vbt_figure_table": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_curve_figure_default_params": (None, [ctypes.POINTER(CurveFigureParams)]),
+    "vbt_curve_figure_create": (c_int, [c_int, ctypes.POINTER(CurveFigureParams), ctypes.POINTER(c_void_p)]),
+    "vbt_curve_figure_destroy": (None, [c_void_p]),
+    "vbt_curve_figure_set": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_curve_figure_render": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "vbt_curve_figure_table": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int,
+                                       ctypes.POINTER(c_int)]),
     "vbt_mjpeg_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_mjpeg_destroy": (None, [c_void_p]),
     "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

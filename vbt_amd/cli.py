@@ -60,10 +60,13 @@
       matching {video}_id{N}_{model}.pkl.gz, MSE and Pearson r of x(t) and y(t) in metres, then the totals line.
   python -m vbt_amd.cli eval MODELS... [--img_dir data/test] [--annotations_dir data/test] [--iou_threshold 0.5]
                            [--detections_df dfs/eval_detections.pkl.gz] [--replace_df] [--score_thresholds "[0.2, 0.5]"] [--curve_dir DIR] [--rgb]
-      reference eval.py:471-521 without the figures: VOC annotations, every image through each model at threshold 0, Hungarian
+                           [--fig_dir DIR] [--fig_size 1120x640] [--fig_scale 2] [--fig_format jpg|ppm] [--fig_quality 90]
+      reference eval.py:471-521: VOC annotations, every image through each model at threshold 0, Hungarian
       matching and the PR / ROC curves on the GPU; writes (or, when it exists and --replace_df is not given, reads) the detections
       DataFrame, prints AP and AUC per model as the reference's legends show them and, for each --score_thresholds value, the
-      closest curve point; --curve_dir writes the curve points as CSV.
+      closest curve point; --curve_dir writes the curve points as CSV.  --fig_dir writes, after the lines, the reference's figures
+      (eval.py:218-468), rendered and encoded on the GPU: precision_recall_iou_{t} and roc_iou_{t} with every model and, with
+      --score_thresholds, precision_recall_{m}_iou_{t} and roc_{m}_iou_{t} per model, annotated at the closest curve points.
 Option names (including the reference's `treshold` / `qualysis` spellings) and defaults follow the reference.
 """
 import contextlib
@@ -546,7 +549,15 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter):
 @click.option("--score_thresholds", default="[]", show_default=True, help='List of score thresholds to locate on the curves, e.g. "[0.2, 0.5]".')
 @click.option("--curve_dir", default=None, show_default=True, help="Directory for the curve points as CSV. If not set they are not written.")
 @click.option("--rgb", is_flag=True, help="Feed RGB to the network (the reference's eval.py feeds cv2's BGR unswapped; that is the default).")
-def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb):
+@click.option("--fig_dir", default=None, show_default=True, help="Directory for saving the figures. If not set the figures won't be saved.")
+@click.option("--fig_size", default="1120x640", show_default=True, type=str,
+              help="WIDTHxHEIGHT of the combined figures in pixels; the per-model figures are three quarters as high.")
+@click.option("--fig_scale", default=2, show_default=True, type=click.IntRange(1, 64), help="Pixels per cell of the figures' text and margins.")
+@click.option("--fig_format", default="jpg", show_default=True, type=click.Choice(["jpg", "ppm"]),
+              help="jpg: baseline JPEG encoded on the GPU; ppm: the raw RGB frame behind a P6 header, lossless.")
+@click.option("--fig_quality", default=90, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --fig_format jpg.")
+def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb, fig_dir, fig_size, fig_scale,
+             fig_format, fig_quality):
     import ast
     import pandas as pd
     from . import evaluate as E
@@ -554,6 +565,9 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
         score_thresholds = list(ast.literal_eval(score_thresholds))                # reference eval.py:26-39
     except (ValueError, SyntaxError, TypeError):
         raise click.BadParameter(score_thresholds)
+    size = re.fullmatch(r"\s*(\d+)\s*[xX]\s*(\d+)\s*", fig_size)
+    if not size:
+        raise click.BadParameter(f"expected WIDTHxHEIGHT, got {fig_size!r}", param_hint="--fig_size")
     if not os.path.exists(detections_df) or replace_df:                            # reference eval.py:506-512
         click.echo(f"Creating dataframe '{detections_df}'.")
         annotations = E.read_annotations(annotations_dir)
@@ -563,7 +577,8 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
         df = pd.read_pickle(detections_df)
     if curve_dir is not None:
         os.makedirs(curve_dir, exist_ok=True)
-    for m, c in E.curves(df, iou_threshold).items():
+    curves = E.curves(df, iou_threshold)
+    for m, c in curves.items():
         click.echo(f"{m}, AP_{iou_threshold * 100:0.0f}={c.ap:.4f}, AUC={c.auc:.4f}  ({c.n_rows} rows, {c.n_pos} correct)")   # eval.py:261,388
         if c.flags:
             click.echo(f"{m}: " + " and ".join(t for b, t in ((E.NO_POSITIVES, "no correct detection"), (E.NO_NEGATIVES, "no incorrect detection"))
@@ -580,6 +595,13 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
                 os.path.join(curve_dir, f"precision_recall_{m}_iou_{iou_threshold}.csv"), index=False)
             pd.DataFrame({"FP Rate": c.fpr, "TP Rate": c.tpr, "Threshold": c.roc_thresholds, "Model": m}).to_csv(
                 os.path.join(curve_dir, f"roc_{m}_iou_{iou_threshold}.csv"), index=False)
+    if fig_dir is not None:                                                        # reference eval.py:517-521
+        try:
+            for draw in (E.plot_precision_recall, E.plot_roc):
+                draw(curves, fig_dir, iou_threshold, score_thresholds, fig_format, fig_quality, width=int(size.group(1)), height=int(size.group(2)),
+                     scale=fig_scale)
+        except ValueError as e:                                                    # (VbtArgError: a figure size the layout refuses)
+            raise click.UsageError(str(e))
 
 
 if __name__ == "__main__":

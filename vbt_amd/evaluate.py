@@ -1,5 +1,6 @@
-"""Detector evaluation - the reference's eval.py without the figures: VOC annotations, detections of every test image at threshold 0,
-Hungarian matching against the ground truth and precision-recall / ROC curves, AP and AUC per model.
+"""Detector evaluation - the reference's eval.py: VOC annotations, detections of every test image at threshold 0, Hungarian matching
+against the ground truth, precision-recall / ROC curves, AP and AUC per model, and the figures of both curve kinds
+(`plot_precision_recall`, `plot_roc`: rendered and encoded on the GPU, vbt_amd/curve_figure.py).
 
 Matching and curves run on the GPU (`vbt_eval_*`, include/vbt_hip.h; vbt_amd/csrc/evaluate.hip); the detections never leave the
 device between the detector and the matcher.  No torch, no scipy, no scikit-learn.
@@ -284,3 +285,85 @@ def curves(df_or_table, iou_threshold=0.5, device=0):
 def closest_point(thresholds, value):
     """index of the curve point whose threshold is closest to `value` (the first among equals: idxmin, eval.py:313-315,443-445)"""
     return int(np.argmin(np.abs(np.asarray(thresholds, np.float64) - value)))
+
+
+def _write_figures(handle_params, figures, paths, fig_format, quality, device):
+    """one handle, one set / render / encode and ONE read-back for `figures`; the files go to `paths`"""
+    from .curve_figure import CurveFigure
+    from .figure import ppm
+    fig = CurveFigure(device, **handle_params)
+    fig.set(figures)
+    if fig_format == "jpg":
+        from .mjpeg import Encoder
+        enc = Encoder(fig.H, fig.W, "rgb24", quality, len(figures), device)
+        enc.encode(fig.device_frames(), len(figures))                               # same stream, no synchronisation in between
+        blobs = enc.read()
+    else:
+        blobs = [ppm(f) for f in fig.frames()]
+    for path, blob in zip(paths, blobs):
+        with open(path, "wb") as f:
+            f.write(blob)
+    return list(paths)
+
+
+def curve_figures(kind, curves, iou_threshold, score_thresholds=None):
+    """(combined figure, [per-model figure, ...]) of `kind` "pr" / "roc" as curve_figure.figure dicts: what plot_precision_recall /
+    plot_roc hand to the GPU.  The per-model list is empty without score thresholds (eval.py:278-279,405-406)."""
+    from . import curve_figure as CF
+    pr = kind == "pr"
+    thresholds = list(score_thresholds) if score_thresholds is not None else []
+    titles = dict(x_title="Recall", y_title="Precision") if pr else dict(x_title="FP Rate", y_title="TP Rate")
+    corner = CF.LOWER_LEFT if pr else CF.LOWER_RIGHT                                # eval.py:264,391
+    series, singles = [], []
+    for k, (m, c) in enumerate(curves.items()):
+        xy = np.stack([c.recall, c.precision], axis=1) if pr else np.stack([c.fpr, c.tpr], axis=1)
+        colour = k % CF.PALETTE_SIZE
+        text = f"{m}, AP{iou_threshold * 100:.0f}={c.ap:.4f}" if pr else f"{m}, AUC={c.auc:.4f}"      # eval.py:261 (without the TeX), 388
+        series.append((xy, text[:63], colour))
+        if not thresholds:
+            continue
+        if pr:
+            thr = np.r_[c.pr_thresholds, c.pr_thresholds[-1:]]                      # eval.py:235
+            order = thresholds[::-1]                                                # eval.py:313
+        else:
+            thr, order = c.roc_thresholds, thresholds                               # eval.py:443
+        marks = []
+        if len(thr):
+            for v in order:
+                i = closest_point(thr, v)
+                marks.append((0, i, f"{thr[i]:.4f}"[:15]))
+        text = f"{m}, AP={c.ap:.4f}" if pr else f"{m}, AUC={c.auc:.4f}"             # eval.py:302,429
+        singles.append(CF.figure([(xy, text[:63], colour)], marks, corner=corner, minor_x=50, minor_y=50, **titles))    # eval.py:305-306,435-436
+    combined = CF.figure(series, corner=corner, minor_x=0 if pr else 100, minor_y=100, **titles)      # eval.py:266,393-394
+    return combined, singles
+
+
+def _plot(kind, stem, curves, fig_dir, iou_threshold, score_thresholds, fig_format, quality, params):
+    from . import curve_figure as CF
+    if fig_format not in ("jpg", "ppm"):
+        raise ValueError(f"fig_format {fig_format!r}: jpg or ppm")
+    os.makedirs(fig_dir, exist_ok=True)
+    device = int(params.pop("device", 0))
+    base = dict(CF.default_params(), **params)
+    combined, singles = curve_figures(kind, curves, iou_threshold, score_thresholds)
+    points = max(sum(len(xy) for xy, _, _ in combined["series"]), 1)
+    base.update(max_figures=1, max_series=max(len(combined["series"]), 1), max_points=points, max_marks=0)
+    written = _write_figures(base, [combined], [os.path.join(fig_dir, f"{stem}_iou_{iou_threshold}.{fig_format}")], fig_format, quality, device)
+    if singles:
+        one = dict(base, height=3 * base["height"] // 4, max_figures=len(singles), max_series=1, max_marks=max(len(f["marks"]) for f in singles))
+        paths = [os.path.join(fig_dir, f"{stem}_{m}_iou_{iou_threshold}.{fig_format}") for m in curves]
+        written += _write_figures(one, singles, paths, fig_format, quality, device)
+    return written
+
+
+def plot_precision_recall(curves, fig_dir, iou_threshold, score_thresholds=None, fig_format="jpg", quality=90, **params):
+    """The reference's plot_precision_recall (eval.py:218) on `curves()`'s result: FIG_DIR/precision_recall_iou_{t}.jpg|ppm with every
+    model, W x H, and with score thresholds one precision_recall_{m}_iou_{t} per model, W x 3H/4, in the model's colour, annotated at
+    the closest curve point of each threshold.  params: width, height, scale, thickness (curve_figure.default_params), device.
+    Returns the paths written."""
+    return _plot("pr", "precision_recall", curves, fig_dir, iou_threshold, score_thresholds, fig_format, quality, dict(params))
+
+
+def plot_roc(curves, fig_dir, iou_threshold, score_thresholds=None, fig_format="jpg", quality=90, **params):
+    """The reference's plot_roc (eval.py:341): FIG_DIR/roc_iou_{t}.jpg|ppm and, with score thresholds, roc_{m}_iou_{t} per model."""
+    return _plot("roc", "roc", curves, fig_dir, iou_threshold, score_thresholds, fig_format, quality, dict(params))
