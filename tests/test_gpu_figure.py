@@ -94,6 +94,20 @@ def test_rendering_twice_equals_once_and_a_range_writes_only_its_frames(cfg):
     assert np.array_equal(part, frames[1:3]) and np.array_equal(before, init[0]) and np.array_equal(after, init[-1])
 
 
+def test_a_frame_pointer_off_alignment_takes_the_byte_stores_and_writes_the_same_bytes():
+    """160 wide (W % 4 == 0) at a device pointer that is not 4-aligned: the byte path of the store where the width alone takes words"""
+    from vbt_amd.mem import DeviceBuffer
+    fig, _, (_, frames, _, _) = gpu(FC.CONFIGS[0])
+    assert fig.W == 160 and fig.params["scale"] == 1
+    init = noise(1, fig.frame_bytes + 8, 31)[0]
+    buf = DeviceBuffer.from_host(init)
+    assert buf.ptr % 4 == 0
+    fig.render(buf.ptr + 1, 0, 1)
+    got = buf.to_host((fig.frame_bytes + 8,), np.uint8)
+    assert np.array_equal(got[1:1 + fig.frame_bytes], frames[0].reshape(-1))         # figure (a) as the aligned render wrote it
+    assert got[0] == init[0] and np.array_equal(got[1 + fig.frame_bytes:], init[1 + fig.frame_bytes:])
+
+
 def test_refusals_that_need_a_handle_and_the_handle_renders_afterwards():
     from vbt_amd import _lib
     from vbt_amd.figure import Figure

@@ -8,18 +8,20 @@
 //     pixel: a lane per series finds the merged points the tile's columns can meet, the workgroup stages them and the records that
 //     touch the tile in LDS (or reads global memory when they do not fit), and every lane decides four adjacent pixels of two rows
 //     by the contract's test (curve_figure_core.h) and stores them once.  Nothing is read from the frames.
+// Shared with figure.hip: the tile's rectangle, the record staging and the RGB24 store (raster_tile.h), the handle's host side (figure_host.h).
 // Compiled without FMA contraction (-ffp-contract=off, as every unit here: build.py), so the doubles of the contract are the ones a
 // host compiler forms from curve_figure_core.h.
 #include <algorithm>
 #include <climits>
 
-#include "common.h"
 #include "curve_figure_core.h"
+#include "figure_host.h"
+#include "raster_tile.h"
 
 namespace vbt {
 
-constexpr int CF_THREADS = 256;
-constexpr int CF_TILE_W = 256, CF_TILE_H = 8;           // a wavefront stores 768 contiguous bytes of one pixel row at a time; two rows per lane
+constexpr int CF_THREADS = RASTER_THREADS;
+constexpr int CF_TILE_H = 8;                            // two rows per lane (profiles/curve_figure.md)
 constexpr int CF_ROWS_PER_LANE = CF_TILE_H / 4;
 constexpr int32_t CF_NO_ROW = INT32_MIN;                // the row of a non-finite point in the workspace
 
@@ -191,18 +193,7 @@ __device__ __forceinline__ void curve_figure_render_tile(const CfRenderArgs& A, 
       const int cc = (int)(cur[j] >> (8 * e) & 0xffu);
       rgb[e] = cf_rgb(over[e] != CF_KIND_NONE ? oc[e] : (cc != 0xff ? cc : uc[e]));
     }
-    if (A.words) {                                                  // W % 4 == 0: px + 3 < W, and p is 4-aligned
-      uint32_t* w = (uint32_t*)p;
-      w[0] = rgb[0] | (rgb[1] & 0xffu) << 24;
-      w[1] = rgb[1] >> 8 | (rgb[2] & 0xffffu) << 16;
-      w[2] = rgb[2] >> 16 | rgb[3] << 8;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        if (px + e >= G.W) break;
-        p[3 * e] = (uint8_t)rgb[e]; p[3 * e + 1] = (uint8_t)(rgb[e] >> 8); p[3 * e + 2] = (uint8_t)(rgb[e] >> 16);
-      }
-    }
+    store_rgb24x4(p, rgb, n, A.words);                              // W % 4 == 0: px + 3 < W, and p is 4-aligned
   }
 }
 
@@ -216,8 +207,7 @@ __global__ __launch_bounds__(CF_THREADS, 4) void curve_figure_render_kernel(CfRe
   const int K = A.figs[fig].n_series, series0 = A.figs[fig].series0, nrec = A.nrec[fig];
   const int32_t* gp = A.pts + (size_t)fig * A.max_points * CF_PT;
   const int32_t* gr = A.recs + (size_t)fig * A.rec_cap * CF_REC;
-  const int x_lo = (int)(blockIdx.x % A.tiles_x) * CF_TILE_W, y_lo = (int)(blockIdx.x / A.tiles_x) * CF_TILE_H;
-  const int x_hi = (x_lo + CF_TILE_W < G.W ? x_lo + CF_TILE_W : G.W) - 1, y_hi = (y_lo + CF_TILE_H < G.H ? y_lo + CF_TILE_H : G.H) - 1;
+  const TileBox box = tile_box<CF_TILE_H>(A.tiles_x, G.W, G.H);
   if (tid == 0) s_found = 0;
   // the points of the tile's columns: a lane per series, on the whole table
   if (tid < K) {
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(CF_THREADS, 4) void curve_figure_render_kernel(CfRe
     const int m = A.cnt[(size_t)fig * CF_MAX_SERIES + tid];
     const CfSeriesView V{gp + (size_t)sr.off * CF_PT, 0, m, sr.colour};
     int i0, i1, k0, k1;
-    cf_item_range(V, 0, m, G.t, x_lo - G.X0, x_hi - G.X0, &i0, &i1, &k0, &k1);
+    cf_item_range(V, 0, m, G.t, box.x_lo - G.X0, box.x_hi - G.X0, &i0, &i1, &k0, &k1);
     const int first = i0 <= i1 ? (i0 > 0 ? i0 - 1 : 0) : 0;
     S.k0[tid] = k0; S.k1[tid] = k1; S.first[tid] = first; S.np[tid] = i0 <= i1 ? i1 - first + 1 : 0;
     S.m[tid] = m; S.colour[tid] = sr.colour; S.off[tid] = sr.off;
@@ -242,52 +232,36 @@ __global__ __launch_bounds__(CF_THREADS, 4) void curve_figure_render_kernel(CfRe
       at += S.np[k];
     }
   }
-  // the records that touch the tile
-  for (int r = tid; r < nrec; r += CF_THREADS) {
-    const int32_t* q = gr + (size_t)r * CF_REC;
-    if (q[CF_R_X0] > x_hi || q[CF_R_X1] < x_lo || q[CF_R_Y0] > y_hi || q[CF_R_Y1] < y_lo) continue;
-    if (q[CF_R_X0] > q[CF_R_X1] || q[CF_R_Y0] > q[CF_R_Y1]) continue;
-    const int k = atomicAdd(&s_found, 1);
-    if (k < VBT_CURVE_FIGURE_STAGE_RECORDS)
-      for (int e = 0; e < CF_REC; e++) s_recs[k * CF_REC + e] = q[e];
-  }
+  stage_tile_records<CF_REC>(gr, nrec, box, s_recs, VBT_CURVE_FIGURE_STAGE_RECORDS, &s_found);
   __syncthreads();
   const int found = s_found;
   uint8_t* frame = A.frames + (size_t)blockIdx.y * A.frame_bytes;
   if (pts_staged && found <= VBT_CURVE_FIGURE_STAGE_RECORDS)
-    curve_figure_render_tile(A, S, K, s_pts, true, s_recs, found, x_lo, y_lo, frame);
+    curve_figure_render_tile(A, S, K, s_pts, true, s_recs, found, box.x_lo, box.y_lo, frame);
   else                                                              // long curves or a crowded tile: the same statements on global memory
-    curve_figure_render_tile(A, S, K, gp, false, gr, nrec, x_lo, y_lo, frame);
+    curve_figure_render_tile(A, S, K, gp, false, gr, nrec, box.x_lo, box.y_lo, frame);
 }
 
 }  // namespace vbt
 
 using namespace vbt;
 
-struct vbt_curve_figure {
-  int device = 0;
+struct vbt_curve_figure : FigureHandle {   // blob: upload (figures | series | marks | points) | workspace | pts | recs | nrec | cnt
   vbt_curve_figure_params prm{};
   CfGeom G{};
-  int rec_cap = 0;
-  uint8_t* blob = nullptr;             // upload (figures | series | marks | points) | workspace | pts | cnt | recs | nrec in one allocation
-  size_t up_cap = 0;
-  int32_t *d_col = nullptr, *d_row = nullptr, *d_pts = nullptr, *d_cnt = nullptr, *d_recs = nullptr, *d_nrec = nullptr;
+  int32_t *d_col = nullptr, *d_row = nullptr, *d_pts = nullptr, *d_cnt = nullptr;
   unsigned long long *d_lo = nullptr, *d_hi = nullptr;
   const CfFigure* d_figs = nullptr;    // inside the upload of the last set
   const CfSeries* d_series = nullptr;
-  int n = 0;                           // figures set
   std::vector<CfFigure> figs;          // the host's copies
   std::vector<CfSeries> series;
-  hipStream_t last = nullptr;          // the stream of the last set or render: vbt_curve_figure_table waits for it
 };
 
 namespace {
 
 int check_curve_figure_params(const vbt_curve_figure_params& p) {
   const char* who = "vbt_curve_figure_create";
-  if (p.width < 1 || p.width > 16384 || p.height < 1 || p.height > 16384) { set_error("%s: figures of 1..16384 pixels a side, got %d x %d", who, p.width, p.height); return VBT_ERR_ARG; }
-  if (p.scale < 1 || p.scale > 64) { set_error("%s: scale %d outside 1..64", who, p.scale); return VBT_ERR_ARG; }
-  if (p.thickness < 1 || p.thickness > 64) { set_error("%s: thickness %d outside 1..64", who, p.thickness); return VBT_ERR_ARG; }
+  if (int rc = check_canvas(who, p.width, p.height, p.scale, p.thickness)) return rc;
   if (p.max_figures < 1 || p.max_figures > CF_MAX_FIGURES) { set_error("%s: max_figures %d outside 1..%d", who, p.max_figures, (int)CF_MAX_FIGURES); return VBT_ERR_ARG; }
   if (p.max_series < 1 || p.max_series > CF_MAX_SERIES) { set_error("%s: max_series %d outside 1..%d", who, p.max_series, (int)CF_MAX_SERIES); return VBT_ERR_ARG; }
   if (p.max_points < 1 || p.max_points > CF_MAX_POINTS) { set_error("%s: max_points %d outside 1..%d", who, p.max_points, (int)CF_MAX_POINTS); return VBT_ERR_ARG; }
@@ -296,13 +270,7 @@ int check_curve_figure_params(const vbt_curve_figure_params& p) {
     set_error("%s: %d figures of %d points: above 2^26 points in all", who, p.max_figures, p.max_points);
     return VBT_ERR_ARG;
   }
-  const CfGeom G = cf_geom(p.width, p.height, p.scale, p.thickness);
-  if (G.PW < CF_MIN_PLOT || G.PH < CF_MIN_PLOT) {
-    set_error("%s: a %d x %d figure at scale %d leaves a plot rectangle of %d x %d, below %d x %d", who, p.width, p.height, p.scale, G.PW, G.PH,
-              (int)CF_MIN_PLOT, (int)CF_MIN_PLOT);
-    return VBT_ERR_ARG;
-  }
-  return VBT_OK;
+  return check_plot_rect(who, cf_geom(p.width, p.height, p.scale, p.thickness), CF_MIN_PLOT);
 }
 
 // 0: n < cap bytes of 0x20..0x7E and a NUL; 1: no NUL; 2: a byte outside (at *at)
@@ -390,8 +358,6 @@ int check_curve_figure_set(int n, const vbt_curve_figure_desc* figs, const vbt_c
   return VBT_OK;
 }
 
-size_t cf_align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 }  // namespace
 
 extern "C" {
@@ -414,34 +380,24 @@ int vbt_curve_figure_create(int device, const vbt_curve_figure_params* params, v
   f->device = device; f->prm = p; f->G = cf_geom(p.width, p.height, p.scale, p.thickness);
   f->rec_cap = CF_FIXED_RECS + 1 + 2 * p.max_series + 3 * p.max_marks;
   const size_t F = (size_t)p.max_figures, P = (size_t)p.max_points;
-  f->up_cap = cf_align64(F * sizeof(CfFigure)) + cf_align64(F * p.max_series * sizeof(CfSeries)) + cf_align64(F * p.max_marks * sizeof(CfMark)) + F * P * 16;
-  const size_t up_b = cf_align64(f->up_cap), i32_b = cf_align64(F * P * 4), key_b = cf_align64(F * P * 8), pts_b = cf_align64(F * P * CF_PT * 4);
-  const size_t cnt_b = cf_align64(F * CF_MAX_SERIES * 4), recs_b = cf_align64(F * (size_t)f->rec_cap * CF_REC * 4), nrec_b = cf_align64(F * 4);
-  const size_t total = up_b + 2 * key_b + 2 * i32_b + pts_b + cnt_b + recs_b + nrec_b;
-  if (hipMalloc((void**)&f->blob, total) != hipSuccess) {
+  Carver C;                                                          // the largest upload, at the blob's head
+  C.add<uint8_t>(align64(F * sizeof(CfFigure)) + align64(F * p.max_series * sizeof(CfSeries)) + align64(F * p.max_marks * sizeof(CfMark)) + F * P * 16);
+  const auto lo = C.add<unsigned long long>(F * P), hi = C.add<unsigned long long>(F * P);
+  const auto col = C.add<int32_t>(F * P), row = C.add<int32_t>(F * P), pts = C.add<int32_t>(F * P * CF_PT);
+  const auto recs = C.add<int32_t>(F * (size_t)f->rec_cap * CF_REC), nrec = C.add<int32_t>(F), cnt = C.add<int32_t>(F * CF_MAX_SERIES);
+  if (hipMalloc((void**)&f->blob, C.bytes()) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("vbt_curve_figure_create: the device cannot give %zu bytes for %d figures of %d points, %d series and %d marks", total, p.max_figures, p.max_points,
-              p.max_series, p.max_marks);
+    set_error("vbt_curve_figure_create: the device cannot give %zu bytes for %d figures of %d points, %d series and %d marks", C.bytes(), p.max_figures,
+              p.max_points, p.max_series, p.max_marks);
     return VBT_ERR_HIP;
   }
-  uint8_t* q = f->blob + up_b;
-  f->d_lo = (unsigned long long*)q; q += key_b;
-  f->d_hi = (unsigned long long*)q; q += key_b;
-  f->d_col = (int32_t*)q; q += i32_b;
-  f->d_row = (int32_t*)q; q += i32_b;
-  f->d_pts = (int32_t*)q; q += pts_b;
-  f->d_cnt = (int32_t*)q; q += cnt_b;
-  f->d_recs = (int32_t*)q; q += recs_b;
-  f->d_nrec = (int32_t*)q;
+  f->d_lo = C.ptr(f->blob, lo); f->d_hi = C.ptr(f->blob, hi); f->d_col = C.ptr(f->blob, col); f->d_row = C.ptr(f->blob, row);
+  f->d_pts = C.ptr(f->blob, pts); f->d_recs = C.ptr(f->blob, recs); f->d_nrec = C.ptr(f->blob, nrec); f->d_cnt = C.ptr(f->blob, cnt);
   *out = f.release();
   return VBT_OK;
 }
 
-void vbt_curve_figure_destroy(vbt_curve_figure* f) {
-  if (!f) return;
-  if (hipSetDevice(f->device) == hipSuccess && f->blob) (void)hipFree(f->blob);   // (waits for the launches still using it)
-  delete f;
-}
+void vbt_curve_figure_destroy(vbt_curve_figure* f) { delete f; }
 
 int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc* figs, const vbt_curve_series* series, const double* xy,
                          const vbt_curve_mark* marks, void* stream) {
@@ -465,7 +421,7 @@ int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc
   VBT_HIP_CHECK(hipSetDevice(f->device));
   f->n = 0;
   if (n == 0) return VBT_OK;
-  const size_t figs_b = cf_align64((size_t)n * sizeof(CfFigure)), ser_b = cf_align64(T.series * sizeof(CfSeries)), mk_b = cf_align64(T.marks * sizeof(CfMark));
+  const size_t figs_b = align64((size_t)n * sizeof(CfFigure)), ser_b = align64(T.series * sizeof(CfSeries)), mk_b = align64(T.marks * sizeof(CfMark));
   std::vector<uint8_t> up(figs_b + ser_b + mk_b + T.points * 16, 0);
   CfFigure* hf = (CfFigure*)up.data();
   CfSeries* hs = (CfSeries*)(up.data() + figs_b);
@@ -500,27 +456,23 @@ int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc
     curve_figure_prepare_kernel<<<dim3((unsigned)n), CF_THREADS, 0, st>>>(A);
     e = hipGetLastError();
   }
-  const hipError_t es = hipStreamSynchronize(st);                  // (`up` leaves scope: the copy must have read it)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) { set_error("vbt_curve_figure_set failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  if (int rc = f->finish_set(who, st, e)) return rc;                   // (`up` leaves scope: the copy must have read it)
   f->figs.assign(hf, hf + n);
   f->series.assign(hs, hs + T.series);
   f->d_figs = (const CfFigure*)f->blob; f->d_series = (const CfSeries*)(f->blob + figs_b);
-  f->n = n; f->last = st;
+  f->n = n;
   return VBT_OK;
 }
 
 int vbt_curve_figure_render(vbt_curve_figure* f, uint8_t* frames_dev, int fig0, int n, void* stream) {
-  if (!f || !frames_dev) { set_error("vbt_curve_figure_render: NULL argument (handle %p, frames %p)", (void*)f, (void*)frames_dev); return VBT_ERR_ARG; }
-  if (f->n == 0) { set_error("vbt_curve_figure_render: no figures are set (vbt_curve_figure_set)"); return VBT_ERR_STATE; }
-  if (fig0 < 0 || n < 0 || (long)fig0 + n > f->n) { set_error("vbt_curve_figure_render: figures %d .. %ld outside the %d that are set", fig0, (long)fig0 + n - 1, f->n); return VBT_ERR_ARG; }
+  if (int rc = check_render_args("vbt_curve_figure_render", "vbt_curve_figure_set", f, frames_dev, fig0, n)) return rc;
   if (n == 0) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(f->device));
   CfRenderArgs A{};
   A.figs = f->d_figs; A.series = f->d_series; A.pts = f->d_pts; A.cnt = f->d_cnt; A.recs = f->d_recs; A.nrec = f->d_nrec;
   A.frames = frames_dev; A.frame_bytes = (size_t)f->G.W * f->G.H * 3;
   A.G = f->G; A.max_points = f->prm.max_points; A.rec_cap = f->rec_cap; A.fig0 = fig0;
-  A.tiles_x = (f->G.W + CF_TILE_W - 1) / CF_TILE_W;
+  A.tiles_x = (f->G.W + RASTER_TILE_W - 1) / RASTER_TILE_W;
   A.words = f->G.W % 4 == 0 && ((uintptr_t)frames_dev & 3) == 0;
   const int tiles_y = (f->G.H + CF_TILE_H - 1) / CF_TILE_H;
   curve_figure_render_kernel<<<dim3((unsigned)(A.tiles_x * tiles_y), (unsigned)n), CF_THREADS, 0, (hipStream_t)stream>>>(A);
@@ -536,13 +488,9 @@ int vbt_curve_figure_table(vbt_curve_figure* f, int fig, int32_t* counts, int ca
     set_error("vbt_curve_figure_table: bad argument");
     return VBT_ERR_ARG;
   }
-  if (f->n == 0) { set_error("vbt_curve_figure_table: no figures are set (vbt_curve_figure_set)"); return VBT_ERR_STATE; }
-  if (fig < 0 || fig >= f->n) { set_error("vbt_curve_figure_table: figure %d outside the %d that are set", fig, f->n); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipSetDevice(f->device));
-  VBT_HIP_CHECK(hipStreamSynchronize(f->last));
-  const CfFigure& F = f->figs[(size_t)fig];
   int32_t nrec = 0, cnt[CF_MAX_SERIES] = {};
-  VBT_HIP_CHECK(hipMemcpy(&nrec, f->d_nrec + fig, 4, hipMemcpyDeviceToHost));
+  if (int rc = table_begin("vbt_curve_figure_table", "vbt_curve_figure_set", f, fig, &nrec)) return rc;
+  const CfFigure& F = f->figs[(size_t)fig];
   VBT_HIP_CHECK(hipMemcpy(cnt, f->d_cnt + (size_t)fig * CF_MAX_SERIES, sizeof(cnt), hipMemcpyDeviceToHost));
   long total = 0;
   for (int k = 0; k < F.n_series; k++) total += cnt[k];

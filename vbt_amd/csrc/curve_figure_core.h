@@ -1,9 +1,10 @@
 // Curve figure (include/vbt_hip.h, "Curve figure"): layout, axes, records, the run merge and the test of one pixel, as host + device
-// functions of plain integers and doubles.  vbt_curve_figure_set's validation, the kernels of curve_figure.hip and a host program
+// functions of plain integers and doubles, on the record table, text test and segment test of raster_core.h (and on nothing of the rep
+// figure's).  vbt_curve_figure_set's validation, the kernels of curve_figure.hip and a host program
 // (tests/fuzz/curve_figure_check.cc) run these statements.  Every double is formed one IEEE operation per statement, without contraction.
 #pragma once
 #include "curve_font.h"
-#include "figure_core.h"
+#include "raster_core.h"
 
 namespace vbt {
 
@@ -12,8 +13,8 @@ enum { CF_CELLS_LEFT = 30, CF_CELLS_RIGHT = 4, CF_CELLS_TOP = 4, CF_CELLS_BOTTOM
 enum { CF_MAX_FIGURES = 1024, CF_MAX_SERIES = 16, CF_MAX_POINTS = 1 << 22, CF_MAX_MARKS = 64, CF_PALETTE = 10 };
 enum { CF_TEXT_MAX = 63, CF_MARK_TEXT_MAX = 15, CF_TITLE_MAX = 31, CF_MINOR_MIN = 20, CF_MINOR_MAX = 1000 };
 enum { CF_PT_COL = 0, CF_PT_ROW, CF_PT_JOIN, CF_PT = 3 };      // merged point: column, row, 1 when a segment joins it to the point before
-// record: 28 int32.  [x0, x1] x [y0, y1] is what of it can be seen (frame coordinates, clipped; empty when x0 > x1 or y0 > y1)
-enum { CF_R_KIND = 0, CF_R_X0, CF_R_Y0, CF_R_X1, CF_R_Y1, CF_R_OX, CF_R_OY, CF_R_VALUE, CF_R_AUX, CF_R_N, CF_R_CHARS = 12, CF_REC = 28 };
+// record: 28 int32, the layout CfRec of raster_core.h
+enum { CF_R_VALUE = CfRec::VALUE, CF_R_AUX = CfRec::AUX, CF_REC = CfRec::REC };
 // the kinds are the priorities of "one writer per pixel": the smallest kind that covers a pixel decides it; 6 is the curves' place
 enum { CF_KIND_LEGEND_TEXT = 0, CF_KIND_SWATCH, CF_KIND_LEGEND_BOX, CF_KIND_MARK_TEXT, CF_KIND_MARKER, CF_KIND_LEADER, CF_KIND_CURVES,
        CF_KIND_LINE, CF_KIND_TEXT, CF_KIND_GRID_MAJOR, CF_KIND_GRID_MINOR, CF_KIND_NONE };
@@ -127,43 +128,6 @@ __host__ __device__ inline int cf_merge_series(const double* xy, int n, int rev,
 
 // ---- records ----
 
-struct CfRecs {
-  int32_t* rec;
-  int cap, n;
-};
-
-__host__ __device__ inline int32_t* cf_new_rec(CfRecs& R, int kind) {
-  if (R.n >= R.cap) return nullptr;                                    // (never: the capacity is sized for every record of a figure)
-  int32_t* r = R.rec + (size_t)R.n * CF_REC;
-  for (int k = 0; k < CF_REC; k++) r[k] = 0;
-  r[CF_R_KIND] = kind;
-  R.n++;
-  return r;
-}
-
-struct CfClip { int x0, y0, x1, y1; };
-
-// a rectangle [x0, x1] x [y0, y1] clipped to c
-__host__ __device__ inline void cf_box_rec(CfRecs& R, int kind, int x0, int y0, int x1, int y1, const CfClip& c, int value, int aux) {
-  int32_t* r = cf_new_rec(R, kind);
-  if (!r) return;
-  r[CF_R_X0] = x0 > c.x0 ? x0 : c.x0; r[CF_R_Y0] = y0 > c.y0 ? y0 : c.y0;
-  r[CF_R_X1] = x1 < c.x1 ? x1 : c.x1; r[CF_R_Y1] = y1 < c.y1 ? y1 : c.y1;
-  r[CF_R_OX] = x0; r[CF_R_OY] = y0; r[CF_R_VALUE] = value; r[CF_R_AUX] = aux;
-}
-
-// n bytes of text whose box has its top left corner at (ox, oy); rot: turned a quarter so that it reads bottom to top
-__host__ __device__ inline void cf_text_rec(CfRecs& R, int kind, int s, int ox, int oy, const uint8_t* chars, int n, int rot, const CfClip& c, int value) {
-  int32_t* r = cf_new_rec(R, kind);
-  if (!r) return;
-  const int wu = (6 * n - 1) * s, hu = 7 * s;
-  const int x1 = ox + (rot ? hu : wu) - 1, y1 = oy + (rot ? wu : hu) - 1;
-  r[CF_R_X0] = ox > c.x0 ? ox : c.x0; r[CF_R_Y0] = oy > c.y0 ? oy : c.y0;
-  r[CF_R_X1] = x1 < c.x1 ? x1 : c.x1; r[CF_R_Y1] = y1 < c.y1 ? y1 : c.y1;
-  r[CF_R_OX] = ox; r[CF_R_OY] = oy; r[CF_R_VALUE] = value; r[CF_R_AUX] = rot; r[CF_R_N] = n;
-  for (int k = 0; k < n; k++) r[CF_R_CHARS + k / 4] |= (int32_t)((uint32_t)chars[k] << (8 * (k % 4)));
-}
-
 __host__ __device__ inline int cf_strlen(const uint8_t* s, int cap) {
   int n = 0;
   while (n < cap && s[n]) n++;
@@ -186,12 +150,12 @@ struct CfMark {
 
 // All records of a figure in table order.  xy: the figure's points (series k at xy + 2 off_k).
 __host__ __device__ inline int cf_records(const CfGeom& G, const CfFigure& F, const CfSeries* ser, const CfMark* marks, const double* xy, int32_t* rec, int cap) {
-  CfRecs R{rec, cap, 0};
+  Recs R{rec, cap, 0};
   const int s = G.s, W = G.W, H = G.H, X0 = G.X0, Y0 = G.Y0, PW = G.PW, PH = G.PH, b = (s + 1) / 2;
-  const CfClip frame{0, 0, W - 1, H - 1}, plot{X0, Y0, X0 + PW - 1, Y0 + PH - 1};
+  const Clip frame{0, 0, W - 1, H - 1}, plot{X0, Y0, X0 + PW - 1, Y0 + PH - 1};
   // 1. spines: left, bottom
-  cf_box_rec(R, CF_KIND_LINE, X0 - s, Y0, X0 - 1, Y0 + PH + s - 1, frame, 0, 0);
-  cf_box_rec(R, CF_KIND_LINE, X0, Y0 + PH, X0 + PW - 1, Y0 + PH + s - 1, frame, 0, 0);
+  rec_box<CfRec>(R, CF_KIND_LINE, X0 - s, Y0, X0 - 1, Y0 + PH + s - 1, frame, 0, 0);
+  rec_box<CfRec>(R, CF_KIND_LINE, X0, Y0 + PH, X0 + PW - 1, Y0 + PH + s - 1, frame, 0, 0);
   // 2. major ticks with their labels and grid lines: x axis, then y axis, 0.0 .. 1.0
   for (int axis = 0; axis < 2; axis++)
     for (int k = 0; k <= 5; k++) {
@@ -200,14 +164,14 @@ __host__ __device__ inline int cf_records(const CfGeom& G, const CfFigure& F, co
       const uint8_t ch[3] = {(uint8_t)('0' + k / 5), '.', (uint8_t)('0' + 2 * k % 10)};
       if (axis == 0) {
         const int x = X0 + cf_col(v, PW);
-        cf_box_rec(R, CF_KIND_LINE, x - s / 2, Y0 + PH + s, x - s / 2 + s - 1, Y0 + PH + 4 * s - 1, frame, milli, 0);
-        cf_text_rec(R, CF_KIND_TEXT, s, x - (17 * s) / 2, Y0 + PH + 5 * s, ch, 3, 0, frame, milli);
-        cf_box_rec(R, CF_KIND_GRID_MAJOR, x, Y0, x + b - 1, Y0 + PH - 1, plot, milli, 0);
+        rec_box<CfRec>(R, CF_KIND_LINE, x - s / 2, Y0 + PH + s, x - s / 2 + s - 1, Y0 + PH + 4 * s - 1, frame, milli, 0);
+        rec_text<CfRec>(R, CF_KIND_TEXT, s, x - (17 * s) / 2, Y0 + PH + 5 * s, ch, 3, 0, frame, milli);
+        rec_box<CfRec>(R, CF_KIND_GRID_MAJOR, x, Y0, x + b - 1, Y0 + PH - 1, plot, milli, 0);
       } else {
         const int y = Y0 + cf_row(v, PH);
-        cf_box_rec(R, CF_KIND_LINE, X0 - 4 * s, y - s / 2, X0 - s - 1, y - s / 2 + s - 1, frame, milli, 1);
-        cf_text_rec(R, CF_KIND_TEXT, s, X0 - 22 * s, y - 3 * s, ch, 3, 0, frame, milli);
-        cf_box_rec(R, CF_KIND_GRID_MAJOR, X0, y, X0 + PW - 1, y + b - 1, plot, milli, 1);
+        rec_box<CfRec>(R, CF_KIND_LINE, X0 - 4 * s, y - s / 2, X0 - s - 1, y - s / 2 + s - 1, frame, milli, 1);
+        rec_text<CfRec>(R, CF_KIND_TEXT, s, X0 - 22 * s, y - 3 * s, ch, 3, 0, frame, milli);
+        rec_box<CfRec>(R, CF_KIND_GRID_MAJOR, X0, y, X0 + PW - 1, y + b - 1, plot, milli, 1);
       }
     }
   // 3. minor grid lines: the multiples of the step up to 1000 that are no major tick
@@ -217,26 +181,26 @@ __host__ __device__ inline int cf_records(const CfGeom& G, const CfFigure& F, co
     for (int milli = step; milli <= 1000; milli += step) {
       if (milli % 200 == 0) continue;
       const double v = (double)milli / 1000.0;
-      if (axis == 0) { const int x = X0 + cf_col(v, PW); cf_box_rec(R, CF_KIND_GRID_MINOR, x, Y0, x + b - 1, Y0 + PH - 1, plot, milli, 0); }
-      else { const int y = Y0 + cf_row(v, PH); cf_box_rec(R, CF_KIND_GRID_MINOR, X0, y, X0 + PW - 1, y + b - 1, plot, milli, 1); }
+      if (axis == 0) { const int x = X0 + cf_col(v, PW); rec_box<CfRec>(R, CF_KIND_GRID_MINOR, x, Y0, x + b - 1, Y0 + PH - 1, plot, milli, 0); }
+      else { const int y = Y0 + cf_row(v, PH); rec_box<CfRec>(R, CF_KIND_GRID_MINOR, X0, y, X0 + PW - 1, y + b - 1, plot, milli, 1); }
     }
   }
   // 4. axis titles
   const int nx = cf_strlen(F.x_title, CF_TITLE_MAX), ny = cf_strlen(F.y_title, CF_TITLE_MAX);
-  if (nx) cf_text_rec(R, CF_KIND_TEXT, s, X0 + (PW - (6 * nx - 1) * s) / 2, Y0 + PH + 14 * s, F.x_title, nx, 0, frame, 0);
-  if (ny) cf_text_rec(R, CF_KIND_TEXT, s, s, Y0 + (PH - (6 * ny - 1) * s) / 2, F.y_title, ny, 1, frame, 0);
+  if (nx) rec_text<CfRec>(R, CF_KIND_TEXT, s, X0 + (PW - text_width(nx, s)) / 2, Y0 + PH + 14 * s, F.x_title, nx, 0, frame, 0);
+  if (ny) rec_text<CfRec>(R, CF_KIND_TEXT, s, s, Y0 + (PH - text_width(ny, s)) / 2, F.y_title, ny, 1, frame, 0);
   // 5. legend: the box, then a swatch and a text per series
   const int K = F.n_series;
   if (K > 0) {
     int L = 0;
     for (int k = 0; k < K; k++) { const int n = cf_strlen(ser[k].text, CF_TEXT_MAX); L = n > L ? n : L; }
-    const int BW = (L ? (6 * L - 1) * s : 0) + 16 * s, BH = 9 * s * K + 4 * s;
+    const int BW = (L ? text_width(L, s) : 0) + 16 * s, BH = 9 * s * K + 4 * s;
     const int bx = F.corner == CF_LEGEND_LOWER_RIGHT ? X0 + PW - 3 * s - BW : X0 + 3 * s, by = Y0 + PH - 3 * s - BH;
-    cf_box_rec(R, CF_KIND_LEGEND_BOX, bx, by, bx + BW - 1, by + BH - 1, frame, BW, BH);
+    rec_box<CfRec>(R, CF_KIND_LEGEND_BOX, bx, by, bx + BW - 1, by + BH - 1, frame, BW, BH);
     for (int k = 0; k < K; k++) {
       const int ty = by + 3 * s + 9 * s * k;
-      cf_box_rec(R, CF_KIND_SWATCH, bx + 3 * s, ty + 2 * s, bx + 11 * s - 1, ty + 5 * s - 1, frame, k, ser[k].colour);
-      cf_text_rec(R, CF_KIND_LEGEND_TEXT, s, bx + 13 * s, ty, ser[k].text, cf_strlen(ser[k].text, CF_TEXT_MAX), 0, frame, k);
+      rec_box<CfRec>(R, CF_KIND_SWATCH, bx + 3 * s, ty + 2 * s, bx + 11 * s - 1, ty + 5 * s - 1, frame, k, ser[k].colour);
+      rec_text<CfRec>(R, CF_KIND_LEGEND_TEXT, s, bx + 13 * s, ty, ser[k].text, cf_strlen(ser[k].text, CF_TEXT_MAX), 0, frame, k);
     }
   }
   // 6. marks: text, marker, leader each
@@ -247,60 +211,46 @@ __host__ __device__ inline int cf_records(const CfGeom& G, const CfFigure& F, co
     const double* p = xy + (size_t)2 * ((size_t)S.off + (size_t)mk.point);
     const int n = cf_strlen(mk.text, CF_MARK_TEXT_MAX);
     if (!cf_point_finite(p)) {                                          // nothing of it can be seen
-      const CfClip none{0, 0, -1, -1};
-      cf_text_rec(R, CF_KIND_MARK_TEXT, s, 0, 0, mk.text, n, 0, none, i);
-      cf_box_rec(R, CF_KIND_MARKER, 0, 0, -1, -1, none, 0, 0);
-      cf_box_rec(R, CF_KIND_LEADER, 0, 0, -1, -1, none, 0, 0);
+      const Clip none{0, 0, -1, -1};
+      rec_text<CfRec>(R, CF_KIND_MARK_TEXT, s, 0, 0, mk.text, n, 0, none, i);
+      rec_box<CfRec>(R, CF_KIND_MARKER, 0, 0, -1, -1, none, 0, 0);
+      rec_box<CfRec>(R, CF_KIND_LEADER, 0, 0, -1, -1, none, 0, 0);
       continue;
     }
-    const int px = X0 + cf_col(p[0], PW), py = Y0 + cf_row(p[1], PH), wu = (6 * n - 1) * s, rad = 2 * s;
+    const int px = X0 + cf_col(p[0], PW), py = Y0 + cf_row(p[1], PH), wu = text_width(n, s), rad = 2 * s;
     int ax, ay, ox;
     if (F.corner == CF_LEGEND_LOWER_RIGHT) { ax = px + (M - i) * 6 * s; ay = py + (i + 1) * 10 * s; ox = ax; }
     else { ax = px - 8 * s; ay = py + ((i < 3 ? i : 3) + 1) * 10 * s; ox = ax - wu + 1; }
-    cf_text_rec(R, CF_KIND_MARK_TEXT, s, ox, ay, mk.text, n, 0, frame, i);
-    cf_box_rec(R, CF_KIND_MARKER, px - rad, py - rad, px + rad, py + rad, frame, px, py);
-    // the leader from the text's corner (ox, oy of the record) to the point (value, aux)
-    int32_t* r = cf_new_rec(R, CF_KIND_LEADER);
-    if (r) {
-      const int x0 = (ax < px ? ax : px) - 1, x1 = (ax < px ? px : ax) + 1, y0 = (ay < py ? ay : py) - 1, y1 = (ay < py ? py : ay) + 1;
-      r[CF_R_X0] = x0 > 0 ? x0 : 0; r[CF_R_Y0] = y0 > 0 ? y0 : 0; r[CF_R_X1] = x1 < W - 1 ? x1 : W - 1; r[CF_R_Y1] = y1 < H - 1 ? y1 : H - 1;
-      r[CF_R_OX] = ax; r[CF_R_OY] = ay; r[CF_R_VALUE] = px; r[CF_R_AUX] = py;
-    }
+    rec_text<CfRec>(R, CF_KIND_MARK_TEXT, s, ox, ay, mk.text, n, 0, frame, i);
+    rec_box<CfRec>(R, CF_KIND_MARKER, px - rad, py - rad, px + rad, py + rad, frame, px, py);
+    // the leader from the text's corner (ox, oy of the record) to the point (value, aux): the box around both, a pixel wider
+    int32_t* r = rec_box<CfRec>(R, CF_KIND_LEADER, (ax < px ? ax : px) - 1, (ay < py ? ay : py) - 1, (ax < px ? px : ax) + 1, (ay < py ? py : ay) + 1, frame, px, py);
+    if (r) { r[REC_OX] = ax; r[REC_OY] = ay; }
   }
   return R.n;
 }
 
 // ---- one pixel ----
 
-__host__ __device__ inline bool cf_text_covers(const int32_t* r, int s, int px, int py) {
-  const int n = r[CF_R_N], rot = r[CF_R_AUX];
-  const int rx = px - r[CF_R_OX], ry = py - r[CF_R_OY];
-  const int ux = rot ? (6 * n - 1) * s - 1 - ry : rx, uy = rot ? rx : ry;
-  const int k = ux / (6 * s), c = (ux - k * 6 * s) / s, row = uy / s;
-  if (c >= 5) return false;
-  const int ch = (int)(((uint32_t)r[CF_R_CHARS + k / 4] >> (8 * (k % 4))) & 255u);
-  return (cf_glyph(ch) >> (5 * (6 - row) + 4 - c)) & 1;
-}
-
 // the colour index record r gives pixel (px, py) of its visible box, -1 when it does not cover it
 __host__ __device__ inline int cf_record_colour(const int32_t* r, int s, int px, int py) {
   const int b = (s + 1) / 2;
-  switch (r[CF_R_KIND]) {
-    case CF_KIND_LEGEND_TEXT: case CF_KIND_MARK_TEXT: case CF_KIND_TEXT: return cf_text_covers(r, s, px, py) ? CF_C_INK : -1;
+  switch (r[REC_KIND]) {
+    case CF_KIND_LEGEND_TEXT: case CF_KIND_MARK_TEXT: case CF_KIND_TEXT: return text_covers<CfRec, cf_glyph>(r, s, px, py) ? CF_C_INK : -1;
     case CF_KIND_SWATCH: return CF_C_SERIES + r[CF_R_AUX];
     case CF_KIND_LEGEND_BOX: {
-      const int rx = px - r[CF_R_OX], ry = py - r[CF_R_OY];
+      const int rx = px - r[REC_OX], ry = py - r[REC_OY];
       return rx < b || ry < b || rx >= r[CF_R_VALUE] - b || ry >= r[CF_R_AUX] - b ? CF_C_BORDER : CF_C_WHITE;
     }
     case CF_KIND_MARKER: {
-      const int64_t dx = px - r[CF_R_VALUE], dy = py - r[CF_R_AUX], rad = r[CF_R_VALUE] - r[CF_R_OX];
+      const int64_t dx = px - r[CF_R_VALUE], dy = py - r[CF_R_AUX], rad = r[CF_R_VALUE] - r[REC_OX];
       return dx * dx + dy * dy <= rad * rad ? CF_C_INK : -1;
     }
-    case CF_KIND_LEADER: return ov_segment_covers(px, py, r[CF_R_OX], r[CF_R_OY], r[CF_R_VALUE], r[CF_R_AUX], 1) ? CF_C_INK : -1;
+    case CF_KIND_LEADER: return ov_segment_covers(px, py, r[REC_OX], r[REC_OY], r[CF_R_VALUE], r[CF_R_AUX], 1) ? CF_C_INK : -1;
     case CF_KIND_LINE: return CF_C_INK;
     case CF_KIND_GRID_MAJOR: return CF_C_GRID_MAJOR;
     case CF_KIND_GRID_MINOR: {                                          // dotted: one block of b pixels in three along the line
-      const int along = r[CF_R_AUX] ? px - r[CF_R_OX] : py - r[CF_R_OY];
+      const int along = r[CF_R_AUX] ? px - r[REC_OX] : py - r[REC_OY];
       return (along / b) % 3 == 0 ? CF_C_GRID_MINOR : -1;
     }
     default: return -1;
@@ -313,9 +263,9 @@ __host__ __device__ inline void cf_records4(const int32_t* recs, int nrec, int s
   for (int e = 0; e < 4; e++) { over[e] = CF_KIND_NONE; under[e] = CF_KIND_NONE; oc[e] = CF_C_WHITE; uc[e] = CF_C_WHITE; }
   for (int k = 0; k < nrec; k++) {
     const int32_t* r = recs + (size_t)k * CF_REC;
-    const int x0 = r[CF_R_X0], x1 = r[CF_R_X1];
-    if (px + n - 1 < x0 || px > x1 || py < r[CF_R_Y0] || py > r[CF_R_Y1]) continue;
-    const int kind = r[CF_R_KIND];
+    const int x0 = r[REC_X0], x1 = r[REC_X1];
+    if (px + n - 1 < x0 || px > x1 || py < r[REC_Y0] || py > r[REC_Y1]) continue;
+    const int kind = r[REC_KIND];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -335,15 +285,6 @@ struct CfSeriesView {
   int base, m, colour;
 };
 
-// first point i of [lo, hi) with col_i >= v, hi if none; the columns do not decrease
-__host__ __device__ inline int cf_col_lower_bound(const CfSeriesView& V, int lo, int hi, int v) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (V.pts[(size_t)(mid - V.base) * CF_PT] >= v) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
 // Item i of a series is the segment from point i - 1 to point i when point i is joined, else the dot of point i.  The items that can
 // cover a pixel of columns [pa, pb] (rectangle coordinates) are [*i0, *i1]: col_i >= pa - h and col_{i-1} <= pb + h, h = (t + 1) / 2.
 // Empty: *i0 > *i1.  [lo, hi) is a range of points known to hold both bounds ([0, m), or bounds *k0, *k1 found for columns that contain
@@ -351,7 +292,7 @@ __host__ __device__ inline int cf_col_lower_bound(const CfSeriesView& V, int lo,
 __host__ __device__ inline void cf_item_range(const CfSeriesView& V, int lo, int hi, int t, int pa, int pb, int* i0, int* i1, int* k0_out, int* k1_out) {
   if (V.m <= 0) { *i0 = 0; *i1 = -1; *k0_out = 0; *k1_out = 0; return; }
   const int h = (t + 1) / 2;
-  const int k0 = cf_col_lower_bound(V, lo, hi, pa - h), k1 = cf_col_lower_bound(V, lo, hi, pb + h + 1);
+  const int k0 = col_lower_bound(V.pts, CF_PT, V.base, lo, hi, pa - h), k1 = col_lower_bound(V.pts, CF_PT, V.base, lo, hi, pb + h + 1);
   *i0 = k0;
   *i1 = k1 < V.m ? k1 : V.m - 1;
   *k0_out = k0; *k1_out = k1;
@@ -367,15 +308,7 @@ __host__ __device__ inline unsigned cf_curve_mask(const CfSeriesView& V, int t, 
   for (int i = i0; i <= i1; i++) {
     const int32_t* b = V.pts + (size_t)(i - V.base) * CF_PT;
     const int32_t* a = b[CF_PT_JOIN] ? b - CF_PT : b;
-    const int ca = a[CF_PT_COL], cb = b[CF_PT_COL], ra = a[CF_PT_ROW], rb = b[CF_PT_ROW];
-    if (qx0 + n - 1 < ca - h || qx0 > cb + h || qy < (ra < rb ? ra : rb) - h || qy > (ra < rb ? rb : ra) + h) continue;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int e = 0; e < 4; e++) {
-      const int qx = qx0 + e;
-      if (e < n && qx >= 0 && qx < PW && ov_segment_covers(qx, qy, ca, ra, cb, rb, t)) m |= 1u << e;
-    }
+    m |= quad_segment_mask(qx0, n, qy, PW, a[CF_PT_COL], a[CF_PT_ROW], b[CF_PT_COL], b[CF_PT_ROW], t);
     if (m == all) break;
   }
   return m;

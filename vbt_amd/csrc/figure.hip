@@ -7,18 +7,20 @@
 //     workgroup finds the points its columns can meet by two binary searches on the column table, stages them and the records that
 //     touch the tile in LDS (or reads global memory when they do not fit), and every lane decides four adjacent pixels by the
 //     contract's test (figure_core.h) and stores them once.  Nothing is read from the frames.
+// Shared with curve_figure.hip: the tile's rectangle, the record staging and the RGB24 store (raster_tile.h), the handle's host side (figure_host.h).
 // This translation unit is compiled without FMA contraction (-ffp-contract=off, as every unit here: build.py), so the doubles of the
 // contract are the ones a host compiler forms from figure_core.h.
 #include <algorithm>
 
-#include "common.h"
 #include "figure_core.h"
+#include "figure_host.h"
+#include "raster_tile.h"
 
 namespace vbt {
 
-constexpr int FIG_THREADS = 256;
-constexpr int FIG_TILE_W = 256, FIG_TILE_H = 32;        // a wavefront stores 768 contiguous bytes of one pixel row at a time
-constexpr int FIG_META = 8;                             // per figure: rows, phases, first row, first phase of the upload
+constexpr int FIG_THREADS = RASTER_THREADS;
+constexpr int FIG_TILE_H = 32;
+constexpr int FIG_META = 8;                           // per figure: rows, phases, first row, first phase of the upload
 
 struct FigPrepArgs {
   const int32_t* meta;     // [n][FIG_META]
@@ -118,20 +120,8 @@ __device__ __forceinline__ void figure_render_tile(const FigRenderArgs& A, const
     uint8_t* p = frame + ((size_t)py * G.W + px) * 3;
     int ci[4] = {0, 0, 0, 0};
     fig_pixels4(G, V, px, py, last - px + 1, seg0, seg1, ci);
-    if (A.words) {                                                  // W % 4 == 0: px + 3 < W, and p is 4-aligned
-      const uint32_t c0 = fig_rgb(ci[0]), c1 = fig_rgb(ci[1]), c2 = fig_rgb(ci[2]), c3 = fig_rgb(ci[3]);
-      uint32_t* w = (uint32_t*)p;
-      w[0] = c0 | (c1 & 0xffu) << 24;
-      w[1] = c1 >> 8 | (c2 & 0xffffu) << 16;
-      w[2] = c2 >> 16 | c3 << 8;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        if (px + e >= G.W) break;
-        const uint32_t c = fig_rgb(ci[e]);
-        p[3 * e] = (uint8_t)c; p[3 * e + 1] = (uint8_t)(c >> 8); p[3 * e + 2] = (uint8_t)(c >> 16);
-      }
-    }
+    const uint32_t rgb[4] = {fig_rgb(ci[0]), fig_rgb(ci[1]), fig_rgb(ci[2]), fig_rgb(ci[3])};
+    store_rgb24x4(p, rgb, last - px + 1, A.words);                  // W % 4 == 0: px + 3 < W, and p is 4-aligned
   }
 }
 
@@ -144,27 +134,18 @@ __global__ __launch_bounds__(FIG_THREADS, 4) void figure_render_kernel(FigRender
   const int T = A.meta[(size_t)fig * FIG_META], nrec = A.nrec[fig];
   const int32_t* gp = A.pts + (size_t)fig * A.max_rows * FIG_PT;
   const int32_t* gr = A.recs + (size_t)fig * A.rec_cap * FIG_REC;
-  const int x_lo = (int)(blockIdx.x % A.tiles_x) * FIG_TILE_W, y_lo = (int)(blockIdx.x / A.tiles_x) * FIG_TILE_H;
-  const int x_hi = (x_lo + FIG_TILE_W < G.W ? x_lo + FIG_TILE_W : G.W) - 1, y_hi = (y_lo + FIG_TILE_H < G.H ? y_lo + FIG_TILE_H : G.H) - 1;
+  const TileBox box = tile_box<FIG_TILE_H>(A.tiles_x, G.W, G.H);
   if (tid == 0) s_found = 0;
   __syncthreads();
   // the points of the tile's columns: once per workgroup, on the whole table
   FigView V{gp, 0, T, gr, nrec, {}, {}};
   int seg0, seg1, k0, k1;
-  fig_seg_range(V, 0, T, G.t, x_lo - G.X0, x_hi - G.X0, &seg0, &seg1, &k0, &k1);
+  fig_seg_range(V, 0, T, G.t, box.x_lo - G.X0, box.x_hi - G.X0, &seg0, &seg1, &k0, &k1);
   const int p0 = seg0, np = seg0 <= seg1 ? (seg1 + 1 < T ? seg1 + 1 : T - 1) - p0 + 1 : 0;
   const bool pts_staged = np <= VBT_FIGURE_STAGE_POINTS;
   if (pts_staged)
     for (int i = tid; i < np * FIG_PT; i += FIG_THREADS) s_pts[i] = gp[(size_t)p0 * FIG_PT + i];
-  // the records that touch the tile
-  for (int r = tid; r < nrec; r += FIG_THREADS) {
-    const int32_t* q = gr + (size_t)r * FIG_REC;
-    if (q[FIG_R_X0] > x_hi || q[FIG_R_X1] < x_lo || q[FIG_R_Y0] > y_hi || q[FIG_R_Y1] < y_lo) continue;
-    if (q[FIG_R_X0] > q[FIG_R_X1] || q[FIG_R_Y0] > q[FIG_R_Y1]) continue;
-    const int k = atomicAdd(&s_found, 1);
-    if (k < VBT_FIGURE_STAGE_RECORDS)
-      for (int e = 0; e < FIG_REC; e++) s_recs[k * FIG_REC + e] = q[e];
-  }
+  stage_tile_records<FIG_REC>(gr, nrec, box, s_recs, VBT_FIGURE_STAGE_RECORDS, &s_found);
   __syncthreads();
   const int found = s_found;
   const bool recs_staged = found <= VBT_FIGURE_STAGE_RECORDS;
@@ -172,11 +153,11 @@ __global__ __launch_bounds__(FIG_THREADS, 4) void figure_render_kernel(FigRender
   if (pts_staged && recs_staged) {
     FigView S{s_pts, p0, T, s_recs, found, {}, {}};
     fig_view_unbounded(S);
-    figure_render_tile(A, S, k0, k1, x_lo, y_lo, frame);
+    figure_render_tile(A, S, k0, k1, box.x_lo, box.y_lo, frame);
   } else {                                                          // a dense series or a crowded tile: the same statements on global memory
     FigView S{pts_staged ? s_pts : gp, pts_staged ? p0 : 0, T, recs_staged ? s_recs : gr, recs_staged ? found : nrec, {}, {}};
     fig_view_unbounded(S);
-    figure_render_tile(A, S, k0, k1, x_lo, y_lo, frame);
+    figure_render_tile(A, S, k0, k1, box.x_lo, box.y_lo, frame);
   }
 }
 
@@ -184,27 +165,19 @@ __global__ __launch_bounds__(FIG_THREADS, 4) void figure_render_kernel(FigRender
 
 using namespace vbt;
 
-struct vbt_figure {
-  int device = 0;
+struct vbt_figure : FigureHandle {     // blob: upload (meta | rows | phases) | head | pts | recs | nrec | smooth
   vbt_figure_params prm{};
   FigGeom G{};
-  int rec_cap = 0;
-  uint8_t* blob = nullptr;             // upload (meta | rows | phases) | smooth | head | pts | recs | nrec in one allocation
-  size_t up_cap = 0;
   double *d_smooth = nullptr, *d_head = nullptr;
-  int32_t *d_pts = nullptr, *d_recs = nullptr, *d_nrec = nullptr;
-  int n = 0;                           // figures set
+  int32_t* d_pts = nullptr;
   std::vector<int32_t> meta;           // the host's copy
-  hipStream_t last = nullptr;          // the stream of the last set or render: vbt_figure_table waits for it
 };
 
 namespace {
 
 int check_figure_params(const vbt_figure_params& p) {
   const char* who = "vbt_figure_create";
-  if (p.width < 1 || p.width > 16384 || p.height < 1 || p.height > 16384) { set_error("%s: figures of 1..16384 pixels a side, got %d x %d", who, p.width, p.height); return VBT_ERR_ARG; }
-  if (p.scale < 1 || p.scale > 64) { set_error("%s: scale %d outside 1..64", who, p.scale); return VBT_ERR_ARG; }
-  if (p.thickness < 1 || p.thickness > 64) { set_error("%s: thickness %d outside 1..64", who, p.thickness); return VBT_ERR_ARG; }
+  if (int rc = check_canvas(who, p.width, p.height, p.scale, p.thickness)) return rc;
   if (p.max_figures < 1 || p.max_figures > FIG_MAX_FIGURES) { set_error("%s: max_figures %d outside 1..%d", who, p.max_figures, (int)FIG_MAX_FIGURES); return VBT_ERR_ARG; }
   if (p.max_rows < 1 || p.max_rows > FIG_MAX_ROWS) { set_error("%s: max_rows %d outside 1..%d", who, p.max_rows, (int)FIG_MAX_ROWS); return VBT_ERR_ARG; }
   if (p.max_phases < 0 || p.max_phases > FIG_MAX_PHASES) { set_error("%s: max_phases %d outside 0..%d", who, p.max_phases, (int)FIG_MAX_PHASES); return VBT_ERR_ARG; }
@@ -212,13 +185,7 @@ int check_figure_params(const vbt_figure_params& p) {
     set_error("%s: %d figures of %d rows and %d phases: above 2^26 rows or 2^22 phases in all", who, p.max_figures, p.max_rows, p.max_phases);
     return VBT_ERR_ARG;
   }
-  const FigGeom G = fig_geom(p.width, p.height, p.scale, p.thickness);
-  if (G.PW < FIG_MIN_PLOT || G.PH < FIG_MIN_PLOT) {
-    set_error("%s: a %d x %d figure at scale %d leaves a plot rectangle of %d x %d, below %d x %d", who, p.width, p.height, p.scale, G.PW, G.PH,
-              (int)FIG_MIN_PLOT, (int)FIG_MIN_PLOT);
-    return VBT_ERR_ARG;
-  }
-  return VBT_OK;
+  return check_plot_rect(who, fig_geom(p.width, p.height, p.scale, p.thickness), FIG_MIN_PLOT);
 }
 
 // the refusals of vbt_figure_set that need no handle and no device; the totals on VBT_OK
@@ -258,8 +225,6 @@ int check_figure_set(int n, const double* rows, const int32_t* row_counts, const
   return VBT_OK;
 }
 
-size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 }  // namespace
 
 extern "C" {
@@ -282,30 +247,25 @@ int vbt_figure_create(int device, const vbt_figure_params* params, vbt_figure** 
   f->device = device; f->prm = p; f->G = fig_geom(p.width, p.height, p.scale, p.thickness);
   f->rec_cap = FIG_FIXED_RECS + 4 * p.max_phases;
   const size_t F = (size_t)p.max_figures, R = (size_t)p.max_rows;
-  f->up_cap = align64(F * FIG_META * 4) + F * R * 7 * 8 + F * (size_t)p.max_phases * 6 * 8;
-  const size_t up_b = align64(f->up_cap), smooth_b = F * 4 * R * 8, head_b = align64(F * FIG_HEAD * 8), pts_b = align64(F * R * FIG_PT * 4);
-  const size_t recs_b = align64(F * (size_t)f->rec_cap * FIG_REC * 4), nrec_b = align64(F * 4);
-  const size_t total = up_b + smooth_b + head_b + pts_b + recs_b + nrec_b;
-  if (hipMalloc((void**)&f->blob, total) != hipSuccess) {
+  Carver C;
+  C.add<uint8_t>(align64(F * FIG_META * 4) + F * R * 7 * 8 + F * (size_t)p.max_phases * 6 * 8);      // the largest upload, at the blob's head
+  const auto head = C.add<double>(F * FIG_HEAD);
+  const auto pts = C.add<int32_t>(F * R * FIG_PT);
+  const auto recs = C.add<int32_t>(F * (size_t)f->rec_cap * FIG_REC);
+  const auto nrec = C.add<int32_t>(F);
+  const auto smooth = C.add<double>(F * 4 * R);
+  if (hipMalloc((void**)&f->blob, C.bytes()) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("vbt_figure_create: the device cannot give %zu bytes for %d figures of %d rows and %d phases", total, p.max_figures, p.max_rows, p.max_phases);
+    set_error("vbt_figure_create: the device cannot give %zu bytes for %d figures of %d rows and %d phases", C.bytes(), p.max_figures, p.max_rows, p.max_phases);
     return VBT_ERR_HIP;
   }
-  uint8_t* q = f->blob + up_b;
-  f->d_smooth = (double*)q; q += smooth_b;
-  f->d_head = (double*)q; q += head_b;
-  f->d_pts = (int32_t*)q; q += pts_b;
-  f->d_recs = (int32_t*)q; q += recs_b;
-  f->d_nrec = (int32_t*)q;
+  f->d_head = C.ptr(f->blob, head); f->d_pts = C.ptr(f->blob, pts); f->d_recs = C.ptr(f->blob, recs);
+  f->d_nrec = C.ptr(f->blob, nrec); f->d_smooth = C.ptr(f->blob, smooth);
   *out = f.release();
   return VBT_OK;
 }
 
-void vbt_figure_destroy(vbt_figure* f) {
-  if (!f) return;
-  if (hipSetDevice(f->device) == hipSuccess && f->blob) (void)hipFree(f->blob);   // (waits for the launches still using it)
-  delete f;
-}
+void vbt_figure_destroy(vbt_figure* f) { delete f; }
 
 int vbt_figure_set(vbt_figure* f, int n, const double* rows7_host, const int32_t* row_counts, const double* phases6_host, const int32_t* phase_counts,
                    void* stream) {
@@ -341,25 +301,21 @@ int vbt_figure_set(vbt_figure* f, int n, const double* rows7_host, const int32_t
     figure_prepare_kernel<<<dim3((unsigned)n), FIG_THREADS, 0, st>>>(A);
     e = hipGetLastError();
   }
-  const hipError_t es = hipStreamSynchronize(st);                  // (`up` leaves scope: the copy must have read it)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) { set_error("vbt_figure_set failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  if (int rc = f->finish_set("vbt_figure_set", st, e)) return rc;      // (`up` leaves scope: the copy must have read it)
   f->meta.assign(meta, meta + (size_t)n * FIG_META);
-  f->n = n; f->last = st;
+  f->n = n;
   return VBT_OK;
 }
 
 int vbt_figure_render(vbt_figure* f, uint8_t* frames_dev, int fig0, int n, void* stream) {
-  if (!f || !frames_dev) { set_error("vbt_figure_render: NULL argument (handle %p, frames %p)", (void*)f, (void*)frames_dev); return VBT_ERR_ARG; }
-  if (f->n == 0) { set_error("vbt_figure_render: no figures are set (vbt_figure_set)"); return VBT_ERR_STATE; }
-  if (fig0 < 0 || n < 0 || (long)fig0 + n > f->n) { set_error("vbt_figure_render: figures %d .. %ld outside the %d that are set", fig0, (long)fig0 + n - 1, f->n); return VBT_ERR_ARG; }
+  if (int rc = check_render_args("vbt_figure_render", "vbt_figure_set", f, frames_dev, fig0, n)) return rc;
   if (n == 0) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(f->device));
   FigRenderArgs A{};
   A.meta = (const int32_t*)f->blob; A.pts = f->d_pts; A.recs = f->d_recs; A.nrec = f->d_nrec;
   A.frames = frames_dev; A.frame_bytes = (size_t)f->G.W * f->G.H * 3;
   A.G = f->G; A.max_rows = f->prm.max_rows; A.rec_cap = f->rec_cap; A.fig0 = fig0;
-  A.tiles_x = (f->G.W + FIG_TILE_W - 1) / FIG_TILE_W;
+  A.tiles_x = (f->G.W + RASTER_TILE_W - 1) / RASTER_TILE_W;
   A.words = f->G.W % 4 == 0 && ((uintptr_t)frames_dev & 3) == 0;
   const int tiles_y = (f->G.H + FIG_TILE_H - 1) / FIG_TILE_H;
   figure_render_kernel<<<dim3((unsigned)(A.tiles_x * tiles_y), (unsigned)n), FIG_THREADS, 0, (hipStream_t)stream>>>(A);
@@ -374,12 +330,8 @@ int vbt_figure_table(vbt_figure* f, int fig, double* head6, int32_t* points, int
     set_error("vbt_figure_table: bad argument");
     return VBT_ERR_ARG;
   }
-  if (f->n == 0) { set_error("vbt_figure_table: no figures are set (vbt_figure_set)"); return VBT_ERR_STATE; }
-  if (fig < 0 || fig >= f->n) { set_error("vbt_figure_table: figure %d outside the %d that are set", fig, f->n); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipSetDevice(f->device));
-  VBT_HIP_CHECK(hipStreamSynchronize(f->last));
   int32_t nrec = 0;
-  VBT_HIP_CHECK(hipMemcpy(&nrec, f->d_nrec + fig, 4, hipMemcpyDeviceToHost));
+  if (int rc = table_begin("vbt_figure_table", "vbt_figure_set", f, fig, &nrec)) return rc;
   VBT_HIP_CHECK(hipMemcpy(head6, f->d_head + (size_t)fig * FIG_HEAD, FIG_HEAD * 8, hipMemcpyDeviceToHost));
   const int T = f->meta[(size_t)fig * FIG_META];
   *n_points = T; *n_records = nrec;

@@ -1,8 +1,8 @@
 // Rep figure (include/vbt_hip.h, "Rep figure"): the figure's layout, axes, records and the test of one pixel, as host + device
-// functions of plain integers and doubles.  vbt_figure_set's validation, the kernels of figure.hip and a host program
+// functions of plain integers and doubles, on the record table, text test and segment test of raster_core.h.  vbt_figure_set's validation, the kernels of figure.hip and a host program
 // (tests/fuzz/figure_check.cc) run these statements.  Every double is formed one IEEE operation per statement, without contraction.
 #pragma once
-#include "overlay_core.h"
+#include "raster_core.h"
 #include "roll_mean.h"
 
 namespace vbt {
@@ -13,8 +13,8 @@ enum { FIG_KEY1_CELLS = 48, FIG_KEY2_CELLS = 70, FIG_LABEL_TOP_CELLS = 2 };     
 enum { FIG_MAX_FIGURES = 4096, FIG_MAX_ROWS = 1 << 20, FIG_MAX_PHASES = 65536, FIG_MAX_TIME_TICKS = 264 };
 enum { FIG_HEAD = 6 };                                                                      // t0, t1, position lo, hi, velocity lo, hi
 enum { FIG_PT_COL = 0, FIG_PT_X, FIG_PT_Y, FIG_PT_DX, FIG_PT_DY, FIG_PT = 5 };             // point record: column, then the row of each series
-// record: 12 int32.  [x0, x1] x [y0, y1] is what of it can be seen (frame coordinates, clipped; empty when x0 > x1 or y0 > y1)
-enum { FIG_R_KIND = 0, FIG_R_X0, FIG_R_Y0, FIG_R_X1, FIG_R_Y1, FIG_R_OX, FIG_R_OY, FIG_R_CHARS, FIG_R_VALUE = 10, FIG_R_AUX = 11, FIG_REC = 12 };
+// record: 12 int32, the layout FigRec of raster_core.h
+enum { FIG_R_VALUE = FigRec::VALUE, FIG_R_AUX = FigRec::AUX, FIG_REC = FigRec::REC };
 enum { FIG_KIND_SPAN = 0, FIG_KIND_LINE = 1, FIG_KIND_SWATCH = 2, FIG_KIND_TEXT = 3 };
 enum { FIG_TEXT_CHARS = 12, FIG_FIXED_RECS = 384 };                                         // records besides the 4 per phase: 8 + 4 + 6 + 32 + 264 + 54 at most
 // colour index of a pixel
@@ -62,13 +62,6 @@ __host__ __device__ inline FigGeom fig_geom(int W, int H, int s, int t) {
   G.PH = rest >= 0 ? rest / 2 : -1;
   G.Y1 = G.Y0 + G.PH + FIG_CELLS_MID * s;
   return G;
-}
-
-// llrint after the clamp to +-32768; a NaN (from inf / inf only) goes to -32768
-__host__ __device__ inline int32_t fig_clamp_round(double v) {
-  if (!(v >= -32768.0)) return -32768;
-  if (v > 32768.0) return 32768;
-  return (int32_t)llrint(v);
 }
 
 __host__ __device__ inline int32_t fig_col(double time, double t0, double t1, int PW) {
@@ -128,41 +121,6 @@ __host__ __device__ inline int64_t fig_value_step(double lo, double hi) {
   return 0;
 }
 
-struct FigRecs {
-  int32_t* rec;
-  int cap, n;
-};
-
-__host__ __device__ inline int32_t* fig_new_rec(FigRecs& R, int kind) {
-  if (R.n >= R.cap) return nullptr;                                    // (never: the capacity is sized for every record of a figure)
-  int32_t* r = R.rec + (size_t)R.n * FIG_REC;
-  for (int k = 0; k < FIG_REC; k++) r[k] = 0;
-  r[FIG_R_KIND] = kind;
-  R.n++;
-  return r;
-}
-
-// a filled rectangle [x0, x1] x [y0, y1] clipped to [cx0, cx1] x [cy0, cy1]
-__host__ __device__ inline void fig_box_rec(FigRecs& R, int kind, int x0, int y0, int x1, int y1, int cx0, int cy0, int cx1, int cy1, int value, int aux) {
-  int32_t* r = fig_new_rec(R, kind);
-  if (!r) return;
-  r[FIG_R_X0] = x0 > cx0 ? x0 : cx0; r[FIG_R_Y0] = y0 > cy0 ? y0 : cy0;
-  r[FIG_R_X1] = x1 < cx1 ? x1 : cx1; r[FIG_R_Y1] = y1 < cy1 ? y1 : cy1;
-  r[FIG_R_OX] = x0; r[FIG_R_OY] = y0; r[FIG_R_VALUE] = value; r[FIG_R_AUX] = aux;
-}
-
-// n characters whose box has its top left corner at (ox, oy); rot: turned a quarter so that it reads bottom to top
-__host__ __device__ inline void fig_text_rec(FigRecs& R, int s, int ox, int oy, const uint8_t* chars, int n, int rot, int cx0, int cy0, int cx1, int cy1, int value) {
-  int32_t* r = fig_new_rec(R, FIG_KIND_TEXT);
-  if (!r) return;
-  const int wu = (6 * n - 1) * s, hu = 7 * s;
-  const int x1 = ox + (rot ? hu : wu) - 1, y1 = oy + (rot ? wu : hu) - 1;
-  r[FIG_R_X0] = ox > cx0 ? ox : cx0; r[FIG_R_Y0] = oy > cy0 ? oy : cy0;
-  r[FIG_R_X1] = x1 < cx1 ? x1 : cx1; r[FIG_R_Y1] = y1 < cy1 ? y1 : cy1;
-  r[FIG_R_OX] = ox; r[FIG_R_OY] = oy; r[FIG_R_VALUE] = value; r[FIG_R_AUX] = n | (rot << 8);
-  for (int k = 0; k < n; k++) r[FIG_R_CHARS + k / 4] |= (int32_t)((uint32_t)chars[k] << (8 * (k % 4)));
-}
-
 // c hundredths (|c| <= 9999) as [-]d.dd / [-]dd.dd; returns the number of characters
 __host__ __device__ inline int fig_centi_chars(int c, uint8_t* out) {
   int n = 0;
@@ -187,8 +145,9 @@ __host__ __device__ inline int fig_int_chars(int64_t v, uint8_t* out) {
 }
 
 // ticks and labels of the value axis of the rectangle at row Y
-__host__ __device__ inline void fig_value_ticks(FigRecs& R, const FigGeom& G, int Y, double lo, double hi) {
+__host__ __device__ inline void fig_value_ticks(Recs& R, const FigGeom& G, int Y, double lo, double hi) {
   const int s = G.s;
+  const Clip frame{0, 0, G.W - 1, G.H - 1};
   if (!(lo >= -1e9) || !(hi <= 1e9)) return;
   const int64_t step = fig_value_step(lo, hi);
   if (step == 0) return;
@@ -202,17 +161,18 @@ __host__ __device__ inline void fig_value_ticks(FigRecs& R, const FigGeom& G, in
     const int row = fig_row(v, lo, hi, G.PH);
     int64_t c = milli / 10;
     c = c < -9999 ? -9999 : (c > 9999 ? 9999 : c);
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 - 3 * s, Y + row - s / 2, G.X0 - s - 1, Y + row - s / 2 + s - 1, 0, 0, G.W - 1, G.H - 1, (int)c, 0);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 - 3 * s, Y + row - s / 2, G.X0 - s - 1, Y + row - s / 2 + s - 1, frame, (int)c, 0);
     uint8_t ch[FIG_TEXT_CHARS];
     const int n = fig_centi_chars((int)c, ch);
-    fig_text_rec(R, s, G.X0 - 4 * s - (6 * n - 1) * s, Y + row - 3 * s, ch, n, 0, 0, 0, G.W - 1, G.H - 1, (int)c);
+    rec_text<FigRec>(R, FIG_KIND_TEXT, s, G.X0 - 4 * s - text_width(n, s), Y + row - 3 * s, ch, n, 0, frame, (int)c);
   }
 }
 
 // minor ticks every u seconds and major ones every 5 u, u the smallest power of ten that gives at most 256 steps between t0 and t1 (1 for
 // every set shorter than 256 s: plot.py:208-215), under the lower rectangle
-__host__ __device__ inline void fig_time_ticks(FigRecs& R, const FigGeom& G, double t0, double t1) {
+__host__ __device__ inline void fig_time_ticks(Recs& R, const FigGeom& G, double t0, double t1) {
   const int s = G.s;
+  const Clip frame{0, 0, G.W - 1, G.H - 1};
   if (!(t0 >= -1e9) || !(t1 <= 1e9)) return;
   const double w = t1 - t0;
   int64_t u = 1;
@@ -227,28 +187,28 @@ __host__ __device__ inline void fig_time_ticks(FigRecs& R, const FigGeom& G, dou
     if (v < t0) continue;
     const bool major = (sec - base) % m == 0;
     const int col = fig_col(v, t0, t1, G.PW);
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 + col - s / 2, top, G.X0 + col - s / 2 + s - 1, top + (major ? 3 : 2) * s - 1, 0, 0, G.W - 1, G.H - 1, (int)sec, major);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 + col - s / 2, top, G.X0 + col - s / 2 + s - 1, top + (major ? 3 : 2) * s - 1, frame, (int)sec, major);
     if (!major) continue;
     uint8_t ch[FIG_TEXT_CHARS];
     const int n = fig_int_chars(sec, ch);
-    fig_text_rec(R, s, G.X0 + col - ((6 * n - 1) * s) / 2, top + 4 * s, ch, n, 0, 0, 0, G.W - 1, G.H - 1, (int)sec);
+    rec_text<FigRec>(R, FIG_KIND_TEXT, s, G.X0 + col - text_width(n, s) / 2, top + 4 * s, ch, n, 0, frame, (int)sec);
   }
 }
 
 // All records of a figure from its head and its phases (each passed ov_hud_phase_check), in the order of the contract: the phase
 // records first - two spans per concentric or eccentric phase, then two labels per concentric one, in phase order - then the fixed ones
 __host__ __device__ inline int fig_records(const FigGeom& G, const double* head, const double* ph, int P, int32_t* rec, int cap) {
-  FigRecs R{rec, cap, 0};
-  const int s = G.s, W = G.W, H = G.H;
+  Recs R{rec, cap, 0};
+  const int s = G.s;
   const double t0 = head[0], t1 = head[1];
   const int Ys[2] = {G.Y0, G.Y1};
+  const Clip frame{0, 0, G.W - 1, G.H - 1}, plot[2] = {{G.X0, G.Y0, G.X0 + G.PW - 1, G.Y0 + G.PH - 1}, {G.X0, G.Y1, G.X0 + G.PW - 1, G.Y1 + G.PH - 1}};
   for (int i = 0; i < P; i++) {
     const double* p = ph + (size_t)i * 6;
     const int type = (int)p[5];
     if (type == 2) continue;
     const int c0 = fig_col(p[0], t0, t1, G.PW), c1 = fig_col(p[1], t0, t1, G.PW);
-    for (int k = 0; k < 2; k++)
-      fig_box_rec(R, FIG_KIND_SPAN, G.X0 + c0, Ys[k], G.X0 + c1, Ys[k] + G.PH - 1, G.X0, Ys[k], G.X0 + G.PW - 1, Ys[k] + G.PH - 1, i, type);
+    for (int k = 0; k < 2; k++) rec_box<FigRec>(R, FIG_KIND_SPAN, G.X0 + c0, Ys[k], G.X0 + c1, Ys[k] + G.PH - 1, plot[k], i, type);
   }
   for (int i = 0; i < P; i++) {
     const double* p = ph + (size_t)i * 6;
@@ -261,7 +221,7 @@ __host__ __device__ inline int fig_records(const FigGeom& G, const double* head,
     for (int k = 0; k < 2; k++) {
       uint8_t ch[FIG_TEXT_CHARS];
       const int n = fig_centi_chars(v[k], ch);
-      fig_text_rec(R, s, G.X0 + cc - 3 * s, Ys[k] + FIG_LABEL_TOP_CELLS * s, ch, n, 1, G.X0, Ys[k], G.X0 + G.PW - 1, Ys[k] + G.PH - 1, v[k]);
+      rec_text<FigRec>(R, FIG_KIND_TEXT, s, G.X0 + cc - 3 * s, Ys[k] + FIG_LABEL_TOP_CELLS * s, ch, n, 1, plot[k], v[k]);
     }
   }
   const uint8_t title[2][7] = {{OV_GLYPH_R, OV_GLYPH_O, OV_GLYPH_M, OV_GLYPH_SPACE, OV_GLYPH_M, 0, 0},
@@ -270,15 +230,15 @@ __host__ __device__ inline int fig_records(const FigGeom& G, const double* head,
   for (int k = 0; k < 2; k++) {
     const int Y = Ys[k];
     // the frame lines lie around the rectangle, s wide, and leave every pixel of it to the curves and spans
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 - s, Y - s, G.X0 + G.PW + s - 1, Y - 1, 0, 0, W - 1, H - 1, 0, 0);
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 - s, Y + G.PH, G.X0 + G.PW + s - 1, Y + G.PH + s - 1, 0, 0, W - 1, H - 1, 0, 0);
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 - s, Y, G.X0 - 1, Y + G.PH - 1, 0, 0, W - 1, H - 1, 0, 0);
-    fig_box_rec(R, FIG_KIND_LINE, G.X0 + G.PW, Y, G.X0 + G.PW + s - 1, Y + G.PH - 1, 0, 0, W - 1, H - 1, 0, 0);
-    fig_text_rec(R, s, G.X0, Y - 9 * s, title[k], k ? 7 : 5, 0, 0, 0, W - 1, H - 1, 0);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 - s, Y - s, G.X0 + G.PW + s - 1, Y - 1, frame, 0, 0);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 - s, Y + G.PH, G.X0 + G.PW + s - 1, Y + G.PH + s - 1, frame, 0, 0);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 - s, Y, G.X0 - 1, Y + G.PH - 1, frame, 0, 0);
+    rec_box<FigRec>(R, FIG_KIND_LINE, G.X0 + G.PW, Y, G.X0 + G.PW + s - 1, Y + G.PH - 1, frame, 0, 0);
+    rec_text<FigRec>(R, FIG_KIND_TEXT, s, G.X0, Y - 9 * s, title[k], k ? 7 : 5, 0, frame, 0);
     for (int j = 0; j < 2; j++) {
       const int kx = G.X0 + (j ? FIG_KEY2_CELLS : FIG_KEY1_CELLS) * s;
-      fig_box_rec(R, FIG_KIND_SWATCH, kx, Y - 7 * s, kx + 6 * s - 1, Y - 4 * s - 1, 0, 0, W - 1, H - 1, 0, FIG_C_X + 2 * k + j);
-      fig_text_rec(R, s, kx + 7 * s, Y - 9 * s, keys[2 * k + j], k ? 2 : 1, 0, 0, 0, W - 1, H - 1, 0);
+      rec_box<FigRec>(R, FIG_KIND_SWATCH, kx, Y - 7 * s, kx + 6 * s - 1, Y - 4 * s - 1, frame, 0, FIG_C_X + 2 * k + j);
+      rec_text<FigRec>(R, FIG_KIND_TEXT, s, kx + 7 * s, Y - 9 * s, keys[2 * k + j], k ? 2 : 1, 0, frame, 0);
     }
     fig_value_ticks(R, G, Y, head[2 + 2 * k], head[3 + 2 * k]);
   }
@@ -301,22 +261,13 @@ __host__ __device__ inline void fig_view_unbounded(FigView& V) {
   for (int k = 0; k < FIG_PT; k++) { V.rlo[k] = -65536; V.rhi[k] = 65536; }
 }
 
-// first point i of [lo, hi) with col_i >= v, hi if none; the columns do not decrease
-__host__ __device__ inline int fig_col_lower_bound(const FigView& V, int lo, int hi, int v) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (V.pts[(size_t)(mid - V.pt_base) * FIG_PT] >= v) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
 // The segments that can cover a pixel of columns [pa, pb] (rectangle coordinates): segment i joins points i and min(i + 1, T - 1),
 // i < max(T - 1, 1); those with col_{i+1} >= pa - h and col_i <= pb + h, h = (t + 1) / 2.  Empty: *seg0 > *seg1.  [lo, hi) is a range
 // of points known to hold both bounds ([0, T), or the bounds *k0, *k1 of columns that contain [pa, pb]).
 __host__ __device__ inline void fig_seg_range(const FigView& V, int lo, int hi, int t, int pa, int pb, int* seg0, int* seg1, int* k0_out, int* k1_out) {
   if (V.T <= 0) { *seg0 = 0; *seg1 = -1; *k0_out = 0; *k1_out = 0; return; }
   const int h = (t + 1) / 2, nseg = V.T > 1 ? V.T - 1 : 1;
-  const int k0 = fig_col_lower_bound(V, lo, hi, pa - h), k1 = fig_col_lower_bound(V, lo, hi, pb + h + 1);
+  const int k0 = col_lower_bound(V.pts, FIG_PT, V.pt_base, lo, hi, pa - h), k1 = col_lower_bound(V.pts, FIG_PT, V.pt_base, lo, hi, pb + h + 1);
   *seg0 = k0 > 0 ? k0 - 1 : 0;
   *seg1 = k1 - 1 < nseg - 1 ? k1 - 1 : nseg - 1;
   *k0_out = k0; *k1_out = k1;
@@ -335,29 +286,10 @@ __host__ __device__ inline unsigned fig_curve_mask(const FigView& V, int t, int 
   for (int i = seg0; i <= seg1; i++) {
     const int j = i + 1 < V.T ? i + 1 : V.T - 1;
     const int32_t *a = V.pts + (size_t)(i - V.pt_base) * FIG_PT, *b = V.pts + (size_t)(j - V.pt_base) * FIG_PT;
-    const int ca = a[0], cb = b[0], ra = a[which], rb = b[which];
-    // a covered pixel lies within t / 2 of a point of the segment: outside its box widened by h nothing is covered
-    if (qx0 + n - 1 < ca - h || qx0 > cb + h || qy < (ra < rb ? ra : rb) - h || qy > (ra < rb ? rb : ra) + h) continue;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int e = 0; e < 4; e++) {
-      const int qx = qx0 + e;
-      if (e < n && qx >= 0 && qx < PW && ov_segment_covers(qx, qy, ca, ra, cb, rb, t)) m |= 1u << e;
-    }
+    m |= quad_segment_mask(qx0, n, qy, PW, a[0], a[which], b[0], b[which], t);
     if (m == all) break;
   }
   return m;
-}
-
-__host__ __device__ inline bool fig_text_covers(const int32_t* r, int s, int px, int py) {
-  const int n = r[FIG_R_AUX] & 255, rot = r[FIG_R_AUX] >> 8;
-  const int rx = px - r[FIG_R_OX], ry = py - r[FIG_R_OY];
-  const int ux = rot ? (6 * n - 1) * s - 1 - ry : rx, uy = rot ? rx : ry;
-  const int k = ux / (6 * s), c = (ux - k * 6 * s) / s, row = uy / s;
-  if (c >= 5) return false;
-  const int g = (int)(((uint32_t)r[FIG_R_CHARS + k / 4] >> (8 * (k % 4))) & 255u);
-  return (fig_glyph(g) >> (5 * (6 - row) + 4 - c)) & 1;
 }
 
 // The colour indices out[e] of the frame pixels (px + e, py), e < n <= 4, all in the frame: for each the first of text, second
@@ -367,15 +299,15 @@ __host__ __device__ inline void fig_pixels4(const FigGeom& G, const FigView& V, 
   unsigned text = 0, second = 0, first = 0;
   for (int k = 0; k < V.nrec; k++) {
     const int32_t* r = V.recs + (size_t)k * FIG_REC;
-    const int x0 = r[FIG_R_X0], x1 = r[FIG_R_X1];
-    if (px + n - 1 < x0 || px > x1 || py < r[FIG_R_Y0] || py > r[FIG_R_Y1]) continue;
-    const int kind = r[FIG_R_KIND], value = r[FIG_R_VALUE], aux = r[FIG_R_AUX];
+    const int x0 = r[REC_X0], x1 = r[REC_X1];
+    if (px + n - 1 < x0 || px > x1 || py < r[REC_Y0] || py > r[REC_Y1]) continue;
+    const int kind = r[REC_KIND], value = r[FIG_R_VALUE], aux = r[FIG_R_AUX];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
     for (int e = 0; e < 4; e++) {
       if (e >= n || px + e < x0 || px + e > x1) continue;
-      if (kind == FIG_KIND_TEXT) { if (fig_text_covers(r, G.s, px + e, py)) text |= 1u << e; }
+      if (kind == FIG_KIND_TEXT) { if (text_covers<FigRec, fig_glyph>(r, G.s, px + e, py)) text |= 1u << e; }
       else if (kind == FIG_KIND_SPAN) { if (value >= span[e]) { span[e] = value; span_type[e] = aux; } }   // the later phase wins
       else line[e] = kind == FIG_KIND_SWATCH ? aux : FIG_C_INK;
     }

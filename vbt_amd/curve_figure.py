@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .mem import DeviceBuffer
+from .figure import FigureHandle
 
 PARAMS = ("width", "height", "scale", "thickness", "max_figures", "max_series", "max_points", "max_marks")
 RECORD = ("kind", "x0", "y0", "x1", "y1", "ox", "oy", "value", "aux", "n", "pad0", "pad1") + tuple(f"chars{k}" for k in range(16))
@@ -67,31 +67,10 @@ def pack(figures):
     return descs, series, allxy, marks
 
 
-class CurveFigure:
+class CurveFigure(FigureHandle):
     """vbt_curve_figure (include/vbt_hip.h): one figure size, scale and curve thickness; up to max_figures figures per set.
     params: width=1120, height=640, scale=2, thickness=2, max_figures=16, max_series=8, max_points=131072, max_marks=8."""
-
-    def __init__(self, device=0, **params):
-        L = _lib.lib()
-        prm = _lib.CurveFigureParams()
-        L.vbt_curve_figure_default_params(ctypes.byref(prm))
-        for k, v in params.items():
-            if k not in PARAMS:
-                raise TypeError(f"CurveFigure: unknown parameter {k!r}")
-            setattr(prm, k, int(v))
-        self.params = {k: getattr(prm, k) for k in PARAMS}
-        self.W, self.H, self.device = prm.width, prm.height, int(device)
-        self.frame_bytes = self.W * self.H * 3
-        h = ctypes.c_void_p()
-        _lib.check(L.vbt_curve_figure_create(self.device, ctypes.byref(prm), ctypes.byref(h)))
-        self._h = h
-        self.n = 0
-        self._buf = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None and getattr(_lib, "_lib", None) is not None:
-            _lib._lib.vbt_curve_figure_destroy(h)
+    API, Params, PARAMS = "vbt_curve_figure", _lib.CurveFigureParams, PARAMS
 
     def set(self, figures, stream=None):
         """figures: a list of `figure(...)` dicts.  One upload, one prepare launch."""
@@ -100,11 +79,6 @@ class CurveFigure:
         _lib.check(_lib.lib().vbt_curve_figure_set(self._h, len(figures), ctypes.addressof(descs), ctypes.addressof(series), xy.ctypes.data,
                                                    ctypes.addressof(marks), stream))
         self.n = len(figures)
-
-    def render(self, frames_ptr, fig0=0, n=None, stream=None):
-        """figures fig0 .. fig0 + n - 1 into n contiguous RGB24 frames at device pointer `frames_ptr`; enqueue only, on `stream`"""
-        n = self.n - fig0 if n is None else n
-        _lib.check(_lib.lib().vbt_curve_figure_render(self._h, int(frames_ptr), int(fig0), int(n), stream))
 
     def table(self, fig):
         """(counts int32 [K] = merged points per series; points int32 [sum, 3] = column, row, join; records int32 [n, 28]) as prepared"""
@@ -119,18 +93,3 @@ class CurveFigure:
         _lib.check(L.vbt_curve_figure_table(self._h, int(fig), counts.ctypes.data, len(counts), ctypes.byref(ns), pts.ctypes.data, len(pts),
                                             ctypes.byref(npts), recs.ctypes.data, len(recs), ctypes.byref(nrec)))
         return counts, pts, recs
-
-    def device_frames(self, stream=None):
-        """all figures rendered into the handle's own device buffer; returns its device pointer (enqueue only)"""
-        need = max(self.n, 1) * self.frame_bytes
-        if self._buf is None or self._buf.nbytes < need:
-            self._buf = DeviceBuffer(need, self.device)
-        if self.n:
-            self.render(self._buf.ptr, 0, self.n, stream)
-        return self._buf.ptr
-
-    def frames(self, stream=None):
-        """uint8 [n, H, W, 3]: every figure rendered and read back in one copy"""
-        self.device_frames(stream)
-        _lib.check(_lib.lib().vbt_stream_synchronize(stream))
-        return self._buf.to_host((self.n, self.H, self.W, 3), np.uint8)

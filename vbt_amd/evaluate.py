@@ -290,20 +290,10 @@ def closest_point(thresholds, value):
 def _write_figures(handle_params, figures, paths, fig_format, quality, device):
     """one handle, one set / render / encode and ONE read-back for `figures`; the files go to `paths`"""
     from .curve_figure import CurveFigure
-    from .figure import ppm
+    from .figure import write_frames
     fig = CurveFigure(device, **handle_params)
     fig.set(figures)
-    if fig_format == "jpg":
-        from .mjpeg import Encoder
-        enc = Encoder(fig.H, fig.W, "rgb24", quality, len(figures), device)
-        enc.encode(fig.device_frames(), len(figures))                               # same stream, no synchronisation in between
-        blobs = enc.read()
-    else:
-        blobs = [ppm(f) for f in fig.frames()]
-    for path, blob in zip(paths, blobs):
-        with open(path, "wb") as f:
-            f.write(blob)
-    return list(paths)
+    return write_frames(fig, paths, fig_format, quality)
 
 
 def curve_figures(kind, curves, iou_threshold, score_thresholds=None):

@@ -23,62 +23,38 @@ def default_params():
     return {k: getattr(p, k) for k in PARAMS}
 
 
-class Figure:
-    """vbt_figure (include/vbt_hip.h): one figure size, scale and curve thickness; up to max_figures figures per set.
-    params: width=1280, height=800, scale=2, thickness=2, max_figures=64, max_rows=16384, max_phases=512."""
+class FigureHandle:
+    """What the figure handles of include/vbt_hip.h share: create and destroy, render into device memory, the handle's own frames.
+    A subclass names its entry points' prefix (API), its params struct (Params) and its fields (PARAMS), and has `set` and `table`."""
+    API, Params, PARAMS = None, None, ()
 
     def __init__(self, device=0, **params):
         L = _lib.lib()
-        prm = _lib.FigureParams()
-        L.vbt_figure_default_params(ctypes.byref(prm))
+        prm = self.Params()
+        getattr(L, self.API + "_default_params")(ctypes.byref(prm))
         for k, v in params.items():
-            if k not in PARAMS:
-                raise TypeError(f"Figure: unknown parameter {k!r}")
+            if k not in self.PARAMS:
+                raise TypeError(f"{type(self).__name__}: unknown parameter {k!r}")
             setattr(prm, k, int(v))
-        self.params = {k: getattr(prm, k) for k in PARAMS}
+        self.params = {k: getattr(prm, k) for k in self.PARAMS}
         self.W, self.H, self.device = prm.width, prm.height, int(device)
         self.frame_bytes = self.W * self.H * 3
         h = ctypes.c_void_p()
-        _lib.check(L.vbt_figure_create(self.device, ctypes.byref(prm), ctypes.byref(h)))
+        _lib.check(getattr(L, self.API + "_create")(self.device, ctypes.byref(prm), ctypes.byref(h)))
         self._h = h
         self.n = 0
         self._buf = None
+        self._enc = None                                                               # (quality, mjpeg.Encoder) of write_frames
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None and getattr(_lib, "_lib", None) is not None:
-            _lib._lib.vbt_figure_destroy(h)
-
-    def set(self, figures, stream=None):
-        """figures: [(rows, phases), ...] - rows float64 [T, 7] (time, x, y, dx, dy, norm_plate_height, norm_plate_width) of one id
-        sorted by time, phases float64 [P, 6] or a list of velocity.Phase.  One upload, one prepare launch."""
-        rows = [np.ascontiguousarray(np.asarray(r, np.float64).reshape(-1, 7)) for r, _ in figures]
-        phs = [phases6(p) for _, p in figures]
-        rc = np.array([len(r) for r in rows], np.int32)
-        pc = np.array([len(p) for p in phs], np.int32)
-        allr = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 7))
-        allp = np.ascontiguousarray(np.concatenate(phs)) if phs else np.zeros((0, 6))
-        _lib.check(_lib.lib().vbt_figure_set(self._h, len(rows), allr.ctypes.data, rc.ctypes.data, allp.ctypes.data, pc.ctypes.data, stream))
-        self.n = len(rows)
+            getattr(_lib._lib, self.API + "_destroy")(h)
 
     def render(self, frames_ptr, fig0=0, n=None, stream=None):
         """figures fig0 .. fig0 + n - 1 into n contiguous RGB24 frames at device pointer `frames_ptr`; enqueue only, on `stream`"""
         n = self.n - fig0 if n is None else n
-        _lib.check(_lib.lib().vbt_figure_render(self._h, int(frames_ptr), int(fig0), int(n), stream))
-
-    def table(self, fig):
-        """(head float64 [6] = t0, t1, position lo, hi, velocity lo, hi; points int32 [T, 5]; records int32 [n, 12]) as prepared"""
-        L = _lib.lib()
-        head = np.zeros(6, np.float64)
-        npts, nrec = ctypes.c_int(), ctypes.c_int()
-        rc = L.vbt_figure_table(self._h, int(fig), head.ctypes.data, None, 0, ctypes.byref(npts), None, 0, ctypes.byref(nrec))
-        if rc != -4:
-            _lib.check(rc)
-        pts = np.zeros((npts.value, 5), np.int32)
-        recs = np.zeros((nrec.value, 12), np.int32)
-        _lib.check(L.vbt_figure_table(self._h, int(fig), head.ctypes.data, pts.ctypes.data, len(pts), ctypes.byref(npts), recs.ctypes.data, len(recs),
-                                      ctypes.byref(nrec)))
-        return head, pts, recs
+        _lib.check(getattr(_lib.lib(), self.API + "_render")(self._h, int(frames_ptr), int(fig0), int(n), stream))
 
     def device_frames(self, stream=None):
         """all figures rendered into the handle's own device buffer; returns its device pointer (enqueue only)"""
@@ -96,10 +72,60 @@ class Figure:
         return self._buf.to_host((self.n, self.H, self.W, 3), np.uint8)
 
 
+class Figure(FigureHandle):
+    """vbt_figure (include/vbt_hip.h): one figure size, scale and curve thickness; up to max_figures figures per set.
+    params: width=1280, height=800, scale=2, thickness=2, max_figures=64, max_rows=16384, max_phases=512."""
+    API, Params, PARAMS = "vbt_figure", _lib.FigureParams, PARAMS
+
+    def set(self, figures, stream=None):
+        """figures: [(rows, phases), ...] - rows float64 [T, 7] (time, x, y, dx, dy, norm_plate_height, norm_plate_width) of one id
+        sorted by time, phases float64 [P, 6] or a list of velocity.Phase.  One upload, one prepare launch."""
+        rows = [np.ascontiguousarray(np.asarray(r, np.float64).reshape(-1, 7)) for r, _ in figures]
+        phs = [phases6(p) for _, p in figures]
+        rc = np.array([len(r) for r in rows], np.int32)
+        pc = np.array([len(p) for p in phs], np.int32)
+        allr = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 7))
+        allp = np.ascontiguousarray(np.concatenate(phs)) if phs else np.zeros((0, 6))
+        _lib.check(_lib.lib().vbt_figure_set(self._h, len(rows), allr.ctypes.data, rc.ctypes.data, allp.ctypes.data, pc.ctypes.data, stream))
+        self.n = len(rows)
+
+    def table(self, fig):
+        """(head float64 [6] = t0, t1, position lo, hi, velocity lo, hi; points int32 [T, 5]; records int32 [n, 12]) as prepared"""
+        L = _lib.lib()
+        head = np.zeros(6, np.float64)
+        npts, nrec = ctypes.c_int(), ctypes.c_int()
+        rc = L.vbt_figure_table(self._h, int(fig), head.ctypes.data, None, 0, ctypes.byref(npts), None, 0, ctypes.byref(nrec))
+        if rc != -4:
+            _lib.check(rc)
+        pts = np.zeros((npts.value, 5), np.int32)
+        recs = np.zeros((nrec.value, 12), np.int32)
+        _lib.check(L.vbt_figure_table(self._h, int(fig), head.ctypes.data, pts.ctypes.data, len(pts), ctypes.byref(npts), recs.ctypes.data, len(recs),
+                                      ctypes.byref(nrec)))
+        return head, pts, recs
+
+
 def ppm(frame):
     """one RGB24 frame [H, W, 3] behind a P6 header"""
     h, w = frame.shape[:2]
     return b"P6\n%d %d\n255\n" % (w, h) + np.ascontiguousarray(frame, np.uint8).tobytes()
+
+
+def write_frames(handle, paths, fig_format, quality):
+    """The figures set in `handle` (a FigureHandle), one file per path: rendered, then as "jpg" encoded on the same stream without a
+    synchronisation in between, or as "ppm" wrapped; one read-back either way.  Returns the paths."""
+    if fig_format == "jpg":
+        if handle._enc is None or handle._enc[0] != quality:
+            from .mjpeg import Encoder
+            handle._enc = (quality, Encoder(handle.H, handle.W, "rgb24", quality, handle.params["max_figures"], handle.device))
+        enc = handle._enc[1]
+        enc.encode(handle.device_frames(), handle.n)
+        blobs = enc.read()
+    else:
+        blobs = [ppm(f) for f in handle.frames()]
+    for path, blob in zip(paths, blobs):
+        with open(path, "wb") as f:
+            f.write(blob)
+    return list(paths)
 
 
 def figure_name(src, fig_format):
@@ -143,24 +169,11 @@ def plot_many(paths, fig_dir, plate_diameter=0.45, fig_format="jpg", quality=90,
     base["max_phases"] = max(base["max_phases"], max(len(p) for _, (_, p) in items))
     base["max_figures"] = min(base["max_figures"], len(items))
     fig = Figure(device, **base)
-    enc = None
-    if fig_format == "jpg":
-        from .mjpeg import Encoder
-        enc = Encoder(fig.H, fig.W, "rgb24", quality, base["max_figures"], device)
     written = []
     for b0 in range(0, len(items), base["max_figures"]):
         batch = items[b0:b0 + base["max_figures"]]
         fig.set([ld for _, ld in batch])
-        if enc is not None:
-            enc.encode(fig.device_frames(), len(batch))                               # same stream, no synchronisation in between
-            blobs = enc.read()
-        else:
-            blobs = [ppm(f) for f in fig.frames()]
-        for (s, _), blob in zip(batch, blobs):
-            path = os.path.join(fig_dir, figure_name(s, fig_format))
-            with open(path, "wb") as f:
-                f.write(blob)
-            written.append(path)
+        written += write_frames(fig, [os.path.join(fig_dir, figure_name(s, fig_format)) for s, _ in batch], fig_format, quality)
     return written
 
 
