@@ -55,6 +55,10 @@ typedef struct {
   int variants[48];
 } vbt_plan_step_space;
 int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, int* n);
+/* Live 16-channel tiles of the part-filled last output block that step (group, alt, step) of the plan space runs tile-major under its
+ * current variant: fused_mbconv launches built with a live-tile count and pw_conv_mfma_i8 variants 9 / 10.  0: the step runs the
+ * block-major layout (a full last block, another family, no such kernel, or VBT_PROJ_TAIL turned it off); < 0: no such step. */
+int vbt_model_step_proj_tail(const vbt_model* m, int group, int alt, int step);
 
 /* ------------------------------------------------------------------ stream placement probe ----------------------------- */
 /* *shared = 1 when the two streams sit on one hardware queue (their kernels cannot overlap): a single wave spins `us`

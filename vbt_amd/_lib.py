@@ -138,6 +138,7 @@ _SIGS = {
     "vbt_streams_share_queue": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_model_read_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vbt_model_plan_space": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_model_step_proj_tail": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_resize_frames_yuv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_model_kernel_stats": (c_int, [c_void_p, c_int, ctypes.POINTER(KernelStat), c_int, ctypes.POINTER(c_int)]),

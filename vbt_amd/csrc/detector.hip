@@ -23,6 +23,7 @@
 //     candidates in LDS -> greedy suppression by one wavefront with ballot/shuffle.
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 #include "detector_model.h"
 #include "op_kernels.h"   // the single-op kernels (pw_a ... pw_f, stem, depthwise, add, pool, resize, decode + NMS, frame resize)
@@ -54,15 +55,19 @@ PwLaunch resolve_pw(const vbt_model* m, const Step& s, int variant, int B) {
   // VBT_PW_VARIANT (tests): the kernel variant of every pointwise conv with K > 256, whatever the plan says
   static const int pw_force = getenv("VBT_PW_VARIANT") ? atoi(getenv("VBT_PW_VARIANT")) : -100;
   // (a forced 7 / 8 leaves the convs that form refuses - one output block, or more than PW_F_MAX_NB - on the plan's variant)
-  const bool f_fits = s.NB >= 2 && s.NB <= PW_F_MAX_NB;
-  if (pw_force != -100 && (f_fits || (pw_force != 7 && pw_force != 8))) variant = pw_force;
-  if (variant == 7 || variant == 8) {   // 64 (7) or 128 (8) pixels per workgroup for ALL output blocks: activations fetched once (pw_f_kernel)
+  // (9 / 10 moreover the convs without a tile-major last block: N % 64 == 0, or a width no shipped model has - pw_f_tail_built)
+  const bool f_fits = s.NB >= 2 && s.NB <= PW_F_MAX_NB, ft_fits = f_fits && s.wp64t && pw_f_tail_built(s.NB, s.ntl);
+  if (pw_force != -100 && (pw_force == 9 || pw_force == 10 ? ft_fits : (f_fits || (pw_force != 7 && pw_force != 8)))) variant = pw_force;
+  if (variant >= 7 && variant <= 10) {   // 64 (7) or 128 (8) pixels per workgroup for ALL output blocks: activations fetched once (pw_f_kernel)
+    const bool tail = variant >= 9;      // 9 / 10: the same two with a tile-major part-filled last block (pack_weights64_tail)
     L.form = PW_F;
-    L.ms = variant - 6;
-    L.lds = s.NB * 8192;   // static: two stages of the K-step's 4 * NB weight tiles
+    L.ms = tail ? variant - 8 : variant - 6;
+    L.ntl = tail ? s.ntl : 0;
+    L.lds = tail ? (4 * (s.NB - 1) + s.ntl) * 2048 : s.NB * 8192;   // static: two stages of the K-step's weight tiles
     L.grid = dim3((unsigned)((M + 64 * L.ms - 1) / (64 * L.ms)), 1);
     if (s.NB < 2) L.refuse(VBT_ERR_ARG, "pw_conv: one output block - nothing for the all-blocks form to share");
     else if (s.NB > PW_F_MAX_NB) L.refuse(VBT_ERR_ARG, "pw_conv: %d output blocks exceed the %d whose accumulators the all-blocks form holds", s.NB, PW_F_MAX_NB);
+    else if (tail && !ft_fits) L.refuse(VBT_ERR_ARG, "pw_conv: no tile-major last block for %d output blocks with %d tail tiles", s.NB, s.ntl);
   } else if (variant >= 3 && variant <= 6) {   // 64 (3 / 5) or 128 (4 / 6) pixels per workgroup; weights shared through LDS (3 / 4: pw_d_kernel)
     L.form = variant <= 4 ? PW_D : PW_E;   // or the block's whole weight panel in LDS and a K loop without barriers (5 / 6: pw_e_kernel)
     L.ms = 2 - (variant & 1);
@@ -107,7 +112,14 @@ static int launch_pw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
       break;
     case PW_F:
 #define PW_F_NB(NBF) (L.ms == 2 ? PW((pw_f_kernel<NBF, 2, 4>), 0) : PW((pw_f_kernel<NBF, 1, 4>), 0))
-      if (s.NB == 2) PW_F_NB(2); else if (s.NB == 3) PW_F_NB(3); else if (s.NB == 4) PW_F_NB(4); else if (s.NB == 5) PW_F_NB(5); else PW_F_NB(6);
+#define PW_F_TAIL(NBF, NTL) (L.ms == 2 ? pw_f_kernel<NBF, 2, 4, NTL><<<L.grid, 256, 0, st>>>(x, s.wp64t, e, ra, out, M, K, s.KS64, N, s.NB) \
+                                     : pw_f_kernel<NBF, 1, 4, NTL><<<L.grid, 256, 0, st>>>(x, s.wp64t, e, ra, out, M, K, s.KS64, N, s.NB))
+      if (L.ntl) {   // the pairs of pw_f_tail_built (detector_model.h)
+        if (s.NB == 2 && L.ntl == 1) PW_F_TAIL(2, 1); else if (s.NB == 2 && L.ntl == 2) PW_F_TAIL(2, 2); else if (s.NB == 2 && L.ntl == 3) PW_F_TAIL(2, 3);
+        else if (s.NB == 2) PW_F_TAIL(2, 4); else if (s.NB == 4) PW_F_TAIL(4, 1); else PW_F_TAIL(6, 2);
+      }
+      else if (s.NB == 2) PW_F_NB(2); else if (s.NB == 3) PW_F_NB(3); else if (s.NB == 4) PW_F_NB(4); else if (s.NB == 5) PW_F_NB(5); else PW_F_NB(6);
+#undef PW_F_TAIL
 #undef PW_F_NB
       break;
     case PW_B:
@@ -179,6 +191,13 @@ static int launch_dw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
 // chunks, 16 = 128-pixel (16 x 8) tiles, 32 = band-Toeplitz depthwise (fused_block.h: TPZ); a bit whose conditions the step does not
 // meet is ignored, except that the whole-image and 128-pixel kernels refuse a step they do not fit and that bit 32 resolves only as
 // 33, 41, 49 or 57 on a step where each of its other bits holds.
+// VBT_PROJ_TAIL (developers; read once per process): "0" = every fused MBConv launch keeps the block-major last projection block, a list
+// such as "b1,b3" = only those blocks run it tile-major (a per-block A/B inside one library); unset: every block that has such a launch
+static bool proj_tail_on(int block) {
+  static const std::string knob = getenv("VBT_PROJ_TAIL") ? std::string(",") + getenv("VBT_PROJ_TAIL") + "," : std::string();
+  if (knob.empty()) return true;
+  return knob.find(",b" + std::to_string(block) + ",") != std::string::npos;
+}
 FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   const FusedArgs& a = s.fa;
   const OpRec& dop = m->ops[s.d_op];
@@ -225,6 +244,9 @@ FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   p.tiles_y = (a.OH + p.TY - 1) / p.TY;
   p.L = FusedLaunch{k, stride, s.nbp, ex, mdw, nt3, ppw2, dw64, fused_tile_lds(a, k, stride, p.TX, p.TY, est, ppw2 ? 2 : 1, s.nbp, e_bytes),
                     (unsigned)((long)B * p.tiles_x * p.tiles_y), tpz_ok};
+  // a part-filled last projection block runs tile-major wherever the step has the panels and the resolved launch is built with a live-tile
+  // count: a property of the step, no variant bit (plan files do not change)
+  if (s.ntl && proj_tail_on(s.block) && (nt3 ? a.wpt3 : a.wpt) && fused_tail_built(p.L, a.KSe, s.ntl)) p.L.ntl = s.ntl;
   if (ppw2 && (a.OW < 16 || a.OH < 8 || !a.wd64)) p.refuse(VBT_ERR_ARG, "fused_mbconv: the 128-pixel variant needs maps of at least 16 x 8");
   else if (ppw2 && p.L.lds_bytes > 64 * 1024) p.refuse(VBT_ERR_ARG, "fused_mbconv: 128-pixel tile needs %d bytes of LDS", p.L.lds_bytes);
   else if (tpz && !tpz_ok) p.refuse(VBT_ERR_ARG, "fused_mbconv: variant %d: the Toeplitz depthwise does not apply to this step", var);

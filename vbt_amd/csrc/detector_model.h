@@ -36,6 +36,8 @@ struct Step {
   long* wp = nullptr;      // packed MFMA weights, 16x16x32 layout (device): stem kernel and the expand stage of the fused kernels
   v4i* wp64 = nullptr;     // pointwise convs: 16x16x64 layout (pack_weights64)
   int KS64 = 0;            // K-steps of 64
+  v4i* wp64t = nullptr;    // the same with a tile-major part-filled last block of `ntl` tiles (pack_weights64_tail); nullptr: N % 64 == 0
+  int ntl = 0;             // live 16-channel tiles of the part-filled last output block (F_PW: of wp64t; F_MBCONV: of fa.wpt / fa.wpt3); 0: none
   int res_op = -1;         // F_PW: the residual ADD evaluated in the epilogue (op = that ADD, p_op = the conv)
   long* wdm = nullptr;     // depthwise: matrix-pipe (diagonal-embedded) weights
   int* bdm = nullptr;      // depthwise: bias folded for raw int8 inputs, padded to 64
@@ -52,6 +54,7 @@ struct Step {
   int src_tensor[3] = {-1, -1, -1};
   FusedArgs fa;
   int nbp = 0, lds_bytes = 0;
+  int block = 0;     // F_MBCONV with ntl > 0: the block's number in the backbone (depthwise convs before its own: b1, b2, ...), for VBT_PROJ_TAIL
   int variant = -1;  // kernel variant chosen by the autotuner (-1 = heuristic default)
   double tuned_ms = 0;
   // F_MULTI: independent fused problems launched as one grid
@@ -173,7 +176,11 @@ struct Verdict {   // rc != VBT_OK: the step is refused, and `why` is the error 
 };
 enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E, PW_F };
 constexpr int PW_F_MAX_NB = 6;   // output blocks whose accumulators one workgroup of the all-blocks form holds (N <= 384)
-struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0; dim3 grid; };
+// the (output blocks, live tiles of the last block) the all-blocks form is built for with a tile-major last block (variants 9 / 10): the
+// large-K projections of the shipped models - Lite0 80 = 64 + 16 and 112 = 64 + 48, Lite2 88 = 64 + 24, 120 = 64 + 56 (four tiles, the
+// last one part-filled), 208 = 3 x 64 + 16 and 352 = 5 x 64 + 32.  Another width needs a line here and one in launch_pw_step.
+static inline bool pw_f_tail_built(int NB, int ntl) { return (NB == 2 && ntl >= 1 && ntl <= 4) || (NB == 4 && ntl == 1) || (NB == 6 && ntl == 2); }
+struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0, ntl = 0; dim3 grid; };
 enum DwForm { DW_ROW, DW_COL, DW_TILE };
 struct DwLaunch : Verdict {   // tile geometry (DW_TILE), rows per lane and row segments (DW_COL), lanes (DW_ROW / DW_COL)
   DwForm form = DW_COL; bool mdw = false; int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0, lds = 0, rows = 0, nseg = 0; long total = 0; dim3 grid;

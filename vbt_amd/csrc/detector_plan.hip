@@ -136,7 +136,7 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
   } else if (st.family == F_PW && st.KS64 <= 4) {
     cand = {0, 1};
   } else if (st.family == F_PW) {
-    cand = {-1, 2, 3, 4, 5, 6, 7, 8};
+    cand = {-1, 2, 3, 4, 5, 6, 7, 8, 9, 10};   // (9 / 10 resolve only where the last output block is part-filled: resolve_pw)
   } else if (is_fused_tile(st.family)) {
     cand = {0, 1, 3, 5};   // VALU dw, matrix-pipe dw, matrix-pipe dw + half-height tile, one workgroup per image
     if (st.family == F_MBCONV && st.fa.nch3 > 0 && st.nbp <= 2 && st.fa.KSe >= 1 && st.fa.KSe <= 4) { cand.push_back(9); cand.push_back(11); }  // 48-channel chunks
@@ -325,6 +325,15 @@ int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, 
         std::copy(ps.variants.begin(), ps.variants.end(), o.variants);
       }
   return VBT_OK;
+}
+
+int vbt_model_step_proj_tail(const vbt_model* m, int group, int alt, int step) {
+  if (!m || group < 0 || group >= (int)m->groups.size() || alt < 0 || alt >= (int)m->groups[group].alts.size() || step < 0 ||
+      step >= (int)m->groups[group].alts[alt].steps.size()) { set_error("vbt_model_step_proj_tail: no such step"); return VBT_ERR_ARG; }
+  const Step& st = m->groups[group].alts[alt].steps[step];
+  if (st.family == F_MBCONV) { const FusedPlan p = resolve_fused(m, st, st.variant, m->max_batch); return p.rc ? 0 : p.L.ntl; }
+  if (st.family == F_PW && st.members.empty()) { const PwLaunch L = resolve_pw(m, st, st.variant, m->max_batch); return L.rc ? 0 : L.ntl; }
+  return 0;
 }
 
 int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, vbt_model** out) {

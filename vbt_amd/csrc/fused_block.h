@@ -62,6 +62,10 @@ struct FusedArgs {
   const unsigned* wtz;
   // project
   const v4i* wp;    // packed for the 16x16x64 MFMA (pack_weights64), K = Ce_pad, one K-step per 64-channel chunk
+  // the same two panels (wp, wp3) with a tile-major part-filled last block (pack_weights64_tail), read by the kernels with a live-tile
+  // count (template NTL > 0); nullptr: Cout % 64 == 0 or no such kernel is built for the step
+  const v4i* wpt;
+  const v4i* wpt3;
   const int* bp;
   const float* mp;
   int KSp, zo, lop, hip;
@@ -114,9 +118,15 @@ constexpr int FB_DST = 80;  // D tile bytes per pixel: 16-byte aligned rows (the
 // TPZ: the DW64 depthwise as a band-Toeplitz product (tpz_geom.h) - 10 taps per instruction and operand read instead of 4, wave w owns
 // the channel quads w NT .. w NT + NT - 1 of the chunk on every position group (no idle wave on 48-channel chunks); the expand
 // stage writes E quad-planar, the D tile, the projection stage and the epilogue are those of the diagonal form.
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false>
+// NTL > 0: the last projection block (NBP - 1) is part-filled and tile-major (FusedArgs::wpt / wpt3): it has NTL live 16-channel tiles,
+// lane (r, g) of tile t ends with channels 64 (NBP - 1) + 16 t + 4 g .. + 3 of pixel r.  Stage P loads and multiplies NTL tiles of that block
+// and the epilogue requantises NTL tiles, one dword each; with the block-major layout (NTL = 0) a block of 24 / 40 / 16 channels spreads over
+// all four tiles and the whole wave runs four requantisations (and residual ADDs) for it, most lanes switched off.  Cout % 4 == 0.
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0>
 __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, unsigned char* fb_smem) {
   static_assert(PPW == 1 || MDW, "128-pixel tiles exist for the matrix-pipe depthwise only");
+  static_assert(NTL >= 0 && NTL <= 4 && (NTL == 0 || EXPAND), "a tile-major last block (MBConv only) holds one to four tiles");
+  constexpr int NBW = NTL ? NBP - 1 : NBP;   // projection blocks of four tiles
   static_assert(!DW64 || (EXPAND && MDW && (KK == 3 || KK == 5)), "DW64: fused expand blocks, 3x3 / 5x5");
   static_assert(!TPZ || (DW64 && (S == 1 || S == 2) && (NT == 3 || NT == 4) && NBP <= 2 && (KSE == 1 || KSE == 2)), "TPZ: a form of DW64");
   constexpr TpzGeom TG = TPZ ? tpz_geom(KK, S, PPW, NT) : TpzGeom{};
@@ -587,14 +597,24 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         bv[pp] = *(const v4i*)(D + (TPZ ? tpz_d_slot(TG, PPW, FB_DST, slot) : slot * FB_DST) + 16 * g);
       }
 #pragma unroll
-      for (int nb = 0; nb < NBP; nb++) {
+      for (int nb = 0; nb < NBW; nb++) {
         const v4i* w = stage_p ? (const v4i*)WPS + (nb * 4) * 64 + lane
+                               : NTL ? (NT == 3 ? a.wpt3 + ((long)(nb * a.KSp3 + c) * 4) * 64 : a.wpt + ((long)(nb * a.KSp + c) * 4) * 64) + lane
                                : (NT == 3 ? a.wp3 + ((long)(nb * a.KSp3 + c) * 4) * 64 : a.wp + ((long)(nb * a.KSp + c) * 4) * 64) + lane;
 #pragma unroll
         for (int t = 0; t < 4; t++) {
           const v4i wv = w[t * 64];
 #pragma unroll
           for (int pp = 0; pp < PPW; pp++) acc[pp][nb][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, bv[pp], acc[pp][nb][t], 0, 0, 0);
+        }
+      }
+      if constexpr (NTL > 0) {   // the tile-major last block: NTL tiles per K-step, behind the NBW full blocks of the panel
+        const v4i* w = (NT == 3 ? a.wpt3 + ((long)NBW * a.KSp3 * 4 + (long)c * NTL) * 64 : a.wpt + ((long)NBW * a.KSp * 4 + (long)c * NTL) * 64) + lane;
+#pragma unroll
+        for (int t = 0; t < NTL; t++) {
+          const v4i wv = w[t * 64];
+#pragma unroll
+          for (int pp = 0; pp < PPW; pp++) acc[pp][NBW][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, bv[pp], acc[pp][NBW][t], 0, 0, 0);
         }
       }
     }
@@ -610,8 +630,19 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   if (py < a.TY && px < a.TX && oy < a.OH && ox < a.OW) {
     const unsigned char* skip = T0 + ((py + a.pad_t) * HWx + (px + a.pad_l)) * a.T0S;  // S == 1 when has_res
     int8_t* orow = a.out + ((b * a.OH + oy) * (long)a.OW + ox) * a.Cout;
+    if constexpr (NTL > 0) {   // the tile-major last block: tile t of this lane = channels 64 NBW + 16 t + 4 g .. + 3, one dword
 #pragma unroll
-    for (int nb = 0; nb < NBP; nb++) {
+      for (int t = 0; t < NTL; t++) {
+        const int c = NBW * 64 + 16 * t + 4 * g;   // (bias / multiplier arrays are padded to 64-channel blocks)
+        const int4 bb = *(const int4*)(a.bp + c);
+        const float4 mu = *(const float4*)(a.mp + c);
+        unsigned dq = rq_pack_i(acc[pp][NBW][t], bb, mu, a.rqp);
+        if (a.has_res) dq = addq4(dq, *(const unsigned*)(skip + min(c, a.Cin - 4)), a.resq);   // Cin == Cout
+        if (c < a.Cout) *(unsigned*)(orow + c) = dq;   // off for part of the lanes on the last tile only (Cout % 16 != 0)
+      }
+    }
+#pragma unroll
+    for (int nb = 0; nb < NBW; nb++) {
       const int c0 = nb * 64 + 16 * g;
       if (c0 >= a.Cout) continue;
       unsigned d[4];
@@ -656,10 +687,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
 #ifndef FB_MINW
 #define FB_MINW 1
 #endif
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false>
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0>
 __global__ __launch_bounds__(256, FB_MINW) void fused_block_kernel(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fb_smem_dyn[];
-  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ>(a, blockIdx.x, fb_smem_dyn);
+  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ, NTL>(a, blockIdx.x, fb_smem_dyn);
 }
 
 // Several independent problems (e.g. the same head layer on all 5 pyramid levels of both heads) in ONE grid:

@@ -48,7 +48,10 @@ namespace vbt {
 
 int launch_fused_mbconv_tpz(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);   // k_fused_mbconv_tpz.hip
 
+int launch_fused_mbconv_tail(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);  // k_fused_mbconv_tail.hip
+
 int launch_fused_mbconv(const FusedArgs& a, const FusedLaunch& L, hipStream_t st) {
+  if (L.ntl) return launch_fused_mbconv_tail(a, L, st);
   if (L.tpz) return launch_fused_mbconv_tpz(a, L, st);
   const dim3 grid(L.grid);
   if (L.ppw2) {

@@ -24,6 +24,7 @@ struct FusedLaunch {
   int lds_bytes;
   unsigned grid;
   bool tpz = false;     // dw64 as a band-Toeplitz product on a quad-planar E (k_fused_mbconv_tpz.hip)
+  int ntl = 0;          // live tiles of a tile-major part-filled last projection block (k_fused_mbconv_tail.hip); 0: block-major
 };
 // The (k, stride, nbp, KSe) the Toeplitz form is built for - what the MBConv steps of the shipped models resolve to (the first five
 // four blocks of the EfficientNet-Lite backbones: the fifth is not cut into 8 x 8 tiles and its 16 x 8 tile does not fit 64 KB, the later
@@ -32,6 +33,16 @@ struct FusedLaunch {
 static inline bool fused_tpz_built(int k, int stride, int nbp, int kse, bool ppw2) {
   return (k == 3 && stride == 2 && nbp == 1 && kse == 1) || (k == 3 && stride == 1 && nbp == 1 && kse == 1) ||
          (k == 5 && stride == 2 && nbp == 1 && kse == 1 && !ppw2) || (k == 5 && stride == 1 && nbp == 1 && kse == 2);
+}
+// The launches built with a live-tile count for a part-filled last projection block (fused_block.h: NTL) - again what the MBConv steps of
+// the shipped models resolve to: every Toeplitz form above with the tail of its blocks (3x3: Cout = 24, two tiles; 5x5: Cout = 40 or
+// Lite2's 48, three), the diagonal 16x16x64 depthwise on 8 x 8 tiles with 48-channel chunks for the two stride-2 blocks the pinned b256 plan
+// keeps on it (3x3/2 -> 24 and 5x5/2 -> 40 channels, K <= 32), and the generic matrix-pipe form of the 3x3/2 block with 40 -> 80 channels
+// (64 + one tile) on 64-channel chunks.  Another shape needs a line here and one in k_fused_mbconv_tail.hip.
+static inline bool fused_tail_built(const FusedLaunch& L, int kse, int ntl) {
+  if (L.tpz) return fused_tpz_built(L.k, L.stride, L.nbp, kse, L.ppw2) && ntl == (L.k == 3 ? 2 : 3);
+  if (L.dw64) return L.nt3 && !L.ppw2 && L.stride == 2 && L.nbp == 1 && kse == 1 && ntl == (L.k == 3 ? 2 : 3);
+  return L.expand && L.mdw && !L.nt3 && !L.ppw2 && !L.dw64 && L.k == 3 && L.stride == 2 && L.nbp == 2 && kse == 2 && ntl == 1;
 }
 int launch_fused_block(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);
 int launch_fused_multi(const FusedArgs* d_args, const MultiTiles& mt, int k, int stride, int nbp, bool mdw, int lds_bytes, unsigned grid,

@@ -98,6 +98,24 @@ __device__ __forceinline__ void store_tile_e(const v4i acc[4], const EpiRegs& er
         if (c0 + 4 * t + j < N) o[4 * t + j] = (int8_t)(d[t] >> (8 * j));
   }
 }
+// the tile-major part-filled last block `nb` (pack_weights64_tail; N % 4 == 0): tile t of lane (r, g) holds channels 64 nb + 16 t + 4 g .. + 3
+// of pixel m: bias, multipliers and the residual dword from that offset, one dword stored per live tile.  The tile loop is a compile-time
+// count; only the last tile's store can be off for part of the lanes (N % 16 != 0).
+template <int NTL>
+__device__ __forceinline__ void store_tail_tiles(const v4i acc[4], const Epi& e, const ResArgs& ra, int8_t* __restrict__ out, long m, int N,
+                                                 int nb, int g) {
+#pragma unroll
+  for (int t = 0; t < NTL; t++) {
+    const int c = nb * 64 + 16 * t + 4 * g;   // (bias / mult arrays are padded to 64-channel blocks)
+    const int4 b = *(const int4*)(e.bias + c);
+    const float4 mu = *(const float4*)(e.mult + c);
+    if (c < N) {
+      unsigned d = rq_pack_i(acc[t], b, mu, e.rq);
+      if (ra.res) d = addq4(d, *(const unsigned*)(ra.res + m * N + c), ra.q);
+      *(unsigned*)(out + m * N + c) = d;
+    }
+  }
+}
 __device__ __forceinline__ v4i ld16(const int8_t* p) {  // 16 bytes, any 4-byte alignment
   v4i v;
   __builtin_memcpy(&v, p, 16);
@@ -417,12 +435,19 @@ __global__ __launch_bounds__(256) void pw_e_kernel(const int8_t* __restrict__ x,
 // the steps past KS are skipped.  With the packed layout [nb][ks][t][lane] a tile holds channels 16 (i >> 2) + 4 t + (i & 3) of its block, so
 // a part-filled last block (N = 80, 112) has four part-filled tiles and no dead one: all 4 * NB tiles are multiplied.
 // The epilogue operands are loaded after the K loop, block by block: they would otherwise hold 12 * NB * MS registers through it.
-template <int NB, int MS, int PD>
+// NTL > 0 (variants 9 / 10): wp is pack_weights64_tail's panel - the part-filled last block holds NTL tile-major tiles (channels 16 t + i on
+// row i of tile t) instead of four part-filled ones.  Waves >= NTL request and stage nothing for that block, a K-step multiplies
+// 4 (NB - 1) + NTL tiles, and the epilogue requantises NTL tiles of the block, one dword (channels 16 t + 4 g .. + 3) per lane and tile.
+template <int NB, int MS, int PD, int NTL = 0>
 __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x, const v4i* __restrict__ wp, Epi e, ResArgs ra,
                                                    int8_t* __restrict__ out, long M, int K, int KS, int N, int /*NB*/) {
   static_assert(PD % 2 == 0, "the activation queue is refilled in pairs of K-steps");
-  __shared__ v4i wbuf[2][NB * 4][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  static_assert(NTL >= 0 && NTL <= 4 && (NTL == 0 || NB >= 2), "a tile-major last block holds one to four tiles");
+  constexpr int NBW = NTL ? NB - 1 : NB;    // blocks of four tiles
+  constexpr int NTT = 4 * NBW + NTL;        // tiles per K-step
+  __shared__ v4i wbuf[2][NTT][64];
+  const int wave = NTL ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool tail_w = wave < NTL;           // this wave stages a tile of the tile-major last block (wave-uniform)
   const int r = lane & 15, g = lane >> 4;
   const long m0 = ((long)blockIdx.x * 4 + wave) * (16 * MS);
   const int8_t* p[MS];
@@ -430,12 +455,17 @@ __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x,
   for (int s = 0; s < MS; s++) p[s] = x + min(m0 + 16 * s + r, M - 1) * K + 16 * g;
   const v4i* w = wp + wave * 64 + lane;   // this wave's tile of block 0, K-step 0; a K-step is 4 * 64 operands further, a block KS K-steps
   const long wblk = (long)KS * 4 * 64;
+  const v4i* wt = wp + NBW * wblk + wave * 64 + lane;   // NTL: this wave's tile of the last block; a K-step is NTL * 64 operands further
   v4i wst[NB], wnx[NB];   // the weight operands of the next K-step (stored to LDS at the end of this one) and of the one after it
 #pragma unroll
-  for (int b = 0; b < NB; b++) wst[b] = w[b * wblk];
+  for (int b = 0; b < NBW; b++) wst[b] = w[b * wblk];
   const int k1 = min(1, KS - 1);
 #pragma unroll
-  for (int b = 0; b < NB; b++) wnx[b] = w[b * wblk + (long)k1 * 4 * 64];
+  for (int b = 0; b < NBW; b++) wnx[b] = w[b * wblk + (long)k1 * 4 * 64];
+  if constexpr (NTL > 0) {
+    wst[NBW] = wnx[NBW] = (v4i){0, 0, 0, 0};
+    if (tail_w) { wst[NBW] = wt[0]; wnx[NBW] = wt[(long)k1 * NTL * 64]; }
+  }
   v4i aq[PD][MS];
 #pragma unroll
   for (int i = 0; i < PD; i++) {
@@ -451,7 +481,8 @@ __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x,
 #pragma unroll
       for (int t = 0; t < 4; t++) acc[s][b][t] = (v4i){0, 0, 0, 0};
 #pragma unroll
-  for (int b = 0; b < NB; b++) wbuf[0][b * 4 + wave][lane] = wst[b];
+  for (int b = 0; b < NBW; b++) wbuf[0][b * 4 + wave][lane] = wst[b];
+  if constexpr (NTL > 0) { if (tail_w) wbuf[0][4 * NBW + wave][lane] = wst[NBW]; }
 #pragma unroll
   for (int b = 0; b < NB; b++) wst[b] = wnx[b];
   __syncthreads();
@@ -461,13 +492,14 @@ __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x,
       const int ks = ks0 + j;
       const int kw = min(ks + 2, KS - 1);
 #pragma unroll
-      for (int b = 0; b < NB; b++) wnx[b] = w[b * wblk + (long)kw * 4 * 64];
+      for (int b = 0; b < NBW; b++) wnx[b] = w[b * wblk + (long)kw * 4 * 64];
+      if constexpr (NTL > 0) { if (tail_w) wnx[NBW] = wt[(long)kw * NTL * 64]; }
       asm volatile("" ::: "memory");
       if (ks < KS) {
 #pragma unroll
         for (int b = 0; b < NB; b++)
 #pragma unroll
-          for (int t = 0; t < 4; t++) {
+          for (int t = 0; t < (b < NBW ? 4 : NTL); t++) {
             const v4i wv = wbuf[ks & 1][b * 4 + t][lane];
 #pragma unroll
             for (int s = 0; s < MS; s++) acc[s][b][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, aq[j][s], acc[s][b][t], 0, 0, 0);
@@ -479,14 +511,15 @@ __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x,
         for (int s = 0; s < MS; s++) { aq[j - 1][s] = ld16(p[s] + 64 * kn0); aq[j][s] = ld16(p[s] + 64 * kn); }
       }
 #pragma unroll
-      for (int b = 0; b < NB; b++) wbuf[(ks + 1) & 1][b * 4 + wave][lane] = wst[b];
+      for (int b = 0; b < NBW; b++) wbuf[(ks + 1) & 1][b * 4 + wave][lane] = wst[b];
+      if constexpr (NTL > 0) { if (tail_w) wbuf[(ks + 1) & 1][4 * NBW + wave][lane] = wst[NBW]; }
 #pragma unroll
       for (int b = 0; b < NB; b++) wst[b] = wnx[b];
       __syncthreads();
     }
   }
 #pragma unroll
-  for (int b = 0; b < NB; b++)
+  for (int b = 0; b < NBW; b++)
 #pragma unroll
     for (int s = 0; s < MS; s++) {
       const long m = m0 + 16 * s + r;
@@ -494,6 +527,13 @@ __global__ __launch_bounds__(256) void pw_f_kernel(const int8_t* __restrict__ x,
       load_epi(er, e, ra, min(m, M - 1), N, b, g);
       if (m < M) store_tile_e(acc[s][b], er, e, ra, out, m, N, b, g);
     }
+  if constexpr (NTL > 0) {
+#pragma unroll
+    for (int s = 0; s < MS; s++) {
+      const long m = m0 + 16 * s + r;
+      if (m < M) store_tail_tiles<NTL>(acc[s][NBW], e, ra, out, m, N, NBW, g);
+    }
+  }
 }
 
 __device__ __forceinline__ unsigned max4_s8(unsigned a, unsigned b) {

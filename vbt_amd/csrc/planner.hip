@@ -184,6 +184,15 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
     v4i* dwp;
     if ((rc = upload(m, wp, &dwp))) return rc;
     a.wp = dwp; a.bp = ps.bias; a.mp = ps.mult; a.KSp = Cp / 64;
+    // MBConv with a part-filled last projection block: both panels once more with that block tile-major (the kernels built with a
+    // live-tile count, fused_tail_built; resolve_fused decides per launch)
+    if (expand && tout.c % 64 != 0 && tout.c % 4 == 0 && s.nbp == (tout.c + 63) / 64) {
+      pack_weights64_tail(wpj, tout.c, Ce, Cp / 64, s.nbp, wp);
+      if ((rc = upload(m, wp, &dwp))) return rc;
+      a.wpt = dwp;
+      s.ntl = proj_tail_tiles(tout.c);
+      for (int i = 0; i < d_op; i++) s.block += m->ops[i].type == OP_DW;   // b1 = the block of the graph's second depthwise conv
+    }
     a.zo = tout.zero_point; a.lop = pop.act_min; a.hip = pop.act_max;
     a.rqp = make_rq(a.zo, a.lop, a.hip);
   }
@@ -208,6 +217,11 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
     v4i* d3;
     if ((rc = upload(m, pack_expand48(we, Ce, tin.c, a.KSe), &d1)) || (rc = upload(m, pack_dw_diag(wd, Ce, kk, 48), &d2)) || (rc = upload(m, wp3, &d3))) return rc;
     a.we3 = d1; a.wdm3 = d2; a.wp3 = d3; a.nch3 = nch3; a.KSp3 = nch3;
+    if (s.ntl) {
+      pack_weights64_tail(wpj, tout.c, Ce, nch3, s.nbp, wp3, &kmap);
+      if ((rc = upload(m, wp3, &d3))) return rc;
+      a.wpt3 = d3;
+    }
   }
   if (expand && tin.h * tin.w <= 400 && tout.h * tout.w <= 400 && (rc = make_image_bundle(m, e_op, d_op, p_op, a.KSe, &s.ib))) return rc;
   *out = s;
@@ -1132,6 +1146,12 @@ int build_plan(vbt_model* m) {
           std::vector<v4i> wp64;
           pack_weights64(w, N, K, s.KS64, s.NB, wp64);
           if ((rc = upload(m, wp64, &s.wp64))) return rc;
+          // the all-blocks form with a tile-major part-filled last block (pw_f_kernel, variants 9 / 10): a second panel
+          if (s.KS64 > 4 && N % 64 != 0 && N % 4 == 0 && pw_f_tail_built(s.NB, proj_tail_tiles(N))) {
+            pack_weights64_tail(w, N, K, s.KS64, s.NB, wp64);
+            if ((rc = upload(m, wp64, &s.wp64t))) return rc;
+            s.ntl = proj_tail_tiles(N);
+          }
         }
         s.cost.weight_bytes = (double)N * K;
         s.cost.macs_per_frame = out_el * K;

@@ -50,6 +50,32 @@ inline void pack_weights64(const int8_t* w, int N, int K, int KS, int NB, std::v
         }
 }
 
+// The same with a tile-major part-filled last block (N % 64 != 0 and NB == ceil(N / 64)): the full blocks are pack_weights64's byte for
+// byte, [(nb*KS + ks)*4 + t][lane]; the last block holds only its NTL = ceil((N % 64) / 16) live tiles, [(NB-1)*KS*4 + ks*NTL + t][lane],
+// and lane (i, g) of tile t holds W[cout = 64(NB-1) + 16t + i][k = 64ks + 16g + j], zero beyond N / K.  Lane (r, g) of the accumulator of
+// tile t then ends with channels 64(NB-1) + 16t + 4g .. + 3 of pixel r (pack_band_pw's order), so a kernel multiplies and requantises NTL
+// tiles of that block instead of four part-filled ones.  N % 64 == 0 (or padding blocks past N): exactly pack_weights64.
+inline int proj_tail_tiles(int N) { return ((N % 64) + 15) / 16; }
+inline void pack_weights64_tail(const int8_t* w, int N, int K, int KS, int NB, std::vector<v4i>& out, const std::vector<int>* kmap = nullptr) {
+  if (N % 64 == 0 || NB != (N + 63) / 64) { pack_weights64(w, N, K, KS, NB, out, kmap); return; }
+  const int NTL = proj_tail_tiles(N), nbl = NB - 1;
+  std::vector<v4i> full;
+  pack_weights64(w, 64 * nbl, K, KS, nbl, full, kmap);   // (rows 0 .. 64 nbl - 1 only: whole blocks)
+  out.assign((size_t)nbl * KS * 4 * 64 + (size_t)KS * NTL * 64, (v4i){0, 0, 0, 0});
+  std::copy(full.begin(), full.end(), out.begin());
+  int8_t* o = (int8_t*)(out.data() + (size_t)nbl * KS * 4 * 64);
+  for (int ks = 0; ks < KS; ks++)
+    for (int t = 0; t < NTL; t++)
+      for (int lane = 0; lane < 64; lane++) {
+        const int i = lane & 15, g = lane >> 4, co = 64 * nbl + 16 * t + i;
+        for (int j = 0; j < 16; j++) {
+          const int kp = 64 * ks + 16 * g + j;
+          const int k = kmap ? (kp < (int)kmap->size() ? (*kmap)[kp] : -1) : (kp < K ? kp : -1);
+          o[(((size_t)(ks * NTL + t) * 64 + lane) * 16) + j] = (co < N && k >= 0) ? w[(size_t)co * K + k] : 0;
+        }
+      }
+}
+
 // Zero point folded into the bias: out[c] = bq[c] - zp * sum_k w_c[k] for c < n, zero up to `padded` entries.  W_ROWS: w_c[k] =
 // w[c*K + k] (convs); W_TAPS: w_c[k] = w[k*n + c] (depthwise, K taps).  A kernel that accumulates u = x_q + 128 passes zp = 128 + z_x.
 enum WLayout { W_ROWS, W_TAPS };

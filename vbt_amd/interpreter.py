@@ -112,6 +112,14 @@ class Interpreter:
         return [{"group": e.group, "alt": e.alt, "step": e.step, "chosen": bool(e.chosen), "variant": e.variant, "first_op": e.first_op,
                  "last_op": e.last_op, "family": e.family.decode(), "variants": list(e.variants[:e.n_variants])} for e in buf[:n.value]]
 
+    def proj_tail(self, group, alt, step):
+        """Live tiles of the part-filled last output block that plan-space step runs tile-major under its current variant; 0: block-major
+        (vbt_model_step_proj_tail)."""
+        n = _lib.lib().vbt_model_step_proj_tail(self._h, group, alt, step)
+        if n < 0:
+            _lib.check(n)
+        return n
+
     def read_tensor(self, tid, B):
         shp = (ctypes.c_int * 3)()
         _lib.check(_lib.lib().vbt_model_tensor_shape(self._h, tid, shp))
