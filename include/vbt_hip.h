@@ -1050,6 +1050,92 @@ int vbt_curve_figure_render(vbt_curve_figure* f, uint8_t* frames_dev, int fig0, 
 int vbt_curve_figure_table(vbt_curve_figure* f, int fig, int32_t* counts, int cap_series, int* n_series, int32_t* points, int cap_points,
                            int* n_points, int32_t* records, int cap_records, int* n_records);
 
+/* ------------------------------------------------------------------ Validation figure --------
+ * The accuracy study of the reference's kinovea.py:90-172 / qualysis.py:100-187 for N (ground truth, tracked rows) pairs in one
+ * upload and one prepare launch: per pair the numbers validate.metric_trajectory + validate.compare give (vbt_amd/validate.py), and
+ * the reference's figure of the pair - two stacked panels, X and Y over time, ground truth against tracker - rendered into an RGB24
+ * frame that stays in device memory, where vbt_mjpeg_encode takes it.  The aligned trajectories never leave the device between the
+ * comparison and the figure.  There is no display, no LaTeX table and no p-value (the reference drops them before it prints).  The
+ * statements themselves: vbt_amd/csrc/validation_core.h; in numpy: tests/validation_ref.py.  Every double is IEEE, one operation
+ * per statement, without contraction.
+ *
+ * Input per pair: ref [N][3] = time, x, y in metres; rows [T][5] = time, x, y, norm_plate_height, norm_plate_width of one track.
+ * kind, per pair: 0 = kinovea, 1 = qualisys.
+ *
+ * Numbers.  (1) Window means of the rows exactly as vbt_window_means forms them: kinovea (copy, 5, 5, expanding, expanding),
+ * qualisys (copy, copy, copy, 30, 30).  (2) x = sx * plate_diameter / sw, y = -sy * plate_diameter / sh.  (3) y += mean(ref y) -
+ * mean(y), then x likewise.  (4) Every sum - the means, the MSE, the Pearson terms - is taken in ONE fixed order: 256 partial
+ * sums, partial l = 0.0 + term(l) + term(l + 256) + ... in rising order, then a halving tree over the 256 (p[l] += p[l + h],
+ * h = 128 .. 1).  It is not numpy's pairwise order: parity with numpy is to a tolerance.  (5) t_max = min(last times), t_min =
+ * max(first times), n = (int)(t_max * rate).  (6) The grid as numpy.linspace: step = (t_max - t_min) / (n - 1), ts_i = i * step +
+ * t_min, ts_{n-1} = t_max.  (7) Linear interpolation as scipy's interp1d: lower-bound search, hi clipped to 1..len-1, slope *
+ * (ts - t_lo) + v_lo.  (8) mse = sum((a - b)^2) / n.  (9) Pearson r: centre, divide by sqrt(sum of squares), dot, clamp to
+ * [-1, 1]; a constant series gives NaN and sets flag bit 0 (r_x) or 1 (r_y) of the pair.
+ *
+ * Figure.  s = scale, t = thickness.  Margins in cells of s pixels: left 50, right 4, top 17, between the panels 6, bottom 23; the
+ * panels share what height is left.  Time axis [0, max(last ref time, last tracked time)], minor ticks every second, major,
+ * labelled ones every five (every 10^k seconds from 128 ticks on).  Value axes per panel: m, M over both series, d = M - m,
+ * e = 0.05 d (0.05 for d == 0), lo = m - e, hi = M + e; then with dX = hiX - loX, dY = hiY - loY: kinovea, if dX < dY the X panel
+ * becomes [loX - dY/2, hiX + dY/2]; qualisys, if dX > dY the Y panel becomes [loY - dX/2, hiY + dX/2], else the X panel as for
+ * kinovea.  Value ticks at the multiples of the rep figure's step, labelled d.dd.  Texts: `X [m]`, `Y [m]` turned at the left,
+ * `Time [s]` below; the legend in a border at the top right, two entries side by side: `Kinovea` or `Qualisys`, `Velocity Tracker`.
+ * Curves: four series (ref x, tracker x, ref y, tracker y), each with its own times, as MERGED points (column, row, join) by the
+ * curve figure's run merge on this figure's mapping; the tracker's curve is drawn over the ground truth's.  Colours: ground truth
+ * (53, 25, 62), tracker (243, 118, 81).  Records are the curve figure's 28 int32 with its kinds (0 legend text, 1 swatch, 2 legend
+ * box, 7 lines, 8 text) and its rule: the smallest kind that covers a pixel decides it, the curves have place 6.  Nothing is read
+ * from the frames, rendering twice equals rendering once, every byte of the N frames is written and no byte outside them.
+ *
+ * Staging.  A render workgroup owns a 256 x 8 pixel tile; it keeps the merged points of the four series its columns can meet and
+ * the records that touch it in LDS when there are at most VBT_VALIDATION_STAGE_POINTS / VBT_VALIDATION_STAGE_RECORDS of them, and
+ * reads both from global memory otherwise, by the same statements. */
+#define VBT_VALIDATION_STAGE_POINTS 768
+#define VBT_VALIDATION_STAGE_RECORDS 64
+#define VBT_VALIDATION_KINOVEA 0
+#define VBT_VALIDATION_QUALISYS 1
+typedef struct vbt_validation vbt_validation;
+typedef struct {
+  int32_t width, height;  /* -> 1280 x 640 (the reference's 8 x 4 in) */
+  int32_t scale;          /* pixels per cell -> 2 */
+  int32_t thickness;      /* of the curves -> 2 */
+  int32_t max_pairs;      /* -> 64 */
+  int32_t max_rows;       /* tracked rows per pair -> 4096 */
+  int32_t max_ref_rows;   /* ground truth rows per pair -> 4096 */
+  int32_t max_grid;       /* grid points per pair -> 4096 */
+  int32_t reserved;
+} vbt_validation_params;
+void vbt_validation_default_params(vbt_validation_params* p);
+/* params NULL = the defaults.  VBT_ERR_ARG, before any device call: out NULL, width or height outside 1..16384, scale or thickness
+ * outside 1..64, max_pairs outside 1..1024, max_rows, max_ref_rows or max_grid outside 2..2^20, max_pairs * (max_rows +
+ * max_ref_rows + max_grid) above 2^26, a panel below 16 x 16 pixels.  One allocation, create-time only; VBT_ERR_HIP, naming the
+ * size, when the device cannot give it. */
+int vbt_validation_create(int device, const vbt_validation_params* params, vbt_validation** out);
+void vbt_validation_destroy(vbt_validation* h);
+/* The n pairs: kind[i] = the kind of pair i; ref = the ground truth rows of pair 0, 1, ... one after the other (ref_counts[i] rows of 3 doubles), rows = the
+ * tracked rows likewise (row_counts[i] rows of 5 doubles).  Replaces what the handle held; n = 0 leaves it with nothing set.
+ * Refusals, on the host and before any device call, in this order: VBT_ERR_ARG n < 0, a NULL pointer or (VBT_ERR_CAPACITY) n > 1024;
+ * an unknown kind (the pair is named); plate_diameter or rate that is not finite and > 0; a negative count; then per pair, naming the pair and the row:
+ * a value that is not finite, a plate size <= 0, fewer than 2 rows in either series, a time that does not rise strictly in either
+ * series, no common span or n < 2.  Then the handle (NULL: VBT_ERR_ARG) and VBT_ERR_CAPACITY: more pairs, rows or grid points than
+ * it was created for.  A refused call leaves the handle as it was.  ONE upload and ONE prepare launch, a workgroup per pair, on
+ * `stream`, which it synchronises (the upload buffer is the call's own). */
+int vbt_validation_set(vbt_validation* h, int n, const int32_t* kind, double plate_diameter, double rate, const double* ref, const int32_t* ref_counts,
+                       const double* rows, const int32_t* row_counts, void* stream);
+/* Per pair 8 doubles: mse_x, mse_y, r_x, r_y, n, t_min, t_max, flags; one copy (it waits for the stream of the last set or render).
+ * cap in pairs.  VBT_ERR_STATE: nothing is set; VBT_ERR_CAPACITY: cap below the pairs set. */
+int vbt_validation_stats(vbt_validation* h, double* out, int cap);
+/* What the prepare launch formed for pair `pair`: head[6] = time lo, hi, X lo, hi, Y lo, hi; traj = the aligned trajectory, T rows
+ * of time, x, y; grid = n rows of ts, ref x, tracker x, ref y, tracker y; counts[4] = the merged points of ref x, tracker x, ref y,
+ * tracker y; points = those of all series one after the other, 3 int32 each; records = the 28-int32 records.  *n_rows, *n_grid,
+ * *n_points, *n_records and counts are always set; VBT_ERR_CAPACITY when a capacity (in entries) is below them: nothing else is
+ * copied.  VBT_ERR_STATE: nothing is set; VBT_ERR_ARG: pair outside the pairs set. */
+int vbt_validation_table(vbt_validation* h, int pair, double* head, double* traj, int cap_rows, int* n_rows, double* grid, int cap_grid, int* n_grid,
+                         int32_t* counts, int32_t* points, int cap_points, int* n_points, int32_t* records, int cap_records, int* n_records);
+/* Figures pair0 .. pair0 + n - 1 into n contiguous frames of W * H * 3 bytes at frames_dev.  Enqueue only: ONE launch, grid (tile,
+ * pair); vbt_mjpeg_encode can follow on the same stream.  With W % 4 == 0 and frames_dev 4-aligned four pixels go out as three
+ * 32-bit stores, else as bytes.  VBT_ERR_STATE: nothing is set; VBT_ERR_ARG: a NULL argument, pair0 < 0, n < 0 or pair0 + n above
+ * the pairs set. */
+int vbt_validation_render(vbt_validation* h, uint8_t* frames_dev, int pair0, int n, void* stream);
+
 /* ------------------------------------------------------------------ MJPEG export --------
  * A playable export of the drawn frames (the reference's VideoWriter, track.py:96-98,153-154,241-242): every frame of a batch that
  * sits in device memory is encoded there as one baseline JPEG and only the compressed bytes come back; the host wraps them in an AVI

@@ -85,6 +85,11 @@ class CurveFigureParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "scale", "thickness", "max_figures", "max_series", "max_points", "max_marks")]
 
 
+class ValidationParams(ctypes.Structure):
+    """vbt_validation_params (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "scale", "thickness", "max_pairs", "max_rows", "max_ref_rows", "max_grid", "reserved")]
+
+
 class CurveFigureDesc(ctypes.Structure):
     """vbt_curve_figure_desc (include/vbt_hip.h)"""
     _fields_ = [(k, ctypes.c_int32) for k in ("n_series", "n_marks", "legend_corner", "minor_x", "minor_y")] + \
@@ -241,6 +246,14 @@ _SIGS = {
     "vbt_curve_figure_render": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "vbt_curve_figure_table": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int,
                                        ctypes.POINTER(c_int)]),
+    "vbt_validation_default_params": (None, [ctypes.POINTER(ValidationParams)]),
+    "vbt_validation_create": (c_int, [c_int, ctypes.POINTER(ValidationParams), ctypes.POINTER(c_void_p)]),
+    "vbt_validation_destroy": (None, [c_void_p]),
+    "vbt_validation_set": (c_int, [c_void_p, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_validation_stats": (c_int, [c_void_p, c_void_p, c_int]),
+    "vbt_validation_table": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int), c_void_p,
+                                     c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_validation_render": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "vbt_mjpeg_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_mjpeg_destroy": (None, [c_void_p]),
     "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

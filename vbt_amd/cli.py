@@ -56,8 +56,12 @@
       with the new extension.  Up to 64 files go through one upload, one render and one encode.  Prints what `analyze` prints.
       There is no display, so --show_fig is not offered.
   python -m vbt_amd.cli validate [--kinovea_dir D | --qualysis_dir D] [--df_dir dfs] [--plate_diameter 0.45]
-      reference kinovea.py:29-38,57-172,203-215 / qualysis.py:29-38,57-187 without the figures: per export with a
-      matching {video}_id{N}_{model}.pkl.gz, MSE and Pearson r of x(t) and y(t) in metres, then the totals line.
+      [--fig_dir D [--fig_format jpg|ppm] [--fig_quality 90]]
+      reference kinovea.py:29-38,57-172,203-215 / qualysis.py:29-38,57-187: per export with a
+      matching {video}_id{N}_{model}.pkl.gz, MSE and Pearson r of x(t) and y(t) in metres, then the totals line.  With --fig_dir the
+      numbers and the reference's figure of every pair (kinovea.py:124-154,195-197; written there as .pdf) come from one batch on the
+      GPU (vbt_validation) as DIR/{video}_id{N}_{model}.jpg|ppm; the lines keep their formats, the last bits of the totals differ from
+      the default path's (another summation order).  No --show_fig (no display), no LaTeX table, no p-values.
   python -m vbt_amd.cli eval MODELS... [--img_dir data/test] [--annotations_dir data/test] [--iou_threshold 0.5]
                            [--detections_df dfs/eval_detections.pkl.gz] [--replace_df] [--score_thresholds "[0.2, 0.5]"] [--curve_dir DIR] [--rgb]
                            [--fig_dir DIR] [--fig_size 1120x640] [--fig_scale 2] [--fig_format jpg|ppm] [--fig_quality 90]
@@ -509,7 +513,13 @@ def plot(src, plate_diameter, fig_dir, fig_size, fig_scale, fig_format, fig_qual
 @click.option("--qualysis_dir", default=None, help="Directory containing the qualysis exports (*.tsv).")
 @click.option("--df_dir", default="dfs", show_default=True, help="Directory containing the dfs.")
 @click.option("--plate_diameter", default=0.45, show_default=True, type=float, help="Diameter of the weight plate used in meters.")
-def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter):
+@click.option("--fig_dir", default=None, show_default=True,
+              help="Directory for saving the figures ({video}_id{id}_{model}.jpg|ppm). With it, numbers and figures come from one batch on the GPU. "
+                   "There is no --show_fig (no display), no LaTeX table and no p-values.")
+@click.option("--fig_format", default="jpg", show_default=True, type=click.Choice(["jpg", "ppm"]),
+              help="jpg: baseline JPEG encoded on the GPU; ppm: the raw RGB frame behind a P6 header, lossless.")
+@click.option("--fig_quality", default=90, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --fig_format jpg.")
+def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter, fig_dir, fig_format, fig_quality):
     import glob
     import pandas as pd
     from . import validate as V
@@ -518,7 +528,10 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter):
     source = "kinovea" if kinovea_dir is not None else "qualisys"
     exports = sorted(glob.glob(os.path.join(kinovea_dir, "*.txt") if source == "kinovea" else os.path.join(qualysis_dir, "*.tsv")))
     df_files = sorted(glob.glob(os.path.join(df_dir, "*.pkl.gz")))
-    rows_out = []
+    rows_out, pairs = [], []
+
+    def line(video, r):
+        click.echo(f"{video}: MSEx {r['mse_x']:.4f}  MSEy {r['mse_y']:.4f}  r_x {r['r_x']:.4f}  r_y {r['r_y']:.4f}")
     for ex in exports:
         stem = os.path.basename(ex).split(".")[0]
         match = next((x for x in df_files if os.path.basename(x).startswith(stem)), None)
@@ -528,13 +541,24 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter):
         m = FILENAME_RE.match(os.path.basename(match))
         if not m:
             continue
-        video, tid, _ = m.groups()
+        video, tid, model = m.groups()
         df = pd.read_pickle(match).query(f"id == {tid}").sort_values(by="time")
         rows = np.stack([df[c].to_numpy(np.float64) for c in ("time", "x", "y", "norm_plate_height", "norm_plate_width")], axis=1)
         ref = V.read_kinovea(ex) if source == "kinovea" else V.read_qualisys(ex)
+        if fig_dir is not None:                                                   # the whole corpus in one batch, below
+            pairs.append((ref, rows, f"{video}_id{tid}_{model}", video))          # reference kinovea.py:195-197: that name, as .pdf
+            continue
         r = V.validate_pair(ref, rows, plate_diameter, source)
         rows_out.append((video, r))
-        click.echo(f"{video}: MSEx {r['mse_x']:.4f}  MSEy {r['mse_y']:.4f}  r_x {r['r_x']:.4f}  r_y {r['r_y']:.4f}")
+        line(video, r)
+    if fig_dir is not None:
+        try:
+            results, _ = V.validate_many([p[:3] for p in pairs], source, plate_diameter, fig_dir, fig_format, fig_quality)
+        except ValueError as e:                                                   # (VbtArgError: a pair the set refuses)
+            raise click.UsageError(str(e))
+        for (_, _, _, video), r in zip(pairs, results):
+            rows_out.append((video, r))
+            line(video, r)
     click.echo(f"Total MSEx = {sum(r['mse_x'] for _, r in rows_out)}, MSEy = {sum(r['mse_y'] for _, r in rows_out)}")
 
 
