@@ -1293,6 +1293,61 @@ int vbt_mjpeg_decoder_set_entropy(vbt_mjpeg_decoder* d, int mode, int subseq_byt
 /* The mode, the subsequence size SYNC would use (the default resolved) and AUTO's threshold; any pointer may be NULL. */
 int vbt_mjpeg_decoder_get_entropy(vbt_mjpeg_decoder* d, int* mode, int* subseq_bytes, int* auto_min_interval_bytes);
 
+/* ------------------------------------------------------------------ JPEG stills --------
+ * The way in for image files (the reference's cv2.imread in eval.py:173-180): one batch of JPEG files, EVERY FILE ITS OWN SIZE AND
+ * SAMPLING, decoded on the device - straight to the network input, or to RGB24 frames.  The host parses the headers and uploads
+ * only the compressed bytes.
+ *
+ * Bitstream scope, refusals, entropy decoding with its per-frame scan status codes and its two ways through an interval, and the
+ * reconstruction (dequantisation, islow IDCT, fancy upsampling, JFIF colour) are those of "MJPEG import" above, word for word, with
+ * one difference: no frame size is insisted on, so "a frame size other than the handle's" is not a refusal here.  The kernels are
+ * the same ones; where a frame's blocks, restart positions and output lie comes from a per-frame table that travels with the
+ * descriptors in the batch's ONE H2D copy (32 bytes per frame behind the 4.1 KB descriptors).
+ *
+ * Capacity.  A handle is up to max_batch files per batch and a BUDGET OF 8 x 8 BLOCKS FOR THE WHOLE BATCH, not per file.  A file of
+ * H x W takes, with MW = ceil(W / (8 hs)) and MH = ceil(H / (8 vs)) MCUs a side, MW MH (hs vs + 2) blocks in colour and MW MH in
+ * grey - vbt_jpeg_blocks tells it from the header, so that a caller can cut a file list into batches.  The scratch is 128 bytes of
+ * levels, 64 bytes of planar components and one 4-byte restart-table word per block of budget (a file has fewer restart markers
+ * than blocks): 196 bytes per block, 822 MB for 2^22 blocks (forty-three 1920 x 1080 files at 4:4:4, or eighty-five at 4:2:0).
+ * It is allocated by the first batch, not by vbt_jpeg_stills_create, so that every refusal of an argument, a header or a batch
+ * over the budget is made before any device call; that first call fails with VBT_ERR_HIP, naming the size, when the device
+ * cannot give it.  The compressed bytes travel as in "MJPEG import": two pinned staging buffers used in turn, one device buffer,
+ * growing on demand up to 1 GiB per batch.  One handle serves one stream at a time.
+ *
+ * Output.
+ *   vbt_jpeg_stills_decode_resized: dst_dev = uint8 [B,h,w,3]; frame i is preprocess_image(decode(file i), (h, w), swap_rb), bit for
+ *     bit - the float32 bilinear statement of vbt_resize_frames (half-pixel centres: in = (out + 0.5) scale - 0.5 with scale =
+ *     float32(H_i) / float32(h); lower = max(floor(in), 0), upper = min(ceil(in), H_i - 1), lerp = in - floor(in); top = tl +
+ *     (tr - tl) lx, bottom likewise, value = top + (bottom - top) ly, truncated to uint8) applied to the reconstruction above.  One
+ *     kernel, one thread per output pixel: the four taps are reconstructed from the planes (upsampling and colour at full
+ *     resolution) and lerped; no RGB frame at source size is written or read.  swap_rb != 0 stores B, G, R (the decoder yields RGB).
+ *   vbt_jpeg_stills_decode: frame i as RGB24 [H_i, W_i, 3] at frames_dev_out + out_offsets[i] (B offsets in bytes, any alignment;
+ *     the caller sizes the buffer and keeps the frames apart).
+ * Both parse all B headers first and enqueue nothing on an error, the output untouched: VBT_ERR_ARG for a NULL argument, B < 1,
+ * descending offsets, h or w outside 1..4096; VBT_ERR_CAPACITY for B > max_batch, a batch over the block budget or over 1 GiB of
+ * compressed bytes; VBT_ERR_IO for a refused header, the text naming the frame of the batch and the reason.  Then one H2D copy and
+ * four launches on `stream`; host_bytes may be reused as soon as the call returns. */
+typedef struct vbt_jpeg_stills vbt_jpeg_stills;
+/* Host only, no device call: the blocks one file takes of a handle's budget.  VBT_ERR_IO with the reason when the file is refused. */
+int vbt_jpeg_blocks(const uint8_t* bytes, uint64_t n, uint32_t* blocks);
+/* Host only, no device call.  VBT_ERR_ARG: out NULL, device < 0, max_batch outside 1..1024, block_budget outside 1..2^24.  A device
+ * index the machine does not have is not seen here: the handle's first batch fails with it (VBT_ERR_HIP, "device not available",
+ * as every other *_create says it), like the allocation, with nothing enqueued. */
+int vbt_jpeg_stills_create(int device, int max_batch, uint64_t block_budget, vbt_jpeg_stills** out);
+void vbt_jpeg_stills_destroy(vbt_jpeg_stills* s);
+int vbt_jpeg_stills_decode_resized(vbt_jpeg_stills* s, const uint8_t* host_bytes, const uint64_t* offsets, int B, uint8_t* dst_dev, int h, int w, int swap_rb,
+                                   void* stream);
+int vbt_jpeg_stills_decode(vbt_jpeg_stills* s, const uint8_t* host_bytes, const uint64_t* offsets, int B, uint8_t* frames_dev_out, const uint64_t* out_offsets,
+                           void* stream);
+/* The scan status of every file of the last batch (B words): ONE synchronisation of `stream`, one copy.  VBT_ERR_STATE: nothing
+ * has been decoded yet. */
+int vbt_jpeg_stills_status(vbt_jpeg_stills* s, int32_t* status, void* stream);
+/* As vbt_mjpeg_decoder_set_entropy / _get_entropy (VBT_MJPEG_ENTROPY_*).  AUTO keeps its rule: a batch takes SYNC when some file has
+ * scan bytes / intervals >= auto_min_interval_bytes - files without restart markers, what cameras and Pillow write, are one
+ * interval each. */
+int vbt_jpeg_stills_set_entropy(vbt_jpeg_stills* s, int mode, int subseq_bytes);
+int vbt_jpeg_stills_get_entropy(vbt_jpeg_stills* s, int* mode, int* subseq_bytes, int* auto_min_interval_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,12 @@ int vbt_mjpeg_decode_stage_ms(vbt_mjpeg_decoder* d, float* ms6);
  * INTERVAL), the most rounds any chunk took, intervals finished by the single lane }.  One synchronisation of `stream`, one copy.
  * VBT_ERR_STATE before the first decode. */
 int vbt_mjpeg_decode_entropy_info(vbt_mjpeg_decoder* d, int32_t* info4, void* stream);
+/* JPEG stills, measurement (tools/eval_jpeg_bench.py): the same two queries for a vbt_jpeg_stills handle - the sixth stage time is
+ * upsampling + colour (vbt_jpeg_stills_decode) or upsampling + colour + resize (vbt_jpeg_stills_decode_resized); the variable is read
+ * by the handle's first batch - and the bytes of the last batch's one H2D copy (0 before the first batch). */
+int vbt_jpeg_stills_stage_ms(vbt_jpeg_stills* s, float* ms6);
+int vbt_jpeg_stills_entropy_info(vbt_jpeg_stills* s, int32_t* info4, void* stream);
+int vbt_jpeg_stills_uploaded_bytes(vbt_jpeg_stills* s, uint64_t* bytes);
 
 #ifdef __cplusplus
 }

@@ -267,6 +267,17 @@ _SIGS = {
     "vbt_mjpeg_decoder_set_entropy": (c_int, [c_void_p, c_int, c_int]),
     "vbt_mjpeg_decoder_get_entropy": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "vbt_mjpeg_decode_entropy_info": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vbt_jpeg_blocks": (c_int, [c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
+    "vbt_jpeg_stills_create": (c_int, [c_int, c_int, ctypes.c_uint64, ctypes.POINTER(c_void_p)]),
+    "vbt_jpeg_stills_destroy": (None, [c_void_p]),
+    "vbt_jpeg_stills_decode_resized": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vbt_jpeg_stills_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vbt_jpeg_stills_status": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vbt_jpeg_stills_set_entropy": (c_int, [c_void_p, c_int, c_int]),
+    "vbt_jpeg_stills_get_entropy": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "vbt_jpeg_stills_stage_ms": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "vbt_jpeg_stills_entropy_info": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vbt_jpeg_stills_uploaded_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 

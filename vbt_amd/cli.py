@@ -64,8 +64,9 @@
       the default path's (another summation order).  No --show_fig (no display), no LaTeX table, no p-values.
   python -m vbt_amd.cli eval MODELS... [--img_dir data/test] [--annotations_dir data/test] [--iou_threshold 0.5]
                            [--detections_df dfs/eval_detections.pkl.gz] [--replace_df] [--score_thresholds "[0.2, 0.5]"] [--curve_dir DIR] [--rgb]
-                           [--fig_dir DIR] [--fig_size 1120x640] [--fig_scale 2] [--fig_format jpg|ppm] [--fig_quality 90]
-      reference eval.py:471-521: VOC annotations, every image through each model at threshold 0, Hungarian
+                           [--jpeg_decode auto|gpu|host] [--fig_dir DIR] [--fig_size 1120x640] [--fig_scale 2] [--fig_format jpg|ppm] [--fig_quality 90]
+      reference eval.py:471-521: VOC annotations, every image through each model at threshold 0 (.jpg files decoded on the GPU
+      straight to the network input, mixed sizes in one batch; --jpeg_decode host: with PIL as before), Hungarian
       matching and the PR / ROC curves on the GPU; writes (or, when it exists and --replace_df is not given, reads) the detections
       DataFrame, prints AP and AUC per model as the reference's legends show them and, for each --score_thresholds value, the
       closest curve point; --curve_dir writes the curve points as CSV.  --fig_dir writes, after the lines, the reference's figures
@@ -573,6 +574,9 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter, fig_dir, fig_for
 @click.option("--score_thresholds", default="[]", show_default=True, help='List of score thresholds to locate on the curves, e.g. "[0.2, 0.5]".')
 @click.option("--curve_dir", default=None, show_default=True, help="Directory for the curve points as CSV. If not set they are not written.")
 @click.option("--rgb", is_flag=True, help="Feed RGB to the network (the reference's eval.py feeds cv2's BGR unswapped; that is the default).")
+@click.option("--jpeg_decode", default="auto", show_default=True, type=click.Choice(["auto", "gpu", "host"]),
+              help="Where .jpg test images are decoded. auto: baseline files on the GPU, straight to the network input, and files its decoder "
+                   "refuses (progressive, CMYK, ...) on the host; gpu: such a file is an error; host: every file on the host (PIL).")
 @click.option("--fig_dir", default=None, show_default=True, help="Directory for saving the figures. If not set the figures won't be saved.")
 @click.option("--fig_size", default="1120x640", show_default=True, type=str,
               help="WIDTHxHEIGHT of the combined figures in pixels; the per-model figures are three quarters as high.")
@@ -580,8 +584,8 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter, fig_dir, fig_for
 @click.option("--fig_format", default="jpg", show_default=True, type=click.Choice(["jpg", "ppm"]),
               help="jpg: baseline JPEG encoded on the GPU; ppm: the raw RGB frame behind a P6 header, lossless.")
 @click.option("--fig_quality", default=90, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --fig_format jpg.")
-def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb, fig_dir, fig_size, fig_scale,
-             fig_format, fig_quality):
+def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb, jpeg_decode, fig_dir, fig_size,
+             fig_scale, fig_format, fig_quality):
     import ast
     import pandas as pd
     from . import evaluate as E
@@ -595,7 +599,12 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
     if not os.path.exists(detections_df) or replace_df:                            # reference eval.py:506-512
         click.echo(f"Creating dataframe '{detections_df}'.")
         annotations = E.read_annotations(annotations_dir)
-        df = E.create_detections_df(models, img_dir, annotations, detections_df, rgb=rgb)
+        try:
+            df = E.create_detections_df(models, img_dir, annotations, detections_df, rgb=rgb, jpeg_decode=jpeg_decode)
+        except E.JpegRefused as e:                                                 # (a .jpg that --jpeg_decode gpu refuses: another mode takes it)
+            raise click.UsageError(str(e))
+        except E.JpegDamaged as e:                                                 # (bad data, not bad usage: exit code 1)
+            raise click.ClickException(str(e))
     else:
         click.echo(f"Loading dataframe '{detections_df}'.")
         df = pd.read_pickle(detections_df)

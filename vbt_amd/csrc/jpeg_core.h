@@ -9,11 +9,13 @@
 //                        that synchronise; jpeg_sync_cold: the guess; jpeg_decode_rest: one lane finishes an interval from a true state
 //   jpeg_idct_islow      dequantised coefficients -> 64 samples (the "islow" integer IDCT)
 //   jpeg_chroma_at       one chroma sample at full resolution ("fancy" triangle upsampling); jpeg_ycc_rgb: the colour tables
+//   jpeg_resized_pixel   one pixel of the network input: the four taps of the bilinear resize taken through jpeg_pixel
 // Every loop is bounded by a count known before it starts (MCUs of the interval, 64 coefficients, 16 code lengths, 7 bytes of a
 // refill, the 8 S + 32 symbols of a subsequence of S bytes); none is bounded by the data.  A read past the interval's end, a code no
 // table holds and a coefficient index above 63 each return a status and end the interval.  Nothing is read outside [start, end) of
 // the scan or written outside the frame's levels.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -509,6 +511,37 @@ VBT_HD inline void jpeg_pixel(const JpegDesc& d, const JpegLayout& L, const uint
   const int cb = jpeg_chroma_at(planes + (size_t)L.boff[1] * 64, pw, d.hs, d.vs, dw, dh, y, x);
   const int cr = jpeg_chroma_at(planes + (size_t)L.boff[2] * 64, pw, d.hs, d.vs, dw, dh, y, x);
   jpeg_ycc_rgb(Y, cb, cr, rgb);
+}
+
+// ---- straight to the network input (include/vbt_hip.h, "JPEG stills"): preprocess_image of the decoded frame, the frame never written.
+// jpeg_resize_scale: the source-to-target ratio of one axis, float32 as resize_frames_dev (detector.hip) and oracle/preprocess.py take it; computed on
+// the host and handed to the kernel
+inline float jpeg_resize_scale(int n_in, int n_out) { return (float)n_in / (float)n_out; }
+
+// Output pixel (oy, ox) of the bilinear resize (half-pixel centres, float32, truncating cast: resize_bilinear_kernel, op_kernels.h)
+// of a frame that exists only as its planes: the four taps are jpeg_pixel - fancy upsampling and colour at full resolution - and
+// they are lerped in the order yuv_resize_kernel (yuv_kernels.h) uses.  sy = H / h, sx = W / w (jpeg_resize_scale).  Taps are
+// clamped to 0 .. H - 1 and 0 .. W - 1, so jpeg_pixel reads what it reads for the frame's own pixels and nothing else.
+// swap: out3 = B, G, R.  No contraction of a multiply and an add is allowed (built with -ffp-contract=off).
+VBT_HD inline void jpeg_resized_pixel(const JpegDesc& d, const JpegLayout& L, const uint8_t* planes, float sy, float sx, int oy, int ox, int swap, uint8_t* out3) {
+  const float iy = ((float)oy + 0.5f) * sy - 0.5f, ix = ((float)ox + 0.5f) * sx - 0.5f;
+  const float fy = floorf(iy), fx = floorf(ix);
+  const int cy = (int)ceilf(iy), cx = (int)ceilf(ix);
+  const int y0 = (int)fy > 0 ? (int)fy : 0, y1 = cy < d.H - 1 ? cy : d.H - 1;
+  const int x0 = (int)fx > 0 ? (int)fx : 0, x1 = cx < d.W - 1 ? cx : d.W - 1;
+  const float ly = iy - fy, lx = ix - fx;
+  uint8_t tl[3], tr[3], bl[3], br[3];
+  jpeg_pixel(d, L, planes, y0, x0, tl);
+  jpeg_pixel(d, L, planes, y0, x1, tr);
+  jpeg_pixel(d, L, planes, y1, x0, bl);
+  jpeg_pixel(d, L, planes, y1, x1, br);
+  for (int c = 0; c < 3; c++) {
+    const float a = (float)tl[c], b = (float)tr[c], e = (float)bl[c], f = (float)br[c];
+    const float top = a + (b - a) * lx;
+    const float bot = e + (f - e) * lx;
+    const float v = top + (bot - top) * ly;
+    out3[swap ? 2 - c : c] = (uint8_t)(int)v;
+  }
 }
 
 }  // namespace vbt

@@ -6,9 +6,15 @@ Matching and curves run on the GPU (`vbt_eval_*`, include/vbt_hip.h; vbt_amd/csr
 device between the detector and the matcher.  No torch, no scipy, no scikit-learn.
 
 Images.  eval.py reads every image with cv2.imread and hands that **BGR** array to the network unswapped (eval.py:173-180;
-track.py:171 swaps, eval.py does not).  The default here reproduces that: `.jpg` / `.png` files are decoded with PIL and reordered to
-BGR, `.npy` files hold a decoded image uint8 [H,W,3] in cv2's BGR order; `rgb=True` (CLI `--rgb`) feeds RGB instead.  JPEG decoders
-differ in the low bits, so pixel parity with cv2 is not claimed for `.jpg` sources.
+track.py:171 swaps, eval.py does not).  The default here reproduces that: `.npy` files hold a decoded image uint8 [H,W,3] in cv2's BGR
+order; `.png` files are decoded with PIL and reordered to BGR; `rgb=True` (CLI `--rgb`) feeds RGB instead.
+
+`.jpg` files are decoded on the GPU (`vbt_jpeg_stills`, vbt_amd/stills.py): baseline files of any mix of sizes go, in the given
+order, in batches of compressed bytes to the device, where they are decoded and resized to the network input in one pass - no Pillow,
+no decoded frame on the host or on the bus.  The reconstruction is libjpeg-turbo's default, bit for bit (what Pillow and cv2 give for
+such files), so the result equals the `.npy` route on the same pixels.  A `.jpg` the decoder refuses (progressive, CMYK, ...) is
+decoded with PIL as before; `jpeg_decode` (CLI `--jpeg_decode auto|gpu|host`) makes that an error ("gpu") or the route of every
+`.jpg` ("host").
 """
 import ctypes
 import os
@@ -180,8 +186,43 @@ def model_name(path):
     return os.path.basename(path).split(".")[0]               # eval.py:188
 
 
+JPEG_DECODE_MODES = ("auto", "gpu", "host")
+STILLS_MAX_BLOCK_BUDGET = 1 << 22  # most 8 x 8 blocks per batch of the GPU JPEG decoder (196 B of scratch each): eighty-five 1920 x 1080 files at 4:2:0
+
+
+class JpegRefused(ValueError):
+    """jpeg_decode="gpu" and a .jpg file the GPU decoder does not take; the text names the file and the reason"""
+
+
+class JpegDamaged(ValueError):
+    """a .jpg file whose scan the GPU decoder could not decode to its end; the text names the file and the scan status"""
+
+
+def is_jpeg(path):
+    return path.lower().endswith((".jpg", ".jpeg"))
+
+
+def jpeg_header(jpeg):
+    """(height, width, blocks) of one .jpg the GPU decoder accepts - `jpeg`: the file's bytes, or its path - from vbt_jpeg_probe and
+    vbt_jpeg_blocks (host only, no Pillow), or the reason the decoder refuses it, as a str"""
+    if isinstance(jpeg, str):
+        with open(jpeg, "rb") as f:
+            jpeg = f.read()
+    L = _lib.lib()
+    buf = np.frombuffer(jpeg or b"\0", np.uint8)
+    H, W, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint32()
+    if L.vbt_jpeg_probe(buf.ctypes.data, len(jpeg), ctypes.byref(H), ctypes.byref(W), None, None) or L.vbt_jpeg_blocks(buf.ctypes.data, len(jpeg), ctypes.byref(n)):
+        text = L.vbt_last_error().decode()
+        for prefix in ("vbt_jpeg_probe: ", "vbt_jpeg_blocks: "):
+            if text.startswith(prefix):
+                text = text[len(prefix):]
+        return text
+    return H.value, W.value, int(n.value)
+
+
 def image_size(path):
-    """(height, width) of an image file from its header, without decoding it"""
+    """(height, width) of an image file from its header, without decoding it.  .jpg: Pillow reads only the header when it is there;
+    without Pillow vbt_jpeg_probe says it for the files the GPU decoder accepts."""
     if path.endswith(".npy"):
         shp = np.load(path, mmap_mode="r").shape
         if len(shp) != 3 or shp[2] != 3:
@@ -190,28 +231,105 @@ def image_size(path):
     try:
         from PIL import Image
     except ImportError:
-        raise RuntimeError(f"{path}: reading .jpg / .png images needs PIL (pillow); store the decoded image as .npy uint8 [H,W,3] instead") from None
+        head = jpeg_header(path) if is_jpeg(path) else None
+        if head is not None and not isinstance(head, str):
+            return head[0], head[1]
+        raise RuntimeError(f"{path}: reading .png images and .jpg images the GPU decoder refuses needs PIL (pillow); store the decoded image as "
+                           ".npy uint8 [H,W,3] instead") from None
     with Image.open(path) as im:
         return int(im.size[1]), int(im.size[0])
 
 
-def detections_table(model, images, annotations, rgb=False, device=0, batch=BATCH):
-    """One model over `images` = [(filename, path)]: every image through the pipeline's detector-only step at source resolution
-    (device resize), the detections handed to the matcher on the device.  Images are grouped by size (read from the file headers) and
-    decoded one batch at a time; at most 8 batches of host frames are alive at once.  Returns (table, image_names): table as
-    Evaluator.table(), its `image` column indexing image_names (the order the images were processed in, not the order given)."""
+class SortedImages:
+    """`images` = [(filename, path)] split by route.  stills: the names of the .jpg files the GPU decoder takes, in the given order, with
+    heads[name] = (height, width, blocks) and data[name] = the file's bytes - each file is read once, here, and the compressed bytes stay
+    in memory for as long as this object lives; host: every other name."""
+
+    def __init__(self, images, jpeg_decode="auto"):
+        if jpeg_decode not in JPEG_DECODE_MODES:
+            raise ValueError(f"jpeg_decode {jpeg_decode!r}: one of {', '.join(JPEG_DECODE_MODES)}")
+        self.stills, self.heads, self.data, self.host = [], {}, {}, []
+        for name, path in images:
+            if jpeg_decode != "host" and is_jpeg(path):
+                with open(path, "rb") as f:
+                    data = f.read()
+                head = jpeg_header(data)
+                if not isinstance(head, str) and head[2] > STILLS_MAX_BLOCK_BUDGET:
+                    head = f"{head[2]} blocks of 8 x 8, a batch holds {STILLS_MAX_BLOCK_BUDGET}"
+                if not isinstance(head, str):
+                    self.stills.append(name)
+                    self.heads[name], self.data[name] = head, data
+                    continue
+                if jpeg_decode == "gpu":
+                    raise JpegRefused(f"{path}: the GPU JPEG decoder refuses the file: {head} (--jpeg_decode auto decodes such files on the host)")
+            self.host.append(name)
+
+
+def _stills_table(pipe, ev, stream, srt, paths, annotations, rgb, device, batch):
+    """The .jpg files the GPU decoder accepts, in the given order and whatever their sizes: cut into batches by count and block budget,
+    only the compressed bytes uploaded, decoded and resized to the model's input size into one of two device buffers that detect_into
+    takes by pointer - the order of decode and forwards is track_frames' for .avi sources.  The handle's budget is the largest batch's
+    need, so a directory of small images takes little device memory.  A file whose scan status is not 0 raises JpegDamaged.  Returns
+    the device outputs to keep alive."""
+    from .stills import STATUS_TEXT, JpegStills, plan
+    names, heads = srt.stills, srt.heads
+    n, size = len(names), pipe._size
+    out = [DeviceBuffer(n * MAX_DETECTIONS * 4 * 4, device), DeviceBuffer(n * MAX_DETECTIONS * 4, device), DeviceBuffer(n * MAX_DETECTIONS * 4, device),
+           DeviceBuffer(n * 4, device)]
+    batches = plan([heads[k][2] for k in names], batch, STILLS_MAX_BLOCK_BUDGET)
+    dec = JpegStills(batch, max(sum(heads[k][2] for k in names[i0:i1]) for i0, i1 in batches), device)
+    bufs = [DeviceBuffer(batch * size * size * 3, device) for _ in range(2)]
+    pending = None                                           # the batch whose scan status has not been read yet
+
+    def check_status():
+        for k, st in zip(pending, dec.status()):             # one synchronisation of `stream`
+            if st:
+                raise JpegDamaged(f"{paths[k]}: damaged JPEG scan (status {int(st)}: {STATUS_TEXT.get(int(st), '?')})")
+
+    for j, (i0, i1) in enumerate(batches):
+        part = names[i0:i1]
+        buf = bufs[j % 2]                                    # written again two batches later: the forwards that read it come first
+        pipe.join_detectors(stream.value)
+        try:
+            dec.decode_resized([srt.data[k] for k in part], buf.ptr, size, size, swap_rb=not rgb, stream=stream)   # the decoder yields RGB, eval.py feeds BGR
+        except _lib.VbtError as e:
+            raise _lib.VbtError(f"{paths[part[0]]} .. {paths[part[-1]]}: {e}") from None
+        ptrs = (out[0].ptr + i0 * MAX_DETECTIONS * 16, out[1].ptr + i0 * MAX_DETECTIONS * 4, out[2].ptr + i0 * MAX_DETECTIONS * 4, out[3].ptr + i0 * 4)
+        pipe.detect_into(buf.ptr, *ptrs, stream=stream.value, n_frames=len(part))
+        pipe.join_detectors(stream.value)
+        ev.add(ptrs[0], ptrs[1], ptrs[3], [heads[k][:2] for k in part], [annotations[k] for k in part], stream)
+        pending = part
+        check_status()                                       # (the decoder keeps the status of its last batch only)
+    _lib.check(_lib.lib().vbt_stream_synchronize(stream))    # the decoder and the buffers go away with this frame
+    return out
+
+
+def detections_table(model, images, annotations, rgb=False, device=0, batch=BATCH, jpeg_decode="auto", sorted_images=None):
+    """One model over `images` = [(filename, path)]: every image through the pipeline's detector-only step, the detections handed to
+    the matcher on the device.  `.jpg` files the GPU decoder accepts (jpeg_decode "auto" or "gpu") are decoded on the device straight to
+    the network input, in the given order whatever their sizes (_stills_table).  Everything else - .npy, .png, a .jpg the decoder
+    refuses, or every .jpg with jpeg_decode="host" - is grouped by size (read from the file headers), decoded on the host one batch at a
+    time and resized on the device; at most 8 batches of host frames are alive at once.  jpeg_decode="gpu": a refused .jpg raises
+    JpegRefused, naming the file and the reason.  sorted_images: SortedImages(images, jpeg_decode) made by the caller, so that several
+    models share one reading of the files.
+    Returns (table, image_names): table as Evaluator.table(), its `image` column indexing image_names (the order the images were
+    processed in, not the order given)."""
     from .track import Pipeline
     L = _lib.lib()
     paths = dict(images)
+    srt = sorted_images if sorted_images is not None else SortedImages(images, jpeg_decode)
     groups = {}
-    for name, path in images:
-        groups.setdefault(image_size(path), []).append(name)
+    for name in srt.host:
+        groups.setdefault(image_size(paths[name]), []).append(name)
     pipe = Pipeline(model, batch, max_frames=1, detection_treshold=0.0, device=device)
     stream = ctypes.c_void_p()
     _lib.check(L.vbt_stream_create(int(device), ctypes.byref(stream)))
     ev = Evaluator(max(1, len(images)) * MAX_DETECTIONS, batch, device)
     order, outs, alive = [], [], []                          # outs: device outputs, alive: host frames of steps in flight
     try:
+        if srt.stills:
+            outs.append(_stills_table(pipe, ev, stream, srt, paths, annotations, rgb, device, batch))
+            order += srt.stills
         for (H, W), names in groups.items():
             n = len(names)
             out = [DeviceBuffer(n * MAX_DETECTIONS * 4 * 4, device), DeviceBuffer(n * MAX_DETECTIONS * 4, device),
@@ -243,14 +361,16 @@ def detections_table(model, images, annotations, rgb=False, device=0, batch=BATC
     return table, order
 
 
-def create_detections_df(models, img_dir, annotations, export_path=None, rgb=False, device=0):
+def create_detections_df(models, img_dir, annotations, export_path=None, rgb=False, device=0, jpeg_decode="auto"):
     """create_detections_df of eval.py:156-215: the DataFrame with columns Score (float32), Model, IoU (float64), one row per matched
-    detection, files outer / models inner in the order of `annotations` (eval.py:194-205); written to export_path as a pickle."""
+    detection, files outer / models inner in the order of `annotations` (eval.py:194-205); written to export_path as a pickle.
+    jpeg_decode: where .jpg files are decoded (detections_table)."""
     import pandas as pd
     images = [(name, find_image(img_dir, name)) for name in annotations]
+    srt = SortedImages(images, jpeg_decode)                    # the files are sorted by route, and the .jpg read, once for all models
     per_model = {}
     for m in models:
-        table, order = detections_table(m, images, annotations, rgb=rgb, device=device)
+        table, order = detections_table(m, images, annotations, rgb=rgb, device=device, jpeg_decode=jpeg_decode, sorted_images=srt)
         first = np.searchsorted(table["image"], np.arange(len(order) + 1))       # rows of image k: first[k] .. first[k+1]
         per_model[model_name(m)] = (table, {name: (first[k], first[k + 1]) for k, name in enumerate(order)})
     scores, names, ious = [], [], []

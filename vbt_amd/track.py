@@ -526,12 +526,18 @@ class Pipeline:
         self._enqueued(L.vbt_pipeline_step_runs(self._h, fptr, srcs, int(on_dev), ra, len(runs), H if src_hw is not None else 0, W if src_hw is not None else 0,
                                                 int(bool(swap_rb)), int(bool(track)), outs[0], outs[1], outs[2], outs[3], self._caller_stream(stream) if on_dev else None))
 
-    def detect_into(self, frames, boxes_ptr, scores_ptr, classes_ptr, counts_ptr, stream=None, src_hw=None, swap_rb=False):
+    def detect_into(self, frames, boxes_ptr, scores_ptr, classes_ptr, counts_ptr, stream=None, src_hw=None, swap_rb=False, n_frames=None):
         """Detector-only step over the B <= n_slots frames of `frames` ([B,H,W,3], host or device, as step() takes them) whose
         detections go to the caller's DEVICE buffers given as raw pointers (boxes float32 [B,25,4], scores / classes float32 [B,25],
         counts int32 [B]) instead of the pipeline's ring; the tracker is not stepped.  The caller keeps the buffers alive and
-        untouched until the step has run (join_detectors); no torch on this path (the detector evaluation uses it)."""
+        untouched until the step has run (join_detectors); no torch on this path (the detector evaluation uses it).
+        n_frames: B when `frames` is a raw device pointer, which has no shape (default: all n slots); for an array it must not exceed
+        the array's frames."""
         B = int(frames.shape[0]) if hasattr(frames, "shape") else self.n
+        if n_frames is not None:
+            if hasattr(frames, "shape") and int(n_frames) > B:
+                raise ValueError(f"detect_into: n_frames {n_frames}, the array holds {B}")
+            B = int(n_frames)
         if not 1 <= B <= self.n:
             raise ValueError(f"detect_into: {B} frames, the pipeline has {self.n} slots")
         k = self._next_slot()
