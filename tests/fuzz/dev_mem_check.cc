@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
+#include <vector>
 
 #include "../../vbt_amd/csrc/dev_mem.h"
 #include "../../vbt_amd/csrc/hip_handles.h"
@@ -93,11 +94,75 @@ static int check_handle(const char* name, unsigned flags) {
   return 0;                                         // a, b, c: destruction of moved-from and empty owners
 }
 
+// PinnedBuf::alloc with explicit flags: the same books as without, and the flags of a record the device writes are taken
+static int check_pinned_flags() {
+  const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
+  PinnedBuf<double> a, plain;
+  CHECK(a.alloc((size_t)1 << 57, flags) != hipSuccess);   // a failed alloc leaves the buffer null
+  CHECK(!a && a.get() == nullptr);
+  const hipError_t e = a.alloc(16, flags);
+  CHECK((e == hipSuccess) == (a.get() != nullptr));
+  CHECK(e == plain.alloc(16));                      // the flags are accepted: they change nothing about success or the error
+  CHECK(a.alloc((size_t)1 << 57, flags) != hipSuccess);   // a failed re-alloc frees what was held
+  CHECK(a.get() == nullptr);
+  std::printf("ok PinnedBuf-flags %s\n", e == hipSuccess ? "allocated" : "no-device");
+  return 0;
+}
+
+// What a handle keeps in a std::vector: events, and a ring slot of one buffer and two events.  resize() default-constructs and, when
+// it grows past the capacity, moves every element: each owner must arrive with what it held and leave nothing behind to destroy twice.
+struct Slot {
+  DevBuf<unsigned char> buf;
+  Event free_ev, copy_ev;
+  size_t bytes = 0;
+};
+static int check_vectors() {
+  std::vector<Event> evs;
+  evs.resize(3);
+  hipError_t e = hipSuccess;
+  for (Event& ev : evs) {
+    const hipError_t ei = ev.create(hipEventDisableTiming);
+    CHECK((ei == hipSuccess) == (ev.get() != nullptr));
+    if (e == hipSuccess) e = ei;
+  }
+  const hipEvent_t h0 = evs[0].get(), h2 = evs[2].get();
+  evs.resize(evs.capacity() + 6);                   // reallocates: the elements move
+  CHECK(evs[0].get() == h0 && evs[2].get() == h2 && !evs[3] && !evs.back());
+  std::vector<Event> moved(std::move(evs));
+  CHECK(evs.empty() && moved[0].get() == h0);
+  moved.resize(1);                                  // destroys the tail, created and empty alike
+
+  std::vector<Slot> ring;
+  ring.resize(2);
+  for (Slot& s : ring) {
+    const hipError_t eb = s.buf.alloc(64);
+    if (eb == hipSuccess) s.bytes = 64;
+    CHECK((s.bytes == 0) == (s.buf.get() == nullptr));   // the capacity is 0 whenever the buffer is empty
+    (void)s.free_ev.create(hipEventDisableTiming);
+    (void)s.copy_ev.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = eb;
+  }
+  unsigned char* const b1 = ring[1].buf.get();
+  const hipEvent_t f1 = ring[1].free_ev.get(), c1 = ring[1].copy_ev.get();
+  ring.resize(ring.capacity() + 5);
+  CHECK(ring[1].buf.get() == b1 && ring[1].free_ev.get() == f1 && ring[1].copy_ev.get() == c1);
+  CHECK(!ring.back().buf && !ring.back().free_ev && ring.back().bytes == 0);
+  std::vector<Slot> ring2;
+  ring2 = std::move(ring);
+  CHECK(ring.empty() && ring2[1].buf.get() == b1);
+  CHECK(ring2[1].buf.alloc((size_t)1 << 60) != hipSuccess && !ring2[1].buf);   // a grow that fails: empty, the events stay
+  CHECK(ring2[1].free_ev.get() == f1);
+  std::printf("ok vectors %s\n", e == hipSuccess ? "created" : "no-device");
+  return 0;                                         // moved, ring2: destruction of what is left
+}
+
 int main() {
   std::setvbuf(stdout, nullptr, _IOLBF, 0);
   if (check_buf<DevBuf<double>>("DevBuf")) return 1;
   if (check_buf<PinnedBuf<double>>("PinnedBuf")) return 1;
   if (check_mirror()) return 1;
   if (check_handle<Event>("Event", hipEventDisableTiming)) return 1;
-  return check_handle<Stream>("Stream", hipStreamNonBlocking);
+  if (check_handle<Stream>("Stream", hipStreamNonBlocking)) return 1;
+  if (check_pinned_flags()) return 1;
+  return check_vectors();
 }

@@ -2,7 +2,8 @@
 (vbt_amd/csrc/hip_handles.h: Event, Stream) under -fsanitize=address,undefined: a stand-alone host program
 (tests/fuzz/dev_mem_check.cc) with every device hidden, so that each allocation fails as it does on a machine without a GPU.  Checked:
 a failed alloc leaves the buffer null, a move leaves the source empty, a Mirror is usable after a failed reserve, a failed create leaves
-an event / stream owner empty, empty and moved-from objects destruct cleanly.  Nothing loaded into Python is run under a sanitizer."""
+an event / stream owner empty, empty and moved-from objects destruct cleanly, pinned allocation flags keep the same books, and owners
+held in a std::vector (events; a ring slot of a buffer and two events) survive resize, move and destruction.  Nothing loaded into Python is run under a sanitizer."""
 import os
 import subprocess
 
@@ -33,3 +34,6 @@ def test_owners_keep_their_books_when_every_allocation_fails(harness):
     handles = p.stdout.split("\n")[3:5]       # the event and stream owners: "created" where a device showed
     assert [ln.rsplit(" ", 1)[0] for ln in handles] == ["ok Event", "ok Stream"], p.stdout
     assert all(ln.endswith((" no-device", " created")) for ln in handles), p.stdout
+    more = p.stdout.split("\n")[5:7]          # pinned allocation flags; owners as std::vector elements (resize, move, destruction)
+    assert [ln.rsplit(" ", 1)[0] for ln in more] == ["ok PinnedBuf-flags", "ok vectors"], p.stdout
+    assert more[0].endswith((" no-device", " allocated")) and more[1].endswith((" no-device", " created")), p.stdout

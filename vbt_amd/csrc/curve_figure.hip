@@ -380,19 +380,19 @@ int vbt_curve_figure_create(int device, const vbt_curve_figure_params* params, v
   f->device = device; f->prm = p; f->G = cf_geom(p.width, p.height, p.scale, p.thickness);
   f->rec_cap = CF_FIXED_RECS + 1 + 2 * p.max_series + 3 * p.max_marks;
   const size_t F = (size_t)p.max_figures, P = (size_t)p.max_points;
-  Carver C;                                                          // the largest upload, at the blob's head
+  FigCarver C;                                                          // the largest upload, at the blob's head
   C.add<uint8_t>(align64(F * sizeof(CfFigure)) + align64(F * p.max_series * sizeof(CfSeries)) + align64(F * p.max_marks * sizeof(CfMark)) + F * P * 16);
   const auto lo = C.add<unsigned long long>(F * P), hi = C.add<unsigned long long>(F * P);
   const auto col = C.add<int32_t>(F * P), row = C.add<int32_t>(F * P), pts = C.add<int32_t>(F * P * CF_PT);
   const auto recs = C.add<int32_t>(F * (size_t)f->rec_cap * CF_REC), nrec = C.add<int32_t>(F), cnt = C.add<int32_t>(F * CF_MAX_SERIES);
-  if (hipMalloc((void**)&f->blob, C.bytes()) != hipSuccess) {
+  if (f->blob.alloc(C.bytes()) != hipSuccess) {
     (void)hipGetLastError();
     set_error("vbt_curve_figure_create: the device cannot give %zu bytes for %d figures of %d points, %d series and %d marks", C.bytes(), p.max_figures,
               p.max_points, p.max_series, p.max_marks);
     return VBT_ERR_HIP;
   }
-  f->d_lo = C.ptr(f->blob, lo); f->d_hi = C.ptr(f->blob, hi); f->d_col = C.ptr(f->blob, col); f->d_row = C.ptr(f->blob, row);
-  f->d_pts = C.ptr(f->blob, pts); f->d_recs = C.ptr(f->blob, recs); f->d_nrec = C.ptr(f->blob, nrec); f->d_cnt = C.ptr(f->blob, cnt);
+  f->d_lo = C.ptr(f->blob.get(), lo); f->d_hi = C.ptr(f->blob.get(), hi); f->d_col = C.ptr(f->blob.get(), col); f->d_row = C.ptr(f->blob.get(), row);
+  f->d_pts = C.ptr(f->blob.get(), pts); f->d_recs = C.ptr(f->blob.get(), recs); f->d_nrec = C.ptr(f->blob.get(), nrec); f->d_cnt = C.ptr(f->blob.get(), cnt);
   *out = f.release();
   return VBT_OK;
 }
@@ -445,11 +445,11 @@ int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc
   if (T.marks) memcpy(up.data() + figs_b + ser_b, marks, T.marks * sizeof(CfMark));
   if (T.points) memcpy(up.data() + figs_b + ser_b + mk_b, xy, T.points * 16);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(f->blob, up.data(), up.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(f->blob.get(), up.data(), up.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     CfPrepArgs A{};
-    A.figs = (const CfFigure*)f->blob; A.series = (const CfSeries*)(f->blob + figs_b); A.marks = (const CfMark*)(f->blob + figs_b + ser_b);
-    A.xy = (const double*)(f->blob + figs_b + ser_b + mk_b);
+    A.figs = (const CfFigure*)f->blob.get(); A.series = (const CfSeries*)(f->blob.get() + figs_b); A.marks = (const CfMark*)(f->blob.get() + figs_b + ser_b);
+    A.xy = (const double*)(f->blob.get() + figs_b + ser_b + mk_b);
     A.ws_col = f->d_col; A.ws_row = f->d_row; A.ws_lo = f->d_lo; A.ws_hi = f->d_hi;
     A.pts = f->d_pts; A.cnt = f->d_cnt; A.recs = f->d_recs; A.nrec = f->d_nrec;
     A.G = f->G; A.max_points = f->prm.max_points; A.rec_cap = f->rec_cap;
@@ -459,7 +459,7 @@ int vbt_curve_figure_set(vbt_curve_figure* f, int n, const vbt_curve_figure_desc
   if (int rc = f->finish_set(who, st, e)) return rc;                   // (`up` leaves scope: the copy must have read it)
   f->figs.assign(hf, hf + n);
   f->series.assign(hs, hs + T.series);
-  f->d_figs = (const CfFigure*)f->blob; f->d_series = (const CfSeries*)(f->blob + figs_b);
+  f->d_figs = (const CfFigure*)f->blob.get(); f->d_series = (const CfSeries*)(f->blob.get() + figs_b);
   f->n = n;
   return VBT_OK;
 }

@@ -18,12 +18,11 @@ class OwnedBuf {   // move-only
   }
   ~OwnedBuf() { reset(); }
   // room for `count` elements; what the buffer held before is freed first.  After a failure the buffer is empty.
-  hipError_t alloc(size_t count) {
-    reset();
-    void* p = nullptr;
-    const hipError_t e = PINNED ? hipHostMalloc(&p, sizeof(T) * count, hipHostMallocDefault) : hipMalloc(&p, sizeof(T) * count);
-    if (e == hipSuccess) p_ = (T*)p;
-    return e;
+  hipError_t alloc(size_t count) { return alloc_impl(count, hipHostMallocDefault); }
+  // pinned memory only: hipHostMalloc's flags (mapped, coherent, ...)
+  hipError_t alloc(size_t count, unsigned flags) {
+    static_assert(PINNED, "device memory takes no allocation flags");
+    return alloc_impl(count, flags);
   }
   void reset() {
     if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
@@ -33,6 +32,13 @@ class OwnedBuf {   // move-only
   explicit operator bool() const { return p_ != nullptr; }
 
  private:
+  hipError_t alloc_impl(size_t count, unsigned flags) {
+    reset();
+    void* p = nullptr;
+    const hipError_t e = PINNED ? hipHostMalloc(&p, sizeof(T) * count, flags) : hipMalloc(&p, sizeof(T) * count);
+    if (e == hipSuccess) p_ = (T*)p;
+    return e;
+  }
   T* p_ = nullptr;
 };
 template <class T> using DevBuf = OwnedBuf<T, false>;    // hipMalloc / hipFree

@@ -15,6 +15,7 @@
 // integers, so the curve points equal scikit-learn's bit for bit; AP / AUC differ from numpy's by the summation order only.
 #include "common.h"
 #include "dev_mem.h"
+#include "hip_handles.h"
 #include "lap.h"
 
 #include <algorithm>
@@ -363,18 +364,24 @@ struct CurveBufs {
 
 struct vbt_eval {
   int device = 0, max_batch = 0, rows_cap = 0;
+  // owners of the table's and the per-call scratch's arrays; tab and batch are what the kernels take
+  DevBuf<float> tab_score, batch_score;
+  DevBuf<double> tab_iou, batch_iou;
+  DevBuf<int> tab_image, tab_det, tab_gt, batch_det, batch_gt, batch_cnt;
   EvalTable tab{};
   EvalBatch batch{};
-  EvalState* state = nullptr;
+  DevBuf<EvalState> state;
   // staging of (meta, ground truth) uploads: EV_STAGES pinned slots + their device twins, an event each
-  int* h_stage[EV_STAGES] = {};
-  int* d_stage[EV_STAGES] = {};
-  hipEvent_t ev[EV_STAGES] = {};
-  bool ev_used[EV_STAGES] = {};
+  struct Stage {
+    PinnedBuf<int> host;
+    DevBuf<int> dev;
+    Event ev;
+    bool used = false;
+  } stage[EV_STAGES];
   size_t stage_ints = 0;
   int next_stage = 0;
   hipStream_t last_stream = nullptr;
-  hipEvent_t done = nullptr;        // end of the last call's kernels: a call on another stream waits for it (shared scratch and staging)
+  Event done;                       // end of the last call's kernels: a call on another stream waits for it (shared scratch and staging)
   bool done_used = false;
   int images_host = 0;
   CurveBufs work;
@@ -427,7 +434,7 @@ int curves_run(CurveWork& w, const float* d_scores, const double* d_ious, const 
 
 // the device row count after everything enqueued so far (synchronises the handle's stream)
 int read_state(vbt_eval* e, EvalState* out) {
-  VBT_HIP_CHECK(hipMemcpyAsync(out, e->state, sizeof(EvalState), hipMemcpyDeviceToHost, e->last_stream));
+  VBT_HIP_CHECK(hipMemcpyAsync(out, e->state.get(), sizeof(EvalState), hipMemcpyDeviceToHost, e->last_stream));
   VBT_HIP_CHECK(hipStreamSynchronize(e->last_stream));
   if (out->overflow) {
     set_error("vbt_eval: the table holds %d rows, %d were produced", e->rows_cap, out->n_rows);
@@ -444,33 +451,31 @@ int vbt_eval_create(int device, int max_batch, int rows_cap, vbt_eval** out) {
   if (!out || max_batch < 1 || max_batch > 4096 || rows_cap < 1) { set_error("vbt_eval_create: bad argument"); return VBT_ERR_ARG; }
   *out = nullptr;
   if (int rc = use_device("vbt_eval_create", device)) return rc;
-  vbt_eval* e = new vbt_eval();
+  std::unique_ptr<vbt_eval> e(new vbt_eval());
   e->device = device; e->max_batch = max_batch; e->rows_cap = rows_cap;
-  e->tab.cap = rows_cap;
   e->stage_ints = (size_t)max_batch * 4 + (size_t)max_batch * VBT_EVAL_MAX_GT * 4;
   hipError_t err = hipSuccess;
-  auto get = [&](void** p, size_t bytes) { if (err == hipSuccess) err = hipMalloc(p, bytes); };
+  auto get = [&](auto& buf, size_t count) { if (err == hipSuccess) err = buf.alloc(count); };
   const size_t r = (size_t)rows_cap, s = (size_t)max_batch * EV_MAXD;
-  get((void**)&e->tab.score, 4 * r); get((void**)&e->tab.iou, 8 * r); get((void**)&e->tab.image, 4 * r); get((void**)&e->tab.det, 4 * r);
-  get((void**)&e->tab.gt, 4 * r);
-  get((void**)&e->batch.score, 4 * s); get((void**)&e->batch.iou, 8 * s); get((void**)&e->batch.det, 4 * s); get((void**)&e->batch.gt, 4 * s);
-  get((void**)&e->batch.cnt, 4 * (size_t)max_batch);
-  get((void**)&e->state, sizeof(EvalState));
-  for (int k = 0; k < EV_STAGES; k++) {
-    get((void**)&e->d_stage[k], 4 * e->stage_ints);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&e->h_stage[k], 4 * e->stage_ints, hipHostMallocDefault);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev[k], hipEventDisableTiming);
+  get(e->tab_score, r); get(e->tab_iou, r); get(e->tab_image, r); get(e->tab_det, r); get(e->tab_gt, r);
+  get(e->batch_score, s); get(e->batch_iou, s); get(e->batch_det, s); get(e->batch_gt, s); get(e->batch_cnt, (size_t)max_batch);
+  get(e->state, 1);
+  for (vbt_eval::Stage& st : e->stage) {
+    get(st.dev, e->stage_ints);
+    get(st.host, e->stage_ints);
+    if (err == hipSuccess) err = st.ev.create(hipEventDisableTiming);
   }
-  if (err == hipSuccess) err = hipEventCreateWithFlags(&e->done, hipEventDisableTiming);
-  if (err == hipSuccess) err = hipMemset(e->state, 0, sizeof(EvalState));
+  if (err == hipSuccess) err = e->done.create(hipEventDisableTiming);
+  if (err == hipSuccess) err = hipMemset(e->state.get(), 0, sizeof(EvalState));
   if (err != hipSuccess) {
     set_error("vbt_eval_create: allocation failed: %s", hipGetErrorString(err));
-    vbt_eval_destroy(e);
     return VBT_ERR_HIP;
   }
-  if (int rc = work_alloc(e->work, rows_cap)) { vbt_eval_destroy(e); return rc; }
+  e->tab = EvalTable{e->tab_score.get(), e->tab_iou.get(), e->tab_image.get(), e->tab_det.get(), e->tab_gt.get(), rows_cap};
+  e->batch = EvalBatch{e->batch_score.get(), e->batch_iou.get(), e->batch_det.get(), e->batch_gt.get(), e->batch_cnt.get()};
+  if (int rc = work_alloc(e->work, rows_cap)) return rc;
   e->work_cap = rows_cap;
-  *out = e;
+  *out = e.release();
   return VBT_OK;
 }
 
@@ -478,15 +483,6 @@ void vbt_eval_destroy(vbt_eval* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
-  (void)hipFree(e->tab.score); (void)hipFree(e->tab.iou); (void)hipFree(e->tab.image); (void)hipFree(e->tab.det); (void)hipFree(e->tab.gt);
-  (void)hipFree(e->batch.score); (void)hipFree(e->batch.iou); (void)hipFree(e->batch.det); (void)hipFree(e->batch.gt); (void)hipFree(e->batch.cnt);
-  (void)hipFree(e->state);
-  for (int k = 0; k < EV_STAGES; k++) {
-    (void)hipFree(e->d_stage[k]);
-    if (e->h_stage[k]) (void)hipHostFree(e->h_stage[k]);
-    if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
-  }
-  if (e->done) (void)hipEventDestroy(e->done);
   delete e;
 }
 
@@ -494,7 +490,7 @@ int vbt_eval_reset(vbt_eval* e) {
   if (!e) { set_error("NULL vbt_eval"); return VBT_ERR_ARG; }
   VBT_HIP_CHECK(hipSetDevice(e->device));
   VBT_HIP_CHECK(hipDeviceSynchronize());
-  VBT_HIP_CHECK(hipMemset(e->state, 0, sizeof(EvalState)));
+  VBT_HIP_CHECK(hipMemset(e->state.get(), 0, sizeof(EvalState)));
   e->images_host = 0;
   return VBT_OK;
 }
@@ -524,10 +520,10 @@ int vbt_eval_add_detections(vbt_eval* e, const float* boxes_dev, const float* sc
   VBT_HIP_CHECK(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   // the per-batch scratch, the staging slots and the table are shared by all calls: a call on another stream runs after the last one
-  if (e->done_used && st != e->last_stream) VBT_HIP_CHECK(hipStreamWaitEvent(st, e->done, 0));
-  const int k = e->next_stage;
-  if (e->ev_used[k]) VBT_HIP_CHECK(hipEventSynchronize(e->ev[k]));   // the caller is EV_STAGES uploads ahead of the device
-  int* h = e->h_stage[k];
+  if (e->done_used && st != e->last_stream) VBT_HIP_CHECK(hipStreamWaitEvent(st, e->done.get(), 0));
+  vbt_eval::Stage& sg = e->stage[e->next_stage];
+  if (sg.used) VBT_HIP_CHECK(hipEventSynchronize(sg.ev.get()));   // the caller is EV_STAGES uploads ahead of the device
+  int* h = sg.host.get();
   for (int b = 0; b < B; b++) {
     h[4 * b + 0] = hw_host[2 * b];
     h[4 * b + 1] = hw_host[2 * b + 1];
@@ -535,15 +531,15 @@ int vbt_eval_add_detections(vbt_eval* e, const float* boxes_dev, const float* sc
     h[4 * b + 3] = gt_offsets_host[b + 1] - gt_offsets_host[b];
   }
   if (total > 0) memcpy(h + 4 * (size_t)B, gt_boxes_host + 4 * (size_t)g_first, sizeof(int) * 4 * (size_t)total);
-  VBT_HIP_CHECK(hipMemcpyAsync(e->d_stage[k], h, sizeof(int) * 4 * ((size_t)B + total), hipMemcpyHostToDevice, st));
-  VBT_HIP_CHECK(hipEventRecord(e->ev[k], st));
-  e->ev_used[k] = true;
-  e->next_stage = (k + 1) % EV_STAGES;
-  eval_match_kernel<<<B, 64, 0, st>>>(boxes_dev, scores_dev, counts_dev, e->d_stage[k], e->d_stage[k] + 4 * (size_t)B, e->batch);
+  VBT_HIP_CHECK(hipMemcpyAsync(sg.dev.get(), h, sizeof(int) * 4 * ((size_t)B + total), hipMemcpyHostToDevice, st));
+  VBT_HIP_CHECK(hipEventRecord(sg.ev.get(), st));
+  sg.used = true;
+  e->next_stage = (e->next_stage + 1) % EV_STAGES;
+  eval_match_kernel<<<B, 64, 0, st>>>(boxes_dev, scores_dev, counts_dev, sg.dev.get(), sg.dev.get() + 4 * (size_t)B, e->batch);
   VBT_HIP_CHECK(hipGetLastError());
-  eval_append_kernel<<<1, 64, 0, st>>>(e->batch, B, e->tab, e->state);
+  eval_append_kernel<<<1, 64, 0, st>>>(e->batch, B, e->tab, e->state.get());
   VBT_HIP_CHECK(hipGetLastError());
-  VBT_HIP_CHECK(hipEventRecord(e->done, st));
+  VBT_HIP_CHECK(hipEventRecord(e->done.get(), st));
   e->done_used = true;
   e->last_stream = st;
   e->images_host += B;
@@ -576,7 +572,7 @@ int vbt_eval_curves(vbt_eval* e, double iou_threshold, vbt_eval_summary* s, doub
   EvalState es;
   if (int rc = read_state(e, &es)) return rc;
   // the row count is read by the kernel from the device state: the table never leaves the device for this call
-  return curves_run(e->work.view, e->tab.score, e->tab.iou, &e->state->n_rows, 0, iou_threshold, e->last_stream, s, precision, recall,
+  return curves_run(e->work.view, e->tab.score, e->tab.iou, &e->state.get()->n_rows, 0, iou_threshold, e->last_stream, s, precision, recall,
                     pr_thresholds, pr_cap, fpr, tpr, roc_thresholds, roc_cap);
 }
 

@@ -247,20 +247,20 @@ int vbt_figure_create(int device, const vbt_figure_params* params, vbt_figure** 
   f->device = device; f->prm = p; f->G = fig_geom(p.width, p.height, p.scale, p.thickness);
   f->rec_cap = FIG_FIXED_RECS + 4 * p.max_phases;
   const size_t F = (size_t)p.max_figures, R = (size_t)p.max_rows;
-  Carver C;
+  FigCarver C;
   C.add<uint8_t>(align64(F * FIG_META * 4) + F * R * 7 * 8 + F * (size_t)p.max_phases * 6 * 8);      // the largest upload, at the blob's head
   const auto head = C.add<double>(F * FIG_HEAD);
   const auto pts = C.add<int32_t>(F * R * FIG_PT);
   const auto recs = C.add<int32_t>(F * (size_t)f->rec_cap * FIG_REC);
   const auto nrec = C.add<int32_t>(F);
   const auto smooth = C.add<double>(F * 4 * R);
-  if (hipMalloc((void**)&f->blob, C.bytes()) != hipSuccess) {
+  if (f->blob.alloc(C.bytes()) != hipSuccess) {
     (void)hipGetLastError();
     set_error("vbt_figure_create: the device cannot give %zu bytes for %d figures of %d rows and %d phases", C.bytes(), p.max_figures, p.max_rows, p.max_phases);
     return VBT_ERR_HIP;
   }
-  f->d_head = C.ptr(f->blob, head); f->d_pts = C.ptr(f->blob, pts); f->d_recs = C.ptr(f->blob, recs);
-  f->d_nrec = C.ptr(f->blob, nrec); f->d_smooth = C.ptr(f->blob, smooth);
+  f->d_head = C.ptr(f->blob.get(), head); f->d_pts = C.ptr(f->blob.get(), pts); f->d_recs = C.ptr(f->blob.get(), recs);
+  f->d_nrec = C.ptr(f->blob.get(), nrec); f->d_smooth = C.ptr(f->blob.get(), smooth);
   *out = f.release();
   return VBT_OK;
 }
@@ -292,10 +292,10 @@ int vbt_figure_set(vbt_figure* f, int n, const double* rows7_host, const int32_t
   if (rows_b) memcpy(up.data() + meta_b, rows7_host, rows_b);
   if (ph_b) memcpy(up.data() + meta_b + rows_b, phases6_host, ph_b);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(f->blob, up.data(), up.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(f->blob.get(), up.data(), up.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     FigPrepArgs A{};
-    A.meta = (const int32_t*)f->blob; A.rows = (const double*)(f->blob + meta_b); A.phases = (const double*)(f->blob + meta_b + rows_b);
+    A.meta = (const int32_t*)f->blob.get(); A.rows = (const double*)(f->blob.get() + meta_b); A.phases = (const double*)(f->blob.get() + meta_b + rows_b);
     A.smooth = f->d_smooth; A.head = f->d_head; A.pts = f->d_pts; A.recs = f->d_recs; A.nrec = f->d_nrec;
     A.G = f->G; A.max_rows = f->prm.max_rows; A.rec_cap = f->rec_cap;
     figure_prepare_kernel<<<dim3((unsigned)n), FIG_THREADS, 0, st>>>(A);
@@ -312,7 +312,7 @@ int vbt_figure_render(vbt_figure* f, uint8_t* frames_dev, int fig0, int n, void*
   if (n == 0) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(f->device));
   FigRenderArgs A{};
-  A.meta = (const int32_t*)f->blob; A.pts = f->d_pts; A.recs = f->d_recs; A.nrec = f->d_nrec;
+  A.meta = (const int32_t*)f->blob.get(); A.pts = f->d_pts; A.recs = f->d_recs; A.nrec = f->d_nrec;
   A.frames = frames_dev; A.frame_bytes = (size_t)f->G.W * f->G.H * 3;
   A.G = f->G; A.max_rows = f->prm.max_rows; A.rec_cap = f->rec_cap; A.fig0 = fig0;
   A.tiles_x = (f->G.W + RASTER_TILE_W - 1) / RASTER_TILE_W;

@@ -2,11 +2,14 @@
 // device allocation carved into regions, and the part of the handle the shared calls work on.  `who` is the entry point's name as the
 // error texts give it.
 #pragma once
+#include "carver.h"
 #include "common.h"
+#include "dev_mem.h"
 
 namespace vbt {
 
-inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+using FigCarver = Carver<64>;   // the regions of a figure's blob begin on 64-byte boundaries
+inline size_t align64(size_t v) { return FigCarver::align(v); }
 
 inline int check_canvas(const char* who, int width, int height, int scale, int thickness) {
   if (width < 1 || width > 16384 || height < 1 || height > 16384) { set_error("%s: figures of 1..16384 pixels a side, got %d x %d", who, width, height); return VBT_ERR_ARG; }
@@ -23,26 +26,10 @@ int check_plot_rect(const char* who, const Geom& G, int min_plot) {
   return VBT_ERR_ARG;
 }
 
-// One allocation as regions that each begin on a 64-byte boundary: name every region once with add<T>(count), allocate bytes(), and
-// ptr(blob, region) is where it lies
-class Carver {
-  size_t total = 0;
-
- public:
-  template <class T> struct Region { size_t at; };
-  template <class T> Region<T> add(size_t count) {
-    const Region<T> r{align64(total)};
-    total = r.at + count * sizeof(T);
-    return r;
-  }
-  size_t bytes() const { return total; }
-  template <class T> static T* ptr(uint8_t* blob, Region<T> r) { return (T*)(blob + r.at); }
-};
-
 // What the shared calls need of a handle.  blob is the one allocation, its head the upload of the last set.
 struct FigureHandle {
   int device = 0;
-  uint8_t* blob = nullptr;
+  DevBuf<uint8_t> blob;
   int rec_cap = 0;
   int n = 0;                           // figures set
   hipStream_t last = nullptr;          // the stream of the last set or render: table waits for it
@@ -57,7 +44,7 @@ struct FigureHandle {
     return VBT_OK;
   }
   ~FigureHandle() {
-    if (blob && hipSetDevice(device) == hipSuccess) (void)hipFree(blob);   // (waits for the launches still using it)
+    if (blob) (void)hipSetDevice(device);   // (the blob goes after this: its free waits for the launches still using it)
   }
 };
 

@@ -15,7 +15,9 @@
 // Scratch is sized for the worst case (vbt_hip.h); every store is still checked against its buffer and a miss raises `flag`.
 #include <algorithm>
 
+#include "carver.h"
 #include "common.h"
+#include "dev_mem.h"
 #include "jpeg_parse.h"
 
 namespace vbt {
@@ -378,7 +380,7 @@ using namespace vbt;
 struct vbt_mjpeg {
   int device = 0, H = 0, W = 0, fmt = 0, quality = 0, max_batch = 0, MW = 0, MH = 0;
   size_t frame_bytes = 0, slot_bytes = 0, out_bytes = 0;
-  uint8_t* blob = nullptr;               // tables | offsets + flag | fsize | ioff | sizes | levels | slots | out in one allocation
+  DevBuf<uint8_t> blob;                  // tables | offsets + flag | fsize | ioff | sizes | levels | slots | out in one allocation
   MjArgs args{};
   int pending = 0;                       // frames of the batch that is encoded and not yet read
 };
@@ -456,8 +458,6 @@ bool dct_table_ok() {
   return true;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {
@@ -474,40 +474,42 @@ int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max
   build_tables(H, W, quality, &tab);
   if (!dct_table_ok() || tab.header[0] != 0xFF) { set_error("vbt_mjpeg_create: the built-in tables fail their self-check"); return VBT_ERR_STATE; }
   if (int rc = use_device("vbt_mjpeg_create", device)) return rc;
-  vbt_mjpeg* m = new vbt_mjpeg();
+  std::unique_ptr<vbt_mjpeg> m(new vbt_mjpeg());
   m->device = device; m->H = H; m->W = W; m->fmt = pix_fmt; m->quality = quality; m->max_batch = max_batch;
   m->MW = (W + 15) / 16; m->MH = (H + 15) / 16;
   m->frame_bytes = pix_fmt == VBT_PIX_RGB24 ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2;
   m->slot_bytes = (size_t)MJ_SLOT_PER_MCU * m->MW;
   const size_t B = (size_t)max_batch, units = B * m->MH;
   m->out_bytes = B * (MJ_HEADER + (size_t)m->MH * (m->slot_bytes + 2));
-  const size_t o_tab = 0, o_offsets = align256(sizeof(MjTables)), o_fsize = o_offsets + align256((B + 2) * 8), o_ioff = o_fsize + align256(B * 8),
-               o_sizes = o_ioff + align256(units * 8), o_levels = o_sizes + align256(units * 4),
-               o_slots = o_levels + align256(units * 6 * m->MW * 128), o_out = o_slots + align256(units * m->slot_bytes),
-               total = o_out + align256(m->out_bytes);
-  hipError_t e = hipMalloc((void**)&m->blob, total);
-  if (e == hipSuccess) e = hipMemcpy(m->blob + o_tab, &tab, sizeof(tab), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(m->blob + o_offsets, 0, (B + 2) * 8);
+  Carver<256> C;   // tables | offsets + flag | fsize | ioff | sizes | levels | slots | out
+  const auto r_tab = C.add<MjTables>(1);
+  const auto r_offsets = C.add<uint64_t>(B + 2), r_fsize = C.add<uint64_t>(B), r_ioff = C.add<uint64_t>(units);
+  const auto r_sizes = C.add<uint32_t>(units);
+  const auto r_levels = C.add<int16_t>(units * 6 * m->MW * 64);
+  const auto r_slots = C.add<uint8_t>(units * m->slot_bytes), r_out = C.add<uint8_t>(m->out_bytes);
+  const size_t total = C.padded_bytes();
+  hipError_t e = m->blob.alloc(total);
+  uint8_t* const blob = m->blob.get();
+  if (e == hipSuccess) e = hipMemcpy(C.ptr(blob, r_tab), &tab, sizeof(tab), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(C.ptr(blob, r_offsets), 0, (B + 2) * 8);
   if (e != hipSuccess) {
     set_error("vbt_mjpeg_create: %zu bytes of device memory for %d frames of %d x %d: %s", total, max_batch, W, H, hipGetErrorString(e));
-    if (m->blob) (void)hipFree(m->blob);
-    delete m;
     return VBT_ERR_HIP;
   }
   MjArgs& A = m->args;
   A.frame_bytes = m->frame_bytes; A.H = H; A.W = W; A.fmt = pix_fmt; A.MW = m->MW; A.MH = m->MH;
-  A.tab = (const MjTables*)(m->blob + o_tab);
-  A.offsets = (uint64_t*)(m->blob + o_offsets); A.flag = A.offsets + B + 1; A.fsize = (uint64_t*)(m->blob + o_fsize); A.ioff = (uint64_t*)(m->blob + o_ioff);
-  A.sizes = (uint32_t*)(m->blob + o_sizes); A.levels = (int16_t*)(m->blob + o_levels);
-  A.slots = m->blob + o_slots; A.slot_bytes = m->slot_bytes; A.out = m->blob + o_out; A.out_bytes = m->out_bytes;
-  *out = m;
+  A.tab = C.ptr(blob, r_tab);
+  A.offsets = C.ptr(blob, r_offsets); A.flag = A.offsets + B + 1; A.fsize = C.ptr(blob, r_fsize); A.ioff = C.ptr(blob, r_ioff);
+  A.sizes = C.ptr(blob, r_sizes); A.levels = C.ptr(blob, r_levels);
+  A.slots = C.ptr(blob, r_slots); A.slot_bytes = m->slot_bytes; A.out = C.ptr(blob, r_out); A.out_bytes = m->out_bytes;
+  *out = m.release();
   return VBT_OK;
 }
 
 void vbt_mjpeg_destroy(vbt_mjpeg* m) {
   if (!m) return;
-  if (m->blob && hipSetDevice(m->device) == hipSuccess) (void)hipFree(m->blob);   // (waits for the kernels still using it)
-  delete m;
+  if (m->blob) (void)hipSetDevice(m->device);
+  delete m;   // (the blob's free waits for the kernels still using it)
 }
 
 int vbt_mjpeg_encode(vbt_mjpeg* m, const uint8_t* frames_dev, int B, void* stream) {

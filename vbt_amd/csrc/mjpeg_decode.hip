@@ -23,7 +23,10 @@
 //     bilinear resize through jpeg_pixel, lerped in float32 (jpeg_core.h: jpeg_resized_pixel) - no frame at source size is written.
 #include <algorithm>
 
+#include "carver.h"
 #include "common.h"
+#include "dev_mem.h"
+#include "hip_handles.h"
 #include "jpeg_parse.h"
 
 namespace vbt {
@@ -371,15 +374,15 @@ struct MjdHandle {
   int device = 0, max_batch = 0;
   size_t blocks_cap = 0, rst_words = 0;  // the scratch: blocks of levels and planes, words of restart table
   uint64_t last_upload = 0;              // bytes of the last batch's H2D copy
-  uint8_t* blob = nullptr;               // status | rst_count | rst | levels | planes in one allocation
-  uint8_t* packed = nullptr;             // the batch's descriptors and scans on the device; grows on demand up to MJD_MAX_PACKED
-  size_t packed_cap = 0;
-  uint8_t* stage[2] = {nullptr, nullptr};   // pinned staging, used in turn
+  DevBuf<uint8_t> blob;                  // status | rst_count | rst | levels | planes | info in one allocation
+  DevBuf<uint8_t> packed;                // the batch's descriptors and scans on the device; grows on demand up to MJD_MAX_PACKED
+  size_t packed_cap = 0;                 // (0 whenever packed is empty; stage_cap likewise)
+  PinnedBuf<uint8_t> stage[2];           // pinned staging, used in turn
   size_t stage_cap[2] = {0, 0};
-  hipEvent_t copied[2] = {nullptr, nullptr};   // recorded behind the H2D copy out of stage[i]: the host waits for it before it refills stage[i]
+  Event copied[2];                       // recorded behind the H2D copy out of stage[i]: the host waits for it before it refills stage[i]
   bool in_flight[2] = {false, false};
   int next = 0, last_B = 0;
-  hipEvent_t stamp[7] = {};              // VBT_MJPEG_DECODE_STAMPS=1: around each stage of a decode (vbt_mjpeg_decode_stage_ms)
+  Event stamp[7];                        // VBT_MJPEG_DECODE_STAMPS=1: around each stage of a decode (vbt_mjpeg_decode_stage_ms)
   bool stamps = false;
   int entropy = VBT_MJPEG_ENTROPY_AUTO, subseq = 0;   // vbt_mjpeg_decoder_set_entropy
   int last_path = 0, last_subseq = 0;    // of the last batch
@@ -387,6 +390,9 @@ struct MjdHandle {
   std::vector<JpegDesc> descs;
   std::vector<MjdFrame> geom;
   MjdArgs args{};
+  ~MjdHandle() {
+    if (blob) (void)hipSetDevice(device);   // (the members go after this: the blob's free waits for the kernels still using it)
+  }
 };
 
 // one frame size: every frame of a batch gets the same share of the scratch
@@ -396,10 +402,9 @@ struct vbt_mjpeg_decoder : MjdHandle {
 };
 
 // every frame its own size: the frames of a batch share a budget of blocks.  Nothing is allocated before the first batch, so that
-// every refusal of an argument, a header or a batch over the budget is made without a device
+// every refusal of an argument, a header or a batch over the budget is made without a device; blob tells whether it has been
 struct vbt_jpeg_stills : MjdHandle {
   size_t block_budget = 0;
-  bool allocated = false;
 };
 
 namespace {
@@ -407,45 +412,44 @@ namespace {
 constexpr size_t STILLS_MAX_BUDGET = (size_t)1 << 24;              // blocks: one 16384 x 16384 frame at 4:4:4 takes 3 x 2^22
 constexpr int STILLS_MAX_TARGET = 4096;                            // h, w of decode_resized
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+size_t align256(size_t v) { return Carver<256>::align(v); }
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int sampling_code(const JpegDesc& d) { return (d.hs << 4) | d.vs; }
 
 // the scratch for `blocks` blocks and `rst_words` restart positions, the device buffer of the compressed bytes (packed_init bytes to
-// begin with), the events.  The caller has selected the device; on an error it destroys the handle
+// begin with), the events.  The caller has selected the device; after an error the handle holds none of them
 hipError_t mjd_alloc(MjdHandle* m, size_t blocks, size_t rst_words, size_t packed_init, size_t* bytes) {
   const size_t B = (size_t)m->max_batch;
-  const size_t o_status = 0, o_count = align256(B * 4), o_rst = o_count + align256(B * 4), o_levels = o_rst + align256(rst_words * 4),
-               o_planes = o_levels + align256(blocks * 128), o_info = o_planes + align256(blocks * 64), total = o_info + 256;
+  Carver<256> C;
+  const auto status = C.add<int32_t>(B);
+  const auto count = C.add<uint32_t>(B), rst = C.add<uint32_t>(rst_words);
+  const auto levels = C.add<int16_t>(blocks * 64);
+  const auto planes = C.add<uint8_t>(blocks * 64);
+  const auto info = C.add<int32_t>(64);
   m->blocks_cap = blocks; m->rst_words = rst_words;
-  m->packed_cap = std::min(MJD_MAX_PACKED, align256(packed_init));
-  *bytes = total + m->packed_cap;
-  hipError_t e = hipMalloc((void**)&m->blob, total);
-  if (e == hipSuccess) e = hipMalloc((void**)&m->packed, m->packed_cap);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&m->copied[i], hipEventDisableTiming);
+  const size_t packed_cap = std::min(MJD_MAX_PACKED, align256(packed_init));
+  *bytes = C.bytes() + packed_cap;
+  hipError_t e = m->blob.alloc(C.bytes());
+  if (e == hipSuccess) e = m->packed.alloc(packed_cap);
+  for (int i = 0; i < 2 && e == hipSuccess; i++) e = m->copied[i].create(hipEventDisableTiming);
   const char* env = getenv("VBT_MJPEG_DECODE_STAMPS");
-  if (e == hipSuccess && env && env[0] == '1') {
-    for (int i = 0; i < 7 && e == hipSuccess; i++) e = hipEventCreate(&m->stamp[i]);
-    m->stamps = e == hipSuccess;
+  const bool stamps = env && env[0] == '1';
+  for (int i = 0; i < 7 && stamps && e == hipSuccess; i++) e = m->stamp[i].create(hipEventDefault);
+  if (e != hipSuccess) {
+    m->blob.reset(); m->packed.reset();
+    for (Event& ev : m->copied) ev.reset();
+    for (Event& ev : m->stamp) ev.reset();
+    return e;
   }
+  m->packed_cap = packed_cap;
+  m->stamps = stamps;
+  uint8_t* const blob = m->blob.get();
   MjdArgs& A = m->args;
-  A.status = (int32_t*)(m->blob + o_status); A.rst_count = (uint32_t*)(m->blob + o_count); A.rst = (uint32_t*)(m->blob + o_rst);
-  A.levels = (int16_t*)(m->blob + o_levels); A.planes = m->blob + o_planes;
-  m->info = (int32_t*)(m->blob + o_info);
+  A.status = C.ptr(blob, status); A.rst_count = C.ptr(blob, count); A.rst = C.ptr(blob, rst);
+  A.levels = C.ptr(blob, levels); A.planes = C.ptr(blob, planes);
+  m->info = C.ptr(blob, info);
   return e;
-}
-
-void mjd_free(MjdHandle* m) {
-  if (hipSetDevice(m->device) != hipSuccess) return;
-  if (m->blob) (void)hipFree(m->blob);                            // (waits for the kernels still using it)
-  if (m->packed) (void)hipFree(m->packed);
-  for (int i = 0; i < 2; i++) {
-    if (m->stage[i]) (void)hipHostFree(m->stage[i]);
-    if (m->copied[i]) (void)hipEventDestroy(m->copied[i]);
-  }
-  for (int i = 0; i < 7; i++)
-    if (m->stamp[i]) (void)hipEventDestroy(m->stamp[i]);
 }
 
 // what the parse loop of a batch collects
@@ -501,27 +505,23 @@ int mjd_enqueue(MjdHandle* m, const char* who, const MjdBatch& b, const uint8_t*
   hipStream_t st = (hipStream_t)stream;
   const int s = m->next;
   if (m->in_flight[s]) {                                          // host-side gate: the copy that last read this staging buffer is done
-    VBT_HIP_CHECK(hipEventSynchronize(m->copied[s]));
+    VBT_HIP_CHECK(hipEventSynchronize(m->copied[s].get()));
     m->in_flight[s] = false;
   }
   if (total > m->stage_cap[s]) {
-    if (m->stage[s]) (void)hipHostFree(m->stage[s]);
-    m->stage[s] = nullptr;
-    m->stage_cap[s] = 0;
     const size_t cap = std::min(MJD_MAX_PACKED, align256(total + total / 4));
-    VBT_HIP_CHECK(hipHostMalloc((void**)&m->stage[s], cap, hipHostMallocDefault));
+    m->stage_cap[s] = 0;
+    VBT_HIP_CHECK(m->stage[s].alloc(cap));
     m->stage_cap[s] = cap;
   }
   if (total > m->packed_cap) {                                    // growth frees the old buffer, which waits for the work that reads it
     const size_t cap = std::min(MJD_MAX_PACKED, align256(total + total / 4));
-    (void)hipFree(m->packed);
-    m->packed = nullptr;
     m->packed_cap = 0;
-    hipError_t e = hipMalloc((void**)&m->packed, cap);
+    const hipError_t e = m->packed.alloc(cap);
     if (e != hipSuccess) { set_error("%s: %zu bytes of device memory for the compressed frames: %s", who, cap, hipGetErrorString(e)); return VBT_ERR_HIP; }
     m->packed_cap = cap;
   }
-  uint8_t* pk = m->stage[s];
+  uint8_t* pk = m->stage[s].get();
   size_t at = mjd_head_bytes(B, table);
   for (int i = 0; i < B; i++) {
     JpegDesc& d = m->descs[(size_t)i];
@@ -531,16 +531,16 @@ int mjd_enqueue(MjdHandle* m, const char* who, const MjdBatch& b, const uint8_t*
   }
   memcpy(pk, m->descs.data(), (size_t)B * sizeof(JpegDesc));
   if (table) memcpy(pk + (size_t)B * sizeof(JpegDesc), m->geom.data(), (size_t)B * sizeof(MjdFrame));
-  auto stamp = [&](int i) { return m->stamps ? hipEventRecord(m->stamp[i], st) : hipSuccess; };
+  auto stamp = [&](int i) { return m->stamps ? hipEventRecord(m->stamp[i].get(), st) : hipSuccess; };
   VBT_HIP_CHECK(stamp(0));
-  VBT_HIP_CHECK(hipMemcpyAsync(m->packed, pk, total, hipMemcpyHostToDevice, st));
-  VBT_HIP_CHECK(hipEventRecord(m->copied[s], st));
+  VBT_HIP_CHECK(hipMemcpyAsync(m->packed.get(), pk, total, hipMemcpyHostToDevice, st));
+  VBT_HIP_CHECK(hipEventRecord(m->copied[s].get(), st));
   VBT_HIP_CHECK(stamp(1));
   m->in_flight[s] = true;
   m->next = s ^ 1;
   m->last_upload = total;
   MjdArgs A = A0;
-  A.packed = m->packed; A.B = B;
+  A.packed = m->packed.get(); A.B = B;
   VBT_HIP_CHECK(hipMemsetAsync(A.status, 0, (size_t)B * 4, st));
   VBT_HIP_CHECK(hipMemsetAsync(A.levels, 0, b.blocks * 128, st));
   if (b.sync) VBT_HIP_CHECK(hipMemsetAsync(m->info, 0, 8, st));
@@ -597,8 +597,8 @@ int mjd_stage_ms(MjdHandle* m, const char* who, float* ms6) {
   if (!m || !ms6) { set_error("%s: bad argument", who); return VBT_ERR_ARG; }
   if (!m->stamps || !m->last_B) { set_error("%s: needs VBT_MJPEG_DECODE_STAMPS=1 at create and a decoded batch", who); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(m->device));
-  VBT_HIP_CHECK(hipEventSynchronize(m->stamp[6]));
-  for (int i = 0; i < 6; i++) VBT_HIP_CHECK(hipEventElapsedTime(&ms6[i], m->stamp[i], m->stamp[i + 1]));
+  VBT_HIP_CHECK(hipEventSynchronize(m->stamp[6].get()));
+  for (int i = 0; i < 6; i++) VBT_HIP_CHECK(hipEventElapsedTime(&ms6[i], m->stamp[i].get(), m->stamp[i + 1].get()));
   return VBT_OK;
 }
 
@@ -634,27 +634,22 @@ int vbt_mjpeg_decoder_create(int device, int H, int W, int max_batch, vbt_mjpeg_
   if (H < 1 || W < 1 || H > JPEG_MAX_SIDE || W > JPEG_MAX_SIDE) { set_error("vbt_mjpeg_decoder_create: frames of 1..16384 pixels a side, got %d x %d", H, W); return VBT_ERR_ARG; }
   if (max_batch < 1 || max_batch > MJD_MAX_BATCH) { set_error("vbt_mjpeg_decoder_create: max_batch %d outside 1..%d", max_batch, MJD_MAX_BATCH); return VBT_ERR_ARG; }
   if (int rc = use_device("vbt_mjpeg_decoder_create", device)) return rc;
-  vbt_mjpeg_decoder* m = new vbt_mjpeg_decoder();
+  std::unique_ptr<vbt_mjpeg_decoder> m(new vbt_mjpeg_decoder());
   m->device = device; m->H = H; m->W = W; m->max_batch = max_batch;
   m->frame_blocks = (size_t)jpeg_max_blocks(H, W);
   m->rst_cap = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);
   const size_t B = (size_t)max_batch;
   size_t bytes = 0;
-  const hipError_t e = mjd_alloc(m, B * m->frame_blocks, B * m->rst_cap, B * sizeof(JpegDesc) + B * (4096 + (size_t)H * W / 4), &bytes);
+  const hipError_t e = mjd_alloc(m.get(), B * m->frame_blocks, B * m->rst_cap, B * sizeof(JpegDesc) + B * (4096 + (size_t)H * W / 4), &bytes);
   if (e != hipSuccess) {
     set_error("vbt_mjpeg_decoder_create: %zu bytes of device memory for %d frames of %d x %d: %s", bytes, max_batch, W, H, hipGetErrorString(e));
-    vbt_mjpeg_decoder_destroy(m);
     return VBT_ERR_HIP;
   }
-  *out = m;
+  *out = m.release();
   return VBT_OK;
 }
 
-void vbt_mjpeg_decoder_destroy(vbt_mjpeg_decoder* m) {
-  if (!m) return;
-  mjd_free(m);
-  delete m;
-}
+void vbt_mjpeg_decoder_destroy(vbt_mjpeg_decoder* m) { delete m; }
 
 int vbt_mjpeg_decode(vbt_mjpeg_decoder* m, const uint8_t* host_bytes, const uint64_t* offsets, int B, uint8_t* frames_dev_out, void* stream) {
   if (!m || !host_bytes || !offsets || !frames_dev_out || B < 1) { set_error("vbt_mjpeg_decode: bad argument (handle, bytes, offsets, frames, B >= 1)"); return VBT_ERR_ARG; }
@@ -714,11 +709,7 @@ int vbt_jpeg_stills_create(int device, int max_batch, uint64_t block_budget, vbt
   return VBT_OK;
 }
 
-void vbt_jpeg_stills_destroy(vbt_jpeg_stills* m) {
-  if (!m) return;
-  if (m->allocated) mjd_free(m);
-  delete m;
-}
+void vbt_jpeg_stills_destroy(vbt_jpeg_stills* m) { delete m; }
 
 }  // extern "C"
 
@@ -766,18 +757,12 @@ int stills_run(vbt_jpeg_stills* m, const char* who, const uint8_t* host_bytes, c
     return VBT_ERR_CAPACITY;
   }
   b.blocks = blocks;
-  if (!m->allocated) {
+  if (!m->blob) {
     if (int rc = use_device(who, m->device)) return rc;
     size_t bytes = 0;
     const hipError_t e = mjd_alloc(m, m->block_budget, m->block_budget, (size_t)m->max_batch * (sizeof(JpegDesc) + sizeof(MjdFrame) + 4096) + 16 * m->block_budget, &bytes);
-    m->allocated = true;                                            // (also after a failure: destroy frees what was made)
-    if (e != hipSuccess) {
+    if (e != hipSuccess) {                                          // (the handle holds nothing: the next batch tries again)
       set_error("%s: %zu bytes of device memory for a budget of %zu blocks and %d frames: %s", who, bytes, m->block_budget, m->max_batch, hipGetErrorString(e));
-      mjd_free(m);
-      m->blob = m->packed = nullptr;
-      m->copied[0] = m->copied[1] = nullptr;
-      for (hipEvent_t& ev : m->stamp) ev = nullptr;
-      m->stamps = false; m->allocated = false;
       return VBT_ERR_HIP;
     }
   }

@@ -19,7 +19,10 @@
 // panel (overlay_core.h).
 #include <algorithm>
 
+#include "carver.h"
 #include "common.h"
+#include "dev_mem.h"
+#include "hip_handles.h"
 #include "overlay_core.h"
 #include "tracker_host.h"
 
@@ -320,7 +323,7 @@ struct vbt_overlay {
   size_t frame_bytes = 0;
   int chunks = 2;                        // workgroups per row: box, marker + label, ceil((trail - 1) / 16) of trail segments
   int n = 0, fmax = 0;
-  uint8_t* blob = nullptr;               // rows | frow | fstart | geom in one allocation
+  DevBuf<uint8_t> blob;                  // rows | frow | fstart | geom in one allocation
   const OverlayRow* d_rows = nullptr;
   const int32_t *d_frow = nullptr, *d_fstart = nullptr;
   int32_t* d_geom = nullptr;
@@ -328,18 +331,19 @@ struct vbt_overlay {
   bool follow = false;                   // follow mode (vbt_overlay_follow): the rows are F.rows, everything else of F in follow_blob
   OvFollow F{};
   const int32_t* nrows_dev = nullptr;
-  uint8_t* follow_blob = nullptr;        // geom | link | table | findex | state in one allocation
+  DevBuf<uint8_t> follow_blob;           // geom | link | table | findex | state in one allocation
   bool hud = false;                      // a rep panel is set (vbt_overlay_set_hud)
   vbt_overlay_hud_params hud_prm{};
   uint8_t b0 = 0, b1 = 0, b2 = 0;        // the panel's background in the frames' format
   int hud_P = 0;
-  int32_t* d_hud = nullptr;              // [hud_P][OV_HUD_REC], an allocation of its own (hud_follow: HF.tab, inside hud_follow_blob)
+  DevBuf<int32_t> hud_tab;               // the table of vbt_overlay_set_hud
+  const int32_t* d_hud = nullptr;        // [hud_P][OV_HUD_REC], what a draw reads: hud_tab, or (hud_follow) HF.tab inside hud_follow_blob
   bool hud_follow = false;               // the panel follows the live analysis (vbt_overlay_hud_follow): hud is set too
   OvHudFollow HF{};
   vbt_tracker* hud_trk = nullptr;        // the followed tracker (borrowed)
-  uint8_t* hud_follow_blob = nullptr;    // table | state | view in one allocation
+  DevBuf<uint8_t> hud_follow_blob;       // table | state | view in one allocation
   int hud_flush = 0;                     // flush_view of the updates vbt_pipeline_overlay_draw makes
-  hipEvent_t ev_hud_drawn = nullptr;     // behind the last draw vbt_pipeline_overlay_draw enqueued: its next update waits for it
+  Event ev_hud_drawn;                    // behind the last draw vbt_pipeline_overlay_draw enqueued: its next update waits for it
   bool hud_drawn = false;
 };
 
@@ -452,23 +456,18 @@ void overlay_launch_rows(vbt_overlay* o, uint8_t* frames_dev, int B, int frame0,
 }
 
 void overlay_free_hud(vbt_overlay* o) {
-  if (o->hud_follow) {                     // the table is part of the follow allocation
-    if (o->hud_follow_blob) (void)hipFree(o->hud_follow_blob);   // (waits for the updates and draws still using it)
-    if (o->ev_hud_drawn) (void)hipEventDestroy(o->ev_hud_drawn);
-    o->hud_follow_blob = nullptr; o->ev_hud_drawn = nullptr; o->hud_drawn = false;
-    o->hud_follow = false; o->HF = OvHudFollow{}; o->hud_trk = nullptr; o->hud_flush = 0;
-    o->d_hud = nullptr;
-  }
-  if (o->d_hud) (void)hipFree(o->d_hud);   // (waits for the draws still reading it)
+  o->hud_tab.reset(); o->hud_follow_blob.reset();   // (each waits for the updates and draws still using it)
+  o->ev_hud_drawn.reset(); o->hud_drawn = false;
+  o->hud_follow = false; o->HF = OvHudFollow{}; o->hud_trk = nullptr; o->hud_flush = 0;
   o->d_hud = nullptr; o->hud_P = 0; o->hud = false;
 }
 
 void overlay_free_rows(vbt_overlay* o) {
-  if (o->blob) (void)hipFree(o->blob);   // (waits for the draws still reading it)
-  o->blob = nullptr; o->d_rows = nullptr; o->d_frow = o->d_fstart = nullptr; o->d_geom = nullptr;
+  o->blob.reset();   // (waits for the draws still reading it)
+  o->d_rows = nullptr; o->d_frow = o->d_fstart = nullptr; o->d_geom = nullptr;
   o->n = 0; o->fmax = 0; o->fstart.clear();
-  if (o->follow_blob) (void)hipFree(o->follow_blob);
-  o->follow_blob = nullptr; o->follow = false; o->F = OvFollow{}; o->nrows_dev = nullptr;
+  o->follow_blob.reset();
+  o->follow = false; o->F = OvFollow{}; o->nrows_dev = nullptr;
 }
 
 }  // namespace
@@ -510,7 +509,7 @@ int vbt_overlay_create(int device, int H, int W, int pix_fmt, const vbt_overlay_
 
 void vbt_overlay_destroy(vbt_overlay* o) {
   if (!o) return;
-  if (hipSetDevice(o->device) == hipSuccess) { overlay_free_rows(o); overlay_free_hud(o); }
+  (void)hipSetDevice(o->device);
   delete o;
 }
 
@@ -544,13 +543,14 @@ int vbt_overlay_set_rows(vbt_overlay* o, const void* rows_host, int n, double fp
   memcpy(up.data(), rows, rows_b);
   memcpy(up.data() + rows_b, frow.data(), frow_b);
   memcpy(up.data() + rows_b + frow_b, fstart.data(), fstart_b);
-  VBT_HIP_CHECK(hipMalloc((void**)&o->blob, up_b + geom_b));
-  o->d_rows = (const OverlayRow*)o->blob;
-  o->d_frow = (const int32_t*)(o->blob + rows_b);
-  o->d_fstart = (const int32_t*)(o->blob + rows_b + frow_b);
-  o->d_geom = (int32_t*)(o->blob + up_b);
+  VBT_HIP_CHECK(o->blob.alloc(up_b + geom_b));
+  uint8_t* const blob = o->blob.get();
+  o->d_rows = (const OverlayRow*)blob;
+  o->d_frow = (const int32_t*)(blob + rows_b);
+  o->d_fstart = (const int32_t*)(blob + rows_b + frow_b);
+  o->d_geom = (int32_t*)(blob + up_b);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(o->blob, up.data(), up_b, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(blob, up.data(), up_b, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     overlay_prepare_kernel<<<dim3((unsigned)((n + OV_THREADS - 1) / OV_THREADS)), OV_THREADS, 0, st>>>(o->d_rows, n, fps, o->H, o->W, o->prm.trail, o->d_geom);
     e = hipGetLastError();
@@ -606,27 +606,28 @@ int vbt_overlay_follow(vbt_overlay* o, const void* rows_dev, const int32_t* nrow
   overlay_free_rows(o);
   size_t slots = 64;
   while (slots < 2 * (size_t)rows_cap) slots <<= 1;
-  const size_t geom_b = (size_t)rows_cap * OV_GEOM * 4, link_b = (size_t)rows_cap * OV_LINK * 4, table_b = slots * sizeof(OvIdSlot);
-  const size_t findex_b = ((size_t)max_frame + 1) * 8, state_b = OV_STATE * 4;
-  uint8_t* blob = nullptr;
-  VBT_HIP_CHECK(hipMalloc((void**)&blob, geom_b + link_b + table_b + findex_b + state_b));
-  uint8_t* table = blob + geom_b + link_b;
-  hipError_t e = hipMemsetAsync(blob, 0xff, geom_b + link_b + table_b, nullptr);   // every slot free (id -1), every link "none"
-  if (e == hipSuccess) e = hipMemsetAsync(table + table_b, 0, findex_b + state_b, nullptr);
+  Carver<8> C;   // geom | link | table | findex | state: every region's size is a multiple of 8, they lie back to back
+  const auto geom = C.add<int32_t>((size_t)rows_cap * OV_GEOM), link = C.add<int32_t>((size_t)rows_cap * OV_LINK);
+  const auto table = C.add<OvIdSlot>(slots);
+  const auto findex = C.add<int32_t>(((size_t)max_frame + 1) * 2), state = C.add<int32_t>(OV_STATE);
+  DevBuf<uint8_t> owner;
+  VBT_HIP_CHECK(owner.alloc(C.bytes()));
+  uint8_t* const blob = owner.get();
+  hipError_t e = hipMemsetAsync(blob, 0xff, findex.at, nullptr);   // every slot free (id -1), every link "none"
+  if (e == hipSuccess) e = hipMemsetAsync(blob + findex.at, 0, C.bytes() - findex.at, nullptr);
   const hipError_t es = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) {
-    (void)hipFree(blob);
     set_error("vbt_overlay_follow failed: %s", hipGetErrorString(e));
     return VBT_ERR_HIP;
   }
   OvFollow& F = o->F;
   F.rows = (const OverlayRow*)rows_dev;
-  F.geom = (int32_t*)blob; F.link = (int32_t*)(blob + geom_b); F.table = (OvIdSlot*)table;
-  F.findex = (int32_t*)(table + table_b); F.state = (int32_t*)(table + table_b + findex_b);
+  F.geom = C.ptr(blob, geom); F.link = C.ptr(blob, link); F.table = C.ptr(blob, table);
+  F.findex = C.ptr(blob, findex); F.state = C.ptr(blob, state);
   F.fps = fps; F.rows_cap = rows_cap; F.max_frame = max_frame; F.max_rows_per_frame = max_rows_per_frame; F.table_mask = (int)(slots - 1);
   F.H = o->H; F.W = o->W; F.trail = o->prm.trail;
-  o->follow_blob = blob; o->nrows_dev = nrows_dev; o->follow = true; o->fmax = max_frame;
+  o->follow_blob = std::move(owner); o->nrows_dev = nrows_dev; o->follow = true; o->fmax = max_frame;
   return VBT_OK;
 }
 
@@ -669,20 +670,20 @@ int vbt_overlay_set_hud(vbt_overlay* o, const vbt_overlay_hud_params* params, co
   if (!o) { set_error("vbt_overlay_set_hud: handle is NULL"); return VBT_ERR_ARG; }
   if (int rc = check_hud_geometry("vbt_overlay_set_hud", o, params)) return rc;
   VBT_HIP_CHECK(hipSetDevice(o->device));
-  int32_t* d = nullptr;
+  DevBuf<int32_t> d;
   if (P > 0) {
-    VBT_HIP_CHECK(hipMalloc((void**)&d, tab.size() * 4));
-    hipError_t e = hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    VBT_HIP_CHECK(d.alloc(tab.size()));
+    hipError_t e = hipMemcpyAsync(d.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     const hipError_t es = hipStreamSynchronize((hipStream_t)stream);    // (`tab` leaves scope: the copy must have read it)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) {
-      (void)hipFree(d);
       set_error("vbt_overlay_set_hud failed: %s", hipGetErrorString(e));
       return VBT_ERR_HIP;
     }
   }
   overlay_free_hud(o);
-  o->d_hud = d; o->hud_P = P; o->hud = true; o->hud_prm = *params;
+  o->hud_tab = std::move(d);
+  o->d_hud = o->hud_tab.get(); o->hud_P = P; o->hud = true; o->hud_prm = *params;
   uint8_t c[3];
   overlay_colour(o->fmt, params->bg, c);
   o->b0 = c[0]; o->b1 = c[1]; o->b2 = c[2];
@@ -720,24 +721,26 @@ int vbt_overlay_hud_follow(vbt_overlay* o, const vbt_overlay_hud_params* params,
   if (lt.device != o->device) { set_error("%s: the tracker is on device %d, the handle on device %d", who, lt.device, o->device); return VBT_ERR_ARG; }
   VBT_HIP_CHECK(hipSetDevice(o->device));
   const int cap = lt.c.phase_cap;
-  const size_t tab_b = (size_t)cap * OV_HUD_REC * 4, state_b = OV_HUD_STATE * 4, view_b = (size_t)cap * 6 * sizeof(double);   // (tab_b is a multiple of 8)
-  uint8_t* blob = nullptr;
-  hipEvent_t ev = nullptr;
-  VBT_HIP_CHECK(hipMalloc((void**)&blob, tab_b + state_b + view_b));
-  hipError_t e = hipMemsetAsync(blob, 0, tab_b + state_b + view_b, nullptr);
-  if (e == hipSuccess) e = hipMemsetAsync(blob + tab_b + OV_HUD_STATE_LEADER * 4, 0xff, 8, nullptr);   // leader -1, P = 0: blank until the first update
+  Carver<8> C;   // table | state | view, back to back: the table's and the state's sizes are multiples of 8
+  const auto tab = C.add<int32_t>((size_t)cap * OV_HUD_REC), state = C.add<int32_t>(OV_HUD_STATE);
+  const auto view = C.add<double>((size_t)cap * 6);
+  DevBuf<uint8_t> owner;
+  Event ev;
+  VBT_HIP_CHECK(owner.alloc(C.bytes()));
+  uint8_t* const blob = owner.get();
+  hipError_t e = hipMemsetAsync(blob, 0, C.bytes(), nullptr);
+  if (e == hipSuccess) e = hipMemsetAsync(C.ptr(blob, state) + OV_HUD_STATE_LEADER, 0xff, 8, nullptr);   // leader -1, P = 0: blank until the first update
   const hipError_t es = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = es;
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = ev.create(hipEventDisableTiming);
   if (e != hipSuccess) {
-    (void)hipFree(blob);
     set_error("%s failed: %s", who, hipGetErrorString(e));
     return VBT_ERR_HIP;
   }
   overlay_free_hud(o);
-  o->HF.tab = (int32_t*)blob; o->HF.state = (int32_t*)(blob + tab_b); o->HF.view = (double*)(blob + tab_b + state_b);
+  o->HF.tab = C.ptr(blob, tab); o->HF.state = C.ptr(blob, state); o->HF.view = C.ptr(blob, view);
   o->HF.fps = fps; o->HF.cap = cap; o->HF.clip = clip;
-  o->hud_follow_blob = blob; o->ev_hud_drawn = ev; o->hud_drawn = false; o->hud_trk = t; o->hud_flush = 0;
+  o->hud_follow_blob = std::move(owner); o->ev_hud_drawn = std::move(ev); o->hud_drawn = false; o->hud_trk = t; o->hud_flush = 0;
   o->d_hud = o->HF.tab; o->hud_P = 0; o->hud = true; o->hud_follow = true; o->hud_prm = *params;
   uint8_t c[3];
   overlay_colour(o->fmt, params->bg, c);
@@ -805,12 +808,12 @@ namespace vbt {
 bool overlay_hud_follows(const vbt_overlay* o, const vbt_tracker* t) { return o && o->hud_follow && o->hud_trk == t; }
 
 int overlay_hud_follow_enqueue(vbt_overlay* o, hipStream_t T) {
-  if (o->hud_drawn) VBT_HIP_CHECK(hipStreamWaitEvent(T, o->ev_hud_drawn, 0));
+  if (o->hud_drawn) VBT_HIP_CHECK(hipStreamWaitEvent(T, o->ev_hud_drawn.get(), 0));
   return vbt_overlay_hud_follow_update(o, o->hud_flush, (void*)T);
 }
 
 int overlay_hud_follow_drawn(vbt_overlay* o, hipStream_t stream) {
-  VBT_HIP_CHECK(hipEventRecord(o->ev_hud_drawn, stream));
+  VBT_HIP_CHECK(hipEventRecord(o->ev_hud_drawn.get(), stream));
   o->hud_drawn = true;
   return VBT_OK;
 }

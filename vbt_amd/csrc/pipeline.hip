@@ -5,12 +5,14 @@
 // kernel: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
 // events that order detector(t) -> tracker(t) -> slot reuse, the staging ring of the host-fed mode, the deferred tracker groups of
 // the small-batch path and the step groups of the large-batch path (one forward of G x n images behind G step calls) as one held-back
-// block, clip close.  The stream pool is stream_pool.h, the run lists of a block's walk walk_runs.h.  Plain hipMalloc / hipHostMalloc / hipStream / hipEvent: no framework allocator, no
-// framework streams.
+// block, clip close.  The stream pool is stream_pool.h, the run lists of a block's walk walk_runs.h.  Every device buffer, pinned buffer and event is held by an owner
+// (dev_mem.h, hip_handles.h) and goes with the handle; the streams are borrowed from the pool.  No framework allocator, no framework streams.
 #include <algorithm>
 #include <chrono>
 
 #include "common.h"
+#include "dev_mem.h"
+#include "hip_handles.h"
 #include "stream_pool.h"
 #include "walk_runs.h"
 
@@ -26,11 +28,9 @@ struct vbt_pipeline {
   bool trk_inline = false, placement_ok = true;
   bool live = false;               // vbt_pipeline_live_enable succeeded
   std::vector<double> fps;
-  std::vector<vbt_model*> models;
-  vbt_tracker* trk = nullptr;
   // detector outputs: one array per tensor, [ring slot][batch slot]...: the walk of a block addresses batch slot i of its step g as slot g * n + i
-  float *boxes = nullptr, *scores = nullptr, *classes = nullptr;
-  int32_t* counts = nullptr;
+  DevBuf<float> boxes, scores, classes;
+  DevBuf<int32_t> counts;
   // What the tracker needs to know about the step in a ring slot.  vbt_pipeline_step (fill_step): per batch slot the tracker clip (-1: none)
   // and the 1-based frame number of that clip; vbt_pipeline_step_runs: the runs to walk, and then clip / frame are not read.
   struct Step {
@@ -54,18 +54,18 @@ struct vbt_pipeline {
   std::vector<size_t> walk_cur;
   std::vector<vbt_run> walk_runs;
   hipStream_t det_streams[8] = {nullptr}, copy_stream = nullptr, trk_stream = nullptr;
-  std::vector<hipEvent_t> ev_in, ev_det, ev_trk;
+  std::vector<Event> ev_in, ev_det, ev_trk;
   std::vector<int> trk_ev_of;      // ring slot -> index into ev_trk of the tracker launch that read it last (-1: none)
   int last_trk = -1;               // index into ev_trk of the most recent tracker launch
   struct Stage {
-    uint8_t* buf = nullptr;
-    size_t bytes = 0;
-    hipEvent_t free_ev = nullptr, copy_ev = nullptr;
+    DevBuf<uint8_t> buf;
+    size_t bytes = 0;              // (0 whenever buf is empty)
+    Event free_ev, copy_ev;
     bool free_set = false;
   };
   std::vector<Stage> stage;
   int stage_idx = 0;
-  std::vector<uint8_t*> resized;
+  std::vector<DevBuf<uint8_t>> resized;
   std::vector<int64_t> clip_frames;
   std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
   int row_H = 0, row_h = 0;
@@ -77,13 +77,19 @@ struct vbt_pipeline {
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
   // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
   // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
-  unsigned char* closed_head = nullptr;
+  PinnedBuf<unsigned char> closed_head;
   unsigned char* closed_head_dev = nullptr;   // (its device address)
-  void* closed_rows = nullptr;
-  std::vector<hipEvent_t> ev_closed;
+  DevBuf<unsigned char> closed_rows;
+  std::vector<Event> ev_closed;
   std::vector<char> closed_unread;
   std::vector<int> fc_base;
   hipStream_t read_stream = nullptr;   // the rows of a closed slot come back on it (a pool stream that carries nothing else)
+  // declared last, so destroyed first: the models and the tracker go before the rings and events their launches used
+  struct ModelDelete { void operator()(vbt_model* m) const { vbt_model_destroy(m); } };
+  struct TrackerDelete { void operator()(vbt_tracker* t) const { vbt_tracker_destroy(t); } };
+  std::unique_ptr<vbt_tracker, TrackerDelete> trk;
+  std::vector<std::unique_ptr<vbt_model, ModelDelete>> models;
+  ~vbt_pipeline();
 };
 
 namespace {
@@ -100,13 +106,13 @@ struct StepTimer {
 };
 
 // ---- output ring ----
-inline float* boxes_of(vbt_pipeline* p, int o) { return p->boxes + (size_t)o * p->n * VBT_MAX_DETECTIONS * 4; }
-inline float* scores_of(vbt_pipeline* p, int o) { return p->scores + (size_t)o * p->n * VBT_MAX_DETECTIONS; }
-inline float* classes_of(vbt_pipeline* p, int o) { return p->classes + (size_t)o * p->n * VBT_MAX_DETECTIONS; }
-inline int32_t* counts_of(vbt_pipeline* p, int o) { return p->counts + (size_t)o * p->n; }
+inline float* boxes_of(vbt_pipeline* p, int o) { return p->boxes.get() + (size_t)o * p->n * VBT_MAX_DETECTIONS * 4; }
+inline float* scores_of(vbt_pipeline* p, int o) { return p->scores.get() + (size_t)o * p->n * VBT_MAX_DETECTIONS; }
+inline float* classes_of(vbt_pipeline* p, int o) { return p->classes.get() + (size_t)o * p->n * VBT_MAX_DETECTIONS; }
+inline int32_t* counts_of(vbt_pipeline* p, int o) { return p->counts.get() + (size_t)o * p->n; }
 
 int record_trk(vbt_pipeline* p, int o, hipStream_t T) {
-  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o], T));
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o].get(), T));
   p->trk_ev_of[o] = o;
   p->last_trk = o;
   return VBT_OK;
@@ -156,25 +162,25 @@ int enqueue_tracker(vbt_pipeline* p, int o) {
   hipStream_t T;
   if (p->trk_inline) {
     T = p->det_streams[o % p->depth];
-    if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));   // tracker steps run in frame order
+    if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk].get(), 0));   // tracker steps run in frame order
   } else {
     T = p->trk_stream;
-    VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o], 0));
+    VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o].get(), 0));
   }
   const vbt_pipeline::Step& m = p->meta[o];
   // frame times / clip map / runs of the step travel in the kernel arguments (read during the call, no copy in flight)
   if (!m.runs.empty()) {
-    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.B, m.runs.data(), (int)m.runs.size(),
+    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk.get(), boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.B, m.runs.data(), (int)m.runs.size(),
                                                     p->prm.detection_threshold, (void*)T));
     return record_trk(p, o, T);
   }
   // time = frame number / fps of the clip; fps cannot have changed since the step: a slot close drains before it sets a new one
   for (int i = 0; i < p->n; i++) p->times[i] = m.clip[i] >= 0 ? (double)m.frame[i] / p->fps[m.clip[i]] : -1.0;
   if (m.mapped) {
-    PL_CHECK(vbt_tracker_update_from_slots(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.clip.data(), p->times.data(), p->n,
+    PL_CHECK(vbt_tracker_update_from_slots(p->trk.get(), boxes_of(p, o), scores_of(p, o), counts_of(p, o), m.clip.data(), p->times.data(), p->n,
                                            p->prm.detection_threshold, (void*)T));
   } else {   // (reads the first n_trk slots: slot i is clip i)
-    PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, o), scores_of(p, o), counts_of(p, o), p->times.data(), p->prm.detection_threshold,
+    PL_CHECK(vbt_tracker_update_from_detections(p->trk.get(), boxes_of(p, o), scores_of(p, o), counts_of(p, o), p->times.data(), p->prm.detection_threshold,
                                                 (void*)T));
   }
   return record_trk(p, o, T);
@@ -186,7 +192,7 @@ int wait_slot_free(vbt_pipeline* p, int o, hipStream_t S) {
     set_error("vbt_pipeline: ring slot %d still holds a step whose tracker update has not been enqueued", o);
     return VBT_ERR_STATE;
   }
-  if (p->trk_ev_of[o] >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_trk[p->trk_ev_of[o]], 0));   // the tracker is done with this slot's previous outputs
+  if (p->trk_ev_of[o] >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_trk[p->trk_ev_of[o]].get(), 0));   // the tracker is done with this slot's previous outputs
   return VBT_OK;
 }
 
@@ -214,10 +220,10 @@ int flush_block(vbt_pipeline* p) {
   if (grouped) {
     hipStream_t S = p->det_streams[b.k];
     for (int g = 0; g < used; g++) PL_CHECK(wait_slot_free(p, o0 + g, S));
-    vbt_model* m = p->models[(size_t)b.k];
+    vbt_model* m = p->models[(size_t)b.k].get();
     PL_CHECK(vbt_detect_range_async(m, nullptr, 0, used * n, vbt_model_entry_steps(m), -1, (void*)S, boxes_of(p, o0), scores_of(p, o0), classes_of(p, o0),
                                     counts_of(p, o0)));
-    for (int g = 0; g < used; g++) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o0 + g], S));
+    for (int g = 0; g < used; g++) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o0 + g].get(), S));
   } else if (used == 1) {
     return enqueue_tracker(p, o0);
   }
@@ -234,15 +240,15 @@ int flush_block(vbt_pipeline* p) {
   for (int g = 0; g < used; g++) {   // the last forward of every other stream in the block
     bool last = p->det_streams[fwd_slot(g)] != T;
     for (int h = g + 1; h < used && last; h++) last = fwd_slot(h) != fwd_slot(g);
-    if (last) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o0 + g], 0));
+    if (last) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[o0 + g].get(), 0));
   }
-  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));   // tracker launches run in frame order
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk].get(), 0));   // tracker launches run in frame order
   // (a slot close drains first: fps and the frame bases are those of the whole block)
   std::fill(p->walk_cur.begin(), p->walk_cur.end(), (size_t)0);
   while (next_walk_call(p->walk_per, p->fps.data(), p->walk_cur, p->walk_runs))
-    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk, boxes_of(p, o0), scores_of(p, o0), counts_of(p, o0), used * n, p->walk_runs.data(),
+    PL_CHECK(vbt_tracker_update_from_detections_seq(p->trk.get(), boxes_of(p, o0), scores_of(p, o0), counts_of(p, o0), used * n, p->walk_runs.data(),
                                                     (int)p->walk_runs.size(), p->prm.detection_threshold, (void*)T));
-  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o_last], T));
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o_last].get(), T));
   for (int g = 0; g < used; g++) p->trk_ev_of[o0 + g] = o_last;
   p->last_trk = o_last;
   return VBT_OK;
@@ -268,7 +274,7 @@ int drain(vbt_pipeline* p) {
   PL_CHECK(flush_block(p));
   PL_CHECK(enqueue_lagging(p, 0));
   if (p->trk_inline && p->last_trk >= 0)   // clip close / row reads run on the tracker stream
-    VBT_HIP_CHECK(hipStreamWaitEvent(p->trk_stream, p->ev_trk[p->last_trk], 0));
+    VBT_HIP_CHECK(hipStreamWaitEvent(p->trk_stream, p->ev_trk[p->last_trk].get(), 0));
   return VBT_OK;
 }
 
@@ -284,19 +290,17 @@ int stage_take(vbt_pipeline* p, size_t bytes, bool host_gate, hipStream_t S, int
   if (st.bytes < bytes) {
     // a buffer that has to be replaced may still be read by a forward or written by a copy in flight (up to depth + 2 steps)
     if (st.buf) {
-      if (st.free_set) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev));
-      VBT_HIP_CHECK(hipEventSynchronize(st.copy_ev));
-      VBT_HIP_CHECK(hipFree(st.buf));
-      st.buf = nullptr;
-      st.bytes = 0;
+      if (st.free_set) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev.get()));
+      VBT_HIP_CHECK(hipEventSynchronize(st.copy_ev.get()));
       st.free_set = false;
     }
-    VBT_HIP_CHECK(hipMalloc((void**)&st.buf, bytes + 64));
+    st.bytes = 0;
+    VBT_HIP_CHECK(st.buf.alloc(bytes + 64));   // (frees the old buffer first)
     st.bytes = bytes;
   }
   if (st.free_set) {
-    if (host_gate) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev));
-    else VBT_HIP_CHECK(hipStreamWaitEvent(S, st.free_ev, 0));
+    if (host_gate) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev.get()));
+    else VBT_HIP_CHECK(hipStreamWaitEvent(S, st.free_ev.get(), 0));
   }
   *j_out = j;
   return VBT_OK;
@@ -407,7 +411,7 @@ int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t
 }
 
 int ensure_resized(vbt_pipeline* p, int k) {
-  if (!p->resized[k]) VBT_HIP_CHECK(hipMalloc((void**)&p->resized[k], (size_t)p->n * p->size * p->size * 3 + 64));
+  if (!p->resized[k]) VBT_HIP_CHECK(p->resized[k].alloc((size_t)p->n * p->size * p->size * 3 + 64));
   return VBT_OK;
 }
 
@@ -451,8 +455,8 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
   if (src.on_device) {
     // frames are ready once the caller's stream gets here
     const int ki = k;
-    VBT_HIP_CHECK(hipEventRecord(p->ev_in[ki], (hipStream_t)caller_stream));
-    VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_in[ki], 0));
+    VBT_HIP_CHECK(hipEventRecord(p->ev_in[ki].get(), (hipStream_t)caller_stream));
+    VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_in[ki].get(), 0));
   }
   if (src.frames) {
     if (src.on_device) {
@@ -461,10 +465,10 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
       compact = resize && compact_rows(p, H, W);
       int j = 0;
       PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), true, S, &j));
-      PL_CHECK(upload(p->stage[j].buf, 0, src.frames, B, compact));
-      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev, p->copy_stream));
-      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev, 0));
-      ptr = p->stage[j].buf;
+      PL_CHECK(upload(p->stage[j].buf.get(), 0, src.frames, B, compact));
+      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev.get(), p->copy_stream));
+      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev.get(), 0));
+      ptr = p->stage[j].buf.get();
       *stage_j = j;
     }
   } else {
@@ -472,11 +476,11 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
     compact = !src.on_device && resize && compact_rows(p, H, W);
     int j = 0;
     PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), !src.on_device, S, &j));
-    uint8_t* st = p->stage[j].buf;
+    uint8_t* st = p->stage[j].buf.get();
     if (!src.on_device) {
       for (int i = 0; i < n_runs; i++) PL_CHECK(upload(st, runs[i].slot0, src.run_sources[i], runs[i].n_frames, compact));
-      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev, p->copy_stream));
-      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev, 0));
+      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev.get(), p->copy_stream));
+      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev.get(), 0));
     } else {
       bool aligned = fb % 16 == 0;
       for (int i = 0; i < n_runs && aligned; i++) aligned = ((uintptr_t)src.run_sources[i] & 15) == 0;
@@ -499,11 +503,11 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
     PL_CHECK(ensure_resized(p, k));
     if (yuv) {
       const YuvCompact cl = compact ? yuv_compact(p, H, W) : YuvCompact{0, 0, (size_t)H * W, fb};
-      PL_CHECK(resize_frames_yuv_dev(ptr, B, H, W, p->pix_fmt, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0, p->resized[k], size, size, S));
+      PL_CHECK(resize_frames_yuv_dev(ptr, B, H, W, p->pix_fmt, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0, p->resized[k].get(), size, size, S));
     } else {
-      PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k], size, size, src.swap_rb, compact ? 1 : 0, S));
+      PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k].get(), size, size, src.swap_rb, compact ? 1 : 0, S));
     }
-    ptr = p->resized[k];
+    ptr = p->resized[k].get();
   }
   *frames_dev = ptr;
   return VBT_OK;
@@ -530,9 +534,9 @@ int begin_step(vbt_pipeline* p, int o, int k, bool wait, bool counts_frame, cons
 // Behind the last kernel that reads the step's frames on S: the detections of ring slot o are complete (o < 0: not yet, the entry of
 // a step group), the staging buffer is free again
 int end_detect(vbt_pipeline* p, int o, int stage_j, hipStream_t S) {
-  if (o >= 0) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o], S));
+  if (o >= 0) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o].get(), S));
   if (stage_j >= 0) {
-    VBT_HIP_CHECK(hipEventRecord(p->stage[stage_j].free_ev, S));
+    VBT_HIP_CHECK(hipEventRecord(p->stage[stage_j].free_ev.get(), S));
     p->stage[stage_j].free_set = true;
   }
   return VBT_OK;
@@ -560,7 +564,7 @@ int step_runs_impl(vbt_pipeline* p, const Sources& src, const vbt_run* asm_runs,
   float* s = outs ? out_scores : scores_of(p, o);
   float* c = outs ? out_classes : classes_of(p, o);
   int32_t* cnt = outs ? out_counts : counts_of(p, o);
-  PL_CHECK(vbt_detect_async(p->models[k], fd, B, (void*)S, b, s, c, cnt));
+  PL_CHECK(vbt_detect_async(p->models[k].get(), fd, B, (void*)S, b, s, c, cnt));
   PL_CHECK(end_detect(p, o, stage_j, S));
   vbt_pipeline::Step& m = p->meta[o];
   m.runs.swap(walk_runs);
@@ -593,7 +597,7 @@ int step_frames(vbt_pipeline* p, const Sources& src, const uint8_t* active, cons
   int stage_j = -1;
   PL_CHECK(begin_step(p, o, k, !grouped, true, src, nullptr, 0, n, caller_stream, &fd, &stage_j));
   fill_step(p, p->meta[(size_t)o], active, clip_map, frame_idx, track);
-  vbt_model* mdl = p->models[(size_t)k];
+  vbt_model* mdl = p->models[(size_t)k].get();
   if (grouped) {   // the entry on slice `used` of the forward; it was the staging buffer's only reader
     PL_CHECK(vbt_detect_range_async(mdl, fd, p->blk.used * n, n, 0, vbt_model_entry_steps(mdl), (void*)S, nullptr, nullptr, nullptr, nullptr));
     PL_CHECK(end_detect(p, -1, stage_j, S));
@@ -612,6 +616,23 @@ int step_frames(vbt_pipeline* p, const Sources& src, const uint8_t* active, cons
 }
 
 }  // namespace
+
+// Also the end of a create that fails half way: streams not taken yet are null, models not made yet are absent.
+vbt_pipeline::~vbt_pipeline() {
+  (void)hipSetDevice(device);
+  (void)finish_forward(this);   // (the models' tensors are released below: nothing half-run stays behind)
+  for (int k = 0; k < depth; k++)
+    if (det_streams[k]) (void)hipStreamSynchronize(det_streams[k]);
+  if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+  if (trk_stream) (void)hipStreamSynchronize(trk_stream);
+  {
+    // streams are never destroyed: they go back to the process-wide pool, classified, for the next pipeline
+    std::lock_guard<std::mutex> lock(g_pool_mu);
+    StreamPool& pool = g_pools[device];
+    for (int i : own_streams) pool.free.push_back(i);
+  }
+  // the members go in reverse order of declaration: the models and the tracker first, then the slot-close buffers, the rings, the events
+}
 
 extern "C" {
 
@@ -635,41 +656,7 @@ void vbt_pipeline_default_params(vbt_pipeline_params* p) {
   p->tracker.det_thresh = 0.2;
 }
 
-void vbt_pipeline_destroy(vbt_pipeline* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  (void)finish_forward(p);   // (the models' tensors are released below: nothing half-run stays behind)
-  for (int k = 0; k < p->depth; k++)
-    if (p->det_streams[k]) (void)hipStreamSynchronize(p->det_streams[k]);
-  if (p->copy_stream) (void)hipStreamSynchronize(p->copy_stream);
-  if (p->trk_stream) (void)hipStreamSynchronize(p->trk_stream);
-  for (vbt_model* m : p->models) vbt_model_destroy(m);
-  if (p->trk) vbt_tracker_destroy(p->trk);
-  (void)hipFree(p->boxes);
-  (void)hipFree(p->scores);
-  (void)hipFree(p->classes);
-  (void)hipFree(p->counts);
-  for (auto& s : p->stage) {
-    if (s.buf) (void)hipFree(s.buf);
-    if (s.free_ev) (void)hipEventDestroy(s.free_ev);
-    if (s.copy_ev) (void)hipEventDestroy(s.copy_ev);
-  }
-  for (uint8_t* r : p->resized)
-    if (r) (void)hipFree(r);
-  for (hipEvent_t e : p->ev_in) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->ev_det) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->ev_trk) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->ev_closed) (void)hipEventDestroy(e);
-  if (p->closed_head) (void)hipHostFree(p->closed_head);
-  if (p->closed_rows) (void)hipFree(p->closed_rows);
-  {
-    // streams are never destroyed: they go back to the process-wide pool, classified, for the next pipeline
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    StreamPool& pool = g_pools[p->device];
-    for (int i : p->own_streams) pool.free.push_back(i);
-  }
-  delete p;
-}
+void vbt_pipeline_destroy(vbt_pipeline* p) { delete p; }
 
 int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* prm, const double* fps_host, vbt_pipeline** out) {
   if (!container_path || !prm || !fps_host || !out) { set_error("vbt_pipeline_create: NULL argument"); return VBT_ERR_ARG; }
@@ -680,13 +667,14 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
     return VBT_ERR_ARG;
   }
   if (int rc = use_device("vbt_pipeline_create", prm->device)) return rc;
-  vbt_pipeline* p = new vbt_pipeline();
+  std::unique_ptr<vbt_pipeline> owner(new vbt_pipeline());
+  vbt_pipeline* const p = owner.get();
   p->prm = *prm;
   p->n = prm->n_slots;
   p->n_trk = prm->n_clips > 0 ? prm->n_clips : prm->n_slots;
   p->device = prm->device;
   for (int c = 0; c < p->n_trk; c++) {
-    if (!(fps_host[c] > 0.0)) { delete p; set_error("vbt_pipeline_create: fps of clip %d must be > 0", c); return VBT_ERR_ARG; }
+    if (!(fps_host[c] > 0.0)) { set_error("vbt_pipeline_create: fps of clip %d must be > 0", c); return VBT_ERR_ARG; }
     p->fps.push_back(fps_host[c]);
   }
   p->fc_base.assign((size_t)p->n_trk, 0);
@@ -697,7 +685,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   int mode = prm->tracker_stream;
   if (mode == 0) {
     const char* ts = getenv("VBT_TRACKER_STREAM");
-    if (ts && strcmp(ts, "own") != 0 && strcmp(ts, "inline") != 0) { delete p; set_error("VBT_TRACKER_STREAM must be 'own' or 'inline'"); return VBT_ERR_ARG; }
+    if (ts && strcmp(ts, "own") != 0 && strcmp(ts, "inline") != 0) { set_error("VBT_TRACKER_STREAM must be 'own' or 'inline'"); return VBT_ERR_ARG; }
     mode = ts ? (strcmp(ts, "inline") == 0 ? 2 : 1) : (p->depth >= 3 ? 2 : 1);
   }
   p->trk_inline = mode == 2;
@@ -726,36 +714,37 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   }
   if (p->G > 1) p->defer = 0;
   p->ring = p->G > 1 ? (p->depth + 1) * p->G : p->defer ? 2 * p->depth : p->depth;
-  auto fail = [&](int rc) { vbt_pipeline_destroy(p); return rc; };
   int rc = VBT_OK;
   for (int k = 0; k < p->depth; k++) {
     vbt_model* m = nullptr;
-    if ((rc = vbt_model_create_ex(container_path, p->device, p->G * p->n, prm->model_flags, &m)) != VBT_OK) return fail(rc);
-    p->models.push_back(m);
+    if ((rc = vbt_model_create_ex(container_path, p->device, p->G * p->n, prm->model_flags, &m)) != VBT_OK) return rc;
+    p->models.emplace_back(m);
   }
   int shp[4];
-  if ((rc = vbt_model_input_shape(p->models[0], shp)) != VBT_OK) return fail(rc);
+  if ((rc = vbt_model_input_shape(p->models[0].get(), shp)) != VBT_OK) return rc;
   p->size = shp[1];
-  if ((rc = vbt_tracker_create(p->n_trk, prm->rows_cap, &prm->tracker, p->device, &p->trk)) != VBT_OK) return fail(rc);
-  const size_t R = (size_t)p->ring, n = (size_t)p->n, md = VBT_MAX_DETECTIONS;
-  if (hipMalloc((void**)&p->boxes, R * n * md * 16) != hipSuccess || hipMalloc((void**)&p->scores, R * n * md * 4) != hipSuccess ||
-      hipMalloc((void**)&p->classes, R * n * md * 4) != hipSuccess || hipMalloc((void**)&p->counts, R * n * 4) != hipSuccess) {
-    set_error("vbt_pipeline_create: hipMalloc of the detector output ring failed");
-    return fail(VBT_ERR_HIP);
+  {
+    vbt_tracker* t = nullptr;
+    if ((rc = vbt_tracker_create(p->n_trk, prm->rows_cap, &prm->tracker, p->device, &t)) != VBT_OK) return rc;
+    p->trk.reset(t);
   }
-  (void)hipMemset(p->counts, 0, R * n * 4);
+  const size_t R = (size_t)p->ring, n = (size_t)p->n, md = VBT_MAX_DETECTIONS;
+  if (p->boxes.alloc(R * n * md * 4) != hipSuccess || p->scores.alloc(R * n * md) != hipSuccess || p->classes.alloc(R * n * md) != hipSuccess ||
+      p->counts.alloc(R * n) != hipSuccess) {
+    set_error("vbt_pipeline_create: hipMalloc of the detector output ring failed");
+    return VBT_ERR_HIP;
+  }
+  (void)hipMemset(p->counts.get(), 0, R * n * 4);
   p->meta.resize(R);
   for (auto& m : p->meta) { m.clip.assign(n, -1); m.frame.assign(n, 0); }
   p->times.assign(n, 0.0);
   p->walk_per.resize((size_t)p->n_trk);
   p->walk_cur.resize((size_t)p->n_trk);
   p->trk_ev_of.assign(R, -1);
-  auto new_events = [&](std::vector<hipEvent_t>& v, size_t cnt) {
-    for (size_t i = 0; i < cnt; i++) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
-      v.push_back(e);
-    }
+  auto new_events = [&](std::vector<Event>& v, size_t cnt) {
+    v.resize(cnt);
+    for (Event& e : v)
+      if (e.create(hipEventDisableTiming) != hipSuccess) return false;
     return true;
   };
   bool ok = new_events(p->ev_in, (size_t)p->depth) && new_events(p->ev_det, R) && new_events(p->ev_trk, R);
@@ -763,9 +752,9 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   // forwards, so that a slot's forward never waits for its own copy
   p->stage.resize((size_t)p->depth + 2);
   for (auto& s : p->stage)
-    ok = ok && hipEventCreateWithFlags(&s.free_ev, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.copy_ev, hipEventDisableTiming) == hipSuccess;
-  if (!ok) { set_error("vbt_pipeline_create: hipEventCreate failed"); return fail(VBT_ERR_HIP); }
-  p->resized.assign((size_t)p->depth, nullptr);
+    ok = ok && s.free_ev.create(hipEventDisableTiming) == hipSuccess && s.copy_ev.create(hipEventDisableTiming) == hipSuccess;
+  if (!ok) { set_error("vbt_pipeline_create: hipEventCreate failed"); return VBT_ERR_HIP; }
+  p->resized.resize((size_t)p->depth);
   p->clip_frames.assign(n, 0);
   {
     // the pipeline's own HIP streams (detector slots, copy, tracker): each is bound to its hardware queue at creation
@@ -790,31 +779,30 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
       p->trk_stream = pool.streams[role_idx[9]];
     }
   }
-  if (rc != VBT_OK) return fail(rc);
+  if (rc != VBT_OK) return rc;
   // Self-check: every slot runs its whole plan on a blank batch before the first real frame, so a plan the kernels reject (LDS
   // budget, tile shape) fails here and not in the middle of a clip; the first real step then also finds code objects, arenas and
   // GPU clocks warm.  Detector only: no tracker state is touched.
   const int n_check = prm->selfcheck >= 0 ? prm->selfcheck : env_int("VBT_PIPELINE_SELFCHECK", 1);
   if (n_check > 0) {
-    uint8_t* blank = nullptr;
+    DevBuf<uint8_t> blank;   // (freed when the block ends, behind the synchronisation of every forward that read it)
     const size_t bytes = (size_t)p->G * n * p->size * p->size * 3;   // (a grouped pipeline checks the batch its forwards run at)
-    if (hipMalloc((void**)&blank, bytes + 64) != hipSuccess) { set_error("vbt_pipeline_create: hipMalloc of the self-check batch failed"); return fail(VBT_ERR_HIP); }
-    (void)hipMemset(blank, 0, bytes);
+    if (blank.alloc(bytes + 64) != hipSuccess) { set_error("vbt_pipeline_create: hipMalloc of the self-check batch failed"); return VBT_ERR_HIP; }
+    (void)hipMemset(blank.get(), 0, bytes);
     (void)hipDeviceSynchronize();
     for (int i = 0; i < n_check && rc == VBT_OK; i++)
       for (int k = 0; k < p->depth && rc == VBT_OK; k++)
-        rc = vbt_detect_async(p->models[k], blank, p->G * p->n, (void*)p->det_streams[k], boxes_of(p, k * p->G), scores_of(p, k * p->G),
+        rc = vbt_detect_async(p->models[k].get(), blank.get(), p->G * p->n, (void*)p->det_streams[k], boxes_of(p, k * p->G), scores_of(p, k * p->G),
                               classes_of(p, k * p->G), counts_of(p, k * p->G));
     hipError_t e = hipSuccess;
     for (int k = 0; k < p->depth; k++) {
       const hipError_t ek = hipStreamSynchronize(p->det_streams[k]);
       if (e == hipSuccess) e = ek;
     }
-    (void)hipFree(blank);
-    if (rc != VBT_OK) return fail(rc);
-    if (e != hipSuccess) { set_error("vbt_pipeline_create: self-check forward failed: %s", hipGetErrorString(e)); return fail(VBT_ERR_HIP); }
+    if (rc != VBT_OK) return rc;
+    if (e != hipSuccess) { set_error("vbt_pipeline_create: self-check forward failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   }
-  *out = p;
+  *out = owner.release();
   return VBT_OK;
 }
 
@@ -900,7 +888,7 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
   VBT_HIP_CHECK(hipDeviceSynchronize());
-  PL_CHECK(vbt_tracker_reset(p->trk));
+  PL_CHECK(vbt_tracker_reset(p->trk.get()));
   p->frame_count = 0;
   p->step_idx = 0;
   p->next_o = p->fwd_idx = p->last_o = p->last_k = 0;
@@ -916,7 +904,7 @@ int vbt_pipeline_reset(vbt_pipeline* p) {
 int vbt_pipeline_join_detectors(vbt_pipeline* p, void* stream) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   PL_CHECK(finish_forward(p));
-  for (hipEvent_t e : p->ev_det) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, e, 0));
+  for (const Event& e : p->ev_det) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, e.get(), 0));
   return VBT_OK;
 }
 
@@ -930,7 +918,7 @@ int vbt_pipeline_finish(vbt_pipeline* p) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
-  PL_CHECK(vbt_tracker_finish(p->trk, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
   VBT_HIP_CHECK(hipStreamSynchronize(p->trk_stream));
   return VBT_OK;
 }
@@ -942,41 +930,37 @@ int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
   if (p->closed_head) return VBT_OK;
   VBT_HIP_CHECK(hipSetDevice(p->device));
   const size_t nt = (size_t)p->n_trk;
-  void* rows = nullptr;
-  unsigned char *head = nullptr, *head_dev = nullptr;
-  std::vector<hipEvent_t> evs;
-  auto undo = [&](const char* what, hipError_t e) {
-    for (hipEvent_t x : evs) (void)hipEventDestroy(x);
-    if (head) (void)hipHostFree(head);
-    if (rows) (void)hipFree(rows);
+  auto failed = [](const char* what, hipError_t e) {
     set_error("vbt_pipeline_close_clips_enable: %s failed: %s", what, hipGetErrorString(e));
     return VBT_ERR_HIP;
   };
-  hipError_t e = hipMalloc(&rows, nt * (size_t)p->prm.rows_cap * 64);
-  if (e != hipSuccess) { rows = nullptr; return undo("hipMalloc of the row outboxes", e); }
+  DevBuf<unsigned char> rows;
+  PinnedBuf<unsigned char> head;
+  unsigned char* head_dev = nullptr;
+  std::vector<Event> evs(nt);
+  hipError_t e = rows.alloc(nt * (size_t)p->prm.rows_cap * 64);
+  if (e != hipSuccess) return failed("hipMalloc of the row outboxes", e);
   // coherent: the close kernel's stores reach host memory directly, visible once the close's event has completed
-  e = hipHostMalloc((void**)&head, nt * CLOSED_HEAD_BYTES, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e != hipSuccess) { head = nullptr; return undo("hipHostMalloc of the close records", e); }
-  e = hipHostGetDevicePointer((void**)&head_dev, head, 0);
-  if (e != hipSuccess) return undo("hipHostGetDevicePointer", e);
-  for (size_t c = 0; c < nt; c++) {
-    hipEvent_t ev = nullptr;
-    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) return undo("hipEventCreate", e);
-    evs.push_back(ev);
+  e = head.alloc(nt * CLOSED_HEAD_BYTES, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return failed("hipHostMalloc of the close records", e);
+  e = hipHostGetDevicePointer((void**)&head_dev, head.get(), 0);
+  if (e != hipSuccess) return failed("hipHostGetDevicePointer", e);
+  for (Event& ev : evs) {
+    e = ev.create(hipEventDisableTiming);
+    if (e != hipSuccess) return failed("hipEventCreate", e);
   }
   {
     std::lock_guard<std::mutex> lock(g_pool_mu);
     StreamPool& pool = g_pools[p->device];
     int i = -1;
     const int rc = pool_take(pool, p->device, p->own_streams, -1, false, &i);
-    if (rc != VBT_OK) { undo("taking the read stream", hipSuccess); return rc; }
+    if (rc != VBT_OK) { failed("taking the read stream", hipSuccess); return rc; }
     p->read_stream = pool.streams[(size_t)i];
   }
-  p->closed_rows = rows;
-  p->closed_head = head;
+  p->closed_rows = std::move(rows);
+  p->closed_head = std::move(head);
   p->closed_head_dev = head_dev;
-  p->ev_closed.swap(evs);
+  p->ev_closed = std::move(evs);
   p->closed_unread.assign(nt, 0);
   return VBT_OK;
 }
@@ -1002,18 +986,18 @@ int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
   hipStream_t T = p->trk_stream;
-  PL_CHECK(tracker_close_clips(p->trk, clips, n, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, p->closed_head_dev,
-                               p->closed_rows, T));
+  PL_CHECK(tracker_close_clips(p->trk.get(), clips, n, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, p->closed_head_dev,
+                               p->closed_rows.get(), T));
   for (int i = 0; i < n; i++) {
     const int c = clips[i];
-    VBT_HIP_CHECK(hipEventRecord(p->ev_closed[(size_t)c], T));
+    VBT_HIP_CHECK(hipEventRecord(p->ev_closed[(size_t)c].get(), T));
     p->closed_unread[(size_t)c] = 1;
     p->fc_base[(size_t)c] = p->frame_count;                       // the next plain step is frame 1 of the new clip
     if ((size_t)c < p->clip_frames.size()) p->clip_frames[(size_t)c] = 0;
     if (next_fps) p->fps[(size_t)c] = next_fps[i];
   }
   const int e = p->last_trk >= 0 ? p->last_trk : 0;
-  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e], T));
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e].get(), T));
   p->last_trk = e;
   return VBT_OK;
 }
@@ -1029,7 +1013,7 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
   if (p->closed_unread.empty() || !p->closed_unread[(size_t)clip]) { set_error("vbt_pipeline_closed_clip: slot %d has no unread result", clip); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(finish_forward(p));
-  hipEvent_t ev = p->ev_closed[(size_t)clip];
+  hipEvent_t ev = p->ev_closed[(size_t)clip].get();
   if (wait) {
     VBT_HIP_CHECK(hipEventSynchronize(ev));
   } else {
@@ -1037,14 +1021,14 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
     if (q == hipErrorNotReady) return VBT_OK;
     VBT_HIP_CHECK(q);
   }
-  const unsigned char* h = p->closed_head + (size_t)clip * CLOSED_HEAD_BYTES;
+  const unsigned char* h = p->closed_head.get() + (size_t)clip * CLOSED_HEAD_BYTES;
   const int32_t* hd = (const int32_t*)h;
   rec->clip = clip; rec->best_id = hd[0]; rec->n_rows = hd[1]; rec->n_phases = hd[2]; rec->overflow = hd[3]; rec->reserved = 0;
   if (hd[2] > cap_phases) { set_error("vbt_pipeline_closed_clip: slot %d has %d phases, buffer holds %d", clip, hd[2], cap_phases); return VBT_ERR_CAPACITY; }
   if (rows_host && hd[1] > cap_rows) { set_error("vbt_pipeline_closed_clip: slot %d has %d rows, buffer holds %d", clip, hd[1], cap_rows); return VBT_ERR_CAPACITY; }
   if (hd[2] > 0) memcpy(phases6, h + 16, (size_t)hd[2] * 48);
   if (rows_host && hd[1] > 0) {
-    const unsigned char* src = (const unsigned char*)p->closed_rows + (size_t)clip * p->prm.rows_cap * 64;
+    const unsigned char* src = p->closed_rows.get() + (size_t)clip * p->prm.rows_cap * 64;
     VBT_HIP_CHECK(hipStreamWaitEvent(p->read_stream, ev, 0));   // (done already: the copy waits for this close only)
     VBT_HIP_CHECK(hipMemcpyAsync(rows_host, src, (size_t)hd[1] * 64, hipMemcpyDeviceToHost, p->read_stream));
     VBT_HIP_CHECK(hipStreamSynchronize(p->read_stream));
@@ -1062,15 +1046,15 @@ int vbt_pipeline_close(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int3
   }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
-  PL_CHECK(vbt_tracker_finish(p->trk, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
-  return vbt_tracker_summary(p->trk, best_ids, n_rows, n_phases, overflow, phases6, cap);
+  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  return vbt_tracker_summary(p->trk.get(), best_ids, n_rows, n_phases, overflow, phases6, cap);
 }
 
 int vbt_pipeline_rows_all(vbt_pipeline* p, int32_t* counts, void* rows_host, int cap) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
-  return vbt_tracker_rows_all(p->trk, counts, rows_host, cap, (void*)p->trk_stream);
+  return vbt_tracker_rows_all(p->trk.get(), counts, rows_host, cap, (void*)p->trk_stream);
 }
 
 int vbt_pipeline_rows(vbt_pipeline* p, int clip, int64_t* id, double* cols7, int cap, int* n) {
@@ -1078,7 +1062,7 @@ int vbt_pipeline_rows(vbt_pipeline* p, int clip, int64_t* id, double* cols7, int
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));
   VBT_HIP_CHECK(hipStreamSynchronize(p->trk_stream));
-  return vbt_tracker_rows(p->trk, clip, id, cols7, cap, n);
+  return vbt_tracker_rows(p->trk.get(), clip, id, cols7, cap, n);
 }
 
 int vbt_pipeline_detections(vbt_pipeline* p, float* boxes, float* scores, float* classes, int32_t* counts, int cap_slots, int* B) {
@@ -1105,13 +1089,13 @@ int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(flush_block(p));   // (tracker launches stay in frame order)
   hipStream_t T = p->trk_stream;
-  VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[slot], 0));
-  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk], 0));
+  VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_det[slot].get(), 0));
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent(T, p->ev_trk[p->last_trk].get(), 0));
   std::vector<double> tm((size_t)p->n);
   for (int i = 0; i < count; i++) {
     p->frame_count++;
     for (int c = 0; c < p->n; c++) tm[c] = (double)(p->frame_count - p->fc_base[c]) / p->fps[c];
-    PL_CHECK(vbt_tracker_update_from_detections(p->trk, boxes_of(p, slot), scores_of(p, slot), counts_of(p, slot), tm.data(), p->prm.detection_threshold, (void*)T));
+    PL_CHECK(vbt_tracker_update_from_detections(p->trk.get(), boxes_of(p, slot), scores_of(p, slot), counts_of(p, slot), tm.data(), p->prm.detection_threshold, (void*)T));
   }
   return record_trk(p, slot, T);
 }
@@ -1122,7 +1106,7 @@ int vbt_pipeline_tracker_only_steps(vbt_pipeline* p, int count, int slot) {
 int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   if (p->step_idx > 0) { set_error("vbt_pipeline_live_enable: steps were enqueued (enable before the first step, or after a reset)"); return VBT_ERR_STATE; }
-  PL_CHECK(vbt_tracker_live_enable(p->trk, path_cap, phase_cap, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance));
+  PL_CHECK(vbt_tracker_live_enable(p->trk.get(), path_cap, phase_cap, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance));
   p->live = true;
   return VBT_OK;
 }
@@ -1132,7 +1116,7 @@ int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips
   if (!p->live) { set_error("vbt_pipeline_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));   // (inline mode: the tracker stream now waits for the last tracker launch)
-  return vbt_tracker_live_poll(p->trk, flush_view, clips, phases6, cap, (void*)p->trk_stream);
+  return vbt_tracker_live_poll(p->trk.get(), flush_view, clips, phases6, cap, (void*)p->trk_stream);
 }
 
 // One-pass export.  drain() hands every tracker step still held back to its stream - the block of deferred / grouped steps, the
@@ -1146,14 +1130,14 @@ int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_d
   // the table the handle's previous draw may still read.  It runs on the tracker stream, which drain() has put behind the last
   // tracker launch in every placement, after an event behind that draw; ev_trk[last_trk] is recorded again behind it, so `stream`
   // (below) and every later tracker launch (each waits for ev_trk[last_trk], or runs on the tracker stream) come after the update.
-  const bool panel = overlay_hud_follows(o, p->trk);
+  const bool panel = overlay_hud_follows(o, p->trk.get());
   if (panel) {
     PL_CHECK(overlay_hud_follow_enqueue(o, p->trk_stream));
     const int e = p->last_trk >= 0 ? p->last_trk : 0;
-    VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e], p->trk_stream));
+    VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e].get(), p->trk_stream));
     p->last_trk = e;
   }
-  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, p->ev_trk[p->last_trk], 0));
+  if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, p->ev_trk[p->last_trk].get(), 0));
   PL_CHECK(vbt_overlay_follow_update(o, stream));
   PL_CHECK(vbt_overlay_draw(o, frames_dev, B, frame0, frame_step, stream));
   if (panel) PL_CHECK(overlay_hud_follow_drawn(o, (hipStream_t)stream));
@@ -1182,8 +1166,8 @@ int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
   return VBT_OK;
 }
 
-vbt_model* vbt_pipeline_model(vbt_pipeline* p, int k) { return (p && k >= 0 && k < p->depth) ? p->models[(size_t)k] : nullptr; }
-vbt_tracker* vbt_pipeline_tracker(vbt_pipeline* p) { return p ? p->trk : nullptr; }
+vbt_model* vbt_pipeline_model(vbt_pipeline* p, int k) { return (p && k >= 0 && k < p->depth) ? p->models[(size_t)k].get() : nullptr; }
+vbt_tracker* vbt_pipeline_tracker(vbt_pipeline* p) { return p ? p->trk.get() : nullptr; }
 
 int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device, int T, int src_h, int src_w, int swap_rb, int frame_stride,
                    int64_t* id, double* cols7, int cap, int* n_rows) {
@@ -1219,41 +1203,7 @@ int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device,
     }
   }
   PL_CHECK(vbt_pipeline_finish(p));
-  return vbt_tracker_rows(p->trk, 0, id, cols7, cap, n_rows);
-}
-
-int vbt_host_alloc(size_t bytes, void** out) {
-  if (!out || bytes == 0) { set_error("vbt_host_alloc: bad argument"); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipHostMalloc(out, bytes, hipHostMallocDefault));
-  return VBT_OK;
-}
-int vbt_host_free(void* ptr) {
-  if (ptr) VBT_HIP_CHECK(hipHostFree(ptr));
-  return VBT_OK;
-}
-int vbt_device_alloc(int device, size_t bytes, void** out) {
-  if (!out || bytes == 0) { set_error("vbt_device_alloc: bad argument"); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipSetDevice(device));
-  VBT_HIP_CHECK(hipMalloc(out, bytes));
-  return VBT_OK;
-}
-int vbt_device_free(void* ptr) {
-  if (ptr) VBT_HIP_CHECK(hipFree(ptr));
-  return VBT_OK;
-}
-int vbt_memcpy(void* dst, const void* src, size_t bytes, int kind) {
-  if (!dst || !src || kind < 0 || kind > 1) { set_error("vbt_memcpy: bad argument"); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipMemcpy(dst, src, bytes, kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
-  return VBT_OK;
-}
-int vbt_stream_synchronize(void* stream) {
-  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  return VBT_OK;
-}
-int vbt_device_synchronize(int device) {
-  VBT_HIP_CHECK(hipSetDevice(device));
-  VBT_HIP_CHECK(hipDeviceSynchronize());
-  return VBT_OK;
+  return vbt_tracker_rows(p->trk.get(), 0, id, cols7, cap, n_rows);
 }
 
 }  // extern "C"

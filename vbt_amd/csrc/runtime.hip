@@ -1,5 +1,5 @@
 // Library-wide plumbing of libvbt_hip.so, used by every unit: the per-thread error text, the device check, the per-device opt-in for more
-// than 64 KB of dynamic LDS, and the streams the library hands to its callers.  (roctx ranges: frames.hip.)
+// than 64 KB of dynamic LDS, and the streams and the memory the library hands to its callers.  (roctx ranges: frames.hip.)
 #include <chrono>
 
 #include "common.h"
@@ -91,6 +91,42 @@ int vbt_streams_share_queue(void* a, void* b, int us, int* shared) {
 int vbt_stream_destroy(void* stream) {
   if (!stream) return VBT_OK;
   VBT_HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
+  return VBT_OK;
+}
+
+// Memory and synchronisation for callers without a framework.  What vbt_host_alloc and vbt_device_alloc give belongs to the caller until
+// it hands it back: no owner of dev_mem.h can hold it.
+int vbt_host_alloc(size_t bytes, void** out) {
+  if (!out || bytes == 0) { set_error("vbt_host_alloc: bad argument"); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  return VBT_OK;
+}
+int vbt_host_free(void* ptr) {
+  if (ptr) VBT_HIP_CHECK(hipHostFree(ptr));
+  return VBT_OK;
+}
+int vbt_device_alloc(int device, size_t bytes, void** out) {
+  if (!out || bytes == 0) { set_error("vbt_device_alloc: bad argument"); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipSetDevice(device));
+  VBT_HIP_CHECK(hipMalloc(out, bytes));
+  return VBT_OK;
+}
+int vbt_device_free(void* ptr) {
+  if (ptr) VBT_HIP_CHECK(hipFree(ptr));
+  return VBT_OK;
+}
+int vbt_memcpy(void* dst, const void* src, size_t bytes, int kind) {
+  if (!dst || !src || kind < 0 || kind > 1) { set_error("vbt_memcpy: bad argument"); return VBT_ERR_ARG; }
+  VBT_HIP_CHECK(hipMemcpy(dst, src, bytes, kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+  return VBT_OK;
+}
+int vbt_stream_synchronize(void* stream) {
+  VBT_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return VBT_OK;
+}
+int vbt_device_synchronize(int device) {
+  VBT_HIP_CHECK(hipSetDevice(device));
+  VBT_HIP_CHECK(hipDeviceSynchronize());
   return VBT_OK;
 }
 

@@ -375,20 +375,20 @@ int vbt_validation_create(int device, const vbt_validation_params* params, vbt_v
   ValTables& D = f->D;
   D.max_rows = p.max_rows; D.max_ref = p.max_ref_rows; D.max_grid = p.max_grid; D.rec_cap = f->rec_cap;
   const size_t N = (size_t)p.max_pairs, T = (size_t)p.max_rows, R = (size_t)p.max_ref_rows, Gn = (size_t)p.max_grid;
-  Carver C;                                                          // the largest upload, at the blob's head
+  FigCarver C;                                                          // the largest upload, at the blob's head
   C.add<uint8_t>(align64(N * sizeof(ValPairIn)) + N * (R * 24 + T * 40));
   const auto sm = C.add<double>(N * T * 4), traj = C.add<double>(N * T * 3), grid = C.add<double>(N * Gn * VAL_GRID);
   const auto stats = C.add<double>(N * VAL_STATS), head = C.add<double>(N * VAL_HEAD);
   const auto ws = C.add<int32_t>(N * D.pts_cap() * 2), pts = C.add<int32_t>(N * D.pts_cap() * CF_PT), cnt = C.add<int32_t>(N * VAL_SERIES);
   const auto recs = C.add<int32_t>(N * (size_t)f->rec_cap * CF_REC), nrec = C.add<int32_t>(N);
-  if (hipMalloc((void**)&f->blob, C.bytes()) != hipSuccess) {
+  if (f->blob.alloc(C.bytes()) != hipSuccess) {
     (void)hipGetLastError();
     set_error("vbt_validation_create: the device cannot give %zu bytes for %d pairs of %d + %d rows and %d grid points", C.bytes(), p.max_pairs, p.max_rows,
               p.max_ref_rows, p.max_grid);
     return VBT_ERR_HIP;
   }
-  D.sm = C.ptr(f->blob, sm); D.traj = C.ptr(f->blob, traj); D.grid = C.ptr(f->blob, grid); D.stats = C.ptr(f->blob, stats); D.head = C.ptr(f->blob, head);
-  D.ws = C.ptr(f->blob, ws); D.pts = C.ptr(f->blob, pts); D.cnt = C.ptr(f->blob, cnt); D.recs = C.ptr(f->blob, recs); D.nrec = C.ptr(f->blob, nrec);
+  D.sm = C.ptr(f->blob.get(), sm); D.traj = C.ptr(f->blob.get(), traj); D.grid = C.ptr(f->blob.get(), grid); D.stats = C.ptr(f->blob.get(), stats); D.head = C.ptr(f->blob.get(), head);
+  D.ws = C.ptr(f->blob.get(), ws); D.pts = C.ptr(f->blob.get(), pts); D.cnt = C.ptr(f->blob.get(), cnt); D.recs = C.ptr(f->blob.get(), recs); D.nrec = C.ptr(f->blob.get(), nrec);
   f->d_recs = D.recs; f->d_nrec = D.nrec;
   *out = f.release();
   return VBT_OK;
@@ -423,10 +423,10 @@ int vbt_validation_set(vbt_validation* f, int n, const int32_t* kinds, double pl
   memcpy(up.data() + pairs_b, ref, T.ref * 24);
   memcpy(up.data() + pairs_b + T.ref * 24, rows, T.rows * 40);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(f->blob, up.data(), up.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(f->blob.get(), up.data(), up.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     ValPrepArgs A{};
-    A.pairs = (const ValPairIn*)f->blob; A.ref = (const double*)(f->blob + pairs_b); A.rows = (const double*)(f->blob + pairs_b + T.ref * 24);
+    A.pairs = (const ValPairIn*)f->blob.get(); A.ref = (const double*)(f->blob.get() + pairs_b); A.rows = (const double*)(f->blob.get() + pairs_b + T.ref * 24);
     A.D = f->D; A.G = f->G; A.plate = plate_diameter; A.rate = rate;
     validation_prepare_kernel<<<dim3((unsigned)n), VAL_THREADS, 0, st>>>(A);
     e = hipGetLastError();
