@@ -137,6 +137,24 @@ typedef struct {
 
 /* rows_cap: capacity of the per-clip row log (rows = emitted (id,time,...) records). */
 int vbt_tracker_create(int n_clips, int rows_cap, const vbt_tracker_params* p, int device, vbt_tracker** out);
+/* The second tracker: sort.tracker.SortTracker, the commented-out alternative of reference track.py:16,156
+ * (`SortTracker(max_age=MAX_AGE)`, sort-track 0.0.8), which made the reference's dfs/ result set.  Plain SORT: the same 7-state
+ * filter, association on IoU alone (no direction term, no second round, no score gate, no class test), z built with r = w / h
+ * (no 1e-6), and rows emitted from the filter's posterior box instead of the observation.  The handle is an ordinary vbt_tracker:
+ * every vbt_tracker_* entry below works on it, the row log and everything that reads it are the same.  The fused entries
+ * (vbt_tracker_update_from_*) still apply their det_threshold (reference odt.py:70-75); SORT itself drops no detection.
+ * id_base: the package's id counter is shared by all trackers of a process (the reference's dfs/ file ids run 1, 3, 7, ..., 94); here
+ * it is a parameter - the ids of every clip start at id_base + 1, and vbt_tracker_reset / _reset_clips keep it.
+ * VBT_ERR_ARG, before any device call: a NULL pointer, n_clips or rows_cap < 1, max_age < 0, min_hits < 0, iou_threshold not
+ * finite, id_base < 0 or above VBT_SORT_MAX_ID_BASE. */
+typedef struct {
+  int32_t max_age;       /* SortTracker default 1; reference track.py:156 -> 30 */
+  int32_t min_hits;      /* SortTracker default 3 */
+  int32_t id_base;       /* ids of a clip start at id_base + 1 (0: the first tracker of a process) */
+  double iou_threshold;  /* SortTracker default 0.3 */
+} vbt_sort_params;
+#define VBT_SORT_MAX_ID_BASE 0x3fffffff /* row ids are id_base + 1 + births so far: half of the int32 range is left to the births */
+int vbt_tracker_create_sort(int n_clips, int rows_cap, const vbt_sort_params* p, int device, vbt_tracker** out);
 void vbt_tracker_destroy(vbt_tracker* t);
 int vbt_tracker_reset(vbt_tracker* t);
 /* A fresh clip in each of the slots clips[0..n): its OC-SORT state cleared (ids restart at 1), its row log empty, its frame counter 0
@@ -310,6 +328,11 @@ typedef struct {
 void vbt_pipeline_default_params(vbt_pipeline_params* p);
 /* fps_host [n_clips]: cap.get(cv2.CAP_PROP_FPS) of every clip (reference track.py:138) */
 int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p, const double* fps_host, vbt_pipeline** out);
+/* The pipeline's clips are tracked by SORT (vbt_tracker_create_sort; reference track.py:16,156) instead of OC-SORT from here on:
+ * vbt_pipeline_params.tracker is ignored, detection_threshold still applies.  Valid only before the first vbt_pipeline_step /
+ * _step_runs / vbt_track_clip of the handle (VBT_ERR_STATE afterwards, a vbt_pipeline_reset does not reopen it); call it before
+ * vbt_pipeline_live_enable.  VBT_ERR_ARG as vbt_tracker_create_sort.  Synchronises the device (the clip states are re-initialised). */
+int vbt_pipeline_use_sort(vbt_pipeline* p, const vbt_sort_params* sp);
 void vbt_pipeline_destroy(vbt_pipeline* p);
 
 /* One frame of every clip: frames = uint8 [n_slots,H,W,3], frame number frame_count + 1 of each clip (track.py:161), time stamp

@@ -23,6 +23,11 @@ class TrackerParams(ctypes.Structure):
                 ("asso", ctypes.c_int32), ("iou_threshold", c_double), ("inertia", c_double), ("det_thresh", c_double)]
 
 
+class SortParams(ctypes.Structure):
+    """vbt_sort_params (include/vbt_hip.h): SortTracker(max_age, min_hits, iou_threshold) + the id counter's start"""
+    _fields_ = [("max_age", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("id_base", ctypes.c_int32), ("iou_threshold", c_double)]
+
+
 class Run(ctypes.Structure):
     """vbt_run (include/vbt_hip.h): a run of consecutive frames of one clip inside a detector batch."""
     _fields_ = [("clip", ctypes.c_int32), ("slot0", ctypes.c_int32), ("slot_stride", ctypes.c_int32), ("n_frames", ctypes.c_int32),
@@ -152,8 +157,10 @@ _SIGS = {
     "vbt_model_profile_steps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(StepTime), c_int, ctypes.POINTER(c_int)]),
     "vbt_model_profile_overlap": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_tracker_create": (c_int, [c_int, c_int, ctypes.POINTER(TrackerParams), c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_tracker_create_sort": (c_int, [c_int, c_int, ctypes.POINTER(SortParams), c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_pipeline_use_sort": (c_int, [c_void_p, ctypes.POINTER(SortParams)]),
     "vbt_tracker_destroy": (None, [c_void_p]),
-    "vbt_tracker_reset": (c_int, [c_void_p]),
+    "vbt_tracker_reset":(c_int, [c_void_p]),
     "vbt_tracker_reset_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_tracker_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_tracker_update_from_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),

@@ -1,7 +1,7 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
-                            [--live] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
+                            [--live] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
                             [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
@@ -13,6 +13,8 @@
       --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
       list that changes afterwards (the leading id changes, or a larger rep makes the filter drop small ones) is announced with a
       "revised" line and reprinted from the first rep that differs.  The reps standing at the end are those `analyze` prints.
+      --tracker sort: SortTracker(max_age=30), the commented-out alternative of reference track.py:16,156 (it made the reference's
+      dfs/ frames), instead of OCSort (track.py:157, the default); the file name rule and every other option are the same.
       --concurrent N > 1: all files through one pipeline, N clips side by side (a finished clip's tracker slot takes the next
       file); the same files and lines as N = 1, in input order.  Not with --live.
       --pix_fmt nv12|i420 --size 1920x1080: SRC is a headerless raw video file, YUV 4:2:0 as a decoder emits it (what
@@ -216,6 +218,9 @@ def _raw_size(pix_fmt, size):
 @click.option("--frame_stride", default=1, show_default=True, type=int, help="16 reproduces `frame_count %% 16` of reference track.py:166.")
 @click.option("--time_batch", default=64, show_default=True, type=int, help="Consecutive frames of the clip per detector batch (1 = one frame per step).")
 @click.option("--live", is_flag=True, default=False, help="Print each concentric rep (ROM, ACV) as soon as it is complete.")
+@click.option("--tracker", default="ocsort", show_default=True, type=click.Choice(["ocsort", "sort"]),
+              help="ocsort: OCSort(max_age=30, asso_func='diou', iou_threshold=0.1) of reference track.py:157; sort: SortTracker(max_age=30), its "
+                   "commented-out alternative (track.py:156), which made the reference's dfs/ frames.  Every other option works with either.")
 @click.option("--concurrent", default=1, show_default=True, type=int,
               help="Clips tracked side by side in one pipeline (a finished clip's tracker slot takes the next file); 1 = one pipeline per file.")
 @click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420"]),
@@ -235,8 +240,8 @@ def _raw_size(pix_fmt, size):
               help="With --one_pass: the rep panel fed by the live rep analysis on the GPU - the reps appear on the video as they complete "
                    "(uses --plate_diameter, --hud_scale, --hud_pos; not with --hud or --concurrent above 1).")
 @_hud_options
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, concurrent, pix_fmt, size, video_dir, video_format, video_quality,
-          mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos):
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, tracker, concurrent, pix_fmt, size, video_dir, video_format,
+          video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos):
     from ._lib import VbtArgError
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
@@ -266,14 +271,14 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter)
+                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter, tracker)
     default_fps = fps
     for s in src:
         frames = _open_source(s, pix_fmt, size, mjpeg_entropy)
         fps = _source_fps(frames, default_fps, fps_given)
         if hud_params is not None:                                       # the panel shows the finished analysis: render after tracking
             data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt)
+                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, tracker=tracker)
             line, phases = _export_line(data, s, model, df_dir, plate_diameter)
             _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params)
             click.echo(line)
@@ -286,7 +291,7 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
             try:
                 data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
                                     live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink,
-                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live)
+                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker)
             except VbtArgError as e:                                     # a panel the library refuses (outside the frame, odd origin in a YUV frame)
                 if hud_live is None or "vbt_overlay_hud_follow" not in str(e):
                     raise
@@ -386,7 +391,7 @@ def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, 
 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
-                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45):
+                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45, tracker="ocsort"):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -401,7 +406,7 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     lines, nxt = {}, 0
     fps = [_source_fps(a, fps, fps_given) for a in sources] or fps
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
-                              time_batch=time_batch, pix_fmt=pix_fmt):
+                              time_batch=time_batch, pix_fmt=pix_fmt, tracker=tracker):
         s = src[i]
         if hud_params is None and video_dir is not None:                 # the clip is finished: its rows are all the renderer needs
             _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size)

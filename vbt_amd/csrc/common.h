@@ -69,6 +69,12 @@ int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips);
 // (device, [n_clips][rows_cap] 64-byte rows), then a fresh clip in every listed slot (vbt_tracker_reset_clips)
 int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
                         unsigned char* head, void* out_rows, hipStream_t st);
+// The SORT tracker's parameters as vbt_tracker_create_sort takes them (tracker.hip): VBT_ERR_ARG with the text set for what it
+// refuses; no device call (who: the caller's name)
+int check_sort_params(const char* who, const vbt_sort_params* sp);
+// An unstepped tracker becomes a SORT tracker (vbt_pipeline_use_sort): parameters checked, clip states re-initialised with id_base.
+// VBT_ERR_STATE when it has been stepped.  Synchronises the device.
+int tracker_use_sort(vbt_tracker* t, const vbt_sort_params* sp);
 
 // The pipeline's side of a rep panel that follows the live analysis (overlay.hip; vbt_pipeline_overlay_draw is their one caller).
 // Does the handle's panel follow a clip of tracker t?

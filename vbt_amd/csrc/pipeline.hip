@@ -70,7 +70,8 @@ struct vbt_pipeline {
   std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
   int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
-  int G = 1;                       // steps per forward (vbt_pipeline_params.group)
+  bool ever_stepped = false;       // a step was enqueued on this handle (not cleared by a reset): vbt_pipeline_use_sort comes too late
+  int G = 1;                      // steps per forward (vbt_pipeline_params.group)
   int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step (a block never wraps); forwards opened since creation / reset
   int last_o = 0, last_k = 0;      // ring slot / forward slot of the most recent step
   int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
@@ -524,6 +525,7 @@ int begin_step(vbt_pipeline* p, int o, int k, bool wait, bool counts_frame, cons
     p->next_o = o + 1 + p->G > p->ring ? 0 : o + 1;
   }
   p->step_idx++;
+  p->ever_stepped = true;
   if (counts_frame) p->frame_count++;
   p->last_o = o;
   p->last_k = k;
@@ -1109,6 +1111,13 @@ int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap) {
   PL_CHECK(vbt_tracker_live_enable(p->trk.get(), path_cap, phase_cap, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance));
   p->live = true;
   return VBT_OK;
+}
+
+int vbt_pipeline_use_sort(vbt_pipeline* p, const vbt_sort_params* sp) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  PL_CHECK(check_sort_params("vbt_pipeline_use_sort", sp));
+  if (p->ever_stepped) { set_error("vbt_pipeline_use_sort: steps were enqueued on this pipeline (choose the tracker before the first step)"); return VBT_ERR_STATE; }
+  return tracker_use_sort(p->trk.get(), sp);
 }
 
 int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap) {

@@ -1,5 +1,7 @@
 // On-device OC-SORT tracker and row assembly for gfx950 (MI355X): the step kernels, the handle, the per-clip read-backs.  The step itself
 // is ocsort_step.h; export id selection + rep analysis at the clip close are tracker_analysis.hip, the live rep analysis tracker_live.hip.
+// A handle made by vbt_tracker_create_sort steps sort_step.h instead - SortTracker, the reference's commented-out alternative
+// (track.py:16,156) - on the same state, row log and kernels (templates on the algorithm); everything else in this file is shared.
 //
 // Replaces, per clip (reference track.py:157-234, plot.py:33-47,87-95):
 //   ocsort.OCSort(max_age=30, asso_func="diou", iou_threshold=0.1).update(dets, [])   track.py:157,186
@@ -16,6 +18,8 @@
 //   The 7-state SORT filter decouples into three (position, velocity) 2x2 filters (cx, cy, s) and a
 // scalar one (r): F/H/Q/R never couple them, so the dense 7x7 products of the numpy formulation
 // reduce EXACTLY (same roundings; the dropped terms are exact zeros) to the closed forms below.
+#include <cmath>
+
 #include "common.h"
 #include "tracker_host.h"
 
@@ -38,6 +42,7 @@ static_assert(CLOSED_HEAD_BYTES == 16 + (size_t)MAXPH * 48, "slot close record (
 }  // namespace vbt
 
 #include "ocsort_step.h"
+#include "sort_step.h"
 
 namespace vbt {
 
@@ -50,7 +55,23 @@ __device__ __forceinline__ int put_host_detections(StepShared& sh, const double 
   return m;
 }
 
+// The step kernels below exist once per algorithm, selected at compile time: SORT = false walks ocsort_step (OCSort, track.py:157),
+// SORT = true sort_step (SortTracker, track.py:16,156).  The handle's `sort` flag picks the instantiation at every launch.
+template <bool SORT>
+__device__ __forceinline__ void clip_step(ClipState& st, Row* rows, int rows_cap, StepShared& sh, int nd, double time, const TrackParams& p,
+                                          double q44, double q66, int lane) {
+  if constexpr (SORT) sort_step(st, rows, rows_cap, sh, nd, time, p, q44, q66, lane);
+  else ocsort_step(st, rows, rows_cap, sh, nd, time, p, q44, q66, lane);
+}
+// host-provided detections of a frame -> the detection list, by one lane (OC-SORT gates them by score, SORT takes all)
+template <bool SORT>
+__device__ __forceinline__ int put_host(StepShared& sh, const double (*d)[6], int n, double det_thresh) {
+  if constexpr (SORT) return put_host_detections_all(sh, d, n);
+  else return put_host_detections(sh, d, n, det_thresh);
+}
+
 // Frames come either as double detections (host-provided, OCSort.update call shape) ...
+template <bool SORT>
 __global__ __launch_bounds__(64) void tracker_kernel(ClipState* states, Row* rows, int rows_cap, const double* dets,
                                                      const int* counts, const double* times, int F, int nclips, TrackParams p,
                                                      double q44, double q66) {
@@ -63,9 +84,9 @@ __global__ __launch_bounds__(64) void tracker_kernel(ClipState* states, Row* row
     if (n <= 0) continue;  // reference track.py:180-181: the tracker is not stepped on empty frames
     const double* d = dets + ((size_t)f * nclips + clip) * MAXD * 6;
     __syncthreads();
-    if (lane == 0) sh.flag = put_host_detections(sh, (const double (*)[6])d, n, p.det_thresh);
+    if (lane == 0) sh.flag = put_host<SORT>(sh, (const double (*)[6])d, n, p.det_thresh);
     __syncthreads();
-    ocsort_step(st, myrows, rows_cap, sh, sh.flag, times[(size_t)f * nclips + clip], p, q44, q66, lane);
+    clip_step<SORT>(st, myrows, rows_cap, sh, sh.flag, times[(size_t)f * nclips + clip], p, q44, q66, lane);
   }
 }
 
@@ -80,14 +101,15 @@ struct OneFrameArg {
   int n;
 };
 constexpr int VIEW_DOUBLES = 2 + MAXD * 9 + MAXT * 8;   // last_n, ntrk | last_out[25][9] | per tracker: id, x[7]
+template <bool SORT>
 __global__ __launch_bounds__(64) void tracker_one_kernel(ClipState* states, Row* rows, int rows_cap, int clip, OneFrameArg a, TrackParams p,
                                                          double q44, double q66, double* view) {
   __shared__ StepShared sh;
   const int lane = threadIdx.x;
   ClipState& st = states[clip];
-  if (lane == 0) sh.flag = put_host_detections(sh, a.det, a.n, p.det_thresh);
+  if (lane == 0) sh.flag = put_host<SORT>(sh, a.det, a.n, p.det_thresh);
   __syncthreads();
-  ocsort_step(st, rows + (size_t)clip * rows_cap, rows_cap, sh, sh.flag, a.time, p, q44, q66, lane);
+  clip_step<SORT>(st, rows + (size_t)clip * rows_cap, rows_cap, sh, sh.flag, a.time, p, q44, q66, lane);
   __syncthreads();
   if (lane == 0) { view[0] = (double)st.last_n; view[1] = (double)st.ntrk; }
   for (int i = lane; i < MAXD * 9; i += 64) view[2 + i] = (&st.last_out[0][0])[i];
@@ -110,6 +132,7 @@ struct StepMeta {
   double time[META_SLOTS];
   int clip[META_SLOTS];
 };
+template <bool SORT>
 __global__ __launch_bounds__(64) void tracker_from_det_kernel(ClipState* states, Row* rows, int rows_cap, const float* boxes,
                                                               const float* scores, const int* counts, StepMeta meta, int slot0,
                                                               float det_threshold, TrackParams p, double q44, double q66) {
@@ -122,7 +145,7 @@ __global__ __launch_bounds__(64) void tracker_from_det_kernel(ClipState* states,
   const int nd = load_slot_detections(sh, boxes, scores, counts, slot, det_threshold, p.det_thresh, lane);
   __syncthreads();
   if (nd < 0) return;
-  ocsort_step(st, rows + (size_t)clip * rows_cap, rows_cap, sh, nd, frame_time, p, q44, q66, lane);
+  clip_step<SORT>(st, rows + (size_t)clip * rows_cap, rows_cap, sh, nd, frame_time, p, q44, q66, lane);
 }
 
 // Time-batched form (the reference's unit of work is ONE video, track.py:85-126,159-247): the detector batch holds RUNS of
@@ -142,6 +165,7 @@ struct SeqMeta {
 // tracks (a few KB) are copied in once and written back once, and every Kalman / association step in between works on LDS
 // instead of on dependent global round trips (one clip alone: 21 us -> see DESIGN.md per frame).
 constexpr int SEQ_LDS_MIN = 6;
+template <bool SORT>
 __global__ __launch_bounds__(64) void tracker_seq_kernel(ClipState* states, Row* rows, int rows_cap, const float* boxes,
                                                          const float* scores, const int* counts, SeqMeta meta,
                                                          float det_threshold, TrackParams p, double q44, double q66, int lds_state) {
@@ -174,7 +198,7 @@ __global__ __launch_bounds__(64) void tracker_seq_kernel(ClipState* states, Row*
       cur = nxt;
       if (nd < 0) continue;
       const double frame_time = (double)(r.frame0 + f * r.frame_step) / r.fps;
-      ocsort_step(state, myrows, rows_cap, sh, nd, frame_time, p, q44, q66, lane);
+      clip_step<SORT>(state, myrows, rows_cap, sh, nd, frame_time, p, q44, q66, lane);
     }
   };
   if (cached) walk(*(ClipState*)seq_dyn);
@@ -185,17 +209,17 @@ __global__ __launch_bounds__(64) void tracker_seq_kernel(ClipState* states, Row*
   }
 }
 
-__global__ void init_states_kernel(ClipState* states, int n) {
+__global__ void init_states_kernel(ClipState* states, int n, int id_base) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  init_state(states[i]);
+  init_state(states[i], id_base);
 }
 
 // A fresh clip in every listed slot (vbt_tracker_reset_clips), one workgroup per listed clip: its ClipState as init_states_kernel leaves it
 // and - live analysis on (clips != nullptr) - its LiveClip and LIVE_ENTRIES entries as live_init_kernel leaves them.
-__global__ __launch_bounds__(64) void reset_clips_kernel(ClipState* states, LiveClip* clips, LiveEntry* ents, ClipList l) {
+__global__ __launch_bounds__(64) void reset_clips_kernel(ClipState* states, LiveClip* clips, LiveEntry* ents, ClipList l, int id_base) {
   const int clip = l.clip[blockIdx.x], lane = threadIdx.x;
-  if (lane == 0) init_state(states[clip]);
+  if (lane == 0) init_state(states[clip], id_base);
   if (!clips) return;
   if (lane == 0) live_clip_init(clips[clip]);
   for (int e = lane; e < LIVE_ENTRIES; e += 64) live_entry_free(ents[(size_t)clip * LIVE_ENTRIES + e]);
@@ -216,6 +240,28 @@ int vbt::fetch_state_headers(vbt_tracker* t, std::vector<StateHeader>* h, hipStr
                                  hipMemcpyDeviceToHost, st));
   VBT_HIP_CHECK(hipStreamSynchronize(st));
   return VBT_OK;
+}
+
+int vbt::check_sort_params(const char* who, const vbt_sort_params* sp) {
+  if (!sp) { set_error("%s: NULL parameters", who); return VBT_ERR_ARG; }
+  if (sp->max_age < 0 || sp->min_hits < 0) { set_error("%s: max_age and min_hits must be >= 0", who); return VBT_ERR_ARG; }
+  if (!std::isfinite(sp->iou_threshold)) { set_error("%s: iou_threshold must be finite", who); return VBT_ERR_ARG; }
+  if (sp->id_base < 0 || sp->id_base > VBT_SORT_MAX_ID_BASE) { set_error("%s: id_base must be in [0, %d]", who, VBT_SORT_MAX_ID_BASE); return VBT_ERR_ARG; }
+  return VBT_OK;
+}
+
+int vbt::tracker_use_sort(vbt_tracker* t, const vbt_sort_params* sp) {
+  if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
+  if (int rc = check_sort_params("SORT parameters", sp)) return rc;
+  if (t->stepped) { set_error("the tracker has been stepped: its algorithm is fixed"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  t->sort = true;
+  t->id_base = sp->id_base;
+  t->p = TrackParams{};
+  t->p.max_age = sp->max_age; t->p.min_hits = sp->min_hits; t->p.iou_thr = sp->iou_threshold;
+  t->p.delta_t = 1;                      // (unused by sort_step)
+  t->p.det_thresh = -HUGE_VAL;           // no score gate: put_slot_detections keeps every detection at or above det_threshold
+  return vbt_tracker_reset(t);           // clip states with next_id = id_base
 }
 
 int vbt::check_state_header(const vbt_tracker* t, int clip, const StateHeader& h, int cap) {
@@ -288,9 +334,23 @@ int vbt_tracker_create(int n_clips, int rows_cap, const vbt_tracker_params* prm,
                        : no(t->view.reserve(sizeof(double) * VIEW_DOUBLES))   ? (t->view.dev() ? "pinned view" : "view")
                                                                               : nullptr;
   if (failed) { set_error("hipMalloc failed for %s", failed); return VBT_ERR_HIP; }
-  init_states_kernel<<<(n_clips + 63) / 64, 64>>>(t->states.get(), n_clips);
+  init_states_kernel<<<(n_clips + 63) / 64, 64>>>(t->states.get(), n_clips, t->id_base);
   VBT_HIP_CHECK(hipDeviceSynchronize());
   *out = t.release();
+  return VBT_OK;
+}
+
+int vbt_tracker_create_sort(int n_clips, int rows_cap, const vbt_sort_params* sp, int device, vbt_tracker** out) {
+  if (!out || !sp || n_clips < 1 || rows_cap < 1) { set_error("vbt_tracker_create_sort: bad argument"); return VBT_ERR_ARG; }
+  *out = nullptr;
+  if (int rc = check_sort_params("vbt_tracker_create_sort", sp)) return rc;
+  // the handle, its buffers and fresh clip states are those of any tracker; then the algorithm and its parameters
+  const vbt_tracker_params base = {sp->max_age, sp->min_hits, 1, 0, sp->iou_threshold, 0.0, 0.0};
+  vbt_tracker* t = nullptr;
+  if (int rc = vbt_tracker_create(n_clips, rows_cap, &base, device, &t)) return rc;
+  std::unique_ptr<vbt_tracker> owner(t);
+  if (int rc = tracker_use_sort(t, sp)) return rc;
+  *out = owner.release();
   return VBT_OK;
 }
 
@@ -298,7 +358,7 @@ void vbt_tracker_destroy(vbt_tracker* t) { delete t; }
 
 int vbt_tracker_reset(vbt_tracker* t) {
   if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
-  init_states_kernel<<<(t->n_clips + 63) / 64, 64>>>(t->states.get(), t->n_clips);
+  init_states_kernel<<<(t->n_clips + 63) / 64, 64>>>(t->states.get(), t->n_clips, t->id_base);
   if (t->live) live_init(t);
   VBT_HIP_CHECK(hipDeviceSynchronize());
   t->finished = false;
@@ -314,7 +374,7 @@ int vbt_tracker_reset_clips(vbt_tracker* t, const int32_t* clips, int n, void* s
   hipStream_t st = (hipStream_t)stream;
   for (int i0 = 0; i0 < n; i0 += CLIP_LIST) {
     const ClipList l = clip_list(clips, i0, n);
-    reset_clips_kernel<<<l.n, 64, 0, st>>>(t->states.get(), t->live ? t->lb.clips : nullptr, t->live ? t->lb.ents : nullptr, l);
+    reset_clips_kernel<<<l.n, 64, 0, st>>>(t->states.get(), t->live ? t->lb.clips : nullptr, t->live ? t->lb.ents : nullptr, l, t->id_base);
   }
   VBT_HIP_CHECK(hipGetLastError());
   t->view_clip = -1;
@@ -332,7 +392,8 @@ int vbt_tracker_update(vbt_tracker* t, const double* dets, const int32_t* counts
     a.n = std::min((int)counts[0], MAXD);
     a.time = times[0];
     memcpy(a.det, dets, sizeof(double) * 6 * a.n);
-    tracker_one_kernel<<<1, 64, 0, nullptr>>>(t->states.get(), t->rows.get(), t->rows_cap, 0, a, t->p, t->q44, t->q66, (double*)t->view.dev());
+    (t->sort ? tracker_one_kernel<true> : tracker_one_kernel<false>)<<<1, 64, 0, nullptr>>>(t->states.get(), t->rows.get(), t->rows_cap, 0, a, t->p, t->q44, t->q66,
+                                                                                              (double*)t->view.dev());
     VBT_HIP_CHECK(hipGetLastError());
     if (int rc = live_after(t, nullptr)) return rc;
     VBT_HIP_CHECK(t->view.fetch(sizeof(double) * VIEW_DOUBLES, nullptr));
@@ -349,7 +410,8 @@ int vbt_tracker_update(vbt_tracker* t, const double* dets, const int32_t* counts
   VBT_HIP_CHECK(hipMemcpy(dd.get(), dets, nd * MAXD * 6 * sizeof(double), hipMemcpyHostToDevice));
   VBT_HIP_CHECK(hipMemcpy(dc.get(), counts, nd * sizeof(int), hipMemcpyHostToDevice));
   VBT_HIP_CHECK(hipMemcpy(dt.get(), times, nd * sizeof(double), hipMemcpyHostToDevice));
-  tracker_kernel<<<t->n_clips, 64>>>(t->states.get(), t->rows.get(), t->rows_cap, dd.get(), dc.get(), dt.get(), F, t->n_clips, t->p, t->q44, t->q66);
+  (t->sort ? tracker_kernel<true> : tracker_kernel<false>)<<<t->n_clips, 64>>>(t->states.get(), t->rows.get(), t->rows_cap, dd.get(), dc.get(), dt.get(), F, t->n_clips,
+                                                                               t->p, t->q44, t->q66);
   const int lrc = live_after(t, nullptr);
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) { set_error("tracker kernel failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
@@ -370,8 +432,8 @@ static int launch_steps(vbt_tracker* t, const float* boxes_dev, const float* sco
       meta.time[i] = times[s0 + i];
       meta.clip[i] = clip_of_slot ? clip_of_slot[s0 + i] : s0 + i;
     }
-    tracker_from_det_kernel<<<nb, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, boxes_dev, scores_dev, counts_dev, meta, s0,
-                                               det_threshold, t->p, t->q44, t->q66);
+    (t->sort ? tracker_from_det_kernel<true> : tracker_from_det_kernel<false>)<<<nb, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, boxes_dev, scores_dev,
+                                                                                                 counts_dev, meta, s0, det_threshold, t->p, t->q44, t->q66);
   }
   VBT_HIP_CHECK(hipGetLastError());
   if (int rc = live_after(t, st)) return rc;
@@ -441,15 +503,16 @@ int vbt_tracker_update_from_detections_seq(vbt_tracker* t, const float* boxes_de
     int lds_state = (longest >= lds_min && !lds_off) ? lds_min : 0;
     if (lds_state) {
       // opt in to the dynamic LDS of the cached state once per device; if the runtime refuses, the walk works on global memory
-      static int attr_state[64] = {0};   // per device: 0 = not tried, 1 = granted, -1 = refused
+      static int attr_state[2][64] = {{0}};   // per algorithm and device: 0 = not tried, 1 = granted, -1 = refused
       const int di = t->device < 64 ? t->device : 63;
-      if (attr_state[di] == 0)
-        attr_state[di] = hipFuncSetAttribute(reinterpret_cast<const void*>(&tracker_seq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)sizeof(ClipState)) == hipSuccess ? 1 : -1;
-      if (attr_state[di] < 0) lds_state = 0;
+      int& as = attr_state[t->sort ? 1 : 0][di];
+      if (as == 0)
+        as = hipFuncSetAttribute(t->sort ? reinterpret_cast<const void*>(&tracker_seq_kernel<true>) : reinterpret_cast<const void*>(&tracker_seq_kernel<false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ClipState)) == hipSuccess ? 1 : -1;
+      if (as < 0) lds_state = 0;
     }
-    tracker_seq_kernel<<<nb, 64, lds_state ? sizeof(ClipState) : 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, boxes_dev, scores_dev, counts_dev, meta,
-                                                                           det_threshold, t->p, t->q44, t->q66, lds_state);
+    (t->sort ? tracker_seq_kernel<true> : tracker_seq_kernel<false>)<<<nb, 64, lds_state ? sizeof(ClipState) : 0, st>>>(
+        t->states.get(), t->rows.get(), t->rows_cap, boxes_dev, scores_dev, counts_dev, meta, det_threshold, t->p, t->q44, t->q66, lds_state);
   }
   VBT_HIP_CHECK(hipGetLastError());
   if (int rc = live_after(t, st)) return rc;

@@ -10,6 +10,8 @@
 struct vbt_tracker {
   int n_clips = 0, rows_cap = 0, device = 0;
   vbt::TrackParams p;
+  bool sort = false;                     // the step is sort_step (vbt_tracker_create_sort), not ocsort_step
+  int id_base = 0;                       // row ids of a fresh clip start at id_base + 1 (SORT only; 0 for OC-SORT)
   double q44 = 0, q66 = 0;
   vbt::DevBuf<vbt::ClipState> states;
   vbt::DevBuf<vbt::Row> rows;

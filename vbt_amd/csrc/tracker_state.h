@@ -47,8 +47,9 @@ struct TrackParams {
   double iou_thr, inertia, det_thresh;
 };
 
-__device__ inline void init_state(ClipState& st) {
-  st.ntrk = 0; st.frame_count = 0; st.next_id = 0; st.overflow = 0; st.nrows = 0; st.rows_overflow = 0;
+// id_base: the first track of the clip gets row id id_base + 1 (0 for OC-SORT; vbt_sort_params.id_base for SORT)
+__device__ inline void init_state(ClipState& st, int id_base = 0) {
+  st.ntrk = 0; st.frame_count = 0; st.next_id = id_base; st.overflow = 0; st.nrows = 0; st.rows_overflow = 0;
   st.best_id = -1; st.last_n = 0; st.best_cum = -1.0; st.used = 0ull;
 }
 

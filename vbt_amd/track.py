@@ -23,14 +23,27 @@ from .odt import (calc_bounding_box_center, calc_plate_height, calc_plate_width,
 
 MAX_AGE = 30                                   # reference track.py:22
 COLUMNS = ("id", "time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
+TRACKERS = ("ocsort", "sort")                  # reference track.py:157 (the default everywhere) and its commented-out alternative, track.py:156
 
 
-def track(src, interpreter, detection_treshold=0.5, display_image_height=720, video_path=None, fps=30.0, frame_stride=1):
+def _tracker_name(tracker):
+    if tracker not in TRACKERS:
+        raise ValueError(f"tracker must be one of {TRACKERS} (got {tracker!r})")
+    return tracker
+
+
+def track(src, interpreter, detection_treshold=0.5, display_image_height=720, video_path=None, fps=30.0, frame_stride=1, tracker="ocsort"):
     """Per-frame loop of reference track.py:159-234 with the reference's object call shapes.
     src: iterable of RGB uint8 frames.  frame_stride=16 reproduces `frame_count % 16` of the
-    snapshot (track.py:166); the committed DataFrames were made with stride 1."""
+    snapshot (track.py:166); the committed DataFrames were made with stride 1.
+    tracker: "ocsort" = OCSort(max_age=MAX_AGE, asso_func="diou", iou_threshold=0.1) of track.py:157, "sort" = SortTracker(max_age=MAX_AGE)
+    of track.py:156."""
     data = {k: [] for k in COLUMNS}
-    tracker = OCSort(max_age=MAX_AGE, asso_func="diou", iou_threshold=0.1)
+    if _tracker_name(tracker) == "sort":
+        from .sort import SortTracker
+        tracker = SortTracker(max_age=MAX_AGE)
+    else:
+        tracker = OCSort(max_age=MAX_AGE, asso_func="diou", iou_threshold=0.1)
     frame_count = 0
     for frame in src:
         frame_count += 1
@@ -65,7 +78,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None, tracker="ocsort"):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -86,13 +99,14 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     hud_live (with one_pass and an export): a dict - the live rep panel on every exported frame (include/vbt_hip.h, "Rep panel from the
     live analysis"): live rep analysis is switched on (with or without `live`), the panel follows the clip on the device and shows,
     on every frame of a batch, the leader's reps as they stand after that batch.  Keys: plate_diameter (default 0.45, the live
-    analysis runs with it) and the panel's x, y, scale, full_scale_cm, bg.  The rows are those of a run without it."""
+    analysis runs with it) and the panel's x, y, scale, full_scale_cm, bg.  The rows are those of a run without it.
+    tracker: "ocsort" (default) or "sort" = SortTracker(max_age=30) of track.py:156; everything above reads the row log and works with either."""
     if hud_live is not None and not (one_pass and (video_out is not None or video_sink is not None)):
         raise ValueError("track_frames: hud_live draws on a one-pass export (one_pass=True with video_out or video_sink)")
     if one_pass and (video_out is not None or video_sink is not None):
         return _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw,
-                             export=(video_out, video_sink, video_quality), hud_live=hud_live)
-    data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw)
+                             export=(video_out, video_sink, video_quality), hud_live=hud_live, tracker=tracker)
+    data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, tracker=tracker)
     if video_out is not None:
         from .overlay import render
         render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device)
@@ -102,7 +116,8 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return data
 
 
-def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None, hud_live=None):
+def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None, hud_live=None,
+                  tracker="ocsort"):
     """export: None, or (video_out, video_sink, video_quality) of a one-pass export; hud_live: None, or the live rep panel's dict"""
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
@@ -114,7 +129,7 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
     hud_live = None if hud_live is None else dict(hud_live)
     plate = {} if hud_live is None else dict(plate_diameter=float(hud_live.pop("plate_diameter", 0.45)))   # the live analysis uses the pipeline's
     pipe = Pipeline(model_path, F, max_frames=max(kept, 1), fps=fps, detection_treshold=detection_treshold, device=device,
-                    rows_per_frame=25, tracker_clips=1, **plate)
+                    rows_per_frame=25, tracker_clips=1, tracker=tracker, **plate)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
     src_hw = None if (H, W) == (size, size) and not is_yuv(pix_fmt) else (H, W)
@@ -202,12 +217,13 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
     return pipe.rows(0)
 
 
-def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, pix_fmt="rgb24"):
+def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, pix_fmt="rgb24",
+               tracker="ocsort"):
     """track_frames() for many clips through ONE pipeline: `concurrent` tracker slots, `time_batch` detector slots per step.  Each
     step hands runs of consecutive frames to the open clips (shard.stream_schedule); a clip whose frames are used up is closed in its
     slot (Pipeline.close_clips) and the next source opens there.  Only clips of one source resolution are open together (the
     resize is set per step).  sources: uint8 [T,H,W,3] arrays (numpy / memmap), or [T,H*3//2,W] with pix_fmt "nv12" / "i420"; fps:
-    one value or one per source.
+    one value or one per source; tracker: "ocsort" or "sort", as in track_frames (every clip's ids start at 1).
     Yields (index, rows) as clips finish - rows = the dict track_frames returns for that source."""
     from .shard import stream_schedule
     sources = list(sources)
@@ -221,7 +237,7 @@ def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5
     if not any(kept):
         return
     pipe = Pipeline(model_path, max(1, int(time_batch)), max_frames=max(kept), fps=fps_of[0], detection_treshold=detection_treshold,
-                    device=device, rows_per_frame=25, tracker_clips=int(concurrent), slot_close=True)
+                    device=device, rows_per_frame=25, tracker_clips=int(concurrent), slot_close=True, tracker=tracker)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
     clip_of = {}                                     # tracker slot -> source index of the clip open in it
@@ -312,8 +328,11 @@ class Pipeline:
     convenience for callers who hold them - torch tensors (device or pinned host).  torch is never imported here."""
 
     def __init__(self, model_path, n_clips, max_frames, fps=60.0, detection_treshold=0.5, device=0, rows_per_frame=4,
-                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False, group=None):
+                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False, group=None, tracker="ocsort", id_base=0):
+        """tracker: "ocsort" = OCSort(max_age=30, asso_func="diou", iou_threshold=0.1) (track.py:157), "sort" = SortTracker(max_age=30)
+        (track.py:156; vbt_pipeline_use_sort) whose ids start at id_base + 1 in every clip."""
         L = _lib.lib()
+        self.tracker_name = _tracker_name(tracker)
         self.n = int(n_clips)                       # slots of the detector batch
         # tracker_clips > n_clips: more clips than batch slots; step(clip_map=...) says which clip sits in which slot
         self.n_trk = int(tracker_clips) if tracker_clips is not None else self.n
@@ -344,6 +363,9 @@ class Pipeline:
         _lib.check(rc)
         self._owner = _PipelineHandle(h)            # shared with the borrowed Interpreter / tracker views: the library object lives as long as any of them
         self._h = h
+        if self.tracker_name == "sort":
+            from .sort import sort_params
+            _lib.check(L.vbt_pipeline_use_sort(self._h, ctypes.byref(sort_params(max_age=MAX_AGE, id_base=id_base))))
         if slot_close:                              # close_clips() / closed(): their buffers now, so that no close allocates
             _lib.check(L.vbt_pipeline_close_clips_enable(self._h))
         info = self.info()
