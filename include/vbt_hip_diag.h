@@ -41,6 +41,10 @@ int vbt_model_num_launches(const vbt_model* m);
 
 /* Parity/debug: copy graph tensor `tensor_id` ([B,H,W,C] int8) of the last vbt_detect to host. */
 int vbt_model_read_tensor(vbt_model* m, int tensor_id, int B, int8_t* host_out);
+/* Test equipment: the reverse copy, host [B,H,W,C] int8 into the buffer the plan's launches read for graph tensor `tensor_id`
+ * (same checks as the read).  With vbt_detect_range_async it runs single plan steps on crafted inputs (tests/test_gpu_postprocess.py
+ * drives decode + NMS alone this way); the next full forward overwrites what was written. */
+int vbt_model_write_tensor(vbt_model* m, int tensor_id, int B, const int8_t* host_in);
 
 /* The plan space: what a plan file (VBT_PLAN_FILE) may select, as the loader checks it.  One entry per step of every alternative
  * of every group, in that order; `variants` lists the values a file may name for that step.  *n = the number of entries; a `cap`

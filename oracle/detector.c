@@ -457,6 +457,14 @@ int vbto_run(vbto_model* m, const uint8_t* frame, float* boxes, float* scores, f
   return 0;
 }
 
+/* Test equipment: only the OP_POSTPROCESS op, on the head tensors as they stand (written by a run, or through vbto_tensor_data:
+ * tests/test_postprocess_ref_host.py feeds crafted head bytes this way). */
+int vbto_postprocess(vbto_model* m, float* boxes, float* scores, float* classes, int32_t* count) {
+  for (int i = 0; i < m->hdr.num_ops; i++)
+    if (m->ops[i].type == OP_POSTPROCESS) return run_postprocess(m, &m->ops[i], boxes, scores, classes, count) ? -3 : 0;
+  return -1;
+}
+
 /* Batch helper for the CPU baseline: frames [B,S,S,3]; one private model copy per thread. */
 int vbto_run_batch(const char* path, const uint8_t* frames, int B, int threads,
                    float* boxes, float* scores, float* classes, int32_t* counts) {

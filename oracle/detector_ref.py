@@ -22,6 +22,7 @@ def lib():
         L.vbto_tensor_data.restype = ctypes.c_void_p
         L.vbto_tensor_data.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.vbto_run.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 5
+        L.vbto_postprocess.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4
         L.vbto_run_batch.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
         _LIB = L
     return _LIB
@@ -63,6 +64,26 @@ class OracleDetector:
         n = shp[0] * shp[1] * shp[2]
         p = lib().vbto_tensor_data(self.h, tid)
         return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_int8)), shape=(n,)).reshape(shp[0], shp[1], shp[2]).copy()
+
+    def set_tensor(self, tid, array):
+        """int8 [h,w,c] into the oracle's buffer of tensor `tid` (crafted head bytes for postprocess())."""
+        shp = (ctypes.c_int * 3)()
+        if lib().vbto_tensor_shape(self.h, tid, shp):
+            raise ValueError(f"oracle: no tensor {tid}")
+        a = np.ascontiguousarray(array, dtype=np.int8)
+        if a.shape != (shp[0], shp[1], shp[2]):
+            raise ValueError(f"oracle: tensor {tid} is [{shp[0]},{shp[1]},{shp[2]}], got {a.shape}")
+        ctypes.memmove(lib().vbto_tensor_data(self.h, tid), a.ctypes.data, a.nbytes)
+
+    def postprocess(self):
+        """Only the post-process op, on the head tensors as they stand -> like run()."""
+        boxes = np.zeros((self.MAXDET, 4), np.float32)
+        scores = np.zeros(self.MAXDET, np.float32)
+        classes = np.zeros(self.MAXDET, np.float32)
+        count = np.zeros(1, np.int32)
+        if lib().vbto_postprocess(self.h, boxes.ctypes.data, scores.ctypes.data, classes.ctypes.data, count.ctypes.data):
+            raise RuntimeError("oracle post-process failed")
+        return boxes, scores, classes, int(count[0])
 
 
 def run_batch(path, frames, threads=1):

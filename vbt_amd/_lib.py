@@ -147,6 +147,7 @@ _SIGS = {
     "vbt_stream_destroy": (c_int, [c_void_p]),
     "vbt_streams_share_queue": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_model_read_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "vbt_model_write_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vbt_model_plan_space": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_model_step_proj_tail": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -667,6 +667,15 @@ int vbt_model_read_tensor(vbt_model* m, int id, int B, int8_t* host_out) {
   return VBT_OK;
 }
 
+int vbt_model_write_tensor(vbt_model* m, int id, int B, const int8_t* host_in) {
+  if (!m || !host_in || id < 0 || id >= (int)m->tensors.size() || id == m->hdr.input_tensor) { set_error("bad tensor id"); return VBT_ERR_ARG; }
+  if (B < 1 || B > m->max_batch) { set_error("bad batch"); return VBT_ERR_CAPACITY; }
+  if (!m->materialized[id]) { set_error("tensor %d lives only in LDS (fused away); create the model with VBT_MODEL_NO_FUSION to write it", id); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipDeviceSynchronize());
+  VBT_HIP_CHECK(hipMemcpy(m->tptr[id], host_in, m->telems[id] * B, hipMemcpyHostToDevice));
+  return VBT_OK;
+}
+
 }  // extern "C"
 namespace vbt {
 int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st) {

@@ -126,3 +126,24 @@ class Interpreter:
         out = np.empty((B, shp[0], shp[1], shp[2]), np.int8)
         _lib.check(_lib.lib().vbt_model_read_tensor(self._h, tid, B, out.ctypes.data))
         return out
+
+    def write_tensor(self, tid, array):
+        """int8 [B,h,w,c] (host) into the device buffer of graph tensor `tid` (test equipment: vbt_model_write_tensor)."""
+        shp = (ctypes.c_int * 3)()
+        _lib.check(_lib.lib().vbt_model_tensor_shape(self._h, tid, shp))
+        a = np.ascontiguousarray(array, dtype=np.int8)
+        if a.ndim != 4 or tuple(a.shape[1:]) != (shp[0], shp[1], shp[2]):
+            raise ValueError(f"tensor {tid} is int8 [B,{shp[0]},{shp[1]},{shp[2]}], got {a.shape}")
+        _lib.check(_lib.lib().vbt_model_write_tensor(self._h, tid, a.shape[0], a.ctypes.data))
+
+    def run_postprocess(self, B, fill=0xA5):
+        """The plan's last step (decode + NMS) alone on the head tensors as they stand, frames 0..B-1 (test equipment, see
+        write_tensor).  The four outputs are device buffers filled with the byte `fill` before the launch, so that rows the kernel
+        leaves unwritten show.  -> boxes [B,25,4], scores [B,25], classes [B,25], counts [B]."""
+        from .mem import DeviceBuffer
+        shapes = ((B, MAXDET, 4), (B, MAXDET), (B, MAXDET), (B,))
+        dtypes = (np.float32, np.float32, np.float32, np.int32)
+        bufs = [DeviceBuffer.from_host(np.full(int(np.prod(s)) * 4, fill, np.uint8), self.device) for s in shapes]
+        last = self.num_launches() - 1
+        _lib.check(_lib.lib().vbt_detect_range_async(self._h, None, 0, B, last, -1, None, *[ctypes.c_void_p(b.ptr) for b in bufs]))
+        return tuple(b.to_host(s, d) for b, s, d in zip(bufs, shapes, dtypes))
