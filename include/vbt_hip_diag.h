@@ -63,6 +63,10 @@ int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, 
  * current variant: fused_mbconv launches built with a live-tile count and pw_conv_mfma_i8 variants 9 / 10.  0: the step runs the
  * block-major layout (a full last block, another family, no such kernel, or VBT_PROJ_TAIL turned it off); < 0: no such step. */
 int vbt_model_step_proj_tail(const vbt_model* m, int group, int alt, int step);
+/* 1 if step (group, alt, step) is a fused_mbconv launch that, under its current variant, fetches its chunk parameters once per workgroup and
+ * hands them to its waves through LDS; 0: the step's waves load them from global memory (another family, no such kernel, the tile would not
+ * fit 64 KB of LDS with the parameter area, or VBT_FUSED_PARAMS turned it off); < 0: no such step. */
+int vbt_model_step_fused_params(const vbt_model* m, int group, int alt, int step);
 
 /* ------------------------------------------------------------------ stream placement probe ----------------------------- */
 /* *shared = 1 when the two streams sit on one hardware queue (their kernels cannot overlap): a single wave spins `us`

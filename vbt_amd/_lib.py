@@ -150,6 +150,7 @@ _SIGS = {
     "vbt_model_write_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vbt_model_plan_space": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_model_step_proj_tail": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "vbt_model_step_fused_params": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_resize_frames_yuv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_model_kernel_stats": (c_int, [c_void_p, c_int, ctypes.POINTER(KernelStat), c_int, ctypes.POINTER(c_int)]),

@@ -198,6 +198,15 @@ static bool proj_tail_on(int block) {
   if (knob.empty()) return true;
   return knob.find(",b" + std::to_string(block) + ",") != std::string::npos;
 }
+// VBT_FUSED_PARAMS (developers; read once per process), the same syntax: which blocks fetch their chunk parameters once per workgroup,
+// through LDS (fused_block.h: PLDS); unset: every block whose resolved launch is built that way and whose tile fits with the parameter area
+static bool fused_params_on(int block) {
+  static const std::string knob = getenv("VBT_FUSED_PARAMS") ? std::string(",") + getenv("VBT_FUSED_PARAMS") + "," : std::string();
+  if (knob.empty()) return true;
+  return knob.find(",b" + std::to_string(block) + ",") != std::string::npos;
+}
+// the parameter block of a resolved launch (Step::cpar), or nullptr
+static const unsigned char* fused_params_of(const Step& s, const FusedLaunch& L) { return s.cpar[L.nt3][fused_params_form(L)][L.ntl > 0]; }
 FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   const FusedArgs& a = s.fa;
   const OpRec& dop = m->ops[s.d_op];
@@ -247,6 +256,13 @@ FusedPlan resolve_fused(const vbt_model* m, const Step& s, int variant, int B) {
   // a part-filled last projection block runs tile-major wherever the step has the panels and the resolved launch is built with a live-tile
   // count: a property of the step, no variant bit (plan files do not change)
   if (s.ntl && proj_tail_on(s.block) && (nt3 ? a.wpt3 : a.wpt) && fused_tail_built(p.L, a.KSe, s.ntl)) p.L.ntl = s.ntl;
+  // the chunk parameters once per workgroup, through LDS: again a property of the step - wherever the resolved launch is built that way,
+  // the step has its block, and the tile with the parameter area passes the 64 KB the refusals below hold the other form to and still leaves
+  // the CU's 160 KB of LDS as many workgroups as the kernel's registers do (else the area would cost a wave per SIMD)
+  if (const int wgs = ex && fused_params_on(s.block) && fused_params_of(s, p.L) ? fused_params_built(p.L, a.KSe, p.L.ntl) : 0) {
+    const int lds = p.L.lds_bytes + fused_params_lds(fused_params_geom(nt3 ? 3 : 4, a.KSe, fused_params_form(p.L), k, stride, s.nbp, p.L.ntl));
+    if (lds <= 64 * 1024 && wgs * lds <= 160 * 1024) { p.L.params = true; p.L.lds_bytes = lds; }
+  }
   if (ppw2 && (a.OW < 16 || a.OH < 8 || !a.wd64)) p.refuse(VBT_ERR_ARG, "fused_mbconv: the 128-pixel variant needs maps of at least 16 x 8");
   else if (ppw2 && p.L.lds_bytes > 64 * 1024) p.refuse(VBT_ERR_ARG, "fused_mbconv: 128-pixel tile needs %d bytes of LDS", p.L.lds_bytes);
   else if (tpz && !tpz_ok) p.refuse(VBT_ERR_ARG, "fused_mbconv: variant %d: the Toeplitz depthwise does not apply to this step", var);
@@ -258,6 +274,7 @@ static int launch_fused_step(const vbt_model* m, const Step& s, FusedArgs a, int
   if (p.rc) return p.report();
   if (p.image) return launch_mbconv_image(a, s.ib, p.L.k, p.L.stride, p.maxu, p.PW, p.PH, p.NB, p.L.lds_bytes, B, st);
   a.TX = p.TX; a.TY = p.TY; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
+  a.cpar = p.L.params ? fused_params_of(s, p.L) : nullptr;
   return launch_fused_block(a, p.L, st);
 }
 

@@ -54,7 +54,10 @@ struct Step {
   int src_tensor[3] = {-1, -1, -1};
   FusedArgs fa;
   int nbp = 0, lds_bytes = 0;
-  int block = 0;     // F_MBCONV with ntl > 0: the block's number in the backbone (depthwise convs before its own: b1, b2, ...), for VBT_PROJ_TAIL
+  int block = 0;     // F_MBCONV: the block's number in the backbone (depthwise convs before its own: b1, b2, ...), for VBT_PROJ_TAIL / VBT_FUSED_PARAMS
+  // F_MBCONV: per-chunk parameter blocks (pack_fused_chunk_params) by [48-channel chunks][depthwise form, fused_params_geom.h][tile-major
+  // panel of ntl tiles]; nullptr: no launch with the parameters in LDS is built for that combination
+  const unsigned char* cpar[2][3][2] = {};
   int variant = -1;  // kernel variant chosen by the autotuner (-1 = heuristic default)
   double tuned_ms = 0;
   // F_MULTI: independent fused problems launched as one grid

@@ -336,6 +336,15 @@ int vbt_model_step_proj_tail(const vbt_model* m, int group, int alt, int step) {
   return 0;
 }
 
+int vbt_model_step_fused_params(const vbt_model* m, int group, int alt, int step) {
+  if (!m || group < 0 || group >= (int)m->groups.size() || alt < 0 || alt >= (int)m->groups[group].alts.size() || step < 0 ||
+      step >= (int)m->groups[group].alts[alt].steps.size()) { set_error("vbt_model_step_fused_params: no such step"); return VBT_ERR_ARG; }
+  const Step& st = m->groups[group].alts[alt].steps[step];
+  if (st.family != F_MBCONV) return 0;
+  const FusedPlan p = resolve_fused(m, st, st.variant, m->max_batch);
+  return !p.rc && !p.image && p.L.params;
+}
+
 int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, vbt_model** out) {
   if (!path || !out || max_batch < 1) { set_error("vbt_model_create: bad argument"); return VBT_ERR_ARG; }
   *out = nullptr;

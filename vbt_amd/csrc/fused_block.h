@@ -14,8 +14,13 @@
 // zero point of E because the depthwise pads ITS input) -> barrier -> depthwise (lane = 4 channels x 4
 // output columns, weights in registers, cvt_f32_ubyte + fma, exact) -> barrier -> project accumulation
 // (int8 MFMA, wave w owns pixels 16w..16w+15, accumulators stay in registers across chunks).
+// Where a chunk's parameters come from: every wave loads them from global memory at the top of the stage that needs them (three
+// dependent round trips per chunk, the same bytes in all four waves), or - template flag PLDS, MBConv launches listed by
+// fused_params_built - the workgroup fetches one packed record per chunk (FusedArgs::cpar, fused_params_geom.h) a stage ahead and the
+// stages read it from an LDS area behind D; see the comment at fused_block_body.
 #pragma once
 #include "tpz_geom.h"
+#include "fused_params_geom.h"
 
 struct FusedArgs {
   const int8_t* x;
@@ -70,6 +75,9 @@ struct FusedArgs {
   const float* mp;
   int KSp, zo, lop, hip;
   Rq rqp;
+  // PLDS: the per-chunk parameter block of the resolved launch (its chunking, depthwise form and panel layout: fused_params_geom.h,
+  // pack_fused_chunk_params), nch records and the bias | multiplier tail; nullptr: the launch reads the arrays above
+  const unsigned char* cpar;
   // residual ADD: out = ADD(project output, block input), the graph's input order (AddQ: XNNPACK qs8-vadd, detector.hip)
   int has_res;
   AddQ resq;
@@ -122,7 +130,32 @@ constexpr int FB_DST = 80;  // D tile bytes per pixel: 16-byte aligned rows (the
 // lane (r, g) of tile t ends with channels 64 (NBP - 1) + 16 t + 4 g .. + 3 of pixel r.  Stage P loads and multiplies NTL tiles of that block
 // and the epilogue requantises NTL tiles, one dword each; with the block-major layout (NTL = 0) a block of 24 / 40 / 16 channels spreads over
 // all four tiles and the whole wave runs four requantisations (and residual ADDs) for it, most lanes switched off.  Cout % 4 == 0.
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0>
+// PLDS: a chunk's parameters (expand operands, depthwise operands, the projection's K-step, every bias and multiplier) come from ONE
+// packed record per chunk (FusedArgs::cpar) that the workgroup fetches once, 16 bytes per thread and piece, a stage ahead of its use, and
+// hands to its four waves through a single-buffered area of LDS behind D - instead of every wave loading the same bytes from global memory
+// at the top of every stage, in three dependent round trips per chunk.  Barriers, stage order and arithmetic are those of the other form:
+//   region  read (into registers)   requested (chunk c + 1's, clamped to the last chunk)   written to LDS
+//   Pe      top of stage E          top of stage E(c)                                      stage D(c), after barrier 1: every wave took Pe(c) before it
+//   Pd      top of stage D          top of stage D(c)                                      stage P(c), after barrier 2: every wave took Pd(c) before it
+//   Pp      stage P                 top of stage P(c)                                      stage D(c + 1), after barrier 1: every wave has left P(c)
+// Chunk 0's regions and the epilogue's bias | multipliers are requested before stage L's input loads and written before its barrier.
+// The Toeplitz form reads its taps and bias / multiplier vectors from the area where it uses them (held in registers over the stage beside
+// the fetched pieces they cost a wave per SIMD).  Measured: profiles/r13_fused_params_ab.md.
+//
+// ParamPieces: the pieces one thread holds of a region of NP pieces, piece tid + 256 i in v[i] (the compiler's own vector type: an array
+// of it stays in registers like the accumulators do; HIP's uint4 class did not)
+template <int NP> struct ParamPieces { v4i v[NP > 0 ? (NP + 255) / 256 : 1]; };
+// the loads are unconditional, the index clamped to the region's last piece: no divergence, nothing read past the region
+template <int NP> __device__ __forceinline__ void pp_fetch(ParamPieces<NP>& r, const unsigned char* src, int tid) {
+#pragma unroll
+  for (int i = 0; i < (NP + 255) / 256; i++) r.v[i] = *(const v4i*)(src + 16 * min(tid + 256 * i, NP - 1));
+}
+template <int NP> __device__ __forceinline__ void pp_store(const ParamPieces<NP>& r, unsigned char* dst, int tid) {
+#pragma unroll
+  for (int i = 0; i < (NP + 255) / 256; i++)
+    if (256 * i + 255 < NP || tid + 256 * i < NP) *(v4i*)(dst + 16 * (tid + 256 * i)) = r.v[i];
+}
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0, bool PLDS = false>
 __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, unsigned char* fb_smem) {
   static_assert(PPW == 1 || MDW, "128-pixel tiles exist for the matrix-pipe depthwise only");
   static_assert(NTL >= 0 && NTL <= 4 && (NTL == 0 || EXPAND), "a tile-major last block (MBConv only) holds one to four tiles");
@@ -131,6 +164,9 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   static_assert(!TPZ || (DW64 && (S == 1 || S == 2) && (NT == 3 || NT == 4) && NBP <= 2 && (KSE == 1 || KSE == 2)), "TPZ: a form of DW64");
   constexpr TpzGeom TG = TPZ ? tpz_geom(KK, S, PPW, NT) : TpzGeom{};
   constexpr int KT2 = (S * (S - 1) + KK + 1) / 2;   // TPZ: depthwise MFMAs per unit, two rows of the expanded image each
+  static_assert(!PLDS || (EXPAND && MDW && (KSE == 1 || KSE == 2)), "PLDS: MBConv tiles with register-resident expand weights and no early depthwise request");
+  constexpr FusedParamsGeom PG = fused_params_geom(NT, KSE > 0 ? KSE : 1, TPZ ? FPF_TOEPLITZ : DW64 ? FPF_DIAG64 : FPF_MATRIX, KK, S, NBP, NTL);
+  constexpr int NPE = PLDS ? PG.pe / 16 : 0, NPD = PLDS ? PG.pd / 16 : 0, NPP = PLDS ? PG.pp / 16 : 0, NPB = PLDS ? PG.pb / 16 : 0;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
   // tile -> (image, ty, tx) and every later pixel -> (row, column) split go through fdiv_small: no integer division
   // (~40 VALU instructions each) anywhere in the prologue
@@ -159,6 +195,23 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   if constexpr (!EXPAND && NBP <= 2) stage_p = a.nchunks == 1;
   unsigned char* WPS = D + 64 * PPW * FB_DST;    // [NBP][4][64] x 16 B  (no expand stage: never with TPZ, whose D is 8 TG.DSK bytes longer)
   unsigned char* BPS = WPS + NBP * 4096;         // bias int[NBP*64] | mult float[NBP*64]
+  // PLDS: the parameter area behind D (TPZ: D is 8 TG.DSK bytes longer)
+  unsigned char* const PAe = D + 64 * PPW * FB_DST + (TPZ ? 8 * TG.DSK : 0);
+  unsigned char* const PAd = PAe + PG.pe;
+  unsigned char* const PAp = PAd + PG.pd;
+  unsigned char* const PAb = PAp + PG.pp;
+  constexpr int CH = 16 * NT;                       // channels per chunk
+  const int nch = NT == 3 ? a.nch3 : a.nchunks;
+  ParamPieces<NPE> rpe;
+  ParamPieces<NPD> rpd;
+  ParamPieces<NPP> rpp;
+  ParamPieces<NPB> rpb;
+  if constexpr (PLDS) {   // chunk 0's record and the tail: in flight during stage L, written before its barrier
+    pp_fetch(rpe, a.cpar, tid);
+    pp_fetch(rpd, a.cpar + PG.pe, tid);
+    pp_fetch(rpp, a.cpar + PG.pe + PG.pd, tid);
+    pp_fetch(rpb, a.cpar + (long)nch * PG.chunk, tid);
+  }
 
   // ---- stage L: input halo tile -> LDS ----
   bool summed = false;
@@ -326,10 +379,14 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
     bpre = *(const int4*)(a.bdm + 16 * wave + 4 * g);
     mpre = *(const float4*)(a.md + 16 * wave + 4 * g);
   }
+  if constexpr (PLDS) {
+    pp_store(rpe, PAe, tid);
+    pp_store(rpd, PAd, tid);
+    pp_store(rpp, PAp, tid);
+    pp_store(rpb, PAb, tid);
+  }
   __syncthreads();
 
-  constexpr int CH = 16 * NT;                       // channels per chunk
-  const int nch = NT == 3 ? a.nch3 : a.nchunks;
   const long* const wdm_ = NT == 3 ? a.wdm3 : a.wdm;
   for (int c = 0; c < nch; c++) {
     // low-resolution blocks (KSE >= 3 <=> Cin >= 80: few workgroups, latency-bound): this chunk's depthwise operands are
@@ -346,30 +403,46 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       }
     }
     // TPZ: this wave's depthwise taps (NT * KT2 dwords) are requested before the expand stage and consumed after the barrier
+    // (PLDS: the taps are in LDS by then and are read after the barrier - nothing to hide, fewer registers over the expand stage)
     unsigned wtz[TPZ ? NT * KT2 : 1];
-    if constexpr (TPZ) {
+    if constexpr (TPZ && !PLDS) {
       const unsigned* wt = a.wtz + ((long)(c * 4 * NT + wq0) * KT2) * 64 + lane;
 #pragma unroll
       for (int i = 0; i < NT * KT2; i++) wtz[i] = wt[i * 64];
     }
+    // PLDS: the record of the next chunk (the last chunk asks for its own once more: the loads stay unconditional)
+    const unsigned char* const cnext = PLDS ? a.cpar + (long)min(c + 1, nch - 1) * PG.chunk : nullptr;
     if (EXPAND) {
       // ---- stage E: expand chunk c on every halo pixel ----
       // lane (r, g) owns the 4*NT consecutive channels c*CH + 4*NT*g + 4t + j, t < NT
       int4 eb[NT];
       float4 em[NT];
+      const unsigned zeb = (unsigned)(a.ze & 255) * 0x01010101u;
+      const long* w = (NT == 3 ? a.we3 : a.we) + (long)c * a.KSe * NT * 64 + lane;
+      long wreg[KSE > 0 ? KSE : 1][NT];
+      if constexpr (PLDS) {
+        pp_fetch(rpe, cnext, tid);
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          eb[t] = *(const int4*)(PAe + PG.o_be + 4 * (4 * NT * g + 4 * t));
+          em[t] = *(const float4*)(PAe + PG.o_me + 4 * (4 * NT * g + 4 * t));
+        }
+#pragma unroll
+        for (int ks = 0; ks < KSE; ks++)
+#pragma unroll
+          for (int t = 0; t < NT; t++) wreg[ks][t] = *(const long*)(PAe + 8 * ((ks * NT + t) * 64 + lane));
+      } else {
 #pragma unroll
       for (int t = 0; t < NT; t++) {
         eb[t] = *(const int4*)(a.be + c * CH + 4 * NT * g + 4 * t);
         em[t] = *(const float4*)(a.me + c * CH + 4 * NT * g + 4 * t);
       }
-      const unsigned zeb = (unsigned)(a.ze & 255) * 0x01010101u;
-      const long* w = (NT == 3 ? a.we3 : a.we) + (long)c * a.KSe * NT * 64 + lane;
-      long wreg[KSE > 0 ? KSE : 1][NT];
       if constexpr (KSE > 0) {
 #pragma unroll
         for (int ks = 0; ks < KSE; ks++)
 #pragma unroll
           for (int t = 0; t < NT; t++) wreg[ks][t] = w[(ks * NT + t) * 64];
+      }
       }
       // the requantisation flavour (saturating / explicitly clamped) is uniform: pick it once, outside the loop, so the
       // loop body stays one basic block and the scheduler can overlap the four MFMAs with the previous tile's epilogue
@@ -424,6 +497,11 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       };
       rq_dispatch(a.rqe, expand_loop);
       __syncthreads();
+      if constexpr (PLDS) {
+        pp_store(rpe, PAe, tid);             // Pe(c + 1): read at the top of stage E(c + 1), behind barrier 2
+        if (c > 0) pp_store(rpp, PAp, tid);  // Pp(c), requested in stage P(c - 1): read in stage P(c), behind barrier 2 (chunk 0's: the prologue)
+        pp_fetch(rpd, cnext + PG.pe, tid);
+      }
     }
     // ---- stage D: depthwise on chunk c ----
     if constexpr (TPZ) {
@@ -432,11 +510,20 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       constexpr int NU = NT * PPW, PGE = tpz_e_group(TG, S), PGD = tpz_d_group(TG, PPW, FB_DST);   // position group pg -> pg + 1 in E / in D
       int4 bq[NT];
       float4 mq[NT];
+      if constexpr (!PLDS) {
 #pragma unroll
-      for (int q = 0; q < NT; q++) {
-        bq[q] = *(const int4*)(a.bdm + c * CH + 4 * (wq0 + q));
-        mq[q] = *(const float4*)(a.md + c * CH + 4 * (wq0 + q));
+        for (int q = 0; q < NT; q++) {
+          bq[q] = *(const int4*)(a.bdm + c * CH + 4 * (wq0 + q));
+          mq[q] = *(const float4*)(a.md + c * CH + 4 * (wq0 + q));
+        }
       }
+      // PLDS: a tap, a bias or a multiplier vector is read from LDS where it is used (`wave base + immediate`; each tap serves one pair of
+      // units, so these are the reads the register form makes at the top of the stage) - every one of them before barrier 2
+      const unsigned char* const tzw = PAd + 4 * (wq0 * KT2 * 64 + lane);
+      const unsigned char* const tzb = PAd + 16 * wq0;
+      auto tz_bias = [&](int q) { if constexpr (PLDS) return *(const int4*)(tzb + PG.o_bd + 16 * q); else return bq[q]; };
+      auto tz_mult = [&](int q) { if constexpr (PLDS) return *(const float4*)(tzb + PG.o_md + 16 * q); else return mq[q]; };
+      auto tz_tap = [&](int i) { if constexpr (PLDS) return *(const unsigned*)(tzw + 256 * i); else return wtz[i]; };
       const unsigned char* eb = E + tz_e;
       unsigned char* db = D + tz_d;
       auto tz_walk = [&](auto mode_tag) {
@@ -445,7 +532,7 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         for (int u0 = 0; u0 < NU; u0 += 2) {
           v4i dq[2];
 #pragma unroll
-          for (int u = 0; u < 2; u++) dq[u] = v4i_from(int4_plus(bq[(u0 + u < NU ? u0 + u : u0) / PPW], RM >= 2 ? RQ_KBIAS : 0));
+          for (int u = 0; u < 2; u++) dq[u] = v4i_from(int4_plus(tz_bias((u0 + u < NU ? u0 + u : u0) / PPW), RM >= 2 ? RQ_KBIAS : 0));
 #pragma unroll
           for (int mi = 0; mi < KT2; mi++)
 #pragma unroll
@@ -453,13 +540,13 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
               if (u0 + u >= NU) continue;
               const int q = (u0 + u) / PPW, pg = (u0 + u) % PPW;
               const v4i bv = *(const v4i*)(eb + q * TG.EQS + pg * PGE + mi * 2 * TG.EYS);
-              dq[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(toeplitz_operand(wtz[q * KT2 + mi], r & 3), bv, dq[u], 0, 0, 0);
+              dq[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(toeplitz_operand(tz_tap(q * KT2 + mi), r & 3), bv, dq[u], 0, 0, 0);
             }
 #pragma unroll
           for (int u = 0; u < 2; u++) {
             if (u0 + u >= NU) continue;
             const int q = (u0 + u) / PPW, pg = (u0 + u) % PPW;
-            *(unsigned*)(db + pg * PGD + 4 * q) = rq_pack_b<RM>(dq[u], mq[q], a.rqd);
+            *(unsigned*)(db + pg * PGD + 4 * q) = rq_pack_b<RM>(dq[u], tz_mult(q), a.rqd);
           }
         }
       };
@@ -469,12 +556,12 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       constexpr int KT64 = KK == 3 ? 3 : 7;
       constexpr int PGS = (16 / TXP) * S * HWX * EST;   // slot group pg -> pg + 1
       if (NT == 4 || wave < NT) {   // wave = 16-channel group of the chunk (48-channel chunks: wave 3 sits this stage out)
-        const unsigned long long wc = (unsigned long long)a.wd64c[(long)(c * NT + wave) * 64 + lane];
+        const unsigned long long wc = PLDS ? *(const unsigned long long*)(PAd + 8 * (wave * 64 + lane)) : (unsigned long long)a.wd64c[(long)(c * NT + wave) * 64 + lane];
         v4i wreg[KT64];
 #pragma unroll
         for (int mi = 0; mi < KT64; mi++) wreg[mi] = diag_operand((unsigned)(wc >> (8 * mi)) & 0xffu, r);
-        const int4 bq0 = *(const int4*)(a.bdm + c * CH + 16 * wave + 4 * g);
-        const float4 mum = *(const float4*)(a.md + c * CH + 16 * wave + 4 * g);
+        const int4 bq0 = PLDS ? *(const int4*)(PAd + PG.o_bd + 4 * (16 * wave + 4 * g)) : *(const int4*)(a.bdm + c * CH + 16 * wave + 4 * g);
+        const float4 mum = PLDS ? *(const float4*)(PAd + PG.o_md + 4 * (16 * wave + 4 * g)) : *(const float4*)(a.md + c * CH + 16 * wave + 4 * g);
         const int hb = TXP == 8 ? ((r >> 3) * S * HWX + (r & 7) * S) : r * S;   // window origin of slot r of group 0
         const unsigned char* baseH = E + hb * EST + 16 * wave + g * EST;          // g = column of the tap
         const unsigned char* baseV = E + hb * EST + 16 * wave + g * (HWX * EST);  // g = row of the tap (5x5, column 4)
@@ -516,6 +603,11 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         for (int mi = 0; mi < KT; mi++) wreg[mi] = wpre[mi];
         bqm = bpre;
         mum = mpre;
+      } else if (PLDS && cg_active) {
+#pragma unroll
+        for (int mi = 0; mi < KT; mi++) wreg[mi] = *(const long*)(PAd + 8 * ((wave * KT + mi) * 64 + lane));
+        bqm = *(const int4*)(PAd + PG.o_bd + 4 * (16 * wave + 4 * g));
+        mum = *(const float4*)(PAd + PG.o_md + 4 * (16 * wave + 4 * g));
       } else if (cg_active) {
 #pragma unroll
         for (int mi = 0; mi < KT; mi++) wreg[mi] = wm[mi * 64];
@@ -590,6 +682,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
     // ---- stage P: project accumulation, wave w <- pixel slots 16*PPW*w .. +16*PPW-1, K = this chunk's 64 channels: ONE 16x16x64 MFMA per
     // (slot group, 16-channel tile) and one 16-byte operand read per slot group (two 16x16x32 and two 8-byte reads before) ----
     {
+      if constexpr (PLDS) {
+        pp_store(rpd, PAd, tid);   // Pd(c + 1): read at the top of stage D(c + 1), behind barrier 1
+        pp_fetch(rpp, cnext + PG.pe + PG.pd, tid);
+      }
       v4i bv[PPW];
 #pragma unroll
       for (int pp = 0; pp < PPW; pp++) {
@@ -598,7 +694,7 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       }
 #pragma unroll
       for (int nb = 0; nb < NBW; nb++) {
-        const v4i* w = stage_p ? (const v4i*)WPS + (nb * 4) * 64 + lane
+        const v4i* w = (stage_p || PLDS) ? (const v4i*)(PLDS ? PAp : WPS) + (nb * 4) * 64 + lane
                                : NTL ? (NT == 3 ? a.wpt3 + ((long)(nb * a.KSp3 + c) * 4) * 64 : a.wpt + ((long)(nb * a.KSp + c) * 4) * 64) + lane
                                : (NT == 3 ? a.wp3 + ((long)(nb * a.KSp3 + c) * 4) * 64 : a.wp + ((long)(nb * a.KSp + c) * 4) * 64) + lane;
 #pragma unroll
@@ -609,7 +705,8 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         }
       }
       if constexpr (NTL > 0) {   // the tile-major last block: NTL tiles per K-step, behind the NBW full blocks of the panel
-        const v4i* w = (NT == 3 ? a.wpt3 + ((long)NBW * a.KSp3 * 4 + (long)c * NTL) * 64 : a.wpt + ((long)NBW * a.KSp * 4 + (long)c * NTL) * 64) + lane;
+        const v4i* w = PLDS ? (const v4i*)PAp + (NBW * 4) * 64 + lane
+                            : (NT == 3 ? a.wpt3 + ((long)NBW * a.KSp3 * 4 + (long)c * NTL) * 64 : a.wpt + ((long)NBW * a.KSp * 4 + (long)c * NTL) * 64) + lane;
 #pragma unroll
         for (int t = 0; t < NTL; t++) {
           const v4i wv = w[t * 64];
@@ -634,8 +731,8 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
 #pragma unroll
       for (int t = 0; t < NTL; t++) {
         const int c = NBW * 64 + 16 * t + 4 * g;   // (bias / multiplier arrays are padded to 64-channel blocks)
-        const int4 bb = *(const int4*)(a.bp + c);
-        const float4 mu = *(const float4*)(a.mp + c);
+        const int4 bb = PLDS ? *(const int4*)(PAb + 4 * c) : *(const int4*)(a.bp + c);
+        const float4 mu = PLDS ? *(const float4*)(PAb + NBP * 256 + 4 * c) : *(const float4*)(a.mp + c);
         unsigned dq = rq_pack_i(acc[pp][NBW][t], bb, mu, a.rqp);
         if (a.has_res) dq = addq4(dq, *(const unsigned*)(skip + min(c, a.Cin - 4)), a.resq);   // Cin == Cout
         if (c < a.Cout) *(unsigned*)(orow + c) = dq;   // off for part of the lanes on the last tile only (Cout % 16 != 0)
@@ -650,7 +747,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       for (int t = 0; t < 4; t++) {
         int4 bb;
         float4 mu;
-        if (stage_p) {
+        if constexpr (PLDS) {
+          bb = *(const int4*)(PAb + 4 * (c0 + 4 * t));
+          mu = *(const float4*)(PAb + NBP * 256 + 4 * (c0 + 4 * t));
+        } else if (stage_p) {
           bb = *(const int4*)(BPS + 4 * (c0 + 4 * t));
           mu = *(const float4*)(BPS + NBP * 256 + 4 * (c0 + 4 * t));
         } else {
@@ -687,10 +787,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
 #ifndef FB_MINW
 #define FB_MINW 1
 #endif
-template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0>
+template <int KK, int S, int NBP, bool EXPAND, bool MDW, int KSE = 0, int NT = 4, int PPW = 1, bool DW64 = false, bool TPZ = false, int NTL = 0, bool PLDS = false>
 __global__ __launch_bounds__(256, FB_MINW) void fused_block_kernel(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fb_smem_dyn[];
-  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ, NTL>(a, blockIdx.x, fb_smem_dyn);
+  fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ, NTL, PLDS>(a, blockIdx.x, fb_smem_dyn);
 }
 
 // Several independent problems (e.g. the same head layer on all 5 pyramid levels of both heads) in ONE grid:

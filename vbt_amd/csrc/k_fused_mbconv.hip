@@ -50,7 +50,10 @@ int launch_fused_mbconv_tpz(const FusedArgs& a, const FusedLaunch& L, hipStream_
 
 int launch_fused_mbconv_tail(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);  // k_fused_mbconv_tail.hip
 
+int launch_fused_mbconv_params(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);   // k_fused_mbconv_params.hip
+
 int launch_fused_mbconv(const FusedArgs& a, const FusedLaunch& L, hipStream_t st) {
+  if (L.params) return launch_fused_mbconv_params(a, L, st);
   if (L.ntl) return launch_fused_mbconv_tail(a, L, st);
   if (L.tpz) return launch_fused_mbconv_tpz(a, L, st);
   const dim3 grid(L.grid);

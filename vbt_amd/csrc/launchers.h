@@ -25,6 +25,7 @@ struct FusedLaunch {
   unsigned grid;
   bool tpz = false;     // dw64 as a band-Toeplitz product on a quad-planar E (k_fused_mbconv_tpz.hip)
   int ntl = 0;          // live tiles of a tile-major part-filled last projection block (k_fused_mbconv_tail.hip); 0: block-major
+  bool params = false;  // chunk parameters once per workgroup, through LDS (fused_block.h: PLDS; k_fused_mbconv_params*.hip); lds_bytes includes the area
 };
 // The (k, stride, nbp, KSe) the Toeplitz form is built for - what the MBConv steps of the shipped models resolve to (the first five
 // four blocks of the EfficientNet-Lite backbones: the fifth is not cut into 8 x 8 tiles and its 16 x 8 tile does not fit 64 KB, the later
@@ -44,6 +45,23 @@ static inline bool fused_tail_built(const FusedLaunch& L, int kse, int ntl) {
   if (L.dw64) return L.nt3 && !L.ppw2 && L.stride == 2 && L.nbp == 1 && kse == 1 && ntl == (L.k == 3 ? 2 : 3);
   return L.expand && L.mdw && !L.nt3 && !L.ppw2 && !L.dw64 && L.k == 3 && L.stride == 2 && L.nbp == 2 && kse == 2 && ntl == 1;
 }
+// The launches built with the chunk parameters in LDS (fused_block.h: PLDS): of the launches above that the shipped plans (profiles/plan_lite0.*,
+// plan_lite2.*) resolve to, those whose compiler resource report keeps the waves per SIMD of the other form with no scratch - the diagonal
+// 16x16x64 depthwise of the two stride-2 blocks (8 x 8 tiles, 48-channel chunks) with its live-tile count and block-major (ntl == 0), and the
+// Toeplitz depthwise on 16 x 8 tiles with 48-channel chunks, 3x3/1 with its live-tile count and 5x5/1 with it and block-major.  Returns the
+// waves per SIMD the instantiation runs at (= the workgroups per CU its registers allow; a launch wants as many by LDS), 0: not built.
+// Another shape needs a line here and one in k_fused_mbconv_params.hip.
+static inline int fused_params_built(const FusedLaunch& L, int kse, int ntl) {
+  if (!L.expand || !L.mdw || !L.dw64 || !L.nt3 || L.nbp != 1) return 0;
+  const int want = L.k == 3 ? 2 : 3;   // the live-tile count fused_tail_built knows the shape by
+  if (ntl != 0 && ntl != want) return 0;
+  if (!L.tpz) return !L.ppw2 && L.stride == 2 && kse == 1 ? (L.k == 3 ? 4 : 3) : 0;
+  if (!L.ppw2 || L.stride != 1) return 0;
+  if (L.k == 3) return kse == 1 && ntl ? 4 : 0;
+  return kse == 2 ? 3 : 0;
+}
+// the depthwise form of a launch, as fused_params_geom.h numbers them
+static inline int fused_params_form(const FusedLaunch& L) { return L.tpz ? FPF_TOEPLITZ : L.dw64 ? FPF_DIAG64 : FPF_MATRIX; }
 int launch_fused_block(const FusedArgs& a, const FusedLaunch& L, hipStream_t st);
 int launch_fused_multi(const FusedArgs* d_args, const MultiTiles& mt, int k, int stride, int nbp, bool mdw, int lds_bytes, unsigned grid,
                        hipStream_t st);

@@ -110,6 +110,65 @@ static int make_image_bundle(vbt_model* m, int e_op, int d_op, int p_op, int KSe
   return VBT_OK;
 }
 
+// Per-chunk parameter blocks of an MBConv step (fused_block.h: PLDS; pack_fused_chunk_params): one block for every (chunking, depthwise
+// form, panel layout) whose launch is built with the parameters in LDS (fused_params_built) - each from the host images of the arrays the
+// other kernel form reads, packed once more by the same packers.  s.fa holds the step's device arrays already: a null pointer there
+// means the step has no such array, and no block is made for it.
+static int make_fused_params(vbt_model* m, int e_op, int d_op, int p_op, Step* sp) {
+  Step& s = *sp;
+  const FusedArgs& a = s.fa;
+  const OpRec &eop = m->ops[e_op], &dop = m->ops[d_op], &pop = m->ops[p_op];
+  const TensorRec &tin = m->tensors[eop.inputs[0]], &tdin = m->tensors[dop.inputs[0]], &tdout = m->tensors[dop.output], &tout = m->tensors[pop.output];
+  const int8_t* we = (const int8_t*)(m->blob.data() + eop.w_off);
+  const int8_t* wd = (const int8_t*)(m->blob.data() + dop.w_off);
+  const int8_t* wpj = (const int8_t*)(m->blob.data() + pop.w_off);
+  const int Ce = tdin.c, Cp = (Ce + 63) / 64 * 64, kk = dop.k * dop.k, k = dop.k, S = dop.stride;
+  if (!(a.KSe == 1 || a.KSe == 2) || s.nbp > 2 || !(k == 3 || k == 5)) return VBT_OK;
+  const std::vector<int> be = fold_bias((const int32_t*)(m->blob.data() + eop.b_off), we, Ce, tin.c, tin.zero_point, W_ROWS, Cp);
+  const std::vector<float> me = pad_floats((const float*)(m->blob.data() + eop.m_off), Ce, Cp);
+  const std::vector<int> bdm = fold_bias((const int32_t*)(m->blob.data() + dop.b_off), wd, Ce, kk, tdin.zero_point, W_TAPS, Cp);
+  const std::vector<float> md = pad_floats((const float*)(m->blob.data() + dop.m_off), Ce, Cp);
+  const std::vector<int> bp = fold_bias((const int32_t*)(m->blob.data() + pop.b_off), wpj, tout.c, Ce, tdout.zero_point, W_ROWS, s.nbp * 64);
+  const std::vector<float> mp = pad_floats((const float*)(m->blob.data() + pop.m_off), tout.c, s.nbp * 64);
+  for (int nt3 = 0; nt3 < 2; nt3++) {
+    if (nt3 && !a.nch3) continue;
+    const int NT = nt3 ? 3 : 4, nch = nt3 ? a.nch3 : a.nchunks;
+    std::vector<long> wex;
+    if (nt3) wex = pack_expand48(we, Ce, tin.c, a.KSe);
+    else pack_weights(we, Ce, tin.c, a.KSe, nch, nullptr, wex);
+    const std::vector<int> kmap = nt3 ? kmap48(Ce) : std::vector<int>();
+    for (int form = 0; form < 3; form++) {
+      FusedLaunch L{k, S, s.nbp, true, true, bool(nt3), false, form != FPF_MATRIX, 0, 0, form == FPF_TOEPLITZ};
+      if (form == FPF_TOEPLITZ ? !a.wtz : form == FPF_DIAG64 ? !a.wd64c : false) continue;
+      std::vector<long> dwl;
+      std::vector<unsigned> dwt;
+      for (int tail = 0; tail < 2; tail++) {
+        if (tail && !(nt3 ? a.wpt3 : a.wpt)) continue;
+        const int ntl = tail ? s.ntl : 0;
+        FusedLaunch L2 = L;   // (8 x 8 and 16 x 8 tiles read the same block: the predicate is asked for either tile)
+        L2.ppw2 = true;
+        if (!fused_params_built(L, a.KSe, ntl) && !fused_params_built(L2, a.KSe, ntl)) continue;
+        if (dwl.empty() && dwt.empty()) {
+          if (form == FPF_DIAG64) dwl = pack_dw64_compact(pack_dw64(wd, Ce, k, Cp / 16), k);
+          else if (form == FPF_TOEPLITZ) dwt = pack_expdw2_taps(wd, Ce, 0, Cp / 4, k, S);
+          else dwl = pack_dw_diag(wd, Ce, kk, nt3 ? 48 : 64);
+        }
+        std::vector<v4i> panel;
+        if (tail) pack_weights64_tail(wpj, tout.c, Ce, nch, s.nbp, panel, nt3 ? &kmap : nullptr);
+        else pack_weights64(wpj, tout.c, Ce, nch, s.nbp, panel, nt3 ? &kmap : nullptr);
+        const FusedParamsGeom g = fused_params_geom(NT, a.KSe, form, k, S, s.nbp, ntl);
+        const FusedParamsSrc src{wex.data(), be.data(), me.data(), form == FPF_TOEPLITZ ? (const void*)dwt.data() : (const void*)dwl.data(), bdm.data(), md.data(),
+                                 panel.data(), nch, bp.data(), mp.data()};
+        unsigned char* dev;
+        int rc;
+        if ((rc = upload(m, pack_fused_chunk_params(g, NT, s.nbp, ntl, nch, src), &dev))) return rc;
+        s.cpar[nt3][form][tail] = dev;
+      }
+    }
+  }
+  return VBT_OK;
+}
+
 static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step* out, int sum_op = -1, const NodeSrc* ns = nullptr) {
   const OpRec& dop = m->ops[d_op];
   const OpRec& pop = m->ops[p_op];
@@ -191,8 +250,9 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
       if ((rc = upload(m, wp, &dwp))) return rc;
       a.wpt = dwp;
       s.ntl = proj_tail_tiles(tout.c);
-      for (int i = 0; i < d_op; i++) s.block += m->ops[i].type == OP_DW;   // b1 = the block of the graph's second depthwise conv
     }
+    if (expand)
+      for (int i = 0; i < d_op; i++) s.block += m->ops[i].type == OP_DW;   // b1 = the block of the graph's second depthwise conv
     a.zo = tout.zero_point; a.lop = pop.act_min; a.hip = pop.act_max;
     a.rqp = make_rq(a.zo, a.lop, a.hip);
   }
@@ -223,6 +283,7 @@ static int make_fused(vbt_model* m, int e_op, int d_op, int p_op, int a_op, Step
       a.wpt3 = d3;
     }
   }
+  if (expand && (rc = make_fused_params(m, e_op, d_op, p_op, &s))) return rc;
   if (expand && tin.h * tin.w <= 400 && tout.h * tout.w <= 400 && (rc = make_image_bundle(m, e_op, d_op, p_op, a.KSe, &s.ib))) return rc;
   *out = s;
   return VBT_OK;

@@ -6,10 +6,14 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 #ifdef __HIP__
-#include "dev_common.h"
+#include "launchers.h"
 using vbt::v4i;
+using vbt::FusedParamsGeom;
+#else
+#include "fused_params_geom.h"
 #endif
 
 // Packed MFMA A-operand layout: [(nb*KS + ks)*4 + t][lane][8 bytes]; lane (i = lane&15, g = lane>>4) holds
@@ -341,5 +345,38 @@ inline std::vector<unsigned> pack_expdw2_taps(const int8_t* w, int Ce, int base,
         }
         out[((size_t)q * KT2 + mi) * 64 + lane] = w4;
       }
+  return out;
+}
+
+// Per-chunk parameter block of the fused MBConv tile kernels (fused_params_geom.h; fused_block.h: PLDS): everything a chunk's three
+// stages read, as one contiguous record per chunk, so that a workgroup fetches it once and hands it to its waves through LDS.  The
+// sources are the host images of the arrays the kernels index today, for ONE chunking (NT = 4: we, wdm, wp / wpt; NT = 3: we3, wdm3,
+// wp3 / wpt3), one depthwise form (wdw = wd64c, wtz or wdm / wdm3) and one panel layout (NTL > 0: the tile-major panel):
+struct FusedParamsSrc {
+  const long* we; const int* be; const float* me;         // expand operands | bias | multipliers (padded to 64-channel chunks)
+  const void* wdw; const int* bdm; const float* md;       // depthwise operands of the form | raw-input bias | multipliers
+  const v4i* wproj; int KSp;                              // projection panel and its K-steps (= chunks)
+  const int* bp; const float* mp;                         // projection bias | multipliers, 64 NBP entries each
+};
+inline size_t fused_chunk_params_bytes(const FusedParamsGeom& g, int nch) { return (size_t)nch * g.chunk + g.pb; }
+inline std::vector<unsigned char> pack_fused_chunk_params(const FusedParamsGeom& g, int NT, int NBP, int NTL, int nch, const FusedParamsSrc& s) {
+  std::vector<unsigned char> out(fused_chunk_params_bytes(g, nch), 0);
+  const int CH = 16 * NT, NBW = NTL ? NBP - 1 : NBP;
+  for (int c = 0; c < nch; c++) {
+    unsigned char* R = out.data() + (size_t)c * g.chunk;
+    memcpy(R, (const unsigned char*)s.we + (size_t)c * g.o_be, g.o_be);
+    memcpy(R + g.o_be, s.be + c * CH, 4 * CH);
+    memcpy(R + g.o_me, s.me + c * CH, 4 * CH);
+    R += g.pe;
+    memcpy(R, (const unsigned char*)s.wdw + (size_t)c * g.o_bd, g.o_bd);
+    memcpy(R + g.o_bd, s.bdm + c * CH, 4 * CH);
+    memcpy(R + g.o_md, s.md + c * CH, 4 * CH);
+    R += g.pd;
+    for (int nb = 0; nb < NBW; nb++) memcpy(R + nb * 4096, s.wproj + ((size_t)(nb * s.KSp + c) * 4) * 64, 4096);
+    if (NTL) memcpy(R + NBW * 4096, s.wproj + ((size_t)NBW * s.KSp * 4 + (size_t)c * NTL) * 64, NTL * 1024);
+  }
+  unsigned char* T = out.data() + (size_t)nch * g.chunk;
+  memcpy(T, s.bp, NBP * 256);
+  memcpy(T + NBP * 256, s.mp, NBP * 256);
   return out;
 }

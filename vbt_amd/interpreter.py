@@ -120,6 +120,14 @@ class Interpreter:
             _lib.check(n)
         return n
 
+    def fused_params(self, group, alt, step):
+        """True where that plan-space step is a fused_mbconv launch that fetches its chunk parameters once per workgroup, through LDS
+        (vbt_model_step_fused_params)."""
+        n = _lib.lib().vbt_model_step_fused_params(self._h, group, alt, step)
+        if n < 0:
+            _lib.check(n)
+        return bool(n)
+
     def read_tensor(self, tid, B):
         shp = (ctypes.c_int * 3)()
         _lib.check(_lib.lib().vbt_model_tensor_shape(self._h, tid, shp))
