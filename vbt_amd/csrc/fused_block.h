@@ -20,6 +20,7 @@
 // stages read it from an LDS area behind D; see the comment at fused_block_body.
 #pragma once
 #include "tpz_geom.h"
+#include "halo_geom.h"
 #include "fused_params_geom.h"
 
 struct FusedArgs {
@@ -167,7 +168,9 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   static_assert(!PLDS || (EXPAND && MDW && (KSE == 1 || KSE == 2)), "PLDS: MBConv tiles with register-resident expand weights and no early depthwise request");
   constexpr FusedParamsGeom PG = fused_params_geom(NT, KSE > 0 ? KSE : 1, TPZ ? FPF_TOEPLITZ : DW64 ? FPF_DIAG64 : FPF_MATRIX, KK, S, NBP, NTL);
   constexpr int NPE = PLDS ? PG.pe / 16 : 0, NPD = PLDS ? PG.pd / 16 : 0, NPP = PLDS ? PG.pp / 16 : 0, NPB = PLDS ? PG.pb / 16 : 0;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
+  // (the wave index through readfirstlane: the compiler cannot prove tid >> 6 wave-uniform; with it the per-wave walks below have scalar
+  // counters and trip tests, and `NT == 4 || wave < NT` is a scalar branch)
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 15, g = lane >> 4;
   // tile -> (image, ty, tx) and every later pixel -> (row, column) split go through fdiv_small: no integer division
   // (~40 VALU instructions each) anywhere in the prologue
   const int trow = fdiv_small(tile, frcp(a.tiles_x));
@@ -228,7 +231,7 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       const int hy = fdiv_small(p, rcp_hwx), hx = p - hy * HWx;
       const int iy = iy0 + hy, ix = ix0 + hx;
       unsigned v = zb4;
-      if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+      if (!halo_outside(iy, ix, a.H, a.W)) {
         unsigned us[3] = {0u, 0u, 0u};
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -277,8 +280,9 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
     }
   } else {
     // plain tensor, coalesced along channels; (hy,hx) advance incrementally (no divisions in the loop).
-    // SeparableConv tiles (rows of Cp + 16 bytes, 16-byte aligned) with Cin % 16 == 0 move 16 bytes per lane-iteration.
-    if (!EXPAND && (a.Cin & 15) == 0) {
+    // Cin % 16 == 0: 16 bytes per lane-iteration - half the rounds of the 8-byte form (b1, 16 channels: 2 for its 289 halo pixels instead of
+    // 3).  SeparableConv rows (Cp + 16 bytes) are 16-byte aligned; MBConv rows (Cin + 8 bytes) only 8-byte: two 8-byte stores there.
+    if ((a.Cin & 15) == 0) {
       const int ng = a.Cin >> 4;
       const unsigned zb1 = (unsigned)(a.zx & 255) * 0x01010101u;
       const uint4 zb = make_uint4(zb1, zb1, zb1, zb1);
@@ -290,8 +294,14 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
         const int hy = fdiv_small(p, rcp_hwx), hx = p - hy * HWx;
         const int iy = iy0 + hy, ix = ix0 + hx;
         uint4 v = zb;
-        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = *(const uint4*)(xb + (iy * a.W + ix) * a.Cin + 16 * sg);
-        *(uint4*)(T0 + p * a.T0S + 16 * sg) = v;
+        if (!halo_outside(iy, ix, a.H, a.W)) v = *(const uint4*)(xb + (iy * a.W + ix) * a.Cin + 16 * sg);
+        unsigned char* dst = T0 + p * a.T0S + 16 * sg;
+        if constexpr (EXPAND) {
+          *(uint2*)dst = make_uint2(v.x, v.y);
+          *(uint2*)(dst + 8) = make_uint2(v.z, v.w);
+        } else {
+          *(uint4*)dst = v;
+        }
       }
     } else {
     const int ng = a.Cin >> 3;
@@ -304,7 +314,7 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       const int hy = fdiv_small(p, rcp_hwx), hx = p - hy * HWx;
       const int iy = iy0 + hy, ix = ix0 + hx;
       unsigned long long v = zb;
-      if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = *(const unsigned long long*)(xb + (iy * a.W + ix) * a.Cin + 8 * sg);
+      if (!halo_outside(iy, ix, a.H, a.W)) v = *(const unsigned long long*)(xb + (iy * a.W + ix) * a.Cin + 8 * sg);
       *(unsigned long long*)(T0 + p * a.T0S + 8 * sg) = v;
     }
     }
@@ -316,22 +326,13 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   }
   // which of this wave's halo pixel groups hold out-of-image pixels (expand epilogue), bit i <-> pg = wave + 4i
   const int NPG = (NPh + 15) >> 4;
-  unsigned oob_mask = 0, tail_mask = 0;
-  if (EXPAND) {
-    // interior tiles (halo completely inside the image - most tiles of the large maps) have no out-of-image pixel:
-    // the per-pixel coordinate test is skipped for the whole workgroup
-    const bool border = iy0 < 0 || ix0 < 0 || iy0 + HWy > a.H || ix0 + HWx > a.W;
-    for (int i = 0, pg = wave; pg < NPG; pg += 4, i++) {
-      int p = pg * 16 + r;
-      if (border) {
-        int pc = min(p, NPh - 1);
-        int hy = fdiv_small(pc, rcp_hwx), hx = pc - hy * HWx;
-        int iy = iy0 + hy, ix = ix0 + hx;
-        if (!(iy >= 0 && iy < a.H && ix >= 0 && ix < a.W)) oob_mask |= 1u << i;
-      }
-      if (p >= NPh) tail_mask |= 1u << i;
-    }
-  }
+  // (halo_geom.h; the lanes past the halo's end, on the last group only, need no mask: the expand loop tests p < NPh)
+  unsigned oob_mask = 0;
+  // interior tiles (halo completely inside the image - most tiles of the large maps) have no out-of-image pixel: the whole workgroup
+  // branches round the mask loop (the flag is uniform; held inside the loop the test was if-converted and every tile paid for the
+  // division and the compares) and runs the expand loop's flavour without the select
+  const bool border = EXPAND && halo_border(iy0, ix0, HWx, HWy, a.H, a.W);
+  if (border) oob_mask = halo_oob_mask(wave, r, NPh, HWx, iy0, ix0, a.H, a.W, [&](int p) { return fdiv_small(p, rcp_hwx); });
   v4i acc[PPW][NBP][4];
 #pragma unroll
   for (int pp = 0; pp < PPW; pp++)
@@ -360,7 +361,7 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
   // TPZ: lane (r = position of a group, g = K slice / output pixel of the position) -> E byte offset of its operand (kernel rows
   // 0 / 1, column half g & 1, the wave's first quad) and D byte offset of its output dword on position group 0, once per kernel:
   // every address of the stage is then `lane base + immediate`
-  const int wq0 = TPZ ? __builtin_amdgcn_readfirstlane(wave) * NT : 0;   // the wave's first channel quad of a chunk
+  const int wq0 = TPZ ? wave * NT : 0;   // the wave's first channel quad of a chunk
   int tz_e = 0, tz_d = 0;
   if constexpr (TPZ) {
     tz_e = tpz_e_offset(TG, S, r, g, wq0);
@@ -446,18 +447,22 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
       }
       // the requantisation flavour (saturating / explicitly clamped) is uniform: pick it once, outside the loop, so the
       // loop body stays one basic block and the scheduler can overlap the four MFMAs with the previous tile's epilogue
-      auto expand_loop = [&](auto full_tag) {
+      // the same for the tile's kind: OOB = false (interior tile) has neither the mask bit nor the select
+      auto expand_loop = [&](auto full_tag, auto oob_tag) {
         constexpr int FULLK = decltype(full_tag)::value;
+        constexpr bool OOB = decltype(oob_tag)::value;
         int4 ebk[NT];
 #pragma unroll
         for (int t = 0; t < NT; t++) ebk[t] = int4_plus(eb[t], FULLK >= 2 ? RQ_KBIAS : 0);
+        // (the lane's input row as a 32-bit LDS offset, one 24-bit multiply-add: written as `pc * a.T0S` on the pointer it was a 64-bit
+        // multiply-add.  An offset advanced by 64 T0S per group and clamped to the last pixel's costs the same three instructions and two
+        // more live registers - the 5x5 / 2 kernel then loses its third wave)
         for (int i = 0, pg = wave; pg < NPG; pg += 4, i++) {
           const int p = pg * 16 + r;
-          const int pc = min(p, NPh - 1);
           v4i ea[NT];
 #pragma unroll
           for (int t = 0; t < NT; t++) ea[t] = v4i_from(ebk[t]);
-          const unsigned char* brow = T0 + pc * a.T0S + 8 * g;
+          const unsigned char* brow = T0 + (__umul24((unsigned)min(p, NPh - 1), (unsigned)a.T0S) + 8u * g);
           if constexpr (KSE > 0) {
 #pragma unroll
             for (int ks = 0; ks < KSE; ks++) {
@@ -477,9 +482,10 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
 #pragma unroll
           for (int t = 0; t < NT; t++) {
             d[t] = rq_pack_b<FULLK>(ea[t], em[t], a.rqe);
-            if ((oob_mask >> i) & 1u) d[t] = zeb;
+            if constexpr (OOB)
+              if ((oob_mask >> i) & 1u) d[t] = zeb;
           }
-          if (!((tail_mask >> i) & 1u)) {
+          if (p < NPh) {
             if constexpr (TPZ) {
               // quad-planar: the lane's NT dwords are the quads NT g .. NT g + NT - 1 of halo pixel (hy, hx)
               const int hy = fdiv_small(p, rcp_hwx), hx = p - hy * HWx;
@@ -495,7 +501,8 @@ __device__ __forceinline__ void fused_block_body(const FusedArgs& a, int tile, u
           }
         }
       };
-      rq_dispatch(a.rqe, expand_loop);
+      if (border) rq_dispatch(a.rqe, [&](auto full_tag) { expand_loop(full_tag, std::true_type{}); });
+      else rq_dispatch(a.rqe, [&](auto full_tag) { expand_loop(full_tag, std::false_type{}); });
       __syncthreads();
       if constexpr (PLDS) {
         pp_store(rpe, PAe, tid);             // Pe(c + 1): read at the top of stage E(c + 1), behind barrier 2
