@@ -141,7 +141,7 @@ def postprocess_ref(m, cls, box, chunk=512):
 
 
 def rounds(m, r):
-    """The rounds the kernel's schedule (op_kernels.h: postprocess_kernel, step 3) must run for the reference result r, from the
+    """The rounds the kernel's schedule (k_postprocess.hip: postprocess_kernel, step 3) must run for the reference result r, from the
     reference's histogram, order and `visited` alone: [(kind, n)] with kind 'count4' .. 'count1' (counting sort, threads per key),
     'bitonic', and the same with the prefix 'slice:' for a range of 2048 anchor indices of an oversized bin ('slice:empty': no
     candidate in it).  Ranks are added from the top while fewer than 256 candidates are held and the next bin still fits 2048; the

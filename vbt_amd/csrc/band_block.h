@@ -32,6 +32,10 @@
 #pragma once
 #include <type_traits>
 
+#include "fused_block.h"
+
+namespace vbt {
+
 #ifndef VBT_BD_WAVES
 #define VBT_BD_WAVES 16
 #endif
@@ -592,3 +596,5 @@ __global__ __launch_bounds__(BD_THREADS) void sepconv_band_one_c112_kernel(BandA
   sepconv_band_body<BD_WAVES, 112>(a, (int)blockIdx.x, bd_smem_dyn);
 }
 #endif  // VBT_DEFINE_BAND_KERNELS
+
+}  // namespace vbt

@@ -51,7 +51,7 @@ bool lds_opt_in(const void* fn, LdsOptIn* state);
     }                                                                                    \
   } while (0)
 
-// preprocess_image (reference odt.py:10-19) on device memory (detector.hip, next to the kernel in op_kernels.h); compact != 0: src holds only the row pairs the resize reads
+// preprocess_image (reference odt.py:10-19) on device memory (frames.hip, with its kernel); compact != 0: src holds only the row pairs the resize reads
 int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st);
 // the same for VBT_PIX_NV12 / VBT_PIX_I420 sources, conversion fused (yuv_kernels.h): frame b at src_dev + b * frame_stride, its chroma
 // plane(s) at chroma_off; compact != 0: the luma part holds only the row pairs.  Whole frames: frame_stride H*W*3/2, chroma_off H*W.

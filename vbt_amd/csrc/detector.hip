@@ -1,8 +1,9 @@
 // EfficientDet-Lite int8 detector on gfx950 (MI355X): variant resolution, launches, the forward (eager or hipGraph replay) and the
-// detect entry points of the C ABI.  The single-op kernels are in op_kernels.h, which only this unit includes; the fused kernel families
-// live in their own translation units (k_*.hip, reached through launchers.h).  The model handle and what the detector's units share:
-// detector_model.h; the planner: planner.hip (weight layouts: weight_pack.h); parameter pool, autotuner, plan files and model life
-// cycle: detector_plan.hip; diagnostic timings: detector_profile.hip; error text, device check and LDS opt-in: runtime.hip.
+// detect entry points of the C ABI.  Host code: every kernel - the single-op ones (k_pointwise.hip, k_ops.hip, k_postprocess.hip) and
+// the fused families - lives in a translation unit of its own (k_*.hip) and is reached through launchers.h.  The model handle and what
+// the detector's units share: detector_model.h; the planner: planner.hip (weight layouts: weight_pack.h); parameter pool, autotuner, plan
+// files and model life cycle: detector_plan.hip; diagnostic timings: detector_profile.hip; error text, device check and LDS opt-in:
+// runtime.hip; the frame resize in front of the detector: frames.hip.
 //
 // Replaces the TFLite interpreter invoke at reference odt.py:58-66 (signature_fn(images=...)).
 // Arithmetic contract = the kernels tflite-runtime 2.14 executes on x86-64 (XNNPACK delegate by default, TFLite builtin
@@ -19,18 +20,15 @@
 //   * stand-alone depthwise convs: row / column walkers (v_cvt_f32_ubyteN + v_fma_f32, exact: |sum| < 2^24, 4 channels per
 //     lane on contiguous NHWC channel vectors) or LDS tiles on the matrix pipe (diagonal-embedded weights);
 //   * zero points are folded into the bias on the host at load time; padding uses the zero point;
-//   * decode + NMS: one workgroup per frame, 256-bin score histogram -> bitonic sort of the top
-//     candidates in LDS -> greedy suppression by one wavefront with ballot/shuffle.
+//   * decode + NMS: one workgroup per frame, 256-bin score histogram -> the top candidates sorted in LDS (by counting; a bitonic
+//     network only above 1 024 candidates) -> greedy suppression by one wavefront with ballot / readlane.
 #include <algorithm>
 #include <cmath>
 #include <string>
 
 #include "detector_model.h"
-#include "op_kernels.h"   // the single-op kernels (pw_a ... pw_f, stem, depthwise, add, pool, resize, decode + NMS, frame resize)
 
 namespace vbt {
-
-static_assert(PWM_MAX == PW_MERGE_MAX, "the planner merges as many pointwise convs as one pw_multi_kernel launch takes");
 
 // ---- variant resolution: one pure host function per launch family turns (step, variant, batch; -1 = heuristic default) into the
 // launch it stands for, or refuses it.  The launches, the autotuner's candidates and the plan-file check all ask these.
@@ -95,40 +93,13 @@ static int launch_pw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
   if (L.rc) return L.report();
   const OpRec& pop = m->ops[s.res_op >= 0 ? s.p_op : s.op];
   const TensorRec& tpo = m->tensors[pop.output];
-  const Epi e{s.bias, s.mult, tpo.zero_point, pop.act_min, pop.act_max, make_rq(tpo.zero_point, pop.act_min, pop.act_max)};
-  const ResArgs ra{res, s.addq};
-  const long M = (long)B * tpo.h * tpo.w;
-  const int K = m->tensors[pop.inputs[0]].c, N = tpo.c;
-#define PW(KERNEL, LDS) KERNEL<<<L.grid, 256, LDS, st>>>(x, s.wp64, e, ra, out, M, K, s.KS64, N, s.NB)
-#define PW_A(KS) (L.ms == 2 ? pw_a_kernel<KS, 2><<<L.grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, N, s.NB, L.nb_per_y) \
-                            : pw_a_kernel<KS, 1><<<L.grid, 256, 0, st>>>(x, s.wp64, e, ra, out, M, K, N, s.NB, L.nb_per_y))
-  switch (L.form) {
-    case PW_A: if (s.KS64 == 1) PW_A(1); else if (s.KS64 == 2) PW_A(2); else if (s.KS64 == 3) PW_A(3); else PW_A(4); break;
-    case PW_D: if (L.ms == 2) PW(pw_d_kernel<2>, 0); else PW(pw_d_kernel<1>, 0); break;
-    case PW_C: if (L.ms == 2) PW((pw_c_kernel<1, 2>), 0); else PW((pw_c_kernel<1, 1>), 0); break;
-    case PW_E:
-      if (L.ms == 2) { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<2, 4>); PW((pw_e_kernel<2, 4>), L.lds); }
-      else { if (L.lds > 64 * 1024) VBT_LDS_OPT_IN(pw_e_kernel<1, 4>); PW((pw_e_kernel<1, 4>), L.lds); }
-      break;
-    case PW_F:
-#define PW_F_NB(NBF) (L.ms == 2 ? PW((pw_f_kernel<NBF, 2, 4>), 0) : PW((pw_f_kernel<NBF, 1, 4>), 0))
-#define PW_F_TAIL(NBF, NTL) (L.ms == 2 ? pw_f_kernel<NBF, 2, 4, NTL><<<L.grid, 256, 0, st>>>(x, s.wp64t, e, ra, out, M, K, s.KS64, N, s.NB) \
-                                     : pw_f_kernel<NBF, 1, 4, NTL><<<L.grid, 256, 0, st>>>(x, s.wp64t, e, ra, out, M, K, s.KS64, N, s.NB))
-      if (L.ntl) {   // the pairs of pw_f_tail_built (detector_model.h)
-        if (s.NB == 2 && L.ntl == 1) PW_F_TAIL(2, 1); else if (s.NB == 2 && L.ntl == 2) PW_F_TAIL(2, 2); else if (s.NB == 2 && L.ntl == 3) PW_F_TAIL(2, 3);
-        else if (s.NB == 2) PW_F_TAIL(2, 4); else if (s.NB == 4) PW_F_TAIL(4, 1); else PW_F_TAIL(6, 2);
-      }
-      else if (s.NB == 2) PW_F_NB(2); else if (s.NB == 3) PW_F_NB(3); else if (s.NB == 4) PW_F_NB(4); else if (s.NB == 5) PW_F_NB(5); else PW_F_NB(6);
-#undef PW_F_TAIL
-#undef PW_F_NB
-      break;
-    case PW_B:
-      if (L.nbt == 1) PW(pw_b_kernel<1>, 0); else if (L.nbt == 2) PW(pw_b_kernel<2>, 0); else if (L.nbt == 3) PW(pw_b_kernel<3>, 0); else PW(pw_b_kernel<4>, 0);
-      break;
-  }
-#undef PW
-#undef PW_A
-  return VBT_OK;
+  PwArgs a;
+  a.x = x; a.wp = L.ntl ? s.wp64t : s.wp64; a.out = out;
+  a.e = Epi{s.bias, s.mult, tpo.zero_point, pop.act_min, pop.act_max, make_rq(tpo.zero_point, pop.act_min, pop.act_max)};
+  a.ra = ResArgs{res, s.addq};
+  a.M = (long)B * tpo.h * tpo.w;
+  a.K = m->tensors[pop.inputs[0]].c; a.KS64 = s.KS64; a.N = tpo.c; a.NB = s.NB; a.nb_per_y = L.nb_per_y;
+  return launch_pw(a, L, L.grid, L.lds, st);
 }
 
 // stand-alone depthwise conv: 0 = one output row x 4 columns per lane, 100 / 101 = LDS tiles, chunk-parallel (101: depthwise on the
@@ -172,18 +143,12 @@ static int launch_dw_step(const vbt_model* m, const Step& s, int B, hipStream_t 
     return launch_dw_tile(a, op.k, op.stride, L.mdw, L.grid, L.lds, st);
   }
   const unsigned pb = (unsigned)((128 + ti.zero_point) & 255);
-  const unsigned pad4 = pb | (pb << 8) | (pb << 16) | (pb << 24);
-#define DW_LAUNCH(KERNEL, ...)                                                                    \
-  do {                                                                                            \
-    if (op.k == 3 && op.stride == 1) KERNEL<3, 1><<<L.grid, 256, 0, st>>>(__VA_ARGS__);           \
-    else if (op.k == 3 && op.stride == 2) KERNEL<3, 2><<<L.grid, 256, 0, st>>>(__VA_ARGS__);      \
-    else if (op.k == 5 && op.stride == 1) KERNEL<5, 1><<<L.grid, 256, 0, st>>>(__VA_ARGS__);      \
-    else KERNEL<5, 2><<<L.grid, 256, 0, st>>>(__VA_ARGS__);                                       \
-  } while (0)
-  if (L.form == DW_ROW) DW_LAUNCH(dw_kernel, x, s.wf, e, out, L.total, ti.h, ti.w, to.c, to.h, to.w, op.pad_t, op.pad_l, pad4);
-  else DW_LAUNCH(dw_col_kernel, x, s.wf, e, out, L.total, ti.h, ti.w, to.c, to.h, to.w, op.pad_t, op.pad_l, pad4, L.rows, L.nseg);
-#undef DW_LAUNCH
-  return VBT_OK;
+  DwArgs a;
+  a.x = x; a.wf = s.wf; a.e = e; a.out = out; a.total = L.total;
+  a.H = ti.h; a.W = ti.w; a.C = to.c; a.OH = to.h; a.OW = to.w; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
+  a.pad4 = pb | (pb << 8) | (pb << 16) | (pb << 24);
+  a.rows = L.form == DW_ROW ? 0 : L.rows; a.nseg = L.nseg;
+  return launch_dw(a, op.k, op.stride, L.grid, st);
 }
 
 // fused MBConv / SeparableConv / BiFPN node on LDS tiles (fused_block.h) or, MBConv on a low-resolution map, one workgroup per image
@@ -377,10 +342,7 @@ int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_
   switch (s.family) {
     case F_STEM: {
       const TensorRec& ti = m->tensors[op.inputs[0]];
-      long M = (long)B * to.h * to.w;
-      dim3 grid((unsigned)((M + 63) / 64));
-      stem_kernel<<<grid, 256, 0, st>>>(frame0, s.wp, e, out, M, ti.h, ti.w, to.h, to.w, to.c, op.pad_t, op.pad_l, ti.zero_point);
-      return VBT_OK;
+      return launch_stem(StemArgs{frame0, s.wp, e, out, (long)B * to.h * to.w, ti.h, ti.w, to.h, to.w, to.c, op.pad_t, op.pad_l, ti.zero_point}, st);
     }
     case F_PW: {
       if (s.members.empty())   // op = the op whose output is written: the conv itself, or the residual ADD evaluated in its epilogue (res_op)
@@ -417,30 +379,18 @@ int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_
       }
       pm.n = nconv;
       pm.start[nconv] = acc;
-      for (int i = nconv + 1; i <= PWM_MAX; i++) pm.start[i] = acc;
-      pw_multi_kernel<<<dim3((unsigned)acc), 256, s.nbp ? s.lds_bytes : 0, st>>>(pm);
-      return VBT_OK;
+      for (int i = nconv + 1; i <= PW_MERGE_MAX; i++) pm.start[i] = acc;
+      return launch_pw_multi(pm, (unsigned)acc, s.nbp ? s.lds_bytes : 0, st);
     }
     case F_DW:
       return launch_dw_step(m, s, B, st, TP(op.inputs[0]), out, e);
-    case F_ADD: {
-      long n4 = (long)B * to.h * to.w * to.c / 4;
-      add_kernel<<<dim3((unsigned)((n4 + 1023) / 1024)), 256, 0, st>>>(TP(op.inputs[0]), TP(op.inputs[1]), s.addq, out, n4);
-      return VBT_OK;
-    }
-    case F_MAXPOOL: {
-      const TensorRec& ti = m->tensors[op.inputs[0]];
-      long total = (long)B * to.h * to.w * (to.c / 4);
-      maxpool_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(TP(op.inputs[0]), out, total, ti.h, ti.w, ti.c,
-                                                                             to.h, to.w, op.pad_t, op.pad_l);
-      return VBT_OK;
-    }
+    case F_ADD:
+      return launch_add(TP(op.inputs[0]), TP(op.inputs[1]), s.addq, out, (long)B * to.h * to.w * to.c / 4, st);
+    case F_MAXPOOL:
     case F_RESIZE: {
       const TensorRec& ti = m->tensors[op.inputs[0]];
-      long total = (long)B * to.h * to.w * (to.c / 4);
-      resize_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(TP(op.inputs[0]), out, total, ti.h, ti.w, ti.c,
-                                                                            to.h, to.w);
-      return VBT_OK;
+      const MapArgs a{TP(op.inputs[0]), out, (long)B * to.h * to.w * (to.c / 4), ti.h, ti.w, ti.c, to.h, to.w, op.pad_t, op.pad_l};
+      return s.family == F_MAXPOOL ? launch_maxpool(a, st) : launch_resize_nn(a, st);
     }
     case F_MULTI: {
       if (boff != 0) {  // side-stream sub-batches: pointers differ, launch the members one by one
@@ -484,32 +434,14 @@ int launch_step(vbt_model* m, const Step& s, int B, hipStream_t st, const uint8_
       return launch_stem_block(a, L.direct, (unsigned)((long)B * a.tiles_x * a.tiles_y), st);
     }
     case F_POST: {
-      PostArgs p;
-      int base = 0;
-      p.C = m->hdr.num_classes > 0 ? m->hdr.num_classes : 1;
+      PostArgs p = m->post;   // everything but the head tensors: built once, with the tables (detector_plan.hip)
       for (int l = 0; l < 5; l++) {
-        const TensorRec& tc = m->tensors[op.inputs[l]];
         p.cls[l] = TP(op.inputs[l]);
         p.box[l] = TP(op.inputs[5 + l]);
-        p.base[l] = base;
-        base += tc.h * tc.w * tc.c / p.C;
       }
-      p.base[5] = base;
-      p.anchors = m->d_anchors;
-      p.tables = m->d_luts;
-      p.A = m->hdr.num_anchors;
-      p.max_det = m->hdr.max_detections;
-      p.iou_thr = m->hdr.nms_iou_threshold;
-      int qmin = 128;   // in rank bytes
-      for (int q = 127; q >= -128; q--)
-        if (m->post_tables_host[q + 128] >= m->hdr.nms_score_threshold) qmin = q; else break;
-      p.qmin = qmin;
-      const int lds = post_lds_bytes(p.A);
-      if (lds > 64 * 1024) VBT_LDS_OPT_IN(postprocess_kernel);
-      if (lds > 160 * 1024 || p.A > 65535) { set_error("decode + NMS: %d anchors do not fit the kernel (LDS %d bytes, 16-bit anchor index)", p.A, lds); return VBT_ERR_CAPACITY; }
+      if (m->post_lds > 160 * 1024 || p.A > 65535) { set_error("decode + NMS: %d anchors do not fit the kernel (LDS %d bytes, 16-bit anchor index)", p.A, m->post_lds); return VBT_ERR_CAPACITY; }
       const size_t o = (size_t)boff * m->hdr.max_detections;
-      postprocess_kernel<<<dim3((unsigned)B), POST_THREADS, lds, st>>>(p, boxes + 4 * o, scores + o, classes + o, counts + boff);
-      return VBT_OK;
+      return launch_postprocess(p, m->post_lds, B, boxes + 4 * o, scores + o, classes + o, counts + boff, st);
     }
   }
   return VBT_OK;
@@ -692,52 +624,5 @@ int vbt_model_write_tensor(vbt_model* m, int id, int B, const int8_t* host_in) {
   VBT_HIP_CHECK(hipMemcpy(m->tptr[id], host_in, m->telems[id] * B, hipMemcpyHostToDevice));
   return VBT_OK;
 }
-
-}  // extern "C"
-namespace vbt {
-int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st) {
-  if (compact && H < 2) { set_error("resize: compact rows need a source of at least two rows"); return VBT_ERR_ARG; }
-  const long total = (long)B * h * w;
-  const float sy = (float)H / (float)h, sx = (float)W / (float)w;
-  resize_bilinear_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(src_dev, dst_dev, total, H, W, h, w, sy, sx, swap_rb, compact);
-  VBT_HIP_CHECK(hipGetLastError());
-  return VBT_OK;
-}
-}  // namespace vbt
-extern "C" {
-
-int vbt_resize_frames(const uint8_t* src, int B, int H, int W, int src_on_device, uint8_t* dst, int h, int w, int dst_on_device,
-                      int swap_rb, int device, void* stream) {
-  if (!src || !dst || B < 1 || H < 1 || W < 1 || h < 1 || w < 1) { set_error("vbt_resize_frames: bad argument"); return VBT_ERR_ARG; }
-  if (int rc = use_device("vbt_resize_frames", device)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  size_t sb = (size_t)B * H * W * 3, db = (size_t)B * h * w * 3;
-  DevBuf<uint8_t> ds, dd;   // freed when the function returns: after the stream synchronisation, or - on an error - by a hipFree that waits
-  const uint8_t* sp = src;
-  uint8_t* dp = dst;
-  if (!src_on_device) {
-    VBT_HIP_CHECK(ds.alloc(sb));
-    VBT_HIP_CHECK(hipMemcpyAsync(ds.get(), src, sb, hipMemcpyHostToDevice, st));
-    sp = ds.get();
-  }
-  if (!dst_on_device) {
-    VBT_HIP_CHECK(dd.alloc(db));
-    dp = dd.get();
-  }
-  hipError_t e = resize_frames_dev(sp, B, H, W, dp, h, w, swap_rb, 0, st) == VBT_OK ? hipSuccess : hipErrorLaunchFailure;
-  if (e == hipSuccess && !dst_on_device) e = hipMemcpyAsync(dst, dd.get(), db, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && (ds || dd)) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_error("vbt_resize_frames failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
-  return VBT_OK;
-}
-
-#ifdef VBT_POST_PROF
-int vbt_post_prof_read(unsigned long long* out16, int reset) {
-  if (reset) { unsigned long long z[16] = {0}; VBT_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(vbt::g_post_prof), z, sizeof(z))); return VBT_OK; }
-  VBT_HIP_CHECK(hipDeviceSynchronize());
-  VBT_HIP_CHECK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(vbt::g_post_prof), 16 * sizeof(unsigned long long)));
-  return VBT_OK;
-}
-#endif
 
 }  // extern "C"

@@ -19,9 +19,6 @@ inline const char* const kFamilyName[F_COUNT] = {"stem_conv_mfma_i8", "pw_conv_m
                                                  "maxpool3x3s2", "resize_nn", "decode_nms", "fused_mbconv", "fused_sepconv", "fused_bifpn_node", "fused_heads_multi",
                                                  "fused_stem_block", "fused_expand_dw", "fused_sepconv_band"};
 
-// convs merge_side_convs (planner.hip) puts into one launch: PWM_MAX of pw_multi_kernel (op_kernels.h; detector.hip asserts the two agree)
-constexpr int PW_MERGE_MAX = 8;
-
 // accounting of a step: per-frame bytes / MACs and once-per-launch weight bytes of the graph ops it stands for (element counts far
 // below 2^53: sums are exact in any order)
 struct Cost {
@@ -120,7 +117,8 @@ struct vbt_model {
   size_t out_bytes = 0;
   float* d_anchors = nullptr;
   unsigned char* d_luts = nullptr;   // post-process tables (see PostArgs)
-  std::vector<float> post_tables_host;   // scores indexed by rank byte + 128
+  vbt::PostArgs post = {};           // decode + NMS: everything but the ten head tensor pointers, built once with the tables ...
+  int post_lds = 0;                  // ... and the kernel's dynamic LDS for the model's anchors
   std::vector<vbt::Step> steps;      // execution list (after fusion + autotuning)
   std::vector<vbt::Group> groups;
   std::vector<vbt::Step> op_steps;   // one per graph op (weights live here)
@@ -177,13 +175,7 @@ struct Verdict {   // rc != VBT_OK: the step is refused, and `why` is the error 
   void refuse(int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(why, sizeof(why), fmt, ap); va_end(ap); rc = code; }
   int report() const { set_error("%s", why); return rc; }
 };
-enum PwForm { PW_A, PW_B, PW_C, PW_D, PW_E, PW_F };
-constexpr int PW_F_MAX_NB = 6;   // output blocks whose accumulators one workgroup of the all-blocks form holds (N <= 384)
-// the (output blocks, live tiles of the last block) the all-blocks form is built for with a tile-major last block (variants 9 / 10): the
-// large-K projections of the shipped models - Lite0 80 = 64 + 16 and 112 = 64 + 48, Lite2 88 = 64 + 24, 120 = 64 + 56 (four tiles, the
-// last one part-filled), 208 = 3 x 64 + 16 and 352 = 5 x 64 + 32.  Another width needs a line here and one in launch_pw_step.
-static inline bool pw_f_tail_built(int NB, int ntl) { return (NB == 2 && ntl >= 1 && ntl <= 4) || (NB == 4 && ntl == 1) || (NB == 6 && ntl == 2); }
-struct PwLaunch : Verdict { PwForm form = PW_B; int ms = 1, nbt = 1, nb_per_y = 0, lds = 0, ntl = 0; dim3 grid; };
+struct PwLaunch : Verdict, PwKernel { int nb_per_y = 0, lds = 0; dim3 grid; };   // (PwKernel, PW_F_MAX_NB, pw_f_tail_built: op_args.h)
 enum DwForm { DW_ROW, DW_COL, DW_TILE };
 struct DwLaunch : Verdict {   // tile geometry (DW_TILE), rows per lane and row segments (DW_COL), lanes (DW_ROW / DW_COL)
   DwForm form = DW_COL; bool mdw = false; int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0, lds = 0, rows = 0, nseg = 0; long total = 0; dim3 grid;

@@ -449,7 +449,23 @@ int vbt_model_create_ex(const char* path, int device, int max_batch, int flags, 
       for (int i = -128; i < r; i++) score_by_rank[i + 128] = -1.0f;   // unused rank bytes: below every threshold
       memcpy(dev.data() + 1024, lut.data() + 2048, 4096);
       if ((rc = upload(m, an, &m->d_anchors)) || (rc = upload(m, dev, &m->d_luts))) return fail(rc);
-      m->post_tables_host.assign(score_by_rank, score_by_rank + 256);
+      // the kernel's arguments, all but the head tensor pointers of a launch (launch_step: F_POST)
+      PostArgs& p = m->post;
+      p.C = m->hdr.num_classes > 0 ? m->hdr.num_classes : 1;
+      p.base[0] = 0;
+      for (int l = 0; l < 5; l++) {
+        const TensorRec& tl = m->tensors[op.inputs[l]];
+        p.base[l + 1] = p.base[l] + tl.h * tl.w * tl.c / p.C;
+      }
+      p.anchors = m->d_anchors;
+      p.tables = m->d_luts;
+      p.A = m->hdr.num_anchors;
+      p.max_det = m->hdr.max_detections;
+      p.iou_thr = m->hdr.nms_iou_threshold;
+      p.qmin = 128;   // in rank bytes
+      for (int q = 127; q >= -128; q--)
+        if (score_by_rank[q + 128] >= m->hdr.nms_score_threshold) p.qmin = q; else break;
+      m->post_lds = post_lds_bytes(p.A);
     }
   {
     const char* ns = getenv("VBT_SUBSTREAMS");

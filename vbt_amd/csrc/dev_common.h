@@ -139,6 +139,17 @@ __device__ __forceinline__ unsigned addq4(unsigned ua, unsigned ub, const AddQ& 
   return r ^ 0x80808080u;
 }
 
+// maxima of four int8 lanes per dword (the max pools of k_ops.hip and k_pointwise.hip)
+__device__ __forceinline__ unsigned max4_s8(unsigned a, unsigned b) {
+  unsigned r = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    int x = (int)(int8_t)(a >> (8 * j)), y = (int)(int8_t)(b >> (8 * j));
+    r |= (unsigned)(max(x, y) & 255) << (8 * j);
+  }
+  return r;
+}
+
 struct Epi {  // requantisation parameters of one conv
   const int* bias;    // folded bias, padded to NB*64
   const float* mult;  // padded to NB*64

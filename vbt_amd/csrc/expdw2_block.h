@@ -29,12 +29,15 @@
 #pragma once
 #include <type_traits>
 
+#include "expdw_block.h"
+
 #ifdef VBT_XD_PROF
 #define XD2_STAMP(k) do { if (tid == 0) a.prof[(long)blockIdx.x * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define XD2_STAMP(k) do { } while (0)
 #endif
 
+namespace vbt {
 
 struct ExpDw2Args {
   const int8_t* x;   // [B][H][W][Cin]
@@ -290,3 +293,5 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
   copy_out(c_last - 1);
   XD2_STAMP(2 + 2 * (c_last - c_first));
 }
+
+}  // namespace vbt

@@ -19,6 +19,9 @@
 // instruction: out[c][p] = sum_t W'[c][(t,c')] X[(t,c')][p], W' = w[t][c] delta(c,c'), exact int32.
 // Arithmetic identical to the per-op kernels: same integer accumulations, same single-op float requantisation.
 #pragma once
+#include "fused_block.h"
+
+namespace vbt {
 
 // Waves per workgroup.  Measured end to end with three forwards in flight (A/B of two builds on one box): 16 waves 90.2 k
 // frames/s, 8 waves 91.9 k (92.5 k with the chunks per workgroup re-tuned), 4 waves 86.6 k.  A 16-wave workgroup is faster alone
@@ -172,3 +175,5 @@ __global__ __launch_bounds__(XD_THREADS) void expdw_image_kernel(ExpDwArgs a) {
     }
   }
 }
+
+}  // namespace vbt

@@ -1,6 +1,7 @@
 // Frame plumbing in front of the detector (gfx950): assembling a detector batch from frames that live in different
-// places of device memory (HBM-bound byte moves: 16 bytes per lane, consecutive lanes on consecutive addresses), and the
-// YUV 4:2:0 entry of preprocess_image (yuv_kernels.h: NV12 / I420 -> RGB fused into the bilinear resize).
+// places of device memory (HBM-bound byte moves: 16 bytes per lane, consecutive lanes on consecutive addresses), and the two
+// entries of preprocess_image: the bilinear resize of RGB frames and its YUV 4:2:0 twin (yuv_kernels.h: NV12 / I420 -> RGB fused
+// into the same resize).
 #include <dlfcn.h>
 
 #include "common.h"
@@ -22,6 +23,55 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(uint4* __restrict__ 
 #pragma unroll 4
   for (int k = 0; k < per; k++, i += 256)
     if (i < frame_vec) d[i] = s[i];
+}
+
+// ------------------------------------------------------------------------------------------
+// preprocess_image (reference odt.py:10-19): tf.image.resize bilinear with half-pixel centres
+// [EXTERNAL TF2 ResizeBilinear: in = (out+0.5)*scale-0.5, lower = max(floor(in),0),
+// upper = min(ceil(in), size-1), lerp = in - floor(in); top + (bottom-top)*ly], float32,
+// then tf.cast(..., uint8) = truncation.  Optional BGR->RGB swap (reference track.py:171).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                              long total, int H, int W, int h, int w, float sy, float sx,
+                                                              int swap_rb, int compact) {
+  long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  int ox = (int)(idx % w);
+  long t = idx / w;
+  int oy = (int)(t % h);
+  long b = t / h;
+  float iy = ((float)oy + 0.5f) * sy - 0.5f, ix = ((float)ox + 0.5f) * sx - 0.5f;
+  float fy = floorf(iy), fx = floorf(ix);
+  int y0 = max((int)fy, 0), y1 = min((int)ceilf(iy), H - 1);
+  int x0 = max((int)fx, 0), x1 = min((int)ceilf(ix), W - 1);
+  float ly = iy - fy, lx = ix - fx;
+  // compact: the source holds only the row pairs the resize reads, [B][2h][W][3]: pair oy = source rows p, p + 1 with p = min(y0, H - 2)
+  // (the host-fed pipeline uploads nothing else, pipeline.hip); y0 and y1 then become rows 2 oy + (y - p)
+  const uint8_t* s = src + b * (long)(compact ? 2 * h : H) * W * 3;
+  if (compact) {
+    const int p = min(y0, H - 2);
+    y0 = 2 * oy + (y0 - p);
+    y1 = 2 * oy + (y1 - p);
+  }
+  uint8_t* d = dst + ((b * h + oy) * (long)w + ox) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float tl = (float)s[((long)y0 * W + x0) * 3 + c], tr = (float)s[((long)y0 * W + x1) * 3 + c];
+    float bl = (float)s[((long)y1 * W + x0) * 3 + c], br = (float)s[((long)y1 * W + x1) * 3 + c];
+    float top = tl + (tr - tl) * lx;
+    float bot = bl + (br - bl) * lx;
+    float v = top + (bot - top) * ly;
+    d[swap_rb ? 2 - c : c] = (uint8_t)(int)v;
+  }
+}
+
+int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st) {
+  if (compact && H < 2) { set_error("resize: compact rows need a source of at least two rows"); return VBT_ERR_ARG; }
+  const long total = (long)B * h * w;
+  const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+  resize_bilinear_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(src_dev, dst_dev, total, H, W, h, w, sy, sx, swap_rb, compact);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
 }
 
 int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_fmt, size_t frame_stride, size_t chroma_off, int compact,
@@ -80,6 +130,31 @@ extern "C" int vbt_gather_frames(uint8_t* dst_dev, const uint8_t* const* src_fra
     gather_frames_kernel<<<dim3(chunks, (unsigned)nb), 256, 0, (hipStream_t)stream>>>((uint4*)(dst_dev + (size_t)f0 * frame_bytes), meta, vec, per);
   }
   VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+extern "C" int vbt_resize_frames(const uint8_t* src, int B, int H, int W, int src_on_device, uint8_t* dst, int h, int w, int dst_on_device,
+                                 int swap_rb, int device, void* stream) {
+  if (!src || !dst || B < 1 || H < 1 || W < 1 || h < 1 || w < 1) { set_error("vbt_resize_frames: bad argument"); return VBT_ERR_ARG; }
+  if (int rc = use_device("vbt_resize_frames", device)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  size_t sb = (size_t)B * H * W * 3, db = (size_t)B * h * w * 3;
+  DevBuf<uint8_t> ds, dd;   // freed when the function returns: after the stream synchronisation, or - on an error - by a hipFree that waits
+  const uint8_t* sp = src;
+  uint8_t* dp = dst;
+  if (!src_on_device) {
+    VBT_HIP_CHECK(ds.alloc(sb));
+    VBT_HIP_CHECK(hipMemcpyAsync(ds.get(), src, sb, hipMemcpyHostToDevice, st));
+    sp = ds.get();
+  }
+  if (!dst_on_device) {
+    VBT_HIP_CHECK(dd.alloc(db));
+    dp = dd.get();
+  }
+  hipError_t e = resize_frames_dev(sp, B, H, W, dp, h, w, swap_rb, 0, st) == VBT_OK ? hipSuccess : hipErrorLaunchFailure;
+  if (e == hipSuccess && !dst_on_device) e = hipMemcpyAsync(dst, dd.get(), db, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && (ds || dd)) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { set_error("vbt_resize_frames failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   return VBT_OK;
 }
 

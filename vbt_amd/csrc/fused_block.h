@@ -22,6 +22,9 @@
 #include "tpz_geom.h"
 #include "halo_geom.h"
 #include "fused_params_geom.h"
+#include "dev_common.h"
+
+namespace vbt {
 
 struct FusedArgs {
   const int8_t* x;
@@ -961,3 +964,5 @@ __global__ __launch_bounds__(256) void dw_tile_kernel(DwTileArgs a) {
     }
   }
 }
+
+}  // namespace vbt

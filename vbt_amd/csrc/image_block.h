@@ -16,6 +16,9 @@
 // registers across chunks.  Depthwise weights travel compact ([tap][64] bytes); the diagonal MFMA operand is rebuilt in
 // registers once per chunk.  Same integer / float arithmetic as the tile kernel: identical results.
 #pragma once
+#include "fused_block.h"
+
+namespace vbt {
 
 constexpr int IB_WAVES = 16, IB_THREADS = 64 * IB_WAVES, IB_NPF = 3;  // NPF uint4 prefetch registers per lane (48 KB bundles)
 
@@ -174,3 +177,5 @@ __global__ __launch_bounds__(IB_THREADS) void mbconv_image_kernel(FusedArgs a, I
     }
   }
 }
+
+}  // namespace vbt

@@ -518,7 +518,7 @@ VBT_HD inline void jpeg_pixel(const JpegDesc& d, const JpegLayout& L, const uint
 // the host and handed to the kernel
 inline float jpeg_resize_scale(int n_in, int n_out) { return (float)n_in / (float)n_out; }
 
-// Output pixel (oy, ox) of the bilinear resize (half-pixel centres, float32, truncating cast: resize_bilinear_kernel, op_kernels.h)
+// Output pixel (oy, ox) of the bilinear resize (half-pixel centres, float32, truncating cast: resize_bilinear_kernel, frames.hip)
 // of a frame that exists only as its planes: the four taps are jpeg_pixel - fancy upsampling and colour at full resolution - and
 // they are lerped in the order yuv_resize_kernel (yuv_kernels.h) uses.  sy = H / h, sx = W / w (jpeg_resize_scale).  Taps are
 // clamped to 0 .. H - 1 and 0 .. W - 1, so jpeg_pixel reads what it reads for the frame's own pixels and nothing else.

@@ -1,17 +1,19 @@
 // Host-side entry points of the kernel translation units (k_*.hip).  Each kernel family is compiled in its own translation
 // unit - the template instantiations of the fused MBConv / SeparableConv tiles alone are most of the library's build time -
-// and the planner (detector.hip) reaches the kernels only through these launchers: plain argument structs in, one launch
-// enqueued on `st` out.  A launcher returns VBT_OK or VBT_ERR_ARG (no such instantiation) and sets the error text.
+// and the launch logic (detector.hip) reaches the kernels only through these launchers: plain argument structs in, one launch
+// enqueued on `st` out.  A launcher returns VBT_OK, VBT_ERR_ARG (no such instantiation) or VBT_ERR_HIP (an LDS opt-in refused) and
+// sets the error text.
 #pragma once
 #include "dev_common.h"
-
-namespace vbt {
 #include "fused_block.h"   // FusedArgs, MultiTiles, DwTileArgs, FB_* tile constants (+ the kernel templates)
 #include "stem_block.h"    // StemBlockArgs
 #include "image_block.h"   // ImageBundle, IB_*
 #include "expdw_block.h"   // ExpDwArgs, XD_*
 #include "expdw2_block.h"  // ExpDw2Args, XD2_*
 #include "band_block.h"    // BandArgs, BD_*
+#include "op_args.h"       // PwArgs, PwKernel, PwMulti, StemArgs, DwArgs, MapArgs, PostArgs
+
+namespace vbt {
 
 // fused MBConv / SeparableConv / BiFPN node on LDS tiles (fused_block.h): which instantiation to run
 struct FusedLaunch {
@@ -81,5 +83,21 @@ int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int 
 // network entry: stem 3x3/2 + first SeparableConv (stem_block.h)
 // (direct: the second form of the kernel, plan variant 1)
 int launch_stem_block(const StemBlockArgs& a, bool direct, unsigned grid, hipStream_t st);
+
+// ---- the single-op kernels (op_args.h) ----
+// pointwise conv, one of six forms (k_pointwise.hip); lds_bytes: the dynamic LDS of PW_E (its weight panel)
+int launch_pw(const PwArgs& a, const PwKernel& k, dim3 grid, int lds_bytes, hipStream_t st);
+// several pointwise convs in one grid; lds_bytes: the conv output + first pooled map of a problem that carries its two max pools, else 0
+int launch_pw_multi(const PwMulti& pm, unsigned grid, int lds_bytes, hipStream_t st);
+// stem conv 3x3/2 on the uint8 frames, 64 output pixels per workgroup (k_ops.hip, with the five below)
+int launch_stem(const StemArgs& a, hipStream_t st);
+// stand-alone depthwise conv, row form or column walker (DwArgs::rows); k x k taps, stride 1 or 2
+int launch_dw(const DwArgs& a, int k, int stride, dim3 grid, hipStream_t st);
+int launch_add(const int8_t* xa, const int8_t* xb, const AddQ& q, int8_t* out, long n4, hipStream_t st);   // n4: dwords
+int launch_maxpool(const MapArgs& a, hipStream_t st);
+int launch_resize_nn(const MapArgs& a, hipStream_t st);
+// decode + NMS, one workgroup per frame (k_postprocess.hip); post_lds_bytes: its dynamic LDS for A anchors
+int post_lds_bytes(int A);
+int launch_postprocess(const PostArgs& p, int lds_bytes, int B, float* boxes, float* scores, float* classes, int* counts, hipStream_t st);
 
 }  // namespace vbt

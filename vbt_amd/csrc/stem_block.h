@@ -14,6 +14,9 @@
 // depthwise: diagonal-embedded weights on the 16x16x64 MFMA, tap (row m, column g) per instruction m and lane group g
 // (three instructions for 3x3, every LDS address = lane base + immediate; see DW64 in fused_block.h).
 #pragma once
+#include "fused_block.h"
+
+namespace vbt {
 
 struct StemBlockArgs {
   const uint8_t* frames;
@@ -287,3 +290,5 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
     }
   }
 }
+
+}  // namespace vbt

@@ -13,7 +13,7 @@
 //   DSK  bytes the D tile's pixel slots shift per tile row (stride 1): a lane's output dwords then spread over all the banks a
 //        16-byte-aligned slot pitch can reach (4-way instead of 8-way stores)
 struct TpzGeom { int XB, EQS, EYS, rows, e_bytes, DSK; };
-// the lanes a ds_read_b128 serves together: four groups of 16, one LDS cycle each when conflict-free (also planner.h: xd2_read_cycles)
+// the lanes a ds_read_b128 serves together: four groups of 16, one LDS cycle each when conflict-free (also planner.hip: xd2_read_cycles)
 constexpr int DS_READ_B128_GROUPS[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                             {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                             {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},

@@ -1,20 +1,16 @@
 // Host-side weight / bias layouts of the detector's kernels: one pure function per layout.  Every function reads the container blob
 // (int8 weights, int32 biases, float multipliers) and shapes, and returns the host image of what a kernel reads; none touches the
 // model or HIP.  Weight orders in the blob: convs (stem, pointwise) are rows [cout][K], depthwise convs are taps [tap][C].
-// The functions sit at global scope.  v4i: dev_common.h's in a HIP unit (planner.hip); a plain C++ program that includes this header on
-// its own (tests/test_band_pack_host.py, tests/test_toeplitz_pack_host.py) defines its own 16-byte int vector first.
+// The functions sit at global scope, like the geometry headers they share with the kernels (fused_params_geom.h, tpz_geom.h, halo_geom.h).
+// v4i, the 16-byte int vector of the MFMA operands, is the includer's, named at global scope before this header: planner.hip names
+// dev_common.h's (using vbt::v4i), a plain C++ program (tests/test_band_pack_host.py, tests/test_toeplitz_pack_host.py) defines its own.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
-#ifdef __HIP__
-#include "launchers.h"
-using vbt::v4i;
-using vbt::FusedParamsGeom;
-#else
+
 #include "fused_params_geom.h"
-#endif
 
 // Packed MFMA A-operand layout: [(nb*KS + ks)*4 + t][lane][8 bytes]; lane (i = lane&15, g = lane>>4) holds
 // W[cout = 64nb + 16(i>>2) + 4t + (i&3)][k = 32ks + 8g + j].  kmap translates packed k -> source k (or -1).

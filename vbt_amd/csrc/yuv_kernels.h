@@ -3,7 +3,7 @@
 // A decoder emits NV12 or I420, not packed RGB (the reference's cv2.VideoCapture converts inside the decoder, track.py:135,160).  The
 // kernel below reads the four source pixels of the bilinear resize straight from the planes, converts each to uint8 RGB with the
 // integer BT.601 limited-range formula (20-bit fixed point, int32), and lerps them in float32 exactly as resize_bilinear_kernel
-// (op_kernels.h) does - a full-resolution RGB frame is never written.  The result is, bit for bit,
+// (frames.hip) does - a full-resolution RGB frame is never written.  The result is, bit for bit,
 // preprocess_image(rgb_from_yuv(frame)).
 #pragma once
 #include <hip/hip_runtime.h>
