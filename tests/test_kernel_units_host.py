@@ -1,7 +1,8 @@
 """Where kernels may live under vbt_amd/csrc, as a text scan (no compiler, no GPU):
-the detector's host units hold no kernel and no launch; no #include sits inside an open namespace or extern "C" block, so a name's
-scope never depends on who included a header first; and a header with kernel bodies belongs to exactly one translation unit (the
-*_block.h headers of launchers.h still carry argument structs and kernel templates together and are the exception)."""
+the detector's host units hold no kernel and no launch, and neither they nor launchers.h / plan_geom.h reach a header with a kernel or a
+device builtin; no #include sits inside an open namespace or extern "C" block, so a name's scope never depends on who included a header
+first; a header with kernel bodies belongs to exactly one translation unit - but for fused_block.h, whose users are the fused units its
+top comment lists; and no *_block.h reaches another."""
 import functools
 import os
 import re
@@ -137,14 +138,35 @@ def _closure(name):
     return seen
 
 
+def _device_headers(names):
+    return sorted(h for h in names if "__global__" in _stripped(h) or "__builtin_amdgcn_" in _stripped(h))
+
+
+def test_host_units_and_launchers_reach_no_kernel_header():
+    for name in HOST_UNITS + ["launchers.h", "plan_geom.h"]:
+        bad = _device_headers(_closure(name))
+        assert not bad, f"{name} includes {bad}: argument headers only on the host side"
+    assert _device_headers(["dev_common.h", "fused_block.h"]) == ["dev_common.h", "fused_block.h"], "the scan finds no device code at all"
+
+
 def test_a_header_with_kernels_belongs_to_one_unit():
     units = {u: _closure(u) for u in _sources() if u.endswith(".hip")}
     with_kernels = [h for h in _sources() if h.endswith(".h") and "__global__" in _stripped(h)]
     assert with_kernels, "the scan found no header with a kernel at all"
-    blocks = set(_direct_includes("launchers.h"))
+    assert "fused_block.h" in with_kernels
     for h in with_kernels:
-        if h.endswith("_block.h"):
-            assert h in blocks, f"{h}: the exception covers the block headers of launchers.h only"
-            continue
         users = sorted(u for u, inc in units.items() if h in inc)
+        if h == "fused_block.h":   # the one kernel header several units instantiate: the units its top comment names
+            raw = open(os.path.join(CSRC, h)).read()
+            listed = sorted(set(re.findall(r"\bk_\w+\.hip\b", raw[:raw.index("#pragma once")])))
+            assert listed and users == listed, f"{h} is reached by {users}, its top comment lists {listed}"
+            continue
         assert len(users) == 1, f"{h} holds kernel bodies and is reached by {users or 'no unit'}: exactly one unit may include it"
+
+
+def test_no_block_header_reaches_another():
+    blocks = [h for h in _sources() if h.endswith("_block.h")]
+    assert len(blocks) >= 6
+    for h in blocks:
+        inner = sorted(x for x in _closure(h) if x.endswith("_block.h") and x != h)
+        assert not inner, f"{h} includes {inner}"

@@ -5,16 +5,14 @@
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
-#include "../../vbt_amd/csrc/dev_common.h"
+#include "../../vbt_amd/csrc/band_block.h"
 namespace vbt {
 void set_error(const char*, ...) {}
 
-#include "../../vbt_amd/csrc/fused_block.h"
-#include "../../vbt_amd/csrc/band_block.h"
 template <int NW, bool C64>
 __global__ __launch_bounds__(64 * NW) void band_probe_kernel(BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  sepconv_band_body<NW, C64>(a, (int)blockIdx.x, smem);
+  sepconv_band_body<NW, C64 ? 64 : 0>(a, (int)blockIdx.x, smem);   // (the width at compile time, or from the arguments)
 }
 }
 using namespace vbt;

@@ -8,14 +8,14 @@
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
-#include "../../vbt_amd/csrc/dev_common.h"
+#include "../../vbt_amd/csrc/expdw2_block.h"
 namespace vbt {
 void set_error(const char*, ...) {}
-#include "../../vbt_amd/csrc/expdw2_block.h"
 }
 using namespace vbt;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
+constexpr int XD2_NW = 8, XD2_THREADS = 64 * XD2_NW;   // the 8-wave shape of the kernel, stride 1
 template <int KK, int KS64, int GPW>
 static void run2(const char* name, int H, int Cin, int Ce, int cpw, int B, int eys_pad) {
   ExpDw2Args a{};
@@ -41,12 +41,12 @@ static void run2(const char* name, int H, int Cin, int Ce, int cpw, int B, int e
   a.rqe = make_rq(-128, -128, 127); a.rqd = make_rq(-128, -128, 127);
   a.zeb = 0x80808080u;
   CK(hipMalloc(&a.prof, (size_t)grid * 32 * 8)); CK(hipMemset(a.prof, 0, (size_t)grid * 32 * 8));
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&expdw2_kernel<KK, KS64, GPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&expdw2_kernel<KK, 1, KS64, XD2_NW, GPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   float best = 1e9f;
   for (int it = 0; it < 6; it++) {
     CK(hipEventRecord(e0));
-    expdw2_kernel<KK, KS64, GPW><<<grid, XD2_THREADS, lds>>>(a);
+    expdw2_kernel<KK, 1, KS64, XD2_NW, GPW><<<grid, XD2_THREADS, lds>>>(a);
     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms);
   }

@@ -1,6 +1,6 @@
 // SeparableConv (depthwise 3x3 / 1 SAME -> pointwise) on ROW BANDS of a C-channel map (C = the BiFPN width: 64 / 88 / 112 for
 // EfficientDet-Lite0 / 1 / 2): the BiFPN nodes and the box / class head layers.  Optional BiFPN node input: the band is the sum (+ReLU6) of two or
-// three resampled sources (binary integer ADDs, node_sum4 of fused_block.h).
+// three resampled sources (binary integer ADDs, in the order of node_sum4, fused_block.h).
 //
 // Why not the 64-pixel tile kernel (fused_block.h) here: on these layers a tile does ~120 wave-instructions of
 // requantisation but ~550 in all - tile decode, halo addressing, parameter loads, the epilogue's addressing are paid per 64
@@ -32,19 +32,11 @@
 #pragma once
 #include <type_traits>
 
-#include "fused_block.h"
+#include "dev_common.h"
+#include "band_args.h"
+#include "fused_args.h"   // MultiTiles
 
 namespace vbt {
-
-#ifndef VBT_BD_WAVES
-#define VBT_BD_WAVES 16
-#endif
-constexpr int BD_WAVES = VBT_BD_WAVES, BD_THREADS = 64 * BD_WAVES;
-constexpr int BD_LIT = 3;           // lane-iterations of the load stage whose global loads are in flight together (plain input)
-constexpr int BD_LIT_NODE = 1;      // the same for a node's source loads (up to three 16-byte loads per iteration; registers: the head layers share this kernel)
-constexpr int BD_LIT_NODE_WIDE = 3; // maps of more than 64 channels: LDS leaves at most four waves per SIMD, so 128 registers are free to use
-constexpr int BD_WP_TAIL = 1024;   // bias (512 B) | multipliers (512 B) behind the projection weights in LDS
-constexpr int BD_WD_CHAIN = 12 * 1024 + 512;   // chained form: the twelve depthwise operands | bias (256 B) | multipliers (256 B) behind that
 
 // Developer build (tools/probes/bd_probe.hip): s_memtime stamps of wave 0 at the stage boundaries of every workgroup.
 #ifdef VBT_BD_PROF
@@ -52,32 +44,6 @@ constexpr int BD_WD_CHAIN = 12 * 1024 + 512;   // chained form: the twelve depth
 #else
 #define BD_STAMP(k) do { } while (0)
 #endif
-
-struct BandArgs {
-  const int8_t* x;   // [B][H][W][C] (plain input; unused when n_src > 0)
-  int8_t* out;       // [B][H][W][Cout]
-  int H, W, Cout, rows, nbands;
-  int C, CS;         // input channels (% 8 == 0) / bytes per pixel row of T0 and D: odd multiple of 16 >= C
-  int NCG, KS;       // 16-channel groups of the depthwise: ceil(C / 16) / projection K-steps of 64: ceil(C / 64)
-  unsigned zx4;      // zero point of the depthwise input x4
-  const v4i* wd;     // [cg][m][lane] x 16 B: row i = channel 16cg + i, k = 16g + j -> tap 4m + g, diagonal j == i
-  const int* bd;     // bias with the input zero point folded (16 NCG)
-  const float* md;
-  Rq rqd;
-  const v4i* wp;     // [t][ks][lane] x 16 B: row i = output channel 16t + i, k = 64ks + 16g + j
-  const v4i* wpc;    // chained form (C == 64, else null): [t][lane] x 16 B: row i = output channel 16t + i, byte 4cg + j = k 16cg + 4g + j
-  const int* bp;     // bias with the depthwise output's zero point folded, padded to 64-channel blocks
-  const float* mp;
-  Rq rqp;
-  // BiFPN node: see FusedArgs
-  int n_src, chain;
-  const int8_t* src[3];
-  int sh[3], sw[3], smode[3], spt[3], spl[3];
-  AddQ sumq, preq;
-#ifdef VBT_BD_PROF
-  unsigned long long* prof;
-#endif
-};
 
 __device__ __forceinline__ unsigned band_source4(const BandArgs& a, int j, long b, int iy, int ix, int cd, bool up2) {
   const int C = a.C;
@@ -536,19 +502,7 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
 }
 
 // Several problems in one grid (the same head layer on all pyramid levels of both heads): the problem list lives in HBM.
-#ifndef VBT_BD_HEAD_WAVES
-#define VBT_BD_HEAD_WAVES 8
-#endif
-#ifndef VBT_BD_HEAD_MAXPX
-#define VBT_BD_HEAD_MAXPX 240
-#endif
-constexpr int BD_HEAD_WAVES = VBT_BD_HEAD_WAVES, BD_HEAD_MAXPX = VBT_BD_HEAD_MAXPX;
-// Maps of more than 64 channels (Lite1 / Lite2): 16 waves, held to 64 registers so that two workgroups still share a CU.  With 6 or 7
-// channel groups only NCG * (NW / NCG) waves work in the depthwise stage - 7 of 8, each with every pixel group of the band, against 14 of
-// 16 with half of them (tools/probes/bd_probe.hip, Lite2 head layer at 56x56: 24 000 cycles per band on 8 waves, 16 300 on 16; with
-// one 16-wave workgroup per CU - what an 84-register build gets - the launch was slower all the same).
-constexpr int BD_HEAD_WAVES_WIDE = 16;
-#ifdef VBT_DEFINE_BAND_KERNELS   // the entry points are not templates: exactly one translation unit (k_band.hip) defines them
+// (The entry points are not templates: this header has one includer, k_band.hip.)
 __device__ __forceinline__ int band_problem(const MultiTiles& mt) {
   int pi = 0;
 #pragma unroll
@@ -595,6 +549,5 @@ __global__ __launch_bounds__(BD_THREADS) void sepconv_band_one_c112_kernel(BandA
   extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];
   sepconv_band_body<BD_WAVES, 112>(a, (int)blockIdx.x, bd_smem_dyn);
 }
-#endif  // VBT_DEFINE_BAND_KERNELS
 
 }  // namespace vbt

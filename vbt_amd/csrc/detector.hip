@@ -27,6 +27,7 @@
 #include <string>
 
 #include "detector_model.h"
+#include "tpz_geom.h"   // the Toeplitz form's LDS geometry (resolve_fused)
 
 namespace vbt {
 

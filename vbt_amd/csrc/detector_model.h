@@ -9,7 +9,7 @@
 
 #include "dev_mem.h"
 #include "hip_handles.h"
-#include "launchers.h"   // dev_common.h + the argument structs / tile constants of every kernel family + the launchers
+#include "launchers.h"   // the argument structs / tile constants of every kernel family + the launchers
 #include "plan_geom.h"
 
 namespace vbt {

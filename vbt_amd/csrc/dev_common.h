@@ -1,11 +1,9 @@
 // Device-side helpers shared by every kernel translation unit of libvbt_hip.so: the exact requantisation of the int8
 // convolutions (XNNPACK qs8-qc8w, fp32 scale), the integer ADD (qs8-vadd-minmax) and the MFMA tile store.
 #pragma once
-#include "common.h"
+#include "dev_types.h"   // v4i, Rq, RQ_KBIAS, make_rq, AddQ, make_addq, Epi
 
 namespace vbt {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------
 // device helpers
@@ -20,24 +18,7 @@ __device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) {
   return (unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24);
 }
 
-// The same requantisation in 5 VALU ops + 1 pack op per element: clamp(rne(t) + zp, lo, hi) ==
-// clamp(rne(t), lo - zp, hi - zp) + zp because every quantity after rne() is an exact small integer in
-// fp32; the result is produced in the unsigned domain (q + 128 in [0,255]) so v_cvt_pk_u8_f32 can pack
-// it, and one XOR 0x80808080 per dword turns the four bytes back into int8.
-struct Rq {
-  float lo_f, hi_f, off;  // lo - zp, hi - zp, zp + 128
-  int full;               // lo == -128 && hi == 127: the clamp is the [0,255] saturation of v_cvt_pk_u8_f32 itself
-  int kb;                 // every accumulator of this conv (bias included) lies in (-2^22, 2^22) - proven on the host from the weights
-                          // (conv_acc_bound): kernels may start their accumulators at bias + RQ_KBIAS and read them back as floats
-};
-// int -> float without v_cvt_f32_i32: for -2^22 <= acc < 2^22 the bit pattern 0x4B400000 + acc IS the float 1.5 * 2^23 + acc
-// (exponent of 2^23, mantissa 0x400000 + acc), and subtracting 1.5 * 2^23 is exact.  The MFMA accumulates on top of the initial
-// value, so a conv that starts at bias + RQ_KBIAS ends with that pattern for free; two v_pk_add_f32 then replace four
-// v_cvt_f32_i32 per dword of outputs (15 -> 13 vector instructions per four requantised elements, none of them VOP1).
-constexpr int RQ_KBIAS = 0x4B400000;
-__host__ __device__ inline Rq make_rq(int zp, int lo, int hi, int kb = 0) {
-  return Rq{(float)(lo - zp), (float)(hi - zp), (float)(zp + 128), (lo <= -128 && hi >= 127) ? 1 : 0, kb};
-}
+// the requantisation of Rq (dev_types.h) on a float accumulator -> q + 128 in [0, 255]
 __device__ __forceinline__ float rq_u8(float accf, float mult, const Rq& q) {
   float r = __builtin_rintf(accf * mult);
   return __builtin_amdgcn_fmed3f(r, q.lo_f, q.hi_f) + q.off;
@@ -119,14 +100,7 @@ __device__ __forceinline__ unsigned rq_pack_i(const v4i& acc, const int4& b, con
   return rq_pack_b(a2, mu, q);
 }
 
-// ---- int8 ADD, XNNPACK qs8-vadd-minmax: q = clamp(((bias + a*am + b*bm) >> shift) + z_out, lo, hi).  The kernel's
-// int16 / int8 saturating packs are monotone and the activation range lies inside int8, so the chain of saturations equals
-// one clamp; it is applied before the zero point is added (lo - z_out, hi - z_out), and `off` = z_out + 128 moves the
-// result to its u8 image so that four of them pack with shifts (no masks) and one XOR restores int8.
-struct AddQ { int bias, am, bm, shift, lo, hi, off; };
-static inline AddQ make_addq(const AddParams& p, int z_out, int lo, int hi) {
-  return AddQ{p.bias, p.am, p.bm, p.shift, lo - z_out, hi - z_out, z_out + 128};
-}
+// ---- int8 ADD (AddQ, dev_types.h) ----
 __device__ __forceinline__ int addq_u8(int a, int b, const AddQ& q) {  // -> q + 128 in [0, 255]
   const int t = (q.bias + __mul24(a, q.am) + __mul24(b, q.bm)) >> q.shift;   // |am|, |bm| < 2^22, a, b int8: 24-bit products
   return min(max(t, q.lo), q.hi) + q.off;
@@ -150,12 +124,17 @@ __device__ __forceinline__ unsigned max4_s8(unsigned a, unsigned b) {
   return r;
 }
 
-struct Epi {  // requantisation parameters of one conv
-  const int* bias;    // folded bias, padded to NB*64
-  const float* mult;  // padded to NB*64
-  int zp, lo, hi;
-  Rq rq;
-};
+// two unsigned 16-bit maxima in one VALU op (v_pk_max_u16): the in-place max pools of fused_block.h, band_block.h and k_postprocess.hip
+typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
+  v2u16 x, y;
+  __builtin_memcpy(&x, &a, 4);
+  __builtin_memcpy(&y, &b, 4);
+  v2u16 r = __builtin_elementwise_max(x, y);
+  unsigned o;
+  __builtin_memcpy(&o, &r, 4);
+  return o;
+}
 
 // Lane (r = lane&15 pixel, g = lane>>4) holds acc[t][j] = channel nb*64 + 16g + 4t + j of pixel r.
 __device__ __forceinline__ void store_tile(const v4i acc[4], const Epi& e, int8_t* __restrict__ out, long m, int N,

@@ -29,7 +29,8 @@
 #pragma once
 #include <type_traits>
 
-#include "expdw_block.h"
+#include "dev_common.h"
+#include "expdw_args.h"
 
 #ifdef VBT_XD_PROF
 #define XD2_STAMP(k) do { if (tid == 0) a.prof[(long)blockIdx.x * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -39,35 +40,6 @@
 
 namespace vbt {
 
-struct ExpDw2Args {
-  const int8_t* x;   // [B][H][W][Cin]
-  int8_t* out;       // [B][OH][OW][Ce]: the graph's depthwise output tensor
-  int H, W, Cin, OH, OW, Ce;
-  int pad_t, pad_l;
-  int nchunks, cpw;  // 64-channel chunks in all / per workgroup
-  int nbands, brows; // row bands per image / output rows per band
-  int XB;            // position columns per row: blocks of 4 output columns (stride 1) / of 2 (stride 2)
-  int EQS, EYS;      // E: bytes per (row, quad) = 4 * padded width rounded to 16; bytes per row = 16 * EQS + bank-spreading pad
-  int e_bytes;       // LDS bytes of E (tallest band, + slack for the reads past the last row)
-  int PS;            // D: bytes per quad plane (4 * pixels of the tallest band, rounded so that PS / 4 = 2 mod 32)
-  int pe_off;        // LDS byte offsets of the parameter areas Pe / Pd (behind D)
-  int pd_off;
-  // per chunk, 16-byte pieces, copied to LDS as they are:
-  const v4i* pe;     // expand: weights [ks][t][lane] x 16 B (row i of tile t = channel 64 c + 16 t + i, k = 64 ks + 16 g + j) | bias (input zero
-                     // point folded) x 64 | multipliers x 64                                          = KS64 * 256 + 32 pieces
-  const v4i* pd;     // depthwise: [quad][mi][lane] dwords, byte j = w[2 mi + (g >> 1) - S dy][4 (g & 1) + j - S dx][64 c + 4 quad + cc] for A row
-                     // (lane & 15) = 4 q + cc with q = dx (stride 1: dy = 0) or 2 dy + dx (stride 2); 0 outside the kernel; the MFMA operand
-                     // (dword j = that byte at byte position cc) is rebuilt in registers | bias (expanded zero point folded) x 64 |
-                     // multipliers x 64                                                                = KT2 * 256 + 32 pieces
-  Rq rqe;
-  unsigned zeb;      // zero point of the expanded tensor x4
-  Rq rqd;
-#ifdef VBT_XD_PROF
-  unsigned long long* prof;
-#endif
-};
-
-constexpr int XD2_NPG = 8;   // position groups a band may have (128 positions = 512 output pixels)
 template <int PG, class F, class FC>
 __device__ __forceinline__ void d_pair(F& d_units, FC full_c, int NPGo) {
   if constexpr (PG < XD2_NPG) {

@@ -19,41 +19,10 @@
 // instruction: out[c][p] = sum_t W'[c][(t,c')] X[(t,c')][p], W' = w[t][c] delta(c,c'), exact int32.
 // Arithmetic identical to the per-op kernels: same integer accumulations, same single-op float requantisation.
 #pragma once
-#include "fused_block.h"
+#include "dev_common.h"
+#include "expdw_args.h"
 
 namespace vbt {
-
-// Waves per workgroup.  Measured end to end with three forwards in flight (A/B of two builds on one box): 16 waves 90.2 k
-// frames/s, 8 waves 91.9 k (92.5 k with the chunks per workgroup re-tuned), 4 waves 86.6 k.  A 16-wave workgroup is faster alone
-// (15 vs 21 us on b6) but holds every SIMD of its CU at each of its barriers; 8 waves leave issue slots to the other forwards.
-#ifndef VBT_XD_WAVES
-#define VBT_XD_WAVES 8
-#endif
-constexpr int XD_WAVES = VBT_XD_WAVES, XD_THREADS = 64 * XD_WAVES;
-constexpr int XD_EST = 80;   // bytes per pixel of E and D rows (64 + 16: bank spread, 16-byte aligned)
-
-struct ExpDwArgs {
-  const int8_t* x;   // [B][H][W][Cin]
-  int8_t* out;       // [B][OH][OW][Ce]: the graph's depthwise output tensor
-  int H, W, Cin, OH, OW, Ce;
-  int PW, PH;        // bordered E image (PH: of the tallest band)
-  int t0_bytes, e_bytes;   // LDS bytes of T0 / E (sized for the tallest band)
-  int pad_t, pad_l;
-  int T0S;           // odd multiple of 16 bytes >= Cin
-  int nchunks, cpw;  // 64-channel chunks in all / per workgroup
-  int nbands, brows; // row bands per image (1: the whole image) / output rows per band: maps of more than 400 pixels (Lite1 / Lite2)
-                     // do not fit LDS as a whole - a workgroup then owns `brows` output rows and expands the input rows they need
-  const v4i* we;     // expand weights [chunk][ks][t][lane] x 16 B: row i of tile t = channel 64c + 16t + i, k = 64ks + 16g + j
-  const int* be;     // bias with the input zero point folded, padded to 64 * nchunks
-  const float* me;
-  Rq rqe;
-  unsigned zeb;      // zero point of the expanded tensor x4
-  const long* wdc;   // depthwise [chunk][cg][lane] x 8 B: byte m = weight of tap 4m + g (0 past the kernel) for channel 64c + 16cg + (lane & 15);
-                     // the MFMA operand (that byte on the diagonal of 16) is rebuilt in registers (diag_operand)
-  const int* bd;     // bias with the expanded tensor's zero point folded
-  const float* md;
-  Rq rqd;
-};
 
 template <int KK, int S, int KS64>
 __global__ __launch_bounds__(XD_THREADS) void expdw_image_kernel(ExpDwArgs a) {

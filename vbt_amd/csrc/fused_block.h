@@ -1,5 +1,6 @@
 // Fused block kernel: [expand 1x1 + ReLU6 ->] depthwise kxk (stride 1|2) -> project 1x1 [-> residual ADD]
-// on LDS-resident tiles.  Included by detector.hip after the requantisation helpers.
+// on LDS-resident tiles.  The one kernel header that several units instantiate: k_fused_mbconv.hip, k_fused_mbconv_params.hip,
+// k_fused_mbconv_tail.hip, k_fused_mbconv_tpz.hip and k_fused_sepconv.hip.
 //
 // Covers (a) every MBConv block of the EfficientNet-Lite backbone (the 6x expanded tensor and the
 // depthwise output never touch HBM) and, with EXPAND = false, (b) every SeparableConv of the BiFPN and
@@ -16,107 +17,23 @@
 // (int8 MFMA, wave w owns pixels 16w..16w+15, accumulators stay in registers across chunks).
 // Where a chunk's parameters come from: every wave loads them from global memory at the top of the stage that needs them (three
 // dependent round trips per chunk, the same bytes in all four waves), or - template flag PLDS, MBConv launches listed by
-// fused_params_built - the workgroup fetches one packed record per chunk (FusedArgs::cpar, fused_params_geom.h) a stage ahead and the
+// VBT_FUSED_PARAMS_ROWS (fused_built.h) - the workgroup fetches one packed record per chunk (FusedArgs::cpar, fused_params_geom.h) a stage ahead and the
 // stages read it from an LDS area behind D; see the comment at fused_block_body.
 #pragma once
 #include "tpz_geom.h"
 #include "halo_geom.h"
 #include "fused_params_geom.h"
 #include "dev_common.h"
+#include "fused_args.h"   // FusedArgs, MultiTiles, DwTileArgs, FB_EST, FB_DST
 
 namespace vbt {
 
-struct FusedArgs {
-  const int8_t* x;
-  int8_t* out;
-  int H, W, Cin, OH, OW, Cout;
-  int pad_t, pad_l;
-  int TX, TY, tiles_x, tiles_y;
-  int T0S;       // bytes per halo pixel row in LDS
-  int nchunks;   // Ce_pad / 64
-  int zx;        // zero point of the block input
-  // expand (EXPAND only)
-  const long* we;
-  const int* be;
-  const float* me;
-  int KSe, ze, loe, hie;
-  Rq rqe;
-  // 48-channel chunking (template NT = 3) of the same block, for expanded widths that are multiples of 48 but not of 64
-  // (6 x {16, 24, 40, 80, 112}): no padded channels in the expand / depthwise stages.  nch3 == 0: not available.
-  const long* we3;   // [(c*KSe + ks)*3 + t][lane]: cout = 48c + 12(i>>2) + 4t + (i&3)
-  const long* wdm3;  // [(c*3 + cg)*KT + m][lane]: channel 48c + 16cg + i
-  const v4i* wp3;    // project weights, K-step c (16x16x64 layout) = channels 48c..48c+47 (+16 zero columns)
-  int nch3, KSp3;
-  // depthwise
-  const float* wd;  // [k*k][Ce_pad]
-  const int* bd;    // folded, padded to Ce_pad
-  const float* md;
-  int zd, lod, hid;
-  Rq rqd;
-  // depthwise on the matrix pipe (MDW): diagonal-embedded weights [chunk][cg][m][lane] x 8 B and the bias
-  // folded for raw int8 inputs (bias - z_x * sum(w))
-  const long* wdm;
-  const int* bdm;
-  // the same for the 16x16x64 MFMA (DW64): [16-channel group q][m][lane] x 16 B, lane (i = lane & 15 -> channel 16q + i,
-  // g = lane >> 4): byte j is non-zero only for j == i and holds the weight of tap (m, g):
-  //   3x3: (row m, column g), g = 3 is a zero column           -> 3 instructions
-  //   5x5: m < 5: (row m, column g); m = 5: (row g, column 4); m = 6: g = 0 -> (4, 4), the rest zero -> 7 instructions
-  // so the B operand of (m, g) sits at a compile-time offset from one of two per-lane base addresses
-  const v4i* wd64;
-  // the same operands as one byte each: [16-channel group q][lane] x 8 B, byte m = the non-zero byte of operand (q, m) of that
-  // lane; the kernels rebuild the 16-byte operand in registers (diag_operand)
-  const long* wd64c;
-  // band-Toeplitz depthwise (TPZ): tap table [channel quad q][m][lane] x 4 bytes (pack_expdw2_taps over all Ce_pad / 4 quads - a
-  // 64-channel chunk c starts at quad 16c, a 48-channel chunk at quad 12c); the kernel rebuilds the operands (toeplitz_operand)
-  const unsigned* wtz;
-  // project
-  const v4i* wp;    // packed for the 16x16x64 MFMA (pack_weights64), K = Ce_pad, one K-step per 64-channel chunk
-  // the same two panels (wp, wp3) with a tile-major part-filled last block (pack_weights64_tail), read by the kernels with a live-tile
-  // count (template NTL > 0); nullptr: Cout % 64 == 0 or no such kernel is built for the step
-  const v4i* wpt;
-  const v4i* wpt3;
-  const int* bp;
-  const float* mp;
-  int KSp, zo, lop, hip;
-  Rq rqp;
-  // PLDS: the per-chunk parameter block of the resolved launch (its chunking, depthwise form and panel layout: fused_params_geom.h,
-  // pack_fused_chunk_params), nch records and the bias | multiplier tail; nullptr: the launch reads the arrays above
-  const unsigned char* cpar;
-  // residual ADD: out = ADD(project output, block input), the graph's input order (AddQ: XNNPACK qs8-vadd, detector.hip)
-  int has_res;
-  AddQ resq;
-  // BiFPN node: the tile is the sum (+ReLU6) of two or three sources, each read through a resampling map
-  // (0 identity, 1 nearest-neighbour up: src = floor(dst*in/out), 2 max-pool 3x3/2 SAME).  ADD is binary:
-  //   n_src == 2: tile = ADD(src0, src1; sumq)
-  //   n_src == 3: p = ADD(src0, src1; preq) - the partial sum with its own quantisation - then
-  //               tile = ADD(p, src2; sumq) (chain == 1) or ADD(src2, p; sumq) (chain == 2)
-  int n_src;
-  const int8_t* src[3];
-  int sh[3], sw[3], smode[3], spt[3], spl[3];
-  int chain;
-  AddQ sumq, preq;
-};
-
+// four channels of a BiFPN node's input: the binary integer ADDs of its two or three sources (FusedArgs: chain, sumq, preq)
 __device__ __forceinline__ unsigned node_sum4(const unsigned u[3], const FusedArgs& a) {
   if (a.chain == 0) return addq4(u[0], u[1], a.sumq);
   const unsigned p = addq4(u[0], u[1], a.preq);
   return a.chain == 1 ? addq4(p, u[2], a.sumq) : addq4(u[2], p, a.sumq);
 }
-
-// two unsigned 16-bit maxima in one VALU op (v_pk_max_u16)
-typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  v2u16 x, y;
-  __builtin_memcpy(&x, &a, 4);
-  __builtin_memcpy(&y, &b, 4);
-  v2u16 r = __builtin_elementwise_max(x, y);
-  unsigned o;
-  __builtin_memcpy(&o, &r, 4);
-  return o;
-}
-
-constexpr int FB_EST = 80;  // E tile bytes per pixel (64 + 16: bank spread, 16-B aligned)
-constexpr int FB_DST = 80;  // D tile bytes per pixel: 16-byte aligned rows (the projection reads 16 bytes per lane), 20-dword pitch: conflict-free
 
 // KSE > 0: the expand has exactly KSE K-steps and its weights stay in registers for the whole chunk (the pixel-group
 // loop then issues no global loads); KSE == 0: K-steps are a runtime loop that streams the weights.
@@ -803,12 +720,8 @@ __global__ __launch_bounds__(256, FB_MINW) void fused_block_kernel(FusedArgs a) 
   fused_block_body<KK, S, NBP, EXPAND, MDW, KSE, NT, PPW, DW64, TPZ, NTL, PLDS>(a, blockIdx.x, fb_smem_dyn);
 }
 
-// Several independent problems (e.g. the same head layer on all 5 pyramid levels of both heads) in ONE grid:
-// a workgroup finds its problem from the cumulative tile counts and runs the same body.
-struct MultiTiles {
-  int n;
-  int start[13];  // start[p] = first workgroup of problem p, start[n] = grid size
-};
+// Several independent problems in ONE grid (MultiTiles, fused_args.h): a workgroup finds its problem from the cumulative tile counts and
+// runs the same body.
 template <int KK, int S, int NBP, bool EXPAND, bool MDW>
 __global__ __launch_bounds__(256, FB_MINW) void fused_block_multi_kernel(const FusedArgs* __restrict__ args, MultiTiles mt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fb_smem_dyn[];
@@ -826,19 +739,6 @@ __global__ __launch_bounds__(256, FB_MINW) void fused_block_multi_kernel(const F
 // its dwords straight to HBM.  Used where the column walker is a serial latency chain (small maps,
 // many channels).
 // ------------------------------------------------------------------------------------------
-struct DwTileArgs {
-  const int8_t* x;
-  int8_t* out;
-  const float* wf;   // [k*k][C]
-  const int* bias;   // folded
-  const float* mult;
-  const long* wdm;   // matrix-pipe form [chunk][cg][m][lane] (MDW)
-  const int* bdm;    // bias folded for raw int8 inputs, padded to 64-channel chunks
-  const float* mdm;  // multipliers padded to 64-channel chunks
-  int H, W, C, OH, OW, pad_t, pad_l, TX, TY, tiles_x, tiles_y, zx;
-  Rq rq;
-};
-
 template <int KK, int S, bool MDW>
 __global__ __launch_bounds__(256) void dw_tile_kernel(DwTileArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dt_smem[];

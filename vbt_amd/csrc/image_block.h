@@ -16,17 +16,11 @@
 // registers across chunks.  Depthwise weights travel compact ([tap][64] bytes); the diagonal MFMA operand is rebuilt in
 // registers once per chunk.  Same integer / float arithmetic as the tile kernel: identical results.
 #pragma once
-#include "fused_block.h"
+#include "dev_common.h"
+#include "fused_args.h"   // FusedArgs, FB_EST, FB_DST
+#include "image_block_args.h"
 
 namespace vbt {
-
-constexpr int IB_WAVES = 16, IB_THREADS = 64 * IB_WAVES, IB_NPF = 3;  // NPF uint4 prefetch registers per lane (48 KB bundles)
-
-struct ImageBundle {       // byte offsets inside one chunk's record
-  const unsigned char* data;
-  int bytes;               // record size, multiple of 16
-  int o_be, o_me, o_dw, o_bd, o_md, o_wp;
-};
 
 template <int KK, int S, int MAXU>
 __global__ __launch_bounds__(IB_THREADS) void mbconv_image_kernel(FusedArgs a, ImageBundle wb, int PW, int PH, int NB) {

@@ -1,5 +1,6 @@
 // Fused MBConv blocks on LDS tiles (fused_block.h, EXPAND = true): expand 1x1 -> depthwise -> project 1x1 [+ residual].
 #include "launchers.h"
+#include "fused_block.h"
 
 namespace vbt {
 

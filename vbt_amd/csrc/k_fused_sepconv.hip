@@ -1,6 +1,7 @@
 // SeparableConv / BiFPN node on LDS tiles (fused_block.h, EXPAND = false), the head layers of all levels in one grid
 // (fused_block_multi_kernel) and the stand-alone LDS-tiled depthwise conv (dw_tile_kernel).
 #include "launchers.h"
+#include "fused_block.h"
 
 namespace vbt {
 

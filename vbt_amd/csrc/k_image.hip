@@ -1,5 +1,6 @@
 // One workgroup per image: whole-image MBConv blocks on low-resolution maps (image_block.h).
 #include "launchers.h"
+#include "image_block.h"
 
 namespace vbt {
 

@@ -2,6 +2,7 @@
 // ADD, max pool, nearest-neighbour resize - and their launchers (launchers.h; argument structs: op_args.h).  The only unit that sees
 // these kernels.
 #include "launchers.h"
+#include "dev_common.h"
 
 namespace vbt {
 

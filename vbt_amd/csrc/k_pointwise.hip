@@ -1,6 +1,7 @@
 // Pointwise convs of the int8 detector, one graph op per launch (six forms, pw_a ... pw_f) or several in one grid (pw_multi_kernel),
 // and their launchers (launchers.h; argument structs: op_args.h).  The only unit that sees these kernels.
 #include "launchers.h"
+#include "dev_common.h"
 
 namespace vbt {
 

@@ -1,5 +1,6 @@
 // Decode + NMS of the int8 detector and its launcher (launchers.h; PostArgs: op_args.h).  The only unit that sees the kernel.
-#include "launchers.h"   // + pk_max_u16 (fused_block.h)
+#include "launchers.h"
+#include "dev_common.h"   // pk_max_u16
 
 namespace vbt {
 

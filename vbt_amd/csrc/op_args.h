@@ -1,7 +1,7 @@
 // Argument structs of the single-op kernels (k_pointwise.hip, k_ops.hip, k_postprocess.hip) and what selects their instantiations:
 // what launch_step (detector.hip) fills and the launchers (launchers.h) take.  No kernel body lives here.
 #pragma once
-#include "dev_common.h"
+#include "dev_types.h"
 
 namespace vbt {
 

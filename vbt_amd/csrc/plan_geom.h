@@ -3,7 +3,7 @@
 #pragma once
 #include <algorithm>
 
-#include "launchers.h"   // FusedArgs, BandArgs, FB_* / BD_* tile constants
+#include "launchers.h"   // FusedArgs, BandArgs, FB_* / BD_* tile constants (argument headers only)
 
 namespace vbt {
 

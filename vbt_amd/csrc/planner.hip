@@ -9,6 +9,7 @@
 #include <initializer_list>
 
 #include "detector_model.h"
+#include "tpz_geom.h"   // DS_READ_B128_GROUPS (expdw2 geometry)
 using vbt::v4i;            // weight_pack.h's functions sit at global scope and take the includer's 16-byte int vector
 #include "weight_pack.h"   // the weight / bias layouts of every kernel family: one pure host function each
 

@@ -14,35 +14,10 @@
 // depthwise: diagonal-embedded weights on the 16x16x64 MFMA, tap (row m, column g) per instruction m and lane group g
 // (three instructions for 3x3, every LDS address = lane base + immediate; see DW64 in fused_block.h).
 #pragma once
-#include "fused_block.h"
+#include "dev_common.h"
+#include "stem_block_args.h"
 
 namespace vbt {
-
-struct StemBlockArgs {
-  const uint8_t* frames;
-  int8_t* out;
-  int H, W, SH, SW, Cout;
-  int spad_t, spad_l;   // SAME padding of the stem
-  int tiles_x, tiles_y;
-  unsigned in_pad4;     // out-of-image input byte (uint8 domain, zero point + 128) x 4
-  const long* ws;       // stem weights [t(2)][lane] x 8 B; row i of tile t = cout 8(i>>2) + 4t + (i&3)
-  const int* bs;        // [32] folded bias
-  const float* ms;      // [32]
-  Rq rqs;
-  unsigned zs4;         // stem output zero point x 4
-  const v4i* wd64;      // depthwise [cg(2)][3][lane] x 16 B (FusedArgs::wd64 layout)
-  const int* bdm;
-  const float* mdm;
-  Rq rqd;
-  const long* wp;       // project [lane] x 8 B (row i = cout i, K = 32)
-  const int* bp;        // [16] folded
-  const float* mp;      // [16]
-  Rq rqp;
-  // the direct form (stem_block_direct_kernel)
-  unsigned in_pad4s;    // in_pad4 in the int8 domain (every byte XOR 0x80)
-  const v4i* ws64;      // stem weights [t(2)][lane] x 16 B: lane group g < 3 = kernel row g, bytes 0..8 its nine taps, zero elsewhere
-  const long* wpc;      // project [lane] x 8 B in the K order the depthwise leaves in registers (pack_stem_block_proj_chain)
-};
 
 constexpr int SB_HW = 18, SB_NPH = SB_HW * SB_HW, SB_NPG = (SB_NPH + 15) / 16;
 constexpr int SB_RROWS = 37, SB_RDW = 30, SB_RST = SB_RDW * 4, SB_PST = 32, SB_SST = 48, SB_DST = 40;
