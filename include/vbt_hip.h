@@ -1213,6 +1213,53 @@ int vbt_mjpeg_encode(vbt_mjpeg* m, const uint8_t* frames_dev, int B, void* strea
  * no batch is pending.  A successful read releases the handle for the next vbt_mjpeg_encode. */
 int vbt_mjpeg_read(vbt_mjpeg* m, uint8_t* host_buf, uint64_t cap, uint64_t* offsets, void* stream);
 
+/* ------------------------------------------------------------------ Scaled export --------
+ * The reference shows every annotated frame resized to --display_image_height, the width following the source's aspect ratio
+ * (track.py:69,139-140,237-239).  There is no display here, so the display is the export: frames of H x W in, frames (or JPEGs) of
+ * h x w out, on the device, between the overlay and the encoder or the copy back.
+ *
+ * Order.  The overlay and the panels are drawn at full resolution first, then the frame is resized (track.py:201-224 before :237).
+ * Filter.  cv2.resize's default: bilinear with half-pixel centres, no anti-aliasing (below half size a sample skips source pixels,
+ * as in the reference).  cv2's fixed-point rounding is not the contract; the contract is the integers below (the numpy statement of
+ * it is tests/scale_ref.py), within 0.5 + 255 / 2048 of the bilinear filter in real numbers.
+ *
+ * Size.  vbt_display_size: h = display_height, w = (int)(h * ((double)W / (double)H)) - the reference's expression, in double,
+ * truncated; for the YUV 4:2:0 formats w is then rounded down to even and an odd h is refused.  h and w must lie in 1..16384.  The
+ * handles below take any (h, w), not only aspect-preserving ones.
+ * Axis table, for destination index o of an axis with n_src source and n_dst destination samples, built on the host in double:
+ *     f = max((o + 0.5) * (n_src / n_dst) - 0.5, 0);  i0 = min(floor(f), n_src - 1);  i1 = min(i0 + 1, n_src - 1);
+ *     a = rint((f - i0) * 2048), which lies in 0..2048.
+ * Sample, int32 throughout (the largest sum is 255 * 2^22 + 2^21 < 2^31):
+ *     out = ((p[y0][x0] (2048 - ax) + p[y0][x1] ax) (2048 - ay) + (p[y1][x0] (2048 - ax) + p[y1][x1] ax) ay + 2^21) >> 22.
+ * n_dst == n_src gives a = 0 everywhere: the output is a byte copy.
+ * Planes.  VBT_PIX_RGB24: the three channels of a pixel share one table pair.  NV12 / I420: the luma plane uses the tables of
+ * (H, W) -> (h, w), each chroma plane those of (H/2, W/2) -> (h/2, w/2); samples are scaled as stored (limited range), the output is
+ * in the source's own pixel format, and NV12's interleaved U, V are two planes that share a table pair.
+ * Not covered: anti-aliasing, letterboxing.  HIP kernels for gfx950 (vbt_amd/csrc/scale.hip, the SCALED transform of mjpeg.hip). */
+typedef struct vbt_scaler vbt_scaler;
+/* Host only, no device call.  VBT_ERR_ARG, the text naming the argument: h or w NULL, an unknown pix_fmt, H or W outside 1..16384 or
+ * odd with a YUV format, display_height outside 1..16384 or odd with a YUV format, a resulting width outside 1..16384 (2.. for YUV). */
+int vbt_display_size(int H, int W, int pix_fmt, int display_height, int* h, int* w);
+/* VBT_ERR_ARG, before any device call: out NULL, an unknown pix_fmt, H, W, h or w outside 1..16384, an odd one with a YUV format.
+ * Builds the tables (plane 0 y and x; for YUV plane 1 y and x) and uploads them in one copy: 8 bytes per entry. */
+int vbt_scaler_create(int device, int H, int W, int h, int w, int pix_fmt, vbt_scaler** out);
+void vbt_scaler_destroy(vbt_scaler* s);
+/* B contiguous frames of H x W at src_dev -> B contiguous frames of h x w at dst_dev, both in the layout vbt_overlay_draw takes.
+ * Enqueue only, one launch on `stream`; src is read, every byte of dst is written.  Stores are 32-bit words where a plane's rows
+ * begin 4-aligned (dst_dev, the frame size, the plane's offset and its row bytes all multiples of 4), bytes otherwise.
+ * VBT_ERR_ARG: a NULL argument, B < 1; VBT_ERR_CAPACITY: B > 65535.  Nothing is enqueued on an error. */
+int vbt_scaler_run(vbt_scaler* s, const uint8_t* src_dev, uint8_t* dst_dev, int B, void* stream);
+/* The handle's table of `plane` (0: luma or RGB, 1: chroma of a YUV handle) and `axis` (0: y, 1: x), read back from the device for
+ * tests: i0[k] and a[k] of destination index k.  *n is always set; VBT_ERR_CAPACITY when cap < *n (nothing is copied);
+ * VBT_ERR_ARG: a NULL argument, a plane or axis the handle does not have. */
+int vbt_scaler_tables(vbt_scaler* s, int plane, int axis, int32_t* i0, int32_t* a, int cap, int* n);
+/* A vbt_mjpeg that takes frames of H x W and emits JPEGs of h x w: vbt_mjpeg_encode, vbt_mjpeg_read and vbt_mjpeg_destroy work on
+ * it unchanged, the scratch is sized by (h, w) and the JFIF header says h x w.  Defining property: the bytes are those
+ * vbt_mjpeg_encode of a vbt_mjpeg_create(h, w) handle produces for the frames vbt_scaler_run produces.  The colour stage of the
+ * transform kernel takes each pixel through the sample above; the scaled frame never exists in memory.  With (h, w) == (H, W) the
+ * handle is exactly what vbt_mjpeg_create returns.  VBT_ERR_ARG as vbt_mjpeg_create, for either size. */
+int vbt_mjpeg_create_scaled(int device, int H, int W, int h, int w, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out);
+
 /* ------------------------------------------------------------------ MJPEG import --------
  * The way in for video files (the reference's cv2.VideoCapture, track.py:129-160): the frames of a Motion-JPEG AVI - the files
  * the export above writes, and what many cameras and ffmpeg -c:v mjpeg write - are decoded on the device.  The host parses the

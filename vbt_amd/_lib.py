@@ -267,6 +267,12 @@ _SIGS = {
     "vbt_mjpeg_destroy": (None, [c_void_p]),
     "vbt_mjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_mjpeg_read": (c_int, [c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
+    "vbt_display_size": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "vbt_scaler_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_scaler_destroy": (None, [c_void_p]),
+    "vbt_scaler_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vbt_scaler_tables": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_mjpeg_create_scaled": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_jpeg_probe": (c_int, [c_void_p, ctypes.c_uint64] + [ctypes.POINTER(c_int)] * 4),
     "vbt_mjpeg_decoder_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_mjpeg_decoder_destroy": (None, [c_void_p]),

@@ -3,6 +3,7 @@
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
                             [--live] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
                             [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
+                            [--display_image_height N]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
       import" - and --fps, when not given, is the file's rate / scale; --size and a YUV --pix_fmt do not apply to it;
@@ -42,9 +43,15 @@
       last batch shows what `analyze` prints.  Unlike --hud the count can go down again (the leading id changes, or a larger rep
       makes the filter drop small ones).  Takes --plate_diameter, --hud_scale and --hud_pos; not with --hud, not with --concurrent
       above 1.
+      --display_image_height N (with --video_dir; reference track.py:69,139-140,237-239): every exported frame is drawn at full
+      size and then resized on the GPU to N lines, the width following the source's aspect ratio - int(N * (W / H)), rounded down to
+      even for nv12 / i420 - with cv2.resize's default filter (include/vbt_hip.h, "Scaled export").  The reference resizes what it
+      shows in a window and defaults to 720; there is no window here, the export is resized instead and the default is the full size.
+      Works with every --video_format, --hud, --one_pass, --live_hud, --concurrent and source kind; the panels are placed and checked
+      against the source size and shrink with the frame.
   python -m vbt_amd.cli overlay SRC DATAFRAME [--fps 30] [--frame_stride 1] [--pix_fmt ... --size WxH] [--video_dir DIR]
                               [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync]
-                              [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]]
+                              [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--display_image_height N]
       the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn; --hud takes the
       panel's id from the file name).
   python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
@@ -153,6 +160,42 @@ def _hud_params(hud, video_dir, hud_scale, hud_pos):
     return dict(x=int(m.group(1)), y=int(m.group(2)), scale=int(hud_scale))
 
 
+def _display_option(f):
+    """--display_image_height, for `track` and `overlay`"""
+    return click.option("--display_image_height", default=None, type=int,
+                        help="Height in lines of the exported frames: each is drawn at full size, then resized on the GPU, the width following the "
+                             "source's aspect ratio (needs --video_dir; even for nv12 / i420).  Default: the source's own size - the reference's "
+                             "default of 720 applied to the window it shows, not to a file.")(f)
+
+
+def _check_display_height(display_image_height, video_dir, pix_fmt):
+    """the refusals of --display_image_height that need no source, before anything is opened or written"""
+    from .rawvideo import is_yuv
+    if display_image_height is None:
+        return
+    if video_dir is None:
+        raise click.UsageError("--display_image_height is the size of the exported frames: give --video_dir")
+    if not 1 <= display_image_height <= 16384:
+        raise click.UsageError(f"--display_image_height {display_image_height} is outside 1..16384")
+    if is_yuv(pix_fmt) and display_image_height % 2:
+        raise click.UsageError(f"--display_image_height {display_image_height} is odd: {pix_fmt} frames have an even height")
+
+
+def _display_hw(frames, pix_fmt, display_image_height):
+    """None without --display_image_height, else (h, w) of the export of this source (scale.display_size); a width outside 1..16384
+    is a usage error, raised while nothing has been written for the source yet"""
+    if display_image_height is None:
+        return None
+    from ._lib import VbtArgError
+    from .rawvideo import source_hw
+    from .scale import display_size
+    H, W = source_hw(frames, pix_fmt)
+    try:
+        return display_size(H, W, pix_fmt, display_image_height)
+    except VbtArgError as e:
+        raise click.UsageError(f"--display_image_height: {e}")
+
+
 def _open_source(s, pix_fmt, size, mjpeg_entropy="auto"):
     """One SRC of `track` as the clip array of its pixel format: a .npy stack (no --size) or a headerless raw video file."""
     from .rawvideo import open_raw
@@ -239,12 +282,14 @@ def _raw_size(pix_fmt, size):
 @click.option("--live_hud", is_flag=True, default=False,
               help="With --one_pass: the rep panel fed by the live rep analysis on the GPU - the reps appear on the video as they complete "
                    "(uses --plate_diameter, --hud_scale, --hud_pos; not with --hud or --concurrent above 1).")
+@_display_option
 @_hud_options
 def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, tracker, concurrent, pix_fmt, size, video_dir, video_format,
-          video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos):
+          video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos, display_image_height):
     from ._lib import VbtArgError
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
+    _check_display_height(display_image_height, video_dir, pix_fmt)
     fps_given = _fps_given()
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
     if concurrent < 1:
@@ -271,27 +316,29 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter, tracker)
+                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter, tracker, display_image_height)
     default_fps = fps
     for s in src:
         frames = _open_source(s, pix_fmt, size, mjpeg_entropy)
         fps = _source_fps(frames, default_fps, fps_given)
+        display_hw = _display_hw(frames, pix_fmt, display_image_height)   # before any output file exists
         if hud_params is not None:                                       # the panel shows the finished analysis: render after tracking
             data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
                                 live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, tracker=tracker)
             line, phases = _export_line(data, s, model, df_dir, plate_diameter)
-            _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params)
+            _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params,
+                          display_hw)
             click.echo(line)
             continue
         if hud_live is not None:
             _check_live_hud_fits(frames, pix_fmt, hud_live)                # before any output file exists
         mjpeg = video_dir is not None and video_format == "mjpeg"
-        video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
-        with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
+        video = None if mjpeg else _video_out(video_dir, s, frames, frame_stride, pix_fmt, size, display_hw)
+        with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt, display_hw) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
             try:
                 data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
                                     live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink,
-                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker)
+                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker, display_hw=display_hw)
             except VbtArgError as e:                                     # a panel the library refuses (outside the frame, odd origin in a YUV frame)
                 if hud_live is None or "vbt_overlay_hud_follow" not in str(e):
                     raise
@@ -328,14 +375,16 @@ def _export_line(data, s, model, df_dir, plate_diameter=None):
     return line, (_id_phases(df, best, plate_diameter) if plate_diameter is not None else None)
 
 
-def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size):
+def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size, display_hw=None):
     """The writable map of --video_dir for source `s` (None without --video_dir, or when no frame is kept): DIR/{video}.npy
-    (numpy.lib.format.open_memmap, so a long clip never sits in memory) or, for --size sources, raw DIR/{video}.rgb / .yuv."""
+    (numpy.lib.format.open_memmap, so a long clip never sits in memory) or, for --size sources, raw DIR/{video}.rgb / .yuv.
+    display_hw: the (h, w) of --display_image_height; the frames then have that size."""
     if video_dir is None:
         return None
     os.makedirs(video_dir, exist_ok=True)                                # reference track.py:85-86
     stem = os.path.basename(s).split(".")[0]                             # reference track.py:97
-    shape = (int(frames.shape[0]) // max(int(frame_stride), 1),) + tuple(frames.shape[1:])
+    from .rawvideo import frame_shape
+    shape = (int(frames.shape[0]) // max(int(frame_stride), 1),) + (tuple(frames.shape[1:]) if display_hw is None else frame_shape(pix_fmt, *display_hw))
     if size is None:
         path = os.path.join(video_dir, stem + ".npy")
         if shape[0] == 0:
@@ -349,12 +398,13 @@ def _video_out(video_dir, s, frames, frame_stride, pix_fmt, size):
     return np.memmap(path, dtype=np.uint8, mode="w+", shape=shape)
 
 
-def _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt):
-    """The mjpeg.AviWriter of --video_format mjpeg for source `s`: DIR/{video}.avi at fps / frame_stride"""
+def _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt, display_hw=None):
+    """The mjpeg.AviWriter of --video_format mjpeg for source `s`: DIR/{video}.avi at fps / frame_stride, its header with the
+    (h, w) of --display_image_height when there is one"""
     from .mjpeg import AviWriter, frame_rate
     from .rawvideo import source_hw
     os.makedirs(video_dir, exist_ok=True)
-    H, W = source_hw(frames, pix_fmt)
+    H, W = source_hw(frames, pix_fmt) if display_hw is None else display_hw
     rate, scale = frame_rate(fps, frame_stride)
     path = os.path.join(video_dir, os.path.basename(s).split(".")[0] + ".avi")
     if os.path.exists(path) and os.path.samefile(path, s):
@@ -367,18 +417,21 @@ def _video_done(video):
         video.flush()
 
 
-def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, batch, pix_fmt, size, hud=None, hud_params=None):
+def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, batch, pix_fmt, size, hud=None, hud_params=None,
+                  display_hw=None):
     """The export of a finished clip from its rows: DIR/{video}.avi (mjpeg) or the raw map of _video_out.  Returns the frames written.
     hud_params (--hud): the rep panel of the phases `hud` on every frame; a panel the library refuses (outside the frame, odd origin
     in a YUV frame) is a usage error."""
     from ._lib import VbtArgError
     from .overlay import render
     panel = {} if hud_params is None else dict(hud=hud, hud_params=hud_params)
+    if display_hw is not None:
+        panel["display_hw"] = display_hw
     try:
         if video_format == "mjpeg":
-            with _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt) as sink:   # closed, hence a valid file, on an error too
+            with _avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt, display_hw) as sink:   # closed, hence a valid file, on an error too
                 return render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, sink=sink, quality=video_quality, **panel)
-        video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size)
+        video = _video_out(video_dir, s, frames, frame_stride, pix_fmt, size, display_hw)
         if video is None:
             return 0
         render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=batch, out=video, **panel)
@@ -391,7 +444,8 @@ def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, 
 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
-                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45, tracker="ocsort"):
+                      video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45, tracker="ocsort",
+                      display_image_height=None):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -405,14 +459,17 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
             break
     lines, nxt = {}, 0
     fps = [_source_fps(a, fps, fps_given) for a in sources] or fps
+    display_hw = [_display_hw(a, pix_fmt, display_image_height) for a in sources]    # before any output file exists
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
                               time_batch=time_batch, pix_fmt=pix_fmt, tracker=tracker):
         s = src[i]
         if hud_params is None and video_dir is not None:                 # the clip is finished: its rows are all the renderer needs
-            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size)
+            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size,
+                          display_hw=display_hw[i])
         lines[i], phases = _export_line(data, s, model, df_dir, plate_diameter if hud_params is not None else None)
         if hud_params is not None:                                       # (--hud: the panel needs the export id's phases first)
-            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size, phases, hud_params)
+            _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size, phases, hud_params,
+                          display_hw[i])
         while nxt in lines:
             click.echo(lines.pop(nxt))
             nxt += 1
@@ -434,12 +491,14 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
 @click.option("--video_quality", default=85, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --video_format mjpeg.")
 @click.option("--mjpeg_entropy", default="auto", show_default=True, type=click.Choice(["auto", "interval", "sync"]),
               help="Entropy decoding of .avi sources: one lane per restart interval, subsequences that synchronise, or auto by interval length.")
+@_display_option
 @_hud_options
 def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_format, video_quality, mjpeg_entropy, hud, plate_diameter, hud_scale,
-            hud_pos):
+            hud_pos, display_image_height):
     """Draw the boxes, ids and bar paths of a stored DataFrame into the frames of its clip (what `track --video_dir` writes)."""
     import pandas as pd
     size = _raw_size(pix_fmt, size)
+    _check_display_height(display_image_height, video_dir, pix_fmt)
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
     m = FILENAME_RE.match(os.path.basename(dataframe))
     if hud and not m:
@@ -452,7 +511,8 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
     fps = _source_fps(frames, fps, _fps_given())
     df = pd.read_pickle(dataframe)
     phases = _id_phases(df, int(m.group(2)), plate_diameter) if hud else None
-    n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size, phases, hud_params)
+    n = _render_video(video_dir, video_format, video_quality, src, frames, df, fps, frame_stride, 64, pix_fmt, size, phases, hud_params,
+                      _display_hw(frames, pix_fmt, display_image_height))
     click.echo(f"{src}: {n} frames, {len(df)} rows of {df['id'].nunique()} ids -> {video_dir}")
 
 

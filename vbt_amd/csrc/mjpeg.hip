@@ -3,7 +3,8 @@
 // of it is tests/mjpeg_ref.py).  Four launches per batch:
 //   mjpeg_transform_kernel  grid (groups of 32 MCUs, MCU row, frame): colour conversion of the group's 512 x 16 pixels into LDS (one
 //     thread per 2 x 2 cell: four luma samples, one Cb, one Cr), then one thread per 8 x 8 block: level shift, DCT, quantisation, zigzag;
-//     the int16 levels leave through LDS as one contiguous run per workgroup.
+//     the int16 levels leave through LDS as one contiguous run per workgroup.  Its SCALED instantiation (vbt_mjpeg_create_scaled)
+//     takes each pixel of the colour stage from a larger or smaller source through the four-tap sample of scale_core.h.
 //   mjpeg_entropy_kernel    grid (MCU row, frame), one workgroup per restart interval, walking it in chunks of 256 blocks, a thread per
 //     block: bit count (the DC difference is a subtraction of the neighbour block's quantised DC, so blocks code in parallel), prefix
 //     sum, codes OR-ed into an LDS bit buffer at their offsets, then per thread a run of the chunk's bytes: 0xFF count, prefix sum,
@@ -19,6 +20,7 @@
 #include "common.h"
 #include "dev_mem.h"
 #include "jpeg_parse.h"
+#include "scale_core.h"
 
 namespace vbt {
 
@@ -88,7 +90,50 @@ __device__ __forceinline__ int mj_expand_chroma(int c) {
   return mj_clip8((n >= 0 ? (2 * n + 224) / 448 : -((-2 * n + 224) / 448)) + 128);
 }
 
-__global__ __launch_bounds__(MJ_THREADS) void mjpeg_transform_kernel(MjArgs A) {
+// MjScaled (vbt_mjpeg_create_scaled): pixel (py, px) of the H x W frame that vbt_scaler_run would have written, formed from the
+// SH x SW source by the shared sample (scale_core.h) - coordinates clamped to H x W as the unscaled colour stage clamps them; that
+// frame never exists in memory.
+struct MjScale {
+  const ScTap *ty, *tx, *cty, *ctx;       // luma (or RGB) pair, chroma pair
+  int SH, SW;
+};
+struct MjScaled {
+  const uint8_t* src;
+  int H, W, fmt;                          // the size that is encoded
+  MjScale S;
+  __device__ __forceinline__ void rgb(int py, int px, int* r, int* g, int* b) const {
+    const ScTap y = S.ty[min(py, H - 1)], x = S.tx[min(px, W - 1)];
+    const uint8_t* r0 = src + (size_t)y.i0 * S.SW * 3;
+    const uint8_t* r1 = src + (size_t)sc_i1(y.i0, S.SH) * S.SW * 3;
+    const int x1 = sc_i1(x.i0, S.SW);
+    *r = sc_sample_at(r0, r1, 3, 0, x.i0, x1, x.a, y.a);
+    *g = sc_sample_at(r0, r1, 3, 1, x.i0, x1, x.a, y.a);
+    *b = sc_sample_at(r0, r1, 3, 2, x.i0, x1, x.a, y.a);
+  }
+  __device__ __forceinline__ int luma(int py, int px) const {
+    const ScTap y = S.ty[min(py, H - 1)], x = S.tx[min(px, W - 1)];
+    return sc_sample_at(src + (size_t)y.i0 * S.SW, src + (size_t)sc_i1(y.i0, S.SH) * S.SW, 1, 0, x.i0, sc_i1(x.i0, S.SW), x.a, y.a);
+  }
+  __device__ __forceinline__ void chroma(int cy, int cx, int* U, int* V) const {
+    const int ch = S.SH >> 1, cw = S.SW >> 1;
+    const ScTap y = S.cty[min(cy, (H >> 1) - 1)], x = S.ctx[min(cx, (W >> 1) - 1)];
+    const int y1 = sc_i1(y.i0, ch), x1 = sc_i1(x.i0, cw);
+    const uint8_t* cp = src + (size_t)S.SH * S.SW;
+    if (fmt == VBT_PIX_NV12) {
+      *U = sc_sample_at(cp + (size_t)y.i0 * S.SW, cp + (size_t)y1 * S.SW, 2, 0, x.i0, x1, x.a, y.a);
+      *V = sc_sample_at(cp + (size_t)y.i0 * S.SW, cp + (size_t)y1 * S.SW, 2, 1, x.i0, x1, x.a, y.a);
+    } else {
+      *U = sc_sample_at(cp + (size_t)y.i0 * cw, cp + (size_t)y1 * cw, 1, 0, x.i0, x1, x.a, y.a);
+      cp += (size_t)ch * cw;
+      *V = sc_sample_at(cp + (size_t)y.i0 * cw, cp + (size_t)y1 * cw, 1, 0, x.i0, x1, x.a, y.a);
+    }
+  }
+};
+
+// SCALED (a handle of vbt_mjpeg_create_scaled): A.H x A.W is what is encoded, A.frame_bytes the size of a source frame of S.SH x S.SW,
+// and the colour stage takes its pixels through MjScaled; S is not read otherwise.
+template <bool SCALED>
+__global__ __launch_bounds__(MJ_THREADS) void mjpeg_transform_kernel(MjArgs A, MjScale S) {
   __shared__ __align__(16) uint8_t sY[MJ_GROUP][16][16];
   __shared__ __align__(16) uint8_t sC[2][MJ_GROUP][8][8];
   __shared__ uint16_t sQ[2][64];
@@ -108,8 +153,13 @@ __global__ __launch_bounds__(MJ_THREADS) void mjpeg_transform_kernel(MjArgs A) {
       for (int dy = 0; dy < 2; dy++) {
 #pragma unroll
         for (int dx = 0; dx < 2; dx++) {
-          const uint8_t* p = src + ((size_t)min(py0 + dy, H - 1) * W + min(px0 + dx, W - 1)) * 3;
-          const int r = p[0], g = p[1], b = p[2];
+          int r, g, b;
+          if constexpr (SCALED) {
+            MjScaled{src, H, W, A.fmt, S}.rgb(py0 + dy, px0 + dx, &r, &g, &b);
+          } else {
+            const uint8_t* p = src + ((size_t)min(py0 + dy, H - 1) * W + min(px0 + dx, W - 1)) * 3;
+            r = p[0]; g = p[1]; b = p[2];
+          }
           sY[m][cy * 2 + dy][cx * 2 + dx] = (uint8_t)((19595 * r + 38470 * g + 7471 * b + 32768) >> 16);
           sr += r; sg += g; sb += b;
         }
@@ -121,12 +171,15 @@ __global__ __launch_bounds__(MJ_THREADS) void mjpeg_transform_kernel(MjArgs A) {
       for (int dy = 0; dy < 2; dy++) {
 #pragma unroll
         for (int dx = 0; dx < 2; dx++)
-          sY[m][cy * 2 + dy][cx * 2 + dx] = (uint8_t)mj_expand_luma(src[(size_t)min(py0 + dy, H - 1) * W + min(px0 + dx, W - 1)]);
+          sY[m][cy * 2 + dy][cx * 2 + dx] = (uint8_t)mj_expand_luma(SCALED ? MjScaled{src, H, W, A.fmt, S}.luma(py0 + dy, px0 + dx)
+                                                                           : src[(size_t)min(py0 + dy, H - 1) * W + min(px0 + dx, W - 1)]);
       }
       const int hh = H >> 1, hw = W >> 1, ccy = min(py0 >> 1, hh - 1), ccx = min(px0 >> 1, hw - 1);
       const uint8_t* cp = src + (size_t)H * W;
       int U, V;
-      if (A.fmt == VBT_PIX_NV12) {
+      if constexpr (SCALED) {
+        MjScaled{src, H, W, A.fmt, S}.chroma(py0 >> 1, px0 >> 1, &U, &V);
+      } else if (A.fmt == VBT_PIX_NV12) {
         U = cp[(size_t)ccy * W + 2 * ccx];
         V = cp[(size_t)ccy * W + 2 * ccx + 1];
       } else {
@@ -378,10 +431,12 @@ __global__ __launch_bounds__(MJ_THREADS) void mjpeg_gather_kernel(MjArgs A) {
 using namespace vbt;
 
 struct vbt_mjpeg {
-  int device = 0, H = 0, W = 0, fmt = 0, quality = 0, max_batch = 0, MW = 0, MH = 0;
+  int device = 0, H = 0, W = 0, fmt = 0, quality = 0, max_batch = 0, MW = 0, MH = 0;   // H x W: the size that is encoded
   size_t frame_bytes = 0, slot_bytes = 0, out_bytes = 0;
-  DevBuf<uint8_t> blob;                  // tables | offsets + flag | fsize | ioff | sizes | levels | slots | out in one allocation
+  DevBuf<uint8_t> blob;                  // tables | offsets + flag | fsize | ioff | sizes | levels | slots | out | scale tables in one allocation
   MjArgs args{};
+  bool scaled = false;                   // vbt_mjpeg_create_scaled with another size than the source's: frame_bytes is the source's
+  MjScale scale{};
   int pending = 0;                       // frames of the batch that is encoded and not yet read
 };
 
@@ -460,24 +515,34 @@ bool dct_table_ok() {
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out) {
-  if (!out) { set_error("vbt_mjpeg_create: out is NULL"); return VBT_ERR_ARG; }
+// vbt_mjpeg_create (SH x SW == H x W) and vbt_mjpeg_create_scaled: frames of SH x SW in, JPEGs of H x W out
+int mjpeg_create(const char* who, int device, int SH, int SW, int H, int W, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out) {
+  if (!out) { set_error("%s: out is NULL", who); return VBT_ERR_ARG; }
   *out = nullptr;
-  if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_yuv(pix_fmt)) { set_error("vbt_mjpeg_create: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
-  if (H < 1 || W < 1 || H > 16384 || W > 16384) { set_error("vbt_mjpeg_create: frames of 1..16384 pixels a side, got %d x %d", H, W); return VBT_ERR_ARG; }
-  if (pix_fmt_is_yuv(pix_fmt) && ((H & 1) || (W & 1))) { set_error("vbt_mjpeg_create: YUV 4:2:0 frames have even H and W, got %d x %d", H, W); return VBT_ERR_ARG; }
-  if (quality < 1 || quality > 100) { set_error("vbt_mjpeg_create: quality %d outside 1..100", quality); return VBT_ERR_ARG; }
-  if (max_batch < 1 || max_batch > MJ_MAX_BATCH) { set_error("vbt_mjpeg_create: max_batch %d outside 1..%d", max_batch, MJ_MAX_BATCH); return VBT_ERR_ARG; }
+  const bool scaled = SH != H || SW != W;
+  if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_yuv(pix_fmt)) { set_error("%s: unknown pixel format %d", who, pix_fmt); return VBT_ERR_ARG; }
+  if (SH < 1 || SW < 1 || SH > 16384 || SW > 16384) { set_error("%s: frames of 1..16384 pixels a side, got %d x %d", who, SH, SW); return VBT_ERR_ARG; }
+  if (pix_fmt_is_yuv(pix_fmt) && ((SH & 1) || (SW & 1))) { set_error("%s: YUV 4:2:0 frames have even H and W, got %d x %d", who, SH, SW); return VBT_ERR_ARG; }
+  if (H < 1 || W < 1 || H > 16384 || W > 16384) { set_error("%s: an output (h and w) of 1..16384 pixels a side, got %d x %d", who, H, W); return VBT_ERR_ARG; }
+  if (pix_fmt_is_yuv(pix_fmt) && ((H & 1) || (W & 1))) { set_error("%s: YUV 4:2:0 frames have even h and w, got %d x %d", who, H, W); return VBT_ERR_ARG; }
+  if (quality < 1 || quality > 100) { set_error("%s: quality %d outside 1..100", who, quality); return VBT_ERR_ARG; }
+  if (max_batch < 1 || max_batch > MJ_MAX_BATCH) { set_error("%s: max_batch %d outside 1..%d", who, max_batch, MJ_MAX_BATCH); return VBT_ERR_ARG; }
   MjTables tab;
   build_tables(H, W, quality, &tab);
-  if (!dct_table_ok() || tab.header[0] != 0xFF) { set_error("vbt_mjpeg_create: the built-in tables fail their self-check"); return VBT_ERR_STATE; }
-  if (int rc = use_device("vbt_mjpeg_create", device)) return rc;
+  if (!dct_table_ok() || tab.header[0] != 0xFF) { set_error("%s: the built-in tables fail their self-check", who); return VBT_ERR_STATE; }
+  const ScTableLayout SL = sc_table_layout(H, W, pix_fmt);
+  std::vector<ScTap> taps;
+  if (scaled) {
+    taps.resize((size_t)SL.total);
+    sc_build_tables(SH, SW, H, W, pix_fmt, SL, taps.data());
+  }
+  if (int rc = use_device(who, device)) return rc;
   std::unique_ptr<vbt_mjpeg> m(new vbt_mjpeg());
   m->device = device; m->H = H; m->W = W; m->fmt = pix_fmt; m->quality = quality; m->max_batch = max_batch;
   m->MW = (W + 15) / 16; m->MH = (H + 15) / 16;
-  m->frame_bytes = pix_fmt == VBT_PIX_RGB24 ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2;
+  m->frame_bytes = sc_frame_bytes(SH, SW, pix_fmt);
   m->slot_bytes = (size_t)MJ_SLOT_PER_MCU * m->MW;
   const size_t B = (size_t)max_batch, units = B * m->MH;
   m->out_bytes = B * (MJ_HEADER + (size_t)m->MH * (m->slot_bytes + 2));
@@ -487,13 +552,15 @@ int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max
   const auto r_sizes = C.add<uint32_t>(units);
   const auto r_levels = C.add<int16_t>(units * 6 * m->MW * 64);
   const auto r_slots = C.add<uint8_t>(units * m->slot_bytes), r_out = C.add<uint8_t>(m->out_bytes);
+  const auto r_taps = C.add<ScTap>(taps.size());
   const size_t total = C.padded_bytes();
   hipError_t e = m->blob.alloc(total);
   uint8_t* const blob = m->blob.get();
   if (e == hipSuccess) e = hipMemcpy(C.ptr(blob, r_tab), &tab, sizeof(tab), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(C.ptr(blob, r_offsets), 0, (B + 2) * 8);
+  if (e == hipSuccess && scaled) e = hipMemcpy(C.ptr(blob, r_taps), taps.data(), taps.size() * sizeof(ScTap), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    set_error("vbt_mjpeg_create: %zu bytes of device memory for %d frames of %d x %d: %s", total, max_batch, W, H, hipGetErrorString(e));
+    set_error("%s: %zu bytes of device memory for %d frames of %d x %d: %s", who, total, max_batch, W, H, hipGetErrorString(e));
     return VBT_ERR_HIP;
   }
   MjArgs& A = m->args;
@@ -502,8 +569,25 @@ int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max
   A.offsets = C.ptr(blob, r_offsets); A.flag = A.offsets + B + 1; A.fsize = C.ptr(blob, r_fsize); A.ioff = C.ptr(blob, r_ioff);
   A.sizes = C.ptr(blob, r_sizes); A.levels = C.ptr(blob, r_levels);
   A.slots = C.ptr(blob, r_slots); A.slot_bytes = m->slot_bytes; A.out = C.ptr(blob, r_out); A.out_bytes = m->out_bytes;
+  if (scaled) {
+    const ScTap* t = C.ptr(blob, r_taps);
+    m->scaled = true;
+    m->scale = MjScale{t + SL.at[0][0], t + SL.at[0][1], t + SL.at[1][0], t + SL.at[1][1], SH, SW};
+  }
   *out = m.release();
   return VBT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbt_mjpeg_create(int device, int H, int W, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out) {
+  return mjpeg_create("vbt_mjpeg_create", device, H, W, H, W, pix_fmt, quality, max_batch, out);
+}
+
+int vbt_mjpeg_create_scaled(int device, int H, int W, int h, int w, int pix_fmt, int quality, int max_batch, vbt_mjpeg** out) {
+  return mjpeg_create("vbt_mjpeg_create_scaled", device, H, W, h, w, pix_fmt, quality, max_batch, out);
 }
 
 void vbt_mjpeg_destroy(vbt_mjpeg* m) {
@@ -521,7 +605,11 @@ int vbt_mjpeg_encode(vbt_mjpeg* m, const uint8_t* frames_dev, int B, void* strea
   A.frames = frames_dev; A.B = B;
   hipStream_t st = (hipStream_t)stream;
   VBT_HIP_CHECK(hipMemsetAsync(A.flag, 0, 8, st));
-  mjpeg_transform_kernel<<<dim3((unsigned)((m->MW + MJ_GROUP - 1) / MJ_GROUP), (unsigned)m->MH, (unsigned)B), MJ_THREADS, 0, st>>>(A);
+  const dim3 grid((unsigned)((m->MW + MJ_GROUP - 1) / MJ_GROUP), (unsigned)m->MH, (unsigned)B);
+  if (m->scaled)
+    mjpeg_transform_kernel<true><<<grid, MJ_THREADS, 0, st>>>(A, m->scale);
+  else
+    mjpeg_transform_kernel<false><<<grid, MJ_THREADS, 0, st>>>(A, m->scale);
   mjpeg_entropy_kernel<<<dim3((unsigned)m->MH, (unsigned)B), MJ_THREADS, 0, st>>>(A);
   mjpeg_offsets_kernel<<<dim3((unsigned)B), MJ_THREADS, 0, st>>>(A);
   mjpeg_gather_kernel<<<dim3((unsigned)m->MH, (unsigned)B), MJ_THREADS, 0, st>>>(A);

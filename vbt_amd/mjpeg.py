@@ -22,15 +22,22 @@ AVI_MAX_BYTES = 2 ** 31 - 1              # AVI 1.0: one RIFF chunk, 32-bit sizes
 
 
 class Encoder:
-    """vbt_mjpeg (include/vbt_hip.h): one frame size, pixel format and quality; batches of up to max_batch frames."""
+    """vbt_mjpeg (include/vbt_hip.h): one frame size, pixel format and quality; batches of up to max_batch frames.
+    out_hw=(h, w): the frames of H x W are encoded as JPEGs of h x w (vbt_mjpeg_create_scaled; "Scaled export"), resized in the
+    encoder's colour stage - the bytes Encoder(h, w) gives for the frames scale.Scaler gives."""
 
-    def __init__(self, H, W, pix_fmt="rgb24", quality=85, max_batch=64, device=0):
+    def __init__(self, H, W, pix_fmt="rgb24", quality=85, max_batch=64, device=0, out_hw=None):
         self.H, self.W, self.pix_fmt, self.quality, self.max_batch = int(H), int(W), str(pix_fmt).lower(), int(quality), int(max_batch)
+        self.out_hw = (self.H, self.W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().vbt_mjpeg_create(int(device), self.H, self.W, pix_fmt_code(pix_fmt), self.quality, self.max_batch, ctypes.byref(h)))
+        if out_hw is None:
+            _lib.check(_lib.lib().vbt_mjpeg_create(int(device), self.H, self.W, pix_fmt_code(pix_fmt), self.quality, self.max_batch, ctypes.byref(h)))
+        else:
+            _lib.check(_lib.lib().vbt_mjpeg_create_scaled(int(device), self.H, self.W, self.out_hw[0], self.out_hw[1], pix_fmt_code(pix_fmt), self.quality,
+                                                          self.max_batch, ctypes.byref(h)))
         self._h = h
         self._B, self._stream = 0, None
-        self._host = np.empty(max(4096, self.H * self.W // 2), np.uint8)
+        self._host = np.empty(max(4096, self.out_hw[0] * self.out_hw[1] // 2), np.uint8)
         self.last_bytes = 0
 
     def __del__(self):

@@ -178,7 +178,7 @@ def _hud_params(who, hud_params):
 
 
 def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=None, device=0, sink=None, quality=85, hud=None, hud_params=None,
-           **params):
+           display_hw=None, **params):
     """The kept frames of a clip (1-based number a multiple of frame_stride, reference track.py:166) with the overlay of `data`:
     frames uint8 [T,H,W,3] (or [T,H*3//2,W] for "nv12" / "i420"; numpy array or memmap), `batch` frames at a time through the device.
     Returns (or fills `out`, e.g. a numpy.lib.format.open_memmap) uint8 [T // frame_stride, ...] of the same layout.  Unlike the
@@ -186,19 +186,24 @@ def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=Non
     sink: an mjpeg.AviWriter - each batch is then uploaded, drawn, encoded as JPEG on the device at `quality` (mjpeg.Encoder, on the
     stream of the draw, nothing synchronised in between) and only its compressed bytes are read back and written to the sink; `out`
     is not used and the number of frames written is returned.
-    hud: the phases of one id (what Overlay.set_hud takes) - the rep panel is then drawn on every kept frame, with hud_params (a dict)."""
+    hud: the phases of one id (what Overlay.set_hud takes) - the rep panel is then drawn on every kept frame, with hud_params (a dict).
+    display_hw: (h, w) - every frame is drawn at full size and then resized to h x w on the device (include/vbt_hip.h, "Scaled
+    export"; scale.display_size gives the reference's size for a height): `out` has the layout of (h, w), a sink gets h x w JPEGs."""
     stride = max(int(frame_stride), 1)
     H, W = source_hw(frames, pix_fmt)
     shape = frame_shape(pix_fmt, H, W)
     if tuple(frames.shape[1:]) != shape or frames.dtype != np.uint8:
         raise ValueError(f"render: {pix_fmt} frames must be uint8 [T, {', '.join(str(v) for v in shape)}], got {frames.dtype} {tuple(frames.shape)}")
     kept = int(frames.shape[0]) // stride
+    if display_hw is not None:
+        display_hw = (int(display_hw[0]), int(display_hw[1]))
+    out_shape = shape if display_hw is None else frame_shape(pix_fmt, *display_hw)
     if sink is not None:
         out = None
     elif out is None:
-        out = np.empty((kept,) + shape, np.uint8)
-    elif tuple(out.shape) != (kept,) + shape or out.dtype != np.uint8:
-        raise ValueError(f"render: out must be uint8 {(kept,) + shape}, got {out.dtype} {tuple(out.shape)}")
+        out = np.empty((kept,) + out_shape, np.uint8)
+    elif tuple(out.shape) != (kept,) + out_shape or out.dtype != np.uint8:
+        raise ValueError(f"render: out must be uint8 {(kept,) + out_shape}, got {out.dtype} {tuple(out.shape)}")
     ov = Overlay(H, W, pix_fmt, device=device, **params)
     ov.set_rows(data, fps)
     if hud is not None:
@@ -208,10 +213,16 @@ def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=Non
     fb = int(np.prod(shape))
     buf = DeviceBuffer(B * fb, device)
     host = np.empty((B,) + shape, np.uint8)
-    enc = None
+    enc = scaler = None
     if sink is not None and kept:
         from .mjpeg import Encoder
-        enc = Encoder(H, W, pix_fmt, quality=quality, max_batch=B, device=device)
+        enc = Encoder(H, W, pix_fmt, quality=quality, max_batch=B, device=device, out_hw=display_hw)
+    elif display_hw is not None and kept:                           # the raw route: scaled into a second buffer, that one copied back
+        from .scale import Scaler
+        scaler = Scaler(H, W, display_hw[0], display_hw[1], pix_fmt, device=device)
+        ob = int(np.prod(out_shape))
+        small = DeviceBuffer(B * ob, device)
+        host_out = np.empty((B,) + out_shape, np.uint8)
     for i0 in range(0, kept, B):
         nb = min(B, kept - i0)
         first = (i0 + 1) * stride - 1                               # 0-based index of the batch's first kept frame
@@ -222,6 +233,12 @@ def render(frames, data, fps, frame_stride=1, pix_fmt="rgb24", batch=64, out=Non
             enc.encode(buf.ptr, nb)
             for jpeg in enc.read():
                 sink.write(jpeg)
+            continue
+        if scaler is not None:
+            scaler.run(buf.ptr, small.ptr, nb)
+            _lib.check(L.vbt_stream_synchronize(None))
+            _lib.check(L.vbt_memcpy(host_out.ctypes.data, small.ptr, nb * ob, 1))
+            out[i0:i0 + nb] = host_out[:nb]
             continue
         _lib.check(L.vbt_stream_synchronize(None))
         _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr, nb * fb, 1))

@@ -78,7 +78,7 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None, tracker="ocsort"):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None, tracker="ocsort", display_hw=None):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -100,25 +100,29 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     live analysis"): live rep analysis is switched on (with or without `live`), the panel follows the clip on the device and shows,
     on every frame of a batch, the leader's reps as they stand after that batch.  Keys: plate_diameter (default 0.45, the live
     analysis runs with it) and the panel's x, y, scale, full_scale_cm, bg.  The rows are those of a run without it.
-    tracker: "ocsort" (default) or "sort" = SortTracker(max_age=30) of track.py:156; everything above reads the row log and works with either."""
+    tracker: "ocsort" (default) or "sort" = SortTracker(max_age=30) of track.py:156; everything above reads the row log and works with either.
+    display_hw (with video_out or video_sink): (h, w) - the exported frames are drawn at full size and then resized to h x w on the
+    device (include/vbt_hip.h, "Scaled export"; the reference's --display_image_height, track.py:237-239): video_out has the layout
+    of (h, w), video_sink gets h x w JPEGs.  The rows are those of a run without it."""
     if hud_live is not None and not (one_pass and (video_out is not None or video_sink is not None)):
         raise ValueError("track_frames: hud_live draws on a one-pass export (one_pass=True with video_out or video_sink)")
     if one_pass and (video_out is not None or video_sink is not None):
         return _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw,
-                             export=(video_out, video_sink, video_quality), hud_live=hud_live, tracker=tracker)
+                             export=(video_out, video_sink, video_quality, display_hw), hud_live=hud_live, tracker=tracker)
     data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, tracker=tracker)
     if video_out is not None:
         from .overlay import render
-        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device)
+        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device, display_hw=display_hw)
     if video_sink is not None:
         from .overlay import render
-        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, device=device, sink=video_sink, quality=video_quality)
+        render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, device=device, sink=video_sink, quality=video_quality,
+               display_hw=display_hw)
     return data
 
 
 def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None, hud_live=None,
                   tracker="ocsort"):
-    """export: None, or (video_out, video_sink, video_quality) of a one-pass export; hud_live: None, or the live rep panel's dict"""
+    """export: None, or (video_out, video_sink, video_quality, display_hw) of a one-pass export; hud_live: None, or the live rep panel's dict"""
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
     if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
@@ -151,21 +155,28 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
         shape = frame_shape(pix_fmt, H, W)
         fb = int(np.prod(shape))
         dev = [DeviceBuffer(F * fb, device) for _ in range(2)]
-    ov = enc = host = None
+    ov = enc = host = scaler = None
     if export is not None:
         from .overlay import HUD_FOLLOW_FLAGGED, Overlay, follow_flag_names, hud_follow_flag_names
-        video_out, video_sink, video_quality = export
-        if video_out is not None and (tuple(video_out.shape) != (kept,) + shape or video_out.dtype != np.uint8):
-            raise ValueError(f"track_frames: video_out must be uint8 {(kept,) + shape}, got {video_out.dtype} {tuple(video_out.shape)}")
+        video_out, video_sink, video_quality, display_hw = export
+        if display_hw is not None:
+            display_hw = (int(display_hw[0]), int(display_hw[1]))
+        out_shape = shape if display_hw is None else frame_shape(pix_fmt, *display_hw)
+        if video_out is not None and (tuple(video_out.shape) != (kept,) + out_shape or video_out.dtype != np.uint8):
+            raise ValueError(f"track_frames: video_out must be uint8 {(kept,) + out_shape}, got {video_out.dtype} {tuple(video_out.shape)}")
         ov = Overlay(H, W, pix_fmt, device=device)
         ov.follow(*pipe.tracker.rows_dev(0), max_frame=max(kept * stride, 1), max_rows_per_frame=25, fps=fps)   # (a frame has at most 25 detections)
         if hud_live is not None:
             ov.hud_follow(pipe.tracker, 0, fps, **hud_live)
         if video_sink is not None and kept:
             from .mjpeg import Encoder
-            enc = Encoder(H, W, pix_fmt, quality=video_quality, max_batch=F, device=device)
+            enc = Encoder(H, W, pix_fmt, quality=video_quality, max_batch=F, device=device, out_hw=display_hw)
         if video_out is not None:
-            host = np.empty((F,) + shape, np.uint8)
+            host = np.empty((F,) + out_shape, np.uint8)
+            if display_hw is not None and kept:                          # scaled into a third buffer behind the draw; that one is copied back
+                from .scale import Scaler
+                scaler = Scaler(H, W, display_hw[0], display_hw[1], pix_fmt, device=device)
+                small = DeviceBuffer(F * int(np.prod(out_shape)), device)
     L = _lib.lib()
     for i0 in range(0, len(idx_all), F):
         idx = idx_all[i0:i0 + F]
@@ -189,8 +200,10 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
                     for jpeg in enc.read():
                         video_sink.write(jpeg)
                 if host is not None:
+                    if scaler is not None:
+                        scaler.run(buf.ptr, small.ptr, len(idx), 0)
                     _lib.check(L.vbt_stream_synchronize(None))
-                    _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr, len(idx) * fb, 1))
+                    _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr if scaler is None else small.ptr, len(idx) * int(np.prod(out_shape)), 1))
                     video_out[i0:i0 + len(idx)] = host[:len(idx)]
         else:
             chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
