@@ -527,6 +527,49 @@ int vbt_eval_curves_from_table(const float* scores, const double* ious, int n, d
                                double* precision, double* recall, float* pr_thresholds, int pr_cap, double* fpr, double* tpr,
                                float* roc_thresholds, int roc_cap);
 
+/* ------------------------------------------------------------------ COCO metrics -------------
+ * The second set of numbers the reference reports its detectors by: the twelve COCO detection metrics that model.evaluate prints at
+ * the end of every training log under models/ (train.py:64,70) - COCOeval's evaluateImg / accumulate / summarize for ONE category, no crowd and no
+ * `difficult` boxes (class columns are ignored, as eval.py ignores them).
+ * Box contract, all in double.  A detection (normalised float32 ymin,xmin,ymax,xmax, source size H x W): x = xmin W, y = ymin H,
+ * w = xmax W - x, h = ymax H - y.  Ground truth (integer VOC corners): x = xmin, y = ymin, w = xmax - xmin, h = ymax - ymin.
+ * area = w h in source-image pixels for both.  IoU is maskApi's bbIou on xywh: iw = min(dx+dw, gx+gw) - max(dx, gx), 0 if iw <= 0,
+ * ih likewise, i = iw ih, IoU = i / (dw dh + gw gh - i).
+ * Tables: IoU thresholds np.linspace(.5, .95, 10), recall thresholds np.linspace(0, 1, 101), area ranges [0,1e10], [0,32^2],
+ * [32^2,96^2], [96^2,1e10] (a box is ignored for a range when area < lo || area > hi), maxDets 1 / 10 / 100.
+ * One handle holds ONE model's rows on the device: per detection its score, image number, rank inside its image (descending score,
+ * stable) and two 40-bit masks `matched` and `ignored`, bit a * 10 + t for area range a and IoU threshold t; and the number of
+ * non-ignored ground-truth boxes per range over all images added. */
+typedef struct vbt_coco vbt_coco;
+typedef struct {
+  double stats[12];               /* AP, AP50, AP75, APs, APm, APl, ARmax1, ARmax10, ARmax100, ARs, ARm, ARl; -1: no entry */
+  int32_t n_images, n_rows;       /* images added, rows of the table */
+  int32_t n_gt[4];                /* non-ignored ground-truth boxes per area range */
+} vbt_coco_summary;
+/* max_batch: images per vbt_coco_add_detections call (1..4096); rows_cap: rows the table holds (25 per image is the most). */
+int vbt_coco_create(int device, int max_batch, int rows_cap, vbt_coco** out);
+void vbt_coco_destroy(vbt_coco* c);
+/* an empty table and zero counts again (synchronises the device) */
+int vbt_coco_reset(vbt_coco* c);
+/* The arguments and rules of vbt_eval_add_detections: the detections of B images as the detector leaves them on the device, the
+ * source sizes and the ground truth in CSR form from the host.  evaluateImg of every image for the four ranges and ten thresholds,
+ * one wavefront per image; the detections need not be sorted.  An image with neither boxes nor detections contributes nothing; one
+ * with boxes and no detection counts its boxes.  Enqueue only, one pinned upload per call, calls run in call order whatever their
+ * streams.  VBT_ERR_CAPACITY, with nothing enqueued: B > max_batch, or an image with more than VBT_EVAL_MAX_GT boxes.  Rows beyond
+ * rows_cap are counted, not stored, and reported as VBT_ERR_CAPACITY by vbt_coco_table / vbt_coco_accumulate. */
+int vbt_coco_add_detections(vbt_coco* c, const float* boxes_dev, const float* scores_dev, const int32_t* counts_dev, int B,
+                            const int32_t* hw_host, const int32_t* gt_offsets_host, const int32_t* gt_boxes_host, void* stream);
+/* The rows, images in the order added: *n_rows always; with any array non-NULL one copy per array, cap rows each (VBT_ERR_CAPACITY if
+ * cap < *n_rows).  Synchronises the stream of the last vbt_coco_add_detections. */
+int vbt_coco_table(vbt_coco* c, int* n_rows, float* scores, int32_t* image, int32_t* rank, uint64_t* matched, uint64_t* ignored, int cap);
+/* COCOeval.accumulate and summarize over the device table: one stable sort by descending score (-0.0 and +0.0 one score), then one
+ * workgroup per (range, maxDets, threshold).  precision [10][101][4][3] and scores [10][101][4][3] (the score at each recall
+ * threshold, as double) in [T][R][A][M] order, recall [10][4][3] in [T][A][M] order: COCOeval's arrays without the category axis,
+ * -1 throughout a slice whose range has no non-ignored box.  Every entry equals numpy's bit for bit; a stat is the mean over the
+ * entries > -1 of its slice, summed on the host in index order, or -1.  Any array may be NULL.  Synchronises the stream of the last
+ * vbt_coco_add_detections. */
+int vbt_coco_accumulate(vbt_coco* c, vbt_coco_summary* s, double* precision, double* recall, double* scores);
+
 /* ------------------------------------------------------------------ tracking overlay --------
  * Replaces draw_bounding_box / draw_bar_path (reference track.py:28-62,201-224): the tracked plate's box, its tracking id and the bar
  * path of its last `trail` centres, drawn into frames that already sit in device memory, in place and in the frames' own pixel

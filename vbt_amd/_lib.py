@@ -68,6 +68,11 @@ class EvalSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("n_rows", "n_pos", "n_neg", "n_pr", "n_roc", "flags")] + [("ap", c_double), ("auc", c_double)]
 
 
+class CocoSummary(ctypes.Structure):
+    """vbt_coco_summary (include/vbt_hip.h)"""
+    _fields_ = [("stats", c_double * 12), ("n_images", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_gt", ctypes.c_int32 * 4)]
+
+
 class OverlayParams(ctypes.Structure):
     """vbt_overlay_params (include/vbt_hip.h)"""
     _fields_ = [("trail", ctypes.c_int32), ("thickness", ctypes.c_int32), ("radius", ctypes.c_int32), ("label_scale", ctypes.c_int32),
@@ -224,6 +229,12 @@ _SIGS = {
     "vbt_eval_curves": (c_int, [c_void_p, c_double, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_eval_curves_from_table": (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, ctypes.POINTER(EvalSummary), c_void_p, c_void_p, c_void_p, c_int,
                                            c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_coco_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "vbt_coco_destroy": (None, [c_void_p]),
+    "vbt_coco_reset": (c_int, [c_void_p]),
+    "vbt_coco_add_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vbt_coco_table": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_coco_accumulate": (c_int, [c_void_p, ctypes.POINTER(CocoSummary), c_void_p, c_void_p, c_void_p]),
     "vbt_overlay_default_params": (None, [ctypes.POINTER(OverlayParams)]),
     "vbt_overlay_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(OverlayParams), ctypes.POINTER(c_void_p)]),
     "vbt_overlay_destroy": (None, [c_void_p]),

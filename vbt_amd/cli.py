@@ -74,6 +74,7 @@
   python -m vbt_amd.cli eval MODELS... [--img_dir data/test] [--annotations_dir data/test] [--iou_threshold 0.5]
                            [--detections_df dfs/eval_detections.pkl.gz] [--replace_df] [--score_thresholds "[0.2, 0.5]"] [--curve_dir DIR] [--rgb]
                            [--jpeg_decode auto|gpu|host] [--fig_dir DIR] [--fig_size 1120x640] [--fig_scale 2] [--fig_format jpg|ppm] [--fig_quality 90]
+                           [--coco [--coco_dump DIR]]
       reference eval.py:471-521: VOC annotations, every image through each model at threshold 0 (.jpg files decoded on the GPU
       straight to the network input, mixed sizes in one batch; --jpeg_decode host: with PIL as before), Hungarian
       matching and the PR / ROC curves on the GPU; writes (or, when it exists and --replace_df is not given, reads) the detections
@@ -81,6 +82,10 @@
       closest curve point; --curve_dir writes the curve points as CSV.  --fig_dir writes, after the lines, the reference's figures
       (eval.py:218-468), rendered and encoded on the GPU: precision_recall_iou_{t} and roc_iou_{t} with every model and, with
       --score_thresholds, precision_recall_{m}_iou_{t} and roc_{m}_iou_{t} per model, annotated at the closest curve points.
+      --coco prints, after all that, one line `model: {'AP': ..., ..., 'AP_/barbell': ...}` per model: the twelve COCO detection metrics
+      and the per-class AP that model.evaluate prints at the end of the reference's training logs (train.py:64,70), matched and
+      accumulated on the GPU; it always runs the models (the stored DataFrame has neither boxes nor unmatched detections).  --coco_dump DIR
+      writes instances.json and {model}_detections.json for a cross-check with pycocotools on a machine that has it.
 Option names (including the reference's `treshold` / `qualysis` spellings) and defaults follow the reference.
 """
 import contextlib
@@ -649,8 +654,12 @@ def validate(kinovea_dir, qualysis_dir, df_dir, plate_diameter, fig_dir, fig_for
 @click.option("--fig_format", default="jpg", show_default=True, type=click.Choice(["jpg", "ppm"]),
               help="jpg: baseline JPEG encoded on the GPU; ppm: the raw RGB frame behind a P6 header, lossless.")
 @click.option("--fig_quality", default=90, show_default=True, type=click.IntRange(1, 100), help="JPEG quality of --fig_format jpg.")
+@click.option("--coco", is_flag=True, help="After the lines above, print per model the twelve COCO detection metrics and the per-class AP as the "
+                                           "reference's training logs end (model.evaluate). Always runs the models.")
+@click.option("--coco_dump", default=None, show_default=True, help="With --coco: directory for instances.json and {model}_detections.json, to "
+                                                                   "cross-check the numbers with pycocotools elsewhere.")
 def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, replace_df, score_thresholds, curve_dir, rgb, jpeg_decode, fig_dir, fig_size,
-             fig_scale, fig_format, fig_quality):
+             fig_scale, fig_format, fig_quality, coco, coco_dump):
     import ast
     import pandas as pd
     from . import evaluate as E
@@ -661,6 +670,8 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
     size = re.fullmatch(r"\s*(\d+)\s*[xX]\s*(\d+)\s*", fig_size)
     if not size:
         raise click.BadParameter(f"expected WIDTHxHEIGHT, got {fig_size!r}", param_hint="--fig_size")
+    if coco_dump is not None and not coco:
+        raise click.UsageError("--coco_dump needs --coco")
     if not os.path.exists(detections_df) or replace_df:                            # reference eval.py:506-512
         click.echo(f"Creating dataframe '{detections_df}'.")
         annotations = E.read_annotations(annotations_dir)
@@ -700,6 +711,25 @@ def evaluate(models, img_dir, annotations_dir, iou_threshold, detections_df, rep
                      scale=fig_scale)
         except ValueError as e:                                                    # (VbtArgError: a figure size the layout refuses)
             raise click.UsageError(str(e))
+    if coco:                                                                       # reference train.py:64,70: the dict model.evaluate prints
+        annotations = E.read_annotations(annotations_dir)
+        images = [(name, E.find_image(img_dir, name)) for name in annotations]
+        try:
+            srt = E.SortedImages(images, jpeg_decode)
+            dets, sizes = {}, {}
+            for model in models:
+                res, _, det = E.coco_evaluate(model, images, annotations, rgb=rgb, jpeg_decode=jpeg_decode, sorted_images=srt)
+                line = {k: float(str(np.float32(v))) for k, v in res.metrics().items()}      # through float32, as the log's values
+                click.echo(f"{E.model_name(model)}: {line}")
+                dets[E.model_name(model)] = det
+        except E.JpegRefused as e:
+            raise click.UsageError(str(e))
+        except E.JpegDamaged as e:
+            raise click.ClickException(str(e))
+        if coco_dump is not None:
+            for name, path in images:
+                sizes[name] = srt.heads[name][:2] if name in srt.heads else E.image_size(path)
+            E.coco_dump(coco_dump, annotations, sizes, dets)
 
 
 if __name__ == "__main__":

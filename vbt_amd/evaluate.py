@@ -5,6 +5,10 @@ against the ground truth, precision-recall / ROC curves, AP and AUC per model, a
 Matching and curves run on the GPU (`vbt_eval_*`, include/vbt_hip.h; vbt_amd/csrc/evaluate.hip); the detections never leave the
 device between the detector and the matcher.  No torch, no scipy, no scikit-learn.
 
+The second set of numbers the reference reports its detectors by - the twelve COCO detection metrics and the per-class AP that
+model.evaluate prints at the end of the training logs (train.py:64,70) - comes from the same image path and a second matcher on the
+device (`vbt_coco_*`; vbt_amd/csrc/evaluate_coco.hip): CocoEvaluator, coco_metrics, coco_dump.  No pycocotools.
+
 Images.  eval.py reads every image with cv2.imread and hands that **BGR** array to the network unswapped (eval.py:173-180;
 track.py:171 swaps, eval.py does not).  The default here reproduces that: `.npy` files hold a decoded image uint8 [H,W,3] in cv2's BGR
 order; `.png` files are decoded with PIL and reordered to BGR; `rgb=True` (CLI `--rgb`) feeds RGB instead.
@@ -30,6 +34,7 @@ MAX_DETECTIONS = 25
 MAX_GT = 64                        # VBT_EVAL_MAX_GT
 NO_POSITIVES, NO_NEGATIVES = 1, 2  # VBT_EVAL_NO_*
 BATCH = 64
+COCO_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "ARmax1", "ARmax10", "ARmax100", "ARs", "ARm", "ARl", "AP_/" + LABEL)   # the log's dict
 
 
 class Annotations(dict):
@@ -116,6 +121,18 @@ def curves_from_table(scores, ious, iou_threshold=0.5, device=0):
                        len(sc))
 
 
+def _csr(hw, gt_list):
+    """(hw int32 [B,2], B, offsets int32 [B+1], boxes int32 [*,4]) of per-image sizes and ground-truth arrays"""
+    hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+    B = len(hw)
+    if len(gt_list) != B:
+        raise ValueError("one ground-truth array per image")
+    off = np.zeros(B + 1, np.int32)
+    off[1:] = np.cumsum([len(g) for g in gt_list])
+    gt = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int64).reshape(-1, 4) for g in gt_list]) if B else np.zeros((0, 4)), dtype=np.int32)
+    return hw, B, off, gt
+
+
 class Evaluator:
     """One model's detection table on the device (`vbt_eval`, include/vbt_hip.h)."""
 
@@ -135,13 +152,7 @@ class Evaluator:
     def add(self, boxes_ptr, scores_ptr, counts_ptr, hw, gt_list, stream=None):
         """B images' detections (raw device pointers, the detector's layout) + per image (height, width) and ground-truth boxes
         int [n,4] = ymin,xmin,ymax,xmax.  Enqueue only."""
-        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
-        B = len(hw)
-        if len(gt_list) != B:
-            raise ValueError("one ground-truth array per image")
-        off = np.zeros(B + 1, np.int32)
-        off[1:] = np.cumsum([len(g) for g in gt_list])
-        gt = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int64).reshape(-1, 4) for g in gt_list]) if B else np.zeros((0, 4)), dtype=np.int32)
+        hw, B, off, gt = _csr(hw, gt_list)
         _lib.check(_lib.lib().vbt_eval_add_detections(self._h, boxes_ptr, scores_ptr, counts_ptr, B, hw.ctypes.data, off.ctypes.data,
                                                       gt.ctypes.data if len(gt) else None, stream))
 
@@ -160,6 +171,62 @@ class Evaluator:
         """vbt_eval_curves over the device table."""
         L = _lib.lib()
         return _curve_call(lambda s, *a: L.vbt_eval_curves(self._h, float(iou_threshold), s, *a), self.rows_cap)
+
+
+class CocoResult:
+    """vbt_coco_accumulate's outputs: stats {name: value} in the log's order (COCO_KEYS without the per-class entry), precision
+    [10,101,4,3], recall [10,4,3], scores [10,101,4,3] (COCOeval's arrays without the category axis), n_gt [4], n_images, n_rows."""
+
+    def __init__(self, s, precision, recall, scores):
+        self.stats = dict(zip(COCO_KEYS[:12], (float(v) for v in s.stats)))
+        self.n_images, self.n_rows, self.n_gt = int(s.n_images), int(s.n_rows), np.array(list(s.n_gt), np.int64)
+        self.precision, self.recall, self.scores = precision, recall, scores
+
+    def metrics(self):
+        """the dict model.evaluate prints (train.py:64): the twelve stats and the per-class AP, which with one class is AP"""
+        return dict(self.stats, **{COCO_KEYS[12]: self.stats["AP"]})
+
+
+class CocoEvaluator:
+    """One model's COCO rows on the device (`vbt_coco`, include/vbt_hip.h): the shape of Evaluator."""
+
+    def __init__(self, rows_cap, max_batch=BATCH, device=0):
+        self._h = ctypes.c_void_p()
+        self.rows_cap, self.max_batch, self.device = int(rows_cap), int(max_batch), int(device)
+        _lib.check(_lib.lib().vbt_coco_create(self.device, self.max_batch, self.rows_cap, ctypes.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.lib().vbt_coco_destroy(self._h)
+            self._h = None
+
+    def reset(self):
+        _lib.check(_lib.lib().vbt_coco_reset(self._h))
+
+    def add(self, boxes_ptr, scores_ptr, counts_ptr, hw, gt_list, stream=None):
+        """Evaluator.add's arguments.  Enqueue only."""
+        hw, B, off, gt = _csr(hw, gt_list)
+        _lib.check(_lib.lib().vbt_coco_add_detections(self._h, boxes_ptr, scores_ptr, counts_ptr, B, hw.ctypes.data, off.ctypes.data,
+                                                      gt.ctypes.data if len(gt) else None, stream))
+
+    def table(self):
+        """{"score" f32, "image" i32, "rank" i32, "matched" u64, "ignored" u64}: images in the order added, inside an image by descending
+        score; bit a * 10 + t of the masks belongs to area range a and IoU threshold t (synchronises)."""
+        L = _lib.lib()
+        n = ctypes.c_int(0)
+        _lib.check(L.vbt_coco_table(self._h, ctypes.byref(n), None, None, None, None, None, 0))
+        out = {"score": np.empty(n.value, np.float32), "image": np.empty(n.value, np.int32), "rank": np.empty(n.value, np.int32),
+               "matched": np.empty(n.value, np.uint64), "ignored": np.empty(n.value, np.uint64)}
+        if n.value:
+            _lib.check(L.vbt_coco_table(self._h, ctypes.byref(n), *(out[k].ctypes.data for k in ("score", "image", "rank", "matched", "ignored")), n.value))
+        return out
+
+    def accumulate(self):
+        """vbt_coco_accumulate over the device table: CocoResult."""
+        p, r, sc = np.empty((10, 101, 4, 3)), np.empty((10, 4, 3)), np.empty((10, 101, 4, 3))
+        s = _lib.CocoSummary()
+        _lib.check(_lib.lib().vbt_coco_accumulate(self._h, ctypes.byref(s), p.ctypes.data, r.ctypes.data, sc.ctypes.data))
+        return CocoResult(s, p, r, sc)
 
 
 def match_bboxes(gt_bboxes, det_bboxes, device=0):
@@ -265,12 +332,12 @@ class SortedImages:
             self.host.append(name)
 
 
-def _stills_table(pipe, ev, stream, srt, paths, annotations, rgb, device, batch):
+def _stills_table(pipe, evs, stream, srt, paths, annotations, rgb, device, batch):
     """The .jpg files the GPU decoder accepts, in the given order and whatever their sizes: cut into batches by count and block budget,
     only the compressed bytes uploaded, decoded and resized to the model's input size into one of two device buffers that detect_into
     takes by pointer - the order of decode and forwards is track_frames' for .avi sources.  The handle's budget is the largest batch's
-    need, so a directory of small images takes little device memory.  A file whose scan status is not 0 raises JpegDamaged.  Returns
-    the device outputs to keep alive."""
+    need, so a directory of small images takes little device memory.  A file whose scan status is not 0 raises JpegDamaged.  Every
+    evaluator of `evs` gets every batch.  Returns the device outputs to keep alive."""
     from .stills import STATUS_TEXT, JpegStills, plan
     names, heads = srt.stills, srt.heads
     n, size = len(names), pipe._size
@@ -297,23 +364,18 @@ def _stills_table(pipe, ev, stream, srt, paths, annotations, rgb, device, batch)
         ptrs = (out[0].ptr + i0 * MAX_DETECTIONS * 16, out[1].ptr + i0 * MAX_DETECTIONS * 4, out[2].ptr + i0 * MAX_DETECTIONS * 4, out[3].ptr + i0 * 4)
         pipe.detect_into(buf.ptr, *ptrs, stream=stream.value, n_frames=len(part))
         pipe.join_detectors(stream.value)
-        ev.add(ptrs[0], ptrs[1], ptrs[3], [heads[k][:2] for k in part], [annotations[k] for k in part], stream)
+        for e in evs:
+            e.add(ptrs[0], ptrs[1], ptrs[3], [heads[k][:2] for k in part], [annotations[k] for k in part], stream)
         pending = part
         check_status()                                       # (the decoder keeps the status of its last batch only)
     _lib.check(_lib.lib().vbt_stream_synchronize(stream))    # the decoder and the buffers go away with this frame
     return out
 
 
-def detections_table(model, images, annotations, rgb=False, device=0, batch=BATCH, jpeg_decode="auto", sorted_images=None):
-    """One model over `images` = [(filename, path)]: every image through the pipeline's detector-only step, the detections handed to
-    the matcher on the device.  `.jpg` files the GPU decoder accepts (jpeg_decode "auto" or "gpu") are decoded on the device straight to
-    the network input, in the given order whatever their sizes (_stills_table).  Everything else - .npy, .png, a .jpg the decoder
-    refuses, or every .jpg with jpeg_decode="host" - is grouped by size (read from the file headers), decoded on the host one batch at a
-    time and resized on the device; at most 8 batches of host frames are alive at once.  jpeg_decode="gpu": a refused .jpg raises
-    JpegRefused, naming the file and the reason.  sorted_images: SortedImages(images, jpeg_decode) made by the caller, so that several
-    models share one reading of the files.
-    Returns (table, image_names): table as Evaluator.table(), its `image` column indexing image_names (the order the images were
-    processed in, not the order given)."""
+def _run_model(model, images, annotations, make_evaluators, finish, rgb=False, device=0, batch=BATCH, jpeg_decode="auto", sorted_images=None):
+    """The image path of detections_table for any evaluators: make_evaluators(rows_cap) -> the objects whose add() gets every batch,
+    finish(evaluators, groups) -> the result, called while the stream and the device outputs are alive; groups = [(names, [boxes, scores,
+    classes, counts] DeviceBuffers)] in processing order.  Returns (finish's result, image names in processing order)."""
     from .track import Pipeline
     L = _lib.lib()
     paths = dict(images)
@@ -324,17 +386,17 @@ def detections_table(model, images, annotations, rgb=False, device=0, batch=BATC
     pipe = Pipeline(model, batch, max_frames=1, detection_treshold=0.0, device=device)
     stream = ctypes.c_void_p()
     _lib.check(L.vbt_stream_create(int(device), ctypes.byref(stream)))
-    ev = Evaluator(max(1, len(images)) * MAX_DETECTIONS, batch, device)
-    order, outs, alive = [], [], []                          # outs: device outputs, alive: host frames of steps in flight
+    evs = make_evaluators(max(1, len(images)) * MAX_DETECTIONS)
+    order, outs, alive = [], [], []                          # outs: (names, device outputs), alive: host frames of steps in flight
     try:
         if srt.stills:
-            outs.append(_stills_table(pipe, ev, stream, srt, paths, annotations, rgb, device, batch))
+            outs.append((list(srt.stills), _stills_table(pipe, evs, stream, srt, paths, annotations, rgb, device, batch)))
             order += srt.stills
         for (H, W), names in groups.items():
             n = len(names)
             out = [DeviceBuffer(n * MAX_DETECTIONS * 4 * 4, device), DeviceBuffer(n * MAX_DETECTIONS * 4, device),
                    DeviceBuffer(n * MAX_DETECTIONS * 4, device), DeviceBuffer(n * 4, device)]
-            outs.append(out)
+            outs.append((list(names), out))
             for i0 in range(0, n, batch):
                 part = names[i0:i0 + batch]                     # the last batch of a size group may be partial
                 B = len(part)
@@ -349,16 +411,88 @@ def detections_table(model, images, annotations, rgb=False, device=0, batch=BATC
                         out[3].ptr + i0 * 4)
                 pipe.detect_into(frames, *ptrs, src_hw=(H, W), swap_rb=rgb)
                 pipe.join_detectors(stream.value)
-                ev.add(ptrs[0], ptrs[1], ptrs[3], [(H, W)] * B, [annotations[k] for k in part], stream)
+                for e in evs:
+                    e.add(ptrs[0], ptrs[1], ptrs[3], [(H, W)] * B, [annotations[k] for k in part], stream)
                 order += part
                 if len(alive) >= 8:                             # bound the host memory held for steps in flight
                     _lib.check(L.vbt_stream_synchronize(stream))
                     alive.clear()
-        table = ev.table()                                      # synchronises `stream`
+        result = finish(evs, outs)                              # synchronises `stream`
     finally:
         L.vbt_stream_synchronize(stream)
         L.vbt_stream_destroy(stream)
-    return table, order
+    return result, order
+
+
+def detections_table(model, images, annotations, rgb=False, device=0, batch=BATCH, jpeg_decode="auto", sorted_images=None):
+    """One model over `images` = [(filename, path)]: every image through the pipeline's detector-only step, the detections handed to
+    the matcher on the device.  `.jpg` files the GPU decoder accepts (jpeg_decode "auto" or "gpu") are decoded on the device straight to
+    the network input, in the given order whatever their sizes (_stills_table).  Everything else - .npy, .png, a .jpg the decoder
+    refuses, or every .jpg with jpeg_decode="host" - is grouped by size (read from the file headers), decoded on the host one batch at a
+    time and resized on the device; at most 8 batches of host frames are alive at once.  jpeg_decode="gpu": a refused .jpg raises
+    JpegRefused, naming the file and the reason.  sorted_images: SortedImages(images, jpeg_decode) made by the caller, so that several
+    models share one reading of the files.
+    Returns (table, image_names): table as Evaluator.table(), its `image` column indexing image_names (the order the images were
+    processed in, not the order given)."""
+    return _run_model(model, images, annotations, lambda rows: [Evaluator(rows, batch, device)], lambda evs, _: evs[0].table(), rgb=rgb,
+                      device=device, batch=batch, jpeg_decode=jpeg_decode, sorted_images=sorted_images)
+
+
+def coco_evaluate(model, images, annotations, rgb=False, device=0, batch=BATCH, jpeg_decode="auto", sorted_images=None):
+    """One model over `images` = [(filename, path)] through the image path of detections_table (`.jpg` files are decoded on the GPU), the
+    detections handed to the COCO matcher on the device.  Returns (CocoResult, image names in processing order, detections), detections
+    = {name: (boxes f32 [n,4] normalised ymin,xmin,ymax,xmax, scores f32 [n])} read back for a dump."""
+    def finish(evs, outs):
+        res, det = evs[0].accumulate(), {}                      # synchronises the stream
+        for names, (boxes, scores, _, counts) in outs:
+            n = len(names)
+            bx, sc, ct = boxes.to_host((n, MAX_DETECTIONS, 4), np.float32), scores.to_host((n, MAX_DETECTIONS), np.float32), counts.to_host((n,), np.int32)
+            for i, k in enumerate(names):
+                c = int(min(max(ct[i], 0), MAX_DETECTIONS))
+                det[k] = (bx[i, :c].copy(), sc[i, :c].copy())
+        return res, det
+    (res, det), order = _run_model(model, images, annotations, lambda rows: [CocoEvaluator(rows, batch, device)], finish, rgb=rgb, device=device,
+                                   batch=batch, jpeg_decode=jpeg_decode, sorted_images=sorted_images)
+    return res, order, det
+
+
+def coco_metrics(model, images, annotations, rgb=False, device=0, batch=BATCH, jpeg_decode="auto"):
+    """The dict model.evaluate prints at the end of the reference's training logs (train.py:64,70): the twelve COCO detection metrics
+    (COCOeval: IoU 0.50:0.05:0.95, four area ranges in source-image pixels, maxDets 1 / 10 / 100, 101-point interpolated precision) and
+    'AP_/barbell', which with one class equals 'AP'.  Computed on the GPU (vbt_coco_*, include/vbt_hip.h)."""
+    return coco_evaluate(model, images, annotations, rgb=rgb, device=device, batch=batch, jpeg_decode=jpeg_decode)[0].metrics()
+
+
+def coco_dump(dump_dir, annotations, sizes, per_model):
+    """What pycocotools needs to cross-check the numbers on a machine that has it: DIR/instances.json (images, annotations with bbox
+    xywh, area, iscrowd 0 and ids from 1, one category) and DIR/{model}_detections.json per model (COCO results format) - the boxes of
+    the contract in include/vbt_hip.h, doubles written with repr.  sizes = {name: (height, width)}, per_model = {model name: detections
+    of coco_evaluate}."""
+    import json
+    os.makedirs(dump_dir, exist_ok=True)
+    ids = {name: i + 1 for i, name in enumerate(annotations)}
+    anns = []
+    for name, gt in annotations.items():
+        for ymin, xmin, ymax, xmax in np.asarray(gt, np.int64).reshape(-1, 4).tolist():
+            w, h = float(xmax) - float(xmin), float(ymax) - float(ymin)
+            anns.append({"id": len(anns) + 1, "image_id": ids[name], "category_id": 1, "bbox": [float(xmin), float(ymin), w, h], "area": w * h, "iscrowd": 0})
+    with open(os.path.join(dump_dir, "instances.json"), "w") as f:
+        json.dump({"images": [{"id": ids[k], "file_name": k, "height": int(sizes[k][0]), "width": int(sizes[k][1])} for k in annotations],
+                   "annotations": anns, "categories": [{"id": 1, "name": LABEL}]}, f)
+    written = [os.path.join(dump_dir, "instances.json")]
+    for mname, det in per_model.items():
+        rows = []
+        for name in annotations:
+            boxes, scores = det[name]
+            H, W = float(sizes[name][0]), float(sizes[name][1])
+            for b, sc in zip(boxes.astype(np.float64).tolist(), scores.astype(np.float64).tolist()):
+                x, y = b[1] * W, b[0] * H
+                rows.append({"image_id": ids[name], "category_id": 1, "bbox": [x, y, b[3] * W - x, b[2] * H - y], "score": sc})
+        path = os.path.join(dump_dir, f"{mname}_detections.json")
+        with open(path, "w") as f:
+            json.dump(rows, f)                                   # (json writes a float with repr)
+        written.append(path)
+    return written
 
 
 def create_detections_df(models, img_dir, annotations, export_path=None, rgb=False, device=0, jpeg_decode="auto"):
