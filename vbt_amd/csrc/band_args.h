@@ -1,6 +1,7 @@
 // Arguments and workgroup constants of the row-band SeparableConv kernels (band_block.h).  No kernel body lives here.
 #pragma once
 #include "dev_types.h"
+#include "band_geom.h"   // BD_WP_TAIL, BD_WD_CHAIN
 
 namespace vbt {
 
@@ -11,8 +12,6 @@ constexpr int BD_WAVES = VBT_BD_WAVES, BD_THREADS = 64 * BD_WAVES;
 constexpr int BD_LIT = 3;           // lane-iterations of the load stage whose global loads are in flight together (plain input)
 constexpr int BD_LIT_NODE = 1;      // the same for a node's source loads (up to three 16-byte loads per iteration; registers: the head layers share this kernel)
 constexpr int BD_LIT_NODE_WIDE = 3; // maps of more than 64 channels: LDS leaves at most four waves per SIMD, so 128 registers are free to use
-constexpr int BD_WP_TAIL = 1024;   // bias (512 B) | multipliers (512 B) behind the projection weights in LDS
-constexpr int BD_WD_CHAIN = 12 * 1024 + 512;   // chained form: the twelve depthwise operands | bias (256 B) | multipliers (256 B) behind that
 
 struct BandArgs {
   const int8_t* x;   // [B][H][W][C] (plain input; unused when n_src > 0)
@@ -22,6 +21,7 @@ struct BandArgs {
   int NCG, KS;       // 16-channel groups of the depthwise: ceil(C / 16) / projection K-steps of 64: ceil(C / 64)
   unsigned zx4;      // zero point of the depthwise input x4
   const v4i* wd;     // [cg][m][lane] x 16 B: row i = channel 16cg + i, k = 16g + j -> tap 4m + g, diagonal j == i
+  const unsigned* wdc;   // chained form (C == 64, else null): [cg][lane] x 4 B, byte m = the weight of tap min(4m + g, 8) (0 past tap 8) for channel 16cg + (lane & 15)
   const int* bd;     // bias with the input zero point folded (16 NCG)
   const float* md;
   Rq rqd;

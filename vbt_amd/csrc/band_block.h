@@ -23,10 +23,18 @@
 //              stands.  The MFMA pairs byte (g, p) of A with byte (g, p) of B and sums in exact int32, so the order of K is free: the
 //              projection panel is packed in that order (pack_band_pw_chain) and the result is bit-identical.  No D tile, no second
 //              barrier, no ds_write / ds_read of D, one slot / address computation per pixel group instead of eight.
-//              LDS:  T0 | WP [NT][64] x 16 B in the chained K order | bias | mult | WD [4][3][64] x 16 B depthwise operands | bias
-//              int[64] | mult float[64] - every wave needs all twelve depthwise operands, so they are staged once per workgroup.
-//              A 240-pixel head band is 44.8 KB against 51 KB: still three workgroups per CU (six waves per SIMD), the cap is not lifted.
-//              A 64-pixel band is LARGER than on the two-stage form (WD 12.5 KB against a D of 5 KB).
+//              LDS:  T0 | WP [NT][64] x 16 B in the chained K order | bias int[16 NT] | mult float[16 NT] (BD_WP_TAIL) | WD [4][64] x 4 B
+//              compact depthwise operands (pack_band_dw_compact) | bias int[64] | mult float[64] (BD_WD_CHAIN = 1.5 KB; band_geom.h).
+//              Every wave needs all twelve depthwise operands.  Each is 16 bytes per lane with ONE non-zero byte, so LDS holds that byte
+//              only - byte m of the lane's dword of channel group cg - and a pass reads one dword per channel group and rebuilds the
+//              three operands in registers (diag_operand): 64 sixteen-byte pieces staged per workgroup instead of 768.
+//              A 240-pixel head band is 32.8 KB against 51 KB; the head kernels stay at three workgroups per CU (six waves per SIMD, the
+//              register cap).  A 64-pixel band is now smaller than on the two-stage form (1.5 KB against a D of 5 KB).
+//              The projection has two tile loops, chosen once per band: four whole tiles of dwords (every node, the 64 -> 64 head
+//              layers: a compile-time count, tile t + 1's weights / bias / multipliers requested before tile t is requantised) and the
+//              generic one (the 9- / 18- / 36-channel head outputs).  Output addresses are a scalar 64-bit base per band plus a 32-bit
+//              byte offset per unit.  The head kernel copies its problem record into registers before the walk and goes through
+//              global-address-space pointers (bd_gload16, BD_GLOBAL): no scalar load and no flat access behind the barrier.
 // The planner offers both as kernel variants of the step; the default is the chained form where it exists and max_batch > 8
 // (detector.hip: resolve_band).
 #pragma once
@@ -44,6 +52,28 @@ namespace vbt {
 #else
 #define BD_STAMP(k) do { } while (0)
 #endif
+
+// Loads and stores through pointers of the GLOBAL address space.  A pointer that a kernel reads out of a problem record in memory (the
+// head grids: probs[pi]) is a generic one to the compiler: its accesses compile to flat_*, which count on lgkmcnt as well as vmcnt, so
+// every LDS wait behind an output store waits for the store too.  Everything the band kernels read or write through BandArgs is device
+// memory, so the cast is always valid; a pointer from the kernel-argument segment (the one-problem kernels) is global already.
+#define BD_GLOBAL __attribute__((address_space(1)))
+__device__ __forceinline__ v4i bd_gload16(const void* p) { return *(const BD_GLOBAL v4i*)p; }
+// 16 bytes for the load stage: through the global address space in the chained kernels (G), as the generic load the other forms had
+template <bool G>
+__device__ __forceinline__ uint4 bd_load16(const void* p) {
+  if constexpr (G) {
+    const v4i v = bd_gload16(p);
+    return make_uint4((unsigned)v[0], (unsigned)v[1], (unsigned)v[2], (unsigned)v[3]);
+  } else {
+    return *(const uint4*)p;
+  }
+}
+// a 64-bit value that is the same in every lane (derived from the workgroup index), moved into scalar registers
+__device__ __forceinline__ long bd_uniform64(long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (long)(((unsigned long)hi << 32) | lo);
+}
 
 __device__ __forceinline__ unsigned band_source4(const BandArgs& a, int j, long b, int iy, int ix, int cd, bool up2) {
   const int C = a.C;
@@ -135,14 +165,17 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
 
   // ---- stage L: band + border -> T0; projection weights / bias / multipliers -> LDS ----
   const v4i* wpg = CHAIN ? a.wpc : a.wp;
-  for (int i = tid; i < NT * KS * 64; i += nthreads) *(v4i*)(WP + 16 * i) = wpg[i];
-  if constexpr (CHAIN) {   // all twelve depthwise operands and their bias / multipliers: every wave runs every channel group
-    for (int i = tid; i < 12 * 64; i += nthreads) *(v4i*)(WB + BD_WP_TAIL + 16 * i) = a.wd[i];
-    if (tid >= 64 && tid < 80) *(uint4*)(WB + BD_WP_TAIL + 12 * 1024 + 16 * (tid - 64)) = *(const uint4*)((const unsigned char*)a.bd + 16 * (tid - 64));
-    else if (tid >= 96 && tid < 112) *(uint4*)(WB + BD_WP_TAIL + 12 * 1024 + 256 + 16 * (tid - 96)) = *(const uint4*)((const unsigned char*)a.md + 16 * (tid - 96));
+  for (int i = tid; i < NT * KS * 64; i += nthreads) {
+    if constexpr (CHAIN) *(v4i*)(WP + 16 * i) = bd_gload16(wpg + i);
+    else *(v4i*)(WP + 16 * i) = wpg[i];
   }
-  if (tid < 4 * NT) *(uint4*)(WB + 16 * tid) = *(const uint4*)((const unsigned char*)a.bp + 16 * tid);
-  else if (tid >= 32 && tid < 32 + 4 * NT) *(uint4*)(WB + 512 + 16 * (tid - 32)) = *(const uint4*)((const unsigned char*)a.mp + 16 * (tid - 32));
+  if constexpr (CHAIN) {   // the depthwise operands of all four channel groups (compact: 1 KB) and their bias / multipliers: every wave runs every group
+    if (tid < 64) *(v4i*)(WB + BD_WP_TAIL + 16 * tid) = bd_gload16((const unsigned char*)a.wdc + 16 * tid);
+    else if (tid < 80) *(v4i*)(WB + BD_WP_TAIL + BD_WD_COMPACT + 16 * (tid - 64)) = bd_gload16((const unsigned char*)a.bd + 16 * (tid - 64));
+    else if (tid >= 96 && tid < 112) *(v4i*)(WB + BD_WP_TAIL + BD_WD_COMPACT + 256 + 16 * (tid - 96)) = bd_gload16((const unsigned char*)a.md + 16 * (tid - 96));
+  }
+  if (tid < 4 * NT) *(uint4*)(WB + 16 * tid) = bd_load16<CHAIN>((const unsigned char*)a.bp + 16 * tid);
+  else if (tid >= 32 && tid < 32 + 4 * NT) *(uint4*)(WB + 512 + 16 * (tid - 32)) = bd_load16<CHAIN>((const unsigned char*)a.mp + 16 * (tid - 32));
   const float rcp_pw = frcp(PW);
   if (NODES && a.n_src > 0) {
     const bool up2[3] = {a.H == 2 * a.sh[0] && a.W == 2 * a.sw[0], a.H == 2 * a.sh[1] && a.W == 2 * a.sw[1], a.H == 2 * a.sh[2] && a.W == 2 * a.sw[2]};
@@ -230,7 +263,7 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
           const int iy = y0 + hy - 1, ix = hx - 1;
           pofs[k] = i < total ? p * 80 + 16 * sg : -1;
           v[k] = z4;
-          if (i < total && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v[k] = *(const uint4*)(xb + (iy * a.W + ix) * 64 + 16 * sg);
+          if (i < total && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v[k] = bd_load16<CHAIN>(xb + (iy * a.W + ix) * 64 + 16 * sg);
         }
 #pragma unroll
         for (int k = 0; k < BD_LIT; k++)
@@ -287,12 +320,19 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
     // channel groups of a pixel group and keeps the four packed dwords: lane (r, g) then holds channels 16cg + 4g + 0..3 of pixel r in
     // dword cg - a B operand of the projection as it stands, in the K order the chained weight panel (pack_band_pw_chain) is packed
     // for.  No D tile, no second barrier, one slot / address computation per pixel group instead of one per unit. ----
-    const unsigned char* WD = WB + BD_WP_TAIL;        // [cg][m][lane] x 16 B
-    const unsigned char* WDB = WD + 12 * 1024;        // bias int[64] | multipliers float[64]
+    const unsigned char* WD = WB + BD_WP_TAIL;        // [cg][lane] x 4 B: byte m = the lane's byte of operand m (pack_band_dw_compact)
+    const unsigned char* WDB = WD + BD_WD_COMPACT;    // bias int[64] | multipliers float[64]
     __syncthreads();
     BD_STAMP(1);
-    int8_t* ob = a.out + ((b * a.H + y0) * (long)a.W) * a.Cout + 4 * g;   // the band's pixels are contiguous: (y0 + py) * W + px = y0 * W + slot
-    const bool dword_out = (a.Cout & 3) == 0;
+    // what the walk needs of the arguments, in locals: the head kernels hand in a copy of their problem record, and the pass and tile loops
+    // read none of it from memory again
+    const int Cout = a.Cout;
+    const Rq rqd = a.rqd, rqp = a.rqp;
+    // The band's pixels are contiguous: (y0 + py) * W + px = y0 * W + slot.  Its first output byte is the same for every lane: a 64-bit
+    // scalar base formed once, so a unit's address is that base plus a 32-bit byte offset slot * Cout + 4 g (a band's output is a few KB)
+    BD_GLOBAL int8_t* ob = (BD_GLOBAL int8_t*)a.out + bd_uniform64(((b * a.H + y0) * (long)a.W) * Cout);
+    const bool dword_out = (Cout & 3) == 0;
+    const bool fast4 = NT == 4 && dword_out;   // the projection's four-tile dword form, chosen once per band
     auto chain = [&](auto fd_c, auto u_c, int pg0) {
       constexpr int U = decltype(u_c)::value, FULL = decltype(fd_c)::value;
       int slot[U];
@@ -309,8 +349,9 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
 #pragma unroll
         for (int cg = 0; cg < 4; cg++) {
           v4i wdv[3], bv[U][3], acc[U];
+          const unsigned wc = *(const unsigned*)(WD + (cg * 64 + lane) * 4);
 #pragma unroll
-          for (int m = 0; m < 3; m++) wdv[m] = *(const v4i*)(WD + ((cg * 3 + m) * 64 + lane) * 16);
+          for (int m = 0; m < 3; m++) wdv[m] = diag_operand((wc >> (8 * m)) & 0xffu, r);   // the 16 bytes of pack_band_dw's operand (cg, m, lane)
           const int4 bq = *(const int4*)(WDB + 64 * cg + 16 * g);
           const float4 mu = *(const float4*)(WDB + 256 + 64 * cg + 16 * g);
 #pragma unroll
@@ -324,12 +365,44 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
 #pragma unroll
             for (int u = 0; u < U; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wdv[m], bv[u][m], acc[u], 0, 0, 0);
 #pragma unroll
-          for (int u = 0; u < U; u++) dv[u][cg] = (int)rq_pack_b<FULL>(acc[u], mu, a.rqd);
+          for (int u = 0; u < U; u++) dv[u][cg] = (int)rq_pack_b<FULL>(acc[u], mu, rqd);
           __builtin_amdgcn_sched_barrier(0);   // one channel group's operands at a time: hoisted together, those of all four cost 100 registers more
         }
       }
-      rq_dispatch(a.rqp, [&](auto fp_c) {
+      rq_dispatch(rqp, [&](auto fp_c) {
         constexpr int FULL = decltype(fp_c)::value;
+        unsigned oo[U];   // byte offset of the unit's first dword behind ob, on the clamped slot (the stores are predicated, nothing else is)
+#pragma unroll
+        for (int u = 0; u < U; u++) oo[u] = (unsigned)(min(slot[u], NPo - 1) * Cout + 4 * g);
+        if (fast4) {
+          // four output tiles of dwords (every node, the 64 -> 64 head layers): the tile count is a constant, tile t + 1's weights / bias /
+          // multipliers are requested before tile t is requantised (one tile ahead, no more: all four held at once spilled), and 16 t is
+          // the store's immediate
+          v4i wv = *(const v4i*)(WP + lane * 16);
+          int4 bb = *(const int4*)(WB + 16 * g);
+          float4 mm = *(const float4*)(WB + 512 + 16 * g);
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            v4i wn = wv;
+            int4 bn = bb;
+            float4 mn = mm;
+            if (t < 3) {
+              wn = *(const v4i*)(WP + ((t + 1) * 64 + lane) * 16);
+              bn = *(const int4*)(WB + 64 * (t + 1) + 16 * g);
+              mn = *(const float4*)(WB + 512 + 64 * (t + 1) + 16 * g);
+            }
+            v4i acc[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, dv[u], v4i_from(int4_plus(bb, FULL >= 2 ? RQ_KBIAS : 0)), 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+              const unsigned d = rq_pack_b<FULL>(acc[u], mm, rqp);
+              if (slot[u] < NPo && (t < 3 || 48 + 4 * g < Cout)) *(BD_GLOBAL unsigned*)(ob + oo[u] + 16 * t) = d;   // (NT == 4: Cout > 48, tiles 0..2 are whole)
+            }
+            wv = wn; bb = bn; mm = mn;
+          }
+          return;
+        }
         for (int t = 0; t < NT; t++) {
           const int c0 = 16 * t + 4 * g;
           const v4i wv = *(const v4i*)(WP + (t * 64 + lane) * 16);
@@ -340,13 +413,13 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
           for (int u = 0; u < U; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wv, dv[u], v4i_from(int4_plus(bb, FULL >= 2 ? RQ_KBIAS : 0)), 0, 0, 0);
 #pragma unroll
           for (int u = 0; u < U; u++) {
-            const unsigned d = rq_pack_b<FULL>(acc[u], mm, a.rqp);
-            if (slot[u] < NPo && c0 < a.Cout) {
-              int8_t* o = ob + (long)slot[u] * a.Cout + 16 * t;
-              if (dword_out) *(unsigned*)o = d;
+            const unsigned d = rq_pack_b<FULL>(acc[u], mm, rqp);
+            if (slot[u] < NPo && c0 < Cout) {
+              BD_GLOBAL int8_t* o = ob + oo[u] + 16 * t;
+              if (dword_out) *(BD_GLOBAL unsigned*)o = d;
               else
                 for (int j = 0; j < 4; j++)
-                  if (c0 + j < a.Cout) o[j] = (int8_t)(d >> (8 * j));
+                  if (c0 + j < Cout) o[j] = (int8_t)(d >> (8 * j));
             }
           }
         }
@@ -354,7 +427,7 @@ __device__ __forceinline__ void sepconv_band_body(const BandArgs& a, int local, 
     };
     // the depthwise's requantisation flavour is picked once per band (inside a pass the operand loads every flavour shares were hoisted above
     // the choice and spilled), the projection's once per pass
-    rq_dispatch(a.rqd, [&](auto fd_c) {
+    rq_dispatch(rqd, [&](auto fd_c) {
       int pg = wave;
       for (; pg + nwaves < NPG; pg += 2 * nwaves) chain(fd_c, std::integral_constant<int, 2>{}, pg);
       if (pg < NPG) chain(fd_c, std::integral_constant<int, 1>{}, pg);
@@ -529,7 +602,8 @@ __global__ __launch_bounds__(64 * BD_HEAD_WAVES_WIDE, 2) void sepconv_band_c112_
 __global__ __launch_bounds__(64 * BD_HEAD_WAVES) __attribute__((amdgpu_waves_per_eu(6))) void sepconv_band_chain_kernel(const BandArgs* __restrict__ probs, MultiTiles mt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem_dyn[];
   const int pi = band_problem(mt);
-  sepconv_band_body<BD_HEAD_WAVES, 64, false, true>(probs[pi], (int)blockIdx.x - mt.start[pi], bd_smem_dyn);
+  const BandArgs a = probs[pi];   // the record in registers, read once: through the reference the tile loop re-read Cout from memory per store
+  sepconv_band_body<BD_HEAD_WAVES, 64, false, true>(a, (int)blockIdx.x - mt.start[pi], bd_smem_dyn);
 }
 // One problem (a BiFPN node): the arguments travel in the kernel-argument segment, one dependent memory round trip
 // less at the head of a kernel that is a chain of round trips.

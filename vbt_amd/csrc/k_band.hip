@@ -19,7 +19,7 @@ static int band_attrs() {
 int launch_band_one(const BandArgs& a, bool chained, unsigned grid, int lds_bytes, hipStream_t st) {
   if (band_attrs()) return VBT_ERR_HIP;
   static const bool generic = getenv("VBT_BAND_GENERIC") != nullptr;   // (A/B knob: the any-width kernel on 112-channel maps)
-  if (chained && (a.C != 64 || !a.wpc)) { set_error("fused_sepconv_band: the chained form needs a 64-channel map"); return VBT_ERR_ARG; }
+  if (chained && (a.C != 64 || !a.wpc || !a.wdc)) { set_error("fused_sepconv_band: the chained form needs a 64-channel map"); return VBT_ERR_ARG; }
   if (chained) sepconv_band_one_chain_kernel<<<dim3(grid), BD_THREADS, lds_bytes, st>>>(a);
   else if (a.C == 64) sepconv_band_one_kernel<<<dim3(grid), BD_THREADS, lds_bytes, st>>>(a);
   else if (a.C == 112 && a.CS == 112 && !generic) sepconv_band_one_c112_kernel<<<dim3(grid), BD_THREADS, lds_bytes, st>>>(a);

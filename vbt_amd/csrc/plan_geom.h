@@ -36,11 +36,10 @@ inline int fused_tile_lds(const FusedArgs& a, int k, int stride, int TX, int TY,
 }
 
 // LDS bytes of one row band (band_block.h).
-// chained: the form without the depthwise tile D, with the depthwise operands staged behind the projection panel instead (band_block.h)
+// chained: the form without the depthwise tile D, with the compact depthwise operands staged behind the projection panel instead
+// (band_block.h; the arithmetic is band_geom.h's)
 inline int band_lds(const BandArgs& a, bool chained = false) {
-  const int NT = (a.Cout + 15) / 16;
-  const int t0 = (a.rows + 2) * (a.W + 2) * a.CS, wp = NT * a.KS * 1024 + BD_WP_TAIL;
-  return chained ? t0 + wp + BD_WD_CHAIN : t0 + (((a.rows * a.W + 15) >> 4) << 4) * a.CS + wp;
+  return band_lds_bytes(a.rows, a.W, a.CS, a.Cout, a.KS, chained);
 }
 
 }  // namespace vbt

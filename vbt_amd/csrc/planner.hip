@@ -352,8 +352,11 @@ static int make_band(vbt_model* m, int d_op, int p_op, int sum_op, const NodeSrc
       (rc = upload(m, pad_floats((const float*)(m->blob.data() + dop.m_off), C, a.NCG * 16), &dmd)))
     return rc;
   // the chained form's panel beside the natural-order one: both forms stay launchable (detector.hip: resolve_band)
-  if (C == 64 && to.c <= 64 && (rc = upload(m, pack_band_pw_chain((const int8_t*)(m->blob.data() + pop.w_off), to.c, C), &dpc))) return rc;
-  a.wd = dpd; a.wp = dpp; a.wpc = dpc; a.bd = dbd; a.md = dmd;
+  unsigned* dpdc = nullptr;
+  if (C == 64 && to.c <= 64 && ((rc = upload(m, pack_band_pw_chain((const int8_t*)(m->blob.data() + pop.w_off), to.c, C), &dpc)) ||
+                                (rc = upload(m, pack_band_dw_compact(wd, C), &dpdc))))
+    return rc;
+  a.wd = dpd; a.wdc = dpdc; a.wp = dpp; a.wpc = dpc; a.bd = dbd; a.md = dmd;
   a.bp = m->op_steps[p_op].bias;   // folded with the depthwise output's zero point, padded to 64
   a.mp = m->op_steps[p_op].mult;
   a.rqd = make_rq(td.zero_point, dop.act_min, dop.act_max, conv_kb(m, dop));

@@ -193,6 +193,23 @@ inline std::vector<v4i> pack_band_dw(const int8_t* w, int C) {
       }
   return out;
 }
+// Row-band kernel, chained form (C <= 64), the same operands in compact form: [cg][lane] x 4 B over four channel groups.  Byte m (m = 0..2) of
+// lane (i, g) is the one non-zero byte of pack_band_dw's operand (cg, m, lane): the weight of tap 4m + g for channel 16cg + i, zero where
+// 4m + g > 8 or the channel is past C.  The kernel rebuilds the 16-byte operand in registers (dev_common.h: diag_operand).
+inline std::vector<unsigned> pack_band_dw_compact(const int8_t* w, int C) {
+  std::vector<unsigned> out((size_t)4 * 64, 0u);
+  for (int cg = 0; cg < 4; cg++)
+    for (int lane = 0; lane < 64; lane++) {
+      const int i = lane & 15, g = lane >> 4, ch = 16 * cg + i;
+      unsigned v = 0;
+      for (int mi = 0; mi < 3; mi++) {
+        const int tap = 4 * mi + g;
+        if (tap < 9 && ch < C) v |= (unsigned)(uint8_t)w[(size_t)tap * C + ch] << (8 * mi);
+      }
+      out[(size_t)cg * 64 + lane] = v;
+    }
+  return out;
+}
 // Row-band kernel, projection: [t][ks][lane] x 16 B; lane (i, g) holds W[cout = 16t + i][k = 64ks + 16g + j]
 inline std::vector<v4i> pack_band_pw(const int8_t* w, int N, int C) {
   const int NT = (N + 15) / 16, KS = (C + 63) / 64;
