@@ -227,7 +227,8 @@ int vbt_tracker_rows(vbt_tracker* t, int clip, int64_t* id, double* cols7, int c
 /* End of clips: pick each clip's id with the largest cumulative path length (reference
  * track.py:107-115) and run plot.py's preprocessing + VelocityTracker over its rows on device. */
 int vbt_tracker_finish(vbt_tracker* t, double plate_diameter, double diff_threshold, double min_distance, void* stream);
-/* phases6 [P,6] = time_start,time_end,y_start,y_end,rom,type (reference Phase.py:16-22) */
+/* phases6 [P,6] = time_start,time_end,y_start,y_end,rom,type (reference Phase.py:16-22).  VBT_ERR_CAPACITY, as vbt_tracker_rows,
+ * for a clip that dropped births (more than 64 live tracks) or rows (rows_cap): its log is not the reference's. */
 int vbt_tracker_phases(vbt_tracker* t, int clip, int32_t* best_id, double* phases6, int cap, int* P);
 /* Clip close of every clip at once (arrays of n_clips entries; phases6 is [n_clips][cap][6], rows beyond n_phases[c] are
  * not written): export ids, DataFrame row counts, phase counts and overflow flags are packed on the device into one

@@ -168,6 +168,15 @@ def _crafted_images():
         dets = np.asarray(dets[:25], np.float32)
         images.append((*_pad(dets, rng.random(len(dets), dtype=np.float32)), h, w, gt.astype(int)))
     big = np.array([[10 * (i // 8), 12 * (i % 8), 10 * (i // 8) + 9, 12 * (i % 8) + 11] for i in range(64)])      # 64 disjoint boxes
+    # the solver at the full wave: more boxes than the 25 predictions, so the square problem is n_gt wide and its last n_gt - 25
+    # columns are padding, all equal
+    spread = np.asarray([big[(5 * i) % 64] + [0, 0, -(i % 3), -(i % 4)] for i in range(25)]) / 100.0       # 25 of the 64 boxes, some cut short
+    spread[7], spread[19] = spread[3], (spread[11] + spread[12]) / 2
+    images.append((*_pad(np.asarray(spread, np.float32), rng.random(25, dtype=np.float32)), 100, 100, big))         # 64 x 64, 39 padding columns
+    twice = [big[3 * (i // 2)] for i in range(24)] + [np.r_[big[1][:2], big[2][2:]]]                      # 12 boxes twice, one span of two
+    images.append((*_pad(np.asarray(twice, np.float32) / 100.0, rng.random(25, dtype=np.float32)), 100, 100, big[:40]))  # 40 x 40, exact ties
+    shifted = np.asarray([big[i] + [1, 1, 0, 0] for i in rng.permutation(25)], np.float32) / 100.0
+    images.append((*_pad(shifted, rng.random(25, dtype=np.float32)), 100, 100, big[:26][::-1].copy()))            # 26 x 26: one above the cap
     some = np.asarray([big[i] / np.array([100, 100, 100, 100]) for i in (5, 17, 17, 40, 63)], np.float32)
     zero = np.zeros((0, 4), int)
     images.append((*_pad(some, rng.random(5, dtype=np.float32)), 100, 100, big))                                    # n_gt = 64 > n_pred
@@ -196,12 +205,28 @@ def test_match_crafted_detections_exercise_the_solver():
         ties += any(np.any((m[i][:, None] == m[i][None, :]) & (m[i][:, None] > 0) & ~np.eye(count, dtype=bool)) for i in range(len(gt)))
     assert multi >= 41 and differs * 4 >= multi, (multi, differs)
     assert ties >= 1
+    # ... and of the images with more boxes than predictions, on the padded square problem the device solves: its size, whether the
+    # assignment differs from every prediction taking its best box, positive exact ties inside a box's row
+    tall, tall_differs, tall_ties = [], 0, 0
+    for boxes, scores, count, h, w, gt in images:
+        if count < 2 or len(gt) <= count:
+            continue
+        m = eval_ref.iou_matrix(gt, eval_ref.scale_boxes(boxes[:count], h, w))
+        sq = np.zeros((len(gt), len(gt)))
+        sq[:, :count] = m
+        rows, cols = linear_sum_assignment(1 - sq)
+        tall.append((len(gt), count))
+        tall_differs += not np.array_equal(np.argsort(cols)[:count], m.argmax(axis=0))
+        tall_ties += any(np.any((m[i][:, None] == m[i][None, :]) & (m[i][:, None] > 0) & ~np.eye(count, dtype=bool)) for i in range(len(gt)))
+    assert {(64, 25), (40, 25), (26, 25)} <= set(tall) and len(tall) >= 5, tall
+    assert tall_differs >= 2 and tall_ties >= 2, (tall_differs, tall_ties)
     ev, got = _device_match(images, max_batch=32)
     want = _restated_table(images)
     _check_table(got, want)
     per_image = np.bincount(got["image"], minlength=len(images))
     n = len(images)
     assert list(per_image[n - 7:]) == [5, 5, 0, 0, 2, 3, 25]
+    assert list(per_image[n - 10:n - 7]) == [25, 25, 25]                    # more boxes than predictions: every prediction gets a row
     assert np.all(got["gt_idx"][got["image"] == n - 6] >= 0) and np.all(got["iou"][got["image"] == n - 6] == 0)     # n_gt = 0: all dummy rows
     # the curves over the handle's device table equal the table-in form
     from vbt_amd import evaluate

@@ -159,6 +159,9 @@ int vbt_tracker_phases(vbt_tracker* t, int clip, int32_t* best_id, double* phase
   if (!t || !best_id || !phases6 || !P || clip < 0 || clip >= t->n_clips) { set_error("bad argument"); return VBT_ERR_ARG; }
   if (!t->finished) { set_error("vbt_tracker_phases before vbt_tracker_finish"); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipDeviceSynchronize());
+  StateHeader st;   // a clip that dropped births or rows has no export id to stand behind: refused as vbt_tracker_rows refuses it
+  if (int rc = fetch_state_header(t, clip, &st)) return rc;
+  if (int rc = check_state_header(t, clip, st, t->rows_cap)) return rc;
   int n = 0;
   VBT_HIP_CHECK(hipMemcpy(&n, t->nph.get() + clip, sizeof(int), hipMemcpyDeviceToHost));
   VBT_HIP_CHECK(hipMemcpy(best_id, t->best.get() + clip, sizeof(int), hipMemcpyDeviceToHost));
