@@ -15,9 +15,10 @@ void set_error(const char*, ...) {}
 using namespace vbt;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
-constexpr int XD2_NW = 8, XD2_THREADS = 64 * XD2_NW;   // the 8-wave shape of the kernel, stride 1
-template <int KK, int KS64, int GPW>
+// stride 1; XD2_NW waves (8 or 16), NPGB: the kernel's position-group bound (XD2S_NPG: the small-map instantiation)
+template <int KK, int KS64, int GPW, int XD2_NW = 8, int NPGB = XD2_NPG>
 static void run2(const char* name, int H, int Cin, int Ce, int cpw, int B, int eys_pad) {
+  constexpr int XD2_THREADS = 64 * XD2_NW;
   ExpDw2Args a{};
   const int W = H, OH = H, OW = H, KT2 = (KK + 1) / 2;
   a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Ce = Ce;
@@ -41,12 +42,12 @@ static void run2(const char* name, int H, int Cin, int Ce, int cpw, int B, int e
   a.rqe = make_rq(-128, -128, 127); a.rqd = make_rq(-128, -128, 127);
   a.zeb = 0x80808080u;
   CK(hipMalloc(&a.prof, (size_t)grid * 32 * 8)); CK(hipMemset(a.prof, 0, (size_t)grid * 32 * 8));
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&expdw2_kernel<KK, 1, KS64, XD2_NW, GPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&expdw2_kernel<KK, 1, KS64, XD2_NW, GPW, NPGB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   float best = 1e9f;
   for (int it = 0; it < 6; it++) {
     CK(hipEventRecord(e0));
-    expdw2_kernel<KK, 1, KS64, XD2_NW, GPW><<<grid, XD2_THREADS, lds>>>(a);
+    expdw2_kernel<KK, 1, KS64, XD2_NW, GPW, NPGB><<<grid, XD2_THREADS, lds>>>(a);
     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms);
   }
@@ -61,7 +62,7 @@ static void run2(const char* name, int H, int Cin, int Ce, int cpw, int B, int e
     full++;
     for (int k = 1; k < ns; k++) avg[k] += (double)(s[k] - s[k - 1]);
   }
-  printf("v2 %s H=%d Cin=%d Ce=%d k%d cpw=%d grid=%d lds=%d KB EYS=%d: %.1f us (event)\n  stage ticks (avg over %d wgs): prologue %.0f |", name, H, Cin, Ce, KK, cpw, grid, lds / 1024, a.EYS, best * 1e3, full, avg[1] / full);
+  printf("v2 %s %d waves%s H=%d Cin=%d Ce=%d k%d cpw=%d grid=%d lds=%d KB EYS=%d: %.1f us (event)\n  stage ticks (avg over %d wgs): prologue %.0f |", name, XD2_NW, NPGB < XD2_NPG ? " small" : "", H, Cin, Ce, KK, cpw, grid, lds / 1024, a.EYS, best * 1e3, full, avg[1] / full);
   for (int c = 0; c < cpw; c++) printf(" E+O %.0f D %.0f |", avg[2 + 2 * c] / full, avg[3 + 2 * c] / full);
   printf(" O %.0f\n", avg[ns - 1] / full);
 }
@@ -70,5 +71,12 @@ int main() {
   run2<3, 2, 7>("b6 ", 20, 80, 480, 2, 64, XD2_PAD);
   run2<5, 2, 7>("b9 ", 20, 112, 672, 3, 64, XD2_PAD);
   run2<5, 3, 2>("b12", 10, 192, 1152, 3, 64, XD2_PAD);
+  // the 10 x 10 blocks at B = 256 with the planner's row pad (48): the 16-wave form as pinned before r16, the small-map form
+  run2<5, 3, 1, 16>("b12", 10, 192, 1152, 6, 256, 48);
+  run2<3, 3, 1, 16>("b15", 10, 192, 1152, 6, 256, 48);
+  run2<5, 3, 2, 8, XD2S_NPG>("b12", 10, 192, 1152, 6, 256, 48);
+  run2<3, 3, 2, 8, XD2S_NPG>("b15", 10, 192, 1152, 6, 256, 48);
+  run2<5, 3, 2, 8, XD2S_NPG>("b12", 10, 192, 1152, 9, 256, 48);
+  run2<3, 3, 2, 8, XD2S_NPG>("b15", 10, 192, 1152, 9, 256, 48);
   return 0;
 }

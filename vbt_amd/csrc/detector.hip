@@ -245,18 +245,21 @@ static int launch_fused_step(const vbt_model* m, const Step& s, FusedArgs a, int
 }
 
 // expand + depthwise on whole images or row bands.  Variant: chunks per workgroup on the first form of the kernel (expdw_block.h),
-// 100 + chunks per workgroup on the second (expdw2_block.h) with 8 waves, 200 + chunks with 16 waves; -1: heuristic default
+// 100 + chunks per workgroup on the second (expdw2_block.h) with 8 waves, 200 + chunks with 16 waves, 300 + chunks on its small-map
+// instantiation (two workgroups per CU; 10 x 10 maps only); -1: heuristic default
 ExpDwLaunch resolve_expdw(const vbt_model*, const Step& s, int variant, int B) {
   // VBT_XD_VARIANT (tests): that variant for every step that supports it, whatever the plan says
   static const int xd_force = getenv("VBT_XD_VARIANT") ? atoi(getenv("VBT_XD_VARIANT")) : -100;
-  if (xd_force != -100 && (xd_force < 100 || (s.xd2_ok && (xd_force < 200 ? s.xd2_gpw > 0 : s.xd2_gpw16 > 0)))) variant = std::min(xd_force, xd_force / 100 * 100 + s.xd.nchunks);
+  if (xd_force != -100 && (xd_force < 100 || (s.xd2_ok && (xd_force < 200 ? s.xd2_gpw > 0 : xd_force < 300 ? s.xd2_gpw16 > 0 : s.xd2_small)))) variant = std::min(xd_force, xd_force / 100 * 100 + s.xd.nchunks);
   ExpDwLaunch L;
   if (s.xd2_ok && (variant >= 100 || variant < 0)) {
-    if (variant >= 200 && s.xd2_gpw16 == 0) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the 16-wave form on a step that does not support it"); return L; }
+    if (variant >= 300 && !s.xd2_small) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the small-map form on a step that does not support it"); return L; }
+    if (variant >= 200 && variant < 300 && s.xd2_gpw16 == 0) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the 16-wave form on a step that does not support it"); return L; }
     if (variant >= 100 && variant < 200 && s.xd2_gpw == 0) { L.refuse(VBT_ERR_ARG, "expand + depthwise: plan asks for the 8-wave form on a step that does not support it"); return L; }
     const ExpDw2Args& a = s.xd2;   // the second form
     L.second = true;
-    L.nw = (variant >= 200 || (variant < 0 && s.xd2_gpw16 > 0)) ? 16 : 8;
+    L.small = variant >= 300;
+    L.nw = L.small ? XD2S_WAVES : (variant >= 200 || (variant < 0 && s.xd2_gpw16 > 0)) ? 16 : 8;
     L.gpw = L.nw == 16 ? s.xd2_gpw16 : s.xd2_gpw;
     L.cpw = std::min(variant >= 100 ? variant % 100 : std::max(1, (a.nchunks * a.nbands * B + 1023) / 1024), a.nchunks);   // default: about four workgroups per CU
     L.grid = (unsigned)(B * ((a.nchunks + L.cpw - 1) / L.cpw) * a.nbands);
@@ -277,7 +280,7 @@ static int launch_expdw_step(const vbt_model* m, const Step& s, int B, hipStream
   if (L.second) {
     ExpDw2Args a = s.xd2;
     a.x = x; a.out = out; a.cpw = L.cpw;
-    return launch_expdw2(a, dop.k, dop.stride, (a.Cin + 63) / 64, L.nw, L.gpw, L.grid, L.lds, st);
+    return launch_expdw2(a, dop.k, dop.stride, (a.Cin + 63) / 64, L.nw, L.gpw, L.small, L.grid, L.lds, st);
   }
   ExpDwArgs a = s.xd;
   a.x = x; a.out = out; a.cpw = L.cpw;

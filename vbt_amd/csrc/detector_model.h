@@ -71,6 +71,7 @@ struct Step {
   ExpDw2Args xd2;              // the same step on the second form of the kernel (expdw2_block.h); variant 100 + cpw runs it
   bool xd2_ok = false;
   int xd2_lds = 0, xd2_gpw = 0, xd2_gpw16 = 0;   // input pixel groups per wave on 8 / 16 waves (0: that wave count is not available)
+  bool xd2_small = false;      // the small-map instantiation applies (expdw2_geom.h: expdw2_small_ok); variant 300 + cpw runs it
   // F_MBCONV on a low-resolution map: per-chunk weight records of the whole-image kernel (data == nullptr: not built)
   ImageBundle ib = {nullptr, 0, 0, 0, 0, 0, 0, 0};
 };
@@ -184,8 +185,8 @@ struct FusedPlan : Verdict {
   bool image = false; int PW = 0, PH = 0, NB = 0, maxu = 0;   // whole-image kernel: padded map, output channel blocks, work units per wave
   int TX = 0, TY = 0, tiles_x = 0, tiles_y = 0; FusedLaunch L{};   // (whole image: k, stride and lds_bytes of L)
 };
-struct ExpDwLaunch : Verdict {   // chunks per workgroup; second form: waves per workgroup, input pixel groups per wave
-  bool second = false; int cpw = 1, nw = 0, gpw = 0, lds = 0; unsigned grid = 0;
+struct ExpDwLaunch : Verdict {   // chunks per workgroup; second form: waves per workgroup, input pixel groups per wave, its small-map instantiation
+  bool second = false, small = false; int cpw = 1, nw = 0, gpw = 0, lds = 0; unsigned grid = 0;
 };
 struct BandLaunch : Verdict { bool chained = false; int lds = 0; };
 struct StemLaunch : Verdict { bool direct = false; };

@@ -152,10 +152,11 @@ static std::vector<int> candidate_variants(const vbt_model* m, const Step& st) {
     for (int cpw : {1, 2, 3, 4, 6})
       if (cpw <= st.xd.nchunks) cand.push_back(cpw);
     if (st.xd2_ok)
-      for (int cpw : {1, 2, 3, 4, 6})
+      for (int cpw : {1, 2, 3, 4, 6, 9, 18})   // (18 chunks at 6 / 9 / 18: three, two, one workgroup and prologue per image)
         if (cpw <= st.xd.nchunks) {
           if (st.xd2_gpw > 0) cand.push_back(100 + cpw);
           if (st.xd2_gpw16 > 0) cand.push_back(200 + cpw);
+          if (st.xd2_small) cand.push_back(300 + cpw);
         }
   } else if (st.family == F_BAND) {
     cand = {-1, 0, 1};   // the launch kind's default, two stages, chained (64-channel maps only)

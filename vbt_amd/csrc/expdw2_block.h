@@ -21,8 +21,10 @@
 //     16-byte loads per thread issued a stage ahead, and handed to the waves through LDS.  Per-wave loads of the same data cost 22
 //     vector-memory instructions per wave and chunk - 8 waves x 22 x 16 address cycles = 2800 cycles of the CU's one address path,
 //     the fixed cost the stage stamps showed in every interval.
-//   * LDS: E 39 KB + D 26 KB + parameters 21-25 KB at 20x20 (the first form: 120 KB).  One workgroup per CU either way; the 16-wave shape
-//     (below) puts four waves on every SIMD, so that one wave's LDS / MFMA waits are covered by three others.
+//   * LDS: E 39 KB + D 26 KB + parameters 21-25 KB at 20x20 (the first form: 120 KB).  The general instantiations are alone on their CU -
+//     not for the LDS but for their registers (16 waves x 92-128, 8 waves x 154-256: resource report in profiles/r16_expdw_small_ab.md); the
+//     16-wave shape (below) puts four waves on every SIMD, so that one wave's LDS / MFMA waits are covered by three others.  The small-map
+//     instantiation (10 x 10 maps: 40-50 KB of LDS, 8 waves x 110 registers) is resident twice per CU.
 //   * Stride 2: the operand covers 2 x 2 output pixels x 4 channels (rows 4 py .. 4 py + k + 1 of the expanded image, 8 columns from 4 px:
 //     3 MFMAs per 256 outputs for 3x3, 4 for 5x5 - the diagonal form takes 3 / 7), positions are (output row pair, output column pair).
 // Inputs whose channel count is not a multiple of 8 stay on expdw_block.h.
@@ -40,12 +42,17 @@
 
 namespace vbt {
 
-template <int PG, class F, class FC>
+// position groups PG .. of a band that has NPGo <= NPGB of them, U at a time
+template <int PG, int NPGB, int U, class F, class FC>
 __device__ __forceinline__ void d_pair(F& d_units, FC full_c, int NPGo) {
-  if constexpr (PG < XD2_NPG) {
-    if (PG + 1 < NPGo) d_units(full_c, std::integral_constant<int, 2>{}, std::integral_constant<int, PG>{});
-    else if (PG < NPGo) d_units(full_c, std::integral_constant<int, 1>{}, std::integral_constant<int, PG>{});
-    if (PG + 2 < NPGo) d_pair<PG + 2>(d_units, full_c, NPGo);
+  if constexpr (PG < NPGB) {
+    if constexpr (U == 2) {
+      if (PG + 1 < NPGo) d_units(full_c, std::integral_constant<int, 2>{}, std::integral_constant<int, PG>{});
+      else if (PG < NPGo) d_units(full_c, std::integral_constant<int, 1>{}, std::integral_constant<int, PG>{});
+    } else {
+      if (PG < NPGo) d_units(full_c, std::integral_constant<int, 1>{}, std::integral_constant<int, PG>{});
+    }
+    if (PG + U < NPGo) d_pair<PG + U, NPGB, U>(d_units, full_c, NPGo);
   }
 }
 
@@ -55,8 +62,19 @@ __device__ __forceinline__ void d_pair(F& d_units, FC full_c, int NPGo) {
 // registers, two waves per SIMD.  NW = 16: a tile pair on up to 4 pixel groups, one quad - the compiler has to stay within 128
 // registers, four waves per SIMD: the vector ALU issues a wave-instruction every 2.8 cycles instead of 3.5
 // (tools/probes/valu_rate.hip) and a wave's LDS / MFMA waits are covered by three others instead of one.
-template <int KK, int S, int KS64, int NW, int GPW>
-__global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
+//
+// NPGB: bound of a band's position groups.  XD2_NPG is the general form.  NPGB <= XD2S_NPG is the SMALL-MAP form (expdw2_small_ok,
+// expdw2_geom.h: the 10 x 10 maps of b12-b15), built to be resident TWICE per CU - XD2S_WAVES waves, GPW 2, within 128 registers, four waves
+// per SIMD from two workgroups.  On these maps the 16-wave form waits 43-45 % of its wave cycles (LDS read -> MFMA chain -> requantise ->
+// LDS write -> barrier, twice per chunk) with nobody else on the CU; two resident workgroups of this form deliver chunks 1.4 times as fast,
+// and hold 880 registers per lane of the CU instead of 1 540-1 660 against the other forwards in flight, which is the larger part of what it
+// gains end to end (profiles/r16_expdw_small_ab.md).  It gets there by holding less over the depthwise stage: one position group at a time,
+// bias and multipliers read from the parameter area where they are used, offsets for two position groups instead of eight.  Same arithmetic,
+// same stage order.
+template <int KK, int S, int KS64, int NW, int GPW, int NPGB = XD2_NPG>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NPGB <= XD2S_NPG ? NW / 2 : NW / 4)))
+void expdw2_kernel(ExpDw2Args a) {
+  constexpr bool SMALL = NPGB <= XD2S_NPG;
   constexpr int DY = S, DX = 4 / S;   // output pixels of a depthwise position: 1 x 4 (stride 1), 2 x 2 (stride 2)
   constexpr int XD2_THREADS = 64 * NW, HW2 = NW / 2, QW = 16 / NW;   // threads; waves per tile pair; channel quads per wave in the depthwise
   extern __shared__ __attribute__((aligned(16))) unsigned char xd2_smem[];
@@ -136,12 +154,12 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
   // ---- depthwise stage, per-lane constants: wave owns channel quads 2 wave, 2 wave + 1; lane (r, g) = position r of a group, K slice g ----
   // E byte offset of this lane's operand (kernel rows 0 / 1, column half g & 1, quad cq0) and D byte offset of its output dword for
   // every position group, once per kernel: the stage itself then has no address arithmetic (it was a quarter of its vector instructions)
-  unsigned dofs[XD2_NPG];   // low half: E offset (< 64 KB); high half: D offset (< 64 KB), 0xffff: no such output pixel
+  unsigned dofs[NPGB];   // low half: E offset (< 64 KB); high half: D offset (< 64 KB), 0xffff: no such output pixel
   {
     const int gofs = (g >> 1) * a.EYS + 16 * (g & 1) + cq0 * a.EQS;
     const float rcp_xb = frcp(a.XB);
 #pragma unroll
-    for (int pg = 0; pg < XD2_NPG; pg++) {
+    for (int pg = 0; pg < NPGB; pg++) {
       dofs[pg] = 0xffff0000u;
       if (pg >= NPGo) continue;   // (uniform: a 10x10 map has two position groups, not eight)
       const int n = pg * 16 + r, nc = min(n, NPOS - 1);
@@ -208,14 +226,16 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
       // Interval B: this wave's depthwise parameters out of Pd, depthwise of chunk c, then the next chunk's expand parameters -> Pe
       // (requested in interval A; the expand is done with Pe).
       v4i dwa[QW][KT2];
-      int4 bq[QW];
-      float4 mq[QW];
+      int4 bq[SMALL ? 1 : QW];   // (the small-map form reads bias and multipliers where it uses them: 16 registers less held over the stage)
+      float4 mq[SMALL ? 1 : QW];
 #pragma unroll
       for (int q = 0; q < QW; q++) {
 #pragma unroll
         for (int mi = 0; mi < KT2; mi++) dwa[q][mi] = toeplitz_operand(*(const unsigned*)(Pd + 4 * (((cq0 + q) * KT2 + mi) * 64 + lane)), r & 3);
-        bq[q] = *(const int4*)(Pd + 16 * (KT2 * 256) + 16 * (cq0 + q));
-        mq[q] = *(const float4*)(Pd + 16 * (KT2 * 256 + 16) + 16 * (cq0 + q));
+        if constexpr (!SMALL) {
+          bq[q] = *(const int4*)(Pd + 16 * (KT2 * 256) + 16 * (cq0 + q));
+          mq[q] = *(const float4*)(Pd + 16 * (KT2 * 256 + 16) + 16 * (cq0 + q));
+        }
       }
       auto d_units = [&](auto full_c, auto u_c, auto pg_c) {
         constexpr int U = decltype(u_c)::value, pg0 = decltype(pg_c)::value;
@@ -235,7 +255,10 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
 #pragma unroll
         for (int u = 0; u < U; u++)
 #pragma unroll
-          for (int q = 0; q < QW; q++) acc[u][q] = v4i_from(int4_plus(bq[q], FULL >= 2 ? RQ_KBIAS : 0));
+          for (int q = 0; q < QW; q++) {
+            if constexpr (SMALL) acc[u][q] = v4i_from(int4_plus(*(const int4*)(Pd + 16 * (KT2 * 256) + 16 * (cq0 + q)), FULL >= 2 ? RQ_KBIAS : 0));
+            else acc[u][q] = v4i_from(int4_plus(bq[q], FULL >= 2 ? RQ_KBIAS : 0));
+          }
 #pragma unroll
         for (int mi = 0; mi < KT2; mi++)
 #pragma unroll
@@ -246,7 +269,10 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
         for (int u = 0; u < U; u++) {
           unsigned v[QW];
 #pragma unroll
-          for (int q = 0; q < QW; q++) v[q] = rq_pack_b<FULL>(acc[u][q], mq[q], a.rqd);
+          for (int q = 0; q < QW; q++) {
+            if constexpr (SMALL) v[q] = rq_pack_b<FULL>(acc[u][q], *(const float4*)(Pd + 16 * (KT2 * 256 + 16) + 16 * (cq0 + q)), a.rqd);
+            else v[q] = rq_pack_b<FULL>(acc[u][q], mq[q], a.rqd);
+          }
           if (doff[u] != 0xffff) {
 #pragma unroll
             for (int q = 0; q < QW; q++) *(unsigned*)(D + doff[u] + q * a.PS) = v[q];
@@ -254,7 +280,7 @@ __global__ __launch_bounds__(64 * NW) void expdw2_kernel(ExpDw2Args a) {
         }
       };
       auto d_walk = [&](auto full_c) {   // position groups in pairs (two groups x QW quads: independent MFMA chains), unrolled: register-indexed offsets
-        d_pair<0>(d_units, full_c, NPGo);
+        d_pair<0, NPGB, SMALL ? 1 : 2>(d_units, full_c, NPGo);   // (the small-map form: one group at a time, QW chains)
       };
       rq_dispatch(a.rqd, d_walk);
     }

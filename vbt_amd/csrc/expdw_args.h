@@ -2,6 +2,7 @@
 // lives here.
 #pragma once
 #include "dev_types.h"
+#include "expdw2_geom.h"   // XD2_NPG, XD2S_*
 
 namespace vbt {
 
@@ -66,7 +67,5 @@ struct ExpDw2Args {
   unsigned long long* prof;
 #endif
 };
-
-constexpr int XD2_NPG = 8;   // position groups a band may have (128 positions = 512 output pixels)
 
 }  // namespace vbt

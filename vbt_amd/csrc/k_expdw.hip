@@ -23,14 +23,22 @@ int launch_expdw(const ExpDwArgs& a, int k, int stride, int KS64, unsigned grid_
   return VBT_OK;
 }
 
-template <int KK, int S, int KS64, int NW, int GPW>
+template <int KK, int S, int KS64, int NW, int GPW, int NPGB = XD2_NPG>
 static int launch_expdw2_t(const ExpDw2Args& a, unsigned grid, int lds_bytes, hipStream_t st) {
-  VBT_LDS_OPT_IN(expdw2_kernel<KK, S, KS64, NW, GPW>);
-  expdw2_kernel<KK, S, KS64, NW, GPW><<<dim3(grid), 64 * NW, lds_bytes, st>>>(a);
+  VBT_LDS_OPT_IN(expdw2_kernel<KK, S, KS64, NW, GPW, NPGB>);
+  expdw2_kernel<KK, S, KS64, NW, GPW, NPGB><<<dim3(grid), 64 * NW, lds_bytes, st>>>(a);
   return VBT_OK;
 }
 
-int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int gpw, unsigned grid, int lds_bytes, hipStream_t st) {
+// the small-map instantiation (expdw2_geom.h: expdw2_small_ok): stride 1, XD2S_WAVES waves, XD2S_GPW pixel groups per wave
+static int launch_expdw2_small(const ExpDw2Args& a, int k, int KS64, unsigned grid, int lds_bytes, hipStream_t st) {
+#define XD2S(KK, KS) launch_expdw2_t<KK, 1, KS, XD2S_WAVES, XD2S_GPW, XD2S_NPG>(a, grid, lds_bytes, st)
+  if (k == 3) return KS64 == 2 ? XD2S(3, 2) : KS64 == 3 ? XD2S(3, 3) : XD2S(3, 4);
+  return KS64 == 2 ? XD2S(5, 2) : KS64 == 3 ? XD2S(5, 3) : XD2S(5, 4);
+#undef XD2S
+}
+
+int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int gpw, bool small, unsigned grid, int lds_bytes, hipStream_t st) {
 #define XD2_GPW(KK, KS)                                                                    \
   do {                                                                                     \
     if (stride == 2) {   /* 16 waves only */                                               \
@@ -57,6 +65,10 @@ int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int 
   if ((k != 3 && k != 5) || (stride != 1 && stride != 2) || (stride == 2 && nw != 16) || KS64 < 2 || KS64 > 4 || (nw != 8 && nw != 16) || !gpw_ok) {
     set_error("expdw2: no kernel for k %d, stride %d, %d K steps, %d waves, %d groups per wave", k, stride, KS64, nw, gpw);
     return VBT_ERR_ARG;
+  }
+  if (small) {
+    if (stride != 1 || nw != XD2S_WAVES || gpw != XD2S_GPW) { set_error("expdw2: the small-map form is stride 1, %d waves, %d groups per wave", XD2S_WAVES, XD2S_GPW); return VBT_ERR_ARG; }
+    return launch_expdw2_small(a, k, KS64, grid, lds_bytes, st);
   }
   if (k == 3) XD2_KS(3);
   else XD2_KS(5);

@@ -34,8 +34,8 @@ int launch_band_multi(const BandArgs* d_probs, const MultiTiles& mt, int C, bool
 // whole-image expand + depthwise (expdw_block.h)
 int launch_expdw(const ExpDwArgs& a, int k, int stride, int KS64, unsigned grid, int lds_bytes, hipStream_t st);
 // the same on the second form of the kernel (expdw2_block.h); nw = waves per workgroup (8 or 16; stride 2: 16), gpw = input pixel groups
-// per wave (8 waves: 2, 4 or 7; 16 waves: 1, 2 or 4)
-int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int gpw, unsigned grid, int lds_bytes, hipStream_t st);
+// per wave (8 waves: 2, 4 or 7; 16 waves: 1, 2 or 4); small: the small-map instantiation (expdw2_geom.h: stride 1, 8 waves, gpw 2)
+int launch_expdw2(const ExpDw2Args& a, int k, int stride, int KS64, int nw, int gpw, bool small, unsigned grid, int lds_bytes, hipStream_t st);
 // network entry: stem 3x3/2 + first SeparableConv (stem_block.h)
 // (direct: the second form of the kernel, plan variant 1)
 int launch_stem_block(const StemBlockArgs& a, bool direct, unsigned grid, hipStream_t st);

@@ -9,7 +9,8 @@
 #include <initializer_list>
 
 #include "detector_model.h"
-#include "tpz_geom.h"   // DS_READ_B128_GROUPS (expdw2 geometry)
+#include "expdw2_geom.h"   // expdw2_choose
+#include "tpz_geom.h"
 using vbt::v4i;            // weight_pack.h's functions sit at global scope and take the includer's 16-byte int vector
 #include "weight_pack.h"   // the weight / bias layouts of every kernel family: one pure host function each
 
@@ -678,75 +679,7 @@ static int make_expdw(vbt_model* m, int e_op, int d_op, Step* out) {
 }
 
 // ---- second form of the expand + depthwise kernel (expdw2_block.h): stride 1, Cin % 16 == 0 ----
-// LDS cycles of the depthwise operand reads (ds_read_b128: four groups of 16 lanes, one cycle per group when its 16-byte pieces
-// fall on distinct quarters of the 64 banks; equal addresses broadcast) summed over the positions of a band, for a row stride EYS
-static long xd2_read_cycles(int PR, int XB, int EYS, int RM) {   // PR position rows, RM rows of the expanded image between them
-  const int NPOS = PR * XB;
-  long cycles = 0;
-  for (int pg = 0; pg * 16 < NPOS; pg++)
-    for (int k = 0; k < 4; k++) {
-      std::vector<int> seen[16];
-      int worst = 1;
-      for (int j = 0; j < 16; j++) {
-        const int lane = DS_READ_B128_GROUPS[k][j], r = lane & 15, g = lane >> 4, n = std::min(pg * 16 + r, NPOS - 1);   // (tpz_geom.h)
-        const int addr = (n / XB) * RM * EYS + (n % XB) * 16 + (g >> 1) * EYS + 16 * (g & 1);
-        std::vector<int>& v = seen[(addr >> 4) & 15];
-        if (std::find(v.begin(), v.end(), addr) == v.end()) v.push_back(addr);
-        worst = std::max(worst, (int)v.size());
-      }
-      cycles += worst;
-    }
-  return cycles;
-}
-struct ExpDw2Geom { bool ok; int nbands, brows, XB, EQS, EYS, e_bytes, PS, pe_off, pd_off, lds, gpw, gpw16; };
-static ExpDw2Geom expdw2_geom(int H, int W, int OH, int OW, int k, int stride, int pad_t, int KS64, int nbands) {
-  ExpDw2Geom g{};
-  const int DY = stride, DX = 4 / stride;   // output pixels of a depthwise position: 1 x 4 (stride 1), 2 x 2 (stride 2)
-  g.brows = (OH + nbands - 1) / nbands;
-  if (DY == 2) g.brows = (g.brows + 1) & ~1;   // whole row pairs per band
-  g.nbands = (OH + g.brows - 1) / g.brows;
-  g.XB = (OW + DX - 1) / DX;
-  const int KT2 = (stride * (DY - 1) + k + 1) / 2, PW = (OW - 1) * stride + k;
-  g.EQS = (4 * PW + 15) & ~15;
-  int in_rows = 0;
-  for (int b = 0; b < g.nbands; b++) {
-    const int oy0 = b * g.brows, oy1 = std::min(oy0 + g.brows, OH);
-    const int lo = std::max(oy0 * stride - pad_t, 0), hi = std::min(oy0 * stride - pad_t + (oy1 - oy0 - 1) * stride + k, H);
-    in_rows = std::max(in_rows, hi - lo);
-  }
-  const int PR = (g.brows + DY - 1) / DY;   // position rows of the tallest band
-  long best = -1;
-  for (int pad = 0; pad < 256; pad += 16) {
-    const long cyc = xd2_read_cycles(PR, g.XB, 16 * g.EQS + pad, stride * DY);
-    if (best < 0 || cyc < best) { best = cyc; g.EYS = 16 * g.EQS + pad; }
-  }
-  const int PHe = stride * DY * (PR - 1) + 2 * KT2;   // the last MFMA of a position may read a row past the kernel: zero weights, but the row must exist
-  g.e_bytes = (PHe * g.EYS + 32 + 15) & ~15;
-  int ps4 = g.brows * OW;
-  while ((ps4 & 31) != 2) ps4++;
-  g.PS = 4 * ps4;
-  g.pe_off = g.e_bytes + 16 * g.PS;
-  g.pd_off = g.pe_off + 16 * (KS64 * 256 + 32);
-  g.lds = g.pd_off + 16 * (KT2 * 256 + 32);
-  const int npgi = (in_rows * W + 15) / 16, need = (npgi + 3) / 4;
-  g.gpw = need <= 2 ? 2 : need <= 4 ? 4 : need <= 7 ? 7 : 0;
-  const int need16 = (npgi + 7) / 8;
-  g.gpw16 = need16 <= 1 ? 1 : need16 <= 2 ? 2 : need16 <= 4 ? 4 : 0;
-  if (g.gpw16 * KS64 > 8) g.gpw16 = 0;    // (the input operands a wave keeps: 4 registers each; beyond these the kernels spill)
-  if (g.gpw * KS64 > 21) g.gpw = 0;
-  if (stride == 2) g.gpw = 0;             // stride 2 exists on 16 waves only
-  g.ok = (g.gpw > 0 || g.gpw16 > 0) && g.lds <= 100 * 1024 && PR * g.XB <= 16 * XD2_NPG && g.e_bytes < 65536 && 16 * g.PS < 65535;   // (16-bit LDS offsets in the kernel)
-  return g;
-}
-static ExpDw2Geom expdw2_choose(int H, int W, int OH, int OW, int k, int stride, int pad_t, int KS64) {
-  ExpDw2Geom g{};
-  for (int nb = 1; nb <= OH; nb++) {
-    g = expdw2_geom(H, W, OH, OW, k, stride, pad_t, KS64, nb);
-    if (g.ok) return g;
-  }
-  g.ok = false;
-  return g;
-}
+// (geometry: expdw2_geom.h)
 // fills s->xd2 from the finished first-form arguments s->xd and the host images of its expand weights / biases / multipliers
 static int make_expdw2(vbt_model* m, int e_op, int d_op, Step* s, const std::vector<v4i>& pe, const std::vector<int>& be, const std::vector<float>& me,
                        const std::vector<int>& bd, const std::vector<float>& md) {
@@ -788,6 +721,7 @@ static int make_expdw2(vbt_model* m, int e_op, int d_op, Step* s, const std::vec
   s->xd2_lds = geo.lds;
   s->xd2_gpw = geo.gpw;
   s->xd2_gpw16 = geo.gpw16;
+  s->xd2_small = geo.small;
   return VBT_OK;
 }
 
