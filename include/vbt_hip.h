@@ -119,6 +119,55 @@ int vbt_resize_frames(const uint8_t* src, int B, int H, int W, int src_on_device
 int vbt_resize_frames_yuv(const uint8_t* src, int B, int H, int W, int pix_fmt, int src_on_device, uint8_t* dst, int h, int w,
                           int dst_on_device, int device, void* stream);
 
+/* More source formats, and the colour description of every YUV format.  Codes 3..15 are unknown.
+ *   VBT_PIX_YUYV422 (`yuyv422`, UVC / v4l2 webcams): H rows of 2W bytes, Y0 U Y1 V per pixel pair;
+ *   VBT_PIX_UYVY422 (`uyvy422`, SDI / HDMI capture cards): H rows of 2W bytes, U Y0 V Y1 per pixel pair;
+ *   VBT_PIX_P010 (`p010le`, 10-bit hardware decoders): the NV12 layout in 16-bit little-endian words - H*W luma words, then H/2 rows
+ *     of interleaved U,V words (W words per row).  The sample is word >> 6; the low 6 bits are ignored.
+ * Sizes: the 4:2:2 formats take any H >= 1 and an even W >= 2, P010 even H and W >= 2; no side above 16384.
+ * Chroma, taken nearest: 4:2:2 pixel (y, x) uses the sample of its own pair, (y, x >> 1); P010 uses (y >> 1, x >> 1).
+ * Colour description: a matrix (VBT_CS_*) and a range (VBT_RANGE_*); (VBT_CS_BT601, VBT_RANGE_LIMITED) is the default everywhere.
+ * It applies to all five YUV formats (ffmpeg's yuvj420p is VBT_PIX_I420 with VBT_RANGE_FULL).
+ * Arithmetic contract, all int32, >> arithmetic, clip8 saturating to 0..255:
+ *   Yp = max(0, Y - YOFF);  u = U - COFF;  v = V - COFF
+ *   R = clip8((CY*Yp            + CRV*v + (1<<19)) >> 20)
+ *   G = clip8((CY*Yp - CGU*u    - CGV*v + (1<<19)) >> 20)
+ *   B = clip8((CY*Yp + CBU*u            + (1<<19)) >> 20)
+ * YOFF / COFF: 8-bit limited 16 / 128, 8-bit full 0 / 128, 10-bit limited 64 / 512, 10-bit full 0 / 512.  The 8-bit BT.601 limited
+ * coefficients are those of VBT_PIX_NV12 above (rounded from three decimals), for every 8-bit format.  Every other row is
+ * C = floor(x * 2^20 + 0.5) in double precision with CY = 255/ys, CRV = 2(1-Kr)*255/cs, CGU = 2(1-Kb)Kb/Kg*255/cs,
+ * CGV = 2(1-Kr)Kr/Kg*255/cs, CBU = 2(1-Kb)*255/cs; (Kr, Kb) = (0.299, 0.114) for BT.601, (0.2126, 0.0722) for BT.709, Kg = 1-Kr-Kb;
+ * (ys, cs) = (219, 224) 8-bit limited, (255, 255) 8-bit full, (876, 896) 10-bit limited, (1023, 1023) 10-bit full:
+ *   matrix, depth, range      CY      CRV     CGU     CGV     CBU
+ *   601,  8, limited     1220542  1673527  409993  852492  2116026
+ *   601,  8, full        1048576  1470104  360853  748826  1858077
+ *   601, 10, limited      305236   418389  102698  213115   528805
+ *   601, 10, full         261375   366448   89949  186658   463157
+ *   709,  8, limited     1220945  1879825  223607  558796  2215014
+ *   709,  8, full        1048576  1651297  196424  490864  1945738
+ *   709, 10, limited      305236   469956   55902  139699   553753
+ *   709, 10, full         261375   411614   48962  122356   485008
+ * (the largest intermediate is about 5.8e8).  The uint8 RGB then goes through the arithmetic of vbt_resize_frames, in the same
+ * kernel, as for VBT_PIX_NV12.  Drawing, scaling and JPEG-encoding frames (overlay, scaler, mjpeg handles below) know neither the
+ * new formats nor a colour description: there 16..18 are unknown formats. */
+#define VBT_PIX_YUYV422 16
+#define VBT_PIX_UYVY422 17
+#define VBT_PIX_P010 18
+#define VBT_CS_BT601 0
+#define VBT_CS_BT709 1
+#define VBT_RANGE_LIMITED 0
+#define VBT_RANGE_FULL 1
+/* Bytes of one H x W frame: H*W*3 (RGB24), H*W*3/2 (NV12, I420), H*W*2 (4:2:2), H*W*3 (P010).  0 for an unknown format or a size the
+ * format refuses: H or W < 1, an odd side where the format's chroma needs an even one, a side above 16384 for the 4:2:2 formats and
+ * P010.  RGB24, NV12 and I420 have no upper limit here, as they have none in the pipeline.  Host only. */
+size_t vbt_pix_frame_bytes(int H, int W, int pix_fmt);
+/* vbt_resize_frames for any YUV format under a colour description: src = B frames of vbt_pix_frame_bytes each, dst = uint8
+ * [B,h,w,3] RGB.  VBT_ERR_ARG, before any device call, the text naming the argument: an unknown pix_fmt, matrix or range, a size
+ * the format refuses or, in any format, a side above 16384, VBT_PIX_RGB24 (that is vbt_resize_frames), or a device source of a 4:2:2 or P010 format that is not 4-byte
+ * aligned (the kernel loads a pixel pair as one dword; host sources are staged and may have any alignment). */
+int vbt_resize_frames_pix(const void* src, int B, int H, int W, int pix_fmt, int matrix, int range, int src_on_device,
+                          uint8_t* dst, int h, int w, int dst_on_device, int device, void* stream);
+
 /* ------------------------------------------------------------------ tracker -----------------
  * Replaces ocsort.OCSort (reference track.py:17,157,186-199), the row assembly of
  * reference track.py:189-234 and the export id selection of track.py:107-115.
@@ -361,8 +410,16 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
  * stride of batches, run sources and clips), src_h and src_w must be given, > 0 and even, and swap_rb must be 0 - else VBT_ERR_ARG
  * with nothing enqueued and no state changed.  Conversion and resize run fused on the device (see VBT_PIX_NV12 above); host frames
  * of a source more than twice as tall as the network input upload only the luma row pairs the resize reads plus the chroma
- * plane(s).  VBT_ERR_ARG: an unknown format. */
+ * plane(s).  VBT_ERR_ARG: an unknown format.
+ * VBT_PIX_YUYV422 / VBT_PIX_UYVY422 / VBT_PIX_P010 are accepted too: the frame stride is vbt_pix_frame_bytes(src_h, src_w, format),
+ * the size rules are the format's (4:2:2: any src_h, even src_w; P010: both even; none above 16384), and device frames must be
+ * 4-byte aligned - else VBT_ERR_ARG in the same way.  (NV12 / I420 keep their rule as it was: even sides, no upper limit.)  The compact upload of a 4:2:2 source is that of RGB24 with rows of 2W bytes
+ * (every row carries its own chroma); that of P010 is NV12's with rows of 2W bytes. */
 int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt);
+/* Colour description (VBT_CS_*, VBT_RANGE_*) of the YUV frames of every later step call on this handle, read like the pixel format;
+ * the default is (VBT_CS_BT601, VBT_RANGE_LIMITED).  It is kept but ignored while the format is VBT_PIX_RGB24.  VBT_ERR_ARG, nothing
+ * changed: an unknown matrix or range. */
+int vbt_pipeline_set_colour(vbt_pipeline* p, int matrix, int range);
 /* frames read from the source but not processed (`frame_count % 16`, track.py:161-167): they advance the clip time only */
 int vbt_pipeline_skip_frames(vbt_pipeline* p, int n);
 int vbt_pipeline_set_frame_count(vbt_pipeline* p, int frame_count);

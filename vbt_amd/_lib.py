@@ -158,6 +158,8 @@ _SIGS = {
     "vbt_model_step_fused_params": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_resize_frames_yuv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "vbt_pix_frame_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "vbt_resize_frames_pix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vbt_model_kernel_stats": (c_int, [c_void_p, c_int, ctypes.POINTER(KernelStat), c_int, ctypes.POINTER(c_int)]),
     "vbt_model_profile": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int]),
     "vbt_model_profile_families": (c_int, [c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int]),
@@ -192,6 +194,7 @@ _SIGS = {
     "vbt_pipeline_step_runs": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
     "vbt_pipeline_set_pixel_format": (c_int, [c_void_p, c_int]),
+    "vbt_pipeline_set_colour": (c_int, [c_void_p, c_int, c_int]),
     "vbt_pipeline_skip_frames": (c_int, [c_void_p, c_int]),
     "vbt_pipeline_set_frame_count": (c_int, [c_void_p, c_int]),
     "vbt_pipeline_reset": (c_int, [c_void_p]),

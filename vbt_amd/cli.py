@@ -1,8 +1,8 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
-                            [--live] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|rgb24 --size WxH] [--video_format raw|mjpeg] [--video_quality 85]
-                            [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
+                            [--live] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|yuyv422|uyvy422|p010le|rgb24 --size WxH] [--color_matrix bt601|bt709]
+                            [--color_range limited|full] [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
                             [--display_image_height N]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
       cv2.VideoCapture, track.py:129-160; cv2 is not a dependency here: the frames are decoded on the GPU - include/vbt_hip.h, "MJPEG
@@ -21,6 +21,10 @@
       --pix_fmt nv12|i420 --size 1920x1080: SRC is a headerless raw video file, YUV 4:2:0 as a decoder emits it (what
       `ffmpeg -i clip.mp4 -pix_fmt nv12 -f rawvideo clip.yuv` writes; nothing here runs ffmpeg), mapped read-only; colour conversion and
       resize run fused on the GPU.  --pix_fmt rgb24 --size WxH reads packed raw RGB the same way; without --size SRC is a .npy stack.
+      --pix_fmt yuyv422|uyvy422|p010le --size WxH: packed 4:2:2 as webcams and capture cards deliver it, 10-bit 4:2:0 as hardware
+      decoders do.  --color_matrix bt601|bt709 and --color_range limited|full describe any YUV source (HD material is bt709, ffmpeg's
+      yuvj420p is i420 with full range); not for rgb24 or .avi sources.  These three formats and non-default colour descriptions are
+      tracked, not drawn: --video_dir, --one_pass, --hud, --live_hud and --display_image_height are usage errors with them.
       --video_dir DIR (reference track.py:71,96-98,241-242): every processed frame with the tracked boxes, ids and bar paths drawn on
       the GPU (include/vbt_hip.h, "tracking overlay"), as DIR/{video}.npy for .npy sources and as DIR/{video}.rgb / .yuv - headerless,
       in the source's pixel format, what `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i` reads - for --size sources.  Unlike the reference,
@@ -242,6 +246,23 @@ def _source_fps(frames, fps, given):
     return fps if given or not hasattr(frames, "fps") else float(frames.fps)
 
 
+def _check_colour_options(src, pix_fmt, color_matrix, color_range, exports):
+    """The usage errors of the formats and colour descriptions that are tracked but not drawn, before anything is opened.
+    exports: option name -> was it given, for every option that draws, scales or encodes frames."""
+    from .rawvideo import is_new_format, is_yuv
+    given = [f"{o} {v}" for o, v, d in (("--color_matrix", color_matrix, "bt601"), ("--color_range", color_range, "limited")) if v != d]
+    if given and not is_yuv(pix_fmt):
+        raise click.UsageError(f"{' '.join(given)} describes a YUV source: --pix_fmt {pix_fmt} frames carry no colour description")
+    avi = [s for s in src if _is_avi(s)]
+    if given and avi:
+        raise click.UsageError(f"{' '.join(given)} does not apply to {avi[0]}: a JPEG carries its own colour description")
+    what = ([f"--pix_fmt {pix_fmt}"] if is_new_format(pix_fmt) else []) + given
+    asked = [o for o, on in exports.items() if on]
+    if what and asked:
+        raise click.UsageError(f"{' '.join(what)} is tracked but not drawn: exporting frames ({', '.join(asked)}) takes rgb24, nv12 or i420 "
+                               "sources under bt601 / limited only")
+
+
 def _raw_size(pix_fmt, size):
     """--size as (W, H), or None for .npy sources; the combinations `track` refuses"""
     from .rawvideo import frame_shape, is_yuv, parse_size
@@ -271,8 +292,13 @@ def _raw_size(pix_fmt, size):
                    "commented-out alternative (track.py:156), which made the reference's dfs/ frames.  Every other option works with either.")
 @click.option("--concurrent", default=1, show_default=True, type=int,
               help="Clips tracked side by side in one pipeline (a finished clip's tracker slot takes the next file); 1 = one pipeline per file.")
-@click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420"]),
-              help="Pixel format of the sources; nv12 / i420 (YUV 4:2:0, as a decoder emits it) need --size.")
+@click.option("--pix_fmt", default="rgb24", show_default=True, type=click.Choice(["rgb24", "nv12", "i420", "yuyv422", "uyvy422", "p010le"]),
+              help="Pixel format of the sources; nv12 / i420 (YUV 4:2:0, as a decoder emits it), yuyv422 / uyvy422 (packed 4:2:2, webcams and "
+                   "capture cards) and p010le (10-bit 4:2:0) need --size.  The last three are tracked, not drawn: no --video_dir with them.")
+@click.option("--color_matrix", default="bt601", show_default=True, type=click.Choice(["bt601", "bt709"]),
+              help="Matrix of a YUV source (HD material is bt709); not for rgb24 or .avi sources, not with --video_dir.")
+@click.option("--color_range", default="limited", show_default=True, type=click.Choice(["limited", "full"]),
+              help="Range of a YUV source (ffmpeg's yuvj420p is i420 with full); not for rgb24 or .avi sources, not with --video_dir.")
 @click.option("--size", default=None, type=str, help="WIDTHxHEIGHT of headerless raw video sources, e.g. 1920x1080; without it SRC is a .npy stack.")
 @click.option("--video_dir", default=None, show_default=True,
               help="Directory for exporting the frames with tracked objects and bar path ({video}.npy, or raw {video}.rgb / .yuv with --size).")
@@ -289,11 +315,15 @@ def _raw_size(pix_fmt, size):
                    "(uses --plate_diameter, --hud_scale, --hud_pos; not with --hud or --concurrent above 1).")
 @_display_option
 @_hud_options
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, tracker, concurrent, pix_fmt, size, video_dir, video_format,
-          video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos, display_image_height):
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, tracker, concurrent, pix_fmt, color_matrix, color_range, size,
+          video_dir, video_format, video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos, display_image_height):
     from ._lib import VbtArgError
     from .track import export_dataframe, track_frames
     size = _raw_size(pix_fmt, size)
+    _check_colour_options(src, pix_fmt, color_matrix, color_range,
+                          {"--video_dir": video_dir is not None, "--one_pass": one_pass, "--hud": hud, "--live_hud": live_hud,
+                           "--display_image_height": display_image_height is not None})
+    colour = dict(color_matrix=color_matrix, color_range=color_range)
     _check_display_height(display_image_height, video_dir, pix_fmt)
     fps_given = _fps_given()
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
@@ -321,7 +351,8 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         if live:
             raise click.UsageError("--live works with --concurrent 1 only")
         return _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt, size, video_dir,
-                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter, tracker, display_image_height)
+                                 video_format, video_quality, fps_given, mjpeg_entropy, hud_params, plate_diameter, tracker, display_image_height,
+                                 colour)
     default_fps = fps
     for s in src:
         frames = _open_source(s, pix_fmt, size, mjpeg_entropy)
@@ -329,7 +360,7 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         display_hw = _display_hw(frames, pix_fmt, display_image_height)   # before any output file exists
         if hud_params is not None:                                       # the panel shows the finished analysis: render after tracking
             data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, tracker=tracker)
+                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, tracker=tracker, **colour)
             line, phases = _export_line(data, s, model, df_dir, plate_diameter)
             _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params,
                           display_hw)
@@ -343,7 +374,8 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
             try:
                 data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
                                     live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink,
-                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker, display_hw=display_hw)
+                                    video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker, display_hw=display_hw,
+                                    **colour)
             except VbtArgError as e:                                     # a panel the library refuses (outside the frame, odd origin in a YUV frame)
                 if hud_live is None or "vbt_overlay_hud_follow" not in str(e):
                     raise
@@ -450,7 +482,7 @@ def _render_video(video_dir, video_format, video_quality, s, frames, data, fps, 
 
 def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, concurrent, pix_fmt="rgb24", size=None, video_dir=None,
                       video_format="raw", video_quality=85, fps_given=True, mjpeg_entropy="auto", hud_params=None, plate_diameter=0.45, tracker="ocsort",
-                      display_image_height=None):
+                      display_image_height=None, colour=None):
     """track --concurrent N: the files through ONE pipeline (track.track_many); files, DataFrames and lines as with N = 1.  A clip's
     DataFrame is written as soon as it finishes; its line waits for the clips before it (input order).  The files up to the first one
     that cannot be read are tracked and printed, then that file's error is raised - as N = 1 does."""
@@ -466,7 +498,7 @@ def _track_concurrent(src, model, detection_treshold, df_dir, fps, frame_stride,
     fps = [_source_fps(a, fps, fps_given) for a in sources] or fps
     display_hw = [_display_hw(a, pix_fmt, display_image_height) for a in sources]    # before any output file exists
     for i, data in track_many(sources, model, concurrent, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride,
-                              time_batch=time_batch, pix_fmt=pix_fmt, tracker=tracker):
+                              time_batch=time_batch, pix_fmt=pix_fmt, tracker=tracker, **(colour or {})):
         s = src[i]
         if hud_params is None and video_dir is not None:                 # the clip is finished: its rows are all the renderer needs
             _render_video(video_dir, video_format, video_quality, s, sources[i], data, fps[i], frame_stride, time_batch, pix_fmt, size,

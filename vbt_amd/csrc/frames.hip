@@ -1,7 +1,7 @@
 // Frame plumbing in front of the detector (gfx950): assembling a detector batch from frames that live in different
 // places of device memory (HBM-bound byte moves: 16 bytes per lane, consecutive lanes on consecutive addresses), and the two
-// entries of preprocess_image: the bilinear resize of RGB frames and its YUV 4:2:0 twin (yuv_kernels.h: NV12 / I420 -> RGB fused
-// into the same resize).
+// entries of preprocess_image: the bilinear resize of RGB frames and its YUV twins (yuv_kernels.h: NV12 / I420 -> RGB fused
+// into the same resize; packed 4:2:2, P010 and the BT.709 / full-range descriptions through one template per layout).
 #include <dlfcn.h>
 
 #include "common.h"
@@ -81,6 +81,51 @@ int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_f
   const float sy = (float)H / (float)h, sx = (float)W / (float)w;
   yuv_resize_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(src_dev, dst_dev, total, H, W, h, w, sy, sx, pix_fmt, (long)frame_stride,
                                                                            (long)chroma_off, compact);
+  VBT_HIP_CHECK(hipGetLastError());
+  return VBT_OK;
+}
+
+bool yuv_colour(int pix_fmt, int matrix, int range, YuvColour* c) {
+  if (!pix_fmt_is_source_yuv(pix_fmt) || (matrix != VBT_CS_BT601 && matrix != VBT_CS_BT709) || (range != VBT_RANGE_LIMITED && range != VBT_RANGE_FULL))
+    return false;
+  // [matrix][depth][range] = CY, CRV, CGU, CGV, CBU (include/vbt_hip.h; tests/test_pixfmt_host.py re-derives the rows)
+  static const int tab[2][2][2][5] = {
+      {{{1220542, 1673527, 409993, 852492, 2116026}, {1048576, 1470104, 360853, 748826, 1858077}},
+       {{305236, 418389, 102698, 213115, 528805}, {261375, 366448, 89949, 186658, 463157}}},
+      {{{1220945, 1879825, 223607, 558796, 2215014}, {1048576, 1651297, 196424, 490864, 1945738}},
+       {{305236, 469956, 55902, 139699, 553753}, {261375, 411614, 48962, 122356, 485008}}}};
+  const int deep = pix_fmt == VBT_PIX_P010;
+  const int* t = tab[matrix][deep][range];
+  *c = YuvColour{t[0], t[1], t[2], t[3], t[4], range == VBT_RANGE_FULL ? 0 : (deep ? 64 : 16), deep ? 512 : 128};
+  return true;
+}
+
+int resize_frames_pix_dev(const uint8_t* src_dev, int B, int H, int W, int pix_fmt, int matrix, int range, size_t frame_stride, size_t chroma_off,
+                          int compact, uint8_t* dst_dev, int h, int w, hipStream_t st) {
+  YuvColour cc;
+  if (!yuv_colour(pix_fmt, matrix, range, &cc) || !pix_layout(pix_fmt, H, W).ok || (compact && H < 2)) {
+    set_error("resize: pixel format %d, matrix %d, range %d does not take %d x %d frames", pix_fmt, matrix, range, H, W);
+    return VBT_ERR_ARG;
+  }
+  if (pix_fmt_is_yuv(pix_fmt) && matrix == VBT_CS_BT601 && range == VBT_RANGE_LIMITED)
+    return resize_frames_yuv_dev(src_dev, B, H, W, pix_fmt, frame_stride, chroma_off, compact, dst_dev, h, w, st);
+  if (!pix_fmt_is_yuv(pix_fmt) && (((uintptr_t)src_dev | frame_stride | chroma_off) & 3)) {
+    set_error("resize: a source of pixel format %d must be 4-byte aligned", pix_fmt);
+    return VBT_ERR_ARG;
+  }
+  const long total = (long)B * h * w;
+  const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+  const dim3 grid((unsigned)((total + 255) / 256));
+#define VBT_PIX_LAUNCH(FMT) \
+  pix_resize_kernel<FMT><<<grid, 256, 0, st>>>(src_dev, dst_dev, total, H, W, h, w, sy, sx, cc, (long)frame_stride, (long)chroma_off, compact)
+  switch (pix_fmt) {
+    case VBT_PIX_NV12: VBT_PIX_LAUNCH(VBT_PIX_NV12); break;
+    case VBT_PIX_I420: VBT_PIX_LAUNCH(VBT_PIX_I420); break;
+    case VBT_PIX_YUYV422: VBT_PIX_LAUNCH(VBT_PIX_YUYV422); break;
+    case VBT_PIX_UYVY422: VBT_PIX_LAUNCH(VBT_PIX_UYVY422); break;
+    default: VBT_PIX_LAUNCH(VBT_PIX_P010); break;
+  }
+#undef VBT_PIX_LAUNCH
   VBT_HIP_CHECK(hipGetLastError());
   return VBT_OK;
 }
@@ -183,5 +228,49 @@ extern "C" int vbt_resize_frames_yuv(const uint8_t* src, int B, int H, int W, in
     if (e == hipSuccess) e = es;
   }
   if (e != hipSuccess) { set_error("vbt_resize_frames_yuv failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  return rc;
+}
+
+extern "C" size_t vbt_pix_frame_bytes(int H, int W, int pix_fmt) {
+  return pix_fmt_takes(pix_fmt, H, W) ? pix_layout(pix_fmt, H, W).frame_bytes : 0;
+}
+
+extern "C" int vbt_resize_frames_pix(const void* src, int B, int H, int W, int pix_fmt, int matrix, int range, int src_on_device, uint8_t* dst, int h,
+                                     int w, int dst_on_device, int device, void* stream) {
+  if (!src || !dst || B < 1 || h < 1 || w < 1) { set_error("vbt_resize_frames_pix: bad argument (src, dst, B, h or w)"); return VBT_ERR_ARG; }
+  if (pix_fmt == VBT_PIX_RGB24) { set_error("vbt_resize_frames_pix: pix_fmt VBT_PIX_RGB24 frames go through vbt_resize_frames"); return VBT_ERR_ARG; }
+  if (!pix_fmt_is_source_yuv(pix_fmt)) { set_error("vbt_resize_frames_pix: unknown pix_fmt %d", pix_fmt); return VBT_ERR_ARG; }
+  if (matrix != VBT_CS_BT601 && matrix != VBT_CS_BT709) { set_error("vbt_resize_frames_pix: unknown matrix %d", matrix); return VBT_ERR_ARG; }
+  if (range != VBT_RANGE_LIMITED && range != VBT_RANGE_FULL) { set_error("vbt_resize_frames_pix: unknown range %d", range); return VBT_ERR_ARG; }
+  const PixLayout l = pix_layout(pix_fmt, H, W);
+  if (!l.ok || H > 16384 || W > 16384) {   // (this entry point takes no side above 16384 in any format)
+    set_error("vbt_resize_frames_pix: pix_fmt %d does not take a size of %d x %d (H x W; 4:2:0 and P010: both even, 4:2:2: W even; 1..16384)", pix_fmt, H, W);
+    return VBT_ERR_ARG;
+  }
+  if (src_on_device && !pix_fmt_is_yuv(pix_fmt) && ((uintptr_t)src & 3)) {
+    set_error("vbt_resize_frames_pix: a device src of pix_fmt %d must be 4-byte aligned", pix_fmt);
+    return VBT_ERR_ARG;
+  }
+  if (int rc = use_device("vbt_resize_frames_pix", device)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t fb = l.frame_bytes, sb = (size_t)B * fb, db = (size_t)B * h * w * 3;
+  // every failure below goes through the one clean-up; rc keeps the error a callee already described
+  DevBuf<uint8_t> ds, dd;
+  hipError_t e = hipSuccess;
+  int rc = VBT_OK;
+  if (!src_on_device) {
+    e = ds.alloc(sb);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds.get(), src, sb, hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess && !dst_on_device) e = dd.alloc(db);
+  if (e == hipSuccess)
+    rc = resize_frames_pix_dev(ds ? ds.get() : (const uint8_t*)src, B, H, W, pix_fmt, matrix, range, fb, l.chroma_plane ? (size_t)H * l.row : 0, 0,
+                               dd ? dd.get() : dst, h, w, st);
+  if (e == hipSuccess && rc == VBT_OK && !dst_on_device) e = hipMemcpyAsync(dst, dd.get(), db, hipMemcpyDeviceToHost, st);
+  if (ds || dd) {   // (also after a failure: a copy may still be in flight on the buffers freed when the function returns)
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) { set_error("vbt_resize_frames_pix failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   return rc;
 }

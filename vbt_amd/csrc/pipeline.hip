@@ -18,7 +18,9 @@
 
 // (resize_frames_dev, common.h: preprocess_image reading either whole source frames [B][H][W][3] or, compact != 0, only the row pairs the
 //  bilinear resize touches: [B][2h][W][3], pair d = source rows p(d), p(d) + 1 with p(d) = min(floor(src_y(d)), H - 2);
-//  resize_frames_yuv_dev: the same with the NV12 / I420 conversion fused, vbt_pipeline_set_pixel_format)
+//  resize_frames_pix_dev: the same with the conversion of a YUV format fused - NV12 / I420 / P010 with the chroma plane behind the luma
+//  row pairs, packed 4:2:2 as [B][2h][2W] -, vbt_pipeline_set_pixel_format and vbt_pipeline_set_colour; pix_layout, common.h, is the
+//  one place that knows a format's row and frame bytes)
 
 using namespace vbt;
 
@@ -75,6 +77,7 @@ struct vbt_pipeline {
   int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step (a block never wraps); forwards opened since creation / reset
   int last_o = 0, last_k = 0;      // ring slot / forward slot of the most recent step
   int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
+  int cs_matrix = VBT_CS_BT601, cs_range = VBT_RANGE_LIMITED;   // vbt_pipeline_set_colour
   uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
   // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
   // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
@@ -330,10 +333,10 @@ inline bool compact_rows(const vbt_pipeline* p, int H, int W) {
   return !off && H > 0 && W > 0 && H >= 2 && 2 * p->size < H;
 }
 
-// nf host frames [nf][H][W][3] -> staging buffer (frame slot0 onwards) on the copy stream; compact: only the row pairs
-int h2d_frames(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, int W, bool compact) {
+// nf host frames of H packed rows of `row` bytes (RGB24: 3W, 4:2:2: 2W) -> staging buffer (frame slot0 onwards) on the copy stream;
+// compact: only the row pairs
+int h2d_frames(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, size_t row, bool compact) {
   hipStream_t C = p->copy_stream;
-  const size_t row = (size_t)W * 3;
   if (!compact) {
     const size_t fb = (size_t)H * row;
     VBT_HIP_CHECK(hipMemcpyAsync(stage_buf + (size_t)slot0 * fb, host, (size_t)nf * fb, hipMemcpyHostToDevice, C));
@@ -363,13 +366,13 @@ int h2d_frames(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* ho
   return VBT_OK;
 }
 
-// Compact upload of a YUV 4:2:0 frame (NV12 / I420, H x W, network size h): the luma row pairs 0..h-2, [2 (h - 1)][W], then the
+// Compact upload of a frame with a chroma plane (NV12 / I420: W = row bytes; P010: W = 2 x width; H rows, network size h): the luma row pairs 0..h-2, [2 (h - 1)][W], then the
 // source frame from luma row p(h - 1) to its end as it is - the last pair, the luma rows below it (none or a few) and the whole chroma
 // plane(s).  The tail is one contiguous piece of the source, so the chroma costs no copy call of its own.
 struct YuvCompact {
   size_t tail_src, tail_bytes, chroma_off, frame_bytes;   // tail: offset in the source frame / length; chroma_off, frame_bytes: of the compact frame
 };
-YuvCompact yuv_compact(vbt_pipeline* p, int H, int W) {
+YuvCompact yuv_compact(vbt_pipeline* p, int H, size_t W) {
   const int h = p->size, p_last = row_table(p, H, h)[(size_t)h - 1];
   YuvCompact c;
   c.tail_src = (size_t)p_last * W;
@@ -379,10 +382,10 @@ YuvCompact yuv_compact(vbt_pipeline* p, int H, int W) {
   return c;
 }
 
-// nf host frames of H*W*3/2 bytes -> staging buffer (frame slot0 onwards) on the copy stream; compact: the layout of yuv_compact
-int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, int W, bool compact) {
+// nf host frames of H*row*3/2 bytes -> staging buffer (frame slot0 onwards) on the copy stream; compact: the layout of yuv_compact
+int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, size_t row, bool compact) {
   hipStream_t C = p->copy_stream;
-  const size_t fb = (size_t)H * W * 3 / 2, row = (size_t)W;
+  const size_t fb = (size_t)H * row * 3 / 2;
   if (!compact) {
     VBT_HIP_CHECK(hipMemcpyAsync(stage_buf + (size_t)slot0 * fb, host, (size_t)nf * fb, hipMemcpyHostToDevice, C));
     p->h2d_bytes += (uint64_t)nf * fb;
@@ -390,7 +393,7 @@ int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t
   }
   const int h = p->size;
   const std::vector<int>& tab = row_table(p, H, h);
-  const YuvCompact cl = yuv_compact(p, H, W);
+  const YuvCompact cl = yuv_compact(p, H, row);
   uint8_t* dst = stage_buf + (size_t)slot0 * cl.frame_bytes;
   const int step = h > 1 ? tab[1] - tab[0] : 0;
   bool uniform = h > 2;
@@ -426,14 +429,28 @@ struct Sources {
 };
 
 // What a step may ask for under the pipeline's pixel format; checked before anything is enqueued or counted.
-int check_source_format(const vbt_pipeline* p, const char* fn, int src_h, int src_w, int swap_rb) {
+// frames / run_sources[0..n_sources): the step's sources where they are device pointers (else NULL / 0), for the alignment the 4:2:2
+// and P010 kernels need.
+int check_source_format(const vbt_pipeline* p, const char* fn, int src_h, int src_w, int swap_rb, const uint8_t* frames = nullptr,
+                        const uint8_t* const* run_sources = nullptr, int n_sources = 0) {
   if ((src_h > 0) != (src_w > 0)) { set_error("%s: src_h and src_w come together", fn); return VBT_ERR_ARG; }
-  if (!pix_fmt_is_yuv(p->pix_fmt)) return VBT_OK;
-  if (src_h <= 0 || src_w <= 0 || (src_h & 1) || (src_w & 1)) {
-    set_error("%s: YUV 4:2:0 frames need src_h and src_w, > 0 and even, got %d x %d", fn, src_h, src_w);
+  if (!pix_fmt_is_source_yuv(p->pix_fmt)) return VBT_OK;
+  if (pix_fmt_is_yuv(p->pix_fmt)) {
+    if (src_h <= 0 || src_w <= 0 || (src_h & 1) || (src_w & 1)) {
+      set_error("%s: YUV 4:2:0 frames need src_h and src_w, > 0 and even, got %d x %d", fn, src_h, src_w);
+      return VBT_ERR_ARG;
+    }
+  } else if (!pix_fmt_takes(p->pix_fmt, src_h, src_w)) {
+    set_error("%s: %s frames need src_h and src_w in 1..16384, src_w even%s, got %d x %d", fn, pix_fmt_is_422(p->pix_fmt) ? "YUV 4:2:2" : "P010",
+              pix_fmt_is_422(p->pix_fmt) ? "" : " and src_h even", src_h, src_w);
     return VBT_ERR_ARG;
   }
   if (swap_rb) { set_error("%s: swap_rb does not apply to YUV frames", fn); return VBT_ERR_ARG; }
+  if (!pix_fmt_is_yuv(p->pix_fmt)) {
+    bool aligned = ((uintptr_t)frames & 3) == 0;
+    for (int i = 0; i < n_sources && aligned; i++) aligned = ((uintptr_t)run_sources[i] & 3) == 0;
+    if (!aligned) { set_error("%s: device frames of a 4:2:2 or P010 source must be 4-byte aligned", fn); return VBT_ERR_ARG; }
+  }
   return VBT_OK;
 }
 
@@ -441,14 +458,15 @@ int check_source_format(const vbt_pipeline* p, const char* fn, int src_h, int sr
 int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, const vbt_run* runs, int n_runs, int B, void* caller_stream,
                    const uint8_t** frames_dev, int* stage_j) {
   const int size = p->size;
-  const bool yuv = pix_fmt_is_yuv(p->pix_fmt);   // (a YUV source at the network resolution is still converted)
+  const bool yuv = pix_fmt_is_source_yuv(p->pix_fmt);   // (a YUV source at the network resolution is still converted)
   const bool resize = yuv || (src.src_h > 0 && src.src_w > 0 && (src.src_h != size || src.src_w != size || src.swap_rb));
   const int H = src.src_h > 0 ? src.src_h : size, W = src.src_w > 0 ? src.src_w : size;
-  const size_t fb = yuv ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
-  // bytes of one frame in the staging buffer / upload of nf host frames, per format
-  auto stage_bytes = [&](bool compact_) { return !compact_ ? fb : yuv ? yuv_compact(p, H, W).frame_bytes : (size_t)2 * size * W * 3; };
+  const PixLayout lay = pix_layout(p->pix_fmt, H, W);
+  const size_t row = lay.row, fb = lay.frame_bytes;
+  // bytes of one frame in the staging buffer / upload of nf host frames: packed rows, or a luma plane with the chroma behind it
+  auto stage_bytes = [&](bool compact_) { return !compact_ ? fb : lay.chroma_plane ? yuv_compact(p, H, row).frame_bytes : (size_t)2 * size * row; };
   auto upload = [&](uint8_t* st_, int slot0, const uint8_t* host, int nf, bool compact_) {
-    return yuv ? h2d_frames_yuv(p, st_, slot0, host, nf, H, W, compact_) : h2d_frames(p, st_, slot0, host, nf, H, W, compact_);
+    return lay.chroma_plane ? h2d_frames_yuv(p, st_, slot0, host, nf, H, row, compact_) : h2d_frames(p, st_, slot0, host, nf, H, row, compact_);
   };
   *stage_j = -1;
   const uint8_t* ptr = nullptr;
@@ -503,8 +521,12 @@ int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, co
   if (resize) {
     PL_CHECK(ensure_resized(p, k));
     if (yuv) {
-      const YuvCompact cl = compact ? yuv_compact(p, H, W) : YuvCompact{0, 0, (size_t)H * W, fb};
-      PL_CHECK(resize_frames_yuv_dev(ptr, B, H, W, p->pix_fmt, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0, p->resized[k].get(), size, size, S));
+      // frame stride and chroma offset of what ptr holds: whole frames, the compact frame of yuv_compact, or [2 size] packed 4:2:2 rows
+      YuvCompact cl{0, 0, lay.chroma_plane ? (size_t)H * row : 0, fb};
+      if (compact && lay.chroma_plane) cl = yuv_compact(p, H, row);
+      else if (compact) cl.frame_bytes = (size_t)2 * size * row;
+      PL_CHECK(resize_frames_pix_dev(ptr, B, H, W, p->pix_fmt, p->cs_matrix, p->cs_range, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0,
+                                     p->resized[k].get(), size, size, S));
     } else {
       PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k].get(), size, size, src.swap_rb, compact ? 1 : 0, S));
     }
@@ -812,7 +834,7 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
                       const int32_t* clip_map, const int32_t* frame_idx, int track, void* caller_stream) {
   if (!p || !frames) { set_error("vbt_pipeline_step: NULL argument"); return VBT_ERR_ARG; }
   if ((clip_map != nullptr) != (frame_idx != nullptr)) { set_error("vbt_pipeline_step: clip_map and frame_idx come together"); return VBT_ERR_ARG; }
-  PL_CHECK(check_source_format(p, "vbt_pipeline_step", src_h, src_w, swap_rb));
+  PL_CHECK(check_source_format(p, "vbt_pipeline_step", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
   if (active && p->n_trk != p->n) { set_error("vbt_pipeline_step: `active` needs one clip per slot"); return VBT_ERR_ARG; }
   if (clip_map)
     for (int i = 0; i < p->n; i++)
@@ -835,7 +857,8 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
     set_error("vbt_pipeline_step_runs: out_* come together and are for detector-only steps (track = 0)");
     return VBT_ERR_ARG;
   }
-  PL_CHECK(check_source_format(p, "vbt_pipeline_step_runs", src_h, src_w, swap_rb));
+  PL_CHECK(check_source_format(p, "vbt_pipeline_step_runs", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr,
+                               frames_on_device ? run_sources : nullptr, frames_on_device && run_sources ? n_runs : 0));
   StepTimer timer(p);
   VBT_HIP_CHECK(hipSetDevice(p->device));
   std::vector<vbt_run> ra(runs, runs + n_runs);
@@ -866,8 +889,17 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
 
 int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
-  if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_yuv(pix_fmt)) { set_error("vbt_pipeline_set_pixel_format: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
+  if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_source_yuv(pix_fmt)) { set_error("vbt_pipeline_set_pixel_format: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
   p->pix_fmt = pix_fmt;   // read by the next step call: steps already enqueued carry their own kernels and copies
+  return VBT_OK;
+}
+
+int vbt_pipeline_set_colour(vbt_pipeline* p, int matrix, int range) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (matrix != VBT_CS_BT601 && matrix != VBT_CS_BT709) { set_error("vbt_pipeline_set_colour: unknown matrix %d", matrix); return VBT_ERR_ARG; }
+  if (range != VBT_RANGE_LIMITED && range != VBT_RANGE_FULL) { set_error("vbt_pipeline_set_colour: unknown range %d", range); return VBT_ERR_ARG; }
+  p->cs_matrix = matrix;   // read by the next step call, like the format; not read while the format is VBT_PIX_RGB24
+  p->cs_range = range;
   return VBT_OK;
 }
 
@@ -1182,10 +1214,10 @@ int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device,
                    int64_t* id, double* cols7, int cap, int* n_rows) {
   if (!p || !frames || T < 0 || !id || !cols7 || !n_rows || cap < 0) { set_error("vbt_track_clip: bad argument"); return VBT_ERR_ARG; }
   if (p->n_trk != 1) { set_error("vbt_track_clip: the pipeline must follow exactly one clip (n_clips = 1), it follows %d", p->n_trk); return VBT_ERR_ARG; }
-  PL_CHECK(check_source_format(p, "vbt_track_clip", src_h, src_w, swap_rb));
+  PL_CHECK(check_source_format(p, "vbt_track_clip", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
   const int stride = std::max(frame_stride, 1);
   const int H = src_h > 0 ? src_h : p->size, W = src_w > 0 ? src_w : p->size;
-  const size_t fb = pix_fmt_is_yuv(p->pix_fmt) ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
+  const size_t fb = pix_layout(p->pix_fmt, H, W).frame_bytes;
   PL_CHECK(vbt_pipeline_reset(p));
   // frames whose 1-based number is not a multiple of the stride are read and dropped (track.py:161-167): they only advance the time
   const int kept = T / stride, F = p->n;

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from .interpreter import Interpreter
 from .ocsort import LIVE_PATH_CAP, LIVE_PHASE_CAP, ROW_DTYPE, MultiClipTracker, OCSort, _live_records
-from .rawvideo import frame_shape, is_yuv, pix_fmt_code, source_hw
+from .rawvideo import colour_codes, frame_dtype, frame_shape, is_new_format, is_yuv, pix_fmt_code, source_hw
 from .odt import (calc_bounding_box_center, calc_plate_height, calc_plate_width, results_to_sorttracker_inputs,
                   run_odt)
 
@@ -78,7 +78,8 @@ def track(src, interpreter, detection_treshold=0.5, display_image_height=720, vi
 
 
 def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, live=None, pix_fmt="rgb24",
-                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None, tracker="ocsort", display_hw=None):
+                 src_hw=None, video_out=None, video_sink=None, video_quality=85, one_pass=False, hud_live=None, tracker="ocsort", display_hw=None,
+                 color_matrix="bt601", color_range="limited"):
     """The whole clip loop of reference track.py:129-260 on the time-batched device path: `time_batch` consecutive (kept)
     frames of the clip per detector batch, OC-SORT walking each batch in frame order on the device, nothing but the finished
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
@@ -87,7 +88,10 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     live: optional callable(ocsort.LiveClip, final) - live rep analysis on: called after every batch with the clip's record, and
     once more after the last one with the flush view (final=True: the phases the clip close gives).
     pix_fmt "nv12" / "i420": frames is uint8 [T, H*3//2, W], YUV 4:2:0 as a decoder emits it (rawvideo.py); converted and resized
-    on the GPU.  src_hw=(H, W) is then optional (the shape gives it).
+    on the GPU.  src_hw=(H, W) is then optional (the shape gives it).  "yuyv422" / "uyvy422": uint8 [T, H, 2W], packed 4:2:2;
+    "p010le": little-endian uint16 [T, H*3//2, W].  color_matrix "bt601" / "bt709" and color_range "limited" / "full": the colour
+    description of a YUV source (rawvideo.py); a non-default one with rgb24 frames is a ValueError.  The exports below (video_out,
+    video_sink) do not take the three newer formats or a non-default colour description: ValueError.
     video_out: optional uint8 array [T // frame_stride, ...] with the frames' layout (e.g. a numpy.lib.format.open_memmap) that receives
     every kept frame with the tracked boxes, ids and bar paths drawn (overlay.render; the reference's `--video_dir`, track.py:241-242).
     video_sink: optional mjpeg.AviWriter that receives the same frames encoded as JPEG on the device at video_quality.
@@ -106,10 +110,12 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     of (h, w), video_sink gets h x w JPEGs.  The rows are those of a run without it."""
     if hud_live is not None and not (one_pass and (video_out is not None or video_sink is not None)):
         raise ValueError("track_frames: hud_live draws on a one-pass export (one_pass=True with video_out or video_sink)")
+    colour = _check_colour("track_frames", pix_fmt, color_matrix, color_range, export=video_out is not None or video_sink is not None)
     if one_pass and (video_out is not None or video_sink is not None):
         return _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw,
                              export=(video_out, video_sink, video_quality, display_hw), hud_live=hud_live, tracker=tracker)
-    data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, tracker=tracker)
+    data = _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, tracker=tracker,
+                         color_matrix=colour[0], color_range=colour[1])
     if video_out is not None:
         from .overlay import render
         render(frames, data, fps, frame_stride=frame_stride, pix_fmt=pix_fmt, batch=time_batch, out=video_out, device=device, display_hw=display_hw)
@@ -120,9 +126,25 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     return data
 
 
+def _check_colour(who, pix_fmt, color_matrix, color_range, export=False):
+    """The colour description by name, lower case.  ValueError: an unknown name, a non-default description of rgb24 frames, or an
+    export (drawing, scaling, JPEG encoding) of a format or colour description that only the ingest knows."""
+    colour_codes(color_matrix, color_range)
+    colour = (str(color_matrix).lower(), str(color_range).lower())
+    default = colour == ("bt601", "limited")
+    if not default and not is_yuv(pix_fmt):
+        raise ValueError(f"{who}: color_matrix / color_range describe YUV frames, {pix_fmt} frames carry none")
+    if export and (is_new_format(pix_fmt) or not default):
+        raise ValueError(f"{who}: exported frames are drawn, scaled and encoded as rgb24, nv12 or i420 under (bt601, limited) only, "
+                         f"not {pix_fmt} under ({colour[0]}, {colour[1]})")
+    return colour
+
+
 def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, time_batch, device, live, pix_fmt, src_hw, export=None, hud_live=None,
-                  tracker="ocsort"):
+                  tracker="ocsort", color_matrix="bt601", color_range="limited"):
     """export: None, or (video_out, video_sink, video_quality, display_hw) of a one-pass export; hud_live: None, or the live rep panel's dict"""
+    _check_colour("track_frames", pix_fmt, color_matrix, color_range, export=export is not None)
+    dtype = frame_dtype(pix_fmt)
     T = int(frames.shape[0])
     H, W = source_hw(frames, pix_fmt)
     if src_hw is not None and (int(src_hw[0]), int(src_hw[1])) != (H, W):
@@ -136,10 +158,11 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
                     rows_per_frame=25, tracker_clips=1, tracker=tracker, **plate)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
+    pipe.set_colour(color_matrix, color_range)
     src_hw = None if (H, W) == (size, size) and not is_yuv(pix_fmt) else (H, W)
     if live is not None or hud_live is not None:
         pipe.enable_live()
-    elif export is None and isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags.c_contiguous:
+    elif export is None and isinstance(frames, np.ndarray) and frames.dtype == dtype and frames.flags.c_contiguous:
         return pipe.track_clip(frames, frame_stride=stride, src_hw=src_hw)      # vbt_track_clip: the whole loop inside the library
     # any other sequence (or live analysis, or a one-pass export): chunk by chunk through contiguous host copies
     idx_all = np.arange(stride - 1, T, stride)
@@ -206,7 +229,7 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
                     _lib.check(L.vbt_memcpy(host.ctypes.data, buf.ptr if scaler is None else small.ptr, len(idx) * int(np.prod(out_shape)), 1))
                     video_out[i0:i0 + len(idx)] = host[:len(idx)]
         else:
-            chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=np.uint8)
+            chunk = np.ascontiguousarray(frames[idx[0]:idx[-1] + 1:stride] if stride > 1 else frames[idx[0]:idx[-1] + 1], dtype=dtype)
             pipe.step_runs(chunk, [(0, 0, len(idx), int(idx[0]) + 1, stride)], src_hw=src_hw)
         if live is not None:
             live(pipe.live()[0], False)
@@ -231,14 +254,17 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
 
 
 def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5, frame_stride=1, time_batch=64, device=0, pix_fmt="rgb24",
-               tracker="ocsort"):
+               tracker="ocsort", color_matrix="bt601", color_range="limited"):
     """track_frames() for many clips through ONE pipeline: `concurrent` tracker slots, `time_batch` detector slots per step.  Each
     step hands runs of consecutive frames to the open clips (shard.stream_schedule); a clip whose frames are used up is closed in its
     slot (Pipeline.close_clips) and the next source opens there.  Only clips of one source resolution are open together (the
     resize is set per step).  sources: uint8 [T,H,W,3] arrays (numpy / memmap), or [T,H*3//2,W] with pix_fmt "nv12" / "i420"; fps:
-    one value or one per source; tracker: "ocsort" or "sort", as in track_frames (every clip's ids start at 1).
+    one value or one per source; tracker: "ocsort" or "sort", as in track_frames (every clip's ids start at 1).  The other pixel
+    formats and color_matrix / color_range: as in track_frames, one description for all sources.
     Yields (index, rows) as clips finish - rows = the dict track_frames returns for that source."""
     from .shard import stream_schedule
+    _check_colour("track_many", pix_fmt, color_matrix, color_range)
+    dtype = frame_dtype(pix_fmt)
     sources = list(sources)
     fps_of = np.broadcast_to(np.asarray(fps, np.float64), (len(sources),))
     stride = max(int(frame_stride), 1)
@@ -253,6 +279,7 @@ def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5
                     device=device, rows_per_frame=25, tracker_clips=int(concurrent), slot_close=True, tracker=tracker)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
+    pipe.set_colour(color_matrix, color_range)
     clip_of = {}                                     # tracker slot -> source index of the clip open in it
     unread = {}                                      # tracker slot -> source index of its close not read yet
     for opens, runs, closes in stream_schedule(kept, int(concurrent), pipe.n, groups=hw):
@@ -265,7 +292,7 @@ def track_many(sources, model_path, concurrent, fps=30.0, detection_treshold=0.5
         for slot, _, n, f0 in runs:
             a = sources[clip_of[slot]]
             first = f0 * stride - 1                  # 0-based index of the run's first kept frame
-            chunks.append(np.ascontiguousarray(a[first:first + (n - 1) * stride + 1:stride], dtype=np.uint8))
+            chunks.append(np.ascontiguousarray(a[first:first + (n - 1) * stride + 1:stride], dtype=dtype))
         pipe.step_runs(chunks, [(slot, slot0, n, f0 * stride, stride) for slot, slot0, n, f0 in runs], src_hw=src_hw)
         for slot in list(unread):                    # results the device has finished (never waits)
             got = pipe.closed(slot, wait=False)
@@ -312,20 +339,23 @@ def _torch():
     return sys.modules.get("torch")
 
 
-def _host_or_device_ptr(x):
+def _host_or_device_ptr(x, pix_fmt="rgb24"):
     """(pointer, on_device, keepalive) of a frame source: a torch tensor (device or host / pinned), a numpy array, an object with
-    __cuda_array_interface__, or a raw DEVICE pointer (int) the caller keeps alive."""
+    __cuda_array_interface__, or a raw DEVICE pointer (int) the caller keeps alive.  Elements are bytes - 16-bit words for p010le
+    (numpy uint16; torch uint16 or int16, the same bits)."""
     if isinstance(x, int):
         return x, True, None
+    dtype = frame_dtype(pix_fmt)
     if hasattr(x, "data_ptr"):                                      # torch tensor
-        if x.dtype != _torch().uint8 or not x.is_contiguous():
-            raise ValueError("frames must be a contiguous uint8 tensor")
+        ok = x.dtype == _torch().uint8 if dtype.itemsize == 1 else (x.element_size() == 2 and not x.is_floating_point())
+        if not ok or not x.is_contiguous():
+            raise ValueError(f"frames must be a contiguous {dtype.name} tensor")
         return x.data_ptr(), x.device.type != "cpu", x
     if hasattr(x, "__cuda_array_interface__"):
         return int(x.__cuda_array_interface__["data"][0]), True, x
     a = np.asarray(x)
-    if a.dtype != np.uint8 or not a.flags.c_contiguous:
-        raise ValueError("frames must be a C-contiguous uint8 array")
+    if a.dtype != dtype or not a.flags.c_contiguous:
+        raise ValueError(f"frames must be a C-contiguous {dtype.name} array")
     return a.ctypes.data, False, a
 
 
@@ -415,9 +445,16 @@ class Pipeline:
         """"rgb24" (default), "nv12" or "i420" (vbt_pipeline_set_pixel_format): the format of the frames of every later step(),
         step_runs() and track_clip().  YUV 4:2:0 frames are uint8 [*, H*3//2, W] - the 2-D view of a raw frame, planes as
         include/vbt_hip.h lays them out - need src_hw=(H, W), both even, and take no swap_rb; the BT.601 conversion runs fused with the
-        resize on the device."""
+        resize on the device.  Also "yuyv422" / "uyvy422" (uint8 [*, H, 2W], W even) and "p010le" (uint16 [*, H*3//2, W], H and W
+        even); set_colour() gives the colour description of every YUV format."""
         _lib.check(_lib.lib().vbt_pipeline_set_pixel_format(self._h, pix_fmt_code(pix_fmt)))
         self.pix_fmt = str(pix_fmt).lower()
+
+    def set_colour(self, matrix="bt601", range="limited"):
+        """Colour description of the YUV frames of every later step(), step_runs() and track_clip() (vbt_pipeline_set_colour): matrix
+        "bt601" / "bt709", range "limited" / "full".  Kept, but not read, while the format is "rgb24".  ValueError, nothing changed: a
+        name that is neither."""
+        _lib.check(_lib.lib().vbt_pipeline_set_colour(self._h, *colour_codes(matrix, range)))
 
     def _yuv_hw(self, src_hw, swap_rb):
         """the checks of a YUV step that the library would refuse (check_source_format, pipeline.hip), before a shape is compared"""
@@ -438,13 +475,13 @@ class Pipeline:
     def _source(self, x, k, n_frames=None, hw=None):
         """pointer / residency of one source; a torch device tensor is told to the caching allocator (its storage is used on the slot's
         stream up to `depth` steps after the call returns), anything else that owns memory is kept referenced while steps are in flight"""
-        ptr, on_dev, keep = _host_or_device_ptr(x)
+        ptr, on_dev, keep = _host_or_device_ptr(x, self.pix_fmt)
         if keep is not None:
             shp = tuple(keep.shape)
             if is_yuv(self.pix_fmt):
                 want = frame_shape(self.pix_fmt, *hw)
                 if len(shp) != 3 or shp[1:] != want or (n_frames is not None and shp[0] < n_frames):
-                    raise ValueError(f"{self.pix_fmt} frames must be uint8 [{n_frames if n_frames is not None else 'B'}, {want[0]}, {want[1]}], got {shp}")
+                    raise ValueError(f"{self.pix_fmt} frames must be {frame_dtype(self.pix_fmt).name} [{n_frames if n_frames is not None else 'B'}, {want[0]}, {want[1]}], got {shp}")
             elif len(shp) != 4 or shp[3] != 3 or (hw is not None and shp[1:3] != tuple(hw)) or (n_frames is not None and shp[0] < n_frames):
                 raise ValueError(f"frames must be uint8 [{n_frames if n_frames is not None else 'B'}, {hw[0] if hw else 'H'}, {hw[1] if hw else 'W'}, 3], got {shp}")
             if on_dev and hasattr(keep, "record_stream"):
@@ -601,7 +638,7 @@ class Pipeline:
     def track_clip(self, frames, frame_stride=1, src_hw=None, swap_rb=False):
         """vbt_track_clip: the whole loop of reference track.py:129-260 for ONE clip held in memory (frames uint8 [T,H,W,3] - or
         [T,H*3//2,W] after set_pixel_format("nv12" / "i420") - host or device), `n` consecutive kept frames per detector batch.  Returns the reference's dict of lists (track.py:144-145)."""
-        ptr, on_dev, keep = _host_or_device_ptr(frames)
+        ptr, on_dev, keep = _host_or_device_ptr(frames, self.pix_fmt)
         T = int(frames.shape[0]) if keep is not None else None
         if T is None:
             raise ValueError("track_clip needs an array (its length is the clip's frame count)")
