@@ -329,6 +329,46 @@ int vbt_tracker_live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, 
 int vbt_tracker_live_tracks(vbt_tracker* t, int clip, int flush_view, int64_t* ids, int32_t* n_rows, int32_t* n_phases, int32_t* flags,
                             double* phases6, int cap_tracks, int cap_phases, int* n);
 
+/* Rep metrics (off unless enabled): eight doubles per phase, formed on the device where the phase's bar path is - in the scan, when
+ * the phase is appended to its list - from the very samples and step range its rom is summed over (VelocityTracker.py:171-222), in
+ * IEEE double without contraction, sequentially in index order i = st+1 .. en (st / en: the path samples the phase starts / ends at;
+ * D = plate_diameter; ddx_i, ddy_i: the per-step terms of rom; dt_i = ts[i] - ts[i-1]; v_i = (ddx_i + ddy_i) / dt_i):
+ *   VBT_RM_PV       max v_i (initial value 0.0, a strictly greater value replaces it)          peak velocity, m/s
+ *   VBT_RM_T_PV     ts[i] of the first maximum of PV; ts[st] if no step qualified               its time stamp, s
+ *   VBT_RM_ROM_Y    sum ddy_i                                                                   vertical travel, m
+ *   VBT_RM_ROM_X    sum ddx_i                                                                   horizontal travel, m
+ *   VBT_RM_PV_Y     max ddy_i / dt_i (as PV)                                                    peak vertical velocity, m/s
+ *   VBT_RM_MV       rom / (ts[en] - ts[st]); 0.0 when that duration is <= 0                     the reference's ACV (plot.py:173)
+ *   VBT_RM_X_DEV    max |xs[i] - xs[st]| / ((ws[i] + ws[st]) / 2) * D (initial value 0.0)       largest sideways excursion, m
+ *   VBT_RM_N_STEPS  (double)(en - st) when en > st, else 0.0
+ * A step with dt_i <= 0 adds to the sums but takes no part in the two velocity maxima (a tracker's row log cannot hold one; rows
+ * handed to vbt_analyze_metrics can).  The record travels with its phase: a phase the filter drops later takes its metrics along, so
+ * metrics8 [P][8] is always in the order of phases6 [P][6].  Enabling metrics changes no other output. */
+#define VBT_REP_METRICS 8
+#define VBT_RM_PV 0
+#define VBT_RM_T_PV 1
+#define VBT_RM_ROM_Y 2
+#define VBT_RM_ROM_X 3
+#define VBT_RM_PV_Y 4
+#define VBT_RM_MV 5
+#define VBT_RM_X_DEV 6
+#define VBT_RM_N_STEPS 7
+/* Before the first update (or after vbt_tracker_reset), else VBT_ERR_STATE; before or after vbt_tracker_live_enable; a second call
+ * does nothing.  Allocates n_clips x 512 x 8 doubles (32 KB per clip) for the close and, with live analysis on, n_clips x 65 x
+ * phase_cap x 8 doubles for the live tables + n_clips x phase_cap x 8 for the poll's view (at the default phase_cap of 128: 65 KB x
+ * 66 = 541 KB per clip). */
+int vbt_tracker_rep_metrics_enable(vbt_tracker* t);
+/* After vbt_tracker_finish: metrics8 [P][8] of the clip's export id, in the order of vbt_tracker_phases.  VBT_ERR_STATE when metrics
+ * are not enabled or before the finish; otherwise refused as vbt_tracker_phases refuses. */
+int vbt_tracker_rep_metrics(vbt_tracker* t, int clip, double* metrics8, int cap, int* P);
+/* vbt_tracker_summary with metrics8 [n_clips][cap][8] in the same packed block: still ONE copy and ONE stream synchronisation.
+ * VBT_ERR_STATE when metrics are not enabled. */
+int vbt_tracker_summary_ex(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6,
+                           double* metrics8, int cap);
+/* vbt_tracker_live_poll with the leaders' metrics8 [n_clips][cap][8] (with flush_view: those of the appended phase included), in the
+ * same packed block: ONE copy, ONE synchronisation.  VBT_ERR_STATE when live analysis or metrics are not enabled. */
+int vbt_tracker_live_poll_ex(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap, void* stream);
+
 /* ------------------------------------------------------------------ pipeline ----------------
  * Replaces the clip loop of the reference (track.py:129-260: `while cap.isOpened()` -> cap.read -> run_odt -> OCSort.update ->
  * row assembly, then the export of track.py:103-126 and analyze_df of plot.py:33-47) as ONE object behind the C ABI: SURVEY.md 8b's
@@ -480,6 +520,16 @@ int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap);
 /* Drains the tracker steps still held back (vbt_pipeline_drain), then vbt_tracker_live_poll on the tracker stream: waits for the last
  * tracker launch only, ONE packed copy.  phases6 [n_clips][cap][6] = the leaders' phases. */
 int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap);
+/* Rep metrics of the pipeline's clips (vbt_tracker_rep_metrics_enable): before the first step (or after vbt_pipeline_reset), else
+ * VBT_ERR_STATE; before or after vbt_pipeline_live_enable / vbt_pipeline_close_clips_enable.  With the slot close enabled it adds a
+ * pinned block of 32 KB per tracker clip.  The _ex calls below are their twins with a metrics8 out-array ([..][8] wherever the twin
+ * has phases6 [..][6]) and VBT_ERR_STATE when metrics are not enabled; a slot's metrics are those of the clip just closed in it. */
+int vbt_pipeline_rep_metrics_enable(vbt_pipeline* p);
+int vbt_pipeline_close_ex(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6,
+                          double* metrics8, int cap);
+int vbt_pipeline_closed_clip_ex(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, double* metrics8,
+                                int cap_phases, void* rows_host, int cap_rows);
+int vbt_pipeline_live_poll_ex(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap);
 typedef struct {
   int32_t n_slots, n_clips, rows_cap, device, depth, ring, defer, tracker_inline, image_size, frame_count, steps_enqueued, placement_ok;
   int32_t queue_groups_seen;  /* distinct hardware queues the placement probe has seen on this device */
@@ -522,6 +572,29 @@ int vbt_device_synchronize(int device);
  * flush != 0 runs end_processing(). */
 int vbt_analyze(const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
                 double min_distance, double* phases6, int cap, int* P, int device);
+
+/* vbt_analyze + the rep metrics ("Rep metrics" above) of its phases: metrics8 [P][8]; phases6 is what vbt_analyze returns. */
+int vbt_analyze_metrics(const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
+                        double min_distance, double* phases6, double* metrics8, int cap, int* P, int device);
+
+/* The report of a set: the concentric phases (type 0) of one id in list order are its reps k = 1..n, mv_k / pv_k their VBT_RM_MV /
+ * VBT_RM_PV.  best_k = max over j <= k of mv_j; loss_k = 100 * (1 - mv_k / best_k), 0 when best_k <= 0.  Sums run in list order;
+ * means are over the reps and 0 when there are none. */
+typedef struct {
+  int32_t n_reps;         /* concentric phases */
+  int32_t best_rep;       /* 1-based rep of best_mv (ties: the earlier rep); 0: no rep */
+  int32_t stop_rep;       /* first k with loss_k >= stop_loss_pct; 0: none, or stop_loss_pct <= 0 */
+  int32_t reserved;
+  double best_mv, last_mv, mean_mv;
+  double mean_pv, max_pv;
+  double loss_last_pct;   /* loss_n */
+  double concentric_s, eccentric_s;   /* summed time_end - time_start of the phases of type 0 / type 1 */
+  double mean_x_dev;
+} vbt_set_report;
+/* phases6 [P][6], metrics8 [P][8] as the calls above return them.  loss_pct [cap]: loss_k of the first min(n_reps, cap) reps (the
+ * report covers every rep whatever cap is).  Host only: no device call, usable without a GPU.  VBT_ERR_ARG: a NULL pointer (phases6 /
+ * metrics8 may be NULL when P == 0, loss_pct when cap == 0), P < 0, cap < 0, a stop_loss_pct that is not finite. */
+int vbt_set_summary(const double* phases6, const double* metrics8, int P, double stop_loss_pct, vbt_set_report* out, double* loss_pct, int cap);
 
 /* Trailing / expanding window means of the columns of a row-major float64 table rows[T][ncols] (ncols <= 64),
  * bit-identical to pandas `Series.rolling(window, center=False, min_periods=1).mean()` (windows[c] > 0) and

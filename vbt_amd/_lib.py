@@ -46,6 +46,13 @@ class ClosedClip(ctypes.Structure):
                 ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class SetReport(ctypes.Structure):
+    """vbt_set_report (include/vbt_hip.h)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_reps", "best_rep", "stop_rep", "reserved")] + \
+               [(k, c_double) for k in ("best_mv", "last_mv", "mean_mv", "mean_pv", "max_pv", "loss_last_pct", "concentric_s", "eccentric_s",
+                                        "mean_x_dev")]
+
+
 class PipelineParams(ctypes.Structure):
     """vbt_pipeline_params (include/vbt_hip.h)"""
     _fields_ = [("n_slots", ctypes.c_int32), ("n_clips", ctypes.c_int32), ("rows_cap", ctypes.c_int32), ("device", ctypes.c_int32),
@@ -187,6 +194,10 @@ _SIGS = {
     "vbt_tracker_live_enable": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double]),
     "vbt_tracker_live_poll": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_tracker_live_tracks": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int)]),
+    "vbt_tracker_rep_metrics_enable": (c_int, [c_void_p]),
+    "vbt_tracker_rep_metrics": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_tracker_summary_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_tracker_live_poll_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "vbt_pipeline_default_params": (None, [ctypes.POINTER(PipelineParams)]),
     "vbt_pipeline_create": (c_int, [c_char_p, ctypes.POINTER(PipelineParams), c_void_p, ctypes.POINTER(c_void_p)]),
     "vbt_pipeline_destroy": (None, [c_void_p]),
@@ -211,6 +222,11 @@ _SIGS = {
     "vbt_pipeline_tracker_only_steps": (c_int, [c_void_p, c_int, c_int]),
     "vbt_pipeline_live_enable": (c_int, [c_void_p, c_int, c_int]),
     "vbt_pipeline_live_poll": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "vbt_pipeline_rep_metrics_enable": (c_int, [c_void_p]),
+    "vbt_pipeline_close_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "vbt_pipeline_closed_clip_ex": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ClosedClip), c_void_p, c_void_p, c_int,
+                                            c_void_p, c_int]),
+    "vbt_pipeline_live_poll_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "vbt_pipeline_get_info": (c_int, [c_void_p, ctypes.POINTER(PipelineInfo)]),
     "vbt_pipeline_model": (c_void_p, [c_void_p, c_int]),
     "vbt_pipeline_tracker": (c_void_p, [c_void_p]),
@@ -223,6 +239,9 @@ _SIGS = {
     "vbt_stream_synchronize": (c_int, [c_void_p]),
     "vbt_device_synchronize": (c_int, [c_int]),
     "vbt_analyze": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_int, ctypes.POINTER(c_int), c_int]),
+    "vbt_analyze_metrics": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int),
+                                    c_int]),
+    "vbt_set_summary": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(SetReport), c_void_p, c_int]),
     "vbt_window_means": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     "vbt_eval_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "vbt_eval_destroy": (None, [c_void_p]),

@@ -1,7 +1,7 @@
 """Command line mirror of the reference's entry points, minus GUI/plotting:
 
   python -m vbt_amd.cli track SRC... [--model M] [--detection_treshold 0.5] [--df_dir DIR] [--video_dir DIR] [--fps 30] [--frame_stride 1]
-                            [--live] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|yuyv422|uyvy422|p010le|rgb24 --size WxH] [--color_matrix bt601|bt709]
+                            [--live [--report] [--stop_loss PCT]] [--tracker ocsort|sort] [--concurrent N] [--pix_fmt nv12|i420|yuyv422|uyvy422|p010le|rgb24 --size WxH] [--color_matrix bt601|bt709]
                             [--color_range limited|full] [--video_format raw|mjpeg] [--video_quality 85] [--mjpeg_entropy auto|interval|sync] [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--one_pass [--live_hud]]
                             [--display_image_height N]
       reference track.py:65-126.  SRC = .npy stack of RGB uint8 frames [T,H,W,3], or a Motion-JPEG .avi (the reference's
@@ -14,6 +14,9 @@
       --live: prints each concentric rep of the clip's leading id as soon as it is complete, in the format of `analyze`; a rep
       list that changes afterwards (the leading id changes, or a larger rep makes the filter drop small ones) is announced with a
       "revised" line and reprinted from the first rep that differs.  The reps standing at the end are those `analyze` prints.
+      --live --report: the rep lines of `analyze --report` instead (peak velocity, time to peak, vertical ROM, sideways excursion,
+      velocity loss), from the rep metrics formed on the device inside the live analysis.  --live --stop_loss PCT: one "STOP" line
+      at the first rep whose loss against the best rep so far reaches PCT percent (finite, > 0) - the set should end there.
       --tracker sort: SortTracker(max_age=30), the commented-out alternative of reference track.py:16,156 (it made the reference's
       dfs/ frames), instead of OCSort (track.py:157, the default); the file name rule and every other option are the same.
       --concurrent N > 1: all files through one pipeline, N clips side by side (a finished clip's tracker slot takes the next
@@ -58,9 +61,13 @@
                               [--hud [--plate_diameter 0.45] [--hud_scale 3] [--hud_pos 16,16]] [--display_image_height N]
       the same frames drawn later, from the clip and a stored {video}_id{N}_{model}.pkl.gz (all its ids are drawn; --hud takes the
       panel's id from the file name).
-  python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45]
+  python -m vbt_amd.cli analyze DF.pkl.gz... [--plate_diameter 0.45] [--report [--report_csv FILE]]
       reference plot.py:50-70,73-95,163-173 without the figure: parses {video}_id{N}_{model}.pkl.gz, applies the
       rolling(5)/expanding preprocessing and the VelocityTracker on the GPU, prints ROM and ACV per concentric rep.
+      --report: each rep line goes on with PV (peak velocity), TTP (time from the rep's start to the peak), vROM (vertical travel),
+      xdev (largest sideways excursion from the start) and loss (velocity loss in percent against the best rep so far); then a "set:"
+      line (reps, best / mean ACV, mean / max PV, loss of the last rep, summed concentric / eccentric time, mean xdev).
+      --report_csv FILE: one row per concentric rep of every DataFrame, all eight rep metrics, floats written exactly.
   python -m vbt_amd.cli plot DF.pkl.gz... --fig_dir DIR [--plate_diameter 0.45] [--fig_size 1280x800] [--fig_scale 2] [--fig_format jpg|ppm]
                            [--fig_quality 90]
       reference plot.py:50-232 with the figure, and without matplotlib: per DataFrame the smoothed position and velocity curves, a
@@ -93,6 +100,7 @@
 Option names (including the reference's `treshold` / `qualysis` spellings) and defaults follow the reference.
 """
 import contextlib
+import math
 import os
 import re
 
@@ -112,11 +120,47 @@ def _rep_line(i, p):
     return f"  rep {i}: t {p.time_start:.4f}-{p.time_end:.4f} s  ROM {p.rom:.6f} m  ACV {p.rom / p.duration:.6f} m/s"
 
 
-class _LiveReps:
-    """track --live: the concentric reps of the clip's leader as they complete (see the module docstring)."""
+def _report_lines(phases, metrics, stop_loss=0.0):
+    """--report: (the extended rep lines, the set line, the SetReport) of one id's phases and their rep metrics"""
+    from .velocity import RM_PV, RM_ROM_Y, RM_T_PV, RM_X_DEV, Phase, set_report
+    rep = set_report(phases, metrics, stop_loss)
+    lines = []
+    for k, (p, m) in enumerate(((p, m) for p, m in zip(phases, metrics) if p.type == Phase.CONCENTRIC), 1):
+        lines.append(_rep_line(k, p) + f"  PV {m[RM_PV]:.6f} m/s  TTP {m[RM_T_PV] - p.time_start:.4f} s  vROM {m[RM_ROM_Y]:.6f} m"
+                                       f"  xdev {m[RM_X_DEV]:.6f} m  loss {rep.loss_pct[k - 1]:.2f} %")
+    return lines, _set_line(rep), rep
 
-    def __init__(self, name):
+
+def _set_line(rep):
+    return (f"  set: {rep.n_reps} reps  best ACV {rep.best_mv:.6f} m/s (rep {rep.best_rep})  mean ACV {rep.mean_mv:.6f} m/s  mean PV {rep.mean_pv:.6f} m/s"
+            f"  max PV {rep.max_pv:.6f} m/s  loss {rep.loss_last_pct:.2f} %  concentric {rep.concentric_s:.4f} s  eccentric {rep.eccentric_s:.4f} s"
+            f"  mean xdev {rep.mean_x_dev:.6f} m")
+
+
+REPORT_CSV_COLUMNS = ("video", "id", "rep", "time_start", "time_end", "rom", "acv", "pv", "t_pv", "time_to_peak", "rom_y", "rom_x", "pv_y", "x_dev",
+                      "n_steps", "loss_pct")
+
+
+def _report_csv_rows(video, tid, phases, metrics, rep):
+    """--report_csv: one row per concentric rep; floats as repr() writes them, so that they read back exactly"""
+    from .velocity import RM_MV, RM_N_STEPS, RM_PV, RM_PV_Y, RM_ROM_X, RM_ROM_Y, RM_T_PV, RM_X_DEV, Phase
+    rows = []
+    for k, (p, m) in enumerate(((p, m) for p, m in zip(phases, metrics) if p.type == Phase.CONCENTRIC), 1):
+        vals = [p.time_start, p.time_end, p.rom, m[RM_MV], m[RM_PV], m[RM_T_PV], m[RM_T_PV] - p.time_start, m[RM_ROM_Y], m[RM_ROM_X], m[RM_PV_Y],
+                m[RM_X_DEV], m[RM_N_STEPS], rep.loss_pct[k - 1]]
+        rows.append([video, tid, k] + [repr(float(v)) for v in vals])
+    return rows
+
+
+class _LiveReps:
+    """track --live: the concentric reps of the clip's leader as they complete (see the module docstring).  report: the extended rep
+    line of `analyze --report` (the records then carry rep metrics); stop_loss > 0: one STOP line at the first rep whose velocity loss
+    reaches it (and again should a revision move it)."""
+
+    def __init__(self, name, report=False, stop_loss=None):
         self.name, self.shown, self.warned = name, [], False
+        self.report, self.stop_loss, self.stop_shown = report, stop_loss, None
+        self.rep_metrics = report or stop_loss is not None        # what track_frames reads
 
     def __call__(self, rec, final):
         from .velocity import Phase
@@ -126,6 +170,13 @@ class _LiveReps:
                 self.warned = True
             return
         lines = [_rep_line(i, p) for i, p in enumerate((p for p in rec.phases if p.type == Phase.CONCENTRIC), 1)]
+        stop = None
+        if self.rep_metrics:
+            ext, _, rep = _report_lines(rec.phases, rec.metrics, self.stop_loss or 0.0)
+            if self.report:
+                lines = ext
+            if rep.stop_rep:
+                stop = f"  STOP: rep {rep.stop_rep} lost {rep.loss_pct[rep.stop_rep - 1]:.2f} % (threshold {self.stop_loss:g} %)"
         k = 0
         while k < min(len(lines), len(self.shown)) and lines[k] == self.shown[k]:
             k += 1
@@ -134,16 +185,20 @@ class _LiveReps:
         for ln in lines[k:]:
             click.echo(ln)
         self.shown = lines
+        if stop is not None and stop != self.stop_shown:
+            click.echo(stop)
+            self.stop_shown = stop
 
 
 ANALYZE_COLUMNS = ("time", "x", "y", "dx", "dy", "norm_plate_height", "norm_plate_width")
 
 
-def _id_phases(df, tid, plate_diameter):
-    """The phases of id `tid` of an exported DataFrame (reference plot.py:73-95): what `analyze` prints and what --hud shows"""
+def _id_phases(df, tid, plate_diameter, metrics=False):
+    """The phases of id `tid` of an exported DataFrame (reference plot.py:73-95): what `analyze` prints and what --hud shows.
+    metrics: (phases, their rep metrics [P,8])"""
     from .velocity import analyze_rows
     df = df.query(f"id == {tid}").drop(columns=["id"])
-    return analyze_rows(np.stack([df[c].to_numpy(np.float64) for c in ANALYZE_COLUMNS], axis=1), plate_diameter, preprocess=True)
+    return analyze_rows(np.stack([df[c].to_numpy(np.float64) for c in ANALYZE_COLUMNS], axis=1), plate_diameter, preprocess=True, metrics=metrics)
 
 
 def _hud_options(f):
@@ -287,6 +342,10 @@ def _raw_size(pix_fmt, size):
 @click.option("--frame_stride", default=1, show_default=True, type=int, help="16 reproduces `frame_count %% 16` of reference track.py:166.")
 @click.option("--time_batch", default=64, show_default=True, type=int, help="Consecutive frames of the clip per detector batch (1 = one frame per step).")
 @click.option("--live", is_flag=True, default=False, help="Print each concentric rep (ROM, ACV) as soon as it is complete.")
+@click.option("--report", is_flag=True, default=False,
+              help="With --live: the extended rep line of `analyze --report` (peak velocity, time to peak, vertical ROM, sideways excursion, loss).")
+@click.option("--stop_loss", default=None, type=float,
+              help="With --live: print one STOP line at the first rep whose velocity loss against the best rep so far reaches this percentage.")
 @click.option("--tracker", default="ocsort", show_default=True, type=click.Choice(["ocsort", "sort"]),
               help="ocsort: OCSort(max_age=30, asso_func='diou', iou_threshold=0.1) of reference track.py:157; sort: SortTracker(max_age=30), its "
                    "commented-out alternative (track.py:156), which made the reference's dfs/ frames.  Every other option works with either.")
@@ -315,7 +374,7 @@ def _raw_size(pix_fmt, size):
                    "(uses --plate_diameter, --hud_scale, --hud_pos; not with --hud or --concurrent above 1).")
 @_display_option
 @_hud_options
-def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, tracker, concurrent, pix_fmt, color_matrix, color_range, size,
+def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch, live, report, stop_loss, tracker, concurrent, pix_fmt, color_matrix, color_range, size,
           video_dir, video_format, video_quality, mjpeg_entropy, one_pass, live_hud, hud, plate_diameter, hud_scale, hud_pos, display_image_height):
     from ._lib import VbtArgError
     from .track import export_dataframe, track_frames
@@ -327,6 +386,15 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
     _check_display_height(display_image_height, video_dir, pix_fmt)
     fps_given = _fps_given()
     hud_params = _hud_params(hud, video_dir, hud_scale, hud_pos)
+    if stop_loss is not None and not live:
+        raise click.UsageError("--stop_loss watches the reps as they complete: give --live")
+    if stop_loss is not None and not (math.isfinite(stop_loss) and stop_loss > 0):
+        raise click.UsageError(f"--stop_loss {stop_loss} must be a finite percentage above 0")
+    if report and not live:
+        raise click.UsageError("--report extends the rep lines of --live: give --live (a finished DataFrame: analyze --report)")
+
+    def live_reps(s):
+        return _LiveReps(s, report, stop_loss) if live else None
     if concurrent < 1:
         raise click.UsageError("--concurrent must be at least 1")
     hud_live = None
@@ -360,7 +428,7 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         display_hw = _display_hw(frames, pix_fmt, display_image_height)   # before any output file exists
         if hud_params is not None:                                       # the panel shows the finished analysis: render after tracking
             data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, tracker=tracker, **colour)
+                                live=live_reps(s), pix_fmt=pix_fmt, tracker=tracker, **colour)
             line, phases = _export_line(data, s, model, df_dir, plate_diameter)
             _render_video(video_dir, video_format, video_quality, s, frames, data, fps, frame_stride, time_batch, pix_fmt, size, phases, hud_params,
                           display_hw)
@@ -373,7 +441,7 @@ def track(src, model, detection_treshold, df_dir, fps, frame_stride, time_batch,
         with (_avi_out(video_dir, s, frames, fps, frame_stride, pix_fmt, display_hw) if mjpeg else contextlib.nullcontext()) as sink:   # closed on an error too
             try:
                 data = track_frames(frames, model, fps=fps, detection_treshold=detection_treshold, frame_stride=frame_stride, time_batch=time_batch,
-                                    live=_LiveReps(s) if live else None, pix_fmt=pix_fmt, video_out=video, video_sink=sink,
+                                    live=live_reps(s), pix_fmt=pix_fmt, video_out=video, video_sink=sink,
                                     video_quality=video_quality, one_pass=one_pass, hud_live=hud_live, tracker=tracker, display_hw=display_hw,
                                     **colour)
             except VbtArgError as e:                                     # a panel the library refuses (outside the frame, odd origin in a YUV frame)
@@ -556,9 +624,15 @@ def overlay(src, dataframe, fps, frame_stride, pix_fmt, size, video_dir, video_f
 @main.command()
 @click.argument("src", type=str, nargs=-1)
 @click.option("--plate_diameter", default=0.45, show_default=True, type=float, help="Diameter of the weight plate used in meters.")
-def analyze(src, plate_diameter):
+@click.option("--report", is_flag=True, default=False,
+              help="Per rep also peak velocity (PV), time to peak (TTP), vertical ROM, sideways excursion and velocity loss; then a line for the set.")
+@click.option("--report_csv", default=None, type=str, help="With --report: write one row per concentric rep to this CSV file.")
+def analyze(src, plate_diameter, report, report_csv):
     import pandas as pd
     from .velocity import Phase
+    if report_csv is not None and not report:
+        raise click.UsageError("--report_csv writes the rows of --report: give --report")
+    csv_rows = []
     for s in src:
         if not os.path.isfile(s):
             raise FileNotFoundError(s)                                   # reference plot.py:67-68
@@ -567,11 +641,25 @@ def analyze(src, plate_diameter):
             click.echo(f"Couldn't create a plot for file '{s}'.")        # reference plot.py:81-85
             continue
         video, tid, model = m.groups()
+        if report:
+            phases, metrics = _id_phases(pd.read_pickle(s), tid, plate_diameter, metrics=True)
+            lines, set_line, rep = _report_lines(phases, metrics)
+            click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {rep.n_reps} concentric reps")
+            for ln in lines + [set_line]:
+                click.echo(ln)
+            csv_rows += _report_csv_rows(video, tid, phases, metrics, rep)
+            continue
         phases = _id_phases(pd.read_pickle(s), tid, plate_diameter)
         reps = [p for p in phases if p.type == Phase.CONCENTRIC]
         click.echo(f"{video} (id {tid}, {model}): {len(phases)} phases, {len(reps)} concentric reps")
         for i, p in enumerate(reps, 1):
             click.echo(_rep_line(i, p))
+    if report_csv is not None:
+        import csv
+        with open(report_csv, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(REPORT_CSV_COLUMNS)
+            w.writerows(csv_rows)
 
 
 def _analyze_lines(video, tid, model, phases):

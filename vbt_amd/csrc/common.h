@@ -106,13 +106,15 @@ int resize_frames_pix_dev(const uint8_t* src_dev, int B, int H, int W, int pix_f
 // Slot close (vbt_pipeline_close_clips): the per-clip record close_pack_kernel writes, { int best_id, n_rows, n_phases, overflow ;
 // double phases[512][6] } (512 = the phases a clip keeps, tracker_state.h MAXPH; tracker.hip asserts the two agree)
 constexpr size_t CLOSED_HEAD_BYTES = 16 + 512 * 48;
+constexpr size_t CLOSED_METRICS_BYTES = 512 * 64;   // ... and, with rep metrics enabled, double metrics[512][8] in a block of their own
 // clips[0..n): each in [0, n_clips), none twice, n >= 1 - else VBT_ERR_ARG with the error text set (fn: the caller's name)
 int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips);
 // Device part of vbt_pipeline_close_clips (tracker_analysis.hip), enqueue only, on st: export id + rep analysis of the listed clips (the kernels
 // of vbt_tracker_finish on the list), their records into head (pinned, [n_clips][CLOSED_HEAD_BYTES]) and their rows into out_rows
-// (device, [n_clips][rows_cap] 64-byte rows), then a fresh clip in every listed slot (vbt_tracker_reset_clips)
+// (device, [n_clips][rows_cap] 64-byte rows), then a fresh clip in every listed slot (vbt_tracker_reset_clips).  mhead (or null; needs
+// rep metrics enabled on t): pinned, [n_clips][CLOSED_METRICS_BYTES], the metrics of the records' phases
 int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
-                        unsigned char* head, void* out_rows, hipStream_t st);
+                        unsigned char* head, double* mhead, void* out_rows, hipStream_t st);
 // The SORT tracker's parameters as vbt_tracker_create_sort takes them (tracker.hip): VBT_ERR_ARG with the text set for what it
 // refuses; no device call (who: the caller's name)
 int check_sort_params(const char* who, const vbt_sort_params* sp);

@@ -43,6 +43,9 @@ struct LiveBufs {
   double* paths;               // [n_clips][LIVE_ENTRIES][5][path_cap]
   double* phases;              // [n_clips][LIVE_ENTRIES][phase_cap][6]
   double* view;                // [n_clips][phase_cap][6]: flush-view scratch of the poll
+  // rep metrics (vbt_tracker_rep_metrics_enable); null when they are off
+  double* metrics;             // [n_clips][LIVE_ENTRIES][phase_cap][VT_METRICS]: the records of `phases`
+  double* mview;               // [n_clips][phase_cap][VT_METRICS]: the records of `view`
 };
 
 __device__ inline VtPath live_path(const LiveBufs& b, const LiveCfg& c, int clip, int e) {
@@ -53,6 +56,9 @@ __device__ inline VtPath live_path(const LiveBufs& b, const LiveCfg& c, int clip
 __device__ inline double* live_phases(const LiveBufs& b, const LiveCfg& c, int clip, int e) {
   return b.phases + ((size_t)clip * LIVE_ENTRIES + e) * c.phase_cap * 6;
 }
+__device__ inline double* live_metrics(const LiveBufs& b, const LiveCfg& c, int clip, int e) {
+  return b.metrics ? b.metrics + ((size_t)clip * LIVE_ENTRIES + e) * c.phase_cap * VT_METRICS : nullptr;
+}
 
 __device__ inline void live_entry_init(LiveEntry& x, long long id) {
   x.id = id;
@@ -62,11 +68,12 @@ __device__ inline void live_entry_init(LiveEntry& x, long long id) {
 }
 
 // One row of the entry's id (the rows of an id are applied in log order).  A full entry is frozen: it only counts rows.
+template <bool M>
 __device__ inline void live_apply(LiveEntry& x, const Row& r, const LiveBufs& b, const LiveCfg& c, int clip, int e) {
   if (!x.s.full) {
     const int k = x.nrows % 5;   // slot of row nrows - 5, the one leaving the rolling window
-    vt_row(x.s, x.rm, c.p, &r.time, x.nrows >= 5, x.ring[k][0], x.ring[k][1], live_path(b, c, clip, e), live_phases(b, c, clip, e),
-           c.phase_cap);
+    vt_row<M>(x.s, x.rm, c.p, &r.time, x.nrows >= 5, x.ring[k][0], x.ring[k][1], live_path(b, c, clip, e),
+           VtPhases{live_phases(b, c, clip, e), M ? live_metrics(b, c, clip, e) : nullptr, c.phase_cap});
     x.ring[k][0] = r.x;
     x.ring[k][1] = r.y;
   }
@@ -75,18 +82,24 @@ __device__ inline void live_apply(LiveEntry& x, const Row& r, const LiveBufs& b,
 
 // The entry's phase list into out[phase_cap][6], as it stands or - flush - as end_processing() (VelocityTracker.py:224-230) would
 // leave it, applied to a COPY of the state: it may append one phase and re-filter.  The live state is not touched.  One wavefront,
-// uniform entry; returns the number of phases and ORs the entry's VBT_LIVE_* flags into *flags.
+// uniform entry; returns the number of phases and ORs the entry's VBT_LIVE_* flags into *flags.  M (rep metrics enabled): mout holds
+// room for phase_cap records of VT_METRICS doubles, the metrics of the phases in `out` - those of the appended one included.
+template <bool M = false>
 __device__ inline int live_view(const LiveEntry& x, const LiveBufs& b, const LiveCfg& c, int clip, int e, bool flush, double* out,
-                                int* s_n, int* flags, int lane) {
+                                int* s_n, int* flags, int lane, double* mout = nullptr) {
   const double* ph = live_phases(b, c, clip, e);
   const int nph = x.s.nph;
   for (int i = lane; i < nph * 6; i += 64) out[i] = ph[i];
+  if (M) {
+    const double* pm = live_metrics(b, c, clip, e);
+    for (int i = lane; i < nph * VT_METRICS; i += 64) mout[i] = pm[i];
+  }
   __syncthreads();
   if (lane == 0) {
     int f = x.s.full, m = nph;
     if (flush && x.s.phase != 2 && !f) {
       VtState s = x.s;
-      vt_end_phase(s, c.p, live_path(b, c, clip, e), out, c.phase_cap);
+      vt_end_phase<M>(s, c.p, live_path(b, c, clip, e), VtPhases{out, mout, c.phase_cap});
       f |= s.full;
       m = s.nph;
     }

@@ -29,6 +29,7 @@ struct vbt_pipeline {
   int n = 0, n_trk = 0, depth = 0, ring = 0, defer = 0, device = 0, size = 0;
   bool trk_inline = false, placement_ok = true;
   bool live = false;               // vbt_pipeline_live_enable succeeded
+  bool rep_metrics = false;        // vbt_pipeline_rep_metrics_enable succeeded
   std::vector<double> fps;
   // detector outputs: one array per tensor, [ring slot][batch slot]...: the walk of a block addresses batch slot i of its step g as slot g * n + i
   DevBuf<float> boxes, scores, classes;
@@ -83,6 +84,8 @@ struct vbt_pipeline {
   // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
   PinnedBuf<unsigned char> closed_head;
   unsigned char* closed_head_dev = nullptr;   // (its device address)
+  PinnedBuf<unsigned char> closed_metrics;    // rep metrics on: per tracker clip the metrics of its record's phases (CLOSED_METRICS_BYTES)
+  double* closed_metrics_dev = nullptr;
   DevBuf<unsigned char> closed_rows;
   std::vector<Event> ev_closed;
   std::vector<char> closed_unread;
@@ -957,6 +960,19 @@ int vbt_pipeline_finish(vbt_pipeline* p) {
   return VBT_OK;
 }
 
+// The metrics block of the slot close, once both the slot close and the rep metrics are enabled (whichever came second calls it)
+static int closed_metrics_alloc(vbt_pipeline* p) {
+  if (!p->rep_metrics || !p->closed_head || p->closed_metrics) return VBT_OK;
+  PinnedBuf<unsigned char> m;
+  double* dev = nullptr;
+  hipError_t e = m.alloc((size_t)p->n_trk * CLOSED_METRICS_BYTES, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dev, m.get(), 0);
+  if (e != hipSuccess) { set_error("hipHostMalloc of the close metrics failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
+  p->closed_metrics = std::move(m);
+  p->closed_metrics_dev = dev;
+  return VBT_OK;
+}
+
 // The slot close's buffers, allocated once so that no close allocates: per tracker clip a pinned record, a device row outbox and an
 // event; and the stream the rows come back on.  All or nothing.
 int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
@@ -996,7 +1012,7 @@ int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
   p->closed_head_dev = head_dev;
   p->ev_closed = std::move(evs);
   p->closed_unread.assign(nt, 0);
-  return VBT_OK;
+  return closed_metrics_alloc(p);
 }
 
 // Slot close.  Enqueue only: drain() hands the held-back tracker steps to their streams, the close kernels and the reset follow on the
@@ -1021,7 +1037,7 @@ int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const
   PL_CHECK(drain(p));
   hipStream_t T = p->trk_stream;
   PL_CHECK(tracker_close_clips(p->trk.get(), clips, n, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, p->closed_head_dev,
-                               p->closed_rows.get(), T));
+                               p->closed_metrics_dev, p->closed_rows.get(), T));
   for (int i = 0; i < n; i++) {
     const int c = clips[i];
     VBT_HIP_CHECK(hipEventRecord(p->ev_closed[(size_t)c].get(), T));
@@ -1036,12 +1052,9 @@ int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const
   return VBT_OK;
 }
 
-int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, int cap_phases,
-                             void* rows_host, int cap_rows) {
-  if (!p || !ready || !rec || cap_phases < 0 || (cap_phases > 0 && !phases6) || (rows_host && cap_rows < 0)) {
-    set_error("vbt_pipeline_closed_clip: bad argument");
-    return VBT_ERR_ARG;
-  }
+// vbt_pipeline_closed_clip (metrics8 == nullptr) / vbt_pipeline_closed_clip_ex
+static int closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, double* metrics8, int cap_phases,
+                       void* rows_host, int cap_rows) {
   if (clip < 0 || clip >= p->n_trk) { set_error("vbt_pipeline_closed_clip: slot %d outside the %d clips", clip, p->n_trk); return VBT_ERR_ARG; }
   *ready = 0;
   if (p->closed_unread.empty() || !p->closed_unread[(size_t)clip]) { set_error("vbt_pipeline_closed_clip: slot %d has no unread result", clip); return VBT_ERR_STATE; }
@@ -1061,6 +1074,7 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
   if (hd[2] > cap_phases) { set_error("vbt_pipeline_closed_clip: slot %d has %d phases, buffer holds %d", clip, hd[2], cap_phases); return VBT_ERR_CAPACITY; }
   if (rows_host && hd[1] > cap_rows) { set_error("vbt_pipeline_closed_clip: slot %d has %d rows, buffer holds %d", clip, hd[1], cap_rows); return VBT_ERR_CAPACITY; }
   if (hd[2] > 0) memcpy(phases6, h + 16, (size_t)hd[2] * 48);
+  if (hd[2] > 0 && metrics8) memcpy(metrics8, p->closed_metrics.get() + (size_t)clip * CLOSED_METRICS_BYTES, (size_t)hd[2] * 64);
   if (rows_host && hd[1] > 0) {
     const unsigned char* src = p->closed_rows.get() + (size_t)clip * p->prm.rows_cap * 64;
     VBT_HIP_CHECK(hipStreamWaitEvent(p->read_stream, ev, 0));   // (done already: the copy waits for this close only)
@@ -1070,6 +1084,35 @@ int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vb
   p->closed_unread[(size_t)clip] = 0;
   *ready = 1;
   return VBT_OK;
+}
+
+int vbt_pipeline_closed_clip(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, int cap_phases,
+                             void* rows_host, int cap_rows) {
+  if (!p || !ready || !rec || cap_phases < 0 || (cap_phases > 0 && !phases6) || (rows_host && cap_rows < 0)) {
+    set_error("vbt_pipeline_closed_clip: bad argument");
+    return VBT_ERR_ARG;
+  }
+  return closed_clip(p, clip, wait, ready, rec, phases6, nullptr, cap_phases, rows_host, cap_rows);
+}
+
+int vbt_pipeline_closed_clip_ex(vbt_pipeline* p, int clip, int wait, int* ready, vbt_closed_clip* rec, double* phases6, double* metrics8,
+                                int cap_phases, void* rows_host, int cap_rows) {
+  if (!p || !ready || !rec || cap_phases < 0 || (cap_phases > 0 && (!phases6 || !metrics8)) || (rows_host && cap_rows < 0)) {
+    set_error("vbt_pipeline_closed_clip_ex: bad argument");
+    return VBT_ERR_ARG;
+  }
+  if (!p->rep_metrics) { set_error("vbt_pipeline_closed_clip_ex: rep metrics are not enabled (vbt_pipeline_rep_metrics_enable)"); return VBT_ERR_STATE; }
+  return closed_clip(p, clip, wait, ready, rec, phases6, cap_phases > 0 ? metrics8 : nullptr, cap_phases, rows_host, cap_rows);
+}
+
+int vbt_pipeline_close_ex(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6,
+                          double* metrics8, int cap) {
+  if (!p || !best_ids || !n_rows || !n_phases || !overflow || !phases6 || !metrics8) { set_error("vbt_pipeline_close_ex: NULL argument"); return VBT_ERR_ARG; }
+  if (!p->rep_metrics) { set_error("vbt_pipeline_close_ex: rep metrics are not enabled (vbt_pipeline_rep_metrics_enable)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));
+  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  return vbt_tracker_summary_ex(p->trk.get(), best_ids, n_rows, n_phases, overflow, phases6, metrics8, cap);
 }
 
 int vbt_pipeline_close(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6, int cap) {
@@ -1143,6 +1186,24 @@ int vbt_pipeline_live_enable(vbt_pipeline* p, int path_cap, int phase_cap) {
   PL_CHECK(vbt_tracker_live_enable(p->trk.get(), path_cap, phase_cap, p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance));
   p->live = true;
   return VBT_OK;
+}
+
+int vbt_pipeline_rep_metrics_enable(vbt_pipeline* p) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (p->rep_metrics) return VBT_OK;
+  if (p->step_idx > 0) { set_error("vbt_pipeline_rep_metrics_enable: steps were enqueued (enable before the first step, or after a reset)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(vbt_tracker_rep_metrics_enable(p->trk.get()));
+  p->rep_metrics = true;
+  return closed_metrics_alloc(p);
+}
+
+int vbt_pipeline_live_poll_ex(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap) {
+  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
+  if (!p->live) { set_error("vbt_pipeline_live_poll_ex: live analysis is not enabled"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));   // (as vbt_pipeline_live_poll)
+  return vbt_tracker_live_poll_ex(p->trk.get(), flush_view, clips, phases6, metrics8, cap, (void*)p->trk_stream);
 }
 
 int vbt_pipeline_use_sort(vbt_pipeline* p, const vbt_sort_params* sp) {

@@ -31,6 +31,15 @@ struct VtPath {
   int cap;
 };
 
+// The phase list a scan appends to: ph holds room for `cap` phases of 6 doubles; pm, when rep metrics are enabled, for their `cap`
+// records of VT_METRICS doubles.  The scan's functions are templates on M, metrics formed or not: with M = false pm is never read and
+// the code is the scan as it is without metrics, instruction for instruction; with M = true pm is not null.
+constexpr int VT_METRICS = 8;   // = VBT_REP_METRICS; columns VBT_RM_* (include/vbt_hip.h)
+struct VtPhases {
+  double *ph, *pm;
+  int cap;
+};
+
 __device__ inline void vt_init(VtState& s) {
   s.phase = 2; s.neg = 0; s.pos = 0; s.nph = 0; s.n = 0; s.has_prev = 0; s.has_max = 0; s.y_prev = 0; s.max_y_diff = 0;
   s.whead = 0; s.wcount = 0; s.wtotal = 0.0; s.ver = 0; s.full = 0;
@@ -50,13 +59,18 @@ __device__ inline double ra_update(VtState& s, double v) {  // reference Running
   return s.wtotal / (double)s.wcount;
 }
 
-__device__ inline void vt_filter(VtState& s, double* ph) {  // VelocityTracker.py:50-67
+template <bool M>
+__device__ inline void vt_filter(VtState& s, const VtPhases& l) {  // VelocityTracker.py:50-67
+  double *ph = l.ph, *pm = l.pm;
   double thr = s.max_y_diff / 2;
   int o = 0;
   for (int i = 0; i < s.nph; i++) {
     double yd = fabs(ph[i * 6 + 2] - ph[i * 6 + 3]);
     if (!(yd < thr)) {
-      if (o != i) for (int j = 0; j < 6; j++) ph[o * 6 + j] = ph[i * 6 + j];
+      if (o != i) {
+        for (int j = 0; j < 6; j++) ph[o * 6 + j] = ph[i * 6 + j];
+        if (M) for (int j = 0; j < VT_METRICS; j++) pm[o * VT_METRICS + j] = pm[i * VT_METRICS + j];   // the record travels with its phase
+      }
       o++;
     }
   }
@@ -64,8 +78,35 @@ __device__ inline void vt_filter(VtState& s, double* ph) {  // VelocityTracker.p
   s.nph = o;
 }
 
-// ph holds room for phcap phases
-__device__ inline void vt_end_phase(VtState& s, const VtParams& p, const VtPath& q, double* ph, int phcap) {  // VelocityTracker.py:171-222
+// The rep metrics of the phase just appended ("Rep metrics"): one more pass over the steps st+1 .. en that `rom`
+// was summed over, in index order, every per-step term the expression of vt_end_phase.  m[VT_METRICS].
+__device__ inline void vt_phase_metrics(const VtParams& p, const VtPath& q, int st, int en, double rom, double* m) {
+  const double *xs = q.xs, *ys = q.ys, *ws = q.ws, *hs = q.hs, *ts = q.ts;
+  double pv = 0.0, t_pv = ts[st], rom_y = 0.0, rom_x = 0.0, pv_y = 0.0, x_dev = 0.0;
+  for (int i = st + 1; i < en + 1; i++) {
+    double ddx = fabs(xs[i] - xs[i - 1]) / ((ws[i] + ws[i - 1]) / 2) * p.plate_diameter;
+    double ddy = fabs(ys[i] - ys[i - 1]) / ((hs[i] + hs[i - 1]) / 2) * p.plate_diameter;
+    rom_x += ddx;
+    rom_y += ddy;
+    double dt = ts[i] - ts[i - 1];
+    if (dt > 0) {   // (a tracker's log cannot hold two rows of one time stamp; rows handed to vbt_analyze_metrics can)
+      double v = (ddx + ddy) / dt, vy = ddy / dt;
+      if (v > pv) { pv = v; t_pv = ts[i]; }
+      if (vy > pv_y) pv_y = vy;
+    }
+    double dev = fabs(xs[i] - xs[st]) / ((ws[i] + ws[st]) / 2) * p.plate_diameter;
+    if (dev > x_dev) x_dev = dev;
+  }
+  double dur = ts[en] - ts[st];
+  m[0] = pv; m[1] = t_pv; m[2] = rom_y; m[3] = rom_x; m[4] = pv_y;
+  m[5] = dur > 0 ? rom / dur : 0.0;   // the reference's ACV (plot.py:173)
+  m[6] = x_dev;
+  m[7] = en > st ? (double)(en - st) : 0.0;
+}
+
+template <bool M>
+__device__ inline void vt_end_phase(VtState& s, const VtParams& p, const VtPath& q, const VtPhases& l) {  // VelocityTracker.py:171-222
+  double* ph = l.ph;
   const double *xs = q.xs, *ys = q.ys, *ws = q.ws, *hs = q.hs, *ts = q.ts;
   int imax = 0, imin = 0;
   for (int i = 1; i < s.n; i++) {
@@ -77,7 +118,7 @@ __device__ inline void vt_end_phase(VtState& s, const VtParams& p, const VtPath&
   if (!s.has_max || y_diff > s.max_y_diff) {
     s.max_y_diff = y_diff;
     s.has_max = 1;
-    vt_filter(s, ph);
+    vt_filter<M>(s, l);
   }
   if (y_diff > s.max_y_diff * p.diff_threshold) {
     double distance = 0.0;
@@ -90,15 +131,16 @@ __device__ inline void vt_end_phase(VtState& s, const VtParams& p, const VtPath&
       s.neg = 0; s.pos = 0; s.phase = 2;
       return;
     }
-    if (s.nph < phcap) {
+    if (s.nph < l.cap) {
       double* o = ph + s.nph * 6;
       o[0] = ts[st]; o[1] = ts[en]; o[2] = ys[st]; o[3] = ys[en]; o[4] = distance; o[5] = (double)s.phase;
+      if (M) vt_phase_metrics(p, q, st, en, distance, l.pm + s.nph * VT_METRICS);
       s.nph += 1;
       s.ver += 1;
     } else {
       s.full |= 2;
     }
-    vt_filter(s, ph);
+    vt_filter<M>(s, l);
   }
   s.phase = 2;
   s.pos = 0; s.neg = 0;
@@ -112,8 +154,9 @@ __device__ inline void vt_push(VtState& s, const VtPath& q, double x, double y, 
 // ONE row of one track - the per-row step shared by the close-time scan (analyze_track) and the live analysis
 // (live_analyze_kernel), so that the two cannot drift apart.  r = time,x,y,dx,dy,h,w.  p.preprocess: plot.py:90-95 first, with
 // rm = the rolling(5) x / y and expanding h / w means and (drop_x, drop_y) the raw values leaving the window (drop: row >= 5).
+template <bool M>
 __device__ inline void vt_row(VtState& s, RollMean* rm, const VtParams& p, const double* r, bool drop, double drop_x, double drop_y,
-                              const VtPath& q, double* ph, int phcap) {
+                              const VtPath& q, const VtPhases& l) {
   double time = r[0], x = r[1], y = r[2], h = r[5], w = r[6];
   if (p.preprocess) {  // (dx, dy columns are smoothed there too but never used downstream)
     if (drop) { rm[0].remove(drop_x); rm[1].remove(drop_y); }
@@ -128,11 +171,11 @@ __device__ inline void vt_row(VtState& s, RollMean* rm, const VtParams& p, const
   else if (p.preprocess) dy = r[4];  // first sample: the (smoothed == raw) incoming dy
   if (s.phase != 2) vt_push(s, q, x, y, width, height, time);
   if (s.phase == 0) {
-    if (dy > 0) { s.pos += 1; s.neg = 0; if (s.pos >= 1) vt_end_phase(s, p, q, ph, phcap); }
+    if (dy > 0) { s.pos += 1; s.neg = 0; if (s.pos >= 1) vt_end_phase<M>(s, p, q, l); }
     else s.pos = 0;
   }
   if (s.phase == 1) {
-    if (dy < 0) { s.neg += 1; s.pos = 0; if (s.neg >= 1) vt_end_phase(s, p, q, ph, phcap); }
+    if (dy < 0) { s.neg += 1; s.pos = 0; if (s.neg >= 1) vt_end_phase<M>(s, p, q, l); }
     else { s.neg = 0; s.pos += 1; }
   }
   if (dy < 0 && s.phase == 2) {
@@ -151,8 +194,11 @@ __device__ inline void vt_row(VtState& s, RollMean* rm, const VtParams& p, const
 }
 
 // cols: [T][7] = time,x,y,dx,dy,h,w of ONE track.  One lane per clip does the sequential scan.
-__device__ void analyze_track(const double* cols, int T, const VtParams& p, double* scratch /*5*T*/, double* ph, int* nph_out) {
+// pm: the metrics of the phases (MAXPH records); not read with M = false
+template <bool M>
+__device__ void analyze_track(const double* cols, int T, const VtParams& p, double* scratch /*5*T*/, double* ph, double* pm, int* nph_out) {
   const VtPath q{scratch, scratch + T, scratch + 2 * T, scratch + 3 * T, scratch + 4 * T, T};
+  const VtPhases l{ph, pm, MAXPH};
   VtState s;
   vt_init(s);
   RollMean rm[4];
@@ -160,9 +206,9 @@ __device__ void analyze_track(const double* cols, int T, const VtParams& p, doub
   for (int i = 0; i < T; i++) {
     const bool drop = i >= 5;
     const double* old = cols + (size_t)(drop ? i - 5 : i) * 7;
-    vt_row(s, rm, p, cols + (size_t)i * 7, drop, old[1], old[2], q, ph, MAXPH);
+    vt_row<M>(s, rm, p, cols + (size_t)i * 7, drop, old[1], old[2], q, l);
   }
-  if (p.flush && s.phase != 2) vt_end_phase(s, p, q, ph, MAXPH);  // end_processing, VelocityTracker.py:224-230
+  if (p.flush && s.phase != 2) vt_end_phase<M>(s, p, q, l);  // end_processing, VelocityTracker.py:224-230
   *nph_out = s.nph;
 }
 

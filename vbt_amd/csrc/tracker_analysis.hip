@@ -6,12 +6,14 @@
 
 namespace vbt {
 
+// metrics: [n_clips][MAXPH][VT_METRICS] (M: rep metrics on; else not read)
+template <bool M>
 __global__ __launch_bounds__(64) void analyze_kernel(const double* cols, const int* T, int stride_rows, VtParams p, double* scratch,
-                                                     double* phases, int* nph, ClipList l) {
+                                                     double* phases, double* metrics, int* nph, ClipList l) {
   const int clip = listed_clip(l);
   if (threadIdx.x != 0) return;
-  analyze_track(cols + (size_t)clip * stride_rows * 7, T[clip], p, scratch + (size_t)clip * stride_rows * 5,
-                phases + (size_t)clip * MAXPH * 6, nph + clip);
+  analyze_track<M>(cols + (size_t)clip * stride_rows * 7, T[clip], p, scratch + (size_t)clip * stride_rows * 5,
+                phases + (size_t)clip * MAXPH * 6, M ? metrics + (size_t)clip * MAXPH * VT_METRICS : nullptr, nph + clip);
 }
 
 // pandas rolling(window, min_periods=1).mean() (window > 0) / expanding(min_periods=1).mean() (window == 0) of every
@@ -66,8 +68,10 @@ __global__ __launch_bounds__(64) void select_gather_kernel(ClipState* states, co
 // Clip close: everything the host reads per clip, packed into one block so that ONE copy fetches it:
 //   record c = { int best_id, n_rows, n_phases, overflow ; double phases[cap][6] }
 // On a clip list (vbt_pipeline_close_clips, cap = MAXPH) the records of the listed clips only, straight into pinned host memory.
+// metrics != null: the metrics of those phases too, clip c's min(n_phases, cap) records at mdst + c * mstride doubles.
 __global__ __launch_bounds__(64) void pack_summary_kernel(const ClipState* states, const int* best, const int* nph, const double* phases,
-                                                          int cap, unsigned char* out, ClipList l) {
+                                                          int cap, unsigned char* out, ClipList l, const double* metrics, double* mdst,
+                                                          size_t mstride) {
   const int clip = listed_clip(l), lane = threadIdx.x;
   const size_t rec = 16 + (size_t)cap * 48;
   unsigned char* o = out + clip * rec;
@@ -79,6 +83,11 @@ __global__ __launch_bounds__(64) void pack_summary_kernel(const ClipState* state
   double* ph = (double*)(o + 16);
   const double* src = phases + (size_t)clip * MAXPH * 6;
   for (int i = lane; i < min(n, cap) * 6; i += 64) ph[i] = src[i];
+  if (metrics) {
+    const double* ms = metrics + (size_t)clip * MAXPH * VT_METRICS;
+    double* md = mdst + clip * mstride;
+    for (int i = lane; i < min(n, cap) * VT_METRICS; i += 64) md[i] = ms[i];
+  }
 }
 
 // Slot close (vbt_pipeline_close_clips): the first n_rows rows of every listed clip's log - the 64-byte records of vbt_tracker_rows_all -
@@ -102,7 +111,10 @@ void enqueue_analysis(vbt_tracker* t, double plate_diameter, double diff_thresho
   const int nb = l.n ? l.n : t->n_clips;
   const VtParams vp{plate_diameter, diff_threshold, min_distance, 1, 1};
   select_gather_kernel<<<nb, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, t->cols.get(), t->T.get(), t->best.get(), l);
-  analyze_kernel<<<nb, 64, 0, st>>>(t->cols.get(), t->T.get(), t->rows_cap, vp, t->scratch.get(), t->phases.get(), t->nph.get(), l);
+  if (t->rep_metrics)
+    analyze_kernel<true><<<nb, 64, 0, st>>>(t->cols.get(), t->T.get(), t->rows_cap, vp, t->scratch.get(), t->phases.get(), t->metrics.get(), t->nph.get(), l);
+  else
+    analyze_kernel<false><<<nb, 64, 0, st>>>(t->cols.get(), t->T.get(), t->rows_cap, vp, t->scratch.get(), t->phases.get(), nullptr, t->nph.get(), l);
 }
 
 }  // namespace
@@ -128,12 +140,13 @@ int check_clip_list(const char* fn, const int32_t* clips, int n, int n_clips) {
 }
 
 int tracker_close_clips(vbt_tracker* t, const int32_t* clips, int n, double plate_diameter, double diff_threshold, double min_distance,
-                        unsigned char* head, void* out_rows, hipStream_t st) {
+                        unsigned char* head, double* mhead, void* out_rows, hipStream_t st) {
   RoctxRange range("vbt:close_clips");
   for (int i0 = 0; i0 < n; i0 += CLIP_LIST) {
     const ClipList l = clip_list(clips, i0, n);
     enqueue_analysis(t, plate_diameter, diff_threshold, min_distance, l, st);
-    pack_summary_kernel<<<l.n, 64, 0, st>>>(t->states.get(), t->best.get(), t->nph.get(), t->phases.get(), MAXPH, head, l);
+    pack_summary_kernel<<<l.n, 64, 0, st>>>(t->states.get(), t->best.get(), t->nph.get(), t->phases.get(), MAXPH, head, l,
+                                            mhead ? t->metrics.get() : nullptr, mhead, (size_t)MAXPH * VT_METRICS);
     close_rows_kernel<<<l.n, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, l, (Row*)out_rows);
   }
   VBT_HIP_CHECK(hipGetLastError());
@@ -171,29 +184,82 @@ int vbt_tracker_phases(vbt_tracker* t, int clip, int32_t* best_id, double* phase
   return VBT_OK;
 }
 
-int vbt_analyze(const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
-                double min_distance, double* phases6, int cap, int* P, int device) {
-  if (!cols7 && T > 0) { set_error("vbt_analyze: NULL rows"); return VBT_ERR_ARG; }
-  if (!phases6 || !P || T < 0) { set_error("vbt_analyze: bad argument"); return VBT_ERR_ARG; }
-  if (int rc = use_device("vbt_analyze", device)) return rc;
+// vbt_analyze (metrics8 == nullptr) / vbt_analyze_metrics
+static int analyze_rows(const char* fn, const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
+                        double min_distance, double* phases6, double* metrics8, int cap, int* P, int device) {
+  if (!cols7 && T > 0) { set_error("%s: NULL rows", fn); return VBT_ERR_ARG; }
+  if (!phases6 || !P || T < 0) { set_error("%s: bad argument", fn); return VBT_ERR_ARG; }
+  if (int rc = use_device(fn, device)) return rc;
   *P = 0;
   if (T == 0) return VBT_OK;
-  DevBuf<double> dc, ds, dp;   // freed on every way out; on the good one after the last blocking copy
+  DevBuf<double> dc, ds, dp, dm;   // freed on every way out; on the good one after the last blocking copy
   DevBuf<int> dn, dT;
   VBT_HIP_CHECK(dc.alloc((size_t)7 * T));
   VBT_HIP_CHECK(ds.alloc((size_t)5 * T));
   VBT_HIP_CHECK(dp.alloc((size_t)6 * MAXPH));
+  if (metrics8) VBT_HIP_CHECK(dm.alloc((size_t)VT_METRICS * MAXPH));
   VBT_HIP_CHECK(dn.alloc(1));
   VBT_HIP_CHECK(dT.alloc(1));
   VBT_HIP_CHECK(hipMemcpy(dc.get(), cols7, sizeof(double) * 7 * T, hipMemcpyHostToDevice));
   VBT_HIP_CHECK(hipMemcpy(dT.get(), &T, sizeof(int), hipMemcpyHostToDevice));
   VtParams vp{plate_diameter, diff_threshold, min_distance, preprocess, flush};
-  analyze_kernel<<<1, 64>>>(dc.get(), dT.get(), T, vp, ds.get(), dp.get(), dn.get(), ClipList{});
+  if (metrics8) analyze_kernel<true><<<1, 64>>>(dc.get(), dT.get(), T, vp, ds.get(), dp.get(), dm.get(), dn.get(), ClipList{});
+  else analyze_kernel<false><<<1, 64>>>(dc.get(), dT.get(), T, vp, ds.get(), dp.get(), nullptr, dn.get(), ClipList{});
   int n = 0;
   hipError_t e = hipMemcpy(&n, dn.get(), sizeof(int), hipMemcpyDeviceToHost);
   if (e != hipSuccess) { set_error("analyze kernel failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
   if (n > cap) { set_error("%d phases, buffer holds %d", n, cap); return VBT_ERR_CAPACITY; }
   if (n) (void)hipMemcpy(phases6, dp.get(), sizeof(double) * 6 * n, hipMemcpyDeviceToHost);
+  if (n && metrics8) VBT_HIP_CHECK(hipMemcpy(metrics8, dm.get(), sizeof(double) * VT_METRICS * n, hipMemcpyDeviceToHost));
+  *P = n;
+  return VBT_OK;
+}
+
+int vbt_analyze(const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
+                double min_distance, double* phases6, int cap, int* P, int device) {
+  return analyze_rows("vbt_analyze", cols7, T, preprocess, flush, plate_diameter, diff_threshold, min_distance, phases6, nullptr, cap, P, device);
+}
+
+int vbt_analyze_metrics(const double* cols7, int T, int preprocess, int flush, double plate_diameter, double diff_threshold,
+                        double min_distance, double* phases6, double* metrics8, int cap, int* P, int device) {
+  if (!metrics8) { set_error("vbt_analyze_metrics: bad argument"); return VBT_ERR_ARG; }
+  return analyze_rows("vbt_analyze_metrics", cols7, T, preprocess, flush, plate_diameter, diff_threshold, min_distance, phases6, metrics8, cap, P,
+                      device);
+}
+
+int vbt_tracker_rep_metrics_enable(vbt_tracker* t) {
+  if (!t) { set_error("NULL tracker"); return VBT_ERR_ARG; }
+  if (t->rep_metrics) return VBT_OK;
+  if (t->stepped) { set_error("vbt_tracker_rep_metrics_enable: the tracker has been stepped (enable before the first update, or after a reset)"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipSetDevice(t->device));
+  if (t->metrics.alloc((size_t)t->n_clips * MAXPH * VT_METRICS) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("vbt_tracker_rep_metrics_enable: hipMalloc of the metrics failed (%d clips)", t->n_clips);
+    return VBT_ERR_HIP;
+  }
+  t->rep_metrics = true;
+  if (!live_metrics_alloc(t)) {
+    t->rep_metrics = false;
+    t->metrics.reset();
+    (void)hipGetLastError();
+    set_error("vbt_tracker_rep_metrics_enable: hipMalloc of the live metrics failed (%d clips, phase_cap %d)", t->n_clips, t->lc.phase_cap);
+    return VBT_ERR_HIP;
+  }
+  return VBT_OK;
+}
+
+int vbt_tracker_rep_metrics(vbt_tracker* t, int clip, double* metrics8, int cap, int* P) {
+  if (!t || !metrics8 || !P || clip < 0 || clip >= t->n_clips) { set_error("vbt_tracker_rep_metrics: bad argument"); return VBT_ERR_ARG; }
+  if (!t->rep_metrics) { set_error("vbt_tracker_rep_metrics: rep metrics are not enabled (vbt_tracker_rep_metrics_enable)"); return VBT_ERR_STATE; }
+  if (!t->finished) { set_error("vbt_tracker_rep_metrics before vbt_tracker_finish"); return VBT_ERR_STATE; }
+  VBT_HIP_CHECK(hipDeviceSynchronize());
+  StateHeader st;   // (refused as vbt_tracker_phases refuses it)
+  if (int rc = fetch_state_header(t, clip, &st)) return rc;
+  if (int rc = check_state_header(t, clip, st, t->rows_cap)) return rc;
+  int n = 0;
+  VBT_HIP_CHECK(hipMemcpy(&n, t->nph.get() + clip, sizeof(int), hipMemcpyDeviceToHost));
+  if (n > cap) { set_error("clip %d has %d phases, buffer holds %d", clip, n, cap); return VBT_ERR_CAPACITY; }
+  if (n) VBT_HIP_CHECK(hipMemcpy(metrics8, t->metrics.get() + (size_t)clip * MAXPH * VT_METRICS, sizeof(double) * VT_METRICS * n, hipMemcpyDeviceToHost));
   *P = n;
   return VBT_OK;
 }
@@ -219,23 +285,40 @@ int vbt_window_means(const double* rows, int T, int ncols, const int32_t* window
 
 // Clip close, host side: one pack kernel, ONE asynchronous copy into pinned memory, ONE stream synchronisation (on the
 // stream vbt_tracker_finish ran on - not a device-wide one).
-int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6, int cap) {
-  if (!t || !best_ids || !n_rows || !n_phases || !overflow || !phases6 || cap < 1) { set_error("bad argument"); return VBT_ERR_ARG; }
-  if (!t->finished) { set_error("vbt_tracker_summary before vbt_tracker_finish"); return VBT_ERR_STATE; }
+// metrics8 != nullptr (vbt_tracker_summary_ex): the block carries, behind the n_clips records, n_clips x pcap metrics records.
+static int tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6,
+                           double* metrics8, int cap) {
   const int n = t->n_clips;
   const int pcap = std::min(cap, MAXPH);   // phases packed per clip (a clip never holds more than MAXPH); cap stays the caller's stride
-  const size_t rec = 16 + (size_t)pcap * 48, bytes = rec * n;
+  const size_t rec = 16 + (size_t)pcap * 48, mrec = (size_t)pcap * VT_METRICS * sizeof(double);
+  const size_t bytes = rec * n + (metrics8 ? mrec * n : 0);
   VBT_HIP_CHECK(t->summary.reserve(bytes));
   hipStream_t st = t->finish_stream;
-  pack_summary_kernel<<<n, 64, 0, st>>>(t->states.get(), t->best.get(), t->nph.get(), t->phases.get(), pcap, t->summary.dev(), ClipList{});
+  pack_summary_kernel<<<n, 64, 0, st>>>(t->states.get(), t->best.get(), t->nph.get(), t->phases.get(), pcap, t->summary.dev(), ClipList{},
+                                        metrics8 ? t->metrics.get() : nullptr, (double*)(t->summary.dev() + rec * n), (size_t)pcap * VT_METRICS);
   VBT_HIP_CHECK(t->summary.fetch(bytes, st));
   for (int c = 0; c < n; c++) {
     const unsigned char* r = t->summary.host() + c * rec;
     const int* h = (const int*)r;
     best_ids[c] = h[0]; n_rows[c] = h[1]; n_phases[c] = h[2]; overflow[c] = h[3];
     if (int rc = unpack_phases("clip", c, r + 16, h[2], phases6, (size_t)c, cap)) return rc;
+    if (metrics8) unpack_metrics(t->summary.host() + rec * n + c * mrec, h[2], metrics8, (size_t)c, cap);
   }
   return VBT_OK;
+}
+
+int vbt_tracker_summary(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6, int cap) {
+  if (!t || !best_ids || !n_rows || !n_phases || !overflow || !phases6 || cap < 1) { set_error("bad argument"); return VBT_ERR_ARG; }
+  if (!t->finished) { set_error("vbt_tracker_summary before vbt_tracker_finish"); return VBT_ERR_STATE; }
+  return tracker_summary(t, best_ids, n_rows, n_phases, overflow, phases6, nullptr, cap);
+}
+
+int vbt_tracker_summary_ex(vbt_tracker* t, int32_t* best_ids, int32_t* n_rows, int32_t* n_phases, int32_t* overflow, double* phases6,
+                           double* metrics8, int cap) {
+  if (!t || !best_ids || !n_rows || !n_phases || !overflow || !phases6 || !metrics8 || cap < 1) { set_error("vbt_tracker_summary_ex: bad argument"); return VBT_ERR_ARG; }
+  if (!t->rep_metrics) { set_error("vbt_tracker_summary_ex: rep metrics are not enabled (vbt_tracker_rep_metrics_enable)"); return VBT_ERR_STATE; }
+  if (!t->finished) { set_error("vbt_tracker_summary_ex before vbt_tracker_finish"); return VBT_ERR_STATE; }
+  return tracker_summary(t, best_ids, n_rows, n_phases, overflow, phases6, metrics8, cap);
 }
 
 // DataFrame rows of EVERY clip (all ids, emission order) in one strided copy: rows_host = [n_clips][cap] records of

@@ -33,6 +33,10 @@ struct vbt_tracker {
   vbt::LiveBufs lb{};
   vbt::LiveCfg lc{};
   vbt::Mirror live_poll;                 // packed poll block (live_pack_kernel), grown on demand
+  // rep metrics (vbt_tracker_rep_metrics_enable); off: no allocation, and every kernel gets a null pointer for them
+  bool rep_metrics = false;
+  vbt::DevBuf<double> metrics;             // [n_clips][MAXPH][VT_METRICS]: the records of `phases`
+  vbt::DevBuf<double> live_metrics, live_mview;   // what lb.metrics / lb.mview point into (live analysis on too)
 };
 
 namespace vbt {
@@ -43,6 +47,9 @@ int live_after(vbt_tracker* t, hipStream_t st);
 void live_init(vbt_tracker* t);
 // live analysis off, its tables freed
 void live_free(vbt_tracker* t);
+// The live tables' metrics, when both the live analysis and the rep metrics are on and they are not there yet (whichever of the two
+// enables came second calls it).  false: hipMalloc failed, nothing changed.
+bool live_metrics_alloc(vbt_tracker* t);
 
 // What a reader of the live tables outside the tracker's units needs (the overlay's rep panel, overlay.hip): the tables as the
 // tracker's kernels take them.  on == false: live analysis is not enabled and b holds no pointer.
@@ -77,5 +84,9 @@ int check_state_header(const vbt_tracker* t, int clip, const StateHeader& h, int
 
 // n phases of 48 bytes from a packed record into phases6 + c * cap * 6, or VBT_ERR_CAPACITY ("<what> <id>: n phases, buffer holds cap")
 int unpack_phases(const char* what, long long id, const unsigned char* src, int n, double* phases6, size_t c, int cap);
+// the n <= cap metrics records (64 bytes each) that go with them, into metrics8 + c * cap * 8
+inline void unpack_metrics(const unsigned char* src, int n, double* metrics8, size_t c, int cap) {
+  if (n > 0) memcpy(metrics8 + c * cap * VT_METRICS, src, (size_t)n * VT_METRICS * sizeof(double));
+}
 
 }  // namespace vbt

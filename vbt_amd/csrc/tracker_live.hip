@@ -9,6 +9,8 @@ namespace vbt {
 // One wavefront per clip, after every tracker launch, on the tracker launch's stream: consumes rows [cursor, nrows) of the clip's log,
 // whatever number of frames the launch walked.  Lane e owns entry e (lane 0 also entry 64): the rows of one frame carry distinct ids,
 // so the entries advance side by side, each lane applying its id's rows in log order.  Then the leader: export_id() as it stands.
+// M: rep metrics on (b.metrics is there); M = false is the kernel as it is without them.
+template <bool M>
 __global__ __launch_bounds__(64) void live_analyze_kernel(const ClipState* states, const Row* rows, int rows_cap, LiveBufs b, LiveCfg c) {
   __shared__ long long s_keep[LIVE_ENTRIES];   // ids that can still win the export: the live tracks' and the best dead one
   __shared__ long long s_eid[LIVE_ENTRIES];    // entry ids (-1: free)
@@ -65,12 +67,12 @@ __global__ __launch_bounds__(64) void live_analyze_kernel(const ClipState* state
     while (m0) {
       const int j = __ffsll((long long)m0) - 1;
       m0 &= m0 - 1;
-      live_apply(E[lane], R[base + j], b, c, clip, lane);
+      live_apply<M>(E[lane], R[base + j], b, c, clip, lane);
     }
     while (m1) {
       const int j = __ffsll((long long)m1) - 1;
       m1 &= m1 - 1;
-      live_apply(E[64], R[base + j], b, c, clip, 64);
+      live_apply<M>(E[64], R[base + j], b, c, clip, 64);
     }
   }
   s_ver[lane] = my0 >= 0 ? E[lane].s.ver : -1;
@@ -90,8 +92,10 @@ __global__ __launch_bounds__(64) void live_analyze_kernel(const ClipState* state
 }
 
 // vbt_tracker_live_poll: per clip a record { int64 leader; int32 rows_consumed, n_phases, phase_state, overflow; uint64 seq } (=
-// vbt_live_clip) + the leader's phases [cap][6], packed for ONE copy.  A flagged clip reports no phases.
-__global__ __launch_bounds__(64) void live_pack_kernel(LiveBufs b, LiveCfg c, int flush, int cap, unsigned char* out) {
+// vbt_live_clip) + the leader's phases [cap][6], packed for ONE copy.  A flagged clip reports no phases.  mdst != null
+// (vbt_tracker_live_poll_ex; rep metrics enabled, M): the metrics of those phases too, clip c's at mdst + c * cap * VT_METRICS.
+template <bool M>
+__global__ __launch_bounds__(64) void live_pack_kernel(LiveBufs b, LiveCfg c, int flush, int cap, unsigned char* out, double* mdst) {
   __shared__ int s_e, s_n, s_flags;
   const int clip = blockIdx.x, lane = threadIdx.x;
   const LiveClip& L = b.clips[clip];
@@ -105,8 +109,9 @@ __global__ __launch_bounds__(64) void live_pack_kernel(LiveBufs b, LiveCfg c, in
   __syncthreads();
   const int e = s_e;
   double* view = b.view + (size_t)clip * c.phase_cap * 6;
+  double* mview = M ? b.mview + (size_t)clip * c.phase_cap * VT_METRICS : nullptr;
   int n = 0;
-  if (e >= 0) n = live_view(E[e], b, c, clip, e, flush != 0, view, &s_n, &s_flags, lane);
+  if (e >= 0) n = live_view<M>(E[e], b, c, clip, e, flush != 0, view, &s_n, &s_flags, lane, mview);
   else if (lane == 0 && ld >= 0) s_flags |= LIVE_ROWS_LOST;   // the leader's rows are not in the log
   __syncthreads();
   const int flags = s_flags;
@@ -119,6 +124,10 @@ __global__ __launch_bounds__(64) void live_pack_kernel(LiveBufs b, LiveCfg c, in
   }
   double* dst = (double*)(o + 32);
   for (int i = lane; i < min(n, cap) * 6; i += 64) dst[i] = view[i];
+  if (M) {
+    double* md = mdst + (size_t)clip * cap * VT_METRICS;
+    for (int i = lane; i < min(n, cap) * VT_METRICS; i += 64) md[i] = mview[i];
+  }
 }
 
 // vbt_tracker_live_tracks: every entry of one clip, LIVE_ENTRIES records { int64 id; int32 n_rows, n_phases, flags, phase_state;
@@ -149,7 +158,8 @@ __global__ void live_init_kernel(LiveClip* clips, LiveEntry* ents, int n_clips) 
 int live_after(vbt_tracker* t, hipStream_t st) {
   t->stepped = true;
   if (!t->live) return VBT_OK;
-  live_analyze_kernel<<<t->n_clips, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, t->lb, t->lc);
+  if (t->lb.metrics) live_analyze_kernel<true><<<t->n_clips, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, t->lb, t->lc);
+  else live_analyze_kernel<false><<<t->n_clips, 64, 0, st>>>(t->states.get(), t->rows.get(), t->rows_cap, t->lb, t->lc);
   VBT_HIP_CHECK(hipGetLastError());
   return VBT_OK;
 }
@@ -161,8 +171,21 @@ void live_init(vbt_tracker* t) {
 void live_free(vbt_tracker* t) {
   t->live_clips.reset(); t->live_ents.reset(); t->live_paths.reset(); t->live_phases.reset(); t->live_view.reset();
   t->live_poll.reset();
+  t->live_metrics.reset(); t->live_mview.reset();
   t->lb = LiveBufs{};
   t->live = false;
+}
+
+bool live_metrics_alloc(vbt_tracker* t) {
+  if (!t->live || !t->rep_metrics || t->lb.metrics) return true;
+  const size_t n = (size_t)t->n_clips, cells = (size_t)VT_METRICS * t->lc.phase_cap;
+  if (t->live_metrics.alloc(cells * n * LIVE_ENTRIES) != hipSuccess || t->live_mview.alloc(cells * n) != hipSuccess) {
+    t->live_metrics.reset(); t->live_mview.reset();
+    return false;
+  }
+  t->lb.metrics = t->live_metrics.get();
+  t->lb.mview = t->live_mview.get();
+  return true;
 }
 
 }  // namespace vbt
@@ -193,6 +216,13 @@ int vbt_tracker_live_enable(vbt_tracker* t, int path_cap, int phase_cap, double 
   t->lc.p = VtParams{plate_diameter, diff_threshold, min_distance, 1, 0};
   t->lc.path_cap = path_cap;
   t->lc.phase_cap = phase_cap;
+  t->live = true;
+  if (!live_metrics_alloc(t)) {
+    live_free(t);
+    (void)hipGetLastError();
+    set_error("vbt_tracker_live_enable: hipMalloc of the live metrics failed (%d clips, phase_cap %d)", t->n_clips, phase_cap);
+    return VBT_ERR_HIP;
+  }
   live_init(t);
   const hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) { live_free(t); set_error("live init failed: %s", hipGetErrorString(e)); return VBT_ERR_HIP; }
@@ -201,25 +231,40 @@ int vbt_tracker_live_enable(vbt_tracker* t, int path_cap, int phase_cap, double 
 }
 
 // One pack launch on `stream` (after the tracker launches it carries), ONE copy into pinned memory, ONE synchronisation of that stream.
-int vbt_tracker_live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, int cap, void* stream) {
-  if (!t || !clips || cap < 0 || (cap > 0 && !phases6)) { set_error("vbt_tracker_live_poll: bad argument"); return VBT_ERR_ARG; }
-  if (!t->live) { set_error("vbt_tracker_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
+// metrics8 != nullptr (vbt_tracker_live_poll_ex): the block carries, behind the n_clips records, n_clips x pcap metrics records.
+static int live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap, void* stream) {
   static_assert(sizeof(vbt_live_clip) == 32, "vbt_live_clip record");
   VBT_HIP_CHECK(hipSetDevice(t->device));
   const int n = t->n_clips;
   const int pcap = std::min(cap, t->lc.phase_cap);   // a clip never reports more than phase_cap phases
-  const size_t rec = 32 + (size_t)pcap * 48, bytes = rec * n;
+  const size_t rec = 32 + (size_t)pcap * 48, mrec = (size_t)pcap * VT_METRICS * sizeof(double);
+  const size_t bytes = rec * n + (metrics8 ? mrec * n : 0);
   VBT_HIP_CHECK(t->live_poll.reserve(bytes));
   hipStream_t st = (hipStream_t)stream;
-  live_pack_kernel<<<n, 64, 0, st>>>(t->lb, t->lc, flush_view, pcap, t->live_poll.dev());
+  if (metrics8) live_pack_kernel<true><<<n, 64, 0, st>>>(t->lb, t->lc, flush_view, pcap, t->live_poll.dev(), (double*)(t->live_poll.dev() + rec * n));
+  else live_pack_kernel<false><<<n, 64, 0, st>>>(t->lb, t->lc, flush_view, pcap, t->live_poll.dev(), nullptr);
   VBT_HIP_CHECK(hipGetLastError());
   VBT_HIP_CHECK(t->live_poll.fetch(bytes, st));
   for (int c = 0; c < n; c++) {
     const unsigned char* r = t->live_poll.host() + c * rec;
     memcpy(&clips[c], r, sizeof(vbt_live_clip));
     if (int rc = unpack_phases("clip", c, r + 32, clips[c].n_phases, phases6, (size_t)c, cap)) return rc;
+    if (metrics8) unpack_metrics(t->live_poll.host() + rec * n + c * mrec, clips[c].n_phases, metrics8, (size_t)c, cap);
   }
   return VBT_OK;
+}
+
+int vbt_tracker_live_poll(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, int cap, void* stream) {
+  if (!t || !clips || cap < 0 || (cap > 0 && !phases6)) { set_error("vbt_tracker_live_poll: bad argument"); return VBT_ERR_ARG; }
+  if (!t->live) { set_error("vbt_tracker_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
+  return live_poll(t, flush_view, clips, phases6, nullptr, cap, stream);
+}
+
+int vbt_tracker_live_poll_ex(vbt_tracker* t, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap, void* stream) {
+  if (!t || !clips || cap < 0 || (cap > 0 && (!phases6 || !metrics8))) { set_error("vbt_tracker_live_poll_ex: bad argument"); return VBT_ERR_ARG; }
+  if (!t->live) { set_error("vbt_tracker_live_poll_ex: live analysis is not enabled"); return VBT_ERR_STATE; }
+  if (!t->rep_metrics) { set_error("vbt_tracker_live_poll_ex: rep metrics are not enabled (vbt_tracker_rep_metrics_enable)"); return VBT_ERR_STATE; }
+  return live_poll(t, flush_view, clips, phases6, cap > 0 ? metrics8 : nullptr, cap, stream);
 }
 
 int vbt_tracker_live_tracks(vbt_tracker* t, int clip, int flush_view, int64_t* ids, int32_t* n_rows, int32_t* n_phases, int32_t* flags,

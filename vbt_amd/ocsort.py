@@ -27,11 +27,13 @@ def _params(det_thresh, max_age, min_hits, iou_threshold, delta_t, asso_func, in
 
 class MultiClipTracker:
     def __init__(self, n_clips, rows_cap, det_thresh=0.2, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3,
-                 asso_func="iou", inertia=0.2, device=0):
+                 asso_func="iou", inertia=0.2, device=0, rep_metrics=False):
         self.n_clips, self.rows_cap = int(n_clips), int(rows_cap)
         self._h = ctypes.c_void_p()
         p = _params(det_thresh, max_age, min_hits, iou_threshold, delta_t, asso_func, inertia)
         _lib.check(_lib.lib().vbt_tracker_create(self.n_clips, self.rows_cap, ctypes.byref(p), device, ctypes.byref(self._h)))
+        if rep_metrics:
+            self.enable_rep_metrics()
 
     def rows_dev(self, clip):
         """(rows pointer, row counter pointer, rows_cap) of the clip's row log in device memory (vbt_tracker_rows_dev): what
@@ -130,6 +132,36 @@ def _summary(self, cap=64):
 
 MultiClipTracker.summary = _summary
 
+
+# ---- rep metrics (vbt_tracker_rep_metrics_enable, include/vbt_hip.h) ----
+def _enable_rep_metrics(self):
+    """The eight per-phase metrics (velocity.RM_*) next to every phase list: before the first update_frames / after reset."""
+    _lib.check(_lib.lib().vbt_tracker_rep_metrics_enable(self._h))
+    self._rep_metrics = True
+
+
+def _rep_metrics(self, clip=0):
+    """float64 [P, 8] of the clip's exported id after finish(), in the order of phases(clip)"""
+    m = np.empty((512, 8), np.float64)
+    n = ctypes.c_int()
+    _lib.check(_lib.lib().vbt_tracker_rep_metrics(self._h, int(clip), m.ctypes.data, 512, ctypes.byref(n)))
+    return m[:n.value].copy()
+
+
+def _summary_ex(self, cap=64):
+    """summary() + metrics[n, cap, 8], all in the one packed copy"""
+    n = self.n_clips
+    best, rows, nph, ovf = (np.zeros(n, np.int32) for _ in range(4))
+    ph, m = np.zeros((n, cap, 6), np.float64), np.zeros((n, cap, 8), np.float64)
+    _lib.check(_lib.lib().vbt_tracker_summary_ex(self._h, best.ctypes.data, rows.ctypes.data, nph.ctypes.data, ovf.ctypes.data, ph.ctypes.data,
+                                                 m.ctypes.data, cap))
+    return best, rows, nph, ovf, ph, m
+
+
+MultiClipTracker.enable_rep_metrics = _enable_rep_metrics
+MultiClipTracker.rep_metrics = _rep_metrics
+MultiClipTracker.summary_ex = _summary_ex
+
 ROW_DTYPE = np.dtype([("id", "<i8"), ("time", "<f8"), ("x", "<f8"), ("y", "<f8"), ("dx", "<f8"), ("dy", "<f8"),
                       ("norm_plate_height", "<f8"), ("norm_plate_width", "<f8")])       # the 8 columns of reference track.py:227-234
 
@@ -174,6 +206,14 @@ def _live_records(recs, ph):
             for i, r in enumerate(recs)]
 
 
+# LiveClip + metrics: float64 [n_phases, 8] of the leader's phases (velocity.RM_* columns); what a poll gives with rep metrics enabled
+LiveClipMetrics = collections.namedtuple("LiveClipMetrics", LiveClip._fields + ("metrics",))
+
+
+def _live_records_ex(recs, ph, m):
+    return [LiveClipMetrics(*r, m[i, :len(r.phases)].copy()) for i, r in enumerate(_live_records(recs, ph))]
+
+
 def _enable_live(self, path_cap=LIVE_PATH_CAP, phase_cap=LIVE_PHASE_CAP, plate_diameter=0.45, diff_threshold=0.6, min_distance=0.1):
     """Live rep analysis (before the first update_frames / after reset): every id that can still win the export keeps a VelocityTracker
     fed with its rows as they are emitted.  path_cap: samples of one open phase; phase_cap: phases of one id."""
@@ -187,6 +227,10 @@ def _live(self, flush_view=False, stream=None):
     n, cap = self.n_clips, getattr(self, "_live_phase_cap", LIVE_PHASE_CAP)
     recs = (_lib.LiveClip * n)()
     ph = np.zeros((n, cap, 6), np.float64)
+    if getattr(self, "_rep_metrics", False):
+        m = np.zeros((n, cap, 8), np.float64)
+        _lib.check(_lib.lib().vbt_tracker_live_poll_ex(self._h, int(bool(flush_view)), recs, ph.ctypes.data, m.ctypes.data, cap, stream))
+        return _live_records_ex(recs, ph, m)
     _lib.check(_lib.lib().vbt_tracker_live_poll(self._h, int(bool(flush_view)), recs, ph.ctypes.data, cap, stream))
     return _live_records(recs, ph)
 

@@ -85,7 +85,8 @@ def track_frames(frames, model_path, fps=30.0, detection_treshold=0.5, frame_str
     rows coming back.  frames: uint8 [T,H,W,3] RGB (numpy array or memmap; any resolution - resized on the GPU like
     odt.py:10-19).  frame_stride = the `frame_count % 16` of track.py:166: frames whose 1-based number is not a multiple are
     read and dropped, they only advance the clip time.  Returns the reference's dict of lists (track.py:144-145).
-    live: optional callable(ocsort.LiveClip, final) - live rep analysis on: called after every batch with the clip's record, and
+    live: optional callable(ocsort.LiveClip, final) - live rep analysis on (a callable with a true attribute `rep_metrics` gets
+    ocsort.LiveClipMetrics records, whose .metrics holds the rep metrics of the phases): called after every batch with the clip's record, and
     once more after the last one with the flush view (final=True: the phases the clip close gives).
     pix_fmt "nv12" / "i420": frames is uint8 [T, H*3//2, W], YUV 4:2:0 as a decoder emits it (rawvideo.py); converted and resized
     on the GPU.  src_hw=(H, W) is then optional (the shape gives it).  "yuyv422" / "uyvy422": uint8 [T, H, 2W], packed 4:2:2;
@@ -155,7 +156,7 @@ def _track_frames(frames, model_path, fps, detection_treshold, frame_stride, tim
     hud_live = None if hud_live is None else dict(hud_live)
     plate = {} if hud_live is None else dict(plate_diameter=float(hud_live.pop("plate_diameter", 0.45)))   # the live analysis uses the pipeline's
     pipe = Pipeline(model_path, F, max_frames=max(kept, 1), fps=fps, detection_treshold=detection_treshold, device=device,
-                    rows_per_frame=25, tracker_clips=1, tracker=tracker, **plate)
+                    rows_per_frame=25, tracker_clips=1, tracker=tracker, rep_metrics=bool(getattr(live, "rep_metrics", False)), **plate)
     size = pipe._size
     pipe.set_pixel_format(pix_fmt)
     pipe.set_colour(color_matrix, color_range)
@@ -371,9 +372,11 @@ class Pipeline:
     convenience for callers who hold them - torch tensors (device or pinned host).  torch is never imported here."""
 
     def __init__(self, model_path, n_clips, max_frames, fps=60.0, detection_treshold=0.5, device=0, rows_per_frame=4,
-                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False, group=None, tracker="ocsort", id_base=0):
+                 plate_diameter=0.45, depth=None, tracker_clips=None, slot_close=False, group=None, tracker="ocsort", id_base=0,
+                 rep_metrics=False):
         """tracker: "ocsort" = OCSort(max_age=30, asso_func="diou", iou_threshold=0.1) (track.py:157), "sort" = SortTracker(max_age=30)
-        (track.py:156; vbt_pipeline_use_sort) whose ids start at id_base + 1 in every clip."""
+        (track.py:156; vbt_pipeline_use_sort) whose ids start at id_base + 1 in every clip.  rep_metrics: the eight per-phase metrics
+        (velocity.RM_*) next to every phase list - close_ex(), closed_ex(), and the .metrics of live()'s records."""
         L = _lib.lib()
         self.tracker_name = _tracker_name(tracker)
         self.n = int(n_clips)                       # slots of the detector batch
@@ -411,6 +414,9 @@ class Pipeline:
             _lib.check(L.vbt_pipeline_use_sort(self._h, ctypes.byref(sort_params(max_age=MAX_AGE, id_base=id_base))))
         if slot_close:                              # close_clips() / closed(): their buffers now, so that no close allocates
             _lib.check(L.vbt_pipeline_close_clips_enable(self._h))
+        self.rep_metrics = bool(rep_metrics)
+        if self.rep_metrics:
+            _lib.check(L.vbt_pipeline_rep_metrics_enable(self._h))
         info = self.info()
         self.depth, self._ring, self._defer, self._trk_inline = info.depth, info.ring, info.defer, bool(info.tracker_inline)
         self._size = info.image_size
@@ -421,6 +427,7 @@ class Pipeline:
         self.interpreters = [Interpreter._borrowed(L.vbt_pipeline_model(self._h, k), model_path, device, self.n, self._owner) for k in range(self.depth)]
         self.interpreter = self.interpreters[0]
         self.tracker = MultiClipTracker._borrowed(L.vbt_pipeline_tracker(self._h), self.n_trk, prm.rows_cap, self._owner)
+        self.tracker._rep_metrics = self.rep_metrics
         self._step_idx = 0                          # steps enqueued so far (mirror of the library's counter: which stream a step runs on)
         self._keep = collections.deque(maxlen=2 * self._ring + 4)   # host sources / foreign device arrays of the steps in flight
         self._ext = {}                              # torch.cuda.ExternalStream views of the detector streams (record_stream)
@@ -681,6 +688,11 @@ class Pipeline:
         n, cap = self.n_trk, getattr(self.tracker, "_live_phase_cap", LIVE_PHASE_CAP)
         recs = (_lib.LiveClip * n)()
         ph = np.zeros((n, cap, 6), np.float64)
+        if self.rep_metrics:                        # records with .metrics: float64 [n_phases, 8] of the leader's phases
+            from .ocsort import _live_records_ex
+            m = np.zeros((n, cap, 8), np.float64)
+            _lib.check(_lib.lib().vbt_pipeline_live_poll_ex(self._h, int(bool(flush_view)), recs, ph.ctypes.data, m.ctypes.data, cap))
+            return _live_records_ex(recs, ph, m)
         _lib.check(_lib.lib().vbt_pipeline_live_poll(self._h, int(bool(flush_view)), recs, ph.ctypes.data, cap))
         return _live_records(recs, ph)
 
@@ -711,6 +723,15 @@ class Pipeline:
         _lib.check(_lib.lib().vbt_pipeline_close(self._h, best.ctypes.data, rows.ctypes.data, nph.ctypes.data, ovf.ctypes.data, ph.ctypes.data, int(cap)))
         return best, rows, nph, ovf, ph
 
+    def close_ex(self, cap=32):
+        """close() + metrics[n, cap, 8] (a pipeline created with rep_metrics=True), all in the one packed copy"""
+        n = self.n_trk
+        best, rows, nph, ovf = (np.zeros(n, np.int32) for _ in range(4))
+        ph, m = np.zeros((n, cap, 6), np.float64), np.zeros((n, cap, 8), np.float64)
+        _lib.check(_lib.lib().vbt_pipeline_close_ex(self._h, best.ctypes.data, rows.ctypes.data, nph.ctypes.data, ovf.ctypes.data, ph.ctypes.data,
+                                                    m.ctypes.data, int(cap)))
+        return best, rows, nph, ovf, ph, m
+
     def close_clips(self, clips, next_fps=None):
         """Slot close (a pipeline created with slot_close=True): the listed tracker slots' clips end while the others keep running, and
         each slot starts a fresh clip (fps next_fps - one value or one per slot - or the slot's current one).  Only enqueues
@@ -727,20 +748,34 @@ class Pipeline:
         """The result of slot `clip`'s last close_clips(): None while the device has not done it (wait=False), else
         (best_id, rows, phases, overflow) - the export id of reference track.py:107-115, the clip's rows as rows() gives them, its
         list[velocity.Phase] (plot.py:33-47) and the tracker's overflow flags; export_dataframe() takes the rows as they are."""
+        return self._closed(clip, wait, False)
+
+    def closed_ex(self, clip, wait=True):
+        """closed() + the phases' metrics, float64 [P, 8] (a pipeline created with rep_metrics=True): (best_id, rows, phases, overflow,
+        metrics)"""
+        return self._closed(clip, wait, True)
+
+    def _closed(self, clip, wait, metrics):
         from .ocsort import _phase_list
         rec = _lib.ClosedClip()
         ready = ctypes.c_int()
         ph = np.zeros((512, 6), np.float64)
         rows = np.empty(self.tracker.rows_cap, ROW_DTYPE)
-        _lib.check(_lib.lib().vbt_pipeline_closed_clip(self._h, int(clip), int(bool(wait)), ctypes.byref(ready), ctypes.byref(rec), ph.ctypes.data,
-                                                       len(ph), rows.ctypes.data, len(rows)))
+        if metrics:
+            m = np.zeros((512, 8), np.float64)
+            _lib.check(_lib.lib().vbt_pipeline_closed_clip_ex(self._h, int(clip), int(bool(wait)), ctypes.byref(ready), ctypes.byref(rec),
+                                                              ph.ctypes.data, m.ctypes.data, len(ph), rows.ctypes.data, len(rows)))
+        else:
+            _lib.check(_lib.lib().vbt_pipeline_closed_clip(self._h, int(clip), int(bool(wait)), ctypes.byref(ready), ctypes.byref(rec), ph.ctypes.data,
+                                                           len(ph), rows.ctypes.data, len(rows)))
         if not ready.value:
             return None
         r = rows[:rec.n_rows]
         d = {"id": r["id"].tolist()}
         for nm in COLUMNS[1:]:
             d[nm] = r[nm].tolist()
-        return int(rec.best_id), d, _phase_list(ph[:rec.n_phases]), int(rec.overflow)
+        out = (int(rec.best_id), d, _phase_list(ph[:rec.n_phases]), int(rec.overflow))
+        return out + (m[:rec.n_phases].copy(),) if metrics else out
 
     def rows_all(self, cap=None, out=None):
         """DataFrame rows of every clip, one strided copy (after close() / finish()): (counts[n], rows[n, cap] of ROW_DTYPE).  `out`:
