@@ -464,7 +464,7 @@ def test_sixty_four_clips_without_torch(model_path, tmp_path):
 @pytest.mark.parametrize("H,W", [(1280, 96), (960, 333), (700, 64), (1000, 41), (641, 80)])
 def test_host_frames_at_source_resolution_upload_only_the_rows_the_resize_reads(oracle_lib, model_path, H, W):
     """N2 from host memory (the reference's situation: cap.read() hands over 1080 x 1920 frames, track.py:160): when the source holds more
-    than twice the network's rows, only the row pairs the bilinear resize of odt.py:15-16 reads are uploaded (vbt_amd/csrc/pipeline.hip:
+    than twice the network's rows, only the row pairs the bilinear resize of odt.py:15-16 reads are uploaded (vbt_amd/csrc/upload_plan.h:
     one strided copy for integer scales - 1280 = 4 x 320, 960 = 3 x 320 where the two rows of a pair coincide -, a row table otherwise) and the
     resize kernel indexes the compact buffer.  Detections == oracle preprocess + oracle detector, through step() and through step_runs() with
     one host source per run; the uploaded byte count is the compact one."""

@@ -235,7 +235,7 @@ VARIANTS = [("yuyv422", "bt601", "limited"), ("uyvy422", "bt709", "limited"), ("
 @pytest.mark.parametrize("fmt,matrix,rng", VARIANTS, ids=["-".join(v) for v in VARIANTS])
 def test_pipeline_clip_equals_decoded_rgb_clip(model_path, fmt, matrix, rng, compact):
     """A clip of a new format (or of nv12 under bt709 / full) gives the detections, rows and phases of the RGB clip decoded from it,
-    host-fed and device-resident, and uploads the bytes its layout implies.  compact_rows (pipeline.hip) uploads row pairs when
+    host-fed and device-resident, and uploads the bytes its layout implies.  compact_rows (pipeline_ingest.hip) uploads row pairs when
     2 * 320 < H: 642 rows is the smallest such even height (643 for 4:2:2, which takes odd heights), 640 the largest that uploads whole
     frames.  322 columns keep the clip close to the synthetic one (the detector finds its plates) and make the frames of 642 and 643
     rows no multiple of 16 bytes: device-resident runs are then assembled by one copy per run, those of 640 rows by the gather kernel."""

@@ -13,6 +13,7 @@
 #include "../../include/vbt_hip.h"
 #include "../../include/vbt_hip_diag.h"
 #include "container_parse.h"
+#include "upload_plan.h"   // PixLayout, pix_layout, the pix_fmt_* predicates; the compact layout
 
 namespace vbt {
 
@@ -51,47 +52,21 @@ bool lds_opt_in(const void* fn, LdsOptIn* state);
     }                                                                                    \
   } while (0)
 
-// preprocess_image (reference odt.py:10-19) on device memory (frames.hip, with its kernel); compact != 0: src holds only the row pairs the resize reads
+// a call that returns a VBT_* code and has set the error text (the pipeline's units)
+#define PL_CHECK(expr)            \
+  do {                            \
+    const int rc_ = (expr);       \
+    if (rc_ != VBT_OK) return rc_; \
+  } while (0)
+
+// preprocess_image (reference odt.py:10-19) on device memory (frames.hip, with its kernel); compact != 0: src holds only the row pairs the
+// resize reads (the compact layout, upload_plan.h)
 int resize_frames_dev(const uint8_t* src_dev, int B, int H, int W, uint8_t* dst_dev, int h, int w, int swap_rb, int compact, hipStream_t st);
 // the same for VBT_PIX_NV12 / VBT_PIX_I420 sources, conversion fused (yuv_kernels.h): frame b at src_dev + b * frame_stride, its chroma
 // plane(s) at chroma_off; compact != 0: the luma part holds only the row pairs.  Whole frames: frame_stride H*W*3/2, chroma_off H*W.
-inline bool pix_fmt_is_yuv(int pix_fmt) { return pix_fmt == VBT_PIX_NV12 || pix_fmt == VBT_PIX_I420; }
 int resize_frames_yuv_dev(const uint8_t* src_dev, int B, int H, int W, int pix_fmt, size_t frame_stride, size_t chroma_off, int compact,
                           uint8_t* dst_dev, int h, int w, hipStream_t st);
 
-// Every YUV format the ingest takes (include/vbt_hip.h, "more source formats"); pix_fmt_is_yuv above stays the 4:2:0 pair that the
-// export handles (overlay, scaler, mjpeg) know.
-inline bool pix_fmt_is_422(int pix_fmt) { return pix_fmt == VBT_PIX_YUYV422 || pix_fmt == VBT_PIX_UYVY422; }
-inline bool pix_fmt_is_source_yuv(int pix_fmt) { return pix_fmt_is_yuv(pix_fmt) || pix_fmt_is_422(pix_fmt) || pix_fmt == VBT_PIX_P010; }
-// The one place that knows how a source frame of H x W pixels lies in memory: H rows of `row` bytes (packed pixels, or the luma plane),
-// then - chroma_plane - H/2 rows of chroma in as many bytes per row.  ok: the layout is defined - the format is known, H and W are
-// positive and as even as the format's chroma needs.  It says nothing about an upper limit: that is pix_fmt_takes below.
-struct PixLayout {
-  bool ok, chroma_plane;
-  size_t row, frame_bytes;
-};
-inline PixLayout pix_layout(int pix_fmt, int H, int W) {
-  PixLayout l{false, false, 0, 0};
-  if (H < 1 || W < 1) return l;
-  const bool even = !(H & 1) && !(W & 1);
-  switch (pix_fmt) {
-    case VBT_PIX_RGB24: l.ok = true; l.row = (size_t)W * 3; break;
-    case VBT_PIX_NV12:
-    case VBT_PIX_I420: l.ok = even; l.chroma_plane = true; l.row = (size_t)W; break;
-    case VBT_PIX_YUYV422:
-    case VBT_PIX_UYVY422: l.ok = !(W & 1); l.row = (size_t)W * 2; break;
-    case VBT_PIX_P010: l.ok = even; l.chroma_plane = true; l.row = (size_t)W * 2; break;
-    default: return l;
-  }
-  l.frame_bytes = l.chroma_plane ? (size_t)H * l.row * 3 / 2 : (size_t)H * l.row;
-  return l;
-}
-// Does the format take frames of this size?  The layout must be defined; the 4:2:2 formats and P010 take no side above 16384.  RGB24,
-// NV12 and I420 sources of the pipeline have never had an upper limit and keep none.
-inline bool pix_fmt_takes(int pix_fmt, int H, int W) {
-  const bool limited = pix_fmt_is_422(pix_fmt) || pix_fmt == VBT_PIX_P010;
-  return pix_layout(pix_fmt, H, W).ok && (!limited || (H <= 16384 && W <= 16384));
-}
 // The colour description as the conversion kernels take it (yuv_kernels.h): by value, uniform across the launch
 struct YuvColour { int cy, crv, cgu, cgv, cbu, yoff, coff; };
 // the table of include/vbt_hip.h; false: an unknown format, matrix or range

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
   int x0 = max((int)fx, 0), x1 = min((int)ceilf(ix), W - 1);
   float ly = iy - fy, lx = ix - fx;
   // compact: the source holds only the row pairs the resize reads, [B][2h][W][3]: pair oy = source rows p, p + 1 with p = min(y0, H - 2)
-  // (the host-fed pipeline uploads nothing else, pipeline.hip); y0 and y1 then become rows 2 oy + (y - p)
+  // (the host-fed pipeline uploads nothing else: the compact layout, upload_plan.h); y0 and y1 then become rows 2 oy + (y - p)
   const uint8_t* s = src + b * (long)(compact ? 2 * h : H) * W * 3;
   if (compact) {
     const int p = min(y0, H - 2);

@@ -1,32 +1,29 @@
 // vbt_pipeline: the clip loop of reference track.py:129-260 as one object behind the C ABI (include/vbt_hip.h, "pipeline").
 //
 // Host code only - every kernel it enqueues is reached through the library's own entry points (vbt_detect_async,
-// vbt_tracker_update_from_*, vbt_resize_frames, vbt_gather_frames; the slot close through tracker_close_clips, common.h).  What lives here is the part of the fast path that is not a
-// kernel: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
-// events that order detector(t) -> tracker(t) -> slot reuse, the staging ring of the host-fed mode, the deferred tracker groups of
-// the small-batch path and the step groups of the large-batch path (one forward of G x n images behind G step calls) as one held-back
-// block, clip close.  The stream pool is stream_pool.h, the run lists of a block's walk walk_runs.h.  Every device buffer, pinned buffer and event is held by an owner
-// (dev_mem.h, hip_handles.h) and goes with the handle; the streams are borrowed from the pool.  No framework allocator, no framework streams.
+// vbt_tracker_update_from_*; the slot close through tracker_close_clips, common.h).  What lives here is the scheduling part of the fast
+// path: which stream a forward runs on and that the busy streams sit on distinct hardware queues, the ring of output slots and the
+// events that order detector(t) -> tracker(t) -> slot reuse, the deferred tracker groups of the small-batch path and the step groups of
+// the large-batch path (one forward of G x n images behind G step calls) as one held-back block, clip close.  How a step's frames get
+// to the network resolution - the staging ring of the host-fed mode, the upload, the pixel formats, the resize - is the Ingest object
+// of pipeline_ingest.h, which this unit only hands the step's sources to; the stream pool is stream_pool.h, the run lists of a block's
+// walk walk_runs.h.  Every device buffer, pinned buffer and event is held by an owner (dev_mem.h, hip_handles.h) and goes with the
+// handle; the streams are borrowed from the pool.  No framework allocator, no framework streams.
 #include <algorithm>
 #include <chrono>
 
 #include "common.h"
 #include "dev_mem.h"
 #include "hip_handles.h"
+#include "pipeline_ingest.h"
 #include "stream_pool.h"
 #include "walk_runs.h"
-
-// (resize_frames_dev, common.h: preprocess_image reading either whole source frames [B][H][W][3] or, compact != 0, only the row pairs the
-//  bilinear resize touches: [B][2h][W][3], pair d = source rows p(d), p(d) + 1 with p(d) = min(floor(src_y(d)), H - 2);
-//  resize_frames_pix_dev: the same with the conversion of a YUV format fused - NV12 / I420 / P010 with the chroma plane behind the luma
-//  row pairs, packed 4:2:2 as [B][2h][2W] -, vbt_pipeline_set_pixel_format and vbt_pipeline_set_colour; pix_layout, common.h, is the
-//  one place that knows a format's row and frame bytes)
 
 using namespace vbt;
 
 struct vbt_pipeline {
   vbt_pipeline_params prm{};
-  int n = 0, n_trk = 0, depth = 0, ring = 0, defer = 0, device = 0, size = 0;
+  int n = 0, n_trk = 0, depth = 0, ring = 0, defer = 0, device = 0;
   bool trk_inline = false, placement_ok = true;
   bool live = false;               // vbt_pipeline_live_enable succeeded
   bool rep_metrics = false;        // vbt_pipeline_rep_metrics_enable succeeded
@@ -56,30 +53,18 @@ struct vbt_pipeline {
   std::vector<std::vector<WalkFrame>> walk_per;   // scratch of flush_block: per tracker clip its frames in the block
   std::vector<size_t> walk_cur;
   std::vector<vbt_run> walk_runs;
-  hipStream_t det_streams[8] = {nullptr}, copy_stream = nullptr, trk_stream = nullptr;
-  std::vector<Event> ev_in, ev_det, ev_trk;
+  hipStream_t det_streams[8] = {nullptr}, trk_stream = nullptr;
+  std::vector<Event> ev_det, ev_trk;
   std::vector<int> trk_ev_of;      // ring slot -> index into ev_trk of the tracker launch that read it last (-1: none)
   int last_trk = -1;               // index into ev_trk of the most recent tracker launch
-  struct Stage {
-    DevBuf<uint8_t> buf;
-    size_t bytes = 0;              // (0 whenever buf is empty)
-    Event free_ev, copy_ev;
-    bool free_set = false;
-  };
-  std::vector<Stage> stage;
-  int stage_idx = 0;
-  std::vector<DevBuf<uint8_t>> resized;
+  Ingest ingest;                   // frames in: staging ring, copy stream, pixel format, resize (pipeline_ingest.h)
   std::vector<int64_t> clip_frames;
-  std::vector<int> row_table;      // p(d) of the compact upload, for (row_H, row_h)
-  int row_H = 0, row_h = 0;
   int frame_count = 0, step_idx = 0, last_B = 0;
   bool ever_stepped = false;       // a step was enqueued on this handle (not cleared by a reset): vbt_pipeline_use_sort comes too late
   int G = 1;                      // steps per forward (vbt_pipeline_params.group)
   int next_o = 0, fwd_idx = 0;     // G > 1: ring slot of the next forward's first step (a block never wraps); forwards opened since creation / reset
   int last_o = 0, last_k = 0;      // ring slot / forward slot of the most recent step
-  int pix_fmt = VBT_PIX_RGB24;     // vbt_pipeline_set_pixel_format
-  int cs_matrix = VBT_CS_BT601, cs_range = VBT_RANGE_LIMITED;   // vbt_pipeline_set_colour
-  uint64_t h2d_bytes = 0, step_host_ns = 0, step_calls = 0;
+  uint64_t step_host_ns = 0, step_calls = 0;
   // slot close (vbt_pipeline_close_clips): per tracker clip its record (pinned, CLOSED_HEAD_BYTES), its rows (device, rows_cap rows) and
   // the event of its close; allocated by vbt_pipeline_close_clips_enable.  fc_base: frame_count when the slot last reopened (plain steps count from it)
   PinnedBuf<unsigned char> closed_head;
@@ -122,6 +107,16 @@ int record_trk(vbt_pipeline* p, int o, hipStream_t T) {
   VBT_HIP_CHECK(hipEventRecord(p->ev_trk[o].get(), T));
   p->trk_ev_of[o] = o;
   p->last_trk = o;
+  return VBT_OK;
+}
+
+// Work enqueued on the tracker stream T outside a step (the slot close with its reset, the update of a live panel) becomes the most
+// recent tracker launch: the event of the last launch is recorded again behind it, so every later tracker launch - each waits for
+// ev_trk[last_trk], or runs on the tracker stream itself - and whoever else waits for that event comes after it.
+int rerecord_trk(vbt_pipeline* p, hipStream_t T) {
+  const int e = p->last_trk >= 0 ? p->last_trk : 0;
+  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e].get(), T));
+  p->last_trk = e;
   return VBT_OK;
 }
 
@@ -285,258 +280,11 @@ int drain(vbt_pipeline* p) {
   return VBT_OK;
 }
 
-// ---- staging ring of the host-fed / gathered input ----
-// Before an H2D copy into staging buffer j is enqueued the forward that last read the buffer must be done.  The wait is on the
-// HOST (the event is depth + 2 steps old: it has completed unless the caller is that many steps ahead of the GPU, and then blocking
-// the caller is the back-pressure wanted), NOT a stream wait on the copy stream: a cross-stream event wait in front of a DMA copy
-// makes hipMemcpyAsync itself block the calling thread on this stack (profiles/r04_h2d_pinned_order.md).
-int stage_take(vbt_pipeline* p, size_t bytes, bool host_gate, hipStream_t S, int* j_out) {
-  const int j = p->stage_idx % (int)p->stage.size();
-  p->stage_idx++;
-  vbt_pipeline::Stage& st = p->stage[j];
-  if (st.bytes < bytes) {
-    // a buffer that has to be replaced may still be read by a forward or written by a copy in flight (up to depth + 2 steps)
-    if (st.buf) {
-      if (st.free_set) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev.get()));
-      VBT_HIP_CHECK(hipEventSynchronize(st.copy_ev.get()));
-      st.free_set = false;
-    }
-    st.bytes = 0;
-    VBT_HIP_CHECK(st.buf.alloc(bytes + 64));   // (frees the old buffer first)
-    st.bytes = bytes;
-  }
-  if (st.free_set) {
-    if (host_gate) VBT_HIP_CHECK(hipEventSynchronize(st.free_ev.get()));
-    else VBT_HIP_CHECK(hipStreamWaitEvent(S, st.free_ev.get(), 0));
-  }
-  *j_out = j;
-  return VBT_OK;
-}
-
-// p(d): first source row of the pair output row d reads, in the resize kernel's own float32 arithmetic
-const std::vector<int>& row_table(vbt_pipeline* p, int H, int h) {
-  if (p->row_H != H || p->row_h != h) {
-    p->row_table.resize((size_t)h);
-    const float sy = (float)H / (float)h;
-    for (int d = 0; d < h; d++) {
-      const float iy = ((float)d + 0.5f) * sy - 0.5f;
-      const int y0 = std::max((int)floorf(iy), 0);
-      p->row_table[d] = std::min(y0, H - 2);
-    }
-    p->row_H = H;
-    p->row_h = h;
-  }
-  return p->row_table;
-}
-
-inline bool compact_rows(const vbt_pipeline* p, int H, int W) {
-  // the resize reads two source rows per output row (tf.image.resize bilinear without antialias, odt.py:15-16): when the source holds
-  // more than twice as many rows, only those are uploaded
-  static const bool off = getenv("VBT_NO_ROW_UPLOAD") != nullptr;
-  return !off && H > 0 && W > 0 && H >= 2 && 2 * p->size < H;
-}
-
-// nf host frames of H packed rows of `row` bytes (RGB24: 3W, 4:2:2: 2W) -> staging buffer (frame slot0 onwards) on the copy stream;
-// compact: only the row pairs
-int h2d_frames(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, size_t row, bool compact) {
-  hipStream_t C = p->copy_stream;
-  if (!compact) {
-    const size_t fb = (size_t)H * row;
-    VBT_HIP_CHECK(hipMemcpyAsync(stage_buf + (size_t)slot0 * fb, host, (size_t)nf * fb, hipMemcpyHostToDevice, C));
-    p->h2d_bytes += (uint64_t)nf * fb;
-    return VBT_OK;
-  }
-  const int h = p->size;
-  const std::vector<int>& tab = row_table(p, H, h);
-  uint8_t* dst = stage_buf + (size_t)slot0 * 2 * h * row;
-  const int step = h > 1 ? tab[1] - tab[0] : 0;
-  bool uniform = h > 1;
-  for (int d = 1; d < h && uniform; d++) uniform = tab[d] - tab[d - 1] == step;
-  if (uniform && (long)step * h == H) {
-    // integer scale: the pairs sit at one pitch across the whole batch - ONE strided copy
-    VBT_HIP_CHECK(hipMemcpy2DAsync(dst, 2 * row, host + (size_t)tab[0] * row, (size_t)step * row, 2 * row, (size_t)nf * h, hipMemcpyHostToDevice, C));
-  } else if (uniform) {
-    for (int b = 0; b < nf; b++)
-      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)b * 2 * h * row, 2 * row, host + ((size_t)b * H + tab[0]) * row, (size_t)step * row, 2 * row, (size_t)h,
-                                     hipMemcpyHostToDevice, C));
-  } else {
-    // a row table: pair d of every frame in one strided copy (pitch = one source frame / one compact frame)
-    for (int d = 0; d < h; d++)
-      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)d * 2 * row, (size_t)2 * h * row, host + (size_t)tab[d] * row, (size_t)H * row, 2 * row, (size_t)nf,
-                                     hipMemcpyHostToDevice, C));
-  }
-  p->h2d_bytes += (uint64_t)nf * 2 * h * row;
-  return VBT_OK;
-}
-
-// Compact upload of a frame with a chroma plane (NV12 / I420: W = row bytes; P010: W = 2 x width; H rows, network size h): the luma row pairs 0..h-2, [2 (h - 1)][W], then the
-// source frame from luma row p(h - 1) to its end as it is - the last pair, the luma rows below it (none or a few) and the whole chroma
-// plane(s).  The tail is one contiguous piece of the source, so the chroma costs no copy call of its own.
-struct YuvCompact {
-  size_t tail_src, tail_bytes, chroma_off, frame_bytes;   // tail: offset in the source frame / length; chroma_off, frame_bytes: of the compact frame
-};
-YuvCompact yuv_compact(vbt_pipeline* p, int H, size_t W) {
-  const int h = p->size, p_last = row_table(p, H, h)[(size_t)h - 1];
-  YuvCompact c;
-  c.tail_src = (size_t)p_last * W;
-  c.tail_bytes = (size_t)H * W * 3 / 2 - c.tail_src;
-  c.chroma_off = (size_t)2 * (h - 1) * W + (size_t)(H - p_last) * W;
-  c.frame_bytes = (size_t)2 * (h - 1) * W + c.tail_bytes;
-  return c;
-}
-
-// nf host frames of H*row*3/2 bytes -> staging buffer (frame slot0 onwards) on the copy stream; compact: the layout of yuv_compact
-int h2d_frames_yuv(vbt_pipeline* p, uint8_t* stage_buf, int slot0, const uint8_t* host, int nf, int H, size_t row, bool compact) {
-  hipStream_t C = p->copy_stream;
-  const size_t fb = (size_t)H * row * 3 / 2;
-  if (!compact) {
-    VBT_HIP_CHECK(hipMemcpyAsync(stage_buf + (size_t)slot0 * fb, host, (size_t)nf * fb, hipMemcpyHostToDevice, C));
-    p->h2d_bytes += (uint64_t)nf * fb;
-    return VBT_OK;
-  }
-  const int h = p->size;
-  const std::vector<int>& tab = row_table(p, H, h);
-  const YuvCompact cl = yuv_compact(p, H, row);
-  uint8_t* dst = stage_buf + (size_t)slot0 * cl.frame_bytes;
-  const int step = h > 1 ? tab[1] - tab[0] : 0;
-  bool uniform = h > 2;
-  for (int d = 1; d < h - 1 && uniform; d++) uniform = tab[d] - tab[d - 1] == step;
-  if (uniform && nf < h - 1) {
-    // pairs 0..h-2 sit at one pitch inside a frame: one strided copy per frame (the chroma between the frames breaks the pitch)
-    for (int b = 0; b < nf; b++)
-      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)b * cl.frame_bytes, 2 * row, host + (size_t)b * fb + (size_t)tab[0] * row, (size_t)step * row, 2 * row,
-                                     (size_t)(h - 1), hipMemcpyHostToDevice, C));
-  } else {
-    // pair d of every frame in one strided copy (pitch = one source frame / one compact frame)
-    for (int d = 0; d < h - 1; d++)
-      VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)d * 2 * row, cl.frame_bytes, host + (size_t)tab[d] * row, fb, 2 * row, (size_t)nf, hipMemcpyHostToDevice, C));
-  }
-  // the tails of all frames: one strided copy
-  VBT_HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)2 * (h - 1) * row, cl.frame_bytes, host + cl.tail_src, fb, cl.tail_bytes, (size_t)nf, hipMemcpyHostToDevice, C));
-  p->h2d_bytes += (uint64_t)nf * cl.frame_bytes;
-  return VBT_OK;
-}
-
-int ensure_resized(vbt_pipeline* p, int k) {
-  if (!p->resized[k]) VBT_HIP_CHECK(p->resized[k].alloc((size_t)p->n * p->size * p->size * 3 + 64));
-  return VBT_OK;
-}
-
-struct Sources {
-  const uint8_t* frames;              // assembled batch, or
-  const uint8_t* const* run_sources;  // one source per run
-  bool on_device;
-  int src_h, src_w, swap_rb;
-  Sources(const uint8_t* frames_, const uint8_t* const* run_sources_, int frames_on_device, int src_h_, int src_w_, int swap_rb_)
-      : frames(frames_), run_sources(run_sources_), on_device(frames_on_device != 0), src_h(src_h_), src_w(src_w_), swap_rb(swap_rb_) {}
-};
-
-// What a step may ask for under the pipeline's pixel format; checked before anything is enqueued or counted.
-// frames / run_sources[0..n_sources): the step's sources where they are device pointers (else NULL / 0), for the alignment the 4:2:2
-// and P010 kernels need.
-int check_source_format(const vbt_pipeline* p, const char* fn, int src_h, int src_w, int swap_rb, const uint8_t* frames = nullptr,
-                        const uint8_t* const* run_sources = nullptr, int n_sources = 0) {
-  if ((src_h > 0) != (src_w > 0)) { set_error("%s: src_h and src_w come together", fn); return VBT_ERR_ARG; }
-  if (!pix_fmt_is_source_yuv(p->pix_fmt)) return VBT_OK;
-  if (pix_fmt_is_yuv(p->pix_fmt)) {
-    if (src_h <= 0 || src_w <= 0 || (src_h & 1) || (src_w & 1)) {
-      set_error("%s: YUV 4:2:0 frames need src_h and src_w, > 0 and even, got %d x %d", fn, src_h, src_w);
-      return VBT_ERR_ARG;
-    }
-  } else if (!pix_fmt_takes(p->pix_fmt, src_h, src_w)) {
-    set_error("%s: %s frames need src_h and src_w in 1..16384, src_w even%s, got %d x %d", fn, pix_fmt_is_422(p->pix_fmt) ? "YUV 4:2:2" : "P010",
-              pix_fmt_is_422(p->pix_fmt) ? "" : " and src_h even", src_h, src_w);
-    return VBT_ERR_ARG;
-  }
-  if (swap_rb) { set_error("%s: swap_rb does not apply to YUV frames", fn); return VBT_ERR_ARG; }
-  if (!pix_fmt_is_yuv(p->pix_fmt)) {
-    bool aligned = ((uintptr_t)frames & 3) == 0;
-    for (int i = 0; i < n_sources && aligned; i++) aligned = ((uintptr_t)run_sources[i] & 3) == 0;
-    if (!aligned) { set_error("%s: device frames of a 4:2:2 or P010 source must be 4-byte aligned", fn); return VBT_ERR_ARG; }
-  }
-  return VBT_OK;
-}
-
-// Brings B frames to the network resolution on stream S of forward slot k and returns the device pointer the detector reads.
-int prepare_frames(vbt_pipeline* p, int k, hipStream_t S, const Sources& src, const vbt_run* runs, int n_runs, int B, void* caller_stream,
-                   const uint8_t** frames_dev, int* stage_j) {
-  const int size = p->size;
-  const bool yuv = pix_fmt_is_source_yuv(p->pix_fmt);   // (a YUV source at the network resolution is still converted)
-  const bool resize = yuv || (src.src_h > 0 && src.src_w > 0 && (src.src_h != size || src.src_w != size || src.swap_rb));
-  const int H = src.src_h > 0 ? src.src_h : size, W = src.src_w > 0 ? src.src_w : size;
-  const PixLayout lay = pix_layout(p->pix_fmt, H, W);
-  const size_t row = lay.row, fb = lay.frame_bytes;
-  // bytes of one frame in the staging buffer / upload of nf host frames: packed rows, or a luma plane with the chroma behind it
-  auto stage_bytes = [&](bool compact_) { return !compact_ ? fb : lay.chroma_plane ? yuv_compact(p, H, row).frame_bytes : (size_t)2 * size * row; };
-  auto upload = [&](uint8_t* st_, int slot0, const uint8_t* host, int nf, bool compact_) {
-    return lay.chroma_plane ? h2d_frames_yuv(p, st_, slot0, host, nf, H, row, compact_) : h2d_frames(p, st_, slot0, host, nf, H, row, compact_);
-  };
-  *stage_j = -1;
-  const uint8_t* ptr = nullptr;
-  bool compact = false;
-  if (src.on_device) {
-    // frames are ready once the caller's stream gets here
-    const int ki = k;
-    VBT_HIP_CHECK(hipEventRecord(p->ev_in[ki].get(), (hipStream_t)caller_stream));
-    VBT_HIP_CHECK(hipStreamWaitEvent(S, p->ev_in[ki].get(), 0));
-  }
-  if (src.frames) {
-    if (src.on_device) {
-      ptr = src.frames;
-    } else {
-      compact = resize && compact_rows(p, H, W);
-      int j = 0;
-      PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), true, S, &j));
-      PL_CHECK(upload(p->stage[j].buf.get(), 0, src.frames, B, compact));
-      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev.get(), p->copy_stream));
-      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev.get(), 0));
-      ptr = p->stage[j].buf.get();
-      *stage_j = j;
-    }
-  } else {
-    // one source per run: the batch is assembled in a staging buffer
-    compact = !src.on_device && resize && compact_rows(p, H, W);
-    int j = 0;
-    PL_CHECK(stage_take(p, (size_t)p->n * stage_bytes(compact), !src.on_device, S, &j));
-    uint8_t* st = p->stage[j].buf.get();
-    if (!src.on_device) {
-      for (int i = 0; i < n_runs; i++) PL_CHECK(upload(st, runs[i].slot0, src.run_sources[i], runs[i].n_frames, compact));
-      VBT_HIP_CHECK(hipEventRecord(p->stage[j].copy_ev.get(), p->copy_stream));
-      VBT_HIP_CHECK(hipStreamWaitEvent(S, p->stage[j].copy_ev.get(), 0));
-    } else {
-      bool aligned = fb % 16 == 0;
-      for (int i = 0; i < n_runs && aligned; i++) aligned = ((uintptr_t)src.run_sources[i] & 15) == 0;
-      if (aligned) {
-        std::vector<const uint8_t*> ptrs((size_t)B, nullptr);
-        for (int i = 0; i < n_runs; i++)
-          for (int f = 0; f < runs[i].n_frames; f++) ptrs[(size_t)runs[i].slot0 + f] = src.run_sources[i] + (size_t)f * fb;
-        PL_CHECK(vbt_gather_frames(st, ptrs.data(), B, fb, (void*)S));
-      } else {
-        // a frame size that is not a multiple of 16 bytes (any source resolution is allowed): the gather kernel moves 16-byte
-        // pieces, so the batch is assembled by one device copy per run instead
-        for (int i = 0; i < n_runs; i++)
-          VBT_HIP_CHECK(hipMemcpyAsync(st + (size_t)runs[i].slot0 * fb, src.run_sources[i], (size_t)runs[i].n_frames * fb, hipMemcpyDeviceToDevice, S));
-      }
-    }
-    ptr = st;
-    *stage_j = j;
-  }
-  if (resize) {
-    PL_CHECK(ensure_resized(p, k));
-    if (yuv) {
-      // frame stride and chroma offset of what ptr holds: whole frames, the compact frame of yuv_compact, or [2 size] packed 4:2:2 rows
-      YuvCompact cl{0, 0, lay.chroma_plane ? (size_t)H * row : 0, fb};
-      if (compact && lay.chroma_plane) cl = yuv_compact(p, H, row);
-      else if (compact) cl.frame_bytes = (size_t)2 * size * row;
-      PL_CHECK(resize_frames_pix_dev(ptr, B, H, W, p->pix_fmt, p->cs_matrix, p->cs_range, cl.frame_bytes, cl.chroma_off, compact ? 1 : 0,
-                                     p->resized[k].get(), size, size, S));
-    } else {
-      PL_CHECK(resize_frames_dev(ptr, B, H, W, p->resized[k].get(), size, size, src.swap_rb, compact ? 1 : 0, S));
-    }
-    ptr = p->resized[k].get();
-  }
-  *frames_dev = ptr;
-  return VBT_OK;
+// The end of a run: everything held back goes out, then export id + rep analysis of every clip on the tracker stream.  Enqueue only.
+int drain_and_finish(vbt_pipeline* p) {
+  VBT_HIP_CHECK(hipSetDevice(p->device));
+  PL_CHECK(drain(p));
+  return vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream);
 }
 
 // The front of every step in ring slot o / forward slot k: the slot's previous outputs are free (`wait`: the step writes the slot now
@@ -555,18 +303,14 @@ int begin_step(vbt_pipeline* p, int o, int k, bool wait, bool counts_frame, cons
   p->last_o = o;
   p->last_k = k;
   p->last_B = B;
-  return prepare_frames(p, k, S, src, asm_runs, n_asm, B, caller_stream, frames_dev, stage_j);
+  return p->ingest.prepare(k, S, src, asm_runs, n_asm, B, caller_stream, frames_dev, stage_j);
 }
 
 // Behind the last kernel that reads the step's frames on S: the detections of ring slot o are complete (o < 0: not yet, the entry of
 // a step group), the staging buffer is free again
 int end_detect(vbt_pipeline* p, int o, int stage_j, hipStream_t S) {
   if (o >= 0) VBT_HIP_CHECK(hipEventRecord(p->ev_det[o].get(), S));
-  if (stage_j >= 0) {
-    VBT_HIP_CHECK(hipEventRecord(p->stage[stage_j].free_ev.get(), S));
-    p->stage[stage_j].free_set = true;
-  }
-  return VBT_OK;
+  return p->ingest.frames_read(stage_j, S);
 }
 
 // The tracker launch of a step that is not held back: inline right behind its forward, own stream depth - 1 detector steps behind
@@ -650,7 +394,7 @@ vbt_pipeline::~vbt_pipeline() {
   (void)finish_forward(this);   // (the models' tensors are released below: nothing half-run stays behind)
   for (int k = 0; k < depth; k++)
     if (det_streams[k]) (void)hipStreamSynchronize(det_streams[k]);
-  if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+  if (ingest.stream()) (void)hipStreamSynchronize(ingest.stream());
   if (trk_stream) (void)hipStreamSynchronize(trk_stream);
   {
     // streams are never destroyed: they go back to the process-wide pool, classified, for the next pipeline
@@ -749,7 +493,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   }
   int shp[4];
   if ((rc = vbt_model_input_shape(p->models[0].get(), shp)) != VBT_OK) return rc;
-  p->size = shp[1];
+  const int size = shp[1];
   {
     vbt_tracker* t = nullptr;
     if ((rc = vbt_tracker_create(p->n_trk, prm->rows_cap, &prm->tracker, p->device, &t)) != VBT_OK) return rc;
@@ -774,14 +518,10 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
       if (e.create(hipEventDisableTiming) != hipSuccess) return false;
     return true;
   };
-  bool ok = new_events(p->ev_in, (size_t)p->depth) && new_events(p->ev_det, R) && new_events(p->ev_trk, R);
-  // host-fed mode: H2D copies run on their own stream into a ring of depth + 2 staging buffers, i.e. up to two steps ahead of the
-  // forwards, so that a slot's forward never waits for its own copy
-  p->stage.resize((size_t)p->depth + 2);
-  for (auto& s : p->stage)
-    ok = ok && s.free_ev.create(hipEventDisableTiming) == hipSuccess && s.copy_ev.create(hipEventDisableTiming) == hipSuccess;
-  if (!ok) { set_error("vbt_pipeline_create: hipEventCreate failed"); return VBT_ERR_HIP; }
-  p->resized.resize((size_t)p->depth);
+  if (!new_events(p->ev_det, R) || !new_events(p->ev_trk, R) || !p->ingest.create(p->depth, p->n, size)) {
+    set_error("vbt_pipeline_create: hipEventCreate failed");
+    return VBT_ERR_HIP;
+  }
   p->clip_frames.assign(n, 0);
   {
     // the pipeline's own HIP streams (detector slots, copy, tracker): each is bound to its hardware queue at creation
@@ -802,7 +542,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
     if (rc == VBT_OK) rc = place_streams(pool, p->device, busy, strict, role_idx, p->own_streams, &p->placement_ok);
     if (rc == VBT_OK) {
       for (int k = 0; k < p->depth; k++) p->det_streams[k] = pool.streams[role_idx[k]];
-      p->copy_stream = pool.streams[role_idx[8]];
+      p->ingest.set_stream(pool.streams[role_idx[8]]);
       p->trk_stream = pool.streams[role_idx[9]];
     }
   }
@@ -813,7 +553,7 @@ int vbt_pipeline_create(const char* container_path, const vbt_pipeline_params* p
   const int n_check = prm->selfcheck >= 0 ? prm->selfcheck : env_int("VBT_PIPELINE_SELFCHECK", 1);
   if (n_check > 0) {
     DevBuf<uint8_t> blank;   // (freed when the block ends, behind the synchronisation of every forward that read it)
-    const size_t bytes = (size_t)p->G * n * p->size * p->size * 3;   // (a grouped pipeline checks the batch its forwards run at)
+    const size_t bytes = (size_t)p->G * n * size * size * 3;   // (a grouped pipeline checks the batch its forwards run at)
     if (blank.alloc(bytes + 64) != hipSuccess) { set_error("vbt_pipeline_create: hipMalloc of the self-check batch failed"); return VBT_ERR_HIP; }
     (void)hipMemset(blank.get(), 0, bytes);
     (void)hipDeviceSynchronize();
@@ -837,7 +577,7 @@ int vbt_pipeline_step(vbt_pipeline* p, const uint8_t* frames, int frames_on_devi
                       const int32_t* clip_map, const int32_t* frame_idx, int track, void* caller_stream) {
   if (!p || !frames) { set_error("vbt_pipeline_step: NULL argument"); return VBT_ERR_ARG; }
   if ((clip_map != nullptr) != (frame_idx != nullptr)) { set_error("vbt_pipeline_step: clip_map and frame_idx come together"); return VBT_ERR_ARG; }
-  PL_CHECK(check_source_format(p, "vbt_pipeline_step", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
+  PL_CHECK(p->ingest.check_sources("vbt_pipeline_step", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
   if (active && p->n_trk != p->n) { set_error("vbt_pipeline_step: `active` needs one clip per slot"); return VBT_ERR_ARG; }
   if (clip_map)
     for (int i = 0; i < p->n; i++)
@@ -860,7 +600,7 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
     set_error("vbt_pipeline_step_runs: out_* come together and are for detector-only steps (track = 0)");
     return VBT_ERR_ARG;
   }
-  PL_CHECK(check_source_format(p, "vbt_pipeline_step_runs", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr,
+  PL_CHECK(p->ingest.check_sources("vbt_pipeline_step_runs", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr,
                                frames_on_device ? run_sources : nullptr, frames_on_device && run_sources ? n_runs : 0));
   StepTimer timer(p);
   VBT_HIP_CHECK(hipSetDevice(p->device));
@@ -893,7 +633,7 @@ int vbt_pipeline_step_runs(vbt_pipeline* p, const uint8_t* frames, const uint8_t
 int vbt_pipeline_set_pixel_format(vbt_pipeline* p, int pix_fmt) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   if (pix_fmt != VBT_PIX_RGB24 && !pix_fmt_is_source_yuv(pix_fmt)) { set_error("vbt_pipeline_set_pixel_format: unknown pixel format %d", pix_fmt); return VBT_ERR_ARG; }
-  p->pix_fmt = pix_fmt;   // read by the next step call: steps already enqueued carry their own kernels and copies
+  p->ingest.set_pixel_format(pix_fmt);
   return VBT_OK;
 }
 
@@ -901,8 +641,7 @@ int vbt_pipeline_set_colour(vbt_pipeline* p, int matrix, int range) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   if (matrix != VBT_CS_BT601 && matrix != VBT_CS_BT709) { set_error("vbt_pipeline_set_colour: unknown matrix %d", matrix); return VBT_ERR_ARG; }
   if (range != VBT_RANGE_LIMITED && range != VBT_RANGE_FULL) { set_error("vbt_pipeline_set_colour: unknown range %d", range); return VBT_ERR_ARG; }
-  p->cs_matrix = matrix;   // read by the next step call, like the format; not read while the format is VBT_PIX_RGB24
-  p->cs_range = range;
+  p->ingest.set_colour(matrix, range);
   return VBT_OK;
 }
 
@@ -953,9 +692,7 @@ int vbt_pipeline_drain(vbt_pipeline* p) {
 
 int vbt_pipeline_finish(vbt_pipeline* p) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
-  VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(drain(p));
-  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  PL_CHECK(drain_and_finish(p));
   VBT_HIP_CHECK(hipStreamSynchronize(p->trk_stream));
   return VBT_OK;
 }
@@ -1017,8 +754,7 @@ int vbt_pipeline_close_clips_enable(vbt_pipeline* p) {
 
 // Slot close.  Enqueue only: drain() hands the held-back tracker steps to their streams, the close kernels and the reset follow on the
 // tracker stream (in inline mode drain() made it wait for the last tracker launch), and the reset is recorded as the most recent tracker
-// launch - every later tracker launch waits for it, whichever stream it runs on (enqueue_tracker, flush_block, tracker-only steps run
-// on the tracker stream itself).  The record goes straight into pinned memory (close_pack_kernel), so no copy is enqueued here.
+// launch (rerecord_trk).  The record goes straight into pinned memory (close_pack_kernel), so no copy is enqueued here.
 int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const double* next_fps) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   PL_CHECK(check_clip_list("vbt_pipeline_close_clips", clips, n, p->n_trk));
@@ -1046,10 +782,7 @@ int vbt_pipeline_close_clips(vbt_pipeline* p, const int32_t* clips, int n, const
     if ((size_t)c < p->clip_frames.size()) p->clip_frames[(size_t)c] = 0;
     if (next_fps) p->fps[(size_t)c] = next_fps[i];
   }
-  const int e = p->last_trk >= 0 ? p->last_trk : 0;
-  VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e].get(), T));
-  p->last_trk = e;
-  return VBT_OK;
+  return rerecord_trk(p, T);
 }
 
 // vbt_pipeline_closed_clip (metrics8 == nullptr) / vbt_pipeline_closed_clip_ex
@@ -1109,9 +842,7 @@ int vbt_pipeline_close_ex(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, i
                           double* metrics8, int cap) {
   if (!p || !best_ids || !n_rows || !n_phases || !overflow || !phases6 || !metrics8) { set_error("vbt_pipeline_close_ex: NULL argument"); return VBT_ERR_ARG; }
   if (!p->rep_metrics) { set_error("vbt_pipeline_close_ex: rep metrics are not enabled (vbt_pipeline_rep_metrics_enable)"); return VBT_ERR_STATE; }
-  VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(drain(p));
-  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  PL_CHECK(drain_and_finish(p));
   return vbt_tracker_summary_ex(p->trk.get(), best_ids, n_rows, n_phases, overflow, phases6, metrics8, cap);
 }
 
@@ -1121,9 +852,7 @@ int vbt_pipeline_close(vbt_pipeline* p, int32_t* best_ids, int32_t* n_rows, int3
     if (best_ids || n_rows || n_phases || overflow || phases6) { set_error("vbt_pipeline_close: the output arrays come together"); return VBT_ERR_ARG; }
     return vbt_pipeline_finish(p);
   }
-  VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(drain(p));
-  PL_CHECK(vbt_tracker_finish(p->trk.get(), p->prm.plate_diameter, p->prm.diff_threshold, p->prm.min_distance, (void*)p->trk_stream));
+  PL_CHECK(drain_and_finish(p));
   return vbt_tracker_summary(p->trk.get(), best_ids, n_rows, n_phases, overflow, phases6, cap);
 }
 
@@ -1198,14 +927,6 @@ int vbt_pipeline_rep_metrics_enable(vbt_pipeline* p) {
   return closed_metrics_alloc(p);
 }
 
-int vbt_pipeline_live_poll_ex(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap) {
-  if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
-  if (!p->live) { set_error("vbt_pipeline_live_poll_ex: live analysis is not enabled"); return VBT_ERR_STATE; }
-  VBT_HIP_CHECK(hipSetDevice(p->device));
-  PL_CHECK(drain(p));   // (as vbt_pipeline_live_poll)
-  return vbt_tracker_live_poll_ex(p->trk.get(), flush_view, clips, phases6, metrics8, cap, (void*)p->trk_stream);
-}
-
 int vbt_pipeline_use_sort(vbt_pipeline* p, const vbt_sort_params* sp) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
   PL_CHECK(check_sort_params("vbt_pipeline_use_sort", sp));
@@ -1213,12 +934,22 @@ int vbt_pipeline_use_sort(vbt_pipeline* p, const vbt_sort_params* sp) {
   return tracker_use_sort(p->trk.get(), sp);
 }
 
-int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap) {
+// vbt_pipeline_live_poll (ex false, metrics8 not read) / vbt_pipeline_live_poll_ex
+static int live_poll(vbt_pipeline* p, bool ex, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap) {
   if (!p) { set_error("NULL pipeline"); return VBT_ERR_ARG; }
-  if (!p->live) { set_error("vbt_pipeline_live_poll: live analysis is not enabled"); return VBT_ERR_STATE; }
+  if (!p->live) { set_error("vbt_pipeline_live_poll%s: live analysis is not enabled", ex ? "_ex" : ""); return VBT_ERR_STATE; }
   VBT_HIP_CHECK(hipSetDevice(p->device));
   PL_CHECK(drain(p));   // (inline mode: the tracker stream now waits for the last tracker launch)
+  if (ex) return vbt_tracker_live_poll_ex(p->trk.get(), flush_view, clips, phases6, metrics8, cap, (void*)p->trk_stream);
   return vbt_tracker_live_poll(p->trk.get(), flush_view, clips, phases6, cap, (void*)p->trk_stream);
+}
+
+int vbt_pipeline_live_poll(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, int cap) {
+  return live_poll(p, false, flush_view, clips, phases6, nullptr, cap);
+}
+
+int vbt_pipeline_live_poll_ex(vbt_pipeline* p, int flush_view, vbt_live_clip* clips, double* phases6, double* metrics8, int cap) {
+  return live_poll(p, true, flush_view, clips, phases6, metrics8, cap);
 }
 
 // One-pass export.  drain() hands every tracker step still held back to its stream - the block of deferred / grouped steps, the
@@ -1230,14 +961,12 @@ int vbt_pipeline_overlay_draw(vbt_pipeline* p, vbt_overlay* o, uint8_t* frames_d
   PL_CHECK(drain(p));
   // A panel that follows this tracker's live analysis: its update reads tables the NEXT tracker launch changes in place, and writes
   // the table the handle's previous draw may still read.  It runs on the tracker stream, which drain() has put behind the last
-  // tracker launch in every placement, after an event behind that draw; ev_trk[last_trk] is recorded again behind it, so `stream`
-  // (below) and every later tracker launch (each waits for ev_trk[last_trk], or runs on the tracker stream) come after the update.
+  // tracker launch in every placement, after an event behind that draw, and becomes the most recent tracker launch (rerecord_trk):
+  // `stream` (below) comes after the update too.
   const bool panel = overlay_hud_follows(o, p->trk.get());
   if (panel) {
     PL_CHECK(overlay_hud_follow_enqueue(o, p->trk_stream));
-    const int e = p->last_trk >= 0 ? p->last_trk : 0;
-    VBT_HIP_CHECK(hipEventRecord(p->ev_trk[(size_t)e].get(), p->trk_stream));
-    p->last_trk = e;
+    PL_CHECK(rerecord_trk(p, p->trk_stream));
   }
   if (p->last_trk >= 0) VBT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, p->ev_trk[p->last_trk].get(), 0));
   PL_CHECK(vbt_overlay_follow_update(o, stream));
@@ -1250,7 +979,7 @@ int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
   if (!p || !out) { set_error("vbt_pipeline_get_info: NULL argument"); return VBT_ERR_ARG; }
   memset(out, 0, sizeof(*out));
   out->n_slots = p->n; out->n_clips = p->n_trk; out->rows_cap = p->prm.rows_cap; out->device = p->device; out->depth = p->depth;
-  out->ring = p->ring; out->defer = p->defer; out->tracker_inline = p->trk_inline ? 1 : 0; out->image_size = p->size;
+  out->ring = p->ring; out->defer = p->defer; out->tracker_inline = p->trk_inline ? 1 : 0; out->image_size = p->ingest.image_size();
   out->frame_count = p->frame_count; out->steps_enqueued = p->step_idx; out->placement_ok = p->placement_ok ? 1 : 0;
   out->group = p->G;
   int next_o = 0;
@@ -1260,9 +989,9 @@ int vbt_pipeline_get_info(const vbt_pipeline* p, vbt_pipeline_info* out) {
     out->queue_groups_seen = (int)g_pools[p->device].reps.size();
   }
   for (int k = 0; k < p->depth; k++) out->det_streams[k] = (void*)p->det_streams[k];
-  out->copy_stream = (void*)p->copy_stream;
+  out->copy_stream = (void*)p->ingest.stream();
   out->tracker_stream = (void*)p->trk_stream;
-  out->h2d_bytes = p->h2d_bytes;
+  out->h2d_bytes = p->ingest.uploaded();
   out->step_host_ns = p->step_host_ns;
   out->step_calls = p->step_calls;
   return VBT_OK;
@@ -1275,10 +1004,9 @@ int vbt_track_clip(vbt_pipeline* p, const uint8_t* frames, int frames_on_device,
                    int64_t* id, double* cols7, int cap, int* n_rows) {
   if (!p || !frames || T < 0 || !id || !cols7 || !n_rows || cap < 0) { set_error("vbt_track_clip: bad argument"); return VBT_ERR_ARG; }
   if (p->n_trk != 1) { set_error("vbt_track_clip: the pipeline must follow exactly one clip (n_clips = 1), it follows %d", p->n_trk); return VBT_ERR_ARG; }
-  PL_CHECK(check_source_format(p, "vbt_track_clip", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
+  PL_CHECK(p->ingest.check_sources("vbt_track_clip", src_h, src_w, swap_rb, frames_on_device ? frames : nullptr));
   const int stride = std::max(frame_stride, 1);
-  const int H = src_h > 0 ? src_h : p->size, W = src_w > 0 ? src_w : p->size;
-  const size_t fb = pix_layout(p->pix_fmt, H, W).frame_bytes;
+  const size_t fb = p->ingest.source_frame_bytes(src_h, src_w);
   PL_CHECK(vbt_pipeline_reset(p));
   // frames whose 1-based number is not a multiple of the stride are read and dropped (track.py:161-167): they only advance the time
   const int kept = T / stride, F = p->n;

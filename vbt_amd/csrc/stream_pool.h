@@ -14,12 +14,6 @@
 
 namespace vbt {
 
-#define PL_CHECK(expr)            \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_ != VBT_OK) return rc_; \
-  } while (0)
-
 inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return v && *v ? atoi(v) : dflt;

@@ -31,7 +31,7 @@ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V) {
 // One thread per output pixel, consecutive lanes = consecutive output columns: a wave reads one luma row segment per source row
 // (lanes W / w bytes apart, neighbouring lanes within the same cache lines) and the chroma row under it.
 // Source frame b starts at src + b * frame_stride.  Whole frame (compact == 0): luma row y at y * W.  Compact (the host-fed upload,
-// pipeline.hip): luma holds only the row pairs the resize reads, pair oy = source rows p, p + 1 (p = min(y0, H - 2)) at row 2 oy.
+// upload_plan.h): luma holds only the row pairs the resize reads, pair oy = source rows p, p + 1 (p = min(y0, H - 2)) at row 2 oy.
 // Either way the chroma plane(s) start at chroma_off, whole, in the layout of the format: NV12 [H/2][W] interleaved U,V;
 // I420 [H/2][W/2] U then [H/2][W/2] V.  The chroma sample of source pixel (y, x) is the one at (y >> 1, x >> 1), taken nearest.
 __global__ __launch_bounds__(256) void yuv_resize_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long total, int H, int W,
