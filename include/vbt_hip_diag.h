@@ -59,6 +59,19 @@ typedef struct {
   int variants[48];
 } vbt_plan_step_space;
 int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, int* n);
+/* The execution list: what vbt_detect_range_async's step indices count.  It is the chosen alternatives of the plan space AFTER the
+ * planner merged the side convolutions into one launch, so it cannot be derived from vbt_model_plan_space.  Entry i = plan step i;
+ * *n = vbt_model_num_launches; a `cap` below it is VBT_ERR_CAPACITY with nothing written.  Host only: nothing is launched. */
+typedef struct {
+  char family[32];        /* kernel family, as the plan file spells it */
+  int variant;            /* the step's current variant (-1: the heuristic default) */
+  int reads_frames;       /* 1 if the step reads the uint8 frames (a range holding it needs frames_dev) */
+  int image0_only;        /* 1 if vbt_detect_range_async refuses the step for img0 != 0 (its grid carries whole-batch pointers) */
+  int group, step;        /* where the step sits in the plan space (its group's chosen alternative); -1, -1: the merged launch */
+  int first_op, last_op;  /* lowest and highest graph op the step names (resamples and partial sums it absorbs are not among them) */
+  int n_members;          /* problems launched as one grid (0: a single problem) */
+} vbt_plan_step_info;
+int vbt_model_plan_steps(const vbt_model* m, vbt_plan_step_info* out, int cap, int* n);
 /* Live 16-channel tiles of the part-filled last output block that step (group, alt, step) of the plan space runs tile-major under its
  * current variant: fused_mbconv launches built with a live-tile count and pw_conv_mfma_i8 variants 9 / 10.  0: the step runs the
  * block-major layout (a full last block, another family, no such kernel, or VBT_PROJ_TAIL turned it off); < 0: no such step. */

@@ -90,18 +90,8 @@ def oracle_run(oracle_lib, model_path, frames):
 @pytest.fixture(scope="module")
 def clamped(tmp_path_factory, oracle_lib, model_path, frames):
     """The narrowed-range model of test_gpu_band_chain (the explicit-clamp requantisation flavours) and the oracle's run of it."""
-    from vbt_amd.container import Container
-    raw = bytearray(open(model_path, "rb").read())
-    c = Container(model_path)
-    ops = np.frombuffer(raw, dtype=c.ops.dtype, count=len(c.ops), offset=128 + 32 * len(c.tensors))
-    n = 0
-    for i, r in enumerate(ops):
-        if int(r["type"]) in (1, 2, 3) and i % 3 != 0:
-            r["act_min"], r["act_max"] = max(int(r["act_min"]), -101 + i % 7), min(int(r["act_max"]), 96 - i % 5)
-            n += 1
-    assert n > 100
-    path = str(tmp_path_factory.mktemp("models") / "clamped.vbtm")
-    open(path, "wb").write(bytes(raw))
+    from step_cases import write_clamped          # the one writer of that container
+    path = write_clamped(model_path, str(tmp_path_factory.mktemp("models") / "clamped.vbtm"))
     return path, _oracle(oracle_lib, path, frames)
 
 

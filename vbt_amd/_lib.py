@@ -139,6 +139,12 @@ class PlanStepSpace(ctypes.Structure):
                 ("n_variants", c_int), ("variants", c_int * 48)]
 
 
+class PlanStepInfo(ctypes.Structure):
+    """vbt_plan_step_info (include/vbt_hip_diag.h): one step of the execution list"""
+    _fields_ = [("family", ctypes.c_char * 32), ("variant", c_int), ("reads_frames", c_int), ("image0_only", c_int), ("group", c_int),
+                ("step", c_int), ("first_op", c_int), ("last_op", c_int), ("n_members", c_int)]
+
+
 _SIGS = {
     "vbt_last_error": (c_char_p, []),
     "vbt_device_count": (c_int, []),
@@ -161,6 +167,7 @@ _SIGS = {
     "vbt_model_read_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vbt_model_write_tensor": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vbt_model_plan_space": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "vbt_model_plan_steps": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "vbt_model_step_proj_tail": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_model_step_fused_params": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vbt_resize_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -547,6 +547,36 @@ int vbt_detect_async(vbt_model* m, const uint8_t* frames_dev, int B, void* strea
 
 int vbt_model_entry_steps(const vbt_model* m) { return m ? entry_steps(m) : VBT_ERR_ARG; }
 
+// grids of several problems carry whole-batch pointers (launch_step): such a step runs from image 0 only
+static bool image0_only(const Step& s) { return (s.family == F_PW && !s.members.empty()) || s.family == F_BAND; }
+
+int vbt_model_plan_steps(const vbt_model* m, vbt_plan_step_info* out, int cap, int* n) {
+  if (!m || !n || cap < 0 || (cap > 0 && !out)) { set_error("vbt_model_plan_steps: bad argument"); return VBT_ERR_ARG; }
+  const int ns = (int)m->steps.size();
+  *n = ns;
+  if (ns > cap) { set_error("plan steps: %d steps, buffer holds %d", ns, cap); return VBT_ERR_CAPACITY; }
+  for (int i = 0; i < ns; i++) {
+    const Step& s = m->steps[(size_t)i];
+    vbt_plan_step_info& o = out[i];
+    memset(&o, 0, sizeof(o));
+    snprintf(o.family, sizeof(o.family), "%s", kFamilyName[s.family]);
+    o.variant = s.variant;
+    o.reads_frames = s.family == F_STEM || s.family == F_STEMBLK;
+    o.image0_only = image0_only(s);
+    o.n_members = (int)s.members.size();
+    o.first_op = (int)m->ops.size(); o.last_op = -1;
+    for_each_named_op(s, [&](int op) { o.first_op = std::min(o.first_op, op); o.last_op = std::max(o.last_op, op); });
+    // the step of a chosen alternative this one is a copy of (finalize_plan); the launch merge_side_convs put together has none
+    o.group = o.step = -1;
+    for (size_t gi = 0; gi < m->groups.size() && o.group < 0; gi++) {
+      const Alt& a = m->groups[gi].alts[(size_t)m->groups[gi].chosen];
+      for (size_t si = 0; si < a.steps.size(); si++)
+        if (a.steps[si].op == s.op && a.steps[si].family == s.family && a.steps[si].members.size() == s.members.size()) { o.group = (int)gi; o.step = (int)si; break; }
+    }
+  }
+  return VBT_OK;
+}
+
 int vbt_detect_range_async(vbt_model* m, const uint8_t* frames_dev, int img0, int n_img, int step0, int step1, void* stream, float* boxes,
                            float* scores, float* classes, int32_t* counts) {
   if (!m) { set_error("vbt_detect_range_async: NULL model"); return VBT_ERR_ARG; }
@@ -558,8 +588,7 @@ int vbt_detect_range_async(vbt_model* m, const uint8_t* frames_dev, int img0, in
   for (int i = step0; i < step1; i++) {
     const Step& s = m->steps[(size_t)i];
     if (s.family == F_POST && (!boxes || !scores || !classes || !counts)) { set_error("vbt_detect_range_async: the range ends in decode + NMS, an output pointer is NULL"); return VBT_ERR_ARG; }
-    // grids of several problems carry whole-batch pointers (launch_step)
-    if (img0 != 0 && ((s.family == F_PW && !s.members.empty()) || s.family == F_BAND)) { set_error("vbt_detect_range_async: plan step %d (%s) runs from image 0 only", i, kFamilyName[s.family]); return VBT_ERR_ARG; }
+    if (img0 != 0 && image0_only(s)) { set_error("vbt_detect_range_async: plan step %d (%s) runs from image 0 only", i, kFamilyName[s.family]); return VBT_ERR_ARG; }
   }
   RoctxRange range("vbt:detect");
   if (m->pool_dirty) { const int rc = flush_uploads(m); if (rc) return rc; }

@@ -76,6 +76,15 @@ struct Step {
   ImageBundle ib = {nullptr, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// The graph ops a step names, its members' included (a resample or partial sum it absorbs is named by no step): the one list
+// merge_side_convs, vbt_model_plan_space and vbt_model_plan_steps go by.
+template <typename F>
+inline void for_each_named_op(const Step& s, F&& f) {
+  for (int o : {s.op, s.e_op, s.d_op, s.p_op, s.a_op, s.res_op, s.sum_op})
+    if (o >= 0) f(o);
+  for (const Step& ms : s.members) for_each_named_op(ms, f);
+}
+
 // A group of consecutive graph ops with alternative realisations (all bit-identical); the planner keeps
 // the fastest one measured on this device at this batch size.
 struct Alt {

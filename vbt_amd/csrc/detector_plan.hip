@@ -315,12 +315,7 @@ int vbt_model_plan_space(const vbt_model* m, vbt_plan_step_space* out, int cap, 
         const Step& st = m->groups[gi].alts[ai].steps[si];
         o.variant = st.variant;
         o.first_op = (int)m->ops.size(); o.last_op = -1;
-        std::function<void(const Step&)> span = [&](const Step& s) {
-          for (int op : {s.op, s.e_op, s.d_op, s.p_op, s.a_op, s.sum_op})
-            if (op >= 0) { o.first_op = std::min(o.first_op, op); o.last_op = std::max(o.last_op, op); }
-          for (const Step& mb : s.members) span(mb);
-        };
-        span(st);
+        for_each_named_op(st, [&](int op) { o.first_op = std::min(o.first_op, op); o.last_op = std::max(o.last_op, op); });
         snprintf(o.family, sizeof(o.family), "%s", ps.family.c_str());
         o.n_variants = (int)ps.variants.size();
         std::copy(ps.variants.begin(), ps.variants.end(), o.variants);

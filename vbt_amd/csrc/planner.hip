@@ -960,12 +960,8 @@ static void merge_side_convs(vbt_model* m) {
   const int ns = (int)m->steps.size(), no = (int)m->ops.size();
   // which step runs which graph op: the ops a step names, then (absorbed resamples / partial sums) the step of their consumer
   std::vector<int> step_of(no, -1);
-  std::function<void(const Step&, int)> claim = [&](const Step& s, int i) {
-    for (int o : {s.op, s.e_op, s.d_op, s.p_op, s.a_op, s.res_op, s.sum_op})
-      if (o >= 0 && o < no) step_of[o] = i;
-    for (const Step& ms : s.members) claim(ms, i);
-  };
-  for (int i = 0; i < ns; i++) claim(m->steps[i], i);
+  for (int i = 0; i < ns; i++)
+    for_each_named_op(m->steps[i], [&](int o) { if (o < no) step_of[o] = i; });
   std::vector<std::vector<int>> readers(m->tensors.size());
   std::vector<int> producer(m->tensors.size(), -1);
   for (int o = 0; o < no; o++) {

@@ -112,6 +112,37 @@ class Interpreter:
         return [{"group": e.group, "alt": e.alt, "step": e.step, "chosen": bool(e.chosen), "variant": e.variant, "first_op": e.first_op,
                  "last_op": e.last_op, "family": e.family.decode(), "variants": list(e.variants[:e.n_variants])} for e in buf[:n.value]]
 
+    def plan_steps(self):
+        """The execution list, one dict per plan step (the indices run_steps counts): family, variant, reads_frames, image0_only,
+        group / step (its place in the plan space; -1 for the merged side-conv launch), first_op / last_op, n_members
+        (vbt_model_plan_steps)."""
+        n = ctypes.c_int()
+        rc = _lib.lib().vbt_model_plan_steps(self._h, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):       # VBT_ERR_CAPACITY: the count of steps is in n
+            _lib.check(rc)
+        buf = (_lib.PlanStepInfo * max(n.value, 1))()
+        _lib.check(_lib.lib().vbt_model_plan_steps(self._h, buf, n.value, ctypes.byref(n)))
+        return [{"family": e.family.decode(), "variant": e.variant, "reads_frames": bool(e.reads_frames), "image0_only": bool(e.image0_only),
+                 "group": e.group, "step": e.step, "first_op": e.first_op, "last_op": e.last_op, "n_members": e.n_members}
+                for e in buf[:n.value]]
+
+    def run_steps(self, step0, step1, img0, n_img, frames=None):
+        """Plan steps [step0, step1) alone on images img0 .. img0 + n_img - 1 of the tensors as they stand (test equipment, see
+        write_tensor), then a synchronisation.  frames: uint8 [n_img,S,S,3] (host), the frames OF THAT RANGE, for a range that holds a
+        step reading them.  Decode + NMS has run_postprocess."""
+        buf, ptr = None, None
+        if frames is not None:
+            from .mem import DeviceBuffer
+            f = np.ascontiguousarray(frames, dtype=np.uint8)
+            if f.ndim != 4 or f.shape[0] != n_img or tuple(f.shape[1:]) != tuple(self._shape[1:]):
+                raise ValueError(f"frames must be uint8 [{n_img},{self._shape[1]},{self._shape[2]},3], got {f.shape}")
+            buf = DeviceBuffer.from_host(f, self.device)
+            ptr = ctypes.c_void_p(buf.ptr)
+        try:
+            _lib.check(_lib.lib().vbt_detect_range_async(self._h, ptr, img0, n_img, step0, step1, None, None, None, None, None))
+        finally:
+            _lib.check(_lib.lib().vbt_device_synchronize(self.device))   # (before `buf` is freed, whatever the call answered)
+
     def proj_tail(self, group, alt, step):
         """Live tiles of the part-filled last output block that plan-space step runs tile-major under its current variant; 0: block-major
         (vbt_model_step_proj_tail)."""
