@@ -1,4 +1,4 @@
-"""The SORT tracker on the device (vbt_tracker_create_sort, vbt_amd/csrc/sort_step.h) against the numpy restatement
+"""The SORT tracker on the device (vbt_tracker_create_sort, vbt_amd/csrc/sort_step.h + step_phases.h) against the numpy restatement
 (tests/sort_ref.py) bit for bit, and against the reference's committed SORT frames (tests/golden/dfs_sort.npz) in the terms of
 tests/test_sort_ref_host.py; then every path that steps it (host detections, the one-frame kernel, the fused per-frame kernel, the
 time-batched walk with its two state homes), the pipeline and the CLI.  Inputs and reference replays: tests/sort_cases.py."""

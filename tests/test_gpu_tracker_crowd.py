@@ -267,3 +267,37 @@ def test_a_count_above_25_is_clamped():
     for what, mc, ci in (("one frame per call", one, 0), ("all frames", many, 0), ("two clips", two, 0), ("two clips", two, 1)):
         _assert_rows(mc.rows(ci), rep.rows, what)
         _assert_state(mc, ci, rep, what)
+
+
+# ---- 8. a track whose predicted box is NaN ----
+
+def test_zero_height_detection_is_born_and_removed_by_ocsort():
+    """tests/test_gpu_sort.py's scene under OC-SORT: s = w * h = 0 at the birth, so the predicted box of the next frame is NaN (h = s / w
+    = 0 / 0) and the track leaves the list in the predict phase, twice in ten frames.  Host detections in one launch, and the
+    time-batched walk as one run with the state in LDS, where a slot is freed mid-walk and the write-back has to skip it."""
+    from test_gpu_sort import zero_height_scene
+    from vbt_amd import _lib
+    from vbt_amd.mem import DeviceBuffer
+    frames, tm = zero_height_scene()
+    assert len(frames) == 10 and all(list(frames[f][1]) == [0.4, 0.5, 0.5, 0.5, 0.8, 0.0] for f in (1, 5))
+    boxes, scores, counts, dets32 = cc.as_detector_output(frames)
+    reps = {}
+    for what, fr in (("host", frames), ("walk", dets32)):        # the walk's oracle: on the float64 detections the tracker makes of float32
+        with np.errstate(invalid="ignore"):
+            rep = reps[what] = cc.replay_ocsort_on(fr, tm, max_age=30, asso_func="diou", iou_threshold=0.1)
+        assert len(rep.rows["id"]) == 21 and set(rep.rows["id"]) == {1, 2, 3} and not np.isnan(rep.rows["x"]).any(), what
+        assert [(len(s.before), len(s.ids)) for s in rep.steps][2::4] == [(3, 2), (3, 2)], what     # the list after frames 3 and 7
+        assert [(i, gone) for i, _, gone in cc.deaths(rep)] == [(2, [2]), (6, [2])], what                    # two removals, none by age
+    host = _tracker("diou", 1, 512, 30)
+    host.update_frames(*cc.pack([(frames, tm)]))
+    walk = _tracker("diou", 1, 512, 30)
+    b, s, c = (DeviceBuffer.from_host(np.ascontiguousarray(x)) for x in (boxes, scores, counts))
+    run = (_lib.Run * 1)(_lib.Run(0, 0, 1, len(frames), 1, 1, 30.0))         # 10 frames: above the 6 from which a run keeps the state in LDS
+    _lib.check(_lib.lib().vbt_tracker_update_from_detections_seq(walk.handle, b.ptr, s.ptr, c.ptr, len(frames), run, 1, 0.25, None))
+    for what, mc in (("host", host), ("walk", walk)):
+        rep = reps[what]
+        _assert_rows(mc.rows(0), rep.rows, what)
+        _assert_state(mc, 0, rep, what)
+        assert mc.status(0)["trackers"] == 2, what
+        mc.finish(0.45)
+        assert mc.phases(0)[0] == cc.export_rule(rep.rows)[0] == 1, what

@@ -1,5 +1,5 @@
-// Wave-parallel linear assignment with scipy's tie rule, shared by the OC-SORT tracker (ocsort_step.h) and the detector
-// evaluation (evaluate.hip).  Device code only; one wavefront (64 lanes) per problem.
+// Wave-parallel linear assignment with scipy's tie rule, shared by the trackers (step_phases.h: gate_and_assign of both steps;
+// ocsort_step.h: the second association) and the detector evaluation (evaluate.hip).  Device code only; one wavefront (64 lanes) per problem.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,86 +1,12 @@
-// One OCSort.update() for one clip by one wavefront: the Kalman pieces, the association costs, ocsort_step itself, the detector
-// slot -> detection list loaders and the clip state's copy between global memory and LDS.  Device code, included by tracker.hip - the
-// unit of the step kernels - after its TRK_T0 / TRK_MARK phase-timer macros.  All arithmetic is FP64 with contraction off in the op
-// order of the numpy formulation (tracker.hip's header comment): nothing here may be reordered.
+// One OCSort.update() for one clip by one wavefront: what is OC-SORT's own - the Kalman update with its freeze / unfreeze, the direction
+// term of the first association, the unmatched lists, the second association on the last observations, update(None), the box a row is
+// emitted as - and ocsort_step, which runs them between the phases it shares with sort_step (step_phases.h: predict_and_drop_nan,
+// gate_and_assign, births, emit_and_delete).  Device code, included by tracker.hip.  All arithmetic is FP64 with contraction off in the
+// op order of the numpy formulation (tracker.hip's header comment): nothing here may be reordered.
 #pragma once
-#include "lap.h"
-#include "tracker_state.h"
+#include "step_phases.h"
 
 namespace vbt {
-
-// ------------------------------------------------------------------------------------------
-// Kalman filter pieces (see header comment)
-// ------------------------------------------------------------------------------------------
-// The filter state proper as a LOCAL value: x, the three 2x2 covariance blocks and the variance of r.  predict / update work on a copy
-// in registers that is loaded from the track once and stored back once: through a `Trk&` into LDS or global memory the compiler has to
-// assume that every store may change what the next load reads (the detection, the observation history and the state are all plain
-// double arrays), so the filter arithmetic ran as a chain of store -> wait -> load.
-struct KfCore {
-  double x[7];
-  double B[3][4];
-  double Pr;
-};
-__device__ __forceinline__ void core_load(KfCore& c, const Trk& k) {
-#pragma unroll
-  for (int i = 0; i < 7; i++) c.x[i] = k.x[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) c.B[i][j] = k.B[i][j];
-  c.Pr = k.Pr;
-}
-__device__ __forceinline__ void core_store(Trk& k, const KfCore& c) {
-#pragma unroll
-  for (int i = 0; i < 7; i++) k.x[i] = c.x[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) k.B[i][j] = c.B[i][j];
-  k.Pr = c.Pr;
-}
-__device__ __forceinline__ void kf_predict(KfCore& k, double q44, double q66) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) k.x[i] = k.x[i] + k.x[i + 4];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    double a = k.B[i][0], b = k.B[i][1], c = k.B[i][2], d = k.B[i][3];
-    double qv = i == 2 ? q66 : q44;
-    k.B[i][0] = ((a + c) + (b + d)) + 1.0;
-    k.B[i][1] = (b + d) + 0.0;
-    k.B[i][2] = (c + d) + 0.0;
-    k.B[i][3] = d + qv;
-  }
-  k.Pr = k.Pr + 1.0;
-}
-
-__device__ __forceinline__ void kf_update_math(KfCore& k, const double z[4]) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const double Rc = i == 2 ? 10.0 : 1.0;
-    double a = k.B[i][0], b = k.B[i][1], c = k.B[i][2], d = k.B[i][3];
-    double y = z[i] - k.x[i];
-    double S = a + Rc;
-    double si = 1.0 / S;
-    double kp = a * si, kv = c * si;
-    k.x[i] = k.x[i] + kp * y;
-    k.x[i + 4] = k.x[i + 4] + kv * y;
-    double omk = 1.0 - kp, nkv = 0.0 - kv;
-    double M00 = omk * a, M01 = omk * b, M10 = nkv * a + c, M11 = nkv * b + d;
-    double N00 = M00 * omk, N01 = M00 * nkv + M01, N10 = M10 * omk, N11 = M10 * nkv + M11;
-    double KRp = kp * Rc, KRv = kv * Rc;
-    k.B[i][0] = N00 + KRp * kp;
-    k.B[i][1] = N01 + KRp * kv;
-    k.B[i][2] = N10 + KRv * kp;
-    k.B[i][3] = N11 + KRv * kv;
-  }
-  double y = z[3] - k.x[3];
-  double S = k.Pr + 10.0;
-  double si = 1.0 / S;
-  double kk = k.Pr * si;
-  k.x[3] = k.x[3] + kk * y;
-  double omk = 1.0 - kk;
-  k.Pr = (omk * k.Pr) * omk + (kk * 10.0) * kk;
-}
 
 // kf.update(z) with OC-SORT's freeze / unfreeze (observation-centric re-update); c = the track's filter state (registers)
 __device__ inline void kf_update(Trk& k, KfCore& c, const double* z, double q44, double q66) {
@@ -138,11 +64,6 @@ __device__ inline void bbox_to_z(const double* b, double z[4]) {
   z[2] = w * h;
   z[3] = w / (h + 1e-6);
 }
-__device__ inline void x_to_bbox(const double* x, double o[4]) {
-  double w = sqrt(x[2] * x[3]);
-  double h = x[2] / w;
-  o[0] = x[0] - w / 2.0; o[1] = x[1] - h / 2.0; o[2] = x[0] + w / 2.0; o[3] = x[1] + h / 2.0;
-}
 
 // `last_observation.sum() < 0` is how OC-SORT asks "no observation yet" (placeholder = five -1s); it
 // also fires for a real box far enough outside the image, and that quirk is kept.
@@ -189,12 +110,6 @@ __device__ inline void trk_update(Trk& k, const double* det_in, double q44, doub
   core_store(k, c);
 }
 
-__device__ inline double iou_xyxy(const double* a, const double* b) {
-  double xx1 = fmax(a[0], b[0]), yy1 = fmax(a[1], b[1]), xx2 = fmin(a[2], b[2]), yy2 = fmin(a[3], b[3]);
-  double w = fmax(0.0, xx2 - xx1), h = fmax(0.0, yy2 - yy1);
-  double wh = w * h;
-  return wh / ((a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - wh);
-}
 __device__ inline double diou_xyxy(const double* a, const double* b) {
   double iou = iou_xyxy(a, b);
   double cx1 = (a[0] + a[2]) / 2.0, cy1 = (a[1] + a[3]) / 2.0, cx2 = (b[0] + b[2]) / 2.0, cy2 = (b[1] + b[3]) / 2.0;
@@ -206,76 +121,17 @@ __device__ inline double diou_xyxy(const double* a, const double* b) {
   return (iou - inner / outer + 1.0) / 2.0;
 }
 
-// Linear assignment (lap_solve, lap_small and the wave reductions they use): lap.h, shared with evaluate.hip.
-
-// ------------------------------------------------------------------------------------------
-// one OCSort.update() for one clip, executed by one wavefront
-// ------------------------------------------------------------------------------------------
-struct StepShared {
-  double det[MAXD][6];
-  double tbox[MAXT][4];
-  double tq[MAXT][5];  // per tracker: previous-observation centre (x, y), its validity, velocity direction (x, y)
-  double iou[MAXD][MAXT];
-  double cost[MAXD][MAXT];
-  int d2t[MAXD];      // detection -> tracker position paired by the first association (or -1)
-  int rej[MAXD];      // that pair was rejected (IoU below threshold)
-  int taken[MAXD];    // detection consumed by a tracker (first or second association)
-  int r2c[MAXT];      // assignment scratch
-  int um_d[MAXD];     // unmatched detections, in the reference's list order
-  int um_t[MAXT];
-  int n_um_d, n_um_t, flag;
-  LapShared lap;
-};
+// the box of a row: the last observation, or the filter's box while there is none
+__device__ inline void ocsort_row_box(const Trk& k, double bx[4]) {
+  if (obs_sum_negative(k)) x_to_bbox(k.x, bx);
+  else { bx[0] = k.last_obs[0]; bx[1] = k.last_obs[1]; bx[2] = k.last_obs[2]; bx[3] = k.last_obs[3]; }
+}
 
 __device__ void ocsort_step(ClipState& st, Row* rows, int rows_cap, StepShared& sh, int nd, double time, const TrackParams& p,
                             double q44, double q66, int lane) {
   TRK_T0();
   if (lane == 0) st.frame_count += 1;
-  int T = st.ntrk;
-  // ---- predict (KalmanBoxTracker.predict) ----
-  bool isnan_box = false;
-  if (lane < T) {
-    Trk& k = st.trk[st.order[lane]];
-    KfCore c;
-    core_load(c, k);
-    if ((c.x[6] + c.x[2]) <= 0.0) c.x[6] *= 0.0;
-    kf_predict(c, q44, q66);
-    core_store(k, c);
-    k.age += 1;
-    if (k.time_since_update > 0) k.hit_streak = 0;
-    k.time_since_update += 1;
-    double bx[4];
-    x_to_bbox(c.x, bx);
-    isnan_box = (bx[0] != bx[0]) || (bx[1] != bx[1]) || (bx[2] != bx[2]) || (bx[3] != bx[3]);
-#pragma unroll
-    for (int i = 0; i < 4; i++) sh.tbox[lane][i] = bx[i];
-  }
-  unsigned long long nanmask = __ballot(isnan_box);
-  if (nanmask) {  // drop trackers whose predicted box is NaN (stable compaction)
-    unsigned long long keep = ~nanmask & (T >= 64 ? ~0ull : ((1ull << T) - 1ull));
-    int slot = lane < T ? st.order[lane] : 0;
-    double bx[4] = {0, 0, 0, 0};
-    if (lane < T)
-      for (int i = 0; i < 4; i++) bx[i] = sh.tbox[lane][i];
-    __syncthreads();
-    {  // slots of the dropped trackers go back to the pool: one lane clears their bits (no atomics: the state may sit in LDS)
-      unsigned long long nm = nanmask, clr = 0ull;
-      while (nm) {
-        const int l = __ffsll((long long)nm) - 1;
-        nm &= nm - 1;
-        clr |= 1ull << __shfl(slot, l);
-      }
-      if (lane == 0) st.used &= ~clr;
-    }
-    if (lane < T && !isnan_box) {
-      int np_ = __popcll(keep & ((1ull << lane) - 1ull));
-      st.order[np_] = slot;
-      for (int i = 0; i < 4; i++) sh.tbox[np_][i] = bx[i];
-    }
-    T = __popcll(keep);
-    if (lane == 0) st.ntrk = T;
-  }
-  __syncthreads();
+  const int T = predict_and_drop_nan<false>(st, sh, q44, q66, lane);
   const int slot = lane < T ? st.order[lane] : 0;
   TRK_MARK(0);   // predict
   // ---- first association: IoU + velocity-direction consistency ----
@@ -298,6 +154,7 @@ __device__ void ocsort_step(ClipState& st, Row* rows, int rows_cap, StepShared& 
     sh.tq[lane][3] = k.has_vel ? k.vel[1] : 0.0;   // vx
     sh.tq[lane][4] = k.has_vel ? k.vel[0] : 0.0;   // vy
   }
+  if (lane < MAXD) { sh.d2t[lane] = -1; sh.rej[lane] = 0; sh.taken[lane] = 0; }   // this frame's pairing arrays (their last readers: behind the previous step's barrier)
   __syncthreads();
   {
     const double PI = 3.141592653589793;
@@ -322,36 +179,7 @@ __device__ void ocsort_step(ClipState& st, Row* rows, int rows_cap, StepShared& 
     }
   }
   __syncthreads();
-  int colsum = 0;
-  if (lane < T)
-    for (int d = 0; d < nd; d++) colsum += sh.iou[d][lane] > p.iou_thr ? 1 : 0;
-  TRK_MARK(1);   // cost matrix
-  if (lane < MAXD) { sh.d2t[lane] = -1; sh.rej[lane] = 0; sh.taken[lane] = 0; }
-  __syncthreads();
-  const int maxcol = wave_max_i32(colsum);
-  int maxrow = 0;
-  for (int d = 0; d < nd; d++) {
-    unsigned long long m = __ballot(lane < T && sh.iou[d][lane] > p.iou_thr);
-    maxrow = max(maxrow, __popcll(m));
-  }
-  int my_det = -1;  // detection matched to this lane's tracker
-  if (nd > 0 && T > 0) {
-    if (maxrow == 1 && maxcol == 1) {
-      if (lane < T)
-        for (int d = 0; d < nd; d++)
-          if (sh.iou[d][lane] > p.iou_thr) my_det = d;
-    } else {
-      if (nd <= T) {
-        lap_solve(&sh.cost[0][0], MAXT, false, nd, T, sh.r2c, sh.lap, lane);
-        if (lane < T)
-          for (int d = 0; d < nd; d++)
-            if (sh.r2c[d] == lane) my_det = d;
-      } else {
-        lap_solve(&sh.cost[0][0], MAXT, true, T, nd, sh.r2c, sh.lap, lane);
-        if (lane < T) my_det = sh.r2c[lane];
-      }
-    }
-  }
+  int my_det = gate_and_assign(sh, nd, T, p.iou_thr, lane, _tp);   // detection matched to this lane's tracker
   TRK_MARK(2);   // assignment
   // d2t[d]: tracker position the solver paired with detection d (-1 none); rej[d]: pair rejected (IoU < thr)
   const bool was_paired = lane < T && my_det >= 0;   // the solver paired this lane's tracker with a detection (accepted or not)
@@ -438,195 +266,13 @@ __device__ void ocsort_step(ClipState& st, Row* rows, int rows_cap, StepShared& 
   // ---- unmatched trackers: update(None) ----
   if (lane < nut && sh.um_t[lane] >= 0) trk_update(st.trk[st.order[sh.um_t[lane]]], nullptr, q44, q66, p.delta_t);
   __syncthreads();
-  // ---- births ----
-  nud = sh.n_um_d;
-  if (lane == 0) {
-    for (int i = 0; i < nud; i++) {
-      if (st.ntrk >= MAXT) { st.overflow += 1; continue; }
-      int s = __ffsll((long long)~st.used) - 1;
-      st.used |= 1ull << s;
-      Trk& k = st.trk[s];
-      const double* dt = sh.det[sh.um_d[i]];
-      double z[4];
-      bbox_to_z(dt, z);
-      for (int j = 0; j < 7; j++) k.x[j] = j < 4 ? z[j] : 0.0;
-      for (int b = 0; b < 3; b++) { k.B[b][0] = 10.0; k.B[b][1] = 0.0; k.B[b][2] = 0.0; k.B[b][3] = 10000.0; }
-      k.Pr = 10.0;
-      k.has_saved = 0; k.observed = 0; k.gap = 0; k.has_obs = 0; k.has_vel = 0;
-      for (int j = 0; j < 5; j++) k.last_obs[j] = -1.0;
-      for (int j = 0; j < 4; j++) { k.obs_age[j] = -1; k.last_z[j] = 0.0; }
-      k.vel[0] = k.vel[1] = 0.0;
-      k.time_since_update = 0; k.hits = 0; k.hit_streak = 0; k.age = 0; k.nrows = 0;
-      k.cum = 0.0; k.cum_c = 0.0; k.prev_x = 0.0; k.prev_y = 0.0;
-      k.conf = dt[4]; k.cls = dt[5];
-      k.id = st.next_id++;
-      st.order[st.ntrk++] = s;
-    }
-  }
-  __syncthreads();
+  births<bbox_to_z>(st, sh, lane);
   TRK_MARK(5);   // update(None) + births
-  // ---- emission (reverse list order) + deletion ----
-  T = st.ntrk;
-  bool emit = false, keep = true;
-  int myslot = 0;
-  if (lane < T) {
-    myslot = st.order[lane];
-    const Trk& k = st.trk[myslot];
-    emit = k.time_since_update < 1 && (k.hit_streak >= p.min_hits || st.frame_count <= p.min_hits);
-    keep = !(k.time_since_update > p.max_age);
-  }
-  unsigned long long em = __ballot(emit);
-  const int nem = __popcll(em);
-  const int base = st.nrows;
-  if (emit) {
-    Trk& k = st.trk[myslot];
-    int ridx = lane >= 63 ? 0 : __popcll(em >> (lane + 1));  // rows of later trackers come first
-    double bx[4];
-    if (obs_sum_negative(k)) x_to_bbox(k.x, bx);
-    else { bx[0] = k.last_obs[0]; bx[1] = k.last_obs[1]; bx[2] = k.last_obs[2]; bx[3] = k.last_obs[3]; }
-    double xc = (bx[0] + bx[2]) / 2.0, yc = (bx[1] + bx[3]) / 2.0;
-    if (ridx < MAXD) {
-      double* lo = st.last_out[ridx];
-      lo[0] = bx[0]; lo[1] = bx[1]; lo[2] = bx[2]; lo[3] = bx[3];
-      lo[4] = (double)(k.id + 1); lo[5] = k.cls; lo[6] = k.conf; lo[7] = k.x[4]; lo[8] = k.x[5];
-    }
-    if (base + ridx < rows_cap) {
-      Row r;
-      r.id = k.id + 1; r.time = time; r.x = xc; r.y = yc; r.dx = k.x[4]; r.dy = k.x[5];
-      r.h = fabs(bx[3] - bx[1]); r.w = fabs(bx[2] - bx[0]);
-      rows[base + ridx] = r;
-    }
-    // running path length of this id (reference track.py:109-113: sqrt(dx^2+dy^2), cumulative per id)
-    if (k.nrows > 0) {
-      double ex = xc - k.prev_x, ey = yc - k.prev_y;
-      double dist = sqrt(ex * ex + ey * ey);
-      double yk = dist - k.cum_c;
-      double tk = k.cum + yk;
-      k.cum_c = (tk - k.cum) - yk;
-      k.cum = tk;
-    }
-    k.prev_x = xc; k.prev_y = yc; k.nrows += 1;
-  }
-  if (lane == 0) {
-    st.last_n = min(nem, MAXD);
-    if (base + nem > rows_cap) { st.rows_overflow += base + nem - rows_cap; st.nrows = rows_cap; }
-    else st.nrows = base + nem;
-  }
-  unsigned long long km = __ballot(lane < T && keep);
-  if (km != (T >= 64 ? ~0ull : ((1ull << T) - 1ull))) {
-    __syncthreads();
-    if (lane < T && keep) st.order[__popcll(km & ((1ull << lane) - 1ull))] = myslot;
-    {
-      unsigned long long dm = ~km & (T >= 64 ? ~0ull : ((1ull << T) - 1ull)), clr = 0ull;
-      while (dm) {
-        const int l = __ffsll((long long)dm) - 1;
-        dm &= dm - 1;
-        clr |= 1ull << __shfl(myslot, l);
-      }
-      if (lane == 0) st.used &= ~clr;
-    }
-    // a finished track competes for the export id (max cumulative distance; ties -> lower id);
-    // the few deaths of a frame are serialised
-    unsigned long long dead = ~km & (T >= 64 ? ~0ull : ((1ull << T) - 1ull));
-    while (dead) {
-      int l = __ffsll((long long)dead) - 1;
-      dead &= dead - 1;
-      if (lane == l) {
-        const Trk& k = st.trk[myslot];
-        if (k.nrows >= 2 && (k.cum > st.best_cum || (k.cum == st.best_cum && k.id + 1 < st.best_id))) { st.best_cum = k.cum; st.best_id = k.id + 1; }
-      }
-      __syncthreads();
-    }
-    if (lane == 0) st.ntrk = __popcll(km);
-  }
-  __syncthreads();
+  emit_and_delete<ocsort_row_box>(st, rows, rows_cap, time, p, lane);
   TRK_MARK(6);   // emission + deletion
 #ifdef VBT_TRK_PROF
   if (threadIdx.x == 0) { atomicAdd(&g_trk_prof[8], 1ull); atomicAdd(&g_trk_prof[9], (unsigned long long)nd); atomicAdd(&g_trk_prof[10], (unsigned long long)st.ntrk); }
 #endif
-}
-
-// One detector slot -> the tracker's detection list, lane i = detection i (the slot's 25 scores / boxes arrive in one
-// round trip instead of 25 dependent ones by lane 0): threshold of reference odt.py:70-75 (score >= det_threshold), the
-// reorder of odt.py:102-118 and OC-SORT's own gate (score > det_thresh), order kept.  Returns the number of detections
-// handed to the tracker, or -1 when run_odt would have returned [] (the frame is skipped, track.py:180-181).  Uniform.
-// The slot's count, this lane's score and this lane's box are requested TOGETHER (the count used to gate the score load and the score
-// the box load: three dependent round trips at the head of every frame of a walk), and a walk requests frame f + 1's while it steps
-// through frame f.
-struct RawDet {
-  int n;
-  float s;
-  float4 b;   // ymin,xmin,ymax,xmax
-};
-__device__ __forceinline__ RawDet fetch_slot_detections(const float* boxes, const float* scores, const int* counts, int slot, int lane) {
-  const int l = min(lane, MAXD - 1);   // lanes past the 25 entries re-read the last one (never used)
-  RawDet d;
-  d.n = counts[slot];
-  d.s = scores[slot * MAXD + l];
-  d.b = *(const float4*)(boxes + ((size_t)slot * MAXD + l) * 4);
-  return d;
-}
-__device__ __forceinline__ int put_slot_detections(StepShared& sh, const RawDet& d, float det_threshold, double det_thresh, int lane) {
-  const int n = min(d.n, MAXD);
-  const float s = lane < n ? d.s : 0.0f;
-  const bool kept = lane < n && s >= det_threshold;
-  const bool used = kept && (double)s > det_thresh;
-  const unsigned long long mk = __ballot(kept), mu = __ballot(used);
-  if (used) {
-    const int m = __popcll(mu & ((1ull << lane) - 1ull));
-    sh.det[m][0] = (double)d.b.y; sh.det[m][1] = (double)d.b.x; sh.det[m][2] = (double)d.b.w; sh.det[m][3] = (double)d.b.z;
-    sh.det[m][4] = (double)s; sh.det[m][5] = 0.0;
-  }
-  return mk ? __popcll(mu) : -1;
-}
-__device__ inline int load_slot_detections(StepShared& sh, const float* boxes, const float* scores, const int* counts, int slot,
-                                           float det_threshold, double det_thresh, int lane) {
-  return put_slot_detections(sh, fetch_slot_detections(boxes, scores, counts, slot, lane), det_threshold, det_thresh, lane);
-}
-
-__device__ inline void copy_words(void* dst, const void* src, int bytes, int lane) {   // 8-byte words, one wavefront
-  unsigned long long* d = (unsigned long long*)dst;
-  const unsigned long long* s_ = (const unsigned long long*)src;
-  for (int i = lane; i < bytes / 8; i += 64) d[i] = s_[i];
-}
-static_assert(sizeof(Trk) % 8 == 0 && offsetof(ClipState, trk) % 8 == 0, "8-byte copy granularity");
-// The clip state between global memory and its LDS copy, by one wavefront: the header, then the LIVE tracks only.  All loads of a pass
-// are in flight together (the header in one round trip, the tracks four words per lane at a time): the per-track loop it replaces
-// waited for every 512 bytes - 5.8 us for ten tracks - which only a long run could amortise.  slots = 64 ints of LDS scratch.
-template <bool TO_LDS>
-__device__ inline void clip_state_copy(ClipState* lst, ClipState* gst, int* slots, int lane) {
-  constexpr int HW = (int)(offsetof(ClipState, trk) / 8), HI = (HW + 63) / 64, TW = (int)(sizeof(Trk) / 8);
-  unsigned long long* l = (unsigned long long*)lst;
-  unsigned long long* g = (unsigned long long*)gst;
-  {
-    unsigned long long hv[HI];
-#pragma unroll
-    for (int k = 0; k < HI; k++) { const int i = min(lane + 64 * k, HW - 1); hv[k] = TO_LDS ? g[i] : l[i]; }
-#pragma unroll
-    for (int k = 0; k < HI; k++) { const int i = lane + 64 * k; if (i < HW) (TO_LDS ? l : g)[i] = hv[k]; }
-  }
-  __syncthreads();
-  const unsigned long long used = lst->used;
-  if ((used >> lane) & 1ull) slots[__popcll(used & ((1ull << lane) - 1ull))] = lane;
-  __syncthreads();
-  const int total = __popcll(used) * TW;
-  unsigned long long* lt = (unsigned long long*)&lst->trk[0];
-  unsigned long long* gt = (unsigned long long*)&gst->trk[0];
-  for (int base = 0; base < total; base += 256) {
-    unsigned long long v[4];
-    int off[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int i = min(base + lane + 64 * k, total - 1);
-      const int ord = i / TW, w = i - ord * TW;
-      off[k] = slots[ord] * TW + w;
-      v[k] = TO_LDS ? gt[off[k]] : lt[off[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (base + lane + 64 * k < total) (TO_LDS ? lt : gt)[off[k]] = v[k];
-  }
-  __syncthreads();
 }
 
 }  // namespace vbt

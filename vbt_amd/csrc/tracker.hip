@@ -1,7 +1,9 @@
-// On-device OC-SORT tracker and row assembly for gfx950 (MI355X): the step kernels, the handle, the per-clip read-backs.  The step itself
-// is ocsort_step.h; export id selection + rep analysis at the clip close are tracker_analysis.hip, the live rep analysis tracker_live.hip.
-// A handle made by vbt_tracker_create_sort steps sort_step.h instead - SortTracker, the reference's commented-out alternative
-// (track.py:16,156) - on the same state, row log and kernels (templates on the algorithm); everything else in this file is shared.
+// The on-device trackers and row assembly for gfx950 (MI355X): the step kernels, the handle, the per-clip read-backs.  One step is
+// ocsort_step.h (OC-SORT, the default) or - a handle made by vbt_tracker_create_sort - sort_step.h (SortTracker, the reference's
+// commented-out alternative, track.py:16,156): each is its own association around the phases of step_phases.h, on the filter of
+// box_filter.h and the state of tracker_state.h, and the kernels here are templates on the algorithm.  The detection list loaders and the
+// state's LDS copy are clip_io.h; export id selection + rep analysis at the clip close are tracker_analysis.hip, the live rep analysis
+// tracker_live.hip.
 //
 // Replaces, per clip (reference track.py:157-234, plot.py:33-47,87-95):
 //   ocsort.OCSort(max_age=30, asso_func="diou", iou_threshold=0.1).update(dets, [])   track.py:157,186
@@ -25,14 +27,17 @@
 
 namespace vbt {
 
-// Phase timers of the OC-SORT step (developer builds only: VBT_EXTRA_CXXFLAGS=-DVBT_TRK_PROF): s_memtime deltas per phase,
-// accumulated by lane 0 of every wavefront; read back with vbt_tracker_prof_read.
+// Phase timers of a tracker step (developer builds only: VBT_EXTRA_CXXFLAGS=-DVBT_TRK_PROF): s_memtime deltas per phase, accumulated
+// by lane 0 of every wavefront; read back with vbt_tracker_prof_read.  TrkClock is the step's clock, handed to a shared phase that
+// marks inside its body; it is empty in every other build.
 #ifdef VBT_TRK_PROF
 __device__ unsigned long long g_trk_prof[16];
-#define TRK_T0() unsigned long long _tp = __builtin_amdgcn_s_memtime()
-#define TRK_MARK(i) do { unsigned long long _tn = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0) atomicAdd(&g_trk_prof[i], _tn - _tp); _tp = _tn; } while (0)
+struct TrkClock { unsigned long long t; };
+#define TRK_T0() TrkClock _tp{__builtin_amdgcn_s_memtime()}
+#define TRK_MARK(i) do { unsigned long long _tn = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0) atomicAdd(&g_trk_prof[i], _tn - _tp.t); _tp.t = _tn; } while (0)
 #else
-#define TRK_T0() do {} while (0)
+struct TrkClock {};
+#define TRK_T0() TrkClock _tp
 #define TRK_MARK(i) do {} while (0)
 #endif
 
@@ -41,19 +46,11 @@ static_assert(CLOSED_HEAD_BYTES == 16 + (size_t)MAXPH * 48, "slot close record (
 
 }  // namespace vbt
 
+#include "clip_io.h"
 #include "ocsort_step.h"
 #include "sort_step.h"
 
 namespace vbt {
-
-// Host-provided detections (rows of x1,y1,x2,y2,score,cls) -> the tracker's detection list, by ONE lane: dets = dets[confs > det_thresh],
-// order kept.  Returns the number kept (0: the step still runs, on no detections).
-__device__ __forceinline__ int put_host_detections(StepShared& sh, const double (*d)[6], int n, double det_thresh) {
-  int m = 0;
-  for (int i = 0; i < n && i < MAXD; i++)
-    if (d[i][4] > det_thresh) { for (int j = 0; j < 6; j++) sh.det[m][j] = d[i][j]; m++; }
-  return m;
-}
 
 // The step kernels below exist once per algorithm, selected at compile time: SORT = false walks ocsort_step (OCSort, track.py:157),
 // SORT = true sort_step (SortTracker, track.py:16,156).  The handle's `sort` flag picks the instantiation at every launch.

@@ -10,7 +10,7 @@
 struct vbt_tracker {
   int n_clips = 0, rows_cap = 0, device = 0;
   vbt::TrackParams p;
-  bool sort = false;                     // the step is sort_step (vbt_tracker_create_sort), not ocsort_step
+  bool sort = false;                     // the step is sort_step.h's (vbt_tracker_create_sort), not ocsort_step.h's
   int id_base = 0;                       // row ids of a fresh clip start at id_base + 1 (SORT only; 0 for OC-SORT)
   double q44 = 0, q66 = 0;
   vbt::DevBuf<vbt::ClipState> states;

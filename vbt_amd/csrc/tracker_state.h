@@ -1,6 +1,6 @@
-// The OC-SORT tracker's per-clip state as it sits in device memory, and the small pieces every unit of the tracker shares: the clip
-// list of a launch, a fresh state, the export rule.  Plain structs and device code (tracker.hip holds the step kernels,
-// tracker_analysis.hip the clip close, tracker_live.hip the live rep analysis; the host handle is tracker_host.h).
+// A tracked clip's state as it sits in device memory - one layout under both trackers, OC-SORT and SORT - and the small pieces every
+// unit of the tracker shares: the clip list of a launch, a fresh state, the export rule.  Plain structs and device code (tracker.hip
+// holds the step kernels, tracker_analysis.hip the clip close, tracker_live.hip the live rep analysis; the host handle is tracker_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,6 +73,11 @@ __device__ inline int export_id(const ClipState& st) {
     if (k.nrows >= 2 && (k.cum > bc || (k.cum == bc && (bi < 0 || k.id + 1 < bi)))) { bc = k.cum; bi = k.id + 1; }
   }
   return bi;
+}
+// The same rule at the moment a track leaves the list (step_phases.h: retire): a finished track with at least 2 rows enters the dead
+// ids' summary best_cum / best_id.  By ONE lane at a time: the deaths of a frame are serialised.
+__device__ inline void finished_track_competes(ClipState& st, const Trk& k) {
+  if (k.nrows >= 2 && (k.cum > st.best_cum || (k.cum == st.best_cum && k.id + 1 < st.best_id))) { st.best_cum = k.cum; st.best_id = k.id + 1; }
 }
 
 }  // namespace vbt
